@@ -7,9 +7,11 @@ by PCG to sqrt((B r_k,r_k)/(B r_0,r_0)) < 1e-8.  value = DoF/s = N * steps / tim
 Default workload = the configuration BASELINE.json quotes the metric on: 3-D Poisson 256^3,
 3-level SAAMGE (it fits one MI355X).
 
-    python bench.py --gpus 1 --steps K --warmup W [--n 256] [--levels 3]
+    python bench.py --gpus 1 --steps K --warmup W [--n 256] [--levels 3] [--dump-outputs DIR] [--full]
 
-Prints ONE JSON line (rank 0).  Extra legs, outside the timed region:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the line; with
+--dump-outputs DIR it first writes what the last timed step computed (dump_outputs below).  --full adds the
+true residual of the computed solution and the extra legs, all outside the timed region:
   * roofline: one more step with the library's HIP-event pair around every kernel launch
     (events recorded on the launch stream); reported for the kernel with the largest total
     time (the SpMV family is listed per operator, i.e. per level).  `achieved` / `frac` price the
@@ -229,6 +231,44 @@ def side_workload(capi, name, dev, coarse_solver=None, steps=2):
     return out
 
 
+DUMP_SAMPLE = 1 << 20      # entries of a dumped vector beyond which a fixed sample of this many is written
+
+
+def dump_outputs(out_dir, h, x, hist, its, infos):
+    """--dump-outputs: what the last timed step handed its caller, as float64 .npy files in out_dir -- the PCG solution
+    (x; longer than DUMP_SAMPLE: the entries at fixed positions, seed 0, ascending, listed in x_index), its (B r, r)
+    history and iteration count, the level dimensions and the coarsest Galerkin operator of the hierarchy as (row, col)-
+    sorted triplets (coarse_operator_rows / _cols / _vals, sampled the same way).  At most 5 * DUMP_SAMPLE * 8 bytes."""
+    import numpy as np
+    import torch
+
+    def sample(n):
+        if n <= DUMP_SAMPLE:
+            return None
+        return np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+
+    os.makedirs(out_dir, exist_ok=True)
+    out = {}
+    idx = sample(x.numel())
+    if idx is None:
+        out["x"] = x.cpu().numpy()
+    else:
+        out["x"] = x[torch.from_numpy(idx).to(x.device)].cpu().numpy()
+        out["x_index"] = idx
+    out["pcg_residual_history"] = np.asarray(hist)
+    out["pcg_iterations"] = np.array([its])
+    out["level_dims"] = np.array([i["n"] for i in infos] + [infos[-1]["ncoarse"]])
+    Ac = h.get_csr(len(infos) - 1, "Ac").tocoo()
+    order = np.lexsort((Ac.col, Ac.row))
+    rows, cols, vals = Ac.row[order], Ac.col[order], Ac.data[order]
+    idx = sample(vals.size)
+    if idx is not None:
+        rows, cols, vals = rows[idx], cols[idx], vals[idx]
+    out.update(coarse_operator_rows=rows, coarse_operator_cols=cols, coarse_operator_vals=vals)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def spawn_ranks(n, argv, script=None):
     """`python bench.py --gpus N` without a launcher: N child processes, one per GPU, started before
     this process imports torch or touches the GPU (a process that initialised the GPU must never be
@@ -298,6 +338,11 @@ def main():
     ap.add_argument("--nu-pro", type=int, default=0, help="prolongator smoothing degree (0 = tentative, the reference default)")
     ap.add_argument("--eigensolver", default="subspace", choices=["subspace", "dense"],
                     help="local eigensolver: few-eigenpairs path with certified count (default) or the dense two-stage path only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the true residual of the solution and the extra legs (roofline, general coefficient, "
+                         "configs 2 / 4, cpu_baseline; --no-* below skip single legs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-general", action="store_true", help="skip the general-coefficient leg of the default workload")
@@ -308,6 +353,8 @@ def main():
     ap.add_argument("--coef", default=None, choices=["skew"], help="Poisson workloads: variable coefficient instead of the constant one "
                     "(the timed workload itself becomes the general-coefficient problem; used to profile it)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     for k, v in WORKLOADS[args.workload].items():
         if getattr(args, k) is None:
             setattr(args, k, v)
@@ -383,22 +430,26 @@ def main():
     torch.cuda.synchronize()
     dt = grp.max_time(time.perf_counter() - t0)
     infos = [h.level_info(l) for l in range(args.levels - 1 + int(args.correct_nullspace))]
-    # size-independent check on the full-size problem: true residual of the computed solution
-    # (torch's CSR product, by row blocks of at most 2^28 entries: its int64 copy of the column indices
-    # of a 4e9-entry operator would not fit beside the hierarchy)
-    A_rowptr, A_col, A_val = prob.rowptr.long(), prob.col, prob.val
-    res2 = 0.0
-    r0 = 0
-    while r0 < prob.n:
-        e0 = int(A_rowptr[r0])
-        r1 = int(torch.searchsorted(A_rowptr, torch.tensor(e0 + (1 << 28), device=A_rowptr.device)))
-        r1 = min(prob.n, max(r1 - 1, r0 + 1))
-        e1 = int(A_rowptr[r1])
-        Ablk = torch.sparse_csr_tensor(A_rowptr[r0:r1 + 1] - e0, A_col[e0:e1].long(), A_val[e0:e1], size=(r1 - r0, prob.n))
-        res2 += float(torch.sum((Ablk @ x - prob.b[r0:r1]) ** 2))
-        del Ablk
-        r0 = r1
-    relres = float(res2 ** 0.5 / torch.linalg.norm(prob.b))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, h, x, hist, its, infos)
+    relres = None
+    if args.full:
+        # size-independent check on the full-size problem: true residual of the computed solution
+        # (torch's CSR product, by row blocks of at most 2^28 entries: its int64 copy of the column indices
+        # of a 4e9-entry operator would not fit beside the hierarchy)
+        A_rowptr, A_col, A_val = prob.rowptr.long(), prob.col, prob.val
+        res2 = 0.0
+        r0 = 0
+        while r0 < prob.n:
+            e0 = int(A_rowptr[r0])
+            r1 = int(torch.searchsorted(A_rowptr, torch.tensor(e0 + (1 << 28), device=A_rowptr.device)))
+            r1 = min(prob.n, max(r1 - 1, r0 + 1))
+            e1 = int(A_rowptr[r1])
+            Ablk = torch.sparse_csr_tensor(A_rowptr[r0:r1 + 1] - e0, A_col[e0:e1].long(), A_val[e0:e1], size=(r1 - r0, prob.n))
+            res2 += float(torch.sum((Ablk @ x - prob.b[r0:r1]) ** 2))
+            del Ablk
+            r0 = r1
+        relres = float(res2 ** 0.5 / torch.linalg.norm(prob.b))
     op_formats = [dict(h.level_format(l)["slices"], dictionary_pairs=h.level_format(l)["dictionary_pairs"]) for l in range(args.levels - 1)]
     eig_solved = [[h.level_format(l)["eigenproblems_solved"], infos[l]["nparts"]] for l in range(args.levels - 1)]
     h.close()
@@ -445,7 +496,7 @@ def main():
                    if world > 1 else "single GPU"},
     }
 
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         capi.profile(True)
         capi.profile_reset()
         h, x, its2, conv2, hist2 = one_step(capi, prob, params)      # (single rank: no group)
@@ -494,7 +545,7 @@ def main():
                            "format_GBps": round(s["fmt_bytes"] / max(s["ms"], 1e-9) / 1e6, 1),
                            "csr_model_GBps": round(s["bytes"] / max(s["ms"], 1e-9) / 1e6, 1)}
                           for s in stats[:10]]
-    if rank == 0 and world == 1 and not args.no_general and args.workload == "poisson256" and args.aniso == 1.0 and args.coef is None:
+    if args.full and rank == 0 and world == 1 and not args.no_general and args.workload == "poisson256" and args.aniso == 1.0 and args.coef is None:
         # the same workload on a GENERAL operator (outside the timed region): a coefficient without any symmetry, so that
         # no 64-row slice repeats its (offset, value) pairs -- the pair-coded format of the constant-coefficient headline
         # does not apply and the smoother streams the values
@@ -524,7 +575,7 @@ def main():
         hg.close()
         del gprob, xg
         torch.cuda.empty_cache()
-    if (rank == 0 and world == 1 and not args.no_others and args.workload == "poisson256" and args.n == 256 and args.aniso == 1.0
+    if (args.full and rank == 0 and world == 1 and not args.no_others and args.workload == "poisson256" and args.n == 256 and args.aniso == 1.0
             and args.coef is None and args.nu_pro == 0 and not args.correct_nullspace):
         # BASELINE configs 2 and 4 in the driver's line (outside the timed region; config 5 fills the card and takes ~10 s per
         # step: it stays a separate run, `--workload elasticity_q2`, profiles/r04_bench_elasticity_q2.json)
@@ -541,9 +592,9 @@ def main():
             "aniso128": dict(side_workload(capi, "aniso128", dev), config="BASELINE config 4: K=diag(1,1,1000) 128^3, theta=1e-4 / 1e-5, "
                              "3-level, 4x4x2-AE coarse blocks"),
             "elasticity_q2": "not run here (BASELINE config 5 fills the card, ~10 s per step): python bench.py --workload elasticity_q2"}
-    if rank == 0 and not args.no_cpu_baseline and args.workload != "poisson256":
+    if args.full and rank == 0 and not args.no_cpu_baseline and args.workload != "poisson256":
         log("bench.py: cpu_baseline is timed on the default workload only (poisson256)")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "poisson256" and args.blk == "8,8,4" and args.coef is None:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "poisson256" and args.blk == "8,8,4" and args.coef is None:
         sample = (96, 96, 64)       # ~15 s on the GPU box's 16 cores
         cpu_raw, res["cpu_baseline"] = cpu_baseline(sample, args.levels)
         if args.aniso == 1.0 and args.nu_pro == 0 and not args.correct_nullspace and args.blk == "8,8,4":

@@ -55,14 +55,14 @@ if has timing; then
   echo "timing done"
 fi
 if has bench; then
-  python3 bench.py > $O/bench_poisson256.json 2> $O/bench_poisson256.err
+  python3 bench.py --full > $O/bench_poisson256.json 2> $O/bench_poisson256.err
   echo "default bench done rc=$?"
 fi
 if has workloads; then
-  python3 bench.py --workload poisson128 --no-cpu-baseline --warmup 1 --steps 5 > $O/bench_poisson128.json 2> $O/bench_poisson128.err
-  python3 bench.py --workload aniso128 --no-cpu-baseline --warmup 1 --steps 5 > $O/bench_aniso128.json 2> $O/bench_aniso128.err
+  python3 bench.py --full --workload poisson128 --no-cpu-baseline --warmup 1 --steps 5 > $O/bench_poisson128.json 2> $O/bench_poisson128.err
+  python3 bench.py --full --workload aniso128 --no-cpu-baseline --warmup 1 --steps 5 > $O/bench_aniso128.json 2> $O/bench_aniso128.err
   echo "128 workloads done"
-  python3 bench.py --workload elasticity_q2 --no-cpu-baseline --warmup 1 --steps 3 > $O/bench_elasticity_q2.json 2> $O/bench_elasticity_q2.err
+  python3 bench.py --full --workload elasticity_q2 --no-cpu-baseline --warmup 1 --steps 3 > $O/bench_elasticity_q2.json 2> $O/bench_elasticity_q2.err
   echo "elasticity done rc=$?"
   cd /tmp
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_aniso -o an -- python3 $R/bench.py --workload aniso128 --no-cpu-baseline --no-roofline --warmup 1 --steps 2 > /dev/null 2> $O/stats_aniso.err
