@@ -205,6 +205,27 @@ int saamge_amd_ml_produce_data64(int n, const long long *rowptr, const int *col,
                                  const signed char *bdr_dofs, const int *const *partitions,
                                  const int *nparts, const saamge_amd_params *params, void *stream,
                                  saamge_amd_hierarchy **out);
+/* The same for a mesh whose elements have different numbers of dofs (hexes with prisms, tetrahedra or pyramids; a
+ * variable-order space) -- the reference's elem_to_dof Table and ElementMatrixProvider::GetMatrix(e) of any size:
+ *   elem_ptr     NE + 1 offsets, elem_ptr[0] = 0, at least one dof per element: element e has
+ *                nd_e = elem_ptr[e+1] - elem_ptr[e] dofs
+ *   elem_to_dof  elem_ptr[NE] dof ids, element e's at elem_ptr[e] ...
+ *   elmat        the raw element matrices packed in element order: element e's nd_e x nd_e matrix, row-major, at
+ *                sum_{f<e} nd_f^2 (a 64-bit offset)
+ * Host or device pointers, as above; every other argument as in saamge_amd_ml_produce_data.  Malformed offsets
+ * (elem_ptr[0] != 0, an empty element, decreasing offsets) and dofs out of range are refused (nonzero return,
+ * saamge_amd_last_error) before anything reads through them.  Elements that all have the same size take exactly the
+ * path of saamge_amd_ml_produce_data with that nde (the same hierarchy, bit for bit). */
+int saamge_amd_ml_produce_data_mixed(int n, const int *rowptr, const int *col, const double *val,
+                                     int NE, const int *elem_ptr, const int *elem_to_dof, const double *elmat,
+                                     const signed char *bdr_dofs, const int *const *partitions,
+                                     const int *nparts, const saamge_amd_params *params, void *stream,
+                                     saamge_amd_hierarchy **out);
+int saamge_amd_ml_produce_data_mixed64(int n, const long long *rowptr, const int *col, const double *val,
+                                       int NE, const int *elem_ptr, const int *elem_to_dof, const double *elmat,
+                                       const signed char *bdr_dofs, const int *const *partitions,
+                                       const int *nparts, const saamge_amd_params *params, void *stream,
+                                       saamge_amd_hierarchy **out);
 /* ml_produce_data from PER-RANK inputs (one process per GPU; params->rank / world and the collectives set): what the
  * reference's multi-rank drivers pass (pmltest, amg/CMakeLists.txt:198-203; test/mltest/mltest.cpp:619-745):
  *   A            this rank's row block as a HypreParMatrix holds it -- hypre's ParCSR split (hypre_ParCSRMatrix: `diag` =

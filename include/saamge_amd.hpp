@@ -99,6 +99,9 @@ struct ProblemArrays {
     const double *elmat = nullptr;
     const signed char *bdr_dofs = nullptr;
     std::vector<const int *> partitions;  // one per coarsening
+    // elements of different sizes (saamge_amd_ml_produce_data_mixed): NE + 1 offsets into a flat elem_to_dof, elmat packed
+    // in element order; nde is then ignored.  nullptr: every element has nde dofs.
+    const int *elem_ptr = nullptr;
 };
 
 typedef saamge_amd_hierarchy ml_data_t;  // inc/ml.hpp:118-120
@@ -111,9 +114,12 @@ inline ml_data_t *ml_produce_data(const ProblemArrays &a, const MultilevelParame
     if ((int)a.partitions.size() < mlp.get_num_coarsenings())
         throw std::invalid_argument("ml_produce_data: one partition array per coarsening is required");
     ml_data_t *h = nullptr;
-    if (saamge_amd_ml_produce_data(a.n, a.rowptr, a.col, a.val, a.NE, a.nde, a.elem_to_dof, a.elmat, a.bdr_dofs,
-                                   a.partitions.data(), mlp.nparts_data(), &mlp.p, stream, &h))
-        throw std::runtime_error(saamge_amd_last_error());
+    const int rc = a.elem_ptr
+        ? saamge_amd_ml_produce_data_mixed(a.n, a.rowptr, a.col, a.val, a.NE, a.elem_ptr, a.elem_to_dof, a.elmat, a.bdr_dofs,
+                                           a.partitions.data(), mlp.nparts_data(), &mlp.p, stream, &h)
+        : saamge_amd_ml_produce_data(a.n, a.rowptr, a.col, a.val, a.NE, a.nde, a.elem_to_dof, a.elmat, a.bdr_dofs,
+                                     a.partitions.data(), mlp.nparts_data(), &mlp.p, stream, &h);
+    if (rc) throw std::runtime_error(saamge_amd_last_error());
     return h;
 }
 // ml_free_data (inc/ml.hpp:196)

@@ -413,15 +413,27 @@ inline ml_data_t *ml_produce_data(mfem::HypreParMatrix &Ag, agg_partitioning_rel
     detail::HostCsr A;
     if (!distributed) A = detail::csr_of(Ag);
     const int n = Ag.Height(), NE = r.NE;
-    // element matrices, raw (row-major nde x nde per element); uniform element size required by the batched assembly
+    // element matrices, raw: element e's nd_e x nd_e matrix row-major at sum_{f<e} nd_f^2 (elements of one size: NE x nde x nde)
     const int nde = r.elem_to_dof->RowSize(0);
-    std::vector<double> elmat((size_t)NE * nde * nde);
+    bool mixed = false;
+    long long elsize = 0;
     for (int e = 0; e < NE; ++e) {
-        if (r.elem_to_dof->RowSize(e) != nde) mfem::mfem_error("ml_produce_data: elements with different numbers of dofs are not supported");
+        const long long nd = r.elem_to_dof->RowSize(e);
+        mixed = mixed || nd != nde;
+        elsize += nd * nd;
+    }
+    if (mixed && distributed)
+        mfem::mfem_error("ml_produce_data: elements with different numbers of dofs are not supported on the per-rank path "
+                         "(saamge_amd_ml_produce_data_parcsr)");
+    std::vector<double> elmat((size_t)elsize);
+    size_t off = 0;
+    for (int e = 0; e < NE; ++e) {
+        const int nd = r.elem_to_dof->RowSize(e);
         bool free_matr = false;
         mfem::Matrix *m = elem_data_finest->GetMatrix(e, free_matr);
-        for (int a = 0; a < nde; ++a)
-            for (int b = 0; b < nde; ++b) elmat[((size_t)e * nde + a) * nde + b] = m->Elem(a, b);
+        for (int a = 0; a < nd; ++a)
+            for (int b = 0; b < nd; ++b) elmat[(size_t)off + (size_t)a * nd + b] = m->Elem(a, b);
+        off += (size_t)nd * nd;
         if (free_matr) delete m;
     }
     // partitions of every coarsening: level 0 from agg_part_rels, coarser ones from the partitioner hook on the
@@ -465,9 +477,13 @@ inline ml_data_t *ml_produce_data(mfem::HypreParMatrix &Ag, agg_partitioning_rel
     if (!distributed) {
         std::vector<signed char> bdr((size_t)n);
         for (int i = 0; i < n; ++i) bdr[(size_t)i] = (signed char)r.agg_flags[i];
-        if (saamge_amd_ml_produce_data(n, A.I.data(), A.J.data(), A.V.data(), NE, nde, r.elem_to_dof->GetJ(), elmat.data(),
-                                       bdr.data(), part_ptrs.data(), nparts.data(), &p, nullptr, &h))
-            mfem::mfem_error(saamge_amd_last_error());
+        const int rc = mixed
+            ? saamge_amd_ml_produce_data_mixed(n, A.I.data(), A.J.data(), A.V.data(), NE, r.elem_to_dof->GetI(),
+                                               r.elem_to_dof->GetJ(), elmat.data(), bdr.data(), part_ptrs.data(), nparts.data(),
+                                               &p, nullptr, &h)
+            : saamge_amd_ml_produce_data(n, A.I.data(), A.J.data(), A.V.data(), NE, nde, r.elem_to_dof->GetJ(), elmat.data(),
+                                         bdr.data(), part_ptrs.data(), nparts.data(), &p, nullptr, &h);
+        if (rc) mfem::mfem_error(saamge_amd_last_error());
     } else {
         // per-rank inputs (saamge_amd_ml_produce_data_parcsr): the rank's row block in hypre's own split, its elements with
         // local dofs mapped to true dofs, the flags of the rows it owns, its own partitions (local agglomerate ids)

@@ -29,6 +29,7 @@ SYMBOLS = [
     "saamge_amd_ml_produce_data64", "saamge_amd_get_csr64", "saamge_amd_spmv64", "saamge_amd_set_smoother", "saamge_amd_profile_get2", "saamge_amd_level_format", "saamge_amd_update_operators2",
     "saamge_amd_ml_produce_data_parcsr", "saamge_amd_memory_stats", "saamge_amd_pool_counts",
     "saamge_amd_options_default", "saamge_amd_set_options", "saamge_amd_get_options",
+    "saamge_amd_ml_produce_data_mixed", "saamge_amd_ml_produce_data_mixed64",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong))
@@ -216,27 +217,40 @@ class Hierarchy(object):
         return params
 
     def __init__(self, A_rowptr, A_col, A_val, n, elem_to_dof, elmat, bdr, partitions, nparts,
-                 params, NE, nde, stream=0, group=None, dist_solve=True):
+                 params, NE, nde, stream=0, group=None, dist_solve=True, elem_ptr=None):
+        """elem_ptr (NE + 1 offsets; nde ignored): elements of different sizes -- flat elem_to_dof and the element
+        matrices packed in element order (saamge_amd_ml_produce_data_mixed)."""
         lib = load()
-        self._keep = (A_rowptr, A_col, A_val, elem_to_dof, elmat, bdr, partitions)
+        self._keep = (A_rowptr, A_col, A_val, elem_to_dof, elmat, bdr, partitions, elem_ptr)
         params = self._prepare_params(params, group, stream, dist_solve)
         parts = (C.c_void_p * len(partitions))(*[_ptr(p).value for p in partitions])
         npa = (C.c_int * len(nparts))(*[int(x) for x in nparts])
         h = C.c_void_p()
         # 64-bit row offsets (torch.int64 / np.int64): operators beyond 2^31 stored entries
         wide = str(getattr(A_rowptr, "dtype", "")).endswith("int64")
-        produce = lib.saamge_amd_ml_produce_data64 if wide else lib.saamge_amd_ml_produce_data
-        _check(produce(
-            C.c_int(n), _ptr(A_rowptr), _ptr(A_col), _ptr(A_val), C.c_int(NE), C.c_int(nde),
-            _ptr(elem_to_dof), _ptr(elmat), _ptr(bdr), parts, npa, C.byref(params),
-            C.c_void_p(stream), C.byref(h)))
+        if elem_ptr is not None:
+            produce = lib.saamge_amd_ml_produce_data_mixed64 if wide else lib.saamge_amd_ml_produce_data_mixed
+            _check(produce(
+                C.c_int(n), _ptr(A_rowptr), _ptr(A_col), _ptr(A_val), C.c_int(NE), _ptr(elem_ptr),
+                _ptr(elem_to_dof), _ptr(elmat), _ptr(bdr), parts, npa, C.byref(params),
+                C.c_void_p(stream), C.byref(h)))
+        else:
+            produce = lib.saamge_amd_ml_produce_data64 if wide else lib.saamge_amd_ml_produce_data
+            _check(produce(
+                C.c_int(n), _ptr(A_rowptr), _ptr(A_col), _ptr(A_val), C.c_int(NE), C.c_int(nde),
+                _ptr(elem_to_dof), _ptr(elmat), _ptr(bdr), parts, npa, C.byref(params),
+                C.c_void_p(stream), C.byref(h)))
         self.h = h
         self.n = n
         self.testmesh = bool(params.testmesh)
 
     @classmethod
     def from_problem(cls, prob, params, stream=0, group=None, dist_solve=True):
-        """Build from a saamge_amd.problems.Problem (host numpy arrays)."""
+        """Build from a saamge_amd.problems.Problem (host numpy arrays).  A problem that carries `elem_ptr` (elements of
+        different sizes: flat elem_to_dof, packed elmat) goes through saamge_amd_ml_produce_data_mixed; its element
+        arrays, bdr and partitions may be host arrays or device tensors."""
+        if getattr(prob, "elem_ptr", None) is not None:
+            return cls._from_mixed_problem(prob, params, stream, group, dist_solve)
         A = prob.A.tocsr()
         rowptr = np.ascontiguousarray(A.indptr, dtype=np.int32)
         col = np.ascontiguousarray(A.indices, dtype=np.int32)
@@ -248,6 +262,23 @@ class Hierarchy(object):
         nparts = [int(p.max()) + 1 for p in parts]
         return cls(rowptr, col, val, A.shape[0], e2d, elmat, bdr, parts, nparts, params,
                    e2d.shape[0], e2d.shape[1], stream, group, dist_solve)
+
+    @classmethod
+    def _from_mixed_problem(cls, prob, params, stream, group, dist_solve):
+        def arr(a, dt):          # device tensors pass through, host arrays are made contiguous
+            return a if hasattr(a, "data_ptr") else np.ascontiguousarray(a, dtype=dt)
+        A = prob.A.tocsr()
+        rowptr = np.ascontiguousarray(A.indptr, dtype=np.int32)
+        col = np.ascontiguousarray(A.indices, dtype=np.int32)
+        val = np.ascontiguousarray(A.data, dtype=np.float64)
+        eptr = arr(prob.elem_ptr, np.int32)
+        e2d = arr(prob.elem_to_dof, np.int32)
+        elmat = arr(prob.elmat, np.float64)
+        bdr = arr(prob.bdr, np.int8) if prob.bdr is not None else None
+        parts = [arr(p, np.int32) for p in prob.partitions[:params.num_coarsenings]]
+        nparts = [int(p.max()) + 1 for p in parts]
+        return cls(rowptr, col, val, A.shape[0], e2d, elmat, bdr, parts, nparts, params, len(eptr) - 1, 0,
+                   stream, group, dist_solve, elem_ptr=eptr)
 
     @classmethod
     def from_parcsr(cls, piece, params, stream=0, group=None, dist_solve=True):

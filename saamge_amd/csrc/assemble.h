@@ -12,6 +12,7 @@ struct DevElmats {
     DBuf<int64_t> off;  // [NE+1]
     DBuf<double> val;
     int nde = 0;        // > 0: every element has exactly nde dofs and e2d_J / val are dense arrays
+    int max_nd = 0;     // level 0 of a mesh with elements of different sizes (nde = 0 there): the largest element; 0 elsewhere
     // per-rank inputs: val holds the matrices of the elements [first, first + count) only; kernels that index the array by
     // the element id itself (no `off`) take dense() -- they touch the rank's own elements only
     int64_t first = 0;
@@ -57,7 +58,7 @@ struct AeClasses {
 void ae_build(hipStream_t s, const DevRelations &rel, const DCsr *A, const DevElmats &el, int ae0,
               EigBatch &batch, bool scale, double *Dout, const RowsSpan *rows = nullptr, AeClasses *classes = nullptr);
 
-// Fine level, 8-dof elements: the sparse rows of the AE matrices of a chunk (RW slots per row at
+// Fine level, 8-dof elements, or elements of at most 8 dofs each (DevElmats::max_nd): the sparse rows of the AE matrices of a chunk (RW slots per row at
 // rv / rc[(batch.voff[b] + row) * RW + slot], column -1 = empty).  false: not applicable.
 bool ae_sparse_rows(hipStream_t s, const DevRelations &rel, const DCsr &A, const DevElmats &el, int ae0,
                     const EigBatch &batch, int &RW, const double *&rv, const short *&rc,

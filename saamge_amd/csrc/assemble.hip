@@ -539,6 +539,152 @@ __global__ __launch_bounds__(256) void ae_rows8_lds_kernel(
     }
 }
 
+// The same for elements of at most 8 dofs and of different sizes (level 0 of a mesh of hexes and prisms, tetrahedra or
+// pyramids): an element's slots are found through e2d_I (rows are not 16-byte aligned: scalar loads), its matrix entries read
+// at eloff[e] + kk nd_e + jj.  The per-dof element lists are AR_MW wide (a vertex of a hex / prism mesh lies in up to 12
+// elements); an agglomerate with a dof in more elements takes the walk through global memory.  Every entry is summed over
+// the elements of its row's dof inside the agglomerate in ascending element id, as in ae_build_kernel's generic walk.
+constexpr int AR_MW = 16;
+static size_t rows_mixed_lds(int max_n, int &hsize) {
+    hsize = 64;
+    while (hsize < 2 * max_n) hsize <<= 1;
+    // la0, lg, llen, lne, lflag; hkey, hval; (align) del, dkk, dnd (8 x 9 x 5-element agglomerates of 405 dofs: 53 KB)
+    return (size_t)max_n * (8 + 4 + 4 + 4 + 1) + (size_t)hsize * 6 + 16 + (size_t)max_n * AR_MW * (4 + 1 + 1) + 8;
+}
+__global__ __launch_bounds__(256) void ae_rows_mixed_lds_kernel(
+    int ae0, int RW, int hsize, const int *__restrict__ ns, const int64_t *__restrict__ voff,
+    const int *__restrict__ ae2d_I, const int *__restrict__ ae2d_J, const signed char *__restrict__ flags,
+    const int *__restrict__ d2e_I, const int *__restrict__ d2e_J, const int *__restrict__ part,
+    const int *__restrict__ e2d_I, const int *__restrict__ e2d_J, const int64_t *__restrict__ eloff,
+    const double *__restrict__ elval, const roff_t *__restrict__ Arow, const int *__restrict__ Acol,
+    const double *__restrict__ Aval, double *__restrict__ rvals, short *__restrict__ rcols) {
+    extern __shared__ __align__(16) unsigned char ar_lds[];
+    const int b = blockIdx.x, p = ae0 + b, n = ns[b];
+    roff_t *la0 = (roff_t *)ar_lds;                 // [n] first entry of the row in A
+    int *lg = (int *)(la0 + n);                     // [n] global dof
+    int *llen = lg + n;                             // [n] entries of the row
+    int *lne = llen + n;                            // [n] slots of the dof's element list in use (<= AR_MW)
+    int *hkey = lne + n;                            // [hsize] dof or -1
+    short *hval = (short *)(hkey + hsize);          // [hsize] local index
+    signed char *lflag = (signed char *)(hval + hsize);   // [n]
+    int *del = (int *)(((uintptr_t)(lflag + n) + 3) & ~(uintptr_t)3);         // [n][AR_MW] element or -1
+    unsigned char *dkk = (unsigned char *)(del + AR_MW * (size_t)n);            // [n][AR_MW] slot of the dof in it
+    unsigned char *dnd = dkk + AR_MW * (size_t)n;                               // [n][AR_MW] its number of dofs
+    const int tid = threadIdx.x;
+    for (int i = tid; i < hsize; i += 256) hkey[i] = -1;
+    __syncthreads();
+    const int *dofs = ae2d_J + ae2d_I[p];
+    bool many = false;      // (a dof with more than AR_MW elements: the agglomerate takes the walk through global memory)
+    for (int i = tid; i < n; i += 256) {
+        const int g = dofs[i];
+        const roff_t a0 = Arow[g];
+        lg[i] = g;
+        la0[i] = a0;
+        llen[i] = (int)(Arow[g + 1] - a0);
+        lflag[i] = flags[g];
+        const int cnt = d2e_I[g + 1] - d2e_I[g];
+        many = many || cnt > AR_MW;
+        lne[i] = min(cnt, AR_MW);
+        unsigned hpos = hash_home((unsigned)g, (unsigned)hsize);
+        while (atomicCAS(&hkey[hpos], -1, g) != -1) hpos = (hpos + 1) & (unsigned)(hsize - 1);
+        hval[hpos] = (short)i;
+    }
+    for (int it = tid; it < n * AR_MW; it += 256) {
+        const int i = it / AR_MW, q = it - i * AR_MW;
+        const int g = dofs[i];
+        const int qb = d2e_I[g], cnt = d2e_I[g + 1] - qb;
+        int e = -1, kk = 0, nd = 0;
+        if (q < cnt) {
+            e = d2e_J[qb + q];
+            if (part[e] != p) {
+                e = -1;
+            } else {
+                const int eb = e2d_I[e];
+                nd = e2d_I[e + 1] - eb;
+                while (kk < nd - 1 && e2d_J[eb + kk] != g) ++kk;
+            }
+        }
+        del[it] = e;
+        dkk[it] = (unsigned char)kk;
+        dnd[it] = (unsigned char)nd;
+    }
+    const bool walk = __syncthreads_or(many ? 1 : 0) != 0;
+    const size_t obase = (size_t)voff[b] * RW;
+    constexpr int UN = 4;
+    for (int it0 = tid; it0 < n * RW; it0 += 256 * UN) {
+        int lrs[UN], cs[UN], lcs[UN];
+        double vs[UN];
+        roff_t as[UN];
+        bool on[UN];
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            const int it = it0 + 256 * u;
+            const int lr = it < n * RW ? it / RW : 0, k = it - lr * RW;
+            lrs[u] = lr;
+            on[u] = it < n * RW && k < llen[lr];
+            as[u] = la0[lr] + k;
+            cs[u] = on[u] ? Acol[as[u]] : -1;
+        }
+#pragma unroll
+        for (int u = 0; u < UN; ++u) vs[u] = on[u] ? Aval[as[u]] : 0.0;      // (used unless the entry is assembled from elements)
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            lcs[u] = -1;
+            if (on[u]) {
+                const int c = cs[u];
+                unsigned hpos = hash_home((unsigned)c, (unsigned)hsize);
+                for (;;) {
+                    const int key = hkey[hpos];
+                    if (key == c) { lcs[u] = hval[hpos]; break; }
+                    if (key == -1) break;
+                    hpos = (hpos + 1) & (unsigned)(hsize - 1);
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            const int it = it0 + 256 * u;
+            if (it >= n * RW) continue;
+            const int lr = lrs[u], lc = lcs[u], c = cs[u];
+            double v = 0.0;
+            if (lc >= 0) {
+                const int g = lg[lr];
+                const int fg = lflag[lr], fc = lflag[lc];
+                const bool assembled = (fg & 1) && (fc & 1) && (!((fg | fc) & 2) || c == g);
+                if (!assembled) {
+                    v = vs[u];                      // copied from the global matrix (aggregates.cpp:930-934)
+                } else if (!walk) {                 // agg_assemble_value, aggregates.cpp:68-184
+                    const int nr = lne[lr], nc = lne[lc];
+                    for (int q = 0; q < nr; ++q) {
+                        const int e = del[lr * AR_MW + q];
+                        if (e < 0) continue;
+                        int jj = -1;
+                        for (int q2 = 0; q2 < nc; ++q2)
+                            if (del[lc * AR_MW + q2] == e) jj = dkk[lc * AR_MW + q2];
+                        if (jj >= 0) v += elval[eloff[e] + dkk[lr * AR_MW + q] * dnd[lr * AR_MW + q] + jj];
+                    }
+                } else {
+                    const int qb = d2e_I[g], cnt = d2e_I[g + 1] - qb;
+                    for (int q = 0; q < cnt; ++q) {      // ascending element id
+                        const int e = d2e_J[qb + q];
+                        if (part[e] != p) continue;
+                        const int eb = e2d_I[e], nd = e2d_I[e + 1] - eb;
+                        int kk = -1, jj = -1;
+                        for (int t = 0; t < nd; ++t) {
+                            const int dd = e2d_J[eb + t];
+                            if (dd == g && kk < 0) kk = t;
+                            if (dd == c && jj < 0) jj = t;
+                        }
+                        if (jj >= 0) v += elval[eloff[e] + (int64_t)kk * nd + jj];
+                    }
+                }
+            }
+            rvals[obase + it] = v;
+            rcols[obase + it] = (short)lc;
+        }
+    }
+}
+
 constexpr int AB_MAXE = 8;   // elements per dof kept in the LDS row tables (hexes: <= 8)
 
 // NDE > 0: every element has exactly NDE dofs (level 0: elem_to_dof is a dense NE x NDE array),
@@ -888,7 +1034,13 @@ static void launch_rows8(hipStream_t s, const DevRelations &rel, const DCsr &A, 
     int hsize = 64;
     while (hsize < 2 * batch.max_n) hsize <<= 1;
     const size_t lds = (size_t)batch.max_n * (8 + 4 + 4 + 1) + (size_t)hsize * 6 + 16 + (size_t)batch.max_n * 40 + 8;      // (+ the per-dof element lists)
-    if (!old_rows && lds <= 64 * 1024)
+    if (el.nde != 8) {      // elements of different sizes (the callers checked rows_mixed_fit)
+        int mhsize = 0;
+        const size_t mlds = rows_mixed_lds(batch.max_n, mhsize);
+        hipLaunchKernelGGL(ae_rows_mixed_lds_kernel, dim3(batch.count), dim3(256), mlds, s, ae0, RW, mhsize, batch.n.p,
+                           batch.voff.p, rel.ae2d_I.p, rel.ae2d_J.p, rel.flags.p, rel.d2e_I.p, rel.d2e_J.p, rel.part.p,
+                           rel.e2d_I.p, rel.e2d_J.p, el.off.p, el.val.p, A.rowptr.p, A.col.p, A.val.p, dv, dc);
+    } else if (!old_rows && lds <= 64 * 1024)
         hipLaunchKernelGGL(ae_rows8_lds_kernel, dim3(batch.count), dim3(256), lds, s, ae0, RW, hsize, batch.n.p, batch.voff.p,
                            rel.ae2d_I.p, rel.ae2d_J.p, rel.flags.p, rel.d2e_I.p, rel.d2e_J.p, rel.part.p, rel.e2d_J.p,
                            el.dense(), A.rowptr.p, A.col.p, A.val.p, dv, dc);
@@ -903,9 +1055,19 @@ static void launch_rows8(hipStream_t s, const DevRelations &rel, const DCsr &A, 
     rc = dc;
 }
 
+// level 0 of a mesh whose elements have at most 8 dofs and different sizes, agglomerates whose tables fit the LDS of
+// ae_rows_mixed_lds_kernel (otherwise: the generic assembly)
+static bool rows_mixed_fit(const DevElmats &el, const EigBatch &batch) {
+    if (el.algebraic || el.nde != 0 || el.max_nd < 1 || el.max_nd > 8) return false;
+    int hsize = 0;
+    return rows_mixed_lds(batch.max_n, hsize) <= 64 * 1024;
+}
+
 bool ae_sparse_rows(hipStream_t s, const DevRelations &rel, const DCsr &A, const DevElmats &el, int ae0,
                     const EigBatch &batch, int &RW, const double *&rv, const short *&rc, const RowsSpan *rows) {
-    if (!batch.count || el.algebraic || el.nde != 8 || batch.count > 65535 || batch.max_n > 32767) return false;
+    if (!batch.count || el.algebraic || !(el.nde == 8 || rows_mixed_fit(el, batch)) || batch.count > 65535 ||
+        batch.max_n > 32767)
+        return false;
     if (A.max_row < 0) A.max_row = csr_max_row(s, A);
     RW = A.max_row;
     launch_rows8(s, rel, A, el, ae0, batch, RW, rv, rc, rows);
@@ -1335,14 +1497,17 @@ void ae_build(hipStream_t s, const DevRelations &rel, const DCsr *A, const DevEl
     constexpr bool band_write = true;
     const int band_only = (bwp && band_write && eig_ss_band_enabled()) ? 1 : 0;
     const bool nde8 = el.nde == 8 && batch.count <= 65535;   // (grid.y of the rows kernel)
+    // precomputed sparse rows: 8-dof elements, or elements of at most 8 dofs and different sizes (ae_build_kernel's PRE branch
+    // reads the rows only: its NDE does not matter there)
+    const bool pre = nde8 || (rows_mixed_fit(el, batch) && batch.count <= 65535);
     const double *rv = nullptr;
     const short *rc = nullptr;
-    if (nde8) launch_rows8(s, rel, *A, el, ae0, batch, RW, rv, rc, rows);
+    if (pre) launch_rows8(s, rel, *A, el, ae0, batch, RW, rv, rc, rows);
     // classes of identical agglomerates: only their first members are built (the caller runs the eigensolvers on those);
     // not when D is wanted for every agglomerate (keep_debug)
     DBuf<int> only;
     int nbuild = batch.count;
-    if (classes && nde8 && bwp && !Dout && !batch.has_x0c) {
+    if (classes && pre && bwp && !Dout && !batch.has_x0c) {
         DdSource &src = classes->src;
         src = DdSource();
         src.kind = 0;
@@ -1367,9 +1532,9 @@ void ae_build(hipStream_t s, const DevRelations &rel, const DCsr *A, const DevEl
     for (int n : batch.h_n) bytes += 8.0 * (double)n * n;
     profiler().begin(s);
     if (scale) {
-        if (nde8) launch(ae_build_kernel<true, 8, true>); else launch(ae_build_kernel<true, 0, false>);
+        if (pre) launch(ae_build_kernel<true, 8, true>); else launch(ae_build_kernel<true, 0, false>);
     } else {
-        if (nde8) launch(ae_build_kernel<false, 8, true>); else launch(ae_build_kernel<false, 0, false>);
+        if (pre) launch(ae_build_kernel<false, 8, true>); else launch(ae_build_kernel<false, 0, false>);
     }
     SA_HIP_CHECK(hipGetLastError());
     profiler().end(s, "ae_build", bytes * (double)nbuild / (double)batch.count, 0.0);

@@ -150,7 +150,7 @@ static Params convert_params(const saamge_amd_params *params, void *stream) {
 }
 
 static int produce_data(int n, const void *rowptr, int rowptr_bits, const int *col, const double *val,
-                        int NE, int nde, const int *elem_to_dof, const double *elmat,
+                        int NE, int nde, const int *elem_ptr, const int *elem_to_dof, const double *elmat,
                         const signed char *bdr_dofs, const int *const *partitions,
                         const int *nparts, const saamge_amd_params *params, void *stream,
                         saamge_amd_hierarchy **out) {
@@ -159,7 +159,7 @@ static int produce_data(int n, const void *rowptr, int rowptr_bits, const int *c
                "null argument");
     const Params p = convert_params(params, stream);
     set_thread_stream((hipStream_t)stream);
-    Hierarchy *H = hierarchy_create(n, rowptr, rowptr_bits, col, val, NE, nde, elem_to_dof, elmat, bdr_dofs,
+    Hierarchy *H = hierarchy_create(n, rowptr, rowptr_bits, col, val, NE, nde, elem_ptr, elem_to_dof, elmat, bdr_dofs,
                                     partitions, nparts, p, (hipStream_t)stream);
     *out = new saamge_amd_hierarchy{H};
     SA_API_END
@@ -194,7 +194,7 @@ int saamge_amd_ml_produce_data(int n, const int *rowptr, const int *col, const d
                                const signed char *bdr_dofs, const int *const *partitions,
                                const int *nparts, const saamge_amd_params *params, void *stream,
                                saamge_amd_hierarchy **out) {
-    return produce_data(n, rowptr, 32, col, val, NE, nde, elem_to_dof, elmat, bdr_dofs, partitions, nparts, params, stream, out);
+    return produce_data(n, rowptr, 32, col, val, NE, nde, nullptr, elem_to_dof, elmat, bdr_dofs, partitions, nparts, params, stream, out);
 }
 
 int saamge_amd_ml_produce_data64(int n, const long long *rowptr, const int *col, const double *val,
@@ -202,7 +202,25 @@ int saamge_amd_ml_produce_data64(int n, const long long *rowptr, const int *col,
                                  const signed char *bdr_dofs, const int *const *partitions,
                                  const int *nparts, const saamge_amd_params *params, void *stream,
                                  saamge_amd_hierarchy **out) {
-    return produce_data(n, rowptr, 64, col, val, NE, nde, elem_to_dof, elmat, bdr_dofs, partitions, nparts, params, stream, out);
+    return produce_data(n, rowptr, 64, col, val, NE, nde, nullptr, elem_to_dof, elmat, bdr_dofs, partitions, nparts, params, stream, out);
+}
+
+int saamge_amd_ml_produce_data_mixed(int n, const int *rowptr, const int *col, const double *val,
+                                     int NE, const int *elem_ptr, const int *elem_to_dof, const double *elmat,
+                                     const signed char *bdr_dofs, const int *const *partitions,
+                                     const int *nparts, const saamge_amd_params *params, void *stream,
+                                     saamge_amd_hierarchy **out) {
+    if (!elem_ptr) { g_last_error = "null argument: elem_ptr"; return 1; }
+    return produce_data(n, rowptr, 32, col, val, NE, 0, elem_ptr, elem_to_dof, elmat, bdr_dofs, partitions, nparts, params, stream, out);
+}
+
+int saamge_amd_ml_produce_data_mixed64(int n, const long long *rowptr, const int *col, const double *val,
+                                       int NE, const int *elem_ptr, const int *elem_to_dof, const double *elmat,
+                                       const signed char *bdr_dofs, const int *const *partitions,
+                                       const int *nparts, const saamge_amd_params *params, void *stream,
+                                       saamge_amd_hierarchy **out) {
+    if (!elem_ptr) { g_last_error = "null argument: elem_ptr"; return 1; }
+    return produce_data(n, rowptr, 64, col, val, NE, 0, elem_ptr, elem_to_dof, elmat, bdr_dofs, partitions, nparts, params, stream, out);
 }
 
 int saamge_amd_update_operators(saamge_amd_hierarchy *h, const double *new_val) {

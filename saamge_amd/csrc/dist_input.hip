@@ -216,7 +216,7 @@ Hierarchy *hierarchy_create_dist(const ParCsrIn &A, int NE_loc, int nde, const i
     const int *col_p = din->col.p;
     const double *val_p = din->val.p;
     const int *nparts_p = din->nparts.data();
-    return hierarchy_create((int)n, rowptr_p, 64, col_p, val_p, (int)NE, nde, e2d_p, elmat, bdr_p, parts.data(), nparts_p, p, s,
+    return hierarchy_create((int)n, rowptr_p, 64, col_p, val_p, (int)NE, nde, nullptr, e2d_p, elmat, bdr_p, parts.data(), nparts_p, p, s,
                             std::move(din));
 }
 

@@ -170,6 +170,7 @@ struct Hierarchy {              // ml_data_t
     };
     std::vector<UserSmoother> user_smoothers;
     DBuf<int> own_e2d;          // element-free mode: the generated identity elem_to_dof
+    DBuf<int> e2d_ptr;          // mixed elements: the caller's elem_ptr on the device (the level-0 topology views it)
     // host copies of the coarse partitions (levels >= 1: a few thousand ints), fetched once at the start of the setup: the host
     // build of a coarse level's AE tables starts while the GPU still computes that level's element matrices
     std::vector<hvec<int>> coarse_parts;
@@ -191,8 +192,11 @@ struct Hierarchy {              // ml_data_t
 
 // ml_produce_data (amg/src/ml.cpp:379-472).  All array arguments may be host or device
 // pointers.  partitions[k] maps level-k elements to level-k AEs.
+// elem_ptr (NE + 1 offsets, nde = 0) or nde (elem_ptr = null): element e holds the dofs
+// elem_to_dof[elem_ptr[e] .. elem_ptr[e+1]) (e * nde ...) and its nd_e x nd_e matrix packed in element order.
+// elem_ptr is checked before anything uses it; equal element sizes take the nde path.
 Hierarchy *hierarchy_create(int n, const void *Arow, int rowptr_bits, const int *Acol, const double *Aval, int NE,
-                            int nde, const int *elem_to_dof, const double *elmat,
+                            int nde, const int *elem_ptr, const int *elem_to_dof, const double *elmat,
                             const signed char *bdr, const int *const *partitions,
                             const int *nparts, const Params &p, hipStream_t stream, std::unique_ptr<DistIn> din = nullptr);
 // the same from per-rank inputs (dist_input.hip): elem_to_dof holds GLOBAL dof ids, elmat the matrices of the rank's own

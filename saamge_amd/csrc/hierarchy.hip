@@ -76,6 +76,74 @@ __global__ void iota64_kernel(long n, int64_t scale, int64_t *p) {
     if (i < n) p[i] = i * scale;
 }
 
+// Mixed elements: checks of a device-resident elem_ptr (NE + 1 entries) and elem_to_dof (elem_ptr[NE] entries, read only
+// after the offsets passed), the sizes of the elements and their squares.  info = {error bits, MAX_ELEM_DOFS - smallest element,
+// largest element}, zero-initialised.
+constexpr int MAX_ELEM_DOFS = 32767;
+__global__ __launch_bounds__(256) void elem_ptr_check_kernel(long NE, const int *__restrict__ ptr, int *__restrict__ info) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e == 0 && ptr[0] != 0) atomicOr(&info[0], 1);
+    if (e >= NE) return;
+    const int nd = ptr[e + 1] - ptr[e];
+    if (nd <= 0) atomicOr(&info[0], 2);
+    else if (nd > MAX_ELEM_DOFS) atomicOr(&info[0], 4);
+    else { atomicMax(&info[1], MAX_ELEM_DOFS - nd); atomicMax(&info[2], nd); }
+}
+__global__ __launch_bounds__(256) void dof_range_kernel(long nconn, int ND, const int *__restrict__ J, int *__restrict__ err) {
+    const long k = (long)blockIdx.x * 256 + threadIdx.x;
+    if (k < nconn && (J[k] < 0 || J[k] >= ND)) atomicOr(err, 8);
+}
+__global__ __launch_bounds__(256) void elem_sq_kernel(long NE, const int *__restrict__ ptr, int *__restrict__ sq) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e < NE) { const int nd = ptr[e + 1] - ptr[e]; sq[e] = nd * nd; }
+}
+
+// Checks elem_ptr / elem_to_dof of the mixed entries before any other use: host-resident offsets on the host, device-resident
+// ones by the kernels above.  Returns the element size if all elements have the same, 0 otherwise; max_nd = the largest.
+static int check_elem_ptr(int NE, const int *elem_ptr, const int *elem_to_dof, int ND, int &max_nd, hipStream_t s) {
+    int bits = 0, mn = 0, mx = 0;
+    long nconn = 0;
+    if (!is_device_ptr(elem_ptr)) {
+        bits |= elem_ptr[0] != 0 ? 1 : 0;
+        mn = MAX_ELEM_DOFS;
+        for (int e = 0; e < NE && !bits; ++e) {
+            const int nd = elem_ptr[e + 1] - elem_ptr[e];
+            if (nd <= 0) bits |= 2;
+            else if (nd > MAX_ELEM_DOFS) bits |= 4;
+            else { mn = std::min(mn, nd); mx = std::max(mx, nd); }
+        }
+        if (!bits) nconn = elem_ptr[NE];
+    } else {
+        DBuf<int> info(3);
+        info.zero(s);
+        hipLaunchKernelGGL(elem_ptr_check_kernel, dim3(div_up((long)NE, 256)), dim3(256), 0, s, (long)NE, elem_ptr, info.p);
+        SA_HIP_CHECK(hipGetLastError());
+        const auto h = info.to_host(s);
+        bits = h[0]; mn = MAX_ELEM_DOFS - h[1]; mx = h[2];
+        if (!bits) {
+            int last = 0;
+            SA_HIP_CHECK(hipMemcpyAsync(&last, elem_ptr + NE, sizeof(int), hipMemcpyDeviceToHost, s));
+            SA_HIP_CHECK(hipStreamSynchronize(s));
+            nconn = last;
+        }
+    }
+    SA_REQUIRE(!(bits & 1), "elem_ptr[0] must be 0");
+    SA_REQUIRE(!(bits & 2), "elem_ptr: an element without dofs or decreasing offsets");
+    SA_REQUIRE(!(bits & 4), "elem_ptr: an element with more than 32767 dofs");
+    if (!is_device_ptr(elem_to_dof)) {
+        for (long k = 0; k < nconn; ++k)
+            SA_REQUIRE(elem_to_dof[k] >= 0 && elem_to_dof[k] < ND, "elem_to_dof entry out of range");
+    } else {
+        DBuf<int> err(1);
+        err.zero(s);
+        hipLaunchKernelGGL(dof_range_kernel, dim3(div_up(nconn, 256)), dim3(256), 0, s, nconn, ND, elem_to_dof, err.p);
+        SA_HIP_CHECK(hipGetLastError());
+        SA_REQUIRE(!err.to_host(s)[0], "elem_to_dof entry out of range");
+    }
+    max_nd = mx;
+    return mn == mx ? mx : 0;
+}
+
 __global__ void gather_kernel(long n, const int *__restrict__ idx, const double *__restrict__ src, double *__restrict__ dst) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = src[idx[i]];
@@ -152,6 +220,7 @@ static void join_galerkin(Hierarchy &H) {
 
 struct DeviceInputs {   // level-0 inputs that already live on the device (see hierarchy_create)
     const int *e2d = nullptr, *part = nullptr;
+    const int *e2d_I = nullptr;     // mixed elements (nde = 0): the checked offsets
     const signed char *bdr = nullptr;
     int NE = 0, nde = 0;
 };
@@ -194,7 +263,7 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
     }
     bool on_device = false;
     if (din) {
-        on_device = build_relations_ae_device(L.rel, L.drel, din->e2d, din->NE, din->nde, din->part, nparts,
+        on_device = build_relations_ae_device(L.rel, L.drel, din->e2d, din->NE, din->nde, din->e2d_I, din->part, nparts,
                                               L.A.nrows, din->bdr, s);
         tm.lap("device topology (AE tables)", lev);
     }
@@ -202,9 +271,13 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
         hvec<int> part_h;
         hvec<signed char> bdr_h;
         if (din) {   // agglomerates too large for the device kernels: fetch and take the host path
-            e2d.J = fetch_host(din->e2d, (size_t)din->NE * din->nde, s);
-            e2d.I.resize((size_t)din->NE + 1);
-            for (int e = 0; e <= din->NE; ++e) e2d.I[e] = e * din->nde;
+            if (din->e2d_I) {
+                e2d.I = fetch_host(din->e2d_I, (size_t)din->NE + 1, s);
+            } else {
+                e2d.I.resize((size_t)din->NE + 1);
+                for (int e = 0; e <= din->NE; ++e) e2d.I[e] = e * din->nde;
+            }
+            e2d.J = fetch_host(din->e2d, (size_t)e2d.I[din->NE], s);
             e2d.ncols = L.A.nrows;
             part_h = fetch_host(din->part, (size_t)din->NE, s);
             if (din->bdr) bdr_h = fetch_host(din->bdr, (size_t)L.A.nrows, s);
@@ -1480,7 +1553,7 @@ static void add_nullspace_level(Hierarchy &H) {
 // ml_produce_data
 // ---------------------------------------------------------------------------------------
 Hierarchy *hierarchy_create(int n, const void *Arow, int rowptr_bits, const int *Acol, const double *Aval, int NE,
-                            int nde, const int *elem_to_dof, const double *elmat,
+                            int nde, const int *elem_ptr, const int *elem_to_dof, const double *elmat,
                             const signed char *bdr, const int *const *partitions,
                             const int *nparts, const Params &p, hipStream_t stream, std::unique_ptr<DistIn> dist_inputs) {
     SA_REQUIRE(p.num_coarsenings >= 1 && p.num_coarsenings < MAX_LEVELS, "bad number of coarsenings");
@@ -1497,7 +1570,14 @@ Hierarchy *hierarchy_create(int n, const void *Arow, int rowptr_bits, const int 
         elmat = nullptr;
         bdr = nullptr;
     }
-    SA_REQUIRE(n > 0 && NE > 0 && nde > 0, "empty problem");
+    int max_nd = 0;
+    if (elem_ptr) {       // mixed entries: checked here; elements of one size take the path of the uniform entries from here on
+        SA_REQUIRE(!p.algebraic && !dist_inputs && elem_to_dof && elmat, "elem_ptr needs element arrays");
+        SA_REQUIRE(n > 0 && NE > 0, "empty problem");
+        nde = check_elem_ptr(NE, elem_ptr, elem_to_dof, n, max_nd, stream);
+        if (nde) elem_ptr = nullptr;
+    }
+    SA_REQUIRE(n > 0 && NE > 0 && (nde > 0 || elem_ptr), "empty problem");
     PhaseTimer tm_all(stream), tm0(stream);
     std::unique_ptr<Hierarchy> Hp(new Hierarchy);
     Hierarchy &H = *Hp;
@@ -1534,6 +1614,18 @@ Hierarchy *hierarchy_create(int n, const void *Arow, int rowptr_bits, const int 
             SA_HIP_CHECK(hipGetLastError());
             import_array(L0.elmat.val, elmat, (size_t)H.dist_in->NE_loc * nde * nde, s);
             L0.elmat.first = H.dist_in->elem0;
+        } else if (elem_ptr) {
+            // mixed elements: element e's matrix at sum_{f<e} nd_f^2
+            import_array(H.e2d_ptr, elem_ptr, (size_t)NE + 1, s);
+            DBuf<int> sq((size_t)NE);
+            hipLaunchKernelGGL(elem_sq_kernel, dim3(div_up((long)NE, 256)), dim3(256), 0, s, (long)NE, H.e2d_ptr.p, sq.p);
+            SA_HIP_CHECK(hipGetLastError());
+            exclusive_scan_off(s, NE, sq.p, L0.elmat.off.p);
+            int64_t total = 0;
+            SA_HIP_CHECK(hipMemcpyAsync(&total, L0.elmat.off.p + NE, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+            SA_HIP_CHECK(hipStreamSynchronize(s));
+            import_array(L0.elmat.val, elmat, (size_t)total, s);
+            L0.elmat.max_nd = max_nd;
         } else {
         hipLaunchKernelGGL(iota64_kernel, dim3(div_up((long)NE + 1, 256)), dim3(256), 0, s, (long)NE + 1,
                            (int64_t)nde * nde, L0.elmat.off.p);
@@ -1556,6 +1648,12 @@ Hierarchy *hierarchy_create(int n, const void *Arow, int rowptr_bits, const int 
         din.bdr = bdr;
         din.NE = NE;
         din.nde = nde;
+        din.e2d_I = elem_ptr ? H.e2d_ptr.p : nullptr;
+    } else if (elem_ptr) {
+        e2d.I = fetch_host(H.e2d_ptr.p, (size_t)NE + 1, s);
+        e2d.J = fetch_host(elem_to_dof, (size_t)e2d.I[NE], s);
+        e2d.ncols = n;
+        if (bdr) bdr_h = fetch_host(bdr, (size_t)n, s);
     } else {
         auto J = fetch_host(elem_to_dof, (size_t)NE * nde, s);
         e2d.J = std::move(J);

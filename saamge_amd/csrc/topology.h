@@ -70,13 +70,14 @@ struct DevRelations {
     DBuf<signed char> flags;
 };
 void upload_relations_ae(DevRelations &d, const Relations &r, hipStream_t s);
-// build_relations_ae + upload_relations_ae entirely on the device for device-resident inputs with
-// a fixed number of dofs per element (level 0); the host receives the tables the MIS stage and
-// the next level need, never elem_to_dof.  Returns false (nothing built) when an agglomerate is
-// too large for the LDS kernels: the caller then takes the host path.
+// build_relations_ae + upload_relations_ae entirely on the device for device-resident inputs (level 0):
+// nde dofs per element, or (e2d_I_dev != null, nde = 0) the CSR offsets of elements of different sizes,
+// already checked.  The host receives the tables the MIS stage and the next level need, never
+// elem_to_dof.  Returns false (nothing built) when an agglomerate is too large for the LDS kernels:
+// the caller then takes the host path.
 bool build_relations_ae_device(Relations &r, DevRelations &d, const int *e2d_dev, int NE, int nde,
-                               const int *part_dev, int nparts, int ND, const signed char *bdr_dev,
-                               hipStream_t s);
+                               const int *e2d_I_dev, const int *part_dev, int nparts, int ND,
+                               const signed char *bdr_dev, hipStream_t s);
 void fetch_relations_ae_host(Relations &r, const DevRelations &d, hipStream_t s);
 void upload_relations_mis(DevRelations &d, const Relations &r, hipStream_t s);
 // build_relations_mis + upload_relations_mis on the device (topology_mis.hip): same tables bit for bit; needs the AE

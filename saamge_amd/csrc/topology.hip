@@ -913,7 +913,8 @@ void upload_relations_ae(DevRelations &d, const Relations &r, hipStream_t s) {
 // build_relations_ae, bit for bit, without moving elem_to_dof to the host.
 //   AE_to_elem   count + scan + atomic fill, rows sorted in LDS (bitonic)       ascending elements
 //   AE_to_dof    one workgroup per AE: LDS hash set keyed by dof holding the MIN rank of its
-//                appearances (rank = element position * nde + slot); a dof is kept at its minimum
+//                appearances (rank = element position * nde + slot, or the scan of the element sizes for
+//                elements of different sizes); a dof is kept at its minimum
 //                rank, so compacting the ranks in order gives mfem::Mult's first-encounter order
 //   dof_to_AE    count + scan + atomic fill, short rows sorted per dof (with dof_id_inAE payload)
 // ---------------------------------------------------------------------------------------
@@ -1067,6 +1068,86 @@ __global__ __launch_bounds__(256) void ae_to_dof_kernel(int mode, int nde, int H
     }
 }
 
+// The same for elements of different sizes, mode 2 only: the candidates of agglomerate p are the dofs of its elements in
+// ascending element order, at posoff[ae2e_I[p]] .. posoff[ae2e_I[p + 1]) of the padded buffer (posoff: exclusive scan of the
+// element sizes in AE_to_elem order).  (A copy, not a shared function: the kernel above stays as it is compiled for the
+// uniform path.)
+__global__ __launch_bounds__(256) void ae_to_dof_csr_kernel(int HS, const int *__restrict__ ae2e_I,
+                                                            const int *__restrict__ ae2e_J, const int *__restrict__ e2d_I,
+                                                            const int *__restrict__ e2d_J, const int *__restrict__ posoff,
+                                                            int *__restrict__ rowcnt, int *__restrict__ padded) {
+    extern __shared__ int sh[];
+    __shared__ int wsum[4], total;
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int eb = ae2e_I[p], ne = ae2e_I[p + 1] - eb;
+    const int k0 = posoff[eb], K = posoff[eb + ne] - k0;
+    const int Kpad = (K + 255) & ~255;
+    int *keys = sh, *ranks = sh + HS, *first = sh + 2 * HS, *vals = first + Kpad;
+    for (int i = tid; i < HS; i += 256) { keys[i] = -1; ranks[i] = 0x7fffffff; }
+    for (int i = tid; i < Kpad; i += 256) first[i] = 0;
+    for (int q = tid; q < ne; q += 256) {
+        const int e = ae2e_J[eb + q], b = e2d_I[e], nd = e2d_I[e + 1] - b;
+        int *dst = vals + (posoff[eb + q] - k0);
+        for (int t = 0; t < nd; ++t) dst[t] = e2d_J[b + t];
+    }
+    __syncthreads();
+    for (int idx = tid; idx < K; idx += 256) {
+        const int d = vals[idx];
+        unsigned h = hash_home((unsigned)d, (unsigned)HS);
+        for (;;) {
+            const int prev = atomicCAS(&keys[h], -1, d);
+            if (prev == -1 || prev == d) { atomicMin(&ranks[h], idx); break; }
+            h = (h + 1) & (unsigned)(HS - 1);
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < HS; i += 256)
+        if (keys[i] != -1) first[ranks[i]] = 1;
+    __syncthreads();
+    const int per = Kpad / 256;
+    int run = 0;
+    for (int u = 0; u < per; ++u) run += first[tid * per + u];
+    int incl = run;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(incl, o, 64);
+        if ((tid & 63) >= o) incl += v;
+    }
+    if ((tid & 63) == 63) wsum[tid >> 6] = incl;
+    __syncthreads();
+    if (tid == 0) {
+        int acc = 0;
+        for (int w = 0; w < 4; ++w) { const int v = wsum[w]; wsum[w] = acc; acc += v; }
+        total = acc;
+        rowcnt[p] = total;
+    }
+    __syncthreads();
+    int pos = wsum[tid >> 6] + incl - run;
+    int *o = padded + k0;
+    for (int u = 0; u < per; ++u) {
+        const int idx = tid * per + u;
+        if (first[idx]) o[pos++] = vals[idx];
+    }
+}
+__global__ __launch_bounds__(256) void elem_size_kernel(long NE, const int *__restrict__ ae2e_J, const int *__restrict__ e2d_I,
+                                                        int *__restrict__ sz) {
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (j < NE) { const int e = ae2e_J[j]; sz[j] = e2d_I[e + 1] - e2d_I[e]; }
+}
+__global__ __launch_bounds__(256) void ae_max_k_kernel(int nparts, const int *__restrict__ ae2e_I, const int *__restrict__ posoff,
+                                                       int *__restrict__ kmax) {
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p < nparts) atomicMax(kmax, posoff[ae2e_I[p + 1]] - posoff[ae2e_I[p]]);
+}
+__global__ __launch_bounds__(256) void ae_pack_lists_csr_kernel(const int *__restrict__ ae2e_I, const int *__restrict__ posoff,
+                                                                const int *__restrict__ outI, const int *__restrict__ padded,
+                                                                int *__restrict__ out) {
+    const int p = blockIdx.x, n = outI[p + 1] - outI[p];
+    const int *src = padded + posoff[ae2e_I[p]];
+    int *dst = out + outI[p];
+    for (int i = threadIdx.x; i < n; i += 256) dst[i] = src[i];
+}
+
 __global__ __launch_bounds__(256) void d2ae_fill_kernel(const int *__restrict__ ae2d_I, const int *__restrict__ ae2d_J,
                                                         const int *__restrict__ d2ae_I, int *__restrict__ cursor,
                                                         int *__restrict__ d2ae_J, int *__restrict__ did) {
@@ -1105,16 +1186,27 @@ static void download(hvec<T> &dst, const DBuf<T> &src, size_t n, hipStream_t s) 
 }
 
 bool build_relations_ae_device(Relations &r, DevRelations &d, const int *e2d_dev, int NE, int nde,
-                               const int *part_dev, int nparts, int ND, const signed char *bdr_dev,
-                               hipStream_t s) {
-    const long nconn = (long)NE * nde;
+                               const int *e2d_I_dev, const int *part_dev, int nparts, int ND,
+                               const signed char *bdr_dev, hipStream_t s) {
+    const bool csr = e2d_I_dev != nullptr;      // elements of different sizes
+    long nconn = (long)NE * nde;
+    if (csr) {
+        int last = 0;
+        SA_HIP_CHECK(hipMemcpyAsync(&last, e2d_I_dev + NE, sizeof(int), hipMemcpyDeviceToHost, s));
+        SA_HIP_CHECK(hipStreamSynchronize(s));
+        nconn = last;
+    }
     r.ND = ND;
     r.NE = NE;
     r.nparts = nparts;
     d.e2d_J.view(const_cast<int *>(e2d_dev), (size_t)nconn);
     d.part.view(const_cast<int *>(part_dev), (size_t)NE);
-    d.e2d_I.alloc((size_t)NE + 1);
-    hipLaunchKernelGGL(iota_scaled_kernel, dim3(div_up((long)NE + 1, 256)), dim3(256), 0, s, (long)NE + 1, nde, d.e2d_I.p);
+    if (csr) {
+        d.e2d_I.view(const_cast<int *>(e2d_I_dev), (size_t)NE + 1);
+    } else {
+        d.e2d_I.alloc((size_t)NE + 1);
+        hipLaunchKernelGGL(iota_scaled_kernel, dim3(div_up((long)NE + 1, 256)), dim3(256), 0, s, (long)NE + 1, nde, d.e2d_I.p);
+    }
     DBuf<int> err(1), cnt((size_t)std::max(nparts, ND) + 1);
     err.zero(s);
     hipLaunchKernelGGL(topo_check_kernel, dim3(div_up(nconn, 256)), dim3(256), 0, s, (long)NE, nconn, nparts, ND,
@@ -1165,31 +1257,56 @@ bool build_relations_ae_device(Relations &r, DevRelations &d, const int *e2d_dev
     SA_REQUIRE(!(err.to_host(s)[0] & 4), "empty agglomerate");
     int max_ne = 0;
     for (int p = 0; p < nparts; ++p) max_ne = std::max(max_ne, h_ae2e_I[p + 1] - h_ae2e_I[p]);
-    if ((long)max_ne * nde > TOPO_MAXK || max_ne > 4096) return false;   // host path handles it
+    if ((!csr && (long)max_ne * nde > TOPO_MAXK) || max_ne > 4096) return false;   // host path handles it
     SA_HIP_CHECK(hipMemsetAsync(cnt.p, 0, sizeof(int) * (size_t)nparts, s));
     hipLaunchKernelGGL(key_fill_runs_kernel, dim3(div_up(NE, 256)), dim3(256), 0, s, (long)NE, part_dev, ae2e_I.p, cnt.p,
                        ae2e_J.p);
     int cap = 2;
     while (cap < max_ne) cap <<= 1;
     hipLaunchKernelGGL(row_sort_kernel, dim3(nparts), dim3(256), sizeof(int) * (size_t)cap, s, ae2e_I.p, ae2e_J.p, cap);
+    // elements of different sizes: where the candidate dofs of every agglomerate start (scan of the element sizes in
+    // AE_to_elem order) and the most of them in one agglomerate
+    DBuf<int> posoff;
+    int K = max_ne * nde;
+    if (csr) {
+        DBuf<int> sz((size_t)NE), kmax(1);
+        posoff.alloc((size_t)NE + 1);
+        hipLaunchKernelGGL(elem_size_kernel, dim3(div_up(NE, 256)), dim3(256), 0, s, (long)NE, ae2e_J.p, d.e2d_I.p, sz.p);
+        exclusive_scan_int(s, NE, sz.p, posoff.p);
+        kmax.zero(s);
+        hipLaunchKernelGGL(ae_max_k_kernel, dim3(div_up(nparts, 256)), dim3(256), 0, s, nparts, ae2e_I.p, posoff.p, kmax.p);
+        SA_HIP_CHECK(hipGetLastError());
+        K = kmax.to_host(s)[0];
+        if (K > TOPO_MAXK) return false;
+    }
     // ---- AE_to_dof ----
-    const int K = max_ne * nde;
     int HS = 64;
     while (HS < 2 * K) HS <<= 1;
     const size_t lds = sizeof(int) * ((size_t)2 * HS + 2 * (size_t)((K + 255) & ~255));
     DBuf<int> rowcnt((size_t)nparts);
     d.ae2d_I.alloc((size_t)nparts + 1);
-    // (one pass: counts + lists into a padded buffer of NE * nde slots, then the packed copy)
-    DBuf<int> padded((size_t)NE * nde);
+    // (one pass: counts + lists into a padded buffer of NE * nde (nconn) slots, then the packed copy)
+    DBuf<int> padded((size_t)nconn);
+    if (csr) {
+        if (lds > 64 * 1024)
+            SA_HIP_CHECK(hipFuncSetAttribute((const void *)ae_to_dof_csr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+        hipLaunchKernelGGL(ae_to_dof_csr_kernel, dim3(nparts), dim3(256), lds, s, HS, ae2e_I.p, ae2e_J.p, d.e2d_I.p, e2d_dev,
+                           posoff.p, rowcnt.p, padded.p);
+    } else {
     if (lds > 64 * 1024)
         SA_HIP_CHECK(hipFuncSetAttribute((const void *)ae_to_dof_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     hipLaunchKernelGGL(ae_to_dof_kernel, dim3(nparts), dim3(256), lds, s, 2, nde, HS, ae2e_I.p, ae2e_J.p, e2d_dev,
                        rowcnt.p, nullptr, padded.p);
+    }
     exclusive_scan_int(s, nparts, rowcnt.p, d.ae2d_I.p);
     download(r.AE_to_dof.I, d.ae2d_I, (size_t)nparts + 1, s);
     SA_HIP_CHECK(hipStreamSynchronize(s));
     const long nae2d = r.AE_to_dof.I[nparts];
     d.ae2d_J.alloc((size_t)nae2d);
+    if (csr)
+        hipLaunchKernelGGL(ae_pack_lists_csr_kernel, dim3(nparts), dim3(256), 0, s, ae2e_I.p, posoff.p, d.ae2d_I.p, padded.p,
+                           d.ae2d_J.p);
+    else
     hipLaunchKernelGGL(ae_pack_lists_kernel, dim3(nparts), dim3(256), 0, s, nde, ae2e_I.p, d.ae2d_I.p, padded.p, d.ae2d_J.p);
     // ---- dof_to_AE, dof_id_inAE, flags ----
     d.d2ae_I.alloc((size_t)ND + 1);

@@ -38,6 +38,8 @@ class Problem(object):
 
     @property
     def NE(self):
+        if getattr(self, "elem_ptr", None) is not None:      # elements of different sizes: flat elem_to_dof
+            return len(self.elem_ptr) - 1
         return self.elem_to_dof.shape[0]
 
 
@@ -345,6 +347,126 @@ def poisson3d_problem(n, blk=(8, 8, 4), K=(1.0, 1.0, 1.0), coarse_blk=None,
     return Problem(A=A, b=b, elem_to_dof=elem_to_dof,
                    elmat=np.ascontiguousarray(elmat) if with_elmat else None,
                    bdr=bdr, ess=ess, partitions=parts, dims=n, order=1, Kref=Kref, coefs=c)
+
+
+# the two triangles of a cell's bottom face (unit-square corners, counter-clockwise) for the two diagonals
+_WEDGE_TRIS = ([[(0, 0), (1, 0), (1, 1)], [(0, 0), (1, 1), (0, 1)]],      # diagonal (0,0)-(1,1)
+               [[(0, 0), (1, 0), (0, 1)], [(1, 0), (1, 1), (0, 1)]])      # diagonal (1,0)-(0,1)
+
+
+def wedge_element_matrix(tri, hz):
+    """Exact stiffness of the 6-node P1 wedge (right prism) tri x [0, hz], tri = 3 x 2 vertices: node a * 3 + i is
+    triangle vertex i on the bottom (a = 0) or top (a = 1) face.  K = M_z (x) K_tri + K_z (x) M_tri."""
+    P = np.asarray(tri, dtype=float)
+    T = np.array([P[1] - P[0], P[2] - P[0]]).T
+    area = 0.5 * abs(np.linalg.det(T))
+    G = np.vstack([-np.ones(2), np.eye(2)]) @ np.linalg.inv(T)      # gradients of the barycentric coordinates
+    Kt = area * G @ G.T
+    Mt = area / 12.0 * (np.ones((3, 3)) + np.eye(3))
+    Mz = hz / 6.0 * np.array([[2.0, 1.0], [1.0, 2.0]])
+    Kz = 1.0 / hz * np.array([[1.0, -1.0], [-1.0, 1.0]])
+    return np.kron(Mz, Kt) + np.kron(Kz, Mt)
+
+
+def poisson3d_mixed_problem(n, blk, coarse_blk=None, wedges="half", coef=None, seed=0):
+    """poisson3d_problem on a mesh of Q1 hexes and 6-node P1 wedges (prisms): chosen vertical columns of cells are each
+    split into two wedges by one vertical diagonal plane per column.  Whole columns are split, so the mesh stays conforming
+    and the dofs are the grid's vertices.  wedges: "half" (columns with ex + ey even), "all", or "random" (columns and
+    diagonals drawn from `seed`); "half" and "all" use one diagonal, so that congruent agglomerates repeat.  A split cell
+    gives two consecutive element ids, both in the cell's agglomerate.  coef: None (1), "checkerboard" or "skew" at the
+    element's centroid.  Returns flat elem_to_dof, elem_ptr (NE + 1) and the element matrices packed in element order
+    (element e: nd_e x nd_e row-major at sum_{f<e} nd_f^2)."""
+    if np.isscalar(n):
+        n = (int(n),) * 3
+    nx, ny, nz = n
+    h = (1.0 / nx, 1.0 / ny, 1.0 / nz)
+    nvx, nvy, nvz = nx + 1, ny + 1, nz + 1
+    ND = nvx * nvy * nvz
+    ez, ey, ex = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    ex, ey, ez = ex.ravel(), ey.ravel(), ez.ravel()
+    vid = lambda i, j, k: (k * nvy + j) * nvx + i
+    cy, cx = np.meshgrid(np.arange(ny), np.arange(nx), indexing="ij")
+    if wedges == "all":
+        split_col, diag_col = np.ones((ny, nx), bool), np.zeros((ny, nx), np.int64)
+    elif wedges == "half":
+        split_col, diag_col = (cx + cy) % 2 == 0, np.zeros((ny, nx), np.int64)
+    elif wedges == "random":
+        rng = np.random.default_rng(seed)
+        split_col, diag_col = rng.random((ny, nx)) < 0.5, rng.integers(0, 2, (ny, nx))
+    else:
+        raise ValueError("wedges: 'half', 'all' or 'random'")
+    split = split_col[ey, ex]
+    diag = diag_col[ey, ex]
+    # element ids: cells in lexicographic order, a split cell gives two consecutive ones
+    per_cell = np.where(split, 2, 1)
+    first = np.concatenate([[0], np.cumsum(per_cell)[:-1]])
+    NE = int(per_cell.sum())
+    nd = np.full(NE, 8, np.int64)
+    hexc = np.flatnonzero(~split)
+    spc = np.flatnonzero(split)
+    nd[first[spc]] = 6
+    nd[first[spc] + 1] = 6
+    elem_ptr = np.concatenate([[0], np.cumsum(nd)]).astype(np.int32)
+    moff = np.concatenate([[0], np.cumsum(nd * nd)])
+    e2d = np.zeros(int(elem_ptr[-1]), np.int32)
+    elmat = np.zeros(int(moff[-1]))
+    bvol = np.zeros(NE)                      # f = 1: V / nd_e per node
+    cen = np.zeros((NE, 3))
+    # hexes
+    eh = first[hexc]
+    dofs_h = np.stack([vid(ex[hexc] + a, ey[hexc] + b_, ez[hexc] + c) for (a, b_, c) in _HEX_LOC], axis=1)
+    e2d[elem_ptr[eh][:, None] + np.arange(8)] = dofs_h
+    cen[eh] = np.stack([(ex[hexc] + 0.5) * h[0], (ey[hexc] + 0.5) * h[1], (ez[hexc] + 0.5) * h[2]], axis=1)
+    bvol[eh] = h[0] * h[1] * h[2] / 8.0
+    # wedges: (diagonal, half) -> cells and reference matrix
+    wref = {}
+    for dgl in (0, 1):
+        for half in (0, 1):
+            cells = spc[diag[spc] == dgl]
+            if cells.size == 0:
+                continue
+            tri = _WEDGE_TRIS[dgl][half]
+            ew = first[cells] + half
+            dofs_w = np.stack([vid(ex[cells] + tx, ey[cells] + ty, ez[cells] + a) for a in (0, 1) for (tx, ty) in tri], axis=1)
+            e2d[elem_ptr[ew][:, None] + np.arange(6)] = dofs_w
+            tc = np.mean(np.asarray(tri, dtype=float), axis=0)
+            cen[ew] = np.stack([(ex[cells] + tc[0]) * h[0], (ey[cells] + tc[1]) * h[1], (ez[cells] + 0.5) * h[2]], axis=1)
+            bvol[ew] = 0.5 * h[0] * h[1] * h[2] / 6.0
+            wref[(dgl, half)] = (ew, wedge_element_matrix([(tx * h[0], ty * h[1]) for (tx, ty) in tri], h[2]))
+    if coef == "checkerboard":
+        c = checkerboard_coef(cen[:, 0], cen[:, 1], cen[:, 2])
+    elif coef == "skew":
+        c = np.exp(0.7 * cen[:, 0] + 0.4 * cen[:, 1] - 0.3 * cen[:, 2]) * \
+            (1.0 + 0.3 * np.sin(5.0 * cen[:, 0] + 3.0 * cen[:, 1] + 7.0 * cen[:, 2]))
+    else:
+        c = np.ones(NE)
+    Kh = hex_element_matrix(h)
+    elmat[moff[eh][:, None] + np.arange(64)] = c[eh][:, None] * Kh.ravel()[None, :]
+    for (ew, Kw) in wref.values():
+        elmat[moff[ew][:, None] + np.arange(36)] = c[ew][:, None] * Kw.ravel()[None, :]
+    # ascending element order: the COO entries in packed order
+    rows = np.zeros(elmat.size, np.int64)
+    cols = np.zeros(elmat.size, np.int64)
+    for k, (ids, K) in enumerate([(eh, 8)] + [(ew, 6) for (ew, _) in wref.values()]):
+        d = e2d[elem_ptr[ids][:, None] + np.arange(K)]
+        base = moff[ids][:, None] + np.arange(K * K)
+        rows[base] = np.repeat(d, K, axis=1)
+        cols[base] = np.tile(d, (1, K))
+    A0 = sp.coo_matrix((elmat, (rows, cols)), shape=(ND, ND)).tocsr()
+    A0.sort_indices()
+    b0 = np.zeros(ND)
+    np.add.at(b0, e2d, np.repeat(bvol, nd))
+    iz, iy, ix = np.meshgrid(np.arange(nvz), np.arange(nvy), np.arange(nvx), indexing="ij")
+    ess = ((ix == 0) | (ix == nx) | (iy == 0) | (iy == ny) | (iz == 0) | (iz == nz)).ravel()
+    A, b = _eliminate(A0, b0, ess)
+    bdr = (np.where(ess, AGG_ON_ESS_DOMAIN_BORDER_FLAG, 0) | AGG_OWNED_FLAG).astype(np.int8)
+    part_cell, nb = block_partition(n, blk)
+    parts = [np.repeat(part_cell, per_cell).astype(np.int32)]
+    for cb in (coarse_blk or []):
+        p, nb = block_partition(nb, cb)
+        parts.append(p)
+    return Problem(A=A, b=b, elem_to_dof=e2d, elem_ptr=elem_ptr, elmat=elmat, bdr=bdr, ess=ess, partitions=parts,
+                   dims=n, order=1, coefs=c, centroids=cen)
 
 
 def _lagrange_1d_mixed(order):
