@@ -101,7 +101,7 @@ struct Options {
     int eig_dedupe = 1;               // bitwise identical agglomerate matrices of a batch are solved once
     int eig_outer_panels = 8;         // 16-column panels per outer block of the wide-band factorisations (2: the right-looking two-panel walk)
     int overlap = 15;                 // bit 0 subspace iteration beside the next chunk, 1 halo exchange beside the interior rows, 2 Galerkin product beside the next level, 3 fine operator data beside the AE tables
-    int sell = 31;                    // bit 0 coded slices at all, 1 pair coding, 2 short-chain kernel path, 3 operator-level dictionary, 4 node blocks, 5 (off) coded smoother diagonal
+    int sell = 31;                    // bit 0 coded slices at all, 1 pair coding, 2 short-chain kernel path, 3 operator-level dictionary, 4 node blocks, 5 (off) coded smoother diagonal, 6 (off) row patterns OFF
     int spmv_sell = 0;                // saamge_amd_spmv / spmv64 build and use the SELL copy
     int debug = 0;                    // bit 0 iteration traces of the few-eigenpairs path, 1 operator format census, 2 level tags in the kernel profile
     int host_heap_pad_mb = 256;       // > 0: glibc never trims its heap, serves blocks up to 32 MB from it and grows it in steps of this size (0: allocator left alone)
@@ -247,6 +247,7 @@ typedef int64_t roff_t;
 
 constexpr int SELL_SEG_MAX = 16;      // segments per staged tile
 constexpr int SELL_STAGE_CAP = 3584;  // doubles of x one tile may stage (28 KB of LDS)
+constexpr int SELL_PMAX = 16;         // row patterns per staged tile (DCsr::sell_row_pat)
 
 // Device CSR matrix.
 struct DCsr {
@@ -301,6 +302,15 @@ struct DCsr {
     // of tile T at (T sell_wq + q) 256 + t) and one descriptor word per tile (segments | the four slice widths)
     int sell_wq = 0;
     DBuf<unsigned> sell_codeR;
+    // row patterns (sell_row_patterns_kernel; options().sell bit 6 set: none): the distinct code-word rows of a staged tile,
+    // at most SELL_PMAX of them, in sell_tile_pat[(T SELL_PMAX + p) 8 + q] (zero past sell_wq words and past the tile's count),
+    // and one byte per row, sell_row_pat[256 T + t], naming its pattern.  sell_tile_pinfo[T] > 0: the pattern count;
+    // <= 0: the tile has more patterns and keeps its code words in sell_codeR at slot -sell_tile_pinfo[T] (then only such
+    // tiles have slots there).  Census: pattern tiles and the largest count.
+    DBuf<unsigned char> sell_row_pat;
+    DBuf<unsigned> sell_tile_pat;
+    DBuf<int> sell_tile_pinfo;
+    int sell_pat_tiles = 0, sell_pat_max = 0;
     // the smoother's diagonal factor as byte codes into a table of <= 256 values (operators whose rows repeat: a 256-row tile
     // then reads 256 bytes of it instead of 2 KB); sell_dsrc: the array the codes were made from (build_dinv_codes)
     DBuf<unsigned char> sell_dcode;

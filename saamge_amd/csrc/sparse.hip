@@ -414,9 +414,10 @@ __global__ __launch_bounds__(256) void sell_staged_kernel(int nrows, int row0, i
 // segment count: codes, right-hand side, diagonal, x-row and the tile's one table are requested before any descriptor
 // has arrived; only the x-segments wait for their (scalar-loaded) descriptors.  Operators whose staged tiles all share one
 // table per tile (sell_one_table); same products in the same order as sell_staged_kernel.
+// pinfo (row patterns, sell_row_patterns_kernel): code words only for the tiles that have no patterns, at their slot.
 __global__ __launch_bounds__(256) void sell_regular_codes_kernel(int ntiles, int wq, int ncols, const roff_t *__restrict__ sptr,
                                                                  const int *__restrict__ tile_nseg, const int2 *__restrict__ tile_seg,
-                                                                 const unsigned *__restrict__ codes,
+                                                                 const unsigned *__restrict__ codes, const int *__restrict__ pinfo,
                                                                  unsigned *__restrict__ codesR, int *__restrict__ tile_desc) {
     const int t = blockIdx.x, wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int nseg = tile_nseg[t];
@@ -428,7 +429,9 @@ __global__ __launch_bounds__(256) void sell_regular_codes_kernel(int ntiles, int
     const roff_t beg = sptr[slice];
     const int w = (int)((sptr[slice + 1] - beg) >> 6);
     const unsigned *wp = codes + ((size_t)(beg >> 2) + (size_t)slice * 64 + lane);
-    for (int q = 0; q < wq; ++q) codesR[((size_t)t * wq + q) * 256 + threadIdx.x] = (4 * q < w) ? wp[64 * q] : 0u;
+    const int slot = pinfo ? -pinfo[t] : t;
+    if (slot >= 0)
+        for (int q = 0; q < wq; ++q) codesR[((size_t)slot * wq + q) * 256 + threadIdx.x] = (4 * q < w) ? wp[64 * q] : 0u;
     __shared__ int ws[4];
     if (lane == 0) ws[wv] = w;
     __syncthreads();
@@ -442,6 +445,86 @@ __global__ __launch_bounds__(256) void sell_regular_codes_kernel(int ntiles, int
             inside = inside && g0 >= 0 && g0 + d.y <= ncols;
         }
         tile_desc[t] = nseg | (inside ? 128 : 0) | (ws[0] << 8) | (ws[1] << 14) | (ws[2] << 20) | (ws[3] << 26);
+    }
+}
+
+// Row patterns of the staged tiles (DCsr::sell_row_pat), one workgroup per tile at a time.  The code words of a 256-row tile of a
+// constant-coefficient stencil repeat: the interior rows share one sequence, only rows at line ends and near boundary faces
+// differ.  Pattern p is the row of the p-th row (in row order) that equals none before it: round p takes the first row not
+// yet named (a ballot per wavefront: one barrier per round, no atomics), and every unnamed row compares its words, zero
+// padding included, with that one's.  A tile with more than SELL_PMAX patterns takes a slot for its code words in sell_codeR
+// instead (census[0] counts the slots); census[1]: pattern tiles, census[2]: the largest count, census[3]: the code words of
+// the pattern tiles' slices (no longer streamed).  (A workgroup walks many tiles and adds to the census once: one atomic per
+// tile on the same word took 2.4 ms for the 66 307 tiles of the headline.)
+__global__ __launch_bounds__(256) void sell_row_patterns_kernel(int ntiles, int wq, const roff_t *__restrict__ sptr, const int *__restrict__ tile_nseg,
+                                                                const unsigned *__restrict__ codes, unsigned char *__restrict__ row_pat,
+                                                                unsigned *__restrict__ tile_pat, int *__restrict__ pinfo,
+                                                                unsigned long long *__restrict__ census) {
+    __shared__ unsigned ws[8][256];
+    __shared__ int first[2][4], leaders[SELL_PMAX], nwords;
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    unsigned long long ntile = 0, nmax = 0, nw = 0;      // (thread 0's share of the census)
+    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        if (tile_nseg[t] == 0) {      // (not staged: nothing reads its entries)
+            if (threadIdx.x == 0) pinfo[t] = 0;
+            continue;
+        }
+        const int slice = 4 * t + wv;
+        const roff_t beg = sptr[slice];
+        const int w = (int)((sptr[slice + 1] - beg) >> 6);
+        const unsigned *wp = codes + ((size_t)(beg >> 2) + (size_t)slice * 64 + lane);
+        unsigned my[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            my[q] = (q < wq && 4 * q < w) ? wp[64 * q] : 0u;      // (as sell_regular_codes_kernel lays them out)
+            ws[q][threadIdx.x] = my[q];
+        }
+        if (threadIdx.x == 0) nwords = 0;
+        __syncthreads();
+        if (lane == 0) atomicAdd(&nwords, (w + 3) / 4 * 64);
+        int pid = -1, np = 0;
+        for (;;) {
+            // (two sets of slots: round np + 1 writes the other while a late wavefront may still read this one)
+            const unsigned long long open = __ballot(pid < 0);
+            if (lane == 0) first[np & 1][wv] = open ? 64 * wv + __ffsll((long long)open) - 1 : 256;
+            __syncthreads();
+            const int L = min(min(first[np & 1][0], first[np & 1][1]), min(first[np & 1][2], first[np & 1][3]));
+            if (L == 256) break;
+            if (np == SELL_PMAX) {
+                np = SELL_PMAX + 1;
+                break;
+            }
+            if (threadIdx.x == 0) leaders[np] = L;
+            if (pid < 0) {
+                bool eq = true;
+#pragma unroll
+                for (int q = 0; q < 8; ++q) eq = eq && my[q] == ws[q][L];
+                if (eq) pid = np;
+            }
+            ++np;
+        }
+        const bool over = np > SELL_PMAX;
+        if (threadIdx.x == 0) {
+            if (over) {
+                pinfo[t] = -(int)atomicAdd(census, 1ull);
+            } else {
+                pinfo[t] = np;
+                ntile += 1;
+                nmax = max(nmax, (unsigned long long)np);
+                nw += nwords;
+            }
+        }
+        row_pat[(size_t)t * 256 + threadIdx.x] = over ? 0 : (unsigned char)pid;
+        if (threadIdx.x < SELL_PMAX * 8) {
+            const int p = threadIdx.x >> 3, q = threadIdx.x & 7;
+            tile_pat[(size_t)t * SELL_PMAX * 8 + threadIdx.x] = (!over && p < np) ? ws[q][leaders[p]] : 0u;
+        }
+        __syncthreads();      // (the tile's tables are read to the end before the next one's overwrite them)
+    }
+    if (threadIdx.x == 0 && ntile) {
+        atomicAdd(census + 1, ntile);
+        atomicMax(census + 2, nmax);
+        atomicAdd(census + 3, nw);
     }
 }
 
@@ -459,17 +542,20 @@ struct SellLeftover {
     const int *ntab;
     const unsigned *codes;
 };
-template <int MODE>
-__global__ __launch_bounds__(256) void sell_staged2_kernel(SellLeftover left, int nrows, int row0, int nblocks, int per_xcd, int stage_cap,
-                                                           int ncols, int wq, const unsigned *__restrict__ codesR,
-                                                           const int *__restrict__ tab, const double *__restrict__ vtab,
-                                                           const int *__restrict__ tile_desc, const int2 *__restrict__ tile_seg,
-                                                           const double *__restrict__ x, double *__restrict__ y,
-                                                           const double *__restrict__ b, const double *__restrict__ dinv,
-                                                           double scale, const double *__restrict__ xrow,
-                                                           const unsigned char *__restrict__ dcode = nullptr,
-                                                           const double *__restrict__ dtab = nullptr) {
-    extern __shared__ __align__(16) double lds[];
+// PAT: the tiles' row patterns (sell_staged2_kernel); without: every staged tile's code words (sell_staged2_codes_kernel,
+// options().sell bit 6).  Two kernels, not a run-time switch: the code words of the second are in flight across the staging,
+// and one body holding both would need 66 registers (seven workgroups per CU instead of eight).
+template <int MODE, bool PAT>
+__device__ __forceinline__ void sell_staged2(double *lds, const SellLeftover &left, int nrows, int row0, int nblocks, int per_xcd,
+                                             int stage_cap, int ncols, int wq, const unsigned *__restrict__ codesR,
+                                             const int *__restrict__ tab, const double *__restrict__ vtab,
+                                             const int *__restrict__ tile_desc, const int2 *__restrict__ tile_seg,
+                                             const double *__restrict__ x, double *__restrict__ y,
+                                             const double *__restrict__ b, const double *__restrict__ dinv,
+                                             double scale, const double *__restrict__ xrow,
+                                             const unsigned char *__restrict__ row_pat, const unsigned *__restrict__ tile_pat,
+                                             const int *__restrict__ tile_pinfo,
+                                             const unsigned char *__restrict__ dcode, const double *__restrict__ dtab) {
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if ((int)blockIdx.x >= left.grid_main) {      // (a trailing workgroup: one of the tiles that are not staged)
         const long lrow0 = (long)left.tiles[blockIdx.x - left.grid_main] * 256 - row0;      // the tile's first row, local to the range
@@ -481,15 +567,26 @@ __global__ __launch_bounds__(256) void sell_staged2_kernel(SellLeftover left, in
         return;
     }
     PairEntry *lt = (PairEntry *)(lds + stage_cap);
+    unsigned *pt = (unsigned *)(lt + 64);      // (row patterns: the tile's SELL_PMAX x 8 pattern words)
     const int blk = per_xcd > 0 ? (int)(blockIdx.x & 7u) * per_xcd + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
     if (blk >= nblocks || (long)blk * 256 + 256 > nrows) return;
     const long row = (long)blk * 256 + threadIdx.x;
     const int gtile = (row0 >> 8) + blk;
-    // every stream whose address the block index gives: requested before any descriptor is looked at
-    const unsigned *wp = codesR + ((size_t)gtile * wq) * 256 + threadIdx.x;
+    // every stream whose address the block index gives: requested before any descriptor is looked at.  With row patterns
+    // (DCsr::sell_row_pat) that is one byte per row and the tile's pattern table instead of the row's code words: 0.75 instead
+    // of 8 KB per tile for the 27-point stencil (whether the tile has patterns is known only from its descriptor: both are
+    // requested, and a tile without them reads its code words after the barrier)
     unsigned cws[8];
+    int pid = 0;
+    unsigned pw = 0u;
+    if (PAT) {
+        pid = __builtin_nontemporal_load(row_pat + (size_t)gtile * 256 + threadIdx.x);
+        if (threadIdx.x < SELL_PMAX * 8) pw = __builtin_nontemporal_load(tile_pat + (size_t)gtile * SELL_PMAX * 8 + threadIdx.x);
+    } else {
+        const unsigned *wp = codesR + ((size_t)gtile * wq) * 256 + threadIdx.x;
 #pragma unroll
-    for (int q = 0; q < 8; ++q) cws[q] = (q < wq) ? __builtin_nontemporal_load(wp + 256 * q) : 0u;
+        for (int q = 0; q < 8; ++q) cws[q] = (q < wq) ? __builtin_nontemporal_load(wp + 256 * q) : 0u;
+    }
     double e_b = 0.0, e_d = 0.0, e_x = 0.0;
     // (b and D^-1 are read once per application: streamed past the caches like the code words, so that the L2 keeps x)
     if (MODE == MODE_RESIDUAL) e_b = __builtin_nontemporal_load(b + row);
@@ -504,6 +601,7 @@ __global__ __launch_bounds__(256) void sell_staged2_kernel(SellLeftover left, in
         myval = vtab[(size_t)gtile * 256 + lane];
     }
     const int desc = tile_desc[gtile];
+    const int pinfo = PAT ? tile_pinfo[gtile] : 0;
     const int nseg = desc & 127;
     if (nseg == 0) return;      // (left to sell_tiles_kernel)
     const int w = __builtin_amdgcn_readfirstlane((desc >> (8 + 6 * wv)) & 63);
@@ -566,9 +664,19 @@ __global__ __launch_bounds__(256) void sell_staged2_kernel(SellLeftover left, in
     if (desc & 128) stage(std::false_type());
     else stage(std::true_type());
     if (wv == 0) lt[lane] = PairEntry{(mybase + mytab) << 3, 0, myval};
+    if (PAT && threadIdx.x < SELL_PMAX * 8) pt[threadIdx.x] = pw;
     if (MODE == MODE_SMOOTH && zbase < 0) e_x = xrow[row];      // (no segment holds the own rows: an operator without a diagonal run)
     __syncthreads();
     if (MODE == MODE_SMOOTH && zbase >= 0) e_x = lds[zbase + threadIdx.x];
+    if (PAT && pinfo > 0) {
+        const uint4 c0 = *(const uint4 *)(pt + 8 * pid), c1 = *(const uint4 *)(pt + 8 * pid + 4);
+        cws[0] = c0.x; cws[1] = c0.y; cws[2] = c0.z; cws[3] = c0.w;
+        cws[4] = c1.x; cws[5] = c1.y; cws[6] = c1.z; cws[7] = c1.w;
+    } else if (PAT) {      // (more than SELL_PMAX patterns: the tile's code words, at its slot)
+        const unsigned *wp = codesR + ((size_t)(-pinfo) * wq) * 256 + threadIdx.x;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) cws[q] = (q < wq) ? __builtin_nontemporal_load(wp + 256 * q) : 0u;
+    }
     const char *lb = (const char *)lds + 8 * (lane + 64 * wv);
     double s0 = 0.0, s1 = 0.0;
 #pragma unroll
@@ -602,6 +710,28 @@ __global__ __launch_bounds__(256) void sell_staged2_kernel(SellLeftover left, in
         y[row] = e_x + scale * (e_d * (sum - e_b));
     }
 }
+#define SA_STAGED2_PARAMS                                                                                                         \
+    SellLeftover left, int nrows, int row0, int nblocks, int per_xcd, int stage_cap, int ncols, int wq,                           \
+        const unsigned *__restrict__ codesR, const int *__restrict__ tab, const double *__restrict__ vtab,                        \
+        const int *__restrict__ tile_desc, const int2 *__restrict__ tile_seg, const double *__restrict__ x, double *__restrict__ y, \
+        const double *__restrict__ b, const double *__restrict__ dinv, double scale, const double *__restrict__ xrow,             \
+        const unsigned char *__restrict__ row_pat, const unsigned *__restrict__ tile_pat, const int *__restrict__ tile_pinfo,     \
+        const unsigned char *__restrict__ dcode, const double *__restrict__ dtab
+#define SA_STAGED2_ARGS                                                                                                           \
+    lds, left, nrows, row0, nblocks, per_xcd, stage_cap, ncols, wq, codesR, tab, vtab, tile_desc, tile_seg, x, y, b, dinv, scale, \
+        xrow, row_pat, tile_pat, tile_pinfo, dcode, dtab
+template <int MODE>
+__global__ __launch_bounds__(256) void sell_staged2_kernel(SA_STAGED2_PARAMS) {
+    extern __shared__ __align__(16) double lds[];
+    sell_staged2<MODE, true>(SA_STAGED2_ARGS);
+}
+template <int MODE>
+__global__ __launch_bounds__(256) void sell_staged2_codes_kernel(SA_STAGED2_PARAMS) {
+    extern __shared__ __align__(16) double lds[];
+    sell_staged2<MODE, false>(SA_STAGED2_ARGS);
+}
+#undef SA_STAGED2_PARAMS
+#undef SA_STAGED2_ARGS
 
 // The tiles the staged kernel leaves out, from the list the staging plan made (ids of the whole operator; those
 // outside the row range are skipped), one workgroup per tile through sell_slice.
@@ -1492,17 +1622,43 @@ void build_sell(hipStream_t s, DCsr &A) {
         A.sell_stream_bytes += (4.0 + 8.0 * SELL_SEG_MAX) * ntiles;
         // the regular second copy of the staged tiles' code words + one descriptor word per tile (sell_staged2_kernel)
         A.sell_wq = 0;
+        A.sell_row_pat.release();
+        A.sell_tile_pat.release();
+        A.sell_tile_pinfo.release();
+        A.sell_pat_tiles = A.sell_pat_max = 0;
         if (A.sell_stage_cap > 0 && A.sell_one_table) {
             A.sell_wq = (int)std::min<unsigned long long>(8, (h[7] + 3) / 4);      // (h[7]: the widest slice; staged ones are <= 32)
-            A.sell_codeR.alloc((size_t)ntiles * A.sell_wq * 256);
             A.sell_tile_desc.alloc((size_t)ntiles);
+            // row patterns (bit 6 set: none, every staged tile keeps its code words)
+            int nslots = ntiles;
+            if (!(options().sell & 64)) {
+                A.sell_row_pat.alloc((size_t)ntiles * 256);
+                A.sell_tile_pat.alloc((size_t)ntiles * SELL_PMAX * 8);
+                A.sell_tile_pinfo.alloc((size_t)ntiles);
+                DBuf<unsigned long long> census(4);
+                census.zero(s);
+                hipLaunchKernelGGL(sell_row_patterns_kernel, dim3(std::min(ntiles, 2048)), dim3(256), 0, s, ntiles, A.sell_wq, A.sell_ptr.p, A.sell_tile_nseg.p,
+                                   A.sell_code.p, A.sell_row_pat.p, A.sell_tile_pat.p, A.sell_tile_pinfo.p, census.p);
+                SA_HIP_CHECK(hipGetLastError());
+                unsigned long long hc[4];
+                SA_HIP_CHECK(hipMemcpyAsync(hc, census.p, sizeof(hc), hipMemcpyDeviceToHost, s));
+                SA_HIP_CHECK(hipStreamSynchronize(s));
+                nslots = (int)hc[0];
+                A.sell_pat_tiles = (int)hc[1];
+                A.sell_pat_max = (int)hc[2];
+                // every staged tile reads a byte per row, the pattern table and its count; the pattern tiles no code words
+                A.sell_stream_bytes += (256.0 + 4.0 * SELL_PMAX * 8 + 4.0) * staged_tiles - 4.0 * (double)hc[3];
+            }
+            A.sell_codeR.alloc((size_t)nslots * A.sell_wq * 256);
             hipLaunchKernelGGL(sell_regular_codes_kernel, dim3(ntiles), dim3(256), 0, s, ntiles, A.sell_wq, A.ncols, A.sell_ptr.p,
-                               A.sell_tile_nseg.p, A.sell_tile_seg.p, A.sell_code.p, A.sell_codeR.p, A.sell_tile_desc.p);
+                               A.sell_tile_nseg.p, A.sell_tile_seg.p, A.sell_code.p, A.sell_tile_pinfo.p, A.sell_codeR.p,
+                               A.sell_tile_desc.p);
             SA_HIP_CHECK(hipGetLastError());
         }
     }
     if ((options().debug & 2))
-        std::fprintf(stderr, "build_sell: staging plan: %d of %d tiles, largest %d doubles\n", staged_tiles, div_up(A.nslices, 4), A.sell_stage_cap);
+        std::fprintf(stderr, "build_sell: staging plan: %d of %d tiles, largest %d doubles, row patterns in %d tiles (at most %d)\n",
+                     staged_tiles, div_up(A.nslices, 4), A.sell_stage_cap, A.sell_pat_tiles, A.sell_pat_max);
     if ((options().debug & 2))
         std::fprintf(stderr, "build_sell: %d rows, slices pair/offset/plain %lld/%lld/%lld, widest %llu, stream bytes %.0f, fast path %d\n",
                      A.nrows, (long long)h[0], (long long)h[1], (long long)h[2], h[7], A.sell_stream_bytes, (int)A.sell_fast_ok);
@@ -1561,16 +1717,19 @@ static void launch_spmv(hipStream_t s, const DCsr &A, RowRange rr, const double 
         const int nblocks = div_up((long)div_up(nrows, 64) * 64, 256);
         constexpr bool no_xcd = false;
         const int per_xcd = no_xcd ? 0 : div_up(nblocks, 8);
-        const size_t lds_bytes = 8 * (size_t)A.sell_stage_cap + (A.sell_one_table ? 1 : 4) * 64 * sizeof(PairEntry);
+        const size_t lds_bytes = 8 * (size_t)A.sell_stage_cap + (A.sell_one_table ? 1 : 4) * 64 * sizeof(PairEntry) +
+                                 (A.sell_row_pat.p ? SELL_PMAX * 8 * sizeof(unsigned) : 0);
         // (up to eight tiles that are not staged ride at the end of the staged kernel's grid instead of a launch of their own)
         const int grid_main = no_xcd ? nblocks : per_xcd * 8;
         const bool fold = A.sell_wq > 0 && A.sell_nunstaged > 0 && A.sell_nunstaged <= 8 && 8 * (size_t)A.sell_stage_cap >= 4 * 64 * sizeof(PairEntry);
         if (A.sell_wq > 0) {
             const SellLeftover left{grid_main, fold ? A.sell_nunstaged : 0, A.sell_unstaged.p, A.sell_ptr.p + row0 / 64, A.sell_col.p, A.sell_val.p,
                                     A.sell_ntab.p, A.sell_code.p};
-            hipLaunchKernelGGL((sell_staged2_kernel<MODE>), dim3(grid_main + left.n), dim3(256), lds_bytes, s, left, nrows, row0,
+            auto kern = A.sell_row_pat.p ? sell_staged2_kernel<MODE> : sell_staged2_codes_kernel<MODE>;
+            hipLaunchKernelGGL(kern, dim3(grid_main + left.n), dim3(256), lds_bytes, s, left, nrows, row0,
                                nblocks, per_xcd, A.sell_stage_cap, A.ncols, A.sell_wq, A.sell_codeR.p, A.sell_tab.p, A.sell_vtab.p,
-                               A.sell_tile_desc.p, A.sell_tile_seg.p, x, y, b, dinv, scale, xrow, dcode, (const double *)A.sell_dtab.p);
+                               A.sell_tile_desc.p, A.sell_tile_seg.p, x, y, b, dinv, scale, xrow, A.sell_row_pat.p, A.sell_tile_pat.p,
+                               A.sell_tile_pinfo.p, dcode, (const double *)A.sell_dtab.p);
         } else
         hipLaunchKernelGGL((sell_staged_kernel<MODE>), dim3(no_xcd ? nblocks : per_xcd * 8), dim3(256), lds_bytes, s, nrows, row0,
                            nblocks, per_xcd, A.sell_stage_cap, A.ncols, (int)A.sell_one_table, A.sell_ptr.p + row0 / 64, A.sell_ntab.p, A.sell_tab.p,
