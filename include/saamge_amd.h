@@ -388,6 +388,44 @@ int saamge_amd_profile_get(int i, char *name, int name_len, double *ms, long lon
 int saamge_amd_profile_get2(int i, char *name, int name_len, double *ms, long long *launches, double *bytes, double *flops,
                             double *fmt_bytes);
 
+/* ---- agglomerate partitions built on the device -----------------------------------------------------------------------
+ * The entry points above take partitions[k] / nparts[k] from the caller.  These calls make them: deterministic, every part
+ * connected, none empty, numbered by smallest member.  elems_per_agg is a target; the number of parts produced is returned.
+ * The algorithm (seeded level-synchronous growth, recentring, size repair) is defined by saamge_amd/partition_model.py and
+ * the device gives the same integers.  Arrays may be host or device pointers, each on its own, with
+ * one exception: host columns (adj) need host offsets (xadj), which say how much to copy.  An element that lists a dof
+ * twice is refused.  Parts above max_size are split in at most 32 rounds (enough for meshes by a wide margin; a hub with
+ * thousands of leaves may keep a part above the cap). */
+typedef struct saamge_amd_partition_options {
+    int min_shared;      /* 1: dofs two elements share to be adjacent (1 vertex neighbours, 4 faces of Q1 hexes); mesh entry */
+    int lloyd_iters;     /* 0: recentring passes */
+    int max_size;        /* -1: 2 * elems_per_agg; 0: no cap */
+    int min_size;        /* -1: elems_per_agg / 4; 0: small parts are left alone */
+    unsigned seed;       /* 0 */
+} saamge_amd_partition_options;
+void saamge_amd_partition_options_default(saamge_amd_partition_options *o);
+
+/* One level: a symmetric CSR graph (self-loops are ignored) -> part[n], *nparts_out.  o == NULL: the defaults.  Offsets that
+ * do not ascend from 0, columns outside [0, n) and entries without their transpose are refused. */
+int saamge_amd_partition_graph(int n, const long long *xadj, const int *adj, int elems_per_agg,
+                               const saamge_amd_partition_options *o, void *stream, int *part, int *nparts_out);
+
+/* All levels from the mesh.  elem_ptr == NULL: every element has nde dofs.  elems_per_agg has num_coarsenings entries.
+ * Level k partitions graph k: graph 0 is the element graph, graph k + 1 the quotient graph of level k. */
+typedef struct saamge_amd_partitioning saamge_amd_partitioning;
+int saamge_amd_partition_mesh(int NE, int nde, const int *elem_ptr, const int *elem_to_dof, int ND, int num_coarsenings,
+                              const int *elems_per_agg, const saamge_amd_partition_options *o, void *stream,
+                              saamge_amd_partitioning **out);
+/* Pointers that can be handed to saamge_amd_ml_produce_data* as partitions / nparts; they live as long as the handle.
+ * on_host = 0: device arrays, 1: host copies. */
+int saamge_amd_partitioning_arrays(const saamge_amd_partitioning *p, int on_host, const int *const **partitions,
+                                   const int **nparts_host);
+int saamge_amd_partitioning_get(const saamge_amd_partitioning *p, int level, int *part_host, int *n_elem, int *nparts);
+/* graph `level` (0 .. num_coarsenings); NULL arrays: sizes only.  A getter: copies with a blocking hipMemcpy, on no stream. */
+int saamge_amd_partitioning_graph(const saamge_amd_partitioning *p, int level, long long *xadj, int *adj, int *n,
+                                  long long *nnz);
+void saamge_amd_partitioning_free(saamge_amd_partitioning *p);
+
 #ifdef __cplusplus
 }
 #endif

@@ -162,6 +162,50 @@ inline int kalchev_pcg(ml_data_t *h, const double *b, double *x, int print_iter 
     return conv ? iters : -iters;
 }
 
+// == agglomerate partitions built on the device (saamge_amd_partition_graph / saamge_amd_partition_mesh) ==
+// One level on a symmetric CSR graph (host or device arrays): part is resized to n; returns the number of parts produced
+// (elems_per_agg is a target).  o == nullptr: the library's defaults.
+inline int partition_graph(int n, const long long *xadj, const int *adj, int elems_per_agg, std::vector<int> &part,
+                           const saamge_amd_partition_options *o = nullptr, void *stream = nullptr) {
+    part.assign((size_t)(n > 0 ? n : 0), 0);
+    int nparts = 0;
+    if (saamge_amd_partition_graph(n, xadj, adj, elems_per_agg, o, stream, part.data(), &nparts))
+        throw std::runtime_error(saamge_amd_last_error());
+    return nparts;
+}
+// All levels from a mesh, as host vectors: partitions[k] / nparts[k] for ProblemArrays::partitions and
+// MultilevelParameters' nparts_arr.  elem_ptr == nullptr: every element has nde dofs.
+struct MeshPartitions {
+    std::vector<std::vector<int> > partitions;
+    std::vector<int> nparts;
+    std::vector<const int *> pointers() const {
+        std::vector<const int *> p;
+        for (size_t k = 0; k < partitions.size(); ++k) p.push_back(partitions[k].data());
+        return p;
+    }
+};
+inline MeshPartitions partition_mesh(int NE, int nde, const int *elem_ptr, const int *elem_to_dof, int ND,
+                                     const std::vector<int> &elems_per_agg, const saamge_amd_partition_options *o = nullptr,
+                                     void *stream = nullptr) {
+    saamge_amd_partitioning *P = nullptr;
+    if (saamge_amd_partition_mesh(NE, nde, elem_ptr, elem_to_dof, ND, (int)elems_per_agg.size(), elems_per_agg.data(), o, stream, &P))
+        throw std::runtime_error(saamge_amd_last_error());
+    MeshPartitions out;
+    for (int k = 0; k < (int)elems_per_agg.size(); ++k) {
+        int n_elem = 0, np = 0;
+        int rc = saamge_amd_partitioning_get(P, k, nullptr, &n_elem, &np);
+        out.partitions.push_back(std::vector<int>((size_t)n_elem));
+        if (!rc) rc = saamge_amd_partitioning_get(P, k, out.partitions.back().data(), nullptr, nullptr);
+        if (rc) {
+            saamge_amd_partitioning_free(P);
+            throw std::runtime_error(saamge_amd_last_error());
+        }
+        out.nparts.push_back(np);
+    }
+    saamge_amd_partitioning_free(P);
+    return out;
+}
+
 }  // namespace api
 }  // namespace saamge_amd
 

@@ -211,7 +211,19 @@ inline ml_partitioner_t &ml_coarse_partitioner() {
     };
     return p;
 }
-inline void ml_set_coarse_partitioner(const ml_partitioner_t &p) { ml_coarse_partitioner() = p; }
+namespace detail {
+// true while a hook that returns its own number of parts (ml_device_partitioner) is installed: [0] fine, [1] coarse
+inline bool *partitioner_counts() {
+    static bool f[2] = {false, false};
+    return f;
+}
+inline int count_parts(const int *partition, int n) {
+    int m = -1;
+    for (int e = 0; e < n; ++e) m = partition[e] > m ? partition[e] : m;
+    return m + 1;
+}
+}  // namespace detail
+inline void ml_set_coarse_partitioner(const ml_partitioner_t &p) { ml_coarse_partitioner() = p; detail::partitioner_counts()[1] = false; }
 // Fine partition for the entry points that derive it themselves in the reference (SpectralAMGSolver ->
 // fem_create_partitioning -> METIS, src/solve.cpp:185-187, src/part.cpp:170-183): partition(level 0, NE, nparts,
 // elem_to_elem, out[NE]).  Default: contiguous element ranges.
@@ -221,7 +233,37 @@ inline ml_partitioner_t &ml_fine_partitioner() {
     };
     return p;
 }
-inline void ml_set_fine_partitioner(const ml_partitioner_t &p) { ml_fine_partitioner() = p; }
+inline void ml_set_fine_partitioner(const ml_partitioner_t &p) { ml_fine_partitioner() = p; detail::partitioner_counts()[0] = false; }
+
+// Partitions made on the device by saamge_amd_partition_graph: connected agglomerates on any numbering, where the defaults
+// above cut index ranges.  elem_to_elem is used as the CSR graph it is; the hook's nparts is a TARGET
+// (elems_per_agg = ceil(n_elem / nparts)) and the number of parts produced may differ, as after the reference's
+// connected-components pass (src/part.cpp:193-197).  Installed through the overloads below, the adaptor takes the number
+// of agglomerates of that level from max(partition) + 1 instead of MultilevelParameters::get_nparts.
+struct ml_device_partitioner_t {
+    saamge_amd_partition_options options;
+    void operator()(int, int n_elem, int nparts, const mfem::Table &elem_to_elem, int *partition) const {
+        if (n_elem <= 0) return;
+        const int target = nparts < 1 ? 1 : nparts;
+        const int epa = (int)(((long long)n_elem + target - 1) / target);
+        std::vector<long long> xadj((size_t)n_elem + 1, 0);
+        const bool has_graph = elem_to_elem.Size() >= n_elem;
+        if (has_graph)
+            for (int e = 0; e <= n_elem; ++e) xadj[(size_t)e] = elem_to_elem.GetI()[e];
+        int produced = 0;
+        if (saamge_amd_partition_graph(n_elem, xadj.data(), has_graph ? elem_to_elem.GetJ() : nullptr, epa, &options, nullptr,
+                                       partition, &produced))
+            mfem::mfem_error(saamge_amd_last_error());
+    }
+};
+inline ml_device_partitioner_t ml_device_partitioner(const saamge_amd_partition_options *options = nullptr) {
+    ml_device_partitioner_t p;
+    if (options) p.options = *options;
+    else saamge_amd_partition_options_default(&p.options);
+    return p;
+}
+inline void ml_set_coarse_partitioner(const ml_device_partitioner_t &p) { ml_coarse_partitioner() = p; detail::partitioner_counts()[1] = true; }
+inline void ml_set_fine_partitioner(const ml_device_partitioner_t &p) { ml_fine_partitioner() = p; detail::partitioner_counts()[0] = true; }
 
 namespace detail {
 
@@ -441,10 +483,15 @@ inline ml_data_t *ml_produce_data(mfem::HypreParMatrix &Ag, agg_partitioning_rel
     std::vector<std::vector<int> > parts((size_t)nco);
     std::vector<const int *> part_ptrs((size_t)nco);
     parts[0].assign(r.partitioning, r.partitioning + NE);
+    // agglomerates per level: the parameters' numbers, or what a partitioner that counts for itself produced
+    std::vector<int> nparts((size_t)nco);
+    for (int k = 0; k < nco; ++k) nparts[(size_t)k] = mlp.get_nparts(k);
+    const bool counted = detail::partitioner_counts()[1];
+    if (detail::partitioner_counts()[0]) nparts[0] = detail::count_parts(r.partitioning, NE);
     mfem::Table *e2e = r.elem_to_elem;
     std::vector<mfem::Table *> owned;
     for (int k = 1; k < nco; ++k) {
-        const int n_el_prev = (int)parts[(size_t)k - 1].size(), n_el = mlp.get_nparts(k - 1);
+        const int n_el_prev = (int)parts[(size_t)k - 1].size(), n_el = nparts[(size_t)k - 1];
         mfem::Table e2AE;                                  // element -> AE of level k-1
         e2AE.MakeI(n_el_prev);
         for (int e = 0; e < n_el_prev; ++e) e2AE.AddAColumnInRow(e);
@@ -464,14 +511,13 @@ inline ml_data_t *ml_produce_data(mfem::HypreParMatrix &Ag, agg_partitioning_rel
         owned.push_back(next);
         parts[(size_t)k].resize((size_t)n_el);
         ml_coarse_partitioner()(k, n_el, mlp.get_nparts(k), *next, parts[(size_t)k].data());
+        if (counted) nparts[(size_t)k] = detail::count_parts(parts[(size_t)k].data(), n_el);
         e2e = next;
     }
     for (size_t i = 0; i < owned.size(); ++i) delete owned[i];
     for (int k = 0; k < nco; ++k) part_ptrs[(size_t)k] = parts[(size_t)k].data();
     saamge_amd_params p = mlp.p;
     p.testmesh = r.testmesh ? 1 : 0;
-    std::vector<int> nparts((size_t)nco);
-    for (int k = 0; k < nco; ++k) nparts[(size_t)k] = mlp.get_nparts(k);
     saamge_amd_hierarchy *h = nullptr;
     detail::DistLayout *layout = nullptr;
     if (!distributed) {
@@ -842,6 +888,7 @@ public:
         if (nparts0 < 1) nparts0 = 1;
         int *partitioning = new int[NE];
         ml_fine_partitioner()(0, NE, nparts0, *e2e, partitioning);
+        if (detail::partitioner_counts()[0]) nparts0 = detail::count_parts(partitioning, NE);
         build(aform, Alocal, bdr.data(), e2d, e2e, partitioning, nparts0, elems_per_agg, num_levels, nu_pro, nu_relax, theta,
               polynomial_coarse, coarse_direct);
     }

@@ -30,6 +30,9 @@ SYMBOLS = [
     "saamge_amd_ml_produce_data_parcsr", "saamge_amd_memory_stats", "saamge_amd_pool_counts",
     "saamge_amd_options_default", "saamge_amd_set_options", "saamge_amd_get_options",
     "saamge_amd_ml_produce_data_mixed", "saamge_amd_ml_produce_data_mixed64",
+    "saamge_amd_partition_options_default", "saamge_amd_partition_graph", "saamge_amd_partition_mesh",
+    "saamge_amd_partitioning_arrays", "saamge_amd_partitioning_get", "saamge_amd_partitioning_graph",
+    "saamge_amd_partitioning_free",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong))
@@ -279,6 +282,30 @@ class Hierarchy(object):
         nparts = [int(p.max()) + 1 for p in parts]
         return cls(rowptr, col, val, A.shape[0], e2d, elmat, bdr, parts, nparts, params, len(eptr) - 1, 0,
                    stream, group, dist_solve, elem_ptr=eptr)
+
+    @classmethod
+    def from_partitioning(cls, prob, params, partitioning, on_host=False, stream=0):
+        """from_problem with the partitions of a `Partitioning` (partition_mesh) in place of prob.partitions: its device
+        arrays (on_host=False) or its host copies go to the entry point as they are."""
+        A = prob.A.tocsr()
+        rowptr = np.ascontiguousarray(A.indptr, dtype=np.int32)
+        col = np.ascontiguousarray(A.indices, dtype=np.int32)
+        val = np.ascontiguousarray(A.data, dtype=np.float64)
+        e2d = np.ascontiguousarray(prob.elem_to_dof, dtype=np.int32)
+        elmat = np.ascontiguousarray(prob.elmat, dtype=np.float64)
+        bdr = np.ascontiguousarray(prob.bdr, dtype=np.int8) if prob.bdr is not None else None
+        nc = params.num_coarsenings
+        parts = partitioning.pointers(on_host)[:nc]
+        nparts = partitioning.nparts[:nc]
+        eptr = getattr(prob, "elem_ptr", None)
+        if eptr is not None:
+            eptr = np.ascontiguousarray(eptr, dtype=np.int32)
+            h = cls(rowptr, col, val, A.shape[0], e2d, elmat, bdr, parts, nparts, params, len(eptr) - 1, 0, stream,
+                    elem_ptr=eptr)
+        else:
+            h = cls(rowptr, col, val, A.shape[0], e2d, elmat, bdr, parts, nparts, params, e2d.shape[0], e2d.shape[1], stream)
+        h._keep = h._keep + (partitioning,)
+        return h
 
     @classmethod
     def from_parcsr(cls, piece, params, stream=0, group=None, dist_solve=True):
@@ -601,6 +628,101 @@ def reset_options():
     o = Options()
     load().saamge_amd_options_default(C.byref(o))
     load().saamge_amd_set_options(C.byref(o))
+
+
+class PartitionOptions(C.Structure):      # saamge_amd_partition_options
+    _fields_ = [("min_shared", C.c_int), ("lloyd_iters", C.c_int), ("max_size", C.c_int), ("min_size", C.c_int),
+                ("seed", C.c_uint)]
+
+
+def partition_options(**kw):
+    """The library's defaults with the given fields replaced."""
+    o = PartitionOptions()
+    load().saamge_amd_partition_options_default(C.byref(o))
+    for k, v in kw.items():
+        if k not in dict(PartitionOptions._fields_):
+            raise KeyError(k)
+        setattr(o, k, int(v))
+    return o
+
+
+def partition_graph(n, xadj, adj, elems_per_agg, part=None, stream=0, **opts):
+    """saamge_amd_partition_graph.  xadj (int64) / adj (int32): numpy arrays or device tensors.  part: None (a numpy array
+    is returned) or a device tensor of n int32 that receives the partition.  Returns (part, nparts)."""
+    o = partition_options(**opts)
+    if part is None:
+        part = np.zeros(max(int(n), 1), np.int32)[:int(n)]
+    npt = C.c_int(0)
+    _check(load().saamge_amd_partition_graph(C.c_int(int(n)), _ptr(xadj), _ptr(adj), C.c_int(int(elems_per_agg)), C.byref(o),
+                                             C.c_void_p(stream), _ptr(part), C.byref(npt)))
+    return part, int(npt.value)
+
+
+class Partitioning(object):
+    """saamge_amd_partition_mesh: the partitions of every coarsening, owned by the library until close()."""
+
+    def __init__(self, elem_to_dof, ND, elems_per_agg, elem_ptr=None, nde=0, NE=None, stream=0, **opts):
+        o = partition_options(**opts)
+        if NE is None:
+            NE = len(elem_ptr) - 1 if elem_ptr is not None else int(elem_to_dof.shape[0])
+        if elem_ptr is None and not nde:
+            nde = int(elem_to_dof.shape[1])
+        epa = (C.c_int * len(elems_per_agg))(*[int(x) for x in elems_per_agg])
+        h = C.c_void_p()
+        _check(load().saamge_amd_partition_mesh(C.c_int(int(NE)), C.c_int(int(nde)), _ptr(elem_ptr), _ptr(elem_to_dof),
+                                                C.c_int(int(ND)), C.c_int(len(elems_per_agg)), epa, C.byref(o),
+                                                C.c_void_p(stream), C.byref(h)))
+        self.h = h
+        self.num_coarsenings = len(elems_per_agg)
+        self.nparts, self.n_elem = [], []
+        for k in range(self.num_coarsenings):
+            ne, npt = C.c_int(0), C.c_int(0)
+            _check(load().saamge_amd_partitioning_get(self.h, C.c_int(k), None, C.byref(ne), C.byref(npt)))
+            self.n_elem.append(int(ne.value))
+            self.nparts.append(int(npt.value))
+
+    def pointers(self, on_host=False):
+        """Raw addresses of the partition arrays (device, or the handle's host copies), one per coarsening."""
+        pp = C.POINTER(C.c_void_p)()
+        _check(load().saamge_amd_partitioning_arrays(self.h, C.c_int(int(on_host)), C.byref(pp), None))
+        return [int(pp[k] or 0) for k in range(self.num_coarsenings)]
+
+    def part(self, level):
+        out = np.zeros(max(self.n_elem[level], 1), np.int32)[:self.n_elem[level]]
+        _check(load().saamge_amd_partitioning_get(self.h, C.c_int(level), _ptr(out), None, None))
+        return out
+
+    def graph(self, level, device=False):
+        """(xadj int64, adj int32) of graph `level` (0: elements, k: the quotient graph of level k - 1): numpy arrays, or
+        torch tensors on the GPU with device=True."""
+        n, nnz = C.c_int(0), C.c_longlong(0)
+        _check(load().saamge_amd_partitioning_graph(self.h, C.c_int(level), None, None, C.byref(n), C.byref(nnz)))
+        if device:
+            import torch
+            xadj = torch.zeros(n.value + 1, dtype=torch.int64, device="cuda")
+            adj = torch.zeros(int(nnz.value), dtype=torch.int32, device="cuda")
+        else:
+            xadj = np.zeros(n.value + 1, np.int64)
+            adj = np.zeros(max(int(nnz.value), 1), np.int32)[:int(nnz.value)]
+        _check(load().saamge_amd_partitioning_graph(self.h, C.c_int(level), _ptr(xadj), _ptr(adj), None, None))
+        return xadj, adj
+
+    def close(self):
+        if self.h is not None and self.h.value:
+            free = load().saamge_amd_partitioning_free
+            free.restype = None
+            free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def partition_mesh(elem_to_dof, ND, elems_per_agg, elem_ptr=None, **kw):
+    return Partitioning(elem_to_dof, ND, elems_per_agg, elem_ptr=elem_ptr, **kw)
 
 
 def pool_counts(reset=False):

@@ -5,11 +5,24 @@
 #include <string>
 
 #include "hierarchy.h"
+#include "partition.h"
 
 using namespace saamge_amd;
 
 struct saamge_amd_hierarchy {
     Hierarchy *H;
+};
+
+// saamge_amd_partition_mesh: level k partitions graph k; graph num_levels is the quotient graph of the last level
+struct saamge_amd_partitioning {
+    int device = 0;
+    std::vector<DBuf<int>> part;             // device
+    std::vector<std::vector<int>> part_host;
+    std::vector<const int *> part_ptr, part_host_ptr;
+    std::vector<int> n_elem, nparts;
+    std::vector<DBuf<roff_t>> xadj;
+    std::vector<DBuf<int>> adj;
+    std::vector<int64_t> nnz;
 };
 
 static std::string g_last_error;
@@ -705,5 +718,148 @@ int saamge_amd_profile_get2(int i, char *name, int name_len, double *ms, long lo
     if (fmt_bytes) *fmt_bytes = profiler().stats[i].fmt_bytes;
     return 0;
 }
+
+// ---- partitions from a graph / a mesh (partition.hip) ------------------------------------------------------------------
+static PartitionOptions convert_partition_options(const saamge_amd_partition_options *o) {
+    PartitionOptions p;
+    if (o) { p.min_shared = o->min_shared; p.lloyd_iters = o->lloyd_iters; p.max_size = o->max_size; p.min_size = o->min_size; p.seed = o->seed; }
+    return p;
+}
+
+void saamge_amd_partition_options_default(saamge_amd_partition_options *o) {
+    const PartitionOptions p;
+    o->min_shared = p.min_shared; o->lloyd_iters = p.lloyd_iters; o->max_size = p.max_size; o->min_size = p.min_size; o->seed = p.seed;
+}
+
+int saamge_amd_partition_graph(int n, const long long *xadj, const int *adj, int elems_per_agg,
+                               const saamge_amd_partition_options *o, void *stream, int *part, int *nparts_out) {
+    SA_API_BEGIN
+    SA_REQUIRE(n >= 0, "n < 0");
+    SA_REQUIRE(elems_per_agg >= 1, "elems_per_agg < 1");
+    SA_REQUIRE(xadj && nparts_out && (n == 0 || part), "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    {
+        DBuf<roff_t> dx;
+        DBuf<int> da, dp;
+        import_array(dx, (const roff_t *)xadj, (size_t)n + 1, s);
+        if (!is_device_ptr(adj)) {      // host columns: the offsets are checked before they say how much to copy
+            const bool xh = !is_device_ptr(xadj);
+            if (xh) for (int i = 0; i < n; ++i) SA_REQUIRE(xadj[0] == 0 && xadj[i + 1] >= xadj[i], "xadj: must start at 0 and ascend");
+            const roff_t nnz = n == 0 ? 0 : (xh ? (roff_t)xadj[n] : 0);
+            SA_REQUIRE(xh || n == 0, "xadj on the device with adj on the host");
+            SA_REQUIRE(nnz == 0 || adj, "null argument: adj");
+            da.assign(adj, (size_t)nnz, s);
+        } else {
+            da.view(const_cast<int *>(adj), 0);
+        }
+        check_graph_device(s, n, dx.p, da.p);
+        if (is_device_ptr(part)) dp.view(part, (size_t)n);
+        else dp.alloc((size_t)n);
+        partition_graph_device(s, n, dx.p, da.p, elems_per_agg, convert_partition_options(o), dp.p, nparts_out);
+        if (n && !is_device_ptr(part)) SA_HIP_CHECK(hipMemcpyAsync(part, dp.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+        SA_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    SA_API_END
+}
+
+int saamge_amd_partition_mesh(int NE, int nde, const int *elem_ptr, const int *elem_to_dof, int ND, int num_coarsenings,
+                              const int *elems_per_agg, const saamge_amd_partition_options *o, void *stream,
+                              saamge_amd_partitioning **out) {
+    SA_API_BEGIN
+    SA_REQUIRE(out && elems_per_agg && (NE == 0 || elem_to_dof), "null argument");
+    SA_REQUIRE(NE >= 0 && ND >= 0, "NE < 0 or ND < 0");
+    SA_REQUIRE(elem_ptr || nde >= 1, "elem_ptr or a uniform nde >= 1 is needed");
+    SA_REQUIRE(num_coarsenings >= 1 && num_coarsenings < SAAMGE_AMD_MAX_LEVELS, "num_coarsenings out of range");
+    for (int k = 0; k < num_coarsenings; ++k) SA_REQUIRE(elems_per_agg[k] >= 1, "elems_per_agg < 1");
+    const PartitionOptions po = convert_partition_options(o);
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    std::unique_ptr<saamge_amd_partitioning> P(new saamge_amd_partitioning);
+    P->device = current_device();
+    {
+        DBuf<int> eI, eJ;
+        if (elem_ptr) {
+            import_array(eI, elem_ptr, (size_t)NE + 1, s);
+        } else {
+            SA_REQUIRE((int64_t)NE * nde < INT_MAX, "NE * nde beyond 32 bits");
+            std::vector<int> h((size_t)NE + 1);
+            for (int e = 0; e <= NE; ++e) h[(size_t)e] = e * nde;
+            eI.from_host(h, s);
+        }
+        if (!is_device_ptr(elem_to_dof) && NE) {   // the offsets say how much to copy: checked first
+            const auto hI = eI.to_host(s);
+            for (int e = 0; e < NE; ++e) SA_REQUIRE(hI[0] == 0 && hI[(size_t)e + 1] > hI[(size_t)e], "elem_ptr: must start at 0 and every element needs a dof");
+            eJ.assign(elem_to_dof, (size_t)hI[(size_t)NE], s);
+        } else {
+            eJ.view(const_cast<int *>(elem_to_dof), 0);
+        }
+        check_mesh_device(s, NE, eI.p, eJ.p, ND);
+        P->xadj.emplace_back();
+        P->adj.emplace_back();
+        element_graph_device(s, NE, eI.p, eJ.p, ND, po.min_shared, P->xadj[0], P->adj[0]);
+        SA_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    int n = NE;
+    for (int k = 0; k < num_coarsenings; ++k) {
+        P->part.emplace_back((size_t)n);
+        int np = 0;
+        partition_graph_device(s, n, P->xadj[(size_t)k].p, P->adj[(size_t)k].p, elems_per_agg[k], po, P->part.back().p, &np);
+        P->n_elem.push_back(n);
+        P->nparts.push_back(np);
+        std::vector<int> h((size_t)n);
+        if (n) SA_HIP_CHECK(hipMemcpyAsync(h.data(), P->part.back().p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+        SA_HIP_CHECK(hipStreamSynchronize(s));
+        P->part_host.push_back(std::move(h));
+        P->xadj.emplace_back();
+        P->adj.emplace_back();
+        quotient_graph_device(s, n, P->xadj[(size_t)k].p, P->adj[(size_t)k].p, P->part.back().p, np, P->xadj.back(), P->adj.back());
+        n = np;
+    }
+    for (size_t k = 0; k < P->part.size(); ++k) {
+        P->part_ptr.push_back(P->part[k].p);
+        P->part_host_ptr.push_back(P->part_host[k].data());
+    }
+    for (size_t k = 0; k < P->xadj.size(); ++k) P->nnz.push_back((int64_t)P->adj[k].n);
+    *out = P.release();
+    SA_API_END
+}
+
+int saamge_amd_partitioning_arrays(const saamge_amd_partitioning *p, int on_host, const int *const **partitions,
+                                   const int **nparts_host) {
+    SA_API_BEGIN
+    SA_REQUIRE(p, "null argument");
+    if (partitions) *partitions = on_host ? p->part_host_ptr.data() : p->part_ptr.data();
+    if (nparts_host) *nparts_host = p->nparts.data();
+    SA_API_END
+}
+
+int saamge_amd_partitioning_get(const saamge_amd_partitioning *p, int level, int *part_host, int *n_elem, int *nparts) {
+    SA_API_BEGIN
+    SA_REQUIRE(p, "null argument");
+    SA_REQUIRE(level >= 0 && level < (int)p->part.size(), "level out of range");
+    const std::vector<int> &h = p->part_host[(size_t)level];
+    if (part_host && !h.empty()) std::memcpy(part_host, h.data(), h.size() * sizeof(int));
+    if (n_elem) *n_elem = p->n_elem[(size_t)level];
+    if (nparts) *nparts = p->nparts[(size_t)level];
+    SA_API_END
+}
+
+int saamge_amd_partitioning_graph(const saamge_amd_partitioning *p, int level, long long *xadj, int *adj, int *n,
+                                  long long *nnz) {
+    SA_API_BEGIN
+    SA_REQUIRE(p, "null argument");
+    SA_REQUIRE(level >= 0 && level < (int)p->xadj.size(), "level out of range");
+    SA_REQUIRE(current_device() == p->device, "the calling thread's current HIP device is not the partitioning's device");
+    const size_t l = (size_t)level;
+    const size_t nn = p->xadj[l].n - 1;
+    if (n) *n = (int)nn;
+    if (nnz) *nnz = p->nnz[l];
+    if (xadj) SA_HIP_CHECK(hipMemcpy(xadj, p->xadj[l].p, (nn + 1) * sizeof(roff_t), hipMemcpyDefault));
+    if (adj && p->nnz[l]) SA_HIP_CHECK(hipMemcpy(adj, p->adj[l].p, (size_t)p->nnz[l] * sizeof(int), hipMemcpyDefault));
+    SA_API_END
+}
+
+void saamge_amd_partitioning_free(saamge_amd_partitioning *p) { delete p; }
 
 }  // extern "C"

@@ -1,0 +1,30 @@
+// Agglomerate partitions built on the device from a graph (partition.hip).  The algorithm is defined by
+// saamge_amd/partition_model.py; the kernels restate it and give the same integers.
+#pragma once
+#include "common.h"
+
+namespace saamge_amd {
+
+struct PartitionOptions {
+    int min_shared = 1;   // dofs two elements share to be adjacent (mesh entry only)
+    int lloyd_iters = 0;  // recentring passes
+    int max_size = -1;    // -1: 2 * elems_per_agg, 0: off
+    int min_size = -1;    // -1: elems_per_agg / 4, 0: off
+    unsigned seed = 0;
+};
+
+// Refuses offsets that are not 0-based and ascending, columns outside [0, n) and entries without their transpose.  Reads
+// adj only after xadj has been checked.  Returns xadj[n].
+int64_t check_graph_device(hipStream_t s, int n, const roff_t *xadj, const int *adj);
+// part (device, n entries) and the number of parts produced; the graph is trusted (check_graph_device)
+void partition_graph_device(hipStream_t s, int n, const roff_t *xadj, const int *adj, int elems_per_agg,
+                            const PartitionOptions &o, int *part, int *nparts_out);
+// e2d_I / e2d_J on the device and already checked
+void element_graph_device(hipStream_t s, int NE, const int *e2d_I, const int *e2d_J, int ND, int min_shared,
+                          DBuf<roff_t> &xadj, DBuf<int> &adj);
+void quotient_graph_device(hipStream_t s, int n, const roff_t *xadj, const int *adj, const int *part, int nparts,
+                           DBuf<roff_t> &xq, DBuf<int> &aq);
+// bounded checks of a mesh given as offsets and flat dofs, both on the device; returns elem_ptr[NE]
+long check_mesh_device(hipStream_t s, int NE, const int *e2d_I, const int *e2d_J, int ND);
+
+}  // namespace saamge_amd

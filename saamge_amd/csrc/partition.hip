@@ -1,0 +1,666 @@
+// Agglomerate partitions on the device: element graph from elem_to_dof, seeded level-synchronous growth, recentring,
+// size repair, renumbering and the quotient graph of the next level.  saamge_amd/partition_model.py defines every step;
+// this file restates it.  Every decision is a minimum / maximum / count over integers (atomicMin / atomicMax on packed
+// keys, atomicAdd on counters), so the output does not depend on the order in which threads run.
+//
+// Sweeps over the CSR use PT_LPR lanes per row: the lanes of a group read consecutive entries of the row, reduce by
+// shuffles, and lane 0 writes.  Growth is the pull form with two label buffers (no atomics on labels).
+#include "partition.h"
+
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <climits>
+
+namespace saamge_amd {
+
+// topology.hip: dof -> element lists
+__global__ void d2e_count_kernel(long nconn, const int *__restrict__ e2d_J, int *__restrict__ cnt);
+__global__ void d2e_fill_kernel(int NE, const int *__restrict__ e2d_I, const int *__restrict__ e2d_J,
+                                const int *__restrict__ d2e_I, int *__restrict__ cursor, int *__restrict__ d2e_J);
+
+namespace {
+
+typedef unsigned long long u64;
+constexpr int PT_LPR = 8;          // lanes per row of the CSR sweeps
+constexpr u64 PT_NONE = ~0ull;
+
+inline int pt_bits(int n) {
+    int b = 1;
+    while ((1ll << b) < n) ++b;
+    return b;
+}
+inline dim3 grid_rows(long n) { return dim3((unsigned)((n * PT_LPR + 255) / 256)); }
+inline dim3 grid_flat(long n) { return dim3((unsigned)std::max<long>(1, (n + 255) / 256)); }
+
+__device__ inline unsigned pt_prio(unsigned i, unsigned seed) {
+    unsigned x = i + seed * 0x9E3779B9u;
+    x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
+    return x;
+}
+__device__ inline int group_min(int v) {
+    for (int m = PT_LPR / 2; m; m >>= 1) v = min(v, __shfl_xor(v, m));
+    return v;
+}
+__device__ inline int group_or(int v) {
+    for (int m = PT_LPR / 2; m; m >>= 1) v |= __shfl_xor(v, m);
+    return v;
+}
+__device__ inline u64 shfl_xor_u64(u64 v, int m) {
+    const unsigned lo = __shfl_xor((unsigned)v, m), hi = __shfl_xor((unsigned)(v >> 32), m);
+    return ((u64)hi << 32) | lo;
+}
+__device__ inline u64 group_min_u64(u64 v) {
+    for (int m = PT_LPR / 2; m; m >>= 1) { const u64 o = shfl_xor_u64(v, m); v = o < v ? o : v; }
+    return v;
+}
+
+__global__ __launch_bounds__(256) void pt_fill_int_kernel(long n, int v, int *__restrict__ a) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) a[i] = v;
+}
+__global__ __launch_bounds__(256) void pt_fill_u64_kernel(long n, u64 v, u64 *__restrict__ a) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) a[i] = v;
+}
+
+// ---- growth ---------------------------------------------------------------------------------------------------------
+// counters[0] += nodes labelled in this round, counters[1] += nodes still unlabelled after it
+__global__ __launch_bounds__(256) void pt_grow_kernel(int n, const roff_t *__restrict__ xadj, const int *__restrict__ adj,
+                                                      const int *__restrict__ cur, const int *__restrict__ dom,
+                                                      int *__restrict__ next, int *__restrict__ counters) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const long v = t / PT_LPR;
+    const int lane = (int)(t % PT_LPR);
+    const bool valid = v < n;
+    const int mine = valid ? cur[v] : 0;
+    int best = INT_MAX;
+    if (valid && mine < 0) {
+        const int dv = dom ? dom[v] : 0;
+        for (roff_t k = xadj[v] + lane, e = xadj[v + 1]; k < e; k += PT_LPR) {
+            const int u = adj[k], lu = cur[u];
+            if (lu >= 0 && lu < best && (!dom || dom[u] == dv)) best = lu;
+        }
+    }
+    best = group_min(best);
+    if (valid && lane == 0) {
+        if (mine >= 0) next[v] = mine;
+        else if (best != INT_MAX) { next[v] = best; atomicAdd(&counters[0], 1); }
+        else { next[v] = -1; atomicAdd(&counters[1], 1); }
+    }
+}
+// lowest (priority, id) among the unlabelled nodes
+__global__ __launch_bounds__(256) void pt_min_unlabelled_kernel(int n, const int *__restrict__ label, unsigned seed,
+                                                                u64 *__restrict__ out) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    u64 key = PT_NONE;
+    if (i < n && label[i] < 0) key = ((u64)pt_prio((unsigned)i, seed) << 32) | (unsigned)i;
+    for (int m = 32; m; m >>= 1) { const u64 o = shfl_xor_u64(key, m); key = o < key ? o : key; }
+    if ((threadIdx.x & 63) == 0 && key != PT_NONE) atomicMin(out, key);
+}
+__global__ void pt_stall_seed_kernel(const u64 *__restrict__ key, int newlabel, int *__restrict__ label,
+                                     int *__restrict__ isseed) {
+    const unsigned i = (unsigned)(*key & 0xFFFFFFFFull);
+    label[i] = newlabel;
+    isseed[i] = 1;
+}
+
+// ---- seeding --------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void pt_count_kernel(int n, const int *__restrict__ label, int *__restrict__ sizes) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) atomicAdd(&sizes[label[i]], 1);
+}
+// k[p] = seeds of an oversized part (0: not flagged), km1[p] = the labels it needs beyond its own; info[0] += flagged parts
+__global__ __launch_bounds__(256) void pt_over_kernel(int nlabels, const int *__restrict__ sizes, int max_size, int epa,
+                                                      int *__restrict__ k, int *__restrict__ km1, int *__restrict__ info) {
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= nlabels) return;
+    const int sz = sizes[p];
+    int kp = 0;
+    if (sz > max_size) { kp = max(2, (sz + epa - 1) / epa); atomicAdd(&info[0], 1); }
+    k[p] = kp;
+    km1[p] = kp ? kp - 1 : 0;
+}
+__global__ __launch_bounds__(256) void pt_sort_keys_kernel(int n, const int *__restrict__ label, unsigned seed,
+                                                           u64 *__restrict__ keys, int *__restrict__ ids) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    keys[i] = ((u64)(unsigned)label[i] << 32) | pt_prio((unsigned)i, seed);
+    ids[i] = (int)i;
+}
+__global__ __launch_bounds__(256) void pt_reseed_kernel(int n, const u64 *__restrict__ keys, const int *__restrict__ ids,
+                                                        const int *__restrict__ start, const int *__restrict__ k,
+                                                        const int *__restrict__ off, int nlabels, int *__restrict__ label,
+                                                        int *__restrict__ isseed) {
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const int p = (int)(keys[j] >> 32), node = ids[j], kp = k[p];
+    if (!kp) return;
+    const int r = (int)j - start[p];
+    if (r < kp) { label[node] = r == 0 ? p : nlabels + off[p] + r - 1; isseed[node] = 1; }
+    else { label[node] = -1; isseed[node] = 0; }
+}
+
+// ---- recentring -----------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void pt_boundary_kernel(int n, const roff_t *__restrict__ xadj, const int *__restrict__ adj,
+                                                          const int *__restrict__ label, int *__restrict__ depth) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const long v = t / PT_LPR;
+    const int lane = (int)(t % PT_LPR);
+    const bool valid = v < n;
+    int b = 0;
+    if (valid) {
+        const int lv = label[v];
+        for (roff_t k = xadj[v] + lane, e = xadj[v + 1]; k < e; k += PT_LPR) b |= label[adj[k]] != lv;
+    }
+    b = group_or(b);
+    if (valid && lane == 0) depth[v] = b ? 0 : -1;
+}
+// In place: a node without depth takes d when a neighbour of its part has d - 1.  A depth written in this launch is d, never
+// d - 1, so what a concurrent reader sees of it does not change the outcome.
+__global__ __launch_bounds__(256) void pt_depth_kernel(int n, const roff_t *__restrict__ xadj, const int *__restrict__ adj,
+                                                       const int *__restrict__ label, int d, int *depth,
+                                                       int *__restrict__ counters) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const long v = t / PT_LPR;
+    const int lane = (int)(t % PT_LPR);
+    const bool valid = v < n;
+    int hit = 0;
+    if (valid && depth[v] < 0) {
+        const int lv = label[v];
+        for (roff_t k = xadj[v] + lane, e = xadj[v + 1]; k < e; k += PT_LPR) {
+            const int u = adj[k];
+            hit |= label[u] == lv && depth[u] == d - 1;
+        }
+    }
+    hit = group_or(hit);
+    if (valid && lane == 0 && hit) { depth[v] = d; atomicAdd(&counters[0], 1); }
+}
+__device__ inline u64 centre_key(int depth, unsigned prio) { return ((u64)(unsigned)(depth + 1) << 32) | (0xFFFFFFFFu - prio); }
+__global__ __launch_bounds__(256) void pt_centre_max_kernel(int n, const int *__restrict__ label, const int *__restrict__ depth,
+                                                            const int *__restrict__ isseed, unsigned seed,
+                                                            u64 *__restrict__ best) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int d = depth[i];
+    if (d >= 0 || isseed[i]) atomicMax(&best[label[i]], centre_key(d, pt_prio((unsigned)i, seed)));
+}
+__global__ __launch_bounds__(256) void pt_centre_pick_kernel(int n, int *__restrict__ label, const int *__restrict__ depth,
+                                                             int *__restrict__ isseed, unsigned seed,
+                                                             const u64 *__restrict__ best) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int d = depth[i];
+    const bool pick = (d >= 0 || isseed[i]) && centre_key(d, pt_prio((unsigned)i, seed)) == best[label[i]];
+    isseed[i] = pick ? 1 : 0;
+    if (!pick) label[i] = -1;
+}
+
+// ---- merging of small parts -----------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void pt_propose_kernel(int n, const roff_t *__restrict__ xadj, const int *__restrict__ adj,
+                                                         const int *__restrict__ label, const int *__restrict__ sizes,
+                                                         int min_size, int max_size, u64 *__restrict__ prop) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const long v = t / PT_LPR;
+    const int lane = (int)(t % PT_LPR);
+    const bool valid = v < n;
+    u64 best = PT_NONE;
+    int lp = 0;
+    if (valid) {
+        lp = label[v];
+        const int sp = sizes[lp];
+        if (sp < min_size)
+            for (roff_t k = xadj[v] + lane, e = xadj[v + 1]; k < e; k += PT_LPR) {
+                const int lq = label[adj[k]];
+                if (lq == lp) continue;
+                const int sq = sizes[lq];
+                if (max_size > 0 && sp + sq > max_size) continue;
+                const u64 key = ((u64)(unsigned)sq << 32) | (unsigned)lq;
+                best = key < best ? key : best;
+            }
+    }
+    best = group_min_u64(best);
+    if (valid && lane == 0 && best != PT_NONE) atomicMin(&prop[lp], best);
+}
+__global__ __launch_bounds__(256) void pt_win_kernel(int nlabels, const u64 *__restrict__ prop, const int *__restrict__ sizes,
+                                                     u64 *__restrict__ win) {
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= nlabels || prop[p] == PT_NONE) return;
+    atomicMin(&win[(unsigned)(prop[p] & 0xFFFFFFFFull)], ((u64)(unsigned)sizes[p] << 32) | (unsigned)p);
+}
+__device__ inline bool pt_stationary(const u64 *prop, int q) {
+    if (prop[q] == PT_NONE) return true;
+    const int r = (int)(prop[q] & 0xFFFFFFFFull);
+    return prop[r] != PT_NONE && (int)(prop[r] & 0xFFFFFFFFull) == q && q < r;
+}
+__global__ __launch_bounds__(256) void pt_decide_kernel(int nlabels, const u64 *__restrict__ prop, const u64 *__restrict__ win,
+                                                        int *__restrict__ target, int *__restrict__ info) {
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= nlabels) return;
+    int t = (int)p;
+    if (prop[p] != PT_NONE && !pt_stationary(prop, (int)p)) {
+        const int q = (int)(prop[p] & 0xFFFFFFFFull);
+        if (pt_stationary(prop, q) && (int)(win[q] & 0xFFFFFFFFull) == (int)p) { t = q; atomicAdd(&info[0], 1); }
+    }
+    target[p] = t;
+}
+__global__ __launch_bounds__(256) void pt_relabel_kernel(int n, const int *__restrict__ target, int *__restrict__ label) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) label[i] = target[label[i]];
+}
+
+// ---- renumbering ----------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void pt_minid_kernel(int n, const int *__restrict__ label, int *__restrict__ minid) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) atomicMin(&minid[label[i]], (int)i);
+}
+__global__ __launch_bounds__(256) void pt_first_kernel(int n, const int *__restrict__ label, const int *__restrict__ minid,
+                                                       int *__restrict__ first) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) first[i] = minid[label[i]] == (int)i;
+}
+__global__ __launch_bounds__(256) void pt_newnum_kernel(int n, const int *__restrict__ label, const int *__restrict__ first,
+                                                        const int *__restrict__ rank, int *__restrict__ newnum) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n && first[i]) newnum[label[i]] = rank[i];
+}
+__global__ __launch_bounds__(256) void pt_apply_kernel(int n, const int *__restrict__ label, const int *__restrict__ newnum,
+                                                       int *__restrict__ part) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) part[i] = newnum[label[i]];
+}
+
+// ---- quotient graph -------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void pt_cut_count_kernel(int n, const roff_t *__restrict__ xadj, const int *__restrict__ adj,
+                                                           const int *__restrict__ part, int *__restrict__ cnt) {
+    const long v = (long)blockIdx.x * 256 + threadIdx.x;
+    if (v >= n) return;
+    const int pv = part[v];
+    int c = 0;
+    for (roff_t k = xadj[v], e = xadj[v + 1]; k < e; ++k) c += part[adj[k]] != pv;
+    cnt[v] = c;
+}
+__global__ __launch_bounds__(256) void pt_cut_fill_kernel(int n, const roff_t *__restrict__ xadj, const int *__restrict__ adj,
+                                                          const int *__restrict__ part, const roff_t *__restrict__ pos,
+                                                          u64 *__restrict__ keys) {
+    const long v = (long)blockIdx.x * 256 + threadIdx.x;
+    if (v >= n) return;
+    const int pv = part[v];
+    roff_t o = pos[v];
+    for (roff_t k = xadj[v], e = xadj[v + 1]; k < e; ++k) {
+        const int pu = part[adj[k]];
+        if (pu != pv) keys[o++] = ((u64)(unsigned)pv << 32) | (unsigned)pu;
+    }
+}
+__global__ __launch_bounds__(256) void pt_quot_rows_kernel(long m, const u64 *__restrict__ keys, int *__restrict__ cnt,
+                                                           int *__restrict__ aq) {
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= m) return;
+    atomicAdd(&cnt[(unsigned)(keys[j] >> 32)], 1);
+    aq[j] = (int)(keys[j] & 0xFFFFFFFFull);
+}
+
+// ---- element graph --------------------------------------------------------------------------------------------------
+// One thread per element e.  A candidate f reached through dof number a of e is taken there only when a is the first dof of
+// e that f holds, so every neighbour is seen once; then the dofs from a on are counted.  FILL = false counts, true writes.
+template <bool FILL>
+__global__ __launch_bounds__(256) void pt_elem_graph_kernel(int NE, const int *__restrict__ e2d_I, const int *__restrict__ e2d_J,
+                                                            const int *__restrict__ d2e_I, const int *__restrict__ d2e_J,
+                                                            int min_shared, int *__restrict__ cnt,
+                                                            const roff_t *__restrict__ xadj, int *__restrict__ adj) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= NE) return;
+    const int b0 = e2d_I[e], b1 = e2d_I[e + 1];
+    int c = 0;
+    roff_t o = FILL ? xadj[e] : 0;
+    for (int a = b0; a < b1; ++a) {
+        const int d = e2d_J[a];
+        for (int x = d2e_I[d], x1 = d2e_I[d + 1]; x < x1; ++x) {
+            const int f = d2e_J[x];
+            if (f == (int)e) continue;
+            const int f0 = e2d_I[f], f1 = e2d_I[f + 1];
+            bool earlier = false;
+            for (int b = b0; b < a && !earlier; ++b) {
+                const int db = e2d_J[b];
+                for (int y = f0; y < f1; ++y) earlier |= e2d_J[y] == db;
+            }
+            if (earlier) continue;
+            int shared = 1;
+            for (int b = a + 1; b < b1; ++b) {
+                const int db = e2d_J[b];
+                for (int y = f0; y < f1; ++y) shared += e2d_J[y] == db;
+            }
+            if (shared < min_shared) continue;
+            if (FILL) adj[o++] = f;
+            ++c;
+        }
+    }
+    if (!FILL) cnt[e] = c;
+}
+__global__ __launch_bounds__(256) void pt_row_sort_kernel(int n, const roff_t *__restrict__ xadj, int *__restrict__ adj) {
+    const long v = (long)blockIdx.x * 256 + threadIdx.x;
+    if (v >= n) return;
+    const roff_t b = xadj[v], e = xadj[v + 1];
+    for (roff_t i = b + 1; i < e; ++i) {  // insertion sort, rows are short
+        const int x = adj[i];
+        roff_t j = i - 1;
+        while (j >= b && adj[j] > x) { adj[j + 1] = adj[j]; --j; }
+        adj[j + 1] = x;
+    }
+}
+
+// ---- checks ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void pt_check_xadj_kernel(int n, const roff_t *__restrict__ xadj, int *__restrict__ err) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    if ((i == 0 && xadj[0] != 0) || xadj[i + 1] < xadj[i]) atomicOr(err, 1);
+}
+__global__ __launch_bounds__(256) void pt_check_adj_kernel(int n, const roff_t *__restrict__ xadj, const int *__restrict__ adj,
+                                                           int *__restrict__ err) {
+    const long v = (long)blockIdx.x * 256 + threadIdx.x;
+    if (v >= n) return;
+    for (roff_t k = xadj[v], e = xadj[v + 1]; k < e; ++k) {
+        const int u = adj[k];
+        if (u < 0 || u >= n) { atomicOr(err, 2); continue; }
+        bool back = false;
+        for (roff_t j = xadj[u], je = xadj[u + 1]; j < je && !back; ++j) back = adj[j] == (int)v;
+        if (!back) atomicOr(err, 4);
+    }
+}
+__global__ __launch_bounds__(256) void pt_check_eptr_kernel(int NE, const int *__restrict__ ptr, int *__restrict__ err) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= NE) return;
+    if ((e == 0 && ptr[0] != 0) || ptr[e + 1] <= ptr[e]) atomicOr(err, 1);
+}
+__global__ __launch_bounds__(256) void pt_check_repeat_kernel(int NE, const int *__restrict__ ptr, const int *__restrict__ J,
+                                                              int *__restrict__ err) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= NE) return;
+    for (int a = ptr[e], e1 = ptr[e + 1]; a < e1; ++a)
+        for (int b = a + 1; b < e1; ++b)
+            if (J[a] == J[b]) atomicOr(err, 4);
+}
+__global__ __launch_bounds__(256) void pt_check_dofs_kernel(long nconn, int ND, const int *__restrict__ J, int *__restrict__ err) {
+    const long k = (long)blockIdx.x * 256 + threadIdx.x;
+    if (k < nconn && (J[k] < 0 || J[k] >= ND)) atomicOr(err, 2);
+}
+
+template <class T>
+T read_one(const T *p, hipStream_t s) {
+    T v;
+    SA_HIP_CHECK(hipMemcpyAsync(&v, p, sizeof(T), hipMemcpyDeviceToHost, s));
+    SA_HIP_CHECK(hipStreamSynchronize(s));
+    return v;
+}
+void fill_int(hipStream_t s, long n, int v, int *a) {
+    if (!n) return;
+    hipLaunchKernelGGL(pt_fill_int_kernel, grid_flat(n), dim3(256), 0, s, n, v, a);
+}
+void fill_u64(hipStream_t s, long n, u64 v, u64 *a) {
+    if (!n) return;
+    hipLaunchKernelGGL(pt_fill_u64_kernel, grid_flat(n), dim3(256), 0, s, n, v, a);
+}
+
+struct Grower {
+    hipStream_t s;
+    int n;
+    const roff_t *xadj;
+    const int *adj;
+    unsigned seed;
+    DBuf<int> a, b, isseed, counters;
+    DBuf<u64> key;
+    int *label = nullptr;  // a.p or b.p: the current labels
+    int nlabels = 0;
+    Grower(hipStream_t s_, int n_, const roff_t *x, const int *j, unsigned seed_)
+        : s(s_), n(n_), xadj(x), adj(j), seed(seed_), a((size_t)n_), b((size_t)n_), isseed((size_t)n_), counters(2), key(1) {
+        label = a.p;
+        isseed.zero(s);
+    }
+    int *other() const { return label == a.p ? b.p : a.p; }
+    void grow(const int *dom) {
+        for (;;) {
+            counters.zero(s);
+            hipLaunchKernelGGL(pt_grow_kernel, grid_rows(n), dim3(256), 0, s, n, xadj, adj, (const int *)label, dom, other(), counters.p);
+            SA_HIP_CHECK(hipGetLastError());
+            label = other();
+            const auto c = counters.to_host(s);
+            if (c[1] == 0) return;
+            if (c[0] == 0) {  // a component without a seed
+                fill_u64(s, 1, PT_NONE, key.p);
+                hipLaunchKernelGGL(pt_min_unlabelled_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)label, seed, key.p);
+                hipLaunchKernelGGL(pt_stall_seed_kernel, dim3(1), dim3(1), 0, s, (const u64 *)key.p, nlabels, label, isseed.p);
+                SA_HIP_CHECK(hipGetLastError());
+                ++nlabels;
+            }
+        }
+    }
+    // sizes of the current labels (nlabels + 1 entries allocated, the last unused by the count)
+    void sizes_of(DBuf<int> &sizes) {
+        sizes.alloc((size_t)nlabels + 1);
+        sizes.zero(s);
+        hipLaunchKernelGGL(pt_count_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)label, sizes.p);
+        SA_HIP_CHECK(hipGetLastError());
+    }
+    // the parts with k[p] > 0 are cleared down to their k[p] nodes of lowest priority; km1 = max(k - 1, 0)
+    void reseed(const DBuf<int> &sizes, const DBuf<int> &k, const DBuf<int> &km1) {
+        DBuf<int> start((size_t)nlabels + 1), off((size_t)nlabels + 1);
+        exclusive_scan_int(s, nlabels, sizes.p, start.p);
+        exclusive_scan_int(s, nlabels, km1.p, off.p);
+        DBuf<u64> keys((size_t)n), keys2((size_t)n);
+        DBuf<int> ids((size_t)n), ids2((size_t)n);
+        hipLaunchKernelGGL(pt_sort_keys_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)label, seed, keys.p, ids.p);
+        SA_HIP_CHECK(hipGetLastError());
+        size_t tmp_bytes = 0;
+        const int end_bit = 32 + pt_bits(nlabels);
+        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys.p, keys2.p, ids.p, ids2.p, n, 0, end_bit, s));
+        DBuf<char> tmp(tmp_bytes + 16);
+        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs((void *)tmp.p, tmp_bytes, keys.p, keys2.p, ids.p, ids2.p, n, 0, end_bit, s));
+        hipLaunchKernelGGL(pt_reseed_kernel, grid_flat(n), dim3(256), 0, s, n, (const u64 *)keys2.p, (const int *)ids2.p,
+                           (const int *)start.p, (const int *)k.p, (const int *)off.p, nlabels, label, isseed.p);
+        SA_HIP_CHECK(hipGetLastError());
+        nlabels += read_one(off.p + nlabels, s);  // (synchronises: the temporaries go out of scope)
+    }
+    void recentre() {
+        DBuf<int> depth((size_t)n);
+        hipLaunchKernelGGL(pt_boundary_kernel, grid_rows(n), dim3(256), 0, s, n, xadj, adj, (const int *)label, depth.p);
+        SA_HIP_CHECK(hipGetLastError());
+        for (int d = 1;; ++d) {
+            counters.zero(s);
+            hipLaunchKernelGGL(pt_depth_kernel, grid_rows(n), dim3(256), 0, s, n, xadj, adj, (const int *)label, d, depth.p, counters.p);
+            SA_HIP_CHECK(hipGetLastError());
+            if (counters.to_host(s)[0] == 0) break;
+        }
+        DBuf<u64> best((size_t)nlabels);
+        best.zero(s);
+        hipLaunchKernelGGL(pt_centre_max_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)label, (const int *)depth.p,
+                           (const int *)isseed.p, seed, best.p);
+        hipLaunchKernelGGL(pt_centre_pick_kernel, grid_flat(n), dim3(256), 0, s, n, label, (const int *)depth.p, isseed.p, seed,
+                           (const u64 *)best.p);
+        SA_HIP_CHECK(hipGetLastError());
+        SA_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    bool merge_round(int min_size, int max_size) {
+        DBuf<int> sizes, target((size_t)nlabels), info(1);
+        DBuf<u64> prop((size_t)nlabels), win((size_t)nlabels);
+        sizes_of(sizes);
+        fill_u64(s, nlabels, PT_NONE, prop.p);
+        fill_u64(s, nlabels, PT_NONE, win.p);
+        info.zero(s);
+        hipLaunchKernelGGL(pt_propose_kernel, grid_rows(n), dim3(256), 0, s, n, xadj, adj, (const int *)label, (const int *)sizes.p,
+                           min_size, max_size, prop.p);
+        hipLaunchKernelGGL(pt_win_kernel, grid_flat(nlabels), dim3(256), 0, s, nlabels, (const u64 *)prop.p, (const int *)sizes.p, win.p);
+        hipLaunchKernelGGL(pt_decide_kernel, grid_flat(nlabels), dim3(256), 0, s, nlabels, (const u64 *)prop.p, (const u64 *)win.p,
+                           target.p, info.p);
+        hipLaunchKernelGGL(pt_relabel_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)target.p, label);
+        SA_HIP_CHECK(hipGetLastError());
+        return info.to_host(s)[0] != 0;
+    }
+};
+
+constexpr int PT_MERGE_ROUNDS = 8;
+constexpr int PT_REPAIR_ROUNDS = 32;
+
+}  // namespace
+
+int64_t check_graph_device(hipStream_t s, int n, const roff_t *xadj, const int *adj) {
+    if (n == 0) return 0;
+    DBuf<int> err(1);
+    err.zero(s);
+    hipLaunchKernelGGL(pt_check_xadj_kernel, grid_flat(n), dim3(256), 0, s, n, xadj, err.p);
+    SA_HIP_CHECK(hipGetLastError());
+    SA_REQUIRE(!err.to_host(s)[0], "xadj: must start at 0 and ascend");
+    const roff_t nnz = read_one(xadj + n, s);
+    SA_REQUIRE(nnz == 0 || adj, "null argument: adj");
+    hipLaunchKernelGGL(pt_check_adj_kernel, grid_flat(n), dim3(256), 0, s, n, xadj, adj, err.p);
+    SA_HIP_CHECK(hipGetLastError());
+    const int bits = err.to_host(s)[0];
+    SA_REQUIRE(!(bits & 2), "adj: entry outside [0, n)");
+    SA_REQUIRE(!(bits & 4), "graph is not symmetric: an entry without its transpose");
+    return nnz;
+}
+
+long check_mesh_device(hipStream_t s, int NE, const int *e2d_I, const int *e2d_J, int ND) {
+    if (NE == 0) return 0;
+    DBuf<int> err(1);
+    err.zero(s);
+    hipLaunchKernelGGL(pt_check_eptr_kernel, grid_flat(NE), dim3(256), 0, s, NE, e2d_I, err.p);
+    SA_HIP_CHECK(hipGetLastError());
+    SA_REQUIRE(!err.to_host(s)[0], "elem_ptr: must start at 0 and every element needs a dof");
+    const long nconn = read_one(e2d_I + NE, s);
+    hipLaunchKernelGGL(pt_check_dofs_kernel, grid_flat(nconn), dim3(256), 0, s, nconn, ND, e2d_J, err.p);
+    SA_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(pt_check_repeat_kernel, grid_flat(NE), dim3(256), 0, s, NE, e2d_I, e2d_J, err.p);
+    SA_HIP_CHECK(hipGetLastError());
+    const int bits = err.to_host(s)[0];
+    SA_REQUIRE(!(bits & 2), "elem_to_dof entry out of range");
+    SA_REQUIRE(!(bits & 4), "elem_to_dof: an element lists a dof twice");
+    return nconn;
+}
+
+void partition_graph_device(hipStream_t s, int n, const roff_t *xadj, const int *adj, int epa, const PartitionOptions &o,
+                            int *part, int *nparts_out) {
+    SA_REQUIRE(n >= 0, "n < 0");
+    SA_REQUIRE(epa >= 1, "elems_per_agg < 1");
+    SA_REQUIRE(o.lloyd_iters >= 0 && o.max_size >= -1 && o.min_size >= -1, "partition options: lloyd_iters >= 0, sizes >= -1");
+    *nparts_out = 0;
+    if (n == 0) return;
+    const int max_size = o.max_size < 0 ? (int)std::min<int64_t>(2ll * epa, INT_MAX) : o.max_size;
+    const int min_size = o.min_size < 0 ? epa / 4 : o.min_size;
+    Grower g(s, n, xadj, adj, o.seed);
+    {   // first seeding: one part 0 that holds every node, target seeds
+        const int target = (int)(((int64_t)n + epa - 1) / epa);
+        g.label = g.a.p;
+        g.a.zero(s);
+        g.nlabels = 1;
+        DBuf<int> sizes(2), k(1), km1(2);
+        const int hs[2] = {n, 0}, hk[2] = {target - 1, 0};
+        SA_HIP_CHECK(hipMemcpyAsync(sizes.p, hs, sizeof hs, hipMemcpyHostToDevice, s));
+        SA_HIP_CHECK(hipMemcpyAsync(k.p, &target, sizeof(int), hipMemcpyHostToDevice, s));
+        SA_HIP_CHECK(hipMemcpyAsync(km1.p, hk, sizeof hk, hipMemcpyHostToDevice, s));
+        SA_HIP_CHECK(hipStreamSynchronize(s));
+        g.reseed(sizes, k, km1);
+    }
+    g.grow(nullptr);
+    for (int it = 0; it < o.lloyd_iters; ++it) {
+        g.recentre();
+        g.grow(nullptr);
+    }
+    if (max_size > 0)
+        for (int r = 0; r < PT_REPAIR_ROUNDS; ++r) {  // pieces are strictly smaller; the bound is for hubs (partition_model.py)
+            DBuf<int> sizes, k((size_t)g.nlabels), km1((size_t)g.nlabels + 1), info(1);
+            g.sizes_of(sizes);
+            info.zero(s);
+            hipLaunchKernelGGL(pt_over_kernel, grid_flat(g.nlabels), dim3(256), 0, s, g.nlabels, (const int *)sizes.p, max_size, epa,
+                               k.p, km1.p, info.p);
+            SA_HIP_CHECK(hipGetLastError());
+            if (info.to_host(s)[0] == 0) break;
+            DBuf<int> old((size_t)n);
+            SA_HIP_CHECK(hipMemcpyAsync(old.p, g.label, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, s));
+            g.reseed(sizes, k, km1);
+            g.grow(old.p);
+            SA_HIP_CHECK(hipStreamSynchronize(s));
+        }
+    if (min_size > 0)
+        for (int r = 0; r < PT_MERGE_ROUNDS; ++r)
+            if (!g.merge_round(min_size, max_size)) break;
+    // parts numbered by their smallest member
+    DBuf<int> minid((size_t)g.nlabels), first((size_t)n), rank((size_t)n + 1), newnum((size_t)g.nlabels);
+    fill_int(s, g.nlabels, n, minid.p);
+    hipLaunchKernelGGL(pt_minid_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)g.label, minid.p);
+    hipLaunchKernelGGL(pt_first_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)g.label, (const int *)minid.p, first.p);
+    SA_HIP_CHECK(hipGetLastError());
+    exclusive_scan_int(s, n, first.p, rank.p);
+    hipLaunchKernelGGL(pt_newnum_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)g.label, (const int *)first.p,
+                       (const int *)rank.p, newnum.p);
+    hipLaunchKernelGGL(pt_apply_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)g.label, (const int *)newnum.p, part);
+    SA_HIP_CHECK(hipGetLastError());
+    *nparts_out = read_one(rank.p + n, s);
+}
+
+void element_graph_device(hipStream_t s, int NE, const int *e2d_I, const int *e2d_J, int ND, int min_shared,
+                          DBuf<roff_t> &xadj, DBuf<int> &adj) {
+    SA_REQUIRE(min_shared >= 1, "min_shared < 1");
+    xadj.alloc((size_t)NE + 1);
+    if (NE == 0) { xadj.zero(s); adj.alloc(0); return; }
+    const long nconn = read_one(e2d_I + NE, s);
+    DBuf<int> d2e_I((size_t)ND + 1), d2e_J((size_t)nconn), cnt((size_t)std::max(ND, NE) + 1);
+    cnt.zero(s);
+    hipLaunchKernelGGL(d2e_count_kernel, grid_flat(nconn), dim3(256), 0, s, nconn, e2d_J, cnt.p);
+    SA_HIP_CHECK(hipGetLastError());
+    exclusive_scan_int(s, ND, cnt.p, d2e_I.p);
+    cnt.zero(s);
+    hipLaunchKernelGGL(d2e_fill_kernel, grid_flat(NE), dim3(256), 0, s, NE, e2d_I, e2d_J, (const int *)d2e_I.p, cnt.p, d2e_J.p);
+    // (the lists need no order: every row of the graph is sorted at the end)
+    hipLaunchKernelGGL(pt_elem_graph_kernel<false>, grid_flat(NE), dim3(256), 0, s, NE, e2d_I, e2d_J, (const int *)d2e_I.p,
+                       (const int *)d2e_J.p, min_shared, cnt.p, (const roff_t *)nullptr, (int *)nullptr);
+    SA_HIP_CHECK(hipGetLastError());
+    exclusive_scan_off(s, NE, cnt.p, xadj.p);
+    const roff_t nnz = read_one(xadj.p + NE, s);
+    adj.alloc((size_t)nnz);
+    hipLaunchKernelGGL(pt_elem_graph_kernel<true>, grid_flat(NE), dim3(256), 0, s, NE, e2d_I, e2d_J, (const int *)d2e_I.p,
+                       (const int *)d2e_J.p, min_shared, (int *)nullptr, (const roff_t *)xadj.p, adj.p);
+    hipLaunchKernelGGL(pt_row_sort_kernel, grid_flat(NE), dim3(256), 0, s, NE, (const roff_t *)xadj.p, adj.p);
+    SA_HIP_CHECK(hipGetLastError());
+    SA_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void quotient_graph_device(hipStream_t s, int n, const roff_t *xadj, const int *adj, const int *part, int nparts,
+                           DBuf<roff_t> &xq, DBuf<int> &aq) {
+    xq.alloc((size_t)nparts + 1);
+    DBuf<int> cnt((size_t)std::max(n, nparts) + 1);
+    DBuf<roff_t> pos((size_t)n + 1);
+    roff_t ncut = 0;
+    if (n) {
+        hipLaunchKernelGGL(pt_cut_count_kernel, grid_flat(n), dim3(256), 0, s, n, xadj, adj, part, cnt.p);
+        SA_HIP_CHECK(hipGetLastError());
+        exclusive_scan_off(s, n, cnt.p, pos.p);
+        ncut = read_one(pos.p + n, s);
+    }
+    SA_REQUIRE(ncut < (roff_t)INT_MAX, "quotient graph: more than 2^31 cut edges");
+    DBuf<u64> keys((size_t)ncut), sorted((size_t)ncut), uniq((size_t)ncut);
+    DBuf<int> nsel(1);
+    int m = 0;
+    if (ncut) {
+        hipLaunchKernelGGL(pt_cut_fill_kernel, grid_flat(n), dim3(256), 0, s, n, xadj, adj, part, (const roff_t *)pos.p, keys.p);
+        SA_HIP_CHECK(hipGetLastError());
+        size_t tb = 0, tb2 = 0;
+        const int end_bit = 32 + pt_bits(nparts);
+        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, keys.p, sorted.p, (int)ncut, 0, end_bit, s));
+        SA_HIP_CHECK(hipcub::DeviceSelect::Unique(nullptr, tb2, sorted.p, uniq.p, nsel.p, (int)ncut, s));
+        DBuf<char> tmp(std::max(tb, tb2) + 16);
+        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortKeys((void *)tmp.p, tb, keys.p, sorted.p, (int)ncut, 0, end_bit, s));
+        SA_HIP_CHECK(hipcub::DeviceSelect::Unique((void *)tmp.p, tb2, sorted.p, uniq.p, nsel.p, (int)ncut, s));
+        m = read_one(nsel.p, s);
+    }
+    aq.alloc((size_t)m);
+    SA_HIP_CHECK(hipMemsetAsync(cnt.p, 0, ((size_t)nparts + 1) * sizeof(int), s));
+    if (m) {
+        hipLaunchKernelGGL(pt_quot_rows_kernel, grid_flat(m), dim3(256), 0, s, (long)m, (const u64 *)uniq.p, cnt.p, aq.p);
+        SA_HIP_CHECK(hipGetLastError());
+    }
+    if (nparts) exclusive_scan_off(s, nparts, cnt.p, xq.p);
+    else xq.zero(s);
+    SA_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+}  // namespace saamge_amd

@@ -1,0 +1,252 @@
+"""CPU model of the device partitioner (csrc/partition.hip) -- numpy only, test infrastructure like capi.py.
+
+This file is the DEFINITION of the algorithm: the device code restates it and must give the same integers.  Every step is
+a minimum / maximum / count over integers, so no result depends on an execution order.
+
+  priority     prio(i) = fmix32(i + seed * 0x9E3779B9): a bijection of 32-bit integers, so priorities never tie.
+  element graph  e != f adjacent when they share >= min_shared dofs; symmetric CSR, no self-loops, columns ascending.
+               An element that lists a dof twice is refused.
+  seeding      `reseed`: inside every flagged part p the k[p] nodes of lowest priority become seeds; the lowest keeps the
+               label p, the r-th lowest (r >= 1) gets nlabels + off[p] + r - 1 with off the exclusive sum of k - 1 over the
+               flagged parts in label order.  The first seeding is this with one part 0 holding every node and
+               k = target = ceil(n / elems_per_agg).
+  growth       level-synchronous pull: every unlabelled node with a labelled neighbour (of the same `dom`, when given) takes
+               the smallest such label of the PREVIOUS round.  Nothing changed and nodes are left: the unlabelled node of
+               lowest priority becomes a seed with the next free label.
+  recentring   depth = hops to the nearest node of the own part that has a neighbour in another part, over same-label edges.
+               New seed of a part = its node of largest depth, ties to the lowest priority; a part without boundary keeps
+               its seed.  Labels stay with their parts; growth restarts from the new seeds.
+  size repair  (a) while a part is larger than max_size, at most REPAIR_ROUNDS times: reseed it with
+               max(2, ceil(size / elems_per_agg)) seeds and grow across same-old-label edges only.  Every flagged part is
+               connected and gets two seeds or more, so its pieces are strictly smaller; on meshes a few rounds reach the
+               cap.  A hub with very many leaves shrinks by about one piece per round: the bound ends that, and a part
+               still above the cap after it is left as it is.
+               (b) rounds: a part p smaller than min_size PROPOSES to its adjacent part q of smallest (size, label) among
+               those with size[p] + size[q] <= max_size.  Proposals can only cycle in pairs (the choice is a strict
+               minimum), so: q is STATIONARY when it proposes nothing, or proposes to a part that proposes back and has the
+               larger label.  p joins q when q is stationary, p is not, and p is the proposer of q with the smallest
+               (size, label).  One joiner per part and round keeps the cap.  Until a round merges nothing, at most 8.
+  renumbering  parts 0 .. nparts-1 in the order of their smallest member.
+  quotient     parts adjacent when any of their members are; unweighted, columns ascending.
+"""
+import numpy as np
+
+MERGE_ROUNDS = 8
+REPAIR_ROUNDS = 32
+DEFAULT_LLOYD_ITERS = 0
+
+
+def priority(n, seed=0):
+    x = (np.arange(n, dtype=np.uint64) + np.uint64((int(seed) * 0x9E3779B9) & 0xFFFFFFFF)) & np.uint64(0xFFFFFFFF)
+    x ^= x >> np.uint64(16)
+    x = (x * np.uint64(0x85EBCA6B)) & np.uint64(0xFFFFFFFF)
+    x ^= x >> np.uint64(13)
+    x = (x * np.uint64(0xC2B2AE35)) & np.uint64(0xFFFFFFFF)
+    x ^= x >> np.uint64(16)
+    return x.astype(np.int64)
+
+
+def resolve_sizes(elems_per_agg, max_size=-1, min_size=-1):
+    if max_size < 0:
+        max_size = 2 * elems_per_agg
+    if min_size < 0:
+        min_size = elems_per_agg // 4
+    return int(max_size), int(min_size)
+
+
+def build_element_graph(elem_ptr, elem_to_dof, ND, min_shared=1):
+    """elem_ptr (NE + 1), flat elem_to_dof -> (xadj int64 (NE + 1), adj int32)."""
+    elem_ptr = np.asarray(elem_ptr, np.int64)
+    e2d = np.asarray(elem_to_dof, np.int64)
+    NE = len(elem_ptr) - 1
+    elem = np.repeat(np.arange(NE, dtype=np.int64), np.diff(elem_ptr))
+    if len(np.unique(elem * max(int(ND), 1) + e2d)) != len(e2d):
+        raise ValueError("an element lists a dof twice")
+    order = np.argsort(e2d, kind="stable")
+    dofs, elems = e2d[order], elem[order]
+    cnt = np.bincount(dofs, minlength=ND)
+    start = np.concatenate([[0], np.cumsum(cnt)])
+    keys = []
+    for c in np.unique(cnt):
+        if c < 2:
+            continue
+        d = np.flatnonzero(cnt == c)
+        lists = elems[start[d][:, None] + np.arange(c)[None, :]]          # (m, c)
+        keys.append((lists[:, :, None] * NE + lists[:, None, :]).ravel())
+    if keys:
+        k, shared = np.unique(np.concatenate(keys), return_counts=True)
+        e, f = k // NE, k % NE
+        keep = (e != f) & (shared >= min_shared)
+        e, f = e[keep], f[keep]
+    else:
+        e = f = np.zeros(0, np.int64)
+    xadj = np.concatenate([[0], np.cumsum(np.bincount(e, minlength=NE))]).astype(np.int64)
+    return xadj, f.astype(np.int32)
+
+
+class _Graph(object):
+    def __init__(self, n, xadj, adj):
+        self.n = int(n)
+        self.xadj = np.asarray(xadj, np.int64)
+        self.dst = np.asarray(adj, np.int64)
+        self.src = np.repeat(np.arange(self.n, dtype=np.int64), np.diff(self.xadj))
+
+
+def _grow(g, label, isseed, prio, nlabels, dom=None):
+    BIG = np.iinfo(np.int64).max
+    same = np.ones(len(g.src), bool) if dom is None else dom[g.src] == dom[g.dst]
+    while True:
+        unl = label < 0
+        if not unl.any():
+            return label, nlabels
+        m = same & unl[g.src] & (label[g.dst] >= 0)
+        if m.any():
+            new = np.full(g.n, BIG)
+            np.minimum.at(new, g.src[m], label[g.dst[m]])
+            label = np.where(new < BIG, new, label)
+        else:
+            u = np.flatnonzero(unl)
+            s = u[np.argmin(prio[u])]
+            label = label.copy()
+            label[s] = nlabels
+            isseed[s] = True
+            nlabels += 1
+
+
+def _reseed(g, label, isseed, prio, nlabels, k):
+    """k[p] > 0 flags part p.  Returns the labels with the flagged parts cleared down to their new seeds."""
+    flagged = k > 0
+    off = np.concatenate([[0], np.cumsum(np.where(flagged, k - 1, 0))])
+    order = np.lexsort((prio, label))
+    sizes = np.bincount(label, minlength=nlabels)
+    start = np.concatenate([[0], np.cumsum(sizes)])
+    dom_sorted = label[order]
+    rank = np.arange(g.n) - start[dom_sorted]
+    out = label.copy()
+    infl = flagged[label]
+    out[infl] = -1
+    isseed[infl] = False
+    sel = flagged[dom_sorted] & (rank < k[dom_sorted])
+    nodes, p, r = order[sel], dom_sorted[sel], rank[sel]
+    out[nodes] = np.where(r == 0, p, nlabels + off[p] + r - 1)
+    isseed[nodes] = True
+    return out, nlabels + int(off[-1])
+
+
+def _recentre(g, label, isseed, prio, nlabels):
+    bnd = np.zeros(g.n, bool)
+    bnd[g.src[label[g.src] != label[g.dst]]] = True
+    depth = np.where(bnd, 0, -1).astype(np.int64)
+    same = label[g.src] == label[g.dst]
+    d = 0
+    while True:
+        d += 1
+        m = same & (depth[g.src] < 0) & (depth[g.dst] == d - 1)
+        if not m.any():
+            break
+        depth[g.src[m]] = d
+    submit = (depth >= 0) | isseed
+    key = ((depth + 1) << 32) | (0xFFFFFFFF - prio)
+    best = np.full(nlabels, -1, np.int64)
+    np.maximum.at(best, label[submit], key[submit])
+    newseed = submit & (key == best[label])
+    isseed[:] = newseed
+    return np.where(newseed, label, -1)
+
+
+def _merge_round(g, label, nlabels, max_size, min_size):
+    BIG = np.iinfo(np.int64).max
+    sizes = np.bincount(label, minlength=nlabels)
+    lp, lq = label[g.src], label[g.dst]
+    m = (lp != lq) & (sizes[lp] < min_size)
+    if max_size > 0:
+        m &= sizes[lp] + sizes[lq] <= max_size
+    prop = np.full(nlabels, BIG)
+    np.minimum.at(prop, lp[m], (sizes[lq[m]] << 32) | lq[m])
+    has = prop < BIG
+    q = np.where(has, prop & 0xFFFFFFFF, -1)
+    qs = np.where(has, q, 0)
+    stationary = ~has | ((q[qs] == np.arange(nlabels)) & (np.arange(nlabels) < q))
+    win = np.full(nlabels, BIG)
+    p = np.flatnonzero(has)
+    np.minimum.at(win, q[p], (sizes[p] << 32) | p)
+    join = has & ~stationary & stationary[qs] & ((win[qs] & 0xFFFFFFFF) == np.arange(nlabels))
+    target = np.where(join, q, np.arange(nlabels))
+    return target[label], int(join.sum())
+
+
+def renumber(label, nlabels):
+    n = len(label)
+    minid = np.full(nlabels, n, np.int64)
+    np.minimum.at(minid, label, np.arange(n))
+    first = minid[label] == np.arange(n)
+    rank = np.cumsum(first) - first
+    newnum = np.zeros(nlabels, np.int64)
+    newnum[label[first]] = rank[first]
+    return newnum[label].astype(np.int32), int(first.sum())
+
+
+def partition_graph(n, xadj, adj, elems_per_agg, min_shared=1, lloyd_iters=DEFAULT_LLOYD_ITERS, max_size=-1,
+                    min_size=-1, seed=0):
+    """One level: symmetric CSR graph -> (part int32 (n), nparts).  min_shared is not used here (graph given)."""
+    if elems_per_agg < 1 or n < 0:
+        raise ValueError("elems_per_agg >= 1 and n >= 0")
+    if n == 0:
+        return np.zeros(0, np.int32), 0
+    max_size, min_size = resolve_sizes(elems_per_agg, max_size, min_size)
+    g = _Graph(n, xadj, adj)
+    prio = priority(n, seed)
+    target = -(-n // elems_per_agg)
+    isseed = np.zeros(n, bool)
+    label, nlabels = _reseed(g, np.zeros(n, np.int64), isseed, prio, 1, np.array([target], np.int64))
+    label, nlabels = _grow(g, label, isseed, prio, nlabels)
+    for _ in range(lloyd_iters):
+        label = _recentre(g, label, isseed, prio, nlabels)
+        label, nlabels = _grow(g, label, isseed, prio, nlabels)
+    if max_size > 0:
+        for _ in range(REPAIR_ROUNDS):
+            sizes = np.bincount(label, minlength=nlabels)
+            over = sizes > max_size
+            if not over.any():
+                break
+            k = np.where(over, np.maximum(2, -(-sizes // elems_per_agg)), 0)
+            old = label
+            label, nlabels = _reseed(g, label, isseed, prio, nlabels, k)
+            label, nlabels = _grow(g, label, isseed, prio, nlabels, dom=old)
+    if min_size > 0:
+        for _ in range(MERGE_ROUNDS):
+            label, moved = _merge_round(g, label, nlabels, max_size, min_size)
+            if not moved:
+                break
+    return renumber(label, nlabels)
+
+
+def quotient_graph(n, xadj, adj, part, nparts):
+    g = _Graph(n, xadj, adj)
+    p, q = np.asarray(part, np.int64)[g.src], np.asarray(part, np.int64)[g.dst]
+    cut = p != q
+    k = np.unique(p[cut] * nparts + q[cut])
+    xq = np.concatenate([[0], np.cumsum(np.bincount(k // nparts, minlength=nparts))]).astype(np.int64)
+    return xq, (k % nparts).astype(np.int32)
+
+
+def partition_mesh(elem_ptr, elem_to_dof, ND, elems_per_agg, **opts):
+    """All levels: elems_per_agg is a sequence, one entry per coarsening.  Returns (parts, nparts, graphs): graphs[k] is the
+    (xadj, adj) that parts[k] partitions, graphs[len(parts)] the quotient graph of the last level."""
+    min_shared = opts.get("min_shared", 1)
+    graphs = [build_element_graph(elem_ptr, elem_to_dof, ND, min_shared)]
+    parts, nparts = [], []
+    n = len(elem_ptr) - 1
+    for epa in elems_per_agg:
+        xadj, adj = graphs[-1]
+        part, npt = partition_graph(n, xadj, adj, int(epa), **opts)
+        parts.append(part)
+        nparts.append(npt)
+        graphs.append(quotient_graph(n, xadj, adj, part, npt))
+        n = npt
+    return parts, nparts, graphs
+
+
+def size_stats(part, nparts, elems_per_agg):
+    s = np.bincount(part, minlength=nparts) / float(elems_per_agg)
+    return dict(min=float(s.min()), median=float(np.median(s)), p95=float(np.percentile(s, 95)), max=float(s.max()))
