@@ -312,6 +312,12 @@ int saamge_amd_num_levels(const saamge_amd_hierarchy *h); /* number of operators
  * [7]=total eigenvectors [8]=inner PCG iterations of the last coarsest solve
  * [12]=1 if the level is row-partitioned [13]=first own row [14]=own rows [15]=halo entries received */
 int saamge_amd_level_info(const saamge_amd_hierarchy *h, int level, long long info[16]);
+/* The coarsest solver IN USE (a direct request that could not be served -- a level set beyond the block limit, a
+ * non-positive pivot -- ends in the inner PCG; this tells): info[0] = 1 explicit dense inverse, 2 inner PCG, 3 block-
+ * tridiagonal elimination, 0 the caller's plug (saamge_amd_set_coarse_solver); [1] = rows of the coarsest operator;
+ * [2] = blocks and [3] = rows of the largest block of the block-tridiagonal structure (kind 3, else 0); [4] = doubles held
+ * in the explicit inverses (kind 1: n^2, kind 3: sum n_k^2); [5..7] = 0. */
+int saamge_amd_coarse_solver_info(const saamge_amd_hierarchy *h, long long info[8]);
 /* Storage formats of the level operator's SELL-64 copy (no reference counterpart: hypre keeps CSR): info[0..2] = slices
  * that are pair-coded / offset-coded / plain, [3..5] = their stored entries, [6] = 256-row tiles whose x-segments are
  * staged through LDS, [7] = bytes of matrix data one application streams in these formats, [8] = pairs of the operator-level

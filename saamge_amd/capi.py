@@ -32,7 +32,7 @@ SYMBOLS = [
     "saamge_amd_ml_produce_data_mixed", "saamge_amd_ml_produce_data_mixed64",
     "saamge_amd_partition_options_default", "saamge_amd_partition_graph", "saamge_amd_partition_mesh",
     "saamge_amd_partitioning_arrays", "saamge_amd_partitioning_get", "saamge_amd_partitioning_graph",
-    "saamge_amd_partitioning_free",
+    "saamge_amd_partitioning_free", "saamge_amd_coarse_solver_info",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong))
@@ -454,6 +454,14 @@ class Hierarchy(object):
         keys = ["n", "nnz", "nparts", "num_mises", "ncoarse", "nnzP", "nnzAc", "nvec",
                 "coarse_iters", "evecs_size", "sig_size", "U_size", "row_partitioned", "row0",
                 "own_rows", "halo_recv"]
+        return dict(zip(keys, [int(v) for v in info[:len(keys)]]))
+
+    def coarse_solver_info(self):
+        """The coarsest solver in use: kind (1 dense inverse, 2 inner PCG, 3 block-tridiagonal, 0 the caller's plug), rows
+        of the coarsest operator, blocks / largest block of the block-tridiagonal structure, doubles of explicit inverses."""
+        info = (C.c_longlong * 8)()
+        _check(load().saamge_amd_coarse_solver_info(self.h, info))
+        keys = ["kind", "n", "nblk", "max_block", "inverse_doubles"]
         return dict(zip(keys, [int(v) for v in info[:len(keys)]]))
 
     def level_format(self, level):

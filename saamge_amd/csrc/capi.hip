@@ -441,6 +441,24 @@ int saamge_amd_level_format(const saamge_amd_hierarchy *h, int level, long long 
     SA_API_END
 }
 
+int saamge_amd_coarse_solver_info(const saamge_amd_hierarchy *h, long long info[8]) {
+    SA_API_BEGIN
+    SA_REQUIRE(h && info, "null argument");
+    const Hierarchy &H = *h->H;
+    for (int i = 0; i < 8; ++i) info[i] = 0;
+    SA_REQUIRE(!H.levels.empty(), "no levels");
+    info[0] = H.user_coarse_solve ? 0 : H.coarse_kind;
+    info[1] = H.levels.back()->Ac.nrows;
+    if (H.coarse_kind == 3) {
+        info[2] = H.c_bt.nblk;
+        info[3] = H.c_bt.max_block;
+        info[4] = (long long)H.c_bt.Sinv.n;
+    } else if (H.coarse_kind == 1) {
+        info[4] = (long long)H.c_L.n;
+    }
+    SA_API_END
+}
+
 static int get_csr(const saamge_amd_hierarchy *h, int level, int which, void *rowptr, int rowptr_bits, int *col, double *val) {
     SA_API_BEGIN
     SA_REQUIRE(h, "null argument");

@@ -236,6 +236,7 @@ def test_dense_and_iterative_coarsest_solvers_agree():
     for kind in (1, 2):
         h = capi.Hierarchy.from_problem(prob, capi.default_params(coarse_solver=kind, coarse_rtol=1e-28))
         assert h.level_info(0)["ncoarse"] > 1000
+        assert h.coarse_solver_info()["kind"] == kind
         b = np.cos(np.arange(prob.ND) * 0.21) * (~prob.ess)
         x, it, conv, hist = h.pcg(prob.b, rel_tol=1e-8)
         out[kind] = (h.vcycle(b), x, it, h.level_info(0)["coarse_iters"])
