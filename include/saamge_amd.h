@@ -30,9 +30,13 @@ typedef struct saamge_amd_hierarchy saamge_amd_hierarchy; /* == ml_data_t, inc/m
 
 /* Options of the library's own machinery (no counterpart in the reference): what is left of the environment switches of
  * rounds 1-3.  The variants that were measured without gain are gone; these remain because tests need them to reach a code
- * path or because a caller may want them.  PROCESS-WIDE: saamge_amd_set_options() sets them, and every
- * saamge_amd_ml_produce_data* call sets them from params->options before it builds (the last hierarchy built wins; do not
- * build hierarchies with different options concurrently).  Environment variables that remain: SAAMGE_AMD_TIMING (phase
+ * path or because a caller may want them.  PER HIERARCHY: params->options is what a hierarchy uses for its whole life
+ * (setup, saamge_amd_update_operators, solves); building one neither reads nor alters the default, and hierarchies with
+ * different options may coexist.  saamge_amd_set_options() sets the process-wide DEFAULT: what saamge_amd_get_options
+ * returns (for callers who fill params->options from it) and what the entry points without a hierarchy use
+ * (saamge_amd_spmv / spmv64, saamge_amd_lower_eigens_batched, saamge_amd_inertia_batched); it never reaches a hierarchy
+ * that already exists.  Values out of range are refused (saamge_amd_last_error names the field).  Only host_heap_pad_mb
+ * is a property of the process: the first hierarchy's value applies.  Environment variables that remain: SAAMGE_AMD_TIMING (phase
  * times on stderr), SAAMGE_AMD_SERIAL (no worker threads in the setup: counter passes), SAAMGE_AMD_POOL_MAX_GB (device
  * block cache, default 64), SAAMGE_AMD_THREADS (host threads of the host topology builds). */
 typedef struct saamge_amd_options {
@@ -156,7 +160,7 @@ typedef struct saamge_amd_params {
      * history to 3 digits of its 6e-8 deviation from the oracle's -- that deviation comes from the singular vectors of the
      * smallest kept singular values, not from the eigenvectors.  Allowed: 1e-15 ... 1e-8. */
     double eig_tol;
-    saamge_amd_options options;               /* applied process-wide by saamge_amd_ml_produce_data* (see saamge_amd_options) */
+    saamge_amd_options options;               /* what this hierarchy uses for its whole life (see saamge_amd_options) */
 } saamge_amd_params;
 
 void saamge_amd_params_default(saamge_amd_params *p);

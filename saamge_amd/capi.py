@@ -621,8 +621,10 @@ def get_options():
 
 
 def set_options(**kw):
-    """Process-wide options of the library (saamge_amd_options); returns the previous values.  default_params() copies the
-    current ones into params.options, so that a later ml_produce_data keeps them."""
+    """The process-wide DEFAULT options of the library (saamge_amd_options); returns the previous values.  default_params()
+    copies the current default into params.options, and params.options is what a hierarchy uses for its whole life: a later
+    set_options does not reach hierarchies that already exist.  The entry points without a hierarchy (spmv,
+    lower_eigens_batched) use the default directly."""
     old = get_options()
     new = Options.from_buffer_copy(old)
     for k, v in kw.items():

@@ -1404,11 +1404,11 @@ void ae_build(hipStream_t s, const DevRelations &rel, const DCsr *A, const DevEl
     }
     if (!A || no_fused || lds > 160 * 1024 - 256 || batch.max_n > 32767) {
         if (!split_scale) batch.has_perm = false;       // (the one-kernel scaling works in agglomerate order)
-        const bool band_asm = options().band_assembly != 0;
+        const bool band_asm = batch.opt.band_assembly != 0;
         // (also with the global matrix at hand -- level 0 of Q2 elasticity, whose agglomerates do not fit the fused
         // kernel's LDS: an entry copied from A couples two dofs of an element of this agglomerate, so the band of the
         // element matrices holds it)
-        const bool banded = band_asm && batch.has_perm && split_scale && scale && eig_ss_band_enabled();
+        const bool banded = band_asm && batch.has_perm && split_scale && scale;
         // classes of identical agglomerates on the INPUTS of the assembly (AeInputs above): only their first members are assembled
         // and scaled -- as the batch of the representatives over the same workspace, through the same kernels the whole batch
         // would take (the choice between the one-kernel and the spread scaling is the whole batch's)
@@ -1457,7 +1457,7 @@ void ae_build(hipStream_t s, const DevRelations &rel, const DCsr *A, const DevEl
                     if (rep[i] == i) { pos[i] = (int)cl.reps.size(); cl.reps.push_back(i); }
                 cl.rep_of.resize((size_t)batch.count);
                 for (int i = 0; i < batch.count; ++i) cl.rep_of[i] = pos[rep[i]];
-                if ((options().debug & 1)) std::fprintf(stderr, "duplicate agglomerates (assembly inputs): %d distinct of %d\n", (int)cl.reps.size(), batch.count);
+                if ((batch.opt.debug & 1)) std::fprintf(stderr, "duplicate agglomerates (assembly inputs): %d distinct of %d\n", (int)cl.reps.size(), batch.count);
                 EigBatch cb;
                 eig_batch_compact(s, cb, batch, cl.reps);
                 std::vector<int> ids(cl.reps.size());
@@ -1495,7 +1495,7 @@ void ae_build(hipStream_t s, const DevRelations &rel, const DCsr *A, const DevEl
         batch.has_bw = true;
     }
     constexpr bool band_write = true;
-    const int band_only = (bwp && band_write && eig_ss_band_enabled()) ? 1 : 0;
+    const int band_only = (bwp && band_write) ? 1 : 0;
     const bool nde8 = el.nde == 8 && batch.count <= 65535;   // (grid.y of the rows kernel)
     // precomputed sparse rows: 8-dof elements, or elements of at most 8 dofs and different sizes (ae_build_kernel's PRE branch
     // reads the rows only: its NDE does not matter there)
@@ -1514,7 +1514,7 @@ void ae_build(hipStream_t s, const DevRelations &rel, const DCsr *A, const DevEl
         src.ns = batch.n.p; src.voff = batch.voff.p; src.moff = batch.moff.p;
         src.perm = pm; src.rvals = rv; src.rcols = rc; src.RW = RW;
         classes->searched = true;
-        classes->early = eig_dedupe_find(s, src, batch.count, batch.max_n, classes->cls);
+        classes->early = eig_dedupe_find(s, src, batch.count, batch.max_n, classes->cls, batch.opt.debug);
         if (classes->early) {
             only.from_host(classes->cls.reps, s);
             nbuild = (int)classes->cls.reps.size();
@@ -2037,7 +2037,7 @@ void coarse_elmats_sparse(hipStream_t s, const DevRelations &rel, int ae0, const
             d_rep.from_host(rep, s);
             d_list.from_host(list, s);
             ncompute = (int)list.size();
-            if (options().debug & 1) std::fprintf(stderr, "coarse element matrices: %d distinct of %d\n", ncompute, batch.count);
+            if (batch.opt.debug & 1) std::fprintf(stderr, "coarse element matrices: %d distinct of %d\n", ncompute, batch.count);
         } else {
             rep.clear();
         }
@@ -2049,7 +2049,7 @@ void coarse_elmats_sparse(hipStream_t s, const DevRelations &rel, int ae0, const
     constexpr bool old_only = false;
     const int pool_cap = 6 * batch.max_n, u_cap = 3 * batch.max_n;
     const size_t lds = 8 * (size_t)(pool_cap + u_cap) + 28 * (size_t)batch.max_n + 16;
-    if (options().debug & 2)
+    if (batch.opt.debug & 2)
         std::fprintf(stderr, "coarse_elmats_sparse: %d agglomerates, max n %d, kmax %d, RW %d, LDS %zu\n", batch.count, batch.max_n, kmax, RW, lds);
     const int *only = nullptr;
     DBuf<int> flagged;

@@ -60,16 +60,40 @@ static void options_to_c(const Options &o, saamge_amd_options *c) {
     c->eig_dedupe = o.eig_dedupe; c->eig_outer_panels = o.eig_outer_panels; c->overlap = o.overlap; c->sell = o.sell; c->spmv_sell = o.spmv_sell; c->debug = o.debug;
     c->host_heap_pad_mb = o.host_heap_pad_mb;
 }
-void saamge_amd_options_default(saamge_amd_options *o) { options_to_c(Options(), o); }
-void saamge_amd_get_options(saamge_amd_options *o) { options_to_c(options(), o); }
-void saamge_amd_set_options(const saamge_amd_options *c) {
-    Options &o = options();
+static Options options_from_c(const saamge_amd_options *c) {
+    Options o;
     o.eig_strict = c->eig_strict; o.eig_certify = c->eig_certify; o.eig_min_n = c->eig_min_n;
     o.eig_force_fallback = c->eig_force_fallback; o.eig_dense_only = c->eig_dense_only; o.eig_dense_one_stage = c->eig_dense_one_stage;
     o.eig_nullcheck = c->eig_nullcheck; o.eig_keep_inertia_factor = c->eig_keep_inertia_factor; o.band_assembly = c->band_assembly;
     o.eig_dedupe = c->eig_dedupe; o.eig_outer_panels = c->eig_outer_panels; o.overlap = c->overlap; o.sell = c->sell; o.spmv_sell = c->spmv_sell; o.debug = c->debug;
     o.host_heap_pad_mb = c->host_heap_pad_mb;
+    return o;
 }
+// Called on the options a hierarchy or a hierarchy-free entry point is about to use.
+static void validate_options(const Options &o) {
+    auto flag = [](int v) { return v == 0 || v == 1; };
+    SA_REQUIRE(flag(o.eig_strict), "options: eig_strict must be 0 or 1");
+    SA_REQUIRE(flag(o.eig_certify), "options: eig_certify must be 0 or 1");
+    SA_REQUIRE(o.eig_min_n >= 0, "options: eig_min_n must not be negative");
+    SA_REQUIRE(o.eig_force_fallback >= 0, "options: eig_force_fallback must not be negative");
+    SA_REQUIRE(flag(o.eig_dense_only), "options: eig_dense_only must be 0 or 1");
+    SA_REQUIRE(flag(o.eig_dense_one_stage), "options: eig_dense_one_stage must be 0 or 1");
+    SA_REQUIRE(flag(o.eig_nullcheck), "options: eig_nullcheck must be 0 or 1");
+    SA_REQUIRE(flag(o.eig_keep_inertia_factor), "options: eig_keep_inertia_factor must be 0 or 1");
+    SA_REQUIRE(flag(o.band_assembly), "options: band_assembly must be 0 or 1");
+    SA_REQUIRE(flag(o.eig_dedupe), "options: eig_dedupe must be 0 or 1");
+    SA_REQUIRE(o.eig_outer_panels == 2 || o.eig_outer_panels == 4 || o.eig_outer_panels == 8, "options: eig_outer_panels must be 2, 4 or 8");
+    SA_REQUIRE((o.overlap & ~15) == 0, "options: overlap has bits 0-3");
+    SA_REQUIRE((o.sell & ~127) == 0, "options: sell has bits 0-6");
+    SA_REQUIRE(flag(o.spmv_sell), "options: spmv_sell must be 0 or 1");
+    SA_REQUIRE((o.debug & ~7) == 0, "options: debug has bits 0-2");
+    SA_REQUIRE(o.host_heap_pad_mb >= 0, "options: host_heap_pad_mb must not be negative");
+}
+// The process-wide default: what saamge_amd_get_options returns and the entry points without a hierarchy use.
+static Options g_default_options;
+void saamge_amd_options_default(saamge_amd_options *o) { options_to_c(Options(), o); }
+void saamge_amd_get_options(saamge_amd_options *o) { options_to_c(g_default_options, o); }
+void saamge_amd_set_options(const saamge_amd_options *c) { g_default_options = options_from_c(c); }
 
 void saamge_amd_params_default(saamge_amd_params *p) {
     // defaults of test/mltest/mltest.cpp:332-419
@@ -116,9 +140,10 @@ int saamge_amd_memcpy(void *dst, const void *src, long long bytes) {
 }
 
 static Params convert_params(const saamge_amd_params *params, void *stream) {
-    saamge_amd_set_options(&params->options);
-    host_heap_policy();
     Params p;
+    p.opt = options_from_c(&params->options);
+    validate_options(p.opt);
+    host_heap_policy(p.opt.host_heap_pad_mb);
     p.num_coarsenings = params->num_coarsenings;
     SA_REQUIRE(p.num_coarsenings >= 1 && p.num_coarsenings < MAX_LEVELS, "bad num_coarsenings");
     for (int i = 0; i < MAX_LEVELS; ++i) {
@@ -582,6 +607,8 @@ static int spmv_entry(int nrows, int ncols, const void *rowptr, int rowptr_bits,
                       const double *x, double *y) {
     SA_API_BEGIN
     SA_REQUIRE(rowptr && col && val && x && y && nrows >= 0, "bad argument");
+    const Options opt = g_default_options;
+    validate_options(opt);
     hipStream_t s = 0;
     set_thread_stream(s);
     DCsr A;
@@ -595,8 +622,8 @@ static int spmv_entry(int nrows, int ncols, const void *rowptr, int rowptr_bits,
     import_array(A.col, col, (size_t)A.nnz, s);
     import_array(A.val, val, (size_t)A.nnz, s);
     A.lanes_per_row = pick_lanes_per_row(A.nnz, nrows > 0 ? nrows : 1);
-    // SAAMGE_AMD_SPMV_SELL=1 (tests): through the SELL-64 copy and its coded slices, the format of the level operators
-    if (nrows == ncols && options().spmv_sell) build_sell(s, A);
+    // spmv_sell (tests): through the SELL-64 copy and its coded slices, the format of the level operators
+    if (nrows == ncols && opt.spmv_sell) build_sell(s, A, opt);
     VecIn vx(x, (size_t)ncols, s);
     VecOut vy(y, (size_t)nrows, s, false);
     spmv(s, A, vx.p, vy.p);
@@ -630,13 +657,15 @@ int saamge_amd_lower_eigens_batched(int count, const int *n, const double *A, co
                                     double vl, double vu, int *m, double *evals, double *evecs) {
     SA_API_BEGIN
     SA_REQUIRE(count >= 0 && n && A && D && m && evals && evecs, "bad argument");
+    const Options opt = g_default_options;
+    validate_options(opt);
     hipStream_t s = 0;
     set_thread_stream(s);
     std::vector<int> sizes(n, n + count);
     EigBatch b;
-    eig_batch_alloc(b, sizes, s);
+    eig_batch_alloc(b, sizes, opt, s);
     b.set_window(vu);
-    b.dense_only = options().eig_dense_only != 0;
+    b.dense_only = opt.eig_dense_only != 0;
     SA_HIP_CHECK(hipMemcpyAsync(b.W.p, A, 8 * (size_t)b.h_moff[count], hipMemcpyDefault, s));
     DBuf<double> dD;
     dD.assign(D, (size_t)b.h_voff[count], s);
@@ -676,11 +705,13 @@ int saamge_amd_lower_eigens_batched(int count, const int *n, const double *A, co
 int saamge_amd_inertia_batched(int count, const int *n, const double *A, const double *D, double vu, int *neg) {
     SA_API_BEGIN
     SA_REQUIRE(count >= 0 && n && A && D && neg, "bad argument");
+    const Options opt = g_default_options;
+    validate_options(opt);
     hipStream_t s = 0;
     set_thread_stream(s);
     std::vector<int> sizes(n, n + count);
     EigBatch b;
-    eig_batch_alloc(b, sizes, s);
+    eig_batch_alloc(b, sizes, opt, s);
     b.set_window(vu);
     SA_HIP_CHECK(hipMemcpyAsync(b.W.p, A, 8 * (size_t)b.h_moff[count], hipMemcpyDefault, s));
     DBuf<double> dD;

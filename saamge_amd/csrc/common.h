@@ -84,31 +84,10 @@ inline bool is_device_ptr(const void *p) {
     return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
 }
 
-// ---- options of the library (saamge_amd_options, include/saamge_amd.h): process-wide, set through the C ABI ----------
-// What is left of the ~50 environment switches of rounds 1-3: the variants that were measured without gain are gone, the
-// ones tests need to reach a code path (or a caller may want) are fields here.  Environment variables that remain:
-// SAAMGE_AMD_TIMING, SAAMGE_AMD_SERIAL (diagnostics), SAAMGE_AMD_POOL_MAX_GB, SAAMGE_AMD_THREADS (resources).
-struct Options {
-    int eig_strict = 0;               // few-eigenpairs path: a fallback to the dense path is an error (tests of that path)
-    int eig_certify = 1;              // the count #{lambda < theta} certified by the inertia of C - theta I
-    int eig_min_n = 64;               // smallest agglomerate of a batch that takes the few-eigenpairs path
-    int eig_force_fallback = 0;       // tests: every k-th matrix takes the per-matrix dense fallback
-    int eig_dense_only = 0;           // saamge_amd_lower_eigens_batched: the dense path (a hierarchy: saamge_amd_params.eigensolver)
-    int eig_dense_one_stage = 0;      // dense path: one-stage blocked Householder reduction instead of the two-stage one
-    int eig_nullcheck = 1;            // known-null-vector shortcut (ss_nullcheck_kernel)
-    int eig_keep_inertia_factor = 1;  // wide-band matrices with certified count 0 keep the factor of the inertia pass
-    int band_assembly = 1;            // coarse-level agglomerate matrices assembled inside their band
-    int eig_dedupe = 1;               // bitwise identical agglomerate matrices of a batch are solved once
-    int eig_outer_panels = 8;         // 16-column panels per outer block of the wide-band factorisations (2: the right-looking two-panel walk)
-    int overlap = 15;                 // bit 0 subspace iteration beside the next chunk, 1 halo exchange beside the interior rows, 2 Galerkin product beside the next level, 3 fine operator data beside the AE tables
-    int sell = 31;                    // bit 0 coded slices at all, 1 pair coding, 2 short-chain kernel path, 3 operator-level dictionary, 4 node blocks, 5 (off) coded smoother diagonal, 6 (off) row patterns OFF
-    int spmv_sell = 0;                // saamge_amd_spmv / spmv64 build and use the SELL copy
-    int debug = 0;                    // bit 0 iteration traces of the few-eigenpairs path, 1 operator format census, 2 level tags in the kernel profile
-    int host_heap_pad_mb = 256;       // > 0: glibc never trims its heap, serves blocks up to 32 MB from it and grows it in steps of this size (0: allocator left alone)
-};
-// Applied once, by the first hierarchy of the process (capi.hip): see Options::host_heap_pad_mb and DESIGN.md section 7.0.
-void host_heap_policy();
-Options &options();
+// ---- process-wide diagnostics and the host heap policy (runtime.hip) ----------------------
+// Applied once, with the host_heap_pad_mb of the first hierarchy of the process (capi.hip): see Options::host_heap_pad_mb
+// and DESIGN.md section 7.0.
+void host_heap_policy(int mb);
 bool env_timing();      // SAAMGE_AMD_TIMING
 bool env_timing_host(); // SAAMGE_AMD_TIMING=host
 bool env_serial();      // SAAMGE_AMD_SERIAL: no worker threads in the setup (counter passes)
@@ -189,7 +168,7 @@ struct DBuf {
         const size_t bytes = n * sizeof(T);
         // A large pageable vector goes through a page-locked block of the library's own (never returned to the system): handed
         // over as it is, the runtime registers the caller's pages with the GPU for the transfer and keeps the registration
-        // cached -- pages that go back to the kernel when the vector dies (host_heap_policy, topology.hip).
+        // cached -- pages that go back to the kernel when the vector dies (host_heap_policy, runtime.hip).
         const bool pinned = std::is_same<typename V::allocator_type, PinnedAlloc<typename V::value_type>>::value;
         if (!pinned && bytes >= (256u << 10)) {
             void *stage = pinned_alloc(bytes);
@@ -302,7 +281,7 @@ struct DCsr {
     // of tile T at (T sell_wq + q) 256 + t) and one descriptor word per tile (segments | the four slice widths)
     int sell_wq = 0;
     DBuf<unsigned> sell_codeR;
-    // row patterns (sell_row_patterns_kernel; options().sell bit 6 set: none): the distinct code-word rows of a staged tile,
+    // row patterns (sell_row_patterns_kernel; Options::sell bit 6 set: none): the distinct code-word rows of a staged tile,
     // at most SELL_PMAX of them, in sell_tile_pat[(T SELL_PMAX + p) 8 + q] (zero past sell_wq words and past the tile's count),
     // and one byte per row, sell_row_pat[256 T + t], naming its pattern.  sell_tile_pinfo[T] > 0: the pattern count;
     // <= 0: the tile has more patterns and keeps its code words in sell_codeR at slot -sell_tile_pinfo[T] (then only such
@@ -363,7 +342,7 @@ struct Profiler {
     bool enabled = false;
     std::vector<KernelStat> stats;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    int level_tag = 0;  // SAAMGE_AMD_PROFILE_LEVELS=1: setup kernels of level l > 0 are listed as name@Ll
+    int level_tag = 0;  // Options::debug bit 2: setup kernels of level l > 0 are listed as name@Ll
     KernelStat &get(const std::string &name) {
         for (auto &s : stats)
             if (s.name == name) return s;

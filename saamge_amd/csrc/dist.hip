@@ -262,7 +262,7 @@ bool dist_setup_level(Hierarchy &H, int lev) {
     // (saamge_amd_options.overlap bit 1 cleared: never)
     D.int_row0 = D.row0;
     D.int_nrows = 0;
-    const bool no_overlap = !(options().overlap & 2);
+    const bool no_overlap = !(H.params.opt.overlap & 2);
     if (D.nloc > 0 && !no_overlap) {
         const int nsl = div_up(D.nloc, 64);
         DBuf<int> sflag((size_t)nsl);

@@ -5,6 +5,7 @@
 // C = D^-1/2 A D^-1/2, x = D^-1/2 y.
 #pragma once
 #include "common.h"
+#include "options.h"
 
 namespace saamge_amd {
 
@@ -12,6 +13,7 @@ constexpr int EIG_NB = 32;  // panel width of the one-stage blocked tridiagonali
 constexpr int EIG_SB = 16;  // band width of the two-stage reduction
 
 struct EigBatch {
+    Options opt;            // the options of the hierarchy (or of the call) the batch belongs to
     int count = 0;          // matrices in the batch
     int slot = 0;           // which of the two persistent workspaces backs this batch (chunk pipelining)
     int max_n = 0;
@@ -35,13 +37,13 @@ struct EigBatch {
     DBuf<int64_t> roff;     // [count+1] reflector offsets
     DBuf<double> Gbuf;      // per (matrix, 64-row block) partial V^T X (SB x SB each)
     DBuf<int64_t> goff;
-    // symmetric fused update (SAAMGE_AMD_EIG_FUSED=3): per matrix the 64 x SB partial products of
+    // symmetric fused update: per matrix the 64 x SB partial products of
     // the tiles below the diagonal, tile (I, J) at xpoff[b] + I (I - 1) / 2 + J
     DBuf<double> Xpart;
     DBuf<int64_t> xpoff;
     std::vector<int64_t> h_xpoff;
     std::vector<int64_t> h_roff, h_goff;
-    // few-eigenpairs path (SAAMGE_AMD_EIG=subspace): Ritz values of the accepted block; `dense_only`
+    // few-eigenpairs path: Ritz values of the accepted block; `dense_only`
     // forces the dense path for this batch (fallback after a failed subspace attempt)
     DBuf<double> ss_mu;
     // locked (converged and deflated) pairs of matrices with more wanted pairs than one block holds: see ss_lock_kernel
@@ -103,22 +105,19 @@ struct EigBatch {
 };
 
 // sizes known on the host; allocates everything but leaves W/dis to be filled by the caller
-void eig_batch_alloc(EigBatch &b, const std::vector<int> &sizes, hipStream_t s, int slot = 0);
+void eig_batch_alloc(EigBatch &b, const std::vector<int> &sizes, const Options &opt, hipStream_t s, int slot = 0);
 
 // Phase 1: tridiagonalise every matrix in place.  The default is the two-stage reduction
-// (eig2.hip); SAAMGE_AMD_EIG=onestage selects the one-stage blocked Householder kernel.
+// (eig2.hip); Options::eig_dense_one_stage selects the one-stage blocked Householder kernel.
 // `phases`: 1 = dense -> band only, 2 = band -> tridiagonal only, 3 = both.  The split lets the
 // caller run the (latency-bound) bulge chasing of one chunk beside the (bandwidth-hungry)
 // band reduction of the next one on another stream.
 void eig_tridiagonalize(hipStream_t s, EigBatch &b, int phases = 3);
 void eig_tridiagonalize_two_stage(hipStream_t s, EigBatch &b, int phases);
-bool eig_uses_two_stage();
 void eig_backtransform_two_stage(hipStream_t s, EigBatch &b, const int64_t *xoff, double *evecs);
 int64_t chase_reflector_count(int n);
 void eig_batch_two_stage_buffers(EigBatch &b, size_t nrefl, bool need_bandg, hipStream_t s);
 // few-eigenpairs path (eig2.hip), see there
-bool eig_use_subspace();
-bool eig_ss_band_enabled();                          // banded factorisation on (SAAMGE_AMD_SS_BAND != 0)
 bool eig_batch_takes_subspace(const EigBatch &b);   // what eig_tridiagonalize will decide for this batch
 bool eig_subspace_factor(hipStream_t s, EigBatch &b);
 bool eig_subspace_iterate(hipStream_t s, EigBatch &b, double vu);
@@ -151,7 +150,7 @@ struct DdClasses {
     std::vector<unsigned long long> rep_hash;
 };
 DdSource eig_dedupe_source(const EigBatch &b);
-bool eig_dedupe_find(hipStream_t s, const DdSource &src, int count, int max_n, DdClasses &out);      // false: fewer than a quarter duplicates
+bool eig_dedupe_find(hipStream_t s, const DdSource &src, int count, int max_n, DdClasses &out, int debug);      // false: fewer than a quarter duplicates
 int eig_dedupe_group(const unsigned long long *hh, int count, std::vector<int> &rep);      // rep[i] = first matrix with i's hash; returns the classes
 std::vector<unsigned long long> eig_dedupe_hash_list(hipStream_t s, const DdSource &src, int max_n, const std::vector<int> &list);
 std::vector<long> eig_dedupe_words(hipStream_t s, const DdSource &src, const std::vector<int> &h_n, const std::vector<int> &list);

@@ -746,7 +746,7 @@ __global__ __launch_bounds__(VEC_NT) void eigvec_kernel(
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
-static bool use_one_stage() { return options().eig_dense_one_stage != 0; }
+static bool use_one_stage(const EigBatch &b) { return b.opt.eig_dense_one_stage != 0; }
 
 // Persistent, grow-only device workspace shared by all batches (hipMalloc/hipFree of
 // multi-GB buffers costs 0.1-0.4 s each on this platform; the arena is allocated once per
@@ -775,7 +775,6 @@ void eig_arena_release() {
     }
     g_slot = 0;
 }
-bool eig_uses_two_stage() { return !use_one_stage(); }
 double *eig_arena_bandsave(const EigBatch &b, size_t doubles) {
     g_slot = b.slot;
     EigArena &a = arena();
@@ -790,7 +789,8 @@ double *eig_arena_subpanels(const EigBatch &b, size_t doubles) {
     return a.subpanels.p;
 }
 
-void eig_batch_alloc(EigBatch &b, const std::vector<int> &sizes, hipStream_t s, int slot) {
+void eig_batch_alloc(EigBatch &b, const std::vector<int> &sizes, const Options &opt, hipStream_t s, int slot) {
+    b.opt = opt;
     b.slot = g_slot = slot & 1;
     b.count = (int)sizes.size();
     b.h_n = sizes;
@@ -822,7 +822,7 @@ void eig_batch_alloc(EigBatch &b, const std::vector<int> &sizes, hipStream_t s, 
     arena_view(b.dis, a.dis, rows);
     arena_view(b.m, a.m, (size_t)b.count);
     arena_view(b.j0, a.j0, (size_t)b.count);
-    if (use_one_stage()) arena_view(b.panel, a.panel, rows * EIG_NB);
+    if (use_one_stage(b)) arena_view(b.panel, a.panel, rows * EIG_NB);
 }
 
 void eig_batch_two_stage_buffers(EigBatch &b, size_t nrefl, bool need_bandg, hipStream_t s) {
@@ -1049,7 +1049,7 @@ static int dd_grid_y(const DdSource &src, int count, int max_n) {      // workgr
     return (int)std::max(1l, std::min(std::min(64l, words / 65536), 4096l / std::max(1, count)));
 }
 
-bool eig_dedupe_find(hipStream_t s, const DdSource &src, int count, int max_n, DdClasses &out) {
+bool eig_dedupe_find(hipStream_t s, const DdSource &src, int count, int max_n, DdClasses &out, int debug) {
     out.reps.clear();
     out.rep_of.clear();
     out.rep_hash.clear();
@@ -1083,7 +1083,7 @@ bool eig_dedupe_find(hipStream_t s, const DdSource &src, int count, int max_n, D
     out.rep_of.resize((size_t)count);
     for (int i = 0; i < count; ++i) out.rep_of[i] = pos[rep[i]];
     profiler().end(s, "eig_dedupe", 0.0, 0.0);
-    if ((options().debug & 1)) std::fprintf(stderr, "duplicate agglomerates (%s): %d distinct of %d\n", src.kind ? "bands" : "sparse rows", (int)out.reps.size(), count);
+    if ((debug & 1)) std::fprintf(stderr, "duplicate agglomerates (%s): %d distinct of %d\n", src.kind ? "bands" : "sparse rows", (int)out.reps.size(), count);
     return true;
 }
 // the hashes of SOME matrices of the batch (two words each, in the order of the list)
@@ -1177,6 +1177,7 @@ DdSource eig_dedupe_source(const EigBatch &b) {
 // the batch of the class representatives: the same workspace, per-matrix tables of its own
 void eig_batch_compact(hipStream_t s, EigBatch &cb, EigBatch &full, const std::vector<int> &reps) {
     cb = EigBatch();
+    cb.opt = full.opt;
     cb.slot = g_slot = full.slot;
     cb.count = (int)reps.size();
     cb.h_n.resize(reps.size());
@@ -1232,15 +1233,13 @@ size_t eig_workspace_bytes(int n) {
 }
 
 // The few-eigenpairs path (eig2.hip) is the default for batches whose largest agglomerate has at
-// least SAAMGE_AMD_SS_MIN_N (64) rows -- measured faster than the dense reduction on the 405-row and
+// least Options::eig_min_n (64) rows -- measured faster than the dense reduction on the 405-row and
 // on the 2 600-row agglomerates of the headline problem; a batch it cannot handle (more than six
-// wanted pairs, no convergence) is redone by the dense path.  SAAMGE_AMD_EIG=twostage / onestage /
-// dense switches it off.
-bool eig_use_subspace() { return true; }      // (the dense path alone: EigBatch::dense_only, saamge_amd_params.eigensolver = 1)
-
+// wanted pairs, no convergence) is redone by the dense path.  EigBatch::dense_only (saamge_amd_params.eigensolver = 1,
+// Options::eig_dense_only) switches it off.
 bool eig_batch_takes_subspace(const EigBatch &b) {
     // (saamge_amd_options.eig_min_n: smallest agglomerate size of a batch that takes the few-eigenpairs path)
-    return !b.dense_only && b.max_n >= options().eig_min_n;
+    return !b.dense_only && b.max_n >= b.opt.eig_min_n;
 }
 
 void eig_tridiagonalize(hipStream_t s, EigBatch &b, int phases) {
@@ -1262,7 +1261,7 @@ void eig_tridiagonalize(hipStream_t s, EigBatch &b, int phases) {
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX));
         attr0 = true;
     }
-    if (!use_one_stage()) {
+    if (!use_one_stage(b)) {
         b.two_stage = true;
         eig_tridiagonalize_two_stage(s, b, phases);
         return;

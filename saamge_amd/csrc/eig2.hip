@@ -1080,7 +1080,7 @@ int64_t chase_reflector_count(int n) {
     return r;
 }
 
-// Lanes per chase step and threads per matrix (SAAMGE_AMD_CHASE="ncq,nt" overrides; ncq = 4 | 2
+// Lanes per chase step and threads per matrix (ncq = 4 | 2
 // column groups of 16 lanes per step, nt / (16 ncq) sweeps in flight).  Measured at 128^3
 // (n = 405, 8 192 matrices): 64 lanes per step 42.9 ms, 32 lanes 70.2 ms, 16 lanes 96 ms, and
 // 32 slots instead of 16 do not help the 2 600-row level-1 matrices either (80 vs 60 ms): a step
@@ -1264,7 +1264,7 @@ void eig_backtransform_two_stage(hipStream_t s, EigBatch &b, const int64_t *xoff
 
 
 // =========================================================================================
-// Few-eigenpairs path (SAAMGE_AMD_EIG=subspace, opt-in): the agglomerates want one or two
+// Few-eigenpairs path (eig_batch_takes_subspace): the agglomerates want one or two
 // eigenpairs and the dense reduction pays 2 n^3 flops for them.  Here: C - sigma I = L L^T
 // (sigma < 0, C is positive semidefinite; n^3/3 FMAs through the SAME rank-16 update kernel as
 // the band reduction, with Z = L21 / 2, V = L21), then shift-invert subspace iteration on a block
@@ -2113,7 +2113,7 @@ __global__ __launch_bounds__(256) void ss_rr_kernel(const int *__restrict__ ns, 
         if (iter > 0) {
             int k = 0;
             for (int q = 0; q < NB; ++q) if (sigma + mu_old[q] <= vu) ++k;
-            if (dbg)        // (SAAMGE_AMD_SS_DEBUG: residual bounds and Ritz values of the previous pairs)
+            if (dbg)        // (Options::debug bit 0: residual bounds and Ritz values of the previous pairs)
                 for (int q = 0; q < NB; ++q) { dbg[(size_t)b * 2 * NB + q] = 2.5 * mu_old[q] * sqrt(res2[q]); dbg[(size_t)b * 2 * NB + NB + q] = sigma + mu_old[q]; }
             const int nd = ndefl ? ndefl[b] : 0;
             const int cert0 = inertia ? inertia[b] : -2;     // certified #{lambda < vu}; -1: not certifiable, -2: none
@@ -2151,7 +2151,7 @@ __global__ __launch_bounds__(256) void ss_rr_kernel(const int *__restrict__ ns, 
                 for (int q = 0; q < max(k, 1); ++q) ok = ok && (2.5 * mu_old[q] * sqrt(res2[q]) <= SS_TOL);
                 if (ok) st |= 1 | (k << 4) | (max(k, 1) << 8);
             } else {
-                // no certificate (SAAMGE_AMD_SS_CERTIFY=0): residual bounds of the wanted pairs; the first unwanted
+                // no certificate (Options::eig_certify = 0): residual bounds of the wanted pairs; the first unwanted
                 // one has to be pinned above the window (an eigenvalue lies within the bound of its Ritz value)
                 bool ok = true;
                 for (int q = 0; q < max(k, 1); ++q) ok = ok && (2.5 * mu_old[q] * sqrt(res2[q]) <= SS_TOL);
@@ -3053,11 +3053,6 @@ static void ss_factor_blocked(hipStream_t s, EigBatch &b, bool sgn, int *neg, in
     SA_HIP_CHECK(hipGetLastError());
 }
 
-bool eig_ss_band_enabled() {
-    static const bool v = true;
-    return v;
-}
-
 // C - sigma I = L L^T for every matrix of the batch (in place, L below / L^T above the diagonal).
 // Returns false when a pivot was not positive.
 // Blocked right-looking factorisation of every matrix in place, two panels per pass over the trailing
@@ -3069,8 +3064,8 @@ static void ss_factor_generic(hipStream_t s, EigBatch &b, bool sgn, int *neg, in
     const int nmax = b.max_n;
     const bool prof = profiler().enabled;
     const int *gbw_all = bws ? bws : (sgn ? b.bw.p : nullptr);
-    if (options().eig_outer_panels >= 8) return ss_factor_blocked<8>(s, b, sgn, neg, info_p, gbw_all, bwmax, keep, skip);
-    if (options().eig_outer_panels >= 4) return ss_factor_blocked<4>(s, b, sgn, neg, info_p, gbw_all, bwmax, keep, skip);
+    if (b.opt.eig_outer_panels >= 8) return ss_factor_blocked<8>(s, b, sgn, neg, info_p, gbw_all, bwmax, keep, skip);
+    if (b.opt.eig_outer_panels >= 4) return ss_factor_blocked<4>(s, b, sgn, neg, info_p, gbw_all, bwmax, keep, skip);
     // Two halves of the batch on two streams (round 4): a panel is a latency chain (one workgroup per matrix: diagonal block by
     // one wavefront, then the panel rows), the trailing update is compute-bound -- one half's panels run beside the other half's
     // updates.  Every per-matrix array of the kernels is indexed by the matrix alone, so a half is the same launch with the
@@ -3170,33 +3165,23 @@ bool eig_subspace_factor(hipStream_t s, EigBatch &b) {
     SA_REQUIRE(b.has_window, "few-eigenpairs path: the eigenvalue window must be set before the factorisation");
     DBuf<int> info((size_t)b.count);
     info.zero(s);
-    // banded factorisation (SAAMGE_AMD_SS_BAND=0: treat every matrix as full)
-    const bool use_band = eig_ss_band_enabled();
-    const int *bws = nullptr;
-    int bwmax = nmax;
-    b.h_bw.clear();
-    if (use_band) {
-        if (!b.has_bw) {          // (the fused assembly has already measured them on the sparse rows)
-            if (b.bw.n < (size_t)b.count) b.bw.alloc((size_t)b.count);
-            profiler().begin(s);
-            SA_HIP_CHECK(hipMemsetAsync(b.bw.p, 0, sizeof(int) * (size_t)b.count, s));
-            const int ny = std::max(1, std::min(32, std::min(nmax / 64, 4096 / std::max(1, b.count))));
-            hipLaunchKernelGGL(ss_band_kernel, dim3(b.count, ny), dim3(256), 0, s, b.n.p, b.moff.p, b.W.p, b.bw.p);
-            profiler().end(s, "eig_ss_band", 0.0, 0.0);
-        }
-        b.h_bw.resize((size_t)b.count);
-        SA_HIP_CHECK(hipMemcpyAsync(b.h_bw.data(), b.bw.p, sizeof(int) * (size_t)b.count, hipMemcpyDeviceToHost, s));
-        SA_HIP_CHECK(hipStreamSynchronize(s));
-        bwmax = 0;
-        for (int v : b.h_bw) bwmax = std::max(bwmax, v);
-        bws = b.bw.p;
-    } else {                      // full matrices: bandwidth n - 1 (the inertia pass wants explicit widths)
-        std::vector<int> full((size_t)b.count);
-        for (int i = 0; i < b.count; ++i) full[i] = b.h_n[i] - 1;
-        b.bw.from_host(full, s);
+    // banded factorisation
+    if (!b.has_bw) {          // (the fused assembly has already measured them on the sparse rows)
+        if (b.bw.n < (size_t)b.count) b.bw.alloc((size_t)b.count);
+        profiler().begin(s);
+        SA_HIP_CHECK(hipMemsetAsync(b.bw.p, 0, sizeof(int) * (size_t)b.count, s));
+        const int ny = std::max(1, std::min(32, std::min(nmax / 64, 4096 / std::max(1, b.count))));
+        hipLaunchKernelGGL(ss_band_kernel, dim3(b.count, ny), dim3(256), 0, s, b.n.p, b.moff.p, b.W.p, b.bw.p);
+        profiler().end(s, "eig_ss_band", 0.0, 0.0);
     }
+    b.h_bw.resize((size_t)b.count);
+    SA_HIP_CHECK(hipMemcpyAsync(b.h_bw.data(), b.bw.p, sizeof(int) * (size_t)b.count, hipMemcpyDeviceToHost, s));
+    SA_HIP_CHECK(hipStreamSynchronize(s));
+    int bwmax = 0;
+    for (int v : b.h_bw) bwmax = std::max(bwmax, v);
+    const int *bws = b.bw.p;
     b.ss_bwmax = bwmax;
-    if ((options().debug & 1)) {
+    if ((b.opt.debug & 1)) {
         int bwmin = nmax;
         for (int v : b.h_bw) bwmin = std::min(bwmin, v);
         std::fprintf(stderr, "subspace: %d matrices, n max %d, half bandwidth %d .. %d\n", b.count, nmax, b.h_bw.empty() ? nmax : bwmin, bwmax);
@@ -3211,14 +3196,14 @@ bool eig_subspace_factor(hipStream_t s, EigBatch &b) {
     // ---- certified count: inertia of C - vu I, before the matrices are shifted and overwritten ----
     // (dsygvx counts by bisection, amg/src/xpacks.cpp:226-268; a subspace iteration alone cannot prove
     // that no eigenvalue below vu is missing from its block)
-    const bool certify = options().eig_certify != 0;
+    const bool certify = b.opt.eig_certify != 0;
     b.h_inertia.clear();
     b.ss_save = nullptr;
     // Wide-band matrices (coarse levels): a certified count of 0 means that the inertia pass met positive pivots
     // only, i.e. it WAS the Cholesky factorisation of C - vu I -- and vu is the best shift such a matrix can get
     // (its one wanted pair is the smallest).  Those matrices keep that factor: no restore, no second factorisation
-    // (SAAMGE_AMD_SS_REUSE=0: factor twice as before).
-    const bool reuse = options().eig_keep_inertia_factor != 0;
+    // (Options::eig_keep_inertia_factor = 0: factor twice as before).
+    const bool reuse = b.opt.eig_keep_inertia_factor != 0;
     bool generic_inertia = false;
     if (certify) {
         DBuf<int> neg((size_t)b.count);
@@ -3293,11 +3278,11 @@ bool eig_subspace_factor(hipStream_t s, EigBatch &b) {
     }
     for (size_t i = 0; i < b.h_inertia.size(); ++i)
         if (b.h_inertia[i] > (b.ss_nb == 16 ? 16 - 2 : SS_WANT_MAX) || b.h_inertia[i] < 0) {
-            SA_REQUIRE(!options().eig_strict, "few-eigenpairs path: a matrix has more wanted pairs than the block holds, or no certificate (strict mode)");
+            SA_REQUIRE(!b.opt.eig_strict, "few-eigenpairs path: a matrix has more wanted pairs than the block holds, or no certificate (strict mode)");
             mark_bad((int)i);
         }
-    if (options().eig_force_fallback > 0) {      // tests: every k-th matrix takes the per-matrix fallback
-        const int every = options().eig_force_fallback;
+    if (b.opt.eig_force_fallback > 0) {      // tests: every k-th matrix takes the per-matrix fallback
+        const int every = b.opt.eig_force_fallback;
         for (int i = 3; every > 0 && i < b.count; i += every) mark_bad(i);
     }
     if (too_many_bad()) return false;
@@ -3338,12 +3323,12 @@ bool eig_subspace_factor(hipStream_t s, EigBatch &b) {
     // one pass over the band): they skip the second factorisation, the solves and the Rayleigh-Ritz steps, which
     // then run on a dense list of the others (85 % of the level-0 agglomerates of the 256^3 problem are of this
     // kind; the iteration accepted them after its first step anyway, at the price of a factorisation and two
-    // solves each).  SAAMGE_AMD_SS_NULLCHECK=0 switches the shortcut off.
+    // solves each).  Options::eig_nullcheck = 0 switches the shortcut off.
     b.h_pre.clear();
     DBuf<int> chol_active;
     int nchol = b.count;
     bool use_chol_list = false;
-    const bool nullcheck = options().eig_nullcheck != 0;
+    const bool nullcheck = b.opt.eig_nullcheck != 0;
     const bool generic_reuse = generic_inertia && reuse;
     if ((lds_path || generic_reuse) && nullcheck && !b.h_inertia.empty()) {
         profiler().begin(s);
@@ -3356,7 +3341,7 @@ bool eig_subspace_factor(hipStream_t s, EigBatch &b) {
         profiler().end(s, "eig_ss_nullcheck", cb, 0.0);
         auto hp = b.pre.to_host(s);
         b.h_pre.assign(hp.begin(), hp.end());
-        if ((options().debug & 1) && !lds_path) {
+        if ((b.opt.debug & 1) && !lds_path) {
             auto hv = b.pre_val.to_host(s);
             int shown = 0;
             for (int i = 0; i < b.count && shown < 12; ++i)
@@ -3391,7 +3376,7 @@ bool eig_subspace_factor(hipStream_t s, EigBatch &b) {
             hipLaunchKernelGGL(ss_shift_kernel, dim3(b.count), dim3(256), 0, s, b.n.p, b.moff.p, b.W.p, 0.0, d_shifts.p);
             SA_HIP_CHECK(hipStreamSynchronize(s));     // (d_shifts leaves scope)
         }
-        if ((options().debug & 1))
+        if ((b.opt.debug & 1))
             std::fprintf(stderr, "subspace: %d of %d wide-band matrices keep the factor of the inertia pass, %d are factored again\n",
                          nkeep, b.count, nfactor);
     } else
@@ -3419,10 +3404,10 @@ bool eig_subspace_factor(hipStream_t s, EigBatch &b) {
     auto h = info.to_host(s);
     for (int i = 0; i < b.count; ++i)
         if (h[i] && !b.h_bad[i]) {         // a non-positive pivot: that matrix alone
-            if ((options().debug & 1))
+            if ((b.opt.debug & 1))
                 std::fprintf(stderr, "subspace: non-positive pivot in matrix %d (n %d, band %d, inertia %d, sigma %g)\n", i, b.h_n[i],
                              b.h_bw.empty() ? -1 : b.h_bw[i], b.h_inertia.empty() ? -2 : b.h_inertia[i], b.h_sigma[i]);
-            SA_REQUIRE(!options().eig_strict, "few-eigenpairs path: non-positive pivot (strict mode)");
+            SA_REQUIRE(!b.opt.eig_strict, "few-eigenpairs path: non-positive pivot (strict mode)");
             mark_bad(i);
         }
     return !too_many_bad();
@@ -3449,7 +3434,7 @@ bool eig_subspace_iterate(hipStream_t s, EigBatch &b, double vu) {
     slow_hist.zero(s);
     // wide-band matrices with a saved band: a matrix (certified count 0) that converges too slowly may ask once
     // for a new shift (state bit 2, ss_rr_kernel); the host then restores the bands, shifts that matrix to just
-    // below its smallest Ritz value and factors the batch again (SAAMGE_AMD_SS_RESHIFT=0: never)
+    // below its smallest Ritz value and factors the batch again
     constexpr bool reshift_env = true;
     const bool reshift_on = reshift_env && b.max_n > 1280 && b.ss_save && !b.h_inertia.empty() && b.h_sigma.size() == (size_t)b.count;
     DBuf<int> reshift_ok;
@@ -3473,7 +3458,7 @@ bool eig_subspace_iterate(hipStream_t s, EigBatch &b, double vu) {
         b.ss_Vlock.alloc((size_t)b.h_voff[b.count] * SS_LOCK_PITCH);
         b.ss_has_lock = true;
     }
-    if ((options().debug & 1) && b.max_n > 1280 && !b.h_inertia.empty()) {
+    if ((b.opt.debug & 1) && b.max_n > 1280 && !b.h_inertia.empty()) {
         std::fprintf(stderr, "subspace: certified counts (bad):");
         for (int i = 0; i < b.count; ++i) std::fprintf(stderr, " %d%s", b.h_inertia[i], b.h_bad[i] ? "*" : "");
         std::fprintf(stderr, "\n");
@@ -3534,7 +3519,7 @@ bool eig_subspace_iterate(hipStream_t s, EigBatch &b, double vu) {
         const size_t win_bytes = sizeof(double) * (size_t)NB * (size_t)wr;
         if (b.max_n > 768 && !no_win && win_bytes <= 150 * 1024) {
             // more matrices than CUs: the variant without requests ahead, two workgroups per CU (config 5 at 64^3: solves 448 -> 397 ms
-            // per step; SAAMGE_AMD_SS_TRSOLVE_TWO=0: one per CU always)
+            // per step)
             constexpr bool two_env = true;
             auto go = [&](auto lo, auto up) {
                 SA_HIP_CHECK(hipFuncSetAttribute((const void *)lo, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
@@ -3570,7 +3555,7 @@ bool eig_subspace_iterate(hipStream_t s, EigBatch &b, double vu) {
             profiler().end(s, b.max_n <= 1280 ? "eig_ss_solve" : "eig_ss_solve_g", ab, 0.0);
             profiler().begin(s);
         }
-        const bool dbg_on = (options().debug & 1) != 0;
+        const bool dbg_on = (b.opt.debug & 1) != 0;
         DBuf<double> dbgbuf;
         if (dbg_on) dbgbuf.alloc((size_t)b.count * 2 * NB);
         if (any_lock)
@@ -3619,7 +3604,7 @@ bool eig_subspace_iterate(hipStream_t s, EigBatch &b, double vu) {
                                        b.ss_Vlock.p, b.ss_lock_mu.p, b.ss_ndefl.p, it0.p, iter, state.p, slow_hist.p);
                     SA_HIP_CHECK(hipGetLastError());
                     SA_HIP_CHECK(hipStreamSynchronize(s));
-                    if ((options().debug & 1))
+                    if ((b.opt.debug & 1))
                         std::fprintf(stderr, "subspace: iteration %d, six pairs of %zu matrices locked (first: matrix %d)\n", iter, req.size(), req[0]);
                 }
             }
@@ -3628,14 +3613,14 @@ bool eig_subspace_iterate(hipStream_t s, EigBatch &b, double vu) {
             for (int i = 0; i < b.count; ++i) {
                 const int v = hstate[i];
                 if ((v & 2) && !b.h_bad[i]) {     // gave up during the iteration (too many pairs, breakdown, hopeless rate)
-                    SA_REQUIRE(!options().eig_strict, "few-eigenpairs path gave up on a matrix (strict mode)");
+                    SA_REQUIRE(!b.opt.eig_strict, "few-eigenpairs path gave up on a matrix (strict mode)");
                     mark_bad(i);
                 }
                 if (!(v & 3)) done = false;
                 else ++nconv;
             }
             if (too_many_bad()) failed = true;
-            if (failed && (options().debug & 1)) {
+            if (failed && (b.opt.debug & 1)) {
                 std::fprintf(stderr, "subspace: iteration %d: too many matrices gave up (states:", iter);
                 for (int i = 0; i < b.count && i < 64; ++i) std::fprintf(stderr, " %x", hstate[i]);
                 std::fprintf(stderr, ")\n");
@@ -3698,17 +3683,17 @@ bool eig_subspace_iterate(hipStream_t s, EigBatch &b, double vu) {
                     });
                     SA_HIP_CHECK(hipGetLastError());
                     SA_HIP_CHECK(hipStreamSynchronize(s));
-                    if ((options().debug & 1))
+                    if ((b.opt.debug & 1))
                         std::fprintf(stderr, "subspace: iteration %d, %zu matrices factored again at a shift below their smallest Ritz value\n", iter, req.size());
                     if (too_many_bad()) failed = true;
-                    if (failed && (options().debug & 1)) {
+                    if (failed && (b.opt.debug & 1)) {
                         std::fprintf(stderr, "subspace: iteration %d: the factorisation at the new shifts failed (info:", iter);
                         for (int i = 0; i < b.count && i < 64; ++i) std::fprintf(stderr, " %d", hi2[i]);
                         std::fprintf(stderr, ")\n");
                     }
                 }
             }
-            const bool dbg = (options().debug & 1) != 0;
+            const bool dbg = (b.opt.debug & 1) != 0;
             if (dbg) std::fprintf(stderr, "subspace: iteration %d, %d of %d matrices accepted (n max %d)\n", iter, nconv, b.count, b.max_n);
             if (failed) break;
             h_active.clear();
@@ -3721,14 +3706,14 @@ bool eig_subspace_iterate(hipStream_t s, EigBatch &b, double vu) {
     SA_HIP_CHECK(hipGetLastError());
     if (!prof) profiler().end(s, "eig_ss_iterate", 0.0, 0.0);
     if (!failed && !done) {      // out of iterations: the unfinished matrices go to the dense path
-        SA_REQUIRE(!options().eig_strict, "few-eigenpairs path: no convergence (strict mode)");
+        SA_REQUIRE(!b.opt.eig_strict, "few-eigenpairs path: no convergence (strict mode)");
         { auto t = state.to_host(s); hstate.assign(t.begin(), t.end()); }
         for (int i = 0; i < b.count; ++i) if (!(hstate[i] & 3)) mark_bad(i);
         if (too_many_bad()) failed = true;
     }
     if (failed) {
-        // (SAAMGE_AMD_SS_STRICT: the tests of this path must not pass on the dense fallback)
-        SA_REQUIRE(!options().eig_strict, "few-eigenpairs path gave up on a batch (strict mode)");
+        // (Options::eig_strict: the tests of this path must not pass on the dense fallback)
+        SA_REQUIRE(!b.opt.eig_strict, "few-eigenpairs path gave up on a batch (strict mode)");
         return false;
     }
     // certification: the number of Ritz values inside the window must be the number of eigenvalues
@@ -3741,12 +3726,12 @@ bool eig_subspace_iterate(hipStream_t s, EigBatch &b, double vu) {
             if (b.h_inertia[i] < 0) { ++unsure; mark_bad(i); }
             else if (b.h_inertia[i] != k) { ++bad; mark_bad(i); }
         }
-        const bool dbg = (options().debug & 1) != 0;
+        const bool dbg = (b.opt.debug & 1) != 0;
         if (dbg || bad || unsure)
             std::fprintf(stderr, "saamge_amd: few-eigenpairs batch of %d: %d counts contradicted by the inertia, %d uncertified\n",
                          b.count, bad, unsure);
         if (bad || unsure) {
-            SA_REQUIRE(!options().eig_strict, "few-eigenpairs path: count not certified (strict mode)");
+            SA_REQUIRE(!b.opt.eig_strict, "few-eigenpairs path: count not certified (strict mode)");
             if (too_many_bad()) return false;
         }
     }

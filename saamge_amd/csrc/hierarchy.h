@@ -11,6 +11,7 @@
 #include "common.h"
 #include "eig.h"
 #include "mis.h"
+#include "options.h"
 #include "sparse.h"
 #include "topology.h"
 
@@ -55,6 +56,7 @@ struct Params {                 // MultilevelParameters (amg/inc/ml.hpp:59-114)
     int algebraic = 0;            // element-free mode (tg_produce_data_algebraic): elements = dofs
     int eigensolver = 0;          // 0 few-eigenpairs path (certified count, dense fallback), 1 dense path only
     double eig_tol = 1e-12;       // few-eigenpairs path: acceptance bound of a Ritz pair's residual
+    Options opt;                  // saamge_amd_params.options: what the hierarchy uses for its whole life
 };
 
 struct NextPrep {               // host half of the next level's inputs (prepare_next_host)

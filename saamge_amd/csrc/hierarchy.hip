@@ -14,11 +14,6 @@
 
 namespace saamge_amd {
 
-Profiler &profiler() {
-    static Profiler p;
-    return p;
-}
-
 // smpr_sas_poly_roots (amg/src/smpr.cpp:282-306)
 static std::vector<double> sas_poly_roots(int nu) {
     SA_REQUIRE(nu > 0, "nu_relax must be positive");
@@ -243,20 +238,20 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
     std::thread op_thread;
     std::exception_ptr op_err;
     struct OpJoiner { std::thread &t; ~OpJoiner() { if (t.joinable()) t.join(); } } op_joiner{op_thread};
-    const bool op_early = lev == 0 && din && !env_serial() && !profiler().enabled && H.galerkin_lev < 0 && (options().overlap & 8);
+    const bool op_early = lev == 0 && din && !env_serial() && !profiler().enabled && H.galerkin_lev < 0 && (P.opt.overlap & 8);
     if (op_early) {
         hipStream_t os = side_stream(6);
         const int dev0 = current_device();
         SA_HIP_CHECK(hipStreamSynchronize(s));          // (the operator's arrays are complete)
-        op_thread = std::thread([&L, &op_err, os, dev0]() {
+        op_thread = std::thread([&L, &P, &op_err, os, dev0]() {
             try {
                 adopt_device(dev0);
                 set_thread_stream(os);
-                build_sell(os, L.A);
+                build_sell(os, L.A, P.opt);
                 L.dinv_neg.alloc((size_t)L.A.nrows);
                 DBuf<double> tmp((size_t)L.A.nrows);
                 build_dinv_neg(os, L.A, tmp.p, L.dinv_neg.p);
-                build_dinv_codes(os, L.A, L.dinv_neg.p);
+                build_dinv_codes(os, L.A, L.dinv_neg.p, P.opt);
                 SA_HIP_CHECK(hipStreamSynchronize(os));
             } catch (...) { op_err = std::current_exception(); }
         });
@@ -317,7 +312,7 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
         try {
             adopt_device(dev);   // the worker allocates and copies: same GPU as the caller
             set_thread_stream(mis_stream);
-            // MIS tables on the device (SAAMGE_AMD_HOST_MIS=1: host build); aggregates with arbitration are
+            // MIS tables on the device; aggregates with arbitration are
             // sequential by definition and stay on the host
             constexpr bool host_mis = false;      // (the host build stays the fallback after a hash collision and for aggregates with arbitration)
             PhaseTimer tmis(mis_stream);
@@ -346,11 +341,11 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
     // Galerkin product of the finer level): then after the eigenproblems, which do not read it
     auto operator_data = [&]() {
         join_galerkin(H);
-        build_sell(s, L.A);
+        build_sell(s, L.A, P.opt);
         L.dinv_neg.alloc((size_t)L.A.nrows);
         DBuf<double> tmp((size_t)L.A.nrows);
         build_dinv_neg(s, L.A, tmp.p, L.dinv_neg.p);
-        build_dinv_codes(s, L.A, L.dinv_neg.p);
+        build_dinv_codes(s, L.A, L.dinv_neg.p, P.opt);
         SA_HIP_CHECK(hipStreamSynchronize(s));
     };
     const bool operator_pending = H.galerkin_lev >= 0;
@@ -430,16 +425,16 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
     std::vector<DBuf<double>> kept;          // packed eigenpairs of the chunks' representatives
     std::vector<int> cls_of[2];              // per slot: class of every agglomerate of the chunk (empty: no classes)
     std::vector<int> solve_cls[2];           // per slot: classes of the matrices of the batch that is solved, in its order
-    const bool dedupe = options().eig_dedupe != 0 && !(P.testmesh && lev == 0);
+    const bool dedupe = P.opt.eig_dedupe != 0 && !(P.testmesh && lev == 0);
     bool dedupe_level = true;
     int pend_ae0[2] = {0, 0}, pend_cnt[2] = {0, 0};
     int64_t pend_row0[2] = {0, 0};
     // The subspace iteration of a chunk (a few hundred to a few thousand small matrices still active: launches that
     // fill a fraction of the chip, with a host round trip every few iterations) runs on its own thread and stream
-    // BESIDE the assembly and the factorisations of the next chunk (SAAMGE_AMD_EIG_OVERLAP=0: one after the other).
+    // BESIDE the assembly and the factorisations of the next chunk (Options::overlap bit 0 cleared: one after the other).
     // Only eig_subspace_iterate runs there: it touches its own batch (the other workspace slot) and nothing else;
     // everything that assembles or allocates workspace stays on this thread.
-    const bool overlap_env = (options().overlap & 1) && !env_serial();
+    const bool overlap_env = (P.opt.overlap & 1) && !env_serial();
     const bool overlap_iter = overlap_env && !profiler().enabled;
     hipStream_t iter_stream = overlap_iter ? side_stream(3) : s;
     std::thread iter_thread;
@@ -576,7 +571,7 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
             r.a = a;
             r.b = e;
             EigBatch sub;
-            eig_batch_alloc(sub, std::vector<int>(sizes.begin() + ae0 + a, sizes.begin() + ae0 + e), qb, slot);
+            eig_batch_alloc(sub, std::vector<int>(sizes.begin() + ae0 + a, sizes.begin() + ae0 + e), P.opt, qb, slot);
             sub.dense_only = true;
             sub.set_window(L.theta);
             int64_t rows_before = 0;
@@ -651,7 +646,7 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
         const int slot = idx & 1;
         EigBatch &batch = batches[slot];
         batch = EigBatch();
-        eig_batch_alloc(batch, std::vector<int>(sizes.begin() + ae0, sizes.begin() + ae0 + cnt), qa, slot);
+        eig_batch_alloc(batch, std::vector<int>(sizes.begin() + ae0, sizes.begin() + ae0 + cnt), P.opt, qa, slot);
         batch.dense_only = P.eigensolver == 1;
         batch.ss_tol = P.eig_tol;
         batch.set_window(L.theta);
@@ -676,7 +671,7 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
             bool found = classes.early;
             if (!found && !classes.searched && batch.has_bw) {      // (distinct sparse rows: distinct matrices)
                 src = eig_dedupe_source(batch);
-                found = eig_dedupe_find(qa, src, cnt, batch.max_n, classes.cls);
+                found = eig_dedupe_find(qa, src, cnt, batch.max_n, classes.cls, P.opt.debug);
             }
             // a level whose first chunk has (almost) no identical agglomerates is not searched further: variable coefficients
             if (!found && lvl_classes.empty()) dedupe_level = false;
@@ -874,6 +869,7 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
         io.extra = nextra ? L.extra.p : nullptr;
         io.nextra = nextra;
         io.ND = L.A.nrows;
+        io.debug = P.opt.debug;
         if (world > 1) {
             // every rank takes a contiguous range of MISes (balanced by the r c^2 cost of the SVDs) and the bases,
             // singular values and counts are all-gathered in place: the counterpart of the reference's
@@ -909,7 +905,7 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
             DBuf<int> d_ev;
             bool any = false;
             for (int v_ : L.ae_evclass) any = any || v_ >= 0;
-            if (any && options().eig_dedupe != 0 && !(P.testmesh && lev == 0)) d_ev.from_host(L.ae_evclass, s);
+            if (any && P.opt.eig_dedupe != 0 && !(P.testmesh && lev == 0)) d_ev.from_host(L.ae_evclass, s);
             mis_svd(s, L.drel, nm, max_ctot, io, 0, d_ev.n ? d_ev.p : nullptr);
         }
         { auto t_ = L.d_mis_k.to_host(s); L.mis_k.assign(t_.begin(), t_.end()); }
@@ -966,8 +962,8 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
         });
     }
     // With another spectral level to come the product runs beside that level's element matrices and
-    // eigenproblems (they need its size only); SAAMGE_AMD_NO_OVERLAP=1 and the profiled step keep it in line.
-    const bool no_overlap = !(options().overlap & 4) || env_serial();
+    // eigenproblems (they need its size only); Options::overlap bit 2 cleared and the profiled step keep it in line.
+    const bool no_overlap = !(P.opt.overlap & 4) || env_serial();
     const bool defer = lev + 1 < P.num_coarsenings && P.nu_pro[lev] == 0 && world == 1 && !no_overlap &&
                        !profiler().enabled;
     if (defer) {
@@ -1159,7 +1155,7 @@ static Table prepare_next_level(Hierarchy &H, int lev) {
             ++cnt;
         }
         EigBatch batch;
-        eig_batch_alloc(batch, std::vector<int>(sizes.begin() + ae0, sizes.begin() + ae0 + cnt), s);
+        eig_batch_alloc(batch, std::vector<int>(sizes.begin() + ae0, sizes.begin() + ae0 + cnt), H.params.opt, s);
         std::vector<int64_t> soff((size_t)cnt + 1, 0);
         for (int i = 0; i < cnt; ++i) soff[i + 1] = soff[i] + (int64_t)sizes[ae0 + i] * e2d.row_size(ae0 + i);
         DBuf<int64_t> d_soff;
@@ -1175,7 +1171,7 @@ static Table prepare_next_level(Hierarchy &H, int lev) {
             int kmax = 0;
             for (int km : L.mis_k) kmax = std::max(kmax, km);
             // (classes of the agglomerates' sparse rows, where the eigenproblem stage found them for every agglomerate of the range)
-            bool have_classes = options().eig_dedupe != 0 && (int)L.ae_class.size() == nparts;
+            bool have_classes = H.params.opt.eig_dedupe != 0 && (int)L.ae_class.size() == nparts;
             for (int i = ae0; have_classes && i < ae0 + cnt; ++i) have_classes = L.ae_class[i] >= 0;
             if (have_classes && !d_ae_class.n) d_ae_class.from_host(L.ae_class, s);
             coarse_elmats_sparse(s, L.drel, ae0, batch, RW, rv, rc, L.d_mis_k.p, L.d_mis_u_off.p, L.mis_U.p,
@@ -1214,7 +1210,7 @@ static void setup_coarse_solver(Hierarchy &H) {
     DCsr &Ac = H.levels.back()->Ac;
     hipStream_t s = H.stream;
     const size_t n = (size_t)Ac.nrows;
-    build_sell(s, Ac);
+    build_sell(s, Ac, H.params.opt);
     H.coarse_kind = 2;
     H.c_dinv.alloc(n);
     H.c_r.alloc(n); H.c_z.alloc(n); H.c_d.alloc(n); H.c_q.alloc(n); H.c_t0.alloc(n); H.c_t1.alloc(n);
@@ -1517,7 +1513,7 @@ static void add_nullspace_level(Hierarchy &H) {
     N.theta = 0.0;
     N.nu_relax = 3;
     N.roots = sas_poly_roots(3);
-    build_sell(s, N.A);
+    build_sell(s, N.A, H.params.opt);
     N.dinv_neg.alloc((size_t)nc);
     {
         DBuf<double> tmp((size_t)nc);
@@ -1677,7 +1673,7 @@ Hierarchy *hierarchy_create(int n, const void *Arow, int rowptr_bits, const int 
         hvec<int> part;
         if (lev > 0) part = H.coarse_parts[(size_t)lev];
         else if (!dev_inputs) part = fetch_host(partitions[lev], (size_t)n_elem, s);
-        const bool tag_levels = (options().debug & 4) != 0;
+        const bool tag_levels = (H.params.opt.debug & 4) != 0;
         profiler().level_tag = tag_levels ? lev : 0;
         build_level(H, lev, std::move(e2d), part, nparts[lev], (lev == 0 && bdr && !dev_inputs) ? bdr_h.data() : nullptr,
                     (lev == 0 && dev_inputs) ? &din : nullptr);
@@ -1746,11 +1742,11 @@ void hierarchy_update_operators(Hierarchy &H, const double *new_val) {
     }
     for (int lev = 0; lev < nspec; ++lev) {
         Level &L = *H.levels[lev];
-        build_sell(s, L.A);
+        build_sell(s, L.A, H.params.opt);
         {
             DBuf<double> tmp((size_t)L.A.nrows);
             build_dinv_neg(s, L.A, tmp.p, L.dinv_neg.p);
-            build_dinv_codes(s, L.A, L.dinv_neg.p);
+            build_dinv_codes(s, L.A, L.dinv_neg.p, H.params.opt);
             SA_HIP_CHECK(hipStreamSynchronize(s));
         }
         L.Ac = DCsr();
@@ -1759,7 +1755,7 @@ void hierarchy_update_operators(Hierarchy &H, const double *new_val) {
     }
     if (H.params.correct_nullspace) {   // the scaling_P level: same interpolation, new operators
         Level &N = *H.levels.back();
-        build_sell(s, N.A);
+        build_sell(s, N.A, H.params.opt);
         DBuf<double> tmp((size_t)N.A.nrows);
         build_dinv_neg(s, N.A, tmp.p, N.dinv_neg.p);
         SA_HIP_CHECK(hipStreamSynchronize(s));

@@ -20,6 +20,7 @@ struct MisSvdIO {
     int *k = nullptr;                   // [num_mises] kept vectors  (mis_numcoarsedof)
     int *ncols = nullptr;               // [num_mises] columns that entered the SVD
     int avoid_ess = 1;
+    int debug = 0;                      // Options::debug (bit 0: the census of identical MISes)
     // extra per-dof modes appended after the spectral columns (ExtendWithPolynomials / RBMs,
     // amg/src/contrib.cpp:302-436): ND x nextra, column-major; level 0 only
     const double *extra = nullptr;

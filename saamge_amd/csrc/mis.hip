@@ -354,7 +354,7 @@ void mis_svd(hipStream_t s, const DevRelations &rel, int num_mises, int max_ctot
         SA_HIP_CHECK(hipStreamSynchronize(s));
         const int nrep = last[0] + last[1];
         profiler().end(s, "eig_dedupe", 0.0, 0.0);
-        if (options().debug & 1) std::fprintf(stderr, "MISes: %d distinct of %d\n", nrep, nm);
+        if (io.debug & 1) std::fprintf(stderr, "MISes: %d distinct of %d\n", nrep, nm);
         profiler().begin(s);
         hipLaunchKernelGGL(mis_svd_kernel, dim3(nrep), dim3(64), lds, s, rel.mis2d_I.p,
                            rel.mis2d_J.p, rel.mis2ae_I.p, rel.mis2ae_J.p, rel.ae2d_I.p,

@@ -1,6 +1,7 @@
 // CSR SpMV family, fused polynomial-smoother step, vector kernels (launch wrappers).
 #pragma once
 #include "common.h"
+#include "options.h"
 
 namespace saamge_amd {
 
@@ -10,8 +11,8 @@ struct RowRange {
     int row0 = 0, nrows = -1;
 };
 
-// build the SELL-64 copy of A (used by every routine below when present)
-void build_sell(hipStream_t s, DCsr &A);
+// build the SELL-64 copy of A (used by every routine below when present); of `opt`: sell and debug
+void build_sell(hipStream_t s, DCsr &A, const Options &opt);
 // y = A x
 void spmv(hipStream_t s, const DCsr &A, const double *x, double *y, RowRange rr = RowRange());
 // r = b - A x                                   (reference: amg/src/tg.cpp:115-116)
@@ -29,7 +30,7 @@ void smooth_first(hipStream_t s, int n, const double *dinv_neg, const double *b,
 //                                               (reference: amg/src/mbox.cpp:1839-1861)
 void build_dinv_neg(hipStream_t s, const DCsr &A, double *sqrt_diag_tmp, double *dinv_neg);
 // byte codes of the smoother's diagonal factor (operators with <= 256 distinct values of it and the staged coded format)
-void build_dinv_codes(hipStream_t s, DCsr &A, const double *dinv_neg);
+void build_dinv_codes(hipStream_t s, DCsr &A, const double *dinv_neg, const Options &opt);
 
 // deterministic dot product: out[0] = sum a_i b_i ; `partials` holds >= 1024 doubles
 void dot(hipStream_t s, int n, const double *a, const double *b, double *partials, double *out);

@@ -543,7 +543,7 @@ struct SellLeftover {
     const unsigned *codes;
 };
 // PAT: the tiles' row patterns (sell_staged2_kernel); without: every staged tile's code words (sell_staged2_codes_kernel,
-// options().sell bit 6).  Two kernels, not a run-time switch: the code words of the second are in flight across the staging,
+// Options::sell bit 6).  Two kernels, not a run-time switch: the code words of the second are in flight across the staging,
 // and one body holding both would need 66 registers (seven workgroups per CU instead of eight).
 template <int MODE, bool PAT>
 __device__ __forceinline__ void sell_staged2(double *lds, const SellLeftover &left, int nrows, int row0, int nblocks, int per_xcd,
@@ -1495,7 +1495,7 @@ void export_rowptr32(int *dst_host, const DBuf<roff_t> &src, size_t n, hipStream
     SA_HIP_CHECK(hipStreamSynchronize(s));
 }
 
-void build_sell(hipStream_t s, DCsr &A) {
+void build_sell(hipStream_t s, DCsr &A, const Options &opt) {
     A.has_sell = false;
     A.sell_dcode.release();      // (codes of the smoother's diagonal belong to the operator they were made for: build_dinv_codes)
     A.sell_dsrc = nullptr;
@@ -1516,13 +1516,13 @@ void build_sell(hipStream_t s, DCsr &A) {
                        A.val.p, A.sell_ptr.p, A.sell_col.p, A.sell_val.p);
     SA_HIP_CHECK(hipGetLastError());
     // byte codes for the slices with few distinct column offsets (saamge_amd_options.sell bit 0 cleared: none)
-    const bool no_codes = !(options().sell & 1);
+    const bool no_codes = !(opt.sell & 1);
     A.sell_ntab.alloc((size_t)A.nslices);
     A.sell_tab.alloc((size_t)A.nslices * 64);
     A.sell_code.alloc((size_t)total / 4 + (size_t)A.nslices * 64 + 64);
     A.sell_vtab.alloc((size_t)A.nslices * 64);
     // (bit 1 cleared: offset codes only, values always streamed)
-    const bool no_vals = !(options().sell & 2);
+    const bool no_vals = !(opt.sell & 2);
     constexpr bool no_share = false;
     if (no_codes)
         SA_HIP_CHECK(hipMemsetAsync(A.sell_ntab.p, 0xff, sizeof(int) * (size_t)A.nslices, s));
@@ -1547,7 +1547,7 @@ void build_sell(hipStream_t s, DCsr &A) {
     A.sell_stream_bytes = 4.0 * (double)h[6] + 12.0 * 64.0 * (double)(h[0] - h[8]) + 4.0 * 64.0 * (double)h[1] +
                           8.0 * (double)h[4] + 12.0 * (double)h[5] + 12.0 * (double)A.nslices;
     // operator-level pair dictionary for operators that are all plain slices (bit 3 cleared: never)
-    const bool no_gpair = !(options().sell & 8);
+    const bool no_gpair = !(opt.sell & 8);
     A.sell_gpair = false;
     if (!no_gpair && !no_codes && h[0] == 0 && h[1] == 0 && A.nnz >= (1 << 22) && A.ncols < (1 << 28)) {
         DBuf<int> st((size_t)GD_CAP), ctr(2);
@@ -1571,7 +1571,7 @@ void build_sell(hipStream_t s, DCsr &A) {
             A.sell_stream_bytes = 8.0 * words + 16.0 * (double)hc[0] + 8.0 * (double)A.nslices;
             A.sell_col.release();      // the dictionary replaces the streamed columns and values (12 B per stored entry)
             A.sell_val.release();
-            const bool no_bs3 = !(options().sell & 16);
+            const bool no_bs3 = !(opt.sell & 16);
             A.sell_bs3 = false;
             if (!no_bs3 && A.ncols == A.nrows && A.nrows >= 63) {
                 const int nwaves = div_up(A.nrows, 63), cap = A.nrows / 16 + 1;      // at most a sixteenth of the rows on their own
@@ -1589,13 +1589,13 @@ void build_sell(hipStream_t s, DCsr &A) {
             A.sell_gcode.release();
             A.sell_gtab.release();
         }
-        if ((options().debug & 2))
+        if ((opt.debug & 2))
             std::fprintf(stderr, "build_sell: operator-level pair dictionary: %d pairs%s%s\n", hc[0], A.sell_gpair ? "" : " (abandoned)",
                          A.sell_gpair && A.sell_bs3 ? ", 3 x 3 node blocks" : "");
-        if ((options().debug & 2) && A.sell_gpair)
+        if ((opt.debug & 2) && A.sell_gpair)
             std::fprintf(stderr, "build_sell: %d of %d rows outside regular node blocks\n", A.sell_nirr, A.nrows);
     }
-    const bool no_fast = !(options().sell & 4);
+    const bool no_fast = !(opt.sell & 4);
     A.sell_fast_ok = !no_fast && A.ncols < (1 << 29);      // (32-bit byte offsets into x on the short-chain path)
     // x-staging plan of the pair-coded tiles
     constexpr bool no_stage = false;
@@ -1631,7 +1631,7 @@ void build_sell(hipStream_t s, DCsr &A) {
             A.sell_tile_desc.alloc((size_t)ntiles);
             // row patterns (bit 6 set: none, every staged tile keeps its code words)
             int nslots = ntiles;
-            if (!(options().sell & 64)) {
+            if (!(opt.sell & 64)) {
                 A.sell_row_pat.alloc((size_t)ntiles * 256);
                 A.sell_tile_pat.alloc((size_t)ntiles * SELL_PMAX * 8);
                 A.sell_tile_pinfo.alloc((size_t)ntiles);
@@ -1656,10 +1656,10 @@ void build_sell(hipStream_t s, DCsr &A) {
             SA_HIP_CHECK(hipGetLastError());
         }
     }
-    if ((options().debug & 2))
+    if ((opt.debug & 2))
         std::fprintf(stderr, "build_sell: staging plan: %d of %d tiles, largest %d doubles, row patterns in %d tiles (at most %d)\n",
                      staged_tiles, div_up(A.nslices, 4), A.sell_stage_cap, A.sell_pat_tiles, A.sell_pat_max);
-    if ((options().debug & 2))
+    if ((opt.debug & 2))
         std::fprintf(stderr, "build_sell: %d rows, slices pair/offset/plain %lld/%lld/%lld, widest %llu, stream bytes %.0f, fast path %d\n",
                      A.nrows, (long long)h[0], (long long)h[1], (long long)h[2], h[7], A.sell_stream_bytes, (int)A.sell_fast_ok);
     A.has_sell = true;
@@ -1905,13 +1905,13 @@ __global__ __launch_bounds__(256) void dinv_code_kernel(int n, const double *__r
     for (int probe = 0; probe < 256 && tab[h] != bits; ++probe) h = (h + 1) & 255u;
     code[i] = (unsigned char)h;
 }
-void build_dinv_codes(hipStream_t s, DCsr &A, const double *dinv) {
+void build_dinv_codes(hipStream_t s, DCsr &A, const double *dinv, const Options &opt) {
     A.sell_dcode.release();
     A.sell_dsrc = nullptr;
-    // (only the staged kernel of the coded formats reads them.  options().sell bit 5, off by default: measured on the 256^3
+    // (only the staged kernel of the coded formats reads them.  Options::sell bit 5, off by default: measured on the 256^3
     // problem, 960 instead of 1 079 MB per application (PMC: 967 / 1 086) and 205.1 instead of 210.5 us -- the kernel is not
     // bound by its bytes alone, 2.3 % for 11 % of them)
-    if (!A.nrows || !A.has_sell || A.sell_wq <= 0 || !(options().sell & 32)) return;
+    if (!A.nrows || !A.has_sell || A.sell_wq <= 0 || !(opt.sell & 32)) return;
     A.sell_dtab.alloc(256);
     std::vector<unsigned long long> empty(256, DINV_EMPTY);
     SA_HIP_CHECK(hipMemcpyAsync(A.sell_dtab.p, empty.data(), 256 * sizeof(unsigned long long), hipMemcpyHostToDevice, s));

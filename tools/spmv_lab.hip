@@ -154,7 +154,7 @@ int main(int argc, char **argv) {
     A.col.alloc((size_t)nnz);
     A.val.alloc((size_t)nnz);
     hipLaunchKernelGGL(fill_kernel, dim3(grid), dim3(256), 0, s, n, A.rowptr.p, A.col.p, A.val.p);
-    build_sell(s, A);
+    build_sell(s, A, Options());
     hipStreamSynchronize(s);
     printf("n=%d rows=%ld nnz=%lld slices pair/offset/plain %lld/%lld/%lld stream bytes %.3f GB\n", n, N, (long long)nnz,
            (long long)A.sell_class_slices[0], (long long)A.sell_class_slices[1], (long long)A.sell_class_slices[2],

@@ -22,5 +22,4 @@ for rep in range(3):
     t0 = time.perf_counter()
     _, it, conv, hist = h.pcg(prob.b, x, rel_tol=1e-8, max_iter=200)
     torch.cuda.synchronize()
-    print("solve %.1f ms, %d iterations, coarse graph %s" % ((time.perf_counter() - t0) * 1e3, it,
-          os.environ.get("SAAMGE_AMD_COARSE_GRAPH", "1")), flush=True)
+    print("solve %.1f ms, %d iterations" % ((time.perf_counter() - t0) * 1e3, it), flush=True)
