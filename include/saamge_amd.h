@@ -371,6 +371,24 @@ int saamge_amd_lower_eigens_batched(int count, const int *n, const double *A, co
 int saamge_amd_inertia_batched(int count, const int *n, const double *A, const double *D, double vu,
                                int *neg);
 
+/* ---- the general sparse products of the smoothed prolongator on their own (csrc/spgemm.hip; tests) ----
+ * Host CSR arrays in (32-bit offsets; every row with distinct columns, in any order), the result on the host with every row
+ * sorted by column.  Sizes: a call with Ccol = Cval = NULL returns the row offsets (nrows + 1) and *nnz only.
+ * C = beta E + alpha diag(d) A B with A nrows x ninner, B ninner x ncols, E nrows x ncols or NULL, d (nrows) or NULL.  E given
+ * as B's own three arrays (A square) is the same matrix on the device too.  The structure of C is the structural product
+ * (entries that cancel stay).  *route: 0, 1, 2 = the hash-table product and the table tier (256, 2048, 8192 slots) that held
+ * every row; 3 = the dense-B product; -1 = no kernel ran (no rows) or the product was refused. */
+int saamge_amd_spgemm(int nrows, int ninner, int ncols, const int *Arow, const int *Acol, const double *Aval,
+                      const int *Brow, const int *Bcol, const double *Bval, const int *Erow, const int *Ecol,
+                      const double *Eval, const double *d, double alpha, double beta, int *Crow, long long *Cnnz,
+                      int *Ccol, double *Cval, int *route);
+/* R = P^T (P nrows x ncols) */
+int saamge_amd_csr_transpose(int nrows, int ncols, const int *rowptr, const int *col, const double *val, int *Rrow,
+                             long long *Rnnz, int *Rcol, double *Rval);
+/* C = the entries of A with |v| > tol, in their order (AltThreshold) */
+int saamge_amd_csr_threshold(int nrows, int ncols, const int *rowptr, const int *col, const double *val, double tol,
+                             int *Crow, long long *Cnnz, int *Ccol, double *Cval);
+
 /* ---- device memory kept by the library between calls ----
  * Freed device blocks are cached and reused by later calls (hipMalloc / hipFree stall the host and, for
  * hipFree, the whole device); the eigensolver workspace is persistent.  saamge_amd_release_cached_memory()

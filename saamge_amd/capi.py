@@ -33,6 +33,7 @@ SYMBOLS = [
     "saamge_amd_partition_options_default", "saamge_amd_partition_graph", "saamge_amd_partition_mesh",
     "saamge_amd_partitioning_arrays", "saamge_amd_partitioning_get", "saamge_amd_partitioning_graph",
     "saamge_amd_partitioning_free", "saamge_amd_coarse_solver_info",
+    "saamge_amd_spgemm", "saamge_amd_csr_transpose", "saamge_amd_csr_threshold",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong))
@@ -601,6 +602,65 @@ def inertia_batched(mats, diags, vu):
     neg = np.zeros(count, dtype=np.int32)
     _check(load().saamge_amd_inertia_batched(C.c_int(count), _ptr(n), _ptr(A), _ptr(D), C.c_double(vu), _ptr(neg)))
     return neg
+
+
+# ---- the general sparse products on their own (csrc/spgemm.hip) ----
+ROUTE_NONE, ROUTE_DENSE_B = -1, 3      # saamge_amd_spgemm's *route; 0, 1, 2: the hash path and its table tier
+
+
+def _csr_arrays(M):
+    """(indptr, indices, data) of a scipy CSR matrix AS STORED (no sorting, no summing: the order of a row is part of
+    what the kernels are given)"""
+    return (np.ascontiguousarray(M.indptr, dtype=np.int32), np.ascontiguousarray(M.indices, dtype=np.int32),
+            np.ascontiguousarray(M.data, dtype=np.float64))
+
+
+def _csr_result(shape, call):
+    """call(rowptr, nnz_ref, col, val): first for the sizes, then for the entries"""
+    import scipy.sparse as sp
+    rowptr = np.zeros(shape[0] + 1, dtype=np.int32)
+    nnz = C.c_longlong(0)
+    call(rowptr, nnz, None, None)
+    col = np.zeros(nnz.value, dtype=np.int32)
+    val = np.zeros(nnz.value, dtype=np.float64)
+    if nnz.value:
+        call(rowptr, nnz, col, val)
+    return sp.csr_matrix((val, col, rowptr), shape=shape)
+
+
+def spgemm(A, B, E=None, d=None, alpha=1.0, beta=0.0):
+    """(C, route): C = beta E + alpha diag(d) A B as a scipy CSR matrix and the route of saamge_amd_spgemm.  A, B, E: scipy
+    CSR matrices, passed as stored; `E is B` passes B's arrays twice (one matrix on the device too)."""
+    a, b = _csr_arrays(A), _csr_arrays(B)
+    e = b if E is B else (_csr_arrays(E) if E is not None else (None, None, None))
+    dd = None if d is None else np.ascontiguousarray(d, dtype=np.float64)
+    route = C.c_int(ROUTE_NONE)
+
+    def call(rowptr, nnz, col, val):
+        _check(load().saamge_amd_spgemm(C.c_int(A.shape[0]), C.c_int(A.shape[1]), C.c_int(B.shape[1]), _ptr(a[0]), _ptr(a[1]),
+                                        _ptr(a[2]), _ptr(b[0]), _ptr(b[1]), _ptr(b[2]), _ptr(e[0]), _ptr(e[1]), _ptr(e[2]),
+                                        _ptr(dd), C.c_double(alpha), C.c_double(beta), _ptr(rowptr), C.byref(nnz), _ptr(col),
+                                        _ptr(val), C.byref(route)))
+    out = _csr_result((A.shape[0], B.shape[1]), call)
+    return out, int(route.value)
+
+
+def csr_transpose(P):
+    p = _csr_arrays(P)
+
+    def call(rowptr, nnz, col, val):
+        _check(load().saamge_amd_csr_transpose(C.c_int(P.shape[0]), C.c_int(P.shape[1]), _ptr(p[0]), _ptr(p[1]), _ptr(p[2]),
+                                               _ptr(rowptr), C.byref(nnz), _ptr(col), _ptr(val)))
+    return _csr_result((P.shape[1], P.shape[0]), call)
+
+
+def csr_threshold(A, tol):
+    a = _csr_arrays(A)
+
+    def call(rowptr, nnz, col, val):
+        _check(load().saamge_amd_csr_threshold(C.c_int(A.shape[0]), C.c_int(A.shape[1]), _ptr(a[0]), _ptr(a[1]), _ptr(a[2]),
+                                               C.c_double(tol), _ptr(rowptr), C.byref(nnz), _ptr(col), _ptr(val)))
+    return _csr_result(A.shape, call)
 
 
 def release_cached_memory():

@@ -6,6 +6,7 @@
 
 #include "hierarchy.h"
 #include "partition.h"
+#include "spgemm.h"
 
 using namespace saamge_amd;
 
@@ -637,6 +638,83 @@ int saamge_amd_spmv(int nrows, int ncols, const int *rowptr, const int *col, con
 int saamge_amd_spmv64(int nrows, int ncols, const long long *rowptr, const int *col, const double *val,
                       const double *x, double *y) {
     return spmv_entry(nrows, ncols, rowptr, 64, col, val, x, y);
+}
+
+// ---- the general sparse products on their own (spgemm.hip; tests) -------------------------------------------------------
+// A host CSR matrix on the device.  The arrays are checked first: the kernels trust offsets and column indices.
+static void import_host_csr(DCsr &M, const char *name, int nrows, int ncols, const int *rowptr, const int *col,
+                            const double *val, hipStream_t s) {
+    const std::string who(name);
+    SA_REQUIRE(nrows >= 0 && ncols >= 0 && rowptr, who + ": bad dimensions or no row offsets");
+    SA_REQUIRE(rowptr[0] == 0, who + ": the row offsets must start at 0");
+    for (int i = 0; i < nrows; ++i) SA_REQUIRE(rowptr[i + 1] >= rowptr[i], who + ": the row offsets must ascend");
+    const size_t nnz = (size_t)rowptr[nrows];
+    SA_REQUIRE(nnz == 0 || (col && val), who + ": entries without their arrays");
+    for (size_t k = 0; k < nnz; ++k) SA_REQUIRE(col[k] >= 0 && col[k] < ncols, who + ": a column index out of range");
+    M.nrows = nrows;
+    M.ncols = ncols;
+    M.nnz = (int64_t)nnz;
+    import_rowptr(M.rowptr, rowptr, 32, (size_t)nrows + 1, s);
+    M.col.assign(col, nnz, s);
+    M.val.assign(val, nnz, s);
+    SA_HIP_CHECK(hipStreamSynchronize(s));
+    M.lanes_per_row = pick_lanes_per_row(M.nnz, nrows > 0 ? nrows : 1);
+}
+// row offsets and *nnz always; the entries when both arrays are given (the first call of a caller asks for the sizes)
+static void export_host_csr(const DCsr &M, int *rowptr, long long *nnz, int *col, double *val, hipStream_t s) {
+    if (rowptr) export_rowptr32(rowptr, M.rowptr, (size_t)M.nrows + 1, s);
+    if (nnz) *nnz = (long long)M.nnz;
+    if (col && val && M.nnz) {
+        SA_HIP_CHECK(hipMemcpyAsync(col, M.col.p, 4 * (size_t)M.nnz, hipMemcpyDeviceToHost, s));
+        SA_HIP_CHECK(hipMemcpyAsync(val, M.val.p, 8 * (size_t)M.nnz, hipMemcpyDeviceToHost, s));
+    }
+    SA_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+int saamge_amd_spgemm(int nrows, int ninner, int ncols, const int *Arow, const int *Acol, const double *Aval,
+                      const int *Brow, const int *Bcol, const double *Bval, const int *Erow, const int *Ecol,
+                      const double *Eval, const double *d, double alpha, double beta, int *Crow, long long *Cnnz,
+                      int *Ccol, double *Cval, int *route) {
+    if (route) *route = SPGEMM_ROUTE_NONE;
+    SA_API_BEGIN
+    hipStream_t s = 0;
+    set_thread_stream(s);
+    DCsr A, B, E, Cm;
+    import_host_csr(A, "A", nrows, ninner, Arow, Acol, Aval, s);
+    import_host_csr(B, "B", ninner, ncols, Brow, Bcol, Bval, s);
+    // E given as B's own arrays is B's device copy as well (interp_smooth: P <- P - w D^-1 A P)
+    const bool alias = Erow && Erow == Brow && Ecol == Bcol && Eval == Bval && nrows == ninner;
+    if (Erow && !alias) import_host_csr(E, "E", nrows, ncols, Erow, Ecol, Eval, s);
+    DBuf<double> dd;
+    if (d) dd.assign(d, (size_t)nrows, s);
+    spgemm(s, A, B, Erow ? (alias ? &B : &E) : nullptr, d ? dd.p : nullptr, alpha, beta, Cm);
+    if (route) *route = spgemm_last_route();
+    export_host_csr(Cm, Crow, Cnnz, Ccol, Cval, s);
+    SA_API_END
+}
+
+int saamge_amd_csr_transpose(int nrows, int ncols, const int *rowptr, const int *col, const double *val, int *Rrow,
+                             long long *Rnnz, int *Rcol, double *Rval) {
+    SA_API_BEGIN
+    hipStream_t s = 0;
+    set_thread_stream(s);
+    DCsr P, R;
+    import_host_csr(P, "P", nrows, ncols, rowptr, col, val, s);
+    csr_transpose(s, P, R);
+    export_host_csr(R, Rrow, Rnnz, Rcol, Rval, s);
+    SA_API_END
+}
+
+int saamge_amd_csr_threshold(int nrows, int ncols, const int *rowptr, const int *col, const double *val, double tol,
+                             int *Crow, long long *Cnnz, int *Ccol, double *Cval) {
+    SA_API_BEGIN
+    hipStream_t s = 0;
+    set_thread_stream(s);
+    DCsr A, Cm;
+    import_host_csr(A, "A", nrows, ncols, rowptr, col, val, s);
+    csr_threshold(s, A, tol, Cm);
+    export_host_csr(Cm, Crow, Cnnz, Ccol, Cval, s);
+    SA_API_END
 }
 
 __global__ void apply_dscale_kernel(int count, const int *ns, const int64_t *moff, const int64_t *voff,

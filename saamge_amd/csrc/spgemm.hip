@@ -232,9 +232,14 @@ static bool spgemm_dense_b(hipStream_t s, const DCsr &A, const DCsr &B, DCsr &C)
     return true;
 }
 
+// what spgemm_last_route() reports: a host-side note per thread, no device work
+static thread_local int g_last_route = SPGEMM_ROUTE_NONE;
+int spgemm_last_route() { return g_last_route; }
+
 void spgemm(hipStream_t s, const DCsr &A, const DCsr &B, const DCsr *E, const double *d, double alpha,
             double beta, DCsr &C) {
     SA_REQUIRE(A.ncols == B.nrows, "spgemm: inner dimensions differ");
+    g_last_route = SPGEMM_ROUTE_NONE;
     const int n = A.nrows;
     C.nrows = n;
     C.ncols = B.ncols;
@@ -242,12 +247,21 @@ void spgemm(hipStream_t s, const DCsr &A, const DCsr &B, const DCsr *E, const do
     C.has_sell = false;
     C.max_row = -1;
     C.rowptr.alloc((size_t)n + 1);
-    if (n == 0) return;
+    if (n == 0) {   // the empty matrix: its one row offset
+        C.rowptr.zero(s);
+        C.col.alloc(1);
+        C.val.alloc(1);
+        C.lanes_per_row = 1;
+        return;
+    }
     if (!E && !d && alpha == 1.0 && beta == 0.0) {
         profiler().begin(s);
         const bool done = spgemm_dense_b(s, A, B, C);
         profiler().end(s, "spgemm_dense_b", 0.0, 0.0);
-        if (done) return;
+        if (done) {
+            g_last_route = SPGEMM_ROUTE_DENSE_B;
+            return;
+        }
     }
     DBuf<int> rowcnt((size_t)n), flag(1);
     profiler().begin(s);
@@ -262,6 +276,7 @@ void spgemm(hipStream_t s, const DCsr &A, const DCsr &B, const DCsr *E, const do
         if (flag.to_host(s)[0] == 0) break;
     }
     SA_REQUIRE(tier < 3, "spgemm: a product row has more than ~8000 entries");
+    g_last_route = tier;
     exclusive_scan_off(s, n, rowcnt.p, C.rowptr.p);
     roff_t nnz = 0;
     SA_HIP_CHECK(hipMemcpyAsync(&nnz, C.rowptr.p + n, sizeof(roff_t), hipMemcpyDeviceToHost, s));
@@ -342,7 +357,11 @@ void csr_transpose(hipStream_t s, const DCsr &P, DCsr &R) {
     R.rowptr.alloc((size_t)R.nrows + 1);
     R.col.alloc((size_t)P.nnz + 1);
     R.val.alloc((size_t)P.nnz + 1);
-    if (R.nrows == 0) return;
+    R.lanes_per_row = 1;
+    if (R.nrows == 0 || P.nnz == 0) {   // no kernel has anything to do (and a grid of no blocks is an error): all offsets 0
+        R.rowptr.zero(s);
+        return;
+    }
     DBuf<int> cnt((size_t)R.nrows), tcol((size_t)P.nnz + 1);
     DBuf<double> tval((size_t)P.nnz + 1);
     cnt.zero(s);
@@ -392,6 +411,14 @@ void csr_threshold(hipStream_t s, const DCsr &A, double tol, DCsr &C) {
     C.has_sell = false;
     C.max_row = -1;
     C.rowptr.alloc((size_t)A.nrows + 1);
+    if (A.nrows == 0) {   // (the scan has no block to launch either)
+        C.rowptr.zero(s);
+        C.nnz = 0;
+        C.col.alloc(1);
+        C.val.alloc(1);
+        C.lanes_per_row = 1;
+        return;
+    }
     DBuf<int> cnt((size_t)A.nrows + 1);
     const dim3 grid(div_up(A.nrows, 4));
     if (A.nrows > 0)
