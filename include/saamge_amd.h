@@ -454,6 +454,38 @@ int saamge_amd_partitioning_graph(const saamge_amd_partitioning *p, int level, l
                                   long long *nnz);
 void saamge_amd_partitioning_free(saamge_amd_partitioning *p);
 
+/* ---- the operator assembled on the device from the element matrices -----------------------------------------------------
+ * The entry points above take the assembled, boundary-eliminated operator A from the caller.  These calls make it from the
+ * inputs the hierarchy takes anyway.  Row i holds every dof that shares an element with i, ascending, entries of value zero
+ * included; a value is the sum of the element terms in ascending element id; an off-diagonal entry in the row or column of
+ * an essential dof (bdr_dofs[i] & SAAMGE_AMD_ON_ESS_DOMAIN_BORDER; bdr_dofs == NULL: none) is stored as 0.0, the diagonal
+ * is kept.  saamge_amd/assemble_model.py defines the result and the device gives the same bits.
+ * Arrays may be host or device pointers, each on its own.  Refused: elem_ptr[0] != 0, an empty element, a dof outside
+ * [0, n), an element that lists a dof twice, a dof that lies in no element. */
+typedef struct saamge_amd_operator saamge_amd_operator;
+/* nde > 0 and elem_ptr == NULL: every element has nde dofs.  elem_ptr != NULL: offsets as in
+ * saamge_amd_ml_produce_data_mixed, nde ignored.  elmat packed as in that entry. */
+int  saamge_amd_operator_assemble(int n, int NE, int nde, const int *elem_ptr, const int *elem_to_dof,
+                                  const double *elmat, const signed char *bdr_dofs, void *stream,
+                                  saamge_amd_operator **out);
+/* device arrays, valid as long as the handle lives; what saamge_amd_ml_produce_data64 / _mixed64 take as A */
+int  saamge_amd_operator_arrays(const saamge_amd_operator *op, const long long **rowptr_dev, const int **col_dev,
+                                const double **val_dev, long long *nnz);
+/* host or device output buffers; all NULL: *nnz only.  A getter: blocking copy. */
+int  saamge_amd_operator_get(const saamge_amd_operator *op, long long *rowptr, int *col, double *val, long long *nnz);
+/* new element matrices, same mesh and flags: the numeric pass only, val_dev rewritten in place (on the stream of the
+ * assembly; returns when it is done) */
+int  saamge_amd_operator_update(saamge_amd_operator *op, const double *elmat);
+/* b (n, in place) for essential values x_ess (n, read at essential dofs only); elmat = the matrices of the operator */
+int  saamge_amd_operator_eliminate_rhs(const saamge_amd_operator *op, const double *elmat, const double *x_ess, double *b);
+void saamge_amd_operator_free(saamge_amd_operator *op);
+/* Rows by the path they took: counts[0 .. 2] the symbolic pass (several rows per wavefront; one workgroup per row with the
+ * candidates in LDS; through global memory), counts[3 .. 5] the numeric pass (the same three). */
+int  saamge_amd_operator_path_counts(const saamge_amd_operator *op, long long counts[6]);
+/* Tests: the largest candidate count (sum of the sizes of the elements of a row) of the first two paths for the assemblies
+ * that follow, process-wide.  Defaults and upper limits 64 and 4096; a negative value: the default. */
+int  saamge_amd_operator_set_path_limits(int short_candidates, int lds_candidates);
+
 #ifdef __cplusplus
 }
 #endif

@@ -206,6 +206,54 @@ inline MeshPartitions partition_mesh(int NE, int nde, const int *elem_ptr, const
     return out;
 }
 
+// == the operator assembled on the device (saamge_amd_operator_assemble) ==
+// Owner of the handle.  rowptr() / col() / val() are device arrays that live as long as this object: hand them to
+// saamge_amd_ml_produce_data64 / _mixed64 as A.  elem_ptr == nullptr: every element has nde dofs.
+class AssembledOperator {
+public:
+    AssembledOperator(int n, int NE, int nde, const int *elem_ptr, const int *elem_to_dof, const double *elmat,
+                      const signed char *bdr_dofs, void *stream = nullptr)
+        : op_(nullptr), n_(n), nnz_(0), rowptr_(nullptr), col_(nullptr), val_(nullptr) {
+        if (saamge_amd_operator_assemble(n, NE, nde, elem_ptr, elem_to_dof, elmat, bdr_dofs, stream, &op_))
+            throw std::runtime_error(saamge_amd_last_error());
+        if (saamge_amd_operator_arrays(op_, &rowptr_, &col_, &val_, &nnz_)) {
+            saamge_amd_operator_free(op_);
+            throw std::runtime_error(saamge_amd_last_error());
+        }
+    }
+    ~AssembledOperator() { saamge_amd_operator_free(op_); }
+    int rows() const { return n_; }
+    long long nnz() const { return nnz_; }
+    const long long *rowptr() const { return rowptr_; }
+    const int *col() const { return col_; }
+    const double *val() const { return val_; }
+    saamge_amd_operator *handle() const { return op_; }
+    // host copies
+    void get(std::vector<long long> &rowptr, std::vector<int> &col, std::vector<double> &val) const {
+        rowptr.assign((size_t)n_ + 1, 0);
+        col.assign((size_t)nnz_, 0);
+        val.assign((size_t)nnz_, 0.0);
+        if (saamge_amd_operator_get(op_, rowptr.data(), col.data(), val.data(), nullptr)) throw std::runtime_error(saamge_amd_last_error());
+    }
+    // new element matrices, same mesh: val() rewritten in place (then adapt_update_operators(h, nullptr))
+    void update(const double *elmat) {
+        if (saamge_amd_operator_update(op_, elmat)) throw std::runtime_error(saamge_amd_last_error());
+    }
+    void eliminate_rhs(const double *elmat, const double *x_ess, double *b) const {
+        if (saamge_amd_operator_eliminate_rhs(op_, elmat, x_ess, b)) throw std::runtime_error(saamge_amd_last_error());
+    }
+
+private:
+    AssembledOperator(const AssembledOperator &);
+    AssembledOperator &operator=(const AssembledOperator &);
+    saamge_amd_operator *op_;
+    int n_;
+    long long nnz_;
+    const long long *rowptr_;
+    const int *col_;
+    const double *val_;
+};
+
 }  // namespace api
 }  // namespace saamge_amd
 

@@ -34,6 +34,9 @@ SYMBOLS = [
     "saamge_amd_partitioning_arrays", "saamge_amd_partitioning_get", "saamge_amd_partitioning_graph",
     "saamge_amd_partitioning_free", "saamge_amd_coarse_solver_info",
     "saamge_amd_spgemm", "saamge_amd_csr_transpose", "saamge_amd_csr_threshold",
+    "saamge_amd_operator_assemble", "saamge_amd_operator_arrays", "saamge_amd_operator_get", "saamge_amd_operator_update",
+    "saamge_amd_operator_eliminate_rhs", "saamge_amd_operator_free", "saamge_amd_operator_path_counts",
+    "saamge_amd_operator_set_path_limits",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong))
@@ -306,6 +309,29 @@ class Hierarchy(object):
         else:
             h = cls(rowptr, col, val, A.shape[0], e2d, elmat, bdr, parts, nparts, params, e2d.shape[0], e2d.shape[1], stream)
         h._keep = h._keep + (partitioning,)
+        return h
+
+    @classmethod
+    def from_operator(cls, prob, op, params, stream=0):
+        """from_problem with the operator of an `Operator` in place of prob.A: its device arrays go to the 64-bit entry as
+        they are (no copy), so the hierarchy keeps `op` alive; after op.update(), update_operators(None) takes the new
+        values."""
+        def arr(a, dt):
+            return a if a is None or hasattr(a, "data_ptr") else np.ascontiguousarray(a, dtype=dt)
+        rp, cp, vp, _ = op.arrays()
+        rowptr, col, val = _DevicePointer(rp, "int64"), _DevicePointer(cp, "int32"), _DevicePointer(vp, "float64")
+        e2d = arr(prob.elem_to_dof, np.int32)
+        elmat = arr(prob.elmat, np.float64)
+        bdr = arr(prob.bdr, np.int8)
+        parts = [arr(p, np.int32) for p in prob.partitions[:params.num_coarsenings]]
+        nparts = [int(p.max()) + 1 for p in parts]
+        eptr = getattr(prob, "elem_ptr", None)
+        if eptr is not None:
+            eptr = arr(eptr, np.int32)
+            h = cls(rowptr, col, val, op.n, e2d, elmat, bdr, parts, nparts, params, len(eptr) - 1, 0, stream, elem_ptr=eptr)
+        else:
+            h = cls(rowptr, col, val, op.n, e2d, elmat, bdr, parts, nparts, params, e2d.shape[0], e2d.shape[1], stream)
+        h._keep = h._keep + (op,)
         return h
 
     @classmethod
@@ -793,6 +819,109 @@ class Partitioning(object):
 
 def partition_mesh(elem_to_dof, ND, elems_per_agg, elem_ptr=None, **kw):
     return Partitioning(elem_to_dof, ND, elems_per_agg, elem_ptr=elem_ptr, **kw)
+
+
+class _DevicePointer(object):
+    """A raw device address with the dtype the entry points look at (`Hierarchy` picks the 64-bit entry by it)."""
+
+    def __init__(self, address, dtype):
+        self._address, self.dtype = int(address or 0), dtype
+
+    def data_ptr(self):
+        return self._address
+
+
+class Operator(object):
+    """saamge_amd_operator_assemble: the fine operator assembled on the device from the element matrices, owned by the
+    library until close().  saamge_amd/assemble_model.py defines its pattern and values."""
+
+    def __init__(self, n, elem_to_dof, elmat, bdr=None, elem_ptr=None, nde=0, NE=None, stream=0):
+        if NE is None:
+            NE = len(elem_ptr) - 1 if elem_ptr is not None else int(elem_to_dof.shape[0])
+        if elem_ptr is None and not nde:
+            nde = int(elem_to_dof.shape[1])
+        h = C.c_void_p()
+        _check(load().saamge_amd_operator_assemble(C.c_int(int(n)), C.c_int(int(NE)), C.c_int(int(nde)), _ptr(elem_ptr),
+                                                   _ptr(elem_to_dof), _ptr(elmat), _ptr(bdr), C.c_void_p(stream), C.byref(h)))
+        self.h = h
+        self.n = int(n)
+        nnz = C.c_longlong(0)
+        _check(load().saamge_amd_operator_get(self.h, None, None, None, C.byref(nnz)))
+        self.nnz = int(nnz.value)
+
+    @classmethod
+    def assemble(cls, prob, stream=0, device=False):
+        """From a problems.Problem: its host arrays, or (device=True) copies of them on the GPU."""
+        def arr(a, dt):
+            if a is None or hasattr(a, "data_ptr"):
+                return a
+            a = np.ascontiguousarray(a, dtype=dt)
+            if device:
+                import torch
+                return torch.as_tensor(a).cuda()
+            return a
+        eptr = getattr(prob, "elem_ptr", None)
+        e2d = arr(prob.elem_to_dof, np.int32)
+        op = cls(prob.ND, e2d, arr(prob.elmat, np.float64), arr(prob.bdr, np.int8), elem_ptr=arr(eptr, np.int32),
+                 nde=0 if eptr is not None else int(prob.elem_to_dof.shape[1]), NE=prob.NE, stream=stream)
+        return op
+
+    def arrays(self):
+        """(rowptr, col, val, nnz): raw device addresses, valid until close()."""
+        rp, cp, vp, nnz = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_longlong(0)
+        _check(load().saamge_amd_operator_arrays(self.h, C.byref(rp), C.byref(cp), C.byref(vp), C.byref(nnz)))
+        return int(rp.value or 0), int(cp.value or 0), int(vp.value or 0), int(nnz.value)
+
+    def get(self, device=False):
+        """(rowptr int64, col int32, val float64): numpy arrays, or torch tensors on the GPU with device=True."""
+        if device:
+            import torch
+            rowptr = torch.zeros(self.n + 1, dtype=torch.int64, device="cuda")
+            col = torch.zeros(self.nnz, dtype=torch.int32, device="cuda")
+            val = torch.zeros(self.nnz, dtype=torch.float64, device="cuda")
+        else:
+            rowptr = np.zeros(self.n + 1, np.int64)
+            col = np.zeros(max(self.nnz, 1), np.int32)[:self.nnz]
+            val = np.zeros(max(self.nnz, 1), np.float64)[:self.nnz]
+        _check(load().saamge_amd_operator_get(self.h, _ptr(rowptr), _ptr(col), _ptr(val), None))
+        return rowptr, col, val
+
+    def update(self, elmat):
+        """New element matrices (host array or device tensor), same mesh and flags: the values are rewritten in place."""
+        if not hasattr(elmat, "data_ptr"):
+            elmat = np.ascontiguousarray(elmat, dtype=np.float64)
+        _check(load().saamge_amd_operator_update(self.h, _ptr(elmat)))
+
+    def eliminate_rhs(self, elmat, x_ess, b):
+        """b (numpy array or device tensor) in place; returns it."""
+        if not hasattr(elmat, "data_ptr"):
+            elmat = np.ascontiguousarray(elmat, dtype=np.float64)
+        _check(load().saamge_amd_operator_eliminate_rhs(self.h, _ptr(elmat), _ptr(x_ess), _ptr(b)))
+        return b
+
+    def path_counts(self):
+        """Rows by the path they took: {"symbolic": (short, lds, global), "numeric": (short, lds, global)}."""
+        c = (C.c_longlong * 6)()
+        _check(load().saamge_amd_operator_path_counts(self.h, c))
+        return {"symbolic": tuple(int(v) for v in c[:3]), "numeric": tuple(int(v) for v in c[3:])}
+
+    def close(self):
+        if self.h is not None and self.h.value:
+            free = load().saamge_amd_operator_free
+            free.restype = None
+            free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def operator_path_limits(short_candidates=-1, lds_candidates=-1):
+    """Tests: candidate limits of the short and the LDS path of the assemblies that follow (-1: the default)."""
+    _check(load().saamge_amd_operator_set_path_limits(C.c_int(int(short_candidates)), C.c_int(int(lds_candidates))))
 
 
 def pool_counts(reset=False):

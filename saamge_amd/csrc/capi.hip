@@ -5,6 +5,7 @@
 #include <string>
 
 #include "hierarchy.h"
+#include "operator.h"
 #include "partition.h"
 #include "spgemm.h"
 
@@ -25,6 +26,12 @@ struct saamge_amd_partitioning {
     std::vector<DBuf<int>> adj;
     std::vector<int64_t> nnz;
 };
+
+// saamge_amd_operator_assemble: the assembled operator and the device copies of the mesh tables its numeric pass needs
+struct saamge_amd_operator {
+    AssembledOperator op;
+};
+static OperatorLimits g_operator_limits;      // saamge_amd_operator_set_path_limits (tests)
 
 static std::string g_last_error;
 
@@ -988,5 +995,98 @@ int saamge_amd_partitioning_graph(const saamge_amd_partitioning *p, int level, l
 }
 
 void saamge_amd_partitioning_free(saamge_amd_partitioning *p) { delete p; }
+
+// ---- the operator assembled on the device (operator.hip) ---------------------------------------------------------------
+static void require_operator_device(const AssembledOperator &op) {
+    SA_REQUIRE(current_device() == op.device, "the calling thread's current HIP device is not the operator's device");
+}
+
+int saamge_amd_operator_assemble(int n, int NE, int nde, const int *elem_ptr, const int *elem_to_dof,
+                                 const double *elmat, const signed char *bdr_dofs, void *stream,
+                                 saamge_amd_operator **out) {
+    SA_API_BEGIN
+    SA_REQUIRE(out, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    std::unique_ptr<saamge_amd_operator> P(new saamge_amd_operator);
+    operator_assemble(s, n, NE, nde, elem_ptr, elem_to_dof, elmat, bdr_dofs, g_operator_limits, P->op);
+    *out = P.release();
+    SA_API_END
+}
+
+int saamge_amd_operator_arrays(const saamge_amd_operator *op, const long long **rowptr_dev, const int **col_dev,
+                               const double **val_dev, long long *nnz) {
+    SA_API_BEGIN
+    SA_REQUIRE(op, "null argument");
+    if (rowptr_dev) *rowptr_dev = (const long long *)op->op.rowptr.p;
+    if (col_dev) *col_dev = op->op.col.p;
+    if (val_dev) *val_dev = op->op.val.p;
+    if (nnz) *nnz = (long long)op->op.nnz;
+    SA_API_END
+}
+
+int saamge_amd_operator_get(const saamge_amd_operator *op, long long *rowptr, int *col, double *val, long long *nnz) {
+    SA_API_BEGIN
+    SA_REQUIRE(op, "null argument");
+    const AssembledOperator &o = op->op;
+    require_operator_device(o);
+    if (nnz) *nnz = (long long)o.nnz;
+    if (rowptr) SA_HIP_CHECK(hipMemcpy(rowptr, o.rowptr.p, ((size_t)o.n + 1) * sizeof(roff_t), hipMemcpyDefault));
+    if (col && o.nnz) SA_HIP_CHECK(hipMemcpy(col, o.col.p, (size_t)o.nnz * sizeof(int), hipMemcpyDefault));
+    if (val && o.nnz) SA_HIP_CHECK(hipMemcpy(val, o.val.p, (size_t)o.nnz * sizeof(double), hipMemcpyDefault));
+    SA_API_END
+}
+
+int saamge_amd_operator_update(saamge_amd_operator *op, const double *elmat) {
+    SA_API_BEGIN
+    SA_REQUIRE(op, "null argument");
+    require_operator_device(op->op);
+    ThreadStreamScope scope(op->op.stream);
+    operator_numeric(op->op, elmat);
+    SA_API_END
+}
+
+int saamge_amd_operator_eliminate_rhs(const saamge_amd_operator *op, const double *elmat, const double *x_ess, double *b) {
+    SA_API_BEGIN
+    SA_REQUIRE(op && x_ess && b, "null argument");
+    const AssembledOperator &o = op->op;
+    require_operator_device(o);
+    ThreadStreamScope scope(o.stream);
+    {
+        VecIn vx(x_ess, (size_t)o.n, o.stream);
+        VecOut vb(b, (size_t)o.n, o.stream, true);
+        operator_eliminate_rhs(o, elmat, vx.p, vb.p);
+        vb.finish();
+    }
+    SA_API_END
+}
+
+int saamge_amd_operator_path_counts(const saamge_amd_operator *op, long long counts[6]) {
+    SA_API_BEGIN
+    SA_REQUIRE(op && counts, "null argument");
+    for (int k = 0; k < 3; ++k) { counts[k] = op->op.sym_count[k]; counts[3 + k] = op->op.num_count[k]; }
+    SA_API_END
+}
+
+int saamge_amd_operator_set_path_limits(int short_candidates, int lds_candidates) {
+    SA_API_BEGIN
+    OperatorLimits l;
+    if (short_candidates >= 0) l.short_cand = short_candidates;
+    if (lds_candidates >= 0) l.lds_cand = lds_candidates;
+    SA_REQUIRE(l.short_cand <= OP_SHORT_CAND && l.lds_cand <= OP_LDS_CAND,
+               "operator path limits: at most 64 candidates for the short path and 4096 for the LDS path");
+    g_operator_limits = l;
+    SA_API_END
+}
+
+void saamge_amd_operator_free(saamge_amd_operator *op) {
+    if (!op) return;
+    {   // the blocks go back to the cache ordered after the operator's stream; the caller may destroy the stream next
+        hipStream_t s = op->op.stream;
+        ThreadStreamScope scope(s);
+        delete op;
+        dev_pool_close_stream(s);
+    }
+}
 
 }  // extern "C"
