@@ -423,15 +423,21 @@ int saamge_amd_profile_get2(int i, char *name, int name_len, double *ms, long lo
  * the device gives the same integers.  Arrays may be host or device pointers, each on its own, with
  * one exception: host columns (adj) need host offsets (xadj), which say how much to copy.  An element that lists a dof
  * twice is refused.  Parts above max_size are split in at most 32 rounds (enough for meshes by a wide margin; a hub with
- * thousands of leaves may keep a part above the cap). */
+ * thousands of leaves may keep a part above the cap).  A value of `seeding` other than 0 and 1 is refused before anything
+ * is written; a zero-filled options struct asks for seeding 0. */
 typedef struct saamge_amd_partition_options {
     int min_shared;      /* 1: dofs two elements share to be adjacent (1 vertex neighbours, 4 faces of Q1 hexes); mesh entry */
     int lloyd_iters;     /* 0: recentring passes */
     int max_size;        /* -1: 2 * elems_per_agg; 0: no cap */
     int min_size;        /* -1: elems_per_agg / 4; 0: small parts are left alone */
     unsigned seed;       /* 0 */
+    int seeding;         /* 0: lowest priorities; 1: spaced, the greedy distance-r independent set, topped up to the target count */
 } saamge_amd_partition_options;
 void saamge_amd_partition_options_default(saamge_amd_partition_options *o);
+/* What the spaced seeding did in the calling thread's last partition of one graph (saamge_amd_partition_graph, or the last
+ * level of saamge_amd_partition_mesh): info[0] = the radius r, [1] = independent-set rounds over all radii tried and the
+ * top-up, [2] = seeds of the independent set, [3] = seeds after the top-up.  All 0 after seeding = 0. */
+void saamge_amd_partition_seeding_info(long long info[4]);
 
 /* One level: a symmetric CSR graph (self-loops are ignored) -> part[n], *nparts_out.  o == NULL: the defaults.  Offsets that
  * do not ascend from 0, columns outside [0, n) and entries without their transpose are refused. */

@@ -164,7 +164,8 @@ inline int kalchev_pcg(ml_data_t *h, const double *b, double *x, int print_iter 
 
 // == agglomerate partitions built on the device (saamge_amd_partition_graph / saamge_amd_partition_mesh) ==
 // One level on a symmetric CSR graph (host or device arrays): part is resized to n; returns the number of parts produced
-// (elems_per_agg is a target).  o == nullptr: the library's defaults.
+// (elems_per_agg is a target).  o == nullptr: the library's defaults.  The options struct is handed on whole (o->seeding = 1:
+// spaced seeds).
 inline int partition_graph(int n, const long long *xadj, const int *adj, int elems_per_agg, std::vector<int> &part,
                            const saamge_amd_partition_options *o = nullptr, void *stream = nullptr) {
     part.assign((size_t)(n > 0 ? n : 0), 0);

@@ -30,7 +30,7 @@ SYMBOLS = [
     "saamge_amd_ml_produce_data_parcsr", "saamge_amd_memory_stats", "saamge_amd_pool_counts",
     "saamge_amd_options_default", "saamge_amd_set_options", "saamge_amd_get_options",
     "saamge_amd_ml_produce_data_mixed", "saamge_amd_ml_produce_data_mixed64",
-    "saamge_amd_partition_options_default", "saamge_amd_partition_graph", "saamge_amd_partition_mesh",
+    "saamge_amd_partition_options_default", "saamge_amd_partition_seeding_info", "saamge_amd_partition_graph", "saamge_amd_partition_mesh",
     "saamge_amd_partitioning_arrays", "saamge_amd_partitioning_get", "saamge_amd_partitioning_graph",
     "saamge_amd_partitioning_free", "saamge_amd_coarse_solver_info",
     "saamge_amd_spgemm", "saamge_amd_csr_transpose", "saamge_amd_csr_threshold",
@@ -728,7 +728,7 @@ def reset_options():
 
 class PartitionOptions(C.Structure):      # saamge_amd_partition_options
     _fields_ = [("min_shared", C.c_int), ("lloyd_iters", C.c_int), ("max_size", C.c_int), ("min_size", C.c_int),
-                ("seed", C.c_uint)]
+                ("seed", C.c_uint), ("seeding", C.c_int)]
 
 
 def partition_options(**kw):
@@ -744,7 +744,8 @@ def partition_options(**kw):
 
 def partition_graph(n, xadj, adj, elems_per_agg, part=None, stream=0, **opts):
     """saamge_amd_partition_graph.  xadj (int64) / adj (int32): numpy arrays or device tensors.  part: None (a numpy array
-    is returned) or a device tensor of n int32 that receives the partition.  Returns (part, nparts)."""
+    is returned) or a device tensor of n int32 that receives the partition.  Keywords are the fields of PartitionOptions
+    (seeding=1: spaced seeds).  Returns (part, nparts)."""
     o = partition_options(**opts)
     if part is None:
         part = np.zeros(max(int(n), 1), np.int32)[:int(n)]
@@ -754,8 +755,18 @@ def partition_graph(n, xadj, adj, elems_per_agg, part=None, stream=0, **opts):
     return part, int(npt.value)
 
 
+def partition_seeding_info():
+    """saamge_amd_partition_seeding_info: what the spaced seeding did in this thread's last partition of one graph."""
+    info = (C.c_longlong * 4)()
+    fn = load().saamge_amd_partition_seeding_info
+    fn.restype = None
+    fn(info)
+    return dict(radius=int(info[0]), rounds=int(info[1]), seeds_first=int(info[2]), seeds=int(info[3]))
+
+
 class Partitioning(object):
-    """saamge_amd_partition_mesh: the partitions of every coarsening, owned by the library until close()."""
+    """saamge_amd_partition_mesh: the partitions of every coarsening, owned by the library until close().  Keywords beyond
+    the named ones are the fields of PartitionOptions (seeding=1: spaced seeds)."""
 
     def __init__(self, elem_to_dof, ND, elems_per_agg, elem_ptr=None, nde=0, NE=None, stream=0, **opts):
         o = partition_options(**opts)

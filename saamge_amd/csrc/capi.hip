@@ -856,13 +856,19 @@ int saamge_amd_profile_get2(int i, char *name, int name_len, double *ms, long lo
 // ---- partitions from a graph / a mesh (partition.hip) ------------------------------------------------------------------
 static PartitionOptions convert_partition_options(const saamge_amd_partition_options *o) {
     PartitionOptions p;
-    if (o) { p.min_shared = o->min_shared; p.lloyd_iters = o->lloyd_iters; p.max_size = o->max_size; p.min_size = o->min_size; p.seed = o->seed; }
+    if (o) { p.min_shared = o->min_shared; p.lloyd_iters = o->lloyd_iters; p.max_size = o->max_size; p.min_size = o->min_size; p.seed = o->seed; p.seeding = o->seeding; }
+    SA_REQUIRE(p.seeding == 0 || p.seeding == 1, "partition options: seeding must be 0 or 1");
     return p;
 }
 
 void saamge_amd_partition_options_default(saamge_amd_partition_options *o) {
     const PartitionOptions p;
-    o->min_shared = p.min_shared; o->lloyd_iters = p.lloyd_iters; o->max_size = p.max_size; o->min_size = p.min_size; o->seed = p.seed;
+    o->min_shared = p.min_shared; o->lloyd_iters = p.lloyd_iters; o->max_size = p.max_size; o->min_size = p.min_size; o->seed = p.seed; o->seeding = p.seeding;
+}
+
+void saamge_amd_partition_seeding_info(long long info[4]) {
+    const SeedingStats st = last_seeding_stats();
+    info[0] = st.radius; info[1] = st.rounds; info[2] = st.seeds_first; info[3] = st.seeds;
 }
 
 int saamge_amd_partition_graph(int n, const long long *xadj, const int *adj, int elems_per_agg,
@@ -871,6 +877,7 @@ int saamge_amd_partition_graph(int n, const long long *xadj, const int *adj, int
     SA_REQUIRE(n >= 0, "n < 0");
     SA_REQUIRE(elems_per_agg >= 1, "elems_per_agg < 1");
     SA_REQUIRE(xadj && nparts_out && (n == 0 || part), "null argument");
+    const PartitionOptions po = convert_partition_options(o);
     hipStream_t s = (hipStream_t)stream;
     ThreadStreamScope scope(s);
     {
@@ -890,7 +897,7 @@ int saamge_amd_partition_graph(int n, const long long *xadj, const int *adj, int
         check_graph_device(s, n, dx.p, da.p);
         if (is_device_ptr(part)) dp.view(part, (size_t)n);
         else dp.alloc((size_t)n);
-        partition_graph_device(s, n, dx.p, da.p, elems_per_agg, convert_partition_options(o), dp.p, nparts_out);
+        partition_graph_device(s, n, dx.p, da.p, elems_per_agg, po, dp.p, nparts_out);
         if (n && !is_device_ptr(part)) SA_HIP_CHECK(hipMemcpyAsync(part, dp.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
         SA_HIP_CHECK(hipStreamSynchronize(s));
     }

@@ -11,7 +11,13 @@ struct PartitionOptions {
     int max_size = -1;    // -1: 2 * elems_per_agg, 0: off
     int min_size = -1;    // -1: elems_per_agg / 4, 0: off
     unsigned seed = 0;
+    int seeding = 0;      // 0: lowest priorities, 1: spaced (greedy distance-r independent set, topped up)
 };
+// the spaced seeding of the calling thread's last partition_graph_device; zeros after seeding = 0
+struct SeedingStats {
+    int radius = 0, rounds = 0, seeds_first = 0, seeds = 0;
+};
+SeedingStats last_seeding_stats();
 
 // Refuses offsets that are not 0-based and ascending, columns outside [0, n) and entries without their transpose.  Reads
 // adj only after xadj has been checked.  Returns xadj[n].

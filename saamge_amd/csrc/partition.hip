@@ -4,7 +4,8 @@
 // keys, atomicAdd on counters), so the output does not depend on the order in which threads run.
 //
 // Sweeps over the CSR use PT_LPR lanes per row: the lanes of a group read consecutive entries of the row, reduce by
-// shuffles, and lane 0 writes.  Growth is the pull form with two label buffers (no atomics on labels).
+// shuffles, and lane 0 writes.  Growth is the pull form with two label buffers (no atomics on labels); the ball sweeps of the
+// spaced seeding are the same form with two key / two flag buffers.
 #include "partition.h"
 
 #include <hipcub/hipcub.hpp>
@@ -139,6 +140,101 @@ __global__ __launch_bounds__(256) void pt_reseed_kernel(int n, const u64 *__rest
     const int r = (int)j - start[p];
     if (r < kp) { label[node] = r == 0 ? p : nlabels + off[p] + r - 1; isseed[node] = 1; }
     else { label[node] = -1; isseed[node] = 0; }
+}
+
+// ---- spaced seeding: greedy distance-r independent sets by rounds (partition_model.py, "fixed point") ----------------------
+constexpr int PT_UNDECIDED = 0, PT_SEED = 1, PT_OUT = 2, PT_EXT = 3;  // PT_EXT: a seed of the top-up's extension
+constexpr int PT_RADIUS_MAX = 32;
+
+// One hop of the min-priority ball sweep over closed neighbourhoods.  Keys are priorities in 64 bits, so that PT_NONE lies
+// outside them.  FIRST: the source is the state array, an undecided node offers its priority.  LAST: the minimum is not
+// stored; an undecided node that holds its own priority is flagged as a new seed.
+template <bool FIRST, bool LAST>
+__global__ __launch_bounds__(256) void pt_ball_min_kernel(int n, const roff_t *__restrict__ xadj, const int *__restrict__ adj,
+                                                          const int *__restrict__ state, unsigned seed,
+                                                          const u64 *__restrict__ src, u64 *__restrict__ dst,
+                                                          int *__restrict__ newseed) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const long v = t / PT_LPR;
+    const int lane = (int)(t % PT_LPR);
+    const bool valid = v < n;
+    u64 best = PT_NONE;
+    if (valid) {
+        if (lane == 0) best = FIRST ? (state[v] == PT_UNDECIDED ? (u64)pt_prio((unsigned)v, seed) : PT_NONE) : src[v];
+        for (roff_t k = xadj[v] + lane, e = xadj[v + 1]; k < e; k += PT_LPR) {
+            const int u = adj[k];
+            const u64 key = FIRST ? (state[u] == PT_UNDECIDED ? (u64)pt_prio((unsigned)u, seed) : PT_NONE) : src[u];
+            best = key < best ? key : best;
+        }
+    }
+    best = group_min_u64(best);
+    if (valid && lane == 0) {
+        if (LAST) newseed[v] = state[v] == PT_UNDECIDED && best == (u64)pt_prio((unsigned)v, seed);
+        else dst[v] = best;
+    }
+}
+// One hop of the flag's ball sweep.  LAST: the flag is not stored; an undecided node becomes `seedval` when it is a new seed
+// and out when the flag reached it.  counters[0] += new seeds, counters[1] += nodes still undecided.
+template <bool LAST>
+__global__ __launch_bounds__(256) void pt_ball_flag_kernel(int n, const roff_t *__restrict__ xadj, const int *__restrict__ adj,
+                                                           const int *__restrict__ src, int *__restrict__ dst,
+                                                           const int *__restrict__ newseed, int seedval,
+                                                           int *__restrict__ state, int *__restrict__ counters) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const long v = t / PT_LPR;
+    const int lane = (int)(t % PT_LPR);
+    const bool valid = v < n;
+    int f = 0;
+    if (valid) {
+        if (lane == 0) f = src[v];
+        for (roff_t k = xadj[v] + lane, e = xadj[v + 1]; k < e; k += PT_LPR) f |= src[adj[k]];
+    }
+    f = group_or(f);
+    if (valid && lane == 0) {
+        if (!LAST) dst[v] = f;
+        else if (state[v] == PT_UNDECIDED) {
+            if (newseed[v]) { state[v] = seedval; atomicAdd(&counters[0], 1); }
+            else if (f) state[v] = PT_OUT;
+            else atomicAdd(&counters[1], 1);
+        }
+    }
+}
+// before the extension: the first-stage seeds stay and are flagged, every other node becomes `other`
+__global__ __launch_bounds__(256) void pt_ext_init_kernel(int n, int other, int *__restrict__ state, int *__restrict__ flag) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int s = state[i] == PT_SEED;
+    flag[i] = s;
+    if (!s) state[i] = other;
+}
+// (class, priority): first-stage seeds, then the extension, then the rest
+__global__ __launch_bounds__(256) void pt_spaced_keys_kernel(int n, const int *__restrict__ state, unsigned seed,
+                                                             u64 *__restrict__ keys, int *__restrict__ ids) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int st = state[i];
+    keys[i] = ((u64)(st == PT_SEED ? 0u : st == PT_EXT ? 1u : 2u) << 32) | pt_prio((unsigned)i, seed);
+    ids[i] = (int)i;
+}
+// Sorted keys: [0, ns) the first-stage seeds, [ns, nsel) the members of the extension that top them up, each by priority.
+// The label of a seed is its rank by priority among all of them: its rank in its own run plus, by bisection, the number of
+// lower priorities in the other run.
+__global__ __launch_bounds__(256) void pt_spaced_label_kernel(int n, const u64 *__restrict__ keys, const int *__restrict__ ids,
+                                                              int ns, int nsel, int *__restrict__ label, int *__restrict__ isseed) {
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const int node = ids[j];
+    if (j >= nsel) { label[node] = -1; isseed[node] = 0; return; }
+    const unsigned prio = (unsigned)(keys[j] & 0xFFFFFFFFull);
+    int lo = j < ns ? ns : 0, hi = j < ns ? nsel : ns;
+    const int base = lo;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if ((unsigned)(keys[mid] & 0xFFFFFFFFull) < prio) lo = mid + 1;
+        else hi = mid;
+    }
+    label[node] = (int)(j < ns ? j : j - ns) + (lo - base);
+    isseed[node] = 1;
 }
 
 // ---- recentring -----------------------------------------------------------------------------------------------------
@@ -460,6 +556,95 @@ struct Grower {
         SA_HIP_CHECK(hipGetLastError());
         nlabels += read_one(off.p + nlabels, s);  // (synchronises: the temporaries go out of scope)
     }
+    // Spaced first seeding.  One independent set: rounds of r min sweeps, the decision and r flag sweeps, one read of the
+    // counters per round.  Returns the seeds found; gives up once they exceed `limit` (the set is then not needed).
+    struct Spaced {
+        DBuf<int> state, newseed, fa, fb;
+        DBuf<u64> ka, kb;
+    };
+    int independent_set(Spaced &w, int r, int seedval, int limit, int &rounds) {
+        const int *st = w.state.p;
+        int found = 0;
+        for (;;) {
+            for (int j = 1; j <= r; ++j) {
+                const u64 *src = j % 2 ? w.kb.p : w.ka.p;   // (not read by the first sweep)
+                u64 *dst = j % 2 ? w.ka.p : w.kb.p;
+                if (j == 1 && j == r)
+                    hipLaunchKernelGGL((pt_ball_min_kernel<true, true>), grid_rows(n), dim3(256), 0, s, n, xadj, adj, st, seed, src, dst, w.newseed.p);
+                else if (j == 1)
+                    hipLaunchKernelGGL((pt_ball_min_kernel<true, false>), grid_rows(n), dim3(256), 0, s, n, xadj, adj, st, seed, src, dst, w.newseed.p);
+                else if (j == r)
+                    hipLaunchKernelGGL((pt_ball_min_kernel<false, true>), grid_rows(n), dim3(256), 0, s, n, xadj, adj, st, seed, src, dst, w.newseed.p);
+                else
+                    hipLaunchKernelGGL((pt_ball_min_kernel<false, false>), grid_rows(n), dim3(256), 0, s, n, xadj, adj, st, seed, src, dst, w.newseed.p);
+            }
+            SA_HIP_CHECK(hipGetLastError());
+            counters.zero(s);
+            spread(w, r, seedval);
+            const auto c = counters.to_host(s);
+            ++rounds;
+            found += c[0];
+            if (c[1] == 0 || found > limit) return found;
+        }
+    }
+    // r flag sweeps from newseed; the last one applies the round to the states and counts
+    void spread(Spaced &w, int r, int seedval) {
+        for (int j = 1; j <= r; ++j) {
+            const int *src = j == 1 ? w.newseed.p : (j % 2 ? w.fb.p : w.fa.p);
+            int *dst = j % 2 ? w.fa.p : w.fb.p;
+            if (j == r)
+                hipLaunchKernelGGL(pt_ball_flag_kernel<true>, grid_rows(n), dim3(256), 0, s, n, xadj, adj, src, dst, (const int *)w.newseed.p, seedval, w.state.p, counters.p);
+            else
+                hipLaunchKernelGGL(pt_ball_flag_kernel<false>, grid_rows(n), dim3(256), 0, s, n, xadj, adj, src, dst, (const int *)w.newseed.p, seedval, w.state.p, counters.p);
+        }
+        SA_HIP_CHECK(hipGetLastError());
+    }
+    SeedingStats seed_spaced(int target) {
+        SeedingStats st;
+        Spaced w;
+        w.state.alloc((size_t)n);
+        w.newseed.alloc((size_t)n);
+        w.fa.alloc((size_t)n);
+        w.fb.alloc((size_t)n);
+        w.ka.alloc((size_t)n);
+        w.kb.alloc((size_t)n);
+        int r = 1, ns = 0;
+        for (;; ++r) {   // the smallest radius whose set is within the target
+            w.state.zero(s);
+            ns = independent_set(w, r, PT_SEED, r < PT_RADIUS_MAX ? target : INT_MAX, st.rounds);
+            if (ns <= target || r == PT_RADIUS_MAX) break;
+        }
+        int ne = 0;
+        if (ns < target) {   // top-up from the greedy (r - 1)-independent extension
+            hipLaunchKernelGGL(pt_ext_init_kernel, grid_flat(n), dim3(256), 0, s, n, r == 1 ? PT_EXT : PT_UNDECIDED, w.state.p, w.newseed.p);
+            SA_HIP_CHECK(hipGetLastError());
+            if (r == 1) ne = n - ns;
+            else {
+                counters.zero(s);
+                spread(w, r - 1, PT_SEED);   // the nodes within r - 1 hops of the first stage are out
+                if (counters.to_host(s)[1]) ne = independent_set(w, r - 1, PT_EXT, INT_MAX, st.rounds);
+            }
+        }
+        const int nsel = ns < target ? std::min(target, ns + ne) : ns;
+        DBuf<u64> keys((size_t)n), keys2((size_t)n);
+        DBuf<int> ids((size_t)n), ids2((size_t)n);
+        hipLaunchKernelGGL(pt_spaced_keys_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)w.state.p, seed, keys.p, ids.p);
+        SA_HIP_CHECK(hipGetLastError());
+        size_t tmp_bytes = 0;
+        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys.p, keys2.p, ids.p, ids2.p, n, 0, 34, s));
+        DBuf<char> tmp(tmp_bytes + 16);
+        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs((void *)tmp.p, tmp_bytes, keys.p, keys2.p, ids.p, ids2.p, n, 0, 34, s));
+        label = a.p;
+        hipLaunchKernelGGL(pt_spaced_label_kernel, grid_flat(n), dim3(256), 0, s, n, (const u64 *)keys2.p, (const int *)ids2.p, ns, nsel,
+                           label, isseed.p);
+        SA_HIP_CHECK(hipGetLastError());
+        SA_HIP_CHECK(hipStreamSynchronize(s));   // the temporaries go out of scope
+        nlabels = nsel;
+        st.radius = r;
+        st.seeds_first = ns;
+        st.seeds = nsel;
+        return st;
+    }
     void recentre() {
         DBuf<int> depth((size_t)n);
         hipLaunchKernelGGL(pt_boundary_kernel, grid_rows(n), dim3(256), 0, s, n, xadj, adj, (const int *)label, depth.p);
@@ -500,7 +685,11 @@ struct Grower {
 constexpr int PT_MERGE_ROUNDS = 8;
 constexpr int PT_REPAIR_ROUNDS = 32;
 
+thread_local SeedingStats t_seeding_stats;
+
 }  // namespace
+
+SeedingStats last_seeding_stats() { return t_seeding_stats; }
 
 int64_t check_graph_device(hipStream_t s, int n, const roff_t *xadj, const int *adj) {
     if (n == 0) return 0;
@@ -542,13 +731,17 @@ void partition_graph_device(hipStream_t s, int n, const roff_t *xadj, const int 
     SA_REQUIRE(n >= 0, "n < 0");
     SA_REQUIRE(epa >= 1, "elems_per_agg < 1");
     SA_REQUIRE(o.lloyd_iters >= 0 && o.max_size >= -1 && o.min_size >= -1, "partition options: lloyd_iters >= 0, sizes >= -1");
+    SA_REQUIRE(o.seeding == 0 || o.seeding == 1, "partition options: seeding must be 0 or 1");
     *nparts_out = 0;
+    t_seeding_stats = SeedingStats();
     if (n == 0) return;
     const int max_size = o.max_size < 0 ? (int)std::min<int64_t>(2ll * epa, INT_MAX) : o.max_size;
     const int min_size = o.min_size < 0 ? epa / 4 : o.min_size;
     Grower g(s, n, xadj, adj, o.seed);
-    {   // first seeding: one part 0 that holds every node, target seeds
-        const int target = (int)(((int64_t)n + epa - 1) / epa);
+    const int target = (int)(((int64_t)n + epa - 1) / epa);
+    if (o.seeding == 1) {
+        t_seeding_stats = g.seed_spaced(target);
+    } else {   // first seeding: one part 0 that holds every node, target seeds
         g.label = g.a.p;
         g.a.zero(s);
         g.nlabels = 1;

@@ -9,7 +9,29 @@ a minimum / maximum / count over integers, so no result depends on an execution 
   seeding      `reseed`: inside every flagged part p the k[p] nodes of lowest priority become seeds; the lowest keeps the
                label p, the r-th lowest (r >= 1) gets nlabels + off[p] + r - 1 with off the exclusive sum of k - 1 over the
                flagged parts in label order.  The first seeding is this with one part 0 holding every node and
-               k = target = ceil(n / elems_per_agg).
+               k = target = ceil(n / elems_per_agg).  This is `seeding = 0`.
+  spaced seeds `seeding = 1` replaces the FIRST seeding only (the reseeding of oversized parts stays as above).  dist(u, v) is
+               the hop distance (self-loops ignored, other components infinitely far); a set is r-independent when all its
+               pairs have dist > r.
+               greedy   the greedy r-independent set given a fixed set F: walk the nodes in ascending priority; a node
+                        joins when no member so far, F included, lies within r hops.  Priorities never tie, so the set is
+                        unique.  S_r is this set with F empty; S_0 is every node.
+               radius   target = ceil(n / elems_per_agg); r = the smallest radius >= 1 with |S_r| <= target, and
+                        RADIUS_MAX = 32 when there is none (more components than targets, or a component of larger
+                        diameter: S_32 is kept, and the stalled-growth rule below seeds a component that got no seed).
+               top-up   when |S_r| < target: E = the greedy (r - 1)-independent extension of F = S_r; the
+                        target - |S_r| members of E of lowest priority are added, all of E if there are fewer.  For r = 1
+                        every node outside S_1 is in E and the top-up is by priority alone.  The seed count is
+                        min(target, |S_r| + |E|) (|S_r| when that is above the target); first-stage seeds are pairwise more
+                        than r hops apart, all seeds more than r - 1.
+               labels   the seeds sorted by priority get 0, 1, 2, ... as in the first seeding above.
+               fixed point (the form the device runs, `independent_set_fixed_point`): nodes are undecided, seed or out.
+                        One round: every node takes the minimum priority of the UNDECIDED nodes within r hops (r pull sweeps
+                        over closed neighbourhoods, passing through nodes of every state); an undecided node that holds its
+                        own priority becomes a seed; every undecided node within r hops of a new seed becomes out (r sweeps
+                        of a flag).  Until nobody is undecided.  With F: its members are no candidates and the nodes within
+                        r hops of it start as out.  This is the greedy set: an undecided node that is the minimum of its
+                        ball has every lower-priority node of that ball already out.
   growth       level-synchronous pull: every unlabelled node with a labelled neighbour (of the same `dom`, when given) takes
                the smallest such label of the PREVIOUS round.  Nothing changed and nodes are left: the unlabelled node of
                lowest priority becomes a seed with the next free label.
@@ -34,6 +56,7 @@ import numpy as np
 MERGE_ROUNDS = 8
 REPAIR_ROUNDS = 32
 DEFAULT_LLOYD_ITERS = 0
+RADIUS_MAX = 32
 
 
 def priority(n, seed=0):
@@ -90,6 +113,7 @@ class _Graph(object):
         self.xadj = np.asarray(xadj, np.int64)
         self.dst = np.asarray(adj, np.int64)
         self.src = np.repeat(np.arange(self.n, dtype=np.int64), np.diff(self.xadj))
+        self.rows = np.flatnonzero(np.diff(self.xadj) > 0)          # the rows that have entries
 
 
 def _grow(g, label, isseed, prio, nlabels, dom=None):
@@ -131,6 +155,94 @@ def _reseed(g, label, isseed, prio, nlabels, k):
     out[nodes] = np.where(r == 0, p, nlabels + off[p] + r - 1)
     isseed[nodes] = True
     return out, nlabels + int(off[-1])
+
+
+def _ball_step(g, x, op):
+    """x over closed neighbourhoods: op = np.minimum / np.logical_or, one hop."""
+    out = x.copy()
+    if len(g.rows):
+        out[g.rows] = op(out[g.rows], op.reduceat(x[g.dst], g.xadj[g.rows]))
+    return out
+
+
+def independent_set_greedy(g, prio, r, fixed=None):
+    """The definition: nodes in ascending priority, each joins when no member or node of `fixed` lies within r hops.
+    Returns the members in ascending node order."""
+    blocked = np.zeros(g.n, bool)
+
+    def block(v):
+        blocked[v] = True
+        seen, front = {v}, [v]
+        for _ in range(r):
+            nxt = []
+            for w in front:
+                for u in g.dst[g.xadj[w]:g.xadj[w + 1]].tolist():
+                    if u not in seen:
+                        seen.add(u)
+                        nxt.append(u)
+            blocked[nxt] = True
+            front = nxt
+
+    if fixed is not None:
+        for v in fixed:
+            block(int(v))
+    members = []
+    for v in np.argsort(prio[:g.n], kind="stable"):
+        if not blocked[v]:
+            members.append(int(v))
+            block(int(v))
+    return np.sort(np.array(members, np.int64))
+
+
+def independent_set_fixed_point(g, prio, r, fixed=None):
+    """The same set by rounds that do not depend on an order.  Returns (members ascending, rounds)."""
+    BIG = np.iinfo(np.int64).max
+    UNDECIDED, SEED, OUT = 0, 1, 2
+    state = np.zeros(g.n, np.int8)
+    if fixed is not None and len(fixed):
+        flag = np.zeros(g.n, bool)
+        flag[fixed] = True
+        for _ in range(r):
+            flag = _ball_step(g, flag, np.logical_or)
+        state[flag] = OUT
+        state[fixed] = OUT
+    rounds = 0
+    while (state == UNDECIDED).any():
+        rounds += 1
+        key = np.where(state == UNDECIDED, prio, BIG)
+        for _ in range(r):
+            key = _ball_step(g, key, np.minimum)
+        new = (state == UNDECIDED) & (key == prio)
+        flag = new
+        for _ in range(r):
+            flag = _ball_step(g, flag, np.logical_or)
+        state[flag & (state == UNDECIDED)] = OUT
+        state[new] = SEED
+    return np.flatnonzero(state == SEED), rounds
+
+
+def spaced_seeds(g, prio, target, greedy=False):
+    """`seeding = 1`: dict(radius, first = S_r, ext = E, seeds, rounds); node arrays ascending.  greedy = True runs the
+    sequential definition in place of the fixed point (rounds = 0)."""
+    def indep(r, fixed=None):
+        if greedy:
+            return independent_set_greedy(g, prio, r, fixed), 0
+        return independent_set_fixed_point(g, prio, r, fixed)
+
+    rounds = 0
+    for r in range(1, RADIUS_MAX + 1):
+        first, k = indep(r)
+        rounds += k
+        if len(first) <= target:
+            break
+    ext = np.zeros(0, np.int64)
+    seeds = first
+    if len(first) < target:
+        ext, k = indep(r - 1, first)
+        rounds += k
+        add = ext[np.argsort(prio[ext], kind="stable")[:target - len(first)]]
+        seeds = np.sort(np.concatenate([first, add]))
+    return dict(radius=r, first=first, ext=ext, seeds=seeds, rounds=rounds)
 
 
 def _recentre(g, label, isseed, prio, nlabels):
@@ -187,10 +299,12 @@ def renumber(label, nlabels):
 
 
 def partition_graph(n, xadj, adj, elems_per_agg, min_shared=1, lloyd_iters=DEFAULT_LLOYD_ITERS, max_size=-1,
-                    min_size=-1, seed=0):
+                    min_size=-1, seed=0, seeding=0):
     """One level: symmetric CSR graph -> (part int32 (n), nparts).  min_shared is not used here (graph given)."""
     if elems_per_agg < 1 or n < 0:
         raise ValueError("elems_per_agg >= 1 and n >= 0")
+    if seeding not in (0, 1):
+        raise ValueError("seeding: 0 or 1")
     if n == 0:
         return np.zeros(0, np.int32), 0
     max_size, min_size = resolve_sizes(elems_per_agg, max_size, min_size)
@@ -198,7 +312,14 @@ def partition_graph(n, xadj, adj, elems_per_agg, min_shared=1, lloyd_iters=DEFAU
     prio = priority(n, seed)
     target = -(-n // elems_per_agg)
     isseed = np.zeros(n, bool)
-    label, nlabels = _reseed(g, np.zeros(n, np.int64), isseed, prio, 1, np.array([target], np.int64))
+    if seeding == 0:
+        label, nlabels = _reseed(g, np.zeros(n, np.int64), isseed, prio, 1, np.array([target], np.int64))
+    else:
+        seeds = spaced_seeds(g, prio, target)["seeds"]
+        seeds = seeds[np.argsort(prio[seeds], kind="stable")]
+        label, nlabels = np.full(n, -1, np.int64), len(seeds)
+        label[seeds] = np.arange(nlabels)
+        isseed[seeds] = True
     label, nlabels = _grow(g, label, isseed, prio, nlabels)
     for _ in range(lloyd_iters):
         label = _recentre(g, label, isseed, prio, nlabels)

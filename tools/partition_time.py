@@ -2,7 +2,10 @@
 of the parts, on Q1 hex grids (vertex and face adjacency) and on the half-prism mesh of poisson3d_mixed_problem.  Host
 clock closed by a synchronise, one warm-up, `--reps` repetitions (all listed).  Prints one JSON line per case.
 
-    python tools/partition_time.py [--hex 128,256] [--mixed 64] [--epa 256,64] [--reps 3]
+    python tools/partition_time.py [--hex 128,256] [--mixed 64] [--epa 256,64] [--reps 3] [--seeding {0,1}]
+
+--seeding 1 times the spaced seeding; the line then carries, per level, the radius chosen, the independent-set rounds and
+the seeds before and after the top-up (saamge_amd_partition_seeding_info; zeros for --seeding 0).
 
 graph_ms is the time of partition_mesh with one coarsening minus the level-0 partition timed alone (it includes the
 quotient graph of level 0).  For the hex grids, box_setup_ms is the time of a 3-level hierarchy setup of the Poisson problem
@@ -39,6 +42,7 @@ def main():
     ap.add_argument("--mixed", default="64")
     ap.add_argument("--epa", default="256,64")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--seeding", type=int, choices=(0, 1), default=0)
     a = ap.parse_args()
     epa = [int(x) for x in a.epa.split(",")]
     cases = []
@@ -70,7 +74,7 @@ def main():
         return [round(timed(setup)[0], 2) for _ in range(a.reps)]
 
     for name, e2d, eptr, ND, ms in cases:
-        mesh1 = lambda: capi.partition_mesh(e2d, ND, epa[:1], elem_ptr=eptr, min_shared=ms)
+        mesh1 = lambda: capi.partition_mesh(e2d, ND, epa[:1], elem_ptr=eptr, min_shared=ms, seeding=a.seeding)
         _, P = timed(mesh1)                         # warm-up; its graphs feed the per-level timings
         g0, g1 = P.graph(0, device=True), P.graph(1, device=True)
         n0, n1 = P.n_elem[0], P.nparts[0]
@@ -78,8 +82,8 @@ def main():
         P.close()
         d0 = torch.empty(n0, dtype=torch.int32, device="cuda")
         d1 = torch.empty(n1, dtype=torch.int32, device="cuda")
-        lev0 = lambda: capi.partition_graph(n0, g0[0], g0[1], epa[0], part=d0)[1]
-        lev1 = lambda: capi.partition_graph(n1, g1[0], g1[1], epa[1], part=d1)[1]
+        lev0 = lambda: capi.partition_graph(n0, g0[0], g0[1], epa[0], part=d0, seeding=a.seeding)[1]
+        lev1 = lambda: capi.partition_graph(n1, g1[0], g1[1], epa[1], part=d1, seeding=a.seeding)[1]
         timed(lev0), timed(lev1)
         t_mesh, t0, t1 = [], [], []
         capi.memory_stats(reset_peak=True)
@@ -88,12 +92,14 @@ def main():
             P.close()
             t_mesh.append(t)
             t0.append(timed(lev0)[0])
+            info0 = capi.partition_seeding_info()
             t, np1 = timed(lev1)
+            info1 = capi.partition_seeding_info()
             t1.append(t)
         peak = capi.memory_stats()[1]
         r = lambda v: [round(x, 2) for x in v]
         print(json.dumps({
-            "case": name, "elements": n0, "graph_entries": int(g0[1].numel()), "elems_per_agg": epa,
+            "case": name, "seeding": a.seeding, "seeding_level0": info0, "seeding_level1": info1, "elements": n0, "graph_entries": int(g0[1].numel()), "elems_per_agg": epa,
             "nparts": [n1, int(np1)], "mesh_one_level_ms": r(t_mesh), "level0_ms": r(t0), "level1_ms": r(t1),
             "graph_ms": r([m - l for m, l in zip(t_mesh, t0)]), "peak_device_bytes": int(peak),
             "size_over_epa_level0": pm.size_stats(part0, n1, epa[0]),
