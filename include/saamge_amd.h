@@ -438,11 +438,33 @@ void saamge_amd_partition_options_default(saamge_amd_partition_options *o);
  * level of saamge_amd_partition_mesh): info[0] = the radius r, [1] = independent-set rounds over all radii tried and the
  * top-up, [2] = seeds of the independent set, [3] = seeds after the top-up.  All 0 after seeding = 0. */
 void saamge_amd_partition_seeding_info(long long info[4]);
+/* The options with `growth` as their last field.  saamge_amd_partition_options keeps its size (callers and tests hold it to
+ * six ints), so the field lives in this struct, whose first six fields are those of saamge_amd_partition_options in the same
+ * order, and the _v2 entry points below take it; the entry points without _v2 are these with growth = 0.  A value of
+ * `seeding` or of `growth` other than 0 and 1 is refused before anything is written; a zero-filled struct asks for 0, 0. */
+typedef struct saamge_amd_partition_options_v2 {
+    int min_shared;
+    int lloyd_iters;
+    int max_size;
+    int min_size;
+    unsigned seed;
+    int seeding;
+    int growth;          /* 0: level-synchronous growth; 1: balanced, per round a part takes at most elems_per_agg - size of its
+                            claimants (most neighbours in the part first), the rest is released to growth 0 when no open part
+                            has a claimant; first growth and the regrowth after recentring, not the size repair */
+} saamge_amd_partition_options_v2;
+void saamge_amd_partition_options_v2_default(saamge_amd_partition_options_v2 *o);
+/* The same for the balanced growth (with lloyd_iters > 0: the last growth): info[0] = balanced rounds, [1] = nodes labelled
+ * under a quota, [2] = parts still open at the release, [3] = nodes labelled after the release ([2] = [3] = 0 when every
+ * node was labelled under a quota).  All 0 after growth = 0. */
+void saamge_amd_partition_growth_info(long long info[4]);
 
 /* One level: a symmetric CSR graph (self-loops are ignored) -> part[n], *nparts_out.  o == NULL: the defaults.  Offsets that
  * do not ascend from 0, columns outside [0, n) and entries without their transpose are refused. */
 int saamge_amd_partition_graph(int n, const long long *xadj, const int *adj, int elems_per_agg,
                                const saamge_amd_partition_options *o, void *stream, int *part, int *nparts_out);
+int saamge_amd_partition_graph_v2(int n, const long long *xadj, const int *adj, int elems_per_agg,
+                                  const saamge_amd_partition_options_v2 *o, void *stream, int *part, int *nparts_out);
 
 /* All levels from the mesh.  elem_ptr == NULL: every element has nde dofs.  elems_per_agg has num_coarsenings entries.
  * Level k partitions graph k: graph 0 is the element graph, graph k + 1 the quotient graph of level k. */
@@ -450,6 +472,9 @@ typedef struct saamge_amd_partitioning saamge_amd_partitioning;
 int saamge_amd_partition_mesh(int NE, int nde, const int *elem_ptr, const int *elem_to_dof, int ND, int num_coarsenings,
                               const int *elems_per_agg, const saamge_amd_partition_options *o, void *stream,
                               saamge_amd_partitioning **out);
+int saamge_amd_partition_mesh_v2(int NE, int nde, const int *elem_ptr, const int *elem_to_dof, int ND, int num_coarsenings,
+                                 const int *elems_per_agg, const saamge_amd_partition_options_v2 *o, void *stream,
+                                 saamge_amd_partitioning **out);
 /* Pointers that can be handed to saamge_amd_ml_produce_data* as partitions / nparts; they live as long as the handle.
  * on_host = 0: device arrays, 1: host copies. */
 int saamge_amd_partitioning_arrays(const saamge_amd_partitioning *p, int on_host, const int *const **partitions,

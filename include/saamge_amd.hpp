@@ -165,7 +165,8 @@ inline int kalchev_pcg(ml_data_t *h, const double *b, double *x, int print_iter 
 // == agglomerate partitions built on the device (saamge_amd_partition_graph / saamge_amd_partition_mesh) ==
 // One level on a symmetric CSR graph (host or device arrays): part is resized to n; returns the number of parts produced
 // (elems_per_agg is a target).  o == nullptr: the library's defaults.  The options struct is handed on whole (o->seeding = 1:
-// spaced seeds).
+// spaced seeds).  partition_graph_v2 takes saamge_amd_partition_options_v2, which carries `growth` as well (1: balanced
+// growth); it has a name of its own so that a null pointer for the options means the same in every call written before it.
 inline int partition_graph(int n, const long long *xadj, const int *adj, int elems_per_agg, std::vector<int> &part,
                            const saamge_amd_partition_options *o = nullptr, void *stream = nullptr) {
     part.assign((size_t)(n > 0 ? n : 0), 0);
@@ -174,8 +175,16 @@ inline int partition_graph(int n, const long long *xadj, const int *adj, int ele
         throw std::runtime_error(saamge_amd_last_error());
     return nparts;
 }
+inline int partition_graph_v2(int n, const long long *xadj, const int *adj, int elems_per_agg, std::vector<int> &part,
+                              const saamge_amd_partition_options_v2 *o = nullptr, void *stream = nullptr) {
+    part.assign((size_t)(n > 0 ? n : 0), 0);
+    int nparts = 0;
+    if (saamge_amd_partition_graph_v2(n, xadj, adj, elems_per_agg, o, stream, part.data(), &nparts))
+        throw std::runtime_error(saamge_amd_last_error());
+    return nparts;
+}
 // All levels from a mesh, as host vectors: partitions[k] / nparts[k] for ProblemArrays::partitions and
-// MultilevelParameters' nparts_arr.  elem_ptr == nullptr: every element has nde dofs.
+// MultilevelParameters' nparts_arr.  elem_ptr == nullptr: every element has nde dofs.  partition_mesh_v2: with `growth`.
 struct MeshPartitions {
     std::vector<std::vector<int> > partitions;
     std::vector<int> nparts;
@@ -185,14 +194,11 @@ struct MeshPartitions {
         return p;
     }
 };
-inline MeshPartitions partition_mesh(int NE, int nde, const int *elem_ptr, const int *elem_to_dof, int ND,
-                                     const std::vector<int> &elems_per_agg, const saamge_amd_partition_options *o = nullptr,
-                                     void *stream = nullptr) {
-    saamge_amd_partitioning *P = nullptr;
-    if (saamge_amd_partition_mesh(NE, nde, elem_ptr, elem_to_dof, ND, (int)elems_per_agg.size(), elems_per_agg.data(), o, stream, &P))
-        throw std::runtime_error(saamge_amd_last_error());
+namespace detail {
+// copies the levels of P to the host and frees P
+inline MeshPartitions take_partitions(saamge_amd_partitioning *P, int levels) {
     MeshPartitions out;
-    for (int k = 0; k < (int)elems_per_agg.size(); ++k) {
+    for (int k = 0; k < levels; ++k) {
         int n_elem = 0, np = 0;
         int rc = saamge_amd_partitioning_get(P, k, nullptr, &n_elem, &np);
         out.partitions.push_back(std::vector<int>((size_t)n_elem));
@@ -205,6 +211,23 @@ inline MeshPartitions partition_mesh(int NE, int nde, const int *elem_ptr, const
     }
     saamge_amd_partitioning_free(P);
     return out;
+}
+}  // namespace detail
+inline MeshPartitions partition_mesh(int NE, int nde, const int *elem_ptr, const int *elem_to_dof, int ND,
+                                     const std::vector<int> &elems_per_agg, const saamge_amd_partition_options *o = nullptr,
+                                     void *stream = nullptr) {
+    saamge_amd_partitioning *P = nullptr;
+    if (saamge_amd_partition_mesh(NE, nde, elem_ptr, elem_to_dof, ND, (int)elems_per_agg.size(), elems_per_agg.data(), o, stream, &P))
+        throw std::runtime_error(saamge_amd_last_error());
+    return detail::take_partitions(P, (int)elems_per_agg.size());
+}
+inline MeshPartitions partition_mesh_v2(int NE, int nde, const int *elem_ptr, const int *elem_to_dof, int ND,
+                                        const std::vector<int> &elems_per_agg, const saamge_amd_partition_options_v2 *o = nullptr,
+                                        void *stream = nullptr) {
+    saamge_amd_partitioning *P = nullptr;
+    if (saamge_amd_partition_mesh_v2(NE, nde, elem_ptr, elem_to_dof, ND, (int)elems_per_agg.size(), elems_per_agg.data(), o, stream, &P))
+        throw std::runtime_error(saamge_amd_last_error());
+    return detail::take_partitions(P, (int)elems_per_agg.size());
 }
 
 // == the operator assembled on the device (saamge_amd_operator_assemble) ==

@@ -239,9 +239,12 @@ inline void ml_set_fine_partitioner(const ml_partitioner_t &p) { ml_fine_partiti
 // above cut index ranges.  elem_to_elem is used as the CSR graph it is; the hook's nparts is a TARGET
 // (elems_per_agg = ceil(n_elem / nparts)) and the number of parts produced may differ, as after the reference's
 // connected-components pass (src/part.cpp:193-197).  Installed through the overloads below, the adaptor takes the number
-// of agglomerates of that level from max(partition) + 1 instead of MultilevelParameters::get_nparts.
+// of agglomerates of that level from max(partition) + 1 instead of MultilevelParameters::get_nparts.  `options` keeps its
+// type; `growth` (saamge_amd_partition_options_v2's last field) stands beside it and is 0 unless the hook was made by
+// ml_device_partitioner_v2, which has a name of its own so that ml_device_partitioner(nullptr) still means the defaults.
 struct ml_device_partitioner_t {
     saamge_amd_partition_options options;
+    int growth = 0;
     void operator()(int, int n_elem, int nparts, const mfem::Table &elem_to_elem, int *partition) const {
         if (n_elem <= 0) return;
         const int target = nparts < 1 ? 1 : nparts;
@@ -251,8 +254,10 @@ struct ml_device_partitioner_t {
         if (has_graph)
             for (int e = 0; e <= n_elem; ++e) xadj[(size_t)e] = elem_to_elem.GetI()[e];
         int produced = 0;
-        if (saamge_amd_partition_graph(n_elem, xadj.data(), has_graph ? elem_to_elem.GetJ() : nullptr, epa, &options, nullptr,
-                                       partition, &produced))
+        const saamge_amd_partition_options_v2 o = {options.min_shared, options.lloyd_iters, options.max_size, options.min_size,
+                                                   options.seed, options.seeding, growth};
+        if (saamge_amd_partition_graph_v2(n_elem, xadj.data(), has_graph ? elem_to_elem.GetJ() : nullptr, epa, &o, nullptr,
+                                          partition, &produced))
             mfem::mfem_error(saamge_amd_last_error());
     }
 };
@@ -260,6 +265,16 @@ inline ml_device_partitioner_t ml_device_partitioner(const saamge_amd_partition_
     ml_device_partitioner_t p;
     if (options) p.options = *options;
     else saamge_amd_partition_options_default(&p.options);
+    return p;
+}
+inline ml_device_partitioner_t ml_device_partitioner_v2(const saamge_amd_partition_options_v2 *options = nullptr) {
+    ml_device_partitioner_t p = ml_device_partitioner();
+    if (options) {
+        p.options.min_shared = options->min_shared; p.options.lloyd_iters = options->lloyd_iters;
+        p.options.max_size = options->max_size; p.options.min_size = options->min_size;
+        p.options.seed = options->seed; p.options.seeding = options->seeding;
+        p.growth = options->growth;
+    }
     return p;
 }
 inline void ml_set_coarse_partitioner(const ml_device_partitioner_t &p) { ml_coarse_partitioner() = p; detail::partitioner_counts()[1] = true; }

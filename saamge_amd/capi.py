@@ -30,7 +30,8 @@ SYMBOLS = [
     "saamge_amd_ml_produce_data_parcsr", "saamge_amd_memory_stats", "saamge_amd_pool_counts",
     "saamge_amd_options_default", "saamge_amd_set_options", "saamge_amd_get_options",
     "saamge_amd_ml_produce_data_mixed", "saamge_amd_ml_produce_data_mixed64",
-    "saamge_amd_partition_options_default", "saamge_amd_partition_seeding_info", "saamge_amd_partition_graph", "saamge_amd_partition_mesh",
+    "saamge_amd_partition_options_default", "saamge_amd_partition_seeding_info", "saamge_amd_partition_growth_info", "saamge_amd_partition_options_v2_default",
+    "saamge_amd_partition_graph_v2", "saamge_amd_partition_mesh_v2", "saamge_amd_partition_graph", "saamge_amd_partition_mesh",
     "saamge_amd_partitioning_arrays", "saamge_amd_partitioning_get", "saamge_amd_partitioning_graph",
     "saamge_amd_partitioning_free", "saamge_amd_coarse_solver_info",
     "saamge_amd_spgemm", "saamge_amd_csr_transpose", "saamge_amd_csr_threshold",
@@ -731,27 +732,42 @@ class PartitionOptions(C.Structure):      # saamge_amd_partition_options
                 ("seed", C.c_uint), ("seeding", C.c_int)]
 
 
+class PartitionOptionsV2(C.Structure):    # saamge_amd_partition_options_v2: the same fields, then `growth`
+    _fields_ = PartitionOptions._fields_ + [("growth", C.c_int)]
+
+
 def partition_options(**kw):
-    """The library's defaults with the given fields replaced."""
-    o = PartitionOptions()
-    load().saamge_amd_partition_options_default(C.byref(o))
+    """The library's defaults with the given fields replaced: a PartitionOptions, or a PartitionOptionsV2 when `growth` is
+    among them."""
+    if "growth" in kw:
+        o = PartitionOptionsV2()
+        load().saamge_amd_partition_options_v2_default(C.byref(o))
+    else:
+        o = PartitionOptions()
+        load().saamge_amd_partition_options_default(C.byref(o))
     for k, v in kw.items():
-        if k not in dict(PartitionOptions._fields_):
+        if k not in dict(o._fields_):
             raise KeyError(k)
         setattr(o, k, int(v))
     return o
 
 
+def _v2(o, name):
+    """The entry point that takes the struct o: `name` or `name`_v2."""
+    return getattr(load(), name + "_v2" if isinstance(o, PartitionOptionsV2) else name)
+
+
 def partition_graph(n, xadj, adj, elems_per_agg, part=None, stream=0, **opts):
     """saamge_amd_partition_graph.  xadj (int64) / adj (int32): numpy arrays or device tensors.  part: None (a numpy array
     is returned) or a device tensor of n int32 that receives the partition.  Keywords are the fields of PartitionOptions
-    (seeding=1: spaced seeds).  Returns (part, nparts)."""
+    (seeding=1: spaced seeds) or, with `growth` among them (1: balanced growth), of PartitionOptionsV2, which goes to
+    saamge_amd_partition_graph_v2.  Returns (part, nparts)."""
     o = partition_options(**opts)
     if part is None:
         part = np.zeros(max(int(n), 1), np.int32)[:int(n)]
     npt = C.c_int(0)
-    _check(load().saamge_amd_partition_graph(C.c_int(int(n)), _ptr(xadj), _ptr(adj), C.c_int(int(elems_per_agg)), C.byref(o),
-                                             C.c_void_p(stream), _ptr(part), C.byref(npt)))
+    _check(_v2(o, "saamge_amd_partition_graph")(C.c_int(int(n)), _ptr(xadj), _ptr(adj), C.c_int(int(elems_per_agg)), C.byref(o),
+                                                C.c_void_p(stream), _ptr(part), C.byref(npt)))
     return part, int(npt.value)
 
 
@@ -764,9 +780,19 @@ def partition_seeding_info():
     return dict(radius=int(info[0]), rounds=int(info[1]), seeds_first=int(info[2]), seeds=int(info[3]))
 
 
+def partition_growth_info():
+    """saamge_amd_partition_growth_info: what the balanced growth did in this thread's last partition of one graph."""
+    info = (C.c_longlong * 4)()
+    fn = load().saamge_amd_partition_growth_info
+    fn.restype = None
+    fn(info)
+    return dict(rounds=int(info[0]), quota_nodes=int(info[1]), open_parts=int(info[2]), released_nodes=int(info[3]))
+
+
 class Partitioning(object):
     """saamge_amd_partition_mesh: the partitions of every coarsening, owned by the library until close().  Keywords beyond
-    the named ones are the fields of PartitionOptions (seeding=1: spaced seeds)."""
+    the named ones are the fields of PartitionOptions (seeding=1: spaced seeds) or, with `growth` among them (1: balanced
+    growth), of PartitionOptionsV2 (saamge_amd_partition_mesh_v2)."""
 
     def __init__(self, elem_to_dof, ND, elems_per_agg, elem_ptr=None, nde=0, NE=None, stream=0, **opts):
         o = partition_options(**opts)
@@ -776,9 +802,9 @@ class Partitioning(object):
             nde = int(elem_to_dof.shape[1])
         epa = (C.c_int * len(elems_per_agg))(*[int(x) for x in elems_per_agg])
         h = C.c_void_p()
-        _check(load().saamge_amd_partition_mesh(C.c_int(int(NE)), C.c_int(int(nde)), _ptr(elem_ptr), _ptr(elem_to_dof),
-                                                C.c_int(int(ND)), C.c_int(len(elems_per_agg)), epa, C.byref(o),
-                                                C.c_void_p(stream), C.byref(h)))
+        _check(_v2(o, "saamge_amd_partition_mesh")(C.c_int(int(NE)), C.c_int(int(nde)), _ptr(elem_ptr), _ptr(elem_to_dof),
+                                                   C.c_int(int(ND)), C.c_int(len(elems_per_agg)), epa, C.byref(o),
+                                                   C.c_void_p(stream), C.byref(h)))
         self.h = h
         self.num_coarsenings = len(elems_per_agg)
         self.nparts, self.n_elem = [], []

@@ -854,16 +854,30 @@ int saamge_amd_profile_get2(int i, char *name, int name_len, double *ms, long lo
 }
 
 // ---- partitions from a graph / a mesh (partition.hip) ------------------------------------------------------------------
-static PartitionOptions convert_partition_options(const saamge_amd_partition_options *o) {
+static PartitionOptions convert_partition_options(const saamge_amd_partition_options_v2 *o) {
     PartitionOptions p;
-    if (o) { p.min_shared = o->min_shared; p.lloyd_iters = o->lloyd_iters; p.max_size = o->max_size; p.min_size = o->min_size; p.seed = o->seed; p.seeding = o->seeding; }
+    if (o) { p.min_shared = o->min_shared; p.lloyd_iters = o->lloyd_iters; p.max_size = o->max_size; p.min_size = o->min_size; p.seed = o->seed; p.seeding = o->seeding; p.growth = o->growth; }
     SA_REQUIRE(p.seeding == 0 || p.seeding == 1, "partition options: seeding must be 0 or 1");
+    SA_REQUIRE(p.growth == 0 || p.growth == 1, "partition options: growth must be 0 or 1");
     return p;
 }
+// the entry points without _v2: the same fields, growth = 0
+struct PartitionOptionsV1 {
+    saamge_amd_partition_options_v2 v2;
+    bool given;
+    explicit PartitionOptionsV1(const saamge_amd_partition_options *o) : given(o != nullptr) {
+        if (o) v2 = {o->min_shared, o->lloyd_iters, o->max_size, o->min_size, o->seed, o->seeding, 0};
+    }
+    const saamge_amd_partition_options_v2 *ptr() const { return given ? &v2 : nullptr; }
+};
 
 void saamge_amd_partition_options_default(saamge_amd_partition_options *o) {
     const PartitionOptions p;
     o->min_shared = p.min_shared; o->lloyd_iters = p.lloyd_iters; o->max_size = p.max_size; o->min_size = p.min_size; o->seed = p.seed; o->seeding = p.seeding;
+}
+void saamge_amd_partition_options_v2_default(saamge_amd_partition_options_v2 *o) {
+    const PartitionOptions p;
+    o->min_shared = p.min_shared; o->lloyd_iters = p.lloyd_iters; o->max_size = p.max_size; o->min_size = p.min_size; o->seed = p.seed; o->seeding = p.seeding; o->growth = p.growth;
 }
 
 void saamge_amd_partition_seeding_info(long long info[4]) {
@@ -871,8 +885,19 @@ void saamge_amd_partition_seeding_info(long long info[4]) {
     info[0] = st.radius; info[1] = st.rounds; info[2] = st.seeds_first; info[3] = st.seeds;
 }
 
+void saamge_amd_partition_growth_info(long long info[4]) {
+    const GrowthStats st = last_growth_stats();
+    info[0] = st.rounds; info[1] = st.quota_nodes; info[2] = st.open_parts; info[3] = st.released_nodes;
+}
+
 int saamge_amd_partition_graph(int n, const long long *xadj, const int *adj, int elems_per_agg,
                                const saamge_amd_partition_options *o, void *stream, int *part, int *nparts_out) {
+    const PartitionOptionsV1 v1(o);
+    return saamge_amd_partition_graph_v2(n, xadj, adj, elems_per_agg, v1.ptr(), stream, part, nparts_out);
+}
+
+int saamge_amd_partition_graph_v2(int n, const long long *xadj, const int *adj, int elems_per_agg,
+                                  const saamge_amd_partition_options_v2 *o, void *stream, int *part, int *nparts_out) {
     SA_API_BEGIN
     SA_REQUIRE(n >= 0, "n < 0");
     SA_REQUIRE(elems_per_agg >= 1, "elems_per_agg < 1");
@@ -907,6 +932,13 @@ int saamge_amd_partition_graph(int n, const long long *xadj, const int *adj, int
 int saamge_amd_partition_mesh(int NE, int nde, const int *elem_ptr, const int *elem_to_dof, int ND, int num_coarsenings,
                               const int *elems_per_agg, const saamge_amd_partition_options *o, void *stream,
                               saamge_amd_partitioning **out) {
+    const PartitionOptionsV1 v1(o);
+    return saamge_amd_partition_mesh_v2(NE, nde, elem_ptr, elem_to_dof, ND, num_coarsenings, elems_per_agg, v1.ptr(), stream, out);
+}
+
+int saamge_amd_partition_mesh_v2(int NE, int nde, const int *elem_ptr, const int *elem_to_dof, int ND, int num_coarsenings,
+                                 const int *elems_per_agg, const saamge_amd_partition_options_v2 *o, void *stream,
+                                 saamge_amd_partitioning **out) {
     SA_API_BEGIN
     SA_REQUIRE(out && elems_per_agg && (NE == 0 || elem_to_dof), "null argument");
     SA_REQUIRE(NE >= 0 && ND >= 0, "NE < 0 or ND < 0");

@@ -12,12 +12,19 @@ struct PartitionOptions {
     int min_size = -1;    // -1: elems_per_agg / 4, 0: off
     unsigned seed = 0;
     int seeding = 0;      // 0: lowest priorities, 1: spaced (greedy distance-r independent set, topped up)
+    int growth = 0;       // 0: level-synchronous, 1: balanced (a per-round quota per part, then release)
 };
 // the spaced seeding of the calling thread's last partition_graph_device; zeros after seeding = 0
 struct SeedingStats {
     int radius = 0, rounds = 0, seeds_first = 0, seeds = 0;
 };
 SeedingStats last_seeding_stats();
+// the balanced growth of the calling thread's last partition_graph_device (its last growth, with recentring); zeros after
+// growth = 0.  rounds: those that labelled nodes; open_parts / released_nodes: at the release, 0 when there was none
+struct GrowthStats {
+    int rounds = 0, quota_nodes = 0, open_parts = 0, released_nodes = 0;
+};
+GrowthStats last_growth_stats();
 
 // Refuses offsets that are not 0-based and ascending, columns outside [0, n) and entries without their transpose.  Reads
 // adj only after xadj has been checked.  Returns xadj[n].

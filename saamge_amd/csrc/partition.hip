@@ -5,7 +5,8 @@
 //
 // Sweeps over the CSR use PT_LPR lanes per row: the lanes of a group read consecutive entries of the row, reduce by
 // shuffles, and lane 0 writes.  Growth is the pull form with two label buffers (no atomics on labels); the ball sweeps of the
-// spaced seeding are the same form with two key / two flag buffers.
+// spaced seeding are the same form with two key / two flag buffers.  Balanced growth (`growth = 1`) sweeps once per round for
+// the claims, orders the compacted claimants by two stable radix sorts and labels the first quota[p] of every part.
 #include "partition.h"
 
 #include <hipcub/hipcub.hpp>
@@ -104,6 +105,77 @@ __global__ void pt_stall_seed_kernel(const u64 *__restrict__ key, int newlabel, 
     const unsigned i = (unsigned)(*key & 0xFFFFFFFFull);
     label[i] = newlabel;
     isseed[i] = 1;
+}
+
+
+// ---- balanced growth (partition_model.py, "balanced growth") --------------------------------------------------------------
+constexpr int PT_HITS_MAX = 65535;
+__device__ inline int group_sum(int v) {
+    for (int m = PT_LPR / 2; m; m >>= 1) v += __shfl_xor(v, m);
+    return v;
+}
+// sizes of the parts while nodes are still unlabelled
+__global__ __launch_bounds__(256) void pt_count_labelled_kernel(int n, const int *__restrict__ label, int *__restrict__ sizes) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n && label[i] >= 0) atomicAdd(&sizes[label[i]], 1);
+}
+// The claim sweep.  An unlabelled node with a neighbour in an open part (sizes < cap) claims the smallest such label c; a
+// second pass over the row counts the neighbours labelled c.  Claimants are compacted in any order (the sorts that follow
+// order them by keys that never tie): keys[j] = (HITS_MAX - hits, priority), ids[j] = the node, claim[node] = c.
+// counters[0] += claimants, counters[1] += unlabelled nodes (claimants included).
+__global__ __launch_bounds__(256) void pt_claim_kernel(int n, const roff_t *__restrict__ xadj, const int *__restrict__ adj,
+                                                       const int *__restrict__ label, const int *__restrict__ sizes, int cap,
+                                                       unsigned seed, int *__restrict__ claim, u64 *__restrict__ keys,
+                                                       int *__restrict__ ids, int *__restrict__ counters) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const long v = t / PT_LPR;
+    const int lane = (int)(t % PT_LPR);
+    const bool open_row = v < n && label[v] < 0;
+    int best = INT_MAX;
+    if (open_row)
+        for (roff_t k = xadj[v] + lane, e = xadj[v + 1]; k < e; k += PT_LPR) {
+            const int lu = label[adj[k]];
+            if (lu >= 0 && lu < best && sizes[lu] < cap) best = lu;
+        }
+    best = group_min(best);
+    int hits = 0;
+    if (open_row && best != INT_MAX)
+        for (roff_t k = xadj[v] + lane, e = xadj[v + 1]; k < e; k += PT_LPR) hits += label[adj[k]] == best;
+    hits = group_sum(hits);
+    if (open_row && lane == 0) {
+        atomicAdd(&counters[1], 1);
+        if (best != INT_MAX) {
+            const int j = atomicAdd(&counters[0], 1);
+            keys[j] = ((u64)(unsigned)(PT_HITS_MAX - min(hits, PT_HITS_MAX)) << 32) | pt_prio((unsigned)v, seed);
+            ids[j] = (int)v;
+            claim[v] = best;
+        }
+    }
+}
+__global__ __launch_bounds__(256) void pt_claim_gather_kernel(int m, const int *__restrict__ ids, const int *__restrict__ claim,
+                                                              int *__restrict__ lab) {
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (j < m) lab[j] = claim[ids[j]];
+}
+// lab ascending, the claimants of one part in their order: the rank in the own run, by bisection for its start, against the
+// quota.  A node stands once in ids and the sweep that read the labels is over, so the labels are written in place.
+__global__ __launch_bounds__(256) void pt_claim_apply_kernel(int m, const int *__restrict__ lab, const int *__restrict__ ids,
+                                                             const int *__restrict__ sizes, int cap, int *__restrict__ label) {
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= m) return;
+    const int p = lab[j];
+    int lo = 0, hi = (int)j;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (lab[mid] < p) lo = mid + 1;
+        else hi = mid;
+    }
+    if ((int)j - lo < cap - sizes[p]) label[ids[j]] = p;
+}
+__global__ __launch_bounds__(256) void pt_count_open_kernel(int nlabels, const int *__restrict__ sizes, int cap,
+                                                            int *__restrict__ out) {
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p < nlabels && sizes[p] < cap) atomicAdd(out, 1);
 }
 
 // ---- seeding --------------------------------------------------------------------------------------------------------
@@ -530,6 +602,60 @@ struct Grower {
             }
         }
     }
+    // `growth = 1`: rounds of the claim sweep, the two sorts and the apply step, one read of the counters per round; then the
+    // release to grow().  The round that finds every node labelled, or no claimant, labels nothing and is not counted.
+    GrowthStats grow_balanced(int cap) {
+        GrowthStats st;
+        DBuf<int> sizes((size_t)nlabels), claim((size_t)n), ids((size_t)n), ids2((size_t)n), lab((size_t)n), lab2((size_t)n);
+        DBuf<u64> keys((size_t)n), keys2((size_t)n);
+        const int lab_bits = pt_bits(nlabels);
+        size_t tb1 = 0, tb2 = 0;
+        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb1, keys.p, keys2.p, ids.p, ids2.p, n, 0, 48, s));
+        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb2, lab.p, lab2.p, ids2.p, ids.p, n, 0, lab_bits, s));
+        const size_t tmp_bytes = std::max(tb1, tb2);
+        DBuf<char> tmp(tmp_bytes + 16);
+        int first_unlabelled = -1;
+        for (;;) {
+            sizes.zero(s);
+            counters.zero(s);
+            hipLaunchKernelGGL(pt_count_labelled_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)label, sizes.p);
+            hipLaunchKernelGGL(pt_claim_kernel, grid_rows(n), dim3(256), 0, s, n, xadj, adj, (const int *)label, (const int *)sizes.p,
+                               cap, seed, claim.p, keys.p, ids.p, counters.p);
+            SA_HIP_CHECK(hipGetLastError());
+            const auto c = counters.to_host(s);
+            const int m = c[0], unlabelled = c[1];
+            if (first_unlabelled < 0) first_unlabelled = unlabelled;
+            st.quota_nodes = first_unlabelled - unlabelled;
+            if (unlabelled == 0) break;
+            if (m == 0) {   // release
+                DBuf<int> nopen(1);
+                nopen.zero(s);
+                hipLaunchKernelGGL(pt_count_open_kernel, grid_flat(nlabels), dim3(256), 0, s, nlabels, (const int *)sizes.p, cap, nopen.p);
+                SA_HIP_CHECK(hipGetLastError());
+                st.open_parts = nopen.to_host(s)[0];
+                st.released_nodes = unlabelled;
+                break;
+            }
+            ++st.rounds;
+            // tmp was sized by the queries for n items and is reused for the m <= n of this round.  That rests on the assumption
+            // that the sort never asks for more temporary storage for fewer items; the library chooses its path by the count, so
+            // the assumption is checked by a query for m (a host call, nothing is launched) and not relied on.
+            size_t b1 = 0, b2 = 0;
+            SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, b1, keys.p, keys2.p, ids.p, ids2.p, m, 0, 48, s));
+            SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, b2, lab.p, lab2.p, ids2.p, ids.p, m, 0, lab_bits, s));
+            SA_REQUIRE(b1 <= tmp_bytes && b2 <= tmp_bytes, "balanced growth: the sort asks for more temporary storage for fewer items");
+            SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs((void *)tmp.p, b1, keys.p, keys2.p, ids.p, ids2.p, m, 0, 48, s));
+            hipLaunchKernelGGL(pt_claim_gather_kernel, grid_flat(m), dim3(256), 0, s, m, (const int *)ids2.p, (const int *)claim.p, lab.p);
+            SA_HIP_CHECK(hipGetLastError());
+            SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs((void *)tmp.p, b2, lab.p, lab2.p, ids2.p, ids.p, m, 0, lab_bits, s));
+            hipLaunchKernelGGL(pt_claim_apply_kernel, grid_flat(m), dim3(256), 0, s, m, (const int *)lab2.p, (const int *)ids.p,
+                               (const int *)sizes.p, cap, label);
+            SA_HIP_CHECK(hipGetLastError());
+        }
+        SA_HIP_CHECK(hipStreamSynchronize(s));   // the temporaries go out of scope
+        if (st.released_nodes) grow(nullptr);
+        return st;
+    }
     // sizes of the current labels (nlabels + 1 entries allocated, the last unused by the count)
     void sizes_of(DBuf<int> &sizes) {
         sizes.alloc((size_t)nlabels + 1);
@@ -686,10 +812,12 @@ constexpr int PT_MERGE_ROUNDS = 8;
 constexpr int PT_REPAIR_ROUNDS = 32;
 
 thread_local SeedingStats t_seeding_stats;
+thread_local GrowthStats t_growth_stats;
 
 }  // namespace
 
 SeedingStats last_seeding_stats() { return t_seeding_stats; }
+GrowthStats last_growth_stats() { return t_growth_stats; }
 
 int64_t check_graph_device(hipStream_t s, int n, const roff_t *xadj, const int *adj) {
     if (n == 0) return 0;
@@ -732,8 +860,10 @@ void partition_graph_device(hipStream_t s, int n, const roff_t *xadj, const int 
     SA_REQUIRE(epa >= 1, "elems_per_agg < 1");
     SA_REQUIRE(o.lloyd_iters >= 0 && o.max_size >= -1 && o.min_size >= -1, "partition options: lloyd_iters >= 0, sizes >= -1");
     SA_REQUIRE(o.seeding == 0 || o.seeding == 1, "partition options: seeding must be 0 or 1");
+    SA_REQUIRE(o.growth == 0 || o.growth == 1, "partition options: growth must be 0 or 1");
     *nparts_out = 0;
     t_seeding_stats = SeedingStats();
+    t_growth_stats = GrowthStats();
     if (n == 0) return;
     const int max_size = o.max_size < 0 ? (int)std::min<int64_t>(2ll * epa, INT_MAX) : o.max_size;
     const int min_size = o.min_size < 0 ? epa / 4 : o.min_size;
@@ -753,10 +883,14 @@ void partition_graph_device(hipStream_t s, int n, const roff_t *xadj, const int 
         SA_HIP_CHECK(hipStreamSynchronize(s));
         g.reseed(sizes, k, km1);
     }
-    g.grow(nullptr);
+    const auto grow = [&] {
+        if (o.growth == 1) t_growth_stats = g.grow_balanced(epa);
+        else g.grow(nullptr);
+    };
+    grow();
     for (int it = 0; it < o.lloyd_iters; ++it) {
         g.recentre();
-        g.grow(nullptr);
+        grow();
     }
     if (max_size > 0)
         for (int r = 0; r < PT_REPAIR_ROUNDS; ++r) {  // pieces are strictly smaller; the bound is for hubs (partition_model.py)

@@ -34,7 +34,22 @@ a minimum / maximum / count over integers, so no result depends on an execution 
                         ball has every lower-priority node of that ball already out.
   growth       level-synchronous pull: every unlabelled node with a labelled neighbour (of the same `dom`, when given) takes
                the smallest such label of the PREVIOUS round.  Nothing changed and nodes are left: the unlabelled node of
-               lowest priority becomes a seed with the next free label.
+               lowest priority becomes a seed with the next free label.  This is `growth = 0`.
+  balanced growth  `growth = 1` replaces the growth after the first seeding (either `seeding`) and the regrowth after each
+               recentring pass; the regrowth inside the size repair (`dom`) stays level-synchronous.  cap = elems_per_agg.
+               round    size[p] from the labels of the previous round; p is OPEN while size[p] < cap, its quota is
+                        cap - size[p].  Every unlabelled node u with a neighbour in an open part is a claimant of c(u), the
+                        smallest such label; hits(u) = the number of u's neighbours labelled c(u), clipped to HITS_MAX =
+                        65 535.  The claimants of p in the order (hits descending, priority ascending): the first quota[p]
+                        are labelled p, the others stay unlabelled.  Priorities never tie, so the choice is unique.
+               release  a round without claimant while nodes are unlabelled: the rest is labelled by the growth above,
+                        from all labels as they stand, its rule for a stalled component included.
+               counts   (`growth_info`) balanced rounds = the rounds that had a claimant (each labels a node); nodes
+                        labelled under a quota; parts open at the release and nodes unlabelled at it (0 and 0 when there
+                        was no release).  With recentring they are those of the last growth.
+               A node joins a part only through a neighbour already in it, so parts stay connected.  No part exceeds cap
+               before the release (a round adds at most cap - size[p] to p).  Every step is a minimum, a count or a rank
+               in a strict order, so nothing depends on an execution order.
   recentring   depth = hops to the nearest node of the own part that has a neighbour in another part, over same-label edges.
                New seed of a part = its node of largest depth, ties to the lowest priority; a part without boundary keeps
                its seed.  Labels stay with their parts; growth restarts from the new seeds.
@@ -57,6 +72,7 @@ MERGE_ROUNDS = 8
 REPAIR_ROUNDS = 32
 DEFAULT_LLOYD_ITERS = 0
 RADIUS_MAX = 32
+HITS_MAX = 65535
 
 
 def priority(n, seed=0):
@@ -135,6 +151,48 @@ def _grow(g, label, isseed, prio, nlabels, dom=None):
             label[s] = nlabels
             isseed[s] = True
             nlabels += 1
+
+
+def select_claimants(claim, hits, prio, quota):
+    """claim[u] = c(u) or -1.  Per part the quota[p] claimants first in (hits clipped descending, priority ascending)."""
+    nodes = np.flatnonzero(claim >= 0)
+    h = np.minimum(hits[nodes], HITS_MAX)
+    order = np.lexsort((prio[nodes], -h, claim[nodes]))
+    nodes = nodes[order]
+    lab = claim[nodes]
+    rank = np.arange(len(nodes)) - np.searchsorted(lab, lab, side="left")
+    chosen = np.zeros(len(claim), bool)
+    chosen[nodes[rank < quota[lab]]] = True
+    return chosen
+
+
+def _grow_balanced(g, label, isseed, prio, nlabels, cap, info, hook=None):
+    """`growth = 1`.  info (a list of 4) receives the counts; hook(label, nlabels) sees the labels before the release."""
+    BIG = np.iinfo(np.int64).max
+    info[:] = [0, 0, 0, 0]
+    while True:
+        unl = label < 0
+        if not unl.any():
+            break
+        size = np.bincount(label[~unl], minlength=nlabels)
+        lab_dst = label[g.dst]
+        m = unl[g.src] & (lab_dst >= 0)
+        m[m] = size[lab_dst[m]] < cap
+        if not m.any():
+            info[2], info[3] = int((size < cap).sum()), int(unl.sum())
+            break
+        c = np.full(g.n, BIG)
+        np.minimum.at(c, g.src[m], lab_dst[m])
+        claim = np.where(c < BIG, c, -1)
+        e = (claim[g.src] >= 0) & (lab_dst == claim[g.src])
+        hits = np.bincount(g.src[e], minlength=g.n)
+        chosen = select_claimants(claim, hits, prio, cap - size)
+        label = np.where(chosen, claim, label)
+        info[0] += 1
+        info[1] += int(chosen.sum())
+    if hook is not None:
+        hook(label.copy(), nlabels)
+    return _grow(g, label, isseed, prio, nlabels)
 
 
 def _reseed(g, label, isseed, prio, nlabels, k):
@@ -299,12 +357,18 @@ def renumber(label, nlabels):
 
 
 def partition_graph(n, xadj, adj, elems_per_agg, min_shared=1, lloyd_iters=DEFAULT_LLOYD_ITERS, max_size=-1,
-                    min_size=-1, seed=0, seeding=0):
-    """One level: symmetric CSR graph -> (part int32 (n), nparts).  min_shared is not used here (graph given)."""
+                    min_size=-1, seed=0, seeding=0, growth=0, growth_info=None, balanced_hook=None):
+    """One level: symmetric CSR graph -> (part int32 (n), nparts).  min_shared is not used here (graph given).
+    growth_info: a list that receives the four counts of the last growth (zeros for growth = 0).  balanced_hook(label,
+    nlabels) is called after every balanced phase, before its release (unlabelled nodes are -1)."""
     if elems_per_agg < 1 or n < 0:
         raise ValueError("elems_per_agg >= 1 and n >= 0")
     if seeding not in (0, 1):
         raise ValueError("seeding: 0 or 1")
+    if growth not in (0, 1):
+        raise ValueError("growth: 0 or 1")
+    info = [0, 0, 0, 0] if growth_info is None else growth_info
+    info[:] = [0, 0, 0, 0]
     if n == 0:
         return np.zeros(0, np.int32), 0
     max_size, min_size = resolve_sizes(elems_per_agg, max_size, min_size)
@@ -320,10 +384,15 @@ def partition_graph(n, xadj, adj, elems_per_agg, min_shared=1, lloyd_iters=DEFAU
         label, nlabels = np.full(n, -1, np.int64), len(seeds)
         label[seeds] = np.arange(nlabels)
         isseed[seeds] = True
-    label, nlabels = _grow(g, label, isseed, prio, nlabels)
+    def grow(label, nlabels):
+        if growth == 1:
+            return _grow_balanced(g, label, isseed, prio, nlabels, elems_per_agg, info, balanced_hook)
+        return _grow(g, label, isseed, prio, nlabels)
+
+    label, nlabels = grow(label, nlabels)
     for _ in range(lloyd_iters):
         label = _recentre(g, label, isseed, prio, nlabels)
-        label, nlabels = _grow(g, label, isseed, prio, nlabels)
+        label, nlabels = grow(label, nlabels)
     if max_size > 0:
         for _ in range(REPAIR_ROUNDS):
             sizes = np.bincount(label, minlength=nlabels)

@@ -2,10 +2,12 @@
 of the parts, on Q1 hex grids (vertex and face adjacency) and on the half-prism mesh of poisson3d_mixed_problem.  Host
 clock closed by a synchronise, one warm-up, `--reps` repetitions (all listed).  Prints one JSON line per case.
 
-    python tools/partition_time.py [--hex 128,256] [--mixed 64] [--epa 256,64] [--reps 3] [--seeding {0,1}]
+    python tools/partition_time.py [--hex 128,256] [--mixed 64] [--epa 256,64] [--reps 3] [--seeding {0,1}] [--growth {0,1}]
 
 --seeding 1 times the spaced seeding; the line then carries, per level, the radius chosen, the independent-set rounds and
-the seeds before and after the top-up (saamge_amd_partition_seeding_info; zeros for --seeding 0).
+the seeds before and after the top-up (saamge_amd_partition_seeding_info; zeros for --seeding 0).  --growth 1 times the
+balanced growth; the line carries the mode and, per level, the balanced rounds, the nodes labelled under a quota, the parts
+open at the release and the nodes labelled after it (saamge_amd_partition_growth_info; zeros for --growth 0).
 
 graph_ms is the time of partition_mesh with one coarsening minus the level-0 partition timed alone (it includes the
 quotient graph of level 0).  For the hex grids, box_setup_ms is the time of a 3-level hierarchy setup of the Poisson problem
@@ -43,6 +45,7 @@ def main():
     ap.add_argument("--epa", default="256,64")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--seeding", type=int, choices=(0, 1), default=0)
+    ap.add_argument("--growth", type=int, choices=(0, 1), default=0)
     a = ap.parse_args()
     epa = [int(x) for x in a.epa.split(",")]
     cases = []
@@ -74,7 +77,7 @@ def main():
         return [round(timed(setup)[0], 2) for _ in range(a.reps)]
 
     for name, e2d, eptr, ND, ms in cases:
-        mesh1 = lambda: capi.partition_mesh(e2d, ND, epa[:1], elem_ptr=eptr, min_shared=ms, seeding=a.seeding)
+        mesh1 = lambda: capi.partition_mesh(e2d, ND, epa[:1], elem_ptr=eptr, min_shared=ms, seeding=a.seeding, growth=a.growth)
         _, P = timed(mesh1)                         # warm-up; its graphs feed the per-level timings
         g0, g1 = P.graph(0, device=True), P.graph(1, device=True)
         n0, n1 = P.n_elem[0], P.nparts[0]
@@ -82,8 +85,8 @@ def main():
         P.close()
         d0 = torch.empty(n0, dtype=torch.int32, device="cuda")
         d1 = torch.empty(n1, dtype=torch.int32, device="cuda")
-        lev0 = lambda: capi.partition_graph(n0, g0[0], g0[1], epa[0], part=d0, seeding=a.seeding)[1]
-        lev1 = lambda: capi.partition_graph(n1, g1[0], g1[1], epa[1], part=d1, seeding=a.seeding)[1]
+        lev0 = lambda: capi.partition_graph(n0, g0[0], g0[1], epa[0], part=d0, seeding=a.seeding, growth=a.growth)[1]
+        lev1 = lambda: capi.partition_graph(n1, g1[0], g1[1], epa[1], part=d1, seeding=a.seeding, growth=a.growth)[1]
         timed(lev0), timed(lev1)
         t_mesh, t0, t1 = [], [], []
         capi.memory_stats(reset_peak=True)
@@ -93,13 +96,16 @@ def main():
             t_mesh.append(t)
             t0.append(timed(lev0)[0])
             info0 = capi.partition_seeding_info()
+            ginfo0 = capi.partition_growth_info()
             t, np1 = timed(lev1)
             info1 = capi.partition_seeding_info()
+            ginfo1 = capi.partition_growth_info()
             t1.append(t)
         peak = capi.memory_stats()[1]
         r = lambda v: [round(x, 2) for x in v]
         print(json.dumps({
-            "case": name, "seeding": a.seeding, "seeding_level0": info0, "seeding_level1": info1, "elements": n0, "graph_entries": int(g0[1].numel()), "elems_per_agg": epa,
+            "case": name, "seeding": a.seeding, "seeding_level0": info0, "seeding_level1": info1,
+            "growth": a.growth, "growth_level0": ginfo0, "growth_level1": ginfo1, "elements": n0, "graph_entries": int(g0[1].numel()), "elems_per_agg": epa,
             "nparts": [n1, int(np1)], "mesh_one_level_ms": r(t_mesh), "level0_ms": r(t0), "level1_ms": r(t1),
             "graph_ms": r([m - l for m, l in zip(t_mesh, t0)]), "peak_device_bytes": int(peak),
             "size_over_epa_level0": pm.size_stats(part0, n1, epa[0]),
