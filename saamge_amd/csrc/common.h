@@ -224,10 +224,9 @@ inline hvec<T> fetch_host(const T *src, size_t n, hipStream_t s) {
 // 96^3: 4.2e9) -- the reference splits such an operator over MPI ranks, here one GPU holds it.
 typedef int64_t roff_t;
 
-constexpr int SELL_SEG_MAX = 16;      // segments per staged tile
-constexpr int SELL_STAGE_CAP = 3584;  // doubles of x one tile may stage (28 KB of LDS)
-constexpr int SELL_PMAX = 16;         // row patterns per staged tile (DCsr::sell_row_pat)
-
+}  // namespace saamge_amd
+#include "sell.h"      // struct Sell, SELL_*: the SELL-64 copy of a DCsr
+namespace saamge_amd {
 // Device CSR matrix.
 struct DCsr {
     int nrows = 0, ncols = 0;
@@ -237,67 +236,7 @@ struct DCsr {
     DBuf<double> val;
     int lanes_per_row = 8;  // SpMV launch shape, chosen from the average row length
     mutable int max_row = -1;  // longest row (computed on first use by the fused AE assembly)
-    // optional SELL-64 copy for the SpMV family: slice s = rows 64s..64s+63, entry (k, lane)
-    // at sell_ptr[s] + 64 k + lane (padded with zero values), fully coalesced per wavefront
-    bool has_sell = false;
-    int nslices = 0;
-    int64_t sell_size = 0;
-    DBuf<roff_t> sell_ptr;
-    DBuf<int> sell_col;
-    DBuf<double> sell_val;
-    // coded slices: <= 64 distinct offsets col - row -> sell_tab[64 s + code], one byte per entry
-    // in sell_code (four consecutive entries of a row per word); sell_ntab[s] = -1: plain slice
-    // pair-coded slices (sell_ntab >= 256): <= 64 distinct (offset, VALUE) pairs, sell_vtab holds the values
-    DBuf<int> sell_ntab, sell_tab;
-    DBuf<unsigned> sell_code;
-    DBuf<double> sell_vtab;
-    // census of the copy (build_sell): slices and stored entries per format [pair-coded, offset-coded, plain], the
-    // bytes of matrix data one application streams in the formats in use, and whether the short-chain path of the
-    // pair-coded slices may be used (32-bit byte offsets into x)
-    int64_t sell_class_slices[3] = {0, 0, 0}, sell_class_entries[3] = {0, 0, 0};
-    double sell_stream_bytes = 0.0;
-    bool sell_fast_ok = false;
-    // operator-level pair dictionary (sell_gdict_kernel): an operator none of whose slices could be coded per slice but
-    // whose (offset, value) pairs repeat across the WHOLE operator (a uniform high-order mesh: Q2 elasticity has 243
-    // entries per row and ~4 900 distinct pairs) stores a 16-bit code per entry into one table of 16-byte pairs:
-    // 2 B instead of 12 B per stored entry.  sell_gcode: four codes of a row per 8-byte word, laid out like sell_code.
-    bool sell_gpair = false;
-    bool sell_bs3 = false;         // 3 x 3 node blocks: the lanes of a node share their gathers of x (sell_gpair_kernel)
-    int sell_nirr = 0;             // rows outside regular node blocks ...
-    DBuf<int> sell_irr;            // ... listed: sell_gpair3_fix_kernel redoes them
-    int sell_ng = 0;
-    DBuf<unsigned long long> sell_gcode;
-    DBuf<double2> sell_gtab;       // {offset (as the low 32 bits of .x's pattern), value}: see GPair in sparse.hip
-    // x-staging of the pair-coded slices (sell_stage_kernel): a TILE = 4 consecutive slices = the 256 rows of one workgroup.
-    // Where the column offsets of a tile cluster into few runs (a stencil: 9), the x-entries those runs touch are
-    // contiguous segments: sell_tile_nseg[t] of them (0: not staged), sell_tile_seg[SELL_SEG_MAX t + s] = {first offset
-    // relative to the tile's first row, doubles to load}; the workgroup loads them into LDS with wide coalesced loads
-    // and the products read LDS instead of gathering from global memory.  sell_stage_cap = doubles of the largest tile.
-    DBuf<int> sell_tile_nseg;
-    DBuf<int2> sell_tile_seg;
-    int sell_stage_cap = 0;
-    bool sell_one_table = false;   // every staged tile shares one pair table among its four slices
-    // sell_staged2_kernel (one-table operators): the staged tiles' code words once more in a regular layout (word q of thread t
-    // of tile T at (T sell_wq + q) 256 + t) and one descriptor word per tile (segments | the four slice widths)
-    int sell_wq = 0;
-    DBuf<unsigned> sell_codeR;
-    // row patterns (sell_row_patterns_kernel; Options::sell bit 6 set: none): the distinct code-word rows of a staged tile,
-    // at most SELL_PMAX of them, in sell_tile_pat[(T SELL_PMAX + p) 8 + q] (zero past sell_wq words and past the tile's count),
-    // and one byte per row, sell_row_pat[256 T + t], naming its pattern.  sell_tile_pinfo[T] > 0: the pattern count;
-    // <= 0: the tile has more patterns and keeps its code words in sell_codeR at slot -sell_tile_pinfo[T] (then only such
-    // tiles have slots there).  Census: pattern tiles and the largest count.
-    DBuf<unsigned char> sell_row_pat;
-    DBuf<unsigned> sell_tile_pat;
-    DBuf<int> sell_tile_pinfo;
-    int sell_pat_tiles = 0, sell_pat_max = 0;
-    // the smoother's diagonal factor as byte codes into a table of <= 256 values (operators whose rows repeat: a 256-row tile
-    // then reads 256 bytes of it instead of 2 KB); sell_dsrc: the array the codes were made from (build_dinv_codes)
-    DBuf<unsigned char> sell_dcode;
-    DBuf<unsigned long long> sell_dtab;
-    const double *sell_dsrc = nullptr;
-    DBuf<int> sell_tile_desc;
-    DBuf<int> sell_unstaged;       // tiles left to the gather kernel (sell_nunstaged of them)
-    int sell_nunstaged = 0;
+    Sell sell;  // optional SELL-64 copy for the SpMV family (sell.h)
 };
 
 // exclusive scans (mis.hip); out has n + 1 entries

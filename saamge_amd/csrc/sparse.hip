@@ -3,6 +3,7 @@
 // the XCD L2 keeps the gathered x entries, fused epilogues for the residual, the
 // prolongation-add and the polynomial-smoother step.  HBM-bound: 12 B per nonzero.
 #include "sparse.h"
+#include <array>
 #include <climits>
 
 namespace saamge_amd {
@@ -413,7 +414,7 @@ __global__ __launch_bounds__(256) void sell_staged_kernel(int nrows, int row0, i
 // the widest staged row in words -- and the widths of the four slices ride in one descriptor word per tile next to the
 // segment count: codes, right-hand side, diagonal, x-row and the tile's one table are requested before any descriptor
 // has arrived; only the x-segments wait for their (scalar-loaded) descriptors.  Operators whose staged tiles all share one
-// table per tile (sell_one_table); same products in the same order as sell_staged_kernel.
+// table per tile (Sell::Stage::one_table); same products in the same order as sell_staged_kernel.
 // pinfo (row patterns, sell_row_patterns_kernel): code words only for the tiles that have no patterns, at their slot.
 __global__ __launch_bounds__(256) void sell_regular_codes_kernel(int ntiles, int wq, int ncols, const roff_t *__restrict__ sptr,
                                                                  const int *__restrict__ tile_nseg, const int2 *__restrict__ tile_seg,
@@ -448,11 +449,11 @@ __global__ __launch_bounds__(256) void sell_regular_codes_kernel(int ntiles, int
     }
 }
 
-// Row patterns of the staged tiles (DCsr::sell_row_pat), one workgroup per tile at a time.  The code words of a 256-row tile of a
+// Row patterns of the staged tiles (Sell::Stage::row_pat), one workgroup per tile at a time.  The code words of a 256-row tile of a
 // constant-coefficient stencil repeat: the interior rows share one sequence, only rows at line ends and near boundary faces
 // differ.  Pattern p is the row of the p-th row (in row order) that equals none before it: round p takes the first row not
 // yet named (a ballot per wavefront: one barrier per round, no atomics), and every unnamed row compares its words, zero
-// padding included, with that one's.  A tile with more than SELL_PMAX patterns takes a slot for its code words in sell_codeR
+// padding included, with that one's.  A tile with more than SELL_PMAX patterns takes a slot for its code words in codeR
 // instead (census[0] counts the slots); census[1]: pattern tiles, census[2]: the largest count, census[3]: the code words of
 // the pattern tiles' slices (no longer streamed).  (A workgroup walks many tiles and adds to the census once: one atomic per
 // tile on the same word took 2.4 ms for the 66 307 tiles of the headline.)
@@ -753,7 +754,7 @@ __global__ __launch_bounds__(256) void sell_tiles_kernel(int ntl, const int *__r
                      scale, xrow, vtab);
 }
 
-// x-staging plan of the pair-coded tiles (see DCsr::sell_tile_seg): one wavefront per tile of 4 slices.  The
+// x-staging plan of the pair-coded tiles (see Sell::Stage::tile_seg): one wavefront per tile of 4 slices.  The
 // distinct column offsets of the four slice tables are sorted (bitonic, 256 keys in LDS).  An offset o needs
 // x[R0 + o .. R0 + o + 255] for the tile's 256 rows R0..: offsets no more than 256 + STAGE_GAP apart have ranges that
 // touch or overlap and become one segment [lo, hi] covering x[R0 + lo .. R0 + hi + 255] (a 27-point stencil: one
@@ -850,7 +851,7 @@ __global__ __launch_bounds__(64) void sell_stage_kernel(int ntiles, int nslices,
 }
 
 
-// ---- operator-level pair dictionary (DCsr::sell_gpair) ------------------------------------------------------------
+// ---- operator-level pair dictionary (Sell::Dict) -------------------------------------------------------------------
 struct alignas(16) GPair {
     int off, pad;      // off: (col - row) * 8, a byte offset into x (operators below 2^28 columns)
     double val;
@@ -1495,275 +1496,262 @@ void export_rowptr32(int *dst_host, const DBuf<roff_t> &src, size_t n, hipStream
     SA_HIP_CHECK(hipStreamSynchronize(s));
 }
 
-void build_sell(hipStream_t s, DCsr &A, const Options &opt) {
-    A.has_sell = false;
-    A.sell_dcode.release();      // (codes of the smoother's diagonal belong to the operator they were made for: build_dinv_codes)
-    A.sell_dsrc = nullptr;
-    if (A.nrows == 0) return;
-    A.nslices = div_up(A.nrows, 64);
-    DBuf<int> w64((size_t)A.nslices);
-    const int grid = div_up((long)A.nslices * 64, 256);
+// ---- build_sell, step by step.  A.sell starts out as Sell(): every step only fills ---------------------------------
+// slice widths, their scan, the entries
+static void fill_slices(hipStream_t s, DCsr &A) {
+    Sell &S = A.sell;
+    S.nslices = div_up(A.nrows, 64);
+    DBuf<int> w64((size_t)S.nslices);
+    const int grid = div_up((long)S.nslices * 64, 256);
     hipLaunchKernelGGL(sell_width_kernel, dim3(grid), dim3(256), 0, s, A.nrows, A.rowptr.p, w64.p);
-    A.sell_ptr.alloc((size_t)A.nslices + 1);
-    exclusive_scan_off(s, A.nslices, w64.p, A.sell_ptr.p);
-    roff_t total = 0;
-    SA_HIP_CHECK(hipMemcpyAsync(&total, A.sell_ptr.p + A.nslices, sizeof(roff_t), hipMemcpyDeviceToHost, s));
+    S.ptr.alloc((size_t)S.nslices + 1);
+    exclusive_scan_off(s, S.nslices, w64.p, S.ptr.p);
+    SA_HIP_CHECK(hipMemcpyAsync(&S.size, S.ptr.p + S.nslices, sizeof(roff_t), hipMemcpyDeviceToHost, s));
     SA_HIP_CHECK(hipStreamSynchronize(s));
-    A.sell_size = total;
-    A.sell_col.alloc((size_t)total + 64);
-    A.sell_val.alloc((size_t)total + 64);
-    hipLaunchKernelGGL(sell_fill_kernel, dim3(A.nslices), dim3(64), 0, s, A.nrows, A.rowptr.p, A.col.p,
-                       A.val.p, A.sell_ptr.p, A.sell_col.p, A.sell_val.p);
+    S.col.alloc((size_t)S.size + 64);
+    S.val.alloc((size_t)S.size + 64);
+    hipLaunchKernelGGL(sell_fill_kernel, dim3(S.nslices), dim3(64), 0, s, A.nrows, A.rowptr.p, A.col.p, A.val.p, S.ptr.p, S.col.p, S.val.p);
     SA_HIP_CHECK(hipGetLastError());
-    // byte codes for the slices with few distinct column offsets (saamge_amd_options.sell bit 0 cleared: none)
-    const bool no_codes = !(opt.sell & 1);
-    A.sell_ntab.alloc((size_t)A.nslices);
-    A.sell_tab.alloc((size_t)A.nslices * 64);
-    A.sell_code.alloc((size_t)total / 4 + (size_t)A.nslices * 64 + 64);
-    A.sell_vtab.alloc((size_t)A.nslices * 64);
-    // (bit 1 cleared: offset codes only, values always streamed)
-    const bool no_vals = !(opt.sell & 2);
-    constexpr bool no_share = false;
-    if (no_codes)
-        SA_HIP_CHECK(hipMemsetAsync(A.sell_ntab.p, 0xff, sizeof(int) * (size_t)A.nslices, s));
+}
+// byte codes for the slices with few distinct column offsets (saamge_amd_options.sell bit 0 cleared: none;
+// bit 1 cleared: offset codes only, values always streamed)
+static void code_slices(hipStream_t s, DCsr &A, const Options &opt) {
+    Sell &S = A.sell;
+    S.ntab.alloc((size_t)S.nslices);
+    S.tab.alloc((size_t)S.nslices * 64);
+    S.code.alloc((size_t)S.size / 4 + (size_t)S.nslices * 64 + 64);
+    S.vtab.alloc((size_t)S.nslices * 64);
+    if (!(opt.sell & 1))
+        SA_HIP_CHECK(hipMemsetAsync(S.ntab.p, 0xff, sizeof(int) * (size_t)S.nslices, s));
     else
-        hipLaunchKernelGGL(sell_code_kernel, dim3(div_up(A.nslices, 4)), dim3(256), 0, s, A.nslices, A.sell_ptr.p,
-                           A.sell_col.p, A.sell_val.p, A.sell_ntab.p, A.sell_tab.p, A.sell_vtab.p, A.sell_code.p,
-                           no_vals ? 0 : 1, no_share ? 0 : 1);
+        hipLaunchKernelGGL(sell_code_kernel, dim3(div_up(S.nslices, 4)), dim3(256), 0, s, S.nslices, S.ptr.p,
+                           S.col.p, S.val.p, S.ntab.p, S.tab.p, S.vtab.p, S.code.p, (opt.sell & 2) ? 1 : 0, 1);
     SA_HIP_CHECK(hipGetLastError());
-    // what the copy holds, per slice format: the bytes one application has to move (the roofline of the SpMV family
-    // prices THESE, bench.py) and whether the all-pair-coded fast path applies
+}
+// what the copy holds, per slice format: the bytes one application has to move (the roofline of the SpMV family
+// prices THESE, bench.py).  Returns sell_census_kernel's nine counters.
+static std::array<unsigned long long, 9> census(hipStream_t s, DCsr &A) {
+    Sell &S = A.sell;
     DBuf<unsigned long long> cls(9);
     SA_HIP_CHECK(hipMemsetAsync(cls.p, 0, 9 * sizeof(unsigned long long), s));
-    hipLaunchKernelGGL(sell_census_kernel, dim3(div_up(A.nslices, 256)), dim3(256), 0, s, A.nslices, A.sell_ptr.p,
-                       A.sell_ntab.p, cls.p);
+    hipLaunchKernelGGL(sell_census_kernel, dim3(div_up(S.nslices, 256)), dim3(256), 0, s, S.nslices, S.ptr.p, S.ntab.p, cls.p);
     SA_HIP_CHECK(hipGetLastError());
-    unsigned long long h[9];
-    SA_HIP_CHECK(hipMemcpyAsync(h, cls.p, sizeof(h), hipMemcpyDeviceToHost, s));
+    std::array<unsigned long long, 9> h;
+    SA_HIP_CHECK(hipMemcpyAsync(h.data(), cls.p, sizeof(h), hipMemcpyDeviceToHost, s));
     SA_HIP_CHECK(hipStreamSynchronize(s));
-    for (int c = 0; c < 3; ++c) { A.sell_class_slices[c] = (int64_t)h[c]; A.sell_class_entries[c] = (int64_t)h[3 + c]; }
+    for (int c = 0; c < 3; ++c) { S.class_slices[c] = (int64_t)h[c]; S.class_entries[c] = (int64_t)h[3 + c]; }
     // codes 4 B per word, tables 4 (+8) B per lane of a coded slice, values / columns of the formats that stream them,
     // 8 B slice offset + 4 B table size per slice
-    A.sell_stream_bytes = 4.0 * (double)h[6] + 12.0 * 64.0 * (double)(h[0] - h[8]) + 4.0 * 64.0 * (double)h[1] +
-                          8.0 * (double)h[4] + 12.0 * (double)h[5] + 12.0 * (double)A.nslices;
-    // operator-level pair dictionary for operators that are all plain slices (bit 3 cleared: never)
-    const bool no_gpair = !(opt.sell & 8);
-    A.sell_gpair = false;
-    if (!no_gpair && !no_codes && h[0] == 0 && h[1] == 0 && A.nnz >= (1 << 22) && A.ncols < (1 << 28)) {
-        DBuf<int> st((size_t)GD_CAP), ctr(2);
-        DBuf<unsigned long long> rec(2 * (size_t)GD_CAP);
-        SA_HIP_CHECK(hipMemsetAsync(st.p, 0, sizeof(int) * (size_t)GD_CAP, s));
-        SA_HIP_CHECK(hipMemsetAsync(rec.p, 0, 16 * (size_t)GD_CAP, s));
-        SA_HIP_CHECK(hipMemsetAsync(ctr.p, 0, 2 * sizeof(int), s));
-        A.sell_gcode.alloc((size_t)total / 4 + (size_t)A.nslices * 64 + 64);
-        A.sell_gtab.alloc(GP_MAX);
-        hipLaunchKernelGGL(sell_gdict_kernel, dim3(div_up(A.nslices, 4)), dim3(256), 0, s, A.nslices, A.sell_ptr.p, A.sell_col.p,
-                           A.sell_val.p, st.p, rec.p, ctr.p, (GPair *)A.sell_gtab.p, A.sell_gcode.p);
-        SA_HIP_CHECK(hipGetLastError());
-        int hc[2];
-        SA_HIP_CHECK(hipMemcpyAsync(hc, ctr.p, sizeof(hc), hipMemcpyDeviceToHost, s));
-        SA_HIP_CHECK(hipStreamSynchronize(s));
-        if (!hc[1] && hc[0] <= GP_MAX) {      // (the table has to fit LDS: see sell_gpair_kernel)
-            A.sell_gpair = true;
-            A.sell_ng = hc[0];
-            // codes 2 B per stored entry (rounded up to four per row), the table, 8 B per slice
-            const double words = (double)total / 4.0 + 64.0 * (double)A.nslices;           // upper bound of the 8-byte code words
-            A.sell_stream_bytes = 8.0 * words + 16.0 * (double)hc[0] + 8.0 * (double)A.nslices;
-            A.sell_col.release();      // the dictionary replaces the streamed columns and values (12 B per stored entry)
-            A.sell_val.release();
-            const bool no_bs3 = !(opt.sell & 16);
-            A.sell_bs3 = false;
-            if (!no_bs3 && A.ncols == A.nrows && A.nrows >= 63) {
-                const int nwaves = div_up(A.nrows, 63), cap = A.nrows / 16 + 1;      // at most a sixteenth of the rows on their own
-                A.sell_irr.alloc((size_t)cap);
-                SA_HIP_CHECK(hipMemsetAsync(ctr.p, 0, sizeof(int), s));
-                hipLaunchKernelGGL(sell_bs3_kernel, dim3(div_up(nwaves, 4)), dim3(256), 0, s, A.nrows, nwaves, A.rowptr.p, A.col.p,
-                                   A.sell_irr.p, cap, ctr.p);
-                SA_HIP_CHECK(hipGetLastError());
-                SA_HIP_CHECK(hipMemcpyAsync(&A.sell_nirr, ctr.p, sizeof(int), hipMemcpyDeviceToHost, s));
-                SA_HIP_CHECK(hipStreamSynchronize(s));
-                A.sell_bs3 = A.sell_nirr <= cap;
-                if (!A.sell_bs3) A.sell_irr.release();
-            }
-        } else {
-            A.sell_gcode.release();
-            A.sell_gtab.release();
-        }
-        if ((opt.debug & 2))
-            std::fprintf(stderr, "build_sell: operator-level pair dictionary: %d pairs%s%s\n", hc[0], A.sell_gpair ? "" : " (abandoned)",
-                         A.sell_gpair && A.sell_bs3 ? ", 3 x 3 node blocks" : "");
-        if ((opt.debug & 2) && A.sell_gpair)
-            std::fprintf(stderr, "build_sell: %d of %d rows outside regular node blocks\n", A.sell_nirr, A.nrows);
-    }
-    const bool no_fast = !(opt.sell & 4);
-    A.sell_fast_ok = !no_fast && A.ncols < (1 << 29);      // (32-bit byte offsets into x on the short-chain path)
-    // x-staging plan of the pair-coded tiles
-    constexpr bool no_stage = false;
-    A.sell_stage_cap = 0;
-    int staged_tiles = 0;
-    if (A.sell_fast_ok && !no_stage && h[0] * 2 >= (unsigned long long)A.nslices) {      // (worth a plan: most slices pair-coded)
-        const int ntiles = div_up(A.nslices, 4);
-        A.sell_tile_nseg.alloc((size_t)ntiles);
-        A.sell_tile_seg.alloc((size_t)ntiles * SELL_SEG_MAX);
-        A.sell_unstaged.alloc((size_t)ntiles);
-        DBuf<int> mx(4);
-        SA_HIP_CHECK(hipMemsetAsync(mx.p, 0, 4 * sizeof(int), s));
-        hipLaunchKernelGGL(sell_stage_kernel, dim3(ntiles), dim3(64), 0, s, ntiles, A.nslices, A.nrows, A.sell_ptr.p, A.sell_ntab.p,
-                           A.sell_tab.p, A.sell_tile_nseg.p, A.sell_tile_seg.p, mx.p, A.sell_unstaged.p);
-        SA_HIP_CHECK(hipGetLastError());
-        int hm[4];
-        SA_HIP_CHECK(hipMemcpyAsync(hm, mx.p, sizeof(hm), hipMemcpyDeviceToHost, s));
-        SA_HIP_CHECK(hipStreamSynchronize(s));
-        A.sell_stage_cap = hm[0];
-        staged_tiles = hm[1];
-        A.sell_nunstaged = hm[2];
-        if (A.sell_nunstaged * 4 > ntiles) A.sell_stage_cap = 0;      // too few tiles staged to be worth two launches
-        A.sell_one_table = hm[3] == 0;
-        A.sell_stream_bytes += (4.0 + 8.0 * SELL_SEG_MAX) * ntiles;
-        // the regular second copy of the staged tiles' code words + one descriptor word per tile (sell_staged2_kernel)
-        A.sell_wq = 0;
-        A.sell_row_pat.release();
-        A.sell_tile_pat.release();
-        A.sell_tile_pinfo.release();
-        A.sell_pat_tiles = A.sell_pat_max = 0;
-        if (A.sell_stage_cap > 0 && A.sell_one_table) {
-            A.sell_wq = (int)std::min<unsigned long long>(8, (h[7] + 3) / 4);      // (h[7]: the widest slice; staged ones are <= 32)
-            A.sell_tile_desc.alloc((size_t)ntiles);
-            // row patterns (bit 6 set: none, every staged tile keeps its code words)
-            int nslots = ntiles;
-            if (!(opt.sell & 64)) {
-                A.sell_row_pat.alloc((size_t)ntiles * 256);
-                A.sell_tile_pat.alloc((size_t)ntiles * SELL_PMAX * 8);
-                A.sell_tile_pinfo.alloc((size_t)ntiles);
-                DBuf<unsigned long long> census(4);
-                census.zero(s);
-                hipLaunchKernelGGL(sell_row_patterns_kernel, dim3(std::min(ntiles, 2048)), dim3(256), 0, s, ntiles, A.sell_wq, A.sell_ptr.p, A.sell_tile_nseg.p,
-                                   A.sell_code.p, A.sell_row_pat.p, A.sell_tile_pat.p, A.sell_tile_pinfo.p, census.p);
-                SA_HIP_CHECK(hipGetLastError());
-                unsigned long long hc[4];
-                SA_HIP_CHECK(hipMemcpyAsync(hc, census.p, sizeof(hc), hipMemcpyDeviceToHost, s));
-                SA_HIP_CHECK(hipStreamSynchronize(s));
-                nslots = (int)hc[0];
-                A.sell_pat_tiles = (int)hc[1];
-                A.sell_pat_max = (int)hc[2];
-                // every staged tile reads a byte per row, the pattern table and its count; the pattern tiles no code words
-                A.sell_stream_bytes += (256.0 + 4.0 * SELL_PMAX * 8 + 4.0) * staged_tiles - 4.0 * (double)hc[3];
-            }
-            A.sell_codeR.alloc((size_t)nslots * A.sell_wq * 256);
-            hipLaunchKernelGGL(sell_regular_codes_kernel, dim3(ntiles), dim3(256), 0, s, ntiles, A.sell_wq, A.ncols, A.sell_ptr.p,
-                               A.sell_tile_nseg.p, A.sell_tile_seg.p, A.sell_code.p, A.sell_tile_pinfo.p, A.sell_codeR.p,
-                               A.sell_tile_desc.p);
+    S.stream_bytes = 4.0 * (double)h[6] + 12.0 * 64.0 * (double)(h[0] - h[8]) + 4.0 * 64.0 * (double)h[1] +
+                     8.0 * (double)h[4] + 12.0 * (double)h[5] + 12.0 * (double)S.nslices;
+    return h;
+}
+// operator-level pair dictionary for operators that are all plain slices (bit 3 cleared: never), and their 3 x 3 node
+// blocks (bit 4 cleared: never)
+static void try_dictionary(hipStream_t s, DCsr &A, const Options &opt, const std::array<unsigned long long, 9> &h) {
+    if (!(opt.sell & 8) || !(opt.sell & 1) || h[0] != 0 || h[1] != 0 || A.nnz < (1 << 22) || A.ncols >= (1 << 28)) return;
+    Sell &S = A.sell;
+    Sell::Dict D;
+    DBuf<int> st((size_t)GD_CAP), ctr(2);
+    DBuf<unsigned long long> rec(2 * (size_t)GD_CAP);
+    SA_HIP_CHECK(hipMemsetAsync(st.p, 0, sizeof(int) * (size_t)GD_CAP, s));
+    SA_HIP_CHECK(hipMemsetAsync(rec.p, 0, 16 * (size_t)GD_CAP, s));
+    SA_HIP_CHECK(hipMemsetAsync(ctr.p, 0, 2 * sizeof(int), s));
+    D.gcode.alloc((size_t)S.size / 4 + (size_t)S.nslices * 64 + 64);
+    D.gtab.alloc(GP_MAX);
+    hipLaunchKernelGGL(sell_gdict_kernel, dim3(div_up(S.nslices, 4)), dim3(256), 0, s, S.nslices, S.ptr.p, S.col.p,
+                       S.val.p, st.p, rec.p, ctr.p, (GPair *)D.gtab.p, D.gcode.p);
+    SA_HIP_CHECK(hipGetLastError());
+    int hc[2];
+    SA_HIP_CHECK(hipMemcpyAsync(hc, ctr.p, sizeof(hc), hipMemcpyDeviceToHost, s));
+    SA_HIP_CHECK(hipStreamSynchronize(s));
+    if (!hc[1] && hc[0] <= GP_MAX) {      // (the table has to fit LDS: see sell_gpair_kernel; otherwise D is dropped)
+        D.on = true; D.ng = hc[0];
+        // codes 2 B per stored entry (rounded up to four per row), the table, 8 B per slice
+        const double words = (double)S.size / 4.0 + 64.0 * (double)S.nslices;           // upper bound of the 8-byte code words
+        S.stream_bytes = 8.0 * words + 16.0 * (double)hc[0] + 8.0 * (double)S.nslices;
+        S.col.release(); S.val.release();      // the dictionary replaces the streamed columns and values (12 B per stored entry)
+        if ((opt.sell & 16) && A.ncols == A.nrows && A.nrows >= 63) {
+            const int nwaves = div_up(A.nrows, 63), cap = A.nrows / 16 + 1;      // at most a sixteenth of the rows on their own
+            D.irr.alloc((size_t)cap);
+            SA_HIP_CHECK(hipMemsetAsync(ctr.p, 0, sizeof(int), s));
+            hipLaunchKernelGGL(sell_bs3_kernel, dim3(div_up(nwaves, 4)), dim3(256), 0, s, A.nrows, nwaves, A.rowptr.p, A.col.p,
+                               D.irr.p, cap, ctr.p);
             SA_HIP_CHECK(hipGetLastError());
+            SA_HIP_CHECK(hipMemcpyAsync(&D.nirr, ctr.p, sizeof(int), hipMemcpyDeviceToHost, s));
+            SA_HIP_CHECK(hipStreamSynchronize(s));
+            D.bs3 = D.nirr <= cap;
+            if (!D.bs3) D.irr.release();
         }
+        S.dict = std::move(D);
     }
     if ((opt.debug & 2))
-        std::fprintf(stderr, "build_sell: staging plan: %d of %d tiles, largest %d doubles, row patterns in %d tiles (at most %d)\n",
-                     staged_tiles, div_up(A.nslices, 4), A.sell_stage_cap, A.sell_pat_tiles, A.sell_pat_max);
-    if ((opt.debug & 2))
-        std::fprintf(stderr, "build_sell: %d rows, slices pair/offset/plain %lld/%lld/%lld, widest %llu, stream bytes %.0f, fast path %d\n",
-                     A.nrows, (long long)h[0], (long long)h[1], (long long)h[2], h[7], A.sell_stream_bytes, (int)A.sell_fast_ok);
-    A.has_sell = true;
+        std::fprintf(stderr, "build_sell: operator-level pair dictionary: %d pairs%s%s\n", hc[0], S.dict.on ? "" : " (abandoned)",
+                     S.dict.on && S.dict.bs3 ? ", 3 x 3 node blocks" : "");
+    if ((opt.debug & 2) && S.dict.on)
+        std::fprintf(stderr, "build_sell: %d of %d rows outside regular node blocks\n", S.dict.nirr, A.nrows);
+}
+// x-staging plan of the pair-coded tiles, where most slices are pair-coded; returns the number of staged tiles
+static int plan_staging(hipStream_t s, DCsr &A, const Options &opt, const std::array<unsigned long long, 9> &h) {
+    Sell &S = A.sell; Sell::Stage &G = S.stage;
+    if (!S.fast_ok || h[0] * 2 < (unsigned long long)S.nslices) return 0;
+    const int ntiles = div_up(S.nslices, 4);
+    G.tile_nseg.alloc((size_t)ntiles);
+    G.tile_seg.alloc((size_t)ntiles * SELL_SEG_MAX);
+    G.unstaged.alloc((size_t)ntiles);
+    DBuf<int> mx(4);
+    SA_HIP_CHECK(hipMemsetAsync(mx.p, 0, 4 * sizeof(int), s));
+    hipLaunchKernelGGL(sell_stage_kernel, dim3(ntiles), dim3(64), 0, s, ntiles, S.nslices, A.nrows, S.ptr.p, S.ntab.p,
+                       S.tab.p, G.tile_nseg.p, G.tile_seg.p, mx.p, G.unstaged.p);
+    SA_HIP_CHECK(hipGetLastError());
+    int hm[4];
+    SA_HIP_CHECK(hipMemcpyAsync(hm, mx.p, sizeof(hm), hipMemcpyDeviceToHost, s));
+    SA_HIP_CHECK(hipStreamSynchronize(s));
+    const int staged_tiles = hm[1];
+    G.nunstaged = hm[2];
+    G.cap = G.nunstaged * 4 > ntiles ? 0 : hm[0];      // (0: too few tiles staged to be worth two launches)
+    G.one_table = hm[3] == 0;
+    S.stream_bytes += (4.0 + 8.0 * SELL_SEG_MAX) * ntiles;
+    if (!G.on() || !G.one_table) return staged_tiles;
+    // the regular second copy of the staged tiles' code words + one descriptor word per tile (sell_staged2_kernel)
+    G.wq = (int)std::min<unsigned long long>(8, (h[7] + 3) / 4);      // (h[7]: the widest slice; staged ones are <= 32)
+    G.tile_desc.alloc((size_t)ntiles);
+    // row patterns (bit 6 set: none, every staged tile keeps its code words)
+    int nslots = ntiles;
+    if (!(opt.sell & 64)) {
+        G.row_pat.alloc((size_t)ntiles * 256);
+        G.tile_pat.alloc((size_t)ntiles * SELL_PMAX * 8);
+        G.tile_pinfo.alloc((size_t)ntiles);
+        DBuf<unsigned long long> census(4);
+        census.zero(s);
+        hipLaunchKernelGGL(sell_row_patterns_kernel, dim3(std::min(ntiles, 2048)), dim3(256), 0, s, ntiles, G.wq, S.ptr.p, G.tile_nseg.p,
+                           S.code.p, G.row_pat.p, G.tile_pat.p, G.tile_pinfo.p, census.p);
+        SA_HIP_CHECK(hipGetLastError());
+        unsigned long long hc[4];
+        SA_HIP_CHECK(hipMemcpyAsync(hc, census.p, sizeof(hc), hipMemcpyDeviceToHost, s));
+        SA_HIP_CHECK(hipStreamSynchronize(s));
+        nslots = (int)hc[0]; G.pat_tiles = (int)hc[1]; G.pat_max = (int)hc[2];
+        // every staged tile reads a byte per row, the pattern table and its count; the pattern tiles no code words
+        S.stream_bytes += (256.0 + 4.0 * SELL_PMAX * 8 + 4.0) * staged_tiles - 4.0 * (double)hc[3];
+    }
+    G.codeR.alloc((size_t)nslots * G.wq * 256);
+    hipLaunchKernelGGL(sell_regular_codes_kernel, dim3(ntiles), dim3(256), 0, s, ntiles, G.wq, A.ncols, S.ptr.p,
+                       G.tile_nseg.p, G.tile_seg.p, S.code.p, G.tile_pinfo.p, G.codeR.p, G.tile_desc.p);
+    SA_HIP_CHECK(hipGetLastError());
+    return staged_tiles;
 }
 
-// Rows [rr.row0, rr.row0 + rr.nrows) of A (row0 a multiple of 64 so that SELL slices line up);
-// x is indexed by GLOBAL column, the row-indexed arrays y, b, dinv are global-length too.
-template <int MODE>
-static void launch_spmv(hipStream_t s, const DCsr &A, RowRange rr, const double *x, double *y,
-                        const double *b, const double *dinv, double scale) {
-    const int row0 = rr.nrows < 0 ? 0 : rr.row0;
-    const int nrows = rr.nrows < 0 ? A.nrows : rr.nrows;
-    if (nrows == 0) return;
-    SA_REQUIRE(row0 % 64 == 0 && row0 + nrows <= A.nrows, "bad row range");
-    y += row0;
-    if (b) b += row0;
-    const unsigned char *dcode = (dinv && A.sell_dcode.n == (size_t)A.nrows && dinv == A.sell_dsrc) ? A.sell_dcode.p + row0 : nullptr;
-    if (dinv) dinv += row0;
-    const double *xrow = x + row0;
-    // (y += A x with irregular rows: the wave kernel's result for them would be added before the fix kernel adds the right
-    // one -- the plain dictionary kernel takes that case)
-    if (A.has_sell && A.sell_gpair && A.sell_bs3 && !(MODE == MODE_ADD && A.sell_nirr > 0)) {
-        // waves of 63 rows, numbered over the whole operator; the kernels take whole-operator arrays
-        const int wave0 = row0 / 63, nw = (row0 + nrows - 1) / 63 - wave0 + 1;
-        const int per_xcd = div_up(div_up(nw, 8), 16) * 16;
-        const int wgl = std::min(64, div_up(per_xcd, 16));      // (two workgroups per CU)
-        auto kern = sell_gpair3_kernel<MODE>;
-        SA_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 12 * GP_MAX + 16));
-        hipLaunchKernelGGL(kern, dim3(wgl * 8), dim3(1024), 12 * (size_t)A.sell_ng + 16, s, A.nrows, row0, row0 + nrows, wave0, nw, per_xcd, wgl, A.sell_ng,
-                           A.sell_ptr.p, A.sell_gcode.p, (const GPair *)A.sell_gtab.p, x, y - row0, b ? b - row0 : nullptr,
-                           dinv ? dinv - row0 : nullptr, scale);
-        SA_HIP_CHECK(hipGetLastError());
-        if (A.sell_nirr) {
-            hipLaunchKernelGGL(sell_gpair3_fix_kernel<MODE>, dim3(div_up(A.sell_nirr, 256)), dim3(256), 0, s, A.sell_nirr, A.sell_irr.p,
-                               row0, row0 + nrows, A.sell_ptr.p, A.sell_gcode.p, (const GPair *)A.sell_gtab.p, x, y - row0,
-                               b ? b - row0 : nullptr, dinv ? dinv - row0 : nullptr, scale);
-            SA_HIP_CHECK(hipGetLastError());
-        }
-        return;
-    }
-    if (A.has_sell && A.sell_gpair) {
-        const int nsl = div_up(nrows, 64);
-        const int per_xcd = div_up(div_up(nsl, 8), 16) * 16;
-        const int wg_per_xcd = std::min(32, div_up(per_xcd, 16));
-        const size_t lds = sizeof(GPair) * (size_t)A.sell_ng;
-        auto kern = sell_gpair_kernel<MODE>;
-        SA_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(GPair) * GP_MAX)));
-        hipLaunchKernelGGL(kern, dim3(wg_per_xcd * 8), dim3(1024), lds, s, nrows, row0, nsl, per_xcd, wg_per_xcd, A.sell_ng,
-                           A.sell_ptr.p + row0 / 64, A.sell_gcode.p, (const GPair *)A.sell_gtab.p, x, y, b, dinv, scale, xrow);
-        SA_HIP_CHECK(hipGetLastError());
-        return;
-    }
-    // (tiles are global: a row range takes the staged kernel when it starts on a tile and ends on one or with the operator)
-    if (A.has_sell && A.sell_stage_cap > 0 && row0 % 256 == 0 && (nrows % 256 == 0 || row0 + nrows == A.nrows)) {
-        const int nblocks = div_up((long)div_up(nrows, 64) * 64, 256);
-        constexpr bool no_xcd = false;
-        const int per_xcd = no_xcd ? 0 : div_up(nblocks, 8);
-        const size_t lds_bytes = 8 * (size_t)A.sell_stage_cap + (A.sell_one_table ? 1 : 4) * 64 * sizeof(PairEntry) +
-                                 (A.sell_row_pat.p ? SELL_PMAX * 8 * sizeof(unsigned) : 0);
-        // (up to eight tiles that are not staged ride at the end of the staged kernel's grid instead of a launch of their own)
-        const int grid_main = no_xcd ? nblocks : per_xcd * 8;
-        const bool fold = A.sell_wq > 0 && A.sell_nunstaged > 0 && A.sell_nunstaged <= 8 && 8 * (size_t)A.sell_stage_cap >= 4 * 64 * sizeof(PairEntry);
-        if (A.sell_wq > 0) {
-            const SellLeftover left{grid_main, fold ? A.sell_nunstaged : 0, A.sell_unstaged.p, A.sell_ptr.p + row0 / 64, A.sell_col.p, A.sell_val.p,
-                                    A.sell_ntab.p, A.sell_code.p};
-            auto kern = A.sell_row_pat.p ? sell_staged2_kernel<MODE> : sell_staged2_codes_kernel<MODE>;
-            hipLaunchKernelGGL(kern, dim3(grid_main + left.n), dim3(256), lds_bytes, s, left, nrows, row0,
-                               nblocks, per_xcd, A.sell_stage_cap, A.ncols, A.sell_wq, A.sell_codeR.p, A.sell_tab.p, A.sell_vtab.p,
-                               A.sell_tile_desc.p, A.sell_tile_seg.p, x, y, b, dinv, scale, xrow, A.sell_row_pat.p, A.sell_tile_pat.p,
-                               A.sell_tile_pinfo.p, dcode, (const double *)A.sell_dtab.p);
-        } else
-        hipLaunchKernelGGL((sell_staged_kernel<MODE>), dim3(no_xcd ? nblocks : per_xcd * 8), dim3(256), lds_bytes, s, nrows, row0,
-                           nblocks, per_xcd, A.sell_stage_cap, A.ncols, (int)A.sell_one_table, A.sell_ptr.p + row0 / 64, A.sell_ntab.p, A.sell_tab.p,
-                           A.sell_code.p, x, y, b, dinv, scale, xrow, A.sell_vtab.p, A.sell_tile_nseg.p, A.sell_tile_seg.p);
-        if (A.sell_nunstaged > 0 && !fold)
-            hipLaunchKernelGGL((sell_tiles_kernel<MODE>), dim3(A.sell_nunstaged), dim3(256), 0, s, A.sell_nunstaged, A.sell_unstaged.p,
-                               nrows, row0, A.sell_ptr.p + row0 / 64, A.sell_col.p, A.sell_val.p, A.sell_ntab.p, A.sell_tab.p,
-                               A.sell_code.p, x, y, b, dinv, scale, xrow, A.sell_vtab.p);
-        SA_HIP_CHECK(hipGetLastError());
-        return;
-    }
-    if (A.has_sell) {
-        const int nblocks = div_up((long)div_up(nrows, 64) * 64, 256);
-        constexpr bool no_xcd = false;
-        const int per_xcd = no_xcd ? 0 : div_up(nblocks, 8);     // (0: blocks in launch order)
-        hipLaunchKernelGGL((sell_spmv_kernel<MODE>), dim3(no_xcd ? nblocks : per_xcd * 8), dim3(256), 0, s, nrows, row0, nblocks, per_xcd,
-                           (int)A.sell_fast_ok, A.sell_ptr.p + row0 / 64, A.sell_col.p, A.sell_val.p, A.sell_ntab.p,
-                           A.sell_tab.p, A.sell_code.p, x, y, b, dinv, scale, xrow, A.sell_vtab.p);
-        SA_HIP_CHECK(hipGetLastError());
-        return;
-    }
+void build_sell(hipStream_t s, DCsr &A, const Options &opt) {
+    A.sell = Sell();      // (a rebuild inherits nothing -- nor the codes of the smoother's diagonal: build_dinv_codes)
+    if (A.nrows == 0) return;
+    fill_slices(s, A);
+    code_slices(s, A, opt);
+    const std::array<unsigned long long, 9> h = census(s, A);
+    try_dictionary(s, A, opt, h);
+    A.sell.fast_ok = (opt.sell & 4) && A.ncols < (1 << 29);      // (bit 2; 32-bit byte offsets into x on the short-chain path)
+    const int staged_tiles = plan_staging(s, A, opt, h);
+    if ((opt.debug & 2))
+        std::fprintf(stderr, "build_sell: staging plan: %d of %d tiles, largest %d doubles, row patterns in %d tiles (at most %d)\n",
+                     staged_tiles, div_up(A.sell.nslices, 4), A.sell.stage.cap, A.sell.stage.pat_tiles, A.sell.stage.pat_max);
+    if ((opt.debug & 2))
+        std::fprintf(stderr, "build_sell: %d rows, slices pair/offset/plain %lld/%lld/%lld, widest %llu, stream bytes %.0f, fast path %d\n",
+                     A.nrows, (long long)h[0], (long long)h[1], (long long)h[2], h[7], A.sell.stream_bytes, (int)A.sell.fast_ok);
+    A.sell.built = true;
+}
+
+// ---- the SpMV family's launches: launch_spmv chooses the format, one launcher per format holds its grid and LDS arithmetic -----
+// the rows [row0, row0 + nrows) of the operator: y, b, dinv and dcode start at row0, x is indexed by GLOBAL column (xrow = x + row0)
+struct SpmvArgs { int row0, nrows; const double *x, *xrow; double *y; const double *b, *dinv; double scale; const unsigned char *dcode; };
+// dictionary with 3 x 3 node blocks: waves of 63 rows, numbered over the whole operator; the kernels take whole-operator arrays
+template <int MODE> static void launch_dict3(hipStream_t s, const DCsr &A, const SpmvArgs &a) {
+    const Sell::Dict &D = A.sell.dict;
+    const int row0 = a.row0, nrows = a.nrows;
+    const int wave0 = row0 / 63, nw = (row0 + nrows - 1) / 63 - wave0 + 1;
+    const int per_xcd = div_up(div_up(nw, 8), 16) * 16;
+    const int wgl = std::min(64, div_up(per_xcd, 16));      // (two workgroups per CU)
+    auto kern = sell_gpair3_kernel<MODE>;
+    SA_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 12 * GP_MAX + 16));
+    hipLaunchKernelGGL(kern, dim3(wgl * 8), dim3(1024), 12 * (size_t)D.ng + 16, s, A.nrows, row0, row0 + nrows, wave0, nw, per_xcd, wgl, D.ng,
+                       A.sell.ptr.p, D.gcode.p, (const GPair *)D.gtab.p, a.x, a.y - row0, a.b ? a.b - row0 : nullptr, a.dinv ? a.dinv - row0 : nullptr, a.scale);
+    if (!D.nirr) return;
+    SA_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(sell_gpair3_fix_kernel<MODE>, dim3(div_up(D.nirr, 256)), dim3(256), 0, s, D.nirr, D.irr.p, row0, row0 + nrows, A.sell.ptr.p,
+                       D.gcode.p, (const GPair *)D.gtab.p, a.x, a.y - row0, a.b ? a.b - row0 : nullptr, a.dinv ? a.dinv - row0 : nullptr, a.scale);
+}
+template <int MODE> static void launch_dict(hipStream_t s, const DCsr &A, const SpmvArgs &a) {
+    const Sell::Dict &D = A.sell.dict;
+    const int nsl = div_up(a.nrows, 64);
+    const int per_xcd = div_up(div_up(nsl, 8), 16) * 16;
+    const int wg_per_xcd = std::min(32, div_up(per_xcd, 16));
+    const size_t lds = sizeof(GPair) * (size_t)D.ng;
+    auto kern = sell_gpair_kernel<MODE>;
+    SA_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(GPair) * GP_MAX)));
+    hipLaunchKernelGGL(kern, dim3(wg_per_xcd * 8), dim3(1024), lds, s, a.nrows, a.row0, nsl, per_xcd, wg_per_xcd, D.ng,
+                       A.sell.ptr.p + a.row0 / 64, D.gcode.p, (const GPair *)D.gtab.p, a.x, a.y, a.b, a.dinv, a.scale, a.xrow);
+}
+// staged tiles (a row range of whole tiles: see launch_spmv), and the gather kernel for the tiles that are not staged
+template <int MODE> static void launch_staged(hipStream_t s, const DCsr &A, const SpmvArgs &a) {
+    const Sell &S = A.sell; const Sell::Stage &G = S.stage;
+    const int nblocks = div_up((long)div_up(a.nrows, 64) * 64, 256);
+    const int per_xcd = div_up(nblocks, 8), grid_main = per_xcd * 8;
+    const size_t lds_bytes = 8 * (size_t)G.cap + (G.one_table ? 1 : 4) * 64 * sizeof(PairEntry) +
+                             (G.patterns() ? SELL_PMAX * 8 * sizeof(unsigned) : 0);
+    // (up to eight tiles that are not staged ride at the end of the staged kernel's grid instead of a launch of their own)
+    const bool fold = G.regular() && G.nunstaged > 0 && G.nunstaged <= 8 && 8 * (size_t)G.cap >= 4 * 64 * sizeof(PairEntry);
+    if (G.regular()) {
+        const SellLeftover left{grid_main, fold ? G.nunstaged : 0, G.unstaged.p, S.ptr.p + a.row0 / 64, S.col.p, S.val.p, S.ntab.p, S.code.p};
+        auto kern = G.patterns() ? sell_staged2_kernel<MODE> : sell_staged2_codes_kernel<MODE>;
+        hipLaunchKernelGGL(kern, dim3(grid_main + left.n), dim3(256), lds_bytes, s, left, a.nrows, a.row0, nblocks, per_xcd, G.cap, A.ncols, G.wq,
+                           G.codeR.p, S.tab.p, S.vtab.p, G.tile_desc.p, G.tile_seg.p, a.x, a.y, a.b, a.dinv, a.scale, a.xrow, G.row_pat.p, G.tile_pat.p,
+                           G.tile_pinfo.p, a.dcode, (const double *)S.dcode.tab.p);
+    } else
+        hipLaunchKernelGGL((sell_staged_kernel<MODE>), dim3(grid_main), dim3(256), lds_bytes, s, a.nrows, a.row0, nblocks, per_xcd, G.cap, A.ncols,
+                           (int)G.one_table, S.ptr.p + a.row0 / 64, S.ntab.p, S.tab.p, S.code.p, a.x, a.y, a.b, a.dinv, a.scale, a.xrow, S.vtab.p, G.tile_nseg.p, G.tile_seg.p);
+    if (G.nunstaged > 0 && !fold)
+        hipLaunchKernelGGL((sell_tiles_kernel<MODE>), dim3(G.nunstaged), dim3(256), 0, s, G.nunstaged, G.unstaged.p, a.nrows, a.row0,
+                           S.ptr.p + a.row0 / 64, S.col.p, S.val.p, S.ntab.p, S.tab.p, S.code.p, a.x, a.y, a.b, a.dinv, a.scale, a.xrow, S.vtab.p);
+}
+template <int MODE> static void launch_slices(hipStream_t s, const DCsr &A, const SpmvArgs &a) {
+    const Sell &S = A.sell;
+    const int nblocks = div_up((long)div_up(a.nrows, 64) * 64, 256);
+    const int per_xcd = div_up(nblocks, 8);
+    hipLaunchKernelGGL((sell_spmv_kernel<MODE>), dim3(per_xcd * 8), dim3(256), 0, s, a.nrows, a.row0, nblocks, per_xcd, (int)S.fast_ok,
+                       S.ptr.p + a.row0 / 64, S.col.p, S.val.p, S.ntab.p, S.tab.p, S.code.p, a.x, a.y, a.b, a.dinv, a.scale, a.xrow, S.vtab.p);
+}
+template <int MODE> static void launch_csr(hipStream_t s, const DCsr &A, const SpmvArgs &a) {
     const int L = A.lanes_per_row;
-    const long threads = (long)nrows * L;
-    const int grid = div_up(threads, 256);
+    const int grid = div_up((long)a.nrows * L, 256);
 #define SA_CASE(LL)                                                                              \
     case LL:                                                                                     \
-        hipLaunchKernelGGL((spmv_kernel<LL, MODE>), dim3(grid), dim3(256), 0, s, nrows,          \
-                           A.rowptr.p + row0, A.col.p, A.val.p, x, y, b, dinv, scale, xrow);     \
+        hipLaunchKernelGGL((spmv_kernel<LL, MODE>), dim3(grid), dim3(256), 0, s, a.nrows,        \
+                           A.rowptr.p + a.row0, A.col.p, A.val.p, a.x, a.y, a.b, a.dinv, a.scale, a.xrow); \
         break;
     switch (L) {
         SA_CASE(1) SA_CASE(2) SA_CASE(4) SA_CASE(8) SA_CASE(16) SA_CASE(32) SA_CASE(64)
         default: SA_REQUIRE(false, "bad lanes_per_row");
     }
 #undef SA_CASE
+}
+
+// Rows [rr.row0, rr.row0 + rr.nrows) of A (row0 a multiple of 64 so that SELL slices line up);
+// x is indexed by GLOBAL column, the row-indexed arrays y, b, dinv are global-length too.
+template <int MODE>
+static void launch_spmv(hipStream_t s, const DCsr &A, RowRange rr, const double *x, double *y, const double *b, const double *dinv, double scale) {
+    const int row0 = rr.nrows < 0 ? 0 : rr.row0;
+    const int nrows = rr.nrows < 0 ? A.nrows : rr.nrows;
+    if (nrows == 0) return;
+    SA_REQUIRE(row0 % 64 == 0 && row0 + nrows <= A.nrows, "bad row range");
+    const Sell &S = A.sell;
+    const SpmvArgs a{row0, nrows, x, x + row0, y + row0, b ? b + row0 : nullptr, dinv ? dinv + row0 : nullptr, scale,
+                     S.dcode.for_(dinv) ? S.dcode.code.p + row0 : nullptr};
+    // (y += A x with irregular rows: the wave kernel's result for them would be added before the fix kernel adds the right
+    // one -- the plain dictionary kernel takes that case)
+    if (S.built && S.dict.on && S.dict.bs3 && !(MODE == MODE_ADD && S.dict.nirr > 0)) launch_dict3<MODE>(s, A, a);
+    else if (S.built && S.dict.on) launch_dict<MODE>(s, A, a);
+    // (tiles are global: a row range takes the staged kernel when it starts on a tile and ends on one or with the operator)
+    else if (S.built && S.stage.on() && row0 % 256 == 0 && (nrows % 256 == 0 || row0 + nrows == A.nrows)) launch_staged<MODE>(s, A, a);
+    else if (S.built) launch_slices<MODE>(s, A, a);
+    else launch_csr<MODE>(s, A, a);
     SA_HIP_CHECK(hipGetLastError());
 }
 
@@ -1774,9 +1762,9 @@ static inline double spmv_bytes(const DCsr &A, RowRange rr) {
 static inline double spmv_rows(const DCsr &A, RowRange rr) { return rr.nrows < 0 ? A.nrows : rr.nrows; }
 // bytes of matrix data in the format the kernels run (build_sell's census) + x read and y written once
 static inline double spmv_fmt_bytes(const DCsr &A, RowRange rr) {
-    if (!A.has_sell) return 0.0;
+    if (!A.sell.built) return 0.0;
     const double frac = (rr.nrows < 0 || A.nrows == 0) ? 1.0 : (double)rr.nrows / A.nrows;
-    return (A.sell_stream_bytes + 16.0 * A.nrows) * frac;
+    return (A.sell.stream_bytes + 16.0 * A.nrows) * frac;
 }
 // the SpMV family is listed per operator size: "<name>@<rows>" (the levels of a hierarchy have very different formats)
 static inline std::string spmv_label(const char *name, const DCsr &A) { return std::string(name) + "@" + std::to_string(A.nrows); }
@@ -1793,22 +1781,21 @@ void spmv_residual(hipStream_t s, const DCsr &A, const double *x, const double *
     profiler().begin(s);
     launch_spmv<MODE_RESIDUAL>(s, A, rr, x, r, b, nullptr, 0.0);
     profiler().end(s, spmv_label("spmv_residual", A).c_str(), spmv_bytes(A, rr) + 8.0 * spmv_rows(A, rr), spmv_flops(A, rr),
-                   spmv_fmt_bytes(A, rr) + (A.has_sell ? 8.0 * spmv_rows(A, rr) : 0.0));
+                   spmv_fmt_bytes(A, rr) + (A.sell.built ? 8.0 * spmv_rows(A, rr) : 0.0));
 }
 void spmv_add(hipStream_t s, const DCsr &P, const double *xc, double *x, RowRange rr) {
     profiler().begin(s);
     launch_spmv<MODE_ADD>(s, P, rr, xc, x, nullptr, nullptr, 0.0);
     profiler().end(s, spmv_label("spmv_add", P).c_str(), spmv_bytes(P, rr) + 8.0 * spmv_rows(P, rr), spmv_flops(P, rr),
-                   spmv_fmt_bytes(P, rr) + (P.has_sell ? 8.0 * spmv_rows(P, rr) : 0.0));
+                   spmv_fmt_bytes(P, rr) + (P.sell.built ? 8.0 * spmv_rows(P, rr) : 0.0));
 }
 void smooth_step(hipStream_t s, const DCsr &A, const double *dinv_neg, const double *b,
                  const double *xin, double *xout, double scale, RowRange rr) {
     profiler().begin(s);
     launch_spmv<MODE_SMOOTH>(s, A, rr, xin, xout, b, dinv_neg, scale);
     // (b, and D^-1 as it is read: 8 bytes per row, or its byte code where the operator carries one -- build_dinv_codes)
-    const bool coded_d = A.sell_dcode.n == (size_t)A.nrows && dinv_neg == A.sell_dsrc && A.sell_wq > 0 && A.sell_stage_cap > 0;
     profiler().end(s, spmv_label("smooth_step", A).c_str(), spmv_bytes(A, rr) + 24.0 * spmv_rows(A, rr), spmv_flops(A, rr),
-                   spmv_fmt_bytes(A, rr) + (A.has_sell ? (coded_d ? 9.0 : 16.0) * spmv_rows(A, rr) : 0.0));
+                   spmv_fmt_bytes(A, rr) + (A.sell.built ? (A.sell.dcode.for_(dinv_neg) ? 9.0 : 16.0) * spmv_rows(A, rr) : 0.0));
 }
 
 __global__ __launch_bounds__(256) void smooth_first_kernel(int n, const double *__restrict__ dinv,
@@ -1872,7 +1859,7 @@ void build_dinv_neg(hipStream_t s, const DCsr &A, double *sd, double *out) {
     SA_HIP_CHECK(hipGetLastError());
 }
 
-// The smoother's diagonal factor as byte codes (DCsr::sell_dcode): every value goes into an open-addressing table of 256
+// The smoother's diagonal factor as byte codes (Sell::dcode): every value goes into an open-addressing table of 256
 // slots (key = its bits); more than 256 distinct values (variable coefficients) -- no codes.  The code of a row is the
 // slot of its value, the table is read as doubles.
 constexpr unsigned long long DINV_EMPTY = 0x7FF8DEADBEEF0001ull;      // (a NaN payload no diagonal produces)
@@ -1906,25 +1893,25 @@ __global__ __launch_bounds__(256) void dinv_code_kernel(int n, const double *__r
     code[i] = (unsigned char)h;
 }
 void build_dinv_codes(hipStream_t s, DCsr &A, const double *dinv, const Options &opt) {
-    A.sell_dcode.release();
-    A.sell_dsrc = nullptr;
+    Sell::DCode &D = A.sell.dcode;
+    D = {};
     // (only the staged kernel of the coded formats reads them.  Options::sell bit 5, off by default: measured on the 256^3
     // problem, 960 instead of 1 079 MB per application (PMC: 967 / 1 086) and 205.1 instead of 210.5 us -- the kernel is not
     // bound by its bytes alone, 2.3 % for 11 % of them)
-    if (!A.nrows || !A.has_sell || A.sell_wq <= 0 || !(opt.sell & 32)) return;
-    A.sell_dtab.alloc(256);
+    if (!A.nrows || !A.sell.built || !A.sell.stage.regular() || !(opt.sell & 32)) return;
+    D.tab.alloc(256);
     std::vector<unsigned long long> empty(256, DINV_EMPTY);
-    SA_HIP_CHECK(hipMemcpyAsync(A.sell_dtab.p, empty.data(), 256 * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+    SA_HIP_CHECK(hipMemcpyAsync(D.tab.p, empty.data(), 256 * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
     DBuf<int> overflow(1);
     overflow.zero(s);
     SA_HIP_CHECK(hipStreamSynchronize(s));      // (empty is a local)
-    hipLaunchKernelGGL(dinv_tab_kernel, dim3(div_up(A.nrows, 256)), dim3(256), 0, s, A.nrows, dinv, A.sell_dtab.p, overflow.p);
+    hipLaunchKernelGGL(dinv_tab_kernel, dim3(div_up(A.nrows, 256)), dim3(256), 0, s, A.nrows, dinv, D.tab.p, overflow.p);
     SA_HIP_CHECK(hipGetLastError());
     if (overflow.to_host(s)[0]) return;
-    A.sell_dcode.alloc((size_t)A.nrows);
-    hipLaunchKernelGGL(dinv_code_kernel, dim3(div_up(A.nrows, 256)), dim3(256), 0, s, A.nrows, dinv, A.sell_dtab.p, A.sell_dcode.p);
+    D.code.alloc((size_t)A.nrows);
+    hipLaunchKernelGGL(dinv_code_kernel, dim3(div_up(A.nrows, 256)), dim3(256), 0, s, A.nrows, dinv, D.tab.p, D.code.p);
     SA_HIP_CHECK(hipGetLastError());
-    A.sell_dsrc = dinv;
+    D.src = dinv;
 }
 
 // ---- deterministic dot product -----------------------------------------------------------

@@ -244,7 +244,7 @@ void spgemm(hipStream_t s, const DCsr &A, const DCsr &B, const DCsr *E, const do
     C.nrows = n;
     C.ncols = B.ncols;
     C.nnz = 0;
-    C.has_sell = false;
+    C.sell = Sell();
     C.max_row = -1;
     C.rowptr.alloc((size_t)n + 1);
     if (n == 0) {   // the empty matrix: its one row offset
@@ -352,7 +352,7 @@ void csr_transpose(hipStream_t s, const DCsr &P, DCsr &R) {
     R.nrows = P.ncols;
     R.ncols = P.nrows;
     R.nnz = P.nnz;
-    R.has_sell = false;
+    R.sell = Sell();
     R.max_row = -1;
     R.rowptr.alloc((size_t)R.nrows + 1);
     R.col.alloc((size_t)P.nnz + 1);
@@ -408,7 +408,7 @@ __global__ __launch_bounds__(256) void threshold_kernel(int nrows, double tol, c
 void csr_threshold(hipStream_t s, const DCsr &A, double tol, DCsr &C) {
     C.nrows = A.nrows;
     C.ncols = A.ncols;
-    C.has_sell = false;
+    C.sell = Sell();
     C.max_row = -1;
     C.rowptr.alloc((size_t)A.nrows + 1);
     if (A.nrows == 0) {   // (the scan has no block to launch either)

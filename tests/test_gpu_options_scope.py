@@ -58,6 +58,58 @@ def test_a_hierarchy_keeps_its_options():
                 h.close()
 
 
+def _format(h):
+    return {k: v for k, v in h.level_format(0).items() if k != "eigenproblems_solved"}
+
+
+@pytest.mark.gpu
+def test_rebuild_inherits_nothing():
+    """update_operators rebuilds the SELL copy of every level operator in place.  Here the rebuild CHANGES the format:
+    from the constant-coefficient stencil (pair-coded slices, staged tiles, row patterns) to A' = diag(d) A diag(d) with
+    all d different (no two entries of a slice share an (offset, value) pair: no pair codes, no staging plan) and back.
+    After each rebuild the format census and the level-0 smoother (bitwise) are those of a hierarchy built on that
+    operator directly: nothing of the previous copy is left.
+
+    32 x 32 x 16 nodes: 16 384 dofs, 64 tiles of 256 rows and no partial last slice -- a slice of fewer than 64 rows
+    could still fit its distinct pairs into a table of 64, and every full one has 64 different diagonal entries alone."""
+    import torch
+    from saamge_amd import problems as pr
+    prob = pr.poisson3d_device((31, 31, 15), blk=(8, 8, 4), device="cuda:0")
+    assert prob.n % 256 == 0
+    params = capi.default_params(num_coarsenings=1, theta=0.003, nu_relax=3)
+    torch.manual_seed(20261)
+    b = torch.randn(prob.n, dtype=torch.float64, device="cuda:0")
+    h = h2 = None
+    try:
+        h = _build(prob, params)
+        fmt_rich = _format(h)
+        print("rich:", fmt_rich)
+        assert fmt_rich["slices"]["pair_coded"] > 0 and fmt_rich["staged_tiles"] > 0
+        y_rich = h.smoother(0, b, torch.zeros_like(b)).clone()
+
+        A = h.get_csr(0, "A")
+        d = 1.0 + np.arange(prob.n) / prob.n
+        rows = np.repeat(np.arange(prob.n), np.diff(A.indptr))
+        val2 = A.data * d[rows] * d[A.indices]
+        h.update_operators(val2)
+        fmt_poor = _format(h)
+        print("poor:", fmt_poor)
+        assert fmt_poor["slices"]["pair_coded"] == 0 and fmt_poor["staged_tiles"] == 0
+        assert np.array_equal(A.indices, prob.col.cpu().numpy())      # (get_csr returns the operator in the order it was given)
+        prob2 = pr.Problem(**dict(prob.__dict__, val=torch.from_numpy(val2).to("cuda:0")))
+        h2 = _build(prob2, params)
+        assert _format(h2) == fmt_poor
+        assert torch.equal(h.smoother(0, b, torch.zeros_like(b)), h2.smoother(0, b, torch.zeros_like(b)))
+
+        h.update_operators(A.data)
+        assert _format(h) == fmt_rich
+        assert torch.equal(h.smoother(0, b, torch.zeros_like(b)), y_rich)
+    finally:
+        for hh in (h, h2):
+            if hh is not None:
+                hh.close()
+
+
 @pytest.mark.gpu
 def test_building_does_not_leak_into_the_default():
     prob = _problem()

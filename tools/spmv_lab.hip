@@ -157,15 +157,15 @@ int main(int argc, char **argv) {
     build_sell(s, A, Options());
     hipStreamSynchronize(s);
     printf("n=%d rows=%ld nnz=%lld slices pair/offset/plain %lld/%lld/%lld stream bytes %.3f GB\n", n, N, (long long)nnz,
-           (long long)A.sell_class_slices[0], (long long)A.sell_class_slices[1], (long long)A.sell_class_slices[2],
-           A.sell_stream_bytes * 1e-9);
+           (long long)A.sell.class_slices[0], (long long)A.sell.class_slices[1], (long long)A.sell.class_slices[2],
+           A.sell.stream_bytes * 1e-9);
     DBuf<double> b((size_t)N), dinv((size_t)N), x0((size_t)N), x1((size_t)N), x2((size_t)N);
     hipLaunchKernelGGL(init_kernel, dim3(grid), dim3(256), 0, s, N, b.p, 1.0);
     hipLaunchKernelGGL(init_kernel, dim3(grid), dim3(256), 0, s, N, dinv.p, -0.1);
     hipLaunchKernelGGL(init_kernel, dim3(grid), dim3(256), 0, s, N, x0.p, 0.5);
     hipLaunchKernelGGL(init_kernel, dim3(grid), dim3(256), 0, s, N, x1.p, 0.25);
     const int reps = 20;
-    const double fmt = A.sell_stream_bytes;
+    const double fmt = A.sell.stream_bytes;
     auto report = [&](const char *name, double us, double bytes) {
         printf("%-58s %8.1f us  %6.2f TB/s of %.3f GB\n", name, us, bytes / us * 1e-6, bytes * 1e-9);
         fflush(stdout);
@@ -188,18 +188,18 @@ int main(int argc, char **argv) {
     us = time_us(s, reps, [&](int) { smooth_step(s, A, dinv.p, b.p, x0.p, x2.p, 0.7); spmv(s, A, x0.p, x1.p); });
     report("smooth_step + spmv pair (sum)", us, 2 * fmt + 48.0 * N);
     const int wpr = 7;
-    us = time_us(s, reps, [&](int) { hipLaunchKernelGGL(stream_mix_kernel, dim3(grid), dim3(256), 0, s, N, A.sell_code.p, x0.p, b.p, dinv.p, x1.p, wpr); });
+    us = time_us(s, reps, [&](int) { hipLaunchKernelGGL(stream_mix_kernel, dim3(grid), dim3(256), 0, s, N, A.sell.code.p, x0.p, b.p, dinv.p, x1.p, wpr); });
     report("stream_mix: 7 code words + 3 vectors in, 1 out (coalesced)", us, (4.0 * wpr + 32.0) * N);
-    us = time_us(s, reps, [&](int) { hipLaunchKernelGGL(stream_mix_kernel, dim3(grid), dim3(256), 0, s, N, A.sell_code.p, x0.p, x0.p, x0.p, x1.p, wpr); });
+    us = time_us(s, reps, [&](int) { hipLaunchKernelGGL(stream_mix_kernel, dim3(grid), dim3(256), 0, s, N, A.sell.code.p, x0.p, x0.p, x0.p, x1.p, wpr); });
     report("stream_mix with one vector in", us, (4.0 * wpr + 16.0) * N);
-    us = time_us(s, reps, [&](int) { hipLaunchKernelGGL(stream_mix_kernel, dim3(grid), dim3(256), 0, s, N, A.sell_code.p, x0.p, b.p, dinv.p, x1.p, 0); });
+    us = time_us(s, reps, [&](int) { hipLaunchKernelGGL(stream_mix_kernel, dim3(grid), dim3(256), 0, s, N, A.sell.code.p, x0.p, b.p, dinv.p, x1.p, 0); });
     report("stream_mix without codes (3 vectors in, 1 out)", us, 32.0 * N);
     {
         const int nblocks = (int)((N + 255) / 256), per_xcd = (nblocks + 7) / 8;
 #define LAB(FLAGS, NAME)                                                                                                      \
         us = time_us(s, reps, [&](int) {                                                                                      \
             hipLaunchKernelGGL((lab_kernel<FLAGS>), dim3(((FLAGS) & L_XCD) ? per_xcd * 8 : nblocks), dim3(256), 0, s, (int)N, nblocks, \
-                               per_xcd, A.sell_ptr.p, A.sell_ntab.p, A.sell_tab.p, A.sell_vtab.p, A.sell_code.p, x0.p, b.p, dinv.p, x1.p); \
+                               per_xcd, A.sell.ptr.p, A.sell.ntab.p, A.sell.tab.p, A.sell.vtab.p, A.sell.code.p, x0.p, b.p, dinv.p, x1.p); \
         });                                                                                                                   \
         report(NAME, us, fmt + 32.0 * N);
         LAB(0, "lab: codes + b, dinv, x in, y out (no table, no fma)")
