@@ -679,6 +679,54 @@ bool coarse_e2d_device(hipStream_t s, const DevRelations &rel, const Relations &
 constexpr int RAP_NT = 256;
 constexpr int RAP_HASH = 2048;
 constexpr int RAP_SMALL_ROWS = 64;     // MISes of at most this many dofs take a one-wavefront workgroup in the numeric kernel
+constexpr int RAP_SUB = 64;            // rows of a MIS whose entries are dealt out to the lanes together (one wavefront scans their lengths)
+constexpr int RAP_ROW_CLAMP = 1 << 24; // longest row of A the 32-bit entry counts of RAP_SUB rows allow
+
+// Per dof one word {MIS id: bits 0-31, row in its MIS: bits 32-62, "its MIS has k = 0": bit 63}: the walks over the entries of A
+// gather this instead of mises[], row_in_mis[] and k[mises[]].  Built once per level, after the k are known.
+typedef unsigned long long rap_word_t;
+constexpr rap_word_t RAP_K0 = 1ull << 63;
+__global__ __launch_bounds__(256) void rap_pack_kernel(int n, const int *__restrict__ mises, const int *__restrict__ row_in_mis,
+                                                       const int *__restrict__ k, rap_word_t *__restrict__ pack) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int m = mises[i];
+    pack[i] = (rap_word_t)(unsigned)m | ((rap_word_t)(unsigned)row_in_mis[i] << 32) | (k[m] == 0 ? RAP_K0 : 0ull);
+}
+
+// Lanes 0..63 of the workgroup: the lengths of the rows dofs[0 .. nr) of A (nr <= RAP_SUB), each counted as at most `clamp`, to
+// their exclusive prefix pre[0 .. nr] and the rows' first entries to qs[0 .. nr).  The caller's barrier publishes them.
+__device__ inline void rap_row_prefix(int nr, const int *__restrict__ dofs, const roff_t *__restrict__ Arow, int clamp,
+                                      int *pre, roff_t *qs) {
+    if (threadIdx.x >= 64) return;
+    const int l = threadIdx.x;
+    int len = 0;
+    if (l < nr) {
+        const int g = dofs[l];
+        const roff_t q0 = Arow[g], n = Arow[g + 1] - q0;
+        len = n < (roff_t)clamp ? (int)n : clamp;
+        qs[l] = q0;
+    }
+    int inc = len;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(inc, o, 64);
+        if (l >= o) inc += t;
+    }
+    if (l < nr) pre[l + 1] = inc;
+    if (l == 0) pre[0] = 0;
+}
+
+// Row of entry e of the rows [ra, rb) (base = pre[ra], 0 <= e < pre[rb] - base): the last row that starts at or before e
+// (rows without entries start where the next one does and are passed over).
+__device__ inline int rap_entry_row(const int *pre, int ra, int rb, int base, int e) {
+    int lo = ra, hi = rb;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (pre[mid] - base <= e) lo = mid; else hi = mid;
+    }
+    return lo;
+}
 
 // symbolic: neighbour MISes (with k > 0) of every MIS; pass 0 counts, pass 1 writes the
 // ascending list.
@@ -686,15 +734,19 @@ constexpr int RAP_SMALL_ROWS = 64;     // MISes of at most this many dofs take a
 // RAP_SMALL_ROWS dofs take <64, 256>: one wavefront and 2 KB of tables instead of four and 16 KB (as in rap_numeric_kernel: a
 // workgroup costs tens of microseconds whatever its MIS holds, so what counts is how many are resident); one whose neighbours
 // do not fit 128 of those 256 slots reports cnt = -1 and is done again by <RAP_NT, RAP_HASH>.
+// The entries of RAP_SUB rows at a time are dealt out one per lane (nothing here depends on their order): a vertex MIS keeps
+// 27 lanes busy for one round of gathers instead of one lane for 27.
 template <int NT, int CAP>
 __global__ __launch_bounds__(NT) void rap_symbolic_kernel(
     const int *__restrict__ mlist, int pass, const int *__restrict__ mis2d_I, const int *__restrict__ mis2d_J,
-    const roff_t *__restrict__ Arow, const int *__restrict__ Acol, const int *__restrict__ mises,
+    const roff_t *__restrict__ Arow, const int *__restrict__ Acol, const rap_word_t *__restrict__ pack,
     const int *__restrict__ k, int *__restrict__ cnt, const int *__restrict__ nbr_ptr,
     int *__restrict__ nbr, int *__restrict__ err, int *__restrict__ stage = nullptr, int stage_cap = 0,
     int maxrow = 0) {
     __shared__ int table[CAP];
     __shared__ int nfound;
+    __shared__ roff_t qs[RAP_SUB];
+    __shared__ int pre[RAP_SUB + 1];
     const int m1 = mlist ? mlist[blockIdx.x] : (int)blockIdx.x;
     if (k[m1] == 0) {
         if (pass == 0 && threadIdx.x == 0) cnt[m1] = 0;
@@ -719,11 +771,16 @@ __global__ __launch_bounds__(NT) void rap_symbolic_kernel(
         for (int i = threadIdx.x; i < HS; i += NT) table[i] = -1;
         if (threadIdx.x == 0) { nfound = 0; overflow = 0; }
         __syncthreads();
-        for (int il = threadIdx.x; il < r1; il += NT) {
-            const int g = dofs[il];
-            for (roff_t q = Arow[g]; q < Arow[g + 1]; ++q) {
-                const int m2 = mises[Acol[q]];
-                if (k[m2] == 0) continue;
+        for (int s0 = 0; s0 < r1; s0 += RAP_SUB) {
+            const int nr = min(RAP_SUB, r1 - s0);
+            rap_row_prefix(nr, dofs + s0, Arow, RAP_ROW_CLAMP, pre, qs);
+            __syncthreads();
+            const int ne = pre[nr];
+            for (int e = threadIdx.x; e < ne; e += NT) {
+                const int row = rap_entry_row(pre, 0, nr, 0, e);
+                const rap_word_t w = pack[Acol[qs[row] + (e - pre[row])]];
+                if (w & RAP_K0) continue;
+                const int m2 = (int)(unsigned)w;
                 unsigned h = hash_home((unsigned)m2, (unsigned)HS);
                 for (int probe = 0; probe < HS; ++probe) {
                     const int old = atomicCAS(&table[h], -1, m2);
@@ -733,8 +790,8 @@ __global__ __launch_bounds__(NT) void rap_symbolic_kernel(
                     if (probe == HS - 1) { if (HS == RAP_HASH) atomicExch(err, 1); else overflow = 1; }
                 }
             }
+            __syncthreads();
         }
-        __syncthreads();
         // (more than half full counts as full: the probe sequences get long, and the rank pass below is quadratic)
         const bool full = !certain && (overflow || 2 * nfound > HS);
         const bool again = HS < CAP && full;
@@ -779,6 +836,50 @@ __global__ __launch_bounds__(256) void rap_unstage_kernel(int nm, int cap, const
     if (m < nm && t < nbr_ptr[m + 1] - nbr_ptr[m]) nbr[nbr_ptr[m] + t] = stage[i];
 }
 
+// The walk of one row of A into its row of T by one thread of rap_numeric_kernel.
+// Four entries of the row at a time: their gather chains (column -> MIS word -> slot -> basis entry) are independent and
+// are all requested before the first product; the products are then added in the order of the entries, as a plain loop would.
+__device__ inline void rap_walk_row(roff_t qb, roff_t qe, const int *__restrict__ Acol, const double *__restrict__ Aval,
+                                    const rap_word_t *__restrict__ pack, const double *__restrict__ U, int nn,
+                                    const int *nbl, const long long *uo, const int *kk, const int *rr, const int *pos,
+                                    double *Trow) {
+    for (roff_t q0 = qb; q0 < qe; q0 += 4) {
+        int jj4[4], lo4[4], rim4[4];
+        double a4[4], u4[4];
+        bool on4[4];
+        rap_word_t w4[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const roff_t q = min(q0 + t, qe - 1);
+            jj4[t] = Acol[q];
+            a4[t] = Aval[q];
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) w4[t] = pack[jj4[t]];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int m = (int)(unsigned)w4[t];
+            rim4[t] = (int)((w4[t] >> 32) & 0x7fffffffu);
+            int lo = 0, hi = nn;      // (the neighbour list holds exactly the MISes with k > 0)
+            while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (nbl[mid] <= m) lo = mid; else hi = mid; }
+            lo4[t] = lo;
+            on4[t] = q0 + t < qe && nn != 0 && !(w4[t] & RAP_K0) && nbl[lo] == m;
+            u4[t] = on4[t] ? U[uo[lo] + rim4[t]] : 0.0;
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            if (!on4[t]) continue;
+            const int lo = lo4[t];
+            const int k2 = kk[lo];
+            const int r2 = rr[lo];
+            const double *U2 = U + uo[lo] + rim4[t];
+            double *dst = Trow + pos[lo];
+            dst[0] = fma(a4[t], u4[t], dst[0]);
+            for (int v = 1; v < k2; ++v) dst[v] = fma(a4[t], U2[(size_t)v * r2], dst[v]);
+        }
+    }
+}
+
 // NT threads per workgroup; list != nullptr: the workgroups take the MISes list[0 .. grid) instead of m_first + block.
 // (A workgroup costs tens of microseconds whatever its MIS holds -- a dozen rounds of dependent gathers and as many
 // barriers -- and a CU has room for eight workgroups of four wavefronts: the MISes of at most RAP_SMALL_ROWS dofs, seven
@@ -787,8 +888,8 @@ __global__ __launch_bounds__(256) void rap_unstage_kernel(int nm, int cap, const
 template <int NT>
 __global__ __launch_bounds__(NT) void rap_numeric_kernel(
     const int *__restrict__ list, int m_first, const int *__restrict__ mis2d_I, const int *__restrict__ mis2d_J, const roff_t *__restrict__ Arow,
-    const int *__restrict__ Acol, const double *__restrict__ Aval, const int *__restrict__ mises,
-    const int *__restrict__ row_in_mis, const int *__restrict__ k, const int *__restrict__ coloff,
+    const int *__restrict__ Acol, const double *__restrict__ Aval, const rap_word_t *__restrict__ pack,
+    const int *__restrict__ k, const int *__restrict__ coloff,
     const int64_t *__restrict__ u_off, const double *__restrict__ U,
     const int *__restrict__ nbr_ptr, const int *__restrict__ nbr, const roff_t *__restrict__ crowptr,
     int *__restrict__ ccol, double *__restrict__ cval, int lds_doubles) {
@@ -852,44 +953,7 @@ __global__ __launch_bounds__(NT) void rap_numeric_kernel(
             __syncthreads();
             for (int il = tid; il < rc; il += NT) {
                 const int g = dofs[c0 + il];
-                double *Trow = T + (size_t)il * ncol;
-                // four entries of the row at a time: their gather chains (column -> MIS -> slot -> row in the MIS ->
-                // basis entry) are independent and are all requested before the first product; the products are
-                // then added in the order of the entries, as a plain loop would
-                const roff_t qe = Arow[g + 1];
-                for (roff_t q0 = Arow[g]; q0 < qe; q0 += 4) {
-                    int jj4[4], lo4[4];
-                    double a4[4], u4[4];
-                    bool on4[4];
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        const roff_t q = min(q0 + t, qe - 1);
-                        jj4[t] = Acol[q];
-                        a4[t] = Aval[q];
-                    }
-                    int m4[4], rim4[4];
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) { m4[t] = mises[jj4[t]]; rim4[t] = row_in_mis[jj4[t]]; }
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        int lo = 0, hi = nn;      // (the neighbour list holds exactly the MISes with k > 0)
-                        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (nbl[mid] <= m4[t]) lo = mid; else hi = mid; }
-                        lo4[t] = lo;
-                        on4[t] = q0 + t < qe && nn != 0 && nbl[lo] == m4[t];
-                        u4[t] = on4[t] ? U[uo[lo] + rim4[t]] : 0.0;
-                    }
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        if (!on4[t]) continue;
-                        const int lo = lo4[t];
-                        const int k2 = kk[lo];
-                        const int r2 = rr[lo];
-                        const double *U2 = U + uo[lo] + rim4[t];
-                        double *dst = Trow + pos[lo];
-                        dst[0] = fma(a4[t], u4[t], dst[0]);
-                        for (int v = 1; v < k2; ++v) dst[v] = fma(a4[t], U2[(size_t)v * r2], dst[v]);
-                    }
-                }
+                rap_walk_row(Arow[g], Arow[g + 1], Acol, Aval, pack, U, nn, nbl, uo, kk, rr, pos, T + (size_t)il * ncol);
             }
             __syncthreads();
             for (int idx = tid; idx < kc * ncol; idx += NT) {
@@ -906,6 +970,114 @@ __global__ __launch_bounds__(NT) void rap_numeric_kernel(
             cval[crowptr[coloff[m1] + v0 + v1] + cc] = acc[idx];
         }
     }
+}
+
+// ---- sizes, row lengths and work lists of the product, on the device (the host reads back a few scalars) ----
+enum { RAP_SC_AGAIN = 0, RAP_SC_CNT_MAX, RAP_SC_NEED_MAX, RAP_SC_SMALL_MAX, RAP_SC_SMALL_LDS, RAP_NSC };
+
+// symbolic lists: fa = MISes of at most RAP_SMALL_ROWS dofs, fb = the others
+__global__ __launch_bounds__(256) void rap_sym_class_kernel(int nm, const int *__restrict__ mis2d_I, int *__restrict__ fa,
+                                                            int *__restrict__ fb) {
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    if (m >= nm) return;
+    const int small = mis2d_I[m + 1] - mis2d_I[m] <= RAP_SMALL_ROWS;
+    fa[m] = small;
+    fb[m] = !small;
+}
+
+// how many MISes the small tables could not hold (cnt = -1; flagged in fa) and the longest neighbour list
+__global__ __launch_bounds__(256) void rap_cnt_stats_kernel(int nm, const int *__restrict__ cnt, int *__restrict__ fa,
+                                                            unsigned long long *__restrict__ sc) {
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    const int c = m < nm ? cnt[m] : 0;
+    int neg = c < 0, mx = max(c, 0);
+    if (m < nm) fa[m] = neg;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        neg += __shfl_xor(neg, o, 64);
+        mx = max(mx, __shfl_xor(mx, o, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (neg) atomicAdd(&sc[RAP_SC_AGAIN], (unsigned long long)neg);
+        if (mx) atomicMax(&sc[RAP_SC_CNT_MAX], (unsigned long long)mx);
+    }
+}
+
+// Per MIS with k > 0: the length ncol of its k rows of Ac (the k of its neighbours, summed) and the doubles of LDS it wants.
+//   need: tables + all k rows of the block + 1 row of T if that fits `cap`, else 2 rows (multi-pass);
+//   small_need, in a one-wavefront workgroup: tables + its k output rows + all its rows of T, but no more than 8 KB unless
+//   k + 8 rows need it (the kernel walks the MIS's rows in chunks of what fits).
+__global__ __launch_bounds__(256) void rap_size_kernel(int nm, const int *__restrict__ k, const int *__restrict__ coloff,
+                                                       const int *__restrict__ mis2d_I, const int *__restrict__ nbr_ptr,
+                                                       const int *__restrict__ nbr, unsigned long long cap,
+                                                       int *__restrict__ rowlen, int *__restrict__ small_need,
+                                                       unsigned long long *__restrict__ sc) {
+    typedef unsigned long long u64;
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    u64 need = 0, small = 0;
+    if (m < nm) {
+        const int km = k[m];
+        int sn = 0;
+        if (km > 0) {
+            const int t0 = nbr_ptr[m], t1 = nbr_ptr[m + 1];
+            int ncol = 0;
+            for (int t = t0; t < t1; ++t) ncol += k[nbr[t]];
+            for (int v = 0; v < km; ++v) rowlen[coloff[m] + v] = ncol;
+            const u64 tables = (u64)(3 * (t1 - t0) + 2);
+            need = tables + (u64)(km + 1) * ncol;
+            if (need > cap) need = max(tables + 2ull * ncol, min(need, cap));
+            small = tables + (u64)(km + 8) * ncol;
+            const u64 all = tables + (u64)(km + (mis2d_I[m + 1] - mis2d_I[m])) * ncol;
+            sn = (int)min(min(all, max((u64)1024, small)), (u64)(1u << 30));
+        }
+        small_need[m] = sn;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        need = max(need, (u64)__shfl_xor((long long)need, o, 64));
+        small = max(small, (u64)__shfl_xor((long long)small, o, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (need) atomicMax(&sc[RAP_SC_NEED_MAX], need);
+        if (small) atomicMax(&sc[RAP_SC_SMALL_MAX], small);
+    }
+}
+
+// numeric lists of the MISes [m_lo, m_hi) with k > 0: fa = few dofs and little LDS (one wavefront per MIS; the LDS those need
+// goes to sc), fb = the others
+__global__ __launch_bounds__(256) void rap_num_class_kernel(int nm, int m_lo, int m_hi, const int *__restrict__ k,
+                                                            const int *__restrict__ mis2d_I, const int *__restrict__ small_need,
+                                                            int *__restrict__ fa, int *__restrict__ fb,
+                                                            unsigned long long *__restrict__ sc) {
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    int lds = 0;
+    if (m < nm) {
+        const bool on = m >= m_lo && m < m_hi && k[m] > 0;
+        const bool small = on && mis2d_I[m + 1] - mis2d_I[m] <= RAP_SMALL_ROWS && small_need[m] <= 2048;
+        fa[m] = small;
+        fb[m] = on && !small;
+        if (small) lds = small_need[m];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) lds = max(lds, __shfl_xor(lds, o, 64));
+    if ((threadIdx.x & 63) == 0 && lds) atomicMax(&sc[RAP_SC_SMALL_LDS], (unsigned long long)lds);
+}
+
+__global__ __launch_bounds__(256) void rap_scatter_kernel(int nm, const int *__restrict__ flag, const int *__restrict__ pos,
+                                                          int *__restrict__ list) {
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    if (m < nm && flag[m]) list[pos[m]] = m;
+}
+
+// list = the m < nm with flag[m] != 0, ascending; pos: scratch of nm + 1 ints.  Returns their number.
+static int rap_compact(hipStream_t s, int nm, const int *flag, int *pos, DBuf<int> &list) {
+    exclusive_scan_int(s, nm, flag, pos);
+    int n = 0;
+    SA_HIP_CHECK(hipMemcpyAsync(&n, pos + nm, sizeof(int), hipMemcpyDeviceToHost, s));
+    SA_HIP_CHECK(hipStreamSynchronize(s));
+    list.alloc((size_t)n);
+    if (n) hipLaunchKernelGGL(rap_scatter_kernel, dim3(div_up(nm, 256)), dim3(256), 0, s, nm, flag, (const int *)pos, list.p);
+    return n;
 }
 
 void rap_mis(hipStream_t s, const DevRelations &rel, const Relations &hrel, const DCsr &A,
@@ -925,84 +1097,72 @@ void rap_mis(hipStream_t s, const DevRelations &rel, const Relations &hrel, cons
     err.zero(s);
     if (A.max_row < 0) A.max_row = csr_max_row(s, A);
     const int maxrow = A.max_row;
+    SA_REQUIRE(maxrow <= RAP_ROW_CLAMP, "RAP: a row of A is too long");
     profiler().begin(s);
+    DBuf<rap_word_t> pack((size_t)A.nrows);
+    hipLaunchKernelGGL(rap_pack_kernel, dim3(div_up(A.nrows, 256)), dim3(256), 0, s, A.nrows, rel.mises.p, rel.dof_row_in_mis.p, d_k, pack.p);
     constexpr int STAGE_CAP = 64;
     DBuf<int> stage((size_t)nm * STAGE_CAP);
+    DBuf<int> fa((size_t)nm), fb((size_t)nm), pos((size_t)nm + 1);      // flags and scratch of the list compactions
+    DBuf<unsigned long long> sc(RAP_NSC);
+    const dim3 gm(div_up(nm, 256));
     {   // (two lists by the number of dofs, as for the numeric kernel below)
-        std::vector<int> sym_small, sym_big;
-        for (int m = 0; m < nm; ++m) (hrel.mis_to_dof.row_size(m) <= RAP_SMALL_ROWS ? sym_small : sym_big).push_back(m);
+        hipLaunchKernelGGL(rap_sym_class_kernel, gm, dim3(256), 0, s, nm, rel.mis2d_I.p, fa.p, fb.p);
         DBuf<int> d_sym_small, d_sym_big;
-        d_sym_small.from_host(sym_small, s);
-        d_sym_big.from_host(sym_big, s);
-        if (!sym_big.empty())
-            hipLaunchKernelGGL((rap_symbolic_kernel<RAP_NT, RAP_HASH>), dim3((unsigned)sym_big.size()), dim3(RAP_NT), 0, s, d_sym_big.p, 0,
-                               rel.mis2d_I.p, rel.mis2d_J.p, A.rowptr.p, A.col.p, rel.mises.p, d_k, cnt.p, nullptr, nullptr, err.p, stage.p,
+        const int n_small = rap_compact(s, nm, fa.p, pos.p, d_sym_small), n_big = rap_compact(s, nm, fb.p, pos.p, d_sym_big);
+        if (n_big)
+            hipLaunchKernelGGL((rap_symbolic_kernel<RAP_NT, RAP_HASH>), dim3((unsigned)n_big), dim3(RAP_NT), 0, s, d_sym_big.p, 0,
+                               rel.mis2d_I.p, rel.mis2d_J.p, A.rowptr.p, A.col.p, pack.p, d_k, cnt.p, nullptr, nullptr, err.p, stage.p,
                                STAGE_CAP, maxrow);
-        if (!sym_small.empty())
-            hipLaunchKernelGGL((rap_symbolic_kernel<64, 256>), dim3((unsigned)sym_small.size()), dim3(64), 0, s, d_sym_small.p, 0,
-                               rel.mis2d_I.p, rel.mis2d_J.p, A.rowptr.p, A.col.p, rel.mises.p, d_k, cnt.p, nullptr, nullptr, err.p, stage.p,
+        if (n_small)
+            hipLaunchKernelGGL((rap_symbolic_kernel<64, 256>), dim3((unsigned)n_small), dim3(64), 0, s, d_sym_small.p, 0,
+                               rel.mis2d_I.p, rel.mis2d_J.p, A.rowptr.p, A.col.p, pack.p, d_k, cnt.p, nullptr, nullptr, err.p, stage.p,
                                STAGE_CAP, maxrow);
         SA_HIP_CHECK(hipGetLastError());
         SA_HIP_CHECK(hipStreamSynchronize(s));      // (the lists are freed here)
     }
-    auto h_cnt = cnt.to_host(s);
-    {   // small MISes whose neighbours did not fit the small tables: once more, full size
-        std::vector<int> again;
-        for (int m = 0; m < nm; ++m)
-            if (h_cnt[m] < 0) again.push_back(m);
-        if (!again.empty()) {
-            DBuf<int> d_again;
-            d_again.from_host(again, s);
-            hipLaunchKernelGGL((rap_symbolic_kernel<RAP_NT, RAP_HASH>), dim3((unsigned)again.size()), dim3(RAP_NT), 0, s, d_again.p, 0,
-                               rel.mis2d_I.p, rel.mis2d_J.p, A.rowptr.p, A.col.p, rel.mises.p, d_k, cnt.p, nullptr, nullptr, err.p, stage.p,
-                               STAGE_CAP, maxrow);
-            SA_HIP_CHECK(hipGetLastError());
-            h_cnt = cnt.to_host(s);
-        }
+    sc.zero(s);
+    hipLaunchKernelGGL(rap_cnt_stats_kernel, gm, dim3(256), 0, s, nm, cnt.p, fa.p, sc.p);
+    SA_HIP_CHECK(hipGetLastError());
+    auto h_sc = sc.to_host(s);
+    if (h_sc[RAP_SC_AGAIN]) {   // small MISes whose neighbours did not fit the small tables: once more, full size
+        DBuf<int> d_again;
+        const int n_again = rap_compact(s, nm, fa.p, pos.p, d_again);
+        hipLaunchKernelGGL((rap_symbolic_kernel<RAP_NT, RAP_HASH>), dim3((unsigned)n_again), dim3(RAP_NT), 0, s, d_again.p, 0,
+                           rel.mis2d_I.p, rel.mis2d_J.p, A.rowptr.p, A.col.p, pack.p, d_k, cnt.p, nullptr, nullptr, err.p, stage.p,
+                           STAGE_CAP, maxrow);
+        sc.zero(s);
+        hipLaunchKernelGGL(rap_cnt_stats_kernel, gm, dim3(256), 0, s, nm, cnt.p, fa.p, sc.p);
+        SA_HIP_CHECK(hipGetLastError());
+        h_sc = sc.to_host(s);      // (d_again is freed after this)
     }
-    SA_REQUIRE(err.to_host(s)[0] == 0, "RAP: MIS neighbour table overflow");
-    std::vector<int> h_nbr_ptr((size_t)nm + 1, 0);
-    int cnt_max = 0;
-    for (int m = 0; m < nm; ++m) { h_nbr_ptr[m + 1] = h_nbr_ptr[m] + h_cnt[m]; cnt_max = std::max(cnt_max, (int)h_cnt[m]); }
-    DBuf<int> nbr_ptr, nbr((size_t)h_nbr_ptr[nm] + 1);
-    nbr_ptr.from_host(h_nbr_ptr, s);
+    SA_REQUIRE(err.to_host(s)[0] == 0 && h_sc[RAP_SC_AGAIN] == 0, "RAP: MIS neighbour table overflow");
+    const int cnt_max = (int)h_sc[RAP_SC_CNT_MAX];
+    DBuf<int> nbr_ptr((size_t)nm + 1);
+    exclusive_scan_int(s, nm, cnt.p, nbr_ptr.p);
+    int nbr_total = 0;
+    SA_HIP_CHECK(hipMemcpyAsync(&nbr_total, nbr_ptr.p + nm, sizeof(int), hipMemcpyDeviceToHost, s));
+    SA_HIP_CHECK(hipStreamSynchronize(s));
+    DBuf<int> nbr((size_t)nbr_total + 1);
     if (cnt_max <= STAGE_CAP)      // every list was staged by the counting pass
         hipLaunchKernelGGL(rap_unstage_kernel, dim3(div_up((long)nm * STAGE_CAP, 256)), dim3(256), 0, s, nm, STAGE_CAP, stage.p,
                            nbr_ptr.p, nbr.p);
     else
         hipLaunchKernelGGL((rap_symbolic_kernel<RAP_NT, RAP_HASH>), dim3(nm), dim3(RAP_NT), 0, s, (const int *)nullptr, 1, rel.mis2d_I.p,
-                           rel.mis2d_J.p, A.rowptr.p, A.col.p, rel.mises.p, d_k, cnt.p, nbr_ptr.p, nbr.p, err.p, (int *)nullptr, 0,
+                           rel.mis2d_J.p, A.rowptr.p, A.col.p, pack.p, d_k, cnt.p, nbr_ptr.p, nbr.p, err.p, (int *)nullptr, 0,
                            maxrow);
-    SA_HIP_CHECK(hipGetLastError());
-    auto h_nbr = nbr.to_host(s);
     // row pointers of Ac and LDS sizing
-    std::vector<roff_t> crow((size_t)nc + 1, 0);
-    int64_t nnz = 0;
-    size_t need_max = 0, small_max = 0;
-    // doubles of LDS a MIS wants in a one-wavefront workgroup: tables + its k output rows + all its rows of T, but no more than
-    // 8 KB unless k + 8 rows need it (the kernel walks the MIS's rows in chunks of what fits)
-    std::vector<int> small_need((size_t)nm, 0);
-    for (int m = 0; m < nm; ++m) {
-        if (h_k[m] == 0) continue;
-        int ncol = 0;
-        for (int t = h_nbr_ptr[m]; t < h_nbr_ptr[m + 1]; ++t) ncol += h_k[h_nbr[t]];
-        for (int v = 0; v < h_k[m]; ++v) {
-            crow[(size_t)h_coloff[m] + v + 1] = ncol;
-            nnz += ncol;
-        }
-        // all k rows of the block + 1 row of T if that fits 160 KiB, else 2 rows (multi-pass)
-        size_t need = (size_t)(3 * h_cnt[m] + 2) + (size_t)(h_k[m] + 1) * ncol;
-        const size_t cap = 160 * 1024 / 8;
-        if (need > cap) need = std::max((size_t)(3 * h_cnt[m] + 2) + 2 * (size_t)ncol, std::min(need, cap));
-        if (need > need_max) need_max = need;
-        small_max = std::max(small_max, (size_t)(3 * h_cnt[m] + 2) + (size_t)(h_k[m] + 8) * ncol);
-        {
-            const size_t tables = (size_t)(3 * h_cnt[m] + 2);
-            const size_t all = tables + (size_t)(h_k[m] + hrel.mis_to_dof.row_size(m)) * ncol, floor8 = tables + (size_t)(h_k[m] + 8) * ncol;
-            small_need[m] = (int)std::min<size_t>(std::min(all, std::max((size_t)1024, floor8)), 1u << 30);
-        }
-    }
-    for (int i = 0; i < nc; ++i) crow[i + 1] += crow[i];
+    DBuf<int> rowlen((size_t)nc), small_need((size_t)nm);
+    sc.zero(s);
+    hipLaunchKernelGGL(rap_size_kernel, gm, dim3(256), 0, s, nm, d_k, d_coloff, rel.mis2d_I.p, nbr_ptr.p, nbr.p,
+                       (unsigned long long)(160 * 1024 / 8), rowlen.p, small_need.p, sc.p);
+    SA_HIP_CHECK(hipGetLastError());
+    Ac.rowptr.alloc((size_t)nc + 1);
+    exclusive_scan_off(s, nc, rowlen.p, Ac.rowptr.p);
+    roff_t nnz = 0;
+    SA_HIP_CHECK(hipMemcpyAsync(&nnz, Ac.rowptr.p + nc, sizeof(roff_t), hipMemcpyDeviceToHost, s));
+    h_sc = sc.to_host(s);
+    const size_t need_max = (size_t)h_sc[RAP_SC_NEED_MAX], small_max = (size_t)h_sc[RAP_SC_SMALL_MAX];
     // Blocks that fit 64 KiB in one pass get by with the k output rows + >= 8 rows of T per chunk of
     // MIS rows (16 KiB floor): the kernel is bound by the latency of its dependent gathers, and
     // the smaller footprint puts 8 workgroups instead of 2 on a CU.  Wider blocks keep what they need.
@@ -1012,13 +1172,13 @@ void rap_mis(hipStream_t s, const DevRelations &rel, const Relations &hrel, cons
     SA_HIP_CHECK(hipFuncSetAttribute((const void *)rap_numeric_kernel<RAP_NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     SA_HIP_CHECK(hipFuncSetAttribute((const void *)rap_numeric_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     Ac.nnz = nnz;
-    Ac.rowptr.from_host(crow, s);
     Ac.col.alloc((size_t)nnz);
     Ac.val.alloc((size_t)nnz);
     // Several ranks: the MIS row blocks are split into `world` contiguous ranges balanced by their
     // non-zeros; a rank computes its range only, the caller all-gathers col / val by nnz_off.
     int m_lo = 0, m_hi = nm;
     if (world > 1 && nnz_off) {
+        const auto crow = Ac.rowptr.to_host(s);
         std::vector<int> mb((size_t)world + 1, nm);
         mb[0] = 0;
         int r = 0;
@@ -1033,28 +1193,20 @@ void rap_mis(hipStream_t s, const DevRelations &rel, const Relations &hrel, cons
         m_hi = mb[rank + 1];
     }
     // the MISes of this rank's range in two lists: few dofs (one wavefront per MIS, the LDS those need), the others
-    std::vector<int> small_list, big_list;
-    size_t small_lds = 0;
-    for (int m = m_lo; m < m_hi; ++m) {
-        if (h_k[m] == 0) continue;
-        if (hrel.mis_to_dof.row_size(m) <= RAP_SMALL_ROWS && small_need[m] <= 2048) {
-            small_list.push_back(m);
-            small_lds = std::max(small_lds, (size_t)small_need[m]);
-        } else big_list.push_back(m);
-    }
+    hipLaunchKernelGGL(rap_num_class_kernel, gm, dim3(256), 0, s, nm, m_lo, m_hi, d_k, rel.mis2d_I.p, small_need.p, fa.p, fb.p, sc.p);
     DBuf<int> d_small, d_big;
-    d_small.from_host(small_list, s);
-    d_big.from_host(big_list, s);
-    if (!big_list.empty())
-        hipLaunchKernelGGL(rap_numeric_kernel<RAP_NT>, dim3((unsigned)big_list.size()), dim3(RAP_NT), lds_doubles * 8, s, d_big.p, 0,
-                           rel.mis2d_I.p, rel.mis2d_J.p, A.rowptr.p, A.col.p, A.val.p, rel.mises.p,
-                           rel.dof_row_in_mis.p, d_k, d_coloff, d_u_off, U, nbr_ptr.p, nbr.p, Ac.rowptr.p,
+    const int n_small = rap_compact(s, nm, fa.p, pos.p, d_small), n_big = rap_compact(s, nm, fb.p, pos.p, d_big);
+    const size_t small_lds = (size_t)sc.to_host(s)[RAP_SC_SMALL_LDS];
+    if (n_big)
+        hipLaunchKernelGGL(rap_numeric_kernel<RAP_NT>, dim3((unsigned)n_big), dim3(RAP_NT), lds_doubles * 8, s,
+                           d_big.p, 0, rel.mis2d_I.p, rel.mis2d_J.p, A.rowptr.p, A.col.p, A.val.p, pack.p,
+                           d_k, d_coloff, d_u_off, U, nbr_ptr.p, nbr.p, Ac.rowptr.p,
                            Ac.col.p, Ac.val.p, (int)lds_doubles);
-    if (!small_list.empty()) {
+    if (n_small) {
         const size_t sl = std::max((size_t)256, small_lds);
-        hipLaunchKernelGGL(rap_numeric_kernel<64>, dim3((unsigned)small_list.size()), dim3(64), sl * 8, s, d_small.p, 0,
-                           rel.mis2d_I.p, rel.mis2d_J.p, A.rowptr.p, A.col.p, A.val.p, rel.mises.p,
-                           rel.dof_row_in_mis.p, d_k, d_coloff, d_u_off, U, nbr_ptr.p, nbr.p, Ac.rowptr.p,
+        hipLaunchKernelGGL(rap_numeric_kernel<64>, dim3((unsigned)n_small), dim3(64), sl * 8, s,
+                           d_small.p, 0, rel.mis2d_I.p, rel.mis2d_J.p, A.rowptr.p, A.col.p, A.val.p, pack.p,
+                           d_k, d_coloff, d_u_off, U, nbr_ptr.p, nbr.p, Ac.rowptr.p,
                            Ac.col.p, Ac.val.p, (int)sl);
     }
     SA_HIP_CHECK(hipGetLastError());
