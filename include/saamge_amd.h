@@ -475,6 +475,31 @@ int saamge_amd_partition_mesh(int NE, int nde, const int *elem_ptr, const int *e
 int saamge_amd_partition_mesh_v2(int NE, int nde, const int *elem_ptr, const int *elem_to_dof, int ND, int num_coarsenings,
                                  const int *elems_per_agg, const saamge_amd_partition_options_v2 *o, void *stream,
                                  saamge_amd_partitioning **out);
+
+/* Boundary refinement, off unless asked for: rounds in which nodes on a part's boundary move to the neighbouring part that
+ * holds most of their neighbours, which lowers the edge cut and smooths the parts (partition_model.py, "refine"; DESIGN.md
+ * section 4.5).  Parts stay connected, none is emptied, none grows beyond max_size (0: no cap) or shrinks below
+ * max(min_size, 1) through the pass, and the part count stays.  Deterministic; `seed` orders equal gains as it does elsewhere.
+ *
+ * saamge_amd_partition_refine works on any partition of a symmetric CSR graph, the caller's own included: part (n labels in
+ * [0, nparts), no part empty; host or device pointer, like xadj and adj each on its own) is read and written in place.
+ * renumber = 1 numbers the parts by their smallest member afterwards, 0 keeps the caller's labels.  At most `rounds` rounds
+ * move nodes.  info (may be NULL): [0] = rounds that moved nodes, [1] = nodes moved, [2] = the sum of their gains = cut edges
+ * removed, [3] = 1 if the pass stopped because no node could move, else 0.  Refused before part is written: a malformed graph
+ * (as saamge_amd_partition_graph), a label outside [0, nparts), an empty part, negative rounds / max_size / min_size, renumber
+ * outside {0, 1}.  max_size and min_size are taken as given (no -1 defaults here). */
+int saamge_amd_partition_refine(int n, const long long *xadj, const int *adj, int nparts, int *part, int rounds, int max_size,
+                                int min_size, unsigned seed, int renumber, void *stream, long long info[4]);
+/* saamge_amd_partition_mesh_v2 with the pass after each level's partition: refine_rounds[k] rounds at coarsening k, with that
+ * level's caps (the defaults resolved) and seed from o; the parts are numbered again and the next graph is the quotient graph
+ * of the refined parts.  refine_rounds == NULL or all zeros: saamge_amd_partition_mesh_v2, bit for bit. */
+int saamge_amd_partition_mesh_refined(int NE, int nde, const int *elem_ptr, const int *elem_to_dof, int ND, int num_coarsenings,
+                                      const int *elems_per_agg, const saamge_amd_partition_options_v2 *o, const int *refine_rounds,
+                                      void *stream, saamge_amd_partitioning **out);
+/* info as above for the calling thread's last refinement (saamge_amd_partition_refine, or the last refined level of
+ * saamge_amd_partition_mesh_refined). */
+void saamge_amd_partition_refine_info(long long info[4]);
+
 /* Pointers that can be handed to saamge_amd_ml_produce_data* as partitions / nparts; they live as long as the handle.
  * on_host = 0: device arrays, 1: host copies. */
 int saamge_amd_partitioning_arrays(const saamge_amd_partitioning *p, int on_host, const int *const **partitions,

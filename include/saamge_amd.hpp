@@ -229,6 +229,34 @@ inline MeshPartitions partition_mesh_v2(int NE, int nde, const int *elem_ptr, co
         throw std::runtime_error(saamge_amd_last_error());
     return detail::take_partitions(P, (int)elems_per_agg.size());
 }
+// The boundary refinement pass (saamge_amd_partition_refine) on any partition of a symmetric CSR graph: part (n labels in
+// [0, nparts), host) is refined in place; max_size 0: no cap.  Returns info = {rounds that moved nodes, nodes moved, cut edges
+// removed, 1 if no node could move any more}.
+struct RefineInfo {
+    long long rounds, moved, gain, converged;
+};
+inline RefineInfo partition_refine(int n, const long long *xadj, const int *adj, int nparts, std::vector<int> &part, int rounds,
+                                   int max_size = 0, int min_size = 0, unsigned seed = 0, bool renumber = false,
+                                   void *stream = nullptr) {
+    if (part.size() != (size_t)(n > 0 ? n : 0)) throw std::invalid_argument("partition_refine: part must hold n labels");
+    long long info[4] = {0, 0, 0, 0};
+    if (saamge_amd_partition_refine(n, xadj, adj, nparts, part.data(), rounds, max_size, min_size, seed, renumber ? 1 : 0, stream, info))
+        throw std::runtime_error(saamge_amd_last_error());
+    const RefineInfo r = {info[0], info[1], info[2], info[3]};
+    return r;
+}
+// partition_mesh_v2 with refine_rounds[k] rounds of the pass after the partition of coarsening k (empty: none)
+inline MeshPartitions partition_mesh_refined(int NE, int nde, const int *elem_ptr, const int *elem_to_dof, int ND,
+                                             const std::vector<int> &elems_per_agg, const std::vector<int> &refine_rounds,
+                                             const saamge_amd_partition_options_v2 *o = nullptr, void *stream = nullptr) {
+    if (!refine_rounds.empty() && refine_rounds.size() != elems_per_agg.size())
+        throw std::invalid_argument("partition_mesh_refined: one refine_rounds entry per coarsening");
+    saamge_amd_partitioning *P = nullptr;
+    if (saamge_amd_partition_mesh_refined(NE, nde, elem_ptr, elem_to_dof, ND, (int)elems_per_agg.size(), elems_per_agg.data(), o,
+                                          refine_rounds.empty() ? nullptr : refine_rounds.data(), stream, &P))
+        throw std::runtime_error(saamge_amd_last_error());
+    return detail::take_partitions(P, (int)elems_per_agg.size());
+}
 
 // == the operator assembled on the device (saamge_amd_operator_assemble) ==
 // Owner of the handle.  rowptr() / col() / val() are device arrays that live as long as this object: hand them to

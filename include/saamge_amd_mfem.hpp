@@ -242,9 +242,12 @@ inline void ml_set_fine_partitioner(const ml_partitioner_t &p) { ml_fine_partiti
 // of agglomerates of that level from max(partition) + 1 instead of MultilevelParameters::get_nparts.  `options` keeps its
 // type; `growth` (saamge_amd_partition_options_v2's last field) stands beside it and is 0 unless the hook was made by
 // ml_device_partitioner_v2, which has a name of its own so that ml_device_partitioner(nullptr) still means the defaults.
+// `refine_rounds` (0: off) is set on the hook itself: that many rounds of saamge_amd_partition_refine follow the partition,
+// with the caps the partition was made with, and the parts are numbered again.
 struct ml_device_partitioner_t {
     saamge_amd_partition_options options;
     int growth = 0;
+    int refine_rounds = 0;
     void operator()(int, int n_elem, int nparts, const mfem::Table &elem_to_elem, int *partition) const {
         if (n_elem <= 0) return;
         const int target = nparts < 1 ? 1 : nparts;
@@ -259,6 +262,13 @@ struct ml_device_partitioner_t {
         if (saamge_amd_partition_graph_v2(n_elem, xadj.data(), has_graph ? elem_to_elem.GetJ() : nullptr, epa, &o, nullptr,
                                           partition, &produced))
             mfem::mfem_error(saamge_amd_last_error());
+        if (refine_rounds > 0) {
+            const int max_size = o.max_size < 0 ? (2ll * epa < 2147483647ll ? 2 * epa : 2147483647) : o.max_size;
+            const int min_size = o.min_size < 0 ? epa / 4 : o.min_size;
+            if (saamge_amd_partition_refine(n_elem, xadj.data(), has_graph ? elem_to_elem.GetJ() : nullptr, produced, partition,
+                                            refine_rounds, max_size, min_size, o.seed, 1, nullptr, nullptr))
+                mfem::mfem_error(saamge_amd_last_error());
+        }
     }
 };
 inline ml_device_partitioner_t ml_device_partitioner(const saamge_amd_partition_options *options = nullptr) {

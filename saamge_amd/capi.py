@@ -32,6 +32,7 @@ SYMBOLS = [
     "saamge_amd_ml_produce_data_mixed", "saamge_amd_ml_produce_data_mixed64",
     "saamge_amd_partition_options_default", "saamge_amd_partition_seeding_info", "saamge_amd_partition_growth_info", "saamge_amd_partition_options_v2_default",
     "saamge_amd_partition_graph_v2", "saamge_amd_partition_mesh_v2", "saamge_amd_partition_graph", "saamge_amd_partition_mesh",
+    "saamge_amd_partition_refine", "saamge_amd_partition_mesh_refined", "saamge_amd_partition_refine_info",
     "saamge_amd_partitioning_arrays", "saamge_amd_partitioning_get", "saamge_amd_partitioning_graph",
     "saamge_amd_partitioning_free", "saamge_amd_coarse_solver_info",
     "saamge_amd_spgemm", "saamge_amd_csr_transpose", "saamge_amd_csr_threshold",
@@ -789,12 +790,36 @@ def partition_growth_info():
     return dict(rounds=int(info[0]), quota_nodes=int(info[1]), open_parts=int(info[2]), released_nodes=int(info[3]))
 
 
+def partition_refine(n, xadj, adj, nparts, part, rounds, max_size=0, min_size=0, seed=0, renumber=False, stream=0):
+    """saamge_amd_partition_refine: the boundary refinement pass on any partition, in place.  part: a numpy int32 array or a
+    device tensor of n int32.  Returns (part, info) with info = dict(rounds, moved, gain, converged)."""
+    info = (C.c_longlong * 4)()
+    _check(load().saamge_amd_partition_refine(C.c_int(int(n)), _ptr(xadj), _ptr(adj), C.c_int(int(nparts)), _ptr(part),
+                                              C.c_int(int(rounds)), C.c_int(int(max_size)), C.c_int(int(min_size)),
+                                              C.c_uint(int(seed)), C.c_int(int(renumber)), C.c_void_p(stream), info))
+    return part, dict(rounds=int(info[0]), moved=int(info[1]), gain=int(info[2]), converged=int(info[3]))
+
+
+def partition_refine_info():
+    """saamge_amd_partition_refine_info: what this thread's last refinement pass did."""
+    info = (C.c_longlong * 4)()
+    fn = load().saamge_amd_partition_refine_info
+    fn.restype = None
+    fn(info)
+    return dict(rounds=int(info[0]), moved=int(info[1]), gain=int(info[2]), converged=int(info[3]))
+
+
 class Partitioning(object):
     """saamge_amd_partition_mesh: the partitions of every coarsening, owned by the library until close().  Keywords beyond
     the named ones are the fields of PartitionOptions (seeding=1: spaced seeds) or, with `growth` among them (1: balanced
-    growth), of PartitionOptionsV2 (saamge_amd_partition_mesh_v2)."""
+    growth), of PartitionOptionsV2 (saamge_amd_partition_mesh_v2).  refine_rounds: one count per coarsening, the boundary
+    refinement of saamge_amd_partition_mesh_refined (None: the entry points without it)."""
 
-    def __init__(self, elem_to_dof, ND, elems_per_agg, elem_ptr=None, nde=0, NE=None, stream=0, **opts):
+    def __init__(self, elem_to_dof, ND, elems_per_agg, elem_ptr=None, nde=0, NE=None, stream=0, refine_rounds=None, **opts):
+        if refine_rounds is not None:
+            if len(refine_rounds) != len(elems_per_agg):
+                raise ValueError("refine_rounds: one entry per coarsening")
+            opts.setdefault("growth", 0)      # the refined entry point takes the v2 options
         o = partition_options(**opts)
         if NE is None:
             NE = len(elem_ptr) - 1 if elem_ptr is not None else int(elem_to_dof.shape[0])
@@ -802,9 +827,15 @@ class Partitioning(object):
             nde = int(elem_to_dof.shape[1])
         epa = (C.c_int * len(elems_per_agg))(*[int(x) for x in elems_per_agg])
         h = C.c_void_p()
-        _check(_v2(o, "saamge_amd_partition_mesh")(C.c_int(int(NE)), C.c_int(int(nde)), _ptr(elem_ptr), _ptr(elem_to_dof),
-                                                   C.c_int(int(ND)), C.c_int(len(elems_per_agg)), epa, C.byref(o),
-                                                   C.c_void_p(stream), C.byref(h)))
+        if refine_rounds is not None:
+            rr = (C.c_int * len(refine_rounds))(*[int(x) for x in refine_rounds])
+            _check(load().saamge_amd_partition_mesh_refined(C.c_int(int(NE)), C.c_int(int(nde)), _ptr(elem_ptr), _ptr(elem_to_dof),
+                                                            C.c_int(int(ND)), C.c_int(len(elems_per_agg)), epa, C.byref(o), rr,
+                                                            C.c_void_p(stream), C.byref(h)))
+        else:
+            _check(_v2(o, "saamge_amd_partition_mesh")(C.c_int(int(NE)), C.c_int(int(nde)), _ptr(elem_ptr), _ptr(elem_to_dof),
+                                                       C.c_int(int(ND)), C.c_int(len(elems_per_agg)), epa, C.byref(o),
+                                                       C.c_void_p(stream), C.byref(h)))
         self.h = h
         self.num_coarsenings = len(elems_per_agg)
         self.nparts, self.n_elem = [], []

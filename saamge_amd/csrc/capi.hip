@@ -890,6 +890,27 @@ void saamge_amd_partition_growth_info(long long info[4]) {
     info[0] = st.rounds; info[1] = st.quota_nodes; info[2] = st.open_parts; info[3] = st.released_nodes;
 }
 
+// a caller's graph on the device, checked: host columns need host offsets, which are checked before they say how much to copy
+static void import_graph(hipStream_t s, int n, const long long *xadj, const int *adj, DBuf<roff_t> &dx, DBuf<int> &da) {
+    import_array(dx, (const roff_t *)xadj, (size_t)n + 1, s);
+    if (!is_device_ptr(adj)) {
+        const bool xh = !is_device_ptr(xadj);
+        if (xh) for (int i = 0; i < n; ++i) SA_REQUIRE(xadj[0] == 0 && xadj[i + 1] >= xadj[i], "xadj: must start at 0 and ascend");
+        const roff_t nnz = n == 0 ? 0 : (xh ? (roff_t)xadj[n] : 0);
+        SA_REQUIRE(xh || n == 0, "xadj on the device with adj on the host");
+        SA_REQUIRE(nnz == 0 || adj, "null argument: adj");
+        da.assign(adj, (size_t)nnz, s);
+    } else {
+        da.view(const_cast<int *>(adj), 0);
+    }
+    check_graph_device(s, n, dx.p, da.p);
+}
+
+void saamge_amd_partition_refine_info(long long info[4]) {
+    const RefineStats st = last_refine_stats();
+    info[0] = st.rounds; info[1] = st.moved; info[2] = st.gain; info[3] = st.converged;
+}
+
 int saamge_amd_partition_graph(int n, const long long *xadj, const int *adj, int elems_per_agg,
                                const saamge_amd_partition_options *o, void *stream, int *part, int *nparts_out) {
     const PartitionOptionsV1 v1(o);
@@ -908,23 +929,45 @@ int saamge_amd_partition_graph_v2(int n, const long long *xadj, const int *adj, 
     {
         DBuf<roff_t> dx;
         DBuf<int> da, dp;
-        import_array(dx, (const roff_t *)xadj, (size_t)n + 1, s);
-        if (!is_device_ptr(adj)) {      // host columns: the offsets are checked before they say how much to copy
-            const bool xh = !is_device_ptr(xadj);
-            if (xh) for (int i = 0; i < n; ++i) SA_REQUIRE(xadj[0] == 0 && xadj[i + 1] >= xadj[i], "xadj: must start at 0 and ascend");
-            const roff_t nnz = n == 0 ? 0 : (xh ? (roff_t)xadj[n] : 0);
-            SA_REQUIRE(xh || n == 0, "xadj on the device with adj on the host");
-            SA_REQUIRE(nnz == 0 || adj, "null argument: adj");
-            da.assign(adj, (size_t)nnz, s);
-        } else {
-            da.view(const_cast<int *>(adj), 0);
-        }
-        check_graph_device(s, n, dx.p, da.p);
+        import_graph(s, n, xadj, adj, dx, da);
         if (is_device_ptr(part)) dp.view(part, (size_t)n);
         else dp.alloc((size_t)n);
         partition_graph_device(s, n, dx.p, da.p, elems_per_agg, po, dp.p, nparts_out);
         if (n && !is_device_ptr(part)) SA_HIP_CHECK(hipMemcpyAsync(part, dp.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
         SA_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    SA_API_END
+}
+
+// the refinement pass on a caller's partition (partition.hip): everything is checked, and the work done on a copy, before part
+// is written
+int saamge_amd_partition_refine(int n, const long long *xadj, const int *adj, int nparts, int *part, int rounds, int max_size,
+                                int min_size, unsigned seed, int renumber, void *stream, long long info[4]) {
+    SA_API_BEGIN
+    SA_REQUIRE(n >= 0, "n < 0");
+    SA_REQUIRE(xadj && (n == 0 || part), "null argument");
+    SA_REQUIRE(rounds >= 0 && max_size >= 0 && min_size >= 0, "rounds, max_size and min_size must be >= 0");
+    SA_REQUIRE(renumber == 0 || renumber == 1, "renumber must be 0 or 1");
+    SA_REQUIRE(nparts >= 0 && nparts <= n && (nparts > 0 || n == 0), "nparts outside [1, n]");
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    {
+        DBuf<roff_t> dx;
+        DBuf<int> da, lab((size_t)n), out;
+        import_graph(s, n, xadj, adj, dx, da);
+        if (n) SA_HIP_CHECK(hipMemcpyAsync(lab.p, part, (size_t)n * sizeof(int), hipMemcpyDefault, s));
+        check_partition_device(s, n, lab.p, nparts);
+        const RefineStats st = refine_partition_device(s, n, dx.p, da.p, nparts, lab.p, rounds, max_size, min_size, seed);
+        const int *result = lab.p;
+        if (renumber && n) {
+            int np = 0;
+            out.alloc((size_t)n);
+            renumber_device(s, n, lab.p, nparts, out.p, &np);
+            result = out.p;
+        }
+        if (n) SA_HIP_CHECK(hipMemcpyAsync(part, result, (size_t)n * sizeof(int), hipMemcpyDefault, s));
+        SA_HIP_CHECK(hipStreamSynchronize(s));
+        if (info) { info[0] = st.rounds; info[1] = st.moved; info[2] = st.gain; info[3] = st.converged; }
     }
     SA_API_END
 }
@@ -939,12 +982,19 @@ int saamge_amd_partition_mesh(int NE, int nde, const int *elem_ptr, const int *e
 int saamge_amd_partition_mesh_v2(int NE, int nde, const int *elem_ptr, const int *elem_to_dof, int ND, int num_coarsenings,
                                  const int *elems_per_agg, const saamge_amd_partition_options_v2 *o, void *stream,
                                  saamge_amd_partitioning **out) {
+    return saamge_amd_partition_mesh_refined(NE, nde, elem_ptr, elem_to_dof, ND, num_coarsenings, elems_per_agg, o, nullptr, stream, out);
+}
+
+int saamge_amd_partition_mesh_refined(int NE, int nde, const int *elem_ptr, const int *elem_to_dof, int ND, int num_coarsenings,
+                                      const int *elems_per_agg, const saamge_amd_partition_options_v2 *o, const int *refine_rounds,
+                                      void *stream, saamge_amd_partitioning **out) {
     SA_API_BEGIN
     SA_REQUIRE(out && elems_per_agg && (NE == 0 || elem_to_dof), "null argument");
     SA_REQUIRE(NE >= 0 && ND >= 0, "NE < 0 or ND < 0");
     SA_REQUIRE(elem_ptr || nde >= 1, "elem_ptr or a uniform nde >= 1 is needed");
     SA_REQUIRE(num_coarsenings >= 1 && num_coarsenings < SAAMGE_AMD_MAX_LEVELS, "num_coarsenings out of range");
     for (int k = 0; k < num_coarsenings; ++k) SA_REQUIRE(elems_per_agg[k] >= 1, "elems_per_agg < 1");
+    for (int k = 0; refine_rounds && k < num_coarsenings; ++k) SA_REQUIRE(refine_rounds[k] >= 0, "refine_rounds < 0");
     const PartitionOptions po = convert_partition_options(o);
     hipStream_t s = (hipStream_t)stream;
     ThreadStreamScope scope(s);
@@ -978,6 +1028,16 @@ int saamge_amd_partition_mesh_v2(int NE, int nde, const int *elem_ptr, const int
         P->part.emplace_back((size_t)n);
         int np = 0;
         partition_graph_device(s, n, P->xadj[(size_t)k].p, P->adj[(size_t)k].p, elems_per_agg[k], po, P->part.back().p, &np);
+        if (refine_rounds && refine_rounds[k] > 0 && n) {   // on the numbered parts, which are numbered again afterwards
+            int max_size = 0, min_size = 0;
+            resolve_partition_sizes(elems_per_agg[k], po, &max_size, &min_size);
+            DBuf<int> lab((size_t)n);
+            SA_HIP_CHECK(hipMemcpyAsync(lab.p, P->part.back().p, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, s));
+            refine_partition_device(s, n, P->xadj[(size_t)k].p, P->adj[(size_t)k].p, np, lab.p, refine_rounds[k], max_size, min_size, po.seed);
+            renumber_device(s, n, lab.p, np, P->part.back().p, &np);
+        } else if (refine_rounds) {
+            refine_partition_device(s, 0, nullptr, nullptr, 0, nullptr, 0, 0, 0, po.seed);   // (clears the thread's counts)
+        }
         P->n_elem.push_back(n);
         P->nparts.push_back(np);
         std::vector<int> h((size_t)n);

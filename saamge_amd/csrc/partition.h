@@ -25,6 +25,13 @@ struct GrowthStats {
     int rounds = 0, quota_nodes = 0, open_parts = 0, released_nodes = 0;
 };
 GrowthStats last_growth_stats();
+// the calling thread's last refine_partition_device: rounds that moved nodes, nodes moved, the sum of their gains (= cut edges
+// removed), and whether it stopped for want of a candidate
+struct RefineStats {
+    long long rounds = 0, moved = 0, gain = 0;
+    int converged = 0;
+};
+RefineStats last_refine_stats();
 
 // Refuses offsets that are not 0-based and ascending, columns outside [0, n) and entries without their transpose.  Reads
 // adj only after xadj has been checked.  Returns xadj[n].
@@ -32,6 +39,16 @@ int64_t check_graph_device(hipStream_t s, int n, const roff_t *xadj, const int *
 // part (device, n entries) and the number of parts produced; the graph is trusted (check_graph_device)
 void partition_graph_device(hipStream_t s, int n, const roff_t *xadj, const int *adj, int elems_per_agg,
                             const PartitionOptions &o, int *part, int *nparts_out);
+// the caps partition_graph_device works with
+void resolve_partition_sizes(int elems_per_agg, const PartitionOptions &o, int *max_size, int *min_size);
+// refuses a label outside [0, nparts) and an empty part (label on the device)
+void check_partition_device(hipStream_t s, int n, const int *label, int nparts);
+// The boundary refinement pass (partition_model.py, "refine") on a checked partition, labels in place on the device.
+// max_size 0: no cap.  The graph is trusted (check_graph_device).
+RefineStats refine_partition_device(hipStream_t s, int n, const roff_t *xadj, const int *adj, int nparts, int *label, int rounds,
+                                    int max_size, int min_size, unsigned seed);
+// part (another array than label) = the parts numbered by their smallest member
+void renumber_device(hipStream_t s, int n, const int *label, int nlabels, int *part, int *nparts_out);
 // e2d_I / e2d_J on the device and already checked
 void element_graph_device(hipStream_t s, int NE, const int *e2d_I, const int *e2d_J, int ND, int min_shared,
                           DBuf<roff_t> &xadj, DBuf<int> &adj);

@@ -13,6 +13,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <type_traits>
 
 namespace saamge_amd {
 
@@ -438,6 +439,226 @@ __global__ __launch_bounds__(256) void pt_apply_kernel(int n, const int *__restr
     if (i < n) part[i] = newnum[label[i]];
 }
 
+// ---- boundary refinement (partition_model.py, "refine") ---------------------------------------------------------------------
+constexpr int PT_REFINE_DEG_MAX = 1024, PT_REFINE_LOCAL_MAX = 64, PT_GAIN_MAX = 65535;
+constexpr int PT_WAVE = 64;
+
+__device__ inline u64 group_max_u64(u64 v) {
+    for (int m = PT_LPR / 2; m; m >>= 1) { const u64 o = shfl_xor_u64(v, m); v = o > v ? o : v; }
+    return v;
+}
+// The counts.  One sweep gives own(v); a row with a foreign neighbour that can still be a candidate (own >= 1, its part above
+// the floor, at most PT_REFINE_DEG_MAX entries) is swept again, now from the cache: every foreign entry counts the entries of
+// its label, and the maximum of (count, -label) is the target.  Rows with gain > 0 whose target has room are compacted in any
+// order (nothing that follows depends on it): cand[j] = v, target[v], gain[v].  counters[0] += such rows.
+__global__ __launch_bounds__(256) void pt_refine_count_kernel(int n, const roff_t *__restrict__ xadj, const int *__restrict__ adj,
+                                                              const int *__restrict__ label, const int *__restrict__ sizes,
+                                                              int max_size, int floor_size, int *__restrict__ target,
+                                                              int *__restrict__ gain, int *__restrict__ cand,
+                                                              int *__restrict__ counters) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const long v = t / PT_LPR;
+    const int lane = (int)(t % PT_LPR);
+    const bool valid = v < n;
+    const roff_t b = valid ? xadj[v] : 0, e = valid ? xadj[v + 1] : 0;
+    const int p = valid ? label[v] : 0;
+    int own = 0, foreign = 0;
+    for (roff_t k = b + lane; k < e; k += PT_LPR) {
+        const int u = adj[k];
+        if (u == (int)v) continue;
+        const int lu = label[u];
+        own += lu == p;
+        foreign |= lu != p;
+    }
+    own = group_sum(own);
+    foreign = group_or(foreign);
+    const bool second = valid && foreign && own >= 1 && e - b <= PT_REFINE_DEG_MAX && sizes[p] > floor_size;
+    u64 best = 0;
+    if (second)
+        for (roff_t k = b + lane; k < e; k += PT_LPR) {
+            const int q = label[adj[k]];
+            if (q == p) continue;      // (the entry v itself has the label p)
+            int c = 0;
+            for (roff_t j = b; j < e; ++j) c += label[adj[j]] == q;
+            const u64 key = ((u64)(unsigned)c << 32) | (0xFFFFFFFFu - (unsigned)q);
+            best = key > best ? key : best;
+        }
+    best = group_max_u64(best);
+    if (second && lane == 0) {
+        const int q = (int)(0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull));
+        const int g = (int)(best >> 32) - own;
+        if (g > 0 && (max_size == 0 || sizes[q] < max_size)) {
+            const int j = atomicAdd(&counters[0], 1);
+            cand[j] = (int)v;
+            target[v] = q;
+            gain[v] = g;
+        }
+    }
+}
+// The free check, one wavefront per compacted row v of part p.  N, the neighbours of v labelled p, is gathered into LDS (at
+// most 64, else v is not free) and ordered; lane i owns member i and builds the 64-bit mask of the members it is linked to:
+// those among its neighbours of part p, and those among the neighbours of such a neighbour x != v, found by bisection.  The
+// closure from member 0 is a repeated OR over the wavefront until it is stable; it is tried on the adjacent members alone
+// before the neighbours' neighbours are walked.  A free row gets its key; counters[1] += free
+// rows.  The loop bounds are the same for the four wavefronts of a block, so the barriers are met by all of them.
+__global__ __launch_bounds__(256) void pt_refine_free_kernel(const roff_t *__restrict__ xadj, const int *__restrict__ adj,
+                                                             const int *__restrict__ label, const int *__restrict__ cand,
+                                                             const int *__restrict__ gain, unsigned seed,
+                                                             u64 *__restrict__ key, int *__restrict__ counters) {
+    __shared__ int raw[256 / PT_WAVE][PT_REFINE_LOCAL_MAX], mem[256 / PT_WAVE][PT_REFINE_LOCAL_MAX];
+    const int w = threadIdx.x / PT_WAVE, lane = threadIdx.x % PT_WAVE;
+    const int m = counters[0];
+    for (long base = (long)blockIdx.x * (256 / PT_WAVE); base < m; base += (long)gridDim.x * (256 / PT_WAVE)) {
+        const bool active = base + w < m;
+        const int v = active ? cand[base + w] : 0;
+        const int p = active ? label[v] : 0;
+        const roff_t b = active ? xadj[v] : 0, e = active ? xadj[v + 1] : 0;
+        int cnt = 0;
+        for (roff_t k0 = b; k0 < e; k0 += PT_WAVE) {
+            const roff_t k = k0 + lane;
+            int u = -1;
+            bool in = false;
+            if (k < e) { u = adj[k]; in = u != v && label[u] == p; }
+            const u64 bal = __ballot(in);
+            const int idx = cnt + __popcll(bal & ((1ull << lane) - 1ull));
+            if (in && idx < PT_REFINE_LOCAL_MAX) raw[w][idx] = u;
+            cnt += __popcll(bal);
+        }
+        const bool local = cnt >= 2 && cnt <= PT_REFINE_LOCAL_MAX;
+        __syncthreads();
+        if (local && lane < cnt) {   // rank sort: rows of the library's graphs ascend already, a caller's need not
+            const int mine = raw[w][lane];
+            int r = 0;
+            for (int j = 0; j < cnt; ++j) { const int o = raw[w][j]; r += o < mine || (o == mine && j < lane); }
+            mem[w][r] = mine;
+        }
+        __syncthreads();
+        u64 mask = 0;
+        const int *N = mem[w];
+        const auto find = [&](int y) {
+            int lo = 0, hi = cnt;
+            while (lo < hi) {
+                const int mid = lo + (hi - lo) / 2;
+                if (N[mid] < y) lo = mid + 1;
+                else hi = mid;
+            }
+            if (lo < cnt && N[lo] == y) mask |= 1ull << lo;
+        };
+        // the links of member `lane`: itself, the members among its neighbours of part p and, with TWO_HOP, those among the
+        // neighbours of such a neighbour x != v
+        const auto links = [&](auto two_hop) {
+            constexpr bool TWO_HOP = decltype(two_hop)::value;
+            const int a = N[lane];
+            mask |= 1ull << lane;
+            if (lane > 0 && N[lane - 1] == a) mask |= 1ull << (lane - 1);       // an entry listed twice is one member
+            if (lane + 1 < cnt && N[lane + 1] == a) mask |= 1ull << (lane + 1);
+            for (roff_t k = xadj[a], ke = xadj[a + 1]; k < ke; ++k) {
+                const int x = adj[k];
+                if (x == v || label[x] != p) continue;
+                find(x);
+                if constexpr (TWO_HOP)
+                    for (roff_t j = xadj[x], je = xadj[x + 1]; j < je; ++j) find(adj[j]);
+            }
+        };
+        // the closure from member 0: a repeated OR over the wavefront until it is stable (every lane takes part)
+        const auto connected = [&]() {
+            const u64 all = cnt == 64 ? ~0ull : (1ull << cnt) - 1ull;
+            u64 reach = 1ull;
+            for (;;) {
+                u64 nr = ((reach >> lane) & 1ull) ? mask : 0ull;
+                for (int mm = PT_WAVE / 2; mm; mm >>= 1) nr |= shfl_xor_u64(nr, mm);
+                nr |= reach;
+                if (nr == reach) break;
+                reach = nr;
+            }
+            return reach == all;
+        };
+        bool isfree = cnt == 1;
+        if (local) {     // (uniform in the wavefront)
+            // the adjacent members first: where the graph has triangles they mostly connect N already, and the walk over the
+            // neighbours' neighbours, the long part, is only for the rows they leave open
+            if (lane < cnt) links(std::false_type());
+            isfree = connected();
+            if (!isfree) {
+                if (lane < cnt) links(std::true_type());
+                isfree = connected();
+            }
+        }
+        if (active && isfree && lane == 0) {
+            key[v] = ((u64)(unsigned)(PT_GAIN_MAX - min(gain[v], PT_GAIN_MAX)) << 32) | pt_prio((unsigned)v, seed);
+            atomicAdd(&counters[1], 1);
+        }
+        __syncthreads();
+    }
+}
+// ball = the minimum key within 2 hops: a candidate that holds it wins.  Winners are compacted: counters[2] += winners.
+__global__ __launch_bounds__(256) void pt_refine_winner_kernel(int n, const u64 *__restrict__ key, const u64 *__restrict__ ball,
+                                                               u64 *__restrict__ wkeys, int *__restrict__ wids,
+                                                               int *__restrict__ counters) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const u64 k = key[i];
+    if (k == PT_NONE || ball[i] != k) return;
+    const int j = atomicAdd(&counters[2], 1);
+    wkeys[j] = k;
+    wids[j] = (int)i;
+}
+// the winners in key order: lab[j] = the target, pos[j] = j
+__global__ __launch_bounds__(256) void pt_refine_target_kernel(int m, const int *__restrict__ ids, const int *__restrict__ target,
+                                                               int *__restrict__ lab, int *__restrict__ pos) {
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (j < m) { lab[j] = target[ids[j]]; pos[j] = (int)j; }
+}
+__device__ inline int pt_run_start(const int *lab, int j) {
+    const int p = lab[j];
+    int lo = 0, hi = j;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (lab[mid] < p) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+// lab ascending, the winners of one target in their order: the first max_size - size are admitted (all without a cap).  The
+// answer goes to the winner's place in key order, with the label of its source, or nparts when it is not admitted.
+__global__ __launch_bounds__(256) void pt_refine_admit_kernel(int m, const int *__restrict__ lab, const int *__restrict__ pos,
+                                                              const int *__restrict__ ids, const int *__restrict__ label,
+                                                              const int *__restrict__ sizes, int max_size, int nparts,
+                                                              int *__restrict__ src) {
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= m) return;
+    const bool in = max_size == 0 || (int)j - pt_run_start(lab, (int)j) < max_size - sizes[lab[j]];
+    src[pos[j]] = in ? label[ids[pos[j]]] : nparts;
+}
+// lab ascending, the admitted of one source in their order (the others at the end under nparts): the first size - floor move.
+// A node stands once in ids and the sweeps that read the labels are over, so the labels are written in place.
+// totals[0] += movers, totals[1] += their gains.
+__global__ __launch_bounds__(256) void pt_refine_apply_kernel(int m, const int *__restrict__ lab, const int *__restrict__ ids,
+                                                              const int *__restrict__ sizes, int floor_size, int nparts,
+                                                              const int *__restrict__ target, const int *__restrict__ gain,
+                                                              int *__restrict__ label, u64 *__restrict__ totals) {
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= m) return;
+    const int p = lab[j];
+    if (p == nparts || (int)j - pt_run_start(lab, (int)j) >= sizes[p] - floor_size) return;
+    const int v = ids[j];
+    label[v] = target[v];
+    atomicAdd(&totals[0], 1ull);
+    atomicAdd(&totals[1], (u64)gain[v]);
+}
+__global__ __launch_bounds__(256) void pt_check_labels_kernel(int n, const int *__restrict__ label, int nparts, int *__restrict__ sizes,
+                                                              int *__restrict__ err) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int l = label[i];
+    if (l < 0 || l >= nparts) atomicOr(err, 1);
+    else atomicAdd(&sizes[l], 1);
+}
+__global__ __launch_bounds__(256) void pt_check_empty_kernel(int nparts, const int *__restrict__ sizes, int *__restrict__ err) {
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p < nparts && sizes[p] == 0) atomicOr(err, 2);
+}
+
 // ---- quotient graph -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void pt_cut_count_kernel(int n, const roff_t *__restrict__ xadj, const int *__restrict__ adj,
                                                            const int *__restrict__ part, int *__restrict__ cnt) {
@@ -813,11 +1034,13 @@ constexpr int PT_REPAIR_ROUNDS = 32;
 
 thread_local SeedingStats t_seeding_stats;
 thread_local GrowthStats t_growth_stats;
+thread_local RefineStats t_refine_stats;
 
 }  // namespace
 
 SeedingStats last_seeding_stats() { return t_seeding_stats; }
 GrowthStats last_growth_stats() { return t_growth_stats; }
+RefineStats last_refine_stats() { return t_refine_stats; }
 
 int64_t check_graph_device(hipStream_t s, int n, const roff_t *xadj, const int *adj) {
     if (n == 0) return 0;
@@ -910,18 +1133,107 @@ void partition_graph_device(hipStream_t s, int n, const roff_t *xadj, const int 
     if (min_size > 0)
         for (int r = 0; r < PT_MERGE_ROUNDS; ++r)
             if (!g.merge_round(min_size, max_size)) break;
-    // parts numbered by their smallest member
-    DBuf<int> minid((size_t)g.nlabels), first((size_t)n), rank((size_t)n + 1), newnum((size_t)g.nlabels);
-    fill_int(s, g.nlabels, n, minid.p);
-    hipLaunchKernelGGL(pt_minid_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)g.label, minid.p);
-    hipLaunchKernelGGL(pt_first_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)g.label, (const int *)minid.p, first.p);
+    renumber_device(s, n, g.label, g.nlabels, part, nparts_out);
+}
+
+void resolve_partition_sizes(int epa, const PartitionOptions &o, int *max_size, int *min_size) {
+    *max_size = o.max_size < 0 ? (int)std::min<int64_t>(2ll * epa, INT_MAX) : o.max_size;
+    *min_size = o.min_size < 0 ? epa / 4 : o.min_size;
+}
+
+// parts numbered by their smallest member; label and part are different arrays
+void renumber_device(hipStream_t s, int n, const int *label, int nlabels, int *part, int *nparts_out) {
+    DBuf<int> minid((size_t)nlabels), first((size_t)n), rank((size_t)n + 1), newnum((size_t)nlabels);
+    fill_int(s, nlabels, n, minid.p);
+    hipLaunchKernelGGL(pt_minid_kernel, grid_flat(n), dim3(256), 0, s, n, label, minid.p);
+    hipLaunchKernelGGL(pt_first_kernel, grid_flat(n), dim3(256), 0, s, n, label, (const int *)minid.p, first.p);
     SA_HIP_CHECK(hipGetLastError());
     exclusive_scan_int(s, n, first.p, rank.p);
-    hipLaunchKernelGGL(pt_newnum_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)g.label, (const int *)first.p,
+    hipLaunchKernelGGL(pt_newnum_kernel, grid_flat(n), dim3(256), 0, s, n, label, (const int *)first.p,
                        (const int *)rank.p, newnum.p);
-    hipLaunchKernelGGL(pt_apply_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)g.label, (const int *)newnum.p, part);
+    hipLaunchKernelGGL(pt_apply_kernel, grid_flat(n), dim3(256), 0, s, n, label, (const int *)newnum.p, part);
     SA_HIP_CHECK(hipGetLastError());
     *nparts_out = read_one(rank.p + n, s);
+}
+
+void check_partition_device(hipStream_t s, int n, const int *label, int nparts) {
+    SA_REQUIRE(nparts >= 0 && nparts <= n, "nparts outside [0, n]");
+    if (n == 0) return;
+    DBuf<int> sizes((size_t)nparts), err(1);
+    sizes.zero(s);
+    err.zero(s);
+    hipLaunchKernelGGL(pt_check_labels_kernel, grid_flat(n), dim3(256), 0, s, n, label, nparts, sizes.p, err.p);
+    hipLaunchKernelGGL(pt_check_empty_kernel, grid_flat(nparts), dim3(256), 0, s, nparts, (const int *)sizes.p, err.p);
+    SA_HIP_CHECK(hipGetLastError());
+    const int bits = err.to_host(s)[0];
+    SA_REQUIRE(!(bits & 1), "part: label outside [0, nparts)");
+    SA_REQUIRE(!(bits & 2), "part: an empty part");
+}
+
+// Rounds of: sizes, the count sweep, the free check over the compacted rows, two ball sweeps of the keys, the winners, then
+// the two quotas (sort by key, stable sort by target, stable sort by source) and the apply step.  One read of the counters per
+// round (free rows and winners); the movers and their gains are summed on the device and read once at the end.
+RefineStats refine_partition_device(hipStream_t s, int n, const roff_t *xadj, const int *adj, int nparts, int *label, int rounds,
+                                    int max_size, int min_size, unsigned seed) {
+    SA_REQUIRE(rounds >= 0 && max_size >= 0 && min_size >= 0, "refinement: rounds, max_size and min_size must be >= 0");
+    RefineStats st;
+    t_refine_stats = st;
+    if (n == 0 || rounds == 0) return st;
+    const int floor_size = std::max(min_size, 1);
+    DBuf<int> sizes((size_t)nparts), target((size_t)n), gain((size_t)n), cand((size_t)n), counters(3);
+    DBuf<int> ids((size_t)n), ids2((size_t)n), lab((size_t)n), lab2((size_t)n), pos((size_t)n), pos2((size_t)n);
+    DBuf<u64> key((size_t)n), ka((size_t)n), kb((size_t)n), wkeys((size_t)n), wkeys2((size_t)n), totals(2);
+    const int lab_bits = pt_bits(nparts + 1);
+    size_t tb1 = 0, tb2 = 0;
+    SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb1, wkeys.p, wkeys2.p, ids.p, ids2.p, n, 0, 48, s));
+    SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb2, lab.p, lab2.p, pos.p, pos2.p, n, 0, lab_bits, s));
+    const size_t tmp_bytes = std::max(tb1, tb2);
+    DBuf<char> tmp(tmp_bytes + 16);
+    totals.zero(s);
+    const dim3 free_grid((unsigned)std::min<long>(((long)n + 3) / 4, 2048));
+    while (st.rounds < rounds) {
+        sizes.zero(s);
+        counters.zero(s);
+        fill_u64(s, n, PT_NONE, key.p);
+        hipLaunchKernelGGL(pt_count_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)label, sizes.p);
+        hipLaunchKernelGGL(pt_refine_count_kernel, grid_rows(n), dim3(256), 0, s, n, xadj, adj, (const int *)label, (const int *)sizes.p,
+                           max_size, floor_size, target.p, gain.p, cand.p, counters.p);
+        hipLaunchKernelGGL(pt_refine_free_kernel, free_grid, dim3(256), 0, s, xadj, adj, (const int *)label, (const int *)cand.p,
+                           (const int *)gain.p, seed, key.p, counters.p);
+        hipLaunchKernelGGL((pt_ball_min_kernel<false, false>), grid_rows(n), dim3(256), 0, s, n, xadj, adj, (const int *)nullptr, seed,
+                           (const u64 *)key.p, ka.p, (int *)nullptr);
+        hipLaunchKernelGGL((pt_ball_min_kernel<false, false>), grid_rows(n), dim3(256), 0, s, n, xadj, adj, (const int *)nullptr, seed,
+                           (const u64 *)ka.p, kb.p, (int *)nullptr);
+        hipLaunchKernelGGL(pt_refine_winner_kernel, grid_flat(n), dim3(256), 0, s, n, (const u64 *)key.p, (const u64 *)kb.p, wkeys.p,
+                           ids.p, counters.p);
+        SA_HIP_CHECK(hipGetLastError());
+        const auto c = counters.to_host(s);
+        if (c[1] == 0) { st.converged = 1; break; }
+        const int m = c[2];
+        SA_REQUIRE(m >= 1 && m <= n, "refinement: candidates without a winner");
+        ++st.rounds;
+        // (tmp was sized for n items; the query for m is checked as in grow_balanced)
+        size_t b1 = 0, b2 = 0;
+        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, b1, wkeys.p, wkeys2.p, ids.p, ids2.p, m, 0, 48, s));
+        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, b2, lab.p, lab2.p, pos.p, pos2.p, m, 0, lab_bits, s));
+        SA_REQUIRE(b1 <= tmp_bytes && b2 <= tmp_bytes, "refinement: the sort asks for more temporary storage for fewer items");
+        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs((void *)tmp.p, b1, wkeys.p, wkeys2.p, ids.p, ids2.p, m, 0, 48, s));
+        hipLaunchKernelGGL(pt_refine_target_kernel, grid_flat(m), dim3(256), 0, s, m, (const int *)ids2.p, (const int *)target.p, lab.p, pos.p);
+        SA_HIP_CHECK(hipGetLastError());
+        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs((void *)tmp.p, b2, lab.p, lab2.p, pos.p, pos2.p, m, 0, lab_bits, s));
+        hipLaunchKernelGGL(pt_refine_admit_kernel, grid_flat(m), dim3(256), 0, s, m, (const int *)lab2.p, (const int *)pos2.p,
+                           (const int *)ids2.p, (const int *)label, (const int *)sizes.p, max_size, nparts, lab.p);
+        SA_HIP_CHECK(hipGetLastError());
+        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs((void *)tmp.p, b2, lab.p, lab2.p, ids2.p, ids.p, m, 0, lab_bits, s));
+        hipLaunchKernelGGL(pt_refine_apply_kernel, grid_flat(m), dim3(256), 0, s, m, (const int *)lab2.p, (const int *)ids.p,
+                           (const int *)sizes.p, floor_size, nparts, (const int *)target.p, (const int *)gain.p, label, totals.p);
+        SA_HIP_CHECK(hipGetLastError());
+    }
+    const auto tot = totals.to_host(s);   // (synchronises: the temporaries go out of scope)
+    st.moved = (long long)tot[0];
+    st.gain = (long long)tot[1];
+    t_refine_stats = st;
+    return st;
 }
 
 void element_graph_device(hipStream_t s, int NE, const int *e2d_I, const int *e2d_J, int ND, int min_shared,

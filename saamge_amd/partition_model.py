@@ -63,6 +63,38 @@ a minimum / maximum / count over integers, so no result depends on an execution 
                minimum), so: q is STATIONARY when it proposes nothing, or proposes to a part that proposes back and has the
                larger label.  p joins q when q is stationary, p is not, and p is the proposer of q with the smallest
                (size, label).  One joiner per part and round keeps the cap.  Until a round merges nothing, at most 8.
+  refine       `refine_graph`, `refine_rounds > 0`: boundary refinement, off by default.  It takes any partition (labels in
+               [0, nparts), no part empty) and works after the merges, before the renumbering, with the resolved caps
+               (max_size 0: no cap; floor = max(min_size, 1)).  Entries u == v are ignored throughout; deg(v) is the number
+               of entries of row v.  One round, from the labels and sizes of the previous round:
+               counts   v in part p: own(v) = its neighbours labelled p, c_q(v) = those labelled q != p.  The target t(v) is
+                        the q of largest c_q, ties to the smallest label; gain(v) = c_t - own.
+               candidate  gain > 0, own >= 1, size[t] < max_size (with a cap), size[p] > floor, deg(v) <= REFINE_DEG_MAX =
+                        1024, and v is FREE.
+               free     N = the neighbours of v labelled p.  Not free when own = 0 or own > REFINE_LOCAL_MAX = 64.  Two members
+                        of N are linked when they are adjacent or have a common neighbour x != v labelled p; v is free when N
+                        is connected under the transitive closure of the links (|N| = 1 is).  The two-hop link matters: a face
+                        graph of hexes has no triangles, and only leaves could move without it.
+               winners  key(v) = ((65535 - min(gain, 65535)) << 32) | prio(v); a candidate wins when its key is the minimum
+                        over the candidates within 2 hops (closed balls through nodes of every kind; one pass, not iterated).
+               quotas   the winners per target in the order (clipped gain descending, priority ascending): the first
+                        max_size - size[t] are admitted (all without a cap); the admitted per source in the same order: the
+                        first size[p] - floor move (`select_claimants` twice).
+               apply    the movers take their target's label.
+               The pass stops when a round has no candidate or when `rounds` rounds have moved nodes.  info = [rounds that
+               moved nodes, nodes moved, sum of the gains = cut edges removed, 1 if it stopped for want of a candidate].
+               Why it holds together:
+               - winners are pairwise more than 2 hops apart (of two candidates within 2 hops only the smaller key can be the
+                 minimum of its ball), so movers are never adjacent and each move lowers the cut by exactly its gain;
+               - the cut falls by >= 1 in every round that moves a node, so the pass ends;
+               - a round with a candidate moves a node: the candidate of smallest key wins its ball, is first in its target's
+                 order (quota >= 1, size[t] < max_size) and first in its source's (quota >= 1, size[p] > floor);
+               - a connected part stays connected: the members of N and the nodes x that link them lie within 2 hops of the
+                 mover v, so none of them moves in this round; a path of the part through v enters and leaves it by members
+                 of N and is rerouted through N and the linking nodes;
+               - a joiner stays attached: gain > 0 and own >= 1 give c_t >= 2 neighbours in the target, and they stay;
+               - sizes hold: at most max_size - size[t] nodes join t and at most size[p] - floor leave p, so no part is
+                 emptied, exceeds max_size or falls below floor through the pass; the part count stays.
   renumbering  parts 0 .. nparts-1 in the order of their smallest member.
   quotient     parts adjacent when any of their members are; unweighted, columns ascending.
 """
@@ -73,6 +105,9 @@ REPAIR_ROUNDS = 32
 DEFAULT_LLOYD_ITERS = 0
 RADIUS_MAX = 32
 HITS_MAX = 65535
+REFINE_DEG_MAX = 1024
+REFINE_LOCAL_MAX = 64
+GAIN_MAX = 65535
 
 
 def priority(n, seed=0):
@@ -356,11 +391,147 @@ def renumber(label, nlabels):
     return newnum[label].astype(np.int32), int(first.sum())
 
 
+def _expand_rows(xadj, rows):
+    """(owner, pos): for every entry of the rows given, the index into `rows` and the position in the CSR arrays."""
+    cnt = xadj[rows + 1] - xadj[rows]
+    owner = np.repeat(np.arange(len(rows), dtype=np.int64), cnt)
+    first = np.cumsum(cnt) - cnt
+    pos = np.arange(int(cnt.sum()), dtype=np.int64) - np.repeat(first, cnt) + np.repeat(xadj[rows], cnt)
+    return owner, pos
+
+
+def refine_counts(g, label, nparts):
+    """own, target (-1: no foreign neighbour), c_target per node; entries u == v ignored."""
+    nl = g.src != g.dst
+    src, ls, ld = g.src[nl], label[g.src[nl]], label[g.dst[nl]]
+    own = np.bincount(src[ls == ld], minlength=g.n)
+    f = ls != ld
+    k, cnt = np.unique(src[f] * nparts + ld[f], return_counts=True)
+    v, q = k // nparts, k % nparts
+    order = np.lexsort((q, -cnt, v))
+    v, q, cnt = v[order], q[order], cnt[order]
+    first = np.ones(len(v), bool)
+    first[1:] = v[1:] != v[:-1]
+    target = np.full(g.n, -1, np.int64)
+    ct = np.zeros(g.n, np.int64)
+    target[v[first]] = q[first]
+    ct[v[first]] = cnt[first]
+    return own, target, ct
+
+
+def refine_free(g, label, nodes):
+    """free(v) for the nodes given (each with 1 <= own).  The members (v, a) of N(v) and the nodes (v, x), x != v of v's part
+    adjacent to a member, form a graph with the edges member -- adjacent node; N(v) is connected under the closure of the
+    links exactly when its members lie in one component of it."""
+    n = g.n
+    nodes = np.asarray(nodes, np.int64)
+    if not len(nodes):
+        return np.zeros(0, bool)
+    ci, pos = _expand_rows(g.xadj, nodes)
+    a = g.dst[pos]
+    keep = (label[a] == label[nodes[ci]]) & (a != nodes[ci])
+    mk = np.unique(ci[keep] * n + a[keep])
+    ci, a = mk // n, mk % n
+    ei, pos = _expand_rows(g.xadj, a)
+    x = g.dst[pos]
+    keep = (label[x] == label[a[ei]]) & (x != nodes[ci[ei]])
+    ei, x = ei[keep], x[keep]
+    allk, inv = np.unique(np.concatenate([mk, ci[ei] * n + x]), return_inverse=True)
+    inv = inv.ravel()
+    u, w = inv[:len(mk)][ei], inv[len(mk):]
+    comp = np.arange(len(allk), dtype=np.int64)
+    while True:
+        new = comp.copy()
+        np.minimum.at(new, u, comp[w])
+        np.minimum.at(new, w, comp[u])
+        new = new[new]
+        if (new == comp).all():
+            break
+        comp = new
+    cm = comp[inv[:len(mk)]]
+    lo = np.full(len(nodes), np.iinfo(np.int64).max)
+    hi = np.full(len(nodes), -1, np.int64)
+    np.minimum.at(lo, ci, cm)
+    np.maximum.at(hi, ci, cm)
+    return lo == hi
+
+
+def refine_round(g, label, nparts, prio, max_size, floor):
+    """One round: (new labels, stats).  stats counts what every rule of the round did (the tests read them)."""
+    BIG = np.iinfo(np.int64).max
+    size = np.bincount(label, minlength=nparts)
+    own, target, ct = refine_counts(g, label, nparts)
+    gain = ct - own
+    ts = np.where(target >= 0, target, 0)
+    gainer = (target >= 0) & (gain > 0) & (own >= 1)
+    ok_size = size[label] > floor
+    if max_size > 0:
+        ok_size &= size[ts] < max_size
+    ok_deg = np.diff(g.xadj) <= REFINE_DEG_MAX
+    ok_local = own <= REFINE_LOCAL_MAX
+    pre = gainer & ok_size & ok_deg & ok_local
+    nodes = np.flatnonzero(pre)
+    free = refine_free(g, label, nodes)
+    cand = np.zeros(g.n, bool)
+    cand[nodes[free]] = True
+    st = dict(gainers=int(gainer.sum()), size_refused=int((gainer & ~ok_size).sum()),
+              deg_refused=int((gainer & ok_size & ~ok_deg).sum()),
+              local_refused=int((gainer & ok_size & ok_deg & ~ok_local).sum()), not_free=int(len(nodes) - free.sum()),
+              candidates=int(cand.sum()), winners=0, admitted=0, movers=0, gain=0)
+    if not st["candidates"]:
+        return label, st
+    key = np.where(cand, ((GAIN_MAX - np.minimum(gain, GAIN_MAX)) << 32) | prio, BIG)
+    ball = _ball_step(g, _ball_step(g, key, np.minimum), np.minimum)
+    win = cand & (ball == key)
+    quota = np.full(nparts, BIG) if max_size <= 0 else max_size - size
+    adm = select_claimants(np.where(win, target, -1), gain, prio, quota)
+    move = select_claimants(np.where(adm, label, -1), gain, prio, size - floor)
+    st.update(winners=int(win.sum()), admitted=int(adm.sum()), movers=int(move.sum()), gain=int(gain[move].sum()))
+    return np.where(move, target, label), st
+
+
+def refine_graph(n, xadj, adj, part, nparts, rounds, max_size, min_size, seed=0, info=None, hook=None):
+    """The refinement pass on any partition: labels in [0, nparts), no part empty; max_size 0: no cap.  Returns the labels
+    (int32, the caller's numbering).  info (a list of 4) receives [rounds that moved nodes, nodes moved, sum of the gains,
+    stopped for want of a candidate]; hook(label, stats) is called after every round, the one without candidate included."""
+    if rounds < 0 or max_size < 0 or min_size < 0:
+        raise ValueError("rounds, max_size and min_size >= 0")
+    label = np.asarray(part, np.int64).copy()
+    if len(label) != n or (n and (label.min() < 0 or label.max() >= nparts)):
+        raise ValueError("labels outside [0, nparts)")
+    if (np.bincount(label, minlength=nparts) == 0).any():
+        raise ValueError("an empty part")
+    info = [0, 0, 0, 0] if info is None else info
+    info[:] = [0, 0, 0, 0]
+    g = _Graph(n, xadj, adj)
+    prio = priority(n, seed)
+    floor = max(int(min_size), 1)
+    while info[0] < rounds:
+        label, st = refine_round(g, label, nparts, prio, int(max_size), floor)
+        if hook is not None:
+            hook(label.copy(), st)
+        if not st["candidates"]:
+            info[3] = 1
+            break
+        info[0] += 1
+        info[1] += st["movers"]
+        info[2] += st["gain"]
+    return label.astype(np.int32)
+
+
+def edge_cut(n, xadj, adj, part):
+    """Edges (u, v), u < v, whose ends lie in different parts."""
+    g = _Graph(n, xadj, adj)
+    p = np.asarray(part, np.int64)
+    return int(((p[g.src] != p[g.dst]) & (g.src < g.dst)).sum())
+
+
 def partition_graph(n, xadj, adj, elems_per_agg, min_shared=1, lloyd_iters=DEFAULT_LLOYD_ITERS, max_size=-1,
-                    min_size=-1, seed=0, seeding=0, growth=0, growth_info=None, balanced_hook=None):
+                    min_size=-1, seed=0, seeding=0, growth=0, growth_info=None, balanced_hook=None, refine_rounds=0, refine_info=None, refine_hook=None):
     """One level: symmetric CSR graph -> (part int32 (n), nparts).  min_shared is not used here (graph given).
     growth_info: a list that receives the four counts of the last growth (zeros for growth = 0).  balanced_hook(label,
-    nlabels) is called after every balanced phase, before its release (unlabelled nodes are -1)."""
+    nlabels) is called after every balanced phase, before its release (unlabelled nodes are -1).  refine_rounds > 0: the
+    refinement pass (`refine_graph`) after the merges, with the resolved caps; refine_info receives its four counts."""
     if elems_per_agg < 1 or n < 0:
         raise ValueError("elems_per_agg >= 1 and n >= 0")
     if seeding not in (0, 1):
@@ -408,6 +579,11 @@ def partition_graph(n, xadj, adj, elems_per_agg, min_shared=1, lloyd_iters=DEFAU
             label, moved = _merge_round(g, label, nlabels, max_size, min_size)
             if not moved:
                 break
+    if refine_info is not None:
+        refine_info[:] = [0, 0, 0, 0]
+    if refine_rounds:
+        label, nlabels = renumber(label, nlabels)      # (merged labels leave holes; the pass wants every label in use)
+        label = refine_graph(n, xadj, adj, label, nlabels, refine_rounds, max_size, min_size, seed, refine_info, refine_hook)
     return renumber(label, nlabels)
 
 
@@ -421,14 +597,19 @@ def quotient_graph(n, xadj, adj, part, nparts):
 
 
 def partition_mesh(elem_ptr, elem_to_dof, ND, elems_per_agg, **opts):
-    """All levels: elems_per_agg is a sequence, one entry per coarsening.  Returns (parts, nparts, graphs): graphs[k] is the
+    """All levels: elems_per_agg is a sequence, one entry per coarsening, and so is refine_rounds when given (the quotient
+    graphs are those of the refined partitions).  Returns (parts, nparts, graphs): graphs[k] is the
     (xadj, adj) that parts[k] partitions, graphs[len(parts)] the quotient graph of the last level."""
     min_shared = opts.get("min_shared", 1)
     graphs = [build_element_graph(elem_ptr, elem_to_dof, ND, min_shared)]
     parts, nparts = [], []
     n = len(elem_ptr) - 1
-    for epa in elems_per_agg:
+    opts = dict(opts)
+    refine_rounds = opts.pop("refine_rounds", None)      # one count per coarsening; refine_info: the last level's
+    for k, epa in enumerate(elems_per_agg):
         xadj, adj = graphs[-1]
+        if refine_rounds is not None:
+            opts["refine_rounds"] = int(refine_rounds[k])
         part, npt = partition_graph(n, xadj, adj, int(epa), **opts)
         parts.append(part)
         nparts.append(npt)

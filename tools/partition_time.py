@@ -3,11 +3,17 @@ of the parts, on Q1 hex grids (vertex and face adjacency) and on the half-prism 
 clock closed by a synchronise, one warm-up, `--reps` repetitions (all listed).  Prints one JSON line per case.
 
     python tools/partition_time.py [--hex 128,256] [--mixed 64] [--epa 256,64] [--reps 3] [--seeding {0,1}] [--growth {0,1}]
+                                   [--refine R]
 
 --seeding 1 times the spaced seeding; the line then carries, per level, the radius chosen, the independent-set rounds and
 the seeds before and after the top-up (saamge_amd_partition_seeding_info; zeros for --seeding 0).  --growth 1 times the
 balanced growth; the line carries the mode and, per level, the balanced rounds, the nodes labelled under a quota, the parts
 open at the release and the nodes labelled after it (saamge_amd_partition_growth_info; zeros for --growth 0).
+
+--refine R (default 0: off) times the boundary refinement pass with at most R rounds on the partition of each level as the
+other options made it (saamge_amd_partition_refine with that level's caps, parts numbered again): the line then carries, per
+level, the rounds that moved nodes, the nodes moved, the edge cut before and after and the time of the pass alone.  Both
+levels are those of the unrefined partitions, so the lines of --refine 0 and --refine R describe the same graphs.
 
 graph_ms is the time of partition_mesh with one coarsening minus the level-0 partition timed alone (it includes the
 quotient graph of level 0).  For the hex grids, box_setup_ms is the time of a 3-level hierarchy setup of the Poisson problem
@@ -46,6 +52,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--seeding", type=int, choices=(0, 1), default=0)
     ap.add_argument("--growth", type=int, choices=(0, 1), default=0)
+    ap.add_argument("--refine", type=int, default=0)
     a = ap.parse_args()
     epa = [int(x) for x in a.epa.split(",")]
     cases = []
@@ -76,6 +83,26 @@ def main():
         timed(setup)
         return [round(timed(setup)[0], 2) for _ in range(a.reps)]
 
+    def edge_cut(g, part):
+        xadj, adj = g
+        src = torch.repeat_interleave(torch.arange(part.numel(), device="cuda"), xadj[1:] - xadj[:-1])
+        return int((part[src] != part[adj.long()]).sum().item()) // 2
+
+    def refine_level(n, g, part, nparts, e):
+        """The pass on a copy of `part`, one warm-up: rounds, nodes moved, cut before and after, the times."""
+        max_size, min_size = pm.resolve_sizes(e)
+        out = dict(cut_before=edge_cut(g, part))
+        ms_ = []
+        for _ in range(a.reps + 1):
+            work = part.clone()
+            t, (_, info) = timed(lambda: capi.partition_refine(n, g[0], g[1], nparts, work, a.refine, max_size, min_size,
+                                                               renumber=True))
+            ms_.append(round(t, 2))
+        out.update(rounds=info["rounds"], moved=info["moved"], converged=info["converged"], cut_after=edge_cut(g, work),
+                   refine_ms=ms_[1:])
+        assert out["cut_before"] - out["cut_after"] == info["gain"]
+        return out
+
     for name, e2d, eptr, ND, ms in cases:
         mesh1 = lambda: capi.partition_mesh(e2d, ND, epa[:1], elem_ptr=eptr, min_shared=ms, seeding=a.seeding, growth=a.growth)
         _, P = timed(mesh1)                         # warm-up; its graphs feed the per-level timings
@@ -103,13 +130,18 @@ def main():
             t1.append(t)
         peak = capi.memory_stats()[1]
         r = lambda v: [round(x, 2) for x in v]
-        print(json.dumps({
+        extra = {}
+        if a.refine > 0:
+            timed(lev0)
+            extra = {"refine": a.refine, "refine_level0": refine_level(n0, g0, d0, n1, epa[0]),
+                     "refine_level1": refine_level(n1, g1, d1, int(np1), epa[1])}
+        print(json.dumps(dict({
             "case": name, "seeding": a.seeding, "seeding_level0": info0, "seeding_level1": info1,
             "growth": a.growth, "growth_level0": ginfo0, "growth_level1": ginfo1, "elements": n0, "graph_entries": int(g0[1].numel()), "elems_per_agg": epa,
             "nparts": [n1, int(np1)], "mesh_one_level_ms": r(t_mesh), "level0_ms": r(t0), "level1_ms": r(t1),
             "graph_ms": r([m - l for m, l in zip(t_mesh, t0)]), "peak_device_bytes": int(peak),
             "size_over_epa_level0": pm.size_stats(part0, n1, epa[0]),
-            "size_over_epa_level1": pm.size_stats(d1.cpu().numpy(), int(np1), epa[1])}), flush=True)
+            "size_over_epa_level1": pm.size_stats(d1.cpu().numpy(), int(np1), epa[1])}, **extra)), flush=True)
         del g0, g1, d0, d1
     # last, so that the hierarchies do not enter the partitioner's peak memory
     for n in [int(x) for x in a.hex.split(",") if x]:
