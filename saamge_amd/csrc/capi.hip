@@ -880,13 +880,20 @@ void saamge_amd_partition_options_v2_default(saamge_amd_partition_options_v2 *o)
     o->min_shared = p.min_shared; o->lloyd_iters = p.lloyd_iters; o->max_size = p.max_size; o->min_size = p.min_size; o->seed = p.seed; o->seeding = p.seeding; o->growth = p.growth;
 }
 
+// The counts of the calling thread's last partition and its last refinement pass, for the three _info calls.  The device layer
+// zeroes the partition's record when it accepts its arguments and fills it as it goes; the refinement's record is zeroed here
+// before a pass is entered and set when it returns, so a pass that throws leaves zeros.  A call refused before it reaches the
+// device layer leaves both as they were.
+static thread_local PartitionStats t_partition_stats;
+static thread_local RefineStats t_refine_stats;
+
 void saamge_amd_partition_seeding_info(long long info[4]) {
-    const SeedingStats st = last_seeding_stats();
+    const SeedingStats st = t_partition_stats.seeding;
     info[0] = st.radius; info[1] = st.rounds; info[2] = st.seeds_first; info[3] = st.seeds;
 }
 
 void saamge_amd_partition_growth_info(long long info[4]) {
-    const GrowthStats st = last_growth_stats();
+    const GrowthStats st = t_partition_stats.growth;
     info[0] = st.rounds; info[1] = st.quota_nodes; info[2] = st.open_parts; info[3] = st.released_nodes;
 }
 
@@ -907,7 +914,7 @@ static void import_graph(hipStream_t s, int n, const long long *xadj, const int 
 }
 
 void saamge_amd_partition_refine_info(long long info[4]) {
-    const RefineStats st = last_refine_stats();
+    const RefineStats st = t_refine_stats;
     info[0] = st.rounds; info[1] = st.moved; info[2] = st.gain; info[3] = st.converged;
 }
 
@@ -932,7 +939,7 @@ int saamge_amd_partition_graph_v2(int n, const long long *xadj, const int *adj, 
         import_graph(s, n, xadj, adj, dx, da);
         if (is_device_ptr(part)) dp.view(part, (size_t)n);
         else dp.alloc((size_t)n);
-        partition_graph_device(s, n, dx.p, da.p, elems_per_agg, po, dp.p, nparts_out);
+        partition_graph_device(s, n, dx.p, da.p, elems_per_agg, po, dp.p, nparts_out, &t_partition_stats);
         if (n && !is_device_ptr(part)) SA_HIP_CHECK(hipMemcpyAsync(part, dp.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
         SA_HIP_CHECK(hipStreamSynchronize(s));
     }
@@ -957,7 +964,8 @@ int saamge_amd_partition_refine(int n, const long long *xadj, const int *adj, in
         import_graph(s, n, xadj, adj, dx, da);
         if (n) SA_HIP_CHECK(hipMemcpyAsync(lab.p, part, (size_t)n * sizeof(int), hipMemcpyDefault, s));
         check_partition_device(s, n, lab.p, nparts);
-        const RefineStats st = refine_partition_device(s, n, dx.p, da.p, nparts, lab.p, rounds, max_size, min_size, seed);
+        t_refine_stats = RefineStats();
+        const RefineStats st = t_refine_stats = refine_partition_device(s, n, dx.p, da.p, nparts, lab.p, rounds, max_size, min_size, seed);
         const int *result = lab.p;
         if (renumber && n) {
             int np = 0;
@@ -1027,16 +1035,17 @@ int saamge_amd_partition_mesh_refined(int NE, int nde, const int *elem_ptr, cons
     for (int k = 0; k < num_coarsenings; ++k) {
         P->part.emplace_back((size_t)n);
         int np = 0;
-        partition_graph_device(s, n, P->xadj[(size_t)k].p, P->adj[(size_t)k].p, elems_per_agg[k], po, P->part.back().p, &np);
+        partition_graph_device(s, n, P->xadj[(size_t)k].p, P->adj[(size_t)k].p, elems_per_agg[k], po, P->part.back().p, &np,
+                               &t_partition_stats);
+        if (refine_rounds) t_refine_stats = RefineStats();   // a level without rounds reports zeros; NULL leaves the record alone
         if (refine_rounds && refine_rounds[k] > 0 && n) {   // on the numbered parts, which are numbered again afterwards
             int max_size = 0, min_size = 0;
             resolve_partition_sizes(elems_per_agg[k], po, &max_size, &min_size);
             DBuf<int> lab((size_t)n);
             SA_HIP_CHECK(hipMemcpyAsync(lab.p, P->part.back().p, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, s));
-            refine_partition_device(s, n, P->xadj[(size_t)k].p, P->adj[(size_t)k].p, np, lab.p, refine_rounds[k], max_size, min_size, po.seed);
+            t_refine_stats = refine_partition_device(s, n, P->xadj[(size_t)k].p, P->adj[(size_t)k].p, np, lab.p, refine_rounds[k],
+                                                     max_size, min_size, po.seed);
             renumber_device(s, n, lab.p, np, P->part.back().p, &np);
-        } else if (refine_rounds) {
-            refine_partition_device(s, 0, nullptr, nullptr, 0, nullptr, 0, 0, 0, po.seed);   // (clears the thread's counts)
         }
         P->n_elem.push_back(n);
         P->nparts.push_back(np);

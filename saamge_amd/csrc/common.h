@@ -218,6 +218,14 @@ inline hvec<T> fetch_host(const T *src, size_t n, hipStream_t s) {
     }
     return v;
 }
+// one value from the device (synchronises the stream)
+template <class T>
+inline T read_one(const T *p, hipStream_t s) {
+    T v;
+    SA_HIP_CHECK(hipMemcpyAsync(&v, p, sizeof(T), hipMemcpyDeviceToHost, s));
+    SA_HIP_CHECK(hipStreamSynchronize(s));
+    return v;
+}
 
 // Row offsets of every CSR / SELL operator are 64-bit: column indices and dimensions are int32 like the
 // reference's hypre/MFEM types, but the stored entries of one operator may exceed 2^31 (Q2 elasticity at

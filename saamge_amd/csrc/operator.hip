@@ -44,14 +44,6 @@ constexpr int OP_MAX_ND = 46340;           // nd * nd stays below 2^31
 
 inline dim3 grid_flat(long n) { return dim3((unsigned)std::max<long>(1, (n + 255) / 256)); }
 
-template <class T>
-T read_one(const T *p, hipStream_t s) {
-    T v;
-    SA_HIP_CHECK(hipMemcpyAsync(&v, p, sizeof(T), hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
-    return v;
-}
-
 // a copy the handle owns; a large pageable source goes through a page-locked block (DBuf::from_host says why)
 template <class T>
 void upload(DBuf<T> &dst, const T *src, size_t n, hipStream_t s) {

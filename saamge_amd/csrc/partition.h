@@ -14,31 +14,33 @@ struct PartitionOptions {
     int seeding = 0;      // 0: lowest priorities, 1: spaced (greedy distance-r independent set, topped up)
     int growth = 0;       // 0: level-synchronous, 1: balanced (a per-round quota per part, then release)
 };
-// the spaced seeding of the calling thread's last partition_graph_device; zeros after seeding = 0
+// the spaced seeding of a partition_graph_device; zeros after seeding = 0
 struct SeedingStats {
     int radius = 0, rounds = 0, seeds_first = 0, seeds = 0;
 };
-SeedingStats last_seeding_stats();
-// the balanced growth of the calling thread's last partition_graph_device (its last growth, with recentring); zeros after
-// growth = 0.  rounds: those that labelled nodes; open_parts / released_nodes: at the release, 0 when there was none
+// the balanced growth of a partition_graph_device (its last growth, with recentring); zeros after growth = 0.  rounds: those
+// that labelled nodes; open_parts / released_nodes: at the release, 0 when there was none
 struct GrowthStats {
     int rounds = 0, quota_nodes = 0, open_parts = 0, released_nodes = 0;
 };
-GrowthStats last_growth_stats();
-// the calling thread's last refine_partition_device: rounds that moved nodes, nodes moved, the sum of their gains (= cut edges
-// removed), and whether it stopped for want of a candidate
+struct PartitionStats {
+    SeedingStats seeding;
+    GrowthStats growth;
+};
+// a refine_partition_device: rounds that moved nodes, nodes moved, the sum of their gains (= cut edges removed), and whether
+// it stopped for want of a candidate
 struct RefineStats {
     long long rounds = 0, moved = 0, gain = 0;
     int converged = 0;
 };
-RefineStats last_refine_stats();
 
 // Refuses offsets that are not 0-based and ascending, columns outside [0, n) and entries without their transpose.  Reads
 // adj only after xadj has been checked.  Returns xadj[n].
 int64_t check_graph_device(hipStream_t s, int n, const roff_t *xadj, const int *adj);
-// part (device, n entries) and the number of parts produced; the graph is trusted (check_graph_device)
+// part (device, n entries) and the number of parts produced; the graph is trusted (check_graph_device).  *stats is zeroed
+// once the arguments are accepted, before any work, and filled as the seeding and each growth end.
 void partition_graph_device(hipStream_t s, int n, const roff_t *xadj, const int *adj, int elems_per_agg,
-                            const PartitionOptions &o, int *part, int *nparts_out);
+                            const PartitionOptions &o, int *part, int *nparts_out, PartitionStats *stats);
 // the caps partition_graph_device works with
 void resolve_partition_sizes(int elems_per_agg, const PartitionOptions &o, int *max_size, int *min_size);
 // refuses a label outside [0, nparts) and an empty part (label on the device)

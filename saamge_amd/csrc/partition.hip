@@ -7,6 +7,12 @@
 // shuffles, and lane 0 writes.  Growth is the pull form with two label buffers (no atomics on labels); the ball sweeps of the
 // spaced seeding are the same form with two key / two flag buffers.  Balanced growth (`growth = 1`) sweeps once per round for
 // the claims, orders the compacted claimants by two stable radix sorts and labels the first quota[p] of every part.
+//
+// What the phases share is written once, ahead of them.  On the device: row_lane / row_entries (which lane of which row a
+// thread is, and the walk over its entries), group_reduce (the shuffles, over a row's lanes or a wavefront) and pt_run_start
+// (the rank within a sorted run, for the quotas).  On the host: GraphView with sweep / flat (the two launch shapes), ball_min /
+// ball_flag (the ball sweeps by run-time first / last) and PairSorter (the radix sorts of a phase and their temporary
+// storage).  The counts of a call go back to the caller (PartitionStats, RefineStats); nothing here remembers a call.
 #include "partition.h"
 
 #include <hipcub/hipcub.hpp>
@@ -26,6 +32,7 @@ namespace {
 
 typedef unsigned long long u64;
 constexpr int PT_LPR = 8;          // lanes per row of the CSR sweeps
+constexpr int PT_WAVE = 64;
 constexpr u64 PT_NONE = ~0ull;
 
 inline int pt_bits(int n) {
@@ -41,21 +48,56 @@ __device__ inline unsigned pt_prio(unsigned i, unsigned seed) {
     x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
     return x;
 }
-__device__ inline int group_min(int v) {
-    for (int m = PT_LPR / 2; m; m >>= 1) v = min(v, __shfl_xor(v, m));
-    return v;
+
+// ---- the row sweep --------------------------------------------------------------------------------------------------
+// Thread t of a grid_rows(n) launch is lane t % PT_LPR of row t / PT_LPR.  The lanes of a row are adjacent lanes of one
+// wavefront, and a kernel keeps all of them up to its group_reduce, whether the row is valid or not.
+struct RowLane {
+    long v;
+    int lane;
+    bool valid;   // v < n
+};
+__device__ inline RowLane row_lane(int n) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    return {t / PT_LPR, (int)(t % PT_LPR), t / PT_LPR < n};
 }
-__device__ inline int group_or(int v) {
-    for (int m = PT_LPR / 2; m; m >>= 1) v |= __shfl_xor(v, m);
-    return v;
+// f(k) for the entries k of a row that fall to this lane.  The offsets are read here and nowhere else, so a row whose walk
+// is skipped reads none.
+template <class F>
+__device__ inline void row_entries(roff_t b, roff_t e, int lane, F &&f) {
+    for (roff_t k = b + lane; k < e; k += PT_LPR) f(k);
+}
+template <class F>
+__device__ inline void row_entries(const roff_t *__restrict__ xadj, long v, int lane, F &&f) {
+    row_entries(xadj[v], xadj[v + 1], lane, f);
 }
 __device__ inline u64 shfl_xor_u64(u64 v, int m) {
     const unsigned lo = __shfl_xor((unsigned)v, m), hi = __shfl_xor((unsigned)(v >> 32), m);
     return ((u64)hi << 32) | lo;
 }
-__device__ inline u64 group_min_u64(u64 v) {
-    for (int m = PT_LPR / 2; m; m >>= 1) { const u64 o = shfl_xor_u64(v, m); v = o < v ? o : v; }
+// op over the WIDTH adjacent lanes that hold this one (PT_LPR: a row, PT_WAVE: the wavefront); every lane gets the result
+struct OpMin { template <class T> __device__ T operator()(T a, T b) const { return b < a ? b : a; } };
+struct OpMax { template <class T> __device__ T operator()(T a, T b) const { return b > a ? b : a; } };
+struct OpOr { template <class T> __device__ T operator()(T a, T b) const { return a | b; } };
+struct OpSum { template <class T> __device__ T operator()(T a, T b) const { return a + b; } };
+template <int WIDTH, class T, class Op>
+__device__ inline T group_reduce(T v, Op op) {
+    for (int m = WIDTH / 2; m; m >>= 1) {
+        if constexpr (sizeof(T) == 8) v = op(v, (T)shfl_xor_u64((u64)v, m));
+        else v = op(v, __shfl_xor(v, m));
+    }
     return v;
+}
+// the start of the run of lab[j] in the ascending lab: j minus it is the rank of j among the entries of its label
+__device__ inline int pt_run_start(const int *lab, int j) {
+    const int p = lab[j];
+    int lo = 0, hi = j;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (lab[mid] < p) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
 }
 
 __global__ __launch_bounds__(256) void pt_fill_int_kernel(long n, int v, int *__restrict__ a) {
@@ -72,24 +114,21 @@ __global__ __launch_bounds__(256) void pt_fill_u64_kernel(long n, u64 v, u64 *__
 __global__ __launch_bounds__(256) void pt_grow_kernel(int n, const roff_t *__restrict__ xadj, const int *__restrict__ adj,
                                                       const int *__restrict__ cur, const int *__restrict__ dom,
                                                       int *__restrict__ next, int *__restrict__ counters) {
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    const long v = t / PT_LPR;
-    const int lane = (int)(t % PT_LPR);
-    const bool valid = v < n;
-    const int mine = valid ? cur[v] : 0;
+    const RowLane r = row_lane(n);
+    const int mine = r.valid ? cur[r.v] : 0;
     int best = INT_MAX;
-    if (valid && mine < 0) {
-        const int dv = dom ? dom[v] : 0;
-        for (roff_t k = xadj[v] + lane, e = xadj[v + 1]; k < e; k += PT_LPR) {
+    if (r.valid && mine < 0) {
+        const int dv = dom ? dom[r.v] : 0;
+        row_entries(xadj, r.v, r.lane, [&](roff_t k) {
             const int u = adj[k], lu = cur[u];
             if (lu >= 0 && lu < best && (!dom || dom[u] == dv)) best = lu;
-        }
+        });
     }
-    best = group_min(best);
-    if (valid && lane == 0) {
-        if (mine >= 0) next[v] = mine;
-        else if (best != INT_MAX) { next[v] = best; atomicAdd(&counters[0], 1); }
-        else { next[v] = -1; atomicAdd(&counters[1], 1); }
+    best = group_reduce<PT_LPR>(best, OpMin());
+    if (r.valid && r.lane == 0) {
+        if (mine >= 0) next[r.v] = mine;
+        else if (best != INT_MAX) { next[r.v] = best; atomicAdd(&counters[0], 1); }
+        else { next[r.v] = -1; atomicAdd(&counters[1], 1); }
     }
 }
 // lowest (priority, id) among the unlabelled nodes
@@ -98,8 +137,8 @@ __global__ __launch_bounds__(256) void pt_min_unlabelled_kernel(int n, const int
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     u64 key = PT_NONE;
     if (i < n && label[i] < 0) key = ((u64)pt_prio((unsigned)i, seed) << 32) | (unsigned)i;
-    for (int m = 32; m; m >>= 1) { const u64 o = shfl_xor_u64(key, m); key = o < key ? o : key; }
-    if ((threadIdx.x & 63) == 0 && key != PT_NONE) atomicMin(out, key);
+    key = group_reduce<PT_WAVE>(key, OpMin());
+    if (threadIdx.x % PT_WAVE == 0 && key != PT_NONE) atomicMin(out, key);
 }
 __global__ void pt_stall_seed_kernel(const u64 *__restrict__ key, int newlabel, int *__restrict__ label,
                                      int *__restrict__ isseed) {
@@ -111,12 +150,8 @@ __global__ void pt_stall_seed_kernel(const u64 *__restrict__ key, int newlabel, 
 
 // ---- balanced growth (partition_model.py, "balanced growth") --------------------------------------------------------------
 constexpr int PT_HITS_MAX = 65535;
-__device__ inline int group_sum(int v) {
-    for (int m = PT_LPR / 2; m; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-// sizes of the parts while nodes are still unlabelled
-__global__ __launch_bounds__(256) void pt_count_labelled_kernel(int n, const int *__restrict__ label, int *__restrict__ sizes) {
+// sizes of the parts; unlabelled nodes (during growth) are not counted
+__global__ __launch_bounds__(256) void pt_count_kernel(int n, const int *__restrict__ label, int *__restrict__ sizes) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i < n && label[i] >= 0) atomicAdd(&sizes[label[i]], 1);
 }
@@ -128,28 +163,25 @@ __global__ __launch_bounds__(256) void pt_claim_kernel(int n, const roff_t *__re
                                                        const int *__restrict__ label, const int *__restrict__ sizes, int cap,
                                                        unsigned seed, int *__restrict__ claim, u64 *__restrict__ keys,
                                                        int *__restrict__ ids, int *__restrict__ counters) {
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    const long v = t / PT_LPR;
-    const int lane = (int)(t % PT_LPR);
-    const bool open_row = v < n && label[v] < 0;
+    const RowLane r = row_lane(n);
+    const bool open_row = r.valid && label[r.v] < 0;
     int best = INT_MAX;
     if (open_row)
-        for (roff_t k = xadj[v] + lane, e = xadj[v + 1]; k < e; k += PT_LPR) {
+        row_entries(xadj, r.v, r.lane, [&](roff_t k) {
             const int lu = label[adj[k]];
             if (lu >= 0 && lu < best && sizes[lu] < cap) best = lu;
-        }
-    best = group_min(best);
+        });
+    best = group_reduce<PT_LPR>(best, OpMin());
     int hits = 0;
-    if (open_row && best != INT_MAX)
-        for (roff_t k = xadj[v] + lane, e = xadj[v + 1]; k < e; k += PT_LPR) hits += label[adj[k]] == best;
-    hits = group_sum(hits);
-    if (open_row && lane == 0) {
+    if (open_row && best != INT_MAX) row_entries(xadj, r.v, r.lane, [&](roff_t k) { hits += label[adj[k]] == best; });
+    hits = group_reduce<PT_LPR>(hits, OpSum());
+    if (open_row && r.lane == 0) {
         atomicAdd(&counters[1], 1);
         if (best != INT_MAX) {
             const int j = atomicAdd(&counters[0], 1);
-            keys[j] = ((u64)(unsigned)(PT_HITS_MAX - min(hits, PT_HITS_MAX)) << 32) | pt_prio((unsigned)v, seed);
-            ids[j] = (int)v;
-            claim[v] = best;
+            keys[j] = ((u64)(unsigned)(PT_HITS_MAX - min(hits, PT_HITS_MAX)) << 32) | pt_prio((unsigned)r.v, seed);
+            ids[j] = (int)r.v;
+            claim[r.v] = best;
         }
     }
 }
@@ -158,20 +190,14 @@ __global__ __launch_bounds__(256) void pt_claim_gather_kernel(int m, const int *
     const long j = (long)blockIdx.x * 256 + threadIdx.x;
     if (j < m) lab[j] = claim[ids[j]];
 }
-// lab ascending, the claimants of one part in their order: the rank in the own run, by bisection for its start, against the
-// quota.  A node stands once in ids and the sweep that read the labels is over, so the labels are written in place.
+// lab ascending, the claimants of one part in their order: the rank in the own run against the quota.  A node stands once
+// in ids and the sweep that read the labels is over, so the labels are written in place.
 __global__ __launch_bounds__(256) void pt_claim_apply_kernel(int m, const int *__restrict__ lab, const int *__restrict__ ids,
                                                              const int *__restrict__ sizes, int cap, int *__restrict__ label) {
     const long j = (long)blockIdx.x * 256 + threadIdx.x;
     if (j >= m) return;
     const int p = lab[j];
-    int lo = 0, hi = (int)j;
-    while (lo < hi) {
-        const int mid = lo + (hi - lo) / 2;
-        if (lab[mid] < p) lo = mid + 1;
-        else hi = mid;
-    }
-    if ((int)j - lo < cap - sizes[p]) label[ids[j]] = p;
+    if ((int)j - pt_run_start(lab, (int)j) < cap - sizes[p]) label[ids[j]] = p;
 }
 __global__ __launch_bounds__(256) void pt_count_open_kernel(int nlabels, const int *__restrict__ sizes, int cap,
                                                             int *__restrict__ out) {
@@ -180,10 +206,6 @@ __global__ __launch_bounds__(256) void pt_count_open_kernel(int nlabels, const i
 }
 
 // ---- seeding --------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void pt_count_kernel(int n, const int *__restrict__ label, int *__restrict__ sizes) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) atomicAdd(&sizes[label[i]], 1);
-}
 // k[p] = seeds of an oversized part (0: not flagged), km1[p] = the labels it needs beyond its own; info[0] += flagged parts
 __global__ __launch_bounds__(256) void pt_over_kernel(int nlabels, const int *__restrict__ sizes, int max_size, int epa,
                                                       int *__restrict__ k, int *__restrict__ km1, int *__restrict__ info) {
@@ -227,23 +249,20 @@ __global__ __launch_bounds__(256) void pt_ball_min_kernel(int n, const roff_t *_
                                                           const int *__restrict__ state, unsigned seed,
                                                           const u64 *__restrict__ src, u64 *__restrict__ dst,
                                                           int *__restrict__ newseed) {
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    const long v = t / PT_LPR;
-    const int lane = (int)(t % PT_LPR);
-    const bool valid = v < n;
+    const RowLane r = row_lane(n);
+    const auto offer = [&](int u) { return FIRST ? (state[u] == PT_UNDECIDED ? (u64)pt_prio((unsigned)u, seed) : PT_NONE) : src[u]; };
     u64 best = PT_NONE;
-    if (valid) {
-        if (lane == 0) best = FIRST ? (state[v] == PT_UNDECIDED ? (u64)pt_prio((unsigned)v, seed) : PT_NONE) : src[v];
-        for (roff_t k = xadj[v] + lane, e = xadj[v + 1]; k < e; k += PT_LPR) {
-            const int u = adj[k];
-            const u64 key = FIRST ? (state[u] == PT_UNDECIDED ? (u64)pt_prio((unsigned)u, seed) : PT_NONE) : src[u];
+    if (r.valid) {
+        if (r.lane == 0) best = offer((int)r.v);
+        row_entries(xadj, r.v, r.lane, [&](roff_t k) {
+            const u64 key = offer(adj[k]);
             best = key < best ? key : best;
-        }
+        });
     }
-    best = group_min_u64(best);
-    if (valid && lane == 0) {
-        if (LAST) newseed[v] = state[v] == PT_UNDECIDED && best == (u64)pt_prio((unsigned)v, seed);
-        else dst[v] = best;
+    best = group_reduce<PT_LPR>(best, OpMin());
+    if (r.valid && r.lane == 0) {
+        if (LAST) newseed[r.v] = state[r.v] == PT_UNDECIDED && best == (u64)pt_prio((unsigned)r.v, seed);
+        else dst[r.v] = best;
     }
 }
 // One hop of the flag's ball sweep.  LAST: the flag is not stored; an undecided node becomes `seedval` when it is a new seed
@@ -253,21 +272,18 @@ __global__ __launch_bounds__(256) void pt_ball_flag_kernel(int n, const roff_t *
                                                            const int *__restrict__ src, int *__restrict__ dst,
                                                            const int *__restrict__ newseed, int seedval,
                                                            int *__restrict__ state, int *__restrict__ counters) {
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    const long v = t / PT_LPR;
-    const int lane = (int)(t % PT_LPR);
-    const bool valid = v < n;
+    const RowLane r = row_lane(n);
     int f = 0;
-    if (valid) {
-        if (lane == 0) f = src[v];
-        for (roff_t k = xadj[v] + lane, e = xadj[v + 1]; k < e; k += PT_LPR) f |= src[adj[k]];
+    if (r.valid) {
+        if (r.lane == 0) f = src[r.v];
+        row_entries(xadj, r.v, r.lane, [&](roff_t k) { f |= src[adj[k]]; });
     }
-    f = group_or(f);
-    if (valid && lane == 0) {
-        if (!LAST) dst[v] = f;
-        else if (state[v] == PT_UNDECIDED) {
-            if (newseed[v]) { state[v] = seedval; atomicAdd(&counters[0], 1); }
-            else if (f) state[v] = PT_OUT;
+    f = group_reduce<PT_LPR>(f, OpOr());
+    if (r.valid && r.lane == 0) {
+        if (!LAST) dst[r.v] = f;
+        else if (state[r.v] == PT_UNDECIDED) {
+            if (newseed[r.v]) { state[r.v] = seedval; atomicAdd(&counters[0], 1); }
+            else if (f) state[r.v] = PT_OUT;
             else atomicAdd(&counters[1], 1);
         }
     }
@@ -313,37 +329,31 @@ __global__ __launch_bounds__(256) void pt_spaced_label_kernel(int n, const u64 *
 // ---- recentring -----------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void pt_boundary_kernel(int n, const roff_t *__restrict__ xadj, const int *__restrict__ adj,
                                                           const int *__restrict__ label, int *__restrict__ depth) {
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    const long v = t / PT_LPR;
-    const int lane = (int)(t % PT_LPR);
-    const bool valid = v < n;
+    const RowLane r = row_lane(n);
     int b = 0;
-    if (valid) {
-        const int lv = label[v];
-        for (roff_t k = xadj[v] + lane, e = xadj[v + 1]; k < e; k += PT_LPR) b |= label[adj[k]] != lv;
+    if (r.valid) {
+        const int lv = label[r.v];
+        row_entries(xadj, r.v, r.lane, [&](roff_t k) { b |= label[adj[k]] != lv; });
     }
-    b = group_or(b);
-    if (valid && lane == 0) depth[v] = b ? 0 : -1;
+    b = group_reduce<PT_LPR>(b, OpOr());
+    if (r.valid && r.lane == 0) depth[r.v] = b ? 0 : -1;
 }
 // In place: a node without depth takes d when a neighbour of its part has d - 1.  A depth written in this launch is d, never
 // d - 1, so what a concurrent reader sees of it does not change the outcome.
 __global__ __launch_bounds__(256) void pt_depth_kernel(int n, const roff_t *__restrict__ xadj, const int *__restrict__ adj,
                                                        const int *__restrict__ label, int d, int *depth,
                                                        int *__restrict__ counters) {
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    const long v = t / PT_LPR;
-    const int lane = (int)(t % PT_LPR);
-    const bool valid = v < n;
+    const RowLane r = row_lane(n);
     int hit = 0;
-    if (valid && depth[v] < 0) {
-        const int lv = label[v];
-        for (roff_t k = xadj[v] + lane, e = xadj[v + 1]; k < e; k += PT_LPR) {
+    if (r.valid && depth[r.v] < 0) {
+        const int lv = label[r.v];
+        row_entries(xadj, r.v, r.lane, [&](roff_t k) {
             const int u = adj[k];
             hit |= label[u] == lv && depth[u] == d - 1;
-        }
+        });
     }
-    hit = group_or(hit);
-    if (valid && lane == 0 && hit) { depth[v] = d; atomicAdd(&counters[0], 1); }
+    hit = group_reduce<PT_LPR>(hit, OpOr());
+    if (r.valid && r.lane == 0 && hit) { depth[r.v] = d; atomicAdd(&counters[0], 1); }
 }
 __device__ inline u64 centre_key(int depth, unsigned prio) { return ((u64)(unsigned)(depth + 1) << 32) | (0xFFFFFFFFu - prio); }
 __global__ __launch_bounds__(256) void pt_centre_max_kernel(int n, const int *__restrict__ label, const int *__restrict__ depth,
@@ -369,27 +379,24 @@ __global__ __launch_bounds__(256) void pt_centre_pick_kernel(int n, int *__restr
 __global__ __launch_bounds__(256) void pt_propose_kernel(int n, const roff_t *__restrict__ xadj, const int *__restrict__ adj,
                                                          const int *__restrict__ label, const int *__restrict__ sizes,
                                                          int min_size, int max_size, u64 *__restrict__ prop) {
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    const long v = t / PT_LPR;
-    const int lane = (int)(t % PT_LPR);
-    const bool valid = v < n;
+    const RowLane r = row_lane(n);
     u64 best = PT_NONE;
     int lp = 0;
-    if (valid) {
-        lp = label[v];
+    if (r.valid) {
+        lp = label[r.v];
         const int sp = sizes[lp];
         if (sp < min_size)
-            for (roff_t k = xadj[v] + lane, e = xadj[v + 1]; k < e; k += PT_LPR) {
+            row_entries(xadj, r.v, r.lane, [&](roff_t k) {
                 const int lq = label[adj[k]];
-                if (lq == lp) continue;
+                if (lq == lp) return;
                 const int sq = sizes[lq];
-                if (max_size > 0 && sp + sq > max_size) continue;
+                if (max_size > 0 && sp + sq > max_size) return;
                 const u64 key = ((u64)(unsigned)sq << 32) | (unsigned)lq;
                 best = key < best ? key : best;
-            }
+            });
     }
-    best = group_min_u64(best);
-    if (valid && lane == 0 && best != PT_NONE) atomicMin(&prop[lp], best);
+    best = group_reduce<PT_LPR>(best, OpMin());
+    if (r.valid && r.lane == 0 && best != PT_NONE) atomicMin(&prop[lp], best);
 }
 __global__ __launch_bounds__(256) void pt_win_kernel(int nlabels, const u64 *__restrict__ prop, const int *__restrict__ sizes,
                                                      u64 *__restrict__ win) {
@@ -441,12 +448,7 @@ __global__ __launch_bounds__(256) void pt_apply_kernel(int n, const int *__restr
 
 // ---- boundary refinement (partition_model.py, "refine") ---------------------------------------------------------------------
 constexpr int PT_REFINE_DEG_MAX = 1024, PT_REFINE_LOCAL_MAX = 64, PT_GAIN_MAX = 65535;
-constexpr int PT_WAVE = 64;
 
-__device__ inline u64 group_max_u64(u64 v) {
-    for (int m = PT_LPR / 2; m; m >>= 1) { const u64 o = shfl_xor_u64(v, m); v = o > v ? o : v; }
-    return v;
-}
 // The counts.  One sweep gives own(v); a row with a foreign neighbour that can still be a candidate (own >= 1, its part above
 // the floor, at most PT_REFINE_DEG_MAX entries) is swept again, now from the cache: every foreign entry counts the entries of
 // its label, and the maximum of (count, -label) is the target.  Rows with gain > 0 whose target has room are compacted in any
@@ -456,42 +458,39 @@ __global__ __launch_bounds__(256) void pt_refine_count_kernel(int n, const roff_
                                                               int max_size, int floor_size, int *__restrict__ target,
                                                               int *__restrict__ gain, int *__restrict__ cand,
                                                               int *__restrict__ counters) {
-    const long t = (long)blockIdx.x * 256 + threadIdx.x;
-    const long v = t / PT_LPR;
-    const int lane = (int)(t % PT_LPR);
-    const bool valid = v < n;
-    const roff_t b = valid ? xadj[v] : 0, e = valid ? xadj[v + 1] : 0;
-    const int p = valid ? label[v] : 0;
+    const RowLane r = row_lane(n);
+    const roff_t b = r.valid ? xadj[r.v] : 0, e = r.valid ? xadj[r.v + 1] : 0;   // (the degree enters below: read once)
+    const int p = r.valid ? label[r.v] : 0;
     int own = 0, foreign = 0;
-    for (roff_t k = b + lane; k < e; k += PT_LPR) {
+    row_entries(b, e, r.lane, [&](roff_t k) {
         const int u = adj[k];
-        if (u == (int)v) continue;
+        if (u == (int)r.v) return;
         const int lu = label[u];
         own += lu == p;
         foreign |= lu != p;
-    }
-    own = group_sum(own);
-    foreign = group_or(foreign);
-    const bool second = valid && foreign && own >= 1 && e - b <= PT_REFINE_DEG_MAX && sizes[p] > floor_size;
+    });
+    own = group_reduce<PT_LPR>(own, OpSum());
+    foreign = group_reduce<PT_LPR>(foreign, OpOr());
+    const bool second = r.valid && foreign && own >= 1 && e - b <= PT_REFINE_DEG_MAX && sizes[p] > floor_size;
     u64 best = 0;
     if (second)
-        for (roff_t k = b + lane; k < e; k += PT_LPR) {
+        row_entries(b, e, r.lane, [&](roff_t k) {
             const int q = label[adj[k]];
-            if (q == p) continue;      // (the entry v itself has the label p)
+            if (q == p) return;      // (the entry v itself has the label p)
             int c = 0;
             for (roff_t j = b; j < e; ++j) c += label[adj[j]] == q;
             const u64 key = ((u64)(unsigned)c << 32) | (0xFFFFFFFFu - (unsigned)q);
             best = key > best ? key : best;
-        }
-    best = group_max_u64(best);
-    if (second && lane == 0) {
+        });
+    best = group_reduce<PT_LPR>(best, OpMax());
+    if (second && r.lane == 0) {
         const int q = (int)(0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull));
         const int g = (int)(best >> 32) - own;
         if (g > 0 && (max_size == 0 || sizes[q] < max_size)) {
             const int j = atomicAdd(&counters[0], 1);
-            cand[j] = (int)v;
-            target[v] = q;
-            gain[v] = g;
+            cand[j] = (int)r.v;
+            target[r.v] = q;
+            gain[r.v] = g;
         }
     }
 }
@@ -565,9 +564,7 @@ __global__ __launch_bounds__(256) void pt_refine_free_kernel(const roff_t *__res
             const u64 all = cnt == 64 ? ~0ull : (1ull << cnt) - 1ull;
             u64 reach = 1ull;
             for (;;) {
-                u64 nr = ((reach >> lane) & 1ull) ? mask : 0ull;
-                for (int mm = PT_WAVE / 2; mm; mm >>= 1) nr |= shfl_xor_u64(nr, mm);
-                nr |= reach;
+                const u64 nr = group_reduce<PT_WAVE>(((reach >> lane) & 1ull) ? mask : 0ull, OpOr()) | reach;
                 if (nr == reach) break;
                 reach = nr;
             }
@@ -608,16 +605,6 @@ __global__ __launch_bounds__(256) void pt_refine_target_kernel(int m, const int 
                                                                int *__restrict__ lab, int *__restrict__ pos) {
     const long j = (long)blockIdx.x * 256 + threadIdx.x;
     if (j < m) { lab[j] = target[ids[j]]; pos[j] = (int)j; }
-}
-__device__ inline int pt_run_start(const int *lab, int j) {
-    const int p = lab[j];
-    int lo = 0, hi = j;
-    while (lo < hi) {
-        const int mid = lo + (hi - lo) / 2;
-        if (lab[mid] < p) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
 }
 // lab ascending, the winners of one target in their order: the first max_size - size are admitted (all without a cap).  The
 // answer goes to the winner's place in key order, with the label of its source, or nparts when it is not admitted.
@@ -774,34 +761,88 @@ __global__ __launch_bounds__(256) void pt_check_dofs_kernel(long nconn, int ND, 
     if (k < nconn && (J[k] < 0 || J[k] >= ND)) atomicOr(err, 2);
 }
 
-template <class T>
-T read_one(const T *p, hipStream_t s) {
-    T v;
-    SA_HIP_CHECK(hipMemcpyAsync(&v, p, sizeof(T), hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
-    return v;
-}
-void fill_int(hipStream_t s, long n, int v, int *a) {
-    if (!n) return;
-    hipLaunchKernelGGL(pt_fill_int_kernel, grid_flat(n), dim3(256), 0, s, n, v, a);
-}
-void fill_u64(hipStream_t s, long n, u64 v, u64 *a) {
-    if (!n) return;
-    hipLaunchKernelGGL(pt_fill_u64_kernel, grid_flat(n), dim3(256), 0, s, n, v, a);
-}
-
-struct Grower {
+// ---- launches ---------------------------------------------------------------------------------------------------------
+// the graph of a call with its stream and the seed of its priorities: what the row sweeps are launched with
+struct GraphView {
     hipStream_t s;
     int n;
     const roff_t *xadj;
     const int *adj;
     unsigned seed;
+};
+// one group of PT_LPR lanes per row: kernel(n, xadj, adj, args...)
+template <class K, class... A>
+void sweep(const GraphView &g, K kernel, A... args) {
+    hipLaunchKernelGGL(kernel, grid_rows(g.n), dim3(256), 0, g.s, g.n, g.xadj, g.adj, args...);
+    SA_HIP_CHECK(hipGetLastError());
+}
+// one thread per item: kernel(count, args...)
+template <class K, class... A>
+void flat(hipStream_t s, long count, K kernel, A... args) {
+    hipLaunchKernelGGL(kernel, grid_flat(count), dim3(256), 0, s, count, args...);
+    SA_HIP_CHECK(hipGetLastError());
+}
+void fill_int(hipStream_t s, long n, int v, int *a) {
+    if (n) flat(s, n, pt_fill_int_kernel, v, a);
+}
+void fill_u64(hipStream_t s, long n, u64 v, u64 *a) {
+    if (n) flat(s, n, pt_fill_u64_kernel, v, a);
+}
+// one hop of a ball sweep; first / last pick the instantiation (state and newseed are read by those forms alone)
+void ball_min(const GraphView &g, bool first, bool last, const int *state, const u64 *src, u64 *dst, int *newseed) {
+    const auto kernel = first ? (last ? pt_ball_min_kernel<true, true> : pt_ball_min_kernel<true, false>)
+                              : (last ? pt_ball_min_kernel<false, true> : pt_ball_min_kernel<false, false>);
+    sweep(g, kernel, state, g.seed, src, dst, newseed);
+}
+void ball_flag(const GraphView &g, bool last, const int *src, int *dst, const int *newseed, int seedval, int *state,
+               int *counters) {
+    sweep(g, last ? pt_ball_flag_kernel<true> : pt_ball_flag_kernel<false>, src, dst, newseed, seedval, state, counters);
+}
+
+// The stable radix sorts of (key, value) pairs of one phase, u64 / int and int / int, at most n pairs each.  It owns the
+// sort's temporary storage, sized once by the library's queries for n pairs.
+class PairSorter {
+    hipStream_t s;
+    size_t tmp_bytes;
+    DBuf<char> tmp;
+    template <class K, class V>
+    size_t query(const K *kin, K *kout, const V *vin, V *vout, int m, int end_bit) const {   // (a host call, nothing is launched)
+        size_t b = 0;
+        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, b, kin, kout, vin, vout, m, 0, end_bit, s));
+        return b;
+    }
+
+  public:
+    // key_bits, label_bits: the widest bit range the phase sorts u64 keys and int keys over (0: it sorts none of these)
+    PairSorter(hipStream_t s_, int n, int key_bits, int label_bits = 0) : s(s_) {
+        const int *ci = nullptr;
+        int *i = nullptr;
+        tmp_bytes = query((const u64 *)nullptr, (u64 *)nullptr, ci, i, n, key_bits);
+        if (label_bits) tmp_bytes = std::max(tmp_bytes, query(ci, i, ci, i, n, label_bits));
+        tmp.alloc(tmp_bytes + 16);
+    }
+    // (kout, vout) = the first m <= n pairs of (kin, vin), stably ordered by the bits [0, end_bit) of the keys
+    template <class K, class V>
+    void sort(const K *kin, K *kout, const V *vin, V *vout, int m, int end_bit) {
+        // tmp was sized by the queries for n pairs and serves the m <= n of this call.  That rests on the assumption that the
+        // sort never asks for more temporary storage for fewer pairs or fewer bits; the library chooses its path by the count,
+        // so the assumption is checked by a query for this call and not relied on.
+        size_t b = query(kin, kout, vin, vout, m, end_bit);
+        SA_REQUIRE(b <= tmp_bytes, "partition: the sort asks for more temporary storage than the phase sized it for");
+        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs((void *)tmp.p, b, kin, kout, vin, vout, m, 0, end_bit, s));
+    }
+};
+
+struct Grower {
+    const GraphView g;
+    const hipStream_t s;   // = g.s
+    const int n;           // = g.n
     DBuf<int> a, b, isseed, counters;
     DBuf<u64> key;
     int *label = nullptr;  // a.p or b.p: the current labels
     int nlabels = 0;
-    Grower(hipStream_t s_, int n_, const roff_t *x, const int *j, unsigned seed_)
-        : s(s_), n(n_), xadj(x), adj(j), seed(seed_), a((size_t)n_), b((size_t)n_), isseed((size_t)n_), counters(2), key(1) {
+    explicit Grower(const GraphView &g_)
+        : g(g_), s(g_.s), n(g_.n), a((size_t)n), b((size_t)n), isseed((size_t)n), counters(2), key(1) {
         label = a.p;
         isseed.zero(s);
     }
@@ -809,15 +850,14 @@ struct Grower {
     void grow(const int *dom) {
         for (;;) {
             counters.zero(s);
-            hipLaunchKernelGGL(pt_grow_kernel, grid_rows(n), dim3(256), 0, s, n, xadj, adj, (const int *)label, dom, other(), counters.p);
-            SA_HIP_CHECK(hipGetLastError());
+            sweep(g, pt_grow_kernel, label, dom, other(), counters.p);
             label = other();
             const auto c = counters.to_host(s);
             if (c[1] == 0) return;
             if (c[0] == 0) {  // a component without a seed
                 fill_u64(s, 1, PT_NONE, key.p);
-                hipLaunchKernelGGL(pt_min_unlabelled_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)label, seed, key.p);
-                hipLaunchKernelGGL(pt_stall_seed_kernel, dim3(1), dim3(1), 0, s, (const u64 *)key.p, nlabels, label, isseed.p);
+                flat(s, n, pt_min_unlabelled_kernel, label, g.seed, key.p);
+                hipLaunchKernelGGL(pt_stall_seed_kernel, dim3(1), dim3(1), 0, s, key.p, nlabels, label, isseed.p);
                 SA_HIP_CHECK(hipGetLastError());
                 ++nlabels;
             }
@@ -830,19 +870,13 @@ struct Grower {
         DBuf<int> sizes((size_t)nlabels), claim((size_t)n), ids((size_t)n), ids2((size_t)n), lab((size_t)n), lab2((size_t)n);
         DBuf<u64> keys((size_t)n), keys2((size_t)n);
         const int lab_bits = pt_bits(nlabels);
-        size_t tb1 = 0, tb2 = 0;
-        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb1, keys.p, keys2.p, ids.p, ids2.p, n, 0, 48, s));
-        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb2, lab.p, lab2.p, ids2.p, ids.p, n, 0, lab_bits, s));
-        const size_t tmp_bytes = std::max(tb1, tb2);
-        DBuf<char> tmp(tmp_bytes + 16);
+        PairSorter sorter(s, n, 48, lab_bits);
         int first_unlabelled = -1;
         for (;;) {
             sizes.zero(s);
             counters.zero(s);
-            hipLaunchKernelGGL(pt_count_labelled_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)label, sizes.p);
-            hipLaunchKernelGGL(pt_claim_kernel, grid_rows(n), dim3(256), 0, s, n, xadj, adj, (const int *)label, (const int *)sizes.p,
-                               cap, seed, claim.p, keys.p, ids.p, counters.p);
-            SA_HIP_CHECK(hipGetLastError());
+            flat(s, n, pt_count_kernel, label, sizes.p);
+            sweep(g, pt_claim_kernel, label, sizes.p, cap, g.seed, claim.p, keys.p, ids.p, counters.p);
             const auto c = counters.to_host(s);
             const int m = c[0], unlabelled = c[1];
             if (first_unlabelled < 0) first_unlabelled = unlabelled;
@@ -851,27 +885,16 @@ struct Grower {
             if (m == 0) {   // release
                 DBuf<int> nopen(1);
                 nopen.zero(s);
-                hipLaunchKernelGGL(pt_count_open_kernel, grid_flat(nlabels), dim3(256), 0, s, nlabels, (const int *)sizes.p, cap, nopen.p);
-                SA_HIP_CHECK(hipGetLastError());
+                flat(s, nlabels, pt_count_open_kernel, sizes.p, cap, nopen.p);
                 st.open_parts = nopen.to_host(s)[0];
                 st.released_nodes = unlabelled;
                 break;
             }
             ++st.rounds;
-            // tmp was sized by the queries for n items and is reused for the m <= n of this round.  That rests on the assumption
-            // that the sort never asks for more temporary storage for fewer items; the library chooses its path by the count, so
-            // the assumption is checked by a query for m (a host call, nothing is launched) and not relied on.
-            size_t b1 = 0, b2 = 0;
-            SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, b1, keys.p, keys2.p, ids.p, ids2.p, m, 0, 48, s));
-            SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, b2, lab.p, lab2.p, ids2.p, ids.p, m, 0, lab_bits, s));
-            SA_REQUIRE(b1 <= tmp_bytes && b2 <= tmp_bytes, "balanced growth: the sort asks for more temporary storage for fewer items");
-            SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs((void *)tmp.p, b1, keys.p, keys2.p, ids.p, ids2.p, m, 0, 48, s));
-            hipLaunchKernelGGL(pt_claim_gather_kernel, grid_flat(m), dim3(256), 0, s, m, (const int *)ids2.p, (const int *)claim.p, lab.p);
-            SA_HIP_CHECK(hipGetLastError());
-            SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs((void *)tmp.p, b2, lab.p, lab2.p, ids2.p, ids.p, m, 0, lab_bits, s));
-            hipLaunchKernelGGL(pt_claim_apply_kernel, grid_flat(m), dim3(256), 0, s, m, (const int *)lab2.p, (const int *)ids.p,
-                               (const int *)sizes.p, cap, label);
-            SA_HIP_CHECK(hipGetLastError());
+            sorter.sort(keys.p, keys2.p, ids.p, ids2.p, m, 48);
+            flat(s, m, pt_claim_gather_kernel, ids2.p, claim.p, lab.p);
+            sorter.sort(lab.p, lab2.p, ids2.p, ids.p, m, lab_bits);
+            flat(s, m, pt_claim_apply_kernel, lab2.p, ids.p, sizes.p, cap, label);
         }
         SA_HIP_CHECK(hipStreamSynchronize(s));   // the temporaries go out of scope
         if (st.released_nodes) grow(nullptr);
@@ -881,8 +904,7 @@ struct Grower {
     void sizes_of(DBuf<int> &sizes) {
         sizes.alloc((size_t)nlabels + 1);
         sizes.zero(s);
-        hipLaunchKernelGGL(pt_count_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)label, sizes.p);
-        SA_HIP_CHECK(hipGetLastError());
+        flat(s, n, pt_count_kernel, label, sizes.p);
     }
     // the parts with k[p] > 0 are cleared down to their k[p] nodes of lowest priority; km1 = max(k - 1, 0)
     void reseed(const DBuf<int> &sizes, const DBuf<int> &k, const DBuf<int> &km1) {
@@ -891,16 +913,11 @@ struct Grower {
         exclusive_scan_int(s, nlabels, km1.p, off.p);
         DBuf<u64> keys((size_t)n), keys2((size_t)n);
         DBuf<int> ids((size_t)n), ids2((size_t)n);
-        hipLaunchKernelGGL(pt_sort_keys_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)label, seed, keys.p, ids.p);
-        SA_HIP_CHECK(hipGetLastError());
-        size_t tmp_bytes = 0;
+        flat(s, n, pt_sort_keys_kernel, label, g.seed, keys.p, ids.p);
         const int end_bit = 32 + pt_bits(nlabels);
-        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys.p, keys2.p, ids.p, ids2.p, n, 0, end_bit, s));
-        DBuf<char> tmp(tmp_bytes + 16);
-        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs((void *)tmp.p, tmp_bytes, keys.p, keys2.p, ids.p, ids2.p, n, 0, end_bit, s));
-        hipLaunchKernelGGL(pt_reseed_kernel, grid_flat(n), dim3(256), 0, s, n, (const u64 *)keys2.p, (const int *)ids2.p,
-                           (const int *)start.p, (const int *)k.p, (const int *)off.p, nlabels, label, isseed.p);
-        SA_HIP_CHECK(hipGetLastError());
+        PairSorter sorter(s, n, end_bit);
+        sorter.sort(keys.p, keys2.p, ids.p, ids2.p, n, end_bit);
+        flat(s, n, pt_reseed_kernel, keys2.p, ids2.p, start.p, k.p, off.p, nlabels, label, isseed.p);
         nlabels += read_one(off.p + nlabels, s);  // (synchronises: the temporaries go out of scope)
     }
     // Spaced first seeding.  One independent set: rounds of r min sweeps, the decision and r flag sweeps, one read of the
@@ -910,22 +927,10 @@ struct Grower {
         DBuf<u64> ka, kb;
     };
     int independent_set(Spaced &w, int r, int seedval, int limit, int &rounds) {
-        const int *st = w.state.p;
         int found = 0;
         for (;;) {
-            for (int j = 1; j <= r; ++j) {
-                const u64 *src = j % 2 ? w.kb.p : w.ka.p;   // (not read by the first sweep)
-                u64 *dst = j % 2 ? w.ka.p : w.kb.p;
-                if (j == 1 && j == r)
-                    hipLaunchKernelGGL((pt_ball_min_kernel<true, true>), grid_rows(n), dim3(256), 0, s, n, xadj, adj, st, seed, src, dst, w.newseed.p);
-                else if (j == 1)
-                    hipLaunchKernelGGL((pt_ball_min_kernel<true, false>), grid_rows(n), dim3(256), 0, s, n, xadj, adj, st, seed, src, dst, w.newseed.p);
-                else if (j == r)
-                    hipLaunchKernelGGL((pt_ball_min_kernel<false, true>), grid_rows(n), dim3(256), 0, s, n, xadj, adj, st, seed, src, dst, w.newseed.p);
-                else
-                    hipLaunchKernelGGL((pt_ball_min_kernel<false, false>), grid_rows(n), dim3(256), 0, s, n, xadj, adj, st, seed, src, dst, w.newseed.p);
-            }
-            SA_HIP_CHECK(hipGetLastError());
+            for (int j = 1; j <= r; ++j)   // (the first sweep reads no src, the last writes no dst)
+                ball_min(g, j == 1, j == r, w.state.p, j % 2 ? w.kb.p : w.ka.p, j % 2 ? w.ka.p : w.kb.p, w.newseed.p);
             counters.zero(s);
             spread(w, r, seedval);
             const auto c = counters.to_host(s);
@@ -936,15 +941,9 @@ struct Grower {
     }
     // r flag sweeps from newseed; the last one applies the round to the states and counts
     void spread(Spaced &w, int r, int seedval) {
-        for (int j = 1; j <= r; ++j) {
-            const int *src = j == 1 ? w.newseed.p : (j % 2 ? w.fb.p : w.fa.p);
-            int *dst = j % 2 ? w.fa.p : w.fb.p;
-            if (j == r)
-                hipLaunchKernelGGL(pt_ball_flag_kernel<true>, grid_rows(n), dim3(256), 0, s, n, xadj, adj, src, dst, (const int *)w.newseed.p, seedval, w.state.p, counters.p);
-            else
-                hipLaunchKernelGGL(pt_ball_flag_kernel<false>, grid_rows(n), dim3(256), 0, s, n, xadj, adj, src, dst, (const int *)w.newseed.p, seedval, w.state.p, counters.p);
-        }
-        SA_HIP_CHECK(hipGetLastError());
+        for (int j = 1; j <= r; ++j)
+            ball_flag(g, j == r, j == 1 ? w.newseed.p : (j % 2 ? w.fb.p : w.fa.p), j % 2 ? w.fa.p : w.fb.p, w.newseed.p, seedval,
+                      w.state.p, counters.p);
     }
     SeedingStats seed_spaced(int target) {
         SeedingStats st;
@@ -963,8 +962,7 @@ struct Grower {
         }
         int ne = 0;
         if (ns < target) {   // top-up from the greedy (r - 1)-independent extension
-            hipLaunchKernelGGL(pt_ext_init_kernel, grid_flat(n), dim3(256), 0, s, n, r == 1 ? PT_EXT : PT_UNDECIDED, w.state.p, w.newseed.p);
-            SA_HIP_CHECK(hipGetLastError());
+            flat(s, n, pt_ext_init_kernel, r == 1 ? PT_EXT : PT_UNDECIDED, w.state.p, w.newseed.p);
             if (r == 1) ne = n - ns;
             else {
                 counters.zero(s);
@@ -975,16 +973,11 @@ struct Grower {
         const int nsel = ns < target ? std::min(target, ns + ne) : ns;
         DBuf<u64> keys((size_t)n), keys2((size_t)n);
         DBuf<int> ids((size_t)n), ids2((size_t)n);
-        hipLaunchKernelGGL(pt_spaced_keys_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)w.state.p, seed, keys.p, ids.p);
-        SA_HIP_CHECK(hipGetLastError());
-        size_t tmp_bytes = 0;
-        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys.p, keys2.p, ids.p, ids2.p, n, 0, 34, s));
-        DBuf<char> tmp(tmp_bytes + 16);
-        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs((void *)tmp.p, tmp_bytes, keys.p, keys2.p, ids.p, ids2.p, n, 0, 34, s));
+        flat(s, n, pt_spaced_keys_kernel, w.state.p, g.seed, keys.p, ids.p);
+        PairSorter sorter(s, n, 34);
+        sorter.sort(keys.p, keys2.p, ids.p, ids2.p, n, 34);
         label = a.p;
-        hipLaunchKernelGGL(pt_spaced_label_kernel, grid_flat(n), dim3(256), 0, s, n, (const u64 *)keys2.p, (const int *)ids2.p, ns, nsel,
-                           label, isseed.p);
-        SA_HIP_CHECK(hipGetLastError());
+        flat(s, n, pt_spaced_label_kernel, keys2.p, ids2.p, ns, nsel, label, isseed.p);
         SA_HIP_CHECK(hipStreamSynchronize(s));   // the temporaries go out of scope
         nlabels = nsel;
         st.radius = r;
@@ -994,21 +987,16 @@ struct Grower {
     }
     void recentre() {
         DBuf<int> depth((size_t)n);
-        hipLaunchKernelGGL(pt_boundary_kernel, grid_rows(n), dim3(256), 0, s, n, xadj, adj, (const int *)label, depth.p);
-        SA_HIP_CHECK(hipGetLastError());
+        sweep(g, pt_boundary_kernel, label, depth.p);
         for (int d = 1;; ++d) {
             counters.zero(s);
-            hipLaunchKernelGGL(pt_depth_kernel, grid_rows(n), dim3(256), 0, s, n, xadj, adj, (const int *)label, d, depth.p, counters.p);
-            SA_HIP_CHECK(hipGetLastError());
+            sweep(g, pt_depth_kernel, label, d, depth.p, counters.p);
             if (counters.to_host(s)[0] == 0) break;
         }
         DBuf<u64> best((size_t)nlabels);
         best.zero(s);
-        hipLaunchKernelGGL(pt_centre_max_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)label, (const int *)depth.p,
-                           (const int *)isseed.p, seed, best.p);
-        hipLaunchKernelGGL(pt_centre_pick_kernel, grid_flat(n), dim3(256), 0, s, n, label, (const int *)depth.p, isseed.p, seed,
-                           (const u64 *)best.p);
-        SA_HIP_CHECK(hipGetLastError());
+        flat(s, n, pt_centre_max_kernel, label, depth.p, isseed.p, g.seed, best.p);
+        flat(s, n, pt_centre_pick_kernel, label, depth.p, isseed.p, g.seed, best.p);
         SA_HIP_CHECK(hipStreamSynchronize(s));
     }
     bool merge_round(int min_size, int max_size) {
@@ -1018,13 +1006,10 @@ struct Grower {
         fill_u64(s, nlabels, PT_NONE, prop.p);
         fill_u64(s, nlabels, PT_NONE, win.p);
         info.zero(s);
-        hipLaunchKernelGGL(pt_propose_kernel, grid_rows(n), dim3(256), 0, s, n, xadj, adj, (const int *)label, (const int *)sizes.p,
-                           min_size, max_size, prop.p);
-        hipLaunchKernelGGL(pt_win_kernel, grid_flat(nlabels), dim3(256), 0, s, nlabels, (const u64 *)prop.p, (const int *)sizes.p, win.p);
-        hipLaunchKernelGGL(pt_decide_kernel, grid_flat(nlabels), dim3(256), 0, s, nlabels, (const u64 *)prop.p, (const u64 *)win.p,
-                           target.p, info.p);
-        hipLaunchKernelGGL(pt_relabel_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)target.p, label);
-        SA_HIP_CHECK(hipGetLastError());
+        sweep(g, pt_propose_kernel, label, sizes.p, min_size, max_size, prop.p);
+        flat(s, nlabels, pt_win_kernel, prop.p, sizes.p, win.p);
+        flat(s, nlabels, pt_decide_kernel, prop.p, win.p, target.p, info.p);
+        flat(s, n, pt_relabel_kernel, target.p, label);
         return info.to_host(s)[0] != 0;
     }
 };
@@ -1032,27 +1017,17 @@ struct Grower {
 constexpr int PT_MERGE_ROUNDS = 8;
 constexpr int PT_REPAIR_ROUNDS = 32;
 
-thread_local SeedingStats t_seeding_stats;
-thread_local GrowthStats t_growth_stats;
-thread_local RefineStats t_refine_stats;
-
 }  // namespace
-
-SeedingStats last_seeding_stats() { return t_seeding_stats; }
-GrowthStats last_growth_stats() { return t_growth_stats; }
-RefineStats last_refine_stats() { return t_refine_stats; }
 
 int64_t check_graph_device(hipStream_t s, int n, const roff_t *xadj, const int *adj) {
     if (n == 0) return 0;
     DBuf<int> err(1);
     err.zero(s);
-    hipLaunchKernelGGL(pt_check_xadj_kernel, grid_flat(n), dim3(256), 0, s, n, xadj, err.p);
-    SA_HIP_CHECK(hipGetLastError());
+    flat(s, n, pt_check_xadj_kernel, xadj, err.p);
     SA_REQUIRE(!err.to_host(s)[0], "xadj: must start at 0 and ascend");
     const roff_t nnz = read_one(xadj + n, s);
     SA_REQUIRE(nnz == 0 || adj, "null argument: adj");
-    hipLaunchKernelGGL(pt_check_adj_kernel, grid_flat(n), dim3(256), 0, s, n, xadj, adj, err.p);
-    SA_HIP_CHECK(hipGetLastError());
+    flat(s, n, pt_check_adj_kernel, xadj, adj, err.p);
     const int bits = err.to_host(s)[0];
     SA_REQUIRE(!(bits & 2), "adj: entry outside [0, n)");
     SA_REQUIRE(!(bits & 4), "graph is not symmetric: an entry without its transpose");
@@ -1063,37 +1038,38 @@ long check_mesh_device(hipStream_t s, int NE, const int *e2d_I, const int *e2d_J
     if (NE == 0) return 0;
     DBuf<int> err(1);
     err.zero(s);
-    hipLaunchKernelGGL(pt_check_eptr_kernel, grid_flat(NE), dim3(256), 0, s, NE, e2d_I, err.p);
-    SA_HIP_CHECK(hipGetLastError());
+    flat(s, NE, pt_check_eptr_kernel, e2d_I, err.p);
     SA_REQUIRE(!err.to_host(s)[0], "elem_ptr: must start at 0 and every element needs a dof");
     const long nconn = read_one(e2d_I + NE, s);
-    hipLaunchKernelGGL(pt_check_dofs_kernel, grid_flat(nconn), dim3(256), 0, s, nconn, ND, e2d_J, err.p);
-    SA_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(pt_check_repeat_kernel, grid_flat(NE), dim3(256), 0, s, NE, e2d_I, e2d_J, err.p);
-    SA_HIP_CHECK(hipGetLastError());
+    flat(s, nconn, pt_check_dofs_kernel, ND, e2d_J, err.p);
+    flat(s, NE, pt_check_repeat_kernel, e2d_I, e2d_J, err.p);
     const int bits = err.to_host(s)[0];
     SA_REQUIRE(!(bits & 2), "elem_to_dof entry out of range");
     SA_REQUIRE(!(bits & 4), "elem_to_dof: an element lists a dof twice");
     return nconn;
 }
 
+void resolve_partition_sizes(int epa, const PartitionOptions &o, int *max_size, int *min_size) {
+    *max_size = o.max_size < 0 ? (int)std::min<int64_t>(2ll * epa, INT_MAX) : o.max_size;
+    *min_size = o.min_size < 0 ? epa / 4 : o.min_size;
+}
+
 void partition_graph_device(hipStream_t s, int n, const roff_t *xadj, const int *adj, int epa, const PartitionOptions &o,
-                            int *part, int *nparts_out) {
+                            int *part, int *nparts_out, PartitionStats *stats) {
     SA_REQUIRE(n >= 0, "n < 0");
     SA_REQUIRE(epa >= 1, "elems_per_agg < 1");
     SA_REQUIRE(o.lloyd_iters >= 0 && o.max_size >= -1 && o.min_size >= -1, "partition options: lloyd_iters >= 0, sizes >= -1");
     SA_REQUIRE(o.seeding == 0 || o.seeding == 1, "partition options: seeding must be 0 or 1");
     SA_REQUIRE(o.growth == 0 || o.growth == 1, "partition options: growth must be 0 or 1");
     *nparts_out = 0;
-    t_seeding_stats = SeedingStats();
-    t_growth_stats = GrowthStats();
+    *stats = PartitionStats();
     if (n == 0) return;
-    const int max_size = o.max_size < 0 ? (int)std::min<int64_t>(2ll * epa, INT_MAX) : o.max_size;
-    const int min_size = o.min_size < 0 ? epa / 4 : o.min_size;
-    Grower g(s, n, xadj, adj, o.seed);
+    int max_size = 0, min_size = 0;
+    resolve_partition_sizes(epa, o, &max_size, &min_size);
+    Grower g(GraphView{s, n, xadj, adj, o.seed});
     const int target = (int)(((int64_t)n + epa - 1) / epa);
     if (o.seeding == 1) {
-        t_seeding_stats = g.seed_spaced(target);
+        stats->seeding = g.seed_spaced(target);
     } else {   // first seeding: one part 0 that holds every node, target seeds
         g.label = g.a.p;
         g.a.zero(s);
@@ -1107,7 +1083,7 @@ void partition_graph_device(hipStream_t s, int n, const roff_t *xadj, const int 
         g.reseed(sizes, k, km1);
     }
     const auto grow = [&] {
-        if (o.growth == 1) t_growth_stats = g.grow_balanced(epa);
+        if (o.growth == 1) stats->growth = g.grow_balanced(epa);
         else g.grow(nullptr);
     };
     grow();
@@ -1120,9 +1096,7 @@ void partition_graph_device(hipStream_t s, int n, const roff_t *xadj, const int 
             DBuf<int> sizes, k((size_t)g.nlabels), km1((size_t)g.nlabels + 1), info(1);
             g.sizes_of(sizes);
             info.zero(s);
-            hipLaunchKernelGGL(pt_over_kernel, grid_flat(g.nlabels), dim3(256), 0, s, g.nlabels, (const int *)sizes.p, max_size, epa,
-                               k.p, km1.p, info.p);
-            SA_HIP_CHECK(hipGetLastError());
+            flat(s, g.nlabels, pt_over_kernel, sizes.p, max_size, epa, k.p, km1.p, info.p);
             if (info.to_host(s)[0] == 0) break;
             DBuf<int> old((size_t)n);
             SA_HIP_CHECK(hipMemcpyAsync(old.p, g.label, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, s));
@@ -1136,23 +1110,15 @@ void partition_graph_device(hipStream_t s, int n, const roff_t *xadj, const int 
     renumber_device(s, n, g.label, g.nlabels, part, nparts_out);
 }
 
-void resolve_partition_sizes(int epa, const PartitionOptions &o, int *max_size, int *min_size) {
-    *max_size = o.max_size < 0 ? (int)std::min<int64_t>(2ll * epa, INT_MAX) : o.max_size;
-    *min_size = o.min_size < 0 ? epa / 4 : o.min_size;
-}
-
 // parts numbered by their smallest member; label and part are different arrays
 void renumber_device(hipStream_t s, int n, const int *label, int nlabels, int *part, int *nparts_out) {
     DBuf<int> minid((size_t)nlabels), first((size_t)n), rank((size_t)n + 1), newnum((size_t)nlabels);
     fill_int(s, nlabels, n, minid.p);
-    hipLaunchKernelGGL(pt_minid_kernel, grid_flat(n), dim3(256), 0, s, n, label, minid.p);
-    hipLaunchKernelGGL(pt_first_kernel, grid_flat(n), dim3(256), 0, s, n, label, (const int *)minid.p, first.p);
-    SA_HIP_CHECK(hipGetLastError());
+    flat(s, n, pt_minid_kernel, label, minid.p);
+    flat(s, n, pt_first_kernel, label, minid.p, first.p);
     exclusive_scan_int(s, n, first.p, rank.p);
-    hipLaunchKernelGGL(pt_newnum_kernel, grid_flat(n), dim3(256), 0, s, n, label, (const int *)first.p,
-                       (const int *)rank.p, newnum.p);
-    hipLaunchKernelGGL(pt_apply_kernel, grid_flat(n), dim3(256), 0, s, n, label, (const int *)newnum.p, part);
-    SA_HIP_CHECK(hipGetLastError());
+    flat(s, n, pt_newnum_kernel, label, first.p, rank.p, newnum.p);
+    flat(s, n, pt_apply_kernel, label, newnum.p, part);
     *nparts_out = read_one(rank.p + n, s);
 }
 
@@ -1162,9 +1128,8 @@ void check_partition_device(hipStream_t s, int n, const int *label, int nparts) 
     DBuf<int> sizes((size_t)nparts), err(1);
     sizes.zero(s);
     err.zero(s);
-    hipLaunchKernelGGL(pt_check_labels_kernel, grid_flat(n), dim3(256), 0, s, n, label, nparts, sizes.p, err.p);
-    hipLaunchKernelGGL(pt_check_empty_kernel, grid_flat(nparts), dim3(256), 0, s, nparts, (const int *)sizes.p, err.p);
-    SA_HIP_CHECK(hipGetLastError());
+    flat(s, n, pt_check_labels_kernel, label, nparts, sizes.p, err.p);
+    flat(s, nparts, pt_check_empty_kernel, sizes.p, err.p);
     const int bits = err.to_host(s)[0];
     SA_REQUIRE(!(bits & 1), "part: label outside [0, nparts)");
     SA_REQUIRE(!(bits & 2), "part: an empty part");
@@ -1177,62 +1142,43 @@ RefineStats refine_partition_device(hipStream_t s, int n, const roff_t *xadj, co
                                     int max_size, int min_size, unsigned seed) {
     SA_REQUIRE(rounds >= 0 && max_size >= 0 && min_size >= 0, "refinement: rounds, max_size and min_size must be >= 0");
     RefineStats st;
-    t_refine_stats = st;
     if (n == 0 || rounds == 0) return st;
+    const GraphView g{s, n, xadj, adj, seed};
     const int floor_size = std::max(min_size, 1);
     DBuf<int> sizes((size_t)nparts), target((size_t)n), gain((size_t)n), cand((size_t)n), counters(3);
     DBuf<int> ids((size_t)n), ids2((size_t)n), lab((size_t)n), lab2((size_t)n), pos((size_t)n), pos2((size_t)n);
     DBuf<u64> key((size_t)n), ka((size_t)n), kb((size_t)n), wkeys((size_t)n), wkeys2((size_t)n), totals(2);
     const int lab_bits = pt_bits(nparts + 1);
-    size_t tb1 = 0, tb2 = 0;
-    SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb1, wkeys.p, wkeys2.p, ids.p, ids2.p, n, 0, 48, s));
-    SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb2, lab.p, lab2.p, pos.p, pos2.p, n, 0, lab_bits, s));
-    const size_t tmp_bytes = std::max(tb1, tb2);
-    DBuf<char> tmp(tmp_bytes + 16);
+    PairSorter sorter(s, n, 48, lab_bits);
     totals.zero(s);
     const dim3 free_grid((unsigned)std::min<long>(((long)n + 3) / 4, 2048));
     while (st.rounds < rounds) {
         sizes.zero(s);
         counters.zero(s);
         fill_u64(s, n, PT_NONE, key.p);
-        hipLaunchKernelGGL(pt_count_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)label, sizes.p);
-        hipLaunchKernelGGL(pt_refine_count_kernel, grid_rows(n), dim3(256), 0, s, n, xadj, adj, (const int *)label, (const int *)sizes.p,
-                           max_size, floor_size, target.p, gain.p, cand.p, counters.p);
-        hipLaunchKernelGGL(pt_refine_free_kernel, free_grid, dim3(256), 0, s, xadj, adj, (const int *)label, (const int *)cand.p,
-                           (const int *)gain.p, seed, key.p, counters.p);
-        hipLaunchKernelGGL((pt_ball_min_kernel<false, false>), grid_rows(n), dim3(256), 0, s, n, xadj, adj, (const int *)nullptr, seed,
-                           (const u64 *)key.p, ka.p, (int *)nullptr);
-        hipLaunchKernelGGL((pt_ball_min_kernel<false, false>), grid_rows(n), dim3(256), 0, s, n, xadj, adj, (const int *)nullptr, seed,
-                           (const u64 *)ka.p, kb.p, (int *)nullptr);
-        hipLaunchKernelGGL(pt_refine_winner_kernel, grid_flat(n), dim3(256), 0, s, n, (const u64 *)key.p, (const u64 *)kb.p, wkeys.p,
-                           ids.p, counters.p);
+        flat(s, n, pt_count_kernel, label, sizes.p);
+        sweep(g, pt_refine_count_kernel, label, sizes.p, max_size, floor_size, target.p, gain.p, cand.p, counters.p);
+        hipLaunchKernelGGL(pt_refine_free_kernel, free_grid, dim3(256), 0, s, xadj, adj, label, cand.p, gain.p, seed, key.p,
+                           counters.p);
         SA_HIP_CHECK(hipGetLastError());
+        ball_min(g, false, false, nullptr, key.p, ka.p, nullptr);
+        ball_min(g, false, false, nullptr, ka.p, kb.p, nullptr);
+        flat(s, n, pt_refine_winner_kernel, key.p, kb.p, wkeys.p, ids.p, counters.p);
         const auto c = counters.to_host(s);
         if (c[1] == 0) { st.converged = 1; break; }
         const int m = c[2];
         SA_REQUIRE(m >= 1 && m <= n, "refinement: candidates without a winner");
         ++st.rounds;
-        // (tmp was sized for n items; the query for m is checked as in grow_balanced)
-        size_t b1 = 0, b2 = 0;
-        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, b1, wkeys.p, wkeys2.p, ids.p, ids2.p, m, 0, 48, s));
-        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, b2, lab.p, lab2.p, pos.p, pos2.p, m, 0, lab_bits, s));
-        SA_REQUIRE(b1 <= tmp_bytes && b2 <= tmp_bytes, "refinement: the sort asks for more temporary storage for fewer items");
-        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs((void *)tmp.p, b1, wkeys.p, wkeys2.p, ids.p, ids2.p, m, 0, 48, s));
-        hipLaunchKernelGGL(pt_refine_target_kernel, grid_flat(m), dim3(256), 0, s, m, (const int *)ids2.p, (const int *)target.p, lab.p, pos.p);
-        SA_HIP_CHECK(hipGetLastError());
-        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs((void *)tmp.p, b2, lab.p, lab2.p, pos.p, pos2.p, m, 0, lab_bits, s));
-        hipLaunchKernelGGL(pt_refine_admit_kernel, grid_flat(m), dim3(256), 0, s, m, (const int *)lab2.p, (const int *)pos2.p,
-                           (const int *)ids2.p, (const int *)label, (const int *)sizes.p, max_size, nparts, lab.p);
-        SA_HIP_CHECK(hipGetLastError());
-        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs((void *)tmp.p, b2, lab.p, lab2.p, ids2.p, ids.p, m, 0, lab_bits, s));
-        hipLaunchKernelGGL(pt_refine_apply_kernel, grid_flat(m), dim3(256), 0, s, m, (const int *)lab2.p, (const int *)ids.p,
-                           (const int *)sizes.p, floor_size, nparts, (const int *)target.p, (const int *)gain.p, label, totals.p);
-        SA_HIP_CHECK(hipGetLastError());
+        sorter.sort(wkeys.p, wkeys2.p, ids.p, ids2.p, m, 48);
+        flat(s, m, pt_refine_target_kernel, ids2.p, target.p, lab.p, pos.p);
+        sorter.sort(lab.p, lab2.p, pos.p, pos2.p, m, lab_bits);
+        flat(s, m, pt_refine_admit_kernel, lab2.p, pos2.p, ids2.p, label, sizes.p, max_size, nparts, lab.p);
+        sorter.sort(lab.p, lab2.p, ids2.p, ids.p, m, lab_bits);
+        flat(s, m, pt_refine_apply_kernel, lab2.p, ids.p, sizes.p, floor_size, nparts, target.p, gain.p, label, totals.p);
     }
     const auto tot = totals.to_host(s);   // (synchronises: the temporaries go out of scope)
     st.moved = (long long)tot[0];
     st.gain = (long long)tot[1];
-    t_refine_stats = st;
     return st;
 }
 

@@ -112,6 +112,44 @@ def test_partition_mesh_refined_equals_the_model_on_all_levels(min_shared, growt
     Q.close()
 
 
+def test_partition_mesh_refine_record_without_a_pass():
+    """What saamge_amd_partition_refine_info reports after the mesh entry when the last level has no pass: zeros when
+    refine_rounds is given with 0 rounds there (not the counts of level 0, which moves nodes), and the counts of the earlier
+    call, untouched, when refine_rounds is NULL."""
+    capi = _capi()
+    lib = capi.load()
+    ep, e2d, ND = pc.hex_mesh(12)
+    epa, rounds = [27, 4], [16, 0]
+    want = []
+    parts, nparts, _ = pm.partition_mesh(ep, e2d, ND, epa, refine_rounds=rounds, refine_info=want)
+    plain = pm.partition_mesh(ep, e2d, ND, epa)
+    assert want == [0, 0, 0, 0]
+    assert not np.array_equal(parts[0], plain[0][0])          # level 0 moved nodes: the zeros are not what it left
+    P = capi.partition_mesh(e2d, ND, epa, elem_ptr=ep, refine_rounds=rounds)
+    info = capi.partition_refine_info()
+    assert P.nparts == nparts, (P.nparts, nparts)
+    for k in range(2):
+        assert np.array_equal(P.part(k), parts[k]), "partition %d" % k
+    assert [info[k] for k in _KEYS] == want
+    P.close()
+    # a pass with counts, then the mesh entry without refine_rounds
+    c = rc.get("hex12_vertex")
+    _, left, _ = rc.model("hex12_vertex")
+    assert left[1] > 0
+    capi.partition_refine(c.n, c.xadj, c.adj, c.nparts, c.part.copy(), c.rounds, c.max_size, c.min_size, c.seed)
+    assert [capi.partition_refine_info()[k] for k in _KEYS] == left
+    o = capi.partition_options(growth=0)      # (the _v2 struct, which this entry reads)
+    h = C.c_void_p()
+    rc_ = lib.saamge_amd_partition_mesh_refined(C.c_int(len(ep) - 1), C.c_int(0), ep.ctypes.data_as(C.c_void_p),
+                                                e2d.ctypes.data_as(C.c_void_p), C.c_int(ND), C.c_int(2), (C.c_int * 2)(*epa),
+                                                C.byref(o), None, None, C.byref(h))
+    assert rc_ == 0
+    assert [capi.partition_refine_info()[k] for k in _KEYS] == left
+    free = lib.saamge_amd_partitioning_free
+    free.restype = None
+    free(h)
+
+
 def test_refusals_leave_the_outputs_untouched():
     capi = _capi()
     lib = capi.load()
