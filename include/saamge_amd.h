@@ -71,6 +71,12 @@ typedef struct saamge_amd_options {
                                    * memory) otherwise go back to the kernel with every hierarchy; unmapping pages the GPU driver
                                    * has registered stalled the process's queues for ~20 ms at the start of the next setup in
                                    * half of the processes (measured: DESIGN.md section 7.0).  0: the allocator is left alone. */
+    int ae_order;                 /* 0: the agglomerate matrices of the few-eigenpairs path are ordered by the rank of the global dof
+                                   * number (a lexicographic box: shortest extent fastest).  1: per agglomerate, where that order's
+                                   * structural half bandwidth exceeds 51 and the agglomerate has at most 4096 rows, the level order
+                                   * (Cuthill-McKee from a pseudo-peripheral root, two sweeps; the rule: saamge_amd/ae_order_model.py,
+                                   * DESIGN.md section 4.8) is computed and taken if it is narrower -- for global numberings that
+                                   * scatter an agglomerate's dofs (refined or generated meshes).  See saamge_amd_level_order_info. */
 } saamge_amd_options;
 void saamge_amd_options_default(saamge_amd_options *o);
 void saamge_amd_set_options(const saamge_amd_options *o);
@@ -329,6 +335,11 @@ int saamge_amd_coarse_solver_info(const saamge_amd_hierarchy *h, long long info[
  * lanes of a 3 x 3 node block share their gathers of x, [10] = rows outside regular node blocks, [11] = local eigenproblems this rank SOLVED on the level (its other
  * agglomerates are bitwise identical to one of those and received a copy: saamge_amd_options.eig_dedupe). */
 int saamge_amd_level_format(const saamge_amd_hierarchy *h, int level, long long info[12]);
+/* The local order of the level's agglomerate matrices (saamge_amd_options.ae_order), over the agglomerates whose matrices were
+ * given a permutation (the few-eigenpairs path): info[0] = their number, [1] = those that took the level order, [2] = the
+ * largest structural half bandwidth of the rank / box order, [3] = the largest of the order in use.  With ae_order = 0 the
+ * setup measures nothing: this call then measures the rank / box order of those agglomerates ([1] = 0, [3] = [2]). */
+int saamge_amd_level_order_info(const saamge_amd_hierarchy *h, int level, long long info[4]);
 /* which: 0 A_l, 1 interp, 2 restr, 3 Ac (host output buffers sized from level_info) */
 int saamge_amd_get_csr(const saamge_amd_hierarchy *h, int level, int which, int *rowptr, int *col,
                        double *val);       /* fails on an operator with more than 2^31 - 1 entries */
@@ -382,6 +393,16 @@ int saamge_amd_spgemm(int nrows, int ninner, int ncols, const int *Arow, const i
                       const int *Brow, const int *Bcol, const double *Bval, const int *Erow, const int *Ecol,
                       const double *Eval, const double *d, double alpha, double beta, int *Crow, long long *Cnnz,
                       int *Ccol, double *Cval, int *route);
+/* ---- the local order of the agglomerate matrices on its own (csrc/assemble.hip; tests) ----
+ * Host arrays.  A mesh (NE elements; elem_ptr NULL: nde dofs each, else NE + 1 offsets into elem_to_dof; dofs in [0, ND)) and an
+ * element -> agglomerate map (values in [0, nparts), no agglomerate empty).  The relation tables are built as the setup builds
+ * them.  Out: ae_ptr (nparts + 1) and *nconn always; with ae_to_dof and pos given (nconn entries each) the agglomerates' dofs
+ * in table order, the position of each in its agglomerate's matrix, and per agglomerate bw0 (structural half bandwidth of the
+ * rank / box order), bw (of the order in use) and choice (1: the level order).  mode: saamge_amd_options.ae_order (0: positions
+ * of the rank / box order, choice 0; other values are refused).  Agglomerates of at most 8192 rows. */
+int saamge_amd_ae_order(int ND, int NE, int nde, const int *elem_ptr, const int *elem_to_dof, const int *elem_to_ae,
+                        int nparts, int mode, int *ae_ptr, long long *nconn, int *ae_to_dof, int *pos, int *bw0, int *bw,
+                        int *choice);
 /* R = P^T (P nrows x ncols) */
 int saamge_amd_csr_transpose(int nrows, int ncols, const int *rowptr, const int *col, const double *val, int *Rrow,
                              long long *Rnnz, int *Rcol, double *Rval);

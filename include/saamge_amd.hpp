@@ -258,6 +258,42 @@ inline MeshPartitions partition_mesh_refined(int NE, int nde, const int *elem_pt
     return detail::take_partitions(P, (int)elems_per_agg.size());
 }
 
+// == the local order of the agglomerate matrices (saamge_amd_options.ae_order) ==
+// saamge_amd_ae_order on host arrays: the agglomerates' dof lists (ae_ptr / ae_to_dof, as the setup builds them), the position of
+// every entry in its agglomerate's matrix, and per agglomerate the structural half bandwidth of the rank / box order (bw0), of
+// the order in use (bw) and whether that is the level order (choice).  elem_ptr == nullptr: every element has nde dofs.
+struct AeOrder {
+    std::vector<int> ae_ptr, ae_to_dof, pos, bw0, bw, choice;
+};
+inline AeOrder ae_order(int ND, int NE, int nde, const int *elem_ptr, const int *elem_to_dof, const int *elem_to_ae, int nparts,
+                        int mode) {
+    AeOrder r;
+    r.ae_ptr.assign((size_t)(nparts > 0 ? nparts : 0) + 1, 0);
+    long long nconn = 0;
+    if (saamge_amd_ae_order(ND, NE, nde, elem_ptr, elem_to_dof, elem_to_ae, nparts, mode, r.ae_ptr.data(), &nconn, nullptr, nullptr,
+                            nullptr, nullptr, nullptr))
+        throw std::runtime_error(saamge_amd_last_error());
+    r.ae_to_dof.assign((size_t)nconn, 0);
+    r.pos.assign((size_t)nconn, 0);
+    r.bw0.assign((size_t)nparts, 0);
+    r.bw.assign((size_t)nparts, 0);
+    r.choice.assign((size_t)nparts, 0);
+    if (saamge_amd_ae_order(ND, NE, nde, elem_ptr, elem_to_dof, elem_to_ae, nparts, mode, r.ae_ptr.data(), &nconn,
+                            r.ae_to_dof.data(), r.pos.data(), r.bw0.data(), r.bw.data(), r.choice.data()))
+        throw std::runtime_error(saamge_amd_last_error());
+    return r;
+}
+// saamge_amd_level_order_info of a level: what the setup's ordering pass found
+struct LevelOrderInfo {
+    long long permuted, level_orders, max_bw0, max_bw;
+};
+inline LevelOrderInfo level_order_info(const ml_data_t *h, int level) {
+    long long info[4] = {0, 0, 0, 0};
+    if (saamge_amd_level_order_info(h, level, info)) throw std::runtime_error(saamge_amd_last_error());
+    const LevelOrderInfo r = {info[0], info[1], info[2], info[3]};
+    return r;
+}
+
 // == the operator assembled on the device (saamge_amd_operator_assemble) ==
 // Owner of the handle.  rowptr() / col() / val() are device arrays that live as long as this object: hand them to
 // saamge_amd_ml_produce_data64 / _mixed64 as A.  elem_ptr == nullptr: every element has nde dofs.

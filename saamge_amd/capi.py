@@ -39,6 +39,7 @@ SYMBOLS = [
     "saamge_amd_operator_assemble", "saamge_amd_operator_arrays", "saamge_amd_operator_get", "saamge_amd_operator_update",
     "saamge_amd_operator_eliminate_rhs", "saamge_amd_operator_free", "saamge_amd_operator_path_counts",
     "saamge_amd_operator_set_path_limits",
+    "saamge_amd_level_order_info", "saamge_amd_ae_order",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong))
@@ -52,7 +53,8 @@ ALLTOALLV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlo
 class Options(C.Structure):      # saamge_amd_options
     _fields_ = [(k, C.c_int) for k in ("eig_strict", "eig_certify", "eig_min_n", "eig_force_fallback", "eig_dense_only",
                                        "eig_dense_one_stage", "eig_nullcheck", "eig_keep_inertia_factor", "band_assembly",
-                                       "eig_dedupe", "eig_outer_panels", "overlap", "sell", "spmv_sell", "debug", "host_heap_pad_mb")]
+                                       "eig_dedupe", "eig_outer_panels", "overlap", "sell", "spmv_sell", "debug", "host_heap_pad_mb",
+                                       "ae_order")]
 
 
 class Params(C.Structure):
@@ -503,6 +505,12 @@ class Hierarchy(object):
                 "dictionary_pairs": v[8], "node_blocks": bool(v[9]), "irregular_rows": v[10],
                 "eigenproblems_solved": v[11]}
 
+    def level_order_info(self, level):
+        """[agglomerates given a permutation, those that took the level order, largest bw0, largest bandwidth in use]"""
+        info = (C.c_longlong * 4)()
+        _check(load().saamge_amd_level_order_info(self.h, C.c_int(level), info))
+        return [int(x) for x in info]
+
     def get_csr(self, level, which):
         import scipy.sparse as sp
         info = self.level_info(level)
@@ -700,6 +708,28 @@ def cached_memory_bytes():
     lib = load()
     lib.saamge_amd_cached_memory_bytes.restype = C.c_longlong
     return int(lib.saamge_amd_cached_memory_bytes())
+
+
+def ae_order(ND, elem_to_dof, elem_to_ae, nparts, mode, elem_ptr=None):
+    """saamge_amd_ae_order: (ae_ptr, ae_to_dof, pos, bw0, bw, choice) as numpy int32 arrays.  elem_ptr None: elem_to_dof is
+    (NE, nde); otherwise flat elem_to_dof with NE + 1 offsets."""
+    e2d = np.ascontiguousarray(elem_to_dof, dtype=np.int32)
+    part = np.ascontiguousarray(elem_to_ae, dtype=np.int32)
+    ep = None if elem_ptr is None else np.ascontiguousarray(elem_ptr, dtype=np.int32)
+    NE = len(part)
+    nde = 0 if ep is not None else int(e2d.shape[1])
+    ae_ptr = np.zeros(max(int(nparts), 0) + 1, np.int32)
+    nconn = C.c_longlong(0)
+
+    def call(j, pos, bw0, bw, choice):
+        _check(load().saamge_amd_ae_order(C.c_int(ND), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2d), _ptr(part),
+                                          C.c_int(nparts), C.c_int(mode), _ptr(ae_ptr), C.byref(nconn), _ptr(j), _ptr(pos),
+                                          _ptr(bw0), _ptr(bw), _ptr(choice)))
+    call(None, None, None, None, None)
+    j, pos = np.zeros(nconn.value, np.int32), np.zeros(nconn.value, np.int32)
+    bw0, bw, choice = (np.zeros(nparts, np.int32) for _ in range(3))
+    call(j, pos, bw0, bw, choice)
+    return ae_ptr, j, pos, bw0, bw, choice
 
 
 def get_options():

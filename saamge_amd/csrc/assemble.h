@@ -58,6 +58,14 @@ struct AeClasses {
 void ae_build(hipStream_t s, const DevRelations &rel, const DCsr *A, const DevElmats &el, int ae0,
               EigBatch &batch, bool scale, double *Dout, const RowsSpan *rows = nullptr, AeClasses *classes = nullptr);
 
+// Options::ae_order: after ae_perm_kernel has filled batch.perm / iperm (on the same stream) -- mode 1 replaces the order of an
+// agglomerate by the level order of saamge_amd/ae_order_model.py where that is narrower; mode 0 only measures.  res (device, 3
+// ints per agglomerate, or null): structural half bandwidth of ae_perm_kernel's order, of the order in use, 1 = level order;
+// stats (device, 4 ints, or null): += agglomerates, += level orders, max of the first, max of the second.
+void ae_level_order(hipStream_t s, const DevRelations &rel, int ae0, EigBatch &batch, int mode, int *res, int *stats);
+// ae_perm_kernel (+ ae_level_order) on their own: batch.perm / iperm of the agglomerates [ae0, ae0 + batch.count)
+void ae_order_only(hipStream_t s, const DevRelations &rel, int ae0, EigBatch &batch, int mode, int *res);
+
 // Fine level, 8-dof elements, or elements of at most 8 dofs each (DevElmats::max_nd): the sparse rows of the AE matrices of a chunk (RW slots per row at
 // rv / rc[(batch.voff[b] + row) * RW + slot], column -1 = empty).  false: not applicable.
 bool ae_sparse_rows(hipStream_t s, const DevRelations &rel, const DCsr &A, const DevElmats &el, int ae0,

@@ -1150,6 +1150,309 @@ __global__ __launch_bounds__(256) void ae_perm_kernel(int ae0, const int *__rest
     }
 }
 
+// Options::ae_order = 1: the LEVEL ORDER of saamge_amd/ae_order_model.py (the definition: rule, keys and limits are stated there,
+// this kernel restates them integer for integer), taken per agglomerate where it is narrower than the order ae_perm_kernel has just
+// written.  One workgroup per agglomerate (grid-stride where the adjacency lives in a pool buffer).  The walk that gives an
+// order's structural half bandwidth visits, per row, the elements of its dof that lie in the agglomerate and reads the local
+// numbers of their dofs from elem_ldof: the largest |pos[u] - pos[row]|.  mode 0 stops after that walk (bw0 for the inspection
+// entry points); so does an agglomerate with bw0 <= AO_KEEP_BW or more than AO_MAX_ROWS rows.  Otherwise the local adjacency is
+// built ONCE as a bit matrix (row r is written by the thread that owns r: no atomics), in LDS where it fits; a breadth-first level
+// is "unvisited rows whose bit row meets the frontier's bit vector", n / 32 words per row and level.  A sweep numbers a level by
+// counting, per node, the nodes of the level with a smaller packed key (lowest position among the previous level's neighbours,
+// degree, tie).  No floating point; LDS atomics are atomicMin / atomicMax / atomicAdd on integers only.
+constexpr int AO_KEEP_BW = 51;        // 67 - SB: the narrowest LDS window of the banded factorisation (eig2.hip)
+constexpr int AO_MAX_ROWS = 4096;     // degree and tie in 12 bits each
+constexpr int AO_ROOT_MOVES = 8;
+struct AoTables {
+    const int *ns;
+    const int64_t *voff;
+    const int *ae2d_I, *ae2d_J, *d2e_I, *d2e_J, *part, *e2d_I, *elem_ldof;
+};
+struct AoLds {      // arrays of one agglomerate (n rows, nw = words of a bit row)
+    unsigned long long *key;
+    unsigned *front;
+    unsigned short *rank, *deg, *byrank;
+    short *level, *posa, *posb;
+    const unsigned *adj;
+    int n, nw;
+};
+// levels of the breadth-first search from `root` into a.level; returns the depth (block-uniform)
+__device__ inline int ao_bfs(const AoLds &a, int root) {
+    const int tid = threadIdx.x;
+    for (int v = tid; v < a.n; v += 256) a.level[v] = (short)(v == root ? 0 : -1);
+    __syncthreads();
+    int L = 0;
+    for (;;) {
+        for (int w = tid; w < a.nw; w += 256) {
+            unsigned word = 0;
+            for (int i = 0; i < 32; ++i) { const int v = 32 * w + i; if (v < a.n && a.level[v] == L) word |= 1u << i; }
+            a.front[w] = word;
+        }
+        __syncthreads();
+        int found = 0;
+        for (int v = tid; v < a.n; v += 256) {
+            if (a.level[v] >= 0) continue;
+            const unsigned *row = a.adj + (size_t)v * a.nw;
+            unsigned any = 0;
+            for (int w = 0; w < a.nw; ++w) any |= row[w] & a.front[w];
+            if (any) { a.level[v] = (short)(L + 1); found = 1; }
+        }
+        if (!__syncthreads_or(found)) break;
+        ++L;
+    }
+    return L;
+}
+// the node of level d with the smallest (degree, rank)
+__device__ inline int ao_candidate(const AoLds &a, int d, unsigned *slot) {
+    if (threadIdx.x == 0) *slot = 0xffffffffu;
+    __syncthreads();
+    for (int v = threadIdx.x; v < a.n; v += 256)
+        if (a.level[v] == d) atomicMin(slot, ((unsigned)a.deg[v] << 12) | a.rank[v]);
+    __syncthreads();
+    const int c = a.byrank[min((int)(*slot & 4095u), a.n - 1)];
+    __syncthreads();
+    return c;
+}
+// numbers the component of `root` from position `base` on into pos; tie_a = false: tie = rank, true: tie = n - 1 - posa.
+// Returns the next free position (block-uniform).
+__device__ inline int ao_sweep(const AoLds &a, int root, bool tie_a, short *pos, int base, int *width) {
+    const int tid = threadIdx.x;
+    for (int v = tid; v < a.n; v += 256) a.level[v] = (short)(v == root ? 0 : -1);
+    if (tid == 0) pos[root] = (short)base;
+    __syncthreads();
+    int cnt = 1, L = 0;
+    for (;;) {
+        for (int w = tid; w < a.nw; w += 256) {
+            unsigned word = 0;
+            for (int i = 0; i < 32; ++i) { const int v = 32 * w + i; if (v < a.n && a.level[v] == L) word |= 1u << i; }
+            a.front[w] = word;
+        }
+        if (tid == 0) *width = 0;
+        __syncthreads();
+        int mine = 0;
+        for (int v = tid; v < a.n; v += 256) {
+            if (a.level[v] >= 0) continue;
+            const unsigned *row = a.adj + (size_t)v * a.nw;
+            int first = 0x7fffffff;
+            for (int w = 0; w < a.nw; ++w) {
+                unsigned m = row[w] & a.front[w];
+                while (m) { const int u = 32 * w + __builtin_ctz(m); m &= m - 1; first = min(first, (int)pos[u]); }
+            }
+            if (first == 0x7fffffff) continue;
+            a.level[v] = (short)(L + 1);
+            const unsigned tie = tie_a ? (unsigned)(a.n - 1 - a.posa[v]) : (unsigned)a.rank[v];
+            a.key[v] = ((unsigned long long)(unsigned)first << 24) | ((unsigned long long)a.deg[v] << 12) | tie;
+            ++mine;
+        }
+        if (mine) atomicAdd(width, mine);
+        __syncthreads();
+        const int wd = *width;
+        if (!wd) break;
+        for (int v = tid; v < a.n; v += 256) {
+            if (a.level[v] != L + 1) continue;
+            const unsigned long long kv = a.key[v];
+            int c = 0;
+            for (int u = 0; u < a.n; ++u) c += (a.level[u] == L + 1 && a.key[u] < kv) ? 1 : 0;
+            pos[v] = (short)(base + cnt + c);
+        }
+        cnt += wd;
+        ++L;
+        __syncthreads();
+    }
+    __syncthreads();
+    return base + cnt;
+}
+__global__ __launch_bounds__(256) void ae_level_order_kernel(int ae0, int count, int mode, AoTables t, short *__restrict__ perm,
+                                                             short *__restrict__ iperm, int nmax, int adj_in_lds,
+                                                             unsigned *__restrict__ adj_pool, int *__restrict__ res,
+                                                             int *__restrict__ stats) {
+    extern __shared__ __align__(16) unsigned char ao_lds[];
+    __shared__ int sh_bw[3];
+    __shared__ unsigned sh_min;
+    __shared__ int sh_int;
+    const int tid = threadIdx.x;
+    const int nwmax = (nmax + 31) >> 5;
+    for (int b = blockIdx.x; b < count; b += gridDim.x) {
+        const int n = t.ns[b], p = ae0 + b;
+        const int64_t v0 = t.voff[b];
+        const int *aedofs = t.ae2d_J + t.ae2d_I[p];
+        if (tid < 3) sh_bw[tid] = 0;
+        __syncthreads();
+        {   // bw0 of the order ae_perm_kernel wrote
+            int bw = 0;
+            for (int r = tid; r < n; r += 256) {
+                const int g = aedofs[r], me = perm[v0 + r];
+                for (int q = t.d2e_I[g]; q < t.d2e_I[g + 1]; ++q) {
+                    const int e = t.d2e_J[q];
+                    if (t.part[e] != p) continue;
+                    for (int k = t.e2d_I[e]; k < t.e2d_I[e + 1]; ++k) {
+                        const int l = t.elem_ldof[k];
+                        if ((unsigned)l < (unsigned)n) bw = max(bw, abs((int)perm[v0 + l] - me));
+                    }
+                }
+            }
+            if (bw) atomicMax(&sh_bw[0], bw);
+        }
+        __syncthreads();
+        const int bw0 = sh_bw[0];
+        int bw_used = bw0, choice = 0;
+        if (mode == 1 && bw0 > AO_KEEP_BW && n <= AO_MAX_ROWS && n <= nmax) {
+            const int nw = (n + 31) >> 5;
+            AoLds a;
+            a.n = n; a.nw = nw;
+            unsigned char *q = ao_lds;
+            a.key = (unsigned long long *)q; q += 8 * (size_t)nmax;
+            a.front = (unsigned *)q; q += 4 * (size_t)nwmax;
+            unsigned *adj = adj_in_lds ? (unsigned *)q : adj_pool + (size_t)blockIdx.x * nmax * nwmax;
+            if (adj_in_lds) q += 4 * (size_t)nmax * nwmax;
+            a.adj = adj;
+            a.rank = (unsigned short *)q; q += 2 * (size_t)nmax;
+            a.deg = (unsigned short *)q; q += 2 * (size_t)nmax;
+            a.byrank = (unsigned short *)q; q += 2 * (size_t)nmax;
+            a.level = (short *)q; q += 2 * (size_t)nmax;
+            a.posa = (short *)q; q += 2 * (size_t)nmax;
+            a.posb = (short *)q;
+            int *gd = (int *)a.key;           // (the global numbers, until the first key is written)
+            for (int r = tid; r < n; r += 256) { gd[r] = aedofs[r]; a.posa[r] = -1; a.posb[r] = -1; }
+            __syncthreads();
+            for (int r = tid; r < n; r += 256) {
+                const int g = gd[r];
+                int rk = 0;
+                for (int k = 0; k < n; ++k) rk += gd[k] < g;
+                a.rank[r] = (unsigned short)rk;
+                a.byrank[rk] = (unsigned short)r;
+                // the row's bits: every dof of every element of the row's dof that lies in the agglomerate, but the row itself
+                unsigned *row = adj + (size_t)r * nw;
+                for (int w = 0; w < nw; ++w) row[w] = 0;
+                for (int qq = t.d2e_I[g]; qq < t.d2e_I[g + 1]; ++qq) {
+                    const int e = t.d2e_J[qq];
+                    if (t.part[e] != p) continue;
+                    for (int k = t.e2d_I[e]; k < t.e2d_I[e + 1]; ++k) {
+                        const int l = t.elem_ldof[k];
+                        if ((unsigned)l < (unsigned)n && l != r) row[l >> 5] |= 1u << (l & 31);
+                    }
+                }
+                int dg = 0;
+                for (int w = 0; w < nw; ++w) dg += __popc(row[w]);
+                a.deg[r] = (unsigned short)dg;
+            }
+            __syncthreads();
+            int nxt = 0;
+            while (nxt < n) {      // components by lowest unnumbered rank
+                if (tid == 0) sh_min = 0xffffffffu;
+                __syncthreads();
+                for (int v = tid; v < n; v += 256)
+                    if (a.posa[v] < 0) atomicMin(&sh_min, (unsigned)a.rank[v]);
+                __syncthreads();
+                const unsigned lowest = sh_min;
+                __syncthreads();
+                if (lowest >= (unsigned)n) break;      // (cannot happen: nxt < n leaves an unnumbered row)
+                int root = a.byrank[lowest];
+                int d = ao_bfs(a, root);
+                int cand = ao_candidate(a, d, &sh_min);
+                for (int it = 0; it < AO_ROOT_MOVES; ++it) {
+                    const int dc = ao_bfs(a, cand);
+                    if (dc <= d) break;
+                    root = cand;
+                    d = dc;
+                    cand = ao_candidate(a, d, &sh_min);
+                }
+                const int end = ao_sweep(a, root, false, a.posa, nxt, &sh_int);
+                if (tid == 0) sh_int = -1;
+                __syncthreads();
+                for (int v = tid; v < n; v += 256)
+                    if (a.posa[v] == end - 1) sh_int = v;
+                __syncthreads();
+                const int last = sh_int;
+                __syncthreads();
+                if (last < 0) break;                   // (cannot happen: sweep A numbered end - nxt >= 1 rows)
+                ao_sweep(a, last, true, a.posb, nxt, &sh_int);
+                nxt = end;
+            }
+            {   // bandwidths of the two sweeps
+                int ba = 0, bb = 0;
+                for (int r = tid; r < n; r += 256) {
+                    const int g = aedofs[r], ma = a.posa[r], mb = a.posb[r];
+                    for (int qq = t.d2e_I[g]; qq < t.d2e_I[g + 1]; ++qq) {
+                        const int e = t.d2e_J[qq];
+                        if (t.part[e] != p) continue;
+                        for (int k = t.e2d_I[e]; k < t.e2d_I[e + 1]; ++k) {
+                            const int l = t.elem_ldof[k];
+                            if ((unsigned)l >= (unsigned)n) continue;
+                            ba = max(ba, abs((int)a.posa[l] - ma));
+                            bb = max(bb, abs((int)a.posb[l] - mb));
+                        }
+                    }
+                }
+                if (ba) atomicMax(&sh_bw[1], ba);
+                if (bb) atomicMax(&sh_bw[2], bb);
+            }
+            __syncthreads();
+            const int bwa = sh_bw[1], bwb = sh_bw[2];
+            const short *pos1 = bwb < bwa ? a.posb : a.posa;
+            const int bw1 = min(bwa, bwb);
+            if (bw1 < bw0) {
+                choice = 1;
+                bw_used = bw1;
+                for (int r = tid; r < n; r += 256) {
+                    const int ps = pos1[r];
+                    if ((unsigned)ps < (unsigned)n) { perm[v0 + r] = (short)ps; iperm[v0 + ps] = (short)r; }
+                }
+            }
+        }
+        if (tid == 0) {
+            if (res) { res[3 * (size_t)b] = bw0; res[3 * (size_t)b + 1] = bw_used; res[3 * (size_t)b + 2] = choice; }
+            if (stats) {
+                atomicAdd(stats, 1);
+                if (choice) atomicAdd(stats + 1, 1);
+                atomicMax(stats + 2, bw0);
+                atomicMax(stats + 3, bw_used);
+            }
+        }
+        __syncthreads();
+    }
+}
+// after ae_perm_kernel on the same stream.  res (device, 3 ints per agglomerate, or null): bw0, the bandwidth used, the choice;
+// stats (device, 4 ints, or null): += agglomerates, += level orders taken, max bw0, max bandwidth used
+void ae_level_order(hipStream_t s, const DevRelations &rel, int ae0, EigBatch &batch, int mode, int *res, int *stats) {
+    if (!batch.count) return;
+    SA_REQUIRE(mode == 0 || mode == 1, "ae_order must be 0 or 1");
+    const AoTables t{batch.n.p, batch.voff.p, rel.ae2d_I.p, rel.ae2d_J.p, rel.d2e_I.p, rel.d2e_J.p, rel.part.p, rel.e2d_I.p,
+                     rel.elem_ldof.p};
+    const int nmax = mode ? std::min(batch.max_n, AO_MAX_ROWS) : 0;
+    const size_t nw = (size_t)((nmax + 31) >> 5);
+    const size_t fixed = 8 * (size_t)nmax + 4 * nw + 12 * (size_t)nmax + 16, adj_bytes = 4 * (size_t)nmax * nw;
+    const bool in_lds = fixed + adj_bytes <= 150 * 1024;
+    int grid = batch.count;
+    static DBuf<unsigned> &pool = *new DBuf<unsigned>;      // never destroyed (see g_rows)
+    if (mode && !in_lds) {
+        grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(batch.count, 1024), ((size_t)256 << 20) / adj_bytes));
+        const size_t need = (size_t)grid * nmax * nw;
+        if (pool.n < need) pool.alloc(need);
+    }
+    static bool attr = false;
+    if (!attr) {
+        SA_HIP_CHECK(hipFuncSetAttribute((const void *)ae_level_order_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        attr = true;
+    }
+    profiler().begin(s);
+    hipLaunchKernelGGL(ae_level_order_kernel, dim3(grid), dim3(256), mode ? fixed + (in_lds ? adj_bytes : 0) : 0, s, ae0,
+                       batch.count, mode, t, batch.perm.p, batch.iperm.p, nmax, in_lds ? 1 : 0, pool.p, res, stats);
+    SA_HIP_CHECK(hipGetLastError());
+    profiler().end(s, "ae_level_order", 0.0, 0.0);
+}
+void ae_order_only(hipStream_t s, const DevRelations &rel, int ae0, EigBatch &batch, int mode, int *res) {
+    if (!batch.count) return;
+    SA_REQUIRE(batch.max_n <= 8192, "saamge_amd_ae_order: an agglomerate of more than 8192 rows");
+    const size_t rows_total = (size_t)batch.h_voff[batch.count];
+    if (batch.perm.n < rows_total) { batch.perm.alloc(rows_total); batch.iperm.alloc(rows_total); }
+    hipLaunchKernelGGL(ae_perm_kernel, dim3(batch.count), dim3(256), 2 * sizeof(int) * (size_t)batch.max_n, s, ae0, batch.n.p,
+                       batch.voff.p, rel.ae2d_I.p, rel.ae2d_J.p, batch.perm.p, batch.iperm.p, 1);
+    SA_HIP_CHECK(hipGetLastError());
+    batch.has_perm = true;
+    ae_level_order(s, rel, ae0, batch, mode, res, nullptr);
+}
+
 // The same for the GENERIC assembly (ae_assemble_kernel + the scaling: coarse levels, elements that are not 8-dof hexes): the
 // matrix, its scaling and its band are functions of what that kernel reads -- per row of the agglomerate (in agglomerate
 // order): its position in the matrix, its flag, the coarse start vector; per entry of its row of the global matrix whose column
@@ -1369,6 +1672,7 @@ void ae_build(hipStream_t s, const DevRelations &rel, const DCsr *A, const DevEl
     if (!batch.count) return;
     batch.has_perm = false;
     batch.has_bw = false;
+    batch.order_ran = false;
     if (A && el.algebraic) {
         double bytes = 0.0;
         for (int n : batch.h_n) bytes += 8.0 * (double)n * n;
@@ -1395,6 +1699,8 @@ void ae_build(hipStream_t s, const DevRelations &rel, const DCsr *A, const DevEl
         hipLaunchKernelGGL(ae_perm_kernel, dim3(batch.count), dim3(256), 2 * sizeof(int) * (size_t)batch.max_n, s, ae0,
                            batch.n.p, batch.voff.p, rel.ae2d_I.p, rel.ae2d_J.p, batch.perm.p, batch.iperm.p, box_order);
         batch.has_perm = true;
+        batch.order_ran = true;
+        if (batch.opt.ae_order) ae_level_order(s, rel, ae0, batch, 1, nullptr, batch.order_stats);
     }
     if (A && !no_fused) {
         if (A->max_row < 0) A->max_row = csr_max_row(s, *A);

@@ -67,6 +67,7 @@ static void options_to_c(const Options &o, saamge_amd_options *c) {
     c->eig_nullcheck = o.eig_nullcheck; c->eig_keep_inertia_factor = o.eig_keep_inertia_factor; c->band_assembly = o.band_assembly;
     c->eig_dedupe = o.eig_dedupe; c->eig_outer_panels = o.eig_outer_panels; c->overlap = o.overlap; c->sell = o.sell; c->spmv_sell = o.spmv_sell; c->debug = o.debug;
     c->host_heap_pad_mb = o.host_heap_pad_mb;
+    c->ae_order = o.ae_order;
 }
 static Options options_from_c(const saamge_amd_options *c) {
     Options o;
@@ -75,6 +76,7 @@ static Options options_from_c(const saamge_amd_options *c) {
     o.eig_nullcheck = c->eig_nullcheck; o.eig_keep_inertia_factor = c->eig_keep_inertia_factor; o.band_assembly = c->band_assembly;
     o.eig_dedupe = c->eig_dedupe; o.eig_outer_panels = c->eig_outer_panels; o.overlap = c->overlap; o.sell = c->sell; o.spmv_sell = c->spmv_sell; o.debug = c->debug;
     o.host_heap_pad_mb = c->host_heap_pad_mb;
+    o.ae_order = c->ae_order;
     return o;
 }
 // Called on the options a hierarchy or a hierarchy-free entry point is about to use.
@@ -96,6 +98,7 @@ static void validate_options(const Options &o) {
     SA_REQUIRE(flag(o.spmv_sell), "options: spmv_sell must be 0 or 1");
     SA_REQUIRE((o.debug & ~7) == 0, "options: debug has bits 0-2");
     SA_REQUIRE(o.host_heap_pad_mb >= 0, "options: host_heap_pad_mb must not be negative");
+    SA_REQUIRE(flag(o.ae_order), "options: ae_order must be 0 or 1");
 }
 // The process-wide default: what saamge_amd_get_options returns and the entry points without a hierarchy use.
 static Options g_default_options;
@@ -474,6 +477,47 @@ int saamge_amd_level_format(const saamge_amd_hierarchy *h, int level, long long 
     SA_API_END
 }
 
+int saamge_amd_level_order_info(const saamge_amd_hierarchy *h, int level, long long info[4]) {
+    SA_API_BEGIN
+    SA_REQUIRE(h && info, "null argument");
+    const Hierarchy &H = *h->H;
+    for (int i = 0; i < 4; ++i) info[i] = 0;
+    SA_REQUIRE(level >= 0 && level < (int)H.levels.size(), "no such level");
+    const Level &L = *H.levels[(size_t)level];
+    require_device(H);
+    hipStream_t s = H.stream;
+    if (H.params.opt.ae_order == 1) {      // what the setup's ordering pass added up
+        if (L.order_info.n == 4) {
+            int v[4];
+            SA_HIP_CHECK(hipMemcpyAsync(v, L.order_info.p, sizeof v, hipMemcpyDeviceToHost, s));
+            SA_HIP_CHECK(hipStreamSynchronize(s));
+            for (int i = 0; i < 4; ++i) info[i] = v[i];
+        }
+    } else {      // ae_order = 0: the setup measures nothing; the band of the rank / box order of those chunks, now
+        for (const std::pair<int, int> &c : L.order_chunks) {
+            EigBatch b;
+            b.count = c.second;
+            b.h_voff.assign((size_t)b.count + 1, 0);
+            for (int i = 0; i < b.count; ++i) {
+                const int n = L.rel.AE_to_dof.row_size(c.first + i);
+                b.h_n.push_back(n);
+                b.h_voff[(size_t)i + 1] = b.h_voff[(size_t)i] + n;
+                b.max_n = std::max(b.max_n, n);
+            }
+            info[0] += b.count;
+            if (b.max_n > 8192) continue;      // (ae_order_only's limit)
+            b.n.from_host(b.h_n, s);
+            b.voff.from_host(b.h_voff, s);
+            DBuf<int> res(3 * (size_t)b.count);
+            ae_order_only(s, L.drel, c.first, b, 0, res.p);
+            const hvec<int> hr = res.to_host(s);
+            for (int i = 0; i < b.count; ++i) info[2] = std::max<long long>(info[2], hr[3 * (size_t)i]);
+        }
+        info[3] = info[2];
+    }
+    SA_API_END
+}
+
 int saamge_amd_coarse_solver_info(const saamge_amd_hierarchy *h, long long info[8]) {
     SA_API_BEGIN
     SA_REQUIRE(h && info, "null argument");
@@ -697,6 +741,59 @@ int saamge_amd_spgemm(int nrows, int ninner, int ncols, const int *Arow, const i
     spgemm(s, A, B, Erow ? (alias ? &B : &E) : nullptr, d ? dd.p : nullptr, alpha, beta, Cm);
     if (route) *route = spgemm_last_route();
     export_host_csr(Cm, Crow, Cnnz, Ccol, Cval, s);
+    SA_API_END
+}
+
+int saamge_amd_ae_order(int ND, int NE, int nde, const int *elem_ptr, const int *elem_to_dof, const int *elem_to_ae,
+                        int nparts, int mode, int *ae_ptr, long long *nconn, int *ae_to_dof, int *pos, int *bw0, int *bw,
+                        int *choice) {
+    SA_API_BEGIN
+    SA_REQUIRE(mode == 0 || mode == 1, "saamge_amd_ae_order: ae_order must be 0 or 1");
+    SA_REQUIRE(elem_to_dof && elem_to_ae && ae_ptr && nconn, "saamge_amd_ae_order: null argument");
+    SA_REQUIRE(ND >= 1 && NE >= 1 && nparts >= 1 && (elem_ptr || nde >= 1), "saamge_amd_ae_order: bad size");
+    Table e2d;
+    e2d.I.resize((size_t)NE + 1);
+    if (elem_ptr) {
+        SA_REQUIRE(elem_ptr[0] == 0, "saamge_amd_ae_order: elem_ptr must start at 0");
+        for (int e = 0; e < NE; ++e) SA_REQUIRE(elem_ptr[e + 1] > elem_ptr[e], "saamge_amd_ae_order: every element needs a dof");
+        for (int e = 0; e <= NE; ++e) e2d.I[(size_t)e] = elem_ptr[e];
+    } else {
+        SA_REQUIRE((long long)NE * nde <= 2147483647LL, "saamge_amd_ae_order: mesh too large");
+        for (int e = 0; e <= NE; ++e) e2d.I[(size_t)e] = e * nde;
+    }
+    e2d.J.assign(elem_to_dof, elem_to_dof + e2d.I[(size_t)NE]);
+    hvec<int> part(elem_to_ae, elem_to_ae + NE);
+    Relations rel;
+    build_relations_ae(rel, std::move(e2d), part, nparts, ND, nullptr);      // (checks the ranges)
+    for (int p = 0; p <= nparts; ++p) ae_ptr[p] = rel.AE_to_dof.I[(size_t)p];
+    const size_t rows = (size_t)rel.AE_to_dof.I[(size_t)nparts];
+    *nconn = (long long)rows;
+    if (ae_to_dof && pos) {
+        SA_REQUIRE(bw0 && bw && choice, "saamge_amd_ae_order: null argument");
+        hipStream_t s = 0;
+        set_thread_stream(s);
+        DevRelations drel;
+        upload_relations_ae(drel, rel, s);
+        std::vector<int> sizes((size_t)nparts);
+        for (int p = 0; p < nparts; ++p) sizes[(size_t)p] = rel.AE_to_dof.row_size(p);
+        // (no eigensolver workspace: the sizes and row offsets of the batch only)
+        EigBatch b;
+        b.count = nparts;
+        b.h_n = sizes;
+        b.h_voff.assign((size_t)nparts + 1, 0);
+        for (int p = 0; p < nparts; ++p) {
+            b.h_voff[(size_t)p + 1] = b.h_voff[(size_t)p] + sizes[(size_t)p];
+            b.max_n = std::max(b.max_n, sizes[(size_t)p]);
+        }
+        b.n.from_host(b.h_n, s);
+        b.voff.from_host(b.h_voff, s);
+        DBuf<int> res(3 * (size_t)nparts);
+        ae_order_only(s, drel, 0, b, mode, res.p);
+        const hvec<int> hr = res.to_host(s);
+        const hvec<short> hp = b.perm.to_host(s);
+        for (int p = 0; p < nparts; ++p) { bw0[p] = hr[3 * (size_t)p]; bw[p] = hr[3 * (size_t)p + 1]; choice[p] = hr[3 * (size_t)p + 2]; }
+        for (size_t k = 0; k < rows; ++k) { ae_to_dof[k] = rel.AE_to_dof.J[k]; pos[k] = hp[k]; }
+    }
     SA_API_END
 }
 

@@ -56,6 +56,8 @@ struct EigBatch {
     // identity.  Only the fused assembly sets it, and only for batches that take this path.
     DBuf<short> perm, iperm;      // (iperm: row of the agglomerate at a position of the matrix)
     bool has_perm = false;
+    int *order_stats = nullptr;   // device, 4 ints, or null: where ae_build adds what ae_level_order found (Options::ae_order = 1; saamge_amd_level_order_info)
+    bool order_ran = false;       // ae_build gave the batch a permutation (ae_perm_kernel ran)
     bool has_bw = false;    // bw was filled by the assembly (from the sparse rows): no scan of the dense matrices
     DBuf<int> bw;           // [count] half bandwidths (banded Cholesky), host copy; empty = full matrices
     std::vector<int> h_bw;

@@ -5,6 +5,7 @@
 #include <exception>
 #include <memory>
 #include <thread>
+#include <utility>
 
 #include "assemble.h"
 #include "blocktri.h"
@@ -85,6 +86,8 @@ struct Level {                  // tg_data_t + interp_data_t + agg_partitioning_
     std::vector<int> ae_m;              // eigenvectors per AE
     std::vector<int> ae_class;          // per agglomerate: its class of identical SPARSE ROWS (the eigenproblem stage's, fused fine-level assembly), or -1
     std::vector<int> ae_evclass;        // per agglomerate: the class whose eigenpairs it holds a copy of (any kind of class), or -1
+    DBuf<int> order_info;               // saamge_amd_level_order_info with Options::ae_order = 1: agglomerates given a permutation, level orders taken, max bw0, max bandwidth used
+    std::vector<std::pair<int, int>> order_chunks;      // (first agglomerate, count) of the chunks that were given a permutation: ae_order = 0 measures them on request
     long long ae_solved = 0;            // local eigenproblems actually solved on this level by this rank (the others: copies of a class)
     std::vector<int64_t> ae_xoff, ae_eoff;
     DBuf<double> evals, evecs;          // cut_evects_arr (packed)

@@ -367,6 +367,9 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
     for (int p = 0; p < nparts; ++p) sizes[p] = rel.AE_to_dof.row_size(p);
     L.ae_m.assign((size_t)nparts, 0);
     L.ae_solved = 0;
+    if (L.order_info.n != 4) L.order_info.alloc(4);
+    L.order_info.zero(s);
+    L.order_chunks.clear();
     L.ae_class.assign((size_t)nparts, -1);
     L.ae_evclass.assign((size_t)nparts, -1);
     struct Chunk { int ae0, count; DBuf<double> evals, evecs; std::vector<int64_t> eoff, xoff; DBuf<int64_t> d_eoff, d_xoff; };
@@ -650,6 +653,7 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
         batch.dense_only = P.eigensolver == 1;
         batch.ss_tol = P.eig_tol;
         batch.set_window(L.theta);
+        batch.order_stats = L.order_info.p;
         if (lev > 0 && H.levels[lev - 1]->cvec_next.n == (size_t)L.A.nrows) {
             const size_t rows = (size_t)batch.h_voff[cnt];
             batch.x0c.alloc(rows);
@@ -662,6 +666,7 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
         ae_build(qa, L.drel, lev == 0 ? &L.A : nullptr, L.elmat, ae0, batch, true,
                  P.keep_debug ? L.ae_D.p + row0 : nullptr, keep_rows ? &span : nullptr,
                  dedupe && dedupe_level && !batch.dense_only ? &classes : nullptr);
+        if (batch.order_ran) L.order_chunks.emplace_back(ae0, cnt);
         const int64_t rows_chunk = batch.h_voff[cnt];
         cls_of[slot].clear();
         solve_cls[slot].clear();

@@ -24,6 +24,7 @@ struct Options {
     int spmv_sell = 0;                // saamge_amd_spmv / spmv64 build and use the SELL copy
     int debug = 0;                    // bit 0 iteration traces of the few-eigenpairs path, 1 operator format census, 2 level tags in the kernel profile
     int host_heap_pad_mb = 256;       // > 0: glibc never trims its heap, serves blocks up to 32 MB from it and grows it in steps of this size (0: allocator left alone)
+    int ae_order = 0;                 // local order of the agglomerate matrices: 0 rank / box order (ae_perm_kernel), 1 the level order of ae_order_model.py where it is narrower
 };
 
 }  // namespace saamge_amd
