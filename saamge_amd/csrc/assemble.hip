@@ -1512,12 +1512,6 @@ struct AiTable {
 // A / element ordinal and dof slot), so sums over (word, position) are order-independent and two agglomerates can be compared
 // position by position.  `other` (verification): the same walk over a second agglomerate in lockstep; returns false at the
 // first difference.
-__device__ inline unsigned long long ai_mix(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 struct AiRow {      // what identifies one side of a walk
     int b, p;
     const AiTable *loc;
@@ -1616,31 +1610,17 @@ __device__ inline bool ai_row_walk(const AeInputs &v, const AiRow &x, const AiRo
 constexpr int AI_NT = 256;
 __global__ __launch_bounds__(AI_NT) void asm_hash_kernel(AeInputs v, int hsize, unsigned long long *__restrict__ out) {
     extern __shared__ __align__(16) unsigned char ai_lds[];
-    __shared__ unsigned long long red[2][AI_NT / 64];
     const int b = blockIdx.x, p = v.ae0 + b, n = v.ns[b], tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     AiTable loc{(int *)ai_lds, (short *)(ai_lds + 4 * (size_t)hsize), (unsigned)(hsize - 1)};
     if (v.has_A) loc.build(v, p, n, tid, AI_NT);
     const AiRow x{b, p, &loc};
-    unsigned long long h1 = 0, h2 = 0;
+    DdHash h;
     for (int lr0 = blockIdx.y * (AI_NT / 64) + wv; lr0 < n; lr0 += (AI_NT / 64) * gridDim.y) {
-        const unsigned long long rowtag = (unsigned long long)(lr0 + 1) * 0xC2B2AE3D27D4EB4Full;
-        ai_row_walk<false>(v, x, x, lr0, lane, [&](unsigned long long w, unsigned long long pos) {
-            const unsigned long long k = ai_mix(w + 0x9E3779B97F4A7C15ull * (pos + 1) + rowtag);
-            h1 += k;
-            h2 += (k >> 32) * (k & 0xffffffffull);      // (second sum: the product of the halves of the mixed word; a full second mix was half of the kernel)
-        });
+        const unsigned long long rowtag = (unsigned long long)(lr0 + 1) * 0xC2B2AE3D27D4EB4Full;      // (added to the word: the row of the position)
+        ai_row_walk<false>(v, x, x, lr0, lane, [&](unsigned long long w, unsigned long long pos) { h.add(w + rowtag, pos); });
     }
-    if (tid == 0 && blockIdx.y == 0) { h1 += ai_mix((unsigned long long)n + 0x4444444444444444ull); h2 += ai_mix((unsigned long long)n ^ 0x7777777777777777ull); }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { h1 += __shfl_xor(h1, o, 64); h2 += __shfl_xor(h2, o, 64); }
-    if (lane == 0) { red[0][wv] = h1; red[1][wv] = h2; }
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long s1 = 0, s2 = 0;
-        for (int q = 0; q < AI_NT / 64; ++q) { s1 += red[0][q]; s2 += red[1][q]; }
-        atomicAdd(out + 2 * (size_t)b, s1);
-        atomicAdd(out + 2 * (size_t)b + 1, s2);
-    }
+    if (tid == 0 && blockIdx.y == 0) { h.h1 += dd_mix((unsigned long long)n + 0x4444444444444444ull); h.h2 += dd_mix((unsigned long long)n ^ 0x7777777777777777ull); }
+    h.block_finish<true>(out, b);
 }
 __global__ void scatter_int_kernel(int n, const int *__restrict__ idx, const int *__restrict__ src, int *__restrict__ dst) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1663,7 +1643,7 @@ __global__ __launch_bounds__(AI_NT) void asm_verify_kernel(AeInputs v, int hsize
     if (!ok) differ[b] = 1;
 }
 
-// Classes of identical agglomerates BEFORE their matrices are built (eig.hip, "Duplicate agglomerate matrices"): the fused
+// Classes of identical agglomerates BEFORE their matrices are built (dedupe.hip, "Duplicate agglomerate matrices"): the fused
 // kernel below makes the scaled matrix, its scaling and its band from the agglomerate's sparse rows (RW slots of column +
 // value per row) and its row order alone, so agglomerates whose rows and order agree bit for bit get identical matrices --
 // only one member of a class is built (and factored, and iterated): DdSource kind 0.
@@ -1718,51 +1698,31 @@ void ae_build(hipStream_t s, const DevRelations &rel, const DCsr *A, const DevEl
         // classes of identical agglomerates on the INPUTS of the assembly (AeInputs above): only their first members are assembled
         // and scaled -- as the batch of the representatives over the same workspace, through the same kernels the whole batch
         // would take (the choice between the one-kernel and the spread scaling is the whole batch's)
-        if (classes && scale && banded && !Dout && batch.count >= 16) {
+        if (classes && scale && banded && !Dout) {
             classes->searched = true;
             AeInputs v{batch.n.p, batch.voff.p, batch.has_perm ? batch.perm.p : nullptr, batch.has_x0c ? batch.x0c.p : nullptr,
                        rel.ae2d_I.p, rel.ae2d_J.p, rel.d2ae_I.p, rel.d2ae_J.p, rel.dof_id_inAE.p, rel.flags.p, rel.d2e_I.p, rel.d2e_J.p,
                        rel.part.p, rel.e2d_I.p, rel.e2d_J.p, rel.elem_ldof.p, el.off.p, el.val.p, A ? 1 : 0,
                        A ? A->rowptr.p : nullptr, A ? A->col.p : nullptr, A ? A->val.p : nullptr, ae0};
-            profiler().begin(s);
-            const int ny = std::max(1, std::min(div_up(batch.max_n, 256), 4096 / std::max(1, batch.count)));
-            DBuf<unsigned long long> hash(2 * (size_t)batch.count);
-            hash.zero(s);
+            const dim3 grid(batch.count, std::max(1, std::min(div_up(batch.max_n, 256), 4096 / std::max(1, batch.count))));
             int hsize = 64;
             while (hsize < batch.max_n + batch.max_n / 2) hsize <<= 1;
             const size_t tbytes = A ? 6 * (size_t)hsize : 0;      // (the tables are needed for the rows of the global matrix only)
-            SA_REQUIRE(2 * tbytes <= 150 * 1024, "agglomerate too large for the class search");
-            static bool attr_ai = false;
-            if (!attr_ai) {
-                SA_HIP_CHECK(hipFuncSetAttribute((const void *)asm_hash_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-                SA_HIP_CHECK(hipFuncSetAttribute((const void *)asm_verify_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-                attr_ai = true;
-            }
-            hipLaunchKernelGGL(asm_hash_kernel, dim3(batch.count, ny), dim3(256), tbytes, s, v, hsize, hash.p);
-            SA_HIP_CHECK(hipGetLastError());
-            auto hh = hash.to_host(s);
-            std::vector<int> rep;
-            const int nuniq = eig_dedupe_group(hh.data(), batch.count, rep);
-            bool found = (long)nuniq * 4 <= (long)batch.count * 3;
+            DdClasses &cl = classes->cls;
+            const bool found = dedupe_classes(
+                s, batch.count,
+                [&](unsigned long long *hash) {
+                    SA_REQUIRE(2 * tbytes <= 150 * 1024, "agglomerate too large for the class search");
+                    static bool attr_ai = false;
+                    if (!attr_ai) {
+                        SA_HIP_CHECK(hipFuncSetAttribute((const void *)asm_hash_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+                        SA_HIP_CHECK(hipFuncSetAttribute((const void *)asm_verify_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+                        attr_ai = true;
+                    }
+                    hipLaunchKernelGGL(asm_hash_kernel, grid, dim3(256), tbytes, s, v, hsize, hash);
+                },
+                [&](const int *rep, int *differ) { hipLaunchKernelGGL(asm_verify_kernel, grid, dim3(256), 2 * tbytes, s, v, hsize, rep, differ); }, cl);
             if (found) {
-                DBuf<int> d_rep, differ((size_t)batch.count);
-                d_rep.from_host(rep, s);
-                differ.zero(s);
-                hipLaunchKernelGGL(asm_verify_kernel, dim3(batch.count, ny), dim3(256), 2 * tbytes, s, v, hsize, d_rep.p, differ.p);
-                SA_HIP_CHECK(hipGetLastError());
-                auto hd = differ.to_host(s);
-                for (int i = 0; i < batch.count; ++i)
-                    if (hd[i]) rep[i] = i;
-            }
-            profiler().end(s, "eig_dedupe", 0.0, 0.0);
-            if (found) {
-                DdClasses &cl = classes->cls;
-                cl.reps.clear();
-                std::vector<int> pos((size_t)batch.count, -1);
-                for (int i = 0; i < batch.count; ++i)
-                    if (rep[i] == i) { pos[i] = (int)cl.reps.size(); cl.reps.push_back(i); }
-                cl.rep_of.resize((size_t)batch.count);
-                for (int i = 0; i < batch.count; ++i) cl.rep_of[i] = pos[rep[i]];
                 if ((batch.opt.debug & 1)) std::fprintf(stderr, "duplicate agglomerates (assembly inputs): %d distinct of %d\n", (int)cl.reps.size(), batch.count);
                 EigBatch cb;
                 eig_batch_compact(s, cb, batch, cl.reps);
@@ -2227,7 +2187,7 @@ __global__ __launch_bounds__(ASM_NT) void coarse_elmat_rows_kernel(
     }
 }
 
-// Classes of agglomerates with identical coarse element matrices (eig.hip, "Duplicate agglomerate matrices", one stage further
+// Classes of agglomerates with identical coarse element matrices (dedupe.hip, "Duplicate agglomerate matrices", one stage further
 // down the setup): E_e = P_loc^T A_e P_loc is a function of the agglomerate's sparse rows -- whose class the eigenproblem stage
 // has established, ae_class -- and of its MISes in their order: per MIS the number of basis vectors, the row list in the
 // agglomerate's numbering, the basis itself and the positions of its coarse dofs in the element.  CeIn names those arrays;
@@ -2276,22 +2236,10 @@ __device__ inline bool ce_walk(const CeIn &v, int e, int e2, int tid, int nt_, F
     return ok;
 }
 __global__ __launch_bounds__(256) void ce_hash_kernel(CeIn v, unsigned long long *__restrict__ out) {
-    __shared__ unsigned long long red[2][4];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    unsigned long long h1 = 0, h2 = 0;
-    ce_walk<false>(v, v.ae0 + b, 0, tid, 256, [&](unsigned long long w, unsigned long long pos) {
-        const unsigned long long k = ai_mix(w + 0x9E3779B97F4A7C15ull * (pos + 1));
-        h1 += k;
-        h2 += (k >> 32) * (k & 0xffffffffull);      // (second sum: the product of the halves of the mixed word; a full second mix was half of the kernel)
-    });
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { h1 += __shfl_xor(h1, o, 64); h2 += __shfl_xor(h2, o, 64); }
-    if ((tid & 63) == 0) { red[0][tid >> 6] = h1; red[1][tid >> 6] = h2; }
-    __syncthreads();
-    if (tid == 0) {
-        out[2 * (size_t)b] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-        out[2 * (size_t)b + 1] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-    }
+    const int b = blockIdx.x;
+    DdHash h;
+    ce_walk<false>(v, v.ae0 + b, 0, threadIdx.x, 256, [&](unsigned long long w, unsigned long long pos) { h.add(w, pos); });
+    h.block_finish<false>(out, b);
 }
 __global__ __launch_bounds__(256) void ce_verify_kernel(CeIn v, const int *__restrict__ rep, int *__restrict__ differ) {
     const int b = blockIdx.x, r0 = rep[b];
@@ -2319,35 +2267,18 @@ void coarse_elmats_sparse(hipStream_t s, const DevRelations &rel, int ae0, const
     std::vector<int> rep;
     DBuf<int> d_rep, d_list;
     int ncompute = batch.count;
-    if (ae_class && batch.count >= 16) {
-        profiler().begin(s);
+    if (ae_class) {
         CeIn v{ae_class, rel.ae2mis_I.p, rel.ae2mis_J.p, rel.ae_pair.p, rel.pair_loc_off.p, rel.pair_loc.p, rel.mis2d_I.p, mis_k,
                mis_u_off, mis_u, colpos_ptr, colpos, out_off, ae0};
-        DBuf<unsigned long long> hash(2 * (size_t)batch.count);
-        hipLaunchKernelGGL(ce_hash_kernel, dim3(batch.count), dim3(256), 0, s, v, hash.p);
-        SA_HIP_CHECK(hipGetLastError());
-        auto hh = hash.to_host(s);
-        const int nuniq = eig_dedupe_group(hh.data(), batch.count, rep);
-        if ((long)nuniq * 4 <= (long)batch.count * 3) {
-            DBuf<int> differ((size_t)batch.count);
+        DdClasses cl;
+        if (dedupe_classes(
+                s, batch.count, [&](unsigned long long *hash) { hipLaunchKernelGGL(ce_hash_kernel, dim3(batch.count), dim3(256), 0, s, v, hash); },
+                [&](const int *r, int *differ) { hipLaunchKernelGGL(ce_verify_kernel, dim3(batch.count), dim3(256), 0, s, v, r, differ); }, cl, &rep)) {
             d_rep.from_host(rep, s);
-            differ.zero(s);
-            hipLaunchKernelGGL(ce_verify_kernel, dim3(batch.count), dim3(256), 0, s, v, d_rep.p, differ.p);
-            SA_HIP_CHECK(hipGetLastError());
-            auto hd = differ.to_host(s);
-            std::vector<int> list;
-            for (int i = 0; i < batch.count; ++i) {
-                if (hd[i]) rep[i] = i;
-                if (rep[i] == i) list.push_back(i);
-            }
-            d_rep.from_host(rep, s);
-            d_list.from_host(list, s);
-            ncompute = (int)list.size();
+            d_list.from_host(cl.reps, s);
+            ncompute = (int)cl.reps.size();
             if (batch.opt.debug & 1) std::fprintf(stderr, "coarse element matrices: %d distinct of %d\n", ncompute, batch.count);
-        } else {
-            rep.clear();
         }
-        profiler().end(s, "eig_dedupe", 0.0, 0.0);
     }
     profiler().begin(s);
     // the packed rows of T of one agglomerate in LDS: a pool of 6 doubles per row on average (+ keys, column starts, offsets

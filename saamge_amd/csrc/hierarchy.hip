@@ -148,6 +148,27 @@ __global__ void fill_kernel(long n, double *p, double v) {
     if (i < n) p[i] = v;
 }
 
+// In-place all-gather of an array of which rank r holds the elements [at(begin[r]), at(begin[r + 1])), `bytes` bytes each.
+template <class Begin, class At>
+static void allgather_ranges(const Params &P, void *p, long long bytes, const Begin &begin, At at, const char *what) {
+    std::vector<long long> off(begin.size());
+    for (size_t r = 0; r < off.size(); ++r) off[r] = bytes * (long long)at(begin[r]);
+    SA_REQUIRE(P.allgather(P.allgather_ctx, p, off.data()) == 0, std::string("all-gather (") + what + ") failed");
+}
+static const auto same_index = [](long long i) { return i; };
+// how many items from i0 on (at least one, below i1) fit `budget` bytes
+template <class Bytes>
+static int fit_count(int i0, int i1, size_t budget, Bytes bytes_of) {
+    size_t bytes = 0;
+    int cnt = 0;
+    for (; i0 + cnt < i1; ++cnt) {
+        const size_t add = bytes_of(i0 + cnt);
+        if (cnt > 0 && bytes + add > budget) break;
+        bytes += add;
+    }
+    return cnt;
+}
+
 // ---------------------------------------------------------------------------------------
 // one coarsening: tg_init_data + tg_build_hierarchy + tg_update_coarse_operator
 // ---------------------------------------------------------------------------------------
@@ -164,11 +185,8 @@ static void level_galerkin(Hierarchy &H, int lev, bool first, hipStream_t s) {
         rap_mis(s, L.drel, rel, L.A, L.mis_k, L.mis_coloff, L.d_mis_k.p, L.d_mis_coloff.p,
                 L.d_mis_u_off.p, L.mis_U.p, L.Ac, P.rank, world, world > 1 ? &nnz_off : nullptr);
         if (world > 1 && L.Ac.nnz > 0) {   // every rank computed the row blocks of its MIS range
-            std::vector<long long> off((size_t)world + 1);
-            for (int r = 0; r <= world; ++r) off[r] = 4ll * nnz_off[r];
-            SA_REQUIRE(P.allgather(P.allgather_ctx, L.Ac.col.p, off.data()) == 0, "all-gather (Ac columns) failed");
-            for (int r = 0; r <= world; ++r) off[r] = 8ll * nnz_off[r];
-            SA_REQUIRE(P.allgather(P.allgather_ctx, L.Ac.val.p, off.data()) == 0, "all-gather (Ac values) failed");
+            allgather_ranges(P, L.Ac.col.p, 4, nnz_off, same_index, "Ac columns");
+            allgather_ranges(P, L.Ac.val.p, 8, nnz_off, same_index, "Ac values");
         }
     } else {
         // interp_smooth (amg/src/interp.cpp:172-229): P = prod_k (I + (1/tau_k) Dinv_neg A) P_tent with
@@ -223,36 +241,111 @@ struct DeviceInputs {   // level-0 inputs that already live on the device (see h
 static void prepare_next_host(const Level &L, const roff_t *p_rowptr_dev, const double *p_val_dev, int p_nrows,
                               int64_t p_nnz, hipStream_t s, NextPrep &out);
 
-static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &part, int nparts,
-                        const signed char *bdr_host, const DeviceInputs *din = nullptr) {
-    Level &L = *H.levels[lev];
-    hipStream_t s = H.stream;
-    const Params &P = H.params;
-    L.theta = P.theta[lev];
-    L.nu_relax = P.nu_relax[lev];
-    SA_REQUIRE(P.nu_pro[lev] >= 0 && P.nu_pro[lev] <= 8, "bad prolongator smoothing degree");
-    PhaseTimer tm(s);
+// ---- build_level: one coarsening as a sequence of stages over the state below ----
+// a worker that is joined before what it works on goes away
+struct JoinedThread { std::thread t; ~JoinedThread() { if (t.joinable()) t.join(); } };
+// packed eigenpairs of the agglomerates of one chunk of the eigenproblem stage
+struct Chunk { int ae0, count; DBuf<double> evals, evecs; std::vector<int64_t> eoff, xoff; DBuf<int64_t> d_eoff, d_xoff; };
+struct LevelBuild {
+    Hierarchy &H;
+    const int lev;
+    Level &L;
+    const Params &P;
+    hipStream_t s;
+    const int nparts, world, dev;
+    PhaseTimer tm;
+    // topology: the MIS tables are built on a host thread while the GPU solves the local eigenproblems
+    HostCsr aggA;
+    bool aggregates = false;
+    std::exception_ptr mis_err;
+    bool operator_pending = false;      // the level's operator is still in the making (deferred Galerkin product of the finer level)
+    // local eigenproblems: sizes and ownership of the agglomerates, the chunks' results
+    bool keep_rows = false;
+    std::vector<int> sizes, ae_begin;
+    int ae_lo = 0, ae_hi = 0;
+    std::vector<Chunk> chunks;
+    // (batches: what the eigensolvers run on -- the assembled batch itself, or the batch of the representatives of its
+    // classes of bitwise identical matrices, dedupe.hip "Duplicate agglomerate matrices")
+    EigBatch batches[2], assembled[2];
+    LevelClasses classes;
+    std::vector<DBuf<double>> kept;          // packed eigenpairs of the chunks' representatives
+    std::vector<int> cls_of[2];              // per slot: class of every agglomerate of the chunk (empty: no classes)
+    std::vector<int> solve_cls[2];           // per slot: classes of the matrices of the batch that is solved, in its order
+    bool dedupe = false, dedupe_level = true;
+    int pend_ae0[2] = {0, 0}, pend_cnt[2] = {0, 0};
+    int64_t pend_row0[2] = {0, 0};
+    bool counted[2] = {false, false};
+    bool overlap_iter = false;
+    hipStream_t iter_stream = nullptr;
+    std::exception_ptr iter_err;
+    JoinedThread mis_thread, iter_thread;      // (last: joined first)
+
+    LevelBuild(Hierarchy &H_, int lev_, int nparts_) : H(H_), lev(lev_), L(*H_.levels[lev_]), P(H_.params), s(H_.stream), nparts(nparts_),
+                                                       world(H_.params.world > 1 ? H_.params.world : 1), dev(current_device()), tm(H_.stream) {}
+    const DCsr *fine_A() const { return lev == 0 ? &L.A : nullptr; }
+};
+
+// positions of agglomerate ae's rows among the rows of the agglomerates [ae_lo, ae_hi) of this rank
+static RowsSpan rows_span(const Relations &rel, int ae, int ae_lo, int ae_hi) {
+    const auto &I = rel.AE_to_dof.I;
+    return RowsSpan{(int64_t)I[ae] - (int64_t)I[ae_lo], (int64_t)I[ae_hi] - (int64_t)I[ae_lo]};
+}
+// offsets of packed eigenvalues (m_i each) and eigenvectors (n_i x m_i each)
+static void packed_offsets(int count, const int *m, const int *n, std::vector<int64_t> &eoff, std::vector<int64_t> &xoff) {
+    eoff.assign((size_t)count + 1, 0);
+    xoff.assign((size_t)count + 1, 0);
+    for (int i = 0; i < count; ++i) {
+        eoff[i + 1] = eoff[i] + m[i];
+        xoff[i + 1] = xoff[i] + (int64_t)m[i] * n[i];
+    }
+}
+// contiguous ranges of [0, n), one per rank, balanced by cost(i): begin[r] .. begin[r + 1]
+template <class Cost>
+static std::vector<int> balanced_ranges(int n, int world, Cost cost) {
+    std::vector<int> begin((size_t)world + 1, n);
+    double total = 0.0;
+    for (int i = 0; i < n; ++i) total += cost(i);
+    double run = 0.0;
+    int r = 0;
+    begin[0] = 0;
+    for (int i = 0; i < n && r + 1 < world; ++i) {
+        run += cost(i);
+        while (r + 1 < world && run >= total * (r + 1) / world) begin[++r] = i + 1;
+    }
+    begin[world] = n;
+    return begin;
+}
+
+// SELL-64 copy of the level operator for the SpMV family + smoother data (smpr_init_poly_data,
+// amg/src/smpr.cpp:359-423)
+static void level_operator_data(Level &L, const Params &P, hipStream_t s) {
+    build_sell(s, L.A, P.opt);
+    L.dinv_neg.alloc((size_t)L.A.nrows);
+    DBuf<double> tmp((size_t)L.A.nrows);
+    build_dinv_neg(s, L.A, tmp.p, L.dinv_neg.p);
+    build_dinv_codes(s, L.A, L.dinv_neg.p, P.opt);
+    SA_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// Stage 1: the agglomerate tables, the start of the MIS-table thread, the operator's SELL copy and smoother data.
+static void level_topology(LevelBuild &B, Table &&e2d, const hvec<int> &part, const signed char *bdr_host, const DeviceInputs *din) {
+    Hierarchy &H = B.H; Level &L = B.L; const Params &P = B.P; hipStream_t s = B.s;
+    const int lev = B.lev, nparts = B.nparts;
     // Fine level, device-resident inputs: the SELL copy of the operator and the smoother diagonal (bandwidth work on A alone) are
     // built on a thread and stream of their own BESIDE the device build of the AE tables (integer work on elem_to_dof: sorts,
     // hash sets, atomics), and joined where they used to run, before the eigenproblems.
-    std::thread op_thread;
     std::exception_ptr op_err;
-    struct OpJoiner { std::thread &t; ~OpJoiner() { if (t.joinable()) t.join(); } } op_joiner{op_thread};
+    JoinedThread op_thread;
     const bool op_early = lev == 0 && din && !env_serial() && !profiler().enabled && H.galerkin_lev < 0 && (P.opt.overlap & 8);
     if (op_early) {
         hipStream_t os = side_stream(6);
-        const int dev0 = current_device();
+        const int dev0 = B.dev;
         SA_HIP_CHECK(hipStreamSynchronize(s));          // (the operator's arrays are complete)
-        op_thread = std::thread([&L, &P, &op_err, os, dev0]() {
+        op_thread.t = std::thread([&L, &P, &op_err, os, dev0]() {
             try {
                 adopt_device(dev0);
                 set_thread_stream(os);
-                build_sell(os, L.A, P.opt);
-                L.dinv_neg.alloc((size_t)L.A.nrows);
-                DBuf<double> tmp((size_t)L.A.nrows);
-                build_dinv_neg(os, L.A, tmp.p, L.dinv_neg.p);
-                build_dinv_codes(os, L.A, L.dinv_neg.p, P.opt);
-                SA_HIP_CHECK(hipStreamSynchronize(os));
+                level_operator_data(L, P, os);
             } catch (...) { op_err = std::current_exception(); }
         });
     }
@@ -260,7 +353,7 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
     if (din) {
         on_device = build_relations_ae_device(L.rel, L.drel, din->e2d, din->NE, din->nde, din->e2d_I, din->part, nparts,
                                               L.A.nrows, din->bdr, s);
-        tm.lap("device topology (AE tables)", lev);
+        B.tm.lap("device topology (AE tables)", lev);
     }
     if (!on_device) {
         hvec<int> part_h;
@@ -280,16 +373,16 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
         if (!L.rel_prebuilt)
             build_relations_ae(L.rel, std::move(e2d), din ? part_h : part, nparts, L.A.nrows,
                                din ? (din->bdr ? bdr_h.data() : nullptr) : bdr_host);
-        tm.lap(L.rel_prebuilt ? "host topology (built beside the element matrices)" : "host topology (AE tables)", lev);
+        B.tm.lap(L.rel_prebuilt ? "host topology (built beside the element matrices)" : "host topology (AE tables)", lev);
         upload_relations_ae(L.drel, L.rel, s);
-        tm.lap("upload topology", lev);
+        B.tm.lap("upload topology", lev);
     }
     // the MIS tables are built on a host thread while the GPU solves the local eigenproblems
     // (do_aggregates, amg/src/ml.cpp:149: aggregates with arbitration on the LAST coarsening; the
     // greedy arbitration reads the level matrix on the host)
-    HostCsr aggA;
-    const bool aggregates = P.do_aggregates && lev == P.num_coarsenings - 1;
-    if (aggregates) {
+    HostCsr &aggA = B.aggA;
+    B.aggregates = P.do_aggregates && lev == P.num_coarsenings - 1;
+    if (B.aggregates) {
         join_galerkin(H);     // the arbitration reads this level's operator
         aggA.nrows = L.A.nrows;
         aggA.rowptr.resize((size_t)L.A.nrows + 1);
@@ -302,354 +395,303 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
     }
     // (the tables go to the device from the same thread, on a side stream, while the eigensolver runs)
     hipStream_t mis_stream = side_stream(0);
-    const int dev = current_device();
-    std::exception_ptr mis_err;
     // SAAMGE_AMD_SERIAL=1: no worker threads anywhere in the setup (counter passes attribute launches per thread; the
     // work runs in line, same streams).  The "stream_stack.cpp: Check failed" aborts once seen under rocprofv3 --pmc came
     // from static destructors calling HIP at exit (fixed in round 4: those objects are never destroyed), not from threads
-    const bool serial = env_serial();
-    auto mis_work = [&]() {
+    auto mis_work = [&B, mis_stream]() {
+        Level &L = B.L;
         try {
-            adopt_device(dev);   // the worker allocates and copies: same GPU as the caller
+            adopt_device(B.dev);   // the worker allocates and copies: same GPU as the caller
             set_thread_stream(mis_stream);
             // MIS tables on the device; aggregates with arbitration are
             // sequential by definition and stay on the host
             constexpr bool host_mis = false;      // (the host build stays the fallback after a hash collision and for aggregates with arbitration)
             PhaseTimer tmis(mis_stream);
             bool on_dev = false;
-            if (!aggregates && !host_mis) on_dev = build_relations_mis_device(L.rel, L.drel, mis_stream);
-            if (on_dev) tmis.lap("    device MIS tables", lev);
+            if (!B.aggregates && !host_mis) on_dev = build_relations_mis_device(L.rel, L.drel, mis_stream);
+            if (on_dev) tmis.lap("    device MIS tables", B.lev);
             if (!on_dev) {
                 fetch_relations_ae_host(L.rel, L.drel, mis_stream);
-                build_relations_mis(L.rel, aggregates ? &aggA : nullptr);
+                build_relations_mis(L.rel, B.aggregates ? &B.aggA : nullptr);
                 upload_relations_mis(L.drel, L.rel, mis_stream);
             }
             SA_HIP_CHECK(hipStreamSynchronize(mis_stream));
-        } catch (...) { mis_err = std::current_exception(); }
+        } catch (...) { B.mis_err = std::current_exception(); }
     };
-    std::thread mis_thread;
-    if (serial) {
+    if (env_serial()) {
         mis_work();
         set_thread_stream(s);
     } else {
-        mis_thread = std::thread(mis_work);
+        B.mis_thread.t = std::thread(mis_work);
     }
-    struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{mis_thread};
-    const Relations &rel = L.rel;
-    // SELL-64 copy of the level operator for the SpMV family + smoother data (smpr_init_poly_data,
-    // amg/src/smpr.cpp:359-423); on a coarse level the operator may still be in the making (deferred
+    // the operator's SELL copy and smoother data; on a coarse level the operator may still be in the making (deferred
     // Galerkin product of the finer level): then after the eigenproblems, which do not read it
-    auto operator_data = [&]() {
-        join_galerkin(H);
-        build_sell(s, L.A, P.opt);
-        L.dinv_neg.alloc((size_t)L.A.nrows);
-        DBuf<double> tmp((size_t)L.A.nrows);
-        build_dinv_neg(s, L.A, tmp.p, L.dinv_neg.p);
-        build_dinv_codes(s, L.A, L.dinv_neg.p, P.opt);
-        SA_HIP_CHECK(hipStreamSynchronize(s));
-    };
-    const bool operator_pending = H.galerkin_lev >= 0;
+    B.operator_pending = H.galerkin_lev >= 0;
     // (Measured in round 4 and dropped: the fine level's SELL copy and D^-1 -- 13 ms of bandwidth work the setup itself does not
     // need -- on a thread and stream of their own beside the next level: setup 247 -> 243 ms, but the smoother then ran at 221
     // instead of 216 us per step and the step took 399 instead of 390 ms.)
     if (op_early) {
-        op_thread.join();
+        op_thread.t.join();
         if (op_err) std::rethrow_exception(op_err);
-    } else if (!operator_pending) operator_data();
+    } else if (!B.operator_pending) {
+        join_galerkin(H);
+        level_operator_data(L, P, s);
+    }
     L.roots = sas_poly_roots(L.nu_relax);
+}
 
-    // ---- local spectral problems, chunked over AEs (interp_compute_vectors) ----
+// ---- stage 2: local spectral problems, chunked over AEs (interp_compute_vectors) ----
+// sizes and ownership of the agglomerates, the level's per-agglomerate results cleared
+static void eig_stage_begin(LevelBuild &B) {
+    Hierarchy &H = B.H; Level &L = B.L; const Params &P = B.P; const Relations &rel = L.rel;
+    const int lev = B.lev, nparts = B.nparts, world = B.world;
     // (the sparse rows of the fine AE matrices are kept for the coarse element matrices of the next
     // level when there is one: ~10 bytes per stored entry of the overlapping AE rows)
-    const bool keep_rows = lev == 0 && lev + 1 < P.num_coarsenings &&
-                           (double)L.rel.AE_to_dof.I[nparts] * 30.0 * 10.0 < 32e9;
-    std::vector<int> sizes((size_t)nparts);
+    B.keep_rows = lev == 0 && lev + 1 < P.num_coarsenings && (double)rel.AE_to_dof.I[nparts] * 30.0 * 10.0 < 32e9;
+    std::vector<int> &sizes = B.sizes;
+    sizes.resize((size_t)nparts);
     for (int p = 0; p < nparts; ++p) sizes[p] = rel.AE_to_dof.row_size(p);
     L.ae_m.assign((size_t)nparts, 0);
     L.ae_solved = 0;
     if (L.order_info.n != 4) L.order_info.alloc(4);
-    L.order_info.zero(s);
+    L.order_info.zero(B.s);
     L.order_chunks.clear();
     L.ae_class.assign((size_t)nparts, -1);
     L.ae_evclass.assign((size_t)nparts, -1);
-    struct Chunk { int ae0, count; DBuf<double> evals, evecs; std::vector<int64_t> eoff, xoff; DBuf<int64_t> d_eoff, d_xoff; };
-    std::vector<Chunk> chunks;
     if (P.keep_debug) L.ae_D.alloc((size_t)rel.AE_to_dof.I[nparts]);
     // AE ownership: contiguous ranges balanced by the n^3 cost of the eigenproblems
-    const int world = P.world > 1 ? P.world : 1;
-    std::vector<int> ae_begin((size_t)world + 1, nparts);
-    {
-        double total = 0.0;
-        for (int p = 0; p < nparts; ++p) total += (double)sizes[p] * sizes[p] * sizes[p];
-        double run = 0.0;
-        int r = 0;
-        ae_begin[0] = 0;
-        for (int p = 0; p < nparts && r + 1 < world; ++p) {
-            run += (double)sizes[p] * sizes[p] * sizes[p];
-            while (r + 1 < world && run >= total * (r + 1) / world) ae_begin[++r] = p + 1;
-        }
-        ae_begin[world] = nparts;
-    }
+    B.ae_begin = balanced_ranges(nparts, world, [&](int p) { return (double)sizes[p] * sizes[p] * sizes[p]; });
     if (H.dist_in && lev < (int)H.dist_in->ae_begin.size()) {
         // per-rank inputs: a rank owns the agglomerates made of its own elements (only their element matrices are here)
         const std::vector<long long> &ab = H.dist_in->ae_begin[lev];
         SA_REQUIRE((int)ab.size() == world + 1 && ab[world] == nparts, "per-rank inputs: agglomerate ranges do not match the level");
-        for (int r = 0; r <= world; ++r) ae_begin[r] = (int)ab[r];
+        for (int r = 0; r <= world; ++r) B.ae_begin[r] = (int)ab[r];
     }
     if (world > 1) {
         SA_REQUIRE(P.allgather != nullptr, "world > 1 needs an all-gather callback");
         SA_REQUIRE(!(P.testmesh && lev == 0), "the mltest fixture is single-rank only");
     }
-    const int ae_lo = ae_begin[world > 1 ? P.rank : 0], ae_hi = ae_begin[world > 1 ? P.rank + 1 : 1];
-    L.ae_begin = ae_begin;
-    int64_t row0 = 0;
-    for (int p = 0; p < ae_lo; ++p) row0 += sizes[p];
-    // (a two-stream pipeline over the chunks -- band reduction of chunk i beside the chase of chunk
-    // i-1 -- was measured without gain on MI355X, 256^3: 3.48 s vs 3.29 s, and removed)
-    hipStream_t qa = s, qb = s;
-    SA_HIP_CHECK(hipStreamSynchronize(s));
-    const size_t chunk_bytes = P.workspace_bytes;
-    // (batches: what the eigensolvers run on -- the assembled batch itself, or the batch of the representatives of its
-    // classes of bitwise identical matrices, eig.hip "Duplicate agglomerate matrices"; rep_of: empty = no classes)
-    EigBatch batches[2], assembled[2];
-    // Classes of bitwise identical agglomerates of this level (a rank's part of it): the first member met is solved, in
-    // the chunk it sits in; every later member -- of that chunk or a later one -- receives a copy.  A class keeps the words
-    // it consists of (the first member's: sparse rows or band, eig.h DdSource), against which the candidates of later
-    // chunks are compared word by word, and where its eigenpairs are.
-    struct SolvedClass {
-        int n = 0, m = 0, kind = 0;
-        bool bad = false;           // the few-eigenpairs path gave up on it: every member is redone by the dense path
-        long words = 0;
-        DBuf<unsigned long long> blob;
-        const double *evals = nullptr, *evecs = nullptr;
-    };
-    std::vector<SolvedClass> lvl_classes;
-    std::unordered_map<DdKey, std::vector<int>, DdKeyHash> lvl_by_hash;
-    std::vector<DBuf<double>> kept;          // packed eigenpairs of the chunks' representatives
-    std::vector<int> cls_of[2];              // per slot: class of every agglomerate of the chunk (empty: no classes)
-    std::vector<int> solve_cls[2];           // per slot: classes of the matrices of the batch that is solved, in its order
-    const bool dedupe = P.opt.eig_dedupe != 0 && !(P.testmesh && lev == 0);
-    bool dedupe_level = true;
-    int pend_ae0[2] = {0, 0}, pend_cnt[2] = {0, 0};
-    int64_t pend_row0[2] = {0, 0};
+    B.ae_lo = B.ae_begin[world > 1 ? P.rank : 0];
+    B.ae_hi = B.ae_begin[world > 1 ? P.rank + 1 : 1];
+    L.ae_begin = B.ae_begin;
+    B.dedupe = P.opt.eig_dedupe != 0 && !(P.testmesh && lev == 0);
     // The subspace iteration of a chunk (a few hundred to a few thousand small matrices still active: launches that
     // fill a fraction of the chip, with a host round trip every few iterations) runs on its own thread and stream
     // BESIDE the assembly and the factorisations of the next chunk (Options::overlap bit 0 cleared: one after the other).
     // Only eig_subspace_iterate runs there: it touches its own batch (the other workspace slot) and nothing else;
     // everything that assembles or allocates workspace stays on this thread.
-    const bool overlap_env = (P.opt.overlap & 1) && !env_serial();
-    const bool overlap_iter = overlap_env && !profiler().enabled;
-    hipStream_t iter_stream = overlap_iter ? side_stream(3) : s;
-    std::thread iter_thread;
-    std::exception_ptr iter_err;
-    struct IterJoiner { std::thread &t; ~IterJoiner() { if (t.joinable()) t.join(); } } iter_joiner{iter_thread};
-    bool counted[2] = {false, false};
-    auto start_iterate = [&](int slot) {
-        EigBatch &batch = batches[slot];
-        counted[slot] = false;
-        if (!overlap_iter || !batch.subspace || batch.ss_failed || !batch.count) return;
-        counted[slot] = true;
-        iter_thread = std::thread([&, slot]() {
-            try {
-                adopt_device(dev);
-                set_thread_stream(iter_stream);
-                eig_count(iter_stream, batches[slot], -1.0, L.theta);
-                SA_HIP_CHECK(hipStreamSynchronize(iter_stream));
-            } catch (...) { iter_err = std::current_exception(); }
-        });
+    B.overlap_iter = (P.opt.overlap & 1) && !env_serial() && !profiler().enabled;
+    B.iter_stream = B.overlap_iter ? side_stream(3) : B.s;
+}
+static void eig_start_iterate(LevelBuild &B, int slot) {
+    EigBatch &batch = B.batches[slot];
+    B.counted[slot] = false;
+    if (!B.overlap_iter || !batch.subspace || batch.ss_failed || !batch.count) return;
+    B.counted[slot] = true;
+    B.iter_thread.t = std::thread([&B, slot]() {
+        try {
+            adopt_device(B.dev);
+            set_thread_stream(B.iter_stream);
+            eig_count(B.iter_stream, B.batches[slot], -1.0, B.L.theta);
+            SA_HIP_CHECK(hipStreamSynchronize(B.iter_stream));
+        } catch (...) { B.iter_err = std::current_exception(); }
+    });
+}
+static void eig_join_iterate(LevelBuild &B) {
+    if (B.iter_thread.t.joinable()) B.iter_thread.t.join();
+    if (B.iter_err) { std::exception_ptr e = B.iter_err; B.iter_err = nullptr; std::rethrow_exception(e); }
+}
+// the dense path on (re-)assembled matrices: batch b = the agglomerates from ae0 on, whose first row is row0 of the rank's
+static void eig_dense_pass(LevelBuild &B, EigBatch &b, int ae0, int64_t row0) {
+    const RowsSpan span = rows_span(B.L.rel, ae0, B.ae_lo, B.ae_hi);
+    ae_build(B.s, B.L.drel, B.fine_A(), B.L.elmat, ae0, b, true, B.P.keep_debug ? B.L.ae_D.p + row0 : nullptr, B.keep_rows ? &span : nullptr);
+    eig_tridiagonalize(B.s, b, 3);
+    eig_count(B.s, b, -1.0, B.L.theta);
+}
+// The few-eigenpairs path finished all but a few matrices of chunk c (bad): those are redone by the dense path, as
+// contiguous runs of agglomerates (runs closer than three apart are joined), in the workspace the chunk has just left;
+// then the chunk's packed results are put together.  m_all: eigenvector counts of the first pass (0 for the bad ones).
+static void eig_redo_bad(LevelBuild &B, int slot, Chunk &c, std::vector<int> m_all, std::vector<char> bad) {
+    Level &L = B.L; const Params &P = B.P; hipStream_t s = B.s;
+    const int ae0 = c.ae0, cnt = c.count;
+    const int *sizes = B.sizes.data() + ae0;
+    for (int i = 0; i < cnt; ++i)
+        if (bad[i])
+            for (int j = i + 1; j < std::min(cnt, i + 4); ++j)
+                if (bad[j]) { for (int q = i + 1; q < j; ++q) bad[q] = 1; break; }
+    std::vector<Chunk> redo;      // (a run: ae0 = its first agglomerate within the chunk)
+    for (int a = 0; a < cnt;) {
+        if (!bad[a]) { ++a; continue; }
+        int e = a;
+        while (e < cnt && bad[e]) ++e;
+        redo.emplace_back();
+        Chunk &r = redo.back();
+        r.ae0 = a;
+        r.count = e - a;
+        EigBatch sub;
+        eig_batch_alloc(sub, std::vector<int>(sizes + a, sizes + e), P.opt, s, slot);
+        sub.dense_only = true;
+        sub.set_window(L.theta);
+        eig_dense_pass(B, sub, ae0 + a, B.pend_row0[slot] + L.rel.AE_to_dof.I[ae0 + a] - L.rel.AE_to_dof.I[ae0]);
+        std::copy(sub.h_m.begin(), sub.h_m.begin() + (e - a), m_all.begin() + a);
+        packed_offsets(e - a, sub.h_m.data(), sizes + a, r.eoff, r.xoff);
+        r.evals.alloc((size_t)r.eoff.back() + 1);
+        r.evecs.alloc((size_t)r.xoff.back() + 1);
+        r.d_eoff.from_host(r.eoff, s);
+        r.d_xoff.from_host(r.xoff, s);
+        eig_vectors(s, sub, r.d_eoff.p, r.d_xoff.p, r.evals.p, r.evecs.p);
+        SA_HIP_CHECK(hipStreamSynchronize(s));
+        a = e;
+    }
+    // packed results of the whole chunk: stretches of finished matrices from the first pass, the runs from `redo`
+    std::vector<int64_t> eoff, xoff;
+    std::copy(m_all.begin(), m_all.end(), L.ae_m.begin() + ae0);
+    packed_offsets(cnt, m_all.data(), sizes, eoff, xoff);
+    DBuf<double> evals((size_t)eoff[cnt]), evecs((size_t)xoff[cnt]);
+    auto copy = [&](double *dst, const double *src, int64_t n_) {
+        if (n_ > 0) SA_HIP_CHECK(hipMemcpyAsync(dst, src, 8 * (size_t)n_, hipMemcpyDeviceToDevice, s));
     };
-    auto join_iterate = [&]() {
-        if (iter_thread.joinable()) iter_thread.join();
-        if (iter_err) { std::exception_ptr e = iter_err; iter_err = nullptr; std::rethrow_exception(e); }
-    };
-    auto post = [&](int slot) {   // band -> tridiagonal, counts, eigenvectors of the chunk in `slot`
-        EigBatch &batch = batches[slot];
-        const int ae0 = pend_ae0[slot], cnt = pend_cnt[slot];
-        const std::vector<int> &co = cls_of[slot];
-        bool have = batch.count > 0;      // (with classes: the batch of the NEW classes' representatives, possibly empty)
-        if (have && !counted[slot]) {
-            eig_tridiagonalize(qb, batch, 2);
-            eig_count(qb, batch, -1.0, L.theta);
+    size_t ri = 0;
+    for (int i = 0; i < cnt;) {
+        if (ri < redo.size() && redo[ri].ae0 == i) {
+            const Chunk &r = redo[ri++];
+            copy(evals.p + eoff[i], r.evals.p, r.eoff.back());
+            copy(evecs.p + xoff[i], r.evecs.p, r.xoff.back());
+            i = r.ae0 + r.count;
+        } else {
+            const int e = ri < redo.size() ? redo[ri].ae0 : cnt;       // finished matrices i .. e - 1: contiguous in both
+            copy(evals.p + eoff[i], c.evals.p + c.eoff[i], c.eoff[e] - c.eoff[i]);
+            copy(evecs.p + xoff[i], c.evecs.p + c.xoff[i], c.xoff[e] - c.xoff[i]);
+            i = e;
         }
-        if (have && batch.ss_failed && !co.empty()) {      // the new classes go to the dense path, member by member (below)
-            for (int id : solve_cls[slot]) lvl_classes[id].bad = true;
-            have = false;
-        }
-        if (have && batch.ss_failed) {   // few-eigenpairs path gave up on this chunk: dense path on re-assembled matrices
-            batch.dense_only = true;
-            batch.subspace = batch.ss_failed = false;
-            const RowsSpan span{(int64_t)L.rel.AE_to_dof.I[ae0] - (int64_t)L.rel.AE_to_dof.I[ae_lo], (int64_t)L.rel.AE_to_dof.I[ae_hi] - (int64_t)L.rel.AE_to_dof.I[ae_lo]};      // (positions among the rows of this rank's agglomerates)
-            ae_build(qb, L.drel, lev == 0 ? &L.A : nullptr, L.elmat, ae0, batch, true,
-                     P.keep_debug ? L.ae_D.p + pend_row0[slot] : nullptr, keep_rows ? &span : nullptr);
-            eig_tridiagonalize(qb, batch, 3);
-            eig_count(qb, batch, -1.0, L.theta);
-        }
-        chunks.emplace_back();
-        Chunk &c = chunks.back();
-        c.ae0 = ae0;
-        c.count = cnt;
-        c.eoff.assign((size_t)cnt + 1, 0);
-        c.xoff.assign((size_t)cnt + 1, 0);
-        // per agglomerate of the chunk: eigenvector count and "redo by the dense path" -- its own, or its class's
-        std::vector<int> hm((size_t)cnt);
-        std::vector<char> hbad((size_t)cnt, 0);
-        bool some_bad = have && batch.subspace && batch.nbad > 0;
-        if (!co.empty() && have) {      // the eigenpairs of the classes solved in this chunk, packed; kept for the later members
-            const int nr = batch.count;
-            std::vector<int64_t> re((size_t)nr + 1, 0), rx((size_t)nr + 1, 0);
-            for (int r = 0; r < nr; ++r) {
-                re[r + 1] = re[r] + batch.h_m[r];
-                rx[r + 1] = rx[r] + (int64_t)batch.h_m[r] * batch.h_n[r];
-            }
-            kept.emplace_back((size_t)re[nr] + 1);
-            double *revals = kept.back().p;
-            kept.emplace_back((size_t)rx[nr] + 1);
-            double *revecs = kept.back().p;
-            DBuf<int64_t> d_re, d_rx;
-            d_re.from_host(re, qb);
-            d_rx.from_host(rx, qb);
-            eig_vectors(qb, batch, d_re.p, d_rx.p, revals, revecs);
-            SA_HIP_CHECK(hipStreamSynchronize(qb));
-            for (int r = 0; r < nr; ++r) {
-                SolvedClass &sc = lvl_classes[solve_cls[slot][r]];
-                sc.m = batch.h_m[r];
-                sc.bad = some_bad && batch.h_bad[r];
-                sc.evals = revals + re[r];
-                sc.evecs = revecs + rx[r];
-            }
-        }
-        some_bad = co.empty() ? some_bad : false;
-        for (int i = 0; i < cnt; ++i) {
-            if (co.empty()) {
-                hm[i] = batch.h_m[i];
-                if (some_bad) hbad[i] = batch.h_bad[i];
-            } else {
-                const SolvedClass &sc = lvl_classes[co[i]];
-                if (sc.kind == 0) L.ae_class[ae0 + i] = co[i];
-                if (!sc.bad) L.ae_evclass[ae0 + i] = co[i];
-                hm[i] = sc.bad ? 0 : sc.m;
-                hbad[i] = sc.bad ? 1 : 0;
-                some_bad = some_bad || sc.bad;
-            }
-        }
-        for (int i = 0; i < cnt; ++i) {
-            L.ae_m[ae0 + i] = hm[i];
-            c.eoff[i + 1] = c.eoff[i] + hm[i];
-            c.xoff[i + 1] = c.xoff[i] + (int64_t)hm[i] * sizes[ae0 + i];
-        }
-        c.evals.alloc((size_t)c.eoff[cnt]);
-        c.evecs.alloc((size_t)c.xoff[cnt]);
-        c.d_eoff.from_host(c.eoff, qb);
-        c.d_xoff.from_host(c.xoff, qb);
+    }
+    SA_HIP_CHECK(hipStreamSynchronize(s));
+    c.evals = std::move(evals);
+    c.evecs = std::move(evecs);
+    c.eoff = eoff;
+    c.xoff = xoff;
+}
+// band -> tridiagonal, counts, eigenvectors of the chunk in `slot`
+static void eig_chunk_finish(LevelBuild &B, int slot) {
+    Level &L = B.L; hipStream_t s = B.s;
+    EigBatch &batch = B.batches[slot];
+    const int ae0 = B.pend_ae0[slot], cnt = B.pend_cnt[slot];
+    const int *sizes = B.sizes.data() + ae0;
+    const std::vector<int> &co = B.cls_of[slot];
+    bool have = batch.count > 0;      // (with classes: the batch of the NEW classes' representatives, possibly empty)
+    if (have && !B.counted[slot]) {
+        eig_tridiagonalize(s, batch, 2);
+        eig_count(s, batch, -1.0, L.theta);
+    }
+    if (have && batch.ss_failed && !co.empty()) {      // the new classes go to the dense path, member by member (below)
+        for (int id : B.solve_cls[slot]) B.classes.mark_bad(id);
+        have = false;
+    }
+    if (have && batch.ss_failed) {   // few-eigenpairs path gave up on this chunk: dense path on re-assembled matrices
+        batch.dense_only = true;
+        batch.subspace = batch.ss_failed = false;
+        eig_dense_pass(B, batch, ae0, B.pend_row0[slot]);
+    }
+    B.chunks.emplace_back();
+    Chunk &c = B.chunks.back();
+    c.ae0 = ae0;
+    c.count = cnt;
+    // per agglomerate of the chunk: eigenvector count and "redo by the dense path" -- its own, or its class's
+    std::vector<int> hm((size_t)cnt);
+    std::vector<char> hbad((size_t)cnt, 0);
+    bool some_bad = have && batch.subspace && batch.nbad > 0;
+    if (!co.empty() && have) {      // the eigenpairs of the classes solved in this chunk, packed; kept for the later members
+        const int nr = batch.count;
+        std::vector<int64_t> re, rx;
+        packed_offsets(nr, batch.h_m.data(), batch.h_n.data(), re, rx);
+        B.kept.emplace_back((size_t)re[nr] + 1);
+        double *revals = B.kept.back().p;
+        B.kept.emplace_back((size_t)rx[nr] + 1);
+        double *revecs = B.kept.back().p;
+        DBuf<int64_t> d_re, d_rx;
+        d_re.from_host(re, s);
+        d_rx.from_host(rx, s);
+        eig_vectors(s, batch, d_re.p, d_rx.p, revals, revecs);
+        SA_HIP_CHECK(hipStreamSynchronize(s));
+        for (int r = 0; r < nr; ++r)
+            B.classes.set_result(B.solve_cls[slot][r], batch.h_m[r], some_bad && batch.h_bad[r], revals + re[r], revecs + rx[r]);
+    }
+    some_bad = co.empty() ? some_bad : false;
+    for (int i = 0; i < cnt; ++i) {
         if (co.empty()) {
-            eig_vectors(qb, batch, c.d_eoff.p, c.d_xoff.p, c.evals.p, c.evecs.p);
-        } else {      // a copy of its class's eigenpairs to every agglomerate
-            std::vector<const double *> pe((size_t)cnt), px((size_t)cnt);
-            for (int i = 0; i < cnt; ++i) { pe[i] = lvl_classes[co[i]].evals; px[i] = lvl_classes[co[i]].evecs; }
-            DBuf<const double *> d_pe, d_px;
-            d_pe.from_host(pe, qb);
-            d_px.from_host(px, qb);
-            eig_dedupe_expand(qb, cnt, sizes.empty() ? 1 : *std::max_element(sizes.begin() + ae0, sizes.begin() + ae0 + cnt), d_pe.p, d_px.p,
-                              c.d_eoff.p, c.d_xoff.p, c.evals.p, c.evecs.p);
+            hm[i] = batch.h_m[i];
+            if (some_bad) hbad[i] = batch.h_bad[i];
+        } else {
+            const LevelClasses::Entry &sc = B.classes[co[i]];
+            if (sc.kind == 0) L.ae_class[ae0 + i] = co[i];
+            if (!sc.bad) L.ae_evclass[ae0 + i] = co[i];
+            hm[i] = sc.bad ? 0 : sc.m;
+            hbad[i] = sc.bad ? 1 : 0;
+            some_bad = some_bad || sc.bad;
         }
-        SA_HIP_CHECK(hipStreamSynchronize(qb));
-        if (!some_bad) return;
-        // ---- the few-eigenpairs path finished all but a few matrices of the chunk (h_bad): those are redone by
-        // the dense path, as contiguous runs of agglomerates (runs closer than three apart are joined), in the
-        // workspace the chunk has just left; then the chunk's packed results are put together ----
-        std::vector<char> bad(hbad.begin(), hbad.end());
-        for (int i = 0; i < cnt; ++i)
-            if (bad[i])
-                for (int j = i + 1; j < std::min(cnt, i + 4); ++j)
-                    if (bad[j]) { for (int q = i + 1; q < j; ++q) bad[q] = 1; break; }
-        std::vector<int> m_all(hm.begin(), hm.end());
-        struct Redo { int a, b; DBuf<double> evals, evecs; std::vector<int64_t> eoff, xoff; };
-        std::vector<Redo> redo;
-        for (int a = 0; a < cnt;) {
-            if (!bad[a]) { ++a; continue; }
-            int e = a;
-            while (e < cnt && bad[e]) ++e;
-            redo.emplace_back();
-            Redo &r = redo.back();
-            r.a = a;
-            r.b = e;
-            EigBatch sub;
-            eig_batch_alloc(sub, std::vector<int>(sizes.begin() + ae0 + a, sizes.begin() + ae0 + e), P.opt, qb, slot);
-            sub.dense_only = true;
-            sub.set_window(L.theta);
-            int64_t rows_before = 0;
-            for (int i = 0; i < a; ++i) rows_before += sizes[ae0 + i];
-            const RowsSpan span{(int64_t)L.rel.AE_to_dof.I[ae0 + a] - (int64_t)L.rel.AE_to_dof.I[ae_lo], (int64_t)L.rel.AE_to_dof.I[ae_hi] - (int64_t)L.rel.AE_to_dof.I[ae_lo]};
-            ae_build(qb, L.drel, lev == 0 ? &L.A : nullptr, L.elmat, ae0 + a, sub, true,
-                     P.keep_debug ? L.ae_D.p + pend_row0[slot] + rows_before : nullptr, keep_rows ? &span : nullptr);
-            eig_tridiagonalize(qb, sub, 3);
-            eig_count(qb, sub, -1.0, L.theta);
-            r.eoff.assign((size_t)(e - a) + 1, 0);
-            r.xoff.assign((size_t)(e - a) + 1, 0);
-            for (int i = a; i < e; ++i) {
-                m_all[i] = sub.h_m[i - a];
-                r.eoff[i - a + 1] = r.eoff[i - a] + sub.h_m[i - a];
-                r.xoff[i - a + 1] = r.xoff[i - a] + (int64_t)sub.h_m[i - a] * sizes[ae0 + i];
-            }
-            r.evals.alloc((size_t)r.eoff.back() + 1);
-            r.evecs.alloc((size_t)r.xoff.back() + 1);
-            DBuf<int64_t> de, dx;
-            de.from_host(r.eoff, qb);
-            dx.from_host(r.xoff, qb);
-            eig_vectors(qb, sub, de.p, dx.p, r.evals.p, r.evecs.p);
-            SA_HIP_CHECK(hipStreamSynchronize(qb));
-            a = e;
-        }
-        // packed results of the whole chunk: stretches of finished matrices from the first pass, the runs from `redo`
-        std::vector<int64_t> eoff((size_t)cnt + 1, 0), xoff((size_t)cnt + 1, 0);
-        for (int i = 0; i < cnt; ++i) {
-            L.ae_m[ae0 + i] = m_all[i];
-            eoff[i + 1] = eoff[i] + m_all[i];
-            xoff[i + 1] = xoff[i] + (int64_t)m_all[i] * sizes[ae0 + i];
-        }
-        DBuf<double> evals((size_t)eoff[cnt]), evecs((size_t)xoff[cnt]);
-        auto copy = [&](double *dst, const double *src, int64_t n_) {
-            if (n_ > 0) SA_HIP_CHECK(hipMemcpyAsync(dst, src, 8 * (size_t)n_, hipMemcpyDeviceToDevice, qb));
-        };
-        size_t ri = 0;
-        for (int i = 0; i < cnt;) {
-            if (ri < redo.size() && redo[ri].a == i) {
-                const Redo &r = redo[ri++];
-                copy(evals.p + eoff[i], r.evals.p, r.eoff.back());
-                copy(evecs.p + xoff[i], r.evecs.p, r.xoff.back());
-                i = r.b;
-            } else {
-                const int e = ri < redo.size() ? redo[ri].a : cnt;       // finished matrices i .. e - 1: contiguous in both
-                copy(evals.p + eoff[i], c.evals.p + c.eoff[i], c.eoff[e] - c.eoff[i]);
-                copy(evecs.p + xoff[i], c.evecs.p + c.xoff[i], c.xoff[e] - c.xoff[i]);
-                i = e;
-            }
-        }
-        SA_HIP_CHECK(hipStreamSynchronize(qb));
-        c.evals = std::move(evals);
-        c.evecs = std::move(evecs);
-        c.eoff = eoff;
-        c.xoff = xoff;
-    };
+    }
+    std::copy(hm.begin(), hm.end(), L.ae_m.begin() + ae0);
+    packed_offsets(cnt, hm.data(), sizes, c.eoff, c.xoff);
+    c.evals.alloc((size_t)c.eoff[cnt]);
+    c.evecs.alloc((size_t)c.xoff[cnt]);
+    c.d_eoff.from_host(c.eoff, s);
+    c.d_xoff.from_host(c.xoff, s);
+    if (co.empty()) {
+        eig_vectors(s, batch, c.d_eoff.p, c.d_xoff.p, c.evals.p, c.evecs.p);
+    } else {      // a copy of its class's eigenpairs to every agglomerate
+        std::vector<const double *> pe((size_t)cnt), px((size_t)cnt);
+        for (int i = 0; i < cnt; ++i) { pe[i] = B.classes[co[i]].evals; px[i] = B.classes[co[i]].evecs; }
+        DBuf<const double *> d_pe, d_px;
+        d_pe.from_host(pe, s);
+        d_px.from_host(px, s);
+        eig_dedupe_expand(s, cnt, B.sizes.empty() ? 1 : *std::max_element(sizes, sizes + cnt), d_pe.p, d_px.p,
+                          c.d_eoff.p, c.d_xoff.p, c.evals.p, c.evecs.p);
+    }
+    SA_HIP_CHECK(hipStreamSynchronize(s));
+    if (some_bad) eig_redo_bad(B, slot, c, hm, hbad);
+}
+// how many agglomerates from ae0 on make the next chunk: what fits the workspace
+static int eig_chunk_count(const LevelBuild &B, int ae0) {
+    int cnt = fit_count(ae0, B.ae_hi, B.P.workspace_bytes, [&](int p) { return eig_workspace_bytes(B.sizes[p]); });
+    // Large agglomerates (the wide-band path: one workgroup per matrix in the panel and solve kernels, one or two
+    // workgroups per CU): a chunk of 577 of them is two full rounds over the 256 CUs and a third at a quarter of
+    // the card -- whole multiples of 512 instead (config 5: 27 chunks of 512 instead of 24 of 577).
+    constexpr bool round_chunks = true;
+    if (round_chunks && cnt > 512 && ae0 + cnt < B.ae_hi && B.sizes[ae0] > 1280) cnt = (cnt / 512) * 512;
+    return cnt;
+}
+// Classes within the chunk in `slot` -- known before its matrices were built (asm_cls: the assembly found them on its inputs)
+// or found on the matrices -- against those of the earlier chunks: the batch becomes the batch of the new classes' first members.
+static void eig_chunk_classes(LevelBuild &B, int slot, AeClasses &asm_cls) {
+    EigBatch &batch = B.batches[slot];
+    DdSource src = asm_cls.src;
+    bool found = asm_cls.early;
+    if (!found && !asm_cls.searched && batch.has_bw) {      // (distinct sparse rows: distinct matrices)
+        src = eig_dedupe_source(batch);
+        found = eig_dedupe_find(B.s, src, batch.count, batch.max_n, asm_cls.cls, B.P.opt.debug);
+    }
+    // a level whose first chunk has (almost) no identical agglomerates is not searched further: variable coefficients
+    if (!found && B.classes.empty()) B.dedupe_level = false;
+    if (!found) return;
+    const std::vector<int> solve_list = B.classes.admit(B.s, src, batch.h_n, batch.max_n, asm_cls.cls, B.solve_cls[slot], B.cls_of[slot]);
+    B.assembled[slot] = std::move(batch);
+    eig_batch_compact(B.s, batch, B.assembled[slot], solve_list);
+}
+static void level_eigenproblems(LevelBuild &B) {
+    Hierarchy &H = B.H; Level &L = B.L; const Params &P = B.P; hipStream_t s = B.s;
+    const int lev = B.lev;
+    eig_stage_begin(B);
+    int64_t row0 = L.rel.AE_to_dof.I[B.ae_lo];      // (rows of the agglomerates before this rank's)
+    // (a two-stream pipeline over the chunks -- band reduction of chunk i beside the chase of chunk
+    // i-1 -- was measured without gain on MI355X, 256^3: 3.48 s vs 3.29 s, and removed)
+    SA_HIP_CHECK(hipStreamSynchronize(s));
     int prev = -1, idx = 0;
-    for (int ae0 = ae_lo; ae0 < ae_hi; ++idx) {
-        size_t bytes = 0;
-        int cnt = 0;
-        while (ae0 + cnt < ae_hi) {
-            const size_t add = eig_workspace_bytes(sizes[ae0 + cnt]);
-            if (cnt > 0 && bytes + add > chunk_bytes) break;
-            bytes += add;
-            ++cnt;
-        }
-        // Large agglomerates (the wide-band path: one workgroup per matrix in the panel and solve kernels, one or two
-        // workgroups per CU): a chunk of 577 of them is two full rounds over the 256 CUs and a third at a quarter of
-        // the card -- whole multiples of 512 instead (config 5: 27 chunks of 512 instead of 24 of 577).
-        constexpr bool round_chunks = true;
-        if (round_chunks && cnt > 512 && ae0 + cnt < ae_hi && sizes[ae0] > 1280) cnt = (cnt / 512) * 512;
+    for (int ae0 = B.ae_lo; ae0 < B.ae_hi; ++idx) {
+        const int cnt = eig_chunk_count(B, ae0);
         const int slot = idx & 1;
-        EigBatch &batch = batches[slot];
+        EigBatch &batch = B.batches[slot];
         batch = EigBatch();
-        eig_batch_alloc(batch, std::vector<int>(sizes.begin() + ae0, sizes.begin() + ae0 + cnt), P.opt, qa, slot);
+        eig_batch_alloc(batch, std::vector<int>(B.sizes.begin() + ae0, B.sizes.begin() + ae0 + cnt), P.opt, s, slot);
         batch.dense_only = P.eigensolver == 1;
         batch.ss_tol = P.eig_tol;
         batch.set_window(L.theta);
@@ -657,122 +699,49 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
         if (lev > 0 && H.levels[lev - 1]->cvec_next.n == (size_t)L.A.nrows) {
             const size_t rows = (size_t)batch.h_voff[cnt];
             batch.x0c.alloc(rows);
-            hipLaunchKernelGGL(gather_kernel, dim3(div_up((long)rows, 256)), dim3(256), 0, qa, (long)rows,
+            hipLaunchKernelGGL(gather_kernel, dim3(div_up((long)rows, 256)), dim3(256), 0, s, (long)rows,
                                L.drel.ae2d_J.p + L.rel.AE_to_dof.I[ae0], H.levels[lev - 1]->cvec_next.p, batch.x0c.p);
             batch.has_x0c = true;
         }
-        const RowsSpan span{(int64_t)L.rel.AE_to_dof.I[ae0] - (int64_t)L.rel.AE_to_dof.I[ae_lo], (int64_t)L.rel.AE_to_dof.I[ae_hi] - (int64_t)L.rel.AE_to_dof.I[ae_lo]};      // (positions among the rows of this rank's agglomerates)
-        AeClasses classes;
-        ae_build(qa, L.drel, lev == 0 ? &L.A : nullptr, L.elmat, ae0, batch, true,
-                 P.keep_debug ? L.ae_D.p + row0 : nullptr, keep_rows ? &span : nullptr,
-                 dedupe && dedupe_level && !batch.dense_only ? &classes : nullptr);
+        const RowsSpan span = rows_span(L.rel, ae0, B.ae_lo, B.ae_hi);
+        const bool search = B.dedupe && B.dedupe_level && !batch.dense_only;
+        AeClasses asm_cls;
+        ae_build(s, L.drel, B.fine_A(), L.elmat, ae0, batch, true, P.keep_debug ? L.ae_D.p + row0 : nullptr,
+                 B.keep_rows ? &span : nullptr, search ? &asm_cls : nullptr);
         if (batch.order_ran) L.order_chunks.emplace_back(ae0, cnt);
         const int64_t rows_chunk = batch.h_voff[cnt];
-        cls_of[slot].clear();
-        solve_cls[slot].clear();
-        if (dedupe && dedupe_level && !batch.dense_only) {
-            // classes within the chunk: known before its matrices were built (the fused fine-level assembly) or found on them
-            DdSource src = classes.src;
-            bool found = classes.early;
-            if (!found && !classes.searched && batch.has_bw) {      // (distinct sparse rows: distinct matrices)
-                src = eig_dedupe_source(batch);
-                found = eig_dedupe_find(qa, src, cnt, batch.max_n, classes.cls, P.opt.debug);
-            }
-            // a level whose first chunk has (almost) no identical agglomerates is not searched further: variable coefficients
-            if (!found && lvl_classes.empty()) dedupe_level = false;
-            if (found) {
-                const DdClasses &cl = classes.cls;
-                const int nl = (int)cl.reps.size();
-                std::vector<int> l2g((size_t)nl, -1);
-                // ... against the classes of the earlier chunks: same hash, then word by word against the class's first member
-                std::vector<int> list, qidx, cand;
-                std::vector<const unsigned long long *> blobs;
-                std::vector<long> bwords;
-                for (int q = 0; q < nl; ++q) {
-                    auto it = lvl_by_hash.find(DdKey{cl.rep_hash[2 * (size_t)q], cl.rep_hash[2 * (size_t)q + 1]});
-                    if (it == lvl_by_hash.end()) continue;
-                    for (int id : it->second)
-                        if (lvl_classes[id].kind == src.kind) {
-                            list.push_back(cl.reps[q]); qidx.push_back(q); cand.push_back(id);
-                            blobs.push_back(lvl_classes[id].blob.p); bwords.push_back(lvl_classes[id].words);
-                        }
-                }
-                std::vector<char> same;
-                eig_dedupe_compare(qa, src, batch.max_n, list, blobs, bwords, same);
-                for (size_t t = 0; t < list.size(); ++t)
-                    if (same[t] && l2g[qidx[t]] < 0) l2g[qidx[t]] = cand[t];
-                // the new classes: their words are kept, their first members are what this chunk solves
-                std::vector<int> newq, newlist;
-                for (int q = 0; q < nl; ++q)
-                    if (l2g[q] < 0) { newq.push_back(q); newlist.push_back(cl.reps[q]); }
-                const std::vector<long> nwords = eig_dedupe_words(qa, src, batch.h_n, newlist);
-                std::vector<DBuf<unsigned long long>> nblobs;
-                eig_dedupe_pack(qa, src, batch.max_n, newlist, nwords, nblobs);
-                // (local classes found on the INPUTS of the assembly can share their assembled matrix -- agglomerates that differ
-                // in the flags of their surface dofs only: candidates with the hash of an earlier candidate are compared with it)
-                std::vector<int> alias(newq.size(), -1);
-                {
-                    std::unordered_map<DdKey, int, DdKeyHash> firstc;
-                    std::vector<int> clist, cwho;
-                    std::vector<const unsigned long long *> cblobs;
-                    std::vector<long> cwords;
-                    for (size_t t = 0; t < newq.size(); ++t) {
-                        auto it = firstc.emplace(DdKey{cl.rep_hash[2 * (size_t)newq[t]], cl.rep_hash[2 * (size_t)newq[t] + 1]}, (int)t);
-                        if (it.second) continue;
-                        clist.push_back(newlist[t]); cwho.push_back((int)t);
-                        cblobs.push_back(nblobs[it.first->second].p); cwords.push_back(nwords[it.first->second]);
-                    }
-                    std::vector<char> csame;
-                    eig_dedupe_compare(qa, src, batch.max_n, clist, cblobs, cwords, csame);
-                    for (size_t u = 0; u < clist.size(); ++u)
-                        if (csame[u]) alias[cwho[u]] = firstc[DdKey{cl.rep_hash[2 * (size_t)newq[cwho[u]]], cl.rep_hash[2 * (size_t)newq[cwho[u]] + 1]}];
-                }
-                std::vector<int> solve_list;
-                std::vector<int> id_of(newq.size(), -1);
-                for (size_t t = 0; t < newq.size(); ++t) {
-                    if (alias[t] >= 0) { id_of[t] = id_of[alias[t]]; l2g[newq[t]] = id_of[t]; continue; }
-                    solve_list.push_back(newlist[t]);
-                    const int id = (int)lvl_classes.size();
-                    id_of[t] = id;
-                    lvl_classes.emplace_back();
-                    SolvedClass &sc = lvl_classes.back();
-                    sc.n = batch.h_n[newlist[t]];
-                    sc.kind = src.kind;
-                    sc.words = nwords[t];
-                    sc.blob = std::move(nblobs[t]);
-                    lvl_by_hash[DdKey{cl.rep_hash[2 * (size_t)newq[t]], cl.rep_hash[2 * (size_t)newq[t] + 1]}].push_back(id);
-                    l2g[newq[t]] = id;
-                    solve_cls[slot].push_back(id);
-                }
-                cls_of[slot].resize((size_t)cnt);
-                for (int i = 0; i < cnt; ++i) cls_of[slot][i] = l2g[cl.rep_of[i]];
-                assembled[slot] = std::move(batch);
-                eig_batch_compact(qa, batch, assembled[slot], solve_list);
-            }
-        }
-        if (batch.count) eig_tridiagonalize(qa, batch, 1);
+        B.cls_of[slot].clear();
+        B.solve_cls[slot].clear();
+        if (search) eig_chunk_classes(B, slot, asm_cls);
+        if (batch.count) eig_tridiagonalize(s, batch, 1);
         L.ae_solved += batch.count;      // (eigenproblems that are solved, not copied)
-        pend_ae0[slot] = ae0;
-        pend_cnt[slot] = cnt;
-        pend_row0[slot] = row0;
-        if (prev >= 0) { join_iterate(); post(prev); }
-        start_iterate(slot);
+        B.pend_ae0[slot] = ae0;
+        B.pend_cnt[slot] = cnt;
+        B.pend_row0[slot] = row0;
+        if (prev >= 0) { eig_join_iterate(B); eig_chunk_finish(B, prev); }
+        eig_start_iterate(B, slot);
         prev = slot;
         row0 += rows_chunk;
         ae0 += cnt;
     }
-    if (prev >= 0) { join_iterate(); post(prev); }
-    tm.lap("local eigenproblems", lev);
-    if (operator_pending) {
-        operator_data();
-        tm.lap("operator (deferred Galerkin product) + SELL + D", lev);
+    if (prev >= 0) { eig_join_iterate(B); eig_chunk_finish(B, prev); }
+    B.tm.lap("local eigenproblems", lev);
+    if (B.operator_pending) {
+        join_galerkin(H);
+        level_operator_data(L, P, s);
+        B.tm.lap("operator (deferred Galerkin product) + SELL + D", lev);
     }
+}
+
+// Stage 3: the chunks' eigenpairs as the level's arrays; several ranks: counts and eigenvectors all-gathered.
+static void level_concatenate(LevelBuild &B) {
+    Level &L = B.L; const Params &P = B.P; hipStream_t s = B.s;
+    const int lev = B.lev, nparts = B.nparts, world = B.world;
+    const std::vector<int> &sizes = B.sizes, &ae_begin = B.ae_begin;
     if (world > 1) {   // exchange the number of eigenvectors per AE
         DBuf<int> d_m;
         d_m.from_host(L.ae_m, s);
-        std::vector<long long> off((size_t)world + 1);
-        for (int r = 0; r <= world; ++r) off[r] = 4ll * ae_begin[r];
-        SA_REQUIRE(P.allgather(P.allgather_ctx, d_m.p, off.data()) == 0, "all-gather (counts) failed");
+        allgather_ranges(P, d_m.p, 4, ae_begin, same_index, "counts");
         auto t_ = d_m.to_host(s);
         L.ae_m.assign(t_.begin(), t_.end());
     }
@@ -788,47 +757,38 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
     }
     L.evals.alloc((size_t)L.ae_eoff[nparts]);
     L.evecs.alloc((size_t)L.ae_xoff[nparts]);
-    for (Chunk &c : chunks) {
-        if (c.evals.n)
-            SA_HIP_CHECK(hipMemcpyAsync(L.evals.p + L.ae_eoff[c.ae0], c.evals.p, 8 * c.evals.n,
-                                        hipMemcpyDeviceToDevice, s));
+    for (Chunk &c : B.chunks) {
+        if (c.evals.n) SA_HIP_CHECK(hipMemcpyAsync(L.evals.p + L.ae_eoff[c.ae0], c.evals.p, 8 * c.evals.n, hipMemcpyDeviceToDevice, s));
         if (extra && c.ae0 == 0) {
             const int64_t first = (int64_t)L.ae_m[0] * sizes[0];
             SA_HIP_CHECK(hipMemcpyAsync(L.evecs.p, c.evecs.p, 8 * first, hipMemcpyDeviceToDevice, s));
-            hipLaunchKernelGGL(fill_kernel, dim3(div_up(sizes[0], 256)), dim3(256), 0, s, (long)sizes[0],
-                               L.evecs.p + first, 1.0);
+            hipLaunchKernelGGL(fill_kernel, dim3(div_up(sizes[0], 256)), dim3(256), 0, s, (long)sizes[0], L.evecs.p + first, 1.0);
             if (c.evecs.n > (size_t)first)
-                SA_HIP_CHECK(hipMemcpyAsync(L.evecs.p + L.ae_xoff[1], c.evecs.p + first,
-                                            8 * (c.evecs.n - first), hipMemcpyDeviceToDevice, s));
+                SA_HIP_CHECK(hipMemcpyAsync(L.evecs.p + L.ae_xoff[1], c.evecs.p + first, 8 * (c.evecs.n - first), hipMemcpyDeviceToDevice, s));
         } else if (c.evecs.n) {
-            SA_HIP_CHECK(hipMemcpyAsync(L.evecs.p + L.ae_xoff[c.ae0], c.evecs.p, 8 * c.evecs.n,
-                                        hipMemcpyDeviceToDevice, s));
+            SA_HIP_CHECK(hipMemcpyAsync(L.evecs.p + L.ae_xoff[c.ae0], c.evecs.p, 8 * c.evecs.n, hipMemcpyDeviceToDevice, s));
         }
     }
     SA_HIP_CHECK(hipStreamSynchronize(s));
-    chunks.clear();
+    B.chunks.clear();
     L.ae_m = m_tot;
     if (world > 1) {   // all-gather the eigenvectors (and, for inspection, eigenvalues and D) in place
-        std::vector<long long> off((size_t)world + 1);
-        for (int r = 0; r <= world; ++r) off[r] = 8ll * L.ae_xoff[ae_begin[r]];
-        SA_REQUIRE(P.allgather(P.allgather_ctx, L.evecs.p, off.data()) == 0, "all-gather (eigenvectors) failed");
+        allgather_ranges(P, L.evecs.p, 8, ae_begin, [&](int p) { return L.ae_xoff[p]; }, "eigenvectors");
         if (P.keep_debug) {
-            for (int r = 0; r <= world; ++r) off[r] = 8ll * L.ae_eoff[ae_begin[r]];
-            SA_REQUIRE(P.allgather(P.allgather_ctx, L.evals.p, off.data()) == 0, "all-gather (eigenvalues) failed");
-            int64_t rows = 0;
-            std::vector<int64_t> rowoff((size_t)nparts + 1, 0);
-            for (int p = 0; p < nparts; ++p) rowoff[p + 1] = rowoff[p] + sizes[p];
-            (void)rows;
-            for (int r = 0; r <= world; ++r) off[r] = 8ll * rowoff[ae_begin[r]];
-            SA_REQUIRE(P.allgather(P.allgather_ctx, L.ae_D.p, off.data()) == 0, "all-gather (D) failed");
+            allgather_ranges(P, L.evals.p, 8, ae_begin, [&](int p) { return L.ae_eoff[p]; }, "eigenvalues");
+            allgather_ranges(P, L.ae_D.p, 8, ae_begin, [&](int p) { return L.rel.AE_to_dof.I[p]; }, "D");      // (rows before agglomerate p)
         }
-        tm.lap("all-gather eigenvectors", lev);
+        B.tm.lap("all-gather eigenvectors", lev);
     }
+}
 
-    // ---- MIS stage (ContribTent::contrib_mises) ----
-    if (mis_thread.joinable()) mis_thread.join();
-    if (mis_err) std::rethrow_exception(mis_err);
-    tm.lap("MIS tables (join)", lev);
+// Stage 4: the MIS stage (ContribTent::contrib_mises): gather the eigenvectors on every MIS, SVD.
+static void level_mis_svd(LevelBuild &B) {
+    Level &L = B.L; const Params &P = B.P; const Relations &rel = L.rel; hipStream_t s = B.s;
+    const int lev = B.lev, world = B.world;
+    if (B.mis_thread.t.joinable()) B.mis_thread.t.join();
+    if (B.mis_err) std::rethrow_exception(B.mis_err);
+    B.tm.lap("MIS tables (join)", lev);
     const int nm = rel.num_mises;
     std::vector<int64_t> g_off((size_t)nm + 1, 0);
     L.mis_u_off.assign((size_t)nm + 1, 0);
@@ -859,69 +819,49 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
         d_xoff.from_host(L.ae_xoff, s);
         d_aem.from_host(L.ae_m, s);
         MisSvdIO io;
-        io.ae_m = d_aem.p;
-        io.ae_xoff = d_xoff.p;
-        io.evecs = L.evecs.p;
-        io.g_off = d_goff.p;
-        io.gather = gather;
-        io.u_off = L.d_mis_u_off.p;
-        io.s_off = d_soff.p;
-        io.U = L.mis_U.p;
-        io.sig = L.mis_sig.p;
-        io.k = L.d_mis_k.p;
-        io.ncols = d_ncols.p;
-        io.avoid_ess = P.avoid_ess_bdr_dofs;
-        io.extra = nextra ? L.extra.p : nullptr;
-        io.nextra = nextra;
-        io.ND = L.A.nrows;
-        io.debug = P.opt.debug;
+        io.ae_m = d_aem.p; io.ae_xoff = d_xoff.p; io.evecs = L.evecs.p;
+        io.g_off = d_goff.p; io.gather = gather;
+        io.u_off = L.d_mis_u_off.p; io.s_off = d_soff.p; io.U = L.mis_U.p; io.sig = L.mis_sig.p;
+        io.k = L.d_mis_k.p; io.ncols = d_ncols.p;
+        io.avoid_ess = P.avoid_ess_bdr_dofs; io.extra = nextra ? L.extra.p : nullptr; io.nextra = nextra;
+        io.ND = L.A.nrows; io.debug = P.opt.debug;
         if (world > 1) {
             // every rank takes a contiguous range of MISes (balanced by the r c^2 cost of the SVDs) and the bases,
             // singular values and counts are all-gathered in place: the counterpart of the reference's
             // owner-computes SVD + broadcast (SharedEntityCommunication, amg/src/contrib.cpp:519-548)
-            std::vector<int> mb((size_t)world + 1, nm);
-            double total = 0.0;
-            auto cost = [&](int m) {
+            const std::vector<int> mb = balanced_ranges(nm, world, [&](int m) {
                 const double r = rel.mis_to_dof.row_size(m), c = (double)(L.mis_s_off[m + 1] - L.mis_s_off[m]);
                 return r * std::min(r, c) * std::max(r, c) + 64.0;
-            };
-            for (int m = 0; m < nm; ++m) total += cost(m);
-            double run = 0.0;
-            int rk = 0;
-            mb[0] = 0;
-            for (int m = 0; m < nm && rk + 1 < world; ++m) {
-                run += cost(m);
-                while (rk + 1 < world && run >= total * (rk + 1) / world) mb[++rk] = m + 1;
-            }
-            mb[world] = nm;
+            });
             L.d_mis_k.zero(s);
             d_ncols.zero(s);
             mis_svd(s, L.drel, mb[P.rank + 1] - mb[P.rank], max_ctot, io, mb[P.rank]);
-            std::vector<long long> off((size_t)world + 1);
-            for (int r = 0; r <= world; ++r) off[r] = 8ll * L.mis_u_off[mb[r]];
-            SA_REQUIRE(P.allgather(P.allgather_ctx, L.mis_U.p, off.data()) == 0, "all-gather (MIS bases) failed");
-            for (int r = 0; r <= world; ++r) off[r] = 8ll * L.mis_s_off[mb[r]];
-            SA_REQUIRE(P.allgather(P.allgather_ctx, L.mis_sig.p, off.data()) == 0, "all-gather (singular values) failed");
-            for (int r = 0; r <= world; ++r) off[r] = 4ll * mb[r];
-            SA_REQUIRE(P.allgather(P.allgather_ctx, L.d_mis_k.p, off.data()) == 0, "all-gather (MIS counts) failed");
-            SA_REQUIRE(P.allgather(P.allgather_ctx, d_ncols.p, off.data()) == 0, "all-gather (MIS columns) failed");
+            allgather_ranges(P, L.mis_U.p, 8, mb, [&](int m) { return L.mis_u_off[m]; }, "MIS bases");
+            allgather_ranges(P, L.mis_sig.p, 8, mb, [&](int m) { return L.mis_s_off[m]; }, "singular values");
+            allgather_ranges(P, L.d_mis_k.p, 4, mb, same_index, "MIS counts");
+            allgather_ranges(P, d_ncols.p, 4, mb, same_index, "MIS columns");
         } else {
             // (agglomerates that hold copies of one class's eigenpairs: MISes with identical inputs are decomposed once)
             DBuf<int> d_ev;
             bool any = false;
             for (int v_ : L.ae_evclass) any = any || v_ >= 0;
-            if (any && P.opt.eig_dedupe != 0 && !(P.testmesh && lev == 0)) d_ev.from_host(L.ae_evclass, s);
+            if (any && B.dedupe) d_ev.from_host(L.ae_evclass, s);
             mis_svd(s, L.drel, nm, max_ctot, io, 0, d_ev.n ? d_ev.p : nullptr);
         }
         { auto t_ = L.d_mis_k.to_host(s); L.mis_k.assign(t_.begin(), t_.end()); }
         { auto t_ = d_ncols.to_host(s); L.mis_ncols.assign(t_.begin(), t_.end()); }
     }
-    tm.lap("MIS gather + SVD", lev);
+    B.tm.lap("MIS gather + SVD", lev);
+}
+
+// Stage 5: P and R, the host half of the next level's inputs, the Galerkin product (deferred where it can run beside the next level).
+static void level_transfer(LevelBuild &B) {
+    Hierarchy &H = B.H; Level &L = B.L; const Params &P = B.P; const Relations &rel = L.rel; hipStream_t s = B.s;
+    const int lev = B.lev, dev = B.dev, nm = rel.num_mises;
     L.mis_coloff.assign((size_t)nm + 1, 0);
     for (int m = 0; m < nm; ++m) L.mis_coloff[m + 1] = L.mis_coloff[m] + L.mis_k[m];
     L.d_mis_coloff.from_host(L.mis_coloff, s);
-    build_P_R(s, L.drel, rel, L.mis_k, L.mis_u_off, L.d_mis_k.p, L.d_mis_coloff.p, L.d_mis_u_off.p,
-              L.mis_U.p, L.P, L.R);
+    build_P_R(s, L.drel, rel, L.mis_k, L.mis_u_off, L.d_mis_k.p, L.d_mis_coloff.p, L.d_mis_u_off.p, L.mis_U.p, L.P, L.R);
     if (lev + 1 < P.num_coarsenings) {     // the next level's representation of the constant vector (P^T P = I)
         L.cvec_next.alloc((size_t)L.R.nrows);
         const double *cv = nullptr;
@@ -938,8 +878,7 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
     // the host half of the next level's inputs runs beside the Galerkin product (own thread, own
     // stream); with a smoothed prolongator level_galerkin moves P, so it is done afterwards
     std::exception_ptr prep_err;
-    std::thread prep_thread;
-    struct PrepJoiner { std::thread &t; ~PrepJoiner() { if (t.joinable()) t.join(); } } prep_joiner{prep_thread};
+    JoinedThread prep_thread;
     // (device build first: ~1 ms on the main stream; the host build is the fallback for AEs with more
     // coarse dofs than the kernel's LDS holds)
     constexpr bool host_e2d = false;
@@ -952,12 +891,7 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
     if (lev + 1 < P.num_coarsenings && P.nu_pro[lev] == 0 && !L.next_prep.ready) {
         hipStream_t side = side_stream(1);
         SA_HIP_CHECK(hipStreamSynchronize(s));       // P is complete
-        const roff_t *prp = L.P.rowptr.p;
-        const double *pvl = L.P.val.p;
-        const int pnr = L.P.nrows;
-        const int64_t pnz = L.P.nnz;
-        hipStream_t sd = side;
-        prep_thread = std::thread([&L, &prep_err, prp, pvl, pnr, pnz, sd, dev]() {
+        prep_thread.t = std::thread([&L, &prep_err, prp = L.P.rowptr.p, pvl = L.P.val.p, pnr = L.P.nrows, pnz = L.P.nnz, sd = side, dev]() {
             try {
                 adopt_device(dev);
                 set_thread_stream(sd);
@@ -969,8 +903,7 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
     // With another spectral level to come the product runs beside that level's element matrices and
     // eigenproblems (they need its size only); Options::overlap bit 2 cleared and the profiled step keep it in line.
     const bool no_overlap = !(P.opt.overlap & 4) || env_serial();
-    const bool defer = lev + 1 < P.num_coarsenings && P.nu_pro[lev] == 0 && world == 1 && !no_overlap &&
-                       !profiler().enabled;
+    const bool defer = lev + 1 < P.num_coarsenings && P.nu_pro[lev] == 0 && B.world == 1 && !no_overlap && !profiler().enabled;
     if (defer) {
         SA_HIP_CHECK(hipStreamSynchronize(s));       // the operands are complete
         hipStream_t gs = side_stream(2);
@@ -986,10 +919,24 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
     } else {
         level_galerkin(H, lev, true);
     }
-    if (prep_thread.joinable()) prep_thread.join();
+    if (prep_thread.t.joinable()) prep_thread.t.join();
     if (prep_err) std::rethrow_exception(prep_err);
-    tm.lap(defer ? "P, R (RAP deferred)" : "P, R, RAP", lev);
-    if (!P.keep_debug) {
+    B.tm.lap(defer ? "P, R (RAP deferred)" : "P, R, RAP", lev);
+}
+
+static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &part, int nparts,
+                        const signed char *bdr_host, const DeviceInputs *din = nullptr) {
+    SA_REQUIRE(H.params.nu_pro[lev] >= 0 && H.params.nu_pro[lev] <= 8, "bad prolongator smoothing degree");
+    LevelBuild B(H, lev, nparts);
+    Level &L = B.L;
+    L.theta = B.P.theta[lev];
+    L.nu_relax = B.P.nu_relax[lev];
+    level_topology(B, std::move(e2d), part, bdr_host, din);
+    level_eigenproblems(B);
+    level_concatenate(B);
+    level_mis_svd(B);
+    level_transfer(B);
+    if (!B.P.keep_debug) {
         L.evals.release();
         L.evecs.release();
         L.mis_sig.release();
@@ -1124,8 +1071,8 @@ static Table prepare_next_level(Hierarchy &H, int lev) {
     // element lists just made, the caller's partition -- and nothing below needs its result: it runs on a thread of its own
     // beside the coarse element matrices (20 ms of device work during which this thread only waits).
     std::exception_ptr topo_err;
-    std::thread topo_thread;
-    struct TopoJoiner { std::thread &t; ~TopoJoiner() { if (t.joinable()) t.join(); } } topo_joiner{topo_thread};
+    JoinedThread topo_joined;
+    std::thread &topo_thread = topo_joined.t;
     if (lev + 1 < H.params.num_coarsenings && lev + 1 < (int)H.coarse_parts.size() && !H.coarse_parts[(size_t)lev + 1].empty() &&
         !env_serial()) {
         const int dev = current_device();
@@ -1150,15 +1097,10 @@ static Table prepare_next_level(Hierarchy &H, int lev) {
     const int ae_hi = world > 1 ? L.ae_begin[H.params.rank + 1] : nparts;
     DBuf<int> d_ae_class;
     for (int ae0 = ae_lo; ae0 < ae_hi;) {
-        size_t bytes = 0;
-        int cnt = 0;
-        while (ae0 + cnt < ae_hi) {
-            const size_t n = (size_t)sizes[ae0 + cnt];
-            const size_t add = 8 * (n * n + n * (EIG_NB + 8) + n * (size_t)e2d.row_size(ae0 + cnt));
-            if (cnt > 0 && bytes + add > H.params.workspace_bytes) break;
-            bytes += add;
-            ++cnt;
-        }
+        const int cnt = fit_count(ae0, ae_hi, H.params.workspace_bytes, [&](int p) {
+            const size_t n = (size_t)sizes[p];
+            return 8 * (n * n + n * (EIG_NB + 8) + n * (size_t)e2d.row_size(p));
+        });
         EigBatch batch;
         eig_batch_alloc(batch, std::vector<int>(sizes.begin() + ae0, sizes.begin() + ae0 + cnt), H.params.opt, s);
         std::vector<int64_t> soff((size_t)cnt + 1, 0);
@@ -1170,7 +1112,7 @@ static Table prepare_next_level(Hierarchy &H, int lev) {
         const double *rv = nullptr;
         const short *rc = nullptr;
         constexpr bool dense_only = false;
-        const RowsSpan span{(int64_t)rel.AE_to_dof.I[ae0] - (int64_t)rel.AE_to_dof.I[ae_lo], (int64_t)rel.AE_to_dof.I[ae_hi] - (int64_t)rel.AE_to_dof.I[ae_lo]};
+        const RowsSpan span = rows_span(rel, ae0, ae_lo, ae_hi);
         if (lev == 0 && !dense_only && ae_sparse_rows(s, L.drel, L.A, L.elmat, ae0, batch, RW, rv, rc, &span)) {
             // fine level: straight from the sparse rows of the AE matrices
             int kmax = 0;
@@ -1193,12 +1135,7 @@ static Table prepare_next_level(Hierarchy &H, int lev) {
         if (world > 1 || ae0 + cnt < ae_hi) SA_HIP_CHECK(hipStreamSynchronize(s));
         ae0 += cnt;
     }
-    if (world > 1) {
-        std::vector<long long> off((size_t)world + 1);
-        for (int r = 0; r <= world; ++r) off[r] = 8ll * out_off[L.ae_begin[r]];
-        SA_REQUIRE(H.params.allgather(H.params.allgather_ctx, N.elmat.val.p, off.data()) == 0,
-                   "all-gather (coarse element matrices) failed");
-    }
+    if (world > 1) allgather_ranges(H.params, N.elmat.val.p, 8, L.ae_begin, [&](int p) { return out_off[p]; }, "coarse element matrices");
     if (topo_thread.joinable()) topo_thread.join();
     if (topo_err) std::rethrow_exception(topo_err);
     return e2d;

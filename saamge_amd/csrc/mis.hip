@@ -192,7 +192,7 @@ __global__ __launch_bounds__(64) void mis_svd_kernel(
     if (lane == 0) io.k[m] = k;
 }
 
-// Classes of identical MISes (eig.hip, "Duplicate agglomerate matrices", carried to the MIS stage): what the kernel above
+// Classes of identical MISes (dedupe.hip, "Duplicate agglomerate matrices", carried to the MIS stage): what the kernel above
 // gathers is a function of the MIS's size, the essential-boundary bits of its dofs, and per agglomerate it belongs to the
 // agglomerate's eigenvector block -- identical, bit for bit, for the members of one class of agglomerates (they received
 // copies of the class's eigenpairs: ae_ev = the class per agglomerate, -1 = on its own) -- its size and the MIS's rows in the
@@ -206,12 +206,6 @@ struct MisIn {
     MisSvdIO io;
     const int *ae_ev;
 };
-__device__ inline unsigned long long mi_mix(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
 template <bool PAIR, class F>
 __device__ inline bool mis_walk(const MisIn &v, int m, int m2, int lane, F &&f) {
     const int r = v.mis2d_I[m + 1] - v.mis2d_I[m], qb = v.mis2ae_I[m], nq = v.mis2ae_I[m + 1] - qb;
@@ -260,15 +254,10 @@ __device__ inline bool mis_walk(const MisIn &v, int m, int m2, int lane, F &&f) 
 __global__ __launch_bounds__(256) void mis_hash_kernel(MisIn v, int nm, unsigned long long *__restrict__ h) {
     const int m = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (m >= nm) return;
-    unsigned long long h1 = 0, h2 = 0;
-    mis_walk<false>(v, m, 0, lane, [&](unsigned long long w, unsigned long long pos) {
-        const unsigned long long k = mi_mix(w + 0x9E3779B97F4A7C15ull * (pos + 1));
-        h1 += k;
-        h2 += (k >> 32) * (k & 0xffffffffull);      // (second sum: the product of the halves of the mixed word; a full second mix was half of the kernel)
-    });
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { h1 += __shfl_xor(h1, o, 64); h2 += __shfl_xor(h2, o, 64); }
-    if (lane == 0) { h[2 * (size_t)m] = h1; h[2 * (size_t)m + 1] = h2; }
+    DdHash hs;
+    mis_walk<false>(v, m, 0, lane, [&](unsigned long long w, unsigned long long pos) { hs.add(w, pos); });
+    hs.wave_sum();
+    if (lane == 0) { h[2 * (size_t)m] = hs.h1; h[2 * (size_t)m + 1] = hs.h2; }
 }
 // open-addressing table keyed by the first hash: the smallest MIS of every key
 constexpr unsigned long long MI_EMPTY = ~0ull;
