@@ -403,6 +403,29 @@ int saamge_amd_spgemm(int nrows, int ninner, int ncols, const int *Arow, const i
 int saamge_amd_ae_order(int ND, int NE, int nde, const int *elem_ptr, const int *elem_to_dof, const int *elem_to_ae,
                         int nparts, int mode, int *ae_ptr, long long *nconn, int *ae_to_dof, int *pos, int *bw0, int *bw,
                         int *choice);
+/* ---- element matrices computed on the device (csrc/elmat.hip) ----
+ * The standard order-1 element matrices from vertex coordinates, element -> vertex lists and per-element coefficients, written
+ * in the packed layout saamge_amd_operator_assemble and saamge_amd_ml_produce_data* take (element e: size_e x size_e row-major
+ * at sum_{f<e} size_f^2), so that the physics never exists on the host; saamge_amd/elmat_model.py defines every operation and
+ * the device gives the same bits.  Types by (dim, nodes): (2, 3) P1 triangle, (2, 4) Q1 quadrilateral
+ * (v00, v10, v11, v01), (3, 4) P1 tetrahedron, (3, 6) P1 x P1 wedge (bottom triangle, then top), (3, 8) Q1 hexahedron (MFEM's
+ * vertex order); one quadrature rule per type, exact on affine images.
+ * kind 0 diffusion: ncoef = 1 (c I), dim (diagonal) or dim (dim + 1) / 2 (symmetric: xx, yy, zz, xy, yz, xz / xx, yy, xy), the
+ * matrix nodes x nodes.  kind 1 elasticity (lambda div u div v + 2 mu eps(u):eps(v)): ncoef = 2 (lambda, mu), dof
+ * dim * node + component, the matrix (dim nodes) x (dim nodes).
+ * kind 0 diffusion, 1 elasticity; dim 2 or 3; elem_ptr NULL: nde vertices per element.
+ * coords NV x dim row-major, coef NE x ncoef; elmat_out sized by the caller (sizes: call with elmat_out = NULL);
+ * dof_ptr_out (NE + 1) / elem_to_dof_out: the dof lists the matrices are indexed by (kind 0: the vertex lists;
+ * kind 1: dim * vertex + component), may be NULL.  Any pointer host or device, each on its own.
+ * info[0..4] = triangles, quadrilaterals, tetrahedra, wedges, hexahedra; [5] = doubles written; [6] = first element
+ * with a non-positive Jacobian (-1: none); [7] = 0.
+ * Refused (nonzero return, saamge_amd_last_error names the argument or the first element; elmat_out is then not to be relied
+ * on): dim, kind or ncoef out of range, NULL coords / elem_to_vertex / coef, malformed offsets, a vertex id outside [0, NV), an
+ * element that lists a vertex twice, a node count that is no type of the dimension, an element whose Jacobian determinant is
+ * not positive at a quadrature point.  The checks of the arguments alone run before anything touches the device. */
+int saamge_amd_element_matrices(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                const int *elem_to_vertex, int kind, int ncoef, const double *coef, void *stream,
+                                double *elmat_out, int *dof_ptr_out, int *elem_to_dof_out, long long info[8]);
 /* R = P^T (P nrows x ncols) */
 int saamge_amd_csr_transpose(int nrows, int ncols, const int *rowptr, const int *col, const double *val, int *Rrow,
                              long long *Rnnz, int *Rcol, double *Rval);

@@ -294,6 +294,52 @@ inline LevelOrderInfo level_order_info(const ml_data_t *h, int level) {
     return r;
 }
 
+// == element matrices computed on the device (saamge_amd_element_matrices) ==
+// From vertex coordinates (NV x dim), element -> vertex lists (elem_ptr == nullptr: nde vertices per element) and per-element
+// coefficients (NE x ncoef); kind 0 diffusion, 1 elasticity.  The matrices are packed in element order as the setup entry
+// points and AssembledOperator take them.  Throws with saamge_amd_last_error on a refusal.
+struct ElementMatricesInfo {
+    long long triangles, quadrilaterals, tetrahedra, wedges, hexahedra, doubles, first_bad_element;
+};
+// Into the caller's arrays, each a host or a device pointer (elmat_out == nullptr: the sizes only; the dof lists may be nullptr).
+inline ElementMatricesInfo element_matrices_into(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                                 const int *elem_to_vertex, int kind, int ncoef, const double *coef,
+                                                 double *elmat_out, int *dof_ptr_out = nullptr, int *elem_to_dof_out = nullptr,
+                                                 void *stream = nullptr) {
+    long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (saamge_amd_element_matrices(NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, kind, ncoef, coef, stream, elmat_out,
+                                    dof_ptr_out, elem_to_dof_out, info))
+        throw std::runtime_error(saamge_amd_last_error());
+    const ElementMatricesInfo r = {info[0], info[1], info[2], info[3], info[4], info[5], info[6]};
+    return r;
+}
+// From HOST arrays, as host vectors, with the dof lists the matrices are indexed by (kind 0: the vertex lists; kind 1:
+// dim * vertex + component).
+struct ElementMatrices {
+    std::vector<double> elmat;
+    std::vector<int> dof_ptr, elem_to_dof;
+    ElementMatricesInfo info;
+};
+inline ElementMatrices element_matrices(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                        const int *elem_to_vertex, int kind, int ncoef, const double *coef, void *stream = nullptr) {
+    ElementMatrices r;
+    const size_t comp = kind == 1 && dim > 0 ? (size_t)dim : 1, ne = (size_t)(NE > 0 ? NE : 0);
+    size_t doubles = 0, nconn = 0;
+    for (size_t e = 0; e < ne && (elem_ptr || nde > 0); ++e) {      // (sizes of well-formed input; the call checks it)
+        const size_t nd = elem_ptr ? (size_t)(elem_ptr[e + 1] > elem_ptr[e] ? elem_ptr[e + 1] - elem_ptr[e] : 0) : (size_t)nde;
+        doubles += nd * comp * nd * comp;
+        nconn += nd;
+    }
+    r.elmat.assign(doubles + 1, 0.0);      // (+ 1: data() of an empty vector may be null, which asks for the sizes only)
+    r.dof_ptr.assign(ne + 1, 0);
+    r.elem_to_dof.assign(nconn * comp + 1, 0);
+    r.info = element_matrices_into(NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, kind, ncoef, coef, r.elmat.data(),
+                                   r.dof_ptr.data(), r.elem_to_dof.data(), stream);
+    r.elmat.resize(doubles);
+    r.elem_to_dof.resize(nconn * comp);
+    return r;
+}
+
 // == the operator assembled on the device (saamge_amd_operator_assemble) ==
 // Owner of the handle.  rowptr() / col() / val() are device arrays that live as long as this object: hand them to
 // saamge_amd_ml_produce_data64 / _mixed64 as A.  elem_ptr == nullptr: every element has nde dofs.

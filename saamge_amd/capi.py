@@ -39,7 +39,7 @@ SYMBOLS = [
     "saamge_amd_operator_assemble", "saamge_amd_operator_arrays", "saamge_amd_operator_get", "saamge_amd_operator_update",
     "saamge_amd_operator_eliminate_rhs", "saamge_amd_operator_free", "saamge_amd_operator_path_counts",
     "saamge_amd_operator_set_path_limits",
-    "saamge_amd_level_order_info", "saamge_amd_ae_order",
+    "saamge_amd_level_order_info", "saamge_amd_ae_order", "saamge_amd_element_matrices",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong))
@@ -730,6 +730,75 @@ def ae_order(ND, elem_to_dof, elem_to_ae, nparts, mode, elem_ptr=None):
     bw0, bw, choice = (np.zeros(nparts, np.int32) for _ in range(3))
     call(j, pos, bw0, bw, choice)
     return ae_ptr, j, pos, bw0, bw, choice
+
+
+ELEMENT_TYPES = ("triangles", "quadrilaterals", "tetrahedra", "wedges", "hexahedra")
+
+
+def _element_matrices_call(coords, elem_to_vertex, kind, coef, elem_ptr, stream, elmat, dof_ptr, e2d):
+    """One saamge_amd_element_matrices call on prepared arrays; returns info (8 integers).  A refusal raises RuntimeError with
+    the library's message, and `.info` on it holds what the call had filled in by then (info[6]: the first element with a
+    non-positive Jacobian)."""
+    NV, dim = int(coords.shape[0]), int(coords.shape[1])
+    NE = len(elem_ptr) - 1 if elem_ptr is not None else int(elem_to_vertex.shape[0])
+    nde = 0 if elem_ptr is not None else int(elem_to_vertex.shape[1])
+    ncoef = 1 if len(coef.shape) == 1 else int(coef.shape[1])
+    info = (C.c_longlong * 8)()
+    rc = load().saamge_amd_element_matrices(C.c_int(NV), C.c_int(dim), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(elem_ptr),
+                                            _ptr(elem_to_vertex), C.c_int(int(kind)), C.c_int(ncoef), _ptr(coef),
+                                            C.c_void_p(stream), _ptr(elmat), _ptr(dof_ptr), _ptr(e2d), info)
+    if rc != 0:
+        err = RuntimeError("saamge_amd: " + load().saamge_amd_last_error().decode())
+        err.info = [int(v) for v in info]
+        raise err
+    return [int(v) for v in info]
+
+
+def _element_arrays(coords, elem_to_vertex, coef, elem_ptr):
+    def arr(a, dt):          # device tensors pass through, host arrays are made contiguous
+        return a if a is None or hasattr(a, "data_ptr") else np.ascontiguousarray(a, dtype=dt)
+    return arr(coords, np.float64), arr(elem_to_vertex, np.int32), arr(coef, np.float64), arr(elem_ptr, np.int32)
+
+
+def element_matrices_info(coords, elem_to_vertex, kind, coef, elem_ptr=None, stream=0):
+    """The sizes-only call (elmat_out = NULL): info = [triangles, quadrilaterals, tetrahedra, wedges, hexahedra, doubles the
+    matrices take, -1, 0].  Nothing is written; the mesh and the Jacobians are checked all the same."""
+    coords, e2v, coef, ep = _element_arrays(coords, elem_to_vertex, coef, elem_ptr)
+    return _element_matrices_call(coords, e2v, kind, coef, ep, stream, None, None, None)
+
+
+def element_matrices(coords, elem_to_vertex, kind, coef, elem_ptr=None, device=False, dofs=False, out=None, stream=0):
+    """saamge_amd_element_matrices: the element matrices of a mesh from its vertex coordinates (NV x dim), element -> vertex
+    lists ((NE, nodes), or flat with elem_ptr) and per-element coefficients ((NE,) or (NE, ncoef)); kind 0 diffusion, 1
+    elasticity.  Inputs: numpy arrays or device tensors, each on its own.  Returns elmat -- (NE, size, size), or packed in
+    element order with elem_ptr -- as a numpy array, or with device=True as a torch tensor on the GPU whose data_ptr goes to
+    `Operator` and `Hierarchy.from_operator` unchanged; out: an array / tensor of that many doubles to write into instead of
+    a new one.  dofs=True: (elmat, dof_ptr, elem_to_dof), the int32 dof lists the matrices are indexed by (elem_to_dof
+    (NE, size) without elem_ptr, else flat)."""
+    coords, e2v, coef, ep = _element_arrays(coords, elem_to_vertex, coef, elem_ptr)
+    comp = int(coords.shape[1]) if kind == 1 else 1
+    if ep is None:
+        NE, nconn = int(e2v.shape[0]), int(e2v.shape[0]) * int(e2v.shape[1])
+        doubles = NE * (int(e2v.shape[1]) * comp) ** 2
+    else:
+        NE, nconn = len(ep) - 1, int(e2v.shape[0])
+        nd = (ep[1:] - ep[:-1]) * comp
+        doubles = int((nd.long() ** 2).sum()) if hasattr(nd, "data_ptr") else int((nd.astype(np.int64) ** 2).sum())
+
+    def new(n, np_dt, torch_dt):
+        if device:
+            import torch
+            return torch.zeros(n, dtype=getattr(torch, torch_dt), device="cuda")
+        return np.zeros(max(n, 1), np_dt)[:n]
+    elmat = out if out is not None else new(doubles, np.float64, "float64")
+    dof_ptr = new(NE + 1, np.int32, "int32") if dofs else None
+    e2d = new(nconn * comp, np.int32, "int32") if dofs else None
+    _element_matrices_call(coords, e2v, kind, coef, ep, stream, elmat, dof_ptr, e2d)
+    if ep is None:
+        size = int(e2v.shape[1]) * comp
+        elmat = elmat.reshape(NE, size, size)
+        e2d = e2d.reshape(NE, size) if dofs else None
+    return (elmat, dof_ptr, e2d) if dofs else elmat
 
 
 def get_options():

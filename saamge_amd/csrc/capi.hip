@@ -4,6 +4,7 @@
 
 #include <string>
 
+#include "elmat.h"
 #include "hierarchy.h"
 #include "operator.h"
 #include "partition.h"
@@ -794,6 +795,17 @@ int saamge_amd_ae_order(int ND, int NE, int nde, const int *elem_ptr, const int 
         for (int p = 0; p < nparts; ++p) { bw0[p] = hr[3 * (size_t)p]; bw[p] = hr[3 * (size_t)p + 1]; choice[p] = hr[3 * (size_t)p + 2]; }
         for (size_t k = 0; k < rows; ++k) { ae_to_dof[k] = rel.AE_to_dof.J[k]; pos[k] = hp[k]; }
     }
+    SA_API_END
+}
+
+int saamge_amd_element_matrices(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                const int *elem_to_vertex, int kind, int ncoef, const double *coef, void *stream,
+                                double *elmat_out, int *dof_ptr_out, int *elem_to_dof_out, long long info[8]) {
+    SA_API_BEGIN
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    element_matrices(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, kind, ncoef, coef, elmat_out, dof_ptr_out,
+                     elem_to_dof_out, info);
     SA_API_END
 }
 

@@ -1,0 +1,15 @@
+// Element matrices computed on the device from vertex coordinates, element -> vertex lists and per-element coefficients
+// (elmat.hip).  saamge_amd/elmat_model.py defines the result -- types, rules, the order of every operation -- and the kernels
+// give the same bits.
+#pragma once
+#include "common.h"
+
+namespace saamge_amd {
+
+// The arguments of saamge_amd_element_matrices (include/saamge_amd.h).  The checks that need no device run before the first
+// HIP call; info is filled before a refusal for a non-positive Jacobian is thrown.  Runs on s and returns with s idle.
+void element_matrices(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                      const int *elem_to_vertex, int kind, int ncoef, const double *coef, double *elmat_out, int *dof_ptr_out,
+                      int *elem_to_dof_out, long long info[8]);
+
+}  // namespace saamge_amd

@@ -1,0 +1,489 @@
+// Element matrices on the device from vertex coordinates, element -> vertex lists and per-element coefficients: diffusion with
+// a scalar / diagonal / symmetric tensor and isotropic linear elasticity on the order-1 triangle, quadrilateral, tetrahedron,
+// wedge and hexahedron.  saamge_amd/elmat_model.py defines the result; this file restates it and gives the same bits.
+//
+// One lane per (element, node): a group of ND lanes owns an element, BLOCK / ND elements per workgroup.  The group stages its
+// vertices through LDS and every lane keeps all of them.  Per quadrature point every lane forms the Jacobian, its cofactors and
+// determinant (the same operations in every lane of the group, so the same bits), then the gradient of ITS node (times det) and,
+// for diffusion, its flux K G_a; the group shares these through LDS (two buffers, one barrier per point).  The lane of node a
+// accumulates row block a.  Diffusion entry (a, b) is formed from the operands of the model's a <= b order by both of its
+// owners; an elasticity entry is a sum of products whose factors commute, so the two owners agree as well.  The rows go to an
+// LDS tile and the workgroup writes the tile as consecutive doubles of the packed output.  A mesh of several types is split
+// into one element list per type (make_list, as operator.hip lists rows by path) and each list gets its own launch.
+// No floating-point atomics, no cross-lane reduction of values; the only atomic is the integer minimum that names the first
+// element with a non-positive determinant.
+#include "elmat.h"
+
+#include <algorithm>
+#include <climits>
+
+#include "operator.h"
+#include "partition.h"
+
+// every rounding of the model is one IEEE operation: no product is fused with the sum that follows it, anywhere in this file
+#pragma clang fp contract(off)
+
+namespace saamge_amd {
+
+namespace {
+
+// ---- the rules: the literals of elmat_model.py --------------------------------------------------------------------------
+constexpr double EM_GAUSS[2] = {0.21132486540518713, 0.7886751345948129};
+constexpr double EM_TRI_A = 0.16666666666666666, EM_TRI_B = 0.6666666666666666;
+constexpr int EM_QUAD_LOC[4][2] = {{0, 0}, {1, 0}, {1, 1}, {0, 1}};
+constexpr int EM_HEX_LOC[8][3] = {{0, 0, 0}, {1, 0, 0}, {1, 1, 0}, {0, 1, 0}, {0, 0, 1}, {1, 0, 1}, {1, 1, 1}, {0, 1, 1}};
+constexpr double EM_TRI_D[3][2] = {{-1.0, -1.0}, {1.0, 0.0}, {0.0, 1.0}};
+constexpr double EM_TET_D[4][3] = {{-1.0, -1.0, -1.0}, {1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+constexpr double EM_WEDGE_TRI[3][2] = {{EM_TRI_A, EM_TRI_A}, {EM_TRI_B, EM_TRI_A}, {EM_TRI_A, EM_TRI_B}};
+
+// points of the rule, weight of one point
+template <int DIM, int ND> struct EmType;
+template <> struct EmType<2, 3> { static constexpr int NQ = 1; static constexpr double W = 0.5; };
+template <> struct EmType<2, 4> { static constexpr int NQ = 4; static constexpr double W = 0.25; };
+template <> struct EmType<3, 4> { static constexpr int NQ = 1; static constexpr double W = 0.16666666666666666; };
+template <> struct EmType<3, 6> { static constexpr int NQ = 6; static constexpr double W = 0.08333333333333333; };
+template <> struct EmType<3, 8> { static constexpr int NQ = 8; static constexpr double W = 0.125; };
+
+constexpr int em_type_index(int dim, int nd) {
+    return dim == 2 ? (nd == 3 ? 0 : (nd == 4 ? 1 : -1)) : (nd == 4 ? 2 : (nd == 6 ? 3 : (nd == 8 ? 4 : -1)));
+}
+constexpr int EM_TYPE_ND[5] = {3, 4, 4, 6, 8};
+
+constexpr double em_f(int l, double p) { return l ? p : 1.0 - p; }
+constexpr double em_df(int l) { return l ? 1.0 : -1.0; }
+
+template <int DIM, int ND>
+struct EmGrad {
+    double v[ND][DIM];
+};
+// gradients of the reference shape functions at point q (elmat_model.reference_gradients), folded at compile time
+template <int DIM, int ND>
+constexpr EmGrad<DIM, ND> em_ref_grad(int q) {
+    EmGrad<DIM, ND> g{};
+    if constexpr (DIM == 2 && ND == 3) {
+        for (int a = 0; a < 3; ++a)
+            for (int j = 0; j < 2; ++j) g.v[a][j] = EM_TRI_D[a][j];
+    } else if constexpr (DIM == 3 && ND == 4) {
+        for (int a = 0; a < 4; ++a)
+            for (int j = 0; j < 3; ++j) g.v[a][j] = EM_TET_D[a][j];
+    } else if constexpr (DIM == 2 && ND == 4) {
+        const double px = EM_GAUSS[q & 1], py = EM_GAUSS[(q >> 1) & 1];
+        for (int a = 0; a < 4; ++a) {
+            const int lx = EM_QUAD_LOC[a][0], ly = EM_QUAD_LOC[a][1];
+            g.v[a][0] = em_df(lx) * em_f(ly, py);
+            g.v[a][1] = em_f(lx, px) * em_df(ly);
+        }
+    } else if constexpr (DIM == 3 && ND == 8) {
+        const double px = EM_GAUSS[q & 1], py = EM_GAUSS[(q >> 1) & 1], pz = EM_GAUSS[(q >> 2) & 1];
+        for (int a = 0; a < 8; ++a) {
+            const int lx = EM_HEX_LOC[a][0], ly = EM_HEX_LOC[a][1], lz = EM_HEX_LOC[a][2];
+            g.v[a][0] = em_df(lx) * (em_f(ly, py) * em_f(lz, pz));
+            g.v[a][1] = em_df(ly) * (em_f(lx, px) * em_f(lz, pz));
+            g.v[a][2] = em_df(lz) * (em_f(lx, px) * em_f(ly, py));
+        }
+    } else {
+        static_assert(DIM == 3 && ND == 6, "no such element type");
+        const double xi = EM_WEDGE_TRI[q % 3][0], eta = EM_WEDGE_TRI[q % 3][1], zeta = EM_GAUSS[q / 3];
+        const double T[3] = {(1.0 - xi) - eta, xi, eta};
+        const double L[2] = {1.0 - zeta, zeta};
+        for (int a = 0; a < 2; ++a)
+            for (int i = 0; i < 3; ++i) {
+                g.v[a * 3 + i][0] = EM_TRI_D[i][0] * L[a];
+                g.v[a * 3 + i][1] = EM_TRI_D[i][1] * L[a];
+                g.v[a * 3 + i][2] = T[i] * em_df(a);
+            }
+    }
+    return g;
+}
+
+// the rule's table: one set of gradients per point.  The point loop of the kernel is a real loop (unrolled, the compiler forms
+// the Jacobians of all points ahead of the first barrier and runs out of registers) that reads its point's line through a
+// wave-uniform index.
+template <int DIM, int ND>
+struct EmTable {
+    EmGrad<DIM, ND> p[EmType<DIM, ND>::NQ];
+};
+template <int DIM, int ND>
+constexpr EmTable<DIM, ND> em_table() {
+    EmTable<DIM, ND> t{};
+    for (int q = 0; q < EmType<DIM, ND>::NQ; ++q) t.p[q] = em_ref_grad<DIM, ND>(q);
+    return t;
+}
+template <int DIM, int ND>
+__device__ const EmTable<DIM, ND> EM_TABLE = em_table<DIM, ND>();
+
+// threads per workgroup: 256 where the tile of 256 / nd matrices stays within 40 KB of LDS, else one wavefront
+constexpr int em_block(int dim, int nd, int kind) {
+    const int size = nd * (kind ? dim : 1);
+    return (256 / nd) * size * size * 8 <= 40960 ? 256 : 64;
+}
+
+inline dim3 grid_flat(long n) { return dim3((unsigned)std::max<long>(1, (n + 255) / 256)); }
+
+// ---- the element matrices -------------------------------------------------------------------------------------------------
+// list: the elements of this launch (nullptr: elements 0 .. count - 1); eI nullptr: element e has its vertices at e * ND;
+// moff nullptr: its matrix at e * size^2; out nullptr: only the determinants are checked.
+template <int DIM, int ND, int KIND>
+__global__ __launch_bounds__(em_block(DIM, ND, KIND)) void em_kernel(int count, const int *__restrict__ list,
+                                                                      const int *__restrict__ eI, const int *__restrict__ eJ,
+                                                                      const roff_t *__restrict__ moff,
+                                                                      const double *__restrict__ coords,
+                                                                      const double *__restrict__ coef, int ncoef,
+                                                                      double *__restrict__ out, int *__restrict__ bad) {
+    typedef EmType<DIM, ND> T;
+    constexpr int BLOCK = em_block(DIM, ND, KIND), EPB = BLOCK / ND, COMP = KIND ? DIM : 1, S = ND * COMP, SS = S * S;
+    constexpr int W = KIND ? DIM : 2 * DIM;       // doubles a node shares per point: G_a, and F_a for diffusion
+    __shared__ double tile[EPB * SS];
+    __shared__ double sX[EPB * ND * DIM];
+    __shared__ double sG[2][EPB * ND * W];
+    __shared__ roff_t obase[EPB];
+    const int tid = threadIdx.x, el = tid / ND, a = tid - el * ND;
+    const bool lane = el < EPB;                   // (BLOCK need not be a multiple of ND: the last lanes own nothing)
+    const int elc = lane ? el : EPB - 1;
+    const long slot = (long)blockIdx.x * EPB + el;
+    const bool valid = lane && slot < count;
+    int e = 0;
+    double lam = 1.0, mu = 1.0, K[DIM][DIM];
+#pragma unroll
+    for (int i = 0; i < DIM; ++i)
+#pragma unroll
+        for (int j = 0; j < DIM; ++j) K[i][j] = i == j ? 1.0 : 0.0;
+    if (valid) {
+        e = list ? list[slot] : (int)slot;
+        const long vb = eI ? (long)eI[e] : (long)e * ND;
+        const int v = eJ[vb + a];
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) sX[(el * ND + a) * DIM + d] = coords[(long)v * DIM + d];
+        if (a == 0) obase[el] = moff ? moff[e] : (roff_t)e * SS;
+        const double *c = coef + (long)e * ncoef;
+        if (KIND) {
+            lam = c[0];
+            mu = c[1];
+        } else {
+#pragma unroll
+            for (int i = 0; i < DIM; ++i) K[i][i] = ncoef == 1 ? c[0] : c[i];
+            if (ncoef > DIM) {                    // xx, yy, zz, xy, yz, xz / xx, yy, xy
+                K[0][1] = K[1][0] = c[DIM];
+                if (DIM == 3) {
+                    K[1][DIM - 1] = K[DIM - 1][1] = c[DIM + 1];
+                    K[0][DIM - 1] = K[DIM - 1][0] = c[DIM + 2];
+                }
+            }
+        }
+    } else if (lane) {
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) sX[(el * ND + a) * DIM + d] = 0.0;
+    }
+    __syncthreads();
+    double X[ND][DIM];
+#pragma unroll
+    for (int b = 0; b < ND; ++b)
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) X[b][d] = sX[(elc * ND + b) * DIM + d];
+    double acc[COMP][S];
+    bool flag = false;
+#pragma unroll
+    for (int i = 0; i < COMP; ++i)
+#pragma unroll
+        for (int c = 0; c < S; ++c) acc[i][c] = 0.0;
+#pragma unroll 1
+    for (int q = 0; q < T::NQ; ++q) {
+        const EmGrad<DIM, ND> &dN = EM_TABLE<DIM, ND>.p[q];
+        double J[DIM][DIM], C[DIM][DIM], det;
+#pragma unroll
+        for (int i = 0; i < DIM; ++i)
+#pragma unroll
+            for (int j = 0; j < DIM; ++j) {
+                double t = X[0][i] * dN.v[0][j];
+#pragma unroll
+                for (int b = 1; b < ND; ++b) t = t + X[b][i] * dN.v[b][j];
+                J[i][j] = t;
+            }
+        if constexpr (DIM == 2) {
+            det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+            C[0][0] = J[1][1];
+            C[0][1] = -J[1][0];
+            C[1][0] = -J[0][1];
+            C[1][1] = J[0][0];
+        } else {
+            C[0][0] = J[1][1] * J[2][2] - J[1][2] * J[2][1];
+            C[0][1] = J[1][2] * J[2][0] - J[1][0] * J[2][2];
+            C[0][2] = J[1][0] * J[2][1] - J[1][1] * J[2][0];
+            C[1][0] = J[0][2] * J[2][1] - J[0][1] * J[2][2];
+            C[1][1] = J[0][0] * J[2][2] - J[0][2] * J[2][0];
+            C[1][2] = J[0][1] * J[2][0] - J[0][0] * J[2][1];
+            C[2][0] = J[0][1] * J[1][2] - J[0][2] * J[1][1];
+            C[2][1] = J[0][2] * J[1][0] - J[0][0] * J[1][2];
+            C[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+            det = (J[0][0] * C[0][0] + J[0][1] * C[0][1]) + J[0][2] * C[0][2];
+        }
+        if (!(det > 0.0)) flag = true;
+        const double s = T::W / det;
+        // this lane's node: its reference gradient picked from the constants, G_a = C dN_a, F_a = K G_a
+        double dA[DIM], Ga[DIM], Fa[DIM];
+#pragma unroll
+        for (int j = 0; j < DIM; ++j) {
+            double g = dN.v[0][j];
+#pragma unroll
+            for (int b = 1; b < ND; ++b) g = a == b ? dN.v[b][j] : g;
+            dA[j] = g;
+        }
+#pragma unroll
+        for (int i = 0; i < DIM; ++i) {
+            double t = dA[0] * C[i][0] + dA[1] * C[i][1];
+            if constexpr (DIM == 3) t = t + dA[2] * C[i][2];
+            Ga[i] = t;
+        }
+        double *share = sG[q & 1];
+        if (lane) {
+#pragma unroll
+            for (int i = 0; i < DIM; ++i) share[(el * ND + a) * W + i] = Ga[i];
+        }
+        if constexpr (KIND == 0) {
+#pragma unroll
+            for (int i = 0; i < DIM; ++i) {
+                double t = K[i][0] * Ga[0] + K[i][1] * Ga[1];
+                if constexpr (DIM == 3) t = t + K[i][2] * Ga[2];
+                Fa[i] = t;
+            }
+            if (lane) {
+#pragma unroll
+                for (int i = 0; i < DIM; ++i) share[(el * ND + a) * W + DIM + i] = Fa[i];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int b = 0; b < ND; ++b) {
+            double Gb[DIM];
+#pragma unroll
+            for (int i = 0; i < DIM; ++i) Gb[i] = share[(elc * ND + b) * W + i];
+            if constexpr (KIND == 0) {
+                double Fb[DIM];
+#pragma unroll
+                for (int i = 0; i < DIM; ++i) Fb[i] = share[(elc * ND + b) * W + DIM + i];
+                const bool first = a <= b;        // the entry is F_lo . G_hi with lo <= hi
+                double t = (first ? Fa[0] : Fb[0]) * (first ? Gb[0] : Ga[0]) + (first ? Fa[1] : Fb[1]) * (first ? Gb[1] : Ga[1]);
+                if constexpr (DIM == 3) t = t + (first ? Fa[2] : Fb[2]) * (first ? Gb[2] : Ga[2]);
+                const double term = s * t;
+                acc[0][b] = acc[0][b] + term;
+            } else {
+                double dot = Ga[0] * Gb[0] + Ga[1] * Gb[1];
+                if constexpr (DIM == 3) dot = dot + Ga[2] * Gb[2];
+                const double md = mu * dot;
+#pragma unroll
+                for (int i = 0; i < DIM; ++i)
+#pragma unroll
+                    for (int j = 0; j < DIM; ++j) {
+                        double t = lam * (Ga[i] * Gb[j]) + mu * (Ga[j] * Gb[i]);
+                        if (i == j) t = t + md;
+                        const double term = s * t;
+                        acc[i][DIM * b + j] = acc[i][DIM * b + j] + term;
+                    }
+            }
+        }
+    }
+    if (valid && flag) atomicMin(bad, e);
+    if (!out) return;                             // (the same in every lane of the grid)
+    if (lane) {
+#pragma unroll
+        for (int i = 0; i < COMP; ++i)
+#pragma unroll
+            for (int c = 0; c < S; ++c) tile[(el * S + COMP * a + i) * S + c] = acc[i][c];
+    }
+    __syncthreads();
+    const long left = (long)count - (long)blockIdx.x * EPB;
+    const int total = (int)(left < EPB ? left : EPB) * SS;
+    for (int t = tid; t < total; t += BLOCK) {
+        const int l = t / SS;
+        out[obase[l] + (t - l * SS)] = tile[t];
+    }
+}
+
+// ---- tables ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void em_offsets_kernel(int NE, int nd, int *__restrict__ eI) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e <= NE) eI[e] = (int)(e * nd);
+}
+// type of every element (-1: none, and the smallest such element in *first) and the size of its matrix
+__global__ __launch_bounds__(256) void em_classify_kernel(int NE, int dim, int comp, const int *__restrict__ eI,
+                                                          int *__restrict__ cls, int *__restrict__ sq, int *__restrict__ first) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= NE) return;
+    const int nd = eI[e + 1] - eI[e], t = em_type_index(dim, nd);
+    cls[e] = t;
+    sq[e] = t < 0 ? 0 : nd * comp * nd * comp;
+    if (t < 0) atomicMin(first, (int)e);
+}
+__global__ __launch_bounds__(256) void em_dof_ptr_kernel(int NE, int comp, const int *__restrict__ eI, int *__restrict__ out) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e <= NE) out[e] = comp * eI[e];
+}
+__global__ __launch_bounds__(256) void em_dofs_kernel(long nconn, int comp, const int *__restrict__ eJ, int *__restrict__ out) {
+    const long k = (long)blockIdx.x * 256 + threadIdx.x;
+    if (k >= nconn) return;
+    for (int c = 0; c < comp; ++c) out[k * comp + c] = comp * eJ[k] + c;
+}
+
+struct EmLaunch {
+    hipStream_t s;
+    const int *eI, *eJ;
+    const roff_t *moff;
+    const double *coords, *coef;
+    int ncoef;
+    double *out;
+    int *bad;
+};
+
+template <int DIM, int ND, int KIND>
+void em_launch(const EmLaunch &L, int count, const int *list) {
+    constexpr int BLOCK = em_block(DIM, ND, KIND), EPB = BLOCK / ND;
+    hipLaunchKernelGGL((em_kernel<DIM, ND, KIND>), dim3((unsigned)div_up(count, EPB)), dim3(BLOCK), 0, L.s, count, list, L.eI, L.eJ,
+                       L.moff, L.coords, L.coef, L.ncoef, L.out, L.bad);
+    SA_HIP_CHECK(hipGetLastError());
+}
+template <int KIND>
+void em_launch_type(const EmLaunch &L, int type, int count, const int *list) {
+    switch (type) {
+        case 0: em_launch<2, 3, KIND>(L, count, list); break;
+        case 1: em_launch<2, 4, KIND>(L, count, list); break;
+        case 2: em_launch<3, 4, KIND>(L, count, list); break;
+        case 3: em_launch<3, 6, KIND>(L, count, list); break;
+        default: em_launch<3, 8, KIND>(L, count, list); break;
+    }
+}
+
+const char *const EM_NAME = "saamge_amd_element_matrices: ";
+
+}  // namespace
+
+void element_matrices(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                      const int *elem_to_vertex, int kind, int ncoef, const double *coef, double *elmat_out, int *dof_ptr_out,
+                      int *elem_to_dof_out, long long info[8]) {
+    // ---- what needs no device
+    const std::string name(EM_NAME);
+    if (info) {
+        for (int k = 0; k < 8; ++k) info[k] = 0;
+        info[6] = -1;
+    }
+    SA_REQUIRE(dim == 2 || dim == 3, name + "dim must be 2 or 3");
+    SA_REQUIRE(kind == 0 || kind == 1, name + "kind must be 0 (diffusion) or 1 (elasticity)");
+    if (kind == 1)
+        SA_REQUIRE(ncoef == 2, name + "ncoef must be 2 (lambda, mu) for elasticity");
+    else
+        SA_REQUIRE(ncoef == 1 || ncoef == dim || ncoef == dim * (dim + 1) / 2,
+                   name + "ncoef must be 1, dim or dim (dim + 1) / 2 for diffusion");
+    SA_REQUIRE(NV >= 0 && NE >= 0, name + "NV < 0 or NE < 0");
+    SA_REQUIRE(NE == 0 || (coords && elem_to_vertex && coef), name + "null argument: coords, elem_to_vertex or coef");
+    const int comp = kind ? dim : 1;
+    SA_REQUIRE((int64_t)NV * comp <= INT_MAX, name + "dim * NV beyond 32 bits");
+    if (!elem_ptr) {
+        SA_REQUIRE(em_type_index(dim, nde) >= 0,
+                   name + "nde = " + std::to_string(nde) + " nodes are no supported element type in " + std::to_string(dim) + "D");
+        SA_REQUIRE((int64_t)NE * nde * comp <= INT_MAX, name + "NE * nde beyond 32 bits");
+    }
+    if (NE == 0) return;
+    // ---- the mesh: offsets first, they say how much of elem_to_vertex there is
+    DBuf<int> hold_I, hold_J;
+    const int *eI;
+    if (elem_ptr) {
+        eI = device_view(hold_I, elem_ptr, (size_t)NE + 1, s);
+    } else {
+        hold_I.alloc((size_t)NE + 1);
+        hipLaunchKernelGGL(em_offsets_kernel, grid_flat((long)NE + 1), dim3(256), 0, s, NE, nde, hold_I.p);
+        SA_HIP_CHECK(hipGetLastError());
+        eI = hold_I.p;
+    }
+    const int *eJ = elem_to_vertex;
+    long nconn;
+    if (!is_device_ptr(elem_to_vertex)) {
+        long total = (long)NE * nde;
+        if (elem_ptr) {
+            const hvec<int> hI = fetch_host(eI, (size_t)NE + 1, s);
+            for (int e = 0; e < NE; ++e)
+                SA_REQUIRE(hI[0] == 0 && hI[(size_t)e + 1] > hI[(size_t)e], name + "elem_ptr: must start at 0 and every element needs a vertex");
+            total = hI[(size_t)NE];
+        }
+        upload(hold_J, elem_to_vertex, (size_t)total, s);
+        eJ = hold_J.p;
+    }
+    nconn = check_mesh_device(s, NE, eI, eJ, NV);      // offsets, vertex ids in [0, NV), no vertex twice in an element
+    SA_REQUIRE((int64_t)nconn * comp <= INT_MAX, name + "dim * elem_ptr[NE] beyond 32 bits");
+    // ---- types, lists, offsets of the packed matrices
+    DBuf<int> cls, flag, pos, list[5];
+    DBuf<roff_t> moff;
+    int count[5] = {0, 0, 0, 0, 0};
+    int64_t doubles;
+    DBuf<int> word(1);
+    if (elem_ptr) {
+        DBuf<int> sq((size_t)NE);
+        cls.alloc((size_t)NE);
+        SA_HIP_CHECK(hipMemsetAsync(word.p, 0x7f, sizeof(int), s));
+        hipLaunchKernelGGL(em_classify_kernel, grid_flat(NE), dim3(256), 0, s, NE, dim, comp, eI, cls.p, sq.p, word.p);
+        SA_HIP_CHECK(hipGetLastError());
+        const int first = read_one(word.p, s);
+        if (first < NE) {
+            const int nd = read_one(eI + first + 1, s) - read_one(eI + first, s);
+            SA_REQUIRE(false, name + "element " + std::to_string(first) + ": " + std::to_string(nd) +
+                                  " nodes are no supported element type in " + std::to_string(dim) + "D");
+        }
+        flag.alloc((size_t)NE);
+        pos.alloc((size_t)NE + 1);
+        for (int t = 0; t < 5; ++t)
+            if (em_type_index(dim, EM_TYPE_ND[t]) == t) count[t] = make_list(s, NE, cls.p, t, flag, pos, list[t]);
+        moff.alloc((size_t)NE + 1);
+        exclusive_scan_off(s, NE, sq.p, moff.p);
+        doubles = read_one(moff.p + NE, s);
+    } else {
+        count[em_type_index(dim, nde)] = NE;
+        doubles = (int64_t)NE * (nde * comp) * (nde * comp);
+    }
+    if (info) {
+        for (int t = 0; t < 5; ++t) info[t] = count[t];
+        info[5] = (long long)doubles;
+    }
+    // ---- the matrices (elmat_out NULL: the determinants are still checked)
+    DBuf<double> hold_X, hold_c, hold_out;
+    EmLaunch L;
+    L.s = s;
+    L.eI = elem_ptr ? eI : nullptr;
+    L.eJ = eJ;
+    L.moff = moff.p;
+    L.coords = device_view(hold_X, coords, (size_t)NV * dim, s);
+    L.coef = device_view(hold_c, coef, (size_t)NE * ncoef, s);
+    L.ncoef = ncoef;
+    L.out = elmat_out;
+    if (elmat_out && !is_device_ptr(elmat_out)) {
+        hold_out.alloc((size_t)doubles);
+        L.out = hold_out.p;
+    }
+    L.bad = word.p;
+    SA_HIP_CHECK(hipMemsetAsync(word.p, 0x7f, sizeof(int), s));
+    for (int t = 0; t < 5; ++t) {
+        if (!count[t]) continue;
+        if (kind) em_launch_type<1>(L, t, count[t], list[t].p);
+        else em_launch_type<0>(L, t, count[t], list[t].p);
+    }
+    const int bad = read_one(word.p, s);
+    if (bad < NE) {
+        if (info) info[6] = bad;
+        SA_REQUIRE(false, name + "element " + std::to_string(bad) + ": the Jacobian determinant is not positive");
+    }
+    if (hold_out.p) SA_HIP_CHECK(hipMemcpyAsync(elmat_out, hold_out.p, (size_t)doubles * sizeof(double), hipMemcpyDeviceToHost, s));
+    // ---- the dof lists the matrices are indexed by
+    DBuf<int> dptr, dofs;
+    if (dof_ptr_out) {
+        dptr.alloc((size_t)NE + 1);
+        hipLaunchKernelGGL(em_dof_ptr_kernel, grid_flat((long)NE + 1), dim3(256), 0, s, NE, comp, eI, dptr.p);
+        SA_HIP_CHECK(hipGetLastError());
+        SA_HIP_CHECK(hipMemcpyAsync(dof_ptr_out, dptr.p, ((size_t)NE + 1) * sizeof(int), hipMemcpyDefault, s));
+    }
+    if (elem_to_dof_out) {
+        dofs.alloc((size_t)nconn * comp);
+        hipLaunchKernelGGL(em_dofs_kernel, grid_flat(nconn), dim3(256), 0, s, nconn, comp, eJ, dofs.p);
+        SA_HIP_CHECK(hipGetLastError());
+        SA_HIP_CHECK(hipMemcpyAsync(elem_to_dof_out, dofs.p, (size_t)nconn * comp * sizeof(int), hipMemcpyDefault, s));
+    }
+    SA_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+}  // namespace saamge_amd

@@ -44,33 +44,6 @@ constexpr int OP_MAX_ND = 46340;           // nd * nd stays below 2^31
 
 inline dim3 grid_flat(long n) { return dim3((unsigned)std::max<long>(1, (n + 255) / 256)); }
 
-// a copy the handle owns; a large pageable source goes through a page-locked block (DBuf::from_host says why)
-template <class T>
-void upload(DBuf<T> &dst, const T *src, size_t n, hipStream_t s) {
-    dst.alloc(n);
-    if (!n) return;
-    const size_t bytes = n * sizeof(T);
-    if (!is_device_ptr(src) && bytes >= (256u << 10)) {
-        void *stage = pinned_alloc(bytes);
-        std::memcpy(stage, src, bytes);
-        const hipError_t e = hipMemcpyAsync(dst.p, stage, bytes, hipMemcpyHostToDevice, s);
-        const hipError_t e2 = hipStreamSynchronize(s);
-        pinned_free(stage, bytes);
-        SA_HIP_CHECK(e);
-        SA_HIP_CHECK(e2);
-        return;
-    }
-    SA_HIP_CHECK(hipMemcpyAsync(dst.p, src, bytes, hipMemcpyDefault, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
-}
-// a device pointer is used where it is
-template <class T>
-const T *device_view(DBuf<T> &hold, const T *src, size_t n, hipStream_t s) {
-    if (is_device_ptr(src)) return src;
-    upload(hold, src, n, s);
-    return hold.p;
-}
-
 // ---- tables ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void op_first_free_kernel(int n, const int *__restrict__ cnt, int *__restrict__ first) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
@@ -419,20 +392,6 @@ __global__ __launch_bounds__(256) void op_rhs_kernel(int n, const int *__restric
     if (any) b[i] = bi;
 }
 
-// rows of class `which`, ascending; returns their number
-int make_list(hipStream_t s, int n, const int *cls, int which, DBuf<int> &flag, DBuf<int> &pos, DBuf<int> &list) {
-    hipLaunchKernelGGL(op_flag_kernel, grid_flat(n), dim3(256), 0, s, n, cls, which, flag.p);
-    SA_HIP_CHECK(hipGetLastError());
-    exclusive_scan_int(s, n, flag.p, pos.p);
-    const int m = read_one(pos.p + n, s);
-    list.alloc((size_t)m);
-    if (m) {
-        hipLaunchKernelGGL(op_list_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)flag.p, (const int *)pos.p, list.p);
-        SA_HIP_CHECK(hipGetLastError());
-    }
-    return m;
-}
-
 template <bool FILL>
 void symbolic_pass(hipStream_t s, const AssembledOperator &op, const DBuf<int> *list, const int *count, int *cnt, int *col) {
     const int *dI = op.d2e_I.p, *dJ = op.d2e_J.p, *eI = op.eI.p, *eJ = op.eJ.p;
@@ -467,6 +426,19 @@ void numeric_pass(hipStream_t s, AssembledOperator &op, const double *elmat) {
 }
 
 }  // namespace
+
+int make_list(hipStream_t s, int n, const int *cls, int which, DBuf<int> &flag, DBuf<int> &pos, DBuf<int> &list) {
+    hipLaunchKernelGGL(op_flag_kernel, grid_flat(n), dim3(256), 0, s, n, cls, which, flag.p);
+    SA_HIP_CHECK(hipGetLastError());
+    exclusive_scan_int(s, n, flag.p, pos.p);
+    const int m = read_one(pos.p + n, s);
+    list.alloc((size_t)m);
+    if (m) {
+        hipLaunchKernelGGL(op_list_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)flag.p, (const int *)pos.p, list.p);
+        SA_HIP_CHECK(hipGetLastError());
+    }
+    return m;
+}
 
 void operator_assemble(hipStream_t s, int n, int NE, int nde, const int *elem_ptr, const int *elem_to_dof,
                        const double *elmat, const signed char *bdr_dofs, const OperatorLimits &lim, AssembledOperator &op) {

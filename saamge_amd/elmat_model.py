@@ -1,0 +1,255 @@
+"""CPU model of the device element matrices (csrc/elmat.hip) -- numpy only, test infrastructure like capi.py.
+
+This file is the DEFINITION of the result: the device code restates it and must give the same bits.  Everything is written
+as single IEEE operations in a fixed order (no fused multiply-add, no library sums), vectorised over the elements only.
+
+  types        (dim, nodes): (2, 3) P1 triangle, (2, 4) Q1 quadrilateral (v00, v10, v11, v01), (3, 4) P1 tetrahedron,
+               (3, 6) P1 x P1 wedge (node a * 3 + i: triangle vertex i on the bottom a = 0 / top a = 1 face), (3, 8) Q1
+               hexahedron (vertex order HEX_LOC).  Anything else is refused.
+  rule         reference elements [0, 1]^dim and the unit simplex; triangle, tetrahedron: 1 point; quadrilateral, hexahedron:
+               2 Gauss points per axis (point q: axis d takes GAUSS[(q >> d) & 1]); wedge: point q = 3 * qz + qt, the 3-point
+               degree-2 triangle rule times 2 Gauss points.  The points and the weight of a point are the literals below.
+  point        J[i][j] = sum over the nodes a, ascending, of x_a[i] * dN_a[j], the first product taken as it is; the cofactors
+               C[i][j] and det from the explicit formulas of _cofactors; G_a[i] = sum_j dN_a[j] * C[i][j] (the physical
+               gradient times det); s = weight / det (one division per point).
+  kind 0       diffusion.  K of the element as (xx, yy, zz, xy, yz, xz) in 3D, (xx, yy, xy) in 2D: ncoef = 1 fills the
+               diagonal with c, ncoef = dim gives the diagonal, the missing entries are 0.0 and are multiplied like any
+               other.  F_a = K G_a; entry (a, b) with a <= b gets s * (F_a . G_b) per point, (b, a) is the same double.
+  kind 1       elasticity, ncoef = 2 (lambda, mu), dof dim * a + i:  entry ((a, i), (b, j)) gets per point
+               s * (lambda * (G_a[i] * G_b[j]) + mu * (G_a[j] * G_b[i]) [+ mu * (G_a . G_b) when i == j]).
+  sums         over the points in ascending order, starting from 0.0.
+  layout       packed in element order, row-major, element e at sum_{f<e} size_f^2; (NE, size, size) when elem_ptr is None.
+  refused      dim, kind, ncoef out of range, a node count that is no type of the dimension, malformed offsets, a vertex id
+               outside [0, NV), an element that lists a vertex twice, and an element whose det is not positive at a point
+               (ElementError, .element the smallest such id).
+"""
+import numpy as np
+
+GAUSS = (0.21132486540518713, 0.7886751345948129)        # 1/2 -+ 1/(2 sqrt 3)
+TRI_A, TRI_B = 0.16666666666666666, 0.6666666666666666   # the triangle rule's coordinates 1/6 and 2/3
+QUAD_LOC = [(0, 0), (1, 0), (1, 1), (0, 1)]
+HEX_LOC = [(0, 0, 0), (1, 0, 0), (1, 1, 0), (0, 1, 0), (0, 0, 1), (1, 0, 1), (1, 1, 1), (0, 1, 1)]
+TRI_D = [(-1.0, -1.0), (1.0, 0.0), (0.0, 1.0)]
+TET_D = [(-1.0, -1.0, -1.0), (1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0)]
+WEDGE_TRI = [(TRI_A, TRI_A), (TRI_B, TRI_A), (TRI_A, TRI_B)]
+# weight of one point (all points of a rule weigh the same)
+WEIGHT = {(2, 3): 0.5, (2, 4): 0.25, (3, 4): 0.16666666666666666, (3, 6): 0.08333333333333333, (3, 8): 0.125}
+NPOINTS = {(2, 3): 1, (2, 4): 4, (3, 4): 1, (3, 6): 6, (3, 8): 8}
+TYPE_INDEX = {(2, 3): 0, (2, 4): 1, (3, 4): 2, (3, 6): 3, (3, 8): 4}      # info[0..4] of saamge_amd_element_matrices
+
+
+class ElementError(ValueError):
+    """An element with a non-positive Jacobian determinant; .element is the smallest such id."""
+
+    def __init__(self, element):
+        ValueError.__init__(self, "element %d: the Jacobian determinant is not positive" % element)
+        self.element = int(element)
+
+
+def _f(l, p):
+    return p if l else 1.0 - p
+
+
+def _df(l):
+    return 1.0 if l else -1.0
+
+
+def reference_gradients(dim, nd, q):
+    """dN[a][j] at point q of the type's rule, as Python floats."""
+    if (dim, nd) == (2, 3):
+        return [tuple(d) for d in TRI_D]
+    if (dim, nd) == (3, 4):
+        return [tuple(d) for d in TET_D]
+    if (dim, nd) == (2, 4):
+        px, py = GAUSS[q & 1], GAUSS[(q >> 1) & 1]
+        return [(_df(lx) * _f(ly, py), _f(lx, px) * _df(ly)) for (lx, ly) in QUAD_LOC]
+    if (dim, nd) == (3, 8):
+        px, py, pz = GAUSS[q & 1], GAUSS[(q >> 1) & 1], GAUSS[(q >> 2) & 1]
+        return [(_df(lx) * (_f(ly, py) * _f(lz, pz)), _df(ly) * (_f(lx, px) * _f(lz, pz)), _df(lz) * (_f(lx, px) * _f(ly, py)))
+                for (lx, ly, lz) in HEX_LOC]
+    if (dim, nd) == (3, 6):
+        xi, eta = WEDGE_TRI[q % 3]
+        zeta = GAUSS[q // 3]
+        T = ((1.0 - xi) - eta, xi, eta)
+        L = (1.0 - zeta, zeta)
+        return [(TRI_D[i][0] * L[a], TRI_D[i][1] * L[a], T[i] * _df(a)) for a in (0, 1) for i in (0, 1, 2)]
+    raise ValueError("%d nodes: no supported element type in %dD" % (nd, dim))
+
+
+def _cofactors(J, dim):
+    """(C, det): C[i][j] the cofactor of J[i][j]."""
+    if dim == 2:
+        det = J[0][0] * J[1][1] - J[0][1] * J[1][0]
+        return [[J[1][1], -J[1][0]], [-J[0][1], J[0][0]]], det
+    C = [[J[1][1] * J[2][2] - J[1][2] * J[2][1], J[1][2] * J[2][0] - J[1][0] * J[2][2], J[1][0] * J[2][1] - J[1][1] * J[2][0]],
+         [J[0][2] * J[2][1] - J[0][1] * J[2][2], J[0][0] * J[2][2] - J[0][2] * J[2][0], J[0][1] * J[2][0] - J[0][0] * J[2][1]],
+         [J[0][1] * J[1][2] - J[0][2] * J[1][1], J[0][2] * J[1][0] - J[0][0] * J[1][2], J[0][0] * J[1][1] - J[0][1] * J[1][0]]]
+    det = (J[0][0] * C[0][0] + J[0][1] * C[0][1]) + J[0][2] * C[0][2]
+    return C, det
+
+
+def _dot(u, v, dim):
+    s = u[0] * v[0] + u[1] * v[1]
+    return s + u[2] * v[2] if dim == 3 else s
+
+
+def _tensor(coef, dim):
+    """The symmetric tensor's entries K[i][j] as arrays over the elements."""
+    n, ncoef = coef.shape
+    zero = np.zeros(n)
+    if ncoef == 1:
+        d = [coef[:, 0]] * dim
+        o = [zero] * 3
+    elif ncoef == dim:
+        d = [coef[:, i] for i in range(dim)]
+        o = [zero] * 3
+    else:                                    # xx, yy, zz, xy, yz, xz / xx, yy, xy
+        d = [coef[:, i] for i in range(dim)]
+        o = [coef[:, dim + i] for i in range(ncoef - dim)]
+    if dim == 2:
+        return [[d[0], o[0]], [o[0], d[1]]]
+    return [[d[0], o[0], o[2]], [o[0], d[1], o[1]], [o[2], o[1], d[2]]]
+
+
+def _block(X, dim, nd, kind, coef):
+    """Matrices (n, size, size) of n elements of one type, and per element whether a det was not positive."""
+    n = X.shape[0]
+    size = nd if kind == 0 else dim * nd
+    out = np.zeros((n, size, size))
+    bad = np.zeros(n, bool)
+    w = WEIGHT[(dim, nd)]
+    K = _tensor(coef, dim) if kind == 0 else None
+    with np.errstate(all="ignore"):
+        for q in range(NPOINTS[(dim, nd)]):
+            dN = reference_gradients(dim, nd, q)
+            J = [[None] * dim for _ in range(dim)]
+            for i in range(dim):
+                for j in range(dim):
+                    s = X[:, 0, i] * dN[0][j]
+                    for a in range(1, nd):
+                        s = s + X[:, a, i] * dN[a][j]
+                    J[i][j] = s
+            C, det = _cofactors(J, dim)
+            bad |= ~(det > 0.0)
+            s = w / det
+            G = []
+            for a in range(nd):
+                g = []
+                for i in range(dim):
+                    t = dN[a][0] * C[i][0] + dN[a][1] * C[i][1]
+                    if dim == 3:
+                        t = t + dN[a][2] * C[i][2]
+                    g.append(t)
+                G.append(g)
+            if kind == 0:
+                F = []
+                for a in range(nd):
+                    f = []
+                    for i in range(dim):
+                        t = K[i][0] * G[a][0] + K[i][1] * G[a][1]
+                        if dim == 3:
+                            t = t + K[i][2] * G[a][2]
+                        f.append(t)
+                    F.append(f)
+                for a in range(nd):
+                    for b in range(a, nd):
+                        term = s * _dot(F[a], G[b], dim)
+                        out[:, a, b] = out[:, a, b] + term
+            else:
+                lam, mu = coef[:, 0], coef[:, 1]
+                for a in range(nd):
+                    for b in range(nd):
+                        md = mu * _dot(G[a], G[b], dim)
+                        for i in range(dim):
+                            for j in range(dim):
+                                r, c = dim * a + i, dim * b + j
+                                if r > c:
+                                    continue
+                                t = lam * (G[a][i] * G[b][j]) + mu * (G[a][j] * G[b][i])
+                                if i == j:
+                                    t = t + md
+                                term = s * t
+                                out[:, r, c] = out[:, r, c] + term
+    iu = np.triu_indices(size, 1)
+    out[:, iu[1], iu[0]] = out[:, iu[0], iu[1]]
+    return out, bad
+
+
+def allowed_ncoef(dim, kind):
+    return (2,) if kind == 1 else tuple(sorted({1, dim, dim * (dim + 1) // 2}))
+
+
+def _mesh(coords, elem_to_vertex, elem_ptr):
+    X = np.asarray(coords, np.float64)
+    if X.ndim != 2 or X.shape[1] not in (2, 3):
+        raise ValueError("coords: (NV, dim) with dim 2 or 3 is needed")
+    NV, dim = X.shape
+    e2v = np.asarray(elem_to_vertex)
+    if elem_ptr is None:
+        if e2v.ndim != 2:
+            raise ValueError("elem_to_vertex: (NE, nodes) is needed without elem_ptr")
+        ep = np.arange(e2v.shape[0] + 1, dtype=np.int64) * e2v.shape[1]
+    else:
+        ep = np.asarray(elem_ptr, np.int64)
+        if ep.ndim != 1 or len(ep) < 1 or ep[0] != 0:
+            raise ValueError("elem_ptr: must start at 0")
+        if (np.diff(ep) <= 0).any():
+            raise ValueError("elem_ptr: every element needs a vertex")
+    e2v = e2v.astype(np.int64).ravel()
+    if len(e2v) != ep[-1]:
+        raise ValueError("elem_to_vertex: elem_ptr[NE] entries are needed")
+    if len(e2v) and (e2v.min() < 0 or e2v.max() >= NV):
+        raise ValueError("elem_to_vertex entry out of range")
+    nd = np.diff(ep)
+    elem = np.repeat(np.arange(len(nd), dtype=np.int64), nd)
+    if len(np.unique(elem * max(int(NV), 1) + e2v)) != len(e2v):
+        raise ValueError("an element lists a vertex twice")
+    for e in np.flatnonzero(~np.isin(nd, [k[1] for k in TYPE_INDEX if k[0] == dim])):
+        raise ValueError("element %d: %d nodes are no supported element type in %dD" % (e, nd[e], dim))
+    return X, dim, ep, e2v, nd
+
+
+def element_matrices(coords, elem_to_vertex, kind, coef, elem_ptr=None):
+    """The element matrices: (NE, size, size) when elem_ptr is None, else packed.  coef: (NE,) or (NE, ncoef)."""
+    if kind not in (0, 1):
+        raise ValueError("kind: 0 (diffusion) or 1 (elasticity)")
+    X, dim, ep, e2v, nd = _mesh(coords, elem_to_vertex, elem_ptr)
+    NE = len(nd)
+    coef = np.asarray(coef, np.float64).reshape(NE, -1) if NE else np.zeros((0, allowed_ncoef(dim, kind)[0]))
+    if coef.shape[1] not in allowed_ncoef(dim, kind):
+        raise ValueError("ncoef = %d is not allowed for kind %d in %dD" % (coef.shape[1], kind, dim))
+    comp = 1 if kind == 0 else dim
+    moff = np.concatenate([[0], np.cumsum((nd * comp) ** 2)])
+    out = np.zeros(int(moff[-1]))
+    bad = np.zeros(NE, bool)
+    for c in np.unique(nd):
+        ids = np.flatnonzero(nd == c)
+        blk, bad[ids] = _block(X[e2v[ep[ids][:, None] + np.arange(c)]], dim, int(c), kind, coef[ids])
+        out[moff[ids][:, None] + np.arange((c * comp) ** 2)] = blk.reshape(len(ids), -1)
+    if bad.any():
+        raise ElementError(np.flatnonzero(bad)[0])
+    if elem_ptr is None:
+        return out.reshape(NE, nd[0] * comp, nd[0] * comp) if NE else out.reshape(0, 0, 0)
+    return out
+
+
+def type_counts(dim, elem_to_vertex, elem_ptr=None):
+    """[triangles, quadrilaterals, tetrahedra, wedges, hexahedra]"""
+    nd = np.diff(np.asarray(elem_ptr, np.int64)) if elem_ptr is not None else \
+        np.full(np.asarray(elem_to_vertex).shape[0], np.asarray(elem_to_vertex).shape[1])
+    out = [0] * 5
+    for (d, k), t in TYPE_INDEX.items():
+        if d == dim:
+            out[t] = int((nd == k).sum())
+    return out
+
+
+def dof_lists(dim, elem_to_vertex, kind, elem_ptr=None):
+    """(dof_ptr, elem_to_dof), both int32 and flat: the dofs the matrices are indexed by -- kind 0 the vertex lists, kind 1
+    dim * vertex + component."""
+    e2v = np.asarray(elem_to_vertex)
+    ep = np.arange(e2v.shape[0] + 1, dtype=np.int64) * e2v.shape[1] if elem_ptr is None else np.asarray(elem_ptr, np.int64)
+    e2v = e2v.astype(np.int64).ravel()
+    if kind == 0:
+        return ep.astype(np.int32), e2v.astype(np.int32)
+    return (ep * dim).astype(np.int32), (dim * e2v[:, None] + np.arange(dim)[None, :]).ravel().astype(np.int32)

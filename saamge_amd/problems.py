@@ -985,3 +985,66 @@ def split_parcsr_device(prob, world, rank, levels):
             # (clones: a slice that is contiguous already would be a VIEW that keeps the whole global array alive)
             "elem_to_dof": prob.elem_to_dof[m0:m1].clone(), "elmat": elm[m0:m1].clone(),
             "bdr": prob.bdr[r0:r1].clone(), "partitions": p_loc, "nparts": np_loc}
+
+
+# --------------------------------------------------------------------------
+# meshes for the element matrices computed on the device (saamge_amd_element_matrices): vertex coordinates and
+# element -> vertex lists in place of ready-made element matrices
+# --------------------------------------------------------------------------
+def grid_coords(n):
+    """Vertex coordinates (NV x 3) of the unit-cube grid of poisson3d_problem, poisson3d_mixed_problem and
+    elasticity3d_problem: vertex (i, j, k) has id (k * nvy + j) * nvx + i.  n = (nx, ny) gives the unit-square grid
+    (vertex j * nvx + i) of quad_mesh_problem."""
+    if np.isscalar(n):
+        n = (int(n),) * 3
+    axes = [np.arange(m + 1) * (1.0 / m) for m in n]
+    grids = np.meshgrid(*axes[::-1], indexing="ij")[::-1]      # x fastest
+    return np.ascontiguousarray(np.stack([g.ravel() for g in grids], axis=1))
+
+
+def jitter(coords, dims, amount, seed):
+    """A copy of coords with every vertex (boundary vertices included) moved per axis by at most amount x the mesh width of
+    that axis (the extent of the mesh / dims[axis]), drawn from `seed`."""
+    X = np.array(coords, dtype=np.float64)
+    rng = np.random.default_rng(seed)
+    width = (X.max(axis=0) - X.min(axis=0)) / np.asarray(dims, dtype=np.float64)
+    return X + (2.0 * rng.random(X.shape) - 1.0) * (amount * width)[None, :]
+
+
+_KUHN = [(0, 1, 2), (1, 2, 0), (2, 0, 1), (0, 2, 1), (2, 1, 0), (1, 0, 2)]      # the first three are even permutations
+
+
+def hex_to_tets(n):
+    """Kuhn split of the grid of grid_coords(n) into 6 tetrahedra per cell, (6 NE) x 4 vertex ids, cell by cell: one
+    tetrahedron per order in which the axes are walked from the cell's vertex (0, 0, 0) to (1, 1, 1), its last two vertices
+    swapped where the walk is an odd permutation, so that every tetrahedron is positively oriented."""
+    if np.isscalar(n):
+        n = (int(n),) * 3
+    nx, ny, nz = n
+    nvx, nvy = nx + 1, ny + 1
+    ez, ey, ex = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    base = np.stack([ex.ravel(), ey.ravel(), ez.ravel()], axis=1)
+    vid = lambda p: (p[:, 2] * nvy + p[:, 1]) * nvx + p[:, 0]
+    tets = []
+    for k, perm in enumerate(_KUHN):
+        corner = np.zeros(3, np.int64)
+        v = [vid(base)]
+        for axis in perm:
+            corner[axis] = 1
+            v.append(vid(base + corner[None, :]))
+        if k >= 3:
+            v[2], v[3] = v[3], v[2]
+        tets.append(np.stack(v, axis=1))
+    return np.ascontiguousarray(np.stack(tets, axis=1).reshape(-1, 4).astype(np.int32))
+
+
+def quads_to_tris(nx, ny):
+    """The nx x ny quads of quad_mesh_problem split along the diagonal v00 - v11 into two counter-clockwise triangles each,
+    (2 NE) x 3 vertex ids, quad by quad."""
+    nvx = nx + 1
+    ex, ey = np.meshgrid(np.arange(nx), np.arange(ny), indexing="xy")
+    ex, ey = ex.ravel(), ey.ravel()
+    vid = lambda i, j: j * nvx + i
+    v00, v10, v11, v01 = vid(ex, ey), vid(ex + 1, ey), vid(ex + 1, ey + 1), vid(ex, ey + 1)
+    tris = np.stack([np.stack([v00, v10, v11], axis=1), np.stack([v00, v11, v01], axis=1)], axis=1)
+    return np.ascontiguousarray(tris.reshape(-1, 3).astype(np.int32))
