@@ -10,6 +10,94 @@ namespace saamge_amd {
 
 constexpr int ASM_NT = 256;
 
+// ---------------------------------------------------------------------------------------
+// The entry rule.  Entry (row dof g, column dof c) of the matrix of agglomerate p: where both dofs are
+// interior (entry_assembled) it is the sum of the element-matrix entries of g's elements inside p, in ascending position
+// of g's dof -> element list, per element at the first slot of g and the first slot of c; otherwise it is copied from A.
+// Every kernel below that makes such entries takes the pieces from here.
+// ---------------------------------------------------------------------------------------
+// slot of dof d in an 8-dof element whose dofs are the two int4s (the first match), or -1
+__device__ inline int slot8(const int4 lo, const int4 hi, int d) {
+    return (lo.x == d) ? 0 : (lo.y == d) ? 1 : (lo.z == d) ? 2 : (lo.w == d) ? 3 :
+           (hi.x == d) ? 4 : (hi.y == d) ? 5 : (hi.z == d) ? 6 : (hi.w == d) ? 7 : -1;
+}
+// slot of dof d among the nd dofs of an element (the first match), or -1
+__device__ inline int elem_slot(const int *__restrict__ dofs, int nd, int d) {
+    for (int t = 0; t < nd; ++t)
+        if (dofs[t] == d) return t;
+    return -1;
+}
+// flags fg, fc of the row and the column dof: summed from the element matrices (agg_assemble_value, aggregates.cpp:68-184),
+// or copied from the global matrix (aggregates.cpp:930-934)
+__device__ inline bool entry_assembled(int fg, int fc, int g, int c) {
+    return (fg & 1) && (fc & 1) && (!((fg | fc) & 2) || c == g);
+}
+// number of dof c in agglomerate p through the dof -> AE list, or -1: c is not in p
+__device__ inline int ae_local_id(const int *__restrict__ d2ae_I, const int *__restrict__ d2ae_J,
+                                  const int *__restrict__ dof_id_inAE, int c, int p) {
+    for (int q = d2ae_I[c]; q < d2ae_I[c + 1]; ++q)
+        if (d2ae_J[q] == p) return dof_id_inAE[q];
+    return -1;
+}
+// v + the assembled entry (g, c) over the positions [q0, q1) of the dof -> element list (g's own).  HEX8: every element has
+// 8 dofs, e2d_J and elval are dense arrays (two 16-byte loads per element; e2d_I and eloff are not read); otherwise an
+// element's dofs start at e2d_I[e] and its matrix at eloff[e].
+template <bool HEX8>
+__device__ inline double walk_entry(double v, int p, int g, int c, int q0, int q1, const int *__restrict__ d2e_J,
+                                    const int *__restrict__ part, const int *__restrict__ e2d_I,
+                                    const int *__restrict__ e2d_J, const int64_t *__restrict__ eloff,
+                                    const double *__restrict__ elval) {
+    for (int q = q0; q < q1; ++q) {
+        const int e = d2e_J[q];
+        if (part[e] != p) continue;
+        if (HEX8) {
+            const int4 lo = *(const int4 *)(e2d_J + (size_t)e * 8), hi = *(const int4 *)(e2d_J + (size_t)e * 8 + 4);
+            const int kk = slot8(lo, hi, g), jj = slot8(lo, hi, c);
+            if (jj >= 0) v += elval[((size_t)e * 8 + kk) * 8 + jj];
+        } else {
+            const int eb = e2d_I[e], nd = e2d_I[e + 1] - eb;
+            int kk = -1, jj = -1;
+            for (int t = 0; t < nd; ++t) {      // (both slots in one pass over the element's dofs)
+                const int dd = e2d_J[eb + t];
+                if (dd == g && kk < 0) kk = t;
+                if (dd == c && jj < 0) jj = t;
+            }
+            if (jj >= 0) v += elval[eloff[e] + (int64_t)kk * nd + jj];
+        }
+    }
+    return v;
+}
+// local number of a global dof in an agglomerate, or -1: an LDS hash table of the agglomerate's dofs (open addressing, the size
+// mask + 1 a power of two >= 1.5 n; the list search of ae_local_id costs six dependent global loads per entry of a 375-entry row)
+struct AiTable {
+    int *key;
+    short *val;
+    unsigned mask;
+    __device__ inline void clear(int tid, int nt) const {      // (a barrier before the first insert)
+        for (int i = tid; i <= (int)mask; i += nt) key[i] = -1;
+    }
+    __device__ inline void insert(int g, int i) const {
+        unsigned h = hash_home((unsigned)g, mask + 1u);
+        while (atomicCAS(&key[h], -1, g) != -1) h = (h + 1) & mask;
+        val[h] = (short)i;
+    }
+    __device__ inline void build(const int *__restrict__ dofs, int n, int tid, int nt) const {
+        clear(tid, nt);
+        __syncthreads();
+        for (int i = tid; i < n; i += nt) insert(dofs[i], i);
+        __syncthreads();
+    }
+    __device__ inline int operator()(int c) const {
+        unsigned h = hash_home((unsigned)c, mask + 1u);
+        for (;;) {
+            const int k = key[h];
+            if (k == c) return val[h];
+            if (k == -1) return -1;
+            h = (h + 1) & mask;
+        }
+    }
+};
+
 __global__ __launch_bounds__(ASM_NT) void ae_assemble_kernel(
     int ae0, const int *__restrict__ ns, const int64_t *__restrict__ moff, double *__restrict__ W,
     const int *__restrict__ ae2d_I, const int *__restrict__ ae2d_J, const int *__restrict__ d2ae_I,
@@ -42,15 +130,11 @@ __global__ __launch_bounds__(ASM_NT) void ae_assemble_kernel(
             // entries copied from the global matrix (aggregates.cpp:930-934)
             for (roff_t k = Arow[g]; k < Arow[g + 1]; ++k) {
                 const int c = Acol[k];
-                int idx = -1;
-                for (int q = d2ae_I[c]; q < d2ae_I[c + 1]; ++q)
-                    if (d2ae_J[q] == p) { idx = q; break; }
-                if (idx < 0) continue;  // neighbour not in this AE
-                const int fc = flags[c];
-                const bool assembled = (fg & 1) && (fc & 1) && (!((fg | fc) & 2) || c == g);
-                if (!assembled) {
+                const int lc = ae_local_id(d2ae_I, d2ae_J, dof_id_inAE, c, p);
+                if (lc < 0) continue;  // neighbour not in this AE
+                if (!entry_assembled(fg, flags[c], g, c)) {
                     const double v = Aval[k];
-                    if (v != 0.0) Wm[(size_t)(pm ? pm[dof_id_inAE[idx]] : dof_id_inAE[idx]) * n + lr] = v;
+                    if (v != 0.0) Wm[(size_t)(pm ? pm[lc] : lc) * n + lr] = v;
                 }
             }
         }
@@ -59,15 +143,12 @@ __global__ __launch_bounds__(ASM_NT) void ae_assemble_kernel(
             const int e = d2e_J[q];
             if (part[e] != p) continue;
             const int eb = e2d_I[e], nd = e2d_I[e + 1] - eb;
-            int kk = 0;
-            while (kk < nd && e2d_J[eb + kk] != g) ++kk;
-            const double *M = elval + eloff[e] + (size_t)kk * nd;
+            const double *M = elval + eloff[e] + (size_t)elem_slot(e2d_J + eb, nd, g) * nd;
             for (int jj = 0; jj < nd; ++jj) {
                 bool assembled = true;
                 if (has_A) {
                     const int c = e2d_J[eb + jj];
-                    const int fc = flags[c];
-                    assembled = (fg & 1) && (fc & 1) && (!((fg | fc) & 2) || c == g);
+                    assembled = entry_assembled(fg, flags[c], g, c);
                 }
                 if (assembled) Wm[(size_t)(pm ? pm[elem_ldof[eb + jj]] : elem_ldof[eb + jj]) * n + lr] += M[jj];
             }
@@ -100,9 +181,7 @@ __global__ __launch_bounds__(ASM_NT) void ae_band_topo_kernel(
             const int e = d2e_J[q];
             if (part[e] != p) continue;
             const int eb = e2d_I[e], nd = e2d_I[e + 1] - eb;
-            int kk = 0;
-            while (kk < nd && e2d_J[eb + kk] != g) ++kk;
-            const double *M = elval + eloff[e] + (size_t)kk * nd;
+            const double *M = elval + eloff[e] + (size_t)elem_slot(e2d_J + eb, nd, g) * nd;
             for (int jj = 0; jj < nd; ++jj)
                 if (M[jj] != 0.0) bw = max(bw, abs((int)pm[elem_ldof[eb + jj]] - me));
         }
@@ -349,14 +428,11 @@ __global__ __launch_bounds__(256) void ae_rows8_kernel(
     double v = 0.0;
     if (k < Arow[g + 1] - a0) {
         const int c = Acol[a0 + k];
-        for (int q = d2ae_I[c]; q < d2ae_I[c + 1]; ++q)
-            if (d2ae_J[q] == p) { lc = dof_id_inAE[q]; break; }
+        lc = ae_local_id(d2ae_I, d2ae_J, dof_id_inAE, c, p);
         if (lc >= 0) {
-            const int fg = flags[g], fc = flags[c];
-            const bool assembled = (fg & 1) && (fc & 1) && (!((fg | fc) & 2) || c == g);
-            if (!assembled) {
-                v = Aval[a0 + k];               // copied from the global matrix (aggregates.cpp:930-934)
-            } else {                            // agg_assemble_value, aggregates.cpp:68-184
+            if (!entry_assembled(flags[g], flags[c], g, c)) {
+                v = Aval[a0 + k];
+            } else {
                 const int qb = d2e_I[g], cnt = d2e_I[g + 1] - qb;
                 int es[8], kk[8], jj[8];
 #pragma unroll
@@ -364,10 +440,8 @@ __global__ __launch_bounds__(256) void ae_rows8_kernel(
                     const int e = d2e_J[qb + min(q, cnt - 1)];
                     const int4 lo = *(const int4 *)(e2d_J + (size_t)e * 8), hi = *(const int4 *)(e2d_J + (size_t)e * 8 + 4);
                     es[q] = (q < cnt && part[e] == p) ? e : -1;
-                    kk[q] = (lo.x == g) ? 0 : (lo.y == g) ? 1 : (lo.z == g) ? 2 : (lo.w == g) ? 3 :
-                            (hi.x == g) ? 4 : (hi.y == g) ? 5 : (hi.z == g) ? 6 : 7;
-                    jj[q] = (lo.x == c) ? 0 : (lo.y == c) ? 1 : (lo.z == c) ? 2 : (lo.w == c) ? 3 :
-                            (hi.x == c) ? 4 : (hi.y == c) ? 5 : (hi.z == c) ? 6 : (hi.w == c) ? 7 : -1;
+                    kk[q] = slot8(lo, hi, g);
+                    jj[q] = slot8(lo, hi, c);
                 }
                 double m[8];
 #pragma unroll
@@ -378,17 +452,8 @@ __global__ __launch_bounds__(256) void ae_rows8_kernel(
 #pragma unroll
                 for (int q = 0; q < 8; ++q)
                     if (es[q] >= 0 && jj[q] >= 0) v += m[q];
-                for (int q = 8; q < cnt; ++q) {   // (more than 8 elements at a dof: plain loop)
-                    const int e = d2e_J[qb + q];
-                    if (part[e] != p) continue;
-                    int k2 = -1, j2 = -1;
-                    for (int t = 0; t < 8; ++t) {
-                        const int dd = e2d_J[(size_t)e * 8 + t];
-                        if (dd == g && k2 < 0) k2 = t;
-                        if (dd == c && j2 < 0) j2 = t;
-                    }
-                    if (j2 >= 0) v += elval[((size_t)e * 8 + k2) * 8 + j2];
-                }
+                // (more than 8 elements at a dof: the others one by one)
+                v = walk_entry<true>(v, p, g, c, qb + 8, qb + cnt, d2e_J, part, nullptr, e2d_J, nullptr, elval);
             }
         }
     }
@@ -401,64 +466,109 @@ __global__ __launch_bounds__(256) void ae_rows8_kernel(
 // starts every (row, entry) thread from scratch: the row's dof and row offsets, then, for the entry's column, the
 // dof -> AE list scanned for this agglomerate, the local index, two flags -- a dozen loads per thread, six of them
 // scattered (one cache line per lane) and dependent.  Here the agglomerate's dof list goes into an LDS hash table
-// (dof -> local index) together with the flags and row offsets of its dofs; an entry then costs its column and value
-// (coalesced: the entries of a row are contiguous) and LDS look-ups.  Interface entries (both dofs between
-// agglomerates) still gather their element matrices as above.  hsize: a power of two >= 2 n.
-__global__ __launch_bounds__(256) void ae_rows8_lds_kernel(
+// (AiTable) together with the flags and row offsets of its dofs; an entry then costs its column and value
+// (coalesced: the entries of a row are contiguous) and LDS look-ups.
+// Per dof of the agglomerate: its elements INSIDE the agglomerate, in the order of the dof -> element list, and the dof's
+// slot in each (round 4).  An assembled entry (row g, column c) used to walk g's element list in global memory -- per
+// element its partition and its dofs -- for every one of the row's ~27 entries; now the lists are made once per dof, and
+// an entry matches the row's list against the column's in LDS: one global load (the element-matrix entry) per common
+// element, the same products in the same order.  An agglomerate with a dof in more than MW elements takes walk_entry.
+// HEX8: 8-dof elements, lists of 8, the 8 x 8 match unrolled.  Otherwise elements of at most 8 dofs and of different sizes
+// (level 0 of a mesh of hexes and prisms, tetrahedra or pyramids): lists of AR_MW (a vertex of a hex / prism mesh lies in up
+// to 12 elements), the slots in use and each element's size kept beside them (lne, dnd).
+constexpr int AR_MW = 16;
+constexpr size_t AR_LDS_MAX = 64 * 1024;      // what the kernel may ask for without an attribute
+// The LDS of ae_rows_lds_kernel: the one place that knows its layout.  The host asks size() what to launch with for the
+// largest agglomerate of the batch (the table size hsize: a power of two >= 2 n; 24 bytes cover the alignment of del);
+// the kernel carves its dynamic LDS for its own agglomerate's n rows with the hsize it was launched with.
+template <bool HEX8>
+struct RowsLds {
+    static constexpr int MW = HEX8 ? 8 : AR_MW;
+    // per row: la0, lg, llen (, lne), lflag; del, dkk (, dnd)
+    static constexpr size_t ROW_BYTES = sizeof(roff_t) + (HEX8 ? 2 : 3) * sizeof(int) + 1 + (size_t)MW * (sizeof(int) + (HEX8 ? 1 : 2));
+    static size_t size(int max_n, int &hsize) {
+        for (hsize = 64; hsize < 2 * max_n; hsize <<= 1) {}
+        return (size_t)max_n * ROW_BYTES + (size_t)hsize * (sizeof(int) + sizeof(short)) + 24;
+    }
+    roff_t *la0;            // [n] first entry of the row in A
+    int *lg;                // [n] global dof
+    int *llen;              // [n] entries of the row
+    int *lne;               // [n] slots of the dof's element list in use (<= MW; not HEX8)
+    AiTable loc;            // [hsize] dof -> local index
+    signed char *lflag;     // [n]
+    int *del;               // [n][MW] element or -1
+    unsigned char *dkk;     // [n][MW] slot of the dof in it
+    unsigned char *dnd;     // [n][MW] its number of dofs (not HEX8)
+    __device__ RowsLds(unsigned char *base, int n, int hsize) {
+        size_t o = 0;
+        auto take = [&](size_t sz) { const size_t at = o; o += sz; return base + at; };
+        la0 = (roff_t *)take(sizeof(roff_t) * (size_t)n);
+        lg = (int *)take(sizeof(int) * (size_t)n);
+        llen = (int *)take(sizeof(int) * (size_t)n);
+        lne = (int *)take(HEX8 ? 0 : sizeof(int) * (size_t)n);
+        loc.key = (int *)take(sizeof(int) * (size_t)hsize);
+        loc.val = (short *)take(sizeof(short) * (size_t)hsize);
+        loc.mask = (unsigned)(hsize - 1);
+        lflag = (signed char *)take((size_t)n);
+        o = (o + 3) & ~(size_t)3;
+        del = (int *)take(sizeof(int) * (size_t)MW * n);
+        dkk = take((size_t)MW * n);
+        dnd = take(HEX8 ? 0 : (size_t)MW * n);
+    }
+};
+template <bool HEX8>
+__global__ __launch_bounds__(256) void ae_rows_lds_kernel(
     int ae0, int RW, int hsize, const int *__restrict__ ns, const int64_t *__restrict__ voff,
     const int *__restrict__ ae2d_I, const int *__restrict__ ae2d_J, const signed char *__restrict__ flags,
     const int *__restrict__ d2e_I, const int *__restrict__ d2e_J, const int *__restrict__ part,
-    const int *__restrict__ e2d_J, const double *__restrict__ elval, const roff_t *__restrict__ Arow,
-    const int *__restrict__ Acol, const double *__restrict__ Aval, double *__restrict__ rvals,
-    short *__restrict__ rcols) {
+    const int *__restrict__ e2d_I, const int *__restrict__ e2d_J, const int64_t *__restrict__ eloff,
+    const double *__restrict__ elval, const roff_t *__restrict__ Arow, const int *__restrict__ Acol,
+    const double *__restrict__ Aval, double *__restrict__ rvals, short *__restrict__ rcols) {
     extern __shared__ __align__(16) unsigned char ar_lds[];
+    constexpr int MW = RowsLds<HEX8>::MW;
     const int b = blockIdx.x, p = ae0 + b, n = ns[b];
-    roff_t *la0 = (roff_t *)ar_lds;                 // [n] first entry of the row in A
-    int *lg = (int *)(la0 + n);                     // [n] global dof
-    int *llen = lg + n;                             // [n] entries of the row
-    int *hkey = llen + n;                           // [hsize] dof or -1
-    short *hval = (short *)(hkey + hsize);          // [hsize] local index
-    signed char *lflag = (signed char *)(hval + hsize);   // [n]
-    // per dof of the agglomerate: its elements INSIDE the agglomerate, in the order of the dof -> element list, and the dof's
-    // slot in each (round 4).  An assembled entry (row g, column c) used to walk g's element list in global memory -- per
-    // element its partition and two 16-byte loads of its dofs -- for every one of the row's ~27 entries; now the lists are
-    // made once per dof, and an entry matches the row's list against the column's in LDS: one global load (the element-matrix
-    // entry) per common element, the same products in the same order.
-    int *del = (int *)(((uintptr_t)(lflag + n) + 3) & ~(uintptr_t)3);      // [n][8] element or -1
-    unsigned char *dkk = (unsigned char *)(del + 8 * (size_t)n);          // [n][8] slot of the dof in it
+    const RowsLds<HEX8> L(ar_lds, n, hsize);
     const int tid = threadIdx.x;
-    for (int i = tid; i < hsize; i += 256) hkey[i] = -1;
+    L.loc.clear(tid, 256);
     __syncthreads();
     const int *dofs = ae2d_J + ae2d_I[p];
+    bool many = false;      // (a dof with more than MW elements: the agglomerate takes the walk through global memory)
     for (int i = tid; i < n; i += 256) {
         const int g = dofs[i];
         const roff_t a0 = Arow[g];
-        lg[i] = g;
-        la0[i] = a0;
-        llen[i] = (int)(Arow[g + 1] - a0);
-        lflag[i] = flags[g];
-        unsigned hpos = hash_home((unsigned)g, (unsigned)hsize);
-        while (atomicCAS(&hkey[hpos], -1, g) != -1) hpos = (hpos + 1) & (unsigned)(hsize - 1);
-        hval[hpos] = (short)i;
+        L.lg[i] = g;
+        L.la0[i] = a0;
+        L.llen[i] = (int)(Arow[g + 1] - a0);
+        L.lflag[i] = flags[g];
+        L.loc.insert(g, i);
+        if (!HEX8) {      // (here and not in the loop below: a store by one slot in MW cost the kernel 5 %)
+            const int cnt = d2e_I[g + 1] - d2e_I[g];
+            many = many || cnt > MW;
+            L.lne[i] = min(cnt, MW);
+        }
     }
-    bool many = false;      // (a dof with more than 8 elements: the agglomerate takes the walk through global memory)
-    for (int it = tid; it < n * 8; it += 256) {
-        const int i = it >> 3, q = it & 7;
+    for (int it = tid; it < n * MW; it += 256) {
+        const int i = it / MW, q = it % MW;
         const int g = dofs[i];
         const int qb = d2e_I[g], cnt = d2e_I[g + 1] - qb;
-        many = many || cnt > 8;
-        int e = -1, kk = 0;
+        if (HEX8) many = many || cnt > MW;
+        int e = -1, kk = 0, nd = 0;
         if (q < cnt) {
             e = d2e_J[qb + q];
-            if (part[e] != p) e = -1;
-            else {
+            if (part[e] != p) {
+                e = -1;
+            } else if (HEX8) {
                 const int4 lo = *(const int4 *)(e2d_J + (size_t)e * 8), hi = *(const int4 *)(e2d_J + (size_t)e * 8 + 4);
-                kk = (lo.x == g) ? 0 : (lo.y == g) ? 1 : (lo.z == g) ? 2 : (lo.w == g) ? 3 :
-                     (hi.x == g) ? 4 : (hi.y == g) ? 5 : (hi.z == g) ? 6 : 7;
+                kk = slot8(lo, hi, g);
+            } else {
+                const int eb = e2d_I[e];
+                nd = e2d_I[e + 1] - eb;
+                kk = elem_slot(e2d_J + eb, nd, g);
             }
         }
-        del[it] = e;
-        dkk[it] = (unsigned char)kk;
+        L.del[it] = e;
+        L.dkk[it] = (unsigned char)kk;
+        if (!HEX8) L.dnd[it] = (unsigned char)nd;
     }
     const bool walk = __syncthreads_or(many ? 1 : 0) != 0;
     const size_t obase = (size_t)voff[b] * RW;
@@ -475,26 +585,14 @@ __global__ __launch_bounds__(256) void ae_rows8_lds_kernel(
             const int it = it0 + 256 * u;
             const int lr = it < n * RW ? it / RW : 0, k = it - lr * RW;
             lrs[u] = lr;
-            on[u] = it < n * RW && k < llen[lr];
-            as[u] = la0[lr] + k;
+            on[u] = it < n * RW && k < L.llen[lr];
+            as[u] = L.la0[lr] + k;
             cs[u] = on[u] ? Acol[as[u]] : -1;
         }
 #pragma unroll
         for (int u = 0; u < UN; ++u) vs[u] = on[u] ? Aval[as[u]] : 0.0;      // (used unless the entry is assembled from elements)
 #pragma unroll
-        for (int u = 0; u < UN; ++u) {
-            lcs[u] = -1;
-            if (on[u]) {
-                const int c = cs[u];
-                unsigned hpos = hash_home((unsigned)c, (unsigned)hsize);
-                for (;;) {
-                    const int key = hkey[hpos];
-                    if (key == c) { lcs[u] = hval[hpos]; break; }
-                    if (key == -1) break;
-                    hpos = (hpos + 1) & (unsigned)(hsize - 1);
-                }
-            }
-        }
+        for (int u = 0; u < UN; ++u) lcs[u] = on[u] ? L.loc(cs[u]) : -1;
 #pragma unroll
         for (int u = 0; u < UN; ++u) {
             const int it = it0 + 256 * u;
@@ -502,181 +600,36 @@ __global__ __launch_bounds__(256) void ae_rows8_lds_kernel(
             const int lr = lrs[u], lc = lcs[u], c = cs[u];
             double v = 0.0;
             if (lc >= 0) {
-                const int g = lg[lr];
-                const int fg = lflag[lr], fc = lflag[lc];
-                const bool assembled = (fg & 1) && (fc & 1) && (!((fg | fc) & 2) || c == g);
-                if (!assembled) {
-                    v = vs[u];                      // copied from the global matrix (aggregates.cpp:930-934)
-                } else if (!walk) {                 // agg_assemble_value, aggregates.cpp:68-184: the elements of g inside the agglomerate
-                    // that also hold c, ascending in g's list (the order of the walk below)
+                const int g = L.lg[lr];
+                if (!entry_assembled(L.lflag[lr], L.lflag[lc], g, c)) {
+                    v = vs[u];
+                } else if (!walk) {     // the elements of g inside the agglomerate that also hold c, ascending in g's list (walk_entry's order)
+                    const int *er = L.del + lr * MW, *ec = L.del + lc * MW;
+                    if constexpr (HEX8) {       // the 8 x 8 match, unrolled
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const int e = del[lr * 8 + q];
-                        if (e < 0) continue;
-                        int jj = -1;
+                        for (int q = 0; q < MW; ++q) {
+                            const int e = er[q];
+                            if (e < 0) continue;
+                            int jj = -1;
 #pragma unroll
-                        for (int q2 = 0; q2 < 8; ++q2)
-                            if (del[lc * 8 + q2] == e) jj = dkk[lc * 8 + q2];
-                        if (jj >= 0) v += elval[((size_t)e * 8 + dkk[lr * 8 + q]) * 8 + jj];
-                    }
-                } else {
-                    const int qb = d2e_I[g], cnt = d2e_I[g + 1] - qb;
-                    for (int q = 0; q < cnt; ++q) {      // ascending element id: the order of the kernel above
-                        const int e = d2e_J[qb + q];
-                        if (part[e] != p) continue;
-                        const int4 lo = *(const int4 *)(e2d_J + (size_t)e * 8), hi = *(const int4 *)(e2d_J + (size_t)e * 8 + 4);
-                        const int kk = (lo.x == g) ? 0 : (lo.y == g) ? 1 : (lo.z == g) ? 2 : (lo.w == g) ? 3 :
-                                       (hi.x == g) ? 4 : (hi.y == g) ? 5 : (hi.z == g) ? 6 : 7;
-                        const int jj = (lo.x == c) ? 0 : (lo.y == c) ? 1 : (lo.z == c) ? 2 : (lo.w == c) ? 3 :
-                                       (hi.x == c) ? 4 : (hi.y == c) ? 5 : (hi.z == c) ? 6 : (hi.w == c) ? 7 : -1;
-                        if (jj >= 0) v += elval[((size_t)e * 8 + kk) * 8 + jj];
-                    }
-                }
-            }
-            rvals[obase + it] = v;
-            rcols[obase + it] = (short)lc;
-        }
-    }
-}
-
-// The same for elements of at most 8 dofs and of different sizes (level 0 of a mesh of hexes and prisms, tetrahedra or
-// pyramids): an element's slots are found through e2d_I (rows are not 16-byte aligned: scalar loads), its matrix entries read
-// at eloff[e] + kk nd_e + jj.  The per-dof element lists are AR_MW wide (a vertex of a hex / prism mesh lies in up to 12
-// elements); an agglomerate with a dof in more elements takes the walk through global memory.  Every entry is summed over
-// the elements of its row's dof inside the agglomerate in ascending element id, as in ae_build_kernel's generic walk.
-constexpr int AR_MW = 16;
-static size_t rows_mixed_lds(int max_n, int &hsize) {
-    hsize = 64;
-    while (hsize < 2 * max_n) hsize <<= 1;
-    // la0, lg, llen, lne, lflag; hkey, hval; (align) del, dkk, dnd (8 x 9 x 5-element agglomerates of 405 dofs: 53 KB)
-    return (size_t)max_n * (8 + 4 + 4 + 4 + 1) + (size_t)hsize * 6 + 16 + (size_t)max_n * AR_MW * (4 + 1 + 1) + 8;
-}
-__global__ __launch_bounds__(256) void ae_rows_mixed_lds_kernel(
-    int ae0, int RW, int hsize, const int *__restrict__ ns, const int64_t *__restrict__ voff,
-    const int *__restrict__ ae2d_I, const int *__restrict__ ae2d_J, const signed char *__restrict__ flags,
-    const int *__restrict__ d2e_I, const int *__restrict__ d2e_J, const int *__restrict__ part,
-    const int *__restrict__ e2d_I, const int *__restrict__ e2d_J, const int64_t *__restrict__ eloff,
-    const double *__restrict__ elval, const roff_t *__restrict__ Arow, const int *__restrict__ Acol,
-    const double *__restrict__ Aval, double *__restrict__ rvals, short *__restrict__ rcols) {
-    extern __shared__ __align__(16) unsigned char ar_lds[];
-    const int b = blockIdx.x, p = ae0 + b, n = ns[b];
-    roff_t *la0 = (roff_t *)ar_lds;                 // [n] first entry of the row in A
-    int *lg = (int *)(la0 + n);                     // [n] global dof
-    int *llen = lg + n;                             // [n] entries of the row
-    int *lne = llen + n;                            // [n] slots of the dof's element list in use (<= AR_MW)
-    int *hkey = lne + n;                            // [hsize] dof or -1
-    short *hval = (short *)(hkey + hsize);          // [hsize] local index
-    signed char *lflag = (signed char *)(hval + hsize);   // [n]
-    int *del = (int *)(((uintptr_t)(lflag + n) + 3) & ~(uintptr_t)3);         // [n][AR_MW] element or -1
-    unsigned char *dkk = (unsigned char *)(del + AR_MW * (size_t)n);            // [n][AR_MW] slot of the dof in it
-    unsigned char *dnd = dkk + AR_MW * (size_t)n;                               // [n][AR_MW] its number of dofs
-    const int tid = threadIdx.x;
-    for (int i = tid; i < hsize; i += 256) hkey[i] = -1;
-    __syncthreads();
-    const int *dofs = ae2d_J + ae2d_I[p];
-    bool many = false;      // (a dof with more than AR_MW elements: the agglomerate takes the walk through global memory)
-    for (int i = tid; i < n; i += 256) {
-        const int g = dofs[i];
-        const roff_t a0 = Arow[g];
-        lg[i] = g;
-        la0[i] = a0;
-        llen[i] = (int)(Arow[g + 1] - a0);
-        lflag[i] = flags[g];
-        const int cnt = d2e_I[g + 1] - d2e_I[g];
-        many = many || cnt > AR_MW;
-        lne[i] = min(cnt, AR_MW);
-        unsigned hpos = hash_home((unsigned)g, (unsigned)hsize);
-        while (atomicCAS(&hkey[hpos], -1, g) != -1) hpos = (hpos + 1) & (unsigned)(hsize - 1);
-        hval[hpos] = (short)i;
-    }
-    for (int it = tid; it < n * AR_MW; it += 256) {
-        const int i = it / AR_MW, q = it - i * AR_MW;
-        const int g = dofs[i];
-        const int qb = d2e_I[g], cnt = d2e_I[g + 1] - qb;
-        int e = -1, kk = 0, nd = 0;
-        if (q < cnt) {
-            e = d2e_J[qb + q];
-            if (part[e] != p) {
-                e = -1;
-            } else {
-                const int eb = e2d_I[e];
-                nd = e2d_I[e + 1] - eb;
-                while (kk < nd - 1 && e2d_J[eb + kk] != g) ++kk;
-            }
-        }
-        del[it] = e;
-        dkk[it] = (unsigned char)kk;
-        dnd[it] = (unsigned char)nd;
-    }
-    const bool walk = __syncthreads_or(many ? 1 : 0) != 0;
-    const size_t obase = (size_t)voff[b] * RW;
-    constexpr int UN = 4;
-    for (int it0 = tid; it0 < n * RW; it0 += 256 * UN) {
-        int lrs[UN], cs[UN], lcs[UN];
-        double vs[UN];
-        roff_t as[UN];
-        bool on[UN];
-#pragma unroll
-        for (int u = 0; u < UN; ++u) {
-            const int it = it0 + 256 * u;
-            const int lr = it < n * RW ? it / RW : 0, k = it - lr * RW;
-            lrs[u] = lr;
-            on[u] = it < n * RW && k < llen[lr];
-            as[u] = la0[lr] + k;
-            cs[u] = on[u] ? Acol[as[u]] : -1;
-        }
-#pragma unroll
-        for (int u = 0; u < UN; ++u) vs[u] = on[u] ? Aval[as[u]] : 0.0;      // (used unless the entry is assembled from elements)
-#pragma unroll
-        for (int u = 0; u < UN; ++u) {
-            lcs[u] = -1;
-            if (on[u]) {
-                const int c = cs[u];
-                unsigned hpos = hash_home((unsigned)c, (unsigned)hsize);
-                for (;;) {
-                    const int key = hkey[hpos];
-                    if (key == c) { lcs[u] = hval[hpos]; break; }
-                    if (key == -1) break;
-                    hpos = (hpos + 1) & (unsigned)(hsize - 1);
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < UN; ++u) {
-            const int it = it0 + 256 * u;
-            if (it >= n * RW) continue;
-            const int lr = lrs[u], lc = lcs[u], c = cs[u];
-            double v = 0.0;
-            if (lc >= 0) {
-                const int g = lg[lr];
-                const int fg = lflag[lr], fc = lflag[lc];
-                const bool assembled = (fg & 1) && (fc & 1) && (!((fg | fc) & 2) || c == g);
-                if (!assembled) {
-                    v = vs[u];                      // copied from the global matrix (aggregates.cpp:930-934)
-                } else if (!walk) {                 // agg_assemble_value, aggregates.cpp:68-184
-                    const int nr = lne[lr], nc = lne[lc];
-                    for (int q = 0; q < nr; ++q) {
-                        const int e = del[lr * AR_MW + q];
-                        if (e < 0) continue;
-                        int jj = -1;
-                        for (int q2 = 0; q2 < nc; ++q2)
-                            if (del[lc * AR_MW + q2] == e) jj = dkk[lc * AR_MW + q2];
-                        if (jj >= 0) v += elval[eloff[e] + dkk[lr * AR_MW + q] * dnd[lr * AR_MW + q] + jj];
-                    }
-                } else {
-                    const int qb = d2e_I[g], cnt = d2e_I[g + 1] - qb;
-                    for (int q = 0; q < cnt; ++q) {      // ascending element id
-                        const int e = d2e_J[qb + q];
-                        if (part[e] != p) continue;
-                        const int eb = e2d_I[e], nd = e2d_I[e + 1] - eb;
-                        int kk = -1, jj = -1;
-                        for (int t = 0; t < nd; ++t) {
-                            const int dd = e2d_J[eb + t];
-                            if (dd == g && kk < 0) kk = t;
-                            if (dd == c && jj < 0) jj = t;
+                            for (int q2 = 0; q2 < MW; ++q2)
+                                if (ec[q2] == e) jj = L.dkk[lc * MW + q2];
+                            if (jj >= 0) v += elval[((size_t)e * 8 + L.dkk[lr * MW + q]) * 8 + jj];
                         }
-                        if (jj >= 0) v += elval[eloff[e] + (int64_t)kk * nd + jj];
+                    } else {                    // counted loops over the slots in use
+                        const int nr = L.lne[lr], nc = L.lne[lc];
+                        for (int q = 0; q < nr; ++q) {
+                            const int e = er[q];
+                            if (e < 0) continue;
+                            int jj = -1;
+                            for (int q2 = 0; q2 < nc; ++q2)
+                                if (ec[q2] == e) jj = L.dkk[lc * MW + q2];
+                            if (jj >= 0) v += elval[eloff[e] + L.dkk[lr * MW + q] * L.dnd[lr * MW + q] + jj];
+                        }
                     }
+                } else {
+                    const int qb = d2e_I[g];
+                    v = walk_entry<HEX8>(0.0, p, g, c, qb, d2e_I[g + 1], d2e_J, part, e2d_I, e2d_J, eloff, elval);
                 }
             }
             rvals[obase + it] = v;
@@ -685,10 +638,9 @@ __global__ __launch_bounds__(256) void ae_rows_mixed_lds_kernel(
     }
 }
 
-constexpr int AB_MAXE = 8;   // elements per dof kept in the LDS row tables (hexes: <= 8)
-
-// NDE > 0: every element has exactly NDE dofs (level 0: elem_to_dof is a dense NE x NDE array),
-// which turns the per-element searches into a few independent vector loads.
+// NDE is a tag only: the PRE branch reads the precomputed sparse rows and nothing of the elements, so one instantiation
+// serves every kind of element there; it stays in the name because the benchmark's label table spells
+// ae_build_kernel<true, 8, true>.
 template <bool SCALE, int NDE, bool PRE>
 __global__ __launch_bounds__(AB_NT) void ae_build_kernel(
     int ae0, int RW, const int *__restrict__ ns, const int64_t *__restrict__ moff,
@@ -701,8 +653,9 @@ __global__ __launch_bounds__(AB_NT) void ae_build_kernel(
     const double *__restrict__ elval, const roff_t *__restrict__ Arow, const int *__restrict__ Acol,
     const double *__restrict__ Aval, const double *__restrict__ rvals, const short *__restrict__ rcols,
     const short *__restrict__ perm, int *__restrict__ bw_out, int band_only, const int *__restrict__ only = nullptr) {
+    static_assert(PRE || NDE == 0, "without precomputed rows the elements are walked through e2d_I / eloff");
     extern __shared__ __align__(16) double lds[];
-    __shared__ int anybig, sbw;
+    __shared__ int sbw;
     // (only: the matrices of the batch to build -- the representatives of its classes of identical agglomerates)
     const int b = only ? only[blockIdx.x] : (int)blockIdx.x, p = ae0 + b, n = ns[b];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -710,13 +663,11 @@ __global__ __launch_bounds__(AB_NT) void ae_build_kernel(
     double *vals = lds;                                   // [n * RW]
     double *dg = vals + (size_t)n * RW;                   // [n]
     double *dis = dg + n;                                 // [n]
-    double *colbuf = dis + n;                             // [NW][n]; phases 0-1: the row tables
-    int *rowel = (int *)colbuf;                           // [n * AB_MAXE] elements of the row's dof in this AE
-    short *rowkk = (short *)(rowel + (size_t)n * AB_MAXE);  // [n * AB_MAXE] position of the dof in them
+    double *colbuf = dis + n;                             // [NW][n]
     short *cols = (short *)(colbuf + (size_t)NW * n);     // [n * RW] AE-local column or -1
     int *gdof = (int *)(cols + (((size_t)n * RW + 3) & ~(size_t)3));  // [n] global dof of each row
     const int *aedofs = ae2d_J + ae2d_I[p];
-    if (PRE) {   // sparse rows precomputed by ae_rows8_kernel: coalesced copy into LDS
+    if (PRE) {   // sparse rows precomputed by the ae_rows kernels: coalesced copy into LDS
         const size_t base = (size_t)voff[b] * RW;
         for (int it = tid; it < n * RW; it += AB_NT) {
             vals[it] = rvals[base + it];
@@ -724,90 +675,27 @@ __global__ __launch_bounds__(AB_NT) void ae_build_kernel(
         }
         __syncthreads();
     } else {
-    if (tid == 0) anybig = 0;
-    for (int lr = tid; lr < n; lr += AB_NT) gdof[lr] = aedofs[lr];
-    __syncthreads();
-    // ---- 0. per row: the elements of its dof that lie in this AE, and the dof's slot in them ----
-    for (int it = tid; it < n * AB_MAXE; it += AB_NT) {
-        const int lr = it / AB_MAXE, q = it - lr * AB_MAXE;
-        const int g = gdof[lr];
-        const int qb = d2e_I[g], cnt = d2e_I[g + 1] - qb;
-        int e = -1, kk = 0;
-        if (q == 0 && cnt > AB_MAXE) anybig = 1;
-        if (q < cnt) {
-            e = d2e_J[qb + q];
-            if (part[e] != p) {
-                e = -1;
-            } else if (NDE == 8) {
-                const int4 lo = *(const int4 *)(e2d_J + (size_t)e * 8), hi = *(const int4 *)(e2d_J + (size_t)e * 8 + 4);
-                kk = (lo.x == g) ? 0 : (lo.y == g) ? 1 : (lo.z == g) ? 2 : (lo.w == g) ? 3 :
-                     (hi.x == g) ? 4 : (hi.y == g) ? 5 : (hi.z == g) ? 6 : 7;
-            } else {
-                const int eb = e2d_I[e], nd = e2d_I[e + 1] - eb;
-                while (kk < nd && e2d_J[eb + kk] != g) ++kk;
-            }
-        }
-        rowel[it] = e;
-        rowkk[it] = (short)kk;
-    }
-    __syncthreads();
-    const bool big = anybig != 0;
-    // ---- 1. sparse rows ----
-    for (int it = tid; it < n * RW; it += AB_NT) {
-        const int lr = it / RW, k = it - lr * RW;
-        const int g = gdof[lr];
-        const roff_t a0 = Arow[g];
-        int lc = -1;
-        double v = 0.0;
-        if (k < Arow[g + 1] - a0) {
-            const int c = Acol[a0 + k];
-            for (int q = d2ae_I[c]; q < d2ae_I[c + 1]; ++q)
-                if (d2ae_J[q] == p) { lc = dof_id_inAE[q]; break; }
-            if (lc >= 0) {
-                const int fg = flags[g], fc = flags[c];
-                const bool assembled = (fg & 1) && (fc & 1) && (!((fg | fc) & 2) || c == g);
-                if (!assembled) {
-                    v = Aval[a0 + k];           // copied from the global matrix (aggregates.cpp:930-934)
-                } else if (NDE == 8 && !big) {  // agg_assemble_value, aggregates.cpp:68-184
-                    int es[AB_MAXE], jj[AB_MAXE];
-#pragma unroll
-                    for (int q = 0; q < AB_MAXE; ++q) {
-                        es[q] = rowel[lr * AB_MAXE + q];
-                        const int ec = max(es[q], 0);
-                        const int4 lo = *(const int4 *)(e2d_J + (size_t)ec * 8), hi = *(const int4 *)(e2d_J + (size_t)ec * 8 + 4);
-                        jj[q] = (lo.x == c) ? 0 : (lo.y == c) ? 1 : (lo.z == c) ? 2 : (lo.w == c) ? 3 :
-                                (hi.x == c) ? 4 : (hi.y == c) ? 5 : (hi.z == c) ? 6 : (hi.w == c) ? 7 : -1;
-                    }
-                    double m[AB_MAXE];
-#pragma unroll
-                    for (int q = 0; q < AB_MAXE; ++q) {
-                        const bool on = es[q] >= 0 && jj[q] >= 0;
-                        const int kk = rowkk[lr * AB_MAXE + q];
-                        m[q] = on ? elval[((size_t)es[q] * 8 + kk) * 8 + jj[q]] : 0.0;
-                    }
-#pragma unroll
-                    for (int q = 0; q < AB_MAXE; ++q)
-                        if (es[q] >= 0 && jj[q] >= 0) v += m[q];
-                } else {
-                    for (int q = d2e_I[g]; q < d2e_I[g + 1]; ++q) {
-                        const int e = d2e_J[q];
-                        if (part[e] != p) continue;
-                        const int eb = e2d_I[e], nd = e2d_I[e + 1] - eb;
-                        int kk = -1, j2 = -1;
-                        for (int t = 0; t < nd; ++t) {
-                            const int dd = e2d_J[eb + t];
-                            if (dd == g && kk < 0) kk = t;
-                            if (dd == c && j2 < 0) j2 = t;
-                        }
-                        if (j2 >= 0) v += elval[eloff[e] + (size_t)kk * nd + j2];
-                    }
+        for (int lr = tid; lr < n; lr += AB_NT) gdof[lr] = aedofs[lr];
+        __syncthreads();
+        // ---- 1. sparse rows ----
+        for (int it = tid; it < n * RW; it += AB_NT) {
+            const int lr = it / RW, k = it - lr * RW;
+            const int g = gdof[lr];
+            const roff_t a0 = Arow[g];
+            int lc = -1;
+            double v = 0.0;
+            if (k < Arow[g + 1] - a0) {
+                const int c = Acol[a0 + k];
+                lc = ae_local_id(d2ae_I, d2ae_J, dof_id_inAE, c, p);
+                if (lc >= 0) {
+                    if (!entry_assembled(flags[g], flags[c], g, c)) v = Aval[a0 + k];
+                    else v = walk_entry<false>(0.0, p, g, c, d2e_I[g], d2e_I[g + 1], d2e_J, part, e2d_I, e2d_J, eloff, elval);
                 }
             }
+            vals[it] = v;
+            cols[it] = (short)lc;
         }
-        vals[it] = v;
-        cols[it] = (short)lc;
-    }
-    __syncthreads();
+        __syncthreads();
     }
     // ---- 2. diagonal, 3. D and D^-1/2 ----
     for (int lr = tid; lr < n; lr += AB_NT) {
@@ -915,9 +803,7 @@ __global__ __launch_bounds__(ASM_NT) void ae_extract_kernel(
             const int c = Acol[k];
             const double v = Aval[k];
             if (v == 0.0) continue;
-            int lc = -1;
-            for (int q = d2ae_I[c]; q < d2ae_I[c + 1]; ++q)
-                if (d2ae_J[q] == p) { lc = dof_id_inAE[q]; break; }
+            const int lc = ae_local_id(d2ae_I, d2ae_J, dof_id_inAE, c, p);
             if (lc < 0) continue;
             ++stored;
             rowsum += v;
@@ -950,11 +836,7 @@ __global__ __launch_bounds__(ASM_NT) void ae_window_kernel(
         if (tid == 0) Wm[0] = 1.0;
         return;
     }
-    auto local_id = [&](int c) {
-        for (int q = d2ae_I[c]; q < d2ae_I[c + 1]; ++q)
-            if (d2ae_J[q] == p) return dof_id_inAE[q];
-        return -1;
-    };
+    auto local_id = [&](int c) { return ae_local_id(d2ae_I, d2ae_J, dof_id_inAE, c, p); };
     const int *aedofs = ae2d_J + ae2d_I[p];
     for (int lr = tid; lr < n; lr += ASM_NT) {
         const int g = aedofs[lr];
@@ -1002,9 +884,9 @@ static RowsCache &g_rows = *new RowsCache;       // never destroyed: no HIP call
 static int g_rows_gen = 0;
 void ae_rows_new_build() { ++g_rows_gen; }
 
-static void launch_rows8(hipStream_t s, const DevRelations &rel, const DCsr &A, const DevElmats &el, int ae0,
-                         const EigBatch &batch, int RW, const double *&rv, const short *&rc,
-                         const RowsSpan *rows = nullptr) {
+static void launch_ae_rows(hipStream_t s, const DevRelations &rel, const DCsr &A, const DevElmats &el, int ae0,
+                           const EigBatch &batch, int RW, const double *&rv, const short *&rc,
+                           const RowsSpan *rows = nullptr) {
     static DBuf<double> &g_rvals = *new DBuf<double>;
     static DBuf<short> &g_rcols = *new DBuf<short>;
     double *dv;
@@ -1030,47 +912,45 @@ static void launch_rows8(hipStream_t s, const DevRelations &rel, const DCsr &A, 
         dc = g_rcols.p;
     }
     profiler().begin(s);
-    constexpr bool old_rows = false;      // (the kernel without the LDS hash of the agglomerate's dofs: larger agglomerates only)
-    int hsize = 64;
-    while (hsize < 2 * batch.max_n) hsize <<= 1;
-    const size_t lds = (size_t)batch.max_n * (8 + 4 + 4 + 1) + (size_t)hsize * 6 + 16 + (size_t)batch.max_n * 40 + 8;      // (+ the per-dof element lists)
-    if (el.nde != 8) {      // elements of different sizes (the callers checked rows_mixed_fit)
-        int mhsize = 0;
-        const size_t mlds = rows_mixed_lds(batch.max_n, mhsize);
-        hipLaunchKernelGGL(ae_rows_mixed_lds_kernel, dim3(batch.count), dim3(256), mlds, s, ae0, RW, mhsize, batch.n.p,
-                           batch.voff.p, rel.ae2d_I.p, rel.ae2d_J.p, rel.flags.p, rel.d2e_I.p, rel.d2e_J.p, rel.part.p,
-                           rel.e2d_I.p, rel.e2d_J.p, el.off.p, el.val.p, A.rowptr.p, A.col.p, A.val.p, dv, dc);
-    } else if (!old_rows && lds <= 64 * 1024)
-        hipLaunchKernelGGL(ae_rows8_lds_kernel, dim3(batch.count), dim3(256), lds, s, ae0, RW, hsize, batch.n.p, batch.voff.p,
-                           rel.ae2d_I.p, rel.ae2d_J.p, rel.flags.p, rel.d2e_I.p, rel.d2e_J.p, rel.part.p, rel.e2d_J.p,
-                           el.dense(), A.rowptr.p, A.col.p, A.val.p, dv, dc);
-    else
-    hipLaunchKernelGGL(ae_rows8_kernel, dim3(div_up((long)batch.max_n * RW, 256), batch.count), dim3(256), 0, s,
-                       ae0, RW, batch.n.p, batch.voff.p, rel.ae2d_I.p, rel.ae2d_J.p, rel.d2ae_I.p,
-                       rel.d2ae_J.p, rel.dof_id_inAE.p, rel.flags.p, rel.d2e_I.p, rel.d2e_J.p, rel.part.p,
-                       rel.e2d_J.p, el.dense(), A.rowptr.p, A.col.p, A.val.p, dv, dc);
+    int hsize = 0;
+    size_t lds = 0;
+    auto launch_lds = [&](auto kern, const int *e2d_I, const int64_t *eloff, const double *elval) {
+        hipLaunchKernelGGL(kern, dim3(batch.count), dim3(256), lds, s, ae0, RW, hsize, batch.n.p, batch.voff.p,
+                           rel.ae2d_I.p, rel.ae2d_J.p, rel.flags.p, rel.d2e_I.p, rel.d2e_J.p, rel.part.p, e2d_I, rel.e2d_J.p,
+                           eloff, elval, A.rowptr.p, A.col.p, A.val.p, dv, dc);
+    };
+    if (el.nde != 8) {      // elements of different sizes (rows_eligible: their tables fit)
+        lds = RowsLds<false>::size(batch.max_n, hsize);
+        launch_lds(ae_rows_lds_kernel<false>, rel.e2d_I.p, el.off.p, el.val.p);
+    } else if ((lds = RowsLds<true>::size(batch.max_n, hsize)) <= AR_LDS_MAX)
+        launch_lds(ae_rows_lds_kernel<true>, nullptr, nullptr, el.dense());
+    else                    // larger agglomerates: the kernel without the agglomerate's tables in LDS
+        hipLaunchKernelGGL(ae_rows8_kernel, dim3(div_up((long)batch.max_n * RW, 256), batch.count), dim3(256), 0, s,
+                           ae0, RW, batch.n.p, batch.voff.p, rel.ae2d_I.p, rel.ae2d_J.p, rel.d2ae_I.p,
+                           rel.d2ae_J.p, rel.dof_id_inAE.p, rel.flags.p, rel.d2e_I.p, rel.d2e_J.p, rel.part.p,
+                           rel.e2d_J.p, el.dense(), A.rowptr.p, A.col.p, A.val.p, dv, dc);
     SA_HIP_CHECK(hipGetLastError());
     profiler().end(s, "ae_rows", 0.0, 0.0);
     rv = dv;
     rc = dc;
 }
 
-// level 0 of a mesh whose elements have at most 8 dofs and different sizes, agglomerates whose tables fit the LDS of
-// ae_rows_mixed_lds_kernel (otherwise: the generic assembly)
-static bool rows_mixed_fit(const DevElmats &el, const EigBatch &batch) {
-    if (el.algebraic || el.nde != 0 || el.max_nd < 1 || el.max_nd > 8) return false;
+// Sparse rows ahead of the fused kernel and of the coarse element matrices (launch_ae_rows): level 0 with element matrices,
+// 8-dof elements -- or elements of at most 8 dofs and different sizes whose agglomerates' tables fit the LDS of
+// ae_rows_lds_kernel (otherwise: the generic assembly).  batch.count is grid.y of ae_rows8_kernel, a local column is a short.
+static bool rows_eligible(const DevElmats &el, const EigBatch &batch) {
+    if (!batch.count || el.algebraic || batch.count > 65535 || batch.max_n > 32767) return false;
+    if (el.nde == 8) return true;
     int hsize = 0;
-    return rows_mixed_lds(batch.max_n, hsize) <= 64 * 1024;
+    return el.nde == 0 && el.max_nd >= 1 && el.max_nd <= 8 && RowsLds<false>::size(batch.max_n, hsize) <= AR_LDS_MAX;
 }
 
 bool ae_sparse_rows(hipStream_t s, const DevRelations &rel, const DCsr &A, const DevElmats &el, int ae0,
                     const EigBatch &batch, int &RW, const double *&rv, const short *&rc, const RowsSpan *rows) {
-    if (!batch.count || el.algebraic || !(el.nde == 8 || rows_mixed_fit(el, batch)) || batch.count > 65535 ||
-        batch.max_n > 32767)
-        return false;
+    if (!rows_eligible(el, batch)) return false;
     if (A.max_row < 0) A.max_row = csr_max_row(s, A);
     RW = A.max_row;
-    launch_rows8(s, rel, A, el, ae0, batch, RW, rv, rc, rows);
+    launch_ae_rows(s, rel, A, el, ae0, batch, RW, rv, rc, rows);
     return true;
 }
 
@@ -1080,10 +960,10 @@ bool ae_sparse_rows(hipStream_t s, const DevRelations &rel, const DCsr &A, const
 // in which case the box is renumbered with its SHORTEST extent running fastest: half bandwidth
 // e1 e2 + e1 + 1 with e1 <= e2 the two smaller extents instead of a b + a + 1 (the 9 x 9 x 5 boxes
 // of the headline problem: 51 instead of 91).  Everything is verified entry by entry; any other
-// agglomerate keeps the rank order.  (box_order = 0: rank order only.)
+// agglomerate keeps the rank order.
 __global__ __launch_bounds__(256) void ae_perm_kernel(int ae0, const int *__restrict__ ns, const int64_t *__restrict__ voff,
                                                       const int *__restrict__ ae2d_I, const int *__restrict__ ae2d_J,
-                                                      short *__restrict__ perm, short *__restrict__ iperm, int box_order) {
+                                                      short *__restrict__ perm, short *__restrict__ iperm) {
     extern __shared__ int gd[];          // [n] dofs in table order, [n] sorted
     __shared__ int box[6];               // a, b, c, s2, s3, ok
     const int b = blockIdx.x, n = ns[b];
@@ -1101,7 +981,7 @@ __global__ __launch_bounds__(256) void ae_perm_kernel(int ae0, const int *__rest
     if (threadIdx.x == 0) {
         int a = 1, bb = 1, c = 1, s2 = 0, s3 = 0, ok = 0;
         while (a < n && sid[a] == sid[0] + a) ++a;
-        if (box_order && a < n && n % a == 0) {
+        if (a < n && n % a == 0) {
             s2 = sid[a] - sid[0];
             while (bb * a < n && sid[bb * a] == sid[0] + bb * s2) ++bb;
             if (n % (a * bb) == 0) {
@@ -1447,7 +1327,7 @@ void ae_order_only(hipStream_t s, const DevRelations &rel, int ae0, EigBatch &ba
     const size_t rows_total = (size_t)batch.h_voff[batch.count];
     if (batch.perm.n < rows_total) { batch.perm.alloc(rows_total); batch.iperm.alloc(rows_total); }
     hipLaunchKernelGGL(ae_perm_kernel, dim3(batch.count), dim3(256), 2 * sizeof(int) * (size_t)batch.max_n, s, ae0, batch.n.p,
-                       batch.voff.p, rel.ae2d_I.p, rel.ae2d_J.p, batch.perm.p, batch.iperm.p, 1);
+                       batch.voff.p, rel.ae2d_I.p, rel.ae2d_J.p, batch.perm.p, batch.iperm.p);
     SA_HIP_CHECK(hipGetLastError());
     batch.has_perm = true;
     ae_level_order(s, rel, ae0, batch, mode, res, nullptr);
@@ -1476,35 +1356,6 @@ struct AeInputs {
     const int *Acol;
     const double *Aval;
     int ae0;
-};
-// local number of a global dof in an agglomerate, or -1: an LDS hash table of the agglomerate's dofs (open addressing, hsize a
-// power of two >= 2 n; the list search through dof -> AE of the assembly kernel costs six dependent global loads per entry of a
-// 375-entry row)
-struct AiTable {
-    int *key;
-    short *val;
-    unsigned mask;
-    __device__ inline void build(const AeInputs &v, int p, int n, int tid, int nt) {
-        for (int i = tid; i <= (int)mask; i += nt) key[i] = -1;
-        __syncthreads();
-        const int *dofs = v.ae2d_J + v.ae2d_I[p];
-        for (int i = tid; i < n; i += nt) {
-            const int g = dofs[i];
-            unsigned h = hash_home((unsigned)g, mask + 1u);
-            while (atomicCAS(&key[h], -1, g) != -1) h = (h + 1) & mask;
-            val[h] = (short)i;
-        }
-        __syncthreads();
-    }
-    __device__ inline int operator()(int c) const {
-        unsigned h = hash_home((unsigned)c, mask + 1u);
-        for (;;) {
-            const int k = key[h];
-            if (k == c) return val[h];
-            if (k == -1) return -1;
-            h = (h + 1) & mask;
-        }
-    }
 };
 // The words of row lr0 of agglomerate p (matrix b), visited by a WAVEFRONT: lanes take the entries of the row of the global
 // matrix, then, element by element of the row's dof, the dofs of the element (coalesced reads of the element-matrix row).
@@ -1612,7 +1463,7 @@ __global__ __launch_bounds__(AI_NT) void asm_hash_kernel(AeInputs v, int hsize, 
     extern __shared__ __align__(16) unsigned char ai_lds[];
     const int b = blockIdx.x, p = v.ae0 + b, n = v.ns[b], tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     AiTable loc{(int *)ai_lds, (short *)(ai_lds + 4 * (size_t)hsize), (unsigned)(hsize - 1)};
-    if (v.has_A) loc.build(v, p, n, tid, AI_NT);
+    if (v.has_A) loc.build(v.ae2d_J + v.ae2d_I[p], n, tid, AI_NT);
     const AiRow x{b, p, &loc};
     DdHash h;
     for (int lr0 = blockIdx.y * (AI_NT / 64) + wv; lr0 < n; lr0 += (AI_NT / 64) * gridDim.y) {
@@ -1635,7 +1486,7 @@ __global__ __launch_bounds__(AI_NT) void asm_verify_kernel(AeInputs v, int hsize
     const size_t tb = 6 * (size_t)hsize;      // bytes of one table (keys + values), a multiple of 8
     AiTable locb{(int *)ai_lds, (short *)(ai_lds + 4 * (size_t)hsize), (unsigned)(hsize - 1)};
     AiTable locr{(int *)(ai_lds + tb), (short *)(ai_lds + tb + 4 * (size_t)hsize), (unsigned)(hsize - 1)};
-    if (v.has_A) { locb.build(v, v.ae0 + b, n, tid, AI_NT); locr.build(v, v.ae0 + r0, n, tid, AI_NT); }
+    if (v.has_A) { locb.build(v.ae2d_J + v.ae2d_I[v.ae0 + b], n, tid, AI_NT); locr.build(v.ae2d_J + v.ae2d_I[v.ae0 + r0], n, tid, AI_NT); }
     const AiRow x{b, v.ae0 + b, &locb}, y{r0, v.ae0 + r0, &locr};
     bool ok = true;
     for (int lr0 = blockIdx.y * (AI_NT / 64) + wv; lr0 < n; lr0 += (AI_NT / 64) * gridDim.y)
@@ -1665,30 +1516,27 @@ void ae_build(hipStream_t s, const DevRelations &rel, const DCsr *A, const DevEl
         if (scale) ae_scale(s, batch, Dout);
         return;
     }
-    constexpr bool no_fused = false;
     size_t lds = 0;
     int RW = 0;
     // rows ordered by global dof number for the banded factorisation of the few-eigenpairs path (the
     // fused kernel below, or the plain assembly followed by the two-kernel scaling)
-    constexpr bool use_perm = true;
     const bool split_scale = batch.count <= 2048 && batch.max_n >= 1024;      // (what ae_scale will pick)
-    if (use_perm && scale && eig_batch_takes_subspace(batch) && batch.max_n <= 16384 && ((A && !no_fused) || split_scale)) {
+    if (scale && eig_batch_takes_subspace(batch) && batch.max_n <= 16384 && (A || split_scale)) {
         const size_t rows_total = (size_t)batch.h_voff[batch.count];
         if (batch.perm.n < rows_total) { batch.perm.alloc(rows_total); batch.iperm.alloc(rows_total); }
-        constexpr int box_order = 1;
         hipLaunchKernelGGL(ae_perm_kernel, dim3(batch.count), dim3(256), 2 * sizeof(int) * (size_t)batch.max_n, s, ae0,
-                           batch.n.p, batch.voff.p, rel.ae2d_I.p, rel.ae2d_J.p, batch.perm.p, batch.iperm.p, box_order);
+                           batch.n.p, batch.voff.p, rel.ae2d_I.p, rel.ae2d_J.p, batch.perm.p, batch.iperm.p);
         batch.has_perm = true;
         batch.order_ran = true;
         if (batch.opt.ae_order) ae_level_order(s, rel, ae0, batch, 1, nullptr, batch.order_stats);
     }
-    if (A && !no_fused) {
+    if (A) {
         if (A->max_row < 0) A->max_row = csr_max_row(s, *A);
         RW = A->max_row;
         const size_t n = (size_t)batch.max_n;
         lds = 8 * (n * RW + 2 * n + (AB_NT / 64) * n) + 2 * n * RW + 4 * n + 64;
     }
-    if (!A || no_fused || lds > 160 * 1024 - 256 || batch.max_n > 32767) {
+    if (!A || lds > 160 * 1024 - 256 || batch.max_n > 32767) {
         if (!split_scale) batch.has_perm = false;       // (the one-kernel scaling works in agglomerate order)
         const bool band_asm = batch.opt.band_assembly != 0;
         // (also with the global matrix at hand -- level 0 of Q2 elasticity, whose agglomerates do not fit the fused
@@ -1760,15 +1608,11 @@ void ae_build(hipStream_t s, const DevRelations &rel, const DCsr *A, const DevEl
         bwp = batch.bw.p;
         batch.has_bw = true;
     }
-    constexpr bool band_write = true;
-    const int band_only = (bwp && band_write) ? 1 : 0;
-    const bool nde8 = el.nde == 8 && batch.count <= 65535;   // (grid.y of the rows kernel)
-    // precomputed sparse rows: 8-dof elements, or elements of at most 8 dofs and different sizes (ae_build_kernel's PRE branch
-    // reads the rows only: its NDE does not matter there)
-    const bool pre = nde8 || (rows_mixed_fit(el, batch) && batch.count <= 65535);
+    const int band_only = bwp ? 1 : 0;
+    const bool pre = rows_eligible(el, batch);      // precomputed sparse rows
     const double *rv = nullptr;
     const short *rc = nullptr;
-    if (pre) launch_rows8(s, rel, *A, el, ae0, batch, RW, rv, rc, rows);
+    if (pre) launch_ae_rows(s, rel, *A, el, ae0, batch, RW, rv, rc, rows);
     // classes of identical agglomerates: only their first members are built (the caller runs the eigensolvers on those);
     // not when D is wanted for every agglomerate (keep_debug)
     DBuf<int> only;
@@ -2283,14 +2127,13 @@ void coarse_elmats_sparse(hipStream_t s, const DevRelations &rel, int ae0, const
     profiler().begin(s);
     // the packed rows of T of one agglomerate in LDS: a pool of 6 doubles per row on average (+ keys, column starts, offsets
     // and dof maps: 24 bytes per row); an agglomerate that needs more is redone by the dense-T kernel
-    constexpr bool old_only = false;
     const int pool_cap = 6 * batch.max_n, u_cap = 3 * batch.max_n;
     const size_t lds = 8 * (size_t)(pool_cap + u_cap) + 28 * (size_t)batch.max_n + 16;
     if (batch.opt.debug & 2)
         std::fprintf(stderr, "coarse_elmats_sparse: %d agglomerates, max n %d, kmax %d, RW %d, LDS %zu\n", batch.count, batch.max_n, kmax, RW, lds);
     const int *only = nullptr;
     DBuf<int> flagged;
-    if (!old_only && kmax >= 1 && kmax < 256 && lds <= 64 * 1024) {
+    if (kmax >= 1 && kmax < 256 && lds <= 64 * 1024) {
         flagged.alloc((size_t)batch.count);
         flagged.zero(s);
         hipLaunchKernelGGL(coarse_elmat_rows_kernel, dim3(ncompute), dim3(ASM_NT), lds, s, ae0, RW, pool_cap, u_cap, batch.n.p,

@@ -1111,9 +1111,8 @@ static Table prepare_next_level(Hierarchy &H, int lev) {
         int RW = 0;
         const double *rv = nullptr;
         const short *rc = nullptr;
-        constexpr bool dense_only = false;
         const RowsSpan span = rows_span(rel, ae0, ae_lo, ae_hi);
-        if (lev == 0 && !dense_only && ae_sparse_rows(s, L.drel, L.A, L.elmat, ae0, batch, RW, rv, rc, &span)) {
+        if (lev == 0 && ae_sparse_rows(s, L.drel, L.A, L.elmat, ae0, batch, RW, rv, rc, &span)) {
             // fine level: straight from the sparse rows of the AE matrices
             int kmax = 0;
             for (int km : L.mis_k) kmax = std::max(kmax, km);

@@ -103,6 +103,132 @@ def test_uniform_input_through_mixed_entry_is_bitwise_the_uniform_path(case):
     h2.close()
 
 
+def _copied(prob, weights):
+    """The same problem with every element listed len(weights) times, copy i carrying weights[i] of its matrix (powers
+    of two that sum to 1: the copies of an entry add up to the entry): a dof lies in len(weights) times as many
+    elements, every agglomerate keeps its dofs."""
+    k = len(weights)
+    assert sum(weights) == 1.0 and all(np.frexp(w)[0] == 0.5 for w in weights)
+    e2d = np.ascontiguousarray(np.tile(prob.elem_to_dof, (k, 1)))
+    elmat = np.ascontiguousarray(np.concatenate([w * prob.elmat for w in weights]))
+    A, b = pr._eliminate(pr._assemble(prob.ND, e2d, elmat), prob.b, prob.ess)
+    return pr.Problem(**dict(prob.__dict__, A=A, b=b, elem_to_dof=e2d, elmat=elmat,
+                             partitions=[np.tile(prob.partitions[0], k)] + list(prob.partitions[1:])))
+
+
+def _copied_mixed(prob, weights):
+    """_copied for a mesh with elements of different sizes (flat elem_to_dof, elem_ptr, packed element matrices)."""
+    k = len(weights)
+    assert sum(weights) == 1.0 and all(np.frexp(w)[0] == 0.5 for w in weights)
+    nd = np.tile(np.diff(prob.elem_ptr).astype(np.int64), k)
+    eptr = np.concatenate([[0], np.cumsum(nd)])
+    e2d = np.ascontiguousarray(np.tile(prob.elem_to_dof, k))
+    elmat = np.ascontiguousarray(np.concatenate([w * prob.elmat for w in weights]))
+    moff = np.concatenate([[0], np.cumsum(nd * nd)])
+    eid = np.repeat(np.arange(nd.size), nd * nd)        # element of every packed matrix entry, ascending
+    loc = np.arange(elmat.size) - moff[eid]
+    rows, cols = e2d[eptr[eid] + loc // nd[eid]], e2d[eptr[eid] + loc % nd[eid]]
+    A0 = sp.coo_matrix((elmat, (rows, cols)), shape=(prob.ND, prob.ND)).tocsr()
+    A0.sort_indices()
+    A, b = pr._eliminate(A0, prob.b, prob.ess)
+    return pr.Problem(**dict(prob.__dict__, A=A, b=b, elem_to_dof=e2d, elem_ptr=eptr.astype(np.int32), elmat=elmat,
+                             partitions=[np.tile(prob.partitions[0], k)] + list(prob.partitions[1:])))
+
+
+def _max_valence(prob):
+    return int(np.bincount(prob.elem_to_dof.ravel(), minlength=prob.ND).max())
+
+
+def _profiled_hierarchy(capi, prob, params):
+    capi.profile(True)
+    try:
+        capi.profile_reset()
+        h = capi.Hierarchy.from_problem(prob, params)
+        names = [r["name"] for r in capi.profile_stats() if r["launches"] > 0]
+    finally:
+        capi.profile(False)
+    return h, names
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 1b. a dof in more elements than the per-dof element lists of the 8-dof sparse-row kernel hold (8): the agglomerate
+#     takes the walk through the dof -> element list instead
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("weights,valence", [((0.5, 0.5), 16), ((0.5, 0.25, 0.25), 24)])
+def test_dof_in_more_elements_than_the_row_lists_hold(weights, valence):
+    """Every hex listed two / three times: an interior vertex lies in 16 / 24 elements and the 8-dof kernel walks.  The
+    hierarchy is the oracle's on the same copied mesh, and the mixed entry gives it bit for bit -- through the SAME
+    kernel: elements of one size continue as the uniform entry (hierarchy_create), so this compares the entries, not
+    two kernels.  The walk of the kernel for elements of different sizes is pinned by the next test."""
+    capi = _capi()
+    prob = _copied(pr.poisson3d_problem((8, 8, 4), blk=(4, 4, 2), coef="skew"), weights)
+    assert prob.ND == 405 and _max_valence(prob) == valence
+    mk = lambda: capi.default_params(num_coarsenings=1, theta=0.003, nu_relax=3, keep_debug=True, coarse_rtol=1e-28)
+    h1 = capi.Hierarchy.from_problem(prob, mk())
+    h2 = capi.Hierarchy.from_problem(_as_mixed(prob), mk())
+    _assert_same_hierarchy(h1, h2, 1)
+    b = np.cos(np.arange(prob.ND) * 0.13) * (~prob.ess)
+    assert _same(h1.vcycle(b), h2.vcycle(b))
+    r1, r2 = h1.pcg(prob.b, rel_tol=1e-8), h2.pcg(prob.b, rel_tol=1e-8)
+    assert r1[1] == r2[1] and _same(r1[0], r2[0]) and _same(r1[3], r2[3])
+    H = o.ml_produce_data(prob.A, prob.elem_to_dof, prob.elmat, prob.bdr, prob.partitions[:1], theta=0.003, nu_relax=3)
+    _compare_level(h1, H, 0, 0.003)
+    h1.close()
+    h2.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 1b'. the same for elements of different sizes: hexes and wedges, every element listed twice -- a vertex of the split
+#      columns lies in up to 24 elements, more than the 16 the lists of that kernel hold
+# ---------------------------------------------------------------------------------------------------------------------
+def test_dof_in_more_elements_than_the_mixed_row_lists_hold(monkeypatch):
+    capi = _capi()
+    prob = _copied_mixed(pr.poisson3d_mixed_problem((8, 8, 4), (4, 4, 2), wedges="half", coef="skew", seed=7), (0.5, 0.5))
+    assert set(np.diff(prob.elem_ptr)) == {6, 8}        # (sizes differ: the call stays with the mixed kernels)
+    assert prob.ND == 405 and _max_valence(prob) > 16
+    params = capi.default_params(num_coarsenings=1, theta=0.003, nu_relax=3, keep_debug=True, coarse_rtol=1e-28)
+    h, names = _profiled_hierarchy(capi, prob, params)
+    assert "ae_rows" in names, names
+    H = _mixed_oracle(monkeypatch, prob, 1, theta=0.003, nu_relax=3)
+    _compare_level(h, H, 0, 0.003)
+    b = np.cos(np.arange(prob.ND) * 0.13) * (~prob.ess)
+    x_gpu, x_ref = h.vcycle(b), o.vcycle(H, b)
+    assert np.linalg.norm(x_gpu - x_ref) <= VCYCLE_TOL * np.linalg.norm(x_ref)
+    x, it, conv, hist = h.pcg(prob.b, rel_tol=1e-8)
+    xr, itr, convr, histr = o.solve(H, prob.b, rel_tol=1e-8)
+    assert conv and convr and it == itr
+    assert np.allclose(hist, histr, rtol=1e-7, atol=1e-10 * histr[0])
+    h.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 1c. agglomerates whose tables do not fit the LDS of the sparse-row kernel: 4 agglomerates of 11 x 11 x 10 = 1 210
+#     dofs (93 570 bytes against 64 KB).  The eigenproblem pass takes the generic assembly; the pass that builds the
+#     coarse element matrices takes the sparse rows from the kernel with one thread per (row, entry).  That pass runs
+#     only where a further level needs element matrices: a second coarsening (the four agglomerates into one).
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("weights", [(1.0,), (0.5, 0.5)])
+def test_agglomerates_too_large_for_the_lds_rows_kernel(weights):
+    """(0.5, 0.5): every element twice, an interior vertex in 16 elements -- the kernel's loop over the elements past
+    the eighth."""
+    capi = _capi()
+    prob = pr.poisson3d_problem((20, 20, 9), blk=(10, 10, 9), coarse_blk=[(2, 2, 1)], coef="skew")
+    if len(weights) > 1:
+        prob = _copied(prob, weights)
+    assert _max_valence(prob) == 8 * len(weights)
+    assert np.bincount(prob.partitions[0]).size == 4
+    params = capi.default_params(num_coarsenings=2, theta=0.003, nu_relax=3, keep_debug=True, coarse_rtol=1e-28)
+    h, names = _profiled_hierarchy(capi, prob, params)
+    assert "ae_rows" in names and "ae_assemble" in names and "coarse_elmats" in names, names
+    H = o.ml_produce_data(prob.A, prob.elem_to_dof, prob.elmat, prob.bdr, prob.partitions[:2], theta=0.003, nu_relax=3)
+    _compare_level(h, H, 0, 0.003)
+    _compare_level(h, H, 1, 0.003)
+    x, it, conv, hist = h.pcg(prob.b, rel_tol=1e-8)
+    xr, itr, convr, histr = o.solve(H, prob.b, rel_tol=1e-8)
+    assert conv and convr and it == itr, (it, itr)
+    h.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 2. hex / wedge meshes against the oracle
 # ---------------------------------------------------------------------------------------------------------------------
