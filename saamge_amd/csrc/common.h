@@ -218,12 +218,17 @@ inline hvec<T> fetch_host(const T *src, size_t n, hipStream_t s) {
     }
     return v;
 }
+// n values from the device in one transfer (synchronises the stream)
+template <class T>
+inline void read_back(T *dst, const T *src, size_t n, hipStream_t s) {
+    SA_HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, s));
+    SA_HIP_CHECK(hipStreamSynchronize(s));
+}
 // one value from the device (synchronises the stream)
 template <class T>
 inline T read_one(const T *p, hipStream_t s) {
     T v;
-    SA_HIP_CHECK(hipMemcpyAsync(&v, p, sizeof(T), hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
+    read_back(&v, p, 1, s);
     return v;
 }
 

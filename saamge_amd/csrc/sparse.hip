@@ -10,6 +10,48 @@ namespace saamge_amd {
 
 enum { MODE_PLAIN = 0, MODE_RESIDUAL = 1, MODE_ADD = 2, MODE_SMOOTH = 3 };
 
+// ---- what every kernel of the family shares --------------------------------------------------------------------------
+// The vectors of one application as a kernel indexes them: x by column, the others by the row a kernel computes (xrow: x at
+// those rows).  row_terms takes them as one bundle, filled from the kernel's own __restrict__ parameters.
+struct SpmvVecs {
+    const double *x;
+    double *y;
+    const double *b, *dinv;
+    double scale;
+    const double *xrow;
+};
+// The row's terms of the four modes: y = sum / b - sum / y + sum / x + scale * dinv_neg * (sum - b).  row_terms loads what the
+// mode needs for a live row, spmv_epilogue stores.  The kernels behind the fine smoother -- sell_slice, sell_staged_kernel,
+// sell_staged2 -- load their terms themselves, each where its own streams want them (sell_staged2 also in its own way), and
+// share the epilogue: through row_terms, as through argument bundles, a shared staging routine or a shared product loop, the
+// instruction stream of sell_staged2_kernel<3> is no longer the measured one (profiles/spmv_refactor_resource_usage.txt).
+struct RowTerms { double b, d, x; };
+template <int MODE>
+__device__ __forceinline__ RowTerms row_terms(const SpmvVecs &v, long row, bool live = true) {
+    RowTerms t{0.0, 0.0, 0.0};
+    if (MODE == MODE_RESIDUAL && live) t.b = v.b[row];
+    if (MODE == MODE_ADD && live) t.x = v.y[row];
+    if (MODE == MODE_SMOOTH && live) { t.b = v.b[row]; t.d = v.dinv[row]; t.x = v.xrow[row]; }
+    return t;
+}
+template <int MODE>
+__device__ __forceinline__ void spmv_epilogue(double sum, const RowTerms &t, double scale, double *y, long row) {
+    if (MODE == MODE_PLAIN) {
+        y[row] = sum;
+    } else if (MODE == MODE_RESIDUAL) {
+        y[row] = t.b - sum;
+    } else if (MODE == MODE_ADD) {
+        y[row] = t.x + sum;
+    } else {
+        y[row] = t.x + scale * (t.d * (sum - t.b));
+    }
+}
+// The XCD deal: consecutive workgroups go to the XCDs round-robin (block -> XCD = block % 8, position = block / 8), so XCD k
+// walks the k-th contiguous run of per_xcd tiles (tile_deal on the host; 0: no deal).
+__device__ __forceinline__ int xcd_block(int per_xcd) {
+    return per_xcd > 0 ? (int)(blockIdx.x & 7u) * per_xcd + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+}
+
 template <int L, int MODE>
 __global__ __launch_bounds__(256) void spmv_kernel(int nrows, const roff_t *__restrict__ rowptr,
                                                    const int *__restrict__ col,
@@ -32,17 +74,8 @@ __global__ __launch_bounds__(256) void spmv_kernel(int nrows, const roff_t *__re
     }
 #pragma unroll
     for (int o = L / 2; o > 0; o >>= 1) sum += __shfl_down(sum, o, L);
-    if (lane == 0) {
-        if (MODE == MODE_PLAIN) {
-            y[row] = sum;
-        } else if (MODE == MODE_RESIDUAL) {
-            y[row] = b[row] - sum;
-        } else if (MODE == MODE_ADD) {
-            y[row] += sum;
-        } else {  // x_out = x_in + scale * dinv_neg * (A x - b)
-            y[row] = xrow[row] + scale * (dinv[row] * (sum - b[row]));
-        }
-    }
+    const SpmvVecs v{x, y, b, dinv, scale, xrow};
+    if (lane == 0) spmv_epilogue<MODE>(sum, row_terms<MODE>(v, row), scale, y, row);
 }
 
 // SELL-64: one lane per row, the wavefront walks its slice column by column; val/col loads are
@@ -55,6 +88,18 @@ __global__ __launch_bounds__(256) void spmv_kernel(int nrows, const roff_t *__re
 // four, at the tile's first slice: sell_code_kernel's merge)
 __device__ __forceinline__ int pair_count(int nt) { return nt >= 512 ? nt - 512 : nt - 256; }
 __device__ __forceinline__ size_t pair_table_at(int gslice, int nt) { return (size_t)(nt >= 512 ? (gslice & ~3) : gslice) * 64; }
+// A lane's first code word: the codes of four consecutive entries of a row share one word, the words of a slice that starts at
+// entry `beg` sit at codes[beg / 4 + 64 gslice + 64 (k / 4) + lane] (Sell::code, and Sell::Dict::gcode with 8-byte words).
+template <class W>
+__device__ __forceinline__ W *code_words(W *codes, roff_t beg, int gslice, int lane) {
+    return codes + ((size_t)(beg >> 2) + (size_t)gslice * 64 + lane);
+}
+// All code words of a row of at most 32 entries, requested before the first one is used (a loop would wait for one word per
+// trip: load -> look-up -> gather is a dependent chain); zero past the row's width.
+__device__ __forceinline__ void load_code_words(const unsigned *wp, int w, unsigned (&cws)[8]) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) cws[q] = (4 * q < w) ? __builtin_nontemporal_load(wp + 64 * q) : 0u;
+}
 
 // general path: any mix of slice formats, any width.  Returns the row's sum; `slice` / `gslice` are wave-uniform.
 __device__ __forceinline__ double sell_row_general(int lane, int grow, int gslice, roff_t beg, roff_t end, int nt,
@@ -73,7 +118,7 @@ __device__ __forceinline__ double sell_row_general(int lane, int grow, int gslic
         const int np = pair_count(nt);
         const int mytab = (lane < np) ? tab[pair_table_at(gslice, nt) + lane] : 0;
         const double myval = (lane < np) ? vtab[pair_table_at(gslice, nt) + lane] : 0.0;
-        const unsigned *wp = codes + ((size_t)(beg >> 2) + (size_t)gslice * 64 + lane);
+        const unsigned *wp = code_words(codes, beg, gslice, lane);
         auto quad = [&](unsigned cw) {
             const int i0 = (int)(cw & 255u), i1 = (int)((cw >> 8) & 255u), i2 = (int)((cw >> 16) & 255u), i3 = (int)(cw >> 24);
             const int c0 = grow + __shfl(mytab, i0), c1 = grow + __shfl(mytab, i1);
@@ -88,8 +133,7 @@ __device__ __forceinline__ double sell_row_general(int lane, int grow, int gslic
             // every code word of the row is requested before the first one is used (the loop would wait for one
             // word per trip: load -> permute -> gather is a dependent chain)
             unsigned cws[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) cws[q] = (4 * q < w) ? __builtin_nontemporal_load(wp + 64 * q) : 0u;
+            load_code_words(wp, w, cws);
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 if (4 * q + 4 <= w) quad(cws[q]);
@@ -113,7 +157,7 @@ __device__ __forceinline__ double sell_row_general(int lane, int grow, int gslic
         }
     } else if (nt >= 0) {
         const int mytab = tab[(size_t)gslice * 64 + lane];
-        const unsigned *wp = codes + ((size_t)(beg >> 2) + (size_t)gslice * 64 + lane);
+        const unsigned *wp = code_words(codes, beg, gslice, lane);
         for (; k + 4 <= w; k += 4) {
             const unsigned cw = __builtin_nontemporal_load(wp + 16 * k);
             const double v0 = __builtin_nontemporal_load(vp + 64 * k), v1 = __builtin_nontemporal_load(vp + 64 * (k + 1));
@@ -159,8 +203,8 @@ struct alignas(16) PairEntry {
 // for the gather of x: 27 + 17 others per slice = ~620 of the ~890 cycles a CU spends per slice, at 2.9 TB/s of the
 // bytes the format needs (a pure stream of the same bytes: 5.1 TB/s).  Before that the cross-lane permutes of the
 // table look-ups (96 LDS instructions x 8 cycles per slice) held the same place.  Hence:
-//   * sell_staged_kernel: where the offsets of a 256-row tile cluster into few runs, the workgroup loads the x-segments
-//     those runs touch into LDS with 16-byte coalesced loads (27 gathers per wavefront -> ~7 loads) and the products
+//   * sell_staged_kernel, sell_staged2_kernel: where the offsets of a 256-row tile cluster into few runs, the workgroup
+//     loads the x-segments those runs touch into LDS with 16-byte coalesced loads (27 gathers per wavefront -> ~7 loads) and the products
 //     read LDS; the slice's (offset, value) table sits in LDS too, one 16-byte entry per lane, read with plain LDS
 //     loads (a broadcast for the lanes that share an entry) instead of three permutes per entry.
 //   * sell_slice: the same per slice with gathers from global memory (tiles that cannot be staged), up to 16 in
@@ -170,8 +214,9 @@ struct alignas(16) PairEntry {
 //     instead of all eight (PMC: 2.0 -> 1.14 GB per launch, the format's own bytes being 1.12 GB; speed only, any
 //     placement gives the same result).
 //   * The slice is wave-uniform (readfirstlane): its offsets, width and format come through the scalar cache.
-// Same arithmetic and the same order of additions on every path (two accumulators over whole groups of four entries,
-// the tail into the first).
+// Same arithmetic and THE order of additions of the whole family on every path, so that all formats give the same bits: two
+// accumulators over whole groups of four entries -- even entries into the first, odd ones into the second -- the tail of up to
+// three entries into the first, then their sum.
 template <int MODE>
 __device__ __forceinline__ void sell_slice(PairEntry *lt, int nrows, int row0, long row, int slice, int fast_ok,
                                            const roff_t *__restrict__ sptr, const int *__restrict__ col,
@@ -191,10 +236,9 @@ __device__ __forceinline__ void sell_slice(PairEntry *lt, int nrows, int row0, l
     double e_b = 0.0, e_d = 0.0, e_x = 0.0, sum;
     if (fast_ok && nt >= 256 && w <= 32) {
         const int np = pair_count(nt);
-        const unsigned *wp = codes + ((size_t)(beg >> 2) + (size_t)gslice * 64 + lane);
+        const unsigned *wp = code_words(codes, beg, gslice, lane);
         unsigned cws[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) cws[q] = (4 * q < w) ? __builtin_nontemporal_load(wp + 64 * q) : 0u;
+        load_code_words(wp, w, cws);
         const int mytab = (lane < np) ? tab[pair_table_at(gslice, nt) + lane] : 0;
         const double myval = (lane < np) ? vtab[pair_table_at(gslice, nt) + lane] : 0.0;
         if (MODE == MODE_RESIDUAL && live) e_b = b[row];
@@ -236,15 +280,7 @@ __device__ __forceinline__ void sell_slice(PairEntry *lt, int nrows, int row0, l
         if (MODE == MODE_SMOOTH && live) { e_b = b[row]; e_d = dinv[row]; e_x = xrow[row]; }
     }
     if (!live) return;
-    if (MODE == MODE_PLAIN) {
-        y[row] = sum;
-    } else if (MODE == MODE_RESIDUAL) {
-        y[row] = e_b - sum;
-    } else if (MODE == MODE_ADD) {
-        y[row] = e_x + sum;
-    } else {
-        y[row] = e_x + scale * (e_d * (sum - e_b));
-    }
+    spmv_epilogue<MODE>(sum, RowTerms{e_b, e_d, e_x}, scale, y, row);
 }
 
 template <int MODE>
@@ -262,7 +298,7 @@ __global__ __launch_bounds__(256) void sell_spmv_kernel(int nrows, int row0, int
                                                         const double *__restrict__ xrow,
                                                         const double *__restrict__ vtab) {
     __shared__ PairEntry ltab[4][64];
-    const int blk = per_xcd > 0 ? (int)(blockIdx.x & 7u) * per_xcd + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    const int blk = xcd_block(per_xcd);
     if (blk >= nblocks) return;
     const long row = (long)blk * 256 + threadIdx.x;
     const int slice = __builtin_amdgcn_readfirstlane((int)(row >> 6));
@@ -304,16 +340,11 @@ __global__ __launch_bounds__(256) void sell_staged_kernel(int nrows, int row0, i
     const int nt = ntab[gslice];
     const int np = pair_count(nt);
     const int w = (int)((end - beg) >> 6);
-    const unsigned *wp = codes + ((size_t)(beg >> 2) + (size_t)gslice * 64 + lane);
     unsigned cws[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) cws[q] = (4 * q < w) ? __builtin_nontemporal_load(wp + 64 * q) : 0u;
+    load_code_words(code_words(codes, beg, gslice, lane), w, cws);
     const int mytab = (lane < np) ? tab[pair_table_at(gslice, nt) + lane] : 0;
     const double myval = (lane < np) ? vtab[pair_table_at(gslice, nt) + lane] : 0.0;
-    double e_b = 0.0, e_d = 0.0, e_x = 0.0;
-    if (MODE == MODE_RESIDUAL) e_b = b[row];
-    if (MODE == MODE_ADD) e_x = y[row];
-    if (MODE == MODE_SMOOTH) { e_b = b[row]; e_d = dinv[row]; e_x = xrow[row]; }
+    const RowTerms t = row_terms<MODE>(SpmvVecs{x, y, b, dinv, scale, xrow}, row);
     // the tile's segments: x[R0 + lo .. R0 + lo + len) -> lds[pre ..), 16 bytes per lane (starts and lengths are even).
     // Four segments at a time: the loads of their first two passes (512 doubles per pass of the workgroup), then the
     // LDS stores -- one memory latency per batch, not one per segment; the thread assignment rotates by one wavefront
@@ -395,15 +426,7 @@ __global__ __launch_bounds__(256) void sell_staged_kernel(int nrows, int row0, i
         }
     }
     const double sum = s0 + s1;
-    if (MODE == MODE_PLAIN) {
-        y[row] = sum;
-    } else if (MODE == MODE_RESIDUAL) {
-        y[row] = e_b - sum;
-    } else if (MODE == MODE_ADD) {
-        y[row] = e_x + sum;
-    } else {
-        y[row] = e_x + scale * (e_d * (sum - e_b));
-    }
+    spmv_epilogue<MODE>(sum, t, scale, y, row);
 }
 
 // ---- the staged kernel with descriptor-free streams (round 4) -------------------------------------------------------
@@ -429,7 +452,7 @@ __global__ __launch_bounds__(256) void sell_regular_codes_kernel(int ntiles, int
     const int slice = 4 * t + wv;
     const roff_t beg = sptr[slice];
     const int w = (int)((sptr[slice + 1] - beg) >> 6);
-    const unsigned *wp = codes + ((size_t)(beg >> 2) + (size_t)slice * 64 + lane);
+    const unsigned *wp = code_words(codes, beg, slice, lane);
     const int slot = pinfo ? -pinfo[t] : t;
     if (slot >= 0)
         for (int q = 0; q < wq; ++q) codesR[((size_t)slot * wq + q) * 256 + threadIdx.x] = (4 * q < w) ? wp[64 * q] : 0u;
@@ -473,7 +496,7 @@ __global__ __launch_bounds__(256) void sell_row_patterns_kernel(int ntiles, int 
         const int slice = 4 * t + wv;
         const roff_t beg = sptr[slice];
         const int w = (int)((sptr[slice + 1] - beg) >> 6);
-        const unsigned *wp = codes + ((size_t)(beg >> 2) + (size_t)slice * 64 + lane);
+        const unsigned *wp = code_words(codes, beg, slice, lane);
         unsigned my[8];
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
@@ -569,7 +592,7 @@ __device__ __forceinline__ void sell_staged2(double *lds, const SellLeftover &le
     }
     PairEntry *lt = (PairEntry *)(lds + stage_cap);
     unsigned *pt = (unsigned *)(lt + 64);      // (row patterns: the tile's SELL_PMAX x 8 pattern words)
-    const int blk = per_xcd > 0 ? (int)(blockIdx.x & 7u) * per_xcd + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    const int blk = xcd_block(per_xcd);
     if (blk >= nblocks || (long)blk * 256 + 256 > nrows) return;
     const long row = (long)blk * 256 + threadIdx.x;
     const int gtile = (row0 >> 8) + blk;
@@ -701,15 +724,7 @@ __device__ __forceinline__ void sell_staged2(double *lds, const SellLeftover &le
         }
     }
     const double sum = s0 + s1;
-    if (MODE == MODE_PLAIN) {
-        y[row] = sum;
-    } else if (MODE == MODE_RESIDUAL) {
-        y[row] = e_b - sum;
-    } else if (MODE == MODE_ADD) {
-        y[row] = e_x + sum;
-    } else {
-        y[row] = e_x + scale * (e_d * (sum - e_b));
-    }
+    spmv_epilogue<MODE>(sum, RowTerms{e_b, e_d, e_x}, scale, y, row);
 }
 #define SA_STAGED2_PARAMS                                                                                                         \
     SellLeftover left, int nrows, int row0, int nblocks, int per_xcd, int stage_cap, int ncols, int wq,                           \
@@ -941,7 +956,7 @@ __global__ __launch_bounds__(256) void sell_gdict_kernel(int nslices, const roff
     const roff_t beg = sptr[slice];
     const int w = (int)((sptr[slice + 1] - beg) >> 6);
     const int row = slice * 64 + lane;
-    unsigned long long *wp = gcode + ((size_t)(beg >> 2) + (size_t)slice * 64 + lane);
+    unsigned long long *wp = code_words(gcode, beg, slice, lane);
     unsigned long long word = 0;      // four codes of the row per 8-byte word
     for (int k = 0; k < w; ++k) {
         const int off = scol[beg + 64 * k + lane] - row;
@@ -991,8 +1006,7 @@ __global__ __launch_bounds__(256) void sell_bs3_kernel(int nrows, int nwaves, co
 // memory the table look-ups were vector-memory gathers like those of x (scattered 16-byte entries: ~50 cycles each on
 // the CU's address path) and the kernel was SLOWER than the plain slices it replaces although it moves a sixth of their
 // bytes (3.3 against 3.2 ms per application of the 64^3 Q2 operator); from LDS they cost an LDS read.
-// Same order of additions as the plain path (whole groups of four alternate between the two accumulators, the tail
-// goes to the first): bit-identical results.
+// The order of additions is the family's (see sell_slice), here eight entries per trip: bit-identical results.
 template <int MODE>
 __global__ __launch_bounds__(1024) void sell_gpair_kernel(int nrows, int row0, int nslices, int per_xcd, int wg_per_xcd, int ng,
                                                           const roff_t *__restrict__ sptr,
@@ -1016,11 +1030,8 @@ __global__ __launch_bounds__(1024) void sell_gpair_kernel(int nrows, int row0, i
         const long row = (long)slice * 64 + lane;
         const bool live = row < nrows;
         const int grow = row0 + (int)row;
-        double e_b = 0.0, e_d = 0.0, e_x = 0.0;
-        if (MODE == MODE_RESIDUAL && live) e_b = b[row];
-        if (MODE == MODE_ADD && live) e_x = y[row];
-        if (MODE == MODE_SMOOTH && live) { e_b = b[row]; e_d = dinv[row]; e_x = xrow[row]; }
-        const unsigned long long *wp = gcode + ((size_t)(beg >> 2) + (size_t)gslice * 64 + lane);
+        const RowTerms t = row_terms<MODE>(SpmvVecs{x, y, b, dinv, scale, xrow}, row, live);
+        const unsigned long long *wp = code_words(gcode, beg, gslice, lane);
         const unsigned grow8 = (unsigned)grow << 3;
         double s0 = 0.0, s1 = 0.0;
         int k = 0;
@@ -1057,18 +1068,7 @@ __global__ __launch_bounds__(1024) void sell_gpair_kernel(int nrows, int row0, i
                 s0 = fma(e.val, gp_x(x, grow8, e.off), s0);
             }
         }
-        const double sum = s0 + s1;
-        if (live) {
-            if (MODE == MODE_PLAIN) {
-                y[row] = sum;
-            } else if (MODE == MODE_RESIDUAL) {
-                y[row] = e_b - sum;
-            } else if (MODE == MODE_ADD) {
-                y[row] = e_x + sum;
-            } else {
-                y[row] = e_x + scale * (e_d * (sum - e_b));
-            }
-        }
+        if (live) spmv_epilogue<MODE>(s0 + s1, t, scale, y, row);
     }
 }
 
@@ -1105,19 +1105,6 @@ __device__ __forceinline__ unsigned bs3_own_code(const unsigned long long (&cw)[
     for (int q = 0; q < 3; ++q) c[q] = (unsigned)((cw[(3 * t + q) >> 2] >> (16 * ((3 * t + q) & 3))) & 0xffffull);
     return a == 0 ? c[0] : (a == 1 ? c[1] : c[2]);
 }
-template <int MODE>
-__device__ __forceinline__ void spmv_epilogue(double sum, double *__restrict__ y, const double *__restrict__ b,
-                                              const double *__restrict__ dinv, double scale, const double *__restrict__ xrow, long row) {
-    if (MODE == MODE_PLAIN) {
-        y[row] = sum;
-    } else if (MODE == MODE_RESIDUAL) {
-        y[row] = b[row] - sum;
-    } else if (MODE == MODE_ADD) {
-        y[row] = y[row] + sum;
-    } else {
-        y[row] = xrow[row] + scale * (dinv[row] * (sum - b[row]));
-    }
-}
 // Lean enough for TWO workgroups per CU (32 wavefronts): the table split into values (8 B) and byte offsets (4 B) -- 12 B
 // per pair, 66 KB for 5 540 pairs -- and 63 VGPRs.  A version with one 16-byte table (one workgroup per CU) and a software
 // pipeline over two register sets (code words of group g + 2 and the look-ups + gathers of group g + 1 issued before the
@@ -1146,7 +1133,7 @@ __global__ __launch_bounds__(1024, 2) void sell_gpair3_kernel(int nrows_all, int
         const int slice = row >> 6;
         const roff_t beg = sptr[slice];
         const int w = (int)((sptr[slice + 1] - beg) >> 6), w4 = w & ~3;
-        const unsigned long long *wp = gcode + ((size_t)(beg >> 2) + (size_t)slice * 64 + (row & 63));
+        const unsigned long long *wp = code_words(gcode, beg, slice, row & 63);
         const unsigned short *cp = (const unsigned short *)wp;
         const unsigned row8 = (unsigned)row << 3;
         const int wa = __builtin_amdgcn_readfirstlane(w), wb = __builtin_amdgcn_readlane(w, 62);
@@ -1193,7 +1180,8 @@ __global__ __launch_bounds__(1024, 2) void sell_gpair3_kernel(int nrows_all, int
                 else s0 = fma(v[c], xs[c], s0);
             }
         }
-        if (live) spmv_epilogue<MODE>(s0 + s1, y, b, dinv, scale, x, row);
+        // (whole-operator arrays: the smoother's x-row is x itself.  The row's terms behind the products: 63 VGPRs)
+        if (live) spmv_epilogue<MODE>(s0 + s1, row_terms<MODE>(SpmvVecs{x, y, b, dinv, scale, x}, row), scale, y, row);
     }
 }
 // The irregular rows of a node-block operator, one lane per row (a few rows per thousand: strided reads do not matter).
@@ -1212,14 +1200,14 @@ __global__ __launch_bounds__(256) void sell_gpair3_fix_kernel(int nirr, const in
     const int slice = row >> 6;
     const roff_t beg = sptr[slice];
     const int w = (int)((sptr[slice + 1] - beg) >> 6), w4 = w & ~3;
-    const unsigned short *cp = (const unsigned short *)(gcode + ((size_t)(beg >> 2) + (size_t)slice * 64 + (row & 63)));
+    const unsigned short *cp = (const unsigned short *)code_words(gcode, beg, slice, row & 63);
     double s0 = 0.0, s1 = 0.0;
     for (int k = 0; k < w; ++k) {
         const GPair e = gtab[cp[64 * (size_t)(k - (k & 3)) + (k & 3)]];
         if (k < w4 && (k & 1)) s1 = fma(e.val, gp_x(x, (unsigned)row << 3, e.off), s1);
         else s0 = fma(e.val, gp_x(x, (unsigned)row << 3, e.off), s0);
     }
-    spmv_epilogue<MODE>(s0 + s1, y, b, dinv, scale, x, row);
+    spmv_epilogue<MODE>(s0 + s1, row_terms<MODE>(SpmvVecs{x, y, b, dinv, scale, x}, row), scale, y, row);
 }
 
 // Slice census of a SELL copy: cls[0..2] = pair-coded / offset-coded / plain slices, cls[3..5] = their stored entries
@@ -1353,7 +1341,7 @@ __global__ __launch_bounds__(256) void sell_code_kernel(int nslices, const roff_
     const roff_t beg = have ? sptr[slice] : 0;
     const int w = have ? (int)((sptr[slice + 1] - beg) >> 6) : 0;
     const int row = slice * 64 + lane;
-    unsigned *wp = codes + ((size_t)(beg >> 2) + (size_t)slice * 64 + lane);
+    unsigned *wp = code_words(codes, beg, slice, lane);
     int my_np = -1;
     for (int pass = with_values ? 0 : 1; pass < 2 && have; ++pass) {
         const bool pairs = pass == 0;
@@ -1485,15 +1473,12 @@ void import_rowptr(DBuf<roff_t> &dst, const void *src, int bits, size_t n, hipSt
 
 void export_rowptr32(int *dst_host, const DBuf<roff_t> &src, size_t n, hipStream_t s) {
     if (!n) return;
-    roff_t last = 0;
-    SA_HIP_CHECK(hipMemcpyAsync(&last, src.p + (n - 1), sizeof(roff_t), hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
+    const roff_t last = read_one(src.p + (n - 1), s);
     SA_REQUIRE(last < ((roff_t)1 << 31), "operator has more than 2^31 entries: use the 64-bit getter");
     DBuf<int> narrow(n);
     hipLaunchKernelGGL(narrow_offsets_kernel, dim3(div_up((long)n, 256)), dim3(256), 0, s, (long)n, src.p, narrow.p);
     SA_HIP_CHECK(hipGetLastError());
-    SA_HIP_CHECK(hipMemcpyAsync(dst_host, narrow.p, sizeof(int) * n, hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
+    read_back(dst_host, narrow.p, n, s);
 }
 
 // ---- build_sell, step by step.  A.sell starts out as Sell(): every step only fills ---------------------------------
@@ -1506,8 +1491,7 @@ static void fill_slices(hipStream_t s, DCsr &A) {
     hipLaunchKernelGGL(sell_width_kernel, dim3(grid), dim3(256), 0, s, A.nrows, A.rowptr.p, w64.p);
     S.ptr.alloc((size_t)S.nslices + 1);
     exclusive_scan_off(s, S.nslices, w64.p, S.ptr.p);
-    SA_HIP_CHECK(hipMemcpyAsync(&S.size, S.ptr.p + S.nslices, sizeof(roff_t), hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
+    S.size = read_one(S.ptr.p + S.nslices, s);
     S.col.alloc((size_t)S.size + 64);
     S.val.alloc((size_t)S.size + 64);
     hipLaunchKernelGGL(sell_fill_kernel, dim3(S.nslices), dim3(64), 0, s, A.nrows, A.rowptr.p, A.col.p, A.val.p, S.ptr.p, S.col.p, S.val.p);
@@ -1533,12 +1517,11 @@ static void code_slices(hipStream_t s, DCsr &A, const Options &opt) {
 static std::array<unsigned long long, 9> census(hipStream_t s, DCsr &A) {
     Sell &S = A.sell;
     DBuf<unsigned long long> cls(9);
-    SA_HIP_CHECK(hipMemsetAsync(cls.p, 0, 9 * sizeof(unsigned long long), s));
+    cls.zero(s);
     hipLaunchKernelGGL(sell_census_kernel, dim3(div_up(S.nslices, 256)), dim3(256), 0, s, S.nslices, S.ptr.p, S.ntab.p, cls.p);
     SA_HIP_CHECK(hipGetLastError());
     std::array<unsigned long long, 9> h;
-    SA_HIP_CHECK(hipMemcpyAsync(h.data(), cls.p, sizeof(h), hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
+    read_back(h.data(), cls.p, h.size(), s);
     for (int c = 0; c < 3; ++c) { S.class_slices[c] = (int64_t)h[c]; S.class_entries[c] = (int64_t)h[3 + c]; }
     // codes 4 B per word, tables 4 (+8) B per lane of a coded slice, values / columns of the formats that stream them,
     // 8 B slice offset + 4 B table size per slice
@@ -1554,17 +1537,16 @@ static void try_dictionary(hipStream_t s, DCsr &A, const Options &opt, const std
     Sell::Dict D;
     DBuf<int> st((size_t)GD_CAP), ctr(2);
     DBuf<unsigned long long> rec(2 * (size_t)GD_CAP);
-    SA_HIP_CHECK(hipMemsetAsync(st.p, 0, sizeof(int) * (size_t)GD_CAP, s));
-    SA_HIP_CHECK(hipMemsetAsync(rec.p, 0, 16 * (size_t)GD_CAP, s));
-    SA_HIP_CHECK(hipMemsetAsync(ctr.p, 0, 2 * sizeof(int), s));
+    st.zero(s);
+    rec.zero(s);
+    ctr.zero(s);
     D.gcode.alloc((size_t)S.size / 4 + (size_t)S.nslices * 64 + 64);
     D.gtab.alloc(GP_MAX);
     hipLaunchKernelGGL(sell_gdict_kernel, dim3(div_up(S.nslices, 4)), dim3(256), 0, s, S.nslices, S.ptr.p, S.col.p,
                        S.val.p, st.p, rec.p, ctr.p, (GPair *)D.gtab.p, D.gcode.p);
     SA_HIP_CHECK(hipGetLastError());
-    int hc[2];
-    SA_HIP_CHECK(hipMemcpyAsync(hc, ctr.p, sizeof(hc), hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
+    int hc[2];      // (pairs, abandoned: one transfer)
+    read_back(hc, ctr.p, 2, s);
     if (!hc[1] && hc[0] <= GP_MAX) {      // (the table has to fit LDS: see sell_gpair_kernel; otherwise D is dropped)
         D.on = true; D.ng = hc[0];
         // codes 2 B per stored entry (rounded up to four per row), the table, 8 B per slice
@@ -1578,8 +1560,7 @@ static void try_dictionary(hipStream_t s, DCsr &A, const Options &opt, const std
             hipLaunchKernelGGL(sell_bs3_kernel, dim3(div_up(nwaves, 4)), dim3(256), 0, s, A.nrows, nwaves, A.rowptr.p, A.col.p,
                                D.irr.p, cap, ctr.p);
             SA_HIP_CHECK(hipGetLastError());
-            SA_HIP_CHECK(hipMemcpyAsync(&D.nirr, ctr.p, sizeof(int), hipMemcpyDeviceToHost, s));
-            SA_HIP_CHECK(hipStreamSynchronize(s));
+            D.nirr = read_one(ctr.p, s);
             D.bs3 = D.nirr <= cap;
             if (!D.bs3) D.irr.release();
         }
@@ -1600,13 +1581,12 @@ static int plan_staging(hipStream_t s, DCsr &A, const Options &opt, const std::a
     G.tile_seg.alloc((size_t)ntiles * SELL_SEG_MAX);
     G.unstaged.alloc((size_t)ntiles);
     DBuf<int> mx(4);
-    SA_HIP_CHECK(hipMemsetAsync(mx.p, 0, 4 * sizeof(int), s));
+    mx.zero(s);
     hipLaunchKernelGGL(sell_stage_kernel, dim3(ntiles), dim3(64), 0, s, ntiles, S.nslices, A.nrows, S.ptr.p, S.ntab.p,
                        S.tab.p, G.tile_nseg.p, G.tile_seg.p, mx.p, G.unstaged.p);
     SA_HIP_CHECK(hipGetLastError());
-    int hm[4];
-    SA_HIP_CHECK(hipMemcpyAsync(hm, mx.p, sizeof(hm), hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
+    int hm[4];      // (largest tile, staged tiles, tiles left out, staged tiles with tables of their own)
+    read_back(hm, mx.p, 4, s);
     const int staged_tiles = hm[1];
     G.nunstaged = hm[2];
     G.cap = G.nunstaged * 4 > ntiles ? 0 : hm[0];      // (0: too few tiles staged to be worth two launches)
@@ -1628,8 +1608,7 @@ static int plan_staging(hipStream_t s, DCsr &A, const Options &opt, const std::a
                            S.code.p, G.row_pat.p, G.tile_pat.p, G.tile_pinfo.p, census.p);
         SA_HIP_CHECK(hipGetLastError());
         unsigned long long hc[4];
-        SA_HIP_CHECK(hipMemcpyAsync(hc, census.p, sizeof(hc), hipMemcpyDeviceToHost, s));
-        SA_HIP_CHECK(hipStreamSynchronize(s));
+        read_back(hc, census.p, 4, s);
         nslots = (int)hc[0]; G.pat_tiles = (int)hc[1]; G.pat_max = (int)hc[2];
         // every staged tile reads a byte per row, the pattern table and its count; the pattern tiles no code words
         S.stream_bytes += (256.0 + 4.0 * SELL_PMAX * 8 + 4.0) * staged_tiles - 4.0 * (double)hc[3];
@@ -1662,17 +1641,30 @@ void build_sell(hipStream_t s, DCsr &A, const Options &opt) {
 // ---- the SpMV family's launches: launch_spmv chooses the format, one launcher per format holds its grid and LDS arithmetic -----
 // the rows [row0, row0 + nrows) of the operator: y, b, dinv and dcode start at row0, x is indexed by GLOBAL column (xrow = x + row0)
 struct SpmvArgs { int row0, nrows; const double *x, *xrow; double *y; const double *b, *dinv; double scale; const unsigned char *dcode; };
+// The XCD deal of the tile kernels (xcd_block): the range's 256-row tiles, eight equal runs of them, one workgroup per tile.
+struct TileDeal { int nblocks, per_xcd, grid; };
+static TileDeal tile_deal(int nrows) {
+    const int nblocks = div_up((long)div_up(nrows, 64) * 64, 256), per_xcd = div_up(nblocks, 8);
+    return {nblocks, per_xcd, per_xcd * 8};
+}
+// ... and of the persistent dictionary kernels: n wavefront-units (slices, or waves of 63 rows) in eight runs, each a whole
+// number of 16-wavefront workgroups' trips, walked by at most wg_cap workgroups per XCD.
+struct WaveDeal { int per_xcd, wg_per_xcd; };
+static WaveDeal wave_deal(int n, int wg_cap) {
+    const int per_xcd = div_up(div_up(n, 8), 16) * 16;
+    return {per_xcd, std::min(wg_cap, div_up(per_xcd, 16))};
+}
 // dictionary with 3 x 3 node blocks: waves of 63 rows, numbered over the whole operator; the kernels take whole-operator arrays
 template <int MODE> static void launch_dict3(hipStream_t s, const DCsr &A, const SpmvArgs &a) {
     const Sell::Dict &D = A.sell.dict;
     const int row0 = a.row0, nrows = a.nrows;
     const int wave0 = row0 / 63, nw = (row0 + nrows - 1) / 63 - wave0 + 1;
-    const int per_xcd = div_up(div_up(nw, 8), 16) * 16;
-    const int wgl = std::min(64, div_up(per_xcd, 16));      // (two workgroups per CU)
+    const WaveDeal d = wave_deal(nw, 64);      // (two workgroups per CU)
     auto kern = sell_gpair3_kernel<MODE>;
     SA_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 12 * GP_MAX + 16));
-    hipLaunchKernelGGL(kern, dim3(wgl * 8), dim3(1024), 12 * (size_t)D.ng + 16, s, A.nrows, row0, row0 + nrows, wave0, nw, per_xcd, wgl, D.ng,
-                       A.sell.ptr.p, D.gcode.p, (const GPair *)D.gtab.p, a.x, a.y - row0, a.b ? a.b - row0 : nullptr, a.dinv ? a.dinv - row0 : nullptr, a.scale);
+    hipLaunchKernelGGL(kern, dim3(d.wg_per_xcd * 8), dim3(1024), 12 * (size_t)D.ng + 16, s, A.nrows, row0, row0 + nrows, wave0, nw, d.per_xcd,
+                       d.wg_per_xcd, D.ng, A.sell.ptr.p, D.gcode.p, (const GPair *)D.gtab.p, a.x, a.y - row0, a.b ? a.b - row0 : nullptr,
+                       a.dinv ? a.dinv - row0 : nullptr, a.scale);
     if (!D.nirr) return;
     SA_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(sell_gpair3_fix_kernel<MODE>, dim3(div_up(D.nirr, 256)), dim3(256), 0, s, D.nirr, D.irr.p, row0, row0 + nrows, A.sell.ptr.p,
@@ -1681,41 +1673,39 @@ template <int MODE> static void launch_dict3(hipStream_t s, const DCsr &A, const
 template <int MODE> static void launch_dict(hipStream_t s, const DCsr &A, const SpmvArgs &a) {
     const Sell::Dict &D = A.sell.dict;
     const int nsl = div_up(a.nrows, 64);
-    const int per_xcd = div_up(div_up(nsl, 8), 16) * 16;
-    const int wg_per_xcd = std::min(32, div_up(per_xcd, 16));
+    const WaveDeal d = wave_deal(nsl, 32);      // (one workgroup per CU)
     const size_t lds = sizeof(GPair) * (size_t)D.ng;
     auto kern = sell_gpair_kernel<MODE>;
     SA_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(GPair) * GP_MAX)));
-    hipLaunchKernelGGL(kern, dim3(wg_per_xcd * 8), dim3(1024), lds, s, a.nrows, a.row0, nsl, per_xcd, wg_per_xcd, D.ng,
+    hipLaunchKernelGGL(kern, dim3(d.wg_per_xcd * 8), dim3(1024), lds, s, a.nrows, a.row0, nsl, d.per_xcd, d.wg_per_xcd, D.ng,
                        A.sell.ptr.p + a.row0 / 64, D.gcode.p, (const GPair *)D.gtab.p, a.x, a.y, a.b, a.dinv, a.scale, a.xrow);
 }
 // staged tiles (a row range of whole tiles: see launch_spmv), and the gather kernel for the tiles that are not staged
 template <int MODE> static void launch_staged(hipStream_t s, const DCsr &A, const SpmvArgs &a) {
     const Sell &S = A.sell; const Sell::Stage &G = S.stage;
-    const int nblocks = div_up((long)div_up(a.nrows, 64) * 64, 256);
-    const int per_xcd = div_up(nblocks, 8), grid_main = per_xcd * 8;
+    const TileDeal d = tile_deal(a.nrows);
+    const roff_t *sptr = S.ptr.p + a.row0 / 64;
     const size_t lds_bytes = 8 * (size_t)G.cap + (G.one_table ? 1 : 4) * 64 * sizeof(PairEntry) +
                              (G.patterns() ? SELL_PMAX * 8 * sizeof(unsigned) : 0);
     // (up to eight tiles that are not staged ride at the end of the staged kernel's grid instead of a launch of their own)
     const bool fold = G.regular() && G.nunstaged > 0 && G.nunstaged <= 8 && 8 * (size_t)G.cap >= 4 * 64 * sizeof(PairEntry);
     if (G.regular()) {
-        const SellLeftover left{grid_main, fold ? G.nunstaged : 0, G.unstaged.p, S.ptr.p + a.row0 / 64, S.col.p, S.val.p, S.ntab.p, S.code.p};
+        const SellLeftover left{d.grid, fold ? G.nunstaged : 0, G.unstaged.p, sptr, S.col.p, S.val.p, S.ntab.p, S.code.p};
         auto kern = G.patterns() ? sell_staged2_kernel<MODE> : sell_staged2_codes_kernel<MODE>;
-        hipLaunchKernelGGL(kern, dim3(grid_main + left.n), dim3(256), lds_bytes, s, left, a.nrows, a.row0, nblocks, per_xcd, G.cap, A.ncols, G.wq,
+        hipLaunchKernelGGL(kern, dim3(d.grid + left.n), dim3(256), lds_bytes, s, left, a.nrows, a.row0, d.nblocks, d.per_xcd, G.cap, A.ncols, G.wq,
                            G.codeR.p, S.tab.p, S.vtab.p, G.tile_desc.p, G.tile_seg.p, a.x, a.y, a.b, a.dinv, a.scale, a.xrow, G.row_pat.p, G.tile_pat.p,
                            G.tile_pinfo.p, a.dcode, (const double *)S.dcode.tab.p);
     } else
-        hipLaunchKernelGGL((sell_staged_kernel<MODE>), dim3(grid_main), dim3(256), lds_bytes, s, a.nrows, a.row0, nblocks, per_xcd, G.cap, A.ncols,
-                           (int)G.one_table, S.ptr.p + a.row0 / 64, S.ntab.p, S.tab.p, S.code.p, a.x, a.y, a.b, a.dinv, a.scale, a.xrow, S.vtab.p, G.tile_nseg.p, G.tile_seg.p);
+        hipLaunchKernelGGL((sell_staged_kernel<MODE>), dim3(d.grid), dim3(256), lds_bytes, s, a.nrows, a.row0, d.nblocks, d.per_xcd, G.cap, A.ncols,
+                           (int)G.one_table, sptr, S.ntab.p, S.tab.p, S.code.p, a.x, a.y, a.b, a.dinv, a.scale, a.xrow, S.vtab.p, G.tile_nseg.p, G.tile_seg.p);
     if (G.nunstaged > 0 && !fold)
         hipLaunchKernelGGL((sell_tiles_kernel<MODE>), dim3(G.nunstaged), dim3(256), 0, s, G.nunstaged, G.unstaged.p, a.nrows, a.row0,
-                           S.ptr.p + a.row0 / 64, S.col.p, S.val.p, S.ntab.p, S.tab.p, S.code.p, a.x, a.y, a.b, a.dinv, a.scale, a.xrow, S.vtab.p);
+                           sptr, S.col.p, S.val.p, S.ntab.p, S.tab.p, S.code.p, a.x, a.y, a.b, a.dinv, a.scale, a.xrow, S.vtab.p);
 }
 template <int MODE> static void launch_slices(hipStream_t s, const DCsr &A, const SpmvArgs &a) {
     const Sell &S = A.sell;
-    const int nblocks = div_up((long)div_up(a.nrows, 64) * 64, 256);
-    const int per_xcd = div_up(nblocks, 8);
-    hipLaunchKernelGGL((sell_spmv_kernel<MODE>), dim3(per_xcd * 8), dim3(256), 0, s, a.nrows, a.row0, nblocks, per_xcd, (int)S.fast_ok,
+    const TileDeal d = tile_deal(a.nrows);
+    hipLaunchKernelGGL((sell_spmv_kernel<MODE>), dim3(d.grid), dim3(256), 0, s, a.nrows, a.row0, d.nblocks, d.per_xcd, (int)S.fast_ok,
                        S.ptr.p + a.row0 / 64, S.col.p, S.val.p, S.ntab.p, S.tab.p, S.code.p, a.x, a.y, a.b, a.dinv, a.scale, a.xrow, S.vtab.p);
 }
 template <int MODE> static void launch_csr(hipStream_t s, const DCsr &A, const SpmvArgs &a) {

@@ -60,8 +60,8 @@ def _run(codes, pair_fast=None):
 
 
 def test_sell_formats_match_scipy_and_each_other():
-    full = _run(None)          # pair codes where possible (all-pair operators: the fast kernel, sell_pair_kernel)
-    slow = _run(None, 0)       # the same through the general kernel
+    full = _run(None)          # pair codes where possible (staged tiles: sell_staged_kernel / sell_staged2_kernel; else sell_slice's short-chain path)
+    slow = _run(None, 0)       # the same through sell_row_general (sell_spmv_kernel, no staging)
     assert {k: v[1] for k, v in slow.items()} == {k: v[1] for k, v in full.items()}      # identical bits
     offs = _run(1)             # offset codes only
     plain = _run(0)            # no codes
