@@ -3,6 +3,7 @@
 // owned by one thread and its element contributions are added in ascending element id, so
 // the sums are bit-reproducible and match the reference's accumulation order.
 #include "assemble.h"
+#include "eig_ss_plan.h"
 
 #include <cstdlib>
 
@@ -1040,7 +1041,7 @@ __global__ __launch_bounds__(256) void ae_perm_kernel(int ae0, const int *__rest
 // is "unvisited rows whose bit row meets the frontier's bit vector", n / 32 words per row and level.  A sweep numbers a level by
 // counting, per node, the nodes of the level with a smaller packed key (lowest position among the previous level's neighbours,
 // degree, tie).  No floating point; LDS atomics are atomicMin / atomicMax / atomicAdd on integers only.
-constexpr int AO_KEEP_BW = 51;        // 67 - SB: the narrowest LDS window of the banded factorisation (eig2.hip)
+constexpr int AO_KEEP_BW = SS_NARROWEST_WINDOW_BAND;      // 51: such a band fits the narrowest LDS window of the banded factorisation as it is
 constexpr int AO_MAX_ROWS = 4096;     // degree and tie in 12 bits each
 constexpr int AO_ROOT_MOVES = 8;
 struct AoTables {

@@ -20,6 +20,7 @@
 #include <cfloat>
 
 #include "eig.h"
+#include "eig_ss_plan.h"
 
 #include <cstdlib>
 
@@ -1277,6 +1278,7 @@ void eig_backtransform_two_stage(hipStream_t s, EigBatch &b, const int64_t *xoff
 // pivot) makes the caller fall back to the dense path on a re-assembled matrix.
 // =========================================================================================
 constexpr int SS_B = 8;
+static_assert(SS_PLAN_SB == SB && SS_PLAN_B == SS_B, "eig_ss_plan.h restates the block sizes");
 constexpr double SS_SIGMA = -1e-3;
 constexpr int SS_MAX_ITER = 80;
 // Matrices with more wanted pairs than the block's six: the first six converged pairs are LOCKED (copied out, the block
@@ -2107,6 +2109,8 @@ __global__ __launch_bounds__(256) void ss_rr_kernel(const int *__restrict__ ns, 
     __shared__ double R[NB][NB + 1], S[NB][NB + 1], V[NB][NB + 1];
     __shared__ double rot_c[NB / 2], rot_s[NB / 2], rdi[NB];     // (rdi: reciprocal diagonal of R)
     __shared__ int sh_st, sh_ok;
+    // residual bound of the previous pair q: || C x - lambda x || <= || C - sigma || mu || z - x / mu ||, || C - sigma || <= 2.5
+    auto bound = [&](int q) { return 2.5 * mu_old[q] * sqrt(res2[q]); };
     if (tid == 0) {
         int st = 0;
         // convergence of the PREVIOUS pairs (X, mu_old): || C x - lambda x || <= || C - sigma || mu || z - x / mu ||
@@ -2114,7 +2118,7 @@ __global__ __launch_bounds__(256) void ss_rr_kernel(const int *__restrict__ ns, 
             int k = 0;
             for (int q = 0; q < NB; ++q) if (sigma + mu_old[q] <= vu) ++k;
             if (dbg)        // (Options::debug bit 0: residual bounds and Ritz values of the previous pairs)
-                for (int q = 0; q < NB; ++q) { dbg[(size_t)b * 2 * NB + q] = 2.5 * mu_old[q] * sqrt(res2[q]); dbg[(size_t)b * 2 * NB + NB + q] = sigma + mu_old[q]; }
+                for (int q = 0; q < NB; ++q) { dbg[(size_t)b * 2 * NB + q] = bound(q); dbg[(size_t)b * 2 * NB + NB + q] = sigma + mu_old[q]; }
             const int nd = ndefl ? ndefl[b] : 0;
             const int cert0 = inertia ? inertia[b] : -2;     // certified #{lambda < vu}; -1: not certifiable, -2: none
             const int cert = cert0 > 0 ? cert0 - nd : cert0; // ... of which nd are locked already
@@ -2124,7 +2128,7 @@ __global__ __launch_bounds__(256) void ss_rr_kernel(const int *__restrict__ ns, 
             // cannot make it within the budget gives up now instead of after max_iter iterations
             if (hist && iter >= 1) {
                 double worst = 0.0;
-                for (int q = 0; q < (partial ? SS_LOCK : max(k, 1)); ++q) worst = fmax(worst, 2.5 * mu_old[q] * sqrt(res2[q]));
+                for (int q = 0; q < (partial ? SS_LOCK : max(k, 1)); ++q) worst = fmax(worst, bound(q));
                 const double old = hist[(size_t)b * 4 + (iter & 3)];
                 hist[(size_t)b * 4 + (iter & 3)] = worst;
                 if (iter >= 6 && worst > SS_TOL && old > 0.0) {
@@ -2140,7 +2144,7 @@ __global__ __launch_bounds__(256) void ss_rr_kernel(const int *__restrict__ ns, 
                 // the six smallest Ritz pairs of the block converged (they lie below the window's end: more than six
                 // eigenvalues do): state bit 3 asks the host to lock them
                 bool ok = k >= SS_LOCK;
-                for (int q = 0; q < SS_LOCK; ++q) ok = ok && (2.5 * mu_old[q] * sqrt(res2[q]) <= SS_TOL);
+                for (int q = 0; q < SS_LOCK; ++q) ok = ok && (bound(q) <= SS_TOL);
                 if (ok) st |= 8;
             } else if (k > NB - 2 || cert > NB - 2 || cert == -1) st |= 2;
             else if (cert >= 0) {
@@ -2148,14 +2152,14 @@ __global__ __launch_bounds__(256) void ss_rr_kernel(const int *__restrict__ ns, 
                 // certified count: accept once it is reached and those pairs have converged (count 0: the
                 // smallest pair alone, the reference's "at least one" rule)
                 bool ok = k == cert;
-                for (int q = 0; q < max(k, 1); ++q) ok = ok && (2.5 * mu_old[q] * sqrt(res2[q]) <= SS_TOL);
+                for (int q = 0; q < max(k, 1); ++q) ok = ok && (bound(q) <= SS_TOL);
                 if (ok) st |= 1 | (k << 4) | (max(k, 1) << 8);
             } else {
                 // no certificate (Options::eig_certify = 0): residual bounds of the wanted pairs; the first unwanted
                 // one has to be pinned above the window (an eigenvalue lies within the bound of its Ritz value)
                 bool ok = true;
-                for (int q = 0; q < max(k, 1); ++q) ok = ok && (2.5 * mu_old[q] * sqrt(res2[q]) <= SS_TOL);
-                if (k >= 1) ok = ok && (2.5 * mu_old[k] * sqrt(res2[k]) < 0.5 * (sigma + mu_old[k] - vu));
+                for (int q = 0; q < max(k, 1); ++q) ok = ok && (bound(q) <= SS_TOL);
+                if (k >= 1) ok = ok && (bound(k) < 0.5 * (sigma + mu_old[k] - vu));
                 if (ok) st |= 1 | (k << 4) | (max(k, 1) << 8);
             }
         }
@@ -2181,10 +2185,15 @@ __global__ __launch_bounds__(256) void ss_rr_kernel(const int *__restrict__ ns, 
         }
     }
     __syncthreads();
-    if (NB != 8 && !(sh_st & 3)) {
-        // ---- NB = 16: the same with all 256 threads and workgroup barriers (16 x 16 entries: one per thread; eight disjoint
-        // rotations per step, fifteen steps per sweep) ----
+    if (!(sh_st & 3) && (NB != 8 || tid < 64)) {
+        // ---- S = R^-T Msym R^-1 and its eigen-decomposition by parallel-order Jacobi: one entry of S per thread ----
+        // NB = 8: one wavefront, wavefront barriers; NB = 16: all 256 threads, workgroup barriers (eight disjoint rotations
+        // per step, fifteen steps per sweep)
         const int lr = tid / NB, lc = tid % NB;
+        auto sync = []() {
+            if constexpr (NB == 8) { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+            else __syncthreads();
+        };
         V[lr][lc] = (lr == lc) ? 1.0 : 0.0;
         if (tid < NB) {                     // column c of T1 = R^-T Msym: forward substitution
             const int c = tid;
@@ -2194,7 +2203,7 @@ __global__ __launch_bounds__(256) void ss_rr_kernel(const int *__restrict__ ns, 
                 S[r2][c] = t * rdi[r2];
             }
         }
-        __syncthreads();
+        sync();
         if (tid < NB) {                     // row r of S = T1 R^-1
             const int r2 = tid;
             for (int c = 0; c < NB; ++c) {
@@ -2203,123 +2212,31 @@ __global__ __launch_bounds__(256) void ss_rr_kernel(const int *__restrict__ ns, 
                 S[r2][c] = t * rdi[c];
             }
         }
-        __syncthreads();
+        sync();
         {
             const double t = 0.5 * (S[lr][lc] + S[lc][lr]);
-            __syncthreads();
+            sync();
             S[lr][lc] = t;
         }
-        __syncthreads();
-        for (int sweep = 0; sweep < 16; ++sweep) {
+        sync();
+        constexpr int SWEEPS = NB == 8 ? 12 : 16;
+        for (int sweep = 0; sweep < SWEEPS; ++sweep) {
             double off = (lr != lc) ? S[lr][lc] * S[lr][lc] : 0.0, dg = (lr == lc) ? S[lr][lc] * S[lr][lc] : 0.0;
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) { off += __shfl_xor(off, o, 64); dg += __shfl_xor(dg, o, 64); }
-            if ((tid & 63) == 0) { part[0][0][tid >> 6] = off; part[0][1][tid >> 6] = dg; }
-            __syncthreads();
-            off = (part[0][0][0] + part[0][0][1]) + (part[0][0][2] + part[0][0][3]);
-            dg = (part[0][1][0] + part[0][1][1]) + (part[0][1][2] + part[0][1][3]);
-            __syncthreads();
+            if constexpr (NB != 8) {        // four wavefronts: their sums through LDS
+                if ((tid & 63) == 0) { part[0][0][tid >> 6] = off; part[0][1][tid >> 6] = dg; }
+                sync();
+                off = (part[0][0][0] + part[0][0][1]) + (part[0][0][2] + part[0][0][3]);
+                dg = (part[0][1][0] + part[0][1][1]) + (part[0][1][2] + part[0][1][3]);
+                sync();
+            }
             if (off <= 1e-34 * dg) break;      // (uniform)
             for (int step = 0; step < NB - 1; ++step) {
                 // round-robin pairing of NB players: the last one fixed, the others rotate
                 auto player = [&](int slot) { return slot == NB - 1 ? NB - 1 : (slot + step) % (NB - 1); };
                 if (tid < NB / 2) {
                     int p2 = player(tid), q2 = player(NB - 1 - tid);
-                    if (p2 > q2) { const int t = p2; p2 = q2; q2 = t; }
-                    double cc = 1.0, sn = 0.0;
-                    const double apq = S[p2][q2];
-                    if (apq != 0.0) {
-                        const double d = S[q2][q2] - S[p2][p2];
-                        const double den = fabs(d) + fast_sqrt(fma(d, d, 4.0 * apq * apq));
-                        const double t = ((d >= 0.0) == (apq >= 0.0) ? 2.0 : -2.0) * fabs(apq) * fast_rcp(den);
-                        cc = fast_rsqrt(fma(t, t, 1.0));
-                        sn = t * cc;
-                    }
-                    rot_c[tid] = cc;
-                    rot_s[tid] = sn;
-                }
-                __syncthreads();
-                const int m2 = tid % (NB / 2), k2 = (tid / (NB / 2)) % NB;      // pair m2, row / column k2; threads 0..127 S, 128..255 V
-                int p2 = player(m2), q2 = player(NB - 1 - m2);
-                if (p2 > q2) { const int t = p2; p2 = q2; q2 = t; }
-                const double cc = rot_c[m2], sn = rot_s[m2];
-                {   // columns p, q of S and of V (the entries (k2, p2), (k2, q2) belong to this thread alone)
-                    double (*Mx)[NB + 1] = (tid < NB * NB / 2) ? S : V;
-                    const double a = Mx[k2][p2], bq = Mx[k2][q2];
-                    Mx[k2][p2] = cc * a - sn * bq;
-                    Mx[k2][q2] = sn * a + cc * bq;
-                }
-                __syncthreads();
-                if (tid < NB * NB / 2) {   // rows p, q of S
-                    const double a = S[p2][k2], bq = S[q2][k2];
-                    S[p2][k2] = cc * a - sn * bq;
-                    S[q2][k2] = sn * a + cc * bq;
-                }
-                __syncthreads();
-            }
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int order[NB];
-            for (int q = 0; q < NB; ++q) order[q] = q;
-            for (int a2 = 0; a2 < NB; ++a2)
-                for (int b2 = a2 + 1; b2 < NB; ++b2)
-                    if (S[order[b2]][order[b2]] < S[order[a2]][order[a2]]) { const int t = order[a2]; order[a2] = order[b2]; order[b2] = t; }
-            for (int q = 0; q < NB; ++q) {
-                mus[q] = S[order[q]][order[q]];
-                if (!(mus[q] > 0.0)) sh_ok = 0;
-                res2[q] = (double)order[q];      // (res2 is free now: source column of output q)
-            }
-        }
-        __syncthreads();
-        if (tid < NB) {      // column q of C = R^-1 V(:, src)
-            const int q = tid, src = (int)res2[q];
-            for (int r2 = NB - 1; r2 >= 0; --r2) {
-                double t = V[r2][src];
-                for (int c2 = r2 + 1; c2 < NB; ++c2) t -= R[r2][c2] * Cs[c2][q];
-                Cs[r2][q] = t * rdi[r2];
-            }
-        }
-    }
-    if (NB == 8 && !(sh_st & 3) && tid < 64) {
-        // ---- S = R^-T Msym R^-1 and its eigen-decomposition by parallel-order Jacobi, one wavefront ----
-        const int lr = tid >> 3, lc = tid & 7;
-        auto wsync = []() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); };
-        V[lr][lc] = (lr == lc) ? 1.0 : 0.0;
-        if (tid < NB) {                     // column c of T1 = R^-T Msym: forward substitution
-            const int c = tid;
-            for (int r2 = 0; r2 < NB; ++r2) {
-                double t = 0.5 * (Ms[r2][c] + Ms[c][r2]);
-                for (int q = 0; q < r2; ++q) t -= R[q][r2] * S[q][c];
-                S[r2][c] = t * rdi[r2];
-            }
-        }
-        wsync();
-        if (tid < NB) {                     // row r of S = T1 R^-1
-            const int r2 = tid;
-            for (int c = 0; c < NB; ++c) {
-                double t = S[r2][c];
-                for (int q = 0; q < c; ++q) t -= S[r2][q] * R[q][c];
-                S[r2][c] = t * rdi[c];
-            }
-        }
-        wsync();
-        {
-            const double t = 0.5 * (S[lr][lc] + S[lc][lr]);
-            wsync();
-            S[lr][lc] = t;
-        }
-        wsync();
-        for (int sweep = 0; sweep < 12; ++sweep) {
-            double off = (lr != lc) ? S[lr][lc] * S[lr][lc] : 0.0, dg = (lr == lc) ? S[lr][lc] * S[lr][lc] : 0.0;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) { off += __shfl_xor(off, o, 64); dg += __shfl_xor(dg, o, 64); }
-            if (off <= 1e-34 * dg) break;
-            for (int step = 0; step < 7; ++step) {
-                // round-robin pairing of 8 players: player 7 fixed, the others rotate
-                auto player = [&](int slot) { return slot == 7 ? 7 : (slot + step) % 7; };
-                if (tid < 4) {
-                    int p2 = player(tid), q2 = player(7 - tid);
                     if (p2 > q2) { const int t = p2; p2 = q2; q2 = t; }
                     double cc = 1.0, sn = 0.0;
                     const double apq = S[p2][q2];
@@ -2334,28 +2251,29 @@ __global__ __launch_bounds__(256) void ss_rr_kernel(const int *__restrict__ ns, 
                     rot_c[tid] = cc;
                     rot_s[tid] = sn;
                 }
-                wsync();
-                const int m2 = tid & 3, k2 = (tid >> 2) & 7;      // pair m2, row / column k2; lanes 0..31 S, 32..63 V
-                int p2 = player(m2), q2 = player(7 - m2);
+                sync();
+                // pair m2, row / column k2; the lower half of the threads rotates S, the upper half V
+                const int m2 = tid % (NB / 2), k2 = (tid / (NB / 2)) % NB;
+                int p2 = player(m2), q2 = player(NB - 1 - m2);
                 if (p2 > q2) { const int t = p2; p2 = q2; q2 = t; }
                 const double cc = rot_c[m2], sn = rot_s[m2];
-                {   // columns p, q of S (lanes < 32) and of V (lanes >= 32)
-                    double (*Mx)[NB + 1] = (tid < 32) ? S : V;
+                {   // columns p, q of S and of V (the entries (k2, p2), (k2, q2) belong to this thread alone)
+                    double (*Mx)[NB + 1] = (tid < NB * NB / 2) ? S : V;
                     const double a = Mx[k2][p2], bq = Mx[k2][q2];
-                    wsync();
+                    if constexpr (NB == 8) sync();
                     Mx[k2][p2] = cc * a - sn * bq;
                     Mx[k2][q2] = sn * a + cc * bq;
                 }
-                wsync();
-                if (tid < 32) {   // rows p, q of S
+                sync();
+                if (tid < NB * NB / 2) {   // rows p, q of S
                     const double a = S[p2][k2], bq = S[q2][k2];
                     S[p2][k2] = cc * a - sn * bq;
                     S[q2][k2] = sn * a + cc * bq;
                 }
-                wsync();
+                sync();
             }
         }
-        wsync();
+        sync();
         if (tid == 0) {
             int order[NB];
             for (int q = 0; q < NB; ++q) order[q] = q;
@@ -2365,11 +2283,10 @@ __global__ __launch_bounds__(256) void ss_rr_kernel(const int *__restrict__ ns, 
             for (int q = 0; q < NB; ++q) {
                 mus[q] = S[order[q]][order[q]];
                 if (!(mus[q] > 0.0)) sh_ok = 0;
-                rot_c[0] = 0.0;
                 res2[q] = (double)order[q];      // (res2 is free now: source column of output q)
             }
         }
-        wsync();
+        sync();
         if (tid < NB) {      // column q of C = R^-1 V(:, src)
             const int q = tid, src = (int)res2[q];
             for (int r2 = NB - 1; r2 >= 0; --r2) {
@@ -2975,11 +2892,107 @@ __global__ __launch_bounds__(64 * WV) void band_trail_mfma_kernel(int k0, const 
 }
 
 
+// ---------------------------------------------------------------------------------------
+// The driver.  Which kernel runs, with how many threads and how much LDS, is decided by the pure functions of
+// eig_ss_plan.h; the functions below launch what the plan says and hold no threshold of their own.
+// ---------------------------------------------------------------------------------------
+
+// a matrix that goes to the dense path ALONE (h_bad), as long as such matrices are few: one uncertifiable agglomerate must
+// not send the other 14 000 of its chunk through the dense path
+static void mark_bad(EigBatch &b, int i) { if (!b.h_bad[(size_t)i]) { b.h_bad[(size_t)i] = 1; ++b.nbad; } }
+static bool too_many_bad(const EigBatch &b) { return (long)b.nbad * 10 > (long)b.count; }
+
+// (kernels of the iteration block are templates on its width)
+template <class F>
+static void with_nb(int nb, F f) { if (nb == 16) f(std::integral_constant<int, 16>()); else f(std::integral_constant<int, 8>()); }
+
+// chol_band_lds2_kernel<window, INERTIA> on nwg workgroups: the one place that spells the four windows out
+template <bool INERTIA>
+static void launch_band_lds(hipStream_t s, EigBatch &b, int win, int nwg, int *info, double shift, const int *active) {
+    auto go = [&](auto kern, int w) {
+        SA_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bc2_lds_bytes(w)));
+        hipLaunchKernelGGL(kern, dim3(nwg), dim3(BC_NT), bc2_lds_bytes(w), s, b.n.p, b.moff.p, b.W.p, b.bw.p, info, shift, active);
+    };
+    if (win == 67) go(chol_band_lds2_kernel<67, INERTIA>, 67);
+    else if (win == 68) go(chol_band_lds2_kernel<68, INERTIA>, 68);
+    else if (win == 80) go(chol_band_lds2_kernel<80, INERTIA>, 80);
+    else go(chol_band_lds2_kernel<128, INERTIA>, 128);
+    SA_HIP_CHECK(hipGetLastError());
+}
+
+// the bands of the batch to (RESTORE: back from) b.ss_save; skip: matrices the launch leaves alone
+template <bool RESTORE>
+static void launch_band_copy(hipStream_t s, EigBatch &b, const int *skip = nullptr) {
+    hipLaunchKernelGGL(band_copy_kernel<RESTORE>, dim3(b.count, ss_band_copy_ny(b.count)), dim3(256), 0, s, b.n.p, b.moff.p, b.W.p,
+                       b.bw.p, b.ss_soff.p, b.ss_save, skip);
+}
+
+// Panel kernels come in two workgroup sizes and a signed / unsigned form: f(threads, signed) as compile-time constants
+template <int SMALL, int LARGE, class F>
+static void with_panel(int threads, bool sgn, F f) {
+    auto sized = [&](auto sg) {
+        if (threads == LARGE) f(std::integral_constant<int, LARGE>(), sg);
+        else f(std::integral_constant<int, SMALL>(), sg);
+    };
+    if (sgn) sized(std::true_type()); else sized(std::false_type());
+}
+
+// ---- the two factor walks ----
+// What a walk factors: C - sigma I = L L^T for every matrix of the batch in place (L below / L^T above the diagonal,
+// the diagonal blocks inverted), or, sgn, the indefinite C - theta I = L S L^T of the inertia count (neg receives the
+// negative pivots; the factor is written back only with keep).  info: 1 where a pivot could not be trusted.
+struct SsWalk {
+    EigBatch &b;
+    bool sgn;
+    int *neg, *info;
+    int bwmax, keep;
+    const int *skip;
+    bool prof;
+    const char *panel_label() const { return sgn ? "eig_ss_inertia_panel" : "eig_ss_panel"; }
+    const char *update_label(int np) const { return sgn ? "eig_ss_inertia_update" : (np > 192 ? "eig_ss_update" : "eig_ss_update1"); }
+    // profiler: the lower tiles of the trailing windows behind column k1 (inside the band), read and written once
+    double trail_bytes(int k1) const {
+        double ub = 0.0;
+        for (size_t i = 0; i < b.h_n.size(); ++i) {
+            const double qn = std::min((double)b.h_n[i] - k1, (double)b.h_bw[i]);
+            if (qn >= 1.0) ub += 8.0 * qn * qn;
+        }
+        return ub;
+    }
+};
+// The matrices first .. first + cnt - 1 of the batch on stream q: every per-matrix array of the walks' kernels is indexed
+// by the matrix alone, so a part of the batch is the same launch with the arrays shifted.
+struct SsWalkPart {
+    hipStream_t q;
+    int cnt, cnt8;
+    const int *ns;
+    const int64_t *moff, *voff, *goff;
+    const int *gbw, *sk;
+    int *ng, *info;
+    SsWalkPart(const SsWalk &w, hipStream_t q_, int first, int cnt_)
+        : q(q_), cnt(cnt_), cnt8(8 * div_up(cnt_, 8)), ns(w.b.n.p + first), moff(w.b.moff.p + first), voff(w.b.voff.p + first),
+          goff(w.b.goff.p + first), gbw(w.b.bw.p + first), sk(w.skip ? w.skip + first : nullptr), ng(w.neg ? w.neg + first : nullptr),
+          info(w.info + first) {}
+};
+// step(part, k0) launches the block step at column k0 for one part and says whether columns are left behind it
+template <class Step>
+static void ss_walk_columns(int nmax, int stride, const SsWalkPart *parts, int nparts, Step step) {
+    for (int k0 = 0; k0 < nmax; k0 += stride) {
+        bool more = false;
+        for (int h = 0; h < nparts; ++h) more = step(parts[h], k0) || more;
+        if (!more) break;
+    }
+    SA_HIP_CHECK(hipGetLastError());
+}
+
+// Outer blocks of G sub-panels (chol_panel_ll_kernel, band_trail_mfma_kernel).
+// ONE stream: the two halves on two streams that help the two-panel walk below (panels = latency chains beside the
+// other half's updates) cost these kernels a tenth (config 5: 8.44 against 7.98 s per step) -- a whole chunk's panels
+// fill the card two workgroups deep, and two windows' worth of tiles thrash what one leaves in the caches
 template <int G>
-static void ss_factor_blocked(hipStream_t s, EigBatch &b, bool sgn, int *neg, int *info_p, const int *gbw_all, int bwmax, int keep,
-                              const int *skip) {
+static void ss_factor_blocked(hipStream_t s, const SsWalk &w) {
+    EigBatch &b = w.b;
     const int nmax = b.max_n;
-    const bool prof = profiler().enabled;
     const size_t rows = (size_t)b.h_voff[b.count];
     const size_t pstride = (rows * SB + 15) / 16 * 16;
     if (b.ss_sub_n < pstride * G * 2) {      // (both operand sets, whichever factorisation comes first)
@@ -2987,167 +3000,98 @@ static void ss_factor_blocked(hipStream_t s, EigBatch &b, bool sgn, int *neg, in
         b.ss_sub_n = pstride * G * 2;
     }
     double *Pc = b.ss_sub;
-    double *Pr = sgn ? Pc + pstride * G : Pc;
-    // ONE stream: the two halves on two streams that help the two-panel walk below (panels = latency chains beside the
-    // other half's updates) cost these kernels a tenth (config 5: 8.44 against 7.98 s per step) -- a whole chunk's panels
-    // fill the card two workgroups deep, and two windows' worth of tiles thrash what one leaves in the caches
-    struct Part { hipStream_t q; int first, cnt; };
-    const Part parts[1] = {{s, 0, b.count}};
-    const int nparts = 1;
-    auto step = [&](const Part &P, int k0) {
-        hipStream_t q = P.q;
-        const int f = P.first, cnt = P.cnt;
-        const int cnt8 = 8 * div_up(cnt, 8);
-        const int *ns = b.n.p + f;
-        const int64_t *moff = b.moff.p + f, *voff = b.voff.p + f;
-        const int *gbw = gbw_all ? gbw_all + f : nullptr;
-        const int *sk = skip ? skip + f : nullptr;
-        int *ng = neg ? neg + f : nullptr;
-        int *info = info_p + f;
-        const bool big = std::min(nmax - k0, bwmax + SB * G) > 448;
-        if (prof) profiler().begin(q);
-        {
-            const int g1 = std::min(G, div_up(nmax - k0, SB));
-            if (sgn) {
-                if (big) hipLaunchKernelGGL((chol_panel_ll_kernel<512, G, true>), dim3(cnt), dim3(512), 0, q, k0, 0, g1, ns, moff, voff, b.W.p, Pc, Pr,
-                                            pstride, info, gbw, ng, keep, sk);
-                else hipLaunchKernelGGL((chol_panel_ll_kernel<256, G, true>), dim3(cnt), dim3(256), 0, q, k0, 0, g1, ns, moff, voff, b.W.p, Pc, Pr,
-                                        pstride, info, gbw, ng, keep, sk);
-            } else {
-                if (big) hipLaunchKernelGGL((chol_panel_ll_kernel<512, G, false>), dim3(cnt), dim3(512), 0, q, k0, 0, g1, ns, moff, voff, b.W.p, Pc, Pr,
-                                            pstride, info, gbw, (int *)nullptr, 0, sk);
-                else hipLaunchKernelGGL((chol_panel_ll_kernel<256, G, false>), dim3(cnt), dim3(256), 0, q, k0, 0, g1, ns, moff, voff, b.W.p, Pc, Pr,
-                                        pstride, info, gbw, (int *)nullptr, 0, sk);
-            }
-        }
-        if (prof) profiler().end(q, sgn ? "eig_ss_inertia_panel" : "eig_ss_panel", 0.0, 0.0);
-        const int npmax = std::min(nmax - k0 - SB * G, bwmax);
+    double *Pr = w.sgn ? Pc + pstride * G : Pc;
+    const SsWalkPart whole(w, s, 0, b.count);
+    ss_walk_columns(nmax, SB * G, &whole, 1, [&](const SsWalkPart &P, int k0) {
+        if (w.prof) profiler().begin(P.q);
+        const int g1 = std::min(G, div_up(nmax - k0, SB));
+        with_panel<256, 512>(ss_blocked_panel_threads(nmax - k0, w.bwmax, G), w.sgn, [&](auto nt, auto sg) {
+            constexpr int NT = decltype(nt)::value;
+            constexpr bool SG = decltype(sg)::value;
+            hipLaunchKernelGGL((chol_panel_ll_kernel<NT, G, SG>), dim3(P.cnt), dim3(NT), 0, P.q, k0, 0, g1, P.ns, P.moff, P.voff, b.W.p, Pc, Pr,
+                               pstride, P.info, P.gbw, SG ? P.ng : (int *)nullptr, SG ? w.keep : 0, P.sk);
+        });
+        if (w.prof) profiler().end(P.q, w.panel_label(), 0.0, 0.0);
+        const int npmax = std::min(nmax - k0 - SB * G, w.bwmax);
         if (npmax < 1) return false;
         double ub = 0.0;
-        if (prof) {      // lower tiles of the trailing windows, read and written once
-            for (size_t i = 0; i < b.h_n.size(); ++i) {
-                double qn = (double)b.h_n[i] - k0 - SB * G;
-                if (!b.h_bw.empty()) qn = std::min(qn, (double)b.h_bw[i]);
-                if (qn >= 1.0) ub += 8.0 * qn * qn;
-            }
-            profiler().begin(q);
+        if (w.prof) {
+            ub = w.trail_bytes(k0 + SB * G);
+            profiler().begin(P.q);
         }
-        // (two wavefronts per workgroup: a strip's wavefronts stop at their own diagonal and wait for the last one at the
-        // barriers, and the last strip of a window is partial -- with four, a third of the wavefront-steps were idle)
-        // (four wavefronts per workgroup: with two, fewer wavefront-steps idle at a strip's diagonal but twice the staging
-        // traffic -- 8.10 instead of 7.98 s per step on config 5; with eight 8.5)
+        // (four wavefronts per workgroup: with two, fewer wavefront-steps idle at a strip's diagonal -- a strip's wavefronts
+        // stop at their own diagonal and wait for the last one at the barriers, and the last strip of a window is partial --
+        // but twice the staging traffic: 8.10 instead of 7.98 s per step on config 5; with eight 8.5)
         constexpr int WV = 4;
         const int tiles = div_up(npmax, 32 * WV);
-        if (sgn) hipLaunchKernelGGL((band_trail_mfma_kernel<G, true, WV>), dim3(cnt8 * tiles), dim3(64 * WV), 0, q, k0, ns, moff, voff, b.W.p, Pc, Pr,
-                                    pstride, cnt, tiles, gbw, sk);
-        else hipLaunchKernelGGL((band_trail_mfma_kernel<G, false, WV>), dim3(cnt8 * tiles), dim3(64 * WV), 0, q, k0, ns, moff, voff, b.W.p, Pc, Pr,
-                                pstride, cnt, tiles, gbw, sk);
-        if (prof) profiler().end(q, sgn ? "eig_ss_inertia_update" : (npmax > 192 ? "eig_ss_update" : "eig_ss_update1"), ub, 0.0);
+        if (w.sgn) hipLaunchKernelGGL((band_trail_mfma_kernel<G, true, WV>), dim3(P.cnt8 * tiles), dim3(64 * WV), 0, P.q, k0, P.ns, P.moff, P.voff,
+                                      b.W.p, Pc, Pr, pstride, P.cnt, tiles, P.gbw, P.sk);
+        else hipLaunchKernelGGL((band_trail_mfma_kernel<G, false, WV>), dim3(P.cnt8 * tiles), dim3(64 * WV), 0, P.q, k0, P.ns, P.moff, P.voff,
+                                b.W.p, Pc, Pr, pstride, P.cnt, tiles, P.gbw, P.sk);
+        if (w.prof) profiler().end(P.q, w.update_label(npmax), ub, 0.0);
         return true;
-    };
-    for (int k0 = 0; k0 < nmax; k0 += SB * G) {
-        bool more = false;
-        for (int h = 0; h < nparts; ++h) more = step(parts[h], k0) || more;
-        if (!more) break;
-    }
-    SA_HIP_CHECK(hipGetLastError());
+    });
 }
 
-// C - sigma I = L L^T for every matrix of the batch (in place, L below / L^T above the diagonal).
-// Returns false when a pivot was not positive.
-// Blocked right-looking factorisation of every matrix in place, two panels per pass over the trailing
-// matrix: panel k, its update of the next SB columns only, panel k + 1, then A22(2 SB:, 2 SB:) -=
-// L_k L_k^T + L_{k+1} L_{k+1}^T in one read + write of the lower tiles.  sgn: C - theta I = L S L^T
-// (inertia count; the factor is not kept), neg receives the negative pivots.
-static void ss_factor_generic(hipStream_t s, EigBatch &b, bool sgn, int *neg, int *info_p, const int *bws, int bwmax,
-                              int keep = 0, const int *skip = nullptr) {
+// Blocked right-looking factorisation, two panels per pass over the trailing matrix: panel k, its update of the next SB
+// columns only, panel k + 1, then A22(2 SB:, 2 SB:) -= L_k L_k^T + L_{k+1} L_{k+1}^T in one read + write of the lower tiles.
+// Two halves of the batch on two streams (round 4): a panel is a latency chain (one workgroup per matrix: diagonal block by
+// one wavefront, then the panel rows), the trailing update is compute-bound -- one half's panels run beside the other half's
+// updates (ss_two_stream_split says when).
+static void ss_factor_two_panel(hipStream_t s, const SsWalk &w) {
+    EigBatch &b = w.b;
     const int nmax = b.max_n;
-    const bool prof = profiler().enabled;
-    const int *gbw_all = bws ? bws : (sgn ? b.bw.p : nullptr);
-    if (b.opt.eig_outer_panels >= 8) return ss_factor_blocked<8>(s, b, sgn, neg, info_p, gbw_all, bwmax, keep, skip);
-    if (b.opt.eig_outer_panels >= 4) return ss_factor_blocked<4>(s, b, sgn, neg, info_p, gbw_all, bwmax, keep, skip);
-    // Two halves of the batch on two streams (round 4): a panel is a latency chain (one workgroup per matrix: diagonal block by
-    // one wavefront, then the panel rows), the trailing update is compute-bound -- one half's panels run beside the other half's
-    // updates.  Every per-matrix array of the kernels is indexed by the matrix alone, so a half is the same launch with the
-    // arrays shifted.  Not under the profiler (its event pair brackets one stream), not for small batches.
-    const bool two = !prof && !env_serial() && b.count >= 64;
-    hipStream_t s2 = two ? side_stream(5) : s;
+    const SsSplit split = ss_two_stream_split(b.count, w.prof, env_serial());
+    hipStream_t s2 = split.two ? side_stream(5) : s;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (two) {
+    if (split.two) {
         SA_HIP_CHECK(hipEventCreateWithFlags(&ev0, hipEventDisableTiming));
         SA_HIP_CHECK(hipEventCreateWithFlags(&ev1, hipEventDisableTiming));
         SA_HIP_CHECK(hipEventRecord(ev0, s));                 // the matrices are assembled
         SA_HIP_CHECK(hipStreamWaitEvent(s2, ev0, 0));
     }
-    const int half0 = two ? (b.count / 2 + 7) / 8 * 8 : b.count;      // (multiples of 8: the XCD decode of the tiled kernels)
-    struct Part { hipStream_t q; int first, cnt; };
-    const Part parts[2] = {{s, 0, half0}, {s2, half0, b.count - half0}};
-    const int nparts = (two && b.count - half0 > 0) ? 2 : 1;
-    auto step = [&](const Part &P, int k0) {
-        hipStream_t q = P.q;
-        const int f = P.first, cnt = P.cnt;
-        const int cnt8 = 8 * div_up(cnt, 8);
-        const int *ns = b.n.p + f;
-        const int64_t *moff = b.moff.p + f, *voff = b.voff.p + f, *goff = b.goff.p + f;
-        const int *gbw = gbw_all ? gbw_all + f : nullptr;
-        const int *sk = skip ? skip + f : nullptr;
-        int *ng = neg ? neg + f : nullptr;
-        int *info = info_p + f;
+    const SsWalkPart parts[2] = {SsWalkPart(w, s, 0, split.first), SsWalkPart(w, s2, split.first, b.count - split.first)};
+    const int panel_threads = ss_two_panel_threads(nmax, w.bwmax);
+    const double *vrow = w.sgn ? b.Xbuf.p : nullptr, *zrow = w.sgn ? b.Tfac.p : nullptr;
+    ss_walk_columns(nmax, 2 * SB, parts, split.two ? 2 : 1, [&](const SsWalkPart &P, int k0) {
         auto panel = [&](int kk, double *Vout, double *Zout, int rext, double *Sout) {
-            if (prof) profiler().begin(q);
-            const bool big = std::min(nmax, bwmax + 2 * SB) > 768;
-            if (sgn) {
-                if (big) hipLaunchKernelGGL((chol_panel_kernel<1024, true>), dim3(cnt), dim3(1024), 0, q, kk, ns, moff,
-                                            voff, b.W.p, Vout, Zout, info, gbw, rext, Sout, ng, keep, sk);
-                else hipLaunchKernelGGL((chol_panel_kernel<256, true>), dim3(cnt), dim3(256), 0, q, kk, ns, moff,
-                                        voff, b.W.p, Vout, Zout, info, gbw, rext, Sout, ng, keep, sk);
-            } else {
-                if (big) hipLaunchKernelGGL((chol_panel_kernel<1024, false>), dim3(cnt), dim3(1024), 0, q, kk, ns, moff,
-                                            voff, b.W.p, Vout, Zout, info, gbw, rext, (double *)nullptr, (int *)nullptr, 0, sk);
-                else hipLaunchKernelGGL((chol_panel_kernel<256, false>), dim3(cnt), dim3(256), 0, q, kk, ns, moff,
-                                        voff, b.W.p, Vout, Zout, info, gbw, rext, (double *)nullptr, (int *)nullptr, 0, sk);
-            }
-            if (prof) profiler().end(q, sgn ? "eig_ss_inertia_panel" : "eig_ss_panel", 0.0, 0.0);
+            if (w.prof) profiler().begin(P.q);
+            with_panel<256, 1024>(panel_threads, w.sgn, [&](auto nt, auto sg) {
+                constexpr int NT = decltype(nt)::value;
+                constexpr bool SG = decltype(sg)::value;
+                hipLaunchKernelGGL((chol_panel_kernel<NT, SG>), dim3(P.cnt), dim3(NT), 0, P.q, kk, P.ns, P.moff, P.voff, b.W.p, Vout, Zout, P.info,
+                                   P.gbw, rext, SG ? Sout : (double *)nullptr, SG ? P.ng : (int *)nullptr, SG ? w.keep : 0, P.sk);
+            });
+            if (w.prof) profiler().end(P.q, w.panel_label(), 0.0, 0.0);
         };
-        const double *vrow = sgn ? b.Xbuf.p : nullptr, *zrow = sgn ? b.Tfac.p : nullptr;
         panel(k0, b.Vpk.p, b.Zbuf.p, SB, b.Xbuf.p);
         const int np1f = nmax - k0 - SB;         // order of the trailing matrix after panel k
         if (np1f < 1) return false;
-        const int np1 = std::min(np1f, bwmax);   // ... of its part inside the band
+        const int np1 = std::min(np1f, w.bwmax);   // ... of its part inside the band
         if (np1 >= 1) {
-            if (prof) profiler().begin(q);
-            hipLaunchKernelGGL(sbr_panel_update_kernel, dim3(cnt8 * div_up(np1, 256)), dim3(256), 0, q, k0, ns, moff,
-                               voff, b.W.p, b.Vpk.p, b.Zbuf.p, cnt, div_up(np1, 256), 1, gbw, sk);
-            if (prof) profiler().end(q, sgn ? "eig_ss_inertia_panel" : "eig_ss_panel", 0.0, 0.0);
+            if (w.prof) profiler().begin(P.q);
+            hipLaunchKernelGGL(sbr_panel_update_kernel, dim3(P.cnt8 * div_up(np1, 256)), dim3(256), 0, P.q, k0, P.ns, P.moff,
+                               P.voff, b.W.p, b.Vpk.p, b.Zbuf.p, P.cnt, div_up(np1, 256), 1, P.gbw, P.sk);
+            if (w.prof) profiler().end(P.q, w.panel_label(), 0.0, 0.0);
         }
         panel(k0 + SB, b.Vpk2.p, nullptr, 0, b.Tfac.p);
-        const int np = std::min(np1f - SB, bwmax);    // ... after panel k + 1
+        const int np = std::min(np1f - SB, w.bwmax);    // ... after panel k + 1
         if (np >= 1) {
             double ub = 0.0;
-            if (prof) {      // lower tiles of the trailing matrices (inside the band), read and written once
-                for (size_t i = 0; i < b.h_n.size(); ++i) {
-                    double qn = (double)b.h_n[i] - k0 - 2 * SB;
-                    if (!b.h_bw.empty()) qn = std::min(qn, (double)b.h_bw[i]);
-                    if (qn >= 1.0) ub += 8.0 * qn * qn;
-                }
-                profiler().begin(q);
+            if (w.prof) {
+                ub = w.trail_bytes(k0 + 2 * SB);
+                profiler().begin(P.q);
             }
             // (one row per lane, 108 VGPRs, four wavefronts per SIMD: 8 % faster on the 2 187-row agglomerates of config 5 than two
             // rows per lane at 212 VGPRs and two wavefronts per SIMD)
-            hipLaunchKernelGGL((sbr_fused_kernel<false, 1, 3>), dim3(cnt8 * div_up(np, SF_ROWS)), dim3(S2_NT), 0, q, k0,
-                               ns, moff, voff, b.W.p, b.Vpk.p, b.Vpk2.p, b.Vpk.p, b.Xbuf.p, goff,
-                               b.Gbuf.p, b.trash.p, cnt, div_up(np, SF_ROWS), SB, gbw, vrow, zrow, sk);
-            if (prof) profiler().end(q, sgn ? "eig_ss_inertia_update" : (np > 192 ? "eig_ss_update" : "eig_ss_update1"), ub, 0.0);
+            hipLaunchKernelGGL((sbr_fused_kernel<false, 1, 3>), dim3(P.cnt8 * div_up(np, SF_ROWS)), dim3(S2_NT), 0, P.q, k0,
+                               P.ns, P.moff, P.voff, b.W.p, b.Vpk.p, b.Vpk2.p, b.Vpk.p, b.Xbuf.p, P.goff,
+                               b.Gbuf.p, b.trash.p, P.cnt, div_up(np, SF_ROWS), SB, P.gbw, vrow, zrow, P.sk);
+            if (w.prof) profiler().end(P.q, w.update_label(np), ub, 0.0);
         }
         return true;
-    };
-    for (int k0 = 0; k0 < nmax; k0 += 2 * SB) {
-        bool more = false;
-        for (int h = 0; h < nparts; ++h) more = step(parts[h], k0) || more;
-        if (!more) break;
-    }
-    SA_HIP_CHECK(hipGetLastError());
-    if (two) {
+    });
+    if (split.two) {
         SA_HIP_CHECK(hipEventRecord(ev1, s2));
         SA_HIP_CHECK(hipStreamWaitEvent(s, ev1, 0));
         SA_HIP_CHECK(hipEventDestroy(ev0));
@@ -3155,17 +3099,41 @@ static void ss_factor_generic(hipStream_t s, EigBatch &b, bool sgn, int *neg, in
     }
 }
 
-bool eig_subspace_factor(hipStream_t s, EigBatch &b) {
+// The walk that Options::eig_outer_panels names.  (2 stays a walk of its own: it rounds differently from the blocked one, and
+// on Q2 elasticity it yields the reference's member of the family of valid hierarchies.)
+static void ss_factor_generic(hipStream_t s, EigBatch &b, bool sgn, int *neg, int *info, int bwmax, int keep = 0,
+                              const int *skip = nullptr) {
+    const SsWalk w{b, sgn, neg, info, bwmax, keep, skip, profiler().enabled};
+    if (b.opt.eig_outer_panels >= 8) return ss_factor_blocked<8>(s, w);
+    if (b.opt.eig_outer_panels >= 4) return ss_factor_blocked<4>(s, w);
+    ss_factor_two_panel(s, w);
+}
+
+// ---- eig_subspace_factor, step by step ----
+// What the steps of one factorisation hand each other.
+struct SsFactor {
+    hipStream_t s;
+    EigBatch &b;
+    DBuf<int> info;                  // per matrix: a pivot could not be trusted
+    int bwmax = 0;                   // widest half bandwidth of the batch
+    int win = 0;                     // LDS window of the banded Cholesky (ss_lds_window), 0: the walks through HBM
+    double cb = 0.0;                 // LDS path, profiler: the band read once, the factor written to both triangles
+    bool prof = false;
+    bool reuse = false;              // Options::eig_keep_inertia_factor
+    bool generic_inertia = false;    // the counts came from the in-place walk: bands saved in b.ss_save
+    std::vector<int> h_keep;         // matrices the second factorisation leaves alone
+    int nkeep = 0;                   // ... because they keep the factor of the inertia pass
+    DBuf<int> d_skip;
+    DBuf<int> chol_active;           // LDS path: the matrices the second factorisation still has to do
+    SsFactor(hipStream_t s_, EigBatch &b_) : s(s_), b(b_), info((size_t)b_.count) {}
+    bool generic_reuse() const { return generic_inertia && reuse; }
+};
+
+// 1. half bandwidths of the matrices, on the host too
+static void ss_measure_bands(SsFactor &f) {
+    hipStream_t s = f.s;
+    EigBatch &b = f.b;
     const int nmax = b.max_n;
-    b.ss_nb = 8;      // block of the iteration; 16 where more pairs are wanted than eight vectors reach (decided after the inertia pass)
-    b.h_xpoff.clear();
-    b.h_goff.assign((size_t)b.count + 1, 0);
-    b.h_roff.assign((size_t)b.count + 1, 0);
-    eig_batch_two_stage_buffers(b, 1, false, s);
-    SA_REQUIRE(b.has_window, "few-eigenpairs path: the eigenvalue window must be set before the factorisation");
-    DBuf<int> info((size_t)b.count);
-    info.zero(s);
-    // banded factorisation
     if (!b.has_bw) {          // (the fused assembly has already measured them on the sparse rows)
         if (b.bw.n < (size_t)b.count) b.bw.alloc((size_t)b.count);
         profiler().begin(s);
@@ -3177,124 +3145,107 @@ bool eig_subspace_factor(hipStream_t s, EigBatch &b) {
     b.h_bw.resize((size_t)b.count);
     SA_HIP_CHECK(hipMemcpyAsync(b.h_bw.data(), b.bw.p, sizeof(int) * (size_t)b.count, hipMemcpyDeviceToHost, s));
     SA_HIP_CHECK(hipStreamSynchronize(s));
-    int bwmax = 0;
-    for (int v : b.h_bw) bwmax = std::max(bwmax, v);
-    const int *bws = b.bw.p;
-    b.ss_bwmax = bwmax;
+    for (int v : b.h_bw) f.bwmax = std::max(f.bwmax, v);
+    b.ss_bwmax = f.bwmax;
     if ((b.opt.debug & 1)) {
         int bwmin = nmax;
         for (int v : b.h_bw) bwmin = std::min(bwmin, v);
-        std::fprintf(stderr, "subspace: %d matrices, n max %d, half bandwidth %d .. %d\n", b.count, nmax, b.h_bw.empty() ? nmax : bwmin, bwmax);
+        std::fprintf(stderr, "subspace: %d matrices, n max %d, half bandwidth %d .. %d\n", b.count, nmax, bwmin, f.bwmax);
     }
-    constexpr bool use_lds = true;
-    const bool lds_path = bws && use_lds && bwmax <= 128 - SB;      // the band fits the LDS window: one launch
-    double cb = 0.0;      // the band read once, the factor written to both triangles
-    if (lds_path)
-        for (size_t i = 0; i < b.h_n.size(); ++i) cb += 8.0 * (double)b.h_n[i] * (std::min(b.h_bw[i], b.h_n[i] - 1) + 1);
-    const bool prof = profiler().enabled;
-    auto factor_generic = [&](bool sgn, int *neg) { ss_factor_generic(s, b, sgn, neg, info.p, bws, bwmax); };
-    // ---- certified count: inertia of C - vu I, before the matrices are shifted and overwritten ----
-    // (dsygvx counts by bisection, amg/src/xpacks.cpp:226-268; a subspace iteration alone cannot prove
-    // that no eigenvalue below vu is missing from its block)
-    const bool certify = b.opt.eig_certify != 0;
-    b.h_inertia.clear();
-    b.ss_save = nullptr;
+    f.win = ss_lds_window(f.bwmax);      // the band fits an LDS window: one launch per factorisation
+    if (f.win)
+        for (size_t i = 0; i < b.h_n.size(); ++i) f.cb += 8.0 * (double)b.h_n[i] * (std::min(b.h_bw[i], b.h_n[i] - 1) + 1);
+}
+
+// 2. certified count: inertia of C - vu I, before the matrices are shifted and overwritten
+// (dsygvx counts by bisection, amg/src/xpacks.cpp:226-268; a subspace iteration alone cannot prove
+// that no eigenvalue below vu is missing from its block)
+static void ss_certify_counts(SsFactor &f) {
+    hipStream_t s = f.s;
+    EigBatch &b = f.b;
+    DBuf<int> neg((size_t)b.count);
+    neg.zero(s);
+    if (f.win) {
+        profiler().begin(s);
+        launch_band_lds<true>(s, b, f.win, b.count, neg.p, b.window_vu, nullptr);
+        profiler().end(s, "eig_ss_inertia_lds", f.cb, 0.0);
+        auto h = neg.to_host(s);
+        b.h_inertia.assign(h.begin(), h.end());
+        return;
+    }
+    // in place on the matrices: the band is saved, C - vu I factored, the band restored
+    if (!f.prof) profiler().begin(s);
+    std::vector<int64_t> soff((size_t)b.count + 1, 0);
+    for (int i = 0; i < b.count; ++i) {
+        const int64_t w = std::min(std::max(b.h_bw[i], SB - 1), b.h_n[i] - 1);
+        soff[(size_t)i + 1] = soff[i] + (int64_t)b.h_n[i] * (2 * w + 1);
+    }
+    DBuf<int64_t> d_soff;
+    d_soff.from_host(soff, s);
+    b.ss_save = eig_arena_bandsave(b, (size_t)soff[b.count] + 1);
+    b.ss_soff = std::move(d_soff);
+    launch_band_copy<false>(s, b);
+    hipLaunchKernelGGL(ss_shift_kernel, dim3(b.count), dim3(256), 0, s, b.n.p, b.moff.p, b.W.p, b.window_vu);
     // Wide-band matrices (coarse levels): a certified count of 0 means that the inertia pass met positive pivots
     // only, i.e. it WAS the Cholesky factorisation of C - vu I -- and vu is the best shift such a matrix can get
     // (its one wanted pair is the smallest).  Those matrices keep that factor: no restore, no second factorisation
     // (Options::eig_keep_inertia_factor = 0: factor twice as before).
-    const bool reuse = b.opt.eig_keep_inertia_factor != 0;
-    bool generic_inertia = false;
-    if (certify) {
-        DBuf<int> neg((size_t)b.count);
-        neg.zero(s);
-        if (lds_path) {
-            profiler().begin(s);
-            auto go2 = [&](auto kern, int win) {
-                SA_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bc2_lds_bytes(win)));
-                hipLaunchKernelGGL(kern, dim3(b.count), dim3(BC_NT), bc2_lds_bytes(win), s, b.n.p, b.moff.p, b.W.p, bws, neg.p,
-                                   b.window_vu, (const int *)nullptr);
-            };
-            if (bwmax <= 67 - SB) go2(chol_band_lds2_kernel<67, true>, 67);
-            else if (bwmax <= 68 - SB) go2(chol_band_lds2_kernel<68, true>, 68);
-            else if (bwmax <= 80 - SB) go2(chol_band_lds2_kernel<80, true>, 80);
-            else go2(chol_band_lds2_kernel<128, true>, 128);
-            SA_HIP_CHECK(hipGetLastError());
-            profiler().end(s, "eig_ss_inertia_lds", cb, 0.0);
-            auto h = neg.to_host(s);
-            b.h_inertia.assign(h.begin(), h.end());
-        } else {
-            // in place on the matrices: the band is saved, C - vu I factored, the band restored
-            if (!prof) profiler().begin(s);
-            std::vector<int64_t> soff((size_t)b.count + 1, 0);
-            for (int i = 0; i < b.count; ++i) {
-                const int64_t w = std::min(std::max(b.h_bw.empty() ? b.h_n[i] - 1 : b.h_bw[i], SB - 1), b.h_n[i] - 1);
-                soff[(size_t)i + 1] = soff[i] + (int64_t)b.h_n[i] * (2 * w + 1);
-            }
-            DBuf<int64_t> d_soff;
-            d_soff.from_host(soff, s);
-            double *save = eig_arena_bandsave(b, (size_t)soff[b.count] + 1);
-            b.ss_save = save;
-            const int ny = std::max(1, std::min(64, 8192 / std::max(1, b.count)));
-            hipLaunchKernelGGL(band_copy_kernel<false>, dim3(b.count, ny), dim3(256), 0, s, b.n.p, b.moff.p, b.W.p, b.bw.p, d_soff.p, save);
-            hipLaunchKernelGGL(ss_shift_kernel, dim3(b.count), dim3(256), 0, s, b.n.p, b.moff.p, b.W.p, b.window_vu);
-            // (reuse: the factor is written back; the bands are restored further down, once the counts say which
-            // matrices keep it)
-            ss_factor_generic(s, b, true, neg.p, info.p, bws, bwmax, reuse ? 1 : 0);
-            if (!reuse)
-                hipLaunchKernelGGL(band_copy_kernel<true>, dim3(b.count, ny), dim3(256), 0, s, b.n.p, b.moff.p, b.W.p, b.bw.p, d_soff.p, save);
-            generic_inertia = true;
-            SA_HIP_CHECK(hipGetLastError());
-            b.ss_soff = std::move(d_soff);
-            if (!prof) profiler().end(s, "eig_ss_inertia", 0.0, 0.0);
-            auto h = neg.to_host(s);
-            auto hi = info.to_host(s);
-            b.h_inertia.assign(h.begin(), h.end());
-            for (int i = 0; i < b.count; ++i) if (hi[i]) b.h_inertia[i] = -1;
-            info.zero(s);
-        }
-    }
+    // (reuse: the factor is written back; the bands are restored further down, once the counts say which
+    // matrices keep it)
+    ss_factor_generic(s, b, true, neg.p, f.info.p, f.bwmax, f.reuse ? 1 : 0);
+    if (!f.reuse) launch_band_copy<true>(s, b);
+    f.generic_inertia = true;
+    SA_HIP_CHECK(hipGetLastError());
+    if (!f.prof) profiler().end(s, "eig_ss_inertia", 0.0, 0.0);
+    auto h = neg.to_host(s);
+    auto hi = f.info.to_host(s);
+    b.h_inertia.assign(h.begin(), h.end());
+    for (int i = 0; i < b.count; ++i) if (hi[i]) b.h_inertia[i] = -1;
+    f.info.zero(s);
+}
 
-    // a matrix with more wanted pairs than the block holds, or without a certificate, goes to the dense path:
-    // known here, before the second factorisation and the iterations are spent on it.  It goes ALONE (h_bad) as
-    // long as such matrices are few: one uncertifiable agglomerate must not send the other 14 000 of its chunk
-    // through the dense path.
+// 3. width of the iteration block, and the matrices the path cannot do.  Returns false when those are too many.
+// A matrix with more wanted pairs than the block holds, or without a certificate, goes to the dense path:
+// known here, before the second factorisation and the iterations are spent on it.
+// The block of SIXTEEN vectors (round 4): wide-band matrices -- their solves stream the factor through HBM and work on
+// matrix-core tiles that are 16 columns wide whatever the block holds -- take it as soon as one of them wants more than the
+// six pairs a block of eight converges without locking (config 4 with 8 x 8 x 4-AE coarse blocks: eight wanted pairs, 1 035 ->
+// 799 ms per step); small matrices (right-hand sides in LDS beside the band: no room for sixteen) keep the block of eight and
+// its lock up to twelve wanted pairs, and take the block of sixteen -- through the streaming solves -- for 13 and 14.
+// With six pairs or fewer the block of eight stays: measured on the headline's level 1 (two wanted pairs), sixteen vectors
+// need 13 instead of 16 iterations of 1.4 instead of 1.3 ms -- nothing --, and a different basis of a degenerate eigenspace
+// (the six rigid-body modes of config 5) is a different member of the family of valid hierarchies.
+static bool ss_choose_block(SsFactor &f) {
+    EigBatch &b = f.b;
     b.h_bad.assign((size_t)b.count, 0);
     b.nbad = 0;
-    auto mark_bad = [&](int i) { if (!b.h_bad[(size_t)i]) { b.h_bad[(size_t)i] = 1; ++b.nbad; } };
-    auto too_many_bad = [&]() { return (long)b.nbad * 10 > (long)b.count; };
-    // The block of SIXTEEN vectors (round 4): wide-band matrices -- their solves stream the factor through HBM and work on
-    // matrix-core tiles that are 16 columns wide whatever the block holds -- take it as soon as one of them wants more than the
-    // six pairs a block of eight converges without locking (config 4 with 8 x 8 x 4-AE coarse blocks: eight wanted pairs, 1 035 ->
-    // 799 ms per step); small matrices (right-hand sides in LDS beside the band: no room for sixteen) keep the block of eight and
-    // its lock up to twelve wanted pairs, and take the block of sixteen -- through the streaming solves -- for 13 and 14.
-    // With six pairs or fewer the block of eight stays: measured on the headline's level 1 (two wanted pairs), sixteen vectors
-    // need 13 instead of 16 iterations of 1.4 instead of 1.3 ms -- nothing --, and a different basis of a degenerate eigenspace
-    // (the six rigid-body modes of config 5) is a different member of the family of valid hierarchies.
-    {
-        int maxwant = 0;
-        for (int v : b.h_inertia) maxwant = std::max(maxwant, v);
-        if (maxwant <= 16 - 2 && ((nmax > 1280 && maxwant > SS_B - 2) || maxwant > SS_WANT_MAX)) b.ss_nb = 16;
-    }
+    int maxwant = 0;
+    for (int v : b.h_inertia) maxwant = std::max(maxwant, v);
+    b.ss_nb = ss_block_width(b.max_n, maxwant);
     for (size_t i = 0; i < b.h_inertia.size(); ++i)
-        if (b.h_inertia[i] > (b.ss_nb == 16 ? 16 - 2 : SS_WANT_MAX) || b.h_inertia[i] < 0) {
+        if (b.h_inertia[i] > ss_want_limit(b.ss_nb) || b.h_inertia[i] < 0) {
             SA_REQUIRE(!b.opt.eig_strict, "few-eigenpairs path: a matrix has more wanted pairs than the block holds, or no certificate (strict mode)");
-            mark_bad((int)i);
+            mark_bad(b, (int)i);
         }
     if (b.opt.eig_force_fallback > 0) {      // tests: every k-th matrix takes the per-matrix fallback
         const int every = b.opt.eig_force_fallback;
-        for (int i = 3; every > 0 && i < b.count; i += every) mark_bad(i);
+        for (int i = 3; every > 0 && i < b.count; i += every) mark_bad(b, i);
     }
-    if (too_many_bad()) return false;
-    if (!b.h_inertia.empty()) b.inertia.from_host(b.h_inertia, s);
-    // ---- C - sigma I = L L^T ----
-    // The iteration converges like (lambda_i - sigma) / (lambda_9 - sigma), so the shift belongs just below the
-    // wanted eigenvalues.  C is positive semi-definite (interior agglomerates: exactly singular), which leaves
-    // sigma < 0 in general; but a certified count of 0 says that every eigenvalue lies above vu, and the one
-    // pair the "at least one" rule then asks for is the smallest: those matrices are shifted to just below vu
-    // (agglomerates on an essential boundary, most agglomerates of a coarse level: 17 -> 9 iterations).
-    std::vector<int> h_keep((size_t)b.count, 0);
-    int nkeep = 0;
+    if (too_many_bad(b)) return false;
+    if (!b.h_inertia.empty()) b.inertia.from_host(b.h_inertia, f.s);
+    return true;
+}
+
+// 4. the shift of every matrix, and which matrices keep the factor of the inertia pass (their bands are not restored)
+// The iteration converges like (lambda_i - sigma) / (lambda_9 - sigma), so the shift belongs just below the
+// wanted eigenvalues.  C is positive semi-definite (interior agglomerates: exactly singular), which leaves
+// sigma < 0 in general; but a certified count of 0 says that every eigenvalue lies above vu, and the one
+// pair the "at least one" rule then asks for is the smallest: those matrices are shifted to just below vu
+// (agglomerates on an essential boundary, most agglomerates of a coarse level: 17 -> 9 iterations).
+static void ss_choose_shifts(SsFactor &f) {
+    hipStream_t s = f.s;
+    EigBatch &b = f.b;
+    f.h_keep.assign((size_t)b.count, 0);
     {
         const double vu = b.window_vu;
         const double neg = -std::min(1e-3, std::max(1e-7, std::fabs(vu) / 30.0));
@@ -3302,74 +3253,78 @@ bool eig_subspace_factor(hipStream_t s, EigBatch &b) {
         for (int i = 0; i < b.count && !b.h_inertia.empty(); ++i)
             if (b.h_inertia[i] == 0 && vu > 0.0) {
                 sg[i] = vu - std::max(1e-6, 1e-3 * vu);
-                if (generic_inertia && reuse && !b.h_bad[i]) { sg[i] = vu; h_keep[(size_t)i] = 1; ++nkeep; }
+                if (f.generic_reuse() && !b.h_bad[i]) { sg[i] = vu; f.h_keep[(size_t)i] = 1; ++f.nkeep; }
             }
         b.ss_sigma.from_host(sg, s);
         b.h_sigma = sg;
     }
-    DBuf<int> d_skip;
-    if (generic_inertia && reuse) {       // the bands of the matrices that do not keep the inertia pass's factor
-        d_skip.from_host(h_keep, s);
-        const int ny = std::max(1, std::min(64, 8192 / std::max(1, b.count)));
-        if (nkeep < b.count)
-            hipLaunchKernelGGL(band_copy_kernel<true>, dim3(b.count, ny), dim3(256), 0, s, b.n.p, b.moff.p, b.W.p, b.bw.p,
-                               b.ss_soff.p, b.ss_save, d_skip.p);
-        if (nkeep > 0)
-            hipLaunchKernelGGL(ss_keep_transpose_kernel, dim3(b.count, ny), dim3(256), 0, s, b.n.p, b.moff.p, b.W.p, bws, d_skip.p);
+    if (f.generic_reuse()) {       // the bands of the matrices that do not keep the inertia pass's factor
+        f.d_skip.from_host(f.h_keep, s);
+        if (f.nkeep < b.count) launch_band_copy<true>(s, b, f.d_skip.p);
+        if (f.nkeep > 0)
+            hipLaunchKernelGGL(ss_keep_transpose_kernel, dim3(b.count, ss_band_copy_ny(b.count)), dim3(256), 0, s, b.n.p, b.moff.p, b.W.p,
+                               b.bw.p, f.d_skip.p);
         SA_HIP_CHECK(hipGetLastError());
     }
-    // ---- matrices that are finished before they are factored ----
-    // certified count 1 and x0 = D^1/2 1 already an eigenvector to the acceptance tolerance (ss_nullcheck_kernel:
-    // one pass over the band): they skip the second factorisation, the solves and the Rayleigh-Ritz steps, which
-    // then run on a dense list of the others (85 % of the level-0 agglomerates of the 256^3 problem are of this
-    // kind; the iteration accepted them after its first step anyway, at the price of a factorisation and two
-    // solves each).  Options::eig_nullcheck = 0 switches the shortcut off.
+}
+
+// 5. matrices that are finished before they are factored
+// certified count 1 and x0 = D^1/2 1 already an eigenvector to the acceptance tolerance (ss_nullcheck_kernel:
+// one pass over the band): they skip the second factorisation, the solves and the Rayleigh-Ritz steps, which
+// then run on a dense list of the others (85 % of the level-0 agglomerates of the 256^3 problem are of this
+// kind; the iteration accepted them after its first step anyway, at the price of a factorisation and two
+// solves each).  Options::eig_nullcheck = 0 switches the shortcut off.
+static void ss_known_null_vectors(SsFactor &f) {
+    hipStream_t s = f.s;
+    EigBatch &b = f.b;
     b.h_pre.clear();
-    DBuf<int> chol_active;
-    int nchol = b.count;
-    bool use_chol_list = false;
-    const bool nullcheck = b.opt.eig_nullcheck != 0;
-    const bool generic_reuse = generic_inertia && reuse;
-    if ((lds_path || generic_reuse) && nullcheck && !b.h_inertia.empty()) {
-        profiler().begin(s);
-        b.pre.alloc((size_t)b.count);
-        b.pre_val.alloc(2 * (size_t)b.count);
-        hipLaunchKernelGGL(ss_nullcheck_kernel, dim3(b.count), dim3(NC_NT), sizeof(double) * (size_t)nmax, s, b.n.p, b.moff.p,
-                           b.voff.p, b.W.p, b.dis.p, b.has_perm ? b.perm.p : nullptr, bws, b.inertia.p, b.window_vu, b.ss_tol,
-                           b.pre.p, b.pre_val.p, b.has_x0c ? b.x0c.p : (const double *)nullptr);
-        SA_HIP_CHECK(hipGetLastError());
-        profiler().end(s, "eig_ss_nullcheck", cb, 0.0);
-        auto hp = b.pre.to_host(s);
-        b.h_pre.assign(hp.begin(), hp.end());
-        if ((b.opt.debug & 1) && !lds_path) {
-            auto hv = b.pre_val.to_host(s);
-            int shown = 0;
-            for (int i = 0; i < b.count && shown < 12; ++i)
-                if (b.h_inertia[i] == 1) {
-                    std::fprintf(stderr, "  nullcheck matrix %d: accepted %d, Rayleigh quotient %.3e, %s %.3e\n", i, hp[i], hv[2 * (size_t)i],
-                                 hp[i] ? "1/|x0|" : "residual", std::fabs(hv[2 * (size_t)i + 1]));
-                    ++shown;
-                }
-        }
+    if (!((f.win || f.generic_reuse()) && b.opt.eig_nullcheck != 0 && !b.h_inertia.empty())) return;
+    profiler().begin(s);
+    b.pre.alloc((size_t)b.count);
+    b.pre_val.alloc(2 * (size_t)b.count);
+    hipLaunchKernelGGL(ss_nullcheck_kernel, dim3(b.count), dim3(NC_NT), sizeof(double) * (size_t)b.max_n, s, b.n.p, b.moff.p,
+                       b.voff.p, b.W.p, b.dis.p, b.has_perm ? b.perm.p : nullptr, b.bw.p, b.inertia.p, b.window_vu, b.ss_tol,
+                       b.pre.p, b.pre_val.p, b.has_x0c ? b.x0c.p : (const double *)nullptr);
+    SA_HIP_CHECK(hipGetLastError());
+    profiler().end(s, "eig_ss_nullcheck", f.cb, 0.0);
+    auto hp = b.pre.to_host(s);
+    b.h_pre.assign(hp.begin(), hp.end());
+    if ((b.opt.debug & 1) && !f.win) {
+        auto hv = b.pre_val.to_host(s);
+        int shown = 0;
+        for (int i = 0; i < b.count && shown < 12; ++i)
+            if (b.h_inertia[i] == 1) {
+                std::fprintf(stderr, "  nullcheck matrix %d: accepted %d, Rayleigh quotient %.3e, %s %.3e\n", i, hp[i], hv[2 * (size_t)i],
+                             hp[i] ? "1/|x0|" : "residual", std::fabs(hv[2 * (size_t)i + 1]));
+                ++shown;
+            }
     }
-    if (lds_path && (!b.h_pre.empty() || b.nbad)) {       // the matrices the second factorisation still has to do
+}
+
+// 6. C - sigma I = L L^T for the matrices that still need it
+static void ss_second_factorisation(SsFactor &f) {
+    hipStream_t s = f.s;
+    EigBatch &b = f.b;
+    int nchol = b.count;        // LDS path: matrices the second factorisation still has to do (f.chol_active)
+    bool use_chol_list = false;
+    if (f.win && (!b.h_pre.empty() || b.nbad)) {
         std::vector<int> act;
         for (int i = 0; i < b.count; ++i)
             if (!(b.h_pre.empty() ? 0 : b.h_pre[i]) && !b.h_bad[i]) act.push_back(i);
         nchol = (int)act.size();
-        if (nchol) chol_active.from_host(act, s);
+        if (nchol) f.chol_active.from_host(act, s);
         use_chol_list = true;
     }
-    int nfactor = b.count;      // generic path: matrices the second factorisation still has to do
-    if (generic_reuse) {
+    int nfactor = b.count;      // walks through HBM: matrices the second factorisation still has to do
+    if (f.generic_reuse()) {
         std::vector<double> shifts(b.h_sigma);
         nfactor = 0;
         for (int i = 0; i < b.count; ++i) {
-            if (!b.h_pre.empty() && b.h_pre[i]) h_keep[(size_t)i] = 1;
-            if (b.h_bad[i]) h_keep[(size_t)i] = 1;
-            if (h_keep[(size_t)i]) shifts[(size_t)i] = 0.0; else ++nfactor;
+            if (!b.h_pre.empty() && b.h_pre[i]) f.h_keep[(size_t)i] = 1;
+            if (b.h_bad[i]) f.h_keep[(size_t)i] = 1;
+            if (f.h_keep[(size_t)i]) shifts[(size_t)i] = 0.0; else ++nfactor;
         }
-        d_skip.from_host(h_keep, s);
+        f.d_skip.from_host(f.h_keep, s);
         if (nfactor) {
             DBuf<double> d_shifts;
             d_shifts.from_host(shifts, s);
@@ -3378,380 +3333,425 @@ bool eig_subspace_factor(hipStream_t s, EigBatch &b) {
         }
         if ((b.opt.debug & 1))
             std::fprintf(stderr, "subspace: %d of %d wide-band matrices keep the factor of the inertia pass, %d are factored again\n",
-                         nkeep, b.count, nfactor);
+                         f.nkeep, b.count, nfactor);
     } else
-    hipLaunchKernelGGL(ss_shift_kernel, dim3(b.count), dim3(256), 0, s, b.n.p, b.moff.p, b.W.p, 0.0, b.ss_sigma.p);
-    if (lds_path) {
+        hipLaunchKernelGGL(ss_shift_kernel, dim3(b.count), dim3(256), 0, s, b.n.p, b.moff.p, b.W.p, 0.0, b.ss_sigma.p);
+    if (f.win) {
         profiler().begin(s);
-        auto go2 = [&](auto kern, int win) {
-            if (!nchol) return;
-            SA_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bc2_lds_bytes(win)));
-            hipLaunchKernelGGL(kern, dim3(nchol), dim3(BC_NT), bc2_lds_bytes(win), s, b.n.p, b.moff.p, b.W.p, bws, info.p, 0.0,
-                               use_chol_list ? chol_active.p : (const int *)nullptr);
-        };
-        if (bwmax <= 67 - SB) go2(chol_band_lds2_kernel<67, false>, 67);
-        else if (bwmax <= 68 - SB) go2(chol_band_lds2_kernel<68, false>, 68);
-        else if (bwmax <= 80 - SB) go2(chol_band_lds2_kernel<80, false>, 80);
-        else go2(chol_band_lds2_kernel<128, false>, 128);
-        SA_HIP_CHECK(hipGetLastError());
-        profiler().end(s, "eig_ss_chol_lds", 3.0 * cb, 0.0);
+        if (nchol) launch_band_lds<false>(s, b, f.win, nchol, f.info.p, 0.0, use_chol_list ? f.chol_active.p : (const int *)nullptr);
+        profiler().end(s, "eig_ss_chol_lds", 3.0 * f.cb, 0.0);
     } else {
-        if (!prof) profiler().begin(s);
-        if (!generic_reuse) factor_generic(false, nullptr);
-        else if (nfactor) ss_factor_generic(s, b, false, nullptr, info.p, bws, bwmax, 0, d_skip.p);
-        if (!prof) profiler().end(s, "eig_ss_cholesky", 0.0, 0.0);
+        if (!f.prof) profiler().begin(s);
+        if (!f.generic_reuse()) ss_factor_generic(s, b, false, nullptr, f.info.p, f.bwmax);
+        else if (nfactor) ss_factor_generic(s, b, false, nullptr, f.info.p, f.bwmax, 0, f.d_skip.p);
+        if (!f.prof) profiler().end(s, "eig_ss_cholesky", 0.0, 0.0);
     }
-    auto h = info.to_host(s);
-    for (int i = 0; i < b.count; ++i)
-        if (h[i] && !b.h_bad[i]) {         // a non-positive pivot: that matrix alone
-            if ((b.opt.debug & 1))
-                std::fprintf(stderr, "subspace: non-positive pivot in matrix %d (n %d, band %d, inertia %d, sigma %g)\n", i, b.h_n[i],
-                             b.h_bw.empty() ? -1 : b.h_bw[i], b.h_inertia.empty() ? -2 : b.h_inertia[i], b.h_sigma[i]);
-            SA_REQUIRE(!b.opt.eig_strict, "few-eigenpairs path: non-positive pivot (strict mode)");
-            mark_bad(i);
-        }
-    return !too_many_bad();
 }
 
-// Subspace iteration; fills b.h_m / b.m.  Returns false when some matrix needs the dense path.
-bool eig_subspace_iterate(hipStream_t s, EigBatch &b, double vu) {
-    DBuf<int> state((size_t)b.count);
-    if (b.h_bad.size() != (size_t)b.count) { b.h_bad.assign((size_t)b.count, 0); b.nbad = 0; }
-    {       // matrices already given to the dense path start as "failed": no kernel touches them
-        std::vector<int> st0((size_t)b.count, 0);
-        for (int i = 0; i < b.count; ++i) if (b.h_bad[i]) st0[i] = 2;
-        state.from_host(st0, s);
-    }
-    auto mark_bad = [&](int i) { if (!b.h_bad[(size_t)i]) { b.h_bad[(size_t)i] = 1; ++b.nbad; } };
-    auto too_many_bad = [&]() { return (long)b.nbad * 10 > (long)b.count; };
-    double *X = b.Xbuf.p, *Z = b.Vpk2.p, *mu = b.d.p;     // d: rows >= SS_B per matrix is checked by the caller
-    const int NB = b.ss_nb;
-    // (kernels of the block are templates on its width)
-    auto with_nb = [&](auto f) { if (NB == 16) f(std::integral_constant<int, 16>()); else f(std::integral_constant<int, 8>()); };
-    DBuf<double> mubuf((size_t)b.count * NB);
-    mu = mubuf.p;
-    DBuf<double> slow_hist((size_t)b.count * 4);       // bound of the slowest wanted pair, last four iterations
-    slow_hist.zero(s);
-    // wide-band matrices with a saved band: a matrix (certified count 0) that converges too slowly may ask once
-    // for a new shift (state bit 2, ss_rr_kernel); the host then restores the bands, shifts that matrix to just
-    // below its smallest Ritz value and factors the batch again
-    constexpr bool reshift_env = true;
-    const bool reshift_on = reshift_env && b.max_n > 1280 && b.ss_save && !b.h_inertia.empty() && b.h_sigma.size() == (size_t)b.count;
-    DBuf<int> reshift_ok;
-    std::vector<int> h_reshift_ok((size_t)b.count, 1);
-    std::vector<double> reshift_prev((size_t)b.count, 0.0), reshift_margin((size_t)b.count, 0.0);
-    if (reshift_on) reshift_ok.from_host(h_reshift_ok, s);
-    const bool prof = profiler().enabled;
-    const int *bws = b.h_bw.empty() ? nullptr : b.bw.p;
-    // matrices with seven to twelve wanted pairs: the first six are locked when they have converged (ss_lock_kernel)
-    std::vector<int> h_ndefl((size_t)b.count, 0);
-    bool any_lock = false;
-    for (int i = 0; i < b.count && !b.h_inertia.empty() && NB == 8; ++i) any_lock = any_lock || (!b.h_bad[i] && b.h_inertia[i] > SS_B - 2);
-    DBuf<int> it0;
-    b.ss_has_lock = false;
-    if (any_lock) {
-        b.ss_ndefl.alloc((size_t)b.count);
-        b.ss_ndefl.zero(s);
-        it0.alloc((size_t)b.count);
-        it0.zero(s);
-        b.ss_lock_mu.alloc((size_t)b.count * SS_LOCK_PITCH);
-        b.ss_Vlock.alloc((size_t)b.h_voff[b.count] * SS_LOCK_PITCH);
-        b.ss_has_lock = true;
-    }
-    if ((b.opt.debug & 1) && b.max_n > 1280 && !b.h_inertia.empty()) {
-        std::fprintf(stderr, "subspace: certified counts (bad):");
-        for (int i = 0; i < b.count; ++i) std::fprintf(stderr, " %d%s", b.h_inertia[i], b.h_bad[i] ? "*" : "");
-        std::fprintf(stderr, "\n");
-    }
-    if (!prof) profiler().begin(s);
-    with_nb([&](auto nb) {
-        hipLaunchKernelGGL(ss_init_kernel<decltype(nb)::value>, dim3(b.count), dim3(256), 0, s, b.n.p, b.voff.p, b.dis.p,
-                           b.has_perm ? b.perm.p : nullptr, X, b.has_x0c ? b.x0c.p : (const double *)nullptr);
-    });
-    bool done = false, failed = false;
-    std::vector<int> hstate;
+// 7. a non-positive pivot: that matrix alone.  Returns false when the batch has to take the dense path.
+static bool ss_collect_pivots(SsFactor &f) {
+    EigBatch &b = f.b;
+    auto h = f.info.to_host(f.s);
+    for (int i = 0; i < b.count; ++i)
+        if (h[i] && !b.h_bad[i]) {
+            if ((b.opt.debug & 1))
+                std::fprintf(stderr, "subspace: non-positive pivot in matrix %d (n %d, band %d, inertia %d, sigma %g)\n", i, b.h_n[i],
+                             b.h_bw[i], b.h_inertia.empty() ? -2 : b.h_inertia[i], b.h_sigma[i]);
+            SA_REQUIRE(!b.opt.eig_strict, "few-eigenpairs path: non-positive pivot (strict mode)");
+            mark_bad(b, i);
+        }
+    return !too_many_bad(b);
+}
+
+// C - sigma I = L L^T for every matrix of the batch (in place, L below / L^T above the diagonal), behind the certified
+// counts.  Returns false when the batch has to take the dense path.
+bool eig_subspace_factor(hipStream_t s, EigBatch &b) {
+    b.ss_nb = 8;      // block of the iteration; 16 where more pairs are wanted than eight vectors reach (decided after the inertia pass)
+    b.h_xpoff.clear();
+    b.h_goff.assign((size_t)b.count + 1, 0);
+    b.h_roff.assign((size_t)b.count + 1, 0);
+    eig_batch_two_stage_buffers(b, 1, false, s);
+    SA_REQUIRE(b.has_window, "few-eigenpairs path: the eigenvalue window must be set before the factorisation");
+    SsFactor f(s, b);
+    f.info.zero(s);
+    f.prof = profiler().enabled;
+    f.reuse = b.opt.eig_keep_inertia_factor != 0;
+    ss_measure_bands(f);
+    b.h_inertia.clear();
+    b.ss_save = nullptr;
+    if (b.opt.eig_certify != 0) ss_certify_counts(f);
+    if (!ss_choose_block(f)) return false;
+    ss_choose_shifts(f);
+    ss_known_null_vectors(f);
+    ss_second_factorisation(f);
+    return ss_collect_pivots(f);
+}
+
+// ---- eig_subspace_iterate, step by step ----
+// The loop state of one batch's iteration.
+struct SsIter {
+    hipStream_t s;
+    EigBatch &b;
+    double vu;
+    int NB;                          // width of the block (b.ss_nb)
+    bool prof;
+    int max_iter = SS_MAX_ITER;
+    double *X, *Z;                   // the block, and its image under the solves
+    DBuf<int> state;                 // per matrix, see ss_rr_kernel
+    std::vector<int> hstate;         // ... as last read back
+    DBuf<double> mubuf;              // Ritz values - shift, NB per matrix, ascending
+    DBuf<double> slow_hist;          // bound of the slowest wanted pair, last four iterations
     // Only the matrices that are still iterating are launched, through a dense index list: accepted ones
     // would exit at once, but the survivors (agglomerates on the domain boundary: every 64th id, runs of 64)
     // would then sit on a few CUs -- block ids map to XCDs and CUs round-robin -- and a launch with 6 % of
     // the matrices active took as long as a full one.
     std::vector<int> h_active;
-    h_active.reserve((size_t)b.count);
+    DBuf<int> active;
+    int nact = 0;
+    // matrices with seven to twelve wanted pairs: the first six are locked when they have converged (ss_lock_kernel)
+    bool any_lock = false;
+    std::vector<int> h_ndefl;        // pairs locked so far
+    DBuf<int> it0;                   // iteration at which a matrix's block was last started
+    // wide-band matrices with a saved band: a matrix (certified count 0) that converges too slowly may ask once
+    // for a new shift (state bit 2, ss_rr_kernel); the host then restores the bands, shifts that matrix to just
+    // below its smallest Ritz value and factors the batch again
+    bool reshift_on = false;
+    DBuf<int> reshift_ok;
+    std::vector<int> h_reshift_ok;
+    std::vector<double> reshift_prev, reshift_margin;
+    bool done = false, failed = false;
+    SsIter(hipStream_t s_, EigBatch &b_, double vu_) : s(s_), b(b_), vu(vu_), NB(b_.ss_nb), prof(profiler().enabled), state((size_t)b_.count) {}
+    void read_state() { auto t = state.to_host(s); hstate.assign(t.begin(), t.end()); }
+    void send_active() {
+        nact = (int)h_active.size();
+        if (nact) SA_HIP_CHECK(hipMemcpyAsync(active.p, h_active.data(), sizeof(int) * (size_t)nact, hipMemcpyHostToDevice, s));
+    }
+};
+
+// 1. states, buffers, the start block, the first active list
+static void ss_iter_start(SsIter &it) {
+    hipStream_t s = it.s;
+    EigBatch &b = it.b;
+    const int NB = it.NB;
+    if (b.h_bad.size() != (size_t)b.count) { b.h_bad.assign((size_t)b.count, 0); b.nbad = 0; }
+    {       // matrices already given to the dense path start as "failed": no kernel touches them
+        std::vector<int> st0((size_t)b.count, 0);
+        for (int i = 0; i < b.count; ++i) if (b.h_bad[i]) st0[i] = 2;
+        it.state.from_host(st0, s);
+    }
+    it.X = b.Xbuf.p;
+    it.Z = b.Vpk2.p;
+    it.mubuf.alloc((size_t)b.count * NB);
+    it.slow_hist.alloc((size_t)b.count * 4);
+    it.slow_hist.zero(s);
+    it.reshift_on = b.max_n > 1280 && b.ss_save && !b.h_inertia.empty() && b.h_sigma.size() == (size_t)b.count;
+    it.h_reshift_ok.assign((size_t)b.count, 1);
+    it.reshift_prev.assign((size_t)b.count, 0.0);
+    it.reshift_margin.assign((size_t)b.count, 0.0);
+    if (it.reshift_on) it.reshift_ok.from_host(it.h_reshift_ok, s);
+    it.h_ndefl.assign((size_t)b.count, 0);
+    for (int i = 0; i < b.count && !b.h_inertia.empty() && NB == 8; ++i) it.any_lock = it.any_lock || (!b.h_bad[i] && b.h_inertia[i] > SS_B - 2);
+    b.ss_has_lock = false;
+    if (it.any_lock) {
+        b.ss_ndefl.alloc((size_t)b.count);
+        b.ss_ndefl.zero(s);
+        it.it0.alloc((size_t)b.count);
+        it.it0.zero(s);
+        b.ss_lock_mu.alloc((size_t)b.count * SS_LOCK_PITCH);
+        b.ss_Vlock.alloc((size_t)b.h_voff[b.count] * SS_LOCK_PITCH);
+        b.ss_has_lock = true;
+    }
+    it.max_iter = it.any_lock ? 2 * SS_MAX_ITER : SS_MAX_ITER;      // (a locked matrix starts a second run)
+    if ((b.opt.debug & 1) && b.max_n > 1280 && !b.h_inertia.empty()) {
+        std::fprintf(stderr, "subspace: certified counts (bad):");
+        for (int i = 0; i < b.count; ++i) std::fprintf(stderr, " %d%s", b.h_inertia[i], b.h_bad[i] ? "*" : "");
+        std::fprintf(stderr, "\n");
+    }
+    if (!it.prof) profiler().begin(s);
+    with_nb(NB, [&](auto nb) {
+        hipLaunchKernelGGL(ss_init_kernel<decltype(nb)::value>, dim3(b.count), dim3(256), 0, s, b.n.p, b.voff.p, b.dis.p,
+                           b.has_perm ? b.perm.p : nullptr, it.X, b.has_x0c ? b.x0c.p : (const double *)nullptr);
+    });
+    it.h_active.reserve((size_t)b.count);
     for (int i = 0; i < b.count; ++i)
-        if ((b.h_pre.empty() || !b.h_pre[i]) && !b.h_bad[i]) h_active.push_back(i);
+        if ((b.h_pre.empty() || !b.h_pre[i]) && !b.h_bad[i]) it.h_active.push_back(i);
     if (!b.h_pre.empty())       // finished before the factorisation (eig_subspace_factor): unit vector, Ritz value, state
-        with_nb([&](auto nb) {
+        with_nb(NB, [&](auto nb) {
             hipLaunchKernelGGL(ss_preaccept_kernel<decltype(nb)::value>, dim3(b.count), dim3(256), 0, s, b.n.p, b.voff.p, b.pre.p, b.pre_val.p,
-                               b.ss_sigma.p, X, mu, state.p);
+                               b.ss_sigma.p, it.X, it.mubuf.p, it.state.p);
         });
-    DBuf<int> active((size_t)b.count);
-    int nact = (int)h_active.size();
-    if (nact) SA_HIP_CHECK(hipMemcpyAsync(active.p, h_active.data(), sizeof(int) * (size_t)nact, hipMemcpyHostToDevice, s));
+    it.active.alloc((size_t)b.count);
+    it.send_active();
     SA_HIP_CHECK(hipStreamSynchronize(s));
-    const int max_iter = any_lock ? 2 * SS_MAX_ITER : SS_MAX_ITER;      // (a locked matrix starts a second run)
-    for (int iter = 0; iter < max_iter && !done; ++iter) {
-        if (nact == 0) {                 // every matrix was finished before the factorisation
-            auto t = state.to_host(s);
-            hstate.assign(t.begin(), t.end());
-            done = true;
-            break;
-        }
-        if (prof) profiler().begin(s);
-        const size_t xl_bytes = sizeof(double) * (size_t)b.max_n * XLP + 64;
-        if (b.max_n <= 1280 && NB == 8) {
-            // narrow bands: the deep-prefetch kernel; wider ones: the plain kernel, 256 or 512 threads by the band
-            const int rows = std::min(b.max_n, b.ss_bwmax + SB);     // rows a block step updates
-            auto go = [&](auto kern, int nt) {
-                SA_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-                hipLaunchKernelGGL(kern, dim3(nact), dim3(nt), xl_bytes, s, b.n.p, b.moff.p, b.voff.p, b.W.p, X, Z, state.p, bws, active.p);
-            };
-            if (rows <= 128) go(ss_solve_lds_pf_kernel<128>, 128);
-            else if (rows <= 256) go(ss_solve_lds_kernel<256>, 256);      // (>= SB * SB threads: the block loads)
-            else go(ss_solve_lds_kernel<512>, 512);
-        } else {
-        // Z <- X for the matrices still iterating (the whole buffer used to be copied every iteration: 0.6 s of
-        // config 5's 23 s, where most matrices of a chunk are done long before the last one)
-        with_nb([&](auto nb) {
-            hipLaunchKernelGGL(ss_copy_active_kernel<decltype(nb)::value>, dim3(nact, std::max(1, std::min(16, b.max_n / 256))), dim3(256), 0, s, b.n.p,
-                               b.voff.p, active.p, X, Z);
-        });
-        constexpr bool no_win = false;
-        const int wr = (std::min(b.max_n, bws ? std::max(b.ss_bwmax, SB) : b.max_n) + 2 * SB) | 1;      // rows of the LDS window (odd)
-        const size_t win_bytes = sizeof(double) * (size_t)NB * (size_t)wr;
-        if (b.max_n > 768 && !no_win && win_bytes <= 150 * 1024) {
-            // more matrices than CUs: the variant without requests ahead, two workgroups per CU (config 5 at 64^3: solves 448 -> 397 ms
-            // per step)
-            constexpr bool two_env = true;
-            auto go = [&](auto lo, auto up) {
+}
+
+// 2. Z = (C - sigma)^-1 X for the active matrices, by the kernels of the plan
+static void launch_solves(SsIter &it, const SsSolvePlan &p) {
+    hipStream_t s = it.s;
+    EigBatch &b = it.b;
+    const int nact = it.nact;
+    const int *bws = b.bw.p;
+    double *X = it.X, *Z = it.Z;
+    if (p.lds()) {      // both triangles in one launch, X -> Z
+        auto go = [&](auto kern) {
+            SA_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+            hipLaunchKernelGGL(kern, dim3(nact), dim3(p.threads), p.lds_bytes, s, b.n.p, b.moff.p, b.voff.p, b.W.p, X, Z, it.state.p, bws, it.active.p);
+        };
+        if (p.kind == SsSolve::LdsPrefetch128) go(ss_solve_lds_pf_kernel<128>);
+        else if (p.kind == SsSolve::Lds256) go(ss_solve_lds_kernel<256>);
+        else go(ss_solve_lds_kernel<512>);
+        return;
+    }
+    // Z <- X for the matrices still iterating (the whole buffer used to be copied every iteration: 0.6 s of
+    // config 5's 23 s, where most matrices of a chunk are done long before the last one), then a launch per triangle in place
+    with_nb(it.NB, [&](auto nb) {
+        constexpr int B = decltype(nb)::value;
+        hipLaunchKernelGGL(ss_copy_active_kernel<B>, dim3(nact, p.copy_ny), dim3(256), 0, s, b.n.p, b.voff.p, it.active.p, X, Z);
+        if (p.kind == SsSolve::Window4 || p.kind == SsSolve::Window0x2) {
+            auto win = [&](auto lo, auto up) {
                 SA_HIP_CHECK(hipFuncSetAttribute((const void *)lo, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
                 SA_HIP_CHECK(hipFuncSetAttribute((const void *)up, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-                hipLaunchKernelGGL(lo, dim3(nact), dim3(1024), win_bytes, s, wr, b.n.p, b.moff.p, b.voff.p, b.W.p, Z, state.p, bws, active.p);
-                hipLaunchKernelGGL(up, dim3(nact), dim3(1024), win_bytes, s, wr, b.n.p, b.moff.p, b.voff.p, b.W.p, Z, state.p, bws, active.p);
+                hipLaunchKernelGGL(lo, dim3(nact), dim3(p.threads), p.lds_bytes, s, p.wr, b.n.p, b.moff.p, b.voff.p, b.W.p, Z, it.state.p, bws, it.active.p);
+                hipLaunchKernelGGL(up, dim3(nact), dim3(p.threads), p.lds_bytes, s, p.wr, b.n.p, b.moff.p, b.voff.p, b.W.p, Z, it.state.p, bws, it.active.p);
             };
-            with_nb([&](auto nb) {
-                constexpr int B = decltype(nb)::value;
-                if (two_env && nact > 256 && win_bytes <= 70 * 1024) go(ss_trsolve_win_kernel<false, 0, 2, B>, ss_trsolve_win_kernel<true, 0, 2, B>);
-                else go(ss_trsolve_win_kernel<false, 4, 1, B>, ss_trsolve_win_kernel<true, 4, 1, B>);
-            });
-        } else if (b.max_n > 768) {
-            with_nb([&](auto nb) {
-                constexpr int B = decltype(nb)::value;
-                hipLaunchKernelGGL((ss_trsolve_kernel<false, 1024, B>), dim3(nact), dim3(1024), 0, s, b.n.p, b.moff.p, b.voff.p, b.W.p, Z, state.p, bws, active.p);
-                hipLaunchKernelGGL((ss_trsolve_kernel<true, 1024, B>), dim3(nact), dim3(1024), 0, s, b.n.p, b.moff.p, b.voff.p, b.W.p, Z, state.p, bws, active.p);
-            });
+            if (p.kind == SsSolve::Window0x2) win(ss_trsolve_win_kernel<false, 0, 2, B>, ss_trsolve_win_kernel<true, 0, 2, B>);
+            else win(ss_trsolve_win_kernel<false, 4, 1, B>, ss_trsolve_win_kernel<true, 4, 1, B>);
         } else {
-            with_nb([&](auto nb) {
-                constexpr int B = decltype(nb)::value;
-                hipLaunchKernelGGL((ss_trsolve_kernel<false, 256, B>), dim3(nact), dim3(256), 0, s, b.n.p, b.moff.p, b.voff.p, b.W.p, Z, state.p, bws, active.p);
-                hipLaunchKernelGGL((ss_trsolve_kernel<true, 256, B>), dim3(nact), dim3(256), 0, s, b.n.p, b.moff.p, b.voff.p, b.W.p, Z, state.p, bws, active.p);
-            });
+            auto stream = [&](auto lo, auto up) {
+                hipLaunchKernelGGL(lo, dim3(nact), dim3(p.threads), 0, s, b.n.p, b.moff.p, b.voff.p, b.W.p, Z, it.state.p, bws, it.active.p);
+                hipLaunchKernelGGL(up, dim3(nact), dim3(p.threads), 0, s, b.n.p, b.moff.p, b.voff.p, b.W.p, Z, it.state.p, bws, it.active.p);
+            };
+            if (p.kind == SsSolve::Stream1024) stream(ss_trsolve_kernel<false, 1024, B>, ss_trsolve_kernel<true, 1024, B>);
+            else stream(ss_trsolve_kernel<false, 256, B>, ss_trsolve_kernel<true, 256, B>);
         }
+    });
+}
+static void ss_iter_solves(SsIter &it) {
+    EigBatch &b = it.b;
+    if (it.prof) profiler().begin(it.s);
+    launch_solves(it, ss_solve_plan(b.max_n, b.ss_bwmax, it.NB, it.nact));
+    if (it.prof) {
+        double ab = 0.0;      // the factor once per triangle + the right-hand sides, ACTIVE matrices only
+        for (int i : it.h_active) {
+            const double n = b.h_n[i], w = std::min(n, (double)b.h_bw[i] + SB);
+            ab += 8.0 * n * (2.0 * w - w * w / n) + 2.0 * 8.0 * it.NB * n;
         }
-        if (prof) {
-            double ab = 0.0;      // the factor once per triangle + the right-hand sides, ACTIVE matrices only
-            for (int i : h_active) {
-                const double n = b.h_n[i], w = b.h_bw.empty() ? n : std::min(n, (double)b.h_bw[i] + SB);
-                ab += 8.0 * n * (2.0 * w - w * w / n) + 2.0 * 8.0 * NB * n;
-            }
-            profiler().end(s, b.max_n <= 1280 ? "eig_ss_solve" : "eig_ss_solve_g", ab, 0.0);
-            profiler().begin(s);
+        profiler().end(it.s, b.max_n <= 1280 ? "eig_ss_solve" : "eig_ss_solve_g", ab, 0.0);
+    }
+}
+
+// 3. deflation against the locked pairs, Rayleigh-Ritz on span(Z), convergence of the previous pairs
+static void ss_iter_rayleigh_ritz(SsIter &it, int iter) {
+    hipStream_t s = it.s;
+    EigBatch &b = it.b;
+    const int NB = it.NB;
+    if (it.prof) profiler().begin(s);
+    const bool dbg_on = (b.opt.debug & 1) != 0;
+    DBuf<double> dbgbuf;
+    if (dbg_on) dbgbuf.alloc((size_t)b.count * 2 * NB);
+    if (it.any_lock)
+        hipLaunchKernelGGL(ss_deflate_kernel, dim3(it.nact), dim3(256), 0, s, b.n.p, b.voff.p, b.ss_Vlock.p, b.ss_ndefl.p, it.Z, it.state.p, it.active.p);
+    with_nb(NB, [&](auto nb) {
+        hipLaunchKernelGGL(ss_rr_kernel<decltype(nb)::value>, dim3(it.nact), dim3(256), 0, s, b.n.p, b.voff.p, it.X, it.Z, it.mubuf.p, it.state.p, iter,
+                           b.ss_sigma.p, it.vu, b.h_inertia.empty() ? (const int *)nullptr : b.inertia.p, dbgbuf.p, it.active.p,
+                           it.slow_hist.p, it.max_iter, it.reshift_on ? it.reshift_ok.p : (const int *)nullptr,
+                           it.any_lock ? b.ss_ndefl.p : (const int *)nullptr, it.any_lock ? it.it0.p : (const int *)nullptr, b.ss_tol);
+    });
+    if (dbg_on && iter > 0) {
+        auto hd = dbgbuf.to_host(s);
+        const int show = std::min(b.count, 3);
+        for (int i = 0; i < show; ++i) {
+            const int mi = (int)((int64_t)i * (b.count - 1) / std::max(1, show - 1));
+            std::fprintf(stderr, "  iter %d matrix %d (n %d): bounds %.2e %.2e %.2e | lambda %.6e %.6e %.6e | inertia %d\n", iter, mi, b.h_n[mi],
+                         hd[(size_t)mi * 2 * NB], hd[(size_t)mi * 2 * NB + 1], hd[(size_t)mi * 2 * NB + 2], hd[(size_t)mi * 2 * NB + NB],
+                         hd[(size_t)mi * 2 * NB + NB + 1], hd[(size_t)mi * 2 * NB + NB + 2], b.h_inertia.empty() ? -2 : b.h_inertia[mi]);
         }
-        const bool dbg_on = (b.opt.debug & 1) != 0;
-        DBuf<double> dbgbuf;
-        if (dbg_on) dbgbuf.alloc((size_t)b.count * 2 * NB);
-        if (any_lock)
-            hipLaunchKernelGGL(ss_deflate_kernel, dim3(nact), dim3(256), 0, s, b.n.p, b.voff.p, b.ss_Vlock.p, b.ss_ndefl.p, Z, state.p, active.p);
-        with_nb([&](auto nb) {
-            hipLaunchKernelGGL(ss_rr_kernel<decltype(nb)::value>, dim3(nact), dim3(256), 0, s, b.n.p, b.voff.p, X, Z, mu, state.p, iter,
-                               b.ss_sigma.p, vu, b.h_inertia.empty() ? (const int *)nullptr : b.inertia.p, dbgbuf.p, active.p,
-                               slow_hist.p, max_iter, reshift_on ? reshift_ok.p : (const int *)nullptr,
-                               any_lock ? b.ss_ndefl.p : (const int *)nullptr, any_lock ? it0.p : (const int *)nullptr, b.ss_tol);
-        });
-        if (dbg_on && iter > 0) {
-            auto hd = dbgbuf.to_host(s);
-            const int show = std::min(b.count, 3);
-            const int dbg_one = -1;
-            if (dbg_one >= 0 && dbg_one < b.count) {
-                std::fprintf(stderr, "  iter %d matrix %d: bounds", iter, dbg_one);
-                for (int q = 0; q < 8; ++q) std::fprintf(stderr, " %.2e", hd[(size_t)dbg_one * 16 + q]);
-                std::fprintf(stderr, " | lambda");
-                for (int q = 0; q < 8; ++q) std::fprintf(stderr, " %.5e", hd[(size_t)dbg_one * 16 + 8 + q]);
-                std::fprintf(stderr, " | inertia %d locked %d\n", b.h_inertia.empty() ? -2 : b.h_inertia[dbg_one], h_ndefl[dbg_one]);
-            }
-            for (int i = 0; i < show && dbg_one < 0; ++i) {
-                const int mi = (int)((int64_t)i * (b.count - 1) / std::max(1, show - 1));
-                std::fprintf(stderr, "  iter %d matrix %d (n %d): bounds %.2e %.2e %.2e | lambda %.6e %.6e %.6e | inertia %d\n", iter, mi, b.h_n[mi],
-                             hd[(size_t)mi * 2 * NB], hd[(size_t)mi * 2 * NB + 1], hd[(size_t)mi * 2 * NB + 2], hd[(size_t)mi * 2 * NB + NB],
-                             hd[(size_t)mi * 2 * NB + NB + 1], hd[(size_t)mi * 2 * NB + NB + 2], b.h_inertia.empty() ? -2 : b.h_inertia[mi]);
-            }
+    }
+    if (it.prof) profiler().end(s, "eig_ss_rr", 0.0, 0.0);
+}
+
+// 4a. lock requests (state bit 3): the six converged pairs of those matrices are copied out, their blocks start again
+static void ss_iter_lock(SsIter &it, int iter) {
+    hipStream_t s = it.s;
+    EigBatch &b = it.b;
+    std::vector<int> req;
+    for (int i = 0; i < b.count; ++i)
+        if ((it.hstate[i] & 8) && !(it.hstate[i] & 3) && it.h_ndefl[i] == 0 && !b.h_bad[i]) { req.push_back(i); it.h_ndefl[i] = SS_LOCK; it.hstate[i] = 0; }
+    if (req.empty()) return;
+    DBuf<int> d_req;
+    d_req.from_host(req, s);
+    hipLaunchKernelGGL(ss_lock_kernel, dim3((unsigned)req.size()), dim3(256), 0, s, d_req.p, b.n.p, b.voff.p, it.X, it.mubuf.p, b.ss_sigma.p,
+                       b.ss_Vlock.p, b.ss_lock_mu.p, b.ss_ndefl.p, it.it0.p, iter, it.state.p, it.slow_hist.p);
+    SA_HIP_CHECK(hipGetLastError());
+    SA_HIP_CHECK(hipStreamSynchronize(s));
+    if ((b.opt.debug & 1))
+        std::fprintf(stderr, "subspace: iteration %d, six pairs of %zu matrices locked (first: matrix %d)\n", iter, req.size(), req[0]);
+}
+
+// 4b. re-shift requests (state bit 2): the bands are restored, the granted matrices shifted to just below their smallest
+// Ritz value, the batch factored again
+static void ss_iter_reshift(SsIter &it, int iter) {
+    hipStream_t s = it.s;
+    EigBatch &b = it.b;
+    const int NB = it.NB;
+    std::vector<int> req, cand;
+    for (int i = 0; i < b.count; ++i)
+        if ((it.hstate[i] & 4) && !(it.hstate[i] & 3) && it.h_reshift_ok[i]) cand.push_back(i);
+    std::vector<double> hmu;
+    if (!cand.empty()) { auto t2 = it.mubuf.to_host(s); hmu.assign(t2.begin(), t2.end()); }
+    // The smallest Ritz value comes down towards the eigenvalue: the new shift has to stay below where it
+    // will end.  A request is granted once the value has moved by less than half a percent in an iteration,
+    // and the shift keeps five such steps (at least 2 % of the old distance) below it -- on the 7 900-row
+    // level-1 agglomerates of config 4 with 8 x 8 x 4-AE blocks the value of iteration 6 was still more
+    // than 2 % too high and the factorisation at the new shift met a negative pivot.
+    for (int i : cand) {
+        const double gap = hmu[(size_t)i * NB];
+        const double moved = it.reshift_prev[(size_t)i] > 0.0 ? it.reshift_prev[(size_t)i] - gap : 1e300;
+        it.reshift_prev[(size_t)i] = gap;
+        if (moved <= 0.005 * gap) { it.reshift_margin[(size_t)i] = std::max(0.02 * gap, 5.0 * std::max(moved, 0.0)); req.push_back(i); }
+    }
+    if (req.empty()) return;
+    std::vector<double> delta(req.size());
+    for (size_t t = 0; t < req.size(); ++t) {
+        const int i = req[t];
+        const double gap = hmu[(size_t)i * NB];              // smallest Ritz value - sigma (> 0)
+        const double snew = b.h_sigma[i] + gap - it.reshift_margin[(size_t)i];
+        delta[t] = b.h_sigma[i] - snew;
+        b.h_sigma[i] = snew;
+        it.h_reshift_ok[i] = 0;
+    }
+    b.ss_sigma.from_host(b.h_sigma, s);
+    it.reshift_ok.from_host(it.h_reshift_ok, s);
+    launch_band_copy<true>(s, b);
+    hipLaunchKernelGGL(ss_shift_kernel, dim3(b.count), dim3(256), 0, s, b.n.p, b.moff.p, b.W.p, 0.0, b.ss_sigma.p);
+    DBuf<int> info2((size_t)b.count);
+    info2.zero(s);
+    ss_factor_generic(s, b, false, nullptr, info2.p, b.ss_bwmax);
+    auto hi2 = info2.to_host(s);
+    const int gave_up = 2;      // (source of the copies below: alive until the stream is synchronised)
+    for (int i = 0; i < b.count; ++i)
+        if (hi2[i] && !(it.hstate[i] & 1) && !b.h_bad[i]) {     // the new shift was not below the spectrum after all
+            mark_bad(b, i);
+            it.hstate[i] |= 2;
+            SA_HIP_CHECK(hipMemcpyAsync(it.state.p + i, &gave_up, sizeof(int), hipMemcpyHostToDevice, s));
         }
-        if (prof) profiler().end(s, "eig_ss_rr", 0.0, 0.0);
-        // The state is read back (and the active list rebuilt) after every iteration of the large matrices, whose
-        // iterations cost milliseconds; the small ones (LDS solves, ~0.1 ms for the few hundred survivors of a
-        // chunk) are checked after iterations 1, 3, 6, 9, ...: the read-back's host round trip (~0.25 ms) was
-        // most of an iteration, an accepted matrix leaves the kernels at once, up to two spare iterations are cheap.
-        const bool check = iter >= 1 && (b.max_n > 1280 || iter == 1 || iter % 3 == 0);
-        if (check) {
-            auto t = state.to_host(s);
-            hstate.assign(t.begin(), t.end());
-            if (any_lock) {      // lock requests (state bit 3)
-                std::vector<int> req;
-                for (int i = 0; i < b.count; ++i)
-                    if ((hstate[i] & 8) && !(hstate[i] & 3) && h_ndefl[i] == 0 && !b.h_bad[i]) { req.push_back(i); h_ndefl[i] = SS_LOCK; hstate[i] = 0; }
-                if (!req.empty()) {
-                    DBuf<int> d_req;
-                    d_req.from_host(req, s);
-                    hipLaunchKernelGGL(ss_lock_kernel, dim3((unsigned)req.size()), dim3(256), 0, s, d_req.p, b.n.p, b.voff.p, X, mu, b.ss_sigma.p,
-                                       b.ss_Vlock.p, b.ss_lock_mu.p, b.ss_ndefl.p, it0.p, iter, state.p, slow_hist.p);
-                    SA_HIP_CHECK(hipGetLastError());
-                    SA_HIP_CHECK(hipStreamSynchronize(s));
-                    if ((b.opt.debug & 1))
-                        std::fprintf(stderr, "subspace: iteration %d, six pairs of %zu matrices locked (first: matrix %d)\n", iter, req.size(), req[0]);
-                }
-            }
-            done = true;
-            int nconv = 0;
-            for (int i = 0; i < b.count; ++i) {
-                const int v = hstate[i];
-                if ((v & 2) && !b.h_bad[i]) {     // gave up during the iteration (too many pairs, breakdown, hopeless rate)
-                    SA_REQUIRE(!b.opt.eig_strict, "few-eigenpairs path gave up on a matrix (strict mode)");
-                    mark_bad(i);
-                }
-                if (!(v & 3)) done = false;
-                else ++nconv;
-            }
-            if (too_many_bad()) failed = true;
-            if (failed && (b.opt.debug & 1)) {
-                std::fprintf(stderr, "subspace: iteration %d: too many matrices gave up (states:", iter);
-                for (int i = 0; i < b.count && i < 64; ++i) std::fprintf(stderr, " %x", hstate[i]);
-                std::fprintf(stderr, ")\n");
-            }
-            if (reshift_on && !failed) {
-                std::vector<int> req, cand;
-                for (int i = 0; i < b.count; ++i)
-                    if ((hstate[i] & 4) && !(hstate[i] & 3) && h_reshift_ok[i]) cand.push_back(i);
-                std::vector<double> hmu;
-                if (!cand.empty()) { auto t2 = mubuf.to_host(s); hmu.assign(t2.begin(), t2.end()); }
-                // The smallest Ritz value comes down towards the eigenvalue: the new shift has to stay below where it
-                // will end.  A request is granted once the value has moved by less than half a percent in an iteration,
-                // and the shift keeps five such steps (at least 2 % of the old distance) below it -- on the 7 900-row
-                // level-1 agglomerates of config 4 with 8 x 8 x 4-AE blocks the value of iteration 6 was still more
-                // than 2 % too high and the factorisation at the new shift met a negative pivot.
-                for (int i : cand) {
-                    const double gap = hmu[(size_t)i * NB];
-                    const double moved = reshift_prev[(size_t)i] > 0.0 ? reshift_prev[(size_t)i] - gap : 1e300;
-                    reshift_prev[(size_t)i] = gap;
-                    if (moved <= 0.005 * gap) { reshift_margin[(size_t)i] = std::max(0.02 * gap, 5.0 * std::max(moved, 0.0)); req.push_back(i); }
-                }
-                if (!req.empty()) {
-                    std::vector<double> delta(req.size());
-                    for (size_t t = 0; t < req.size(); ++t) {
-                        const int i = req[t];
-                        const double gap = hmu[(size_t)i * NB];              // smallest Ritz value - sigma (> 0)
-                        const double snew = b.h_sigma[i] + gap - reshift_margin[(size_t)i];
-                        delta[t] = b.h_sigma[i] - snew;
-                        b.h_sigma[i] = snew;
-                        h_reshift_ok[i] = 0;
-                    }
-                    b.ss_sigma.from_host(b.h_sigma, s);
-                    reshift_ok.from_host(h_reshift_ok, s);
-                    const int ny = std::max(1, std::min(64, 8192 / std::max(1, b.count)));
-                    hipLaunchKernelGGL(band_copy_kernel<true>, dim3(b.count, ny), dim3(256), 0, s, b.n.p, b.moff.p, b.W.p, b.bw.p,
-                                       b.ss_soff.p, b.ss_save);
-                    hipLaunchKernelGGL(ss_shift_kernel, dim3(b.count), dim3(256), 0, s, b.n.p, b.moff.p, b.W.p, 0.0, b.ss_sigma.p);
-                    DBuf<int> info2((size_t)b.count);
-                    info2.zero(s);
-                    ss_factor_generic(s, b, false, nullptr, info2.p, bws, b.ss_bwmax);
-                    auto hi2 = info2.to_host(s);
-                    std::vector<int> st_fix;
-                    for (int i = 0; i < b.count; ++i)
-                        if (hi2[i] && !(hstate[i] & 1) && !b.h_bad[i]) {     // the new shift was not below the spectrum after all
-                            mark_bad(i);
-                            hstate[i] |= 2;
-                            st_fix.push_back(i);
-                        }
-                    for (int i : st_fix) {
-                        const int two = 2;
-                        SA_HIP_CHECK(hipMemcpyAsync(state.p + i, &two, sizeof(int), hipMemcpyHostToDevice, s));
-                    }
-                    DBuf<int> d_req;
-                    DBuf<double> d_delta;
-                    d_req.from_host(req, s);
-                    d_delta.from_host(delta, s);
-                    with_nb([&](auto nb) {
-                        hipLaunchKernelGGL(ss_reshift_mu_kernel<decltype(nb)::value>, dim3(div_up((long)req.size() * NB, 256)), dim3(256), 0, s, (int)req.size(),
-                                           d_req.p, d_delta.p, mu, slow_hist.p);
-                    });
-                    SA_HIP_CHECK(hipGetLastError());
-                    SA_HIP_CHECK(hipStreamSynchronize(s));
-                    if ((b.opt.debug & 1))
-                        std::fprintf(stderr, "subspace: iteration %d, %zu matrices factored again at a shift below their smallest Ritz value\n", iter, req.size());
-                    if (too_many_bad()) failed = true;
-                    if (failed && (b.opt.debug & 1)) {
-                        std::fprintf(stderr, "subspace: iteration %d: the factorisation at the new shifts failed (info:", iter);
-                        for (int i = 0; i < b.count && i < 64; ++i) std::fprintf(stderr, " %d", hi2[i]);
-                        std::fprintf(stderr, ")\n");
-                    }
-                }
-            }
-            const bool dbg = (b.opt.debug & 1) != 0;
-            if (dbg) std::fprintf(stderr, "subspace: iteration %d, %d of %d matrices accepted (n max %d)\n", iter, nconv, b.count, b.max_n);
-            if (failed) break;
-            h_active.clear();
-            for (int i = 0; i < b.count; ++i)
-                if (!(hstate[i] & 3)) h_active.push_back(i);
-            nact = (int)h_active.size();
-            if (nact) SA_HIP_CHECK(hipMemcpyAsync(active.p, h_active.data(), sizeof(int) * (size_t)nact, hipMemcpyHostToDevice, s));
+    DBuf<int> d_req;
+    DBuf<double> d_delta;
+    d_req.from_host(req, s);
+    d_delta.from_host(delta, s);
+    with_nb(NB, [&](auto nb) {
+        hipLaunchKernelGGL(ss_reshift_mu_kernel<decltype(nb)::value>, dim3(div_up((long)req.size() * NB, 256)), dim3(256), 0, s, (int)req.size(),
+                           d_req.p, d_delta.p, it.mubuf.p, it.slow_hist.p);
+    });
+    SA_HIP_CHECK(hipGetLastError());
+    SA_HIP_CHECK(hipStreamSynchronize(s));
+    if ((b.opt.debug & 1))
+        std::fprintf(stderr, "subspace: iteration %d, %zu matrices factored again at a shift below their smallest Ritz value\n", iter, req.size());
+    if (too_many_bad(b)) it.failed = true;
+    if (it.failed && (b.opt.debug & 1)) {
+        std::fprintf(stderr, "subspace: iteration %d: the factorisation at the new shifts failed (info:", iter);
+        for (int i = 0; i < b.count && i < 64; ++i) std::fprintf(stderr, " %d", hi2[i]);
+        std::fprintf(stderr, ")\n");
+    }
+}
+
+// 4. the state comes back: lock requests, matrices that gave up, re-shift requests, the new active list
+static void ss_iter_read_state(SsIter &it, int iter) {
+    EigBatch &b = it.b;
+    it.read_state();
+    if (it.any_lock) ss_iter_lock(it, iter);
+    it.done = true;
+    int nconv = 0;
+    for (int i = 0; i < b.count; ++i) {
+        const int v = it.hstate[i];
+        if ((v & 2) && !b.h_bad[i]) {     // gave up during the iteration (too many pairs, breakdown, hopeless rate)
+            SA_REQUIRE(!b.opt.eig_strict, "few-eigenpairs path gave up on a matrix (strict mode)");
+            mark_bad(b, i);
         }
+        if (!(v & 3)) it.done = false;
+        else ++nconv;
+    }
+    if (too_many_bad(b)) it.failed = true;
+    if (it.failed && (b.opt.debug & 1)) {
+        std::fprintf(stderr, "subspace: iteration %d: too many matrices gave up (states:", iter);
+        for (int i = 0; i < b.count && i < 64; ++i) std::fprintf(stderr, " %x", it.hstate[i]);
+        std::fprintf(stderr, ")\n");
+    }
+    if (it.reshift_on && !it.failed) ss_iter_reshift(it, iter);
+    if ((b.opt.debug & 1)) std::fprintf(stderr, "subspace: iteration %d, %d of %d matrices accepted (n max %d)\n", iter, nconv, b.count, b.max_n);
+    if (it.failed) return;
+    it.h_active.clear();
+    for (int i = 0; i < b.count; ++i)
+        if (!(it.hstate[i] & 3)) it.h_active.push_back(i);
+    it.send_active();
+}
+
+// 5. certification: the number of Ritz values inside the window must be the number of eigenvalues
+// below vu (inertia of C - vu I); anything else sends the matrix (too many: the batch) to the dense path
+static bool ss_iter_certify(SsIter &it) {
+    EigBatch &b = it.b;
+    if (b.h_inertia.empty()) return true;
+    int bad = 0, unsure = 0;
+    for (int i = 0; i < b.count; ++i) {
+        if (b.h_bad[i]) continue;
+        const int k = ((it.hstate[i] >> 4) & 15) + it.h_ndefl[i];
+        if (b.h_inertia[i] < 0) { ++unsure; mark_bad(b, i); }
+        else if (b.h_inertia[i] != k) { ++bad; mark_bad(b, i); }
+    }
+    if ((b.opt.debug & 1) || bad || unsure)
+        std::fprintf(stderr, "saamge_amd: few-eigenpairs batch of %d: %d counts contradicted by the inertia, %d uncertified\n",
+                     b.count, bad, unsure);
+    if (bad || unsure) {
+        SA_REQUIRE(!b.opt.eig_strict, "few-eigenpairs path: count not certified (strict mode)");
+        if (too_many_bad(b)) return false;
+    }
+    return true;
+}
+
+// Subspace iteration; fills b.h_m / b.m.  Returns false when some matrix needs the dense path.
+bool eig_subspace_iterate(hipStream_t s, EigBatch &b, double vu) {
+    SsIter it(s, b, vu);
+    ss_iter_start(it);
+    for (int iter = 0; iter < it.max_iter && !it.done && !it.failed; ++iter) {
+        if (it.nact == 0) {                 // every matrix was finished before the factorisation
+            it.read_state();
+            it.done = true;
+            break;
+        }
+        ss_iter_solves(it);
+        ss_iter_rayleigh_ritz(it, iter);
+        if (ss_reads_state(b.max_n, iter)) ss_iter_read_state(it, iter);
     }
     SA_HIP_CHECK(hipGetLastError());
-    if (!prof) profiler().end(s, "eig_ss_iterate", 0.0, 0.0);
-    if (!failed && !done) {      // out of iterations: the unfinished matrices go to the dense path
+    if (!it.prof) profiler().end(s, "eig_ss_iterate", 0.0, 0.0);
+    if (!it.failed && !it.done) {      // out of iterations: the unfinished matrices go to the dense path
         SA_REQUIRE(!b.opt.eig_strict, "few-eigenpairs path: no convergence (strict mode)");
-        { auto t = state.to_host(s); hstate.assign(t.begin(), t.end()); }
-        for (int i = 0; i < b.count; ++i) if (!(hstate[i] & 3)) mark_bad(i);
-        if (too_many_bad()) failed = true;
+        it.read_state();
+        for (int i = 0; i < b.count; ++i) if (!(it.hstate[i] & 3)) mark_bad(b, i);
+        if (too_many_bad(b)) it.failed = true;
     }
-    if (failed) {
+    if (it.failed) {
         // (Options::eig_strict: the tests of this path must not pass on the dense fallback)
         SA_REQUIRE(!b.opt.eig_strict, "few-eigenpairs path gave up on a batch (strict mode)");
         return false;
     }
-    // certification: the number of Ritz values inside the window must be the number of eigenvalues
-    // below vu (inertia of C - vu I); anything else sends the batch to the dense path
-    if (!b.h_inertia.empty()) {
-        int bad = 0, unsure = 0;
-        for (int i = 0; i < b.count; ++i) {
-            if (b.h_bad[i]) continue;
-            const int k = ((hstate[i] >> 4) & 15) + h_ndefl[i];
-            if (b.h_inertia[i] < 0) { ++unsure; mark_bad(i); }
-            else if (b.h_inertia[i] != k) { ++bad; mark_bad(i); }
-        }
-        const bool dbg = (b.opt.debug & 1) != 0;
-        if (dbg || bad || unsure)
-            std::fprintf(stderr, "saamge_amd: few-eigenpairs batch of %d: %d counts contradicted by the inertia, %d uncertified\n",
-                         b.count, bad, unsure);
-        if (bad || unsure) {
-            SA_REQUIRE(!b.opt.eig_strict, "few-eigenpairs path: count not certified (strict mode)");
-            if (too_many_bad()) return false;
-        }
-    }
+    if (!ss_iter_certify(it)) return false;
     b.h_m.assign((size_t)b.count, 1);
-    for (int i = 0; i < b.count; ++i) b.h_m[i] = b.h_bad[i] ? 0 : (hstate[i] >> 8) + h_ndefl[i];
+    for (int i = 0; i < b.count; ++i) b.h_m[i] = b.h_bad[i] ? 0 : (it.hstate[i] >> 8) + it.h_ndefl[i];
     b.m.from_host(b.h_m, s);
-    b.ss_mu = std::move(mubuf);
+    b.ss_mu = std::move(it.mubuf);
     return true;
 }
 
 void eig_subspace_vectors(hipStream_t s, EigBatch &b, const int64_t *eoff, const int64_t *xoff, double *evals,
                           double *evecs) {
     profiler().begin(s);
-    auto launch = [&](auto nb) {
+    with_nb(b.ss_nb, [&](auto nb) {
         hipLaunchKernelGGL(ss_output_kernel<decltype(nb)::value>, dim3(b.count), dim3(256), 0, s, b.n.p, b.voff.p, b.Xbuf.p, b.ss_mu.p, b.dis.p,
                            b.has_perm ? b.perm.p : nullptr, b.m.p, eoff, xoff, evals, evecs, b.ss_sigma.p,
                            b.ss_has_lock ? b.ss_ndefl.p : (const int *)nullptr, b.ss_has_lock ? b.ss_Vlock.p : (const double *)nullptr,
                            b.ss_has_lock ? b.ss_lock_mu.p : (const double *)nullptr);
-    };
-    if (b.ss_nb == 16) launch(std::integral_constant<int, 16>()); else launch(std::integral_constant<int, 8>());
+    });
     SA_HIP_CHECK(hipGetLastError());
     profiler().end(s, "eig_ss_output", 0.0, 0.0);
 }

@@ -170,19 +170,60 @@ def test_batched_eigens_banded_matrices_take_the_few_eigenpairs_path():
     try:
         for shapes in ([(70, 1), (96, 5), (130, 17), (64, 40)], [(200, 52)], [(150, 60), (90, 3)], [(300, 100), (77, 2)],
                        [(300, 120), (257, 256), (80, 4)]):
-            mats = [band_laplacian(n, bw) for n, bw in shapes]
-            Ds = [o.snd_D_from_dense(L) for L in mats]
-            theta = 2e-3
-            res = capi.lower_eigens_batched(mats, Ds, -1.0, theta)
-            for L, D, (w, X) in zip(mats, Ds, res):
-                wr, Xr = o.lower_eigens_dense(L, D, theta)
-                assert len(w) == len(wr) and 1 <= len(w) <= 6
-                assert np.allclose(w, wr, atol=EIG_TOL)
-                R = L @ X - (D[:, None] * X) * w[None, :]
-                assert np.abs(R).max() <= 1e-10
-                assert np.allclose(_proj(X, D), _proj(Xr, D), atol=PROJ_TOL)
+            _check_banded_batch(capi, o, [band_laplacian(n, bw) for n, bw in shapes])
     finally:
         capi.set_options(eig_strict=old.eig_strict)
+
+
+def _check_banded_batch(capi, o, mats):
+    Ds = [o.snd_D_from_dense(L) for L in mats]
+    theta = 2e-3
+    res = capi.lower_eigens_batched(mats, Ds, -1.0, theta)
+    for L, D, (w, X) in zip(mats, Ds, res):
+        wr, Xr = o.lower_eigens_dense(L, D, theta)
+        assert len(w) == len(wr) and 1 <= len(w) <= 6
+        assert np.allclose(w, wr, atol=EIG_TOL)
+        R = L @ X - (D[:, None] * X) * w[None, :]
+        assert np.abs(R).max() <= 1e-10
+        assert np.allclose(_proj(X, D), _proj(Xr, D), atol=PROJ_TOL)
+
+
+def _band_laplacian_fast(rng, n, bw):
+    """band_laplacian of the test above without its loop over the diagonals (a stream of its own: the cases above keep theirs)"""
+    U = np.triu(rng.uniform(0.5, 1.5, size=(n, n)), 1)
+    U -= np.triu(U, bw + 1)                      # distances 1 .. bw
+    W = -(U + U.T)
+    L = W + np.diag(-W.sum(axis=1))
+    return L + np.diag(1e-4 * rng.uniform(0.5, 1.0, size=n))     # SPD, one eigenvalue near zero
+
+
+# Batches that reach the plan values (csrc/eig_ss_plan.h, DESIGN.md section 4.12) the batches above do not:
+#   wide1024  two-panel walk (eig_outer_panels = 2) with 1 024-thread panels, min(800, 750 + 32) > 768; LDS solves with 512 threads
+#   g4_512    blocked walk with G = 4 and 512-thread panels, min(500, 330 + 64) > 448
+#   two_halves 64 matrices: with eig_outer_panels = 2 the two halves of the batch on two streams; band 120 > 112, so the in-place
+#             inertia pass with save / restore runs on all 64
+#   stream1024 the streaming solves with 1 024 threads: the window of 2 431 rows x 8 vectors (155 584 B) is over 150 KB
+_PLAN_BATCHES = {
+    "wide1024": [(800, 750)],
+    "g4_512": [(500, 330), (90, 3)],
+    "two_halves": [(130 + k % 5, 120) for k in range(64)],
+    "stream1024": [(2400, 2399)],
+}
+
+
+@pytest.mark.parametrize("name,panels", [("wide1024", 2), ("wide1024", 4), ("wide1024", 8), ("g4_512", 4), ("two_halves", 2),
+                                         ("two_halves", 8), ("stream1024", 8)])
+def test_batched_eigens_banded_matrices_reach_every_kernel_plan(name, panels):
+    """The strict test above (same body, oracle and tolerances) on the batches of _PLAN_BATCHES, under the factor walk that
+    eig_outer_panels names."""
+    capi, o = _capi(), _oracle()
+    rng = np.random.default_rng(23)
+    mats = [_band_laplacian_fast(rng, n, bw) for n, bw in _PLAN_BATCHES[name]]
+    old = capi.set_options(eig_strict=1, eig_outer_panels=panels)
+    try:
+        _check_banded_batch(capi, o, mats)
+    finally:
+        capi.set_options(eig_strict=old.eig_strict, eig_outer_panels=old.eig_outer_panels)
 
 
 @pytest.mark.gpu
