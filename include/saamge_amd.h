@@ -404,12 +404,18 @@ int saamge_amd_ae_order(int ND, int NE, int nde, const int *elem_ptr, const int 
                         int nparts, int mode, int *ae_ptr, long long *nconn, int *ae_to_dof, int *pos, int *bw0, int *bw,
                         int *choice);
 /* ---- element matrices computed on the device (csrc/elmat.hip) ----
- * The standard order-1 element matrices from vertex coordinates, element -> vertex lists and per-element coefficients, written
+ * The standard order-1 and tensor-product order-2 element matrices from vertex coordinates, element -> vertex lists and per-element coefficients, written
  * in the packed layout saamge_amd_operator_assemble and saamge_amd_ml_produce_data* take (element e: size_e x size_e row-major
  * at sum_{f<e} size_f^2), so that the physics never exists on the host; saamge_amd/elmat_model.py defines every operation and
  * the device gives the same bits.  Types by (dim, nodes): (2, 3) P1 triangle, (2, 4) Q1 quadrilateral
  * (v00, v10, v11, v01), (3, 4) P1 tetrahedron, (3, 6) P1 x P1 wedge (bottom triangle, then top), (3, 8) Q1 hexahedron (MFEM's
  * vertex order); one quadrature rule per type, exact on affine images.
+ * Order 2: (2, 9) Q2 quadrilateral, nodes in MFEM's H1 order (the vertices v00, v10, v11, v01, the edge midpoints bottom, right,
+ * top, left, the centre), and (3, 27) Q2 hexahedron, nodes lexicographic (node (iz * 3 + iy) * 3 + ix).  The node order is an
+ * input convention: the dof lists follow it, a caller with another order permutes its node lists and nothing else.  For these
+ * coords holds ALL nodes (NV of them) and the lists hold 9 / 27 node ids; the geometry is isoparametric (the Jacobian runs over
+ * all nodes, so an element may be curved; a straight-sided one has its extra nodes at the averages of its corners).  Rule: 3
+ * Gauss points per axis, exact for both forms on parallelepipeds.  One list (elem_ptr) may hold elements of both orders.
  * kind 0 diffusion: ncoef = 1 (c I), dim (diagonal) or dim (dim + 1) / 2 (symmetric: xx, yy, zz, xy, yz, xz / xx, yy, xy), the
  * matrix nodes x nodes.  kind 1 elasticity (lambda div u div v + 2 mu eps(u):eps(v)): ncoef = 2 (lambda, mu), dof
  * dim * node + component, the matrix (dim nodes) x (dim nodes).
@@ -418,7 +424,8 @@ int saamge_amd_ae_order(int ND, int NE, int nde, const int *elem_ptr, const int 
  * dof_ptr_out (NE + 1) / elem_to_dof_out: the dof lists the matrices are indexed by (kind 0: the vertex lists;
  * kind 1: dim * vertex + component), may be NULL.  Any pointer host or device, each on its own.
  * info[0..4] = triangles, quadrilaterals, tetrahedra, wedges, hexahedra; [5] = doubles written; [6] = first element
- * with a non-positive Jacobian (-1: none); [7] = 0.
+ * with a non-positive Jacobian (-1: none); [7] = order-2 elements (9-node quadrilaterals, 27-node hexahedra; [0..4] count
+ * the order-1 elements only).
  * Refused (nonzero return, saamge_amd_last_error names the argument or the first element; elmat_out is then not to be relied
  * on): dim, kind or ncoef out of range, NULL coords / elem_to_vertex / coef, malformed offsets, a vertex id outside [0, NV), an
  * element that lists a vertex twice, a node count that is no type of the dimension, an element whose Jacobian determinant is

@@ -296,10 +296,12 @@ inline LevelOrderInfo level_order_info(const ml_data_t *h, int level) {
 
 // == element matrices computed on the device (saamge_amd_element_matrices) ==
 // From vertex coordinates (NV x dim), element -> vertex lists (elem_ptr == nullptr: nde vertices per element) and per-element
-// coefficients (NE x ncoef); kind 0 diffusion, 1 elasticity.  The matrices are packed in element order as the setup entry
+// coefficients (NE x ncoef); kind 0 diffusion, 1 elasticity.  nde 9 in 2D / 27 in 3D: the order-2 quadrilateral / hexahedron
+// (coords then holds all nodes; node orders in saamge_amd.h).  The matrices are packed in element order as the setup entry
 // points and AssembledOperator take them.  Throws with saamge_amd_last_error on a refusal.
 struct ElementMatricesInfo {
     long long triangles, quadrilaterals, tetrahedra, wedges, hexahedra, doubles, first_bad_element;
+    long long order2;      // the order-2 elements (9-node quadrilaterals, 27-node hexahedra); the five counts above are order 1
 };
 // Into the caller's arrays, each a host or a device pointer (elmat_out == nullptr: the sizes only; the dof lists may be nullptr).
 inline ElementMatricesInfo element_matrices_into(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
@@ -310,7 +312,7 @@ inline ElementMatricesInfo element_matrices_into(int NV, int dim, const double *
     if (saamge_amd_element_matrices(NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, kind, ncoef, coef, stream, elmat_out,
                                     dof_ptr_out, elem_to_dof_out, info))
         throw std::runtime_error(saamge_amd_last_error());
-    const ElementMatricesInfo r = {info[0], info[1], info[2], info[3], info[4], info[5], info[6]};
+    const ElementMatricesInfo r = {info[0], info[1], info[2], info[3], info[4], info[5], info[6], info[7]};
     return r;
 }
 // From HOST arrays, as host vectors, with the dof lists the matrices are indexed by (kind 0: the vertex lists; kind 1:

@@ -761,8 +761,9 @@ def _element_arrays(coords, elem_to_vertex, coef, elem_ptr):
 
 
 def element_matrices_info(coords, elem_to_vertex, kind, coef, elem_ptr=None, stream=0):
-    """The sizes-only call (elmat_out = NULL): info = [triangles, quadrilaterals, tetrahedra, wedges, hexahedra, doubles the
-    matrices take, -1, 0].  Nothing is written; the mesh and the Jacobians are checked all the same."""
+    """The sizes-only call (elmat_out = NULL): info = [triangles, quadrilaterals, tetrahedra, wedges, hexahedra (the order-1
+    elements), doubles the matrices take, -1, order-2 elements (9-node quadrilaterals, 27-node hexahedra)].  Nothing is
+    written; the mesh and the Jacobians are checked all the same."""
     coords, e2v, coef, ep = _element_arrays(coords, elem_to_vertex, coef, elem_ptr)
     return _element_matrices_call(coords, e2v, kind, coef, ep, stream, None, None, None)
 
@@ -770,7 +771,9 @@ def element_matrices_info(coords, elem_to_vertex, kind, coef, elem_ptr=None, str
 def element_matrices(coords, elem_to_vertex, kind, coef, elem_ptr=None, device=False, dofs=False, out=None, stream=0):
     """saamge_amd_element_matrices: the element matrices of a mesh from its vertex coordinates (NV x dim), element -> vertex
     lists ((NE, nodes), or flat with elem_ptr) and per-element coefficients ((NE,) or (NE, ncoef)); kind 0 diffusion, 1
-    elasticity.  Inputs: numpy arrays or device tensors, each on its own.  Returns elmat -- (NE, size, size), or packed in
+    elasticity.  Lists of 9 (2D) / 27 (3D) nodes are the order-2 quadrilateral (MFEM's H1 order: vertices, edge midpoints,
+    centre) / hexahedron (lexicographic); coords then holds all nodes, and the elements may be curved (elmat_model.py).
+    Inputs: numpy arrays or device tensors, each on its own.  Returns elmat -- (NE, size, size), or packed in
     element order with elem_ptr -- as a numpy array, or with device=True as a torch tensor on the GPU whose data_ptr goes to
     `Operator` and `Hierarchy.from_operator` unchanged; out: an array / tensor of that many doubles to write into instead of
     a new one.  dofs=True: (elmat, dof_ptr, elem_to_dof), the int32 dof lists the matrices are indexed by (elem_to_dof

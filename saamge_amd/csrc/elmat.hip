@@ -12,6 +12,9 @@
 // into one element list per type (make_list, as operator.hip lists rows by path) and each list gets its own launch.
 // No floating-point atomics, no cross-lane reduction of values; the only atomic is the integer minimum that names the first
 // element with a non-positive determinant.
+//
+// The order-2 quadrilateral (9 nodes) and hexahedron (27 nodes) have their own kernel, em2_kernel, with its own decomposition
+// (27 divides no wavefront and a node's row block of the hex is 243 accumulators): lanes own ENTRIES, see there.
 #include "elmat.h"
 
 #include <algorithm>
@@ -44,10 +47,13 @@ template <> struct EmType<3, 4> { static constexpr int NQ = 1; static constexpr 
 template <> struct EmType<3, 6> { static constexpr int NQ = 6; static constexpr double W = 0.08333333333333333; };
 template <> struct EmType<3, 8> { static constexpr int NQ = 8; static constexpr double W = 0.125; };
 
+// types 0 .. 4: order 1 (info[0 .. 4]); 5, 6: the order-2 quadrilateral and hexahedron (info[7] counts both)
+constexpr int EM_TYPES = 7;
 constexpr int em_type_index(int dim, int nd) {
-    return dim == 2 ? (nd == 3 ? 0 : (nd == 4 ? 1 : -1)) : (nd == 4 ? 2 : (nd == 6 ? 3 : (nd == 8 ? 4 : -1)));
+    return dim == 2 ? (nd == 3 ? 0 : (nd == 4 ? 1 : (nd == 9 ? 5 : -1)))
+                    : (nd == 4 ? 2 : (nd == 6 ? 3 : (nd == 8 ? 4 : (nd == 27 ? 6 : -1))));
 }
-constexpr int EM_TYPE_ND[5] = {3, 4, 4, 6, 8};
+constexpr int EM_TYPE_ND[EM_TYPES] = {3, 4, 4, 6, 8, 9, 27};
 
 constexpr double em_f(int l, double p) { return l ? p : 1.0 - p; }
 constexpr double em_df(int l) { return l ? 1.0 : -1.0; }
@@ -299,6 +305,301 @@ __global__ __launch_bounds__(em_block(DIM, ND, KIND)) void em_kernel(int count, 
     }
 }
 
+// ---- order 2: the 9-node quadrilateral and the 27-node hexahedron ----------------------------------------------------------
+// The literals and the expressions of elmat_model.py (GAUSS3, GAUSS3_W, _n2, _d2, Q2_QUAD_LOC; the hex is lexicographic).
+constexpr double EM2_GAUSS[3] = {0.11270166537925831, 0.5, 0.8872983346207417};
+constexpr double EM2_W[3] = {0.2777777777777778, 0.4444444444444444, 0.2777777777777778};
+constexpr int EM2_QUAD_LOC[9][2] = {{0, 0}, {2, 0}, {2, 2}, {0, 2}, {1, 0}, {2, 1}, {1, 2}, {0, 1}, {1, 1}};
+constexpr double em2_n(int l, double p) {
+    return l == 0 ? (2.0 * p - 1.0) * (p - 1.0) : (l == 1 ? (4.0 * p) * (1.0 - p) : p * (2.0 * p - 1.0));
+}
+constexpr double em2_d(int l, double p) { return l == 0 ? 4.0 * p - 3.0 : (l == 1 ? 4.0 - 8.0 * p : 4.0 * p - 1.0); }
+constexpr int em2_nodes(int dim) { return dim == 2 ? 9 : 27; }
+
+// the rule's table, folded at compile time: the reference gradient of node a at point q (node-major, so that lanes that differ
+// in the point read neighbouring doubles) and the weight of point q
+template <int DIM>
+struct Em2Table {
+    double dN[em2_nodes(DIM)][em2_nodes(DIM)][DIM];
+    double w[em2_nodes(DIM)];
+};
+template <int DIM>
+constexpr Em2Table<DIM> em2_table() {
+    Em2Table<DIM> t{};
+    for (int q = 0; q < em2_nodes(DIM); ++q) {
+        const int qx = q % 3, qy = (q / 3) % 3, qz = q / 9;
+        const double px = EM2_GAUSS[qx], py = EM2_GAUSS[qy], pz = EM2_GAUSS[qz];
+        t.w[q] = DIM == 2 ? EM2_W[qx] * EM2_W[qy] : (EM2_W[qx] * EM2_W[qy]) * EM2_W[qz];
+        for (int a = 0; a < em2_nodes(DIM); ++a) {
+            if (DIM == 2) {
+                const int ix = EM2_QUAD_LOC[a][0], iy = EM2_QUAD_LOC[a][1];
+                t.dN[a][q][0] = em2_d(ix, px) * em2_n(iy, py);
+                t.dN[a][q][1] = em2_n(ix, px) * em2_d(iy, py);
+            } else {
+                const int ix = a % 3, iy = (a / 3) % 3, iz = a / 9;
+                t.dN[a][q][0] = em2_d(ix, px) * (em2_n(iy, py) * em2_n(iz, pz));
+                t.dN[a][q][1] = em2_d(iy, py) * (em2_n(ix, px) * em2_n(iz, pz));
+                t.dN[a][q][DIM - 1] = em2_d(iz, pz) * (em2_n(ix, px) * em2_n(iy, py));
+            }
+        }
+    }
+    return t;
+}
+template <int DIM>
+__device__ const Em2Table<DIM> EM2_TABLE = em2_table<DIM>();
+
+// BLOCK threads, EPB elements per workgroup, BS x BS node pairs per lane in the entry phase, QC points per pass.
+// The hex of elasticity: one element (its tile is 52 KB), 378 node pairs on 384 lanes.  The hex of diffusion: lanes own
+// 3 x 3 node pairs (the flux of 3 nodes and the gradient of 3 nodes from LDS feed 9 entries: one pair per lane would wait
+// for LDS), 45 lanes per element; the gradients of 3 points at a time keep four elements within 27 KB.
+template <int DIM, int KIND> struct Em2Cfg;
+template <> struct Em2Cfg<2, 0> { static constexpr int BLOCK = 256, EPB = 5, BS = 1, QC = 9; };
+template <> struct Em2Cfg<2, 1> { static constexpr int BLOCK = 256, EPB = 5, BS = 1, QC = 9; };
+template <> struct Em2Cfg<3, 0> { static constexpr int BLOCK = 192, EPB = 4, BS = 3, QC = 3; };
+template <> struct Em2Cfg<3, 1> { static constexpr int BLOCK = 384, EPB = 1, BS = 1, QC = 27; };
+
+// list, eI, moff, out: as in em_kernel.  Phases, a barrier between each:
+//   stage   the nodes' coordinates and the coefficients of the workgroup's elements into LDS
+//   J       one lane per (element, point, i, j): J[i][j], the sum over the nodes in ascending order
+//   point   one lane per (element, point): cofactors, det (not positive: the element id to *bad), s = weight / det
+//   then per pass of QC points
+//   G       one lane per (element, point, node): G_a = C dN_a and, for diffusion, F_a = K G_a
+//   entry   one lane per (element, BS x BS block of node pairs a <= b): a real loop over the pass's points, in ascending
+//           order, that adds the point's term to the lane's accumulators -- the whole sum of an entry lives in one lane, so
+//           the bits are the model's, and no entry is computed twice
+//   tile    the entries and their mirror images to an LDS tile (over the dead gradients), written out as consecutive doubles
+template <int DIM, int KIND>
+__global__ __launch_bounds__((Em2Cfg<DIM, KIND>::BLOCK)) void em2_kernel(int count, const int *__restrict__ list,
+                                                                       const int *__restrict__ eI, const int *__restrict__ eJ,
+                                                                       const roff_t *__restrict__ moff,
+                                                                       const double *__restrict__ coords,
+                                                                       const double *__restrict__ coef, int ncoef,
+                                                                       double *__restrict__ out, int *__restrict__ bad) {
+    typedef Em2Cfg<DIM, KIND> Cfg;
+    constexpr int BLOCK = Cfg::BLOCK, EPB = Cfg::EPB, BS = Cfg::BS, QC = Cfg::QC;
+    constexpr int ND = em2_nodes(DIM), NQ = ND, COMP = KIND ? DIM : 1, S = ND * COMP, SS = S * S;
+    constexpr int NB = ND / BS, NBP = NB * (NB + 1) / 2;      // blocks of nodes, pairs A <= B of them
+    constexpr int DD = DIM * DIM, PW = DD + 1;                // a point keeps its cofactors and s
+    constexpr int GW = KIND ? DIM : 2 * DIM;                  // a node keeps G_a, and F_a for diffusion
+    constexpr int NACC = KIND ? DD : BS * BS;
+    constexpr int NP = EPB * NQ * PW, NG = EPB * QC * ND * GW, NT = EPB * SS, WORK = NP + NG > NT ? NP + NG : NT;
+    static_assert(EPB * NBP <= BLOCK && NQ % QC == 0 && ND % BS == 0 && NG >= EPB * NQ * DD && (KIND == 0 || BS == 1), "em2 plan");
+    __shared__ double sX[EPB * ND * DIM];
+    __shared__ double sK[EPB * DD];                           // K[i][j], or lambda, mu
+    __shared__ double work[WORK];
+    __shared__ roff_t obase[EPB];
+    __shared__ int sE[EPB];                                   // the element of a slot, -1: none
+    double *const sP = work, *const sG = work + NP, *const sJ = sG, *const tile = work;
+    const Em2Table<DIM> &T = EM2_TABLE<DIM>;
+    const int tid = threadIdx.x;
+    // ---- stage
+    for (int idx = tid; idx < EPB * ND; idx += BLOCK) {
+        const int el = idx / ND, a = idx - el * ND;
+        const long slot = (long)blockIdx.x * EPB + el;
+        double x[DIM];
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) x[d] = 0.0;
+        if (slot < count) {
+            const int e = list ? list[slot] : (int)slot;
+            const long vb = eI ? (long)eI[e] : (long)e * ND;
+            const int v = eJ[vb + a];
+#pragma unroll
+            for (int d = 0; d < DIM; ++d) x[d] = coords[(long)v * DIM + d];
+            if (a == 0) {
+                sE[el] = e;
+                obase[el] = moff ? moff[e] : (roff_t)e * SS;
+                const double *c = coef + (long)e * ncoef;
+                double *K = sK + el * DD;
+                if (KIND) {
+                    K[0] = c[0];
+                    K[1] = c[1];
+                } else {
+#pragma unroll
+                    for (int i = 0; i < DD; ++i) K[i] = 0.0;
+#pragma unroll
+                    for (int i = 0; i < DIM; ++i) K[i * DIM + i] = ncoef == 1 ? c[0] : c[i];
+                    if (ncoef > DIM) {                        // xx, yy, zz, xy, yz, xz / xx, yy, xy
+                        K[0 * DIM + 1] = K[1 * DIM + 0] = c[DIM];
+                        if (DIM == 3) {
+                            K[1 * DIM + DIM - 1] = K[(DIM - 1) * DIM + 1] = c[DIM + 1];
+                            K[0 * DIM + DIM - 1] = K[(DIM - 1) * DIM + 0] = c[DIM + 2];
+                        }
+                    }
+                }
+            }
+        } else if (a == 0) {
+            sE[el] = -1;
+#pragma unroll
+            for (int i = 0; i < DD; ++i) sK[el * DD + i] = 0.0;
+        }
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) sX[idx * DIM + d] = x[d];
+    }
+    __syncthreads();
+    // ---- J
+    for (int idx = tid; idx < EPB * NQ * DD; idx += BLOCK) {
+        const int el = idx / (NQ * DD), r = idx - el * (NQ * DD), q = r / DD, ij = r - q * DD, i = ij / DIM, j = ij - i * DIM;
+        const double *X = sX + el * ND * DIM + i;
+        double t = X[0] * T.dN[0][q][j];
+        for (int a = 1; a < ND; ++a) t = t + X[a * DIM] * T.dN[a][q][j];
+        sJ[idx] = t;
+    }
+    __syncthreads();
+    // ---- point
+    for (int idx = tid; idx < EPB * NQ; idx += BLOCK) {
+        const int el = idx / NQ, q = idx - el * NQ;
+        double J[DIM][DIM], C[DIM][DIM], det;
+#pragma unroll
+        for (int i = 0; i < DIM; ++i)
+#pragma unroll
+            for (int j = 0; j < DIM; ++j) J[i][j] = sJ[idx * DD + i * DIM + j];
+        if constexpr (DIM == 2) {
+            det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+            C[0][0] = J[1][1];
+            C[0][1] = -J[1][0];
+            C[1][0] = -J[0][1];
+            C[1][1] = J[0][0];
+        } else {
+            C[0][0] = J[1][1] * J[2][2] - J[1][2] * J[2][1];
+            C[0][1] = J[1][2] * J[2][0] - J[1][0] * J[2][2];
+            C[0][2] = J[1][0] * J[2][1] - J[1][1] * J[2][0];
+            C[1][0] = J[0][2] * J[2][1] - J[0][1] * J[2][2];
+            C[1][1] = J[0][0] * J[2][2] - J[0][2] * J[2][0];
+            C[1][2] = J[0][1] * J[2][0] - J[0][0] * J[2][1];
+            C[2][0] = J[0][1] * J[1][2] - J[0][2] * J[1][1];
+            C[2][1] = J[0][2] * J[1][0] - J[0][0] * J[1][2];
+            C[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+            det = (J[0][0] * C[0][0] + J[0][1] * C[0][1]) + J[0][2] * C[0][2];
+        }
+        if (!(det > 0.0) && sE[el] >= 0) atomicMin(bad, sE[el]);
+        double *P = sP + idx * PW;
+#pragma unroll
+        for (int i = 0; i < DIM; ++i)
+#pragma unroll
+            for (int j = 0; j < DIM; ++j) P[i * DIM + j] = C[i][j];
+        P[DD] = T.w[q] / det;
+    }
+    if (!out) return;                             // (the same in every lane of the grid)
+    // ---- this lane's block of node pairs
+    const bool own = tid < EPB * NBP;
+    const int eb = own ? tid / NBP : 0;
+    int A = 0, B = own ? tid - eb * NBP : 0;
+    while (B >= NB - A) {
+        B -= NB - A;
+        ++A;
+    }
+    B += A;
+    double acc[NACC];
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
+    for (int q0 = 0; q0 < NQ; q0 += QC) {
+        __syncthreads();                          // the points are there; the last pass (and J) has been read
+        // ---- G
+        for (int idx = tid; idx < EPB * QC * ND; idx += BLOCK) {
+            const int el = idx / (QC * ND), r = idx - el * (QC * ND), qq = r / ND, a = r - qq * ND, q = q0 + qq;
+            const double *P = sP + (el * NQ + q) * PW;
+            double dA[DIM], G[DIM];
+#pragma unroll
+            for (int j = 0; j < DIM; ++j) dA[j] = T.dN[a][q][j];
+#pragma unroll
+            for (int i = 0; i < DIM; ++i) {
+                double t = dA[0] * P[i * DIM + 0] + dA[1] * P[i * DIM + 1];
+                if constexpr (DIM == 3) t = t + dA[2] * P[i * DIM + 2];
+                G[i] = t;
+            }
+            double *g = sG + idx * GW;
+#pragma unroll
+            for (int i = 0; i < DIM; ++i) g[i] = G[i];
+            if constexpr (KIND == 0) {
+                const double *K = sK + el * DD;
+#pragma unroll
+                for (int i = 0; i < DIM; ++i) {
+                    double t = K[i * DIM + 0] * G[0] + K[i * DIM + 1] * G[1];
+                    if constexpr (DIM == 3) t = t + K[i * DIM + 2] * G[2];
+                    g[DIM + i] = t;
+                }
+            }
+        }
+        __syncthreads();
+        // ---- entry
+        const double *Pq = sP + (eb * NQ + q0) * PW + DD;
+        const double *ga = sG + (eb * QC * ND + A * BS) * GW, *gb = sG + (eb * QC * ND + B * BS) * GW;
+#pragma unroll 1
+        for (int qq = 0; qq < QC; ++qq) {
+            const double s = Pq[qq * PW];
+            const double *pa = ga + qq * ND * GW, *pb = gb + qq * ND * GW;
+            if constexpr (KIND == 0) {
+                double Fa[BS][DIM], Gb[BS][DIM];
+#pragma unroll
+                for (int k = 0; k < BS; ++k)
+#pragma unroll
+                    for (int i = 0; i < DIM; ++i) {
+                        Fa[k][i] = pa[k * GW + DIM + i];
+                        Gb[k][i] = pb[k * GW + i];
+                    }
+#pragma unroll
+                for (int k = 0; k < BS; ++k)
+#pragma unroll
+                    for (int l = 0; l < BS; ++l) {            // (a > b inside a diagonal block: computed, never stored)
+                        double t = Fa[k][0] * Gb[l][0] + Fa[k][1] * Gb[l][1];
+                        if constexpr (DIM == 3) t = t + Fa[k][2] * Gb[l][2];
+                        const double term = s * t;
+                        acc[k * BS + l] = acc[k * BS + l] + term;
+                    }
+            } else {
+                const double lam = sK[eb * DD], mu = sK[eb * DD + 1];
+                double Ga[DIM], Gb[DIM];
+#pragma unroll
+                for (int i = 0; i < DIM; ++i) {
+                    Ga[i] = pa[i];
+                    Gb[i] = pb[i];
+                }
+                double dot = Ga[0] * Gb[0] + Ga[1] * Gb[1];
+                if constexpr (DIM == 3) dot = dot + Ga[2] * Gb[2];
+                const double md = mu * dot;
+#pragma unroll
+                for (int i = 0; i < DIM; ++i)
+#pragma unroll
+                    for (int j = 0; j < DIM; ++j) {
+                        double t = lam * (Ga[i] * Gb[j]) + mu * (Ga[j] * Gb[i]);
+                        if (i == j) t = t + md;
+                        const double term = s * t;
+                        acc[i * DIM + j] = acc[i * DIM + j] + term;
+                    }
+            }
+        }
+    }
+    __syncthreads();                              // the gradients are dead: the tile takes their place
+    // ---- tile
+    if (own) {
+        double *t = tile + eb * SS;
+        if constexpr (KIND == 0) {
+#pragma unroll
+            for (int k = 0; k < BS; ++k)
+#pragma unroll
+                for (int l = 0; l < BS; ++l) {
+                    const int a = A * BS + k, b = B * BS + l;
+                    if (a <= b) t[a * S + b] = t[b * S + a] = acc[k * BS + l];
+                }
+        } else {
+#pragma unroll
+            for (int i = 0; i < DIM; ++i)
+#pragma unroll
+                for (int j = 0; j < DIM; ++j) {
+                    const int r = DIM * A + i, c = DIM * B + j;
+                    if (r <= c) t[r * S + c] = t[c * S + r] = acc[i * DIM + j];
+                }
+        }
+    }
+    __syncthreads();
+    const long left = (long)count - (long)blockIdx.x * EPB;
+    const int total = (int)(left < EPB ? left : EPB) * SS;
+    for (int t = tid; t < total; t += BLOCK) {
+        const int l = t / SS;
+        out[obase[l] + (t - l * SS)] = tile[t];
+    }
+}
+
 // ---- tables ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void em_offsets_kernel(int NE, int nd, int *__restrict__ eI) {
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
@@ -341,6 +642,13 @@ void em_launch(const EmLaunch &L, int count, const int *list) {
                        L.moff, L.coords, L.coef, L.ncoef, L.out, L.bad);
     SA_HIP_CHECK(hipGetLastError());
 }
+template <int DIM, int KIND>
+void em2_launch(const EmLaunch &L, int count, const int *list) {
+    typedef Em2Cfg<DIM, KIND> Cfg;
+    hipLaunchKernelGGL((em2_kernel<DIM, KIND>), dim3((unsigned)div_up(count, Cfg::EPB)), dim3(Cfg::BLOCK), 0, L.s, count, list, L.eI,
+                       L.eJ, L.moff, L.coords, L.coef, L.ncoef, L.out, L.bad);
+    SA_HIP_CHECK(hipGetLastError());
+}
 template <int KIND>
 void em_launch_type(const EmLaunch &L, int type, int count, const int *list) {
     switch (type) {
@@ -348,7 +656,9 @@ void em_launch_type(const EmLaunch &L, int type, int count, const int *list) {
         case 1: em_launch<2, 4, KIND>(L, count, list); break;
         case 2: em_launch<3, 4, KIND>(L, count, list); break;
         case 3: em_launch<3, 6, KIND>(L, count, list); break;
-        default: em_launch<3, 8, KIND>(L, count, list); break;
+        case 4: em_launch<3, 8, KIND>(L, count, list); break;
+        case 5: em2_launch<2, KIND>(L, count, list); break;
+        default: em2_launch<3, KIND>(L, count, list); break;
     }
 }
 
@@ -409,9 +719,9 @@ void element_matrices(hipStream_t s, int NV, int dim, const double *coords, int 
     nconn = check_mesh_device(s, NE, eI, eJ, NV);      // offsets, vertex ids in [0, NV), no vertex twice in an element
     SA_REQUIRE((int64_t)nconn * comp <= INT_MAX, name + "dim * elem_ptr[NE] beyond 32 bits");
     // ---- types, lists, offsets of the packed matrices
-    DBuf<int> cls, flag, pos, list[5];
+    DBuf<int> cls, flag, pos, list[EM_TYPES];
     DBuf<roff_t> moff;
-    int count[5] = {0, 0, 0, 0, 0};
+    int count[EM_TYPES] = {0, 0, 0, 0, 0, 0, 0};
     int64_t doubles;
     DBuf<int> word(1);
     if (elem_ptr) {
@@ -428,7 +738,7 @@ void element_matrices(hipStream_t s, int NV, int dim, const double *coords, int 
         }
         flag.alloc((size_t)NE);
         pos.alloc((size_t)NE + 1);
-        for (int t = 0; t < 5; ++t)
+        for (int t = 0; t < EM_TYPES; ++t)
             if (em_type_index(dim, EM_TYPE_ND[t]) == t) count[t] = make_list(s, NE, cls.p, t, flag, pos, list[t]);
         moff.alloc((size_t)NE + 1);
         exclusive_scan_off(s, NE, sq.p, moff.p);
@@ -440,6 +750,7 @@ void element_matrices(hipStream_t s, int NV, int dim, const double *coords, int 
     if (info) {
         for (int t = 0; t < 5; ++t) info[t] = count[t];
         info[5] = (long long)doubles;
+        info[7] = (long long)count[5] + count[6];      // the order-2 elements
     }
     // ---- the matrices (elmat_out NULL: the determinants are still checked)
     DBuf<double> hold_X, hold_c, hold_out;
@@ -458,7 +769,7 @@ void element_matrices(hipStream_t s, int NV, int dim, const double *coords, int 
     }
     L.bad = word.p;
     SA_HIP_CHECK(hipMemsetAsync(word.p, 0x7f, sizeof(int), s));
-    for (int t = 0; t < 5; ++t) {
+    for (int t = 0; t < EM_TYPES; ++t) {
         if (!count[t]) continue;
         if (kind) em_launch_type<1>(L, t, count[t], list[t].p);
         else em_launch_type<0>(L, t, count[t], list[t].p);

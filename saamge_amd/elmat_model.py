@@ -1,14 +1,25 @@
 """CPU model of the device element matrices (csrc/elmat.hip) -- numpy only, test infrastructure like capi.py.
 
 This file is the DEFINITION of the result: the device code restates it and must give the same bits.  Everything is written
-as single IEEE operations in a fixed order (no fused multiply-add, no library sums), vectorised over the elements only.
+as single IEEE operations in a fixed order (no fused multiply-add, no library sums), vectorised over the elements and, where
+every lane of the vector does the same operation, over the nodes and node pairs of an element (elementwise, so the roundings
+are those of the scalar formulas).
 
   types        (dim, nodes): (2, 3) P1 triangle, (2, 4) Q1 quadrilateral (v00, v10, v11, v01), (3, 4) P1 tetrahedron,
                (3, 6) P1 x P1 wedge (node a * 3 + i: triangle vertex i on the bottom a = 0 / top a = 1 face), (3, 8) Q1
-               hexahedron (vertex order HEX_LOC).  Anything else is refused.
+               hexahedron (vertex order HEX_LOC); order 2: (2, 9) Q2 quadrilateral (MFEM's H1 order: the vertices v00, v10,
+               v11, v01, the edge midpoints bottom, right, top, left, the centre -- tensor positions Q2_QUAD_LOC) and (3, 27)
+               Q2 hexahedron (lexicographic: node (iz * 3 + iy) * 3 + ix).  Anything else is refused.
+  geometry     isoparametric: the Jacobian below runs over ALL nodes of the element, so an order-2 element may be curved; a
+               straight-sided one has its extra nodes at the multilinear image of its corners.
   rule         reference elements [0, 1]^dim and the unit simplex; triangle, tetrahedron: 1 point; quadrilateral, hexahedron:
                2 Gauss points per axis (point q: axis d takes GAUSS[(q >> d) & 1]); wedge: point q = 3 * qz + qt, the 3-point
                degree-2 triangle rule times 2 Gauss points.  The points and the weight of a point are the literals below.
+  order 2      3 Gauss points per axis, GAUSS3 with the 1-D weights GAUSS3_W; point q = (qz * 3 + qy) * 3 + qx, its weight
+               (wx * wy) * wz (wx * wy in 2D).  The 1-D shape functions on the nodes 0, 1/2, 1 and their derivatives are the
+               expressions of _n2 and _d2; the gradient of node (ix, iy, iz) is (d(ix, px) * (n(iy, py) * n(iz, pz)),
+               d(iy, py) * (n(ix, px) * n(iz, pz)), d(iz, pz) * (n(ix, px) * n(iy, py))), in 2D (d(ix, px) * n(iy, py),
+               n(ix, px) * d(iy, py)).
   point        J[i][j] = sum over the nodes a, ascending, of x_a[i] * dN_a[j], the first product taken as it is; the cofactors
                C[i][j] and det from the explicit formulas of _cofactors; G_a[i] = sum_j dN_a[j] * C[i][j] (the physical
                gradient times det); s = weight / det (one division per point).
@@ -36,6 +47,13 @@ WEDGE_TRI = [(TRI_A, TRI_A), (TRI_B, TRI_A), (TRI_A, TRI_B)]
 WEIGHT = {(2, 3): 0.5, (2, 4): 0.25, (3, 4): 0.16666666666666666, (3, 6): 0.08333333333333333, (3, 8): 0.125}
 NPOINTS = {(2, 3): 1, (2, 4): 4, (3, 4): 1, (3, 6): 6, (3, 8): 8}
 TYPE_INDEX = {(2, 3): 0, (2, 4): 1, (3, 4): 2, (3, 6): 3, (3, 8): 4}      # info[0..4] of saamge_amd_element_matrices
+# ---- order 2 (their number is info[7])
+GAUSS3 = (0.11270166537925831, 0.5, 0.8872983346207417)  # 1/2 - sqrt(15)/10, 1/2, 1/2 + sqrt(15)/10
+GAUSS3_W = (0.2777777777777778, 0.4444444444444444, 0.2777777777777778)      # 5/18, 4/9, 5/18
+Q2_QUAD_LOC = [(0, 0), (2, 0), (2, 2), (0, 2), (1, 0), (2, 1), (1, 2), (0, 1), (1, 1)]
+Q2_HEX_LOC = [(ix, iy, iz) for iz in range(3) for iy in range(3) for ix in range(3)]
+ORDER2 = ((2, 9), (3, 27))
+NPOINTS.update({(2, 9): 9, (3, 27): 27})
 
 
 class ElementError(ValueError):
@@ -54,8 +72,42 @@ def _df(l):
     return 1.0 if l else -1.0
 
 
+def _n2(l, p):
+    """1-D order-2 shape function of node l (at 0, 1/2, 1) at p"""
+    if l == 0:
+        return (2.0 * p - 1.0) * (p - 1.0)
+    if l == 1:
+        return (4.0 * p) * (1.0 - p)
+    return p * (2.0 * p - 1.0)
+
+
+def _d2(l, p):
+    """its derivative"""
+    if l == 0:
+        return 4.0 * p - 3.0
+    if l == 1:
+        return 4.0 - 8.0 * p
+    return 4.0 * p - 1.0
+
+
+def point_weight(dim, nd, q):
+    """weight of point q of the type's rule"""
+    if (dim, nd) == (2, 9):
+        return GAUSS3_W[q % 3] * GAUSS3_W[q // 3]
+    if (dim, nd) == (3, 27):
+        return (GAUSS3_W[q % 3] * GAUSS3_W[(q // 3) % 3]) * GAUSS3_W[q // 9]
+    return WEIGHT[(dim, nd)]
+
+
 def reference_gradients(dim, nd, q):
     """dN[a][j] at point q of the type's rule, as Python floats."""
+    if (dim, nd) == (2, 9):
+        px, py = GAUSS3[q % 3], GAUSS3[q // 3]
+        return [(_d2(ix, px) * _n2(iy, py), _n2(ix, px) * _d2(iy, py)) for (ix, iy) in Q2_QUAD_LOC]
+    if (dim, nd) == (3, 27):
+        px, py, pz = GAUSS3[q % 3], GAUSS3[(q // 3) % 3], GAUSS3[q // 9]
+        return [(_d2(ix, px) * (_n2(iy, py) * _n2(iz, pz)), _d2(iy, py) * (_n2(ix, px) * _n2(iz, pz)),
+                 _d2(iz, pz) * (_n2(ix, px) * _n2(iy, py))) for (ix, iy, iz) in Q2_HEX_LOC]
     if (dim, nd) == (2, 3):
         return [tuple(d) for d in TRI_D]
     if (dim, nd) == (3, 4):
@@ -112,13 +164,14 @@ def _tensor(coef, dim):
 
 
 def _block(X, dim, nd, kind, coef):
-    """Matrices (n, size, size) of n elements of one type, and per element whether a det was not positive."""
+    """Matrices (n, size, size) of n elements of one type, and per element whether a det was not positive.  The node pairs
+    (a, b) with a <= b are the lanes of one vector: every line below is the scalar formula of the entry, elementwise."""
     n = X.shape[0]
     size = nd if kind == 0 else dim * nd
-    out = np.zeros((n, size, size))
     bad = np.zeros(n, bool)
-    w = WEIGHT[(dim, nd)]
     K = _tensor(coef, dim) if kind == 0 else None
+    pa, pb = np.triu_indices(nd)                                     # the pairs a <= b
+    acc = np.zeros((n, len(pa)) if kind == 0 else (n, len(pa), dim, dim))
     with np.errstate(all="ignore"):
         for q in range(NPOINTS[(dim, nd)]):
             dN = reference_gradients(dim, nd, q)
@@ -131,45 +184,41 @@ def _block(X, dim, nd, kind, coef):
                     J[i][j] = s
             C, det = _cofactors(J, dim)
             bad |= ~(det > 0.0)
-            s = w / det
-            G = []
-            for a in range(nd):
-                g = []
-                for i in range(dim):
-                    t = dN[a][0] * C[i][0] + dN[a][1] * C[i][1]
-                    if dim == 3:
-                        t = t + dN[a][2] * C[i][2]
-                    g.append(t)
-                G.append(g)
+            s = (point_weight(dim, nd, q) / det)[:, None]
+            dA = np.array(dN)                                        # (nd, dim)
+            G = []                                                   # G[i]: (n, nd), component i of every node's gradient
+            for i in range(dim):
+                t = dA[None, :, 0] * C[i][0][:, None] + dA[None, :, 1] * C[i][1][:, None]
+                if dim == 3:
+                    t = t + dA[None, :, 2] * C[i][2][:, None]
+                G.append(t)
+            Ga, Gb = [g[:, pa] for g in G], [g[:, pb] for g in G]
             if kind == 0:
                 F = []
-                for a in range(nd):
-                    f = []
-                    for i in range(dim):
-                        t = K[i][0] * G[a][0] + K[i][1] * G[a][1]
-                        if dim == 3:
-                            t = t + K[i][2] * G[a][2]
-                        f.append(t)
-                    F.append(f)
-                for a in range(nd):
-                    for b in range(a, nd):
-                        term = s * _dot(F[a], G[b], dim)
-                        out[:, a, b] = out[:, a, b] + term
+                for i in range(dim):
+                    t = K[i][0][:, None] * G[0] + K[i][1][:, None] * G[1]
+                    if dim == 3:
+                        t = t + K[i][2][:, None] * G[2]
+                    F.append(t[:, pa])
+                term = s * _dot(F, Gb, dim)
+                acc = acc + term
             else:
-                lam, mu = coef[:, 0], coef[:, 1]
-                for a in range(nd):
-                    for b in range(nd):
-                        md = mu * _dot(G[a], G[b], dim)
-                        for i in range(dim):
-                            for j in range(dim):
-                                r, c = dim * a + i, dim * b + j
-                                if r > c:
-                                    continue
-                                t = lam * (G[a][i] * G[b][j]) + mu * (G[a][j] * G[b][i])
-                                if i == j:
-                                    t = t + md
-                                term = s * t
-                                out[:, r, c] = out[:, r, c] + term
+                lam, mu = coef[:, 0][:, None], coef[:, 1][:, None]
+                md = mu * _dot(Ga, Gb, dim)
+                for i in range(dim):
+                    for j in range(dim):                             # (on a == b the entries with i > j are not used)
+                        t = lam * (Ga[i] * Gb[j]) + mu * (Ga[j] * Gb[i])
+                        if i == j:
+                            t = t + md
+                        term = s * t
+                        acc[:, :, i, j] = acc[:, :, i, j] + term
+    out = np.zeros((n, size, size))
+    if kind == 0:
+        out[:, pa, pb] = acc
+    else:
+        for i in range(dim):
+            for j in range(dim):
+                out[:, dim * pa + i, dim * pb + j] = acc[:, :, i, j]
     iu = np.triu_indices(size, 1)
     out[:, iu[1], iu[0]] = out[:, iu[0], iu[1]]
     return out, bad
@@ -204,7 +253,7 @@ def _mesh(coords, elem_to_vertex, elem_ptr):
     elem = np.repeat(np.arange(len(nd), dtype=np.int64), nd)
     if len(np.unique(elem * max(int(NV), 1) + e2v)) != len(e2v):
         raise ValueError("an element lists a vertex twice")
-    for e in np.flatnonzero(~np.isin(nd, [k[1] for k in TYPE_INDEX if k[0] == dim])):
+    for e in np.flatnonzero(~np.isin(nd, [k[1] for k in tuple(TYPE_INDEX) + ORDER2 if k[0] == dim])):
         raise ValueError("element %d: %d nodes are no supported element type in %dD" % (e, nd[e], dim))
     return X, dim, ep, e2v, nd
 
@@ -242,6 +291,13 @@ def type_counts(dim, elem_to_vertex, elem_ptr=None):
         if d == dim:
             out[t] = int((nd == k).sum())
     return out
+
+
+def order2_count(dim, elem_to_vertex, elem_ptr=None):
+    """the number of order-2 elements (info[7] of saamge_amd_element_matrices)"""
+    nd = np.diff(np.asarray(elem_ptr, np.int64)) if elem_ptr is not None else \
+        np.full(np.asarray(elem_to_vertex).shape[0], np.asarray(elem_to_vertex).shape[1])
+    return int(sum((nd == k).sum() for (d, k) in ORDER2 if d == dim))
 
 
 def dof_lists(dim, elem_to_vertex, kind, elem_ptr=None):

@@ -523,6 +523,16 @@ def hex_elasticity_matrix_tensor(h, order, lam=1.0, mu=1.0):
     return 0.5 * (Ke + Ke.T)
 
 
+def hex_diffusion_matrix_tensor(h, order, K=(1.0, 1.0, 1.0)):
+    """Stiffness of div(diag(K) grad) on an h[0] x h[1] x h[2] box with tensor-product Lagrange elements of the given order
+    (order 2: the 27-node hex), as Kronecker sums of the 1-D matrices; local numbering node = (iz * n1 + iy) * n1 + ix."""
+    M1, K1, _ = _lagrange_1d(order)
+    hx, hy, hz = h
+    return (K[0] * (hy * hz / hx) * np.kron(M1, np.kron(M1, K1)) +
+            K[1] * (hx * hz / hy) * np.kron(M1, np.kron(K1, M1)) +
+            K[2] * (hx * hy / hz) * np.kron(K1, np.kron(M1, M1)))
+
+
 def elasticity3d_q2_problem(n, blk=(2, 2, 2), lam=1.0, mu=1.0, order=2):
     """BASELINE config 5 in small: unit cube of n hexes with tensor-product elements of `order`
     (2: 27 nodes, 81 dofs per element), 3 displacement components per node (byVDIM), clamped
@@ -1048,3 +1058,45 @@ def quads_to_tris(nx, ny):
     v00, v10, v11, v01 = vid(ex, ey), vid(ex + 1, ey), vid(ex + 1, ey + 1), vid(ex, ey + 1)
     tris = np.stack([np.stack([v00, v10, v11], axis=1), np.stack([v00, v11, v01], axis=1)], axis=1)
     return np.ascontiguousarray(tris.reshape(-1, 3).astype(np.int32))
+
+
+# ---- order 2: the 27-node hex grid, and straight-sided elements from moved corners
+Q2_QUAD_LOC = [(0, 0), (2, 0), (2, 2), (0, 2), (1, 0), (2, 1), (1, 2), (0, 1), (1, 1)]      # quad_mesh_problem(order=2)
+Q2_HEX_LOC = [(ix, iy, iz) for iz in range(3) for iy in range(3) for ix in range(3)]        # elasticity3d_q2_problem
+
+
+def q2_hex_nodes(n):
+    """element -> node lists (NE x 27, lexicographic: local node (iz * 3 + iy) * 3 + ix) of the Q2 hex grid of
+    elasticity3d_q2_problem(n): the nodes are the (2 nx + 1)(2 ny + 1)(2 nz + 1) grid that grid_coords((2 nx, 2 ny, 2 nz))
+    numbers the same way."""
+    if np.isscalar(n):
+        n = (int(n),) * 3
+    nx, ny, nz = n
+    gx, gy = 2 * nx + 1, 2 * ny + 1
+    ez, ey, ex = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    ex, ey, ez = ex.ravel(), ey.ravel(), ez.ravel()
+    return np.ascontiguousarray(np.stack([((2 * ez + c) * gy + 2 * ey + b) * gx + 2 * ex + a for (a, b, c) in Q2_HEX_LOC],
+                                         axis=1).astype(np.int32))
+
+
+def q2_straight_sided(coords, elem_to_node):
+    """A copy of coords in which every node of a Q2 quad (9 nodes, Q2_QUAD_LOC) / hex (27 nodes, Q2_HEX_LOC) mesh that is no
+    corner vertex sits at the multilinear image of its element's corners: edge nodes at the average of two corners, face
+    nodes of four, the hex centre of eight.  Move the corners (jitter), then call this: the elements are straight-sided."""
+    X = np.array(coords, dtype=np.float64)
+    e2n = np.asarray(elem_to_node)
+    loc = np.array(Q2_QUAD_LOC if e2n.shape[1] == 9 else Q2_HEX_LOC)
+    assert e2n.shape[1] == 3 ** loc.shape[1] and X.shape[1] == loc.shape[1]
+    corner = {tuple(l): k for k, l in enumerate(loc.tolist()) if 1 not in l}
+    for k, l in enumerate(loc.tolist()):
+        if 1 not in l:
+            continue
+        ends = [[v] if v != 1 else [0, 2] for v in l]             # per axis: the corner positions this node lies between
+        combos = [[]]
+        for opts in ends:
+            combos = [c + [o] for c in combos for o in opts]
+        acc = X[e2n[:, corner[tuple(combos[0])]]]
+        for c in combos[1:]:
+            acc = acc + X[e2n[:, corner[tuple(c)]]]
+        X[e2n[:, k]] = acc / len(combos)
+    return X

@@ -5,10 +5,17 @@ beside the path this replaces: the element matrices generated on the host as pro
 scaled per element) and uploaded.  Host clock closed by a synchronise, one
 warm-up, `--reps` repetitions (all listed).  One JSON line per case.
 
-    python tools/elmat_time.py [--hex 128,256] [--elasticity 64] [--reps 3] [--hbm-gbs 8000] [--no-host]
+    python tools/elmat_time.py [--hex 128,256] [--elasticity 64] [--q2-hex 64,128] [--q2-elasticity 32,64] [--quad9 2048]
+                               [--reps 3] [--host-reps 3] [--hbm-gbs 8000] [--fp64-gops 39300] [--no-host]
 
 The vertices are jittered by 0.2 mesh widths, so no two elements are alike.  A case that does not fit is reported as skipped
 with the error.
+
+The order-2 cases (27-node hexes on n^3 elements, 9-node quadrilaterals on n^2; every node moved by 0.1 of the node spacing,
+so the elements are curved) also list `ops_per_element`: the unfused floating-point operations the definition
+(saamge_amd/elmat_model.py) spends on one element, counted from its formulas (arithmetic, not a measurement), and
+`compute_bound_ms`, that count at --fp64-gops (the fp64 vector rate with a fused multiply-add counted once: the kernel may
+not fuse).
 """
 import argparse
 import json
@@ -28,7 +35,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--hex", default="128,256")
     ap.add_argument("--elasticity", default="64")
+    ap.add_argument("--q2-hex", default="64,128")
+    ap.add_argument("--q2-elasticity", default="32,64")
+    ap.add_argument("--quad9", default="2048")
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--host-reps", type=int, default=None)
+    ap.add_argument("--fp64-gops", type=float, default=39300.0)
     ap.add_argument("--hbm-gbs", type=float, default=8000.0)
     ap.add_argument("--no-host", action="store_true")
     a = ap.parse_args()
@@ -59,12 +71,48 @@ def main():
                           dim=1).to(torch.int32).contiguous()
         return X, e2v, g
 
-    cases = [("hex_diffusion%d" % n, n, 0) for n in ints(a.hex)] + [("hex_elasticity%d" % n, n, 1) for n in ints(a.elasticity)]
-    for name, n, kind in cases:
+    def mesh_q2(n, dim):
+        """the (2 n + 1)^dim node grid with every node moved by 0.1 of the node spacing, and the node lists: the hex
+        lexicographic, the quadrilateral in MFEM's H1 order"""
+        gn = 2 * n + 1
+        ax = torch.arange(gn, device=dev, dtype=torch.float64) / (2 * n)
+        shape = (gn,) * dim
+        X = torch.stack([ax.view([-1 if k == dim - 1 - d else 1 for k in range(dim)]).expand(shape).reshape(-1)
+                         for d in range(dim)], dim=1)
+        g = torch.Generator(device=dev)
+        g.manual_seed(7)
+        X = (X + (2.0 * torch.rand(X.shape, generator=g, device=dev, dtype=torch.float64) - 1.0) * (0.1 / (2 * n))).contiguous()
+        if dim == 3:
+            ez = torch.arange(n, device=dev).view(-1, 1, 1)
+            ey = torch.arange(n, device=dev).view(1, -1, 1)
+            ex = torch.arange(n, device=dev).view(1, 1, -1)
+            lists = [(((2 * ez + c) * gn + (2 * ey + b)) * gn + (2 * ex + a_)).reshape(-1) for (a_, b, c) in problems.Q2_HEX_LOC]
+        else:
+            ey = torch.arange(n, device=dev).view(-1, 1)
+            ex = torch.arange(n, device=dev).view(1, -1)
+            lists = [((2 * ey + b) * gn + (2 * ex + a_)).reshape(-1) for (a_, b) in problems.Q2_QUAD_LOC]
+        return X, torch.stack(lists, dim=1).to(torch.int32).contiguous(), g
+
+    def ops_per_element(dim, nd, kind):
+        """unfused operations of the definition for one element: per point the Jacobian, cofactors, determinant and the one
+        division, per (point, node) G_a (and F_a), per (point, node pair a <= b) the entry's term and its addition"""
+        nq, pairs, dot = nd, nd * (nd + 1) // 2, 2 * dim - 1
+        point = dim * dim * (2 * nd - 1) + (33 if dim == 3 else 6)
+        node = dim * dot * (1 if kind else 2)
+        pair = dot + 1 + 3 * dim * dim + 3 * dim * dim + dim if kind else dot + 2
+        return nq * (point + nd * node + pairs * pair)
+
+    host_reps = a.reps if a.host_reps is None else a.host_reps
+    cases = [("hex_diffusion%d" % n, n, 0, 3, 8) for n in ints(a.hex)] + \
+            [("hex_elasticity%d" % n, n, 1, 3, 8) for n in ints(a.elasticity)] + \
+            [("q2_hex_diffusion%d" % n, n, 0, 3, 27) for n in ints(a.q2_hex)] + \
+            [("q2_hex_elasticity%d" % n, n, 1, 3, 27) for n in ints(a.q2_elasticity)] + \
+            [("quad9_diffusion%d" % n, n, 0, 2, 9) for n in ints(a.quad9)]
+    for name, n, kind, dim, nd in cases:
         try:
-            X, e2v, g = mesh(n)
-            NE = n ** 3
-            size = 24 if kind else 8
+            X, e2v, g = mesh(n) if nd == 8 else mesh_q2(n, dim)
+            NE = n ** dim
+            size = nd * (dim if kind else 1)
             coef = 0.5 + 1.5 * torch.rand((NE, 2) if kind else (NE,), generator=g, device=dev, dtype=torch.float64)
             out = torch.zeros(NE * size * size, dtype=torch.float64, device=dev)
             run = lambda: capi.element_matrices(X, e2v, kind, coef, device=True, out=out, stream=stream())
@@ -76,14 +124,22 @@ def main():
             rec = {"case": name, "elements": NE, "matrix_size": size, "output_bytes": int(out_bytes), "input_bytes": int(in_bytes),
                    "device_ms": [round(x, 3) for x in t_dev], "hbm_bound_ms": round(bound_ms, 3),
                    "fraction_of_bound": round(bound_ms / min(t_dev), 3)}
+            if nd != 8:
+                rec["ops_per_element"] = ops_per_element(dim, nd, kind)
+                rec["compute_bound_ms"] = round(1e3 * NE * rec["ops_per_element"] / (a.fp64_gops * 1e9), 3)
             if not a.no_host:
                 # what a driver without this call does: the matrices on the host (here the cheapest generator there is, one
                 # box matrix scaled per element -- an integrator call per element costs more), then the upload
                 h = (1.0 / n,) * 3
-                Kref = problems.hex_elasticity_matrix(h) if kind else problems.hex_element_matrix(h)
+                if nd == 8:
+                    Kref = problems.hex_elasticity_matrix(h) if kind else problems.hex_element_matrix(h)
+                elif nd == 27:
+                    Kref = problems.hex_elasticity_matrix_tensor(h, 2) if kind else problems.hex_diffusion_matrix_tensor(h, 2)
+                else:
+                    Kref = problems.quad_mesh_problem(1, 1, order=2, coef=1.0).elmat[0]      # (the square's: it scales with h^0)
                 c = coef.reshape(NE, -1)[:, 0].cpu().numpy()
                 t_gen, t_up = [], []
-                for _ in range(a.reps):
+                for _ in range(host_reps):
                     t = time.perf_counter()
                     host = np.ascontiguousarray(c[:, None, None] * Kref[None, :, :])
                     t_gen.append(1e3 * (time.perf_counter() - t))
