@@ -433,6 +433,28 @@ int saamge_amd_ae_order(int ND, int NE, int nde, const int *elem_ptr, const int 
 int saamge_amd_element_matrices(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                                 const int *elem_to_vertex, int kind, int ncoef, const double *coef, void *stream,
                                 double *elmat_out, int *dof_ptr_out, int *elem_to_dof_out, long long info[8]);
+/* ---- mass matrices and load vectors computed on the device (csrc/elmat.hip) ----
+ * The zeroth-order forms on the types, node orders and isoparametric geometry of saamge_amd_element_matrices, so that the
+ * right-hand side and sigma M + K never exist on the host either; saamge_amd/elmat_model.py (element_mass, element_loads)
+ * defines every operation and the device gives the same bits.  The rule of a type is its rule above, except three points on the
+ * triangle and four on the tetrahedron (exact for the P1 mass on affine simplices).  vdim 1: one dof per node; vdim = dim: dof
+ * dim * node + component, the layout of elasticity.  coef: NE doubles, c of (c u, v).
+ * saamge_amd_element_mass: elmat_inout in the packed layout above (element e: size_e x size_e at sum_{f<e} size_f^2, size_e =
+ * vdim * nodes); the components do not couple (an entry between two components is + 0.0).  accumulate != 0: the matrices are
+ * ADDED to what elmat_inout holds, one addition per entry -- K + sigma M from the output of saamge_amd_element_matrices of
+ * the same mesh and layout, with sigma in coef.  elmat_inout NULL (accumulate 0): the sizes only.
+ * saamge_amd_element_loads: src NV x vdim, the source at the nodes; coef NULL: 1.  elvec_out packed, element e: size_e doubles at
+ * sum_{f<e} size_f (NULL: the sizes only); saamge_amd_operator_assemble_rhs takes it.
+ * Any pointer host or device, each on its own.  info as above, [5] = doubles written.
+ * Refused, before anything touches the device: vdim not 1 or dim, NULL coef for the mass, NULL src, accumulate with NULL
+ * elmat_inout; and everything saamge_amd_element_matrices refuses of the mesh, the first element with a non-positive Jacobian
+ * determinant at a point of the mass rule in info[6]. */
+int saamge_amd_element_mass(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                            const int *elem_to_vertex, int vdim, const double *coef, void *stream, int accumulate,
+                            double *elmat_inout, long long info[8]);
+int saamge_amd_element_loads(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                             const int *elem_to_vertex, int vdim, const double *coef, const double *src, void *stream,
+                             double *elvec_out, long long info[8]);
 /* R = P^T (P nrows x ncols) */
 int saamge_amd_csr_transpose(int nrows, int ncols, const int *rowptr, const int *col, const double *val, int *Rrow,
                              long long *Rnnz, int *Rcol, double *Rval);
@@ -585,6 +607,10 @@ int  saamge_amd_operator_get(const saamge_amd_operator *op, long long *rowptr, i
 int  saamge_amd_operator_update(saamge_amd_operator *op, const double *elmat);
 /* b (n, in place) for essential values x_ess (n, read at essential dofs only); elmat = the matrices of the operator */
 int  saamge_amd_operator_eliminate_rhs(const saamge_amd_operator *op, const double *elmat, const double *x_ess, double *b);
+/* b (n, overwritten) from packed element vectors (element e: nd_e doubles at elem_ptr[e], the output of
+ * saamge_amd_element_loads on the mesh of the operator): b_i the sum of the terms of dof i in ascending element id.  Essential
+ * dofs are assembled like any other; saamge_amd_operator_eliminate_rhs overwrites them afterwards.  Host or device pointers. */
+int  saamge_amd_operator_assemble_rhs(const saamge_amd_operator *op, const double *elvec, double *b);
 void saamge_amd_operator_free(saamge_amd_operator *op);
 /* Rows by the path they took: counts[0 .. 2] the symbolic pass (several rows per wavefront; one workgroup per row with the
  * candidates in LDS; through global memory), counts[3 .. 5] the numeric pass (the same three). */

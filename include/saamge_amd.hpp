@@ -342,6 +342,30 @@ inline ElementMatrices element_matrices(int NV, int dim, const double *coords, i
     return r;
 }
 
+// == mass matrices and load vectors computed on the device (saamge_amd_element_mass, saamge_amd_element_loads) ==
+// Into the caller's arrays, each a host or a device pointer.  vdim 1 or dim; coef NE doubles.  accumulate: added to the
+// matrices elmat_inout holds (K + sigma M); elmat_inout == nullptr without accumulate: the sizes only.
+inline ElementMatricesInfo element_mass_into(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                             const int *elem_to_vertex, int vdim, const double *coef, double *elmat_inout,
+                                             bool accumulate = false, void *stream = nullptr) {
+    long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (saamge_amd_element_mass(NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, coef, stream, accumulate ? 1 : 0,
+                                elmat_inout, info))
+        throw std::runtime_error(saamge_amd_last_error());
+    const ElementMatricesInfo r = {info[0], info[1], info[2], info[3], info[4], info[5], info[6], info[7]};
+    return r;
+}
+// src: the source at the nodes (NV x vdim); coef == nullptr: 1.  elvec_out: element e's vdim * nodes doubles, packed.
+inline ElementMatricesInfo element_loads_into(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                              const int *elem_to_vertex, int vdim, const double *coef, const double *src,
+                                              double *elvec_out, void *stream = nullptr) {
+    long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (saamge_amd_element_loads(NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, coef, src, stream, elvec_out, info))
+        throw std::runtime_error(saamge_amd_last_error());
+    const ElementMatricesInfo r = {info[0], info[1], info[2], info[3], info[4], info[5], info[6], info[7]};
+    return r;
+}
+
 // == the operator assembled on the device (saamge_amd_operator_assemble) ==
 // Owner of the handle.  rowptr() / col() / val() are device arrays that live as long as this object: hand them to
 // saamge_amd_ml_produce_data64 / _mixed64 as A.  elem_ptr == nullptr: every element has nde dofs.
@@ -377,6 +401,10 @@ public:
     }
     void eliminate_rhs(const double *elmat, const double *x_ess, double *b) const {
         if (saamge_amd_operator_eliminate_rhs(op_, elmat, x_ess, b)) throw std::runtime_error(saamge_amd_last_error());
+    }
+    // b (n, overwritten) from the packed element vectors of element_loads_into on the operator's mesh
+    void assemble_rhs(const double *elvec, double *b) const {
+        if (saamge_amd_operator_assemble_rhs(op_, elvec, b)) throw std::runtime_error(saamge_amd_last_error());
     }
 
 private:

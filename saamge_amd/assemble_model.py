@@ -111,3 +111,18 @@ def eliminate_rhs(n, elem_ptr, elem_to_dof, elmat, bdr, x_ess, b):
     diag = np.flatnonzero((row == col) & ess[row])
     out[row[diag]] = val[diag] * x[row[diag]]
     return out
+
+
+def assemble_rhs(n, elem_ptr, elem_to_dof, elvec):
+    """b (n,): b_i the sum of the element terms of dof i in ascending element id, the first term taken as it is
+    (_sum_in_order's rule).  elvec packed in element order (element e at sum_{f<e} nd_f), or (NE, nde) without elem_ptr.
+    Essential dofs are assembled like any other; eliminate_rhs overwrites them afterwards."""
+    ep, e2d, nd = _mesh(n, elem_ptr, elem_to_dof)
+    term = np.asarray(elvec, np.float64).ravel()
+    if len(term) != len(e2d):
+        raise ValueError("elvec: sum of nd_e entries are needed")
+    order = np.argsort(e2d, kind="stable")                           # packed order is element order: stable keeps it
+    key = e2d[order]
+    start = np.flatnonzero(np.concatenate([[True], key[1:] != key[:-1]])) if len(key) else np.zeros(0, np.int64)
+    size = np.diff(np.concatenate([start, [len(key)]]))
+    return _sum_in_order(term[order], start, size)                   # (_mesh refuses a dof in no element: n groups)

@@ -40,6 +40,7 @@ SYMBOLS = [
     "saamge_amd_operator_eliminate_rhs", "saamge_amd_operator_free", "saamge_amd_operator_path_counts",
     "saamge_amd_operator_set_path_limits",
     "saamge_amd_level_order_info", "saamge_amd_ae_order", "saamge_amd_element_matrices",
+    "saamge_amd_element_mass", "saamge_amd_element_loads", "saamge_amd_operator_assemble_rhs",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong))
@@ -804,6 +805,78 @@ def element_matrices(coords, elem_to_vertex, kind, coef, elem_ptr=None, device=F
     return (elmat, dof_ptr, e2d) if dofs else elmat
 
 
+def _mass_call(fn, info):
+    rc = fn()
+    if rc != 0:
+        err = RuntimeError("saamge_amd: " + load().saamge_amd_last_error().decode())
+        err.info = [int(v) for v in info]
+        raise err
+    return [int(v) for v in info]
+
+
+def _mass_sizes(coords, e2v, ep, vdim, square):
+    """(NV, dim, NE, nde, doubles of the packed result)"""
+    NV, dim = int(coords.shape[0]), int(coords.shape[1])
+    if ep is None:
+        NE, nde = int(e2v.shape[0]), int(e2v.shape[1])
+        return NV, dim, NE, nde, NE * (nde * vdim) ** 2 if square else NE * nde * vdim
+    nd = (ep[1:] - ep[:-1]) * vdim
+    nd = nd.long() if hasattr(nd, "data_ptr") else nd.astype(np.int64)
+    return NV, dim, len(ep) - 1, 0, int((nd ** 2).sum()) if square else int(nd.sum())
+
+
+def _new_doubles(n, device):
+    if device:
+        import torch
+        return torch.zeros(n, dtype=torch.float64, device="cuda")
+    return np.zeros(max(n, 1), np.float64)[:n]
+
+
+def element_mass(coords, elem_to_vertex, coef, vdim=1, elem_ptr=None, add_to=None, device=False, out=None, stream=0,
+                 sizes_only=False):
+    """saamge_amd_element_mass: the mass matrices (c u, v) of a mesh, c = coef (NE,), on the types and in the layout of
+    `element_matrices`; vdim 1, or dim for the dof layout of elasticity.  add_to: an array / tensor that holds matrices of that
+    layout (the output of `element_matrices`); the mass matrices are added to it IN PLACE and it is returned -- K + sigma M with
+    sigma in coef.  Otherwise as `element_matrices`: inputs numpy arrays or device tensors, each on its own; device=True: a
+    torch tensor on the GPU; out: doubles to write into.  sizes_only: info (8 integers), nothing written.  A refusal raises
+    RuntimeError with `.info`."""
+    coords, e2v, coef, ep = _element_arrays(coords, elem_to_vertex, coef, elem_ptr)
+    vdim = int(vdim)
+    NV, dim, NE, nde, doubles = _mass_sizes(coords, e2v, ep, vdim, True)
+    info = (C.c_longlong * 8)()
+    if sizes_only:
+        elmat = None
+    elif add_to is not None:
+        elmat = add_to
+    else:
+        elmat = out if out is not None else _new_doubles(doubles, device)
+    got = _mass_call(lambda: load().saamge_amd_element_mass(
+        C.c_int(NV), C.c_int(dim), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_int(vdim), _ptr(coef),
+        C.c_void_p(stream), C.c_int(1 if add_to is not None else 0), _ptr(elmat), info), info)
+    if sizes_only:
+        return got
+    if ep is None and add_to is None:
+        elmat = elmat.reshape(NE, nde * vdim, nde * vdim)
+    return elmat
+
+
+def element_loads(coords, elem_to_vertex, src, vdim=1, coef=None, elem_ptr=None, device=False, out=None, stream=0):
+    """saamge_amd_element_loads: the load vectors (c f, v) of the source f given at the nodes, src (NV, vdim) or (NV,); coef
+    (NE,), None: 1.  Returns (NE, size) or, with elem_ptr, the packed vectors `Operator.assemble_rhs` takes; device=, out=,
+    stream= as in `element_matrices`."""
+    coords, e2v, coef, ep = _element_arrays(coords, elem_to_vertex, coef, elem_ptr)
+    if src is not None and not hasattr(src, "data_ptr"):
+        src = np.ascontiguousarray(src, dtype=np.float64)
+    vdim = int(vdim)
+    NV, dim, NE, nde, doubles = _mass_sizes(coords, e2v, ep, vdim, False)
+    info = (C.c_longlong * 8)()
+    elvec = out if out is not None else _new_doubles(doubles, device)
+    _mass_call(lambda: load().saamge_amd_element_loads(
+        C.c_int(NV), C.c_int(dim), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_int(vdim), _ptr(coef),
+        _ptr(src), C.c_void_p(stream), _ptr(elvec), info), info)
+    return elvec.reshape(NE, nde * vdim) if ep is None else elvec
+
+
 def get_options():
     o = Options()
     load().saamge_amd_get_options(C.byref(o))
@@ -1067,6 +1140,16 @@ class Operator(object):
         if not hasattr(elmat, "data_ptr"):
             elmat = np.ascontiguousarray(elmat, dtype=np.float64)
         _check(load().saamge_amd_operator_eliminate_rhs(self.h, _ptr(elmat), _ptr(x_ess), _ptr(b)))
+        return b
+
+    def assemble_rhs(self, elvec, b=None, device=False):
+        """b (n, overwritten; a new numpy array, or device tensor with device=True, when None) from the packed element vectors
+        of `element_loads` on the operator's mesh (host array or device tensor); returns b."""
+        if not hasattr(elvec, "data_ptr"):
+            elvec = np.ascontiguousarray(elvec, dtype=np.float64)
+        if b is None:
+            b = _new_doubles(self.n, device)
+        _check(load().saamge_amd_operator_assemble_rhs(self.h, _ptr(elvec), _ptr(b)))
         return b
 
     def path_counts(self):

@@ -809,6 +809,26 @@ int saamge_amd_element_matrices(int NV, int dim, const double *coords, int NE, i
     SA_API_END
 }
 
+int saamge_amd_element_mass(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                            const int *elem_to_vertex, int vdim, const double *coef, void *stream, int accumulate,
+                            double *elmat_inout, long long info[8]) {
+    SA_API_BEGIN
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    element_mass(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, coef, accumulate, elmat_inout, info);
+    SA_API_END
+}
+
+int saamge_amd_element_loads(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                             const int *elem_to_vertex, int vdim, const double *coef, const double *src, void *stream,
+                             double *elvec_out, long long info[8]) {
+    SA_API_BEGIN
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    element_loads(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, coef, src, elvec_out, info);
+    SA_API_END
+}
+
 int saamge_amd_csr_transpose(int nrows, int ncols, const int *rowptr, const int *col, const double *val, int *Rrow,
                              long long *Rnnz, int *Rcol, double *Rval) {
     SA_API_BEGIN
@@ -1273,6 +1293,20 @@ int saamge_amd_operator_eliminate_rhs(const saamge_amd_operator *op, const doubl
         VecIn vx(x_ess, (size_t)o.n, o.stream);
         VecOut vb(b, (size_t)o.n, o.stream, true);
         operator_eliminate_rhs(o, elmat, vx.p, vb.p);
+        vb.finish();
+    }
+    SA_API_END
+}
+
+int saamge_amd_operator_assemble_rhs(const saamge_amd_operator *op, const double *elvec, double *b) {
+    SA_API_BEGIN
+    SA_REQUIRE(op && b, "null argument");
+    const AssembledOperator &o = op->op;
+    require_operator_device(o);
+    ThreadStreamScope scope(o.stream);
+    {
+        VecOut vb(b, (size_t)o.n, o.stream, false);
+        operator_assemble_rhs(o, elvec, vb.p);
         vb.finish();
     }
     SA_API_END

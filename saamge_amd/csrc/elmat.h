@@ -12,4 +12,13 @@ void element_matrices(hipStream_t s, int NV, int dim, const double *coords, int 
                       const int *elem_to_vertex, int kind, int ncoef, const double *coef, double *elmat_out, int *dof_ptr_out,
                       int *elem_to_dof_out, long long info[8]);
 
+// The arguments of saamge_amd_element_mass: the mass matrices with the per-element coefficient coef, vdim 1 or dim; accumulate:
+// added to the matrices elmat_inout holds.  elmat_model.element_mass defines the result.
+void element_mass(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                  const int *elem_to_vertex, int vdim, const double *coef, int accumulate, double *elmat_inout, long long info[8]);
+// The arguments of saamge_amd_element_loads: the load vectors of the nodal source src (NV x vdim); coef NULL: 1.0.
+void element_loads(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                   const int *elem_to_vertex, int vdim, const double *coef, const double *src, double *elvec_out,
+                   long long info[8]);
+
 }  // namespace saamge_amd

@@ -15,6 +15,9 @@
 //
 // The order-2 quadrilateral (9 nodes) and hexahedron (27 nodes) have their own kernel, em2_kernel, with its own decomposition
 // (27 divides no wavefront and a node's row block of the hex is 243 accumulators): lanes own ENTRIES, see there.
+//
+// The zeroth-order forms -- mass matrices, with or without a target they are added to, and load vectors of a nodal source --
+// have a kernel family of their own for all seven types (mass_kernel, load_kernel) in em2_kernel's phase structure.
 #include "elmat.h"
 
 #include <algorithm>
@@ -600,6 +603,331 @@ __global__ __launch_bounds__((Em2Cfg<DIM, KIND>::BLOCK)) void em2_kernel(int cou
     }
 }
 
+// ---- mass matrices and load vectors ------------------------------------------------------------------------------------------
+// elmat_model.py's element_mass / element_loads.  The rule of a type is its stiffness rule, except for the simplices: three
+// points (EM_WEDGE_TRI, weight 1/6) on the triangle and four (EM_TET_A / EM_TET_B, weight 1/24) on the tetrahedron.
+constexpr double EM_TET_A = 0.1381966011250105, EM_TET_B = 0.5854101966249685;
+constexpr int mass_points(int dim, int nd) { return nd == 9 || nd == 27 ? nd : (dim == 2 ? (nd == 3 ? 3 : 4) : (nd == 4 ? 4 : nd)); }
+
+// the rule's table, folded at compile time: reference gradients and shape values of node a at point q (dN node-major as in
+// Em2Table, N point-major: the entry phase reads N of neighbouring nodes at one point) and the weight of point q
+template <int DIM, int ND>
+struct MassTable {
+    static constexpr int NQ = mass_points(DIM, ND);
+    double dN[ND][NQ][DIM];
+    double N[NQ][ND];
+    double w[NQ];
+};
+template <int DIM, int ND>
+constexpr MassTable<DIM, ND> mass_table() {
+    MassTable<DIM, ND> t{};
+    constexpr int NQ = MassTable<DIM, ND>::NQ;
+    if constexpr (ND == em2_nodes(DIM)) {
+        const Em2Table<DIM> g = em2_table<DIM>();
+        for (int q = 0; q < NQ; ++q) {
+            const double px = EM2_GAUSS[q % 3], py = EM2_GAUSS[(q / 3) % 3], pz = EM2_GAUSS[q / 9];
+            t.w[q] = g.w[q];
+            for (int a = 0; a < ND; ++a) {
+                for (int j = 0; j < DIM; ++j) t.dN[a][q][j] = g.dN[a][q][j];
+                if (DIM == 2)
+                    t.N[q][a] = em2_n(EM2_QUAD_LOC[a % 9][0], px) * em2_n(EM2_QUAD_LOC[a % 9][1], py);
+                else
+                    t.N[q][a] = em2_n(a % 3, px) * (em2_n((a / 3) % 3, py) * em2_n(a / 9, pz));
+            }
+        }
+    } else {
+        for (int q = 0; q < NQ; ++q) {
+            const EmGrad<DIM, ND> g = em_ref_grad<DIM, ND>(q);     // (the simplices': the same at every point)
+            for (int a = 0; a < ND; ++a)
+                for (int j = 0; j < DIM; ++j) t.dN[a][q][j] = g.v[a][j];
+            t.w[q] = EmType<DIM, ND>::W;
+            if constexpr (DIM == 2 && ND == 3) {
+                const double x = EM_WEDGE_TRI[q][0], y = EM_WEDGE_TRI[q][1];
+                t.w[q] = 0.16666666666666666;
+                t.N[q][0] = (1.0 - x) - y;
+                t.N[q][1] = x;
+                t.N[q][2] = y;
+            } else if constexpr (DIM == 3 && ND == 4) {
+                const double x = q == 1 ? EM_TET_B : EM_TET_A, y = q == 2 ? EM_TET_B : EM_TET_A, z = q == 3 ? EM_TET_B : EM_TET_A;
+                t.w[q] = 0.041666666666666664;
+                t.N[q][0] = ((1.0 - x) - y) - z;
+                t.N[q][1] = x;
+                t.N[q][2] = y;
+                t.N[q][3] = z;
+            } else if constexpr (DIM == 2 && ND == 4) {
+                const double px = EM_GAUSS[q & 1], py = EM_GAUSS[(q >> 1) & 1];
+                for (int a = 0; a < 4; ++a) t.N[q][a] = em_f(EM_QUAD_LOC[a][0], px) * em_f(EM_QUAD_LOC[a][1], py);
+            } else if constexpr (DIM == 3 && ND == 8) {
+                const double px = EM_GAUSS[q & 1], py = EM_GAUSS[(q >> 1) & 1], pz = EM_GAUSS[(q >> 2) & 1];
+                for (int a = 0; a < 8; ++a)
+                    t.N[q][a] = em_f(EM_HEX_LOC[a][0], px) * (em_f(EM_HEX_LOC[a][1], py) * em_f(EM_HEX_LOC[a][2], pz));
+            } else {
+                const double xi = EM_WEDGE_TRI[q % 3][0], eta = EM_WEDGE_TRI[q % 3][1], zeta = EM_GAUSS[q / 3];
+                const double T[3] = {(1.0 - xi) - eta, xi, eta};
+                const double L[2] = {1.0 - zeta, zeta};
+                for (int a = 0; a < 2; ++a)
+                    for (int i = 0; i < 3; ++i) t.N[q][a * 3 + i] = T[i] * L[a];
+            }
+        }
+    }
+    return t;
+}
+template <int DIM, int ND>
+__device__ const MassTable<DIM, ND> MASS_TABLE = mass_table<DIM, ND>();
+
+// the node pairs a <= b of an element, row by row: a * 32 + b
+template <int ND>
+struct MassPairs {
+    unsigned short ab[ND * (ND + 1) / 2];
+};
+template <int ND>
+constexpr MassPairs<ND> mass_pairs() {
+    MassPairs<ND> p{};
+    int k = 0;
+    for (int a = 0; a < ND; ++a)
+        for (int b = a; b < ND; ++b) p.ab[k++] = (unsigned short)(a * 32 + b);
+    return p;
+}
+template <int ND>
+__device__ const MassPairs<ND> MASS_PAIRS = mass_pairs<ND>();
+
+constexpr int MASS_BLOCK = 256;
+// elements per workgroup: a tile of at most 24 KB, at most 32 elements; the order-2 hexahedron of the vector form alone (52 KB)
+constexpr int mass_epb(int nd, int vdim) {
+    const int e = 24576 / (nd * vdim * nd * vdim * 8);
+    return e < 1 ? 1 : (e > 32 ? 32 : e);
+}
+constexpr int load_epb(int nd) { return nd >= 27 ? 8 : (nd >= 8 ? 16 : 32); }
+
+// The first phases of both kernels (em2_kernel's, for every type), a barrier after each:
+//   J       one lane per (element, point, i, j): J[i][j], the sum over the nodes in ascending order
+//   point   one lane per (element, point): det from the cofactors (not positive: the element id to *bad),
+//           s = (weight * det) * c -- no division
+// Order 1 (at most 8 nodes): the lane of a point forms its whole Jacobian in registers -- per node 6 doubles from LDS feed 9
+// products, where a lane per J[i][j] reads 2 doubles per product and the phase waits for LDS -- and goes on to the point's
+// det without a barrier; J[i][j] is the same sum in the same order.
+// sX: the nodes' coordinates, sD: the rule's reference gradients (dN[a][q][j], the LDS copy mass_stage made: a lane of J
+// reads ND of them at addresses that differ from lane to lane, which the vector memory path serves a few lanes per clock),
+// sC: c per element, sE: the element of a slot (-1: none); sJ and sD may lie over anything that is written after the barrier
+// that follows.
+template <int DIM, int ND, int EPB>
+__device__ inline void mass_point_phases(const double *sX, const double *sD, const double *sC, const int *sE, double *sJ, double *sS,
+                                         int *bad) {
+    constexpr int NQ = MassTable<DIM, ND>::NQ, DD = DIM * DIM;
+    const MassTable<DIM, ND> &T = MASS_TABLE<DIM, ND>;
+    const int tid = threadIdx.x;
+    constexpr bool WHOLE = ND <= 8;
+    if constexpr (!WHOLE) {
+        for (int idx = tid; idx < EPB * NQ * DD; idx += MASS_BLOCK) {
+            const int el = idx / (NQ * DD), r = idx - el * (NQ * DD), q = r / DD, ij = r - q * DD, i = ij / DIM, j = ij - i * DIM;
+            const double *X = sX + el * ND * DIM + i, *D = sD + q * DIM + j;
+            double t = X[0] * D[0];
+            for (int a = 1; a < ND; ++a) t = t + X[a * DIM] * D[a * NQ * DIM];
+            sJ[idx] = t;
+        }
+        __syncthreads();
+    }
+    for (int idx = tid; idx < EPB * NQ; idx += MASS_BLOCK) {
+        const int el = idx / NQ, q = idx - el * NQ;
+        double J[DIM][DIM], det;
+        if constexpr (WHOLE) {
+            const double *X = sX + el * ND * DIM, *D = sD + q * DIM;
+#pragma unroll
+            for (int a = 0; a < ND; ++a)
+#pragma unroll
+                for (int i = 0; i < DIM; ++i)
+#pragma unroll
+                    for (int j = 0; j < DIM; ++j) {
+                        const double p = X[a * DIM + i] * D[a * NQ * DIM + j];
+                        J[i][j] = a ? J[i][j] + p : p;
+                    }
+        } else {
+#pragma unroll
+            for (int i = 0; i < DIM; ++i)
+#pragma unroll
+                for (int j = 0; j < DIM; ++j) J[i][j] = sJ[idx * DD + i * DIM + j];
+        }
+        if constexpr (DIM == 2) {
+            det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+        } else {
+            const double C00 = J[1][1] * J[2][2] - J[1][2] * J[2][1];
+            const double C01 = J[1][2] * J[2][0] - J[1][0] * J[2][2];
+            const double C02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
+            det = (J[0][0] * C00 + J[0][1] * C01) + J[0][2] * C02;
+        }
+        if (!(det > 0.0) && sE[el] >= 0) atomicMin(bad, sE[el]);
+        sS[idx] = (T.w[q] * det) * sC[el];
+    }
+    __syncthreads();
+}
+
+// stage of both kernels: coordinates, coefficient (coef nullptr: 1.0), element id, the rule's shape values and reference
+// gradients; src (nullptr: none): the nodal source (NV x VDIM) of the nodes to sF
+template <int DIM, int ND, int VDIM, int EPB>
+__device__ inline void mass_stage(int count, const int *__restrict__ list, const int *__restrict__ eI, const int *__restrict__ eJ,
+                                  const double *__restrict__ coords, const double *__restrict__ coef,
+                                  const double *__restrict__ src, double *sX, double *sC, int *sE, double *sN, double *sD,
+                                  double *sF) {
+    constexpr int NQ = MassTable<DIM, ND>::NQ;
+    const int tid = threadIdx.x;
+    for (int idx = tid; idx < EPB * ND; idx += MASS_BLOCK) {
+        const int el = idx / ND, a = idx - el * ND;
+        const long slot = (long)blockIdx.x * EPB + el;
+        double x[DIM], f[VDIM];
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) x[d] = 0.0;
+#pragma unroll
+        for (int i = 0; i < VDIM; ++i) f[i] = 0.0;
+        if (slot < count) {
+            const int e = list ? list[slot] : (int)slot;
+            const long vb = eI ? (long)eI[e] : (long)e * ND;
+            const int v = eJ[vb + a];
+#pragma unroll
+            for (int d = 0; d < DIM; ++d) x[d] = coords[(long)v * DIM + d];
+            if (src) {
+#pragma unroll
+                for (int i = 0; i < VDIM; ++i) f[i] = src[(long)v * VDIM + i];
+            }
+            if (a == 0) {
+                sE[el] = e;
+                sC[el] = coef ? coef[e] : 1.0;
+            }
+        } else if (a == 0) {
+            sE[el] = -1;
+            sC[el] = 0.0;
+        }
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) sX[idx * DIM + d] = x[d];
+        if (src) {
+#pragma unroll
+            for (int i = 0; i < VDIM; ++i) sF[idx * VDIM + i] = f[i];
+        }
+    }
+    const double *N = &MASS_TABLE<DIM, ND>.N[0][0];
+    for (int idx = tid; idx < NQ * ND; idx += MASS_BLOCK) sN[idx] = N[idx];
+    const double *D = &MASS_TABLE<DIM, ND>.dN[0][0][0];
+    for (int idx = tid; idx < ND * NQ * DIM; idx += MASS_BLOCK) sD[idx] = D[idx];
+    __syncthreads();
+}
+
+// The mass matrices.  list, eI, moff, out: as in em_kernel; out holds the matrices to add to when accumulate.  Phases:
+//   stage, J, point   above
+//   fill    (vector form or accumulate) the tile from zeros or from the target, as consecutive doubles; an entry between two
+//           components gets its + 0.0 here
+//   entry   one lane per (element, node pair a <= b): the whole sum over the points, in ascending order, lives in the lane; it
+//           goes (is added) to the tile at (a, b) and (b, a) of every component
+//   tile    written out as consecutive doubles
+template <int DIM, int ND, int VDIM>
+__global__ __launch_bounds__(MASS_BLOCK) void mass_kernel(int count, const int *__restrict__ list, const int *__restrict__ eI,
+                                                          const int *__restrict__ eJ, const roff_t *__restrict__ moff,
+                                                          const double *__restrict__ coords, const double *__restrict__ coef,
+                                                          int accumulate, double *out, int *__restrict__ bad) {
+    constexpr int BLOCK = MASS_BLOCK, EPB = mass_epb(ND, VDIM), NQ = MassTable<DIM, ND>::NQ, DD = DIM * DIM;
+    constexpr int S = ND * VDIM, SS = S * S, NPAIR = ND * (ND + 1) / 2;
+    constexpr int NT = EPB * SS, NJ = ND <= 8 ? 0 : EPB * NQ * DD;      // (order 1 keeps J in registers)
+    constexpr int ND_ = ND * NQ * DIM, WORK = NT > NJ + ND_ ? NT : NJ + ND_;
+    __shared__ double sX[EPB * ND * DIM];
+    __shared__ double sN[NQ * ND];
+    __shared__ double sS[EPB * NQ];
+    __shared__ double sC[EPB];
+    __shared__ double work[WORK];
+    __shared__ roff_t obase[EPB];
+    __shared__ int sE[EPB];
+    double *const tile = work;
+    const int tid = threadIdx.x;
+    mass_stage<DIM, ND, 1, EPB>(count, list, eI, eJ, coords, coef, nullptr, sX, sC, sE, sN, work + NJ, nullptr);
+    mass_point_phases<DIM, ND, EPB>(sX, work + NJ, sC, sE, work, sS, bad);      // (J and the gradients lie under the tile)
+    if (!out) return;                             // (the same in every lane of the grid)
+    if (tid < EPB) obase[tid] = sE[tid] < 0 ? 0 : (moff ? moff[sE[tid]] : (roff_t)sE[tid] * SS);
+    __syncthreads();
+    const long left = (long)count - (long)blockIdx.x * EPB;
+    const int total = (int)(left < EPB ? left : EPB) * SS;
+    const bool fill = VDIM > 1 || accumulate;
+    if (fill) {
+        // ---- fill
+        for (int t = tid; t < total; t += BLOCK) {
+            const int l = t / SS, rc = t - l * SS, r = rc / S, c = rc - r * S;
+            double v = accumulate ? out[obase[l] + rc] : 0.0;
+            if (r % VDIM != c % VDIM) v = v + 0.0;
+            tile[t] = v;
+        }
+        __syncthreads();
+    }
+    // ---- entry
+    for (int idx = tid; idx < EPB * NPAIR; idx += BLOCK) {
+        const int el = idx / NPAIR, ab = MASS_PAIRS<ND>.ab[idx - el * NPAIR], a = ab >> 5, b = ab & 31;
+        const double *s = sS + el * NQ;
+        double acc = 0.0;
+#pragma unroll 1
+        for (int q = 0; q < NQ; ++q) {
+            const double term = s[q] * (sN[q * ND + a] * sN[q * ND + b]);
+            acc = acc + term;
+        }
+        double *t = tile + el * SS;
+#pragma unroll
+        for (int i = 0; i < VDIM; ++i) {
+            const int r = VDIM * a + i, c = VDIM * b + i;
+            t[r * S + c] = fill ? t[r * S + c] + acc : acc;
+            if (a != b) t[c * S + r] = fill ? t[c * S + r] + acc : acc;
+        }
+    }
+    __syncthreads();
+    // ---- tile
+    for (int t = tid; t < total; t += BLOCK) {
+        const int l = t / SS;
+        out[obase[l] + (t - l * SS)] = tile[t];
+    }
+}
+
+// The load vectors: element e's ND * VDIM doubles at VDIM * (its offset in the vertex lists).  Phases:
+//   stage, J, point   above; the nodal source of the element's nodes is staged with the coordinates
+//   source  one lane per (element, point, component): fq = sum over the nodes, ascending, of N_c * src_c; s * fq is kept
+//   dof     one lane per (element, node, component): the whole sum over the points of (s * fq) * N_a, written where it belongs
+template <int DIM, int ND, int VDIM>
+__global__ __launch_bounds__(MASS_BLOCK) void load_kernel(int count, const int *__restrict__ list, const int *__restrict__ eI,
+                                                          const int *__restrict__ eJ, const double *__restrict__ coords,
+                                                          const double *__restrict__ coef, const double *__restrict__ src,
+                                                          double *__restrict__ out, int *__restrict__ bad) {
+    constexpr int BLOCK = MASS_BLOCK, EPB = load_epb(ND), NQ = MassTable<DIM, ND>::NQ, DD = DIM * DIM;
+    __shared__ double sX[EPB * ND * DIM];
+    __shared__ double sF[EPB * ND * VDIM];
+    __shared__ double sN[NQ * ND];
+    __shared__ double sS[EPB * NQ];
+    __shared__ double sC[EPB];
+    __shared__ double sJ[ND <= 8 ? 1 : EPB * NQ * DD];      // (order 1 keeps J in registers)
+    __shared__ double sD[ND * NQ * DIM];
+    __shared__ double sQ[EPB * NQ * VDIM];
+    __shared__ int sE[EPB];
+    const int tid = threadIdx.x;
+    mass_stage<DIM, ND, VDIM, EPB>(count, list, eI, eJ, coords, coef, src, sX, sC, sE, sN, sD, sF);
+    mass_point_phases<DIM, ND, EPB>(sX, sD, sC, sE, sJ, sS, bad);
+    if (!out) return;                             // (the same in every lane of the grid)
+    // ---- source
+    for (int idx = tid; idx < EPB * NQ * VDIM; idx += BLOCK) {
+        const int el = idx / (NQ * VDIM), r = idx - el * (NQ * VDIM), q = r / VDIM, i = r - q * VDIM;
+        const double *F = sF + el * ND * VDIM + i, *N = sN + q * ND;
+        double fq = N[0] * F[0];
+        for (int c = 1; c < ND; ++c) fq = fq + N[c] * F[c * VDIM];
+        sQ[idx] = sS[el * NQ + q] * fq;
+    }
+    __syncthreads();
+    // ---- dof
+    for (int idx = tid; idx < EPB * ND * VDIM; idx += BLOCK) {
+        const int el = idx / (ND * VDIM), r = idx - el * (ND * VDIM), a = r / VDIM, i = r - a * VDIM;
+        const int e = sE[el];
+        if (e < 0) continue;
+        const double *Q = sQ + el * NQ * VDIM + i;
+        double acc = 0.0;
+#pragma unroll 1
+        for (int q = 0; q < NQ; ++q) {
+            const double term = Q[q * VDIM] * sN[q * ND + a];
+            acc = acc + term;
+        }
+        const long vb = eI ? (long)eI[e] : (long)e * ND;
+        out[vb * VDIM + r] = acc;
+    }
+}
+
 // ---- tables ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void em_offsets_kernel(int NE, int nd, int *__restrict__ eI) {
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
@@ -662,7 +990,177 @@ void em_launch_type(const EmLaunch &L, int type, int count, const int *list) {
     }
 }
 
+template <int DIM, int ND>
+void mass_launch(const EmLaunch &L, int vdim, int accumulate, int count, const int *list) {
+    if (vdim == 1)
+        hipLaunchKernelGGL((mass_kernel<DIM, ND, 1>), dim3((unsigned)div_up(count, mass_epb(ND, 1))), dim3(MASS_BLOCK), 0, L.s, count,
+                           list, L.eI, L.eJ, L.moff, L.coords, L.coef, accumulate, L.out, L.bad);
+    else
+        hipLaunchKernelGGL((mass_kernel<DIM, ND, DIM>), dim3((unsigned)div_up(count, mass_epb(ND, DIM))), dim3(MASS_BLOCK), 0, L.s,
+                           count, list, L.eI, L.eJ, L.moff, L.coords, L.coef, accumulate, L.out, L.bad);
+    SA_HIP_CHECK(hipGetLastError());
+}
+template <int DIM, int ND>
+void load_launch(const EmLaunch &L, int vdim, const double *src, int count, const int *list) {
+    const dim3 grid((unsigned)div_up(count, load_epb(ND)));
+    if (vdim == 1)
+        hipLaunchKernelGGL((load_kernel<DIM, ND, 1>), grid, dim3(MASS_BLOCK), 0, L.s, count, list, L.eI, L.eJ, L.coords, L.coef, src,
+                           L.out, L.bad);
+    else
+        hipLaunchKernelGGL((load_kernel<DIM, ND, DIM>), grid, dim3(MASS_BLOCK), 0, L.s, count, list, L.eI, L.eJ, L.coords, L.coef,
+                           src, L.out, L.bad);
+    SA_HIP_CHECK(hipGetLastError());
+}
+// src nullptr: the mass matrices, else the load vectors
+void mass_launch_type(const EmLaunch &L, int type, int vdim, int accumulate, const double *src, int count, const int *list) {
+#define SA_MASS_CASE(T, DIM, ND)                                       \
+    case T:                                                            \
+        if (src) load_launch<DIM, ND>(L, vdim, src, count, list);      \
+        else mass_launch<DIM, ND>(L, vdim, accumulate, count, list);   \
+        break;
+    switch (type) {
+        SA_MASS_CASE(0, 2, 3)
+        SA_MASS_CASE(1, 2, 4)
+        SA_MASS_CASE(2, 3, 4)
+        SA_MASS_CASE(3, 3, 6)
+        SA_MASS_CASE(4, 3, 8)
+        SA_MASS_CASE(5, 2, 9)
+        default: SA_MASS_CASE(6, 3, 27)
+    }
+#undef SA_MASS_CASE
+}
+
 const char *const EM_NAME = "saamge_amd_element_matrices: ";
+
+// ---- what the three entry points share ------------------------------------------------------------------------------------
+// the checks that need no device: info as a call without elements leaves it, the dimension and the counts ...
+void em_begin(const std::string &name, int NV, int dim, int NE, long long info[8]) {
+    if (info) {
+        for (int k = 0; k < 8; ++k) info[k] = 0;
+        info[6] = -1;
+    }
+    SA_REQUIRE(dim == 2 || dim == 3, name + "dim must be 2 or 3");
+    SA_REQUIRE(NV >= 0 && NE >= 0, name + "NV < 0 or NE < 0");
+}
+// ... and the sizes; comp: dofs per node
+void em_check_sizes(const std::string &name, int NV, int dim, int NE, int nde, const int *elem_ptr, int comp) {
+    SA_REQUIRE((int64_t)NV * comp <= INT_MAX, name + "dim * NV beyond 32 bits");
+    if (!elem_ptr) {
+        SA_REQUIRE(em_type_index(dim, nde) >= 0,
+                   name + "nde = " + std::to_string(nde) + " nodes are no supported element type in " + std::to_string(dim) + "D");
+        SA_REQUIRE((int64_t)NE * nde * comp <= INT_MAX, name + "NE * nde beyond 32 bits");
+    }
+}
+
+// the mesh on the device, checked; the elements of every type; square: the offsets of the packed matrices
+struct EmMesh {
+    DBuf<int> hold_I, hold_J, list[EM_TYPES], word;
+    DBuf<roff_t> moff;
+    const int *eI = nullptr, *eJ = nullptr;
+    long nconn = 0;
+    int count[EM_TYPES] = {0, 0, 0, 0, 0, 0, 0};
+    int64_t doubles = 0;          // of the packed result: sum of size^2 (square) or of size
+};
+void em_mesh(hipStream_t s, const std::string &name, int NV, int dim, int NE, int nde, const int *elem_ptr,
+             const int *elem_to_vertex, int comp, bool square, EmMesh &M, long long info[8]) {
+    // ---- the mesh: offsets first, they say how much of elem_to_vertex there is
+    if (elem_ptr) {
+        M.eI = device_view(M.hold_I, elem_ptr, (size_t)NE + 1, s);
+    } else {
+        M.hold_I.alloc((size_t)NE + 1);
+        hipLaunchKernelGGL(em_offsets_kernel, grid_flat((long)NE + 1), dim3(256), 0, s, NE, nde, M.hold_I.p);
+        SA_HIP_CHECK(hipGetLastError());
+        M.eI = M.hold_I.p;
+    }
+    M.eJ = elem_to_vertex;
+    if (!is_device_ptr(elem_to_vertex)) {
+        long total = (long)NE * nde;
+        if (elem_ptr) {
+            const hvec<int> hI = fetch_host(M.eI, (size_t)NE + 1, s);
+            for (int e = 0; e < NE; ++e)
+                SA_REQUIRE(hI[0] == 0 && hI[(size_t)e + 1] > hI[(size_t)e], name + "elem_ptr: must start at 0 and every element needs a vertex");
+            total = hI[(size_t)NE];
+        }
+        upload(M.hold_J, elem_to_vertex, (size_t)total, s);
+        M.eJ = M.hold_J.p;
+    }
+    M.nconn = check_mesh_device(s, NE, M.eI, M.eJ, NV);      // offsets, vertex ids in [0, NV), no vertex twice in an element
+    SA_REQUIRE((int64_t)M.nconn * comp <= INT_MAX, name + "dim * elem_ptr[NE] beyond 32 bits");
+    // ---- types, lists, offsets of the packed matrices
+    M.word.alloc(1);
+    if (elem_ptr) {
+        DBuf<int> sq((size_t)NE), cls((size_t)NE), flag, pos;
+        SA_HIP_CHECK(hipMemsetAsync(M.word.p, 0x7f, sizeof(int), s));
+        hipLaunchKernelGGL(em_classify_kernel, grid_flat(NE), dim3(256), 0, s, NE, dim, comp, M.eI, cls.p, sq.p, M.word.p);
+        SA_HIP_CHECK(hipGetLastError());
+        const int first = read_one(M.word.p, s);
+        if (first < NE) {
+            const int nd = read_one(M.eI + first + 1, s) - read_one(M.eI + first, s);
+            SA_REQUIRE(false, name + "element " + std::to_string(first) + ": " + std::to_string(nd) +
+                                  " nodes are no supported element type in " + std::to_string(dim) + "D");
+        }
+        flag.alloc((size_t)NE);
+        pos.alloc((size_t)NE + 1);
+        for (int t = 0; t < EM_TYPES; ++t)
+            if (em_type_index(dim, EM_TYPE_ND[t]) == t) M.count[t] = make_list(s, NE, cls.p, t, flag, pos, M.list[t]);
+        if (square) {
+            M.moff.alloc((size_t)NE + 1);
+            exclusive_scan_off(s, NE, sq.p, M.moff.p);
+            M.doubles = read_one(M.moff.p + NE, s);
+        } else {
+            M.doubles = (int64_t)M.nconn * comp;
+        }
+    } else {
+        M.count[em_type_index(dim, nde)] = NE;
+        M.doubles = square ? (int64_t)NE * (nde * comp) * (nde * comp) : (int64_t)NE * nde * comp;
+    }
+    if (info) {
+        for (int t = 0; t < 5; ++t) info[t] = M.count[t];
+        info[5] = (long long)M.doubles;
+        info[7] = (long long)M.count[5] + M.count[6];      // the order-2 elements
+    }
+}
+
+// the integer minimum the kernels left in M.word: the first element with a non-positive determinant
+void em_refuse_bad(hipStream_t s, const std::string &name, const EmMesh &M, int NE, long long info[8]) {
+    const int bad = read_one(M.word.p, s);
+    if (bad < NE) {
+        if (info) info[6] = bad;
+        SA_REQUIRE(false, name + "element " + std::to_string(bad) + ": the Jacobian determinant is not positive");
+    }
+}
+
+// the mass matrices (src nullptr) or the load vectors of the arguments of saamge_amd_element_mass / _loads, already checked
+void mass_or_loads(hipStream_t s, const std::string &name, int NV, int dim, const double *coords, int NE, int nde,
+                   const int *elem_ptr, const int *elem_to_vertex, int vdim, const double *coef, const double *src, int accumulate,
+                   double *out, long long info[8]) {
+    if (NE == 0) return;
+    EmMesh M;
+    em_mesh(s, name, NV, dim, NE, nde, elem_ptr, elem_to_vertex, vdim, !src, M, info);
+    DBuf<double> hold_X, hold_c, hold_src, hold_out;
+    EmLaunch L;
+    L.s = s;
+    L.eI = elem_ptr ? M.eI : nullptr;
+    L.eJ = M.eJ;
+    L.moff = M.moff.p;
+    L.coords = device_view(hold_X, coords, (size_t)NV * dim, s);
+    L.coef = coef ? device_view(hold_c, coef, (size_t)NE, s) : nullptr;
+    L.ncoef = 1;
+    L.out = out;
+    if (out && !is_device_ptr(out)) {
+        if (accumulate) upload(hold_out, (const double *)out, (size_t)M.doubles, s);
+        else hold_out.alloc((size_t)M.doubles);
+        L.out = hold_out.p;
+    }
+    L.bad = M.word.p;
+    const double *dsrc = src ? device_view(hold_src, src, (size_t)NV * vdim, s) : nullptr;
+    SA_HIP_CHECK(hipMemsetAsync(M.word.p, 0x7f, sizeof(int), s));
+    for (int t = 0; t < EM_TYPES; ++t)
+        if (M.count[t]) mass_launch_type(L, t, vdim, accumulate, dsrc, M.count[t], M.list[t].p);
+    em_refuse_bad(s, name, M, NE, info);
+    if (hold_out.p) SA_HIP_CHECK(hipMemcpyAsync(out, hold_out.p, (size_t)M.doubles * sizeof(double), hipMemcpyDeviceToHost, s));
+    SA_HIP_CHECK(hipStreamSynchronize(s));
+}
 
 }  // namespace
 
@@ -671,94 +1169,29 @@ void element_matrices(hipStream_t s, int NV, int dim, const double *coords, int 
                       int *elem_to_dof_out, long long info[8]) {
     // ---- what needs no device
     const std::string name(EM_NAME);
-    if (info) {
-        for (int k = 0; k < 8; ++k) info[k] = 0;
-        info[6] = -1;
-    }
-    SA_REQUIRE(dim == 2 || dim == 3, name + "dim must be 2 or 3");
+    em_begin(name, NV, dim, NE, info);
     SA_REQUIRE(kind == 0 || kind == 1, name + "kind must be 0 (diffusion) or 1 (elasticity)");
     if (kind == 1)
         SA_REQUIRE(ncoef == 2, name + "ncoef must be 2 (lambda, mu) for elasticity");
     else
         SA_REQUIRE(ncoef == 1 || ncoef == dim || ncoef == dim * (dim + 1) / 2,
                    name + "ncoef must be 1, dim or dim (dim + 1) / 2 for diffusion");
-    SA_REQUIRE(NV >= 0 && NE >= 0, name + "NV < 0 or NE < 0");
     SA_REQUIRE(NE == 0 || (coords && elem_to_vertex && coef), name + "null argument: coords, elem_to_vertex or coef");
     const int comp = kind ? dim : 1;
-    SA_REQUIRE((int64_t)NV * comp <= INT_MAX, name + "dim * NV beyond 32 bits");
-    if (!elem_ptr) {
-        SA_REQUIRE(em_type_index(dim, nde) >= 0,
-                   name + "nde = " + std::to_string(nde) + " nodes are no supported element type in " + std::to_string(dim) + "D");
-        SA_REQUIRE((int64_t)NE * nde * comp <= INT_MAX, name + "NE * nde beyond 32 bits");
-    }
+    em_check_sizes(name, NV, dim, NE, nde, elem_ptr, comp);
     if (NE == 0) return;
-    // ---- the mesh: offsets first, they say how much of elem_to_vertex there is
-    DBuf<int> hold_I, hold_J;
-    const int *eI;
-    if (elem_ptr) {
-        eI = device_view(hold_I, elem_ptr, (size_t)NE + 1, s);
-    } else {
-        hold_I.alloc((size_t)NE + 1);
-        hipLaunchKernelGGL(em_offsets_kernel, grid_flat((long)NE + 1), dim3(256), 0, s, NE, nde, hold_I.p);
-        SA_HIP_CHECK(hipGetLastError());
-        eI = hold_I.p;
-    }
-    const int *eJ = elem_to_vertex;
-    long nconn;
-    if (!is_device_ptr(elem_to_vertex)) {
-        long total = (long)NE * nde;
-        if (elem_ptr) {
-            const hvec<int> hI = fetch_host(eI, (size_t)NE + 1, s);
-            for (int e = 0; e < NE; ++e)
-                SA_REQUIRE(hI[0] == 0 && hI[(size_t)e + 1] > hI[(size_t)e], name + "elem_ptr: must start at 0 and every element needs a vertex");
-            total = hI[(size_t)NE];
-        }
-        upload(hold_J, elem_to_vertex, (size_t)total, s);
-        eJ = hold_J.p;
-    }
-    nconn = check_mesh_device(s, NE, eI, eJ, NV);      // offsets, vertex ids in [0, NV), no vertex twice in an element
-    SA_REQUIRE((int64_t)nconn * comp <= INT_MAX, name + "dim * elem_ptr[NE] beyond 32 bits");
-    // ---- types, lists, offsets of the packed matrices
-    DBuf<int> cls, flag, pos, list[EM_TYPES];
-    DBuf<roff_t> moff;
-    int count[EM_TYPES] = {0, 0, 0, 0, 0, 0, 0};
-    int64_t doubles;
-    DBuf<int> word(1);
-    if (elem_ptr) {
-        DBuf<int> sq((size_t)NE);
-        cls.alloc((size_t)NE);
-        SA_HIP_CHECK(hipMemsetAsync(word.p, 0x7f, sizeof(int), s));
-        hipLaunchKernelGGL(em_classify_kernel, grid_flat(NE), dim3(256), 0, s, NE, dim, comp, eI, cls.p, sq.p, word.p);
-        SA_HIP_CHECK(hipGetLastError());
-        const int first = read_one(word.p, s);
-        if (first < NE) {
-            const int nd = read_one(eI + first + 1, s) - read_one(eI + first, s);
-            SA_REQUIRE(false, name + "element " + std::to_string(first) + ": " + std::to_string(nd) +
-                                  " nodes are no supported element type in " + std::to_string(dim) + "D");
-        }
-        flag.alloc((size_t)NE);
-        pos.alloc((size_t)NE + 1);
-        for (int t = 0; t < EM_TYPES; ++t)
-            if (em_type_index(dim, EM_TYPE_ND[t]) == t) count[t] = make_list(s, NE, cls.p, t, flag, pos, list[t]);
-        moff.alloc((size_t)NE + 1);
-        exclusive_scan_off(s, NE, sq.p, moff.p);
-        doubles = read_one(moff.p + NE, s);
-    } else {
-        count[em_type_index(dim, nde)] = NE;
-        doubles = (int64_t)NE * (nde * comp) * (nde * comp);
-    }
-    if (info) {
-        for (int t = 0; t < 5; ++t) info[t] = count[t];
-        info[5] = (long long)doubles;
-        info[7] = (long long)count[5] + count[6];      // the order-2 elements
-    }
+    EmMesh M;
+    em_mesh(s, name, NV, dim, NE, nde, elem_ptr, elem_to_vertex, comp, true, M, info);
+    const int *eI = M.eI, *eJ = M.eJ;
+    const long nconn = M.nconn;
+    const int64_t doubles = M.doubles;      // (info[5])
     // ---- the matrices (elmat_out NULL: the determinants are still checked)
     DBuf<double> hold_X, hold_c, hold_out;
     EmLaunch L;
     L.s = s;
     L.eI = elem_ptr ? eI : nullptr;
     L.eJ = eJ;
-    L.moff = moff.p;
+    L.moff = M.moff.p;
     L.coords = device_view(hold_X, coords, (size_t)NV * dim, s);
     L.coef = device_view(hold_c, coef, (size_t)NE * ncoef, s);
     L.ncoef = ncoef;
@@ -767,18 +1200,14 @@ void element_matrices(hipStream_t s, int NV, int dim, const double *coords, int 
         hold_out.alloc((size_t)doubles);
         L.out = hold_out.p;
     }
-    L.bad = word.p;
-    SA_HIP_CHECK(hipMemsetAsync(word.p, 0x7f, sizeof(int), s));
+    L.bad = M.word.p;
+    SA_HIP_CHECK(hipMemsetAsync(M.word.p, 0x7f, sizeof(int), s));
     for (int t = 0; t < EM_TYPES; ++t) {
-        if (!count[t]) continue;
-        if (kind) em_launch_type<1>(L, t, count[t], list[t].p);
-        else em_launch_type<0>(L, t, count[t], list[t].p);
+        if (!M.count[t]) continue;
+        if (kind) em_launch_type<1>(L, t, M.count[t], M.list[t].p);
+        else em_launch_type<0>(L, t, M.count[t], M.list[t].p);
     }
-    const int bad = read_one(word.p, s);
-    if (bad < NE) {
-        if (info) info[6] = bad;
-        SA_REQUIRE(false, name + "element " + std::to_string(bad) + ": the Jacobian determinant is not positive");
-    }
+    em_refuse_bad(s, name, M, NE, info);
     if (hold_out.p) SA_HIP_CHECK(hipMemcpyAsync(elmat_out, hold_out.p, (size_t)doubles * sizeof(double), hipMemcpyDeviceToHost, s));
     // ---- the dof lists the matrices are indexed by
     DBuf<int> dptr, dofs;
@@ -795,6 +1224,31 @@ void element_matrices(hipStream_t s, int NV, int dim, const double *coords, int 
         SA_HIP_CHECK(hipMemcpyAsync(elem_to_dof_out, dofs.p, (size_t)nconn * comp * sizeof(int), hipMemcpyDefault, s));
     }
     SA_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void element_mass(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                  const int *elem_to_vertex, int vdim, const double *coef, int accumulate, double *elmat_inout, long long info[8]) {
+    const std::string name("saamge_amd_element_mass: ");
+    em_begin(name, NV, dim, NE, info);
+    SA_REQUIRE(vdim == 1 || vdim == dim, name + "vdim must be 1 or dim");
+    SA_REQUIRE(NE == 0 || coef, name + "null argument: coef");
+    SA_REQUIRE(NE == 0 || (coords && elem_to_vertex), name + "null argument: coords or elem_to_vertex");
+    SA_REQUIRE(!accumulate || elmat_inout, name + "null argument: accumulate needs the matrices in elmat_inout");
+    em_check_sizes(name, NV, dim, NE, nde, elem_ptr, vdim);
+    mass_or_loads(s, name, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, coef, nullptr, accumulate ? 1 : 0, elmat_inout,
+                  info);
+}
+
+void element_loads(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                   const int *elem_to_vertex, int vdim, const double *coef, const double *src, double *elvec_out,
+                   long long info[8]) {
+    const std::string name("saamge_amd_element_loads: ");
+    em_begin(name, NV, dim, NE, info);
+    SA_REQUIRE(vdim == 1 || vdim == dim, name + "vdim must be 1 or dim");
+    SA_REQUIRE(src, name + "null argument: src");
+    SA_REQUIRE(NE == 0 || (coords && elem_to_vertex), name + "null argument: coords or elem_to_vertex");
+    em_check_sizes(name, NV, dim, NE, nde, elem_ptr, vdim);
+    mass_or_loads(s, name, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, coef, src, 0, elvec_out, info);
 }
 
 }  // namespace saamge_amd

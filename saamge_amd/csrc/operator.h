@@ -72,5 +72,8 @@ void operator_assemble(hipStream_t s, int n, int NE, int nde, const int *elem_pt
 void operator_numeric(AssembledOperator &op, const double *elmat);
 // b (n, in place) for the essential values x_ess, both on the device; elmat a host or device pointer
 void operator_eliminate_rhs(const AssembledOperator &op, const double *elmat, const double *x_ess, double *b);
+// b (n, on the device, overwritten) from the packed element vectors (element e at the offset of its dof list; host or device
+// pointer): assemble_model.assemble_rhs
+void operator_assemble_rhs(const AssembledOperator &op, const double *elvec, double *b);
 
 }  // namespace saamge_amd

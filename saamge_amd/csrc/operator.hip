@@ -392,6 +392,29 @@ __global__ __launch_bounds__(256) void op_rhs_kernel(int n, const int *__restric
     if (any) b[i] = bi;
 }
 
+// One thread per dof: the terms of its elements in ascending element id, the first one taken as it is.  The element vectors
+// are packed like the dof lists, so a term lies at the position of the dof in eJ.
+__global__ __launch_bounds__(256) void op_rhs_assemble_kernel(int n, const int *__restrict__ d2e_I, const int *__restrict__ d2e_J,
+                                                              const int *__restrict__ eI, const int *__restrict__ eJ,
+                                                              const double *__restrict__ elvec, double *__restrict__ b) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const int i = (int)t;
+    double sum = 0.0;
+    bool have = false;
+    for (int x = d2e_I[i], x1 = d2e_I[i + 1]; x < x1; ++x) {
+        const int e = d2e_J[x], eb = eI[e], nd = eI[e + 1] - eb;
+        for (int a = 0; a < nd; ++a) {
+            if (eJ[eb + a] != i) continue;
+            const double term = elvec[eb + a];
+            sum = have ? sum + term : term;
+            have = true;
+            break;
+        }
+    }
+    b[i] = sum;
+}
+
 template <bool FILL>
 void symbolic_pass(hipStream_t s, const AssembledOperator &op, const DBuf<int> *list, const int *count, int *cnt, int *col) {
     const int *dI = op.d2e_I.p, *dJ = op.d2e_J.p, *eI = op.eI.p, *eJ = op.eJ.p;
@@ -553,6 +576,18 @@ void operator_eliminate_rhs(const AssembledOperator &op, const double *elmat, co
     hipLaunchKernelGGL(op_rhs_kernel, grid_flat(op.n), dim3(256), 0, s, op.n, (const int *)op.d2e_I.p, (const int *)op.d2e_J.p,
                        (const int *)op.eI.p, (const int *)op.eJ.p, (const roff_t *)op.moff.p, op.nde, d,
                        (const signed char *)op.bdr.p, (const roff_t *)op.rowptr.p, (const int *)op.col.p, x_ess, b);
+    SA_HIP_CHECK(hipGetLastError());
+    SA_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+void operator_assemble_rhs(const AssembledOperator &op, const double *elvec, double *b) {
+    SA_REQUIRE(elvec || !op.nconn, "null argument: elvec");
+    if (!op.n) return;
+    hipStream_t s = op.stream;
+    DBuf<double> hold;
+    const double *d = device_view(hold, elvec, (size_t)op.nconn, s);
+    hipLaunchKernelGGL(op_rhs_assemble_kernel, grid_flat(op.n), dim3(256), 0, s, op.n, (const int *)op.d2e_I.p,
+                       (const int *)op.d2e_J.p, (const int *)op.eI.p, (const int *)op.eJ.p, d, b);
     SA_HIP_CHECK(hipGetLastError());
     SA_HIP_CHECK(hipStreamSynchronize(s));
 }

@@ -33,6 +33,7 @@ are those of the scalar formulas).
   refused      dim, kind, ncoef out of range, a node count that is no type of the dimension, malformed offsets, a vertex id
                outside [0, NV), an element that lists a vertex twice, and an element whose det is not positive at a point
                (ElementError, .element the smallest such id).
+  zeroth order element_mass and element_loads, on the same types, node orders and geometry: defined at the end of this file.
 """
 import numpy as np
 
@@ -309,3 +310,186 @@ def dof_lists(dim, elem_to_vertex, kind, elem_ptr=None):
     if kind == 0:
         return ep.astype(np.int32), e2v.astype(np.int32)
     return (ep * dim).astype(np.int32), (dim * e2v[:, None] + np.arange(dim)[None, :]).ravel().astype(np.int32)
+
+
+# ---- mass matrices and load vectors (zeroth-order forms) ---------------------------------------------------------------------
+#   rule         the type's rule above, except the simplices (one point is not enough for a product of two shape functions):
+#                triangle: the three points of WEDGE_TRI, weight 1/6 each; tetrahedron: four points, weight 1/24 each, point 0
+#                (TET_A, TET_A, TET_A) and point q = 1 .. 3 with coordinate q - 1 replaced by TET_B.
+#   shapes       N_a at a point, written out like the gradients (shape_values).
+#   point        J, the cofactors and det exactly as above, from the type's gradients at that point (constant for the
+#                simplices, formed per point all the same); a det that is not positive refuses the element;
+#                s = (weight * det) * c_e -- no division.
+#   mass         entry (a, b) with a <= b gets s * (N_a * N_b) per point, summed over the points in ascending order from 0.0;
+#                (b, a) is the same double.  vdim = dim: dof dim * a + i, entry ((a, i), (b, j)) the scalar entry when i == j
+#                and +0.0 otherwise.  add_to: the result is add_to + m, one addition per entry after m is complete.
+#   loads        src nodal (NV, vdim): per point fq_i = sum_c N_c * src[c][i], nodes ascending, the first product as it is;
+#                dof (a, i) gets (s * fq_i) * N_a, summed over the points from 0.0.  coef None: 1.0.  Packed: element e at
+#                sum_{f<e} size_f; (NE, size) when elem_ptr is None.
+TET_A, TET_B = 0.1381966011250105, 0.5854101966249685    # (5 - sqrt 5) / 20, (5 + 3 sqrt 5) / 20
+TET_POINTS = [(TET_A, TET_A, TET_A), (TET_B, TET_A, TET_A), (TET_A, TET_B, TET_A), (TET_A, TET_A, TET_B)]
+MASS_NPOINTS = dict(NPOINTS)
+MASS_NPOINTS.update({(2, 3): 3, (3, 4): 4})
+MASS_WEIGHT = {(2, 3): 0.16666666666666666, (3, 4): 0.041666666666666664}
+
+
+def mass_point_weight(dim, nd, q):
+    """weight of point q of the type's mass rule"""
+    return MASS_WEIGHT[(dim, nd)] if (dim, nd) in MASS_WEIGHT else point_weight(dim, nd, q)
+
+
+def shape_values(dim, nd, q):
+    """N[a] at point q of the type's mass rule, as Python floats."""
+    if (dim, nd) == (2, 9):
+        px, py = GAUSS3[q % 3], GAUSS3[q // 3]
+        return [_n2(ix, px) * _n2(iy, py) for (ix, iy) in Q2_QUAD_LOC]
+    if (dim, nd) == (3, 27):
+        px, py, pz = GAUSS3[q % 3], GAUSS3[(q // 3) % 3], GAUSS3[q // 9]
+        return [_n2(ix, px) * (_n2(iy, py) * _n2(iz, pz)) for (ix, iy, iz) in Q2_HEX_LOC]
+    if (dim, nd) == (2, 3):
+        x, y = WEDGE_TRI[q]
+        return [(1.0 - x) - y, x, y]
+    if (dim, nd) == (3, 4):
+        x, y, z = TET_POINTS[q]
+        return [((1.0 - x) - y) - z, x, y, z]
+    if (dim, nd) == (2, 4):
+        px, py = GAUSS[q & 1], GAUSS[(q >> 1) & 1]
+        return [_f(lx, px) * _f(ly, py) for (lx, ly) in QUAD_LOC]
+    if (dim, nd) == (3, 8):
+        px, py, pz = GAUSS[q & 1], GAUSS[(q >> 1) & 1], GAUSS[(q >> 2) & 1]
+        return [_f(lx, px) * (_f(ly, py) * _f(lz, pz)) for (lx, ly, lz) in HEX_LOC]
+    if (dim, nd) == (3, 6):
+        xi, eta = WEDGE_TRI[q % 3]
+        zeta = GAUSS[q // 3]
+        T = ((1.0 - xi) - eta, xi, eta)
+        L = (1.0 - zeta, zeta)
+        return [T[i] * L[a] for a in (0, 1) for i in (0, 1, 2)]
+    raise ValueError("%d nodes: no supported element type in %dD" % (nd, dim))
+
+
+def _mass_points(X, dim, nd, c):
+    """Per point of the mass rule: (N, s) with s = (weight * det) * c over the n elements of X, and per element whether a det
+    was not positive."""
+    bad = np.zeros(X.shape[0], bool)
+    out = []
+    with np.errstate(all="ignore"):
+        for q in range(MASS_NPOINTS[(dim, nd)]):
+            dN = reference_gradients(dim, nd, q)                     # (the simplices': the same at every point)
+            J = [[None] * dim for _ in range(dim)]
+            for i in range(dim):
+                for j in range(dim):
+                    t = X[:, 0, i] * dN[0][j]
+                    for a in range(1, nd):
+                        t = t + X[:, a, i] * dN[a][j]
+                    J[i][j] = t
+            _, det = _cofactors(J, dim)
+            bad |= ~(det > 0.0)
+            out.append((shape_values(dim, nd, q), (mass_point_weight(dim, nd, q) * det) * c))
+    return out, bad
+
+
+def _mass_block(X, dim, nd, c):
+    """Scalar mass matrices (n, nd, nd) of n elements of one type."""
+    n = X.shape[0]
+    pa, pb = np.triu_indices(nd)
+    acc = np.zeros((n, len(pa)))
+    points, bad = _mass_points(X, dim, nd, c)
+    with np.errstate(all="ignore"):
+        for N, s in points:
+            NN = np.array([N[a] * N[b] for a, b in zip(pa, pb)])
+            term = s[:, None] * NN[None, :]
+            acc = acc + term
+    out = np.zeros((n, nd, nd))
+    out[:, pa, pb] = acc
+    out[:, pb, pa] = acc
+    return out, bad
+
+
+def _load_block(X, dim, nd, c, F):
+    """Load vectors (n, nd, vdim) of n elements of one type; F: (n, nd, vdim) the nodal source."""
+    n, vdim = X.shape[0], F.shape[2]
+    acc = np.zeros((n, nd, vdim))
+    points, bad = _mass_points(X, dim, nd, c)
+    with np.errstate(all="ignore"):
+        for N, s in points:
+            fq = N[0] * F[:, 0, :]
+            for a in range(1, nd):
+                fq = fq + N[a] * F[:, a, :]
+            sf = s[:, None] * fq
+            term = sf[:, None, :] * np.array(N)[None, :, None]
+            acc = acc + term
+    return acc, bad
+
+
+def _vdim(vdim, dim):
+    if vdim not in (1, dim):
+        raise ValueError("vdim: 1 or dim")
+    return int(vdim)
+
+
+def element_mass(coords, elem_to_vertex, coef, vdim=1, elem_ptr=None, add_to=None):
+    """The mass matrices with the per-element coefficient coef (NE,): (NE, size, size) when elem_ptr is None, else packed;
+    size = vdim * nodes.  add_to: matrices of the same layout (diffusion for vdim 1, elasticity for vdim dim) the result is
+    added to."""
+    X, dim, ep, e2v, nd = _mesh(coords, elem_to_vertex, elem_ptr)
+    vdim = _vdim(vdim, dim)
+    NE = len(nd)
+    if coef is None:
+        raise ValueError("coef: (NE,) is needed")
+    coef = np.asarray(coef, np.float64).reshape(-1)
+    if len(coef) != NE:
+        raise ValueError("coef: (NE,) is needed")
+    moff = np.concatenate([[0], np.cumsum((nd * vdim) ** 2)])
+    out = np.zeros(int(moff[-1]))
+    bad = np.zeros(NE, bool)
+    for c in np.unique(nd):
+        ids = np.flatnonzero(nd == c)
+        c = int(c)
+        m, bad[ids] = _mass_block(X[e2v[ep[ids][:, None] + np.arange(c)]], dim, c, coef[ids])
+        if vdim > 1:
+            full = np.zeros((len(ids), c, vdim, c, vdim))
+            for i in range(vdim):
+                full[:, :, i, :, i] = m
+            m = full
+        out[moff[ids][:, None] + np.arange((c * vdim) ** 2)] = m.reshape(len(ids), -1)
+    if bad.any():
+        raise ElementError(np.flatnonzero(bad)[0])
+    if add_to is not None:
+        base = np.asarray(add_to, np.float64).ravel()
+        if len(base) != len(out):
+            raise ValueError("add_to: the layout of the result is needed")
+        out = base + out
+    if elem_ptr is None:
+        return out.reshape(NE, nd[0] * vdim, nd[0] * vdim) if NE else out.reshape(0, 0, 0)
+    return out
+
+
+def element_loads(coords, elem_to_vertex, src, vdim=1, coef=None, elem_ptr=None):
+    """The load vectors of the nodal source src (NV, vdim) (or (NV,) for vdim 1) with the per-element coefficient coef (NE,),
+    None: 1.0.  (NE, size) when elem_ptr is None, else packed."""
+    X, dim, ep, e2v, nd = _mesh(coords, elem_to_vertex, elem_ptr)
+    vdim = _vdim(vdim, dim)
+    NE, NV = len(nd), X.shape[0]
+    if src is None:
+        raise ValueError("src: (NV, vdim) is needed")
+    F = np.asarray(src, np.float64)
+    if F.size != NV * vdim:
+        raise ValueError("src: (NV, vdim) is needed")
+    F = F.reshape(NV, vdim)
+    coef = np.ones(NE) if coef is None else np.asarray(coef, np.float64).reshape(-1)
+    if len(coef) != NE:
+        raise ValueError("coef: (NE,) is needed")
+    voff = np.concatenate([[0], np.cumsum(nd * vdim)])
+    out = np.zeros(int(voff[-1]))
+    bad = np.zeros(NE, bool)
+    for c in np.unique(nd):
+        ids = np.flatnonzero(nd == c)
+        c = int(c)
+        v = e2v[ep[ids][:, None] + np.arange(c)]
+        blk, bad[ids] = _load_block(X[v], dim, c, coef[ids], F[v])
+        out[voff[ids][:, None] + np.arange(c * vdim)] = blk.reshape(len(ids), -1)
+    if bad.any():
+        raise ElementError(np.flatnonzero(bad)[0])
+    if elem_ptr is None:
+        return out.reshape(NE, nd[0] * vdim) if NE else out.reshape(0, 0)
+    return out

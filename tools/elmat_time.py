@@ -6,7 +6,15 @@ scaled per element) and uploaded.  Host clock closed by a synchronise, one
 warm-up, `--reps` repetitions (all listed).  One JSON line per case.
 
     python tools/elmat_time.py [--hex 128,256] [--elasticity 64] [--q2-hex 64,128] [--q2-elasticity 32,64] [--quad9 2048]
-                               [--reps 3] [--host-reps 3] [--hbm-gbs 8000] [--fp64-gops 39300] [--no-host]
+                               [--reps 3] [--host-reps 3] [--hbm-gbs 8000] [--fp64-gops 39300] [--no-host] [--no-mass]
+                               [--rhs 256]
+
+Beside every stiffness case, on the same mesh and in the same run (--no-mass: not): the mass matrices of the same layout
+(saamge_amd_element_mass; vdim 1 beside diffusion, dim beside elasticity), written (`<case>:mass`) and added to the stiffness
+matrices (`<case>:mass_accumulate`; its bound reads the target once and writes it once), and the load vectors of a nodal source
+(`<case>:loads`; saamge_amd_element_loads), each with `stiffness_fraction_of_bound`, the yardstick.  --rhs n: the right-hand
+side of Q1 diffusion on n^3 hexes assembled from its element vectors (saamge_amd_operator_assemble_rhs) against reading them
+once.
 
 The vertices are jittered by 0.2 mesh widths, so no two elements are alike.  A case that does not fit is reported as skipped
 with the error.
@@ -43,6 +51,8 @@ def main():
     ap.add_argument("--fp64-gops", type=float, default=39300.0)
     ap.add_argument("--hbm-gbs", type=float, default=8000.0)
     ap.add_argument("--no-host", action="store_true")
+    ap.add_argument("--no-mass", action="store_true")
+    ap.add_argument("--rhs", default="")
     a = ap.parse_args()
     ints = lambda v: [int(x) for x in v.split(",") if x]
     stream = lambda: torch.cuda.current_stream().cuda_stream
@@ -148,6 +158,37 @@ def main():
                 rec["host_generate_ms"] = [round(x, 1) for x in t_gen]
                 rec["upload_ms"] = [round(x, 1) for x in t_up]
             print(json.dumps(rec), flush=True)
+            if not a.no_mass:
+                vdim = dim if kind else 1
+                sigma = coef.reshape(NE, -1)[:, 0].contiguous()
+                src = torch.rand((X.shape[0], vdim), generator=g, device=dev, dtype=torch.float64)
+                vec = torch.zeros(NE * size, dtype=torch.float64, device=dev)
+                calls = [("mass", out_bytes, lambda: capi.element_mass(X, e2v, sigma, vdim=vdim, out=out, stream=stream())),
+                         ("mass_accumulate", 2 * out_bytes, lambda: capi.element_mass(X, e2v, sigma, vdim=vdim, add_to=out, stream=stream())),
+                         ("loads", 8 * vec.numel(), lambda: capi.element_loads(X, e2v, src, vdim=vdim, coef=sigma, out=vec, stream=stream()))]
+                for tag, nbytes, call in calls:
+                    timed(call)                    # warm-up
+                    t = [timed(call)[0] for _ in range(a.reps)]
+                    b_ms = 1e3 * nbytes / (a.hbm_gbs * 1e9)
+                    print(json.dumps({"case": name + ":" + tag, "elements": NE, "vdim": vdim, "bound_bytes": int(nbytes),
+                                      "device_ms": [round(x, 3) for x in t], "hbm_bound_ms": round(b_ms, 4),
+                                      "fraction_of_bound": round(b_ms / min(t), 4),
+                                      "stiffness_fraction_of_bound": rec["fraction_of_bound"]}), flush=True)
+                src = vec = None
+            if kind == 0 and nd == 8 and n in ints(a.rhs):
+                vec = capi.element_loads(X, e2v, torch.ones(X.shape[0], dtype=torch.float64, device=dev), device=True)
+                op = capi.Operator(X.shape[0], e2v, out, None)
+                try:
+                    b = torch.zeros(X.shape[0], dtype=torch.float64, device=dev)
+                    timed(lambda: op.assemble_rhs(vec, b=b))
+                    t = [timed(lambda: op.assemble_rhs(vec, b=b))[0] for _ in range(a.reps)]
+                    b_ms = 1e3 * 8 * vec.numel() / (a.hbm_gbs * 1e9)
+                    print(json.dumps({"case": "assemble_rhs%d" % n, "dofs": int(X.shape[0]), "elvec_bytes": int(8 * vec.numel()),
+                                      "device_ms": [round(x, 3) for x in t], "hbm_bound_ms": round(b_ms, 4),
+                                      "fraction_of_bound": round(b_ms / min(t), 4)}), flush=True)
+                finally:
+                    op.close()
+                vec = b = None
         except (RuntimeError, MemoryError) as e:
             print(json.dumps({"case": name, "skipped": str(e)[:200]}), flush=True)
         X = e2v = coef = out = None
