@@ -455,6 +455,35 @@ int saamge_amd_element_mass(int NV, int dim, const double *coords, int NE, int n
 int saamge_amd_element_loads(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                              const int *elem_to_vertex, int vdim, const double *coef, const double *src, void *stream,
                              double *elvec_out, long long info[8]);
+/* ---- boundary forms computed on the device (csrc/elmat.hip) ----
+ * The face mass (Robin: (c u, v) over faces) and the face loads (Neumann: (c g, v) over faces) of a list of NF faces, ADDED into
+ * the packed matrices / vectors of the owning elements, so that the element matrices still sum to the operator and everything
+ * downstream (saamge_amd_operator_assemble, _assemble_rhs, saamge_amd_ml_produce_data*) takes them unchanged;
+ * saamge_amd/elmat_model.py (FACE_NODES, boundary_mass, boundary_loads) defines every operation and the device gives the same
+ * bits.  Face f is the local face face_local[f] of element face_elem[f]; local faces by element type, as the element's local
+ * node ids: triangle (0,1) (1,2) (2,0); quadrilateral (0,1) (1,2) (2,3) (3,0); 9-node quadrilateral (0,4,1) (1,5,2) (2,6,3)
+ * (3,7,0); tetrahedron (1,2,3) (0,3,2) (0,1,3) (0,2,1); wedge (0,2,1) (3,4,5) (0,1,4,3) (1,2,5,4) (2,0,3,5); hexahedron (3,2,1,0)
+ * (0,1,5,4) (1,2,6,5) (2,3,7,6) (3,0,4,7) (4,5,6,7); 27-node hexahedron: the same six faces with their 9 nodes.  The call does
+ * not know what a boundary is: interior faces are allowed.  coef: NF doubles, c per face.  The faces of one element are added
+ * in ascending local face index, whatever the order of the list; entries that no listed face touches keep their bits.
+ * saamge_amd_boundary_mass: elmat_inout holds the matrices of saamge_amd_element_matrices / _mass of the same mesh and vdim;
+ * vdim = dim adds the face entry to ((a, i), (b, i)) of every component i.
+ * saamge_amd_boundary_loads: g NV x vdim, the data at the nodes; coef NULL: 1; elvec_inout holds the vectors of
+ * saamge_amd_element_loads.  Data that jumps across an edge: one call per side with its own g, the calls accumulate.
+ * elmat_inout / elvec_inout NULL: the checks and info only.  Any pointer host or device, each on its own.  NF = 0: nothing.
+ * info[0..4] = faces by type: 2-node segments, 3-node segments, triangles, 4-node quadrilaterals, 9-node quadrilaterals;
+ * [5] = additions made (a double that two faces touch counts twice); [6] = first refused face (-1: none); [7] = distinct
+ * elements touched.
+ * Refused, before anything touches the device: vdim not 1 or dim, NF < 0, NULL face lists, NULL coef for the mass, NULL g;
+ * then everything saamge_amd_element_mass refuses of the mesh; then the first face of the list with face_elem outside [0, NE) or
+ * face_local outside the range of the element's type; then the first face whose (element, local face) the list holds more than
+ * once; then the first face whose measure is not positive at a point of its rule. */
+int saamge_amd_boundary_mass(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                             const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim,
+                             const double *coef, void *stream, double *elmat_inout, long long info[8]);
+int saamge_amd_boundary_loads(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                              const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim,
+                              const double *coef, const double *g, void *stream, double *elvec_inout, long long info[8]);
 /* R = P^T (P nrows x ncols) */
 int saamge_amd_csr_transpose(int nrows, int ncols, const int *rowptr, const int *col, const double *val, int *Rrow,
                              long long *Rnnz, int *Rcol, double *Rval);

@@ -366,6 +366,36 @@ inline ElementMatricesInfo element_loads_into(int NV, int dim, const double *coo
     return r;
 }
 
+// == boundary forms computed on the device (saamge_amd_boundary_mass, saamge_amd_boundary_loads) ==
+// The face mass / face loads of the NF listed faces (element face_elem[f], local face face_local[f]; local faces in
+// saamge_amd.h) added into the caller's packed matrices / vectors, each array a host or a device pointer; nullptr for
+// elmat_inout / elvec_inout: the checks and the counts only.
+struct BoundaryFormsInfo {
+    long long segments2, segments3, triangles, quadrilaterals4, quadrilaterals9, additions, first_bad_face, elements;
+};
+inline BoundaryFormsInfo boundary_mass_into(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                            const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local,
+                                            int vdim, const double *coef, double *elmat_inout, void *stream = nullptr) {
+    long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (saamge_amd_boundary_mass(NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, vdim, coef, stream,
+                                 elmat_inout, info))
+        throw std::runtime_error(saamge_amd_last_error());
+    const BoundaryFormsInfo r = {info[0], info[1], info[2], info[3], info[4], info[5], info[6], info[7]};
+    return r;
+}
+// g: the data at the nodes (NV x vdim); coef == nullptr: 1.
+inline BoundaryFormsInfo boundary_loads_into(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                             const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local,
+                                             int vdim, const double *coef, const double *g, double *elvec_inout,
+                                             void *stream = nullptr) {
+    long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (saamge_amd_boundary_loads(NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, vdim, coef, g,
+                                  stream, elvec_inout, info))
+        throw std::runtime_error(saamge_amd_last_error());
+    const BoundaryFormsInfo r = {info[0], info[1], info[2], info[3], info[4], info[5], info[6], info[7]};
+    return r;
+}
+
 // == the operator assembled on the device (saamge_amd_operator_assemble) ==
 // Owner of the handle.  rowptr() / col() / val() are device arrays that live as long as this object: hand them to
 // saamge_amd_ml_produce_data64 / _mixed64 as A.  elem_ptr == nullptr: every element has nde dofs.

@@ -41,6 +41,7 @@ SYMBOLS = [
     "saamge_amd_operator_set_path_limits",
     "saamge_amd_level_order_info", "saamge_amd_ae_order", "saamge_amd_element_matrices",
     "saamge_amd_element_mass", "saamge_amd_element_loads", "saamge_amd_operator_assemble_rhs",
+    "saamge_amd_boundary_mass", "saamge_amd_boundary_loads",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong))
@@ -875,6 +876,65 @@ def element_loads(coords, elem_to_vertex, src, vdim=1, coef=None, elem_ptr=None,
         C.c_int(NV), C.c_int(dim), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_int(vdim), _ptr(coef),
         _ptr(src), C.c_void_p(stream), _ptr(elvec), info), info)
     return elvec.reshape(NE, nde * vdim) if ep is None else elvec
+
+
+def _face_arrays(face_elem, face_local, coef):
+    def arr(a, dt):
+        return a if a is None or hasattr(a, "data_ptr") else np.ascontiguousarray(a, dtype=dt).ravel()
+    fe, fl, coef = arr(face_elem, np.int32), arr(face_local, np.int32), arr(coef, np.float64)
+    return fe, fl, coef, 0 if fe is None else int(fe.shape[0])
+
+
+def _in_place_target(add_to, doubles, device):
+    """The target of a boundary call, written in place: add_to -- a device tensor, or a writeable C-contiguous float64 numpy
+    array -- or, for None, new zeros (on the GPU with device=True)"""
+    if add_to is None:
+        return _new_doubles(doubles, device)
+    if not hasattr(add_to, "data_ptr") and not (isinstance(add_to, np.ndarray) and add_to.dtype == np.float64 and
+                                                  add_to.flags["C_CONTIGUOUS"] and add_to.flags["WRITEABLE"]):
+        raise ValueError("add_to: a device tensor or a writeable C-contiguous float64 array is needed (it is written in place)")
+    return add_to
+
+
+def boundary_mass(coords, elem_to_vertex, face_elem, face_local, coef, vdim=1, elem_ptr=None, add_to=None, device=False,
+                  stream=0, sizes_only=False):
+    """saamge_amd_boundary_mass: the face mass (c u, v) of the listed faces -- face f is the local face face_local[f]
+    (elmat_model.FACE_NODES) of element face_elem[f], c = coef (NF,) -- added IN PLACE to add_to, an array / tensor in the layout
+    of `element_matrices` / `element_mass` with the same vdim, which is returned: the Robin term.  add_to None: the face terms
+    alone, in new zero matrices (device=True: a torch tensor on the GPU).  Inputs numpy arrays or device tensors, each on its own.  sizes_only: info (8 integers: faces by type [0..4], additions, -1, elements touched), nothing
+    written.  A refusal raises RuntimeError with `.info` (info[6]: the first refused face)."""
+    coords, e2v, _, ep = _element_arrays(coords, elem_to_vertex, None, elem_ptr)
+    fe, fl, coef, NF = _face_arrays(face_elem, face_local, coef)
+    vdim = int(vdim)
+    NV, dim, NE, nde, doubles = _mass_sizes(coords, e2v, ep, vdim, True)
+    if not sizes_only:
+        add_to = _in_place_target(add_to, doubles, device)
+    info = (C.c_longlong * 8)()
+    got = _mass_call(lambda: load().saamge_amd_boundary_mass(
+        C.c_int(NV), C.c_int(dim), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_int(NF), _ptr(fe), _ptr(fl),
+        C.c_int(vdim), _ptr(coef), C.c_void_p(stream), _ptr(None if sizes_only else add_to), info), info)
+    return got if sizes_only else add_to
+
+
+def boundary_loads(coords, elem_to_vertex, face_elem, face_local, g, vdim=1, coef=None, elem_ptr=None, add_to=None, device=False,
+                   stream=0, sizes_only=False):
+    """saamge_amd_boundary_loads: the face loads (c g, v) of the data g given at the nodes, (NV, vdim) or (NV,), on the listed
+    faces, coef (NF,) or None: 1 -- added IN PLACE to add_to, an array / tensor in the layout of `element_loads`, which is
+    returned: the Neumann term.  Data that jumps across an edge takes one call per side; the calls accumulate.  Otherwise as
+    `boundary_mass`."""
+    coords, e2v, _, ep = _element_arrays(coords, elem_to_vertex, None, elem_ptr)
+    fe, fl, coef, NF = _face_arrays(face_elem, face_local, coef)
+    if g is not None and not hasattr(g, "data_ptr"):
+        g = np.ascontiguousarray(g, dtype=np.float64)
+    vdim = int(vdim)
+    NV, dim, NE, nde, doubles = _mass_sizes(coords, e2v, ep, vdim, False)
+    if not sizes_only:
+        add_to = _in_place_target(add_to, doubles, device)
+    info = (C.c_longlong * 8)()
+    got = _mass_call(lambda: load().saamge_amd_boundary_loads(
+        C.c_int(NV), C.c_int(dim), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_int(NF), _ptr(fe), _ptr(fl),
+        C.c_int(vdim), _ptr(coef), _ptr(g), C.c_void_p(stream), _ptr(None if sizes_only else add_to), info), info)
+    return got if sizes_only else add_to
 
 
 def get_options():

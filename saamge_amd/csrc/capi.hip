@@ -829,6 +829,27 @@ int saamge_amd_element_loads(int NV, int dim, const double *coords, int NE, int 
     SA_API_END
 }
 
+int saamge_amd_boundary_mass(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                             const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim,
+                             const double *coef, void *stream, double *elmat_inout, long long info[8]) {
+    SA_API_BEGIN
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    boundary_mass(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, vdim, coef, elmat_inout, info);
+    SA_API_END
+}
+
+int saamge_amd_boundary_loads(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                              const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim,
+                              const double *coef, const double *g, void *stream, double *elvec_inout, long long info[8]) {
+    SA_API_BEGIN
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    boundary_loads(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, vdim, coef, g, elvec_inout,
+                   info);
+    SA_API_END
+}
+
 int saamge_amd_csr_transpose(int nrows, int ncols, const int *rowptr, const int *col, const double *val, int *Rrow,
                              long long *Rnnz, int *Rcol, double *Rval) {
     SA_API_BEGIN

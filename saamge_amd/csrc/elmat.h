@@ -21,4 +21,15 @@ void element_loads(hipStream_t s, int NV, int dim, const double *coords, int NE,
                    const int *elem_to_vertex, int vdim, const double *coef, const double *src, double *elvec_out,
                    long long info[8]);
 
+// The arguments of saamge_amd_boundary_mass: the mass matrices of the NF listed faces (element face_elem[f], local face
+// face_local[f], coefficient coef[f]) added to the matrices elmat_inout holds.  elmat_model.boundary_mass defines the result.
+void boundary_mass(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                   const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim, const double *coef,
+                   double *elmat_inout, long long info[8]);
+// The arguments of saamge_amd_boundary_loads: the load vectors of the nodal g (NV x vdim) on the listed faces added to the
+// vectors elvec_inout holds; coef NULL: 1.0.  elmat_model.boundary_loads defines the result.
+void boundary_loads(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                    const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim, const double *coef,
+                    const double *g, double *elvec_inout, long long info[8]);
+
 }  // namespace saamge_amd

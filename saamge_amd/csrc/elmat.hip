@@ -18,10 +18,15 @@
 //
 // The zeroth-order forms -- mass matrices, with or without a target they are added to, and load vectors of a nodal source --
 // have a kernel family of their own for all seven types (mass_kernel, load_kernel) in em2_kernel's phase structure.
+//
+// The boundary forms -- the mass and the loads of a list of faces, added into the owning elements' matrices and vectors -- have
+// kernels templated on the face type (bdr_mass_kernel, bdr_load_kernel) and run one pass per local face index.
 #include "elmat.h"
 
 #include <algorithm>
 #include <climits>
+#include <utility>
+#include <vector>
 
 #include "operator.h"
 #include "partition.h"
@@ -928,6 +933,286 @@ __global__ __launch_bounds__(MASS_BLOCK) void load_kernel(int count, const int *
     }
 }
 
+// ---- boundary forms: the face mass and the face loads -----------------------------------------------------------------------
+// elmat_model.py's boundary_mass / boundary_loads.  A face is (element, local face index); the face types are the 2-node and
+// 3-node segment (DIM 2) and the triangle, the 4-node and the 9-node quadrilateral (DIM 3).  The kernels are templated on the
+// FACE type <DIM, FN>; the element type enters through the local node ids of the face (BdrFace, a kernel argument), the
+// element's node count nd and its offsets.  The host buckets the faces by (element type, local face) and runs one pass per local
+// face index in ascending order on the stream: within a pass an element occurs at most once, so the read-modify-write of its
+// entries needs no atomic and the model's order of additions holds by construction.
+constexpr int BDR_MAX_FACES = 6;
+// info[0 .. 4]: 2-node segments, 3-node segments, triangles, 4-node quadrilaterals, 9-node quadrilaterals
+constexpr int bdr_face_type(int dim, int fn) { return dim == 2 ? fn - 2 : (fn == 3 ? 2 : (fn == 4 ? 3 : 4)); }
+struct BdrFace {
+    int node[9];
+};
+// elmat_model.FACE_NODES, by the type index of em_type_index
+constexpr int bdr_num_faces(int type) { return type == 0 ? 3 : (type == 3 ? 5 : (type == 4 || type == 6 ? 6 : 4)); }
+constexpr int BDR_FACE_NODES[EM_TYPES][BDR_MAX_FACES] = {{2, 2, 2, 0, 0, 0}, {2, 2, 2, 2, 0, 0}, {3, 3, 3, 3, 0, 0}, {3, 3, 4, 4, 4, 0},
+                                                          {4, 4, 4, 4, 4, 4}, {3, 3, 3, 3, 0, 0}, {9, 9, 9, 9, 9, 9}};
+constexpr int BDR_HEX_FACES[6][4] = {{3, 2, 1, 0}, {0, 1, 5, 4}, {1, 2, 6, 5}, {2, 3, 7, 6}, {3, 0, 4, 7}, {4, 5, 6, 7}};
+constexpr BdrFace bdr_face(int type, int lf) {
+    constexpr int TRI[3][2] = {{0, 1}, {1, 2}, {2, 0}};
+    constexpr int QUAD[4][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 0}};
+    constexpr int QUAD9[4][3] = {{0, 4, 1}, {1, 5, 2}, {2, 6, 3}, {3, 7, 0}};
+    constexpr int TET[4][3] = {{1, 2, 3}, {0, 3, 2}, {0, 1, 3}, {0, 2, 1}};
+    constexpr int WEDGE[5][4] = {{0, 2, 1, 0}, {3, 4, 5, 0}, {0, 1, 4, 3}, {1, 2, 5, 4}, {2, 0, 3, 5}};
+    BdrFace f{};
+    const int fn = BDR_FACE_NODES[type][lf];
+    for (int k = 0; k < fn; ++k) {
+        if (type == 0) f.node[k] = TRI[lf][k];
+        else if (type == 1) f.node[k] = QUAD[lf][k];
+        else if (type == 2) f.node[k] = TET[lf][k];
+        else if (type == 3) f.node[k] = WEDGE[lf][k];
+        else if (type == 4) f.node[k] = BDR_HEX_FACES[lf][k];
+        else if (type == 5) f.node[k] = QUAD9[lf][k];
+        else {      // the node at face position (u, v) of Q2_QUAD_LOC: P(c0) + u (P(c1) - P(c0)) / 2 + v (P(c3) - P(c0)) / 2
+            const int *c = BDR_HEX_FACES[lf];
+            int p[3] = {0, 0, 0};
+            for (int d = 0; d < 3; ++d)
+                p[d] = 2 * EM_HEX_LOC[c[0]][d] + EM2_QUAD_LOC[k][0] * (EM_HEX_LOC[c[1]][d] - EM_HEX_LOC[c[0]][d]) +
+                       EM2_QUAD_LOC[k][1] * (EM_HEX_LOC[c[3]][d] - EM_HEX_LOC[c[0]][d]);
+            f.node[k] = (p[2] * 3 + p[1]) * 3 + p[0];
+        }
+    }
+    return f;
+}
+
+// the rule of a face type, folded at compile time from the expressions of mass_table: the segments have their own lines
+// (em_f / em_df on the 2 Gauss points, em2_n / em2_d on the 3), a face of DIM 3 is the element type (2, FN)
+constexpr int bdr_points(int dim, int fn) { return dim == 2 ? fn : mass_points(2, fn); }
+template <int DIM, int FN>
+struct BdrTable {
+    static constexpr int NQ = bdr_points(DIM, FN);
+    double dN[FN][NQ][DIM - 1];
+    double N[NQ][FN];
+    double w[NQ];
+};
+template <int DIM, int FN>
+constexpr BdrTable<DIM, FN> bdr_table() {
+    BdrTable<DIM, FN> t{};
+    constexpr int NQ = BdrTable<DIM, FN>::NQ;
+    if constexpr (DIM == 3) {
+        const MassTable<2, FN> m = mass_table<2, FN>();
+        for (int q = 0; q < NQ; ++q) {
+            t.w[q] = m.w[q];
+            for (int a = 0; a < FN; ++a) {
+                t.N[q][a] = m.N[q][a];
+                t.dN[a][q][0] = m.dN[a][q][0];
+                t.dN[a][q][DIM - 2] = m.dN[a][q][1];
+            }
+        }
+    } else {
+        for (int q = 0; q < NQ; ++q) {
+            const double p = FN == 2 ? EM_GAUSS[q % 2] : EM2_GAUSS[q];
+            t.w[q] = FN == 2 ? 0.5 : EM2_W[q];
+            for (int a = 0; a < FN; ++a) {
+                t.N[q][a] = FN == 2 ? em_f(a, p) : em2_n(a, p);
+                t.dN[a][q][0] = FN == 2 ? em_df(a) : em2_d(a, p);
+            }
+        }
+    }
+    return t;
+}
+template <int DIM, int FN>
+__device__ const BdrTable<DIM, FN> BDR_TABLE = bdr_table<DIM, FN>();
+
+constexpr int BDR_BLOCK = 256;
+constexpr int bdr_fpb(int fn) { return fn == 9 ? 5 : (fn == 4 ? 16 : 32); }      // faces per workgroup
+
+// The checks of the face list.  Face f with face_elem outside [0, NE) or face_local outside the range of the element's type:
+// key[f] = -1 and f to the integer minimum words[0]; else key[f] = type * 8 + local face, and the face's bit is set in the byte
+// of its element (mask: one byte per element, four to a word) -- a bit that was already set raises words[1].
+__global__ __launch_bounds__(256) void bdr_check_kernel(int NF, int NE, int dim, const int *__restrict__ eI,
+                                                        const int *__restrict__ face_elem, const int *__restrict__ face_local,
+                                                        unsigned *__restrict__ mask, int *__restrict__ key, int *__restrict__ words) {
+    const long f = (long)blockIdx.x * 256 + threadIdx.x;
+    if (f >= NF) return;
+    const int e = face_elem[f], lf = face_local[f];
+    int k = -1;
+    if (e >= 0 && e < NE) {
+        const int t = em_type_index(dim, eI[e + 1] - eI[e]);      // (the mesh has been checked: t >= 0)
+        if (t >= 0 && lf >= 0 && lf < bdr_num_faces(t)) {
+            k = t * 8 + lf;
+            const unsigned bit = 1u << (8 * (e & 3) + lf);
+            if (atomicOr(mask + (e >> 2), bit) & bit) atomicOr(words + 1, 1);
+        }
+    }
+    key[f] = k;
+    if (k < 0) atomicMin(words, (int)f);
+}
+// the number of elements whose byte of the mask is not zero, added to *count
+__global__ __launch_bounds__(256) void bdr_touched_kernel(int nwords, const unsigned *__restrict__ mask, int *__restrict__ count) {
+    const long w = (long)blockIdx.x * 256 + threadIdx.x;
+    if (w >= nwords) return;
+    const unsigned m = mask[w];
+    const int n = ((m & 0xffu) != 0) + ((m & 0xff00u) != 0) + ((m & 0xff0000u) != 0) + ((m & 0xff000000u) != 0);
+    if (n) atomicAdd(count, n);
+}
+
+// Phases of both kernels, a barrier after each:
+//   stage   one lane per (face, face node): the node's coordinates (and g) into LDS; the face's element, coefficient, offsets
+//   point   one lane per (face, point): the tangents, m2, meas = sqrt(m2) and s = (w * meas) * c in registers; a measure that
+//           is not positive sends the face's index in the list to the integer minimum *bad
+// list: the faces of this launch (indices into face_elem / coef), all of one element type (nd nodes) and one local face F.
+template <int DIM, int FN, int VDIM, int FPB>
+__device__ inline void bdr_stage_points(int count, const int *__restrict__ list, const BdrFace &F, int nd, const int *__restrict__ eI,
+                                        const int *__restrict__ eJ, const int *__restrict__ face_elem,
+                                        const double *__restrict__ coords, const double *__restrict__ coef,
+                                        const double *__restrict__ g, double *sX, double *sG, double *sS, int *sE, int *bad) {
+    constexpr int NQ = BdrTable<DIM, FN>::NQ;
+    const BdrTable<DIM, FN> &T = BDR_TABLE<DIM, FN>;
+    __shared__ double sC[FPB];
+    __shared__ int sF[FPB];
+    const int tid = threadIdx.x;
+    for (int idx = tid; idx < FPB * FN; idx += BDR_BLOCK) {
+        const int fl = idx / FN, a = idx - fl * FN;
+        const long slot = (long)blockIdx.x * FPB + fl;
+        double x[DIM], gv[VDIM];
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) x[d] = 0.0;
+#pragma unroll
+        for (int i = 0; i < VDIM; ++i) gv[i] = 0.0;
+        if (slot < count) {
+            const int f = list[slot], e = face_elem[f];
+            const long vb = eI ? (long)eI[e] : (long)e * nd;
+            const int v = eJ[vb + F.node[a]];
+#pragma unroll
+            for (int d = 0; d < DIM; ++d) x[d] = coords[(long)v * DIM + d];
+            if (g) {
+#pragma unroll
+                for (int i = 0; i < VDIM; ++i) gv[i] = g[(long)v * VDIM + i];
+            }
+            if (a == 0) {
+                sE[fl] = e;
+                sF[fl] = f;
+                sC[fl] = coef ? coef[f] : 1.0;
+            }
+        } else if (a == 0) {
+            sE[fl] = -1;
+            sF[fl] = -1;
+            sC[fl] = 0.0;
+        }
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) sX[idx * DIM + d] = x[d];
+        if (g) {
+#pragma unroll
+            for (int i = 0; i < VDIM; ++i) sG[idx * VDIM + i] = gv[i];
+        }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < FPB * NQ; idx += BDR_BLOCK) {
+        const int fl = idx / NQ, q = idx - fl * NQ;
+        const double *X = sX + fl * FN * DIM;
+        double t[DIM - 1][DIM], m2;
+#pragma unroll
+        for (int j = 0; j < DIM - 1; ++j)
+#pragma unroll
+            for (int i = 0; i < DIM; ++i) {
+                double v = X[i] * T.dN[0][q][j];
+#pragma unroll
+                for (int c = 1; c < FN; ++c) v = v + X[c * DIM + i] * T.dN[c][q][j];
+                t[j][i] = v;
+            }
+        if constexpr (DIM == 2) {
+            m2 = t[0][0] * t[0][0] + t[0][1] * t[0][1];
+        } else {
+            const double n0 = t[0][1] * t[DIM - 2][2] - t[0][2] * t[DIM - 2][1];
+            const double n1 = t[0][2] * t[DIM - 2][0] - t[0][0] * t[DIM - 2][2];
+            const double n2 = t[0][0] * t[DIM - 2][1] - t[0][1] * t[DIM - 2][0];
+            m2 = (n0 * n0 + n1 * n1) + n2 * n2;
+        }
+        const double meas = sqrt(m2);
+        if (!(meas > 0.0) && sF[fl] >= 0) atomicMin(bad, sF[fl]);
+        sS[idx] = (T.w[q] * meas) * sC[fl];
+    }
+    __syncthreads();
+}
+
+// The face mass, added to the matrices in out (nullptr: the checks only).  After stage and point:
+//   entry   one lane per (face, node pair a <= b of the face): the whole sum over the points, in ascending order, lives in the
+//           lane and is added to the element's entries (a, b) and (b, a) of every component in global memory
+template <int DIM, int FN, int VDIM>
+__global__ __launch_bounds__(BDR_BLOCK) void bdr_mass_kernel(int count, const int *__restrict__ list, const BdrFace F, int nd,
+                                                             const int *__restrict__ eI, const int *__restrict__ eJ,
+                                                             const roff_t *__restrict__ moff, const int *__restrict__ face_elem,
+                                                             const double *__restrict__ coords, const double *__restrict__ coef,
+                                                             double *out, int *__restrict__ bad) {
+    constexpr int FPB = bdr_fpb(FN), NQ = BdrTable<DIM, FN>::NQ, NPAIR = FN * (FN + 1) / 2;
+    const BdrTable<DIM, FN> &T = BDR_TABLE<DIM, FN>;
+    __shared__ double sX[FPB * FN * DIM];
+    __shared__ double sS[FPB * NQ];
+    __shared__ int sE[FPB];
+    bdr_stage_points<DIM, FN, VDIM, FPB>(count, list, F, nd, eI, eJ, face_elem, coords, coef, nullptr, sX, nullptr, sS, sE, bad);
+    if (!out) return;                             // (the same in every lane of the grid)
+    const int S = nd * VDIM;
+    for (int idx = threadIdx.x; idx < FPB * NPAIR; idx += BDR_BLOCK) {
+        const int fl = idx / NPAIR, ab = MASS_PAIRS<FN>.ab[idx - fl * NPAIR], a = ab >> 5, b = ab & 31;
+        const int e = sE[fl];
+        if (e < 0) continue;
+        const double *s = sS + fl * NQ;
+        double acc = 0.0;
+#pragma unroll 1
+        for (int q = 0; q < NQ; ++q) {
+            const double term = s[q] * (T.N[q][a] * T.N[q][b]);
+            acc = acc + term;
+        }
+        double *m = out + (moff ? moff[e] : (roff_t)e * S * S);
+        const int na = F.node[a], nb = F.node[b];
+#pragma unroll
+        for (int i = 0; i < VDIM; ++i) {
+            const long r = VDIM * na + i, c = VDIM * nb + i;
+            m[r * S + c] = m[r * S + c] + acc;
+            if (a != b) m[c * S + r] = m[c * S + r] + acc;
+        }
+    }
+}
+
+// The face loads of the nodal g (NV x VDIM), added to the vectors in out (nullptr: the checks only).  After stage and point:
+//   source  one lane per (face, point, component): gq = sum over the face nodes, ascending, of N_c * g_c; s * gq is kept
+//   dof     one lane per (face, face node, component): the whole sum over the points of (s * gq) * N_a, added to the element's
+//           vector at the dof of the node in global memory
+template <int DIM, int FN, int VDIM>
+__global__ __launch_bounds__(BDR_BLOCK) void bdr_load_kernel(int count, const int *__restrict__ list, const BdrFace F, int nd,
+                                                             const int *__restrict__ eI, const int *__restrict__ eJ,
+                                                             const int *__restrict__ face_elem, const double *__restrict__ coords,
+                                                             const double *__restrict__ coef, const double *__restrict__ g,
+                                                             double *out, int *__restrict__ bad) {
+    constexpr int FPB = bdr_fpb(FN), NQ = BdrTable<DIM, FN>::NQ;
+    const BdrTable<DIM, FN> &T = BDR_TABLE<DIM, FN>;
+    __shared__ double sX[FPB * FN * DIM];
+    __shared__ double sG[FPB * FN * VDIM];
+    __shared__ double sS[FPB * NQ];
+    __shared__ double sQ[FPB * NQ * VDIM];
+    __shared__ int sE[FPB];
+    bdr_stage_points<DIM, FN, VDIM, FPB>(count, list, F, nd, eI, eJ, face_elem, coords, coef, g, sX, sG, sS, sE, bad);
+    if (!out) return;                             // (the same in every lane of the grid)
+    const int tid = threadIdx.x;
+    for (int idx = tid; idx < FPB * NQ * VDIM; idx += BDR_BLOCK) {
+        const int fl = idx / (NQ * VDIM), r = idx - fl * (NQ * VDIM), q = r / VDIM, i = r - q * VDIM;
+        const double *G = sG + fl * FN * VDIM + i;
+        double gq = T.N[q][0] * G[0];
+        for (int c = 1; c < FN; ++c) gq = gq + T.N[q][c] * G[c * VDIM];
+        sQ[idx] = sS[fl * NQ + q] * gq;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < FPB * FN * VDIM; idx += BDR_BLOCK) {
+        const int fl = idx / (FN * VDIM), r = idx - fl * (FN * VDIM), a = r / VDIM, i = r - a * VDIM;
+        const int e = sE[fl];
+        if (e < 0) continue;
+        const double *Q = sQ + fl * NQ * VDIM + i;
+        double acc = 0.0;
+#pragma unroll 1
+        for (int q = 0; q < NQ; ++q) {
+            const double term = Q[q * VDIM] * T.N[q][a];
+            acc = acc + term;
+        }
+        const long vb = eI ? (long)eI[e] : (long)e * nd;
+        double *v = out + (vb + F.node[a]) * VDIM + i;
+        *v = *v + acc;
+    }
+}
+
 // ---- tables ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void em_offsets_kernel(int NE, int nd, int *__restrict__ eI) {
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
@@ -1162,6 +1447,143 @@ void mass_or_loads(hipStream_t s, const std::string &name, int NV, int dim, cons
     SA_HIP_CHECK(hipStreamSynchronize(s));
 }
 
+// ---- boundary forms ---------------------------------------------------------------------------------------------------------
+struct BdrLaunch {
+    hipStream_t s;
+    const int *eI, *eJ, *face_elem;
+    const roff_t *moff;
+    const double *coords, *coef, *g;
+    double *out;
+    int *bad;
+};
+template <int DIM, int FN, int VDIM>
+void bdr_launch(const BdrLaunch &L, const BdrFace &F, int nd, int count, const int *list) {
+    const dim3 grid((unsigned)div_up(count, bdr_fpb(FN)));
+    if (L.g)
+        hipLaunchKernelGGL((bdr_load_kernel<DIM, FN, VDIM>), grid, dim3(BDR_BLOCK), 0, L.s, count, list, F, nd, L.eI, L.eJ, L.face_elem,
+                           L.coords, L.coef, L.g, L.out, L.bad);
+    else
+        hipLaunchKernelGGL((bdr_mass_kernel<DIM, FN, VDIM>), grid, dim3(BDR_BLOCK), 0, L.s, count, list, F, nd, L.eI, L.eJ, L.moff,
+                           L.face_elem, L.coords, L.coef, L.out, L.bad);
+    SA_HIP_CHECK(hipGetLastError());
+}
+// the faces `list` of elements of type `type` (em_type_index) with the local face index lf
+void bdr_launch_face(const BdrLaunch &L, int dim, int vdim, int type, int lf, int count, const int *list) {
+    const BdrFace F = bdr_face(type, lf);
+    const int nd = EM_TYPE_ND[type], fn = BDR_FACE_NODES[type][lf];
+#define SA_BDR_CASE(DIM, FN)                                            \
+    if (dim == DIM && fn == FN) {                                       \
+        if (vdim == 1) bdr_launch<DIM, FN, 1>(L, F, nd, count, list);   \
+        else bdr_launch<DIM, FN, DIM>(L, F, nd, count, list);           \
+        return;                                                         \
+    }
+    SA_BDR_CASE(2, 2)
+    SA_BDR_CASE(2, 3)
+    SA_BDR_CASE(3, 3)
+    SA_BDR_CASE(3, 4)
+    SA_BDR_CASE(3, 9)
+#undef SA_BDR_CASE
+    SA_REQUIRE(false, "boundary forms: no such face type");
+}
+
+// the face mass (g nullptr) or the face loads of the arguments of saamge_amd_boundary_mass / _loads, already checked
+void boundary_forms(hipStream_t s, const std::string &name, int NV, int dim, const double *coords, int NE, int nde,
+                    const int *elem_ptr, const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim,
+                    const double *coef, const double *g, double *out, long long info[8]) {
+    if (NF == 0) return;
+    if (NE == 0 && info) info[6] = 0;
+    SA_REQUIRE(NE > 0, name + "face 0: face_elem is outside [0, NE)");
+    EmMesh M;
+    em_mesh(s, name, NV, dim, NE, nde, elem_ptr, elem_to_vertex, vdim, !g, M, nullptr);
+    // ---- the face list: ranges, the mask of the (element, local face) pairs, the key of every face
+    DBuf<int> hold_fe, hold_fl, key((size_t)NF), words(3), flag((size_t)NF), pos((size_t)NF + 1);
+    const int *fe = device_view(hold_fe, face_elem, (size_t)NF, s), *fl = device_view(hold_fl, face_local, (size_t)NF, s);
+    const int nwords = (int)(((int64_t)NE + 3) / 4);
+    DBuf<unsigned> mask((size_t)nwords);
+    mask.zero(s);
+    const int init[3] = {INT_MAX, 0, 0};
+    SA_HIP_CHECK(hipMemcpyAsync(words.p, init, sizeof(init), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(bdr_check_kernel, grid_flat(NF), dim3(256), 0, s, NF, NE, dim, M.eI, fe, fl, mask.p, key.p, words.p);
+    SA_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(bdr_touched_kernel, grid_flat(nwords), dim3(256), 0, s, nwords, (const unsigned *)mask.p, words.p + 2);
+    SA_HIP_CHECK(hipGetLastError());
+    int w[3];
+    read_back(w, (const int *)words.p, 3, s);
+    if (w[0] < NF) {
+        if (info) info[6] = w[0];
+        const int e = read_one(fe + w[0], s);
+        SA_REQUIRE(false, name + "face " + std::to_string(w[0]) + ": " +
+                              (e < 0 || e >= NE ? "face_elem is outside [0, NE)" : "face_local is outside the element type's range"));
+    }
+    if (w[1]) {      // a pair is listed twice: the first face of the list that is one of a repeated pair, found on the host
+        const hvec<int> he = fetch_host(fe, (size_t)NF, s), hl = fetch_host(fl, (size_t)NF, s);
+        std::vector<std::pair<int64_t, int>> pairs((size_t)NF);
+        for (int f = 0; f < NF; ++f) pairs[(size_t)f] = {(int64_t)he[(size_t)f] * 8 + hl[(size_t)f], f};
+        std::sort(pairs.begin(), pairs.end());
+        int first = NF;
+        for (size_t k = 0; k + 1 < pairs.size(); ++k)
+            if (pairs[k].first == pairs[k + 1].first && (k == 0 || pairs[k - 1].first != pairs[k].first)) first = std::min(first, pairs[k].second);
+        if (info) info[6] = first;
+        SA_REQUIRE(false, name + "face " + std::to_string(first) + ": the same (element, local face) is listed twice");
+    }
+    // ---- one list per (element type, local face)
+    DBuf<int> list[EM_TYPES][BDR_MAX_FACES];
+    int count[EM_TYPES][BDR_MAX_FACES] = {};
+    int64_t doubles = 0;
+    for (int t = 0; t < EM_TYPES; ++t) {
+        if (!M.count[t]) continue;
+        for (int lf = 0; lf < bdr_num_faces(t); ++lf) {
+            const int c = count[t][lf] = make_list(s, NF, key.p, t * 8 + lf, flag, pos, list[t][lf]);
+            const int fn = BDR_FACE_NODES[t][lf];
+            if (info) info[bdr_face_type(dim, fn)] += c;
+            doubles += (int64_t)c * (g ? fn * vdim : fn * fn * vdim);
+        }
+    }
+    if (info) {
+        info[5] = (long long)doubles;
+        info[7] = w[2];
+    }
+    // ---- the passes: ascending local face, so that the faces of one element are added in that order
+    DBuf<double> hold_X, hold_c, hold_g, hold_out;
+    BdrLaunch L;
+    L.s = s;
+    L.eI = elem_ptr ? M.eI : nullptr;
+    L.eJ = M.eJ;
+    L.face_elem = fe;
+    L.moff = M.moff.p;
+    L.coords = device_view(hold_X, coords, (size_t)NV * dim, s);
+    L.coef = coef ? device_view(hold_c, coef, (size_t)NF, s) : nullptr;
+    L.g = g ? device_view(hold_g, g, (size_t)NV * vdim, s) : nullptr;
+    L.out = out;
+    if (out && !is_device_ptr(out)) {
+        upload(hold_out, (const double *)out, (size_t)M.doubles, s);
+        L.out = hold_out.p;
+    }
+    L.bad = words.p;
+    SA_HIP_CHECK(hipMemsetAsync(words.p, 0x7f, sizeof(int), s));
+    for (int lf = 0; lf < BDR_MAX_FACES; ++lf)
+        for (int t = 0; t < EM_TYPES; ++t)
+            if (count[t][lf]) bdr_launch_face(L, dim, vdim, t, lf, count[t][lf], list[t][lf].p);
+    const int bad = read_one((const int *)words.p, s);
+    if (bad < NF) {
+        if (info) info[6] = bad;
+        SA_REQUIRE(false, name + "face " + std::to_string(bad) + ": the measure is not positive");
+    }
+    if (hold_out.p) SA_HIP_CHECK(hipMemcpyAsync(out, hold_out.p, (size_t)M.doubles * sizeof(double), hipMemcpyDeviceToHost, s));
+    SA_HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// the checks of both entry points that need no device
+void bdr_begin(const std::string &name, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+               const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim, long long info[8]) {
+    em_begin(name, NV, dim, NE, info);
+    SA_REQUIRE(NF >= 0, name + "NF < 0");
+    SA_REQUIRE(vdim == 1 || vdim == dim, name + "vdim must be 1 or dim");
+    SA_REQUIRE(NF == 0 || (face_elem && face_local), name + "null argument: face_elem or face_local");
+    SA_REQUIRE(NF == 0 || NE == 0 || (coords && elem_to_vertex), name + "null argument: coords or elem_to_vertex");
+    em_check_sizes(name, NV, dim, NE, nde, elem_ptr, vdim);
+}
+
 }  // namespace
 
 void element_matrices(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
@@ -1249,6 +1671,26 @@ void element_loads(hipStream_t s, int NV, int dim, const double *coords, int NE,
     SA_REQUIRE(NE == 0 || (coords && elem_to_vertex), name + "null argument: coords or elem_to_vertex");
     em_check_sizes(name, NV, dim, NE, nde, elem_ptr, vdim);
     mass_or_loads(s, name, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, coef, src, 0, elvec_out, info);
+}
+
+void boundary_mass(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                   const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim, const double *coef,
+                   double *elmat_inout, long long info[8]) {
+    const std::string name("saamge_amd_boundary_mass: ");
+    bdr_begin(name, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, vdim, info);
+    SA_REQUIRE(NF == 0 || coef, name + "null argument: coef");
+    boundary_forms(s, name, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, vdim, coef, nullptr,
+                   elmat_inout, info);
+}
+
+void boundary_loads(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                    const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim, const double *coef,
+                    const double *g, double *elvec_inout, long long info[8]) {
+    const std::string name("saamge_amd_boundary_loads: ");
+    bdr_begin(name, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, vdim, info);
+    SA_REQUIRE(g, name + "null argument: g");
+    boundary_forms(s, name, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, vdim, coef, g,
+                   elvec_inout, info);
 }
 
 }  // namespace saamge_amd

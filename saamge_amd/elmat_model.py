@@ -33,7 +33,9 @@ are those of the scalar formulas).
   refused      dim, kind, ncoef out of range, a node count that is no type of the dimension, malformed offsets, a vertex id
                outside [0, NV), an element that lists a vertex twice, and an element whose det is not positive at a point
                (ElementError, .element the smallest such id).
-  zeroth order element_mass and element_loads, on the same types, node orders and geometry: defined at the end of this file.
+  zeroth order element_mass and element_loads, on the same types, node orders and geometry: defined further down in this file.
+  boundary     FACE_NODES, boundary_mass and boundary_loads: the face mass and the face loads of a list of (element, local face)
+               pairs, added into the owning elements' matrices and vectors: defined at the end of this file.
 """
 import numpy as np
 
@@ -492,4 +494,229 @@ def element_loads(coords, elem_to_vertex, src, vdim=1, coef=None, elem_ptr=None)
         raise ElementError(np.flatnonzero(bad)[0])
     if elem_ptr is None:
         return out.reshape(NE, nd[0] * vdim) if NE else out.reshape(0, 0)
+    return out
+
+
+# ---- boundary forms: the face mass (Robin) and the face loads (Neumann) ---------------------------------------------------------
+#   face         a pair (element id, local face index); FACE_NODES[(dim, nodes)][local face] lists the element's local node ids of
+#                the face in the node order of the face's own type: the 2-node / 3-node segment (start, end / start, middle, end),
+#                the triangle, the 4-node quadrilateral (QUAD_LOC order) and the 9-node quadrilateral (Q2_QUAD_LOC order).
+#   rule         of the face type (face_rule): the 2-node segment has the 2 GAUSS points, weight 0.5 each, shapes _f, derivatives
+#                _df; the 3-node segment GAUSS3 / GAUSS3_W, _n2, _d2; a triangle, 4-node or 9-node quadrilateral face has the mass
+#                rule, shape values and reference gradients of the element type (2, 3), (2, 4), (2, 9).
+#   point        tangents t_j[i] = sum over the face nodes c, ascending, of x_c[i] * dN_c[j], the first product as it is;
+#                dim 2: m2 = t[0] * t[0] + t[1] * t[1]; dim 3: n = t_0 x t_1 (n0 = t0y * t1z - t0z * t1y, n1 = t0z * t1x - t0x * t1z,
+#                n2 = t0x * t1y - t0y * t1x), m2 = (n0 * n0 + n1 * n1) + n2 * n2; meas = sqrt(m2), correctly rounded;
+#                s = (w * meas) * c_f with the coefficient c_f of the face.  A face with a point where not (meas > 0) is refused.
+#   mass         face entry (a, b), a <= b in face-node order, is the sum over the points, ascending from 0.0, of s * (N_a * N_b);
+#                (b, a) is the same double.  The complete face matrix is added to the owning element's packed matrix, one addition
+#                per entry: vdim 1 at (node a, node b), vdim = dim at ((a, i), (b, i)) for every component i.  Entries no listed
+#                face touches keep their bits.  The faces of one element are added in ascending local face index, whatever the
+#                order of the list.
+#   loads        g nodal (NV, vdim): per point gq_i = sum over the face nodes c, ascending, of N_c * g[c][i]; face dof (a, i) gets
+#                the sum over the points from 0.0 of (s * gq_i) * N_a, added to the element's packed vector at the dof of local
+#                node a, same face order.  coef None: 1.0.
+#   refused      vdim, missing arguments, what _mesh refuses, then the first face (lowest index in the list) with face_elem outside
+#                [0, NE) or face_local outside the type's range, then the first face whose (element, local face) the list holds
+#                more than once, then the first face with a non-positive measure (FaceError, .face).
+def _hex27_faces(hex_faces):
+    out = []
+    for c in hex_faces:
+        P = [np.array(HEX_LOC[k]) * 2 for k in c]
+        face = []
+        for (u, v) in Q2_QUAD_LOC:
+            ix, iy, iz = P[0] + u * (P[1] - P[0]) // 2 + v * (P[3] - P[0]) // 2
+            face.append(int((iz * 3 + iy) * 3 + ix))
+        out.append(tuple(face))
+    return tuple(out)
+
+
+_HEX_FACES = ((3, 2, 1, 0), (0, 1, 5, 4), (1, 2, 6, 5), (2, 3, 7, 6), (3, 0, 4, 7), (4, 5, 6, 7))
+FACE_NODES = {
+    (2, 3): ((0, 1), (1, 2), (2, 0)),
+    (2, 4): ((0, 1), (1, 2), (2, 3), (3, 0)),
+    (2, 9): ((0, 4, 1), (1, 5, 2), (2, 6, 3), (3, 7, 0)),
+    (3, 4): ((1, 2, 3), (0, 3, 2), (0, 1, 3), (0, 2, 1)),
+    (3, 6): ((0, 2, 1), (3, 4, 5), (0, 1, 4, 3), (1, 2, 5, 4), (2, 0, 3, 5)),
+    (3, 8): _HEX_FACES,
+    (3, 27): _hex27_faces(_HEX_FACES),
+}
+# (dim, face nodes) -> info[0..4] of saamge_amd_boundary_mass / _loads: 2-node segments, 3-node segments, triangles, 4-node
+# quadrilaterals, 9-node quadrilaterals
+FACE_TYPE_INDEX = {(2, 2): 0, (2, 3): 1, (3, 3): 2, (3, 4): 3, (3, 9): 4}
+MAX_FACES = 6
+
+
+class FaceError(ValueError):
+    """A refused face of a face list; .face is its index in the list (the smallest such index)."""
+
+    def __init__(self, face, what):
+        ValueError.__init__(self, "face %d: %s" % (face, what))
+        self.face = int(face)
+
+
+def face_rule(dim, fn):
+    """The rule of the face type with fn nodes of a dim-dimensional element: per point (N[a], dN[a][j], weight)."""
+    if (dim, fn) == (2, 2):
+        return [([_f(0, p), _f(1, p)], [(_df(0),), (_df(1),)], 0.5) for p in GAUSS]
+    if (dim, fn) == (2, 3):
+        return [([_n2(k, p) for k in range(3)], [(_d2(k, p),) for k in range(3)], GAUSS3_W[q]) for q, p in enumerate(GAUSS3)]
+    if (dim, fn) not in FACE_TYPE_INDEX:
+        raise ValueError("%d nodes: no face type of a %dD element" % (fn, dim))
+    return [(shape_values(2, fn, q), reference_gradients(2, fn, q), mass_point_weight(2, fn, q)) for q in range(MASS_NPOINTS[(2, fn)])]
+
+
+def _face_points(X, dim, fn, c):
+    """Per point of the face rule: (N, s) with s = (weight * meas) * c over the n faces of X (n, fn, dim), and per face whether
+    a measure was not positive."""
+    bad = np.zeros(X.shape[0], bool)
+    out = []
+    with np.errstate(all="ignore"):
+        for N, dN, w in face_rule(dim, fn):
+            t = [[None] * dim for _ in range(dim - 1)]
+            for j in range(dim - 1):
+                for i in range(dim):
+                    v = X[:, 0, i] * dN[0][j]
+                    for a in range(1, fn):
+                        v = v + X[:, a, i] * dN[a][j]
+                    t[j][i] = v
+            if dim == 2:
+                m2 = t[0][0] * t[0][0] + t[0][1] * t[0][1]
+            else:
+                (ax, ay, az), (bx, by, bz) = t
+                n0, n1, n2 = ay * bz - az * by, az * bx - ax * bz, ax * by - ay * bx
+                m2 = (n0 * n0 + n1 * n1) + n2 * n2
+            meas = np.sqrt(m2)
+            bad |= ~(meas > 0.0)
+            out.append((N, (w * meas) * c))
+    return out, bad
+
+
+def _face_list(dim, nd, face_elem, face_local):
+    """The checked face list as int64 arrays."""
+    if face_elem is None or face_local is None:
+        raise ValueError("face_elem and face_local: (NF,) are needed")
+    fe, fl = np.asarray(face_elem).astype(np.int64).ravel(), np.asarray(face_local).astype(np.int64).ravel()
+    if len(fe) != len(fl):
+        raise ValueError("face_elem and face_local: (NF,) are needed")
+    NE = len(nd)
+    wrong_e = (fe < 0) | (fe >= NE)
+    nfaces = np.zeros(len(fe), np.int64)
+    counts = {k[1]: len(v) for k, v in FACE_NODES.items() if k[0] == dim}
+    if NE:
+        nfaces[~wrong_e] = np.array([counts[int(c)] for c in nd[fe[~wrong_e]]], np.int64)
+    wrong = wrong_e | (fl < 0) | (fl >= nfaces)
+    if wrong.any():
+        f = int(np.flatnonzero(wrong)[0])
+        raise FaceError(f, "face_elem is outside [0, NE)" if wrong_e[f] else "face_local is outside the element type's range")
+    key = fe * MAX_FACES + fl
+    uniq, first, count = np.unique(key, return_index=True, return_counts=True)
+    if (count > 1).any():
+        raise FaceError(int(first[count > 1].min()), "the same (element, local face) is listed twice")
+    return fe, fl
+
+
+def _face_buckets(dim, nd, fe, fl):
+    """(local face, nodes of the element type, the faces of the list): by ascending local face, then node count."""
+    for lf in range(MAX_FACES):
+        sel = np.flatnonzero(fl == lf)
+        for c in np.unique(nd[fe[sel]]):
+            yield lf, int(c), sel[nd[fe[sel]] == c]
+
+
+def _face_coef(coef, NF, needed):
+    if coef is None:
+        if needed:
+            raise ValueError("coef: (NF,) is needed")
+        return np.ones(NF)
+    coef = np.asarray(coef, np.float64).reshape(-1)
+    if len(coef) != NF:
+        raise ValueError("coef: (NF,) is needed")
+    return coef
+
+
+def _refuse_measure(bad):
+    if bad.any():
+        raise FaceError(int(np.flatnonzero(bad)[0]), "the measure is not positive")
+
+
+def boundary_mass(coords, elem_to_vertex, face_elem, face_local, coef, vdim=1, elem_ptr=None, add_to=None):
+    """add_to plus the face mass matrices (coef_f u, v)_face of the listed faces, coef (NF,): a new array in the layout of
+    add_to, which is that of element_matrices / element_mass ((NE, size, size) when elem_ptr is None, else packed)."""
+    X, dim, ep, e2v, nd = _mesh(coords, elem_to_vertex, elem_ptr)
+    vdim = _vdim(vdim, dim)
+    if coef is None:
+        raise ValueError("coef: (NF,) is needed")
+    fe, fl = _face_list(dim, nd, face_elem, face_local)
+    coef = _face_coef(coef, len(fe), True)
+    if add_to is None:
+        raise ValueError("add_to: the matrices the faces are added to are needed")
+    moff = np.concatenate([[0], np.cumsum((nd * vdim) ** 2)])
+    out = np.array(add_to, np.float64).ravel()
+    if len(out) != moff[-1]:
+        raise ValueError("add_to: the layout of element_matrices is needed")
+    bad = np.zeros(len(fe), bool)
+    with np.errstate(all="ignore"):
+        for lf, c, ids in _face_buckets(dim, nd, fe, fl):
+            nodes = np.array(FACE_NODES[(dim, c)][lf])
+            fn, S = len(nodes), c * vdim
+            points, bad[ids] = _face_points(X[e2v[ep[fe[ids]][:, None] + nodes]], dim, fn, coef[ids])
+            pa, pb = np.triu_indices(fn)
+            acc = np.zeros((len(ids), len(pa)))
+            for N, s in points:
+                NN = np.array([N[a] * N[b] for a, b in zip(pa, pb)])
+                term = s[:, None] * NN[None, :]
+                acc = acc + term
+            base = moff[fe[ids]]
+            for k, (a, b) in enumerate(zip(pa, pb)):
+                for i in range(vdim):
+                    r, cc = vdim * nodes[a] + i, vdim * nodes[b] + i
+                    for idx in ([base + r * S + cc] if a == b else [base + r * S + cc, base + cc * S + r]):
+                        out[idx] = out[idx] + acc[:, k]          # (an element occurs once in a bucket: no index twice)
+    _refuse_measure(bad)
+    if elem_ptr is None:
+        return out.reshape(len(nd), nd[0] * vdim, nd[0] * vdim) if len(nd) else out.reshape(0, 0, 0)
+    return out
+
+
+def boundary_loads(coords, elem_to_vertex, face_elem, face_local, g, vdim=1, coef=None, elem_ptr=None, add_to=None):
+    """add_to plus the face load vectors (coef_f g, v)_face of the listed faces, g nodal (NV, vdim) or (NV,), coef (NF,) or None
+    (1.0): a new array in the layout of add_to, which is that of element_loads."""
+    X, dim, ep, e2v, nd = _mesh(coords, elem_to_vertex, elem_ptr)
+    vdim = _vdim(vdim, dim)
+    NV = X.shape[0]
+    if g is None:
+        raise ValueError("g: (NV, vdim) is needed")
+    G = np.asarray(g, np.float64)
+    if G.size != NV * vdim:
+        raise ValueError("g: (NV, vdim) is needed")
+    G = G.reshape(NV, vdim)
+    fe, fl = _face_list(dim, nd, face_elem, face_local)
+    coef = _face_coef(coef, len(fe), False)
+    if add_to is None:
+        raise ValueError("add_to: the vectors the faces are added to are needed")
+    out = np.array(add_to, np.float64).ravel()
+    if len(out) != ep[-1] * vdim:
+        raise ValueError("add_to: the layout of element_loads is needed")
+    bad = np.zeros(len(fe), bool)
+    with np.errstate(all="ignore"):
+        for lf, c, ids in _face_buckets(dim, nd, fe, fl):
+            nodes = np.array(FACE_NODES[(dim, c)][lf])
+            fn = len(nodes)
+            v = e2v[ep[fe[ids]][:, None] + nodes]
+            points, bad[ids] = _face_points(X[v], dim, fn, coef[ids])
+            F = G[v]                                                 # (n, fn, vdim)
+            acc = np.zeros((len(ids), fn, vdim))
+            for N, s in points:
+                gq = N[0] * F[:, 0, :]
+                for a in range(1, fn):
+                    gq = gq + N[a] * F[:, a, :]
+                sg = s[:, None] * gq
+                term = sg[:, None, :] * np.array(N)[None, :, None]
+                acc = acc + term
+            idx = (ep[fe[ids]] * vdim)[:, None, None] + (vdim * nodes)[None, :, None] + np.arange(vdim)[None, None, :]
+            out[idx] = out[idx] + acc
+    _refuse_measure(bad)
+    if elem_ptr is None:
+        return out.reshape(len(nd), nd[0] * vdim) if len(nd) else out.reshape(0, 0)
     return out

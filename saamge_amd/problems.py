@@ -1100,3 +1100,29 @@ def q2_straight_sided(coords, elem_to_node):
             acc = acc + X[e2n[:, corner[tuple(c)]]]
         X[e2n[:, k]] = acc / len(combos)
     return X
+
+
+# ---- the faces of a mesh that belong to one element only (harness for saamge_amd_boundary_mass / _loads)
+def boundary_faces(dim, elem_to_vertex, elem_ptr=None):
+    """(face_elem, face_local), int32, ascending by (element, local face): the faces -- elmat_model.FACE_NODES of the element's
+    type -- whose node set no other element's face has.  On a conforming mesh these are the boundary faces."""
+    from .elmat_model import FACE_NODES
+    e2v = np.asarray(elem_to_vertex)
+    ep = np.arange(e2v.shape[0] + 1, dtype=np.int64) * e2v.shape[1] if elem_ptr is None else np.asarray(elem_ptr, np.int64)
+    e2v = e2v.astype(np.int64).ravel()
+    nd = np.diff(ep)
+    rows, elem, local = [], [], []
+    for c in np.unique(nd):
+        ids = np.flatnonzero(nd == c)
+        for lf, nodes in enumerate(FACE_NODES[(dim, int(c))]):
+            v = np.sort(e2v[ep[ids][:, None] + np.array(nodes)], axis=1)
+            rows.append(np.pad(v, ((0, 0), (0, 9 - v.shape[1])), constant_values=-1))
+            elem.append(ids)
+            local.append(np.full(len(ids), lf, np.int64))
+    if not rows:
+        return np.zeros(0, np.int32), np.zeros(0, np.int32)
+    rows, elem, local = np.concatenate(rows), np.concatenate(elem), np.concatenate(local)
+    _, inverse, count = np.unique(rows, axis=0, return_inverse=True, return_counts=True)
+    once = np.flatnonzero(count[inverse.ravel()] == 1)
+    order = np.lexsort((local[once], elem[once]))
+    return elem[once][order].astype(np.int32), local[once][order].astype(np.int32)

@@ -7,7 +7,7 @@ warm-up, `--reps` repetitions (all listed).  One JSON line per case.
 
     python tools/elmat_time.py [--hex 128,256] [--elasticity 64] [--q2-hex 64,128] [--q2-elasticity 32,64] [--quad9 2048]
                                [--reps 3] [--host-reps 3] [--hbm-gbs 8000] [--fp64-gops 39300] [--no-host] [--no-mass]
-                               [--rhs 256]
+                               [--rhs 256] [--boundary]
 
 Beside every stiffness case, on the same mesh and in the same run (--no-mass: not): the mass matrices of the same layout
 (saamge_amd_element_mass; vdim 1 beside diffusion, dim beside elasticity), written (`<case>:mass`) and added to the stiffness
@@ -15,6 +15,11 @@ matrices (`<case>:mass_accumulate`; its bound reads the target once and writes i
 (`<case>:loads`; saamge_amd_element_loads), each with `stiffness_fraction_of_bound`, the yardstick.  --rhs n: the right-hand
 side of Q1 diffusion on n^3 hexes assembled from its element vectors (saamge_amd_operator_assemble_rhs) against reading them
 once.
+
+--boundary: only the boundary forms (saamge_amd_boundary_mass / _loads) on ALL boundary faces of Q1 hexes 128^3 and 256^3, Q2
+hexes 64^3 (vdim 1 and 3) and 9-node quadrilaterals 2048^2, same protocol (device inputs, jittered, host clock round the whole
+call, one warm-up, --reps repetitions); the yardstick of a case is `element_mass` with `add_to` on the same mesh in the same run
+(`mass_accumulate_ms`): the boundary call touches about 6 / n of the elements and should land below it.
 
 The vertices are jittered by 0.2 mesh widths, so no two elements are alike.  A case that does not fit is reported as skipped
 with the error.
@@ -53,6 +58,7 @@ def main():
     ap.add_argument("--no-host", action="store_true")
     ap.add_argument("--no-mass", action="store_true")
     ap.add_argument("--rhs", default="")
+    ap.add_argument("--boundary", action="store_true")
     a = ap.parse_args()
     ints = lambda v: [int(x) for x in v.split(",") if x]
     stream = lambda: torch.cuda.current_stream().cuda_stream
@@ -111,6 +117,50 @@ def main():
         node = dim * dot * (1 if kind else 2)
         pair = dot + 1 + 3 * dim * dim + 3 * dim * dim + dim if kind else dot + 2
         return nq * (point + nd * node + pairs * pair)
+
+    def grid_boundary(n, dim):
+        """(face_elem, face_local) of all boundary faces of the n^dim grid (element (ez * n + ey) * n + ex), on the device; the
+        local faces of elmat_model.FACE_NODES: hexahedron z = 0, y = 0, x = 1, y = 1, x = 0, z = 1; quadrilateral y = 0, x = 1,
+        y = 1, x = 0"""
+        idx = torch.arange(n ** dim, device=dev, dtype=torch.int32)
+        ex, ey, ez = idx % n, (idx // n) % n, idx // (n * n)
+        sides = [ez == 0, ey == 0, ex == n - 1, ey == n - 1, ex == 0, ez == n - 1] if dim == 3 else \
+                [ey == 0, ex == n - 1, ey == n - 1, ex == 0]
+        fe = torch.cat([idx[m] for m in sides])
+        fl = torch.cat([torch.full((int(m.sum()),), k, device=dev, dtype=torch.int32) for k, m in enumerate(sides)])
+        return fe.contiguous(), fl.contiguous()
+
+    if a.boundary:
+        for name, n, dim, nd, vdim in [("hex128", 128, 3, 8, 1), ("hex256", 256, 3, 8, 1), ("q2_hex64", 64, 3, 27, 1),
+                                       ("q2_hex64_vdim3", 64, 3, 27, 3), ("quad9_2048", 2048, 2, 9, 1)]:
+            try:
+                X, e2v, g = mesh(n) if nd == 8 else mesh_q2(n, dim)
+                NE, size = n ** dim, nd * vdim
+                fe, fl = grid_boundary(n, dim)
+                NF = int(fe.numel())
+                alpha = 0.5 + 1.5 * torch.rand(NF, generator=g, device=dev, dtype=torch.float64)
+                sigma = 0.5 + 1.5 * torch.rand(NE, generator=g, device=dev, dtype=torch.float64)
+                gn = torch.rand((X.shape[0], vdim), generator=g, device=dev, dtype=torch.float64)
+                out = torch.zeros(NE * size * size, dtype=torch.float64, device=dev)
+                vec = torch.zeros(NE * size, dtype=torch.float64, device=dev)
+                info = capi.boundary_mass(X, e2v, fe, fl, alpha, vdim=vdim, sizes_only=True)
+                rec = {"case": "boundary:" + name, "elements": NE, "faces": NF, "vdim": vdim, "elements_touched": info[7],
+                       "mass_additions": info[5]}
+                for tag, call in [("mass_accumulate_ms", lambda: capi.element_mass(X, e2v, sigma, vdim=vdim, add_to=out, stream=stream())),
+                                  ("boundary_mass_ms", lambda: capi.boundary_mass(X, e2v, fe, fl, alpha, vdim=vdim, add_to=out, stream=stream())),
+                                  ("boundary_loads_ms", lambda: capi.boundary_loads(X, e2v, fe, fl, gn, vdim=vdim, coef=alpha, add_to=vec,
+                                                                                    stream=stream()))]:
+                    timed(call)                    # warm-up
+                    rec[tag] = [round(timed(call)[0], 3) for _ in range(a.reps)]
+                rec["boundary_mass_over_yardstick"] = round(min(rec["boundary_mass_ms"]) / min(rec["mass_accumulate_ms"]), 4)
+                rec["boundary_loads_over_yardstick"] = round(min(rec["boundary_loads_ms"]) / min(rec["mass_accumulate_ms"]), 4)
+                print(json.dumps(rec), flush=True)
+            except (RuntimeError, MemoryError) as e:
+                print(json.dumps({"case": "boundary:" + name, "skipped": str(e)[:200]}), flush=True)
+            X = e2v = out = vec = fe = fl = alpha = sigma = gn = None
+            torch.cuda.empty_cache()
+            capi.release_cached_memory()
+        return
 
     host_reps = a.reps if a.host_reps is None else a.host_reps
     cases = [("hex_diffusion%d" % n, n, 0, 3, 8) for n in ints(a.hex)] + \
