@@ -416,6 +416,12 @@ int saamge_amd_ae_order(int ND, int NE, int nde, const int *elem_ptr, const int 
  * coords holds ALL nodes (NV of them) and the lists hold 9 / 27 node ids; the geometry is isoparametric (the Jacobian runs over
  * all nodes, so an element may be curved; a straight-sided one has its extra nodes at the averages of its corners).  Rule: 3
  * Gauss points per axis, exact for both forms on parallelepipeds.  One list (elem_ptr) may hold elements of both orders.
+ * Order-2 simplices: (2, 6) P2 triangle, nodes = the vertices 0, 1, 2, then the midpoints of the edges (0,1), (1,2), (2,0); and
+ * (3, 10) P2 tetrahedron, nodes = the vertices 0 .. 3, then the midpoints of the edges (0,1), (0,2), (0,3), (1,2), (1,3), (2,3)
+ * (believed to be MFEM's H1 order-2 orders; not verified against MFEM, this table is the definition).  Isoparametric like the
+ * other order-2 types: coords holds all nodes, an element may be curved, a straight-sided one has its midside nodes at
+ * 0.5 * (a + b).  Shape functions on the barycentric coordinates L: vertex i L_i (2 L_i - 1), edge (i, j) 4 L_i L_j.  Rules: the
+ * 3-point degree-2 rule on the triangle, the 4-point degree-2 rule on the tetrahedron, exact for both forms on affine images.
  * kind 0 diffusion: ncoef = 1 (c I), dim (diagonal) or dim (dim + 1) / 2 (symmetric: xx, yy, zz, xy, yz, xz / xx, yy, xy), the
  * matrix nodes x nodes.  kind 1 elasticity (lambda div u div v + 2 mu eps(u):eps(v)): ncoef = 2 (lambda, mu), dof
  * dim * node + component, the matrix (dim nodes) x (dim nodes).
@@ -424,8 +430,8 @@ int saamge_amd_ae_order(int ND, int NE, int nde, const int *elem_ptr, const int 
  * dof_ptr_out (NE + 1) / elem_to_dof_out: the dof lists the matrices are indexed by (kind 0: the vertex lists;
  * kind 1: dim * vertex + component), may be NULL.  Any pointer host or device, each on its own.
  * info[0..4] = triangles, quadrilaterals, tetrahedra, wedges, hexahedra; [5] = doubles written; [6] = first element
- * with a non-positive Jacobian (-1: none); [7] = order-2 elements (9-node quadrilaterals, 27-node hexahedra; [0..4] count
- * the order-1 elements only).
+ * with a non-positive Jacobian (-1: none); [7] = order-2 elements (9-node quadrilaterals, 27-node hexahedra, 6-node triangles,
+ * 10-node tetrahedra; [0..4] count the order-1 elements only).
  * Refused (nonzero return, saamge_amd_last_error names the argument or the first element; elmat_out is then not to be relied
  * on): dim, kind or ncoef out of range, NULL coords / elem_to_vertex / coef, malformed offsets, a vertex id outside [0, NV), an
  * element that lists a vertex twice, a node count that is no type of the dimension, an element whose Jacobian determinant is
@@ -437,7 +443,10 @@ int saamge_amd_element_matrices(int NV, int dim, const double *coords, int NE, i
  * The zeroth-order forms on the types, node orders and isoparametric geometry of saamge_amd_element_matrices, so that the
  * right-hand side and sigma M + K never exist on the host either; saamge_amd/elmat_model.py (element_mass, element_loads)
  * defines every operation and the device gives the same bits.  The rule of a type is its rule above, except three points on the
- * triangle and four on the tetrahedron (exact for the P1 mass on affine simplices).  vdim 1: one dof per node; vdim = dim: dof
+ * triangle and four on the tetrahedron (exact for the P1 mass on affine simplices), and on the order-2 simplices a 6-point
+ * degree-4 rule (6-node triangle) and a 14-point degree-5 rule (10-node tetrahedron), positive weights, interior points, exact
+ * for the P2 mass on affine simplices -- so a curved element may be refused here at a point the stiffness rule does not have.
+ * info[0..4] and [7] as above ([7] counts all four order-2 types).  vdim 1: one dof per node; vdim = dim: dof
  * dim * node + component, the layout of elasticity.  coef: NE doubles, c of (c u, v).
  * saamge_amd_element_mass: elmat_inout in the packed layout above (element e: size_e x size_e at sum_{f<e} size_f^2, size_e =
  * vdim * nodes); the components do not couple (an entry between two components is + 0.0).  accumulate != 0: the matrices are
@@ -463,7 +472,10 @@ int saamge_amd_element_loads(int NV, int dim, const double *coords, int NE, int 
  * bits.  Face f is the local face face_local[f] of element face_elem[f]; local faces by element type, as the element's local
  * node ids: triangle (0,1) (1,2) (2,0); quadrilateral (0,1) (1,2) (2,3) (3,0); 9-node quadrilateral (0,4,1) (1,5,2) (2,6,3)
  * (3,7,0); tetrahedron (1,2,3) (0,3,2) (0,1,3) (0,2,1); wedge (0,2,1) (3,4,5) (0,1,4,3) (1,2,5,4) (2,0,3,5); hexahedron (3,2,1,0)
- * (0,1,5,4) (1,2,6,5) (2,3,7,6) (3,0,4,7) (4,5,6,7); 27-node hexahedron: the same six faces with their 9 nodes.  The call does
+ * (0,1,5,4) (1,2,6,5) (2,3,7,6) (3,0,4,7) (4,5,6,7); 27-node hexahedron: the same six faces with their 9 nodes; 6-node
+ * triangle: the 3-node segments (0,3,1) (1,4,2) (2,5,0); 10-node tetrahedron: the tetrahedron's four faces as 6-node triangles
+ * (three vertices, then the midpoints of (v0,v1), (v1,v2), (v2,v0)): (1,2,3,7,9,8) (0,3,2,6,9,5) (0,1,3,4,8,6) (0,2,1,5,7,4); a
+ * 6-node triangular face has the shape functions of the 6-node triangle and its 6-point rule.  The call does
  * not know what a boundary is: interior faces are allowed.  coef: NF doubles, c per face.  The faces of one element are added
  * in ascending local face index, whatever the order of the list; entries that no listed face touches keep their bits.
  * saamge_amd_boundary_mass: elmat_inout holds the matrices of saamge_amd_element_matrices / _mass of the same mesh and vdim;
@@ -471,7 +483,8 @@ int saamge_amd_element_loads(int NV, int dim, const double *coords, int NE, int 
  * saamge_amd_boundary_loads: g NV x vdim, the data at the nodes; coef NULL: 1; elvec_inout holds the vectors of
  * saamge_amd_element_loads.  Data that jumps across an edge: one call per side with its own g, the calls accumulate.
  * elmat_inout / elvec_inout NULL: the checks and info only.  Any pointer host or device, each on its own.  NF = 0: nothing.
- * info[0..4] = faces by type: 2-node segments, 3-node segments, triangles, 4-node quadrilaterals, 9-node quadrilaterals;
+ * info[0..4] = faces by type: 2-node segments, 3-node segments (whichever element type owns them), triangles (of 3 and of 6
+ * nodes), 4-node quadrilaterals, 9-node quadrilaterals;
  * [5] = additions made (a double that two faces touch counts twice); [6] = first refused face (-1: none); [7] = distinct
  * elements touched.
  * Refused, before anything touches the device: vdim not 1 or dim, NF < 0, NULL face lists, NULL coef for the mass, NULL g;

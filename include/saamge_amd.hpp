@@ -296,12 +296,14 @@ inline LevelOrderInfo level_order_info(const ml_data_t *h, int level) {
 
 // == element matrices computed on the device (saamge_amd_element_matrices) ==
 // From vertex coordinates (NV x dim), element -> vertex lists (elem_ptr == nullptr: nde vertices per element) and per-element
-// coefficients (NE x ncoef); kind 0 diffusion, 1 elasticity.  nde 9 in 2D / 27 in 3D: the order-2 quadrilateral / hexahedron
+// coefficients (NE x ncoef); kind 0 diffusion, 1 elasticity.  nde 9 in 2D / 27 in 3D: the order-2 quadrilateral / hexahedron;
+// nde 6 in 2D / 10 in 3D: the order-2 triangle / tetrahedron (vertices, then edge midpoints)
 // (coords then holds all nodes; node orders in saamge_amd.h).  The matrices are packed in element order as the setup entry
 // points and AssembledOperator take them.  Throws with saamge_amd_last_error on a refusal.
 struct ElementMatricesInfo {
     long long triangles, quadrilaterals, tetrahedra, wedges, hexahedra, doubles, first_bad_element;
-    long long order2;      // the order-2 elements (9-node quadrilaterals, 27-node hexahedra); the five counts above are order 1
+    long long order2;      // the order-2 elements (9-node quadrilaterals, 27-node hexahedra, 6-node triangles, 10-node
+                           // tetrahedra); the five counts above are order 1
 };
 // Into the caller's arrays, each a host or a device pointer (elmat_out == nullptr: the sizes only; the dof lists may be nullptr).
 inline ElementMatricesInfo element_matrices_into(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
@@ -369,7 +371,8 @@ inline ElementMatricesInfo element_loads_into(int NV, int dim, const double *coo
 // == boundary forms computed on the device (saamge_amd_boundary_mass, saamge_amd_boundary_loads) ==
 // The face mass / face loads of the NF listed faces (element face_elem[f], local face face_local[f]; local faces in
 // saamge_amd.h) added into the caller's packed matrices / vectors, each array a host or a device pointer; nullptr for
-// elmat_inout / elvec_inout: the checks and the counts only.
+// elmat_inout / elvec_inout: the checks and the counts only.  segments3 counts the 3-node segments of 9-node quadrilaterals and of
+// 6-node triangles, triangles the triangular faces of 3 nodes (tetrahedron, wedge) and of 6 nodes (10-node tetrahedron).
 struct BoundaryFormsInfo {
     long long segments2, segments3, triangles, quadrilaterals4, quadrilaterals9, additions, first_bad_face, elements;
 };

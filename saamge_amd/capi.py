@@ -764,7 +764,8 @@ def _element_arrays(coords, elem_to_vertex, coef, elem_ptr):
 
 def element_matrices_info(coords, elem_to_vertex, kind, coef, elem_ptr=None, stream=0):
     """The sizes-only call (elmat_out = NULL): info = [triangles, quadrilaterals, tetrahedra, wedges, hexahedra (the order-1
-    elements), doubles the matrices take, -1, order-2 elements (9-node quadrilaterals, 27-node hexahedra)].  Nothing is
+    elements), doubles the matrices take, -1, order-2 elements (9-node quadrilaterals, 27-node hexahedra, 6-node triangles,
+    10-node tetrahedra)].  Nothing is
     written; the mesh and the Jacobians are checked all the same."""
     coords, e2v, coef, ep = _element_arrays(coords, elem_to_vertex, coef, elem_ptr)
     return _element_matrices_call(coords, e2v, kind, coef, ep, stream, None, None, None)
@@ -774,7 +775,9 @@ def element_matrices(coords, elem_to_vertex, kind, coef, elem_ptr=None, device=F
     """saamge_amd_element_matrices: the element matrices of a mesh from its vertex coordinates (NV x dim), element -> vertex
     lists ((NE, nodes), or flat with elem_ptr) and per-element coefficients ((NE,) or (NE, ncoef)); kind 0 diffusion, 1
     elasticity.  Lists of 9 (2D) / 27 (3D) nodes are the order-2 quadrilateral (MFEM's H1 order: vertices, edge midpoints,
-    centre) / hexahedron (lexicographic); coords then holds all nodes, and the elements may be curved (elmat_model.py).
+    centre) / hexahedron (lexicographic), lists of 6 (2D) / 10 (3D) nodes the order-2 triangle / tetrahedron (the vertices, then
+    the edge midpoints in the order of elmat_model.P2_EDGES; problems.p2_simplex_nodes makes such lists from a vertex mesh);
+    coords then holds all nodes, and the elements may be curved (elmat_model.py).
     Inputs: numpy arrays or device tensors, each on its own.  Returns elmat -- (NE, size, size), or packed in
     element order with elem_ptr -- as a numpy array, or with device=True as a torch tensor on the GPU whose data_ptr goes to
     `Operator` and `Hierarchy.from_operator` unchanged; out: an array / tensor of that many doubles to write into instead of
@@ -840,7 +843,8 @@ def element_mass(coords, elem_to_vertex, coef, vdim=1, elem_ptr=None, add_to=Non
     layout (the output of `element_matrices`); the mass matrices are added to it IN PLACE and it is returned -- K + sigma M with
     sigma in coef.  Otherwise as `element_matrices`: inputs numpy arrays or device tensors, each on its own; device=True: a
     torch tensor on the GPU; out: doubles to write into.  sizes_only: info (8 integers), nothing written.  A refusal raises
-    RuntimeError with `.info`."""
+    RuntimeError with `.info`.  The order-2 simplices have mass rules of their own (6 / 14 points): a curved element can be
+    refused here that `element_matrices` accepts."""
     coords, e2v, coef, ep = _element_arrays(coords, elem_to_vertex, coef, elem_ptr)
     vdim = int(vdim)
     NV, dim, NE, nde, doubles = _mass_sizes(coords, e2v, ep, vdim, True)
@@ -902,7 +906,8 @@ def boundary_mass(coords, elem_to_vertex, face_elem, face_local, coef, vdim=1, e
     (elmat_model.FACE_NODES) of element face_elem[f], c = coef (NF,) -- added IN PLACE to add_to, an array / tensor in the layout
     of `element_matrices` / `element_mass` with the same vdim, which is returned: the Robin term.  add_to None: the face terms
     alone, in new zero matrices (device=True: a torch tensor on the GPU).  Inputs numpy arrays or device tensors, each on its own.  sizes_only: info (8 integers: faces by type [0..4], additions, -1, elements touched), nothing
-    written.  A refusal raises RuntimeError with `.info` (info[6]: the first refused face)."""
+    written.  A refusal raises RuntimeError with `.info` (info[6]: the first refused face).  Faces by type: 2-node segments,
+    3-node segments, triangles (of 3 and of 6 nodes), 4-node and 9-node quadrilaterals (elmat_model.face_info_index)."""
     coords, e2v, _, ep = _element_arrays(coords, elem_to_vertex, None, elem_ptr)
     fe, fl, coef, NF = _face_arrays(face_elem, face_local, coef)
     vdim = int(vdim)

@@ -14,10 +14,11 @@
 // element with a non-positive determinant.
 //
 // The order-2 quadrilateral (9 nodes) and hexahedron (27 nodes) have their own kernel, em2_kernel, with its own decomposition
-// (27 divides no wavefront and a node's row block of the hex is 243 accumulators): lanes own ENTRIES, see there.
+// (27 divides no wavefront and a node's row block of the hex is 243 accumulators): lanes own ENTRIES, see there.  The order-2
+// triangle (6 nodes) and tetrahedron (10 nodes) are two more node counts of the same kernel, with the simplex rules.
 //
 // The zeroth-order forms -- mass matrices, with or without a target they are added to, and load vectors of a nodal source --
-// have a kernel family of their own for all seven types (mass_kernel, load_kernel) in em2_kernel's phase structure.
+// have a kernel family of their own for all nine types (mass_kernel, load_kernel) in em2_kernel's phase structure.
 //
 // The boundary forms -- the mass and the loads of a list of faces, added into the owning elements' matrices and vectors -- have
 // kernels templated on the face type (bdr_mass_kernel, bdr_load_kernel) and run one pass per local face index.
@@ -55,13 +56,14 @@ template <> struct EmType<3, 4> { static constexpr int NQ = 1; static constexpr 
 template <> struct EmType<3, 6> { static constexpr int NQ = 6; static constexpr double W = 0.08333333333333333; };
 template <> struct EmType<3, 8> { static constexpr int NQ = 8; static constexpr double W = 0.125; };
 
-// types 0 .. 4: order 1 (info[0 .. 4]); 5, 6: the order-2 quadrilateral and hexahedron (info[7] counts both)
-constexpr int EM_TYPES = 7;
+// types 0 .. 4: order 1 (info[0 .. 4]); 5, 6: the order-2 quadrilateral and hexahedron; 7, 8: the order-2 triangle (6 nodes)
+// and tetrahedron (10 nodes); info[7] counts all four
+constexpr int EM_TYPES = 9;
 constexpr int em_type_index(int dim, int nd) {
-    return dim == 2 ? (nd == 3 ? 0 : (nd == 4 ? 1 : (nd == 9 ? 5 : -1)))
-                    : (nd == 4 ? 2 : (nd == 6 ? 3 : (nd == 8 ? 4 : (nd == 27 ? 6 : -1))));
+    return dim == 2 ? (nd == 3 ? 0 : (nd == 4 ? 1 : (nd == 9 ? 5 : (nd == 6 ? 7 : -1))))
+                    : (nd == 4 ? 2 : (nd == 6 ? 3 : (nd == 8 ? 4 : (nd == 27 ? 6 : (nd == 10 ? 8 : -1)))));
 }
-constexpr int EM_TYPE_ND[EM_TYPES] = {3, 4, 4, 6, 8, 9, 27};
+constexpr int EM_TYPE_ND[EM_TYPES] = {3, 4, 4, 6, 8, 9, 27, 6, 10};
 
 constexpr double em_f(int l, double p) { return l ? p : 1.0 - p; }
 constexpr double em_df(int l) { return l ? 1.0 : -1.0; }
@@ -313,7 +315,7 @@ __global__ __launch_bounds__(em_block(DIM, ND, KIND)) void em_kernel(int count, 
     }
 }
 
-// ---- order 2: the 9-node quadrilateral and the 27-node hexahedron ----------------------------------------------------------
+// ---- order 2: the 9-node quadrilateral, the 27-node hexahedron, the 6-node triangle and the 10-node tetrahedron ------------
 // The literals and the expressions of elmat_model.py (GAUSS3, GAUSS3_W, _n2, _d2, Q2_QUAD_LOC; the hex is lexicographic).
 constexpr double EM2_GAUSS[3] = {0.11270166537925831, 0.5, 0.8872983346207417};
 constexpr double EM2_W[3] = {0.2777777777777778, 0.4444444444444444, 0.2777777777777778};
@@ -324,47 +326,105 @@ constexpr double em2_n(int l, double p) {
 constexpr double em2_d(int l, double p) { return l == 0 ? 4.0 * p - 3.0 : (l == 1 ? 4.0 - 8.0 * p : 4.0 * p - 1.0); }
 constexpr int em2_nodes(int dim) { return dim == 2 ? 9 : 27; }
 
-// the rule's table, folded at compile time: the reference gradient of node a at point q (node-major, so that lanes that differ
-// in the point read neighbouring doubles) and the weight of point q
+// The order-2 simplices (elmat_model._p2_simplex): the vertices, then the midpoints of the edges EM_P2_TRI_EDGES / EM_P2_TET_EDGES.  N and dN at the
+// reference point pt from the barycentric coordinates L and their constant gradients EM_TRI_D / EM_TET_D.
+constexpr int p2s_nodes(int dim) { return dim == 2 ? 6 : 10; }
+constexpr bool p2s_type(int dim, int nd) { return nd == p2s_nodes(dim); }
+constexpr int EM_P2_TRI_EDGES[3][2] = {{0, 1}, {1, 2}, {2, 0}};
+constexpr int EM_P2_TET_EDGES[6][2] = {{0, 1}, {0, 2}, {0, 3}, {1, 2}, {1, 3}, {2, 3}};
 template <int DIM>
-struct Em2Table {
-    double dN[em2_nodes(DIM)][em2_nodes(DIM)][DIM];
-    double w[em2_nodes(DIM)];
+struct P2Simplex {
+    double N[p2s_nodes(DIM)];
+    double dN[p2s_nodes(DIM)][DIM];
 };
 template <int DIM>
-constexpr Em2Table<DIM> em2_table() {
-    Em2Table<DIM> t{};
-    for (int q = 0; q < em2_nodes(DIM); ++q) {
-        const int qx = q % 3, qy = (q / 3) % 3, qz = q / 9;
-        const double px = EM2_GAUSS[qx], py = EM2_GAUSS[qy], pz = EM2_GAUSS[qz];
-        t.w[q] = DIM == 2 ? EM2_W[qx] * EM2_W[qy] : (EM2_W[qx] * EM2_W[qy]) * EM2_W[qz];
-        for (int a = 0; a < em2_nodes(DIM); ++a) {
-            if (DIM == 2) {
-                const int ix = EM2_QUAD_LOC[a][0], iy = EM2_QUAD_LOC[a][1];
-                t.dN[a][q][0] = em2_d(ix, px) * em2_n(iy, py);
-                t.dN[a][q][1] = em2_n(ix, px) * em2_d(iy, py);
-            } else {
-                const int ix = a % 3, iy = (a / 3) % 3, iz = a / 9;
-                t.dN[a][q][0] = em2_d(ix, px) * (em2_n(iy, py) * em2_n(iz, pz));
-                t.dN[a][q][1] = em2_d(iy, py) * (em2_n(ix, px) * em2_n(iz, pz));
-                t.dN[a][q][DIM - 1] = em2_d(iz, pz) * (em2_n(ix, px) * em2_n(iy, py));
+constexpr P2Simplex<DIM> p2_simplex(const double *pt) {
+    P2Simplex<DIM> r{};
+    double L[4] = {0.0, 0.0, 0.0, 0.0}, D[4][3] = {};
+    if (DIM == 2) L[0] = (1.0 - pt[0]) - pt[1];
+    else L[0] = ((1.0 - pt[0]) - pt[1]) - pt[DIM - 1];
+    for (int k = 0; k < DIM; ++k) L[1 + k] = pt[k];
+    for (int i = 0; i <= DIM; ++i)
+        for (int k = 0; k < DIM; ++k) D[i][k] = DIM == 2 ? EM_TRI_D[i % 3][k % 2] : EM_TET_D[i][k];
+    for (int i = 0; i <= DIM; ++i) {
+        r.N[i] = L[i] * (2.0 * L[i] - 1.0);
+        for (int k = 0; k < DIM; ++k) r.dN[i][k] = (4.0 * L[i] - 1.0) * D[i][k];
+    }
+    for (int e = 0; e < p2s_nodes(DIM) - DIM - 1; ++e) {
+        const int i = DIM == 2 ? EM_P2_TRI_EDGES[e % 3][0] : EM_P2_TET_EDGES[e][0];
+        const int j = DIM == 2 ? EM_P2_TRI_EDGES[e % 3][1] : EM_P2_TET_EDGES[e][1];
+        r.N[DIM + 1 + e] = (4.0 * L[i]) * L[j];
+        for (int k = 0; k < DIM; ++k) r.dN[DIM + 1 + e][k] = (4.0 * L[i]) * D[j][k] + (4.0 * L[j]) * D[i][k];
+    }
+    return r;
+}
+constexpr double EM_TET_A = 0.1381966011250105, EM_TET_B = 0.5854101966249685;
+// point q of the stiffness rules of the order-2 simplices: the order-1 mass rules (EM_WEDGE_TRI; EM_TET_A / EM_TET_B)
+struct EmPoint {
+    double x[3];
+};
+constexpr EmPoint p2s_point(int dim, int q) {
+    if (dim == 2) return EmPoint{{EM_WEDGE_TRI[q % 3][0], EM_WEDGE_TRI[q % 3][1], 0.0}};
+    return EmPoint{{q == 1 ? EM_TET_B : EM_TET_A, q == 2 ? EM_TET_B : EM_TET_A, q == 3 ? EM_TET_B : EM_TET_A}};
+}
+
+// the rule's table, folded at compile time: the reference gradient of node a at point q (node-major, so that lanes that differ
+// in the point read neighbouring doubles) and the weight of point q.  The tensor-product types have as many points as nodes;
+// the triangle has 3 and the tetrahedron 4.
+constexpr int em2_points(int dim, int nd) { return p2s_type(dim, nd) ? dim + 1 : nd; }
+template <int DIM, int ND>
+struct Em2Table {
+    double dN[ND][em2_points(DIM, ND)][DIM];
+    double w[em2_points(DIM, ND)];
+};
+template <int DIM, int ND>
+constexpr Em2Table<DIM, ND> em2_table() {
+    Em2Table<DIM, ND> t{};
+    if constexpr (p2s_type(DIM, ND)) {
+        for (int q = 0; q <= DIM; ++q) {
+            const EmPoint pt = p2s_point(DIM, q);
+            const P2Simplex<DIM> f = p2_simplex<DIM>(pt.x);
+            t.w[q] = DIM == 2 ? 0.16666666666666666 : 0.041666666666666664;
+            for (int a = 0; a < ND; ++a)
+                for (int j = 0; j < DIM; ++j) t.dN[a][q][j] = f.dN[a][j];
+        }
+    } else {
+        for (int q = 0; q < em2_nodes(DIM); ++q) {
+            const int qx = q % 3, qy = (q / 3) % 3, qz = q / 9;
+            const double px = EM2_GAUSS[qx], py = EM2_GAUSS[qy], pz = EM2_GAUSS[qz];
+            t.w[q] = DIM == 2 ? EM2_W[qx] * EM2_W[qy] : (EM2_W[qx] * EM2_W[qy]) * EM2_W[qz];
+            for (int a = 0; a < em2_nodes(DIM); ++a) {
+                if (DIM == 2) {
+                    const int ix = EM2_QUAD_LOC[a][0], iy = EM2_QUAD_LOC[a][1];
+                    t.dN[a][q][0] = em2_d(ix, px) * em2_n(iy, py);
+                    t.dN[a][q][1] = em2_n(ix, px) * em2_d(iy, py);
+                } else {
+                    const int ix = a % 3, iy = (a / 3) % 3, iz = a / 9;
+                    t.dN[a][q][0] = em2_d(ix, px) * (em2_n(iy, py) * em2_n(iz, pz));
+                    t.dN[a][q][1] = em2_d(iy, py) * (em2_n(ix, px) * em2_n(iz, pz));
+                    t.dN[a][q][DIM - 1] = em2_d(iz, pz) * (em2_n(ix, px) * em2_n(iy, py));
+                }
             }
         }
     }
     return t;
 }
-template <int DIM>
-__device__ const Em2Table<DIM> EM2_TABLE = em2_table<DIM>();
+template <int DIM, int ND>
+__device__ const Em2Table<DIM, ND> EM2_TABLE = em2_table<DIM, ND>();
 
 // BLOCK threads, EPB elements per workgroup, BS x BS node pairs per lane in the entry phase, QC points per pass.
 // The hex of elasticity: one element (its tile is 52 KB), 378 node pairs on 384 lanes.  The hex of diffusion: lanes own
 // 3 x 3 node pairs (the flux of 3 nodes and the gradient of 3 nodes from LDS feed 9 entries: one pair per lane would wait
 // for LDS), 45 lanes per element; the gradients of 3 points at a time keep four elements within 27 KB.
-template <int DIM, int KIND> struct Em2Cfg;
-template <> struct Em2Cfg<2, 0> { static constexpr int BLOCK = 256, EPB = 5, BS = 1, QC = 9; };
-template <> struct Em2Cfg<2, 1> { static constexpr int BLOCK = 256, EPB = 5, BS = 1, QC = 9; };
-template <> struct Em2Cfg<3, 0> { static constexpr int BLOCK = 192, EPB = 4, BS = 3, QC = 3; };
-template <> struct Em2Cfg<3, 1> { static constexpr int BLOCK = 384, EPB = 1, BS = 1, QC = 27; };
+// The simplices are small: 21 / 55 node pairs, 3 / 4 points in one pass; 12 triangles (252 lanes, the tile of elasticity
+// 13.8 KB) and 4 tetrahedra (220 lanes, 28.8 KB) per workgroup of 256 keep five or more workgroups on a compute unit.
+template <int DIM, int ND, int KIND> struct Em2Cfg;
+template <> struct Em2Cfg<2, 9, 0> { static constexpr int BLOCK = 256, EPB = 5, BS = 1, QC = 9; };
+template <> struct Em2Cfg<2, 9, 1> { static constexpr int BLOCK = 256, EPB = 5, BS = 1, QC = 9; };
+template <> struct Em2Cfg<3, 27, 0> { static constexpr int BLOCK = 192, EPB = 4, BS = 3, QC = 3; };
+template <> struct Em2Cfg<3, 27, 1> { static constexpr int BLOCK = 384, EPB = 1, BS = 1, QC = 27; };
+template <int KIND> struct Em2Cfg<2, 6, KIND> { static constexpr int BLOCK = 256, EPB = 12, BS = 1, QC = 3; };
+template <int KIND> struct Em2Cfg<3, 10, KIND> { static constexpr int BLOCK = 256, EPB = 4, BS = 1, QC = 4; };
 
 // list, eI, moff, out: as in em_kernel.  Phases, a barrier between each:
 //   stage   the nodes' coordinates and the coefficients of the workgroup's elements into LDS
@@ -376,16 +436,16 @@ template <> struct Em2Cfg<3, 1> { static constexpr int BLOCK = 384, EPB = 1, BS 
 //           order, that adds the point's term to the lane's accumulators -- the whole sum of an entry lives in one lane, so
 //           the bits are the model's, and no entry is computed twice
 //   tile    the entries and their mirror images to an LDS tile (over the dead gradients), written out as consecutive doubles
-template <int DIM, int KIND>
-__global__ __launch_bounds__((Em2Cfg<DIM, KIND>::BLOCK)) void em2_kernel(int count, const int *__restrict__ list,
-                                                                       const int *__restrict__ eI, const int *__restrict__ eJ,
-                                                                       const roff_t *__restrict__ moff,
-                                                                       const double *__restrict__ coords,
-                                                                       const double *__restrict__ coef, int ncoef,
-                                                                       double *__restrict__ out, int *__restrict__ bad) {
-    typedef Em2Cfg<DIM, KIND> Cfg;
+template <int DIM, int ND, int KIND>
+__global__ __launch_bounds__((Em2Cfg<DIM, ND, KIND>::BLOCK)) void em2_kernel(int count, const int *__restrict__ list,
+                                                                           const int *__restrict__ eI, const int *__restrict__ eJ,
+                                                                           const roff_t *__restrict__ moff,
+                                                                           const double *__restrict__ coords,
+                                                                           const double *__restrict__ coef, int ncoef,
+                                                                           double *__restrict__ out, int *__restrict__ bad) {
+    typedef Em2Cfg<DIM, ND, KIND> Cfg;
     constexpr int BLOCK = Cfg::BLOCK, EPB = Cfg::EPB, BS = Cfg::BS, QC = Cfg::QC;
-    constexpr int ND = em2_nodes(DIM), NQ = ND, COMP = KIND ? DIM : 1, S = ND * COMP, SS = S * S;
+    constexpr int NQ = em2_points(DIM, ND), COMP = KIND ? DIM : 1, S = ND * COMP, SS = S * S;
     constexpr int NB = ND / BS, NBP = NB * (NB + 1) / 2;      // blocks of nodes, pairs A <= B of them
     constexpr int DD = DIM * DIM, PW = DD + 1;                // a point keeps its cofactors and s
     constexpr int GW = KIND ? DIM : 2 * DIM;                  // a node keeps G_a, and F_a for diffusion
@@ -398,7 +458,7 @@ __global__ __launch_bounds__((Em2Cfg<DIM, KIND>::BLOCK)) void em2_kernel(int cou
     __shared__ roff_t obase[EPB];
     __shared__ int sE[EPB];                                   // the element of a slot, -1: none
     double *const sP = work, *const sG = work + NP, *const sJ = sG, *const tile = work;
-    const Em2Table<DIM> &T = EM2_TABLE<DIM>;
+    const Em2Table<DIM, ND> &T = EM2_TABLE<DIM, ND>;
     const int tid = threadIdx.x;
     // ---- stage
     for (int idx = tid; idx < EPB * ND; idx += BLOCK) {
@@ -610,9 +670,31 @@ __global__ __launch_bounds__((Em2Cfg<DIM, KIND>::BLOCK)) void em2_kernel(int cou
 
 // ---- mass matrices and load vectors ------------------------------------------------------------------------------------------
 // elmat_model.py's element_mass / element_loads.  The rule of a type is its stiffness rule, except for the simplices: three
-// points (EM_WEDGE_TRI, weight 1/6) on the triangle and four (EM_TET_A / EM_TET_B, weight 1/24) on the tetrahedron.
-constexpr double EM_TET_A = 0.1381966011250105, EM_TET_B = 0.5854101966249685;
-constexpr int mass_points(int dim, int nd) { return nd == 9 || nd == 27 ? nd : (dim == 2 ? (nd == 3 ? 3 : 4) : (nd == 4 ? 4 : nd)); }
+// points (EM_WEDGE_TRI, weight 1/6) on the triangle and four (EM_TET_A / EM_TET_B, weight 1/24) on the tetrahedron.  The order-2
+// simplices: 6 points (degree 4) on the triangle, 14 (degree 5) on the tetrahedron -- elmat_model's P2_TRI_POINTS / P2_TET_POINTS.
+constexpr int mass_points(int dim, int nd) {
+    return nd == 9 || nd == 27 ? nd : (dim == 2 ? (nd == 3 ? 3 : (nd == 6 ? 6 : 4)) : (nd == 4 ? 4 : (nd == 10 ? 14 : nd)));
+}
+constexpr double EM_P2_TRI_A[2] = {0.44594849091596483, 0.09157621350977073};
+constexpr double EM_P2_TRI_W[2] = {0.11169079483900572, 0.054975871827660935};
+constexpr double EM_P2_TET_A[2] = {0.3108859192633006, 0.09273525031089122};
+constexpr double EM_P2_TET_W[3] = {0.018781320953002643, 0.012248840519393659, 0.007091003462846911};
+constexpr double EM_P2_TET_EDGE_A = 0.04550370412564965;
+// point q of the mass rule of an order-2 simplex and its weight
+constexpr EmPoint p2s_mass_point(int dim, int q) {
+    if (dim == 2) {
+        const double a = EM_P2_TRI_A[q / 3], b = 1.0 - 2.0 * a;
+        return EmPoint{{q % 3 == 1 ? b : a, q % 3 == 2 ? b : a, 0.0}};
+    }
+    if (q < 8) {
+        const double a = EM_P2_TET_A[q / 4], b = 1.0 - 3.0 * a;
+        return EmPoint{{q % 4 == 1 ? b : a, q % 4 == 2 ? b : a, q % 4 == 3 ? b : a}};
+    }
+    const double a = EM_P2_TET_EDGE_A, b = 0.5 - a;
+    const int i = EM_P2_TET_EDGES[q - 8][0], j = EM_P2_TET_EDGES[q - 8][1];      // barycentrics i and j are b, the point (L1, L2, L3)
+    return EmPoint{{i == 1 || j == 1 ? b : a, i == 2 || j == 2 ? b : a, i == 3 || j == 3 ? b : a}};
+}
+constexpr double p2s_mass_weight(int dim, int q) { return dim == 2 ? EM_P2_TRI_W[q / 3] : EM_P2_TET_W[q < 8 ? q / 4 : 2]; }
 
 // the rule's table, folded at compile time: reference gradients and shape values of node a at point q (dN node-major as in
 // Em2Table, N point-major: the entry phase reads N of neighbouring nodes at one point) and the weight of point q
@@ -627,8 +709,18 @@ template <int DIM, int ND>
 constexpr MassTable<DIM, ND> mass_table() {
     MassTable<DIM, ND> t{};
     constexpr int NQ = MassTable<DIM, ND>::NQ;
-    if constexpr (ND == em2_nodes(DIM)) {
-        const Em2Table<DIM> g = em2_table<DIM>();
+    if constexpr (p2s_type(DIM, ND)) {
+        for (int q = 0; q < NQ; ++q) {
+            const EmPoint pt = p2s_mass_point(DIM, q);
+            const P2Simplex<DIM> f = p2_simplex<DIM>(pt.x);
+            t.w[q] = p2s_mass_weight(DIM, q);
+            for (int a = 0; a < ND; ++a) {
+                t.N[q][a] = f.N[a];
+                for (int j = 0; j < DIM; ++j) t.dN[a][q][j] = f.dN[a][j];
+            }
+        }
+    } else if constexpr (ND == em2_nodes(DIM)) {
+        const Em2Table<DIM, ND> g = em2_table<DIM, ND>();
         for (int q = 0; q < NQ; ++q) {
             const double px = EM2_GAUSS[q % 3], py = EM2_GAUSS[(q / 3) % 3], pz = EM2_GAUSS[q / 9];
             t.w[q] = g.w[q];
@@ -698,9 +790,10 @@ __device__ const MassPairs<ND> MASS_PAIRS = mass_pairs<ND>();
 
 constexpr int MASS_BLOCK = 256;
 // elements per workgroup: a tile of at most 24 KB, at most 32 elements; the order-2 hexahedron of the vector form alone (52 KB)
+// the tetrahedron of order 2, scalar form: 16, its 14 Jacobians per element (not the tile) fill the work space
 constexpr int mass_epb(int nd, int vdim) {
     const int e = 24576 / (nd * vdim * nd * vdim * 8);
-    return e < 1 ? 1 : (e > 32 ? 32 : e);
+    return nd == 10 && vdim == 1 ? 16 : (e < 1 ? 1 : (e > 32 ? 32 : e));
 }
 constexpr int load_epb(int nd) { return nd >= 27 ? 8 : (nd >= 8 ? 16 : 32); }
 
@@ -935,21 +1028,23 @@ __global__ __launch_bounds__(MASS_BLOCK) void load_kernel(int count, const int *
 
 // ---- boundary forms: the face mass and the face loads -----------------------------------------------------------------------
 // elmat_model.py's boundary_mass / boundary_loads.  A face is (element, local face index); the face types are the 2-node and
-// 3-node segment (DIM 2) and the triangle, the 4-node and the 9-node quadrilateral (DIM 3).  The kernels are templated on the
+// 3-node segment (DIM 2) and the triangle, the 4-node and the 9-node quadrilateral and the 6-node triangle (DIM 3).  The kernels are templated on the
 // FACE type <DIM, FN>; the element type enters through the local node ids of the face (BdrFace, a kernel argument), the
 // element's node count nd and its offsets.  The host buckets the faces by (element type, local face) and runs one pass per local
 // face index in ascending order on the stream: within a pass an element occurs at most once, so the read-modify-write of its
 // entries needs no atomic and the model's order of additions holds by construction.
 constexpr int BDR_MAX_FACES = 6;
-// info[0 .. 4]: 2-node segments, 3-node segments, triangles, 4-node quadrilaterals, 9-node quadrilaterals
-constexpr int bdr_face_type(int dim, int fn) { return dim == 2 ? fn - 2 : (fn == 3 ? 2 : (fn == 4 ? 3 : 4)); }
+// info[0 .. 4]: 2-node segments, 3-node segments (of 9-node quadrilaterals and of 6-node triangles), triangles of 3 and of 6
+// nodes, 4-node quadrilaterals, 9-node quadrilaterals
+constexpr int bdr_face_type(int dim, int fn) { return dim == 2 ? fn - 2 : (fn == 3 || fn == 6 ? 2 : (fn == 4 ? 3 : 4)); }
 struct BdrFace {
     int node[9];
 };
 // elmat_model.FACE_NODES, by the type index of em_type_index
-constexpr int bdr_num_faces(int type) { return type == 0 ? 3 : (type == 3 ? 5 : (type == 4 || type == 6 ? 6 : 4)); }
+constexpr int bdr_num_faces(int type) { return type == 0 || type == 7 ? 3 : (type == 3 ? 5 : (type == 4 || type == 6 ? 6 : 4)); }
 constexpr int BDR_FACE_NODES[EM_TYPES][BDR_MAX_FACES] = {{2, 2, 2, 0, 0, 0}, {2, 2, 2, 2, 0, 0}, {3, 3, 3, 3, 0, 0}, {3, 3, 4, 4, 4, 0},
-                                                          {4, 4, 4, 4, 4, 4}, {3, 3, 3, 3, 0, 0}, {9, 9, 9, 9, 9, 9}};
+                                                          {4, 4, 4, 4, 4, 4}, {3, 3, 3, 3, 0, 0}, {9, 9, 9, 9, 9, 9}, {3, 3, 3, 0, 0, 0},
+                                                          {6, 6, 6, 6, 0, 0}};
 constexpr int BDR_HEX_FACES[6][4] = {{3, 2, 1, 0}, {0, 1, 5, 4}, {1, 2, 6, 5}, {2, 3, 7, 6}, {3, 0, 4, 7}, {4, 5, 6, 7}};
 constexpr BdrFace bdr_face(int type, int lf) {
     constexpr int TRI[3][2] = {{0, 1}, {1, 2}, {2, 0}};
@@ -957,6 +1052,8 @@ constexpr BdrFace bdr_face(int type, int lf) {
     constexpr int QUAD9[4][3] = {{0, 4, 1}, {1, 5, 2}, {2, 6, 3}, {3, 7, 0}};
     constexpr int TET[4][3] = {{1, 2, 3}, {0, 3, 2}, {0, 1, 3}, {0, 2, 1}};
     constexpr int WEDGE[5][4] = {{0, 2, 1, 0}, {3, 4, 5, 0}, {0, 1, 4, 3}, {1, 2, 5, 4}, {2, 0, 3, 5}};
+    constexpr int TRI6[3][3] = {{0, 3, 1}, {1, 4, 2}, {2, 5, 0}};
+    constexpr int TET10[4][6] = {{1, 2, 3, 7, 9, 8}, {0, 3, 2, 6, 9, 5}, {0, 1, 3, 4, 8, 6}, {0, 2, 1, 5, 7, 4}};
     BdrFace f{};
     const int fn = BDR_FACE_NODES[type][lf];
     for (int k = 0; k < fn; ++k) {
@@ -966,6 +1063,8 @@ constexpr BdrFace bdr_face(int type, int lf) {
         else if (type == 3) f.node[k] = WEDGE[lf][k];
         else if (type == 4) f.node[k] = BDR_HEX_FACES[lf][k];
         else if (type == 5) f.node[k] = QUAD9[lf][k];
+        else if (type == 7) f.node[k] = TRI6[lf][k];
+        else if (type == 8) f.node[k] = TET10[lf][k];
         else {      // the node at face position (u, v) of Q2_QUAD_LOC: P(c0) + u (P(c1) - P(c0)) / 2 + v (P(c3) - P(c0)) / 2
             const int *c = BDR_HEX_FACES[lf];
             int p[3] = {0, 0, 0};
@@ -1255,10 +1354,10 @@ void em_launch(const EmLaunch &L, int count, const int *list) {
                        L.moff, L.coords, L.coef, L.ncoef, L.out, L.bad);
     SA_HIP_CHECK(hipGetLastError());
 }
-template <int DIM, int KIND>
+template <int DIM, int ND, int KIND>
 void em2_launch(const EmLaunch &L, int count, const int *list) {
-    typedef Em2Cfg<DIM, KIND> Cfg;
-    hipLaunchKernelGGL((em2_kernel<DIM, KIND>), dim3((unsigned)div_up(count, Cfg::EPB)), dim3(Cfg::BLOCK), 0, L.s, count, list, L.eI,
+    typedef Em2Cfg<DIM, ND, KIND> Cfg;
+    hipLaunchKernelGGL((em2_kernel<DIM, ND, KIND>), dim3((unsigned)div_up(count, Cfg::EPB)), dim3(Cfg::BLOCK), 0, L.s, count, list, L.eI,
                        L.eJ, L.moff, L.coords, L.coef, L.ncoef, L.out, L.bad);
     SA_HIP_CHECK(hipGetLastError());
 }
@@ -1270,8 +1369,10 @@ void em_launch_type(const EmLaunch &L, int type, int count, const int *list) {
         case 2: em_launch<3, 4, KIND>(L, count, list); break;
         case 3: em_launch<3, 6, KIND>(L, count, list); break;
         case 4: em_launch<3, 8, KIND>(L, count, list); break;
-        case 5: em2_launch<2, KIND>(L, count, list); break;
-        default: em2_launch<3, KIND>(L, count, list); break;
+        case 5: em2_launch<2, 9, KIND>(L, count, list); break;
+        case 6: em2_launch<3, 27, KIND>(L, count, list); break;
+        case 7: em2_launch<2, 6, KIND>(L, count, list); break;
+        default: em2_launch<3, 10, KIND>(L, count, list); break;
     }
 }
 
@@ -1310,7 +1411,9 @@ void mass_launch_type(const EmLaunch &L, int type, int vdim, int accumulate, con
         SA_MASS_CASE(3, 3, 6)
         SA_MASS_CASE(4, 3, 8)
         SA_MASS_CASE(5, 2, 9)
-        default: SA_MASS_CASE(6, 3, 27)
+        SA_MASS_CASE(6, 3, 27)
+        SA_MASS_CASE(7, 2, 6)
+        default: SA_MASS_CASE(8, 3, 10)
     }
 #undef SA_MASS_CASE
 }
@@ -1343,7 +1446,7 @@ struct EmMesh {
     DBuf<roff_t> moff;
     const int *eI = nullptr, *eJ = nullptr;
     long nconn = 0;
-    int count[EM_TYPES] = {0, 0, 0, 0, 0, 0, 0};
+    int count[EM_TYPES] = {};
     int64_t doubles = 0;          // of the packed result: sum of size^2 (square) or of size
 };
 void em_mesh(hipStream_t s, const std::string &name, int NV, int dim, int NE, int nde, const int *elem_ptr,
@@ -1402,7 +1505,7 @@ void em_mesh(hipStream_t s, const std::string &name, int NV, int dim, int NE, in
     if (info) {
         for (int t = 0; t < 5; ++t) info[t] = M.count[t];
         info[5] = (long long)M.doubles;
-        info[7] = (long long)M.count[5] + M.count[6];      // the order-2 elements
+        info[7] = (long long)M.count[5] + M.count[6] + M.count[7] + M.count[8];      // the order-2 elements
     }
 }
 
@@ -1482,6 +1585,7 @@ void bdr_launch_face(const BdrLaunch &L, int dim, int vdim, int type, int lf, in
     SA_BDR_CASE(3, 3)
     SA_BDR_CASE(3, 4)
     SA_BDR_CASE(3, 9)
+    SA_BDR_CASE(3, 6)
 #undef SA_BDR_CASE
     SA_REQUIRE(false, "boundary forms: no such face type");
 }

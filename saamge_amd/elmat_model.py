@@ -9,7 +9,11 @@ are those of the scalar formulas).
                (3, 6) P1 x P1 wedge (node a * 3 + i: triangle vertex i on the bottom a = 0 / top a = 1 face), (3, 8) Q1
                hexahedron (vertex order HEX_LOC); order 2: (2, 9) Q2 quadrilateral (MFEM's H1 order: the vertices v00, v10,
                v11, v01, the edge midpoints bottom, right, top, left, the centre -- tensor positions Q2_QUAD_LOC) and (3, 27)
-               Q2 hexahedron (lexicographic: node (iz * 3 + iy) * 3 + ix).  Anything else is refused.
+               Q2 hexahedron (lexicographic: node (iz * 3 + iy) * 3 + ix); order-2 simplices: (2, 6) P2 triangle (the vertices
+               0, 1, 2, then the midpoints of the edges (0,1), (1,2), (2,0)) and (3, 10) P2 tetrahedron (the vertices 0 .. 3,
+               then the midpoints of the edges (0,1), (0,2), (0,3), (1,2), (1,3), (2,3)) -- P2_EDGES; believed to be MFEM's H1
+               order-2 orders, which could not be verified against MFEM itself: the table is the definition.  Anything else
+               is refused.
   geometry     isoparametric: the Jacobian below runs over ALL nodes of the element, so an order-2 element may be curved; a
                straight-sided one has its extra nodes at the multilinear image of its corners.
   rule         reference elements [0, 1]^dim and the unit simplex; triangle, tetrahedron: 1 point; quadrilateral, hexahedron:
@@ -20,6 +24,13 @@ are those of the scalar formulas).
                expressions of _n2 and _d2; the gradient of node (ix, iy, iz) is (d(ix, px) * (n(iy, py) * n(iz, pz)),
                d(iy, py) * (n(ix, px) * n(iz, pz)), d(iz, pz) * (n(ix, px) * n(iy, py))), in 2D (d(ix, px) * n(iy, py),
                n(ix, px) * d(iy, py)).
+  simplices    order 2 on the barycentric coordinates L_0 = ((1 - x) - y) - z (2D: (1 - x) - y), L_1 = x, L_2 = y, L_3 = z with
+               the constant gradients dL_i = TRI_D[i] / TET_D[i]: vertex node i: N = L_i * (2.0 * L_i - 1.0), gradient component
+               k (4.0 * L_i - 1.0) * dL_i[k]; edge node (i, j): N = (4.0 * L_i) * L_j, gradient component k
+               (4.0 * L_i) * dL_j[k] + (4.0 * L_j) * dL_i[k] (_p2_simplex).  Stiffness rules (degree 2): triangle the three
+               points of WEDGE_TRI, weight 1/6 each; tetrahedron TET_POINTS, weight 1/24 each.  Mass, loads and faces:
+               P2_TRI_POINTS (6 points, degree 4) and P2_TET_POINTS (14 points, degree 5) with the weights P2_TRI_W, P2_TET_W
+               (the reference measure included), further down.
   point        J[i][j] = sum over the nodes a, ascending, of x_a[i] * dN_a[j], the first product taken as it is; the cofactors
                C[i][j] and det from the explicit formulas of _cofactors; G_a[i] = sum_j dN_a[j] * C[i][j] (the physical
                gradient times det); s = weight / det (one division per point).
@@ -55,8 +66,16 @@ GAUSS3 = (0.11270166537925831, 0.5, 0.8872983346207417)  # 1/2 - sqrt(15)/10, 1/
 GAUSS3_W = (0.2777777777777778, 0.4444444444444444, 0.2777777777777778)      # 5/18, 4/9, 5/18
 Q2_QUAD_LOC = [(0, 0), (2, 0), (2, 2), (0, 2), (1, 0), (2, 1), (1, 2), (0, 1), (1, 1)]
 Q2_HEX_LOC = [(ix, iy, iz) for iz in range(3) for iy in range(3) for ix in range(3)]
-ORDER2 = ((2, 9), (3, 27))
+ORDER2 = ((2, 9), (3, 27), (2, 6), (3, 10))
 NPOINTS.update({(2, 9): 9, (3, 27): 27})
+# the order-2 simplices: edge (i, j) of midside node dim + 1 + k; their stiffness rules are the order-1 mass rules
+P2_EDGES = {2: ((0, 1), (1, 2), (2, 0)), 3: ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))}
+P2_SIMPLEX = ((2, 6), (3, 10))
+NPOINTS.update({(2, 6): 3, (3, 10): 4})
+WEIGHT.update({(2, 6): 0.16666666666666666, (3, 10): 0.041666666666666664})
+# every type by the device's internal index (csrc/elmat.hip em_type_index); TYPE_INDEX stays the order-1 part, info[0..4]
+ALL_TYPE_INDEX = dict(TYPE_INDEX)
+ALL_TYPE_INDEX.update({(2, 9): 5, (3, 27): 6, (2, 6): 7, (3, 10): 8})
 
 
 class ElementError(ValueError):
@@ -93,6 +112,18 @@ def _d2(l, p):
     return 4.0 * p - 1.0
 
 
+def _p2_simplex(dim, pt):
+    """(N[a], dN[a][k]) of the order-2 simplex at the reference point pt, as Python floats."""
+    L = [(1.0 - pt[0]) - pt[1], pt[0], pt[1]] if dim == 2 else [((1.0 - pt[0]) - pt[1]) - pt[2], pt[0], pt[1], pt[2]]
+    D = TRI_D if dim == 2 else TET_D
+    N = [L[i] * (2.0 * L[i] - 1.0) for i in range(dim + 1)]
+    dN = [tuple((4.0 * L[i] - 1.0) * D[i][k] for k in range(dim)) for i in range(dim + 1)]
+    for (i, j) in P2_EDGES[dim]:
+        N.append((4.0 * L[i]) * L[j])
+        dN.append(tuple((4.0 * L[i]) * D[j][k] + (4.0 * L[j]) * D[i][k] for k in range(dim)))
+    return N, dN
+
+
 def point_weight(dim, nd, q):
     """weight of point q of the type's rule"""
     if (dim, nd) == (2, 9):
@@ -111,6 +142,10 @@ def reference_gradients(dim, nd, q):
         px, py, pz = GAUSS3[q % 3], GAUSS3[(q // 3) % 3], GAUSS3[q // 9]
         return [(_d2(ix, px) * (_n2(iy, py) * _n2(iz, pz)), _d2(iy, py) * (_n2(ix, px) * _n2(iz, pz)),
                  _d2(iz, pz) * (_n2(ix, px) * _n2(iy, py))) for (ix, iy, iz) in Q2_HEX_LOC]
+    if (dim, nd) == (2, 6):
+        return _p2_simplex(2, WEDGE_TRI[q])[1]
+    if (dim, nd) == (3, 10):
+        return _p2_simplex(3, TET_POINTS[q])[1]
     if (dim, nd) == (2, 3):
         return [tuple(d) for d in TRI_D]
     if (dim, nd) == (3, 4):
@@ -256,7 +291,7 @@ def _mesh(coords, elem_to_vertex, elem_ptr):
     elem = np.repeat(np.arange(len(nd), dtype=np.int64), nd)
     if len(np.unique(elem * max(int(NV), 1) + e2v)) != len(e2v):
         raise ValueError("an element lists a vertex twice")
-    for e in np.flatnonzero(~np.isin(nd, [k[1] for k in tuple(TYPE_INDEX) + ORDER2 if k[0] == dim])):
+    for e in np.flatnonzero(~np.isin(nd, [k[1] for k in ALL_TYPE_INDEX if k[0] == dim])):
         raise ValueError("element %d: %d nodes are no supported element type in %dD" % (e, nd[e], dim))
     return X, dim, ep, e2v, nd
 
@@ -297,7 +332,7 @@ def type_counts(dim, elem_to_vertex, elem_ptr=None):
 
 
 def order2_count(dim, elem_to_vertex, elem_ptr=None):
-    """the number of order-2 elements (info[7] of saamge_amd_element_matrices)"""
+    """the number of order-2 elements of all four types (info[7] of saamge_amd_element_matrices)"""
     nd = np.diff(np.asarray(elem_ptr, np.int64)) if elem_ptr is not None else \
         np.full(np.asarray(elem_to_vertex).shape[0], np.asarray(elem_to_vertex).shape[1])
     return int(sum((nd == k).sum() for (d, k) in ORDER2 if d == dim))
@@ -317,7 +352,12 @@ def dof_lists(dim, elem_to_vertex, kind, elem_ptr=None):
 # ---- mass matrices and load vectors (zeroth-order forms) ---------------------------------------------------------------------
 #   rule         the type's rule above, except the simplices (one point is not enough for a product of two shape functions):
 #                triangle: the three points of WEDGE_TRI, weight 1/6 each; tetrahedron: four points, weight 1/24 each, point 0
-#                (TET_A, TET_A, TET_A) and point q = 1 .. 3 with coordinate q - 1 replaced by TET_B.
+#                (TET_A, TET_A, TET_A) and point q = 1 .. 3 with coordinate q - 1 replaced by TET_B.  Order-2 simplices:
+#                triangle 6 points in two orbits (a, a), (b, a), (a, b) with b = 1.0 - 2.0 * a; tetrahedron 14 points: two
+#                orbits (a, a, a), (b, a, a), (a, b, a), (a, a, b) with b = 1.0 - 3.0 * a, then one point per edge (i, j) in
+#                the order of P2_EDGES whose barycentric coordinates i and j are b = 0.5 - a and the other two a, the point
+#                being (L_1, L_2, L_3).  Their shape values and gradients are _p2_simplex's AT THE MASS POINTS
+#                (mass_reference_gradients: the gradients are not constant).
 #   shapes       N_a at a point, written out like the gradients (shape_values).
 #   point        J, the cofactors and det exactly as above, from the type's gradients at that point (constant for the
 #                simplices, formed per point all the same); a det that is not positive refuses the element;
@@ -333,11 +373,33 @@ TET_POINTS = [(TET_A, TET_A, TET_A), (TET_B, TET_A, TET_A), (TET_A, TET_B, TET_A
 MASS_NPOINTS = dict(NPOINTS)
 MASS_NPOINTS.update({(2, 3): 3, (3, 4): 4})
 MASS_WEIGHT = {(2, 3): 0.16666666666666666, (3, 4): 0.041666666666666664}
+P2_TRI_A = (0.44594849091596483, 0.09157621350977073)
+P2_TRI_W = tuple(w for w in (0.11169079483900572, 0.054975871827660935) for _ in range(3))
+P2_TRI_POINTS = [p for a in P2_TRI_A for b in (1.0 - 2.0 * a,) for p in ((a, a), (b, a), (a, b))]
+P2_TET_A = (0.3108859192633006, 0.09273525031089122)
+P2_TET_EDGE_A = 0.04550370412564965
+P2_TET_W = tuple(w for w in (0.018781320953002643, 0.012248840519393659) for _ in range(4)) + (0.007091003462846911,) * 6
+P2_TET_POINTS = [p for a in P2_TET_A for b in (1.0 - 3.0 * a,) for p in ((a, a, a), (b, a, a), (a, b, a), (a, a, b))] + \
+    [tuple((0.5 - P2_TET_EDGE_A) if k in e else P2_TET_EDGE_A for k in (1, 2, 3)) for e in P2_EDGES[3]]
+MASS_NPOINTS.update({(2, 6): 6, (3, 10): 14})
 
 
 def mass_point_weight(dim, nd, q):
     """weight of point q of the type's mass rule"""
+    if (dim, nd) == (2, 6):
+        return P2_TRI_W[q]
+    if (dim, nd) == (3, 10):
+        return P2_TET_W[q]
     return MASS_WEIGHT[(dim, nd)] if (dim, nd) in MASS_WEIGHT else point_weight(dim, nd, q)
+
+
+def mass_reference_gradients(dim, nd, q):
+    """dN[a][j] at point q of the type's MASS rule: the stiffness rule's, except for the order-2 simplices"""
+    if (dim, nd) == (2, 6):
+        return _p2_simplex(2, P2_TRI_POINTS[q])[1]
+    if (dim, nd) == (3, 10):
+        return _p2_simplex(3, P2_TET_POINTS[q])[1]
+    return reference_gradients(dim, nd, q)
 
 
 def shape_values(dim, nd, q):
@@ -348,6 +410,10 @@ def shape_values(dim, nd, q):
     if (dim, nd) == (3, 27):
         px, py, pz = GAUSS3[q % 3], GAUSS3[(q // 3) % 3], GAUSS3[q // 9]
         return [_n2(ix, px) * (_n2(iy, py) * _n2(iz, pz)) for (ix, iy, iz) in Q2_HEX_LOC]
+    if (dim, nd) == (2, 6):
+        return _p2_simplex(2, P2_TRI_POINTS[q])[0]
+    if (dim, nd) == (3, 10):
+        return _p2_simplex(3, P2_TET_POINTS[q])[0]
     if (dim, nd) == (2, 3):
         x, y = WEDGE_TRI[q]
         return [(1.0 - x) - y, x, y]
@@ -376,7 +442,7 @@ def _mass_points(X, dim, nd, c):
     out = []
     with np.errstate(all="ignore"):
         for q in range(MASS_NPOINTS[(dim, nd)]):
-            dN = reference_gradients(dim, nd, q)                     # (the simplices': the same at every point)
+            dN = mass_reference_gradients(dim, nd, q)                # (the order-1 simplices': the same at every point)
             J = [[None] * dim for _ in range(dim)]
             for i in range(dim):
                 for j in range(dim):
@@ -500,10 +566,14 @@ def element_loads(coords, elem_to_vertex, src, vdim=1, coef=None, elem_ptr=None)
 # ---- boundary forms: the face mass (Robin) and the face loads (Neumann) ---------------------------------------------------------
 #   face         a pair (element id, local face index); FACE_NODES[(dim, nodes)][local face] lists the element's local node ids of
 #                the face in the node order of the face's own type: the 2-node / 3-node segment (start, end / start, middle, end),
-#                the triangle, the 4-node quadrilateral (QUAD_LOC order) and the 9-node quadrilateral (Q2_QUAD_LOC order).
+#                the triangle, the 4-node quadrilateral (QUAD_LOC order), the 9-node quadrilateral (Q2_QUAD_LOC order) and the
+#                6-node triangle (the three vertices, then the midpoints of (v0, v1), (v1, v2), (v2, v0): the order of (2, 6)).
+#                The P2 triangle's faces are 3-node segments, the P2 tetrahedron's four faces are those of the tetrahedron as
+#                6-node triangles (believed to be MFEM's orientation, like the rest of the table; the table is the definition).
 #   rule         of the face type (face_rule): the 2-node segment has the 2 GAUSS points, weight 0.5 each, shapes _f, derivatives
 #                _df; the 3-node segment GAUSS3 / GAUSS3_W, _n2, _d2; a triangle, 4-node or 9-node quadrilateral face has the mass
-#                rule, shape values and reference gradients of the element type (2, 3), (2, 4), (2, 9).
+#                rule, shape values and reference gradients of the element type (2, 3), (2, 4), (2, 9); a 6-node triangle
+#                those of (2, 6): the 6-point rule.
 #   point        tangents t_j[i] = sum over the face nodes c, ascending, of x_c[i] * dN_c[j], the first product as it is;
 #                dim 2: m2 = t[0] * t[0] + t[1] * t[1]; dim 3: n = t_0 x t_1 (n0 = t0y * t1z - t0z * t1y, n1 = t0z * t1x - t0x * t1z,
 #                n2 = t0x * t1y - t0y * t1x), m2 = (n0 * n0 + n1 * n1) + n2 * n2; meas = sqrt(m2), correctly rounded;
@@ -536,14 +606,25 @@ FACE_NODES = {
     (2, 3): ((0, 1), (1, 2), (2, 0)),
     (2, 4): ((0, 1), (1, 2), (2, 3), (3, 0)),
     (2, 9): ((0, 4, 1), (1, 5, 2), (2, 6, 3), (3, 7, 0)),
+    (2, 6): ((0, 3, 1), (1, 4, 2), (2, 5, 0)),
+    (3, 10): ((1, 2, 3, 7, 9, 8), (0, 3, 2, 6, 9, 5), (0, 1, 3, 4, 8, 6), (0, 2, 1, 5, 7, 4)),
     (3, 4): ((1, 2, 3), (0, 3, 2), (0, 1, 3), (0, 2, 1)),
     (3, 6): ((0, 2, 1), (3, 4, 5), (0, 1, 4, 3), (1, 2, 5, 4), (2, 0, 3, 5)),
     (3, 8): _HEX_FACES,
     (3, 27): _hex27_faces(_HEX_FACES),
 }
 # (dim, face nodes) -> info[0..4] of saamge_amd_boundary_mass / _loads: 2-node segments, 3-node segments, triangles, 4-node
-# quadrilaterals, 9-node quadrilaterals
-FACE_TYPE_INDEX = {(2, 2): 0, (2, 3): 1, (3, 3): 2, (3, 4): 3, (3, 9): 4}
+# quadrilaterals, 9-node quadrilaterals.  The 6-node triangle is face type 5; info counts it with the triangles
+# (face_info_index): info[1] counts the 3-node segments whichever element type owns them, info[2] the triangular faces of 3
+# and of 6 nodes.
+FACE_TYPE_INDEX = {(2, 2): 0, (2, 3): 1, (3, 3): 2, (3, 4): 3, (3, 9): 4, (3, 6): 5}
+
+
+def face_info_index(dim, fn):
+    """the entry of info[0..4] of saamge_amd_boundary_mass / _loads that counts the faces of this type"""
+    t = FACE_TYPE_INDEX[(dim, fn)]
+    return 2 if t == 5 else t
+
 MAX_FACES = 6
 
 
@@ -563,7 +644,8 @@ def face_rule(dim, fn):
         return [([_n2(k, p) for k in range(3)], [(_d2(k, p),) for k in range(3)], GAUSS3_W[q]) for q, p in enumerate(GAUSS3)]
     if (dim, fn) not in FACE_TYPE_INDEX:
         raise ValueError("%d nodes: no face type of a %dD element" % (fn, dim))
-    return [(shape_values(2, fn, q), reference_gradients(2, fn, q), mass_point_weight(2, fn, q)) for q in range(MASS_NPOINTS[(2, fn)])]
+    return [(shape_values(2, fn, q), mass_reference_gradients(2, fn, q), mass_point_weight(2, fn, q))
+            for q in range(MASS_NPOINTS[(2, fn)])]
 
 
 def _face_points(X, dim, fn, c):

@@ -1102,6 +1102,38 @@ def q2_straight_sided(coords, elem_to_node):
     return X
 
 
+# ---- order-2 simplices: the 6-node triangle and the 10-node tetrahedron from a vertex mesh
+P2_EDGES = {3: ((0, 1), (1, 2), (2, 0)), 4: ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))}      # elmat_model.P2_EDGES by vertex count
+
+
+def p2_simplex_nodes(coords, elem_to_vertex):
+    """(all coordinates, element -> node lists) of the P2 mesh on a triangle (NE x 3) / tetrahedron (NE x 4) mesh: one midside
+    node per distinct edge, numbered after the vertices in ascending (min, max) vertex pair and placed at 0.5 * (a + b); the
+    lists (NE x 6 / NE x 10, int32) hold the vertices, then the midside nodes of the edges P2_EDGES in that order."""
+    X = np.asarray(coords, dtype=np.float64)
+    e2v = np.asarray(elem_to_vertex).astype(np.int64)
+    NV = X.shape[0]
+    edges = P2_EDGES[e2v.shape[1]]
+    a = np.stack([e2v[:, i] for (i, j) in edges], axis=1)
+    b = np.stack([e2v[:, j] for (i, j) in edges], axis=1)
+    key = np.minimum(a, b) * NV + np.maximum(a, b)
+    uniq, inverse = np.unique(key.ravel(), return_inverse=True)
+    mid = 0.5 * (X[uniq // NV] + X[uniq % NV])
+    e2n = np.concatenate([e2v, NV + inverse.reshape(key.shape)], axis=1)
+    return np.ascontiguousarray(np.concatenate([X, mid])), np.ascontiguousarray(e2n.astype(np.int32))
+
+
+def p2_simplex_straight_sided(coords, elem_to_node):
+    """A copy of coords in which every midside node of a P2 triangle (6 nodes) / tetrahedron (10 nodes) mesh sits at
+    0.5 * (a + b) of its edge's vertices.  Move the vertices (jitter), then call this: the elements are straight-sided."""
+    X = np.array(coords, dtype=np.float64)
+    e2n = np.asarray(elem_to_node)
+    nv = {6: 3, 10: 4}[e2n.shape[1]]
+    for k, (i, j) in enumerate(P2_EDGES[nv]):
+        X[e2n[:, nv + k]] = 0.5 * (X[e2n[:, i]] + X[e2n[:, j]])
+    return X
+
+
 # ---- the faces of a mesh that belong to one element only (harness for saamge_amd_boundary_mass / _loads)
 def boundary_faces(dim, elem_to_vertex, elem_ptr=None):
     """(face_elem, face_local), int32, ascending by (element, local face): the faces -- elmat_model.FACE_NODES of the element's

@@ -7,7 +7,7 @@ warm-up, `--reps` repetitions (all listed).  One JSON line per case.
 
     python tools/elmat_time.py [--hex 128,256] [--elasticity 64] [--q2-hex 64,128] [--q2-elasticity 32,64] [--quad9 2048]
                                [--reps 3] [--host-reps 3] [--hbm-gbs 8000] [--fp64-gops 39300] [--no-host] [--no-mass]
-                               [--rhs 256] [--boundary]
+                               [--rhs 256] [--boundary] [--p2-simplex] [--p2-tet 64] [--p2-tri 2048]
 
 Beside every stiffness case, on the same mesh and in the same run (--no-mass: not): the mass matrices of the same layout
 (saamge_amd_element_mass; vdim 1 beside diffusion, dim beside elasticity), written (`<case>:mass`) and added to the stiffness
@@ -20,6 +20,12 @@ once.
 hexes 64^3 (vdim 1 and 3) and 9-node quadrilaterals 2048^2, same protocol (device inputs, jittered, host clock round the whole
 call, one warm-up, --reps repetitions); the yardstick of a case is `element_mass` with `add_to` on the same mesh in the same run
 (`mass_accumulate_ms`): the boundary call touches about 6 / n of the elements and should land below it.
+
+--p2-simplex: only the order-2 simplices -- 10-node tetrahedra from the Kuhn split of the --p2-tet^3 grid and 6-node triangles
+from the diagonal split of the --p2-tri^2 grid, their nodes the (2 n + 1)^dim half-grid with every node moved by 0.1 of the node
+spacing -- under the same protocol: diffusion, elasticity, mass (vdim 1 and dim, written), loads, and the boundary mass and loads
+on all boundary faces; after each, the same form on the 27-node hexes / 9-node quadrilaterals of the same grid in the same run,
+the yardstick (`yardstick_fraction_of_bound`, or `yardstick_ms` for the boundary forms).
 
 The vertices are jittered by 0.2 mesh widths, so no two elements are alike.  A case that does not fit is reported as skipped
 with the error.
@@ -59,6 +65,9 @@ def main():
     ap.add_argument("--no-mass", action="store_true")
     ap.add_argument("--rhs", default="")
     ap.add_argument("--boundary", action="store_true")
+    ap.add_argument("--p2-simplex", action="store_true")
+    ap.add_argument("--p2-tet", type=int, default=64)
+    ap.add_argument("--p2-tri", type=int, default=2048)
     a = ap.parse_args()
     ints = lambda v: [int(x) for x in v.split(",") if x]
     stream = lambda: torch.cuda.current_stream().cuda_stream
@@ -129,6 +138,105 @@ def main():
         fe = torch.cat([idx[m] for m in sides])
         fl = torch.cat([torch.full((int(m.sum()),), k, device=dev, dtype=torch.int32) for k, m in enumerate(sides)])
         return fe.contiguous(), fl.contiguous()
+
+    def mesh_p2(n, dim):
+        """The order-2 simplex split of the n^dim grid on the nodes of mesh_q2 (node (z * gn + y) * gn + x of the half-grid): 6
+        tetrahedra per cell (problems.hex_to_tets) or 2 triangles (problems.quads_to_tris), a midside node at the sum of its two
+        vertices' grid positions.  Returns X, the node lists, the generator and the nodes' half-grid positions (NE, nodes, dim)."""
+        from saamge_amd import elmat_model
+        X, _, g = mesh_q2(n, dim)
+        gn = 2 * n + 1
+        idx = torch.arange(n ** dim, device=dev)
+        base = torch.stack([idx % n, (idx // n) % n] + ([idx // (n * n)] if dim == 3 else []), dim=1)      # (cells, dim): x, y(, z)
+        if dim == 3:
+            corners = []
+            for k, perm in enumerate(problems._KUHN):
+                c, v = [0, 0, 0], [[0, 0, 0]]
+                for axis in perm:
+                    c[axis] = 1
+                    v.append(list(c))
+                if k >= 3:
+                    v[2], v[3] = v[3], v[2]
+                corners.append(v)
+        else:
+            corners = [[[0, 0], [1, 0], [1, 1]], [[0, 0], [1, 1], [0, 1]]]
+        corners = torch.tensor(corners, device=dev)                                    # (simplices per cell, dim + 1, dim)
+        V = base[:, None, None, :] + corners[None, :, :, :]                            # (cells, per cell, dim + 1, dim)
+        V = V.reshape(-1, dim + 1, dim)
+        mids = [V[:, i] + V[:, j] for (i, j) in elmat_model.P2_EDGES[dim]]
+        P = torch.cat([2 * V, torch.stack(mids, dim=1)], dim=1)                        # half-grid positions of all nodes
+        ids = P[..., 0] + gn * P[..., 1] + (gn * gn * P[..., 2] if dim == 3 else 0)
+        return X, ids.to(torch.int32).contiguous(), g, P
+
+    def simplex_boundary(P, n, dim):
+        """(face_elem, face_local) of the faces of the split whose vertices all lie on one side of the box"""
+        from saamge_amd import elmat_model
+        fe, fl = [], []
+        ne = torch.arange(P.shape[0], device=dev, dtype=torch.int32)
+        for lf, nodes in enumerate(elmat_model.FACE_NODES[(dim, P.shape[1])]):
+            Q = P[:, list(nodes)]
+            on = ((Q == 0).all(dim=1) | (Q == 2 * n).all(dim=1)).any(dim=1)
+            fe.append(ne[on])
+            fl.append(torch.full((int(on.sum()),), lf, device=dev, dtype=torch.int32))
+        return torch.cat(fe).contiguous(), torch.cat(fl).contiguous()
+
+    if a.p2_simplex:
+        def reps(call):
+            timed(call)                            # warm-up
+            return [round(timed(call)[0], 3) for _ in range(a.reps)]
+        for dim, n in ((3, a.p2_tet), (2, a.p2_tri)):
+            seen = {}
+            for fam in ("q2", "p2"):               # the yardstick first
+                try:
+                    if fam == "p2":
+                        X, e2n, g, P = mesh_p2(n, dim)
+                        fe, fl = simplex_boundary(P, n, dim)
+                        P = None
+                    else:
+                        X, e2n, g = mesh_q2(n, dim)
+                        fe, fl = grid_boundary(n, dim)
+                    NE, nd, NF = int(e2n.shape[0]), int(e2n.shape[1]), int(fe.numel())
+                    name = {27: "hex27", 9: "quad9", 10: "tet10", 6: "tri6"}[nd] + "_%d" % n
+                    c1 = 0.5 + 1.5 * torch.rand(NE, generator=g, device=dev, dtype=torch.float64)
+                    c2 = 0.5 + 1.5 * torch.rand((NE, 2), generator=g, device=dev, dtype=torch.float64)
+                    alpha = 0.5 + 1.5 * torch.rand(NF, generator=g, device=dev, dtype=torch.float64)
+                    src = torch.rand((X.shape[0], dim), generator=g, device=dev, dtype=torch.float64)
+                    src1 = src[:, 0].contiguous()
+                    out = torch.zeros(NE * (nd * dim) ** 2, dtype=torch.float64, device=dev)
+                    vec = torch.zeros(NE * nd * dim, dtype=torch.float64, device=dev)
+                    o1, v1 = out[:NE * nd * nd], vec[:NE * nd]
+                    st = stream
+                    forms = [("diffusion", 8 * o1.numel(), lambda: capi.element_matrices(X, e2n, 0, c1, device=True, out=o1, stream=st())),
+                             ("elasticity", 8 * out.numel(), lambda: capi.element_matrices(X, e2n, 1, c2, device=True, out=out, stream=st())),
+                             ("mass_vdim1", 8 * o1.numel(), lambda: capi.element_mass(X, e2n, c1, out=o1, stream=st())),
+                             ("mass_vdim%d" % dim, 8 * out.numel(), lambda: capi.element_mass(X, e2n, c1, vdim=dim, out=out, stream=st())),
+                             ("loads_vdim1", 8 * v1.numel(), lambda: capi.element_loads(X, e2n, src1, coef=c1, out=v1, stream=st())),
+                             ("loads_vdim%d" % dim, 8 * vec.numel(), lambda: capi.element_loads(X, e2n, src, vdim=dim, coef=c1, out=vec, stream=st()))]
+                    for tag, nbytes, call in forms:
+                        t = reps(call)
+                        b_ms = 1e3 * nbytes / (a.hbm_gbs * 1e9)
+                        rec = {"case": "%s:%s" % (name, tag), "elements": NE, "bound_bytes": int(nbytes), "device_ms": t,
+                               "hbm_bound_ms": round(b_ms, 4), "fraction_of_bound": round(b_ms / min(t), 4)}
+                        if fam == "q2":
+                            seen[tag] = rec["fraction_of_bound"]
+                        else:
+                            rec["yardstick_fraction_of_bound"] = seen.get(tag)
+                        print(json.dumps(rec), flush=True)
+                    for tag, call in [("boundary_mass", lambda: capi.boundary_mass(X, e2n, fe, fl, alpha, add_to=o1, stream=st())),
+                                      ("boundary_loads", lambda: capi.boundary_loads(X, e2n, fe, fl, src1, coef=alpha, add_to=v1, stream=st()))]:
+                        t = reps(call)
+                        rec = {"case": "%s:%s" % (name, tag), "elements": NE, "faces": NF, "device_ms": t}
+                        if fam == "q2":
+                            seen[tag] = min(t)
+                        else:
+                            rec["yardstick_ms"] = seen.get(tag)
+                        print(json.dumps(rec), flush=True)
+                except (RuntimeError, MemoryError) as e:
+                    print(json.dumps({"case": "%s %dD n = %d" % (fam, dim, n), "skipped": str(e)[:200]}), flush=True)
+                X = e2n = out = vec = o1 = v1 = fe = fl = alpha = src = src1 = c1 = c2 = None
+                torch.cuda.empty_cache()
+                capi.release_cached_memory()
+        return
 
     if a.boundary:
         for name, n, dim, nd, vdim in [("hex128", 128, 3, 8, 1), ("hex256", 256, 3, 8, 1), ("q2_hex64", 64, 3, 27, 1),
