@@ -497,6 +497,49 @@ int saamge_amd_boundary_mass(int NV, int dim, const double *coords, int NE, int 
 int saamge_amd_boundary_loads(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                               const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim,
                               const double *coef, const double *g, void *stream, double *elvec_inout, long long info[8]);
+/* ---- the faces of a mesh found on the device (csrc/mesh_faces.hip) ----
+ * Which element lies across each local face, and from that the boundary face list the boundary forms take, the element graph
+ * through faces that saamge_amd_partition_graph takes, and the essential-dof flags that saamge_amd_operator_assemble and
+ * saamge_amd_ml_produce_data* take: saamge_amd/mesh_model.py defines every integer and the device gives the same.  Element types
+ * and local faces are those of the boundary forms above.  A SLOT is (element, local face), s = slot_ptr[e] + lf.  The CORNERS
+ * of a face: in 2D its first and last node; of a triangular face (3 or 6 nodes) its first three nodes, of a quadrilateral face
+ * (4 or 9 nodes) its first four.  Two slots match when their sorted corner vertex ids are equal (midside and centre nodes take no
+ * part: a hexahedron and a 27-node hexahedron on the same four vertices are neighbours).  One slot alone is a boundary face; three
+ * or more on one corner set make the mesh non-manifold, which is refused.
+ * saamge_amd_face_table_build: nbr_elem[s] / nbr_local[s] the element and local face across slot s (-1, -1: boundary); bdr_elem /
+ * bdr_local the NB boundary faces ascending by (element, local face); xadj (NE + 1) / adj (nnz): row e the distinct elements
+ * across the faces of e, ascending, no self loop.  info[0] = slots, [1] = interior pairs, [2] = boundary faces ([0] = 2 [1] + [2]),
+ * [3] = graph entries, [4] = interior pairs whose two faces differ in their node count, [5] = the most elements at one vertex,
+ * [6] = -1 or the lowest element with a non-manifold face (then only [0], [5], [6] are filled), [7] = elements without a neighbour.
+ * Any input a host or device pointer, each on its own.  NE = 0 is legal.  Refused, before anything touches the device: out NULL,
+ * dim not 2 or 3, NV < 0, NE < 0, elem_to_vertex NULL, without elem_ptr an nde that is no type of the dimension or NE * nde
+ * beyond 32 bits; then malformed offsets, a vertex id outside [0, NV) (before any kernel reads through the ids), a vertex listed
+ * twice, the first element whose node count is no type of the dimension; then the non-manifold mesh.
+ * saamge_amd_face_table_arrays: the device arrays, valid while the handle lives; any pointer may be NULL.
+ * saamge_amd_face_table_get: blocking copies into host or device buffers; NULL: skipped; all NULL: the counts only.
+ * saamge_amd_face_nodes: the global node ids of the NF listed faces in each face's own node order, midside nodes included:
+ * face_ptr_out NF + 1 ints, face_nodes_out *count_out ints; outputs NULL: the count only.
+ * saamge_amd_face_dofs: bdr_dofs_inout[vdim * a + i] |= flag for every node a of every listed face and every component i with
+ * bit i of comp_mask set; vdim * NV bytes, read and written in place, other bytes and other bits keep their value.  vdim 1 or
+ * dim; flag in 1 .. 127 (SAAMGE_AMD_ON_ESS_DOMAIN_BORDER); comp_mask in 1 .. 2^vdim - 1.  info[0] = faces, [1] = distinct nodes
+ * touched, [2] = bytes whose value changed, [3] = -1 or the first refused face.
+ * Both face-list calls refuse what saamge_amd_boundary_mass refuses of the mesh and of a face list (the first face out of range,
+ * then the first face listed twice), nothing of the measure; NF = 0 writes nothing. */
+typedef struct saamge_amd_face_table saamge_amd_face_table;
+int saamge_amd_face_table_build(int NV, int dim, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex, void *stream,
+                                saamge_amd_face_table **out, long long info[8]);
+int saamge_amd_face_table_arrays(const saamge_amd_face_table *t, const long long **slot_ptr, const int **nbr_elem,
+                                 const int **nbr_local, long long *NB, const int **bdr_elem, const int **bdr_local,
+                                 const long long **xadj, const int **adj, long long *nnz);
+int saamge_amd_face_table_get(const saamge_amd_face_table *t, long long *slot_ptr, int *nbr_elem, int *nbr_local, long long *NB,
+                              int *bdr_elem, int *bdr_local, long long *xadj, int *adj, long long *nnz);
+void saamge_amd_face_table_free(saamge_amd_face_table *t);
+int saamge_amd_face_nodes(int NV, int dim, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex, int NF,
+                          const int *face_elem, const int *face_local, void *stream, int *face_ptr_out, int *face_nodes_out,
+                          long long *count_out);
+int saamge_amd_face_dofs(int NV, int dim, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex, int NF,
+                         const int *face_elem, const int *face_local, int vdim, unsigned comp_mask, int flag, void *stream,
+                         signed char *bdr_dofs_inout, long long info[4]);
 /* R = P^T (P nrows x ncols) */
 int saamge_amd_csr_transpose(int nrows, int ncols, const int *rowptr, const int *col, const double *val, int *Rrow,
                              long long *Rnnz, int *Rcol, double *Rval);

@@ -451,6 +451,117 @@ private:
     const double *val_;
 };
 
+// == the faces of a mesh found on the device (saamge_amd_face_table_build, _face_nodes, _face_dofs) ==
+// Owner of the handle: which element lies across each local face, the boundary faces and the element graph through faces
+// (definitions in saamge_amd.h).  The pointers are device arrays that live as long as this object: bdr_elem() / bdr_local() go
+// to boundary_mass_into / boundary_loads_into / face_dofs_into, xadj() / adj() to saamge_amd_partition_graph.  Movable, not
+// copyable.  elem_ptr == nullptr: every element has nde nodes.
+struct FaceTableInfo {
+    long long slots, pairs, boundary_faces, graph_entries, mixed_pairs, max_valence, first_bad_element, isolated_elements;
+};
+class FaceTable {
+public:
+    FaceTable(int NV, int dim, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex, void *stream = nullptr)
+        : t_(nullptr), NE_(NE), NB_(0), nnz_(0), info_(), slot_ptr_(nullptr), xadj_(nullptr), nbr_elem_(nullptr), nbr_local_(nullptr),
+          bdr_elem_(nullptr), bdr_local_(nullptr), adj_(nullptr) {
+        long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (saamge_amd_face_table_build(NV, dim, NE, nde, elem_ptr, elem_to_vertex, stream, &t_, info))
+            throw std::runtime_error(saamge_amd_last_error());
+        const FaceTableInfo r = {info[0], info[1], info[2], info[3], info[4], info[5], info[6], info[7]};
+        info_ = r;
+        if (saamge_amd_face_table_arrays(t_, &slot_ptr_, &nbr_elem_, &nbr_local_, &NB_, &bdr_elem_, &bdr_local_, &xadj_, &adj_, &nnz_)) {
+            saamge_amd_face_table_free(t_);
+            throw std::runtime_error(saamge_amd_last_error());
+        }
+    }
+    FaceTable(FaceTable &&o) noexcept
+        : t_(o.t_), NE_(o.NE_), NB_(o.NB_), nnz_(o.nnz_), info_(o.info_), slot_ptr_(o.slot_ptr_), xadj_(o.xadj_),
+          nbr_elem_(o.nbr_elem_), nbr_local_(o.nbr_local_), bdr_elem_(o.bdr_elem_), bdr_local_(o.bdr_local_), adj_(o.adj_) {
+        o.t_ = nullptr;
+    }
+    FaceTable &operator=(FaceTable &&o) noexcept {
+        if (this != &o) {
+            saamge_amd_face_table_free(t_);
+            t_ = o.t_; NE_ = o.NE_; NB_ = o.NB_; nnz_ = o.nnz_; info_ = o.info_;
+            slot_ptr_ = o.slot_ptr_; xadj_ = o.xadj_; nbr_elem_ = o.nbr_elem_; nbr_local_ = o.nbr_local_;
+            bdr_elem_ = o.bdr_elem_; bdr_local_ = o.bdr_local_; adj_ = o.adj_;
+            o.t_ = nullptr;
+        }
+        return *this;
+    }
+    FaceTable(const FaceTable &) = delete;
+    FaceTable &operator=(const FaceTable &) = delete;
+    ~FaceTable() { saamge_amd_face_table_free(t_); }
+    int elements() const { return NE_; }
+    long long slots() const { return info_.slots; }
+    long long boundary_faces() const { return NB_; }
+    long long nnz() const { return nnz_; }
+    const FaceTableInfo &info() const { return info_; }
+    const long long *slot_ptr() const { return slot_ptr_; }
+    const int *nbr_elem() const { return nbr_elem_; }
+    const int *nbr_local() const { return nbr_local_; }
+    const int *bdr_elem() const { return bdr_elem_; }
+    const int *bdr_local() const { return bdr_local_; }
+    const long long *xadj() const { return xadj_; }
+    const int *adj() const { return adj_; }
+    saamge_amd_face_table *handle() const { return t_; }
+    // host copies
+    void get(std::vector<long long> &slot_ptr, std::vector<int> &nbr_elem, std::vector<int> &nbr_local, std::vector<int> &bdr_elem,
+             std::vector<int> &bdr_local, std::vector<long long> &xadj, std::vector<int> &adj) const {
+        slot_ptr.assign((size_t)NE_ + 1, 0);
+        xadj.assign((size_t)NE_ + 1, 0);
+        nbr_elem.assign((size_t)info_.slots, 0);
+        nbr_local.assign((size_t)info_.slots, 0);
+        bdr_elem.assign((size_t)NB_, 0);
+        bdr_local.assign((size_t)NB_, 0);
+        adj.assign((size_t)nnz_, 0);
+        if (saamge_amd_face_table_get(t_, slot_ptr.data(), nbr_elem.data(), nbr_local.data(), nullptr, bdr_elem.data(),
+                                      bdr_local.data(), xadj.data(), adj.data(), nullptr))
+            throw std::runtime_error(saamge_amd_last_error());
+    }
+
+private:
+    saamge_amd_face_table *t_;
+    int NE_;
+    long long NB_, nnz_;
+    FaceTableInfo info_;
+    const long long *slot_ptr_, *xadj_;
+    const int *nbr_elem_, *nbr_local_, *bdr_elem_, *bdr_local_, *adj_;
+};
+// the global node ids of the listed faces, in each face's own node order, on the host: face f is nodes[face_ptr[f] ..
+// face_ptr[f + 1]).  The inputs are host or device pointers, each on its own.
+struct FaceNodes {
+    std::vector<int> face_ptr, nodes;
+};
+inline FaceNodes face_nodes(int NV, int dim, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex, int NF,
+                            const int *face_elem, const int *face_local, void *stream = nullptr) {
+    long long count = 0;
+    if (saamge_amd_face_nodes(NV, dim, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, stream, nullptr, nullptr, &count))
+        throw std::runtime_error(saamge_amd_last_error());
+    FaceNodes r;
+    r.face_ptr.assign((size_t)(NF > 0 ? NF : 0) + 1, 0);
+    r.nodes.assign((size_t)count, 0);
+    if (NF > 0 && saamge_amd_face_nodes(NV, dim, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, stream,
+                                        r.face_ptr.data(), r.nodes.data(), &count))
+        throw std::runtime_error(saamge_amd_last_error());
+    return r;
+}
+// bdr_dofs_inout[vdim * a + i] |= flag for every node a of the listed faces and every component i of comp_mask, in place (a host
+// or a device pointer of vdim * NV bytes)
+struct FaceDofsInfo {
+    long long faces, nodes, changed, first_bad_face;
+};
+inline FaceDofsInfo face_dofs_into(int NV, int dim, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex, int NF,
+                                   const int *face_elem, const int *face_local, int vdim, unsigned comp_mask,
+                                   signed char *bdr_dofs_inout, int flag = SAAMGE_AMD_ON_ESS_DOMAIN_BORDER, void *stream = nullptr) {
+    long long info[4] = {0, 0, 0, 0};
+    if (saamge_amd_face_dofs(NV, dim, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, vdim, comp_mask, flag, stream,
+                             bdr_dofs_inout, info))
+        throw std::runtime_error(saamge_amd_last_error());
+    const FaceDofsInfo r = {info[0], info[1], info[2], info[3]};
+    return r;
+}
+
 }  // namespace api
 }  // namespace saamge_amd
 

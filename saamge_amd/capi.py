@@ -42,6 +42,8 @@ SYMBOLS = [
     "saamge_amd_level_order_info", "saamge_amd_ae_order", "saamge_amd_element_matrices",
     "saamge_amd_element_mass", "saamge_amd_element_loads", "saamge_amd_operator_assemble_rhs",
     "saamge_amd_boundary_mass", "saamge_amd_boundary_loads",
+    "saamge_amd_face_table_build", "saamge_amd_face_table_arrays", "saamge_amd_face_table_get", "saamge_amd_face_table_free",
+    "saamge_amd_face_nodes", "saamge_amd_face_dofs",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong))
@@ -940,6 +942,144 @@ def boundary_loads(coords, elem_to_vertex, face_elem, face_local, g, vdim=1, coe
         C.c_int(NV), C.c_int(dim), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_int(NF), _ptr(fe), _ptr(fl),
         C.c_int(vdim), _ptr(coef), _ptr(g), C.c_void_p(stream), _ptr(None if sizes_only else add_to), info), info)
     return got if sizes_only else add_to
+
+
+def _mesh_sizes(NV, e2v, ep):
+    """(NV, NE, nde) of a mesh given as (NE, nodes) lists, or flat lists with elem_ptr"""
+    if ep is None:
+        return int(NV), int(e2v.shape[0]), int(e2v.shape[1])
+    return int(NV), len(ep) - 1, 0
+
+
+def _new_ints(n, np_dt, torch_dt, device):
+    if device:
+        import torch
+        return torch.zeros(int(n), dtype=getattr(torch, torch_dt), device="cuda")
+    return np.zeros(max(int(n), 1), np_dt)[:int(n)]
+
+
+class FaceTable(object):
+    """saamge_amd_face_table_build: which element lies across each local face of a mesh, owned by the library until free()
+    (or the end of a `with` block).  saamge_amd/mesh_model.py defines every integer.  elem_to_vertex ((NE, nodes), or flat with
+    elem_ptr) and elem_ptr: numpy arrays or device tensors, each on its own.  `.info`: the 8 integers of the call; a refusal
+    raises RuntimeError with `.info` (info[6]: the lowest element with a non-manifold face)."""
+
+    def __init__(self, NV, dim, elem_to_vertex, elem_ptr=None, stream=0):
+        _, e2v, _, ep = _element_arrays(None, elem_to_vertex, None, elem_ptr)
+        NV, NE, nde = _mesh_sizes(NV, e2v, ep)
+        h = C.c_void_p()
+        info = (C.c_longlong * 8)()
+        self.h = None
+        self.info = _mass_call(lambda: load().saamge_amd_face_table_build(
+            C.c_int(NV), C.c_int(int(dim)), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_void_p(stream), C.byref(h), info), info)
+        self.h = h
+        self.NE = NE
+        NB, nnz = C.c_longlong(0), C.c_longlong(0)
+        _check(load().saamge_amd_face_table_get(self.h, None, None, None, C.byref(NB), None, None, None, None, C.byref(nnz)))
+        self.NB, self.nnz, self.slots = int(NB.value), int(nnz.value), self.info[0]
+
+    @classmethod
+    def build(cls, NV, dim, elem_to_vertex, elem_ptr=None, stream=0):
+        return cls(NV, dim, elem_to_vertex, elem_ptr=elem_ptr, stream=stream)
+
+    def arrays(self):
+        """dict of raw device addresses (slot_ptr, nbr_elem, nbr_local, bdr_elem, bdr_local, xadj, adj) and the counts NB, nnz;
+        valid until free().  `pointer(name)` wraps one for the other entry points."""
+        p = [C.c_void_p() for _ in range(7)]
+        NB, nnz = C.c_longlong(0), C.c_longlong(0)
+        _check(load().saamge_amd_face_table_arrays(self.h, C.byref(p[0]), C.byref(p[1]), C.byref(p[2]), C.byref(NB), C.byref(p[3]),
+                                                   C.byref(p[4]), C.byref(p[5]), C.byref(p[6]), C.byref(nnz)))
+        names = ("slot_ptr", "nbr_elem", "nbr_local", "bdr_elem", "bdr_local", "xadj", "adj")
+        out = {k: int(v.value or 0) for k, v in zip(names, p)}
+        out.update(NB=int(NB.value), nnz=int(nnz.value))
+        return out
+
+    def pointer(self, name):
+        """the handle's device array `name` as an object the wrappers take in place of a device tensor (valid until free())"""
+        a = self.arrays()
+        n = {"slot_ptr": self.NE + 1, "xadj": self.NE + 1, "nbr_elem": self.slots, "nbr_local": self.slots, "bdr_elem": self.NB,
+             "bdr_local": self.NB, "adj": self.nnz}[name]
+        d = _DevicePointer(a[name], np.int64 if name in ("slot_ptr", "xadj") else np.int32)
+        d.shape = (n,)
+        return d
+
+    def get(self, device=False):
+        """(slot_ptr int64, nbr_elem, nbr_local, bdr_elem, bdr_local int32, xadj int64, adj int32): numpy arrays, or torch tensors
+        on the GPU with device=True."""
+        out = [_new_ints(self.NE + 1, np.int64, "int64", device), _new_ints(self.slots, np.int32, "int32", device),
+               _new_ints(self.slots, np.int32, "int32", device), _new_ints(self.NB, np.int32, "int32", device),
+               _new_ints(self.NB, np.int32, "int32", device), _new_ints(self.NE + 1, np.int64, "int64", device),
+               _new_ints(self.nnz, np.int32, "int32", device)]
+        _check(load().saamge_amd_face_table_get(self.h, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), None, _ptr(out[3]), _ptr(out[4]),
+                                                _ptr(out[5]), _ptr(out[6]), None))
+        return tuple(out)
+
+    def free(self):
+        if self.h is not None and self.h.value:
+            free = load().saamge_amd_face_table_free
+            free.restype = None
+            free(self.h)
+        self.h = None
+
+    close = free
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+        return False
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def face_nodes(NV, dim, elem_to_vertex, face_elem, face_local, elem_ptr=None, device=False, stream=0):
+    """saamge_amd_face_nodes: (face_ptr int32 (NF + 1), nodes int32) -- the global node ids of each listed face in the face's own
+    node order (elmat_model.FACE_NODES), midside nodes included.  Inputs numpy arrays or device tensors, each on its own;
+    device=True: torch tensors on the GPU.  Choose faces by position with your own arithmetic on coords[nodes]."""
+    _, e2v, _, ep = _element_arrays(None, elem_to_vertex, None, elem_ptr)
+    fe, fl, _, NF = _face_arrays(face_elem, face_local, None)
+    NV, NE, nde = _mesh_sizes(NV, e2v, ep)
+    count = C.c_longlong(0)
+
+    def call(fptr, nodes):
+        _check(load().saamge_amd_face_nodes(C.c_int(NV), C.c_int(int(dim)), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_int(NF),
+                                            _ptr(fe), _ptr(fl), C.c_void_p(stream), _ptr(fptr), _ptr(nodes), C.byref(count)))
+    call(None, None)
+    fptr = _new_ints(NF + 1, np.int32, "int32", device)
+    nodes = _new_ints(count.value, np.int32, "int32", device)
+    if NF:
+        call(fptr, nodes)
+    return fptr, nodes
+
+
+def face_dofs(NV, dim, elem_to_vertex, face_elem, face_local, bdr_dofs, vdim=1, comp_mask=None, flag=0x02, elem_ptr=None,
+              stream=0):
+    """saamge_amd_face_dofs: bdr_dofs[vdim * a + i] |= flag IN PLACE for every node a of every listed face and every component i
+    with bit i of comp_mask set (None: all vdim components); flag: SAAMGE_AMD_ON_ESS_DOMAIN_BORDER by default.  bdr_dofs: a device
+    tensor or a writeable C-contiguous int8 numpy array of vdim * NV entries -- what `Operator` and `Hierarchy` take as bdr.
+    Returns info = [faces, distinct nodes touched, bytes whose value changed, -1]; a refusal raises RuntimeError with `.info`
+    (info[3]: the first refused face)."""
+    _, e2v, _, ep = _element_arrays(None, elem_to_vertex, None, elem_ptr)
+    fe, fl, _, NF = _face_arrays(face_elem, face_local, None)
+    NV, NE, nde = _mesh_sizes(NV, e2v, ep)
+    vdim = int(vdim)
+    if comp_mask is None:
+        comp_mask = (1 << vdim) - 1
+    if bdr_dofs is not None and not hasattr(bdr_dofs, "data_ptr") and not (
+            isinstance(bdr_dofs, np.ndarray) and bdr_dofs.dtype == np.int8 and bdr_dofs.flags["C_CONTIGUOUS"] and
+            bdr_dofs.flags["WRITEABLE"]):
+        raise ValueError("bdr_dofs: a device tensor or a writeable C-contiguous int8 array is needed (it is written in place)")
+    if bdr_dofs is not None and int(np.prod(tuple(bdr_dofs.shape))) != vdim * NV and vdim in (1, int(dim)):
+        raise ValueError("bdr_dofs: vdim * NV entries are needed")
+    info = (C.c_longlong * 4)()
+    return _mass_call(lambda: load().saamge_amd_face_dofs(
+        C.c_int(NV), C.c_int(int(dim)), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_int(NF), _ptr(fe), _ptr(fl), C.c_int(vdim),
+        C.c_uint(int(comp_mask) & 0xffffffff), C.c_int(int(flag)), C.c_void_p(stream), _ptr(bdr_dofs), info), info)
 
 
 def get_options():

@@ -6,6 +6,7 @@
 
 #include "elmat.h"
 #include "hierarchy.h"
+#include "mesh_faces.h"
 #include "operator.h"
 #include "partition.h"
 #include "spgemm.h"
@@ -31,6 +32,9 @@ struct saamge_amd_partitioning {
 // saamge_amd_operator_assemble: the assembled operator and the device copies of the mesh tables its numeric pass needs
 struct saamge_amd_operator {
     AssembledOperator op;
+};
+struct saamge_amd_face_table {
+    FaceTable t;
 };
 static OperatorLimits g_operator_limits;      // saamge_amd_operator_set_path_limits (tests)
 
@@ -847,6 +851,81 @@ int saamge_amd_boundary_loads(int NV, int dim, const double *coords, int NE, int
     ThreadStreamScope scope(s);
     boundary_loads(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, vdim, coef, g, elvec_inout,
                    info);
+    SA_API_END
+}
+
+// ---- the faces of a mesh (mesh_faces.hip) -----------------------------------------------------------------------------------
+int saamge_amd_face_table_build(int NV, int dim, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex, void *stream,
+                                saamge_amd_face_table **out, long long info[8]) {
+    SA_API_BEGIN
+    SA_REQUIRE(out, "saamge_amd_face_table_build: null argument: out");
+    *out = nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    std::unique_ptr<saamge_amd_face_table> P(new saamge_amd_face_table);
+    face_table_build(s, NV, dim, NE, nde, elem_ptr, elem_to_vertex, P->t, info);
+    *out = P.release();
+    SA_API_END
+}
+
+int saamge_amd_face_table_arrays(const saamge_amd_face_table *t, const long long **slot_ptr, const int **nbr_elem,
+                                 const int **nbr_local, long long *NB, const int **bdr_elem, const int **bdr_local,
+                                 const long long **xadj, const int **adj, long long *nnz) {
+    SA_API_BEGIN
+    SA_REQUIRE(t, "saamge_amd_face_table_arrays: null argument");
+    if (slot_ptr) *slot_ptr = (const long long *)t->t.slot_ptr.p;
+    if (nbr_elem) *nbr_elem = t->t.nbr_elem.p;
+    if (nbr_local) *nbr_local = t->t.nbr_local.p;
+    if (NB) *NB = t->t.NB;
+    if (bdr_elem) *bdr_elem = t->t.bdr_elem.p;
+    if (bdr_local) *bdr_local = t->t.bdr_local.p;
+    if (xadj) *xadj = (const long long *)t->t.xadj.p;
+    if (adj) *adj = t->t.adj.p;
+    if (nnz) *nnz = t->t.nnz;
+    SA_API_END
+}
+
+int saamge_amd_face_table_get(const saamge_amd_face_table *t, long long *slot_ptr, int *nbr_elem, int *nbr_local, long long *NB,
+                              int *bdr_elem, int *bdr_local, long long *xadj, int *adj, long long *nnz) {
+    SA_API_BEGIN
+    SA_REQUIRE(t, "saamge_amd_face_table_get: null argument");
+    const FaceTable &T = t->t;
+    if (NB) *NB = T.NB;
+    if (nnz) *nnz = T.nnz;
+    if (slot_ptr || nbr_elem || nbr_local || bdr_elem || bdr_local || xadj || adj)
+        SA_REQUIRE(current_device() == T.device, "the calling thread's current HIP device is not the face table's device");
+    const auto copy = [](void *dst, const void *src, size_t bytes) {
+        if (dst && bytes) SA_HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyDefault));
+    };
+    copy(slot_ptr, T.slot_ptr.p, T.slot_ptr.n * sizeof(roff_t));
+    copy(nbr_elem, T.nbr_elem.p, T.nbr_elem.n * sizeof(int));
+    copy(nbr_local, T.nbr_local.p, T.nbr_local.n * sizeof(int));
+    copy(bdr_elem, T.bdr_elem.p, T.bdr_elem.n * sizeof(int));
+    copy(bdr_local, T.bdr_local.p, T.bdr_local.n * sizeof(int));
+    copy(xadj, T.xadj.p, T.xadj.n * sizeof(roff_t));
+    copy(adj, T.adj.p, T.adj.n * sizeof(int));
+    SA_API_END
+}
+
+void saamge_amd_face_table_free(saamge_amd_face_table *t) { delete t; }
+
+int saamge_amd_face_nodes(int NV, int dim, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex, int NF,
+                          const int *face_elem, const int *face_local, void *stream, int *face_ptr_out, int *face_nodes_out,
+                          long long *count_out) {
+    SA_API_BEGIN
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    face_nodes(s, NV, dim, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, face_ptr_out, face_nodes_out, count_out);
+    SA_API_END
+}
+
+int saamge_amd_face_dofs(int NV, int dim, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex, int NF,
+                         const int *face_elem, const int *face_local, int vdim, unsigned comp_mask, int flag, void *stream,
+                         signed char *bdr_dofs_inout, long long info[4]) {
+    SA_API_BEGIN
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    face_dofs(s, NV, dim, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, vdim, comp_mask, flag, bdr_dofs_inout, info);
     SA_API_END
 }
 

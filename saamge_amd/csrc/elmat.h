@@ -4,6 +4,8 @@
 #pragma once
 #include "common.h"
 
+#include <string>
+
 namespace saamge_amd {
 
 // The arguments of saamge_amd_element_matrices (include/saamge_amd.h).  The checks that need no device run before the first
@@ -31,5 +33,29 @@ void boundary_mass(hipStream_t s, int NV, int dim, const double *coords, int NE,
 void boundary_loads(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                     const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim, const double *coef,
                     const double *g, double *elvec_inout, long long info[8]);
+
+// A mesh argument brought to the device and checked: what every call of elmat.hip and of mesh_faces.hip starts with.  elem_ptr
+// NULL: NE elements of nde nodes each.  Host arrays are uploaded (the offsets first: they say how much of elem_to_vertex there
+// is), device arrays are used where they are.  Refused with `name` in front or by check_mesh_device: malformed offsets, a vertex
+// id outside [0, NV) -- before any kernel reads through the ids --, a vertex listed twice in an element.  NE > 0.
+struct DeviceMesh {
+    DBuf<int> hold_I, hold_J;
+    const int *eI = nullptr, *eJ = nullptr;      // NE + 1 offsets, the flat vertex lists
+    long nconn = 0;                              // eI[NE]
+};
+void import_mesh(hipStream_t s, const std::string &name, int NV, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex,
+                 DeviceMesh &M);
+
+// The checks of a face list, shared by the boundary forms and the face-list calls of mesh_faces.hip.  The mesh (NE > 0
+// elements, offsets eI on the device) has been checked.  Refused with `name` in front: the first face (lowest index) with
+// face_elem outside [0, NE) or face_local outside the range of the element's type, then the first face whose (element, local
+// face) the list holds more than once; *refused (may be NULL) gets that index.  face_elem / face_local: host or device pointers.
+struct FaceList {
+    DBuf<int> hold_fe, hold_fl, key;      // key[f] = type * 8 + local face (em_type_index)
+    const int *fe = nullptr, *fl = nullptr;      // the lists on the device
+    int touched = 0;                      // distinct elements of the list
+};
+void check_face_list(hipStream_t s, const std::string &name, int dim, int NE, const int *eI, int NF, const int *face_elem,
+                     const int *face_local, FaceList &L, long long *refused);
 
 }  // namespace saamge_amd

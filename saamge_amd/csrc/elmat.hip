@@ -23,6 +23,7 @@
 // The boundary forms -- the mass and the loads of a list of faces, added into the owning elements' matrices and vectors -- have
 // kernels templated on the face type (bdr_mass_kernel, bdr_load_kernel) and run one pass per local face index.
 #include "elmat.h"
+#include "elmat_types.h"
 
 #include <algorithm>
 #include <climits>
@@ -43,7 +44,6 @@ namespace {
 constexpr double EM_GAUSS[2] = {0.21132486540518713, 0.7886751345948129};
 constexpr double EM_TRI_A = 0.16666666666666666, EM_TRI_B = 0.6666666666666666;
 constexpr int EM_QUAD_LOC[4][2] = {{0, 0}, {1, 0}, {1, 1}, {0, 1}};
-constexpr int EM_HEX_LOC[8][3] = {{0, 0, 0}, {1, 0, 0}, {1, 1, 0}, {0, 1, 0}, {0, 0, 1}, {1, 0, 1}, {1, 1, 1}, {0, 1, 1}};
 constexpr double EM_TRI_D[3][2] = {{-1.0, -1.0}, {1.0, 0.0}, {0.0, 1.0}};
 constexpr double EM_TET_D[4][3] = {{-1.0, -1.0, -1.0}, {1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
 constexpr double EM_WEDGE_TRI[3][2] = {{EM_TRI_A, EM_TRI_A}, {EM_TRI_B, EM_TRI_A}, {EM_TRI_A, EM_TRI_B}};
@@ -56,14 +56,7 @@ template <> struct EmType<3, 4> { static constexpr int NQ = 1; static constexpr 
 template <> struct EmType<3, 6> { static constexpr int NQ = 6; static constexpr double W = 0.08333333333333333; };
 template <> struct EmType<3, 8> { static constexpr int NQ = 8; static constexpr double W = 0.125; };
 
-// types 0 .. 4: order 1 (info[0 .. 4]); 5, 6: the order-2 quadrilateral and hexahedron; 7, 8: the order-2 triangle (6 nodes)
-// and tetrahedron (10 nodes); info[7] counts all four
-constexpr int EM_TYPES = 9;
-constexpr int em_type_index(int dim, int nd) {
-    return dim == 2 ? (nd == 3 ? 0 : (nd == 4 ? 1 : (nd == 9 ? 5 : (nd == 6 ? 7 : -1))))
-                    : (nd == 4 ? 2 : (nd == 6 ? 3 : (nd == 8 ? 4 : (nd == 27 ? 6 : (nd == 10 ? 8 : -1)))));
-}
-constexpr int EM_TYPE_ND[EM_TYPES] = {3, 4, 4, 6, 8, 9, 27, 6, 10};
+// (the type indices -- EM_TYPES, em_type_index, EM_TYPE_ND -- and the local faces are in elmat_types.h)
 
 constexpr double em_f(int l, double p) { return l ? p : 1.0 - p; }
 constexpr double em_df(int l) { return l ? 1.0 : -1.0; }
@@ -319,7 +312,6 @@ __global__ __launch_bounds__(em_block(DIM, ND, KIND)) void em_kernel(int count, 
 // The literals and the expressions of elmat_model.py (GAUSS3, GAUSS3_W, _n2, _d2, Q2_QUAD_LOC; the hex is lexicographic).
 constexpr double EM2_GAUSS[3] = {0.11270166537925831, 0.5, 0.8872983346207417};
 constexpr double EM2_W[3] = {0.2777777777777778, 0.4444444444444444, 0.2777777777777778};
-constexpr int EM2_QUAD_LOC[9][2] = {{0, 0}, {2, 0}, {2, 2}, {0, 2}, {1, 0}, {2, 1}, {1, 2}, {0, 1}, {1, 1}};
 constexpr double em2_n(int l, double p) {
     return l == 0 ? (2.0 * p - 1.0) * (p - 1.0) : (l == 1 ? (4.0 * p) * (1.0 - p) : p * (2.0 * p - 1.0));
 }
@@ -1033,49 +1025,10 @@ __global__ __launch_bounds__(MASS_BLOCK) void load_kernel(int count, const int *
 // element's node count nd and its offsets.  The host buckets the faces by (element type, local face) and runs one pass per local
 // face index in ascending order on the stream: within a pass an element occurs at most once, so the read-modify-write of its
 // entries needs no atomic and the model's order of additions holds by construction.
-constexpr int BDR_MAX_FACES = 6;
 // info[0 .. 4]: 2-node segments, 3-node segments (of 9-node quadrilaterals and of 6-node triangles), triangles of 3 and of 6
 // nodes, 4-node quadrilaterals, 9-node quadrilaterals
 constexpr int bdr_face_type(int dim, int fn) { return dim == 2 ? fn - 2 : (fn == 3 || fn == 6 ? 2 : (fn == 4 ? 3 : 4)); }
-struct BdrFace {
-    int node[9];
-};
-// elmat_model.FACE_NODES, by the type index of em_type_index
-constexpr int bdr_num_faces(int type) { return type == 0 || type == 7 ? 3 : (type == 3 ? 5 : (type == 4 || type == 6 ? 6 : 4)); }
-constexpr int BDR_FACE_NODES[EM_TYPES][BDR_MAX_FACES] = {{2, 2, 2, 0, 0, 0}, {2, 2, 2, 2, 0, 0}, {3, 3, 3, 3, 0, 0}, {3, 3, 4, 4, 4, 0},
-                                                          {4, 4, 4, 4, 4, 4}, {3, 3, 3, 3, 0, 0}, {9, 9, 9, 9, 9, 9}, {3, 3, 3, 0, 0, 0},
-                                                          {6, 6, 6, 6, 0, 0}};
-constexpr int BDR_HEX_FACES[6][4] = {{3, 2, 1, 0}, {0, 1, 5, 4}, {1, 2, 6, 5}, {2, 3, 7, 6}, {3, 0, 4, 7}, {4, 5, 6, 7}};
-constexpr BdrFace bdr_face(int type, int lf) {
-    constexpr int TRI[3][2] = {{0, 1}, {1, 2}, {2, 0}};
-    constexpr int QUAD[4][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 0}};
-    constexpr int QUAD9[4][3] = {{0, 4, 1}, {1, 5, 2}, {2, 6, 3}, {3, 7, 0}};
-    constexpr int TET[4][3] = {{1, 2, 3}, {0, 3, 2}, {0, 1, 3}, {0, 2, 1}};
-    constexpr int WEDGE[5][4] = {{0, 2, 1, 0}, {3, 4, 5, 0}, {0, 1, 4, 3}, {1, 2, 5, 4}, {2, 0, 3, 5}};
-    constexpr int TRI6[3][3] = {{0, 3, 1}, {1, 4, 2}, {2, 5, 0}};
-    constexpr int TET10[4][6] = {{1, 2, 3, 7, 9, 8}, {0, 3, 2, 6, 9, 5}, {0, 1, 3, 4, 8, 6}, {0, 2, 1, 5, 7, 4}};
-    BdrFace f{};
-    const int fn = BDR_FACE_NODES[type][lf];
-    for (int k = 0; k < fn; ++k) {
-        if (type == 0) f.node[k] = TRI[lf][k];
-        else if (type == 1) f.node[k] = QUAD[lf][k];
-        else if (type == 2) f.node[k] = TET[lf][k];
-        else if (type == 3) f.node[k] = WEDGE[lf][k];
-        else if (type == 4) f.node[k] = BDR_HEX_FACES[lf][k];
-        else if (type == 5) f.node[k] = QUAD9[lf][k];
-        else if (type == 7) f.node[k] = TRI6[lf][k];
-        else if (type == 8) f.node[k] = TET10[lf][k];
-        else {      // the node at face position (u, v) of Q2_QUAD_LOC: P(c0) + u (P(c1) - P(c0)) / 2 + v (P(c3) - P(c0)) / 2
-            const int *c = BDR_HEX_FACES[lf];
-            int p[3] = {0, 0, 0};
-            for (int d = 0; d < 3; ++d)
-                p[d] = 2 * EM_HEX_LOC[c[0]][d] + EM2_QUAD_LOC[k][0] * (EM_HEX_LOC[c[1]][d] - EM_HEX_LOC[c[0]][d]) +
-                       EM2_QUAD_LOC[k][1] * (EM_HEX_LOC[c[3]][d] - EM_HEX_LOC[c[0]][d]);
-            f.node[k] = (p[2] * 3 + p[1]) * 3 + p[0];
-        }
-    }
-    return f;
-}
+// (BdrFace, bdr_num_faces, BDR_FACE_NODES and bdr_face: elmat_types.h)
 
 // the rule of a face type, folded at compile time from the expressions of mass_table: the segments have their own lines
 // (em_f / em_df on the 2 Gauss points, em2_n / em2_d on the 3), a face of DIM 3 is the element type (2, FN)
@@ -1441,38 +1394,15 @@ void em_check_sizes(const std::string &name, int NV, int dim, int NE, int nde, c
 }
 
 // the mesh on the device, checked; the elements of every type; square: the offsets of the packed matrices
-struct EmMesh {
-    DBuf<int> hold_I, hold_J, list[EM_TYPES], word;
+struct EmMesh : DeviceMesh {
+    DBuf<int> list[EM_TYPES], word;
     DBuf<roff_t> moff;
-    const int *eI = nullptr, *eJ = nullptr;
-    long nconn = 0;
     int count[EM_TYPES] = {};
     int64_t doubles = 0;          // of the packed result: sum of size^2 (square) or of size
 };
 void em_mesh(hipStream_t s, const std::string &name, int NV, int dim, int NE, int nde, const int *elem_ptr,
              const int *elem_to_vertex, int comp, bool square, EmMesh &M, long long info[8]) {
-    // ---- the mesh: offsets first, they say how much of elem_to_vertex there is
-    if (elem_ptr) {
-        M.eI = device_view(M.hold_I, elem_ptr, (size_t)NE + 1, s);
-    } else {
-        M.hold_I.alloc((size_t)NE + 1);
-        hipLaunchKernelGGL(em_offsets_kernel, grid_flat((long)NE + 1), dim3(256), 0, s, NE, nde, M.hold_I.p);
-        SA_HIP_CHECK(hipGetLastError());
-        M.eI = M.hold_I.p;
-    }
-    M.eJ = elem_to_vertex;
-    if (!is_device_ptr(elem_to_vertex)) {
-        long total = (long)NE * nde;
-        if (elem_ptr) {
-            const hvec<int> hI = fetch_host(M.eI, (size_t)NE + 1, s);
-            for (int e = 0; e < NE; ++e)
-                SA_REQUIRE(hI[0] == 0 && hI[(size_t)e + 1] > hI[(size_t)e], name + "elem_ptr: must start at 0 and every element needs a vertex");
-            total = hI[(size_t)NE];
-        }
-        upload(M.hold_J, elem_to_vertex, (size_t)total, s);
-        M.eJ = M.hold_J.p;
-    }
-    M.nconn = check_mesh_device(s, NE, M.eI, M.eJ, NV);      // offsets, vertex ids in [0, NV), no vertex twice in an element
+    import_mesh(s, name, NV, NE, nde, elem_ptr, elem_to_vertex, M);
     SA_REQUIRE((int64_t)M.nconn * comp <= INT_MAX, name + "dim * elem_ptr[NE] beyond 32 bits");
     // ---- types, lists, offsets of the packed matrices
     M.word.alloc(1);
@@ -1599,37 +1529,12 @@ void boundary_forms(hipStream_t s, const std::string &name, int NV, int dim, con
     SA_REQUIRE(NE > 0, name + "face 0: face_elem is outside [0, NE)");
     EmMesh M;
     em_mesh(s, name, NV, dim, NE, nde, elem_ptr, elem_to_vertex, vdim, !g, M, nullptr);
-    // ---- the face list: ranges, the mask of the (element, local face) pairs, the key of every face
-    DBuf<int> hold_fe, hold_fl, key((size_t)NF), words(3), flag((size_t)NF), pos((size_t)NF + 1);
-    const int *fe = device_view(hold_fe, face_elem, (size_t)NF, s), *fl = device_view(hold_fl, face_local, (size_t)NF, s);
-    const int nwords = (int)(((int64_t)NE + 3) / 4);
-    DBuf<unsigned> mask((size_t)nwords);
-    mask.zero(s);
-    const int init[3] = {INT_MAX, 0, 0};
-    SA_HIP_CHECK(hipMemcpyAsync(words.p, init, sizeof(init), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(bdr_check_kernel, grid_flat(NF), dim3(256), 0, s, NF, NE, dim, M.eI, fe, fl, mask.p, key.p, words.p);
-    SA_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(bdr_touched_kernel, grid_flat(nwords), dim3(256), 0, s, nwords, (const unsigned *)mask.p, words.p + 2);
-    SA_HIP_CHECK(hipGetLastError());
-    int w[3];
-    read_back(w, (const int *)words.p, 3, s);
-    if (w[0] < NF) {
-        if (info) info[6] = w[0];
-        const int e = read_one(fe + w[0], s);
-        SA_REQUIRE(false, name + "face " + std::to_string(w[0]) + ": " +
-                              (e < 0 || e >= NE ? "face_elem is outside [0, NE)" : "face_local is outside the element type's range"));
-    }
-    if (w[1]) {      // a pair is listed twice: the first face of the list that is one of a repeated pair, found on the host
-        const hvec<int> he = fetch_host(fe, (size_t)NF, s), hl = fetch_host(fl, (size_t)NF, s);
-        std::vector<std::pair<int64_t, int>> pairs((size_t)NF);
-        for (int f = 0; f < NF; ++f) pairs[(size_t)f] = {(int64_t)he[(size_t)f] * 8 + hl[(size_t)f], f};
-        std::sort(pairs.begin(), pairs.end());
-        int first = NF;
-        for (size_t k = 0; k + 1 < pairs.size(); ++k)
-            if (pairs[k].first == pairs[k + 1].first && (k == 0 || pairs[k - 1].first != pairs[k].first)) first = std::min(first, pairs[k].second);
-        if (info) info[6] = first;
-        SA_REQUIRE(false, name + "face " + std::to_string(first) + ": the same (element, local face) is listed twice");
-    }
+    // ---- the face list: ranges, repeated pairs, the key of every face
+    FaceList FL;
+    check_face_list(s, name, dim, NE, M.eI, NF, face_elem, face_local, FL, info ? info + 6 : nullptr);
+    const int *fe = FL.fe;
+    const DBuf<int> &key = FL.key;
+    DBuf<int> words(1), flag((size_t)NF), pos((size_t)NF + 1);
     // ---- one list per (element type, local face)
     DBuf<int> list[EM_TYPES][BDR_MAX_FACES];
     int count[EM_TYPES][BDR_MAX_FACES] = {};
@@ -1645,7 +1550,7 @@ void boundary_forms(hipStream_t s, const std::string &name, int NV, int dim, con
     }
     if (info) {
         info[5] = (long long)doubles;
-        info[7] = w[2];
+        info[7] = FL.touched;
     }
     // ---- the passes: ascending local face, so that the faces of one element are added in that order
     DBuf<double> hold_X, hold_c, hold_g, hold_out;
@@ -1689,6 +1594,71 @@ void bdr_begin(const std::string &name, int NV, int dim, const double *coords, i
 }
 
 }  // namespace
+
+// The mesh argument of every call of this file and of mesh_faces.hip (elmat.h)
+void import_mesh(hipStream_t s, const std::string &name, int NV, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex,
+                 DeviceMesh &M) {
+    // ---- the mesh: offsets first, they say how much of elem_to_vertex there is
+    if (elem_ptr) {
+        M.eI = device_view(M.hold_I, elem_ptr, (size_t)NE + 1, s);
+    } else {
+        M.hold_I.alloc((size_t)NE + 1);
+        hipLaunchKernelGGL(em_offsets_kernel, grid_flat((long)NE + 1), dim3(256), 0, s, NE, nde, M.hold_I.p);
+        SA_HIP_CHECK(hipGetLastError());
+        M.eI = M.hold_I.p;
+    }
+    M.eJ = elem_to_vertex;
+    if (!is_device_ptr(elem_to_vertex)) {
+        long total = (long)NE * nde;
+        if (elem_ptr) {
+            const hvec<int> hI = fetch_host(M.eI, (size_t)NE + 1, s);
+            for (int e = 0; e < NE; ++e)
+                SA_REQUIRE(hI[0] == 0 && hI[(size_t)e + 1] > hI[(size_t)e], name + "elem_ptr: must start at 0 and every element needs a vertex");
+            total = hI[(size_t)NE];
+        }
+        upload(M.hold_J, elem_to_vertex, (size_t)total, s);
+        M.eJ = M.hold_J.p;
+    }
+    M.nconn = check_mesh_device(s, NE, M.eI, M.eJ, NV);      // offsets, vertex ids in [0, NV), no vertex twice in an element
+}
+
+// The checks of a face list (elmat.h): shared by the boundary forms and the face-list calls of mesh_faces.hip.
+void check_face_list(hipStream_t s, const std::string &name, int dim, int NE, const int *eI, int NF, const int *face_elem,
+                     const int *face_local, FaceList &L, long long *refused) {
+    L.key.alloc((size_t)NF);
+    DBuf<int> words(3);
+    const int *fe = L.fe = device_view(L.hold_fe, face_elem, (size_t)NF, s);
+    const int *fl = L.fl = device_view(L.hold_fl, face_local, (size_t)NF, s);
+    const int nwords = (int)(((int64_t)NE + 3) / 4);
+    DBuf<unsigned> mask((size_t)nwords);
+    mask.zero(s);
+    const int init[3] = {INT_MAX, 0, 0};
+    SA_HIP_CHECK(hipMemcpyAsync(words.p, init, sizeof(init), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(bdr_check_kernel, grid_flat(NF), dim3(256), 0, s, NF, NE, dim, eI, fe, fl, mask.p, L.key.p, words.p);
+    SA_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(bdr_touched_kernel, grid_flat(nwords), dim3(256), 0, s, nwords, (const unsigned *)mask.p, words.p + 2);
+    SA_HIP_CHECK(hipGetLastError());
+    int w[3];
+    read_back(w, (const int *)words.p, 3, s);
+    if (w[0] < NF) {
+        if (refused) *refused = w[0];
+        const int e = read_one(fe + w[0], s);
+        SA_REQUIRE(false, name + "face " + std::to_string(w[0]) + ": " +
+                              (e < 0 || e >= NE ? "face_elem is outside [0, NE)" : "face_local is outside the element type's range"));
+    }
+    if (w[1]) {      // a pair is listed twice: the first face of the list that is one of a repeated pair, found on the host
+        const hvec<int> he = fetch_host(fe, (size_t)NF, s), hl = fetch_host(fl, (size_t)NF, s);
+        std::vector<std::pair<int64_t, int>> pairs((size_t)NF);
+        for (int f = 0; f < NF; ++f) pairs[(size_t)f] = {(int64_t)he[(size_t)f] * 8 + hl[(size_t)f], f};
+        std::sort(pairs.begin(), pairs.end());
+        int first = NF;
+        for (size_t k = 0; k + 1 < pairs.size(); ++k)
+            if (pairs[k].first == pairs[k + 1].first && (k == 0 || pairs[k - 1].first != pairs[k].first)) first = std::min(first, pairs[k].second);
+        if (refused) *refused = first;
+        SA_REQUIRE(false, name + "face " + std::to_string(first) + ": the same (element, local face) is listed twice");
+    }
+    L.touched = w[2];
+}
 
 void element_matrices(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                       const int *elem_to_vertex, int kind, int ncoef, const double *coef, double *elmat_out, int *dof_ptr_out,
