@@ -540,6 +540,48 @@ int saamge_amd_face_nodes(int NV, int dim, int NE, int nde, const int *elem_ptr,
 int saamge_amd_face_dofs(int NV, int dim, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex, int NF,
                          const int *face_elem, const int *face_local, int vdim, unsigned comp_mask, int flag, void *stream,
                          signed char *bdr_dofs_inout, long long info[4]);
+/* ---- an order-1 mesh lifted to order 2 on the device (csrc/mesh_lift.hip) ----
+ * From an order-1 mesh to the order-2 mesh on the same elements, in the node orders saamge_amd_element_matrices takes: the
+ * 3-node triangle becomes the 6-node, the 4-node quadrilateral the 9-node, the 4-node tetrahedron the 10-node, the 8-node
+ * hexahedron the 27-node one; with elem_ptr one list may mix them.  saamge_amd/mesh_lift_model.py defines every integer and every
+ * coordinate bit and the device gives the same.
+ * Edges: the local edges of a type are the corner pairs (0,1) (1,2) (2,0) of a triangle, (0,1) (1,2) (2,3) (3,0) of a
+ * quadrilateral, (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) of a tetrahedron and the 12 pairs of hexahedron corners that differ in one
+ * reference coordinate.  An edge is the vertex pair a < b and a OWNS it: edge_ptr (NV + 1) counts the owned edges per vertex,
+ * edge_hi (NEd) holds the b of each edge ascending within each owner, so edge k is the k-th pair in ascending (a, b) order.
+ * Node ids: the vertices keep [0, NV), listed by an element or not; edge k is node NV + k; each distinct quadrilateral face of a
+ * hexahedron is node NV + NEd + f, f the rank, in slot order, of its representative slot of the face table of the order-1 mesh
+ * (the lower slot of an interior pair, the slot itself on the boundary), face_slot[f] that slot; the centre of the c-th
+ * quadrilateral (2D) / hexahedron (3D) in element order is node NV + NEd + NFq + c.
+ * Local order: triangle and tetrahedron: the vertices, then the edges in the order above; quadrilateral: the vertices, the edge
+ * nodes, the centre; hexahedron: lexicographic (iz * 3 + iy) * 3 + ix -- a position without a 1 is a corner, with one 1 the edge
+ * between its two corners, with two the local face of its four corners, (1, 1, 1) the centre.
+ * Coordinates (coords NULL: none): vertices are copied; an edge node is 0.5 * (X[a] + X[b]); a face node
+ * 0.25 * ((X[v0] + X[v1]) + (X[v2] + X[v3])) with v0 < v1 < v2 < v3 the face's vertex ids ascending; a quadrilateral's centre
+ * 0.25 * ((c0 + c1) + (c2 + c3)) and a hexahedron's 0.125 * (((c0 + c1) + (c2 + c3)) + ((c4 + c5) + (c6 + c7))) in the element's
+ * local order.  Midside nodes of a curved boundary are the caller's to move in coords2.
+ * info[0] = NV2 = NV + [1] + [2] + [3], [1] = NEd, [2] = NFq, [3] = centre nodes, [4] = entries of elem_to_node, [5] = the most
+ * edges one vertex owns, [6] = -1 or the lowest refused element, [7] = vertices that no element lists.
+ * faces: a handle of saamge_amd_face_table_build on the same order-1 mesh, used only where the mesh has a hexahedron; NULL: the
+ * table is built inside and released before return.  Any input a host or device pointer, each on its own.  NE = 0 is legal.
+ * Refused, before anything touches the device: out NULL, dim not 2 or 3, NV < 0, NE < 0, elem_to_vertex NULL, without elem_ptr an
+ * nde that is no type of the dimension or lists beyond 32 bits, a face table of another number of elements; then what
+ * saamge_amd_face_table_build refuses of the mesh (a vertex id outside [0, NV) before any kernel reads through the ids); then
+ * the lowest element that is a wedge (there is no 18-node type) or of order 2 already; a face table whose slots are not those
+ * of the mesh; a non-manifold mesh with a hexahedron; NV2 beyond 2^31 - 1.  A refusal writes no output and leaves *out untouched.
+ * saamge_amd_mesh_lift_arrays: the device arrays (coords2 NV2 x dim or NULL, elem_ptr2 NE + 1, elem_to_node info[4], edge_ptr
+ * NV + 1, edge_hi NEd, face_slot NFq), valid while the handle lives; any pointer may be NULL.
+ * saamge_amd_mesh_lift_get: blocking copies into host or device buffers; NULL: skipped. */
+typedef struct saamge_amd_mesh_lift saamge_amd_mesh_lift;
+int saamge_amd_mesh_lift_order2(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                const int *elem_to_vertex, const saamge_amd_face_table *faces, void *stream,
+                                saamge_amd_mesh_lift **out, long long info[8]);
+int saamge_amd_mesh_lift_arrays(const saamge_amd_mesh_lift *m, int *NV2, const double **coords2, const int **elem_ptr2,
+                                const int **elem_to_node, const long long **edge_ptr, const int **edge_hi,
+                                const long long **face_slot);
+int saamge_amd_mesh_lift_get(const saamge_amd_mesh_lift *m, int *NV2, double *coords2, int *elem_ptr2, int *elem_to_node,
+                             long long *edge_ptr, int *edge_hi, long long *face_slot);
+void saamge_amd_mesh_lift_free(saamge_amd_mesh_lift *m);
 /* R = P^T (P nrows x ncols) */
 int saamge_amd_csr_transpose(int nrows, int ncols, const int *rowptr, const int *col, const double *val, int *Rrow,
                              long long *Rnnz, int *Rcol, double *Rval);

@@ -528,6 +528,80 @@ private:
     const long long *slot_ptr_, *xadj_;
     const int *nbr_elem_, *nbr_local_, *bdr_elem_, *bdr_local_, *adj_;
 };
+// An order-1 mesh lifted to order 2 on the same elements, owned by the library (saamge_amd_mesh_lift_order2; definitions in
+// saamge_amd.h).  The pointers are device arrays that live as long as this object: coords2() (nullptr without coords),
+// elem_ptr2() and elem_to_node() go to element_matrices_into and its kin and to FaceTable.  faces: the FaceTable of the same
+// order-1 mesh, used where the mesh has a hexahedron; nullptr: built inside.  Movable, not copyable.
+struct MeshLiftInfo {
+    long long nodes, edges, face_nodes, centre_nodes, entries, max_owned_edges, first_bad_element, unlisted_vertices;
+};
+class MeshLift {
+public:
+    MeshLift(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex,
+             const FaceTable *faces = nullptr, void *stream = nullptr)
+        : m_(nullptr), NV_(NV), NE_(NE), dim_(dim), NV2_(0), info_(), coords2_(nullptr), elem_ptr2_(nullptr), elem_to_node_(nullptr),
+          edge_hi_(nullptr), edge_ptr_(nullptr), face_slot_(nullptr) {
+        long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (saamge_amd_mesh_lift_order2(NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, faces ? faces->handle() : nullptr, stream,
+                                        &m_, info))
+            throw std::runtime_error(saamge_amd_last_error());
+        const MeshLiftInfo r = {info[0], info[1], info[2], info[3], info[4], info[5], info[6], info[7]};
+        info_ = r;
+        if (saamge_amd_mesh_lift_arrays(m_, &NV2_, &coords2_, &elem_ptr2_, &elem_to_node_, &edge_ptr_, &edge_hi_, &face_slot_)) {
+            saamge_amd_mesh_lift_free(m_);
+            throw std::runtime_error(saamge_amd_last_error());
+        }
+    }
+    MeshLift(MeshLift &&o) noexcept
+        : m_(o.m_), NV_(o.NV_), NE_(o.NE_), dim_(o.dim_), NV2_(o.NV2_), info_(o.info_), coords2_(o.coords2_), elem_ptr2_(o.elem_ptr2_),
+          elem_to_node_(o.elem_to_node_), edge_hi_(o.edge_hi_), edge_ptr_(o.edge_ptr_), face_slot_(o.face_slot_) {
+        o.m_ = nullptr;
+    }
+    MeshLift &operator=(MeshLift &&o) noexcept {
+        if (this != &o) {
+            saamge_amd_mesh_lift_free(m_);
+            m_ = o.m_; NV_ = o.NV_; NE_ = o.NE_; dim_ = o.dim_; NV2_ = o.NV2_; info_ = o.info_;
+            coords2_ = o.coords2_; elem_ptr2_ = o.elem_ptr2_; elem_to_node_ = o.elem_to_node_; edge_hi_ = o.edge_hi_;
+            edge_ptr_ = o.edge_ptr_; face_slot_ = o.face_slot_;
+            o.m_ = nullptr;
+        }
+        return *this;
+    }
+    MeshLift(const MeshLift &) = delete;
+    MeshLift &operator=(const MeshLift &) = delete;
+    ~MeshLift() { saamge_amd_mesh_lift_free(m_); }
+    int elements() const { return NE_; }
+    int nodes() const { return NV2_; }
+    const MeshLiftInfo &info() const { return info_; }
+    const double *coords2() const { return coords2_; }
+    const int *elem_ptr2() const { return elem_ptr2_; }
+    const int *elem_to_node() const { return elem_to_node_; }
+    const long long *edge_ptr() const { return edge_ptr_; }
+    const int *edge_hi() const { return edge_hi_; }
+    const long long *face_slot() const { return face_slot_; }
+    saamge_amd_mesh_lift *handle() const { return m_; }
+    // host copies; coords2 stays empty where the lift was made without coordinates
+    void get(std::vector<double> &coords2, std::vector<int> &elem_ptr2, std::vector<int> &elem_to_node, std::vector<long long> &edge_ptr,
+             std::vector<int> &edge_hi, std::vector<long long> &face_slot) const {
+        coords2.assign(coords2_ ? (size_t)NV2_ * (size_t)dim_ : 0, 0.0);
+        elem_ptr2.assign((size_t)NE_ + 1, 0);
+        elem_to_node.assign((size_t)info_.entries, 0);
+        edge_ptr.assign((size_t)NV_ + 1, 0);
+        edge_hi.assign((size_t)info_.edges, 0);
+        face_slot.assign((size_t)info_.face_nodes, 0);
+        if (saamge_amd_mesh_lift_get(m_, nullptr, coords2.data(), elem_ptr2.data(), elem_to_node.data(), edge_ptr.data(), edge_hi.data(),
+                                     face_slot.data()))
+            throw std::runtime_error(saamge_amd_last_error());
+    }
+
+private:
+    saamge_amd_mesh_lift *m_;
+    int NV_, NE_, dim_, NV2_;
+    MeshLiftInfo info_;
+    const double *coords2_;
+    const int *elem_ptr2_, *elem_to_node_, *edge_hi_;
+    const long long *edge_ptr_, *face_slot_;
+};
 // the global node ids of the listed faces, in each face's own node order, on the host: face f is nodes[face_ptr[f] ..
 // face_ptr[f + 1]).  The inputs are host or device pointers, each on its own.
 struct FaceNodes {

@@ -44,6 +44,7 @@ SYMBOLS = [
     "saamge_amd_boundary_mass", "saamge_amd_boundary_loads",
     "saamge_amd_face_table_build", "saamge_amd_face_table_arrays", "saamge_amd_face_table_get", "saamge_amd_face_table_free",
     "saamge_amd_face_nodes", "saamge_amd_face_dofs",
+    "saamge_amd_mesh_lift_order2", "saamge_amd_mesh_lift_arrays", "saamge_amd_mesh_lift_get", "saamge_amd_mesh_lift_free",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong))
@@ -1080,6 +1081,98 @@ def face_dofs(NV, dim, elem_to_vertex, face_elem, face_local, bdr_dofs, vdim=1, 
     return _mass_call(lambda: load().saamge_amd_face_dofs(
         C.c_int(NV), C.c_int(int(dim)), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_int(NF), _ptr(fe), _ptr(fl), C.c_int(vdim),
         C.c_uint(int(comp_mask) & 0xffffffff), C.c_int(int(flag)), C.c_void_p(stream), _ptr(bdr_dofs), info), info)
+
+
+class MeshLift(object):
+    """saamge_amd_mesh_lift_order2: an order-1 mesh lifted to order 2 on the same elements -- all node coordinates, the element
+    -> node lists in the node orders `element_matrices` takes (6-node triangle, 9-node quadrilateral, 10-node tetrahedron,
+    27-node hexahedron), and the edge table found on the way -- owned by the library until free() (or the end of a `with`
+    block).  saamge_amd/mesh_lift_model.py defines every integer and every coordinate bit.  coords ((NV, dim), or None: no
+    coordinates, then NV and dim are needed), elem_to_vertex ((NE, nodes), or flat with elem_ptr) and elem_ptr: numpy arrays or
+    device tensors, each on its own.  faces: a `FaceTable` of the same mesh (used where the mesh has a hexahedron), None: built
+    inside.  `.info`: the 8 integers of the call (NV2, edges, face nodes, centre nodes, entries of elem_to_node, the most edges
+    of a vertex, -1, unlisted vertices); a refusal raises RuntimeError with `.info` (info[6]: the lowest refused element)."""
+    NAMES = ("coords2", "elem_ptr2", "elem_to_node", "edge_ptr", "edge_hi", "face_slot")
+
+    def __init__(self, coords, elem_to_vertex, elem_ptr=None, faces=None, NV=None, dim=None, stream=0):
+        coords, e2v, _, ep = _element_arrays(coords, elem_to_vertex, None, elem_ptr)
+        if coords is not None:
+            NV, dim = int(coords.shape[0]), int(coords.shape[1])
+        elif NV is None or dim is None:
+            raise ValueError("without coords, NV and dim are needed")
+        NV, NE, nde = _mesh_sizes(NV, e2v, ep)
+        h = C.c_void_p()
+        info = (C.c_longlong * 8)()
+        self.h = None
+        self.info = _mass_call(lambda: load().saamge_amd_mesh_lift_order2(
+            C.c_int(NV), C.c_int(int(dim)), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v),
+            faces.h if faces is not None else None, C.c_void_p(stream), C.byref(h), info), info)
+        self.h = h
+        self.NV, self.NE, self.dim, self.has_coords = NV, NE, int(dim), coords is not None
+        self.NV2, self.NEd, self.NFq, self.NC, self.entries = self.info[:5]
+
+    @classmethod
+    def build(cls, coords, elem_to_vertex, elem_ptr=None, faces=None, NV=None, dim=None, stream=0):
+        return cls(coords, elem_to_vertex, elem_ptr=elem_ptr, faces=faces, NV=NV, dim=dim, stream=stream)
+
+    def _sizes(self):
+        return {"coords2": self.NV2 * self.dim if self.has_coords else 0, "elem_ptr2": self.NE + 1, "elem_to_node": self.entries,
+                "edge_ptr": self.NV + 1, "edge_hi": self.NEd, "face_slot": self.NFq}
+
+    def arrays(self):
+        """dict of raw device addresses (coords2 -- 0 without coordinates --, elem_ptr2, elem_to_node, edge_ptr, edge_hi,
+        face_slot) and NV2; valid until free().  `pointer(name)` wraps one for the other entry points."""
+        p = [C.c_void_p() for _ in range(6)]
+        NV2 = C.c_int(0)
+        _check(load().saamge_amd_mesh_lift_arrays(self.h, C.byref(NV2), *[C.byref(v) for v in p]))
+        out = {k: int(v.value or 0) for k, v in zip(self.NAMES, p)}
+        out.update(NV2=int(NV2.value))
+        return out
+
+    def pointer(self, name, shape=None):
+        """the handle's device array `name` as an object the wrappers take in place of a device tensor (valid until free());
+        coords2 has the shape (NV2, dim), the others are flat unless `shape` says otherwise (elem_to_node as (NE, nodes) on a
+        mesh of one type)"""
+        dt = {"coords2": np.float64, "edge_ptr": np.int64, "face_slot": np.int64}.get(name, np.int32)
+        d = _DevicePointer(self.arrays()[name], dt)
+        d.shape = tuple(shape) if shape is not None else (self.NV2, self.dim) if name == "coords2" else (self._sizes()[name],)
+        assert int(np.prod(d.shape)) == self._sizes()[name]
+        return d
+
+    def get(self, device=False):
+        """(coords2 float64 (NV2, dim) or None, elem_ptr2 int32, elem_to_node int32 (flat: element e is
+        elem_to_node[elem_ptr2[e]:elem_ptr2[e + 1]], on a mesh of one type too), edge_ptr int64, edge_hi int32, face_slot int64):
+        numpy arrays, or torch tensors on the GPU with device=True."""
+        n = self._sizes()
+        out = [_new_doubles(n["coords2"], device) if self.has_coords else None, _new_ints(n["elem_ptr2"], np.int32, "int32", device),
+               _new_ints(n["elem_to_node"], np.int32, "int32", device), _new_ints(n["edge_ptr"], np.int64, "int64", device),
+               _new_ints(n["edge_hi"], np.int32, "int32", device), _new_ints(n["face_slot"], np.int64, "int64", device)]
+        _check(load().saamge_amd_mesh_lift_get(self.h, None, *[_ptr(a) for a in out]))
+        if self.has_coords:
+            out[0] = out[0].reshape(self.NV2, self.dim)
+        return tuple(out)
+
+    def free(self):
+        if self.h is not None and self.h.value:
+            free = load().saamge_amd_mesh_lift_free
+            free.restype = None
+            free(self.h)
+        self.h = None
+
+    close = free
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+        return False
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 def get_options():

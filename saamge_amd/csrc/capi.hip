@@ -7,6 +7,7 @@
 #include "elmat.h"
 #include "hierarchy.h"
 #include "mesh_faces.h"
+#include "mesh_lift.h"
 #include "operator.h"
 #include "partition.h"
 #include "spgemm.h"
@@ -35,6 +36,9 @@ struct saamge_amd_operator {
 };
 struct saamge_amd_face_table {
     FaceTable t;
+};
+struct saamge_amd_mesh_lift {
+    MeshLift l;
 };
 static OperatorLimits g_operator_limits;      // saamge_amd_operator_set_path_limits (tests)
 
@@ -928,6 +932,57 @@ int saamge_amd_face_dofs(int NV, int dim, int NE, int nde, const int *elem_ptr, 
     face_dofs(s, NV, dim, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, vdim, comp_mask, flag, bdr_dofs_inout, info);
     SA_API_END
 }
+
+// ---- an order-1 mesh lifted to order 2 (mesh_lift.hip) ------------------------------------------------------------------------
+int saamge_amd_mesh_lift_order2(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                const int *elem_to_vertex, const saamge_amd_face_table *faces, void *stream,
+                                saamge_amd_mesh_lift **out, long long info[8]) {
+    SA_API_BEGIN
+    SA_REQUIRE(out, "saamge_amd_mesh_lift_order2: null argument: out");
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    std::unique_ptr<saamge_amd_mesh_lift> P(new saamge_amd_mesh_lift);
+    mesh_lift_order2(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, faces ? &faces->t : nullptr, P->l, info);
+    *out = P.release();
+    SA_API_END
+}
+
+int saamge_amd_mesh_lift_arrays(const saamge_amd_mesh_lift *m, int *NV2, const double **coords2, const int **elem_ptr2,
+                                const int **elem_to_node, const long long **edge_ptr, const int **edge_hi,
+                                const long long **face_slot) {
+    SA_API_BEGIN
+    SA_REQUIRE(m, "saamge_amd_mesh_lift_arrays: null argument");
+    if (NV2) *NV2 = m->l.NV2;
+    if (coords2) *coords2 = m->l.coords2.p;
+    if (elem_ptr2) *elem_ptr2 = m->l.elem_ptr2.p;
+    if (elem_to_node) *elem_to_node = m->l.elem_to_node.p;
+    if (edge_ptr) *edge_ptr = (const long long *)m->l.edge_ptr.p;
+    if (edge_hi) *edge_hi = m->l.edge_hi.p;
+    if (face_slot) *face_slot = (const long long *)m->l.face_slot.p;
+    SA_API_END
+}
+
+int saamge_amd_mesh_lift_get(const saamge_amd_mesh_lift *m, int *NV2, double *coords2, int *elem_ptr2, int *elem_to_node,
+                             long long *edge_ptr, int *edge_hi, long long *face_slot) {
+    SA_API_BEGIN
+    SA_REQUIRE(m, "saamge_amd_mesh_lift_get: null argument");
+    const MeshLift &L = m->l;
+    if (NV2) *NV2 = L.NV2;
+    if (coords2 || elem_ptr2 || elem_to_node || edge_ptr || edge_hi || face_slot)
+        SA_REQUIRE(current_device() == L.device, "the calling thread's current HIP device is not the lifted mesh's device");
+    const auto copy = [](void *dst, const void *src, size_t bytes) {
+        if (dst && bytes) SA_HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyDefault));
+    };
+    copy(coords2, L.coords2.p, L.coords2.n * sizeof(double));
+    copy(elem_ptr2, L.elem_ptr2.p, L.elem_ptr2.n * sizeof(int));
+    copy(elem_to_node, L.elem_to_node.p, L.elem_to_node.n * sizeof(int));
+    copy(edge_ptr, L.edge_ptr.p, L.edge_ptr.n * sizeof(roff_t));
+    copy(edge_hi, L.edge_hi.p, L.edge_hi.n * sizeof(int));
+    copy(face_slot, L.face_slot.p, L.face_slot.n * sizeof(roff_t));
+    SA_API_END
+}
+
+void saamge_amd_mesh_lift_free(saamge_amd_mesh_lift *m) { delete m; }
 
 int saamge_amd_csr_transpose(int nrows, int ncols, const int *rowptr, const int *col, const double *val, int *Rrow,
                              long long *Rnnz, int *Rcol, double *Rval) {
