@@ -582,6 +582,52 @@ int saamge_amd_mesh_lift_arrays(const saamge_amd_mesh_lift *m, int *NV2, const d
 int saamge_amd_mesh_lift_get(const saamge_amd_mesh_lift *m, int *NV2, double *coords2, int *elem_ptr2, int *elem_to_node,
                              long long *edge_ptr, int *edge_hi, long long *face_slot);
 void saamge_amd_mesh_lift_free(saamge_amd_mesh_lift *m);
+/* ---- an order-1 mesh refined uniformly on the device (csrc/mesh_refine.hip) ----
+ * Every triangle and quadrilateral becomes 4, every tetrahedron and hexahedron 8 elements of its own type, `levels` times; with
+ * elem_ptr one list may mix the types.  One step is the lift above plus the children: saamge_amd/mesh_refine_model.py defines
+ * every integer and every coordinate bit and the device gives the same.
+ * GUARANTEED element numbering: child k of element e is element nc * e + k of the next level, nc = 4 in 2D and 8 in 3D.  The
+ * parent of element c is c / nc, its ancestor s levels up is c >> (2 s) in 2D and c >> (3 s) in 3D, and the descendants of one
+ * element are a connected agglomerate: the nested partitions saamge_amd_ml_produce_data takes are arange(NE) >> (2 s | 3 s).
+ * Vertex numbering: the vertex ids of level j + 1 are the node ids of the lift of level j -- the vertices of level j keep their
+ * ids, then come its edges, the quadrilateral faces of its hexahedra, its centres -- and coords of level j + 1 is coords2 of that
+ * lift, bit for bit (coords NULL: none).  New vertices on a curved boundary are the caller's to move.
+ * Children, as indices into the parent's lifted local node list: triangle (0,3,5) (3,1,4) (5,4,2) (3,4,5); quadrilateral and
+ * hexahedron: corner j of child k is the lifted node at reference position LOC[k] + LOC[j], so child k holds the parent's corner
+ * k at its own position k; tetrahedron (0,4,5,6) (4,1,7,8) (5,7,2,9) (6,8,9,3) and the inner octahedron cut along m02 - m13:
+ * (4,5,6,8) (7,5,4,8) (5,6,8,9) (8,7,5,9).  A child has a positive Jacobian determinant where its parent has one.
+ * want_interp != 0 keeps P_0 .. P_{levels-1}: P_j is a CSR matrix (int rowptr, as saamge_amd_spmv, saamge_amd_spgemm and
+ * saamge_amd_csr_transpose take it) with one row per vertex of level j + 1 and one column per vertex of level j, columns
+ * ascending: (v, 1.0) for a kept vertex, (a, 0.5) (b, 0.5) for an edge, the four vertices of a face at 0.25, the four corners of
+ * a quadrilateral at 0.25 or the eight of a hexahedron at 0.125 for a centre.
+ * info[0] = NV of the result, [1] = its NE, [2] = entries of its elem_to_vertex, [3] = levels, [4] = total nnz of the kept P,
+ * [5] = the most edges one vertex owns over all lifted levels, [6] = -1 or the lowest refused element, [7] = vertices that no
+ * element lists.  Any input a host or device pointer, each on its own.  NE = 0 is legal.
+ * Refused: out NULL, levels < 1, levels > 15; then per level what the lift refuses, in its order (at level 0 that is every
+ * refusal of the caller's mesh; later the NV of the next level beyond 2^31 - 1), the vertex list of the next level beyond
+ * 2^31 - 1 entries, with want_interp nnz of P_j beyond 2^31 - 1 -- each before that level is allocated.  A refusal leaves *out
+ * untouched and info = {0, 0, 0, 0, 0, 0, -1 or the element, 0}.  The meshes of the levels between are not kept.
+ * saamge_amd_mesh_refine_arrays: the device arrays of the result (coords NV x dim or NULL, elem_ptr NE + 1 -- always given --,
+ * elem_to_vertex info[2]), valid while the handle lives; any pointer may be NULL.  saamge_amd_mesh_refine_get: blocking copies
+ * into host or device buffers; NULL: skipped.
+ * saamge_amd_mesh_refine_level_info, level in [0, levels]: info[0] = NV, [1] = NE, [2] = entries of the vertex list, [3] = NEd,
+ * [4] = NFq, [5] = centres, [6] = the most edges one vertex owns, [7] = nnz of P_level (0: not kept); the last level was not
+ * lifted, its [3] .. [7] are -1.
+ * saamge_amd_mesh_refine_interp_arrays / _interp_get, level in [0, levels): P_level as device arrays (rowptr nrows + 1, col and
+ * val nnz) / as blocking copies; refused without want_interp. */
+typedef struct saamge_amd_refined_mesh saamge_amd_refined_mesh;
+int saamge_amd_mesh_refine(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex,
+                           int levels, int want_interp, void *stream, saamge_amd_refined_mesh **out, long long info[8]);
+int saamge_amd_mesh_refine_arrays(const saamge_amd_refined_mesh *m, int *NV, int *NE, const double **coords, const int **elem_ptr,
+                                  const int **elem_to_vertex);
+int saamge_amd_mesh_refine_get(const saamge_amd_refined_mesh *m, int *NV, int *NE, double *coords, int *elem_ptr,
+                               int *elem_to_vertex);
+int saamge_amd_mesh_refine_level_info(const saamge_amd_refined_mesh *m, int level, long long info[8]);
+int saamge_amd_mesh_refine_interp_arrays(const saamge_amd_refined_mesh *m, int level, int *nrows, int *ncols, long long *nnz,
+                                         const int **rowptr, const int **col, const double **val);
+int saamge_amd_mesh_refine_interp_get(const saamge_amd_refined_mesh *m, int level, int *nrows, int *ncols, long long *nnz,
+                                      int *rowptr, int *col, double *val);
+void saamge_amd_mesh_refine_free(saamge_amd_refined_mesh *m);
 /* R = P^T (P nrows x ncols) */
 int saamge_amd_csr_transpose(int nrows, int ncols, const int *rowptr, const int *col, const double *val, int *Rrow,
                              long long *Rnnz, int *Rcol, double *Rval);

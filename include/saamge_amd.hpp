@@ -602,6 +602,97 @@ private:
     const int *elem_ptr2_, *elem_to_node_, *edge_hi_;
     const long long *edge_ptr_, *face_slot_;
 };
+// An order-1 mesh refined uniformly `levels` times, owned by the library (saamge_amd_mesh_refine; definitions in saamge_amd.h).
+// The pointers are device arrays that live as long as this object: coords() (nullptr without coords), elem_ptr() and
+// elem_to_vertex() go to element_matrices_into and its kin, to FaceTable and to MeshLift.  Child k of element e is element
+// nc * e + k of the next level (nc = 4 in 2D, 8 in 3D): the ancestor s levels up is c >> (2 s) or c >> (3 s).  Movable, not
+// copyable.
+struct MeshRefineInfo {
+    long long vertices, elements, entries, levels, interp_nnz, max_owned_edges, first_bad_element, unlisted_vertices;
+};
+struct MeshRefineLevelInfo {      // of one level; the last level was not lifted: -1 from `edges` on
+    long long vertices, elements, entries, edges, face_nodes, centre_nodes, max_owned_edges, interp_nnz;
+};
+struct MeshInterp {               // P_level on the host (CSR, columns ascending)
+    int nrows, ncols;
+    std::vector<int> rowptr, col;
+    std::vector<double> val;
+};
+class MeshRefine {
+public:
+    MeshRefine(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex, int levels = 1,
+               bool want_interp = false, void *stream = nullptr)
+        : m_(nullptr), dim_(dim), NV_(0), NE_(0), info_(), coords_(nullptr), elem_ptr_(nullptr), elem_to_vertex_(nullptr) {
+        long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (saamge_amd_mesh_refine(NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, levels, want_interp ? 1 : 0, stream, &m_, info))
+            throw std::runtime_error(saamge_amd_last_error());
+        const MeshRefineInfo r = {info[0], info[1], info[2], info[3], info[4], info[5], info[6], info[7]};
+        info_ = r;
+        if (saamge_amd_mesh_refine_arrays(m_, &NV_, &NE_, &coords_, &elem_ptr_, &elem_to_vertex_)) {
+            saamge_amd_mesh_refine_free(m_);
+            throw std::runtime_error(saamge_amd_last_error());
+        }
+    }
+    MeshRefine(MeshRefine &&o) noexcept
+        : m_(o.m_), dim_(o.dim_), NV_(o.NV_), NE_(o.NE_), info_(o.info_), coords_(o.coords_), elem_ptr_(o.elem_ptr_),
+          elem_to_vertex_(o.elem_to_vertex_) {
+        o.m_ = nullptr;
+    }
+    MeshRefine &operator=(MeshRefine &&o) noexcept {
+        if (this != &o) {
+            saamge_amd_mesh_refine_free(m_);
+            m_ = o.m_; dim_ = o.dim_; NV_ = o.NV_; NE_ = o.NE_; info_ = o.info_;
+            coords_ = o.coords_; elem_ptr_ = o.elem_ptr_; elem_to_vertex_ = o.elem_to_vertex_;
+            o.m_ = nullptr;
+        }
+        return *this;
+    }
+    MeshRefine(const MeshRefine &) = delete;
+    MeshRefine &operator=(const MeshRefine &) = delete;
+    ~MeshRefine() { saamge_amd_mesh_refine_free(m_); }
+    int vertices() const { return NV_; }
+    int elements() const { return NE_; }
+    int levels() const { return (int)info_.levels; }
+    const MeshRefineInfo &info() const { return info_; }
+    const double *coords() const { return coords_; }
+    const int *elem_ptr() const { return elem_ptr_; }
+    const int *elem_to_vertex() const { return elem_to_vertex_; }
+    saamge_amd_refined_mesh *handle() const { return m_; }
+    MeshRefineLevelInfo level_info(int level) const {
+        long long v[8];
+        if (saamge_amd_mesh_refine_level_info(m_, level, v)) throw std::runtime_error(saamge_amd_last_error());
+        const MeshRefineLevelInfo r = {v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]};
+        return r;
+    }
+    // host copies; coords stays empty where the mesh was refined without coordinates
+    void get(std::vector<double> &coords, std::vector<int> &elem_ptr, std::vector<int> &elem_to_vertex) const {
+        coords.assign(coords_ ? (size_t)NV_ * (size_t)dim_ : 0, 0.0);
+        elem_ptr.assign((size_t)NE_ + 1, 0);
+        elem_to_vertex.assign((size_t)info_.entries, 0);
+        if (saamge_amd_mesh_refine_get(m_, nullptr, nullptr, coords.data(), elem_ptr.data(), elem_to_vertex.data()))
+            throw std::runtime_error(saamge_amd_last_error());
+    }
+    // P_level on the host (the mesh was refined with want_interp)
+    MeshInterp interp(int level) const {
+        MeshInterp P;
+        long long nnz = 0;
+        if (saamge_amd_mesh_refine_interp_get(m_, level, &P.nrows, &P.ncols, &nnz, nullptr, nullptr, nullptr))
+            throw std::runtime_error(saamge_amd_last_error());
+        P.rowptr.assign((size_t)P.nrows + 1, 0);
+        P.col.assign((size_t)nnz, 0);
+        P.val.assign((size_t)nnz, 0.0);
+        if (saamge_amd_mesh_refine_interp_get(m_, level, nullptr, nullptr, nullptr, P.rowptr.data(), P.col.data(), P.val.data()))
+            throw std::runtime_error(saamge_amd_last_error());
+        return P;
+    }
+
+private:
+    saamge_amd_refined_mesh *m_;
+    int dim_, NV_, NE_;
+    MeshRefineInfo info_;
+    const double *coords_;
+    const int *elem_ptr_, *elem_to_vertex_;
+};
 // the global node ids of the listed faces, in each face's own node order, on the host: face f is nodes[face_ptr[f] ..
 // face_ptr[f + 1]).  The inputs are host or device pointers, each on its own.
 struct FaceNodes {

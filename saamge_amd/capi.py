@@ -45,6 +45,8 @@ SYMBOLS = [
     "saamge_amd_face_table_build", "saamge_amd_face_table_arrays", "saamge_amd_face_table_get", "saamge_amd_face_table_free",
     "saamge_amd_face_nodes", "saamge_amd_face_dofs",
     "saamge_amd_mesh_lift_order2", "saamge_amd_mesh_lift_arrays", "saamge_amd_mesh_lift_get", "saamge_amd_mesh_lift_free",
+    "saamge_amd_mesh_refine", "saamge_amd_mesh_refine_arrays", "saamge_amd_mesh_refine_get", "saamge_amd_mesh_refine_level_info",
+    "saamge_amd_mesh_refine_interp_arrays", "saamge_amd_mesh_refine_interp_get", "saamge_amd_mesh_refine_free",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong))
@@ -1155,6 +1157,124 @@ class MeshLift(object):
     def free(self):
         if self.h is not None and self.h.value:
             free = load().saamge_amd_mesh_lift_free
+            free.restype = None
+            free(self.h)
+        self.h = None
+
+    close = free
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+        return False
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class MeshRefine(object):
+    """saamge_amd_mesh_refine: an order-1 mesh refined uniformly `levels` times on the device -- every triangle and quadrilateral
+    into 4, every tetrahedron and hexahedron into 8 elements of its own type --, owned by the library until free() (or the end of
+    a `with` block).  saamge_amd/mesh_refine_model.py defines every integer and every coordinate bit.  Child k of element e is
+    element nc * e + k of the next level (nc = 4 | 8): the nested partitions are arange(NE) >> (2 s | 3 s).  coords ((NV, dim), or
+    None: no coordinates, then NV and dim are needed), elem_to_vertex ((NE, nodes), or flat with elem_ptr) and elem_ptr: numpy
+    arrays or device tensors, each on its own.  want_interp: the vertex -> vertex interpolations P_0 .. P_{levels-1} are kept
+    (`interp(level)`).  `.info`: the 8 integers of the call (NV, NE and entries of elem_to_vertex of the result, levels, total nnz
+    of the kept P, the most edges of a vertex, -1, unlisted vertices); a refusal raises RuntimeError with `.info` (info[6]: the
+    lowest refused element)."""
+    NAMES = ("coords", "elem_ptr", "elem_to_vertex")
+
+    def __init__(self, coords, elem_to_vertex, elem_ptr=None, levels=1, want_interp=False, NV=None, dim=None, stream=0):
+        coords, e2v, _, ep = _element_arrays(coords, elem_to_vertex, None, elem_ptr)
+        if coords is not None:
+            NV, dim = int(coords.shape[0]), int(coords.shape[1])
+        elif NV is None or dim is None:
+            raise ValueError("without coords, NV and dim are needed")
+        NV, NE, nde = _mesh_sizes(NV, e2v, ep)
+        h = C.c_void_p()
+        info = (C.c_longlong * 8)()
+        self.h = None
+        self.info = _mass_call(lambda: load().saamge_amd_mesh_refine(
+            C.c_int(NV), C.c_int(int(dim)), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_int(int(levels)),
+            C.c_int(int(bool(want_interp))), C.c_void_p(stream), C.byref(h), info), info)
+        self.h = h
+        self.dim, self.has_coords, self.want_interp = int(dim), coords is not None, bool(want_interp)
+        self.NV, self.NE, self.entries, self.levels = self.info[:4]
+
+    @classmethod
+    def build(cls, coords, elem_to_vertex, elem_ptr=None, levels=1, want_interp=False, NV=None, dim=None, stream=0):
+        return cls(coords, elem_to_vertex, elem_ptr=elem_ptr, levels=levels, want_interp=want_interp, NV=NV, dim=dim, stream=stream)
+
+    def _sizes(self):
+        return {"coords": self.NV * self.dim if self.has_coords else 0, "elem_ptr": self.NE + 1, "elem_to_vertex": self.entries}
+
+    def arrays(self):
+        """dict of raw device addresses (coords -- 0 without coordinates --, elem_ptr, elem_to_vertex) and NV, NE; valid until
+        free().  `pointer(name)` wraps one for the other entry points."""
+        p = [C.c_void_p() for _ in range(3)]
+        NV, NE = C.c_int(0), C.c_int(0)
+        _check(load().saamge_amd_mesh_refine_arrays(self.h, C.byref(NV), C.byref(NE), *[C.byref(v) for v in p]))
+        out = {k: int(v.value or 0) for k, v in zip(self.NAMES, p)}
+        out.update(NV=int(NV.value), NE=int(NE.value))
+        return out
+
+    def pointer(self, name, shape=None):
+        """the handle's device array `name` as an object the wrappers take in place of a device tensor (valid until free());
+        coords has the shape (NV, dim), the others are flat unless `shape` says otherwise (elem_to_vertex as (NE, nodes) on a
+        mesh of one type)"""
+        d = _DevicePointer(self.arrays()[name], np.float64 if name == "coords" else np.int32)
+        d.shape = tuple(shape) if shape is not None else (self.NV, self.dim) if name == "coords" else (self._sizes()[name],)
+        assert int(np.prod(d.shape)) == self._sizes()[name]
+        return d
+
+    def get(self, device=False):
+        """(coords float64 (NV, dim) or None, elem_ptr int32, elem_to_vertex int32 (flat: element c is
+        elem_to_vertex[elem_ptr[c]:elem_ptr[c + 1]], on a mesh of one type too)): numpy arrays, or torch tensors on the GPU with
+        device=True."""
+        n = self._sizes()
+        out = [_new_doubles(n["coords"], device) if self.has_coords else None, _new_ints(n["elem_ptr"], np.int32, "int32", device),
+               _new_ints(n["elem_to_vertex"], np.int32, "int32", device)]
+        _check(load().saamge_amd_mesh_refine_get(self.h, None, None, *[_ptr(a) for a in out]))
+        if self.has_coords:
+            out[0] = out[0].reshape(self.NV, self.dim)
+        return tuple(out)
+
+    def level_info(self, level):
+        """[NV, NE, entries of the vertex list, NEd, NFq, centres, the most edges of a vertex, nnz of P_level] of level `level`
+        in [0, levels]; the last level was not lifted: -1 from NEd on"""
+        info = (C.c_longlong * 8)()
+        _check(load().saamge_amd_mesh_refine_level_info(self.h, C.c_int(int(level)), info))
+        return [int(v) for v in info]
+
+    def interp_arrays(self, level):
+        """P_level as a dict of raw device addresses (rowptr, col, val) and nrows, ncols, nnz; valid until free()"""
+        p = [C.c_void_p() for _ in range(3)]
+        nrows, ncols, nnz = C.c_int(0), C.c_int(0), C.c_longlong(0)
+        _check(load().saamge_amd_mesh_refine_interp_arrays(self.h, C.c_int(int(level)), C.byref(nrows), C.byref(ncols), C.byref(nnz),
+                                                           *[C.byref(v) for v in p]))
+        out = {k: int(v.value or 0) for k, v in zip(("rowptr", "col", "val"), p)}
+        out.update(nrows=int(nrows.value), ncols=int(ncols.value), nnz=int(nnz.value))
+        return out
+
+    def interp(self, level, device=False):
+        """P_level as (nrows, ncols, rowptr int32, col int32, val float64): numpy arrays, or torch tensors on the GPU with
+        device=True"""
+        nrows, ncols, nnz = C.c_int(0), C.c_int(0), C.c_longlong(0)
+        _check(load().saamge_amd_mesh_refine_interp_get(self.h, C.c_int(int(level)), C.byref(nrows), C.byref(ncols), C.byref(nnz),
+                                                        None, None, None))
+        out = [_new_ints(nrows.value + 1, np.int32, "int32", device), _new_ints(nnz.value, np.int32, "int32", device),
+               _new_doubles(nnz.value, device)]
+        _check(load().saamge_amd_mesh_refine_interp_get(self.h, C.c_int(int(level)), None, None, None, *[_ptr(a) for a in out]))
+        return (int(nrows.value), int(ncols.value)) + tuple(out)
+
+    def free(self):
+        if self.h is not None and self.h.value:
+            free = load().saamge_amd_mesh_refine_free
             free.restype = None
             free(self.h)
         self.h = None

@@ -8,6 +8,7 @@
 #include "hierarchy.h"
 #include "mesh_faces.h"
 #include "mesh_lift.h"
+#include "mesh_refine.h"
 #include "operator.h"
 #include "partition.h"
 #include "spgemm.h"
@@ -40,7 +41,10 @@ struct saamge_amd_face_table {
 struct saamge_amd_mesh_lift {
     MeshLift l;
 };
-static OperatorLimits g_operator_limits;      // saamge_amd_operator_set_path_limits (tests)
+struct saamge_amd_refined_mesh {
+    MeshRefine r;
+};
+static OperatorLimits g_operator_limits;     // saamge_amd_operator_set_path_limits (tests)
 
 static std::string g_last_error;
 
@@ -983,6 +987,99 @@ int saamge_amd_mesh_lift_get(const saamge_amd_mesh_lift *m, int *NV2, double *co
 }
 
 void saamge_amd_mesh_lift_free(saamge_amd_mesh_lift *m) { delete m; }
+
+// ---- an order-1 mesh refined uniformly (mesh_refine.hip) ------------------------------------------------------------------------
+int saamge_amd_mesh_refine(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex,
+                           int levels, int want_interp, void *stream, saamge_amd_refined_mesh **out, long long info[8]) {
+    SA_API_BEGIN
+    SA_REQUIRE(out, "saamge_amd_mesh_refine: null argument: out");
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    std::unique_ptr<saamge_amd_refined_mesh> P(new saamge_amd_refined_mesh);
+    mesh_refine(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, levels, want_interp, P->r, info);
+    *out = P.release();
+    SA_API_END
+}
+
+int saamge_amd_mesh_refine_arrays(const saamge_amd_refined_mesh *m, int *NV, int *NE, const double **coords, const int **elem_ptr,
+                                  const int **elem_to_vertex) {
+    SA_API_BEGIN
+    SA_REQUIRE(m, "saamge_amd_mesh_refine_arrays: null argument");
+    if (NV) *NV = m->r.NV;
+    if (NE) *NE = m->r.NE;
+    if (coords) *coords = m->r.coords.p;
+    if (elem_ptr) *elem_ptr = m->r.elem_ptr.p;
+    if (elem_to_vertex) *elem_to_vertex = m->r.elem_to_vertex.p;
+    SA_API_END
+}
+
+int saamge_amd_mesh_refine_get(const saamge_amd_refined_mesh *m, int *NV, int *NE, double *coords, int *elem_ptr,
+                               int *elem_to_vertex) {
+    SA_API_BEGIN
+    SA_REQUIRE(m, "saamge_amd_mesh_refine_get: null argument");
+    const MeshRefine &R = m->r;
+    if (NV) *NV = R.NV;
+    if (NE) *NE = R.NE;
+    if (coords || elem_ptr || elem_to_vertex)
+        SA_REQUIRE(current_device() == R.device, "the calling thread's current HIP device is not the refined mesh's device");
+    const auto copy = [](void *dst, const void *src, size_t bytes) {
+        if (dst && bytes) SA_HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyDefault));
+    };
+    copy(coords, R.coords.p, R.coords.n * sizeof(double));
+    copy(elem_ptr, R.elem_ptr.p, R.elem_ptr.n * sizeof(int));
+    copy(elem_to_vertex, R.elem_to_vertex.p, R.elem_to_vertex.n * sizeof(int));
+    SA_API_END
+}
+
+int saamge_amd_mesh_refine_level_info(const saamge_amd_refined_mesh *m, int level, long long info[8]) {
+    SA_API_BEGIN
+    SA_REQUIRE(m && info, "saamge_amd_mesh_refine_level_info: null argument");
+    SA_REQUIRE(level >= 0 && level <= m->r.levels, "saamge_amd_mesh_refine_level_info: level is outside [0, levels]");
+    const MeshRefineLevel &l = m->r.level[(size_t)level];
+    const long long v[8] = {l.NV, l.NE, l.entries, l.NEd, l.NFq, l.NC, l.max_owned, l.nnz};
+    for (int k = 0; k < 8; ++k) info[k] = v[k];
+    SA_API_END
+}
+
+static const MeshInterp &refine_interp(const saamge_amd_refined_mesh *m, int level, const std::string &name) {
+    SA_REQUIRE(m, name + "null argument");
+    SA_REQUIRE(!m->r.P.empty(), name + "the mesh was refined without want_interp");
+    SA_REQUIRE(level >= 0 && level < m->r.levels, name + "level is outside [0, levels)");
+    return m->r.P[(size_t)level];
+}
+
+int saamge_amd_mesh_refine_interp_arrays(const saamge_amd_refined_mesh *m, int level, int *nrows, int *ncols, long long *nnz,
+                                         const int **rowptr, const int **col, const double **val) {
+    SA_API_BEGIN
+    const MeshInterp &P = refine_interp(m, level, "saamge_amd_mesh_refine_interp_arrays: ");
+    if (nrows) *nrows = P.nrows;
+    if (ncols) *ncols = P.ncols;
+    if (nnz) *nnz = P.nnz;
+    if (rowptr) *rowptr = P.rowptr.p;
+    if (col) *col = P.col.p;
+    if (val) *val = P.val.p;
+    SA_API_END
+}
+
+int saamge_amd_mesh_refine_interp_get(const saamge_amd_refined_mesh *m, int level, int *nrows, int *ncols, long long *nnz,
+                                      int *rowptr, int *col, double *val) {
+    SA_API_BEGIN
+    const MeshInterp &P = refine_interp(m, level, "saamge_amd_mesh_refine_interp_get: ");
+    if (nrows) *nrows = P.nrows;
+    if (ncols) *ncols = P.ncols;
+    if (nnz) *nnz = P.nnz;
+    if (rowptr || col || val)
+        SA_REQUIRE(current_device() == m->r.device, "the calling thread's current HIP device is not the refined mesh's device");
+    const auto copy = [](void *dst, const void *src, size_t bytes) {
+        if (dst && bytes) SA_HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyDefault));
+    };
+    copy(rowptr, P.rowptr.p, P.rowptr.n * sizeof(int));
+    copy(col, P.col.p, P.col.n * sizeof(int));
+    copy(val, P.val.p, P.val.n * sizeof(double));
+    SA_API_END
+}
+
+void saamge_amd_mesh_refine_free(saamge_amd_refined_mesh *m) { delete m; }
 
 int saamge_amd_csr_transpose(int nrows, int ncols, const int *rowptr, const int *col, const double *val, int *Rrow,
                              long long *Rnnz, int *Rcol, double *Rval) {
