@@ -464,6 +464,42 @@ int saamge_amd_element_mass(int NV, int dim, const double *coords, int NE, int n
 int saamge_amd_element_loads(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                              const int *elem_to_vertex, int vdim, const double *coef, const double *src, void *stream,
                              double *elvec_out, long long info[8]);
+/* ---- data at the points of the mass rule (csrc/elmat.hip) ----
+ * The points of an element are those of its type's MASS rule (the rule saamge_amd_element_mass / _loads integrate with), in the
+ * rule's order: point q of element e has the global index qp_ptr[e] + q, qp_ptr NE + 1 offsets of 64 bits, NQ = qp_ptr[NE].
+ * saamge_amd/elmat_model.py (element_points, element_eval, element_loads_points, element_errors) defines every operation and
+ * the device gives the same bits.  The shared arguments, the pointers (host or device, each on its own), the stream and
+ * info[0..4], [7] as for saamge_amd_element_loads; info[5] = NQ, [6] = the first element with a non-positive determinant (-1:
+ * none).  A refusal writes no output.
+ * saamge_amd_element_points: qp_ptr_out (NE + 1), xq_out (NQ x dim) the physical coordinates x_q[i] = sum_a N_a(q) X[a][i], the
+ * nodes ascending; wdet_out (NQ) weight_q * det J_q.  Any of the three may be NULL.
+ * saamge_amd_element_eval: u NV x vdim at the nodes; uq_out (NQ x vdim) sum_a N_a u[a][i]; gradq_out (NQ x vdim x dim), entry
+ * (i, j) the derivative of component i along x_j: r[i][k] = sum_a u[a][i] dN_a[k], then (sum_k r[i][k] C[j][k]) / det with the
+ * cofactors C of the Jacobian, the division last.  Either output may be NULL.
+ * saamge_amd_element_loads_points: fq NQ x vdim, the source AT THE POINTS; coef NE doubles or NULL: 1.  Entry (a, i) is the sum
+ * over the points, ascending from 0.0, of (s fq[q][i]) N_a, s = (w det) coef[e]; elvec_out in the packed layout of
+ * saamge_amd_element_loads (saamge_amd_operator_assemble_rhs takes it), NULL: the checks only.  A coefficient that varies inside
+ * an element is folded into fq by the caller.
+ * saamge_amd_element_errors: u NV x vdim, exq NQ x vdim and exgradq NQ x vdim x dim the exact values / gradients at the points
+ * (either may be NULL); err_out NE x 2: column 0 sum_q wdet_q sum_i (uq_i - exq_i)^2, column 1 the same of the gradients over
+ * (i, j); a column whose exact data is NULL is 0.0.  The entries are SQUARES of the element contributions: the caller sums
+ * them and takes the root -- the library forms no total, so no order of execution enters a result.
+ * Refused, in this order: vdim not 1 or dim, NULL coords / elem_to_vertex; everything saamge_amd_element_loads refuses of the
+ * mesh; NULL u (eval, errors) or NULL fq (loads_points); the first element with a non-positive Jacobian determinant at a point
+ * of the mass rule (info[6]).  The calls with optional outputs are not refused when all of them are NULL: the mesh and the
+ * determinants are checked and info is filled. */
+int saamge_amd_element_points(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                              const int *elem_to_vertex, void *stream, long long *qp_ptr_out, double *xq_out, double *wdet_out,
+                              long long info[8]);
+int saamge_amd_element_eval(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                            const int *elem_to_vertex, int vdim, const double *u, void *stream, double *uq_out, double *gradq_out,
+                            long long info[8]);
+int saamge_amd_element_loads_points(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                    const int *elem_to_vertex, int vdim, const double *coef, const double *fq, void *stream,
+                                    double *elvec_out, long long info[8]);
+int saamge_amd_element_errors(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                              const int *elem_to_vertex, int vdim, const double *u, const double *exq, const double *exgradq,
+                              void *stream, double *err_out, long long info[8]);
 /* ---- boundary forms computed on the device (csrc/elmat.hip) ----
  * The face mass (Robin: (c u, v) over faces) and the face loads (Neumann: (c g, v) over faces) of a list of NF faces, ADDED into
  * the packed matrices / vectors of the owning elements, so that the element matrices still sum to the operator and everything

@@ -368,6 +368,50 @@ inline ElementMatricesInfo element_loads_into(int NV, int dim, const double *coo
     return r;
 }
 
+// == data at the points of the mass rule (saamge_amd_element_points, _eval, _loads_points, _errors) ==
+// Point q of element e has the global index qp_ptr[e] + q; NQ = qp_ptr[NE] comes back in `doubles`.  Into the caller's arrays,
+// each a host or a device pointer; the outputs of points and eval may each be nullptr.  Layouts and operations in saamge_amd.h.
+inline ElementMatricesInfo element_points_into(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                               const int *elem_to_vertex, long long *qp_ptr_out, double *xq_out, double *wdet_out,
+                                               void *stream = nullptr) {
+    long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (saamge_amd_element_points(NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, stream, qp_ptr_out, xq_out, wdet_out, info))
+        throw std::runtime_error(saamge_amd_last_error());
+    const ElementMatricesInfo r = {info[0], info[1], info[2], info[3], info[4], info[5], info[6], info[7]};
+    return r;
+}
+// u: NV x vdim at the nodes; uq_out NQ x vdim, gradq_out NQ x vdim x dim
+inline ElementMatricesInfo element_eval_into(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                             const int *elem_to_vertex, int vdim, const double *u, double *uq_out,
+                                             double *gradq_out, void *stream = nullptr) {
+    long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (saamge_amd_element_eval(NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, u, stream, uq_out, gradq_out, info))
+        throw std::runtime_error(saamge_amd_last_error());
+    const ElementMatricesInfo r = {info[0], info[1], info[2], info[3], info[4], info[5], info[6], info[7]};
+    return r;
+}
+// fq: the source at the points (NQ x vdim); coef == nullptr: 1.  elvec_out: the layout of element_loads_into.
+inline ElementMatricesInfo element_loads_points_into(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                                     const int *elem_to_vertex, int vdim, const double *coef, const double *fq,
+                                                     double *elvec_out, void *stream = nullptr) {
+    long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (saamge_amd_element_loads_points(NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, coef, fq, stream, elvec_out, info))
+        throw std::runtime_error(saamge_amd_last_error());
+    const ElementMatricesInfo r = {info[0], info[1], info[2], info[3], info[4], info[5], info[6], info[7]};
+    return r;
+}
+// err_out NE x 2: the squared L2 error against exq and the squared error of the gradient against exgradq, per element; exact data
+// nullptr: 0.0 in that column.  The caller sums and takes the root.
+inline ElementMatricesInfo element_errors_into(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                               const int *elem_to_vertex, int vdim, const double *u, const double *exq,
+                                               const double *exgradq, double *err_out, void *stream = nullptr) {
+    long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (saamge_amd_element_errors(NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, u, exq, exgradq, stream, err_out, info))
+        throw std::runtime_error(saamge_amd_last_error());
+    const ElementMatricesInfo r = {info[0], info[1], info[2], info[3], info[4], info[5], info[6], info[7]};
+    return r;
+}
+
 // == boundary forms computed on the device (saamge_amd_boundary_mass, saamge_amd_boundary_loads) ==
 // The face mass / face loads of the NF listed faces (element face_elem[f], local face face_local[f]; local faces in
 // saamge_amd.h) added into the caller's packed matrices / vectors, each array a host or a device pointer; nullptr for

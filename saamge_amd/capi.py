@@ -42,6 +42,7 @@ SYMBOLS = [
     "saamge_amd_level_order_info", "saamge_amd_ae_order", "saamge_amd_element_matrices",
     "saamge_amd_element_mass", "saamge_amd_element_loads", "saamge_amd_operator_assemble_rhs",
     "saamge_amd_boundary_mass", "saamge_amd_boundary_loads",
+    "saamge_amd_element_points", "saamge_amd_element_eval", "saamge_amd_element_loads_points", "saamge_amd_element_errors",
     "saamge_amd_face_table_build", "saamge_amd_face_table_arrays", "saamge_amd_face_table_get", "saamge_amd_face_table_free",
     "saamge_amd_face_nodes", "saamge_amd_face_dofs",
     "saamge_amd_mesh_lift_order2", "saamge_amd_mesh_lift_arrays", "saamge_amd_mesh_lift_get", "saamge_amd_mesh_lift_free",
@@ -885,6 +886,101 @@ def element_loads(coords, elem_to_vertex, src, vdim=1, coef=None, elem_ptr=None,
         C.c_int(NV), C.c_int(dim), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_int(vdim), _ptr(coef),
         _ptr(src), C.c_void_p(stream), _ptr(elvec), info), info)
     return elvec.reshape(NE, nde * vdim) if ep is None else elvec
+
+
+# ---- data at the points of the mass rule (elmat_model.element_points / _eval / _loads_points / _errors) ----
+def _num_points(coords, e2v, ep):
+    """NQ: the points of the mass rules of all elements"""
+    from .elmat_model import MASS_NPOINTS
+    dim = int(coords.shape[1])
+    if ep is None:
+        return int(e2v.shape[0]) * MASS_NPOINTS.get((dim, int(e2v.shape[1])), 0)
+    nd = ep[1:] - ep[:-1]
+    nd = nd.cpu().numpy() if hasattr(nd, "data_ptr") else np.asarray(nd)
+    return int(sum(int((nd == k).sum()) * n for (d, k), n in MASS_NPOINTS.items() if d == dim))
+
+
+def _doubles(a):
+    return a if a is None or hasattr(a, "data_ptr") else np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _new_or(out, n, device, want):
+    """the output array of a call: `out`, or new zeros when it is wanted"""
+    if out is not None:
+        return out
+    return _new_doubles(n, device) if want else None
+
+
+def element_points(coords, elem_to_vertex, elem_ptr=None, device=False, want=("qp_ptr", "xq", "wdet"), out=None, stream=0,
+                   sizes_only=False):
+    """saamge_amd_element_points: (qp_ptr (NE + 1,) int64, xq (NQ, dim), wdet (NQ,)) -- the points of every element's mass rule
+    (point q of element e: index qp_ptr[e] + q), their physical coordinates and weight * det there.  want: which of the three
+    are asked for, the others are passed as NULL and come back None; out: a dict of arrays / tensors to write into, by the same
+    names.  device=True: torch tensors on the GPU.  sizes_only: info (8 integers: the type counts in [0..4] and [7], [5] = NQ).
+    A refusal raises RuntimeError with `.info` (info[6]: the first element with a non-positive determinant)."""
+    coords, e2v, _, ep = _element_arrays(coords, elem_to_vertex, None, elem_ptr)
+    NV, dim, NE, nde, _ = _mass_sizes(coords, e2v, ep, 1, False)
+    out = dict(out or {})
+    want = () if sizes_only else tuple(want)
+    NQ = _num_points(coords, e2v, ep)
+    qp = out.get("qp_ptr")
+    if qp is None and "qp_ptr" in want:
+        qp = _new_ints(NE + 1, np.int64, "int64", device)
+    xq = _new_or(out.get("xq"), NQ * dim, device, "xq" in want)
+    wdet = _new_or(out.get("wdet"), NQ, device, "wdet" in want)
+    info = (C.c_longlong * 8)()
+    got = _mass_call(lambda: load().saamge_amd_element_points(
+        C.c_int(NV), C.c_int(dim), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_void_p(stream), _ptr(qp),
+        _ptr(xq), _ptr(wdet), info), info)
+    if sizes_only:
+        return got
+    return qp, None if xq is None else xq.reshape(NQ, dim), wdet
+
+
+def element_eval(coords, elem_to_vertex, u, vdim=1, elem_ptr=None, device=False, want=("uq", "gradq"), out=None, stream=0):
+    """saamge_amd_element_eval: (uq (NQ, vdim), gradq (NQ, vdim, dim)) of the nodal field u, (NV, vdim) or (NV,), at the points of
+    `element_points`; gradq[q, i, j] is the derivative of component i along x_j.  want / out / device / stream as there."""
+    coords, e2v, _, ep = _element_arrays(coords, elem_to_vertex, None, elem_ptr)
+    vdim = int(vdim)
+    NV, dim, NE, nde, _ = _mass_sizes(coords, e2v, ep, vdim, False)
+    out = dict(out or {})
+    NQ = _num_points(coords, e2v, ep)
+    uq = _new_or(out.get("uq"), NQ * vdim, device, "uq" in want)
+    gq = _new_or(out.get("gradq"), NQ * vdim * dim, device, "gradq" in want)
+    info = (C.c_longlong * 8)()
+    _mass_call(lambda: load().saamge_amd_element_eval(
+        C.c_int(NV), C.c_int(dim), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_int(vdim), _ptr(_doubles(u)),
+        C.c_void_p(stream), _ptr(uq), _ptr(gq), info), info)
+    return None if uq is None else uq.reshape(NQ, vdim), None if gq is None else gq.reshape(NQ, vdim, dim)
+
+
+def element_loads_points(coords, elem_to_vertex, fq, vdim=1, coef=None, elem_ptr=None, device=False, out=None, stream=0):
+    """saamge_amd_element_loads_points: the load vectors (c f, v) of a source given AT THE POINTS of `element_points`, fq
+    (NQ, vdim) or (NQ,); coef (NE,), None: 1.  Returns what `element_loads` returns, in its layout."""
+    coords, e2v, coef, ep = _element_arrays(coords, elem_to_vertex, coef, elem_ptr)
+    vdim = int(vdim)
+    NV, dim, NE, nde, doubles = _mass_sizes(coords, e2v, ep, vdim, False)
+    info = (C.c_longlong * 8)()
+    elvec = out if out is not None else _new_doubles(doubles, device)
+    _mass_call(lambda: load().saamge_amd_element_loads_points(
+        C.c_int(NV), C.c_int(dim), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_int(vdim), _ptr(coef),
+        _ptr(_doubles(fq)), C.c_void_p(stream), _ptr(elvec), info), info)
+    return elvec.reshape(NE, nde * vdim) if ep is None else elvec
+
+
+def element_errors(coords, elem_to_vertex, u, exq=None, exgradq=None, vdim=1, elem_ptr=None, device=False, out=None, stream=0):
+    """saamge_amd_element_errors: (NE, 2) -- per element the squared L2 error of the nodal u against exq (NQ, vdim) at the points
+    of `element_points`, and the squared error of its gradient against exgradq (NQ, vdim, dim); None: that column is 0.0.  The
+    caller sums a column and takes the root."""
+    coords, e2v, _, ep = _element_arrays(coords, elem_to_vertex, None, elem_ptr)
+    vdim = int(vdim)
+    NV, dim, NE, nde, _ = _mass_sizes(coords, e2v, ep, vdim, False)
+    info = (C.c_longlong * 8)()
+    err = out if out is not None else _new_doubles(NE * 2, device)
+    _mass_call(lambda: load().saamge_amd_element_errors(
+        C.c_int(NV), C.c_int(dim), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_int(vdim), _ptr(_doubles(u)),
+        _ptr(_doubles(exq)), _ptr(_doubles(exgradq)), C.c_void_p(stream), _ptr(err), info), info)
+    return err.reshape(NE, 2)
 
 
 def _face_arrays(face_elem, face_local, coef):

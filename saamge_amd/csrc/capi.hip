@@ -862,6 +862,46 @@ int saamge_amd_boundary_loads(int NV, int dim, const double *coords, int NE, int
     SA_API_END
 }
 
+int saamge_amd_element_points(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                              const int *elem_to_vertex, void *stream, long long *qp_ptr_out, double *xq_out, double *wdet_out,
+                              long long info[8]) {
+    SA_API_BEGIN
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    element_points(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, qp_ptr_out, xq_out, wdet_out, info);
+    SA_API_END
+}
+
+int saamge_amd_element_eval(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                            const int *elem_to_vertex, int vdim, const double *u, void *stream, double *uq_out, double *gradq_out,
+                            long long info[8]) {
+    SA_API_BEGIN
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    element_eval(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, u, uq_out, gradq_out, info);
+    SA_API_END
+}
+
+int saamge_amd_element_loads_points(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                    const int *elem_to_vertex, int vdim, const double *coef, const double *fq, void *stream,
+                                    double *elvec_out, long long info[8]) {
+    SA_API_BEGIN
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    element_loads_points(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, coef, fq, elvec_out, info);
+    SA_API_END
+}
+
+int saamge_amd_element_errors(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                              const int *elem_to_vertex, int vdim, const double *u, const double *exq, const double *exgradq,
+                              void *stream, double *err_out, long long info[8]) {
+    SA_API_BEGIN
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    element_errors(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, u, exq, exgradq, err_out, info);
+    SA_API_END
+}
+
 // ---- the faces of a mesh (mesh_faces.hip) -----------------------------------------------------------------------------------
 int saamge_amd_face_table_build(int NV, int dim, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex, void *stream,
                                 saamge_amd_face_table **out, long long info[8]) {

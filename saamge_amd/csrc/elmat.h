@@ -34,6 +34,26 @@ void boundary_loads(hipStream_t s, int NV, int dim, const double *coords, int NE
                     const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim, const double *coef,
                     const double *g, double *elvec_inout, long long info[8]);
 
+// Data at the points of the mass rule (elmat_model.element_points / element_eval / element_loads_points / element_errors): point q
+// of element e has the global index qp_ptr[e] + q, NQ = qp_ptr[NE].  Every pointer host or device; a refusal writes no output.
+// The arguments of saamge_amd_element_points: qp_ptr_out (NE + 1), xq_out (NQ x dim), wdet_out (NQ); any of them may be NULL.
+void element_points(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                    const int *elem_to_vertex, long long *qp_ptr_out, double *xq_out, double *wdet_out, long long info[8]);
+// The arguments of saamge_amd_element_eval: the nodal u (NV x vdim) at the points, uq_out (NQ x vdim) and gradq_out
+// (NQ x vdim x dim); either may be NULL.
+void element_eval(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                  const int *elem_to_vertex, int vdim, const double *u, double *uq_out, double *gradq_out, long long info[8]);
+// The arguments of saamge_amd_element_loads_points: the load vectors of fq (NQ x vdim) given at the points, in the layout of
+// element_loads; coef NULL: 1.0.
+void element_loads_points(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                          const int *elem_to_vertex, int vdim, const double *coef, const double *fq, double *elvec_out,
+                          long long info[8]);
+// The arguments of saamge_amd_element_errors: err_out (NE x 2), the squared errors of the nodal u against exq (NQ x vdim) and of
+// its gradient against exgradq (NQ x vdim x dim); exact data NULL: that column is 0.0.
+void element_errors(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                    const int *elem_to_vertex, int vdim, const double *u, const double *exq, const double *exgradq, double *err_out,
+                    long long info[8]);
+
 // A mesh argument brought to the device and checked: what every call of elmat.hip and of mesh_faces.hip starts with.  elem_ptr
 // NULL: NE elements of nde nodes each.  Host arrays are uploaded (the offsets first: they say how much of elem_to_vertex there
 // is), device arrays are used where they are.  Refused with `name` in front or by check_mesh_device: malformed offsets, a vertex

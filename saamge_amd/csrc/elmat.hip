@@ -20,6 +20,10 @@
 // The zeroth-order forms -- mass matrices, with or without a target they are added to, and load vectors of a nodal source --
 // have a kernel family of their own for all nine types (mass_kernel, load_kernel) in em2_kernel's phase structure.
 //
+// Data at the points of the mass rule -- where the points are, a nodal field and its gradient there, the loads of a source given
+// there, the squared errors per element -- has kernels on the first phases of load_kernel with a lane per (element, point,
+// component) after them (qp_points_kernel, qp_eval_kernel, qp_load_kernel, qp_error_kernel).
+//
 // The boundary forms -- the mass and the loads of a list of faces, added into the owning elements' matrices and vectors -- have
 // kernels templated on the face type (bdr_mass_kernel, bdr_load_kernel) and run one pass per local face index.
 #include "elmat.h"
@@ -800,9 +804,10 @@ constexpr int load_epb(int nd) { return nd >= 27 ? 8 : (nd >= 8 ? 16 : 32); }
 // reads ND of them at addresses that differ from lane to lane, which the vector memory path serves a few lanes per clock),
 // sC: c per element, sE: the element of a slot (-1: none); sJ and sD may lie over anything that is written after the barrier
 // that follows.
-template <int DIM, int ND, int EPB>
+// KEEP: the point's cofactors C[i][j] (elmat_model._cofactors) and det go to sP as DIM * DIM + 1 doubles per (element, point).
+template <int DIM, int ND, int EPB, bool KEEP = false>
 __device__ inline void mass_point_phases(const double *sX, const double *sD, const double *sC, const int *sE, double *sJ, double *sS,
-                                         int *bad) {
+                                         int *bad, double *sP = nullptr) {
     constexpr int NQ = MassTable<DIM, ND>::NQ, DD = DIM * DIM;
     const MassTable<DIM, ND> &T = MASS_TABLE<DIM, ND>;
     const int tid = threadIdx.x;
@@ -839,12 +844,32 @@ __device__ inline void mass_point_phases(const double *sX, const double *sD, con
         }
         if constexpr (DIM == 2) {
             det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+            if constexpr (KEEP) {
+                double *P = sP + idx * (DD + 1);
+                P[0] = J[1][1];
+                P[1] = -J[1][0];
+                P[2] = -J[0][1];
+                P[3] = J[0][0];
+            }
         } else {
             const double C00 = J[1][1] * J[2][2] - J[1][2] * J[2][1];
             const double C01 = J[1][2] * J[2][0] - J[1][0] * J[2][2];
             const double C02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
             det = (J[0][0] * C00 + J[0][1] * C01) + J[0][2] * C02;
+            if constexpr (KEEP) {
+                double *P = sP + idx * (DD + 1);
+                P[0] = C00;
+                P[1] = C01;
+                P[2] = C02;
+                P[3] = J[0][2] * J[2][1] - J[0][1] * J[2][2];
+                P[4] = J[0][0] * J[2][2] - J[0][2] * J[2][0];
+                P[5] = J[0][1] * J[2][0] - J[0][0] * J[2][1];
+                P[6] = J[0][1] * J[1][2] - J[0][2] * J[1][1];
+                P[7] = J[0][2] * J[1][0] - J[0][0] * J[1][2];
+                P[8] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+            }
         }
+        if constexpr (KEEP) sP[idx * (DD + 1) + DD] = det;
         if (!(det > 0.0) && sE[el] >= 0) atomicMin(bad, sE[el]);
         sS[idx] = (T.w[q] * det) * sC[el];
     }
@@ -969,6 +994,26 @@ __global__ __launch_bounds__(MASS_BLOCK) void mass_kernel(int count, const int *
     }
 }
 
+// the last phase of the load kernels: sQ holds s * fq per (element, point, component)
+template <int ND, int VDIM, int EPB, int NQ>
+__device__ inline void load_dof_phase(const int *__restrict__ eI, const int *sE, const double *sQ, const double *sN,
+                                      double *__restrict__ out) {
+    for (int idx = threadIdx.x; idx < EPB * ND * VDIM; idx += MASS_BLOCK) {
+        const int el = idx / (ND * VDIM), r = idx - el * (ND * VDIM), a = r / VDIM, i = r - a * VDIM;
+        const int e = sE[el];
+        if (e < 0) continue;
+        const double *Q = sQ + el * NQ * VDIM + i;
+        double acc = 0.0;
+#pragma unroll 1
+        for (int q = 0; q < NQ; ++q) {
+            const double term = Q[q * VDIM] * sN[q * ND + a];
+            acc = acc + term;
+        }
+        const long vb = eI ? (long)eI[e] : (long)e * ND;
+        out[vb * VDIM + r] = acc;
+    }
+}
+
 // The load vectors: element e's ND * VDIM doubles at VDIM * (its offset in the vertex lists).  Phases:
 //   stage, J, point   above; the nodal source of the element's nodes is staged with the coordinates
 //   source  one lane per (element, point, component): fq = sum over the nodes, ascending, of N_c * src_c; s * fq is kept
@@ -1001,20 +1046,221 @@ __global__ __launch_bounds__(MASS_BLOCK) void load_kernel(int count, const int *
         sQ[idx] = sS[el * NQ + q] * fq;
     }
     __syncthreads();
-    // ---- dof
-    for (int idx = tid; idx < EPB * ND * VDIM; idx += BLOCK) {
-        const int el = idx / (ND * VDIM), r = idx - el * (ND * VDIM), a = r / VDIM, i = r - a * VDIM;
-        const int e = sE[el];
+    load_dof_phase<ND, VDIM, EPB, NQ>(eI, sE, sQ, sN, out);
+}
+
+// ---- data at the points of the mass rule --------------------------------------------------------------------------------------
+// elmat_model.py's element_points / element_eval / element_loads_points / element_errors.  Point q of element e has the global
+// index qoff[e] + q (qoff: NE + 1 offsets, 64 bits).  The kernels are load_kernel's: stage, J and point as above (the rules are
+// MASS_TABLE's, nothing is restated), then ONE LANE PER (element, point, component) -- the outputs are point-major, and the
+// points of the consecutive elements of a workgroup are consecutive in them, so consecutive lanes store consecutive doubles (a
+// lane per element would store NQ * DIM doubles apart).  No lane adds to what another lane wrote and no total is formed.
+// Elements per workgroup: load_kernel's, except the order-2 hexahedron, where eval and errors keep the cofactors of 27 points per
+// element too (qp_load_kernel keeps none and takes load_epb).
+constexpr int qp_epb(int nd) { return nd >= 27 ? 4 : load_epb(nd); }
+
+// uq = sum over the nodes, ascending, of N_a * f_a and, GRAD, g[j] = (r[0] * C[j][0] + r[1] * C[j][1] (+ r[2] * C[j][2])) / det
+// with r[k] = sum over the nodes, ascending, of f_a * dN_a[k].  F: the component's nodal values (stride VDIM), N: the point's
+// shape values, D: the point's reference gradients (node stride NQ * DIM), P: the point's cofactors and det.
+template <int DIM, int ND, int VDIM, bool GRAD>
+__device__ inline void qp_value(const double *F, const double *N, const double *D, const double *P, double &uq, double g[DIM]) {
+    constexpr int NQ = MassTable<DIM, ND>::NQ, DD = DIM * DIM;
+    double r[DIM];
+    uq = N[0] * F[0];
+    if constexpr (GRAD) {
+#pragma unroll
+        for (int k = 0; k < DIM; ++k) r[k] = F[0] * D[k];
+    }
+    for (int a = 1; a < ND; ++a) {
+        const double f = F[a * VDIM];
+        uq = uq + N[a] * f;
+        if constexpr (GRAD) {
+#pragma unroll
+            for (int k = 0; k < DIM; ++k) r[k] = r[k] + f * D[a * NQ * DIM + k];
+        }
+    }
+    if constexpr (GRAD) {
+        const double det = P[DD];
+#pragma unroll
+        for (int j = 0; j < DIM; ++j) {
+            double t = r[0] * P[j * DIM + 0] + r[1] * P[j * DIM + 1];
+            if constexpr (DIM == 3) t = t + r[2] * P[j * DIM + 2];
+            g[j] = t / det;
+        }
+    }
+}
+
+// the points: xq (NQ x DIM) and wdet (NQ); either may be nullptr
+template <int DIM, int ND>
+__global__ __launch_bounds__(MASS_BLOCK) void qp_points_kernel(int count, const int *__restrict__ list, const int *__restrict__ eI,
+                                                               const int *__restrict__ eJ, const roff_t *__restrict__ qoff,
+                                                               const double *__restrict__ coords, double *__restrict__ xq,
+                                                               double *__restrict__ wdet, int *__restrict__ bad) {
+    constexpr int BLOCK = MASS_BLOCK, EPB = qp_epb(ND), NQ = MassTable<DIM, ND>::NQ, DD = DIM * DIM;
+    __shared__ double sX[EPB * ND * DIM];
+    __shared__ double sN[NQ * ND];
+    __shared__ double sS[EPB * NQ];
+    __shared__ double sC[EPB];
+    __shared__ double sJ[ND <= 8 ? 1 : EPB * NQ * DD];
+    __shared__ double sD[ND * NQ * DIM];
+    __shared__ roff_t sO[EPB];
+    __shared__ int sE[EPB];
+    const int tid = threadIdx.x;
+    mass_stage<DIM, ND, 1, EPB>(count, list, eI, eJ, coords, nullptr, nullptr, sX, sC, sE, sN, sD, nullptr);
+    if (tid < EPB) sO[tid] = sE[tid] < 0 ? 0 : qoff[sE[tid]];
+    mass_point_phases<DIM, ND, EPB>(sX, sD, sC, sE, sJ, sS, bad);      // (the coefficient is 1.0: s = weight * det)
+    if (wdet) {
+        for (int idx = tid; idx < EPB * NQ; idx += BLOCK) {
+            const int el = idx / NQ;
+            if (sE[el] >= 0) wdet[sO[el] + (idx - el * NQ)] = sS[idx];
+        }
+    }
+    if (xq) {
+        for (int idx = tid; idx < EPB * NQ * DIM; idx += BLOCK) {
+            const int el = idx / (NQ * DIM), r = idx - el * (NQ * DIM), q = r / DIM, i = r - q * DIM;
+            if (sE[el] < 0) continue;
+            double x, unused[DIM];
+            qp_value<DIM, ND, DIM, false>(sX + el * ND * DIM + i, sN + q * ND, nullptr, nullptr, x, unused);
+            xq[sO[el] * DIM + r] = x;
+        }
+    }
+}
+
+// the nodal u (NV x VDIM) at the points: uq (NQ x VDIM) and gradq (NQ x VDIM x DIM); either may be nullptr
+template <int DIM, int ND, int VDIM>
+__global__ __launch_bounds__(MASS_BLOCK) void qp_eval_kernel(int count, const int *__restrict__ list, const int *__restrict__ eI,
+                                                             const int *__restrict__ eJ, const roff_t *__restrict__ qoff,
+                                                             const double *__restrict__ coords, const double *__restrict__ u,
+                                                             double *__restrict__ uq, double *__restrict__ gradq,
+                                                             int *__restrict__ bad) {
+    constexpr int BLOCK = MASS_BLOCK, EPB = qp_epb(ND), NQ = MassTable<DIM, ND>::NQ, DD = DIM * DIM, PW = DD + 1;
+    __shared__ double sX[EPB * ND * DIM];
+    __shared__ double sF[EPB * ND * VDIM];
+    __shared__ double sN[NQ * ND];
+    __shared__ double sS[EPB * NQ];
+    __shared__ double sC[EPB];
+    __shared__ double sJ[ND <= 8 ? 1 : EPB * NQ * DD];
+    __shared__ double sD[ND * NQ * DIM];
+    __shared__ double sP[EPB * NQ * PW];
+    __shared__ roff_t sO[EPB];
+    __shared__ int sE[EPB];
+    const int tid = threadIdx.x;
+    mass_stage<DIM, ND, VDIM, EPB>(count, list, eI, eJ, coords, nullptr, u, sX, sC, sE, sN, sD, sF);
+    if (tid < EPB) sO[tid] = sE[tid] < 0 ? 0 : qoff[sE[tid]];
+    mass_point_phases<DIM, ND, EPB, true>(sX, sD, sC, sE, sJ, sS, bad, sP);
+    for (int idx = tid; idx < EPB * NQ * VDIM; idx += BLOCK) {
+        const int el = idx / (NQ * VDIM), r = idx - el * (NQ * VDIM), q = r / VDIM, i = r - q * VDIM;
+        if (sE[el] < 0) continue;
+        const double *F = sF + el * ND * VDIM + i, *N = sN + q * ND, *D = sD + q * DIM, *P = sP + (el * NQ + q) * PW;
+        const roff_t at = sO[el] * VDIM + r;
+        double v, g[DIM];
+        if (gradq) {
+            qp_value<DIM, ND, VDIM, true>(F, N, D, P, v, g);
+#pragma unroll
+            for (int j = 0; j < DIM; ++j) gradq[at * DIM + j] = g[j];
+        } else {
+            qp_value<DIM, ND, VDIM, false>(F, N, D, P, v, g);
+        }
+        if (uq) uq[at] = v;
+    }
+}
+
+// the load vectors of fq (NQ x VDIM) given at the points: load_kernel with the source read where load_kernel interpolates it
+template <int DIM, int ND, int VDIM>
+__global__ __launch_bounds__(MASS_BLOCK) void qp_load_kernel(int count, const int *__restrict__ list, const int *__restrict__ eI,
+                                                             const int *__restrict__ eJ, const roff_t *__restrict__ qoff,
+                                                             const double *__restrict__ coords, const double *__restrict__ coef,
+                                                             const double *__restrict__ fq, double *__restrict__ out,
+                                                             int *__restrict__ bad) {
+    constexpr int BLOCK = MASS_BLOCK, EPB = load_epb(ND), NQ = MassTable<DIM, ND>::NQ, DD = DIM * DIM;
+    __shared__ double sX[EPB * ND * DIM];
+    __shared__ double sN[NQ * ND];
+    __shared__ double sS[EPB * NQ];
+    __shared__ double sC[EPB];
+    __shared__ double sJ[ND <= 8 ? 1 : EPB * NQ * DD];
+    __shared__ double sD[ND * NQ * DIM];
+    __shared__ double sQ[EPB * NQ * VDIM];
+    __shared__ roff_t sO[EPB];
+    __shared__ int sE[EPB];
+    const int tid = threadIdx.x;
+    mass_stage<DIM, ND, 1, EPB>(count, list, eI, eJ, coords, coef, nullptr, sX, sC, sE, sN, sD, nullptr);
+    if (tid < EPB) sO[tid] = sE[tid] < 0 ? 0 : qoff[sE[tid]];
+    mass_point_phases<DIM, ND, EPB>(sX, sD, sC, sE, sJ, sS, bad);
+    // ---- source
+    for (int idx = tid; idx < EPB * NQ * VDIM; idx += BLOCK) {
+        const int el = idx / (NQ * VDIM), r = idx - el * (NQ * VDIM);
+        sQ[idx] = sE[el] < 0 ? 0.0 : sS[el * NQ + r / VDIM] * fq[sO[el] * VDIM + r];
+    }
+    __syncthreads();
+    load_dof_phase<ND, VDIM, EPB, NQ>(eI, sE, sQ, sN, out);
+}
+
+// the squared errors of the nodal u per element: err[e][0] against exq (NQ x VDIM), err[e][1] of the gradient against exgradq
+// (NQ x VDIM x DIM); exact data nullptr: 0.0.  After stage, J and point:
+//   point   one lane per (element, point): the components in ascending order, wdet * d to LDS
+//   sum     one lane per (element, column): the whole sum over the points, in ascending order, lives in the lane
+template <int DIM, int ND, int VDIM>
+__global__ __launch_bounds__(MASS_BLOCK) void qp_error_kernel(int count, const int *__restrict__ list, const int *__restrict__ eI,
+                                                              const int *__restrict__ eJ, const roff_t *__restrict__ qoff,
+                                                              const double *__restrict__ coords, const double *__restrict__ u,
+                                                              const double *__restrict__ exq, const double *__restrict__ exgradq,
+                                                              double *__restrict__ err, int *__restrict__ bad) {
+    constexpr int BLOCK = MASS_BLOCK, EPB = qp_epb(ND), NQ = MassTable<DIM, ND>::NQ, DD = DIM * DIM, PW = DD + 1;
+    __shared__ double sX[EPB * ND * DIM];
+    __shared__ double sF[EPB * ND * VDIM];
+    __shared__ double sN[NQ * ND];
+    __shared__ double sS[EPB * NQ];
+    __shared__ double sC[EPB];
+    __shared__ double sJ[ND <= 8 ? 1 : EPB * NQ * DD];
+    __shared__ double sD[ND * NQ * DIM];
+    __shared__ double sP[EPB * NQ * PW];
+    __shared__ double sQ[EPB * NQ * 2];
+    __shared__ roff_t sO[EPB];
+    __shared__ int sE[EPB];
+    const int tid = threadIdx.x;
+    mass_stage<DIM, ND, VDIM, EPB>(count, list, eI, eJ, coords, nullptr, u, sX, sC, sE, sN, sD, sF);
+    if (tid < EPB) sO[tid] = sE[tid] < 0 ? 0 : qoff[sE[tid]];
+    mass_point_phases<DIM, ND, EPB, true>(sX, sD, sC, sE, sJ, sS, bad, sP);
+    // ---- point
+    for (int idx = tid; idx < EPB * NQ; idx += BLOCK) {
+        const int el = idx / NQ, q = idx - el * NQ;
+        double d0 = 0.0, d1 = 0.0;
+        if (sE[el] >= 0) {
+            const roff_t at = (sO[el] + q) * VDIM;
+            for (int i = 0; i < VDIM; ++i) {
+                const double *F = sF + el * ND * VDIM + i, *N = sN + q * ND, *D = sD + q * DIM, *P = sP + idx * PW;
+                double v, g[DIM];
+                if (exgradq) {
+                    qp_value<DIM, ND, VDIM, true>(F, N, D, P, v, g);
+#pragma unroll
+                    for (int j = 0; j < DIM; ++j) {
+                        const double d = g[j] - exgradq[(at + i) * DIM + j];
+                        const double dd = d * d;
+                        d1 = i + j ? d1 + dd : dd;
+                    }
+                } else {
+                    qp_value<DIM, ND, VDIM, false>(F, N, D, P, v, g);
+                }
+                if (exq) {
+                    const double d = v - exq[at + i];
+                    const double dd = d * d;
+                    d0 = i ? d0 + dd : dd;
+                }
+            }
+        }
+        sQ[idx * 2] = exq ? sS[idx] * d0 : 0.0;
+        sQ[idx * 2 + 1] = exgradq ? sS[idx] * d1 : 0.0;
+    }
+    __syncthreads();
+    // ---- sum
+    for (int idx = tid; idx < EPB * 2; idx += BLOCK) {
+        const int el = idx >> 1, e = sE[el];
         if (e < 0) continue;
-        const double *Q = sQ + el * NQ * VDIM + i;
+        const double *Q = sQ + el * NQ * 2 + (idx & 1);
         double acc = 0.0;
 #pragma unroll 1
-        for (int q = 0; q < NQ; ++q) {
-            const double term = Q[q * VDIM] * sN[q * ND + a];
-            acc = acc + term;
-        }
-        const long vb = eI ? (long)eI[e] : (long)e * ND;
-        out[vb * VDIM + r] = acc;
+        for (int q = 0; q < NQ; ++q) acc = acc + Q[q * 2];
+        err[(long)e * 2 + (idx & 1)] = acc;
     }
 }
 
@@ -1480,6 +1726,161 @@ void mass_or_loads(hipStream_t s, const std::string &name, int NV, int dim, cons
     SA_HIP_CHECK(hipStreamSynchronize(s));
 }
 
+// ---- data at the points of the mass rule --------------------------------------------------------------------------------------
+// the number of points of every element (its type has been checked)
+__global__ __launch_bounds__(256) void qp_count_kernel(int NE, int dim, const int *__restrict__ eI, int *__restrict__ cnt) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e < NE) cnt[e] = mass_points(dim, eI[e + 1] - eI[e]);
+}
+__global__ __launch_bounds__(256) void qp_offsets_kernel(int NE, int nq, roff_t *__restrict__ qoff) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e <= NE) qoff[e] = (roff_t)e * nq;
+}
+
+enum QpCall { QP_POINTS, QP_EVAL, QP_LOADS, QP_ERRORS };
+struct QpLaunch {
+    EmLaunch L;               // (coef: of QP_LOADS; out: its vectors)
+    const roff_t *qoff;
+    const double *in;         // u (QP_EVAL, QP_ERRORS) or fq (QP_LOADS)
+    const double *exq, *exgradq;
+    double *a, *b;            // xq, wdet / uq, gradq / -, - / err, -
+};
+template <int DIM, int ND, int VDIM>
+void qp_launch(QpCall call, const QpLaunch &Q, int count, const int *list) {
+    const EmLaunch &L = Q.L;
+    const dim3 grid((unsigned)div_up(count, call == QP_LOADS ? load_epb(ND) : qp_epb(ND))), block(MASS_BLOCK);
+    if (call == QP_POINTS)
+        hipLaunchKernelGGL((qp_points_kernel<DIM, ND>), grid, block, 0, L.s, count, list, L.eI, L.eJ, Q.qoff, L.coords, Q.a, Q.b, L.bad);
+    else if (call == QP_EVAL)
+        hipLaunchKernelGGL((qp_eval_kernel<DIM, ND, VDIM>), grid, block, 0, L.s, count, list, L.eI, L.eJ, Q.qoff, L.coords, Q.in, Q.a,
+                           Q.b, L.bad);
+    else if (call == QP_LOADS)
+        hipLaunchKernelGGL((qp_load_kernel<DIM, ND, VDIM>), grid, block, 0, L.s, count, list, L.eI, L.eJ, Q.qoff, L.coords, L.coef, Q.in,
+                           L.out, L.bad);
+    else
+        hipLaunchKernelGGL((qp_error_kernel<DIM, ND, VDIM>), grid, block, 0, L.s, count, list, L.eI, L.eJ, Q.qoff, L.coords, Q.in, Q.exq,
+                           Q.exgradq, Q.a, L.bad);
+    SA_HIP_CHECK(hipGetLastError());
+}
+void qp_launch_type(QpCall call, const QpLaunch &Q, int type, int vdim, int count, const int *list) {
+#define SA_QP_CASE(T, DIM, ND)                                                  \
+    case T:                                                                     \
+        if (vdim == 1) qp_launch<DIM, ND, 1>(call, Q, count, list);             \
+        else qp_launch<DIM, ND, DIM>(call, Q, count, list);                     \
+        break;
+    switch (type) {
+        SA_QP_CASE(0, 2, 3)
+        SA_QP_CASE(1, 2, 4)
+        SA_QP_CASE(2, 3, 4)
+        SA_QP_CASE(3, 3, 6)
+        SA_QP_CASE(4, 3, 8)
+        SA_QP_CASE(5, 2, 9)
+        SA_QP_CASE(6, 3, 27)
+        SA_QP_CASE(7, 2, 6)
+        default: SA_QP_CASE(8, 3, 10)
+    }
+#undef SA_QP_CASE
+}
+
+// an output of `n` doubles that may be a host pointer: the kernels write to dev(), finish() copies it home
+struct QpOut {
+    double *user = nullptr;
+    DBuf<double> hold;
+    size_t n = 0;
+    double *dev(double *p, size_t count) {
+        user = p;
+        n = count;
+        if (!p || is_device_ptr(p)) return p;
+        hold.alloc(count);
+        return hold.p;
+    }
+    void finish(hipStream_t s) {
+        if (hold.p && n) SA_HIP_CHECK(hipMemcpyAsync(user, hold.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+};
+
+// The four calls on data at the points, the arguments the C ABI names.  A refusal writes no output: the determinants of the
+// whole mesh are checked (mass_kernel without an output) before the first kernel that writes.
+void points_call(QpCall call, hipStream_t s, const std::string &name, int NV, int dim, const double *coords, int NE, int nde,
+                 const int *elem_ptr, const int *elem_to_vertex, int vdim, const double *coef, const double *in, const char *in_name,
+                 const double *exq, const double *exgradq, long long *qp_ptr_out, double *out_a, double *out_b, long long info[8]) {
+    em_begin(name, NV, dim, NE, info);
+    SA_REQUIRE(vdim == 1 || vdim == dim, name + "vdim must be 1 or dim");
+    SA_REQUIRE(NE == 0 || (coords && elem_to_vertex), name + "null argument: coords or elem_to_vertex");
+    em_check_sizes(name, NV, dim, NE, nde, elem_ptr, vdim);
+    EmMesh M;
+    if (NE) em_mesh(s, name, NV, dim, NE, nde, elem_ptr, elem_to_vertex, vdim, false, M, info);
+    if (info) info[5] = 0;
+    SA_REQUIRE(call == QP_POINTS || in, name + "null argument: " + in_name);
+    if (NE == 0) {
+        const long long zero = 0;
+        if (qp_ptr_out) SA_HIP_CHECK(hipMemcpyAsync(qp_ptr_out, &zero, sizeof(zero), hipMemcpyDefault, s));
+        SA_HIP_CHECK(hipStreamSynchronize(s));
+        return;
+    }
+    // ---- the offsets of the points
+    DBuf<roff_t> qoff((size_t)NE + 1);
+    int64_t NQ;
+    if (elem_ptr) {
+        DBuf<int> cnt((size_t)NE);
+        hipLaunchKernelGGL(qp_count_kernel, grid_flat(NE), dim3(256), 0, s, NE, dim, M.eI, cnt.p);
+        SA_HIP_CHECK(hipGetLastError());
+        exclusive_scan_off(s, NE, cnt.p, qoff.p);
+        NQ = read_one(qoff.p + NE, s);
+    } else {
+        const int nq = mass_points(dim, nde);
+        hipLaunchKernelGGL(qp_offsets_kernel, grid_flat((long)NE + 1), dim3(256), 0, s, NE, nq, qoff.p);
+        SA_HIP_CHECK(hipGetLastError());
+        NQ = (int64_t)NE * nq;
+    }
+    if (info) info[5] = (long long)NQ;
+    // ---- the determinants, before anything is written
+    DBuf<double> hold_X, hold_c, hold_in, hold_e, hold_g;
+    QpLaunch Q;
+    EmLaunch &L = Q.L;
+    L.s = s;
+    L.eI = elem_ptr ? M.eI : nullptr;
+    L.eJ = M.eJ;
+    L.moff = nullptr;
+    L.coords = device_view(hold_X, coords, (size_t)NV * dim, s);
+    L.coef = nullptr;
+    L.ncoef = 1;
+    L.out = nullptr;
+    L.bad = M.word.p;
+    SA_HIP_CHECK(hipMemsetAsync(M.word.p, 0x7f, sizeof(int), s));
+    for (int t = 0; t < EM_TYPES; ++t)
+        if (M.count[t]) mass_launch_type(L, t, 1, 0, nullptr, M.count[t], M.list[t].p);
+    em_refuse_bad(s, name, M, NE, info);
+    // ---- the call
+    QpOut oa, ob;
+    const size_t nq = (size_t)NQ;
+    Q.qoff = qoff.p;
+    Q.in = in ? device_view(hold_in, in, call == QP_LOADS ? nq * vdim : (size_t)NV * vdim, s) : nullptr;
+    Q.exq = exq ? device_view(hold_e, exq, nq * vdim, s) : nullptr;
+    Q.exgradq = exgradq ? device_view(hold_g, exgradq, nq * vdim * dim, s) : nullptr;
+    Q.a = Q.b = nullptr;
+    if (call == QP_POINTS) {
+        Q.a = oa.dev(out_a, nq * dim);
+        Q.b = ob.dev(out_b, nq);
+    } else if (call == QP_EVAL) {
+        Q.a = oa.dev(out_a, nq * vdim);
+        Q.b = ob.dev(out_b, nq * vdim * dim);
+    } else if (call == QP_LOADS) {
+        L.coef = coef ? device_view(hold_c, coef, (size_t)NE, s) : nullptr;
+        L.out = oa.dev(out_a, (size_t)M.doubles);
+    } else {
+        Q.a = oa.dev(out_a, (size_t)NE * 2);
+    }
+    if (Q.a || Q.b || L.out) {
+        for (int t = 0; t < EM_TYPES; ++t)
+            if (M.count[t]) qp_launch_type(call, Q, t, vdim, M.count[t], M.list[t].p);
+    }
+    oa.finish(s);
+    ob.finish(s);
+    if (qp_ptr_out) SA_HIP_CHECK(hipMemcpyAsync(qp_ptr_out, qoff.p, ((size_t)NE + 1) * sizeof(roff_t), hipMemcpyDefault, s));
+    SA_HIP_CHECK(hipStreamSynchronize(s));
+}
+
 // ---- boundary forms ---------------------------------------------------------------------------------------------------------
 struct BdrLaunch {
     hipStream_t s;
@@ -1765,6 +2166,32 @@ void boundary_loads(hipStream_t s, int NV, int dim, const double *coords, int NE
     SA_REQUIRE(g, name + "null argument: g");
     boundary_forms(s, name, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, vdim, coef, g,
                    elvec_inout, info);
+}
+
+void element_points(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                    const int *elem_to_vertex, long long *qp_ptr_out, double *xq_out, double *wdet_out, long long info[8]) {
+    points_call(QP_POINTS, s, "saamge_amd_element_points: ", NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, 1, nullptr, nullptr,
+                "", nullptr, nullptr, qp_ptr_out, xq_out, wdet_out, info);
+}
+
+void element_eval(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                  const int *elem_to_vertex, int vdim, const double *u, double *uq_out, double *gradq_out, long long info[8]) {
+    points_call(QP_EVAL, s, "saamge_amd_element_eval: ", NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, nullptr, u, "u",
+                nullptr, nullptr, nullptr, uq_out, gradq_out, info);
+}
+
+void element_loads_points(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                          const int *elem_to_vertex, int vdim, const double *coef, const double *fq, double *elvec_out,
+                          long long info[8]) {
+    points_call(QP_LOADS, s, "saamge_amd_element_loads_points: ", NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, coef, fq,
+                "fq", nullptr, nullptr, nullptr, elvec_out, nullptr, info);
+}
+
+void element_errors(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                    const int *elem_to_vertex, int vdim, const double *u, const double *exq, const double *exgradq, double *err_out,
+                    long long info[8]) {
+    points_call(QP_ERRORS, s, "saamge_amd_element_errors: ", NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, nullptr, u, "u",
+                exq, exgradq, nullptr, err_out, nullptr, info);
 }
 
 }  // namespace saamge_amd

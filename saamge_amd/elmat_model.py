@@ -45,6 +45,9 @@ are those of the scalar formulas).
                outside [0, NV), an element that lists a vertex twice, and an element whose det is not positive at a point
                (ElementError, .element the smallest such id).
   zeroth order element_mass and element_loads, on the same types, node orders and geometry: defined further down in this file.
+  points       element_points, element_eval, element_loads_points and element_errors: the points of the mass rule, a nodal field
+               and its gradient there, the loads of a source given there and the squared errors per element: defined after the
+               boundary forms.
   boundary     FACE_NODES, boundary_mass and boundary_loads: the face mass and the face loads of a list of (element, local face)
                pairs, added into the owning elements' matrices and vectors: defined at the end of this file.
 """
@@ -801,4 +804,195 @@ def boundary_loads(coords, elem_to_vertex, face_elem, face_local, g, vdim=1, coe
     _refuse_measure(bad)
     if elem_ptr is None:
         return out.reshape(len(nd), nd[0] * vdim) if len(nd) else out.reshape(0, 0)
+    return out
+
+
+# ---- data at the points of the mass rule: the points, evaluation, loads of point data, errors ----------------------------------------
+#   points       the points of an element are those of its type's MASS rule (MASS_NPOINTS, shape_values, mass_reference_gradients,
+#                mass_point_weight), in the rule's order; point q of element e has the global index qp_ptr[e] + q, qp_ptr (NE + 1,
+#                int64), NQ = qp_ptr[NE].  xq[q][i] = sum over the nodes a, ascending, of N_a * x_a[i], the first product as it is;
+#                wdet[q] = weight_q * det_q: the bits of s of _mass_points with the coefficient 1.0.
+#   eval         u nodal (NV, vdim): uq[q][i] = sum over the nodes, ascending, of N_a * u_a[i] (fq of _load_block).  Gradient:
+#                r[i][k] = sum over the nodes, ascending, of u_a[i] * dN_a[k], the first product as it is (J with u in the place of
+#                x); t[i][j] = r[i][0] * C[j][0] + r[i][1] * C[j][1] (+ r[i][2] * C[j][2]) with the cofactors C of _cofactors;
+#                gradq[q][i][j] = t[i][j] / det: the derivative of component i along x_j, the division last.
+#   loads        fq (NQ, vdim) at the points: dof (a, i) gets the sum over the points, ascending from 0.0, of (s * fq[q][i]) * N_a,
+#                s = (weight * det) * coef_e (coef None: 1.0); the packed layout of element_loads.
+#   errors       (NE, 2).  Column 0: the sum over the points, ascending from 0.0, of wdet_q * d_q, d_q = the sum over i, ascending, of
+#                (uq_i - exq_i) * (uq_i - exq_i), the first square as it is; column 1 the same with gradq - exgradq over (i, j), i
+#                outermost.  A column whose exact data is None is 0.0.
+#   refused      vdim, then what _mesh refuses; then a missing u / fq (or one of the wrong size; then exact data of the wrong
+#                size); then the first element with a non-positive determinant (ElementError).
+def _points_block(X, dim, nd):
+    """Per point of the mass rule of n elements of one type: (N, dN, C, det), and per element whether a det was not positive."""
+    bad = np.zeros(X.shape[0], bool)
+    out = []
+    with np.errstate(all="ignore"):
+        for q in range(MASS_NPOINTS[(dim, nd)]):
+            dN = mass_reference_gradients(dim, nd, q)
+            J = [[None] * dim for _ in range(dim)]
+            for i in range(dim):
+                for j in range(dim):
+                    t = X[:, 0, i] * dN[0][j]
+                    for a in range(1, nd):
+                        t = t + X[:, a, i] * dN[a][j]
+                    J[i][j] = t
+            C, det = _cofactors(J, dim)
+            bad |= ~(det > 0.0)
+            out.append((shape_values(dim, nd, q), dN, C, det))
+    return out, bad
+
+
+def _eval_point(N, dN, C, det, F, dim, grad):
+    """(uq (n, vdim), gradq (n, vdim, dim) or None) at one point; F: (n, nd, vdim) the nodal field."""
+    nd = F.shape[1]
+    uq = N[0] * F[:, 0, :]
+    for a in range(1, nd):
+        uq = uq + N[a] * F[:, a, :]
+    if not grad:
+        return uq, None
+    g = np.zeros(F.shape[:1] + (F.shape[2], dim))
+    r = []
+    for k in range(dim):
+        t = F[:, 0, :] * dN[0][k]
+        for a in range(1, nd):
+            t = t + F[:, a, :] * dN[a][k]
+        r.append(t)
+    for j in range(dim):
+        t = r[0] * C[j][0][:, None] + r[1] * C[j][1][:, None]
+        if dim == 3:
+            t = t + r[2] * C[j][2][:, None]
+        g[:, :, j] = t / det[:, None]
+    return uq, g
+
+
+def _points_mesh(coords, elem_to_vertex, elem_ptr, vdim):
+    shape = np.shape(coords)
+    if len(shape) == 2 and shape[1] in (2, 3):
+        _vdim(vdim, shape[1])                                        # (refused before the mesh is looked at)
+    X, dim, ep, e2v, nd = _mesh(coords, elem_to_vertex, elem_ptr)
+    vdim = _vdim(vdim, dim)
+    npts = np.array([MASS_NPOINTS[(dim, int(c))] for c in nd], np.int64)
+    qp = np.concatenate([[0], np.cumsum(npts)]).astype(np.int64)
+    return X, dim, ep, e2v, nd, vdim, qp
+
+
+def _point_data(a, n, what, needed=True):
+    if a is None:
+        if needed:
+            raise ValueError("%s is needed" % what)
+        return None
+    a = np.asarray(a, np.float64)
+    if a.size != int(np.prod(n)):
+        raise ValueError("%s is needed" % what)
+    return a.reshape(n)
+
+
+def _types(nd, ep, e2v):
+    """(node count, element ids, their vertex lists (n, nodes)) per type, ascending node count"""
+    for c in np.unique(nd):
+        ids = np.flatnonzero(nd == c)
+        yield int(c), ids, e2v[ep[ids][:, None] + np.arange(int(c))]
+
+
+def _refuse_det(bad):
+    if bad.any():
+        raise ElementError(np.flatnonzero(bad)[0])
+
+
+def element_points(coords, elem_to_vertex, elem_ptr=None):
+    """(qp_ptr (NE + 1,) int64, xq (NQ, dim), wdet (NQ,)): the points of the mass rule of every element and weight * det there."""
+    X, dim, ep, e2v, nd, _, qp = _points_mesh(coords, elem_to_vertex, elem_ptr, 1)
+    NQ = int(qp[-1])
+    xq, wdet = np.zeros((NQ, dim)), np.zeros(NQ)
+    bad = np.zeros(len(nd), bool)
+    with np.errstate(all="ignore"):
+        for c, ids, v in _types(nd, ep, e2v):
+            points, bad[ids] = _points_block(X[v], dim, c)
+            for q, (N, dN, C, det) in enumerate(points):
+                xq[qp[ids] + q] = _eval_point(N, dN, C, det, X[v], dim, False)[0]
+                wdet[qp[ids] + q] = mass_point_weight(dim, c, q) * det
+    _refuse_det(bad)
+    return qp, xq, wdet
+
+
+def element_eval(coords, elem_to_vertex, u, vdim=1, elem_ptr=None, grad=True):
+    """(uq (NQ, vdim), gradq (NQ, vdim, dim)) of the nodal field u (NV, vdim) or (NV,) at the points; grad=False: gradq is None."""
+    X, dim, ep, e2v, nd, vdim, qp = _points_mesh(coords, elem_to_vertex, elem_ptr, vdim)
+    U = _point_data(u, (X.shape[0], vdim), "u: (NV, vdim)")
+    NQ = int(qp[-1])
+    uq, gq = np.zeros((NQ, vdim)), np.zeros((NQ, vdim, dim)) if grad else None
+    bad = np.zeros(len(nd), bool)
+    with np.errstate(all="ignore"):
+        for c, ids, v in _types(nd, ep, e2v):
+            points, bad[ids] = _points_block(X[v], dim, c)
+            for q, (N, dN, C, det) in enumerate(points):
+                a, g = _eval_point(N, dN, C, det, U[v], dim, grad)
+                uq[qp[ids] + q] = a
+                if grad:
+                    gq[qp[ids] + q] = g
+    _refuse_det(bad)
+    return uq, gq
+
+
+def element_loads_points(coords, elem_to_vertex, fq, vdim=1, coef=None, elem_ptr=None):
+    """The load vectors of the source fq (NQ, vdim) or (NQ,) given at the points, with the per-element coefficient coef (NE,), None:
+    1.0, in the layout of element_loads."""
+    X, dim, ep, e2v, nd, vdim, qp = _points_mesh(coords, elem_to_vertex, elem_ptr, vdim)
+    NE = len(nd)
+    F = _point_data(fq, (int(qp[-1]), vdim), "fq: (NQ, vdim)")
+    coef = np.ones(NE) if coef is None else np.asarray(coef, np.float64).reshape(-1)
+    if len(coef) != NE:
+        raise ValueError("coef: (NE,) is needed")
+    voff = np.concatenate([[0], np.cumsum(nd * vdim)])
+    out = np.zeros(int(voff[-1]))
+    bad = np.zeros(NE, bool)
+    with np.errstate(all="ignore"):
+        for c, ids, v in _types(nd, ep, e2v):
+            points, bad[ids] = _mass_points(X[v], dim, c, coef[ids])
+            acc = np.zeros((len(ids), c, vdim))
+            for q, (N, s) in enumerate(points):
+                sf = s[:, None] * F[qp[ids] + q]
+                term = sf[:, None, :] * np.array(N)[None, :, None]
+                acc = acc + term
+            out[voff[ids][:, None] + np.arange(c * vdim)] = acc.reshape(len(ids), -1)
+    _refuse_det(bad)
+    if elem_ptr is None:
+        return out.reshape(NE, nd[0] * vdim) if NE else out.reshape(0, 0)
+    return out
+
+
+def element_errors(coords, elem_to_vertex, u, exq=None, exgradq=None, vdim=1, elem_ptr=None):
+    """(NE, 2): per element the squared L2 error of the nodal u against the exact values exq (NQ, vdim) at the points, and the
+    squared error of its gradient against exgradq (NQ, vdim, dim); a column whose exact data is None is 0.0."""
+    X, dim, ep, e2v, nd, vdim, qp = _points_mesh(coords, elem_to_vertex, elem_ptr, vdim)
+    NE, NQ = len(nd), int(qp[-1])
+    U = _point_data(u, (X.shape[0], vdim), "u: (NV, vdim)")
+    E = _point_data(exq, (NQ, vdim), "exq: (NQ, vdim)", False)
+    EG = _point_data(exgradq, (NQ, vdim, dim), "exgradq: (NQ, vdim, dim)", False)
+    out = np.zeros((NE, 2))
+    bad = np.zeros(NE, bool)
+    with np.errstate(all="ignore"):
+        for c, ids, v in _types(nd, ep, e2v):
+            points, bad[ids] = _points_block(X[v], dim, c)
+            acc0, acc1 = np.zeros(len(ids)), np.zeros(len(ids))
+            for q, (N, dN, C, det) in enumerate(points):
+                wdet = mass_point_weight(dim, c, q) * det
+                a, g = _eval_point(N, dN, C, det, U[v], dim, EG is not None)
+                if E is not None:
+                    d = (a - E[qp[ids] + q]).reshape(len(ids), -1)
+                    t = d[:, 0] * d[:, 0]
+                    for k in range(1, d.shape[1]):
+                        t = t + d[:, k] * d[:, k]
+                    term = wdet * t
+                    acc0 = acc0 + term
+                if EG is not None:
+                    d = (g - EG[qp[ids] + q]).reshape(len(ids), -1)
+                    t = d[:, 0] * d[:, 0]
+                    for k in range(1, d.shape[1]):
+                        t = t + d[:, k] * d[:, k]
+                    term = wdet * t
+                    acc1 = acc1 + term
+            out[ids, 0], out[ids, 1] = acc0, acc1
+    _refuse_det(bad)
     return out

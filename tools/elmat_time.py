@@ -7,7 +7,7 @@ warm-up, `--reps` repetitions (all listed).  One JSON line per case.
 
     python tools/elmat_time.py [--hex 128,256] [--elasticity 64] [--q2-hex 64,128] [--q2-elasticity 32,64] [--quad9 2048]
                                [--reps 3] [--host-reps 3] [--hbm-gbs 8000] [--fp64-gops 39300] [--no-host] [--no-mass]
-                               [--rhs 256] [--boundary] [--p2-simplex] [--p2-tet 64] [--p2-tri 2048]
+                               [--rhs 256] [--boundary] [--p2-simplex] [--p2-tet 64] [--p2-tri 2048] [--points]
 
 Beside every stiffness case, on the same mesh and in the same run (--no-mass: not): the mass matrices of the same layout
 (saamge_amd_element_mass; vdim 1 beside diffusion, dim beside elasticity), written (`<case>:mass`) and added to the stiffness
@@ -26,6 +26,11 @@ from the diagonal split of the --p2-tri^2 grid, their nodes the (2 n + 1)^dim ha
 spacing -- under the same protocol: diffusion, elasticity, mass (vdim 1 and dim, written), loads, and the boundary mass and loads
 on all boundary faces; after each, the same form on the 27-node hexes / 9-node quadrilaterals of the same grid in the same run,
 the yardstick (`yardstick_fraction_of_bound`, or `yardstick_ms` for the boundary forms).
+
+--points: only the data at quadrature points (saamge_amd_element_points, _eval with and without the gradient, _loads_points,
+_errors with both columns; vdim 1) on Q1 hexes 128^3 and 256^3, Q2 hexes 64^3 and the 10-node tetrahedra of the 64^3 split, same
+protocol; `bound_bytes` is what the call must move -- coordinates, vertex lists, nodal and point inputs read once, outputs
+written once -- and `hbm_bound_ms` that at --hbm-gbs; after them saamge_amd_element_loads on the same mesh in the same run.
 
 The vertices are jittered by 0.2 mesh widths, so no two elements are alike.  A case that does not fit is reported as skipped
 with the error.
@@ -66,6 +71,7 @@ def main():
     ap.add_argument("--rhs", default="")
     ap.add_argument("--boundary", action="store_true")
     ap.add_argument("--p2-simplex", action="store_true")
+    ap.add_argument("--points", action="store_true")
     ap.add_argument("--p2-tet", type=int, default=64)
     ap.add_argument("--p2-tri", type=int, default=2048)
     a = ap.parse_args()
@@ -236,6 +242,51 @@ def main():
                 X = e2n = out = vec = o1 = v1 = fe = fl = alpha = src = src1 = c1 = c2 = None
                 torch.cuda.empty_cache()
                 capi.release_cached_memory()
+        return
+
+    if a.points:
+        def reps(call):
+            timed(call)                            # warm-up
+            return [round(timed(call)[0], 3) for _ in range(a.reps)]
+        for name, n, nd in [("hex128", 128, 8), ("hex256", 256, 8), ("q2_hex64", 64, 27), ("tet10_64", 64, 10)]:
+            try:
+                X, e2v, g = mesh(n) if nd == 8 else (mesh_q2(n, 3) if nd == 27 else mesh_p2(n, 3)[:3])
+                NE, NV = int(e2v.shape[0]), int(X.shape[0])
+                NQ = capi.element_points(X, e2v, sizes_only=True)[5]
+                u = torch.rand(NV, generator=g, device=dev, dtype=torch.float64)
+                fq = torch.rand(NQ, generator=g, device=dev, dtype=torch.float64)
+                exg = torch.rand((NQ, 1, 3), generator=g, device=dev, dtype=torch.float64)
+                qp = torch.zeros(NE + 1, dtype=torch.int64, device=dev)
+                xq = torch.zeros(NQ * 3, dtype=torch.float64, device=dev)
+                gq = torch.zeros(NQ * 3, dtype=torch.float64, device=dev)
+                wdet, uq = torch.zeros(NQ, dtype=torch.float64, device=dev), torch.zeros(NQ, dtype=torch.float64, device=dev)
+                vec = torch.zeros(NE * nd, dtype=torch.float64, device=dev)
+                err = torch.zeros(NE * 2, dtype=torch.float64, device=dev)
+                st = stream
+                mesh_bytes = 8 * X.numel() + 4 * e2v.numel()      # read once by every call
+                calls = [("points", mesh_bytes + 8 * (NE + 1) + 8 * 4 * NQ,
+                          lambda: capi.element_points(X, e2v, out={"qp_ptr": qp, "xq": xq, "wdet": wdet}, stream=st())),
+                         ("eval", mesh_bytes + 8 * NV + 8 * 4 * NQ,
+                          lambda: capi.element_eval(X, e2v, u, out={"uq": uq, "gradq": gq}, stream=st())),
+                         ("eval_values_only", mesh_bytes + 8 * NV + 8 * NQ,
+                          lambda: capi.element_eval(X, e2v, u, want=("uq",), out={"uq": uq}, stream=st())),
+                         ("loads_points", mesh_bytes + 8 * NQ + 8 * vec.numel(),
+                          lambda: capi.element_loads_points(X, e2v, fq, out=vec, stream=st())),
+                         ("errors", mesh_bytes + 8 * NV + 8 * 4 * NQ + 8 * err.numel(),
+                          lambda: capi.element_errors(X, e2v, u, fq, exg, out=err, stream=st())),
+                         ("loads (nodal, the yardstick)", mesh_bytes + 8 * NV + 8 * vec.numel(),
+                          lambda: capi.element_loads(X, e2v, u, out=vec, stream=st()))]
+                for tag, nbytes, call in calls:
+                    t = reps(call)
+                    b_ms = 1e3 * nbytes / (a.hbm_gbs * 1e9)
+                    print(json.dumps({"case": "points:%s:%s" % (name, tag), "elements": NE, "points": NQ, "bound_bytes": int(nbytes),
+                                      "device_ms": t, "hbm_bound_ms": round(b_ms, 4), "fraction_of_bound": round(b_ms / min(t), 4)}),
+                          flush=True)
+            except (RuntimeError, MemoryError) as e:
+                print(json.dumps({"case": "points:" + name, "skipped": str(e)[:200]}), flush=True)
+            X = e2v = u = fq = exg = qp = xq = gq = wdet = uq = vec = err = None
+            torch.cuda.empty_cache()
+            capi.release_cached_memory()
         return
 
     if a.boundary:
