@@ -962,23 +962,45 @@ bool ae_sparse_rows(hipStream_t s, const DevRelations &rel, const DCsr &A, const
 // e1 e2 + e1 + 1 with e1 <= e2 the two smaller extents instead of a b + a + 1 (the 9 x 9 x 5 boxes
 // of the headline problem: 51 instead of 91).  Everything is verified entry by entry; any other
 // agglomerate keeps the rank order.
+// The sorted list: SORT = false ranks every dof against all the others (n LDS reads per row -- nothing at the few hundred rows of
+// a fine agglomerate); SORT = true (batches of AE_SORT_MIN rows and more, launch_ae_perm) sorts a copy padded with INT_MAX to
+// the next power of two m by a bitonic network, log2 m (log2 m + 1) / 2 passes of m / 2 exchanges.  The dofs of an agglomerate
+// are distinct, so both give the same list.
+constexpr int AE_SORT_MIN = 1024;
+template <bool SORT>
 __global__ __launch_bounds__(256) void ae_perm_kernel(int ae0, const int *__restrict__ ns, const int64_t *__restrict__ voff,
                                                       const int *__restrict__ ae2d_I, const int *__restrict__ ae2d_J,
                                                       short *__restrict__ perm, short *__restrict__ iperm) {
-    extern __shared__ int gd[];          // [n] dofs in table order, [n] sorted
+    extern __shared__ int gd[];          // [n] dofs in table order, [n] sorted (SORT: [m])
     __shared__ int box[6];               // a, b, c, s2, s3, ok
     const int b = blockIdx.x, n = ns[b];
     int *sid = gd + n;
     const int *aedofs = ae2d_J + ae2d_I[ae0 + b];
     for (int r = threadIdx.x; r < n; r += 256) gd[r] = aedofs[r];
     __syncthreads();
-    for (int r = threadIdx.x; r < n; r += 256) {
-        const int g = gd[r];
-        int rank = 0;
-        for (int k = 0; k < n; ++k) rank += gd[k] < g;
-        sid[rank] = g;
+    if (SORT) {
+        int m = 1;
+        while (m < n) m <<= 1;
+        for (int i = threadIdx.x; i < m; i += 256) sid[i] = i < n ? gd[i] : INT_MAX;
+        __syncthreads();
+        for (int k = 2; k <= m; k <<= 1)
+            for (int j = k >> 1; j > 0; j >>= 1) {
+                for (int t = threadIdx.x; t < (m >> 1); t += 256) {
+                    const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = i | j;      // the pair (i, i + j) of exchange t
+                    const int x = sid[i], y = sid[p];
+                    if ((x > y) == ((i & k) == 0)) { sid[i] = y; sid[p] = x; }
+                }
+                __syncthreads();
+            }
+    } else {
+        for (int r = threadIdx.x; r < n; r += 256) {
+            const int g = gd[r];
+            int rank = 0;
+            for (int k = 0; k < n; ++k) rank += gd[k] < g;
+            sid[rank] = g;
+        }
+        __syncthreads();
     }
-    __syncthreads();
     if (threadIdx.x == 0) {
         int a = 1, bb = 1, c = 1, s2 = 0, s3 = 0, ok = 0;
         while (a < n && sid[a] == sid[0] + a) ++a;
@@ -1029,6 +1051,26 @@ __global__ __launch_bounds__(256) void ae_perm_kernel(int ae0, const int *__rest
         perm[voff[b] + r] = (short)pos;
         iperm[voff[b] + pos] = (short)r;
     }
+}
+// batch.perm / iperm of the agglomerates [ae0, ae0 + batch.count) on stream s.  Dynamic LDS: the dofs and the sorted list -- the
+// latter padded to a power of two where the list is sorted (above 64 KB, agglomerates of more than 8192 rows, by attribute).
+static void launch_ae_perm(hipStream_t s, const DevRelations &rel, int ae0, const EigBatch &batch) {
+    if (batch.max_n < AE_SORT_MIN) {
+        hipLaunchKernelGGL(ae_perm_kernel<false>, dim3(batch.count), dim3(256), 2 * sizeof(int) * (size_t)batch.max_n, s, ae0,
+                           batch.n.p, batch.voff.p, rel.ae2d_I.p, rel.ae2d_J.p, batch.perm.p, batch.iperm.p);
+        return;
+    }
+    size_t m = 1;
+    while (m < (size_t)batch.max_n) m <<= 1;
+    const size_t lds = sizeof(int) * ((size_t)batch.max_n + m);
+    SA_REQUIRE(lds <= 150 * 1024, "agglomerate too large for the row order");
+    static bool attr = false;
+    if (lds > 64 * 1024 && !attr) {
+        SA_HIP_CHECK(hipFuncSetAttribute((const void *)ae_perm_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        attr = true;
+    }
+    hipLaunchKernelGGL(ae_perm_kernel<true>, dim3(batch.count), dim3(256), lds, s, ae0, batch.n.p, batch.voff.p, rel.ae2d_I.p,
+                       rel.ae2d_J.p, batch.perm.p, batch.iperm.p);
 }
 
 // Options::ae_order = 1: the LEVEL ORDER of saamge_amd/ae_order_model.py (the definition: rule, keys and limits are stated there,
@@ -1327,8 +1369,7 @@ void ae_order_only(hipStream_t s, const DevRelations &rel, int ae0, EigBatch &ba
     SA_REQUIRE(batch.max_n <= 8192, "saamge_amd_ae_order: an agglomerate of more than 8192 rows");
     const size_t rows_total = (size_t)batch.h_voff[batch.count];
     if (batch.perm.n < rows_total) { batch.perm.alloc(rows_total); batch.iperm.alloc(rows_total); }
-    hipLaunchKernelGGL(ae_perm_kernel, dim3(batch.count), dim3(256), 2 * sizeof(int) * (size_t)batch.max_n, s, ae0, batch.n.p,
-                       batch.voff.p, rel.ae2d_I.p, rel.ae2d_J.p, batch.perm.p, batch.iperm.p);
+    launch_ae_perm(s, rel, ae0, batch);
     SA_HIP_CHECK(hipGetLastError());
     batch.has_perm = true;
     ae_level_order(s, rel, ae0, batch, mode, res, nullptr);
@@ -1359,7 +1400,8 @@ struct AeInputs {
     int ae0;
 };
 // The words of row lr0 of agglomerate p (matrix b), visited by a WAVEFRONT: lanes take the entries of the row of the global
-// matrix, then, element by element of the row's dof, the dofs of the element (coalesced reads of the element-matrix row).
+// matrix, then the dofs of all the elements of the row's dof in one flat loop (AiHeads: what is known per element, fetched by a
+// lane per element first; reads of the element-matrix rows).
 // F(word, position): every word carries a position that does not depend on the lane that visits it (entry index in the row of
 // A / element ordinal and dof slot), so sums over (word, position) are order-independent and two agglomerates can be compared
 // position by position.  `other` (verification): the same walk over a second agglomerate in lockstep; returns false at the
@@ -1368,8 +1410,29 @@ struct AiRow {      // what identifies one side of a walk
     int b, p;
     const AiTable *loc;
 };
+// what a wavefront keeps per element of the 64 at hand (PAIR: x2 of the second agglomerate)
+struct AiHeads {
+    int pre[65];                 // dofs of the elements inside the agglomerate before element t
+    int eb[64], nd[64], kk[64], eb2[64], kk2[64];
+    int64_t eo[64], eo2[64];
+};
+// a wavefront's writes to its own piece of LDS before its lanes read one another's, and the reverse
+__device__ inline void wave_lds_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// v of lanes 0 .. lane summed (every lane of the wavefront calls it)
+__device__ inline int wave_inclusive_sum(int v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(v, o, 64);
+        if (lane >= o) v += up;
+    }
+    return v;
+}
 template <bool PAIR, class F>
-__device__ inline bool ai_row_walk(const AeInputs &v, const AiRow &x, const AiRow &y, int lr0, int lane, F &&f) {
+__device__ inline bool ai_row_walk(const AeInputs &v, const AiRow &x, const AiRow &y, int lr0, int lane, AiHeads &hd, F &&f) {
     const int gx = v.ae2d_J[v.ae2d_I[x.p] + lr0], gy = PAIR ? v.ae2d_J[v.ae2d_I[y.p] + lr0] : 0;
     bool ok = true;
     if (lane == 0) {
@@ -1411,57 +1474,82 @@ __device__ inline bool ai_row_walk(const AeInputs &v, const AiRow &x, const AiRo
     const int qx = v.d2e_I[gx], cx = v.d2e_I[gx + 1] - qx;
     const int qy = PAIR ? v.d2e_I[gy] : 0;
     if (PAIR && cx != v.d2e_I[gy + 1] - qy) return false;
-    for (int q = 0; q < cx; ++q) {      // (wave-uniform)
-        const int e = v.d2e_J[qx + q];
-        const bool in = v.part[e] == x.p;
-        int e2 = 0;
-        if (PAIR) {
-            e2 = v.d2e_J[qy + q];
-            if (in != (v.part[e2] == y.p)) return false;
-        }
-        if (!in) continue;
-        const int eb = v.e2d_I[e], nd = v.e2d_I[e + 1] - eb;
-        const int eb2 = PAIR ? v.e2d_I[e2] : 0;
-        if (PAIR && nd != v.e2d_I[e2 + 1] - eb2) return false;
-        // the dof's slot in the element: found by the lanes
-        int kk = nd, kk2 = nd;
-        for (int j0 = 0; j0 < nd && kk == nd; j0 += 64) {
-            const unsigned long long m = __ballot(j0 + lane < nd && v.e2d_J[eb + j0 + lane] == gx);
-            if (m) kk = j0 + __builtin_ctzll(m);
-        }
-        if (PAIR) {
-            for (int j0 = 0; j0 < nd && kk2 == nd; j0 += 64) {
-                const unsigned long long m = __ballot(j0 + lane < nd && v.e2d_J[eb2 + j0 + lane] == gy);
-                if (m) kk2 = j0 + __builtin_ctzll(m);
-            }
-            if (kk != kk2) return false;
-        } else if (lane == 0) {
-            f(((unsigned long long)(unsigned)nd << 32) | (unsigned)kk, (2ull << 40) + ((unsigned long long)q << 20));
-        }
-        const double *M = v.elval + v.eloff[e] + (size_t)kk * nd;
-        const double *M2 = PAIR ? v.elval + v.eloff[e2] + (size_t)kk * nd : nullptr;
-        for (int jj = lane; jj < nd; jj += 64) {
-            const int d = v.e2d_J[eb + jj];
-            const unsigned long long w = ((unsigned long long)(unsigned)v.elem_ldof[eb + jj] << 8) |
-                                         (v.has_A ? (unsigned long long)(unsigned char)v.flags[d] | (d == gx ? 1ull << 40 : 0ull) : 0ull);
-            const unsigned long long a = (unsigned long long)__double_as_longlong(M[jj]);
+    // the elements of the row's dof, 64 at a time: a lane per element fetches what the walk needs of it (d2e_J -> part -> e2d_I,
+    // eloff), a prefix sum of the dof counts of the elements inside the agglomerate then lets the lanes run over all their dofs
+    // in one flat loop -- twice: for the dof's slot in each element, then for the words.
+    for (int q0 = 0; q0 < cx; q0 += 64) {      // (wave-uniform)
+        const int nq = min(64, cx - q0);
+        bool in = false, same = true;
+        int nd = 0;
+        if (lane < nq) {
+            const int e = v.d2e_J[qx + q0 + lane];
+            in = v.part[e] == x.p;
+            const int eb = v.e2d_I[e];
+            nd = v.e2d_I[e + 1] - eb;
+            hd.eb[lane] = eb;
+            hd.nd[lane] = nd;
+            hd.eo[lane] = v.eloff[e];
+            hd.kk[lane] = nd;
             if (PAIR) {
-                const int d2 = v.e2d_J[eb2 + jj];
-                const unsigned long long w2 = ((unsigned long long)(unsigned)v.elem_ldof[eb2 + jj] << 8) |
-                                              (v.has_A ? (unsigned long long)(unsigned char)v.flags[d2] | (d2 == gy ? 1ull << 40 : 0ull) : 0ull);
-                ok = ok && w == w2 && a == (unsigned long long)__double_as_longlong(M2[jj]);
-            } else {
-                const unsigned long long pos = (3ull << 40) + ((unsigned long long)q << 20) + 2 * (unsigned long long)jj;
-                f(w, pos);
-                f(a, pos + 1);
+                const int e2 = v.d2e_J[qy + q0 + lane], eb2 = v.e2d_I[e2];
+                same = in == (v.part[e2] == y.p) && (!in || nd == v.e2d_I[e2 + 1] - eb2);
+                hd.eb2[lane] = eb2;
+                hd.eo2[lane] = v.eloff[e2];
+                hd.kk2[lane] = nd;
             }
         }
+        if (PAIR && !__all(same)) return false;
+        const int inc = wave_inclusive_sum(in ? nd : 0, lane);
+        hd.pre[lane + 1] = inc;
+        if (lane == 0) hd.pre[0] = 0;
+        const int total = __shfl(inc, 63, 64);
+        wave_lds_fence();
+        // the dof's slot in every element: the first of the element's dofs that is the row's
+        int t = 0;      // the element of this lane's dof: moves forward only
+        for (int i = lane; i < total; i += 64) {
+            while (i >= hd.pre[t + 1]) ++t;
+            const int jj = i - hd.pre[t];
+            if (v.e2d_J[hd.eb[t] + jj] == gx) atomicMin(&hd.kk[t], jj);
+            if (PAIR && v.e2d_J[hd.eb2[t] + jj] == gy) atomicMin(&hd.kk2[t], jj);
+        }
+        wave_lds_fence();
+        if (in) {
+            if (PAIR) same = hd.kk[lane] == hd.kk2[lane];
+            else f(((unsigned long long)(unsigned)nd << 32) | (unsigned)hd.kk[lane], (2ull << 40) + ((unsigned long long)(q0 + lane) << 20));
+        }
+        if (PAIR && !__all(same)) return false;
+        t = 0;
+        for (int base = 0; base < total; base += 64) {      // (wave-uniform)
+            const int i = base + lane;
+            if (i < total) {
+                while (i >= hd.pre[t + 1]) ++t;
+                const int jj = i - hd.pre[t], eb = hd.eb[t];
+                const size_t mrow = (size_t)hd.kk[t] * hd.nd[t] + jj;      // (row kk of the element matrix)
+                const int d = v.e2d_J[eb + jj];
+                const unsigned long long w = ((unsigned long long)(unsigned)v.elem_ldof[eb + jj] << 8) |
+                                             (v.has_A ? (unsigned long long)(unsigned char)v.flags[d] | (d == gx ? 1ull << 40 : 0ull) : 0ull);
+                const unsigned long long a = (unsigned long long)__double_as_longlong(v.elval[hd.eo[t] + mrow]);
+                if (PAIR) {
+                    const int eb2 = hd.eb2[t], d2 = v.e2d_J[eb2 + jj];
+                    const unsigned long long w2 = ((unsigned long long)(unsigned)v.elem_ldof[eb2 + jj] << 8) |
+                                                  (v.has_A ? (unsigned long long)(unsigned char)v.flags[d2] | (d2 == gy ? 1ull << 40 : 0ull) : 0ull);
+                    ok = ok && w == w2 && a == (unsigned long long)__double_as_longlong(v.elval[hd.eo2[t] + mrow]);
+                } else {
+                    const unsigned long long pos = (3ull << 40) + ((unsigned long long)(q0 + t) << 20) + 2 * (unsigned long long)jj;
+                    f(w, pos);
+                    f(a, pos + 1);
+                }
+            }
+            if (PAIR && !__all(ok)) return false;
+        }
+        wave_lds_fence();      // (the next 64 elements overwrite hd)
     }
     return ok;
 }
 constexpr int AI_NT = 256;
 __global__ __launch_bounds__(AI_NT) void asm_hash_kernel(AeInputs v, int hsize, unsigned long long *__restrict__ out) {
     extern __shared__ __align__(16) unsigned char ai_lds[];
+    __shared__ AiHeads hd[AI_NT / 64];
     const int b = blockIdx.x, p = v.ae0 + b, n = v.ns[b], tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     AiTable loc{(int *)ai_lds, (short *)(ai_lds + 4 * (size_t)hsize), (unsigned)(hsize - 1)};
     if (v.has_A) loc.build(v.ae2d_J + v.ae2d_I[p], n, tid, AI_NT);
@@ -1469,7 +1557,7 @@ __global__ __launch_bounds__(AI_NT) void asm_hash_kernel(AeInputs v, int hsize, 
     DdHash h;
     for (int lr0 = blockIdx.y * (AI_NT / 64) + wv; lr0 < n; lr0 += (AI_NT / 64) * gridDim.y) {
         const unsigned long long rowtag = (unsigned long long)(lr0 + 1) * 0xC2B2AE3D27D4EB4Full;      // (added to the word: the row of the position)
-        ai_row_walk<false>(v, x, x, lr0, lane, [&](unsigned long long w, unsigned long long pos) { h.add(w + rowtag, pos); });
+        ai_row_walk<false>(v, x, x, lr0, lane, hd[wv], [&](unsigned long long w, unsigned long long pos) { h.add(w + rowtag, pos); });
     }
     if (tid == 0 && blockIdx.y == 0) { h.h1 += dd_mix((unsigned long long)n + 0x4444444444444444ull); h.h2 += dd_mix((unsigned long long)n ^ 0x7777777777777777ull); }
     h.block_finish<true>(out, b);
@@ -1480,6 +1568,7 @@ __global__ void scatter_int_kernel(int n, const int *__restrict__ idx, const int
 }
 __global__ __launch_bounds__(AI_NT) void asm_verify_kernel(AeInputs v, int hsize, const int *__restrict__ rep, int *__restrict__ differ) {
     extern __shared__ __align__(16) unsigned char ai_lds[];
+    __shared__ AiHeads hd[AI_NT / 64];
     const int b = blockIdx.x, r0 = rep[b], tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     if (r0 == b) return;
     const int n = v.ns[b];
@@ -1491,7 +1580,7 @@ __global__ __launch_bounds__(AI_NT) void asm_verify_kernel(AeInputs v, int hsize
     const AiRow x{b, v.ae0 + b, &locb}, y{r0, v.ae0 + r0, &locr};
     bool ok = true;
     for (int lr0 = blockIdx.y * (AI_NT / 64) + wv; lr0 < n; lr0 += (AI_NT / 64) * gridDim.y)
-        ok = ai_row_walk<true>(v, x, y, lr0, lane, [](unsigned long long, unsigned long long) {}) && ok;
+        ok = ai_row_walk<true>(v, x, y, lr0, lane, hd[wv], [](unsigned long long, unsigned long long) {}) && ok;
     if (!ok) differ[b] = 1;
 }
 
@@ -1525,8 +1614,7 @@ void ae_build(hipStream_t s, const DevRelations &rel, const DCsr *A, const DevEl
     if (scale && eig_batch_takes_subspace(batch) && batch.max_n <= 16384 && (A || split_scale)) {
         const size_t rows_total = (size_t)batch.h_voff[batch.count];
         if (batch.perm.n < rows_total) { batch.perm.alloc(rows_total); batch.iperm.alloc(rows_total); }
-        hipLaunchKernelGGL(ae_perm_kernel, dim3(batch.count), dim3(256), 2 * sizeof(int) * (size_t)batch.max_n, s, ae0,
-                           batch.n.p, batch.voff.p, rel.ae2d_I.p, rel.ae2d_J.p, batch.perm.p, batch.iperm.p);
+        launch_ae_perm(s, rel, ae0, batch);
         batch.has_perm = true;
         batch.order_ran = true;
         if (batch.opt.ae_order) ae_level_order(s, rel, ae0, batch, 1, nullptr, batch.order_stats);
@@ -1561,11 +1649,12 @@ void ae_build(hipStream_t s, const DevRelations &rel, const DCsr *A, const DevEl
             const bool found = dedupe_classes(
                 s, batch.count,
                 [&](unsigned long long *hash) {
-                    SA_REQUIRE(2 * tbytes <= 150 * 1024, "agglomerate too large for the class search");
+                    // (the tables are 6 x a power of two bytes: 96 KB is the most that passed 150 KB; the kernels' AiHeads need the rest)
+                    SA_REQUIRE(2 * tbytes <= 128 * 1024, "agglomerate too large for the class search");
                     static bool attr_ai = false;
                     if (!attr_ai) {
-                        SA_HIP_CHECK(hipFuncSetAttribute((const void *)asm_hash_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-                        SA_HIP_CHECK(hipFuncSetAttribute((const void *)asm_verify_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+                        SA_HIP_CHECK(hipFuncSetAttribute((const void *)asm_hash_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+                        SA_HIP_CHECK(hipFuncSetAttribute((const void *)asm_verify_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
                         attr_ai = true;
                     }
                     hipLaunchKernelGGL(asm_hash_kernel, grid, dim3(256), tbytes, s, v, hsize, hash);
@@ -2036,8 +2125,12 @@ __global__ __launch_bounds__(ASM_NT) void coarse_elmat_rows_kernel(
 // down the setup): E_e = P_loc^T A_e P_loc is a function of the agglomerate's sparse rows -- whose class the eigenproblem stage
 // has established, ae_class -- and of its MISes in their order: per MIS the number of basis vectors, the row list in the
 // agglomerate's numbering, the basis itself and the positions of its coarse dofs in the element.  CeIn names those arrays;
-// ce_walk visits the words of one agglomerate (a workgroup per agglomerate, threads over the entries of each MIS) either summing
-// mixed (word, position) pairs (the 128-bit hash) or comparing them with the first member of the class in lockstep.
+// ce_walk visits the words of one agglomerate, a WAVEFRONT per agglomerate, either summing mixed (word, position) pairs (the
+// 128-bit hash) or comparing them with the first member of the class in lockstep.  The lanes first fetch what is known per MIS
+// (k, r, where its row list, its column positions and its basis are: 64 MISes at a time) and a prefix sum of the MISes' word
+// counts 1 + k + r + r k; one flat loop then runs over all the words, every lane finding the MIS of its word in the prefix
+// sums -- the chain of dependent loads is paid once per agglomerate, not once per MIS.  Every word keeps the position it has
+// always had: (t + 1) << 40 of MIS t, + 1 << 36, 2 << 36, 3 << 36 for the three lists.
 struct CeIn {
     const int *ae_class, *ae2mis_I, *ae2mis_J, *ae_pair;
     const int64_t *pair_loc_off;
@@ -2048,48 +2141,98 @@ struct CeIn {
     const int64_t *out_off;
     int ae0;
 };
+constexpr int CE_WAVES = 4;      // agglomerates per workgroup
+// what a wavefront keeps per MIS of the 64 at hand (PAIR: x2 of the second agglomerate, whose k and r are the first one's)
+struct CeHeads {
+    int pre[65];                 // words before MIS t of the 64 at hand
+    int k[64], r[64], cp[64], cp2[64];
+    int64_t loc[64], u[64], loc2[64], u2[64];
+};
 template <bool PAIR, class F>
-__device__ inline bool ce_walk(const CeIn &v, int e, int e2, int tid, int nt_, F &&f) {
+__device__ inline bool ce_walk(const CeIn &v, int e, int e2, int lane, CeHeads &hd, F &&f) {
     const int mb = v.ae2mis_I[e], nm = v.ae2mis_I[e + 1] - mb;
     const int mb2 = PAIR ? v.ae2mis_I[e2] : 0;
     if (PAIR && (nm != v.ae2mis_I[e2 + 1] - mb2 || v.ae_class[e] != v.ae_class[e2] ||
                  v.out_off[e + 1] - v.out_off[e] != v.out_off[e2 + 1] - v.out_off[e2])) return false;
     bool ok = true;
-    if (!PAIR && tid == 0) { f((unsigned long long)(unsigned)v.ae_class[e], 1ull); f((unsigned long long)nm, 2ull); f((unsigned long long)(v.out_off[e + 1] - v.out_off[e]), 3ull); }
-    for (int t = 0; t < nm; ++t) {      // (workgroup-uniform)
-        const int mis = v.ae2mis_J[mb + t], k = v.mis_k[mis], r = v.mis2d_I[mis + 1] - v.mis2d_I[mis];
-        const int *loc = v.pair_loc + v.pair_loc_off[v.ae_pair[mb + t]];
-        const int *cp = v.colpos + v.colpos_ptr[mb + t];
-        const double *U = v.mis_u + v.mis_u_off[mis];
-        const unsigned long long tag = (unsigned long long)(t + 1) << 40;
-        if (PAIR) {
-            const int mis2 = v.ae2mis_J[mb2 + t];
-            if (k != v.mis_k[mis2] || r != v.mis2d_I[mis2 + 1] - v.mis2d_I[mis2]) return false;
-            const int *loc2 = v.pair_loc + v.pair_loc_off[v.ae_pair[mb2 + t]];
-            const int *cp2 = v.colpos + v.colpos_ptr[mb2 + t];
-            const long long *U1 = (const long long *)U, *U2 = (const long long *)(v.mis_u + v.mis_u_off[mis2]);
-            for (int i = tid; i < k; i += nt_) ok = ok && cp[i] == cp2[i];
-            for (int i = tid; i < r; i += nt_) ok = ok && loc[i] == loc2[i];
-            for (int i = tid; i < r * k; i += nt_) ok = ok && U1[i] == U2[i];
-        } else {
-            if (tid == 0) f(((unsigned long long)(unsigned)k << 32) | (unsigned)r, tag);
-            for (int i = tid; i < k; i += nt_) f((unsigned long long)(unsigned)cp[i], tag + (1ull << 36) + (unsigned long long)i);
-            for (int i = tid; i < r; i += nt_) f((unsigned long long)(unsigned)loc[i], tag + (2ull << 36) + (unsigned long long)i);
-            for (int i = tid; i < r * k; i += nt_) f((unsigned long long)__double_as_longlong(U[i]), tag + (3ull << 36) + (unsigned long long)i);
+    if (!PAIR && lane == 0) { f((unsigned long long)(unsigned)v.ae_class[e], 1ull); f((unsigned long long)nm, 2ull); f((unsigned long long)(v.out_off[e + 1] - v.out_off[e]), 3ull); }
+    for (int t0 = 0; t0 < nm; t0 += 64) {      // (wave-uniform)
+        const int nt = min(64, nm - t0);
+        int cnt = 0;
+        bool same = true;
+        if (lane < nt) {
+            const int mis = v.ae2mis_J[mb + t0 + lane], k = v.mis_k[mis], r = v.mis2d_I[mis + 1] - v.mis2d_I[mis];
+            hd.k[lane] = k;
+            hd.r[lane] = r;
+            hd.cp[lane] = v.colpos_ptr[mb + t0 + lane];
+            hd.loc[lane] = v.pair_loc_off[v.ae_pair[mb + t0 + lane]];
+            hd.u[lane] = v.mis_u_off[mis];
+            if (PAIR) {
+                const int mis2 = v.ae2mis_J[mb2 + t0 + lane];
+                same = k == v.mis_k[mis2] && r == v.mis2d_I[mis2 + 1] - v.mis2d_I[mis2];
+                hd.cp2[lane] = v.colpos_ptr[mb2 + t0 + lane];
+                hd.loc2[lane] = v.pair_loc_off[v.ae_pair[mb2 + t0 + lane]];
+                hd.u2[lane] = v.mis_u_off[mis2];
+            }
+            cnt = 1 + k + r + r * k;
         }
+        if (PAIR && !__all(same)) return false;
+        const int inc = wave_inclusive_sum(cnt, lane);
+        hd.pre[lane + 1] = inc;
+        if (lane == 0) hd.pre[0] = 0;
+        const int total = __shfl(inc, 63, 64);
+        wave_lds_fence();
+        int t = 0;      // the MIS of this lane's word: moves forward only
+        for (int base = 0; base < total; base += 64) {      // (wave-uniform)
+            const int i = base + lane;
+            if (i < total) {
+                while (i >= hd.pre[t + 1]) ++t;
+                const int k = hd.k[t], r = hd.r[t];
+                int j = i - hd.pre[t];
+                const unsigned long long tag = (unsigned long long)(t0 + t + 1) << 40;
+                unsigned long long w, w2 = 0, pos;
+                if (j == 0) {
+                    w = w2 = ((unsigned long long)(unsigned)k << 32) | (unsigned)r;
+                    pos = tag;
+                } else if ((j -= 1) < k) {
+                    w = (unsigned long long)(unsigned)v.colpos[hd.cp[t] + j];
+                    if (PAIR) w2 = (unsigned long long)(unsigned)v.colpos[hd.cp2[t] + j];
+                    pos = tag + (1ull << 36) + (unsigned long long)j;
+                } else if ((j -= k) < r) {
+                    w = (unsigned long long)(unsigned)v.pair_loc[hd.loc[t] + j];
+                    if (PAIR) w2 = (unsigned long long)(unsigned)v.pair_loc[hd.loc2[t] + j];
+                    pos = tag + (2ull << 36) + (unsigned long long)j;
+                } else {
+                    j -= r;
+                    w = (unsigned long long)__double_as_longlong(v.mis_u[hd.u[t] + j]);
+                    if (PAIR) w2 = (unsigned long long)__double_as_longlong(v.mis_u[hd.u2[t] + j]);
+                    pos = tag + (3ull << 36) + (unsigned long long)j;
+                }
+                if (PAIR) ok = w == w2;
+                else f(w, pos);
+            }
+            if (PAIR && !__all(ok)) return false;
+        }
+        wave_lds_fence();      // (the next 64 MISes overwrite hd)
     }
-    return ok;
+    return true;
 }
-__global__ __launch_bounds__(256) void ce_hash_kernel(CeIn v, unsigned long long *__restrict__ out) {
-    const int b = blockIdx.x;
+__global__ __launch_bounds__(64 * CE_WAVES) void ce_hash_kernel(CeIn v, int count, unsigned long long *__restrict__ out) {
+    __shared__ CeHeads hd[CE_WAVES];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, b = blockIdx.x * CE_WAVES + wv;
+    if (b >= count) return;
     DdHash h;
-    ce_walk<false>(v, v.ae0 + b, 0, threadIdx.x, 256, [&](unsigned long long w, unsigned long long pos) { h.add(w, pos); });
-    h.block_finish<false>(out, b);
+    ce_walk<false>(v, v.ae0 + b, 0, lane, hd[wv], [&](unsigned long long w, unsigned long long pos) { h.add(w, pos); });
+    h.wave_sum();
+    if (lane == 0) { out[2 * (size_t)b] = h.h1; out[2 * (size_t)b + 1] = h.h2; }
 }
-__global__ __launch_bounds__(256) void ce_verify_kernel(CeIn v, const int *__restrict__ rep, int *__restrict__ differ) {
-    const int b = blockIdx.x, r0 = rep[b];
+__global__ __launch_bounds__(64 * CE_WAVES) void ce_verify_kernel(CeIn v, int count, const int *__restrict__ rep, int *__restrict__ differ) {
+    __shared__ CeHeads hd[CE_WAVES];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, b = blockIdx.x * CE_WAVES + wv;
+    if (b >= count) return;
+    const int r0 = rep[b];
     if (r0 == b) return;
-    if (!ce_walk<true>(v, v.ae0 + b, v.ae0 + r0, threadIdx.x, 256, [](unsigned long long, unsigned long long) {})) differ[b] = 1;
+    if (!ce_walk<true>(v, v.ae0 + b, v.ae0 + r0, lane, hd[wv], [](unsigned long long, unsigned long long) {}) && lane == 0) differ[b] = 1;
 }
 // E of every member of a class from the class's first member
 __global__ __launch_bounds__(256) void ce_copy_kernel(int ae0, const int *__restrict__ rep, const int64_t *__restrict__ out_off,
@@ -2117,8 +2260,10 @@ void coarse_elmats_sparse(hipStream_t s, const DevRelations &rel, int ae0, const
                mis_u_off, mis_u, colpos_ptr, colpos, out_off, ae0};
         DdClasses cl;
         if (dedupe_classes(
-                s, batch.count, [&](unsigned long long *hash) { hipLaunchKernelGGL(ce_hash_kernel, dim3(batch.count), dim3(256), 0, s, v, hash); },
-                [&](const int *r, int *differ) { hipLaunchKernelGGL(ce_verify_kernel, dim3(batch.count), dim3(256), 0, s, v, r, differ); }, cl, &rep)) {
+                s, batch.count,
+                [&](unsigned long long *hash) { hipLaunchKernelGGL(ce_hash_kernel, dim3(div_up(batch.count, CE_WAVES)), dim3(64 * CE_WAVES), 0, s, v, batch.count, hash); },
+                [&](const int *r, int *differ) { hipLaunchKernelGGL(ce_verify_kernel, dim3(div_up(batch.count, CE_WAVES)), dim3(64 * CE_WAVES), 0, s, v, batch.count, r, differ); },
+                cl, &rep)) {
             d_rep.from_host(rep, s);
             d_list.from_host(cl.reps, s);
             ncompute = (int)cl.reps.size();
