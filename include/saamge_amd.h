@@ -500,6 +500,32 @@ int saamge_amd_element_loads_points(int NV, int dim, const double *coords, int N
 int saamge_amd_element_errors(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                               const int *elem_to_vertex, int vdim, const double *u, const double *exq, const double *exgradq,
                               void *stream, double *err_out, long long info[8]);
+/* ---- coefficients at the points: element matrices with k(x), sigma(x) given inside the elements (csrc/elmat.hip; DESIGN.md
+ * section 4.9.6) ----
+ * saamge_amd_element_matrices and saamge_amd_element_mass with a coefficient row per POINT in the place of one per element:
+ * coefq has NQ rows, row qp_ptr[e] + q belongs to point q of element e -- the indexing of saamge_amd_element_points / _eval, so
+ * that k(u_q) formed from the output of saamge_amd_element_eval goes in as it is.  saamge_amd/elmat_model.py
+ * (element_matrices_points, element_mass_points) defines every operation and the device gives the same bits.
+ * THE RULE of both calls is the type's MASS rule: the stiffness forms are integrated at the points of the mass rule here.  For
+ * the quadrilateral, the hexahedron, the wedge and the 9-node / 27-node types that is the rule of saamge_amd_element_matrices
+ * (equal coefficients at the points of an element give its bits); the triangle has 3 points here against 1 and the tetrahedron 4
+ * against 1 (the tetrahedron still gives the same bits, the triangle agrees to rounding), the 6-node triangle 6 against 3 and the
+ * 10-node tetrahedron 14 against 4: these agree to rounding with saamge_amd_element_matrices on affine elements and differ by the
+ * quadrature on curved ones, and a CURVED 6-node triangle or 10-node tetrahedron can be refused here for a non-positive
+ * determinant at a point saamge_amd_element_matrices does not have.
+ * saamge_amd_element_matrices_points: coefq NQ x ncoef row-major; kind, ncoef, the outputs (elmat_out NULL: the sizes only; the
+ * dof lists), info and the refusals are those of saamge_amd_element_matrices, with coefq in the place of coef.  Per point, kind
+ * 0: F_a = K_q G_a with K_q from the point's row; kind 1: lambda_q, mu_q of the point's row.
+ * saamge_amd_element_mass_points: coefq NQ doubles, s = (w det) coefq[qp_ptr[e] + q]; vdim, accumulate, elmat_inout, info and the
+ * refusals are those of saamge_amd_element_mass -- K(u) + sigma(u) M by a call of each with accumulate.
+ * Any pointer host or device, each on its own.  The checks of the arguments alone run before anything touches the device; the
+ * first element with a non-positive determinant is reported in info[6] and the output is then not to be relied on. */
+int saamge_amd_element_matrices_points(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                       const int *elem_to_vertex, int kind, int ncoef, const double *coefq /* NQ x ncoef */,
+                                       void *stream, double *elmat_out, int *dof_ptr_out, int *elem_to_dof_out, long long info[8]);
+int saamge_amd_element_mass_points(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                   const int *elem_to_vertex, int vdim, const double *coefq /* NQ */, void *stream, int accumulate,
+                                   double *elmat_inout, long long info[8]);
 /* ---- boundary forms computed on the device (csrc/elmat.hip) ----
  * The face mass (Robin: (c u, v) over faces) and the face loads (Neumann: (c g, v) over faces) of a list of NF faces, ADDED into
  * the packed matrices / vectors of the owning elements, so that the element matrices still sum to the operator and everything

@@ -412,6 +412,32 @@ inline ElementMatricesInfo element_errors_into(int NV, int dim, const double *co
     return r;
 }
 
+// == coefficients at the points (saamge_amd_element_matrices_points, saamge_amd_element_mass_points) ==
+// element_matrices_into / element_mass_into with a coefficient row per POINT of the mass rule in the place of one per element:
+// coefq NQ x ncoef (stiffness) or NQ (mass), row qp_ptr[e] + q for point q of element e, the indexing of element_points_into /
+// element_eval_into.  Both forms integrate with the mass rule here (saamge_amd.h).  Everything else as the calls they parallel.
+inline ElementMatricesInfo element_matrices_points_into(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                                        const int *elem_to_vertex, int kind, int ncoef, const double *coefq,
+                                                        double *elmat_out, int *dof_ptr_out = nullptr,
+                                                        int *elem_to_dof_out = nullptr, void *stream = nullptr) {
+    long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (saamge_amd_element_matrices_points(NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, kind, ncoef, coefq, stream, elmat_out,
+                                           dof_ptr_out, elem_to_dof_out, info))
+        throw std::runtime_error(saamge_amd_last_error());
+    const ElementMatricesInfo r = {info[0], info[1], info[2], info[3], info[4], info[5], info[6], info[7]};
+    return r;
+}
+inline ElementMatricesInfo element_mass_points_into(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                                    const int *elem_to_vertex, int vdim, const double *coefq, double *elmat_inout,
+                                                    bool accumulate = false, void *stream = nullptr) {
+    long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (saamge_amd_element_mass_points(NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, coefq, stream, accumulate ? 1 : 0,
+                                       elmat_inout, info))
+        throw std::runtime_error(saamge_amd_last_error());
+    const ElementMatricesInfo r = {info[0], info[1], info[2], info[3], info[4], info[5], info[6], info[7]};
+    return r;
+}
+
 // == boundary forms computed on the device (saamge_amd_boundary_mass, saamge_amd_boundary_loads) ==
 // The face mass / face loads of the NF listed faces (element face_elem[f], local face face_local[f]; local faces in
 // saamge_amd.h) added into the caller's packed matrices / vectors, each array a host or a device pointer; nullptr for

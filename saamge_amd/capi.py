@@ -43,6 +43,7 @@ SYMBOLS = [
     "saamge_amd_element_mass", "saamge_amd_element_loads", "saamge_amd_operator_assemble_rhs",
     "saamge_amd_boundary_mass", "saamge_amd_boundary_loads",
     "saamge_amd_element_points", "saamge_amd_element_eval", "saamge_amd_element_loads_points", "saamge_amd_element_errors",
+    "saamge_amd_element_matrices_points", "saamge_amd_element_mass_points",
     "saamge_amd_face_table_build", "saamge_amd_face_table_arrays", "saamge_amd_face_table_get", "saamge_amd_face_table_free",
     "saamge_amd_face_nodes", "saamge_amd_face_dofs",
     "saamge_amd_mesh_lift_order2", "saamge_amd_mesh_lift_arrays", "saamge_amd_mesh_lift_get", "saamge_amd_mesh_lift_free",
@@ -743,18 +744,19 @@ def ae_order(ND, elem_to_dof, elem_to_ae, nparts, mode, elem_ptr=None):
 ELEMENT_TYPES = ("triangles", "quadrilaterals", "tetrahedra", "wedges", "hexahedra")
 
 
-def _element_matrices_call(coords, elem_to_vertex, kind, coef, elem_ptr, stream, elmat, dof_ptr, e2d):
+def _element_matrices_call(coords, elem_to_vertex, kind, coef, elem_ptr, stream, elmat, dof_ptr, e2d,
+                           fn="saamge_amd_element_matrices"):
     """One saamge_amd_element_matrices call on prepared arrays; returns info (8 integers).  A refusal raises RuntimeError with
     the library's message, and `.info` on it holds what the call had filled in by then (info[6]: the first element with a
-    non-positive Jacobian)."""
+    non-positive Jacobian).  fn: the call itself or saamge_amd_element_matrices_points, which has its arguments (coef: coefq)."""
     NV, dim = int(coords.shape[0]), int(coords.shape[1])
     NE = len(elem_ptr) - 1 if elem_ptr is not None else int(elem_to_vertex.shape[0])
     nde = 0 if elem_ptr is not None else int(elem_to_vertex.shape[1])
     ncoef = 1 if len(coef.shape) == 1 else int(coef.shape[1])
     info = (C.c_longlong * 8)()
-    rc = load().saamge_amd_element_matrices(C.c_int(NV), C.c_int(dim), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(elem_ptr),
-                                            _ptr(elem_to_vertex), C.c_int(int(kind)), C.c_int(ncoef), _ptr(coef),
-                                            C.c_void_p(stream), _ptr(elmat), _ptr(dof_ptr), _ptr(e2d), info)
+    rc = getattr(load(), fn)(C.c_int(NV), C.c_int(dim), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(elem_ptr),
+                             _ptr(elem_to_vertex), C.c_int(int(kind)), C.c_int(ncoef), _ptr(coef),
+                             C.c_void_p(stream), _ptr(elmat), _ptr(dof_ptr), _ptr(e2d), info)
     if rc != 0:
         err = RuntimeError("saamge_amd: " + load().saamge_amd_last_error().decode())
         err.info = [int(v) for v in info]
@@ -789,6 +791,10 @@ def element_matrices(coords, elem_to_vertex, kind, coef, elem_ptr=None, device=F
     `Operator` and `Hierarchy.from_operator` unchanged; out: an array / tensor of that many doubles to write into instead of
     a new one.  dofs=True: (elmat, dof_ptr, elem_to_dof), the int32 dof lists the matrices are indexed by (elem_to_dof
     (NE, size) without elem_ptr, else flat)."""
+    return _element_matrices(coords, elem_to_vertex, kind, coef, elem_ptr, device, dofs, out, stream, "saamge_amd_element_matrices")
+
+
+def _element_matrices(coords, elem_to_vertex, kind, coef, elem_ptr, device, dofs, out, stream, fn):
     coords, e2v, coef, ep = _element_arrays(coords, elem_to_vertex, coef, elem_ptr)
     comp = int(coords.shape[1]) if kind == 1 else 1
     if ep is None:
@@ -807,7 +813,7 @@ def element_matrices(coords, elem_to_vertex, kind, coef, elem_ptr=None, device=F
     elmat = out if out is not None else new(doubles, np.float64, "float64")
     dof_ptr = new(NE + 1, np.int32, "int32") if dofs else None
     e2d = new(nconn * comp, np.int32, "int32") if dofs else None
-    _element_matrices_call(coords, e2v, kind, coef, ep, stream, elmat, dof_ptr, e2d)
+    _element_matrices_call(coords, e2v, kind, coef, ep, stream, elmat, dof_ptr, e2d, fn)
     if ep is None:
         size = int(e2v.shape[1]) * comp
         elmat = elmat.reshape(NE, size, size)
@@ -981,6 +987,47 @@ def element_errors(coords, elem_to_vertex, u, exq=None, exgradq=None, vdim=1, el
         C.c_int(NV), C.c_int(dim), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_int(vdim), _ptr(_doubles(u)),
         _ptr(_doubles(exq)), _ptr(_doubles(exgradq)), C.c_void_p(stream), _ptr(err), info), info)
     return err.reshape(NE, 2)
+
+
+# ---- coefficients at the points (elmat_model.element_matrices_points / element_mass_points) ----
+def element_matrices_points(coords, elem_to_vertex, kind, coefq, elem_ptr=None, device=False, dofs=False, out=None, stream=0):
+    """saamge_amd_element_matrices_points: `element_matrices` with a coefficient row per POINT of `element_points` in the place
+    of one per element -- coefq (NQ,) or (NQ, ncoef), row qp_ptr[e] + q for point q of element e (what `element_eval` returns is
+    indexed so).  Both forms are integrated with the type's MASS rule here; everything else -- kinds, ncoef, the layout, device=,
+    dofs=, out=, stream=, the refusals -- as `element_matrices`.  A curved 6-node triangle / 10-node tetrahedron can be refused
+    here at a point `element_matrices` does not have."""
+    return _element_matrices(coords, elem_to_vertex, kind, coefq, elem_ptr, device, dofs, out, stream,
+                             "saamge_amd_element_matrices_points")
+
+
+def element_matrices_points_info(coords, elem_to_vertex, kind, coefq, elem_ptr=None, stream=0):
+    """The sizes-only call (elmat_out = NULL) of `element_matrices_points`: info as `element_matrices_info`."""
+    coords, e2v, coefq, ep = _element_arrays(coords, elem_to_vertex, coefq, elem_ptr)
+    return _element_matrices_call(coords, e2v, kind, coefq, ep, stream, None, None, None, "saamge_amd_element_matrices_points")
+
+
+def element_mass_points(coords, elem_to_vertex, coefq, vdim=1, elem_ptr=None, add_to=None, device=False, out=None, stream=0,
+                        sizes_only=False):
+    """saamge_amd_element_mass_points: `element_mass` with the coefficient coefq (NQ,) given at the points of `element_points`;
+    vdim, add_to (added IN PLACE: K(u) + sigma(u) M), device=, out=, stream=, sizes_only and the refusals as there."""
+    coords, e2v, coefq, ep = _element_arrays(coords, elem_to_vertex, coefq, elem_ptr)
+    vdim = int(vdim)
+    NV, dim, NE, nde, doubles = _mass_sizes(coords, e2v, ep, vdim, True)
+    info = (C.c_longlong * 8)()
+    if sizes_only:
+        elmat = None
+    elif add_to is not None:
+        elmat = add_to
+    else:
+        elmat = out if out is not None else _new_doubles(doubles, device)
+    got = _mass_call(lambda: load().saamge_amd_element_mass_points(
+        C.c_int(NV), C.c_int(dim), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_int(vdim), _ptr(coefq),
+        C.c_void_p(stream), C.c_int(1 if add_to is not None else 0), _ptr(elmat), info), info)
+    if sizes_only:
+        return got
+    if ep is None and add_to is None:
+        elmat = elmat.reshape(NE, nde * vdim, nde * vdim)
+    return elmat
 
 
 def _face_arrays(face_elem, face_local, coef):

@@ -902,6 +902,27 @@ int saamge_amd_element_errors(int NV, int dim, const double *coords, int NE, int
     SA_API_END
 }
 
+int saamge_amd_element_matrices_points(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                       const int *elem_to_vertex, int kind, int ncoef, const double *coefq, void *stream,
+                                       double *elmat_out, int *dof_ptr_out, int *elem_to_dof_out, long long info[8]) {
+    SA_API_BEGIN
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    element_matrices_points(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, kind, ncoef, coefq, elmat_out, dof_ptr_out,
+                            elem_to_dof_out, info);
+    SA_API_END
+}
+
+int saamge_amd_element_mass_points(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                   const int *elem_to_vertex, int vdim, const double *coefq, void *stream, int accumulate,
+                                   double *elmat_inout, long long info[8]) {
+    SA_API_BEGIN
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    element_mass_points(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, coefq, accumulate, elmat_inout, info);
+    SA_API_END
+}
+
 // ---- the faces of a mesh (mesh_faces.hip) -----------------------------------------------------------------------------------
 int saamge_amd_face_table_build(int NV, int dim, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex, void *stream,
                                 saamge_amd_face_table **out, long long info[8]) {

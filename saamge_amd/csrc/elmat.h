@@ -54,6 +54,17 @@ void element_errors(hipStream_t s, int NV, int dim, const double *coords, int NE
                     const int *elem_to_vertex, int vdim, const double *u, const double *exq, const double *exgradq, double *err_out,
                     long long info[8]);
 
+// Coefficients at the points (elmat_model.element_matrices_points / element_mass_points): the calls above with a coefficient row
+// per point of the MASS rule -- row qp_ptr[e] + q of coefq belongs to point q of element e -- in the place of one per element.
+// The arguments of saamge_amd_element_matrices_points (coefq NQ x ncoef; the stiffness forms integrate with the mass rule here)
+// and of saamge_amd_element_mass_points (coefq NQ); checks, outputs and info as element_matrices / element_mass.
+void element_matrices_points(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                             const int *elem_to_vertex, int kind, int ncoef, const double *coefq, double *elmat_out,
+                             int *dof_ptr_out, int *elem_to_dof_out, long long info[8]);
+void element_mass_points(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                         const int *elem_to_vertex, int vdim, const double *coefq, int accumulate, double *elmat_inout,
+                         long long info[8]);
+
 // A mesh argument brought to the device and checked: what every call of elmat.hip and of mesh_faces.hip starts with.  elem_ptr
 // NULL: NE elements of nde nodes each.  Host arrays are uploaded (the offsets first: they say how much of elem_to_vertex there
 // is), device arrays are used where they are.  Refused with `name` in front or by check_mesh_device: malformed offsets, a vertex

@@ -24,6 +24,9 @@
 // there, the squared errors per element -- has kernels on the first phases of load_kernel with a lane per (element, point,
 // component) after them (qp_points_kernel, qp_eval_kernel, qp_load_kernel, qp_error_kernel).
 //
+// Coefficients at those points -- the stiffness forms and the mass with a coefficient row per point in the place of one per
+// element -- run the bodies of em2_kernel and mass_kernel on the mass rule of all nine types (emkq_kernel, mass_kq_kernel).
+//
 // The boundary forms -- the mass and the loads of a list of faces, added into the owning elements' matrices and vectors -- have
 // kernels templated on the face type (bdr_mass_kernel, bdr_load_kernel) and run one pass per local face index.
 #include "elmat.h"
@@ -370,6 +373,7 @@ constexpr EmPoint p2s_point(int dim, int q) {
 constexpr int em2_points(int dim, int nd) { return p2s_type(dim, nd) ? dim + 1 : nd; }
 template <int DIM, int ND>
 struct Em2Table {
+    static constexpr int NQ = em2_points(DIM, ND);
     double dN[ND][em2_points(DIM, ND)][DIM];
     double w[em2_points(DIM, ND)];
 };
@@ -432,29 +436,50 @@ template <int KIND> struct Em2Cfg<3, 10, KIND> { static constexpr int BLOCK = 25
 //           order, that adds the point's term to the lane's accumulators -- the whole sum of an entry lives in one lane, so
 //           the bits are the model's, and no entry is computed twice
 //   tile    the entries and their mirror images to an LDS tile (over the dead gradients), written out as consecutive doubles
-template <int DIM, int ND, int KIND>
-__global__ __launch_bounds__((Em2Cfg<DIM, ND, KIND>::BLOCK)) void em2_kernel(int count, const int *__restrict__ list,
-                                                                           const int *__restrict__ eI, const int *__restrict__ eJ,
-                                                                           const roff_t *__restrict__ moff,
-                                                                           const double *__restrict__ coords,
-                                                                           const double *__restrict__ coef, int ncoef,
-                                                                           double *__restrict__ out, int *__restrict__ bad) {
-    typedef Em2Cfg<DIM, ND, KIND> Cfg;
+// K[i * DIM + j] from a row of ncoef coefficients (elmat_model._tensor): ncoef 1 fills the diagonal with c[0], DIM gives the
+// diagonal, more the symmetric tensor as xx, yy, zz, xy, yz, xz / xx, yy, xy
+template <int DIM>
+__device__ __forceinline__ void em_tensor(const double *c, int ncoef, double *K) {
+#pragma unroll
+    for (int i = 0; i < DIM * DIM; ++i) K[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < DIM; ++i) K[i * DIM + i] = ncoef == 1 ? c[0] : c[i];
+    if (ncoef > DIM) {
+        K[0 * DIM + 1] = K[1 * DIM + 0] = c[DIM];
+        if (DIM == 3) {
+            K[1 * DIM + DIM - 1] = K[(DIM - 1) * DIM + 1] = c[DIM + 1];
+            K[0 * DIM + DIM - 1] = K[(DIM - 1) * DIM + 0] = c[DIM + 2];
+        }
+    }
+}
+
+// The body serves two kernels.  em2_kernel: the order-2 types with their stiffness rule (Em2Table) and one coefficient row per
+// element (KQ false: coef + e * ncoef, expanded to K[i][j] / lambda, mu in the stage phase).  emkq_kernel, after the mass
+// tables: all nine types with their MASS rule (MassTable, the same dN[a][q][j] and w[q]) and one coefficient row per POINT (KQ
+// true): the stage phase copies the NQ * ncoef doubles of every element of the workgroup, at coef + qoff[e] * ncoef, as they
+// are; the G phase forms K_q from the row of ITS point -- the global q = q0 + qq, not the index in the pass -- and the entry
+// phase of elasticity reads lambda_q, mu_q of the point of its term.
+template <int DIM, int ND, int KIND, class Cfg, class Table, bool KQ>
+__device__ __forceinline__ void em2_body(const Table &T, int count, const int *__restrict__ list, const int *__restrict__ eI,
+                                         const int *__restrict__ eJ, const roff_t *__restrict__ moff,
+                                         const roff_t *__restrict__ qoff, const double *__restrict__ coords,
+                                         const double *__restrict__ coef, int ncoef, double *__restrict__ out,
+                                         int *__restrict__ bad) {
     constexpr int BLOCK = Cfg::BLOCK, EPB = Cfg::EPB, BS = Cfg::BS, QC = Cfg::QC;
-    constexpr int NQ = em2_points(DIM, ND), COMP = KIND ? DIM : 1, S = ND * COMP, SS = S * S;
+    constexpr int NQ = Table::NQ, COMP = KIND ? DIM : 1, S = ND * COMP, SS = S * S;
     constexpr int NB = ND / BS, NBP = NB * (NB + 1) / 2;      // blocks of nodes, pairs A <= B of them
     constexpr int DD = DIM * DIM, PW = DD + 1;                // a point keeps its cofactors and s
     constexpr int GW = KIND ? DIM : 2 * DIM;                  // a node keeps G_a, and F_a for diffusion
     constexpr int NACC = KIND ? DD : BS * BS;
     constexpr int NP = EPB * NQ * PW, NG = EPB * QC * ND * GW, NT = EPB * SS, WORK = NP + NG > NT ? NP + NG : NT;
+    constexpr int NK = KQ ? EPB * NQ * (KIND ? 2 : DIM * (DIM + 1) / 2) : EPB * DD;      // (the longest row a point may have)
     static_assert(EPB * NBP <= BLOCK && NQ % QC == 0 && ND % BS == 0 && NG >= EPB * NQ * DD && (KIND == 0 || BS == 1), "em2 plan");
     __shared__ double sX[EPB * ND * DIM];
-    __shared__ double sK[EPB * DD];                           // K[i][j], or lambda, mu
+    __shared__ double sK[NK];                                 // K[i][j], or lambda, mu; KQ: the rows of the points as given
     __shared__ double work[WORK];
     __shared__ roff_t obase[EPB];
     __shared__ int sE[EPB];                                   // the element of a slot, -1: none
     double *const sP = work, *const sG = work + NP, *const sJ = sG, *const tile = work;
-    const Em2Table<DIM, ND> &T = EM2_TABLE<DIM, ND>;
     const int tid = threadIdx.x;
     // ---- stage
     for (int idx = tid; idx < EPB * ND; idx += BLOCK) {
@@ -472,32 +497,36 @@ __global__ __launch_bounds__((Em2Cfg<DIM, ND, KIND>::BLOCK)) void em2_kernel(int
             if (a == 0) {
                 sE[el] = e;
                 obase[el] = moff ? moff[e] : (roff_t)e * SS;
-                const double *c = coef + (long)e * ncoef;
-                double *K = sK + el * DD;
-                if (KIND) {
-                    K[0] = c[0];
-                    K[1] = c[1];
-                } else {
-#pragma unroll
-                    for (int i = 0; i < DD; ++i) K[i] = 0.0;
-#pragma unroll
-                    for (int i = 0; i < DIM; ++i) K[i * DIM + i] = ncoef == 1 ? c[0] : c[i];
-                    if (ncoef > DIM) {                        // xx, yy, zz, xy, yz, xz / xx, yy, xy
-                        K[0 * DIM + 1] = K[1 * DIM + 0] = c[DIM];
-                        if (DIM == 3) {
-                            K[1 * DIM + DIM - 1] = K[(DIM - 1) * DIM + 1] = c[DIM + 1];
-                            K[0 * DIM + DIM - 1] = K[(DIM - 1) * DIM + 0] = c[DIM + 2];
-                        }
+                if constexpr (!KQ) {
+                    const double *c = coef + (long)e * ncoef;
+                    double *K = sK + el * DD;
+                    if (KIND) {
+                        K[0] = c[0];
+                        K[1] = c[1];
+                    } else {
+                        em_tensor<DIM>(c, ncoef, K);
                     }
                 }
             }
         } else if (a == 0) {
             sE[el] = -1;
+            if constexpr (!KQ) {
 #pragma unroll
-            for (int i = 0; i < DD; ++i) sK[el * DD + i] = 0.0;
+                for (int i = 0; i < DD; ++i) sK[el * DD + i] = 0.0;
+            }
         }
 #pragma unroll
         for (int d = 0; d < DIM; ++d) sX[idx * DIM + d] = x[d];
+    }
+    if constexpr (KQ) {       // the rows of the points: NQ * ncoef consecutive doubles per element, point q at (el * NQ + q) * ncoef
+        const int row = NQ * ncoef;
+        for (int idx = tid; idx < EPB * row; idx += BLOCK) {
+            const int el = idx / row;
+            const long slot = (long)blockIdx.x * EPB + el;
+            double c = 0.0;
+            if (slot < count) c = coef[qoff[list ? list[slot] : (int)slot] * ncoef + (idx - el * row)];
+            sK[idx] = c;
+        }
     }
     __syncthreads();
     // ---- J
@@ -576,6 +605,11 @@ __global__ __launch_bounds__((Em2Cfg<DIM, ND, KIND>::BLOCK)) void em2_kernel(int
             for (int i = 0; i < DIM; ++i) g[i] = G[i];
             if constexpr (KIND == 0) {
                 const double *K = sK + el * DD;
+                double Kq[KQ ? DD : 1];
+                if constexpr (KQ) {                           // K_q of THIS point, from its row
+                    em_tensor<DIM>(sK + (el * NQ + q) * ncoef, ncoef, Kq);
+                    K = Kq;
+                }
 #pragma unroll
                 for (int i = 0; i < DIM; ++i) {
                     double t = K[i * DIM + 0] * G[0] + K[i * DIM + 1] * G[1];
@@ -611,7 +645,8 @@ __global__ __launch_bounds__((Em2Cfg<DIM, ND, KIND>::BLOCK)) void em2_kernel(int
                         acc[k * BS + l] = acc[k * BS + l] + term;
                     }
             } else {
-                const double lam = sK[eb * DD], mu = sK[eb * DD + 1];
+                const double *c = KQ ? sK + (eb * NQ + q0 + qq) * 2 : sK + eb * DD;      // (KQ: the row of the term's point)
+                const double lam = c[0], mu = c[1];
                 double Ga[DIM], Gb[DIM];
 #pragma unroll
                 for (int i = 0; i < DIM; ++i) {
@@ -662,6 +697,17 @@ __global__ __launch_bounds__((Em2Cfg<DIM, ND, KIND>::BLOCK)) void em2_kernel(int
         const int l = t / SS;
         out[obase[l] + (t - l * SS)] = tile[t];
     }
+}
+
+template <int DIM, int ND, int KIND>
+__global__ __launch_bounds__((Em2Cfg<DIM, ND, KIND>::BLOCK)) void em2_kernel(int count, const int *__restrict__ list,
+                                                                           const int *__restrict__ eI, const int *__restrict__ eJ,
+                                                                           const roff_t *__restrict__ moff,
+                                                                           const double *__restrict__ coords,
+                                                                           const double *__restrict__ coef, int ncoef,
+                                                                           double *__restrict__ out, int *__restrict__ bad) {
+    em2_body<DIM, ND, KIND, Em2Cfg<DIM, ND, KIND>, Em2Table<DIM, ND>, false>(EM2_TABLE<DIM, ND>, count, list, eI, eJ, moff, nullptr,
+                                                                             coords, coef, ncoef, out, bad);
 }
 
 // ---- mass matrices and load vectors ------------------------------------------------------------------------------------------
@@ -805,7 +851,8 @@ constexpr int load_epb(int nd) { return nd >= 27 ? 8 : (nd >= 8 ? 16 : 32); }
 // sC: c per element, sE: the element of a slot (-1: none); sJ and sD may lie over anything that is written after the barrier
 // that follows.
 // KEEP: the point's cofactors C[i][j] (elmat_model._cofactors) and det go to sP as DIM * DIM + 1 doubles per (element, point).
-template <int DIM, int ND, int EPB, bool KEEP = false>
+// CQ: the coefficient of a point stands in sS where its s goes, in the place of sC[el] (elmat_model.element_mass_points).
+template <int DIM, int ND, int EPB, bool KEEP = false, bool CQ = false>
 __device__ inline void mass_point_phases(const double *sX, const double *sD, const double *sC, const int *sE, double *sJ, double *sS,
                                          int *bad, double *sP = nullptr) {
     constexpr int NQ = MassTable<DIM, ND>::NQ, DD = DIM * DIM;
@@ -871,14 +918,14 @@ __device__ inline void mass_point_phases(const double *sX, const double *sD, con
         }
         if constexpr (KEEP) sP[idx * (DD + 1) + DD] = det;
         if (!(det > 0.0) && sE[el] >= 0) atomicMin(bad, sE[el]);
-        sS[idx] = (T.w[q] * det) * sC[el];
+        sS[idx] = (T.w[q] * det) * (CQ ? sS[idx] : sC[el]);
     }
     __syncthreads();
 }
 
 // stage of both kernels: coordinates, coefficient (coef nullptr: 1.0), element id, the rule's shape values and reference
-// gradients; src (nullptr: none): the nodal source (NV x VDIM) of the nodes to sF
-template <int DIM, int ND, int VDIM, int EPB>
+// gradients; src (nullptr: none): the nodal source (NV x VDIM) of the nodes to sF.  COEF false: sC is left to the caller.
+template <int DIM, int ND, int VDIM, int EPB, bool COEF = true>
 __device__ inline void mass_stage(int count, const int *__restrict__ list, const int *__restrict__ eI, const int *__restrict__ eJ,
                                   const double *__restrict__ coords, const double *__restrict__ coef,
                                   const double *__restrict__ src, double *sX, double *sC, int *sE, double *sN, double *sD,
@@ -905,11 +952,11 @@ __device__ inline void mass_stage(int count, const int *__restrict__ list, const
             }
             if (a == 0) {
                 sE[el] = e;
-                sC[el] = coef ? coef[e] : 1.0;
+                if constexpr (COEF) sC[el] = coef ? coef[e] : 1.0;
             }
         } else if (a == 0) {
             sE[el] = -1;
-            sC[el] = 0.0;
+            if constexpr (COEF) sC[el] = 0.0;
         }
 #pragma unroll
         for (int d = 0; d < DIM; ++d) sX[idx * DIM + d] = x[d];
@@ -932,11 +979,14 @@ __device__ inline void mass_stage(int count, const int *__restrict__ list, const
 //   entry   one lane per (element, node pair a <= b): the whole sum over the points, in ascending order, lives in the lane; it
 //           goes (is added) to the tile at (a, b) and (b, a) of every component
 //   tile    written out as consecutive doubles
-template <int DIM, int ND, int VDIM>
-__global__ __launch_bounds__(MASS_BLOCK) void mass_kernel(int count, const int *__restrict__ list, const int *__restrict__ eI,
-                                                          const int *__restrict__ eJ, const roff_t *__restrict__ moff,
-                                                          const double *__restrict__ coords, const double *__restrict__ coef,
-                                                          int accumulate, double *out, int *__restrict__ bad) {
+// The body serves mass_kernel (CQ false: coef one double per element) and mass_kq_kernel (CQ true: coef one double per POINT,
+// point q of element e at qoff[e] + q, staged into sS ahead of mass_stage, whose barrier covers it; the point phase replaces
+// it by s, so the workgroup takes no more LDS than mass_kernel's).
+template <int DIM, int ND, int VDIM, bool CQ>
+__device__ __forceinline__ void mass_body(int count, const int *__restrict__ list, const int *__restrict__ eI,
+                                          const int *__restrict__ eJ, const roff_t *__restrict__ moff,
+                                          const roff_t *__restrict__ qoff, const double *__restrict__ coords,
+                                          const double *__restrict__ coef, int accumulate, double *out, int *__restrict__ bad) {
     constexpr int BLOCK = MASS_BLOCK, EPB = mass_epb(ND, VDIM), NQ = MassTable<DIM, ND>::NQ, DD = DIM * DIM;
     constexpr int S = ND * VDIM, SS = S * S, NPAIR = ND * (ND + 1) / 2;
     constexpr int NT = EPB * SS, NJ = ND <= 8 ? 0 : EPB * NQ * DD;      // (order 1 keeps J in registers)
@@ -950,8 +1000,15 @@ __global__ __launch_bounds__(MASS_BLOCK) void mass_kernel(int count, const int *
     __shared__ int sE[EPB];
     double *const tile = work;
     const int tid = threadIdx.x;
-    mass_stage<DIM, ND, 1, EPB>(count, list, eI, eJ, coords, coef, nullptr, sX, sC, sE, sN, work + NJ, nullptr);
-    mass_point_phases<DIM, ND, EPB>(sX, work + NJ, sC, sE, work, sS, bad);      // (J and the gradients lie under the tile)
+    if constexpr (CQ) {
+        for (int idx = tid; idx < EPB * NQ; idx += BLOCK) {
+            const int el = idx / NQ;
+            const long slot = (long)blockIdx.x * EPB + el;
+            sS[idx] = slot < count ? coef[qoff[list ? list[slot] : (int)slot] + (idx - el * NQ)] : 0.0;
+        }
+    }
+    mass_stage<DIM, ND, 1, EPB, !CQ>(count, list, eI, eJ, coords, coef, nullptr, sX, sC, sE, sN, work + NJ, nullptr);
+    mass_point_phases<DIM, ND, EPB, false, CQ>(sX, work + NJ, sC, sE, work, sS, bad);      // (J and the gradients lie under the tile)
     if (!out) return;                             // (the same in every lane of the grid)
     if (tid < EPB) obase[tid] = sE[tid] < 0 ? 0 : (moff ? moff[sE[tid]] : (roff_t)sE[tid] * SS);
     __syncthreads();
@@ -992,6 +1049,52 @@ __global__ __launch_bounds__(MASS_BLOCK) void mass_kernel(int count, const int *
         const int l = t / SS;
         out[obase[l] + (t - l * SS)] = tile[t];
     }
+}
+
+template <int DIM, int ND, int VDIM>
+__global__ __launch_bounds__(MASS_BLOCK) void mass_kernel(int count, const int *__restrict__ list, const int *__restrict__ eI,
+                                                          const int *__restrict__ eJ, const roff_t *__restrict__ moff,
+                                                          const double *__restrict__ coords, const double *__restrict__ coef,
+                                                          int accumulate, double *out, int *__restrict__ bad) {
+    mass_body<DIM, ND, VDIM, false>(count, list, eI, eJ, moff, nullptr, coords, coef, accumulate, out, bad);
+}
+// coefq: one coefficient per point, point q of element e at qoff[e] + q
+template <int DIM, int ND, int VDIM>
+__global__ __launch_bounds__(MASS_BLOCK) void mass_kq_kernel(int count, const int *__restrict__ list, const int *__restrict__ eI,
+                                                             const int *__restrict__ eJ, const roff_t *__restrict__ moff,
+                                                             const roff_t *__restrict__ qoff, const double *__restrict__ coords,
+                                                             const double *__restrict__ coefq, int accumulate, double *out,
+                                                             int *__restrict__ bad) {
+    mass_body<DIM, ND, VDIM, true>(count, list, eI, eJ, moff, qoff, coords, coefq, accumulate, out, bad);
+}
+
+// ---- the element matrices with coefficients at the points (elmat_model.element_matrices_points) -------------------------------
+// em2_kernel's body on the MASS rule of every type, a coefficient row per point.  The plans of the order-1 types: one node pair
+// per lane, all points in one pass (the hexahedron of diffusion: two passes of 4, which halves the gradients kept), as many
+// elements as fill 256 lanes: 42 triangles (252 lanes), 25 quadrilaterals / tetrahedra (250), 12 wedges (252), 7 hexahedra (252).
+// The order-2 types keep Em2Cfg's plans; the 10-node tetrahedron has 14 points here and takes two passes of 7 (4 does not
+// divide 14).  The largest workgroups: the 27-node hexahedron (Em2Cfg's 27 / 53 KB plus the rows of its points) and the tiles of
+// elasticity of the wedge and the hexahedron (31 / 32 KB).
+template <int DIM, int ND, int KIND> struct EmKqCfg : Em2Cfg<DIM, ND, KIND> {};
+template <int KIND> struct EmKqCfg<2, 3, KIND> { static constexpr int BLOCK = 256, EPB = 42, BS = 1, QC = 3; };
+template <int KIND> struct EmKqCfg<2, 4, KIND> { static constexpr int BLOCK = 256, EPB = 25, BS = 1, QC = 4; };
+template <int KIND> struct EmKqCfg<3, 4, KIND> { static constexpr int BLOCK = 256, EPB = 25, BS = 1, QC = 4; };
+template <int KIND> struct EmKqCfg<3, 6, KIND> { static constexpr int BLOCK = 256, EPB = 12, BS = 1, QC = 6; };
+template <> struct EmKqCfg<3, 8, 0> { static constexpr int BLOCK = 256, EPB = 7, BS = 1, QC = 4; };
+template <> struct EmKqCfg<3, 8, 1> { static constexpr int BLOCK = 256, EPB = 7, BS = 1, QC = 8; };
+template <int KIND> struct EmKqCfg<3, 10, KIND> { static constexpr int BLOCK = 256, EPB = 4, BS = 1, QC = 7; };
+
+// coefq: NQ x ncoef, the row of point q of element e at (qoff[e] + q) * ncoef; everything else as em2_kernel
+template <int DIM, int ND, int KIND>
+__global__ __launch_bounds__((EmKqCfg<DIM, ND, KIND>::BLOCK)) void emkq_kernel(int count, const int *__restrict__ list,
+                                                                             const int *__restrict__ eI, const int *__restrict__ eJ,
+                                                                             const roff_t *__restrict__ moff,
+                                                                             const roff_t *__restrict__ qoff,
+                                                                             const double *__restrict__ coords,
+                                                                             const double *__restrict__ coefq, int ncoef,
+                                                                             double *__restrict__ out, int *__restrict__ bad) {
+    em2_body<DIM, ND, KIND, EmKqCfg<DIM, ND, KIND>, MassTable<DIM, ND>, true>(MASS_TABLE<DIM, ND>, count, list, eI, eJ, moff, qoff,
+                                                                              coords, coefq, ncoef, out, bad);
 }
 
 // the last phase of the load kernels: sQ holds s * fq per (element, point, component)
@@ -1544,6 +1647,7 @@ struct EmLaunch {
     int ncoef;
     double *out;
     int *bad;
+    const roff_t *qoff = nullptr;      // the offsets of the points: coef then holds a row per POINT (emkq_kernel, mass_kq_kernel)
 };
 
 template <int DIM, int ND, int KIND>
@@ -1560,8 +1664,30 @@ void em2_launch(const EmLaunch &L, int count, const int *list) {
                        L.eJ, L.moff, L.coords, L.coef, L.ncoef, L.out, L.bad);
     SA_HIP_CHECK(hipGetLastError());
 }
+template <int DIM, int ND, int KIND>
+void emkq_launch(const EmLaunch &L, int count, const int *list) {
+    typedef EmKqCfg<DIM, ND, KIND> Cfg;
+    hipLaunchKernelGGL((emkq_kernel<DIM, ND, KIND>), dim3((unsigned)div_up(count, Cfg::EPB)), dim3(Cfg::BLOCK), 0, L.s, count, list, L.eI,
+                       L.eJ, L.moff, L.qoff, L.coords, L.coef, L.ncoef, L.out, L.bad);
+    SA_HIP_CHECK(hipGetLastError());
+}
+template <int KIND>
+void emkq_launch_type(const EmLaunch &L, int type, int count, const int *list) {
+    switch (type) {
+        case 0: emkq_launch<2, 3, KIND>(L, count, list); break;
+        case 1: emkq_launch<2, 4, KIND>(L, count, list); break;
+        case 2: emkq_launch<3, 4, KIND>(L, count, list); break;
+        case 3: emkq_launch<3, 6, KIND>(L, count, list); break;
+        case 4: emkq_launch<3, 8, KIND>(L, count, list); break;
+        case 5: emkq_launch<2, 9, KIND>(L, count, list); break;
+        case 6: emkq_launch<3, 27, KIND>(L, count, list); break;
+        case 7: emkq_launch<2, 6, KIND>(L, count, list); break;
+        default: emkq_launch<3, 10, KIND>(L, count, list); break;
+    }
+}
 template <int KIND>
 void em_launch_type(const EmLaunch &L, int type, int count, const int *list) {
+    if (L.qoff) return emkq_launch_type<KIND>(L, type, count, list);
     switch (type) {
         case 0: em_launch<2, 3, KIND>(L, count, list); break;
         case 1: em_launch<2, 4, KIND>(L, count, list); break;
@@ -1577,7 +1703,13 @@ void em_launch_type(const EmLaunch &L, int type, int count, const int *list) {
 
 template <int DIM, int ND>
 void mass_launch(const EmLaunch &L, int vdim, int accumulate, int count, const int *list) {
-    if (vdim == 1)
+    if (L.qoff && vdim == 1)
+        hipLaunchKernelGGL((mass_kq_kernel<DIM, ND, 1>), dim3((unsigned)div_up(count, mass_epb(ND, 1))), dim3(MASS_BLOCK), 0, L.s, count,
+                           list, L.eI, L.eJ, L.moff, L.qoff, L.coords, L.coef, accumulate, L.out, L.bad);
+    else if (L.qoff)
+        hipLaunchKernelGGL((mass_kq_kernel<DIM, ND, DIM>), dim3((unsigned)div_up(count, mass_epb(ND, DIM))), dim3(MASS_BLOCK), 0, L.s,
+                           count, list, L.eI, L.eJ, L.moff, L.qoff, L.coords, L.coef, accumulate, L.out, L.bad);
+    else if (vdim == 1)
         hipLaunchKernelGGL((mass_kernel<DIM, ND, 1>), dim3((unsigned)div_up(count, mass_epb(ND, 1))), dim3(MASS_BLOCK), 0, L.s, count,
                            list, L.eI, L.eJ, L.moff, L.coords, L.coef, accumulate, L.out, L.bad);
     else
@@ -1694,21 +1826,51 @@ void em_refuse_bad(hipStream_t s, const std::string &name, const EmMesh &M, int 
     }
 }
 
-// the mass matrices (src nullptr) or the load vectors of the arguments of saamge_amd_element_mass / _loads, already checked
+// ---- the offsets of the points of the mass rule ------------------------------------------------------------------------------
+// the number of points of every element (its type has been checked)
+__global__ __launch_bounds__(256) void qp_count_kernel(int NE, int dim, const int *__restrict__ eI, int *__restrict__ cnt) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e < NE) cnt[e] = mass_points(dim, eI[e + 1] - eI[e]);
+}
+__global__ __launch_bounds__(256) void qp_offsets_kernel(int NE, int nq, roff_t *__restrict__ qoff) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e <= NE) qoff[e] = (roff_t)e * nq;
+}
+// qoff: the NE + 1 offsets on the device; returns NQ
+int64_t qp_offsets(hipStream_t s, int dim, int NE, int nde, const int *elem_ptr, const EmMesh &M, DBuf<roff_t> &qoff) {
+    qoff.alloc((size_t)NE + 1);
+    if (elem_ptr) {
+        DBuf<int> cnt((size_t)NE);
+        hipLaunchKernelGGL(qp_count_kernel, grid_flat(NE), dim3(256), 0, s, NE, dim, M.eI, cnt.p);
+        SA_HIP_CHECK(hipGetLastError());
+        exclusive_scan_off(s, NE, cnt.p, qoff.p);
+        return read_one(qoff.p + NE, s);
+    }
+    const int nq = mass_points(dim, nde);
+    hipLaunchKernelGGL(qp_offsets_kernel, grid_flat((long)NE + 1), dim3(256), 0, s, NE, nq, qoff.p);
+    SA_HIP_CHECK(hipGetLastError());
+    return (int64_t)NE * nq;
+}
+
+// the mass matrices (src nullptr) or the load vectors of the arguments of saamge_amd_element_mass / _loads, already checked;
+// at_points (saamge_amd_element_mass_points): coef holds one double per point of the mass rule
 void mass_or_loads(hipStream_t s, const std::string &name, int NV, int dim, const double *coords, int NE, int nde,
                    const int *elem_ptr, const int *elem_to_vertex, int vdim, const double *coef, const double *src, int accumulate,
-                   double *out, long long info[8]) {
+                   double *out, long long info[8], bool at_points = false) {
     if (NE == 0) return;
     EmMesh M;
     em_mesh(s, name, NV, dim, NE, nde, elem_ptr, elem_to_vertex, vdim, !src, M, info);
     DBuf<double> hold_X, hold_c, hold_src, hold_out;
+    DBuf<roff_t> qoff;
+    const size_t ncoef = at_points ? (size_t)qp_offsets(s, dim, NE, nde, elem_ptr, M, qoff) : (size_t)NE;
     EmLaunch L;
+    L.qoff = qoff.p;
     L.s = s;
     L.eI = elem_ptr ? M.eI : nullptr;
     L.eJ = M.eJ;
     L.moff = M.moff.p;
     L.coords = device_view(hold_X, coords, (size_t)NV * dim, s);
-    L.coef = coef ? device_view(hold_c, coef, (size_t)NE, s) : nullptr;
+    L.coef = coef ? device_view(hold_c, coef, ncoef, s) : nullptr;
     L.ncoef = 1;
     L.out = out;
     if (out && !is_device_ptr(out)) {
@@ -1727,15 +1889,6 @@ void mass_or_loads(hipStream_t s, const std::string &name, int NV, int dim, cons
 }
 
 // ---- data at the points of the mass rule --------------------------------------------------------------------------------------
-// the number of points of every element (its type has been checked)
-__global__ __launch_bounds__(256) void qp_count_kernel(int NE, int dim, const int *__restrict__ eI, int *__restrict__ cnt) {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e < NE) cnt[e] = mass_points(dim, eI[e + 1] - eI[e]);
-}
-__global__ __launch_bounds__(256) void qp_offsets_kernel(int NE, int nq, roff_t *__restrict__ qoff) {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e <= NE) qoff[e] = (roff_t)e * nq;
-}
 
 enum QpCall { QP_POINTS, QP_EVAL, QP_LOADS, QP_ERRORS };
 struct QpLaunch {
@@ -1819,20 +1972,8 @@ void points_call(QpCall call, hipStream_t s, const std::string &name, int NV, in
         return;
     }
     // ---- the offsets of the points
-    DBuf<roff_t> qoff((size_t)NE + 1);
-    int64_t NQ;
-    if (elem_ptr) {
-        DBuf<int> cnt((size_t)NE);
-        hipLaunchKernelGGL(qp_count_kernel, grid_flat(NE), dim3(256), 0, s, NE, dim, M.eI, cnt.p);
-        SA_HIP_CHECK(hipGetLastError());
-        exclusive_scan_off(s, NE, cnt.p, qoff.p);
-        NQ = read_one(qoff.p + NE, s);
-    } else {
-        const int nq = mass_points(dim, nde);
-        hipLaunchKernelGGL(qp_offsets_kernel, grid_flat((long)NE + 1), dim3(256), 0, s, NE, nq, qoff.p);
-        SA_HIP_CHECK(hipGetLastError());
-        NQ = (int64_t)NE * nq;
-    }
+    DBuf<roff_t> qoff;
+    const int64_t NQ = qp_offsets(s, dim, NE, nde, elem_ptr, M, qoff);
     if (info) info[5] = (long long)NQ;
     // ---- the determinants, before anything is written
     DBuf<double> hold_X, hold_c, hold_in, hold_e, hold_g;
@@ -2061,11 +2202,12 @@ void check_face_list(hipStream_t s, const std::string &name, int dim, int NE, co
     L.touched = w[2];
 }
 
-void element_matrices(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
-                      const int *elem_to_vertex, int kind, int ncoef, const double *coef, double *elmat_out, int *dof_ptr_out,
-                      int *elem_to_dof_out, long long info[8]) {
+namespace {
+// saamge_amd_element_matrices and, at_points, saamge_amd_element_matrices_points: coef then holds a row per point of the mass rule
+void stiffness(hipStream_t s, const std::string &name, bool at_points, int NV, int dim, const double *coords, int NE, int nde,
+               const int *elem_ptr, const int *elem_to_vertex, int kind, int ncoef, const double *coef, double *elmat_out,
+               int *dof_ptr_out, int *elem_to_dof_out, long long info[8]) {
     // ---- what needs no device
-    const std::string name(EM_NAME);
     em_begin(name, NV, dim, NE, info);
     SA_REQUIRE(kind == 0 || kind == 1, name + "kind must be 0 (diffusion) or 1 (elasticity)");
     if (kind == 1)
@@ -2073,7 +2215,8 @@ void element_matrices(hipStream_t s, int NV, int dim, const double *coords, int 
     else
         SA_REQUIRE(ncoef == 1 || ncoef == dim || ncoef == dim * (dim + 1) / 2,
                    name + "ncoef must be 1, dim or dim (dim + 1) / 2 for diffusion");
-    SA_REQUIRE(NE == 0 || (coords && elem_to_vertex && coef), name + "null argument: coords, elem_to_vertex or coef");
+    SA_REQUIRE(NE == 0 || (coords && elem_to_vertex && coef),
+               name + "null argument: coords, elem_to_vertex or " + (at_points ? "coefq" : "coef"));
     const int comp = kind ? dim : 1;
     em_check_sizes(name, NV, dim, NE, nde, elem_ptr, comp);
     if (NE == 0) return;
@@ -2084,13 +2227,16 @@ void element_matrices(hipStream_t s, int NV, int dim, const double *coords, int 
     const int64_t doubles = M.doubles;      // (info[5])
     // ---- the matrices (elmat_out NULL: the determinants are still checked)
     DBuf<double> hold_X, hold_c, hold_out;
+    DBuf<roff_t> qoff;
+    const size_t rows = at_points ? (size_t)qp_offsets(s, dim, NE, nde, elem_ptr, M, qoff) : (size_t)NE;
     EmLaunch L;
     L.s = s;
     L.eI = elem_ptr ? eI : nullptr;
     L.eJ = eJ;
     L.moff = M.moff.p;
+    L.qoff = qoff.p;
     L.coords = device_view(hold_X, coords, (size_t)NV * dim, s);
-    L.coef = device_view(hold_c, coef, (size_t)NE * ncoef, s);
+    L.coef = device_view(hold_c, coef, rows * ncoef, s);
     L.ncoef = ncoef;
     L.out = elmat_out;
     if (elmat_out && !is_device_ptr(elmat_out)) {
@@ -2121,6 +2267,35 @@ void element_matrices(hipStream_t s, int NV, int dim, const double *coords, int 
         SA_HIP_CHECK(hipMemcpyAsync(elem_to_dof_out, dofs.p, (size_t)nconn * comp * sizeof(int), hipMemcpyDefault, s));
     }
     SA_HIP_CHECK(hipStreamSynchronize(s));
+}
+}  // namespace
+
+void element_matrices(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                      const int *elem_to_vertex, int kind, int ncoef, const double *coef, double *elmat_out, int *dof_ptr_out,
+                      int *elem_to_dof_out, long long info[8]) {
+    stiffness(s, EM_NAME, false, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, kind, ncoef, coef, elmat_out, dof_ptr_out,
+              elem_to_dof_out, info);
+}
+
+void element_matrices_points(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                             const int *elem_to_vertex, int kind, int ncoef, const double *coefq, double *elmat_out,
+                             int *dof_ptr_out, int *elem_to_dof_out, long long info[8]) {
+    stiffness(s, "saamge_amd_element_matrices_points: ", true, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, kind, ncoef, coefq,
+              elmat_out, dof_ptr_out, elem_to_dof_out, info);
+}
+
+void element_mass_points(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                         const int *elem_to_vertex, int vdim, const double *coefq, int accumulate, double *elmat_inout,
+                         long long info[8]) {
+    const std::string name("saamge_amd_element_mass_points: ");
+    em_begin(name, NV, dim, NE, info);
+    SA_REQUIRE(vdim == 1 || vdim == dim, name + "vdim must be 1 or dim");
+    SA_REQUIRE(NE == 0 || coefq, name + "null argument: coefq");
+    SA_REQUIRE(NE == 0 || (coords && elem_to_vertex), name + "null argument: coords or elem_to_vertex");
+    SA_REQUIRE(!accumulate || elmat_inout, name + "null argument: accumulate needs the matrices in elmat_inout");
+    em_check_sizes(name, NV, dim, NE, nde, elem_ptr, vdim);
+    mass_or_loads(s, name, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, coefq, nullptr, accumulate ? 1 : 0, elmat_inout,
+                  info, true);
 }
 
 void element_mass(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,

@@ -48,7 +48,9 @@ are those of the scalar formulas).
   points       element_points, element_eval, element_loads_points and element_errors: the points of the mass rule, a nodal field
                and its gradient there, the loads of a source given there and the squared errors per element: defined after the
                boundary forms.
-  boundary     FACE_NODES, boundary_mass and boundary_loads: the face mass and the face loads of a list of (element, local face)
+  point coef   element_matrices_points and element_mass_points: the stiffness forms and the mass with a coefficient per point of
+               the mass rule in the place of the coefficient per element: defined at the end of this file.
+  boundary    FACE_NODES, boundary_mass and boundary_loads: the face mass and the face loads of a list of (element, local face)
                pairs, added into the owning elements' matrices and vectors: defined at the end of this file.
 """
 import numpy as np
@@ -204,18 +206,23 @@ def _tensor(coef, dim):
     return [[d[0], o[0], o[2]], [o[0], d[1], o[1]], [o[2], o[1], d[2]]]
 
 
-def _block(X, dim, nd, kind, coef):
+def _block(X, dim, nd, kind, coef, rows=None):
     """Matrices (n, size, size) of n elements of one type, and per element whether a det was not positive.  The node pairs
-    (a, b) with a <= b are the lanes of one vector: every line below is the scalar formula of the entry, elementwise."""
+    (a, b) with a <= b are the lanes of one vector: every line below is the scalar formula of the entry, elementwise.
+    rows None: coef holds one row per element and the rule is the type's stiffness rule.  Otherwise (element_matrices_points)
+    the rule is the type's MASS rule and point q of element k takes the row rows[k] + q of coef; nothing else differs."""
     n = X.shape[0]
     size = nd if kind == 0 else dim * nd
     bad = np.zeros(n, bool)
-    K = _tensor(coef, dim) if kind == 0 else None
     pa, pb = np.triu_indices(nd)                                     # the pairs a <= b
     acc = np.zeros((n, len(pa)) if kind == 0 else (n, len(pa), dim, dim))
+    npoints, gradients, weight = (NPOINTS, reference_gradients, point_weight) if rows is None else \
+        (MASS_NPOINTS, mass_reference_gradients, mass_point_weight)
     with np.errstate(all="ignore"):
-        for q in range(NPOINTS[(dim, nd)]):
-            dN = reference_gradients(dim, nd, q)
+        for q in range(npoints[(dim, nd)]):
+            cq = coef if rows is None else coef[rows + q]
+            K = _tensor(cq, dim) if kind == 0 else None
+            dN = gradients(dim, nd, q)
             J = [[None] * dim for _ in range(dim)]
             for i in range(dim):
                 for j in range(dim):
@@ -225,7 +232,7 @@ def _block(X, dim, nd, kind, coef):
                     J[i][j] = s
             C, det = _cofactors(J, dim)
             bad |= ~(det > 0.0)
-            s = (point_weight(dim, nd, q) / det)[:, None]
+            s = (weight(dim, nd, q) / det)[:, None]
             dA = np.array(dN)                                        # (nd, dim)
             G = []                                                   # G[i]: (n, nd), component i of every node's gradient
             for i in range(dim):
@@ -244,7 +251,7 @@ def _block(X, dim, nd, kind, coef):
                 term = s * _dot(F, Gb, dim)
                 acc = acc + term
             else:
-                lam, mu = coef[:, 0][:, None], coef[:, 1][:, None]
+                lam, mu = cq[:, 0][:, None], cq[:, 1][:, None]
                 md = mu * _dot(Ga, Gb, dim)
                 for i in range(dim):
                     for j in range(dim):                             # (on a == b the entries with i > j are not used)
@@ -438,9 +445,9 @@ def shape_values(dim, nd, q):
     raise ValueError("%d nodes: no supported element type in %dD" % (nd, dim))
 
 
-def _mass_points(X, dim, nd, c):
+def _mass_points(X, dim, nd, c, rows=None):
     """Per point of the mass rule: (N, s) with s = (weight * det) * c over the n elements of X, and per element whether a det
-    was not positive."""
+    was not positive.  rows (element_mass_points): c holds one coefficient per point, point q of element k takes c[rows[k] + q]."""
     bad = np.zeros(X.shape[0], bool)
     out = []
     with np.errstate(all="ignore"):
@@ -455,16 +462,17 @@ def _mass_points(X, dim, nd, c):
                     J[i][j] = t
             _, det = _cofactors(J, dim)
             bad |= ~(det > 0.0)
-            out.append((shape_values(dim, nd, q), (mass_point_weight(dim, nd, q) * det) * c))
+            cq = c if rows is None else c[rows + q]
+            out.append((shape_values(dim, nd, q), (mass_point_weight(dim, nd, q) * det) * cq))
     return out, bad
 
 
-def _mass_block(X, dim, nd, c):
-    """Scalar mass matrices (n, nd, nd) of n elements of one type."""
+def _mass_block(X, dim, nd, c, rows=None):
+    """Scalar mass matrices (n, nd, nd) of n elements of one type; rows: as in _mass_points."""
     n = X.shape[0]
     pa, pb = np.triu_indices(nd)
     acc = np.zeros((n, len(pa)))
-    points, bad = _mass_points(X, dim, nd, c)
+    points, bad = _mass_points(X, dim, nd, c, rows)
     with np.errstate(all="ignore"):
         for N, s in points:
             NN = np.array([N[a] * N[b] for a, b in zip(pa, pb)])
@@ -995,4 +1003,81 @@ def element_errors(coords, elem_to_vertex, u, exq=None, exgradq=None, vdim=1, el
                     acc1 = acc1 + term
             out[ids, 0], out[ids, 1] = acc0, acc1
     _refuse_det(bad)
+    return out
+
+
+# ---- coefficients at the points: the stiffness forms and the mass with one coefficient per point of the mass rule ----------------------
+#   points       those of the type's MASS rule for both forms (MASS_NPOINTS, mass_reference_gradients, mass_point_weight), so that
+#                one point index serves all point data: row qp_ptr[e] + q of coefq belongs to point q of element e, the indexing of
+#                element_points and element_eval.  For the quadrilateral, hexahedron, wedge and their order-2 relatives this is the
+#                stiffness rule of element_matrices; the triangle has 3 points here against 1, the tetrahedron 4 against 1, the
+#                6-node triangle 6 against 3 and the 10-node tetrahedron 14 against 4.
+#   stiffness    per point everything is _block's: J over the nodes ascending, _cofactors, s = weight / det, G_a, then kind 0
+#                F_a = K_q G_a with K_q = _tensor of the POINT's row (ncoef 1, dim or dim (dim + 1) / 2, the missing entries 0.0 and
+#                multiplied like any other), kind 1 the term with lambda_q, mu_q of the point's row; the terms are added over the
+#                points ascending from 0.0.  The packed layout and dof_lists are element_matrices'.
+#   mass         element_mass with s = (weight * det) * coefq[qp_ptr[e] + q] in _mass_points; coefq (NQ,).
+#   refused      what the form they parallel refuses, in its order, with coefq (of the wrong size) in the place of coef; ElementError
+#                names the smallest element whose det is not positive at a point of the MASS rule: a curved 6-node triangle or
+#                10-node tetrahedron can be refused here at a point element_matrices does not have.
+def element_matrices_points(coords, elem_to_vertex, kind, coefq, elem_ptr=None):
+    """The element matrices with the coefficients coefq (NQ, ncoef) or (NQ,) given at the points of element_points: (NE, size, size)
+    when elem_ptr is None, else packed."""
+    if kind not in (0, 1):
+        raise ValueError("kind: 0 (diffusion) or 1 (elasticity)")
+    X, dim, ep, e2v, nd, _, qp = _points_mesh(coords, elem_to_vertex, elem_ptr, 1)
+    NE, NQ = len(nd), int(qp[-1])
+    if coefq is None:
+        raise ValueError("coefq: (NQ, ncoef) is needed")
+    coefq = np.asarray(coefq, np.float64)
+    if NQ == 0:
+        coefq = np.zeros((0, allowed_ncoef(dim, kind)[0]))
+    elif coefq.size % NQ or coefq.size == 0:
+        raise ValueError("coefq: (NQ, ncoef) is needed")
+    else:
+        coefq = coefq.reshape(NQ, -1)
+    if coefq.shape[1] not in allowed_ncoef(dim, kind):
+        raise ValueError("ncoef = %d is not allowed for kind %d in %dD" % (coefq.shape[1], kind, dim))
+    comp = 1 if kind == 0 else dim
+    moff = np.concatenate([[0], np.cumsum((nd * comp) ** 2)])
+    out = np.zeros(int(moff[-1]))
+    bad = np.zeros(NE, bool)
+    for c, ids, v in _types(nd, ep, e2v):
+        blk, bad[ids] = _block(X[v], dim, c, kind, coefq, qp[ids])
+        out[moff[ids][:, None] + np.arange((c * comp) ** 2)] = blk.reshape(len(ids), -1)
+    _refuse_det(bad)
+    if elem_ptr is None:
+        return out.reshape(NE, nd[0] * comp, nd[0] * comp) if NE else out.reshape(0, 0, 0)
+    return out
+
+
+def element_mass_points(coords, elem_to_vertex, coefq, vdim=1, elem_ptr=None, add_to=None):
+    """The mass matrices with the coefficient coefq (NQ,) given at the points of element_points, in the layout of element_mass;
+    add_to as there."""
+    X, dim, ep, e2v, nd, vdim, qp = _points_mesh(coords, elem_to_vertex, elem_ptr, vdim)
+    NE, NQ = len(nd), int(qp[-1])
+    if coefq is None:
+        raise ValueError("coefq: (NQ,) is needed")
+    coefq = np.asarray(coefq, np.float64).reshape(-1)
+    if len(coefq) != NQ:
+        raise ValueError("coefq: (NQ,) is needed")
+    moff = np.concatenate([[0], np.cumsum((nd * vdim) ** 2)])
+    out = np.zeros(int(moff[-1]))
+    bad = np.zeros(NE, bool)
+    for c, ids, v in _types(nd, ep, e2v):
+        m, bad[ids] = _mass_block(X[v], dim, c, coefq, qp[ids])
+        if vdim > 1:
+            full = np.zeros((len(ids), c, vdim, c, vdim))
+            for i in range(vdim):
+                full[:, :, i, :, i] = m
+            m = full
+        out[moff[ids][:, None] + np.arange((c * vdim) ** 2)] = m.reshape(len(ids), -1)
+    _refuse_det(bad)
+    if add_to is not None:
+        base = np.asarray(add_to, np.float64).ravel()
+        if len(base) != len(out):
+            raise ValueError("add_to: the layout of the result is needed")
+        out = base + out
+    if elem_ptr is None:
+        return out.reshape(NE, nd[0] * vdim, nd[0] * vdim) if NE else out.reshape(0, 0, 0)
     return out

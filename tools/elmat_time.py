@@ -7,7 +7,7 @@ warm-up, `--reps` repetitions (all listed).  One JSON line per case.
 
     python tools/elmat_time.py [--hex 128,256] [--elasticity 64] [--q2-hex 64,128] [--q2-elasticity 32,64] [--quad9 2048]
                                [--reps 3] [--host-reps 3] [--hbm-gbs 8000] [--fp64-gops 39300] [--no-host] [--no-mass]
-                               [--rhs 256] [--boundary] [--p2-simplex] [--p2-tet 64] [--p2-tri 2048] [--points]
+                               [--rhs 256] [--boundary] [--p2-simplex] [--p2-tet 64] [--p2-tri 2048] [--points] [--point-coef]
 
 Beside every stiffness case, on the same mesh and in the same run (--no-mass: not): the mass matrices of the same layout
 (saamge_amd_element_mass; vdim 1 beside diffusion, dim beside elasticity), written (`<case>:mass`) and added to the stiffness
@@ -31,6 +31,15 @@ the yardstick (`yardstick_fraction_of_bound`, or `yardstick_ms` for the boundary
 _errors with both columns; vdim 1) on Q1 hexes 128^3 and 256^3, Q2 hexes 64^3 and the 10-node tetrahedra of the 64^3 split, same
 protocol; `bound_bytes` is what the call must move -- coordinates, vertex lists, nodal and point inputs read once, outputs
 written once -- and `hbm_bound_ms` that at --hbm-gbs; after them saamge_amd_element_loads on the same mesh in the same run.
+
+--point-coef: only the element matrices with coefficients at the points (saamge_amd_element_matrices_points: diffusion with a
+symmetric tensor per point, elasticity; saamge_amd_element_mass_points written and accumulated, vdim 1) on Q1 hexes 128^3, Q2
+hexes 64^3 and the 10-node tetrahedra of the 64^3 split, same protocol; directly after each, in the same run, the call it
+parallels with per-element coefficients (saamge_amd_element_matrices / _mass), the yardstick.  `bound_bytes` is what the call
+must move (coordinates, vertex lists and coefficients read once, the matrices written once -- read and written for
+accumulate), `hbm_bound_ms` that at --hbm-gbs, `expected_extra_ms` the coefficient bytes the new call reads beyond its
+yardstick at that rate, `ratio` new / yardstick (best of the repetitions) and `point_ratio` the points of the mass rule over the
+points of the yardstick's rule.
 
 The vertices are jittered by 0.2 mesh widths, so no two elements are alike.  A case that does not fit is reported as skipped
 with the error.
@@ -72,6 +81,7 @@ def main():
     ap.add_argument("--boundary", action="store_true")
     ap.add_argument("--p2-simplex", action="store_true")
     ap.add_argument("--points", action="store_true")
+    ap.add_argument("--point-coef", action="store_true")
     ap.add_argument("--p2-tet", type=int, default=64)
     ap.add_argument("--p2-tri", type=int, default=2048)
     a = ap.parse_args()
@@ -285,6 +295,61 @@ def main():
             except (RuntimeError, MemoryError) as e:
                 print(json.dumps({"case": "points:" + name, "skipped": str(e)[:200]}), flush=True)
             X = e2v = u = fq = exg = qp = xq = gq = wdet = uq = vec = err = None
+            torch.cuda.empty_cache()
+            capi.release_cached_memory()
+        return
+
+    if a.point_coef:
+        def reps(call):
+            timed(call)                            # warm-up
+            return [round(timed(call)[0], 3) for _ in range(a.reps)]
+        for name, n, nd, stiff_points in [("hex128", 128, 8, 8), ("q2_hex64", 64, 27, 27), ("tet10_64", 64, 10, 4)]:
+            try:
+                X, e2v, g = mesh(n) if nd == 8 else (mesh_q2(n, 3) if nd == 27 else mesh_p2(n, 3)[:3])
+                NE = int(e2v.shape[0])
+                NQ = capi.element_points(X, e2v, sizes_only=True)[5]
+                nq = NQ // NE
+
+                def coefs(rows):
+                    """(symmetric tensor, lambda / mu, scalar) with `rows` rows: the diagonal in [0.5, 2), off it in [-0.2, 0.2]"""
+                    k = 0.5 + 1.5 * torch.rand((rows, 6), generator=g, device=dev, dtype=torch.float64)
+                    k[:, 3:] = (k[:, 3:] - 1.25) * (0.4 / 1.5)
+                    return k, 0.5 + 1.5 * torch.rand((rows, 2), generator=g, device=dev, dtype=torch.float64), k[:, 0].contiguous()
+                kq, lq, sq = coefs(NQ)
+                ke, le, se = coefs(NE)
+                out = torch.zeros(NE * (nd * 3) ** 2, dtype=torch.float64, device=dev)
+                o1 = out[:NE * nd * nd]
+                st = stream
+                mesh_bytes = 8 * X.numel() + 4 * e2v.numel()
+                pairs = [
+                    ("diffusion_sym", 8 * o1.numel(), 6,
+                     lambda: capi.element_matrices_points(X, e2v, 0, kq, device=True, out=o1, stream=st()),
+                     lambda: capi.element_matrices(X, e2v, 0, ke, device=True, out=o1, stream=st())),
+                    ("elasticity", 8 * out.numel(), 2,
+                     lambda: capi.element_matrices_points(X, e2v, 1, lq, device=True, out=out, stream=st()),
+                     lambda: capi.element_matrices(X, e2v, 1, le, device=True, out=out, stream=st())),
+                    ("mass", 8 * o1.numel(), 1,
+                     lambda: capi.element_mass_points(X, e2v, sq, out=o1, stream=st()),
+                     lambda: capi.element_mass(X, e2v, se, out=o1, stream=st())),
+                    ("mass_accumulate", 16 * o1.numel(), 1,
+                     lambda: capi.element_mass_points(X, e2v, sq, add_to=o1, stream=st()),
+                     lambda: capi.element_mass(X, e2v, se, add_to=o1, stream=st())),
+                ]
+                for tag, out_bytes, ncoef, new, old in pairs:
+                    t_new, t_old = reps(new), reps(old)
+                    b_new, b_old = mesh_bytes + out_bytes + 8 * ncoef * NQ, mesh_bytes + out_bytes + 8 * ncoef * NE
+                    ms = lambda b: round(1e3 * b / (a.hbm_gbs * 1e9), 4)
+                    print(json.dumps({"case": "point_coef:%s:%s" % (name, tag), "elements": NE, "points": NQ, "device_ms": t_new,
+                                      "bound_bytes": int(b_new), "hbm_bound_ms": ms(b_new),
+                                      "fraction_of_bound": round(ms(b_new) / min(t_new), 4),
+                                      "yardstick_ms": t_old, "yardstick_bound_bytes": int(b_old), "yardstick_hbm_bound_ms": ms(b_old),
+                                      "yardstick_fraction_of_bound": round(ms(b_old) / min(t_old), 4),
+                                      "expected_extra_ms": ms(b_new - b_old), "measured_extra_ms": round(min(t_new) - min(t_old), 3),
+                                      "ratio": round(min(t_new) / min(t_old), 3),
+                                      "point_ratio": 1.0 if tag.startswith("mass") else round(nq / stiff_points, 3)}), flush=True)
+            except (RuntimeError, MemoryError) as e:
+                print(json.dumps({"case": "point_coef:" + name, "skipped": str(e)[:200]}), flush=True)
+            X = e2v = kq = lq = sq = ke = le = se = out = o1 = None
             torch.cuda.empty_cache()
             capi.release_cached_memory()
         return
