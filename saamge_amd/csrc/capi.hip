@@ -816,8 +816,8 @@ int saamge_amd_element_matrices(int NV, int dim, const double *coords, int NE, i
     SA_API_BEGIN
     hipStream_t s = (hipStream_t)stream;
     ThreadStreamScope scope(s);
-    element_matrices(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, kind, ncoef, coef, elmat_out, dof_ptr_out,
-                     elem_to_dof_out, info);
+    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
+    element_matrices(s, m, kind, ncoef, coef, elmat_out, dof_ptr_out, elem_to_dof_out, info);
     SA_API_END
 }
 
@@ -827,7 +827,8 @@ int saamge_amd_element_mass(int NV, int dim, const double *coords, int NE, int n
     SA_API_BEGIN
     hipStream_t s = (hipStream_t)stream;
     ThreadStreamScope scope(s);
-    element_mass(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, coef, accumulate, elmat_inout, info);
+    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
+    element_mass(s, m, vdim, coef, accumulate, elmat_inout, info);
     SA_API_END
 }
 
@@ -837,7 +838,8 @@ int saamge_amd_element_loads(int NV, int dim, const double *coords, int NE, int 
     SA_API_BEGIN
     hipStream_t s = (hipStream_t)stream;
     ThreadStreamScope scope(s);
-    element_loads(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, coef, src, elvec_out, info);
+    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
+    element_loads(s, m, vdim, coef, src, elvec_out, info);
     SA_API_END
 }
 
@@ -847,7 +849,8 @@ int saamge_amd_boundary_mass(int NV, int dim, const double *coords, int NE, int 
     SA_API_BEGIN
     hipStream_t s = (hipStream_t)stream;
     ThreadStreamScope scope(s);
-    boundary_mass(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, vdim, coef, elmat_inout, info);
+    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
+    boundary_mass(s, m, NF, face_elem, face_local, vdim, coef, elmat_inout, info);
     SA_API_END
 }
 
@@ -857,8 +860,8 @@ int saamge_amd_boundary_loads(int NV, int dim, const double *coords, int NE, int
     SA_API_BEGIN
     hipStream_t s = (hipStream_t)stream;
     ThreadStreamScope scope(s);
-    boundary_loads(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, vdim, coef, g, elvec_inout,
-                   info);
+    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
+    boundary_loads(s, m, NF, face_elem, face_local, vdim, coef, g, elvec_inout, info);
     SA_API_END
 }
 
@@ -868,7 +871,8 @@ int saamge_amd_element_points(int NV, int dim, const double *coords, int NE, int
     SA_API_BEGIN
     hipStream_t s = (hipStream_t)stream;
     ThreadStreamScope scope(s);
-    element_points(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, qp_ptr_out, xq_out, wdet_out, info);
+    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
+    element_points(s, m, qp_ptr_out, xq_out, wdet_out, info);
     SA_API_END
 }
 
@@ -878,7 +882,8 @@ int saamge_amd_element_eval(int NV, int dim, const double *coords, int NE, int n
     SA_API_BEGIN
     hipStream_t s = (hipStream_t)stream;
     ThreadStreamScope scope(s);
-    element_eval(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, u, uq_out, gradq_out, info);
+    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
+    element_eval(s, m, vdim, u, uq_out, gradq_out, info);
     SA_API_END
 }
 
@@ -888,7 +893,8 @@ int saamge_amd_element_loads_points(int NV, int dim, const double *coords, int N
     SA_API_BEGIN
     hipStream_t s = (hipStream_t)stream;
     ThreadStreamScope scope(s);
-    element_loads_points(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, coef, fq, elvec_out, info);
+    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
+    element_loads_points(s, m, vdim, coef, fq, elvec_out, info);
     SA_API_END
 }
 
@@ -898,7 +904,8 @@ int saamge_amd_element_errors(int NV, int dim, const double *coords, int NE, int
     SA_API_BEGIN
     hipStream_t s = (hipStream_t)stream;
     ThreadStreamScope scope(s);
-    element_errors(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, u, exq, exgradq, err_out, info);
+    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
+    element_errors(s, m, vdim, u, exq, exgradq, err_out, info);
     SA_API_END
 }
 
@@ -908,8 +915,8 @@ int saamge_amd_element_matrices_points(int NV, int dim, const double *coords, in
     SA_API_BEGIN
     hipStream_t s = (hipStream_t)stream;
     ThreadStreamScope scope(s);
-    element_matrices_points(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, kind, ncoef, coefq, elmat_out, dof_ptr_out,
-                            elem_to_dof_out, info);
+    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
+    element_matrices_points(s, m, kind, ncoef, coefq, elmat_out, dof_ptr_out, elem_to_dof_out, info);
     SA_API_END
 }
 
@@ -919,7 +926,8 @@ int saamge_amd_element_mass_points(int NV, int dim, const double *coords, int NE
     SA_API_BEGIN
     hipStream_t s = (hipStream_t)stream;
     ThreadStreamScope scope(s);
-    element_mass_points(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, coefq, accumulate, elmat_inout, info);
+    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
+    element_mass_points(s, m, vdim, coefq, accumulate, elmat_inout, info);
     SA_API_END
 }
 

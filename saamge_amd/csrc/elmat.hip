@@ -29,8 +29,15 @@
 //
 // The boundary forms -- the mass and the loads of a list of faces, added into the owning elements' matrices and vectors -- have
 // kernels templated on the face type (bdr_mass_kernel, bdr_load_kernel) and run one pass per local face index.
+//
+// Where things are.  elmat_ref.h (plain C++, held to the model by a host test): the shape functions of every type, the rules, the
+// table builders, the list of the types with with_elem_type / with_face_type / with_vdim, the one dispatch.  This file: the
+// device objects of the tables, the kernels with the pieces they share (em_cofactors, em_write_tile), one launcher per family
+// that turns a type index into a launch (em_launch_type, mass_launch_type, qp_launch_type, bdr_launch_face), the frame of a
+// call (EmFrame: mesh, launch arguments, outputs on the host or the device, the bad word, the loop over the types, the
+// refusal, the copy home) and the four drivers on it (stiffness, mass_or_loads, points_call, boundary_forms).  DESIGN.md 4.9.7.
 #include "elmat.h"
-#include "elmat_types.h"
+#include "elmat_ref.h"
 
 #include <algorithm>
 #include <climits>
@@ -47,86 +54,30 @@ namespace saamge_amd {
 
 namespace {
 
-// ---- the rules: the literals of elmat_model.py --------------------------------------------------------------------------
-constexpr double EM_GAUSS[2] = {0.21132486540518713, 0.7886751345948129};
-constexpr double EM_TRI_A = 0.16666666666666666, EM_TRI_B = 0.6666666666666666;
-constexpr int EM_QUAD_LOC[4][2] = {{0, 0}, {1, 0}, {1, 1}, {0, 1}};
-constexpr double EM_TRI_D[3][2] = {{-1.0, -1.0}, {1.0, 0.0}, {0.0, 1.0}};
-constexpr double EM_TET_D[4][3] = {{-1.0, -1.0, -1.0}, {1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
-constexpr double EM_WEDGE_TRI[3][2] = {{EM_TRI_A, EM_TRI_A}, {EM_TRI_B, EM_TRI_A}, {EM_TRI_A, EM_TRI_B}};
-
-// points of the rule, weight of one point
-template <int DIM, int ND> struct EmType;
-template <> struct EmType<2, 3> { static constexpr int NQ = 1; static constexpr double W = 0.5; };
-template <> struct EmType<2, 4> { static constexpr int NQ = 4; static constexpr double W = 0.25; };
-template <> struct EmType<3, 4> { static constexpr int NQ = 1; static constexpr double W = 0.16666666666666666; };
-template <> struct EmType<3, 6> { static constexpr int NQ = 6; static constexpr double W = 0.08333333333333333; };
-template <> struct EmType<3, 8> { static constexpr int NQ = 8; static constexpr double W = 0.125; };
-
-// (the type indices -- EM_TYPES, em_type_index, EM_TYPE_ND -- and the local faces are in elmat_types.h)
-
-constexpr double em_f(int l, double p) { return l ? p : 1.0 - p; }
-constexpr double em_df(int l) { return l ? 1.0 : -1.0; }
-
-template <int DIM, int ND>
-struct EmGrad {
-    double v[ND][DIM];
-};
-// gradients of the reference shape functions at point q (elmat_model.reference_gradients), folded at compile time
-template <int DIM, int ND>
-constexpr EmGrad<DIM, ND> em_ref_grad(int q) {
-    EmGrad<DIM, ND> g{};
-    if constexpr (DIM == 2 && ND == 3) {
-        for (int a = 0; a < 3; ++a)
-            for (int j = 0; j < 2; ++j) g.v[a][j] = EM_TRI_D[a][j];
-    } else if constexpr (DIM == 3 && ND == 4) {
-        for (int a = 0; a < 4; ++a)
-            for (int j = 0; j < 3; ++j) g.v[a][j] = EM_TET_D[a][j];
-    } else if constexpr (DIM == 2 && ND == 4) {
-        const double px = EM_GAUSS[q & 1], py = EM_GAUSS[(q >> 1) & 1];
-        for (int a = 0; a < 4; ++a) {
-            const int lx = EM_QUAD_LOC[a][0], ly = EM_QUAD_LOC[a][1];
-            g.v[a][0] = em_df(lx) * em_f(ly, py);
-            g.v[a][1] = em_f(lx, px) * em_df(ly);
-        }
-    } else if constexpr (DIM == 3 && ND == 8) {
-        const double px = EM_GAUSS[q & 1], py = EM_GAUSS[(q >> 1) & 1], pz = EM_GAUSS[(q >> 2) & 1];
-        for (int a = 0; a < 8; ++a) {
-            const int lx = EM_HEX_LOC[a][0], ly = EM_HEX_LOC[a][1], lz = EM_HEX_LOC[a][2];
-            g.v[a][0] = em_df(lx) * (em_f(ly, py) * em_f(lz, pz));
-            g.v[a][1] = em_df(ly) * (em_f(lx, px) * em_f(lz, pz));
-            g.v[a][2] = em_df(lz) * (em_f(lx, px) * em_f(ly, py));
-        }
-    } else {
-        static_assert(DIM == 3 && ND == 6, "no such element type");
-        const double xi = EM_WEDGE_TRI[q % 3][0], eta = EM_WEDGE_TRI[q % 3][1], zeta = EM_GAUSS[q / 3];
-        const double T[3] = {(1.0 - xi) - eta, xi, eta};
-        const double L[2] = {1.0 - zeta, zeta};
-        for (int a = 0; a < 2; ++a)
-            for (int i = 0; i < 3; ++i) {
-                g.v[a * 3 + i][0] = EM_TRI_D[i][0] * L[a];
-                g.v[a * 3 + i][1] = EM_TRI_D[i][1] * L[a];
-                g.v[a * 3 + i][2] = T[i] * em_df(a);
-            }
-    }
-    return g;
-}
-
-// the rule's table: one set of gradients per point.  The point loop of the kernel is a real loop (unrolled, the compiler forms
-// the Jacobians of all points ahead of the first barrier and runs out of registers) that reads its point's line through a
-// wave-uniform index.
-template <int DIM, int ND>
-struct EmTable {
-    EmGrad<DIM, ND> p[EmType<DIM, ND>::NQ];
-};
-template <int DIM, int ND>
-constexpr EmTable<DIM, ND> em_table() {
-    EmTable<DIM, ND> t{};
-    for (int q = 0; q < EmType<DIM, ND>::NQ; ++q) t.p[q] = em_ref_grad<DIM, ND>(q);
-    return t;
-}
+// ---- the reference elements: elmat_ref.h has the shape functions, the rules and the table builders; here are the device objects
+// the rule's table of the order-1 types: one set of gradients per point.  The point loop of em_kernel is a real loop (unrolled,
+// the compiler forms the Jacobians of all points ahead of the first barrier and runs out of registers) that reads its point's
+// line through a wave-uniform index.
 template <int DIM, int ND>
 __device__ const EmTable<DIM, ND> EM_TABLE = em_table<DIM, ND>();
+// the mass rule of all nine types: reference gradients, shape values, weights (RefTable)
+template <int DIM, int ND>
+__device__ const MassTable<DIM, ND> MASS_TABLE = mass_table<DIM, ND>();
+// the stiffness rule of the order-2 types, the two segments: only the tables that are not a mass table are objects of their own
+template <int DIM, int ND>
+__device__ const Em2Table<DIM, ND> EM2_TABLE = em2_table<DIM, ND>();
+template <int FN>
+__device__ const BdrTable<2, FN> SEG_TABLE = bdr_table<2, FN>();
+template <int DIM, int ND>
+__device__ __forceinline__ const Em2Table<DIM, ND> &em2_rule_table() {
+    if constexpr (EM2_IS_MASS<DIM, ND>) return MASS_TABLE<DIM, ND>;
+    else return EM2_TABLE<DIM, ND>;
+}
+template <int DIM, int FN>
+__device__ __forceinline__ const BdrTable<DIM, FN> &bdr_rule_table() {
+    if constexpr (DIM == 3) return MASS_TABLE<2, FN>;
+    else return SEG_TABLE<FN>;
+}
 
 // threads per workgroup: 256 where the tile of 256 / nd matrices stays within 40 KB of LDS, else one wavefront
 constexpr int em_block(int dim, int nd, int kind) {
@@ -135,6 +86,45 @@ constexpr int em_block(int dim, int nd, int kind) {
 }
 
 inline dim3 grid_flat(long n) { return dim3((unsigned)std::max<long>(1, (n + 255) / 256)); }
+
+// ---- pieces the kernels share (a piece is shared only where the kernel's gfx950 body stays the parent's) ------
+// the cofactors C[i][j] of J[i][j] and the determinant (elmat_model._cofactors), in the statement order of em_kernel and em2_body:
+// the order of the source decides the operand order of the compiled products
+template <int DIM>
+__device__ __forceinline__ void em_cofactors(const double (&J)[DIM][DIM], double (&C)[DIM][DIM], double &det) {
+    if constexpr (DIM == 2) {
+        det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+        C[0][0] = J[1][1];
+        C[0][1] = -J[1][0];
+        C[1][0] = -J[0][1];
+        C[1][1] = J[0][0];
+    } else {
+        C[0][0] = J[1][1] * J[2][2] - J[1][2] * J[2][1];
+        C[0][1] = J[1][2] * J[2][0] - J[1][0] * J[2][2];
+        C[0][2] = J[1][0] * J[2][1] - J[1][1] * J[2][0];
+        C[1][0] = J[0][2] * J[2][1] - J[0][1] * J[2][2];
+        C[1][1] = J[0][0] * J[2][2] - J[0][2] * J[2][0];
+        C[1][2] = J[0][1] * J[2][0] - J[0][0] * J[2][1];
+        C[2][0] = J[0][1] * J[1][2] - J[0][2] * J[1][1];
+        C[2][1] = J[0][2] * J[1][0] - J[0][0] * J[1][2];
+        C[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+        det = (J[0][0] * C[0][0] + J[0][1] * C[0][1]) + J[0][2] * C[0][2];
+    }
+}
+// the doubles of the workgroup's tile that belong to elements (the last workgroup may hold fewer than EPB) ...
+template <int EPB, int SS>
+__device__ __forceinline__ int em_tile_doubles(int count) {
+    const long left = (long)count - (long)blockIdx.x * EPB;
+    return (int)(left < EPB ? left : EPB) * SS;
+}
+// ... and their way out: consecutive lanes write consecutive doubles of the packed output, element l of the tile at obase[l]
+template <int BLOCK, int SS>
+__device__ __forceinline__ void em_write_tile(int total, const roff_t *obase, const double *tile, double *__restrict__ out) {
+    for (int t = threadIdx.x; t < total; t += BLOCK) {
+        const int l = t / SS;
+        out[obase[l] + (t - l * SS)] = tile[t];
+    }
+}
 
 // ---- the element matrices -------------------------------------------------------------------------------------------------
 // list: the elements of this launch (nullptr: elements 0 .. count - 1); eI nullptr: element e has its vertices at e * ND;
@@ -146,7 +136,7 @@ __global__ __launch_bounds__(em_block(DIM, ND, KIND)) void em_kernel(int count, 
                                                                       const double *__restrict__ coords,
                                                                       const double *__restrict__ coef, int ncoef,
                                                                       double *__restrict__ out, int *__restrict__ bad) {
-    typedef EmType<DIM, ND> T;
+    typedef EmTable<DIM, ND> T;                   // NQ points, the weight W of each
     constexpr int BLOCK = em_block(DIM, ND, KIND), EPB = BLOCK / ND, COMP = KIND ? DIM : 1, S = ND * COMP, SS = S * S;
     constexpr int W = KIND ? DIM : 2 * DIM;       // doubles a node shares per point: G_a, and F_a for diffusion
     __shared__ double tile[EPB * SS];
@@ -215,24 +205,7 @@ __global__ __launch_bounds__(em_block(DIM, ND, KIND)) void em_kernel(int count, 
                 for (int b = 1; b < ND; ++b) t = t + X[b][i] * dN.v[b][j];
                 J[i][j] = t;
             }
-        if constexpr (DIM == 2) {
-            det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-            C[0][0] = J[1][1];
-            C[0][1] = -J[1][0];
-            C[1][0] = -J[0][1];
-            C[1][1] = J[0][0];
-        } else {
-            C[0][0] = J[1][1] * J[2][2] - J[1][2] * J[2][1];
-            C[0][1] = J[1][2] * J[2][0] - J[1][0] * J[2][2];
-            C[0][2] = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-            C[1][0] = J[0][2] * J[2][1] - J[0][1] * J[2][2];
-            C[1][1] = J[0][0] * J[2][2] - J[0][2] * J[2][0];
-            C[1][2] = J[0][1] * J[2][0] - J[0][0] * J[2][1];
-            C[2][0] = J[0][1] * J[1][2] - J[0][2] * J[1][1];
-            C[2][1] = J[0][2] * J[1][0] - J[0][0] * J[1][2];
-            C[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-            det = (J[0][0] * C[0][0] + J[0][1] * C[0][1]) + J[0][2] * C[0][2];
-        }
+        em_cofactors<DIM>(J, C, det);
         if (!(det > 0.0)) flag = true;
         const double s = T::W / det;
         // this lane's node: its reference gradient picked from the constants, G_a = C dN_a, F_a = K G_a
@@ -316,102 +289,8 @@ __global__ __launch_bounds__(em_block(DIM, ND, KIND)) void em_kernel(int count, 
 }
 
 // ---- order 2: the 9-node quadrilateral, the 27-node hexahedron, the 6-node triangle and the 10-node tetrahedron ------------
-// The literals and the expressions of elmat_model.py (GAUSS3, GAUSS3_W, _n2, _d2, Q2_QUAD_LOC; the hex is lexicographic).
-constexpr double EM2_GAUSS[3] = {0.11270166537925831, 0.5, 0.8872983346207417};
-constexpr double EM2_W[3] = {0.2777777777777778, 0.4444444444444444, 0.2777777777777778};
-constexpr double em2_n(int l, double p) {
-    return l == 0 ? (2.0 * p - 1.0) * (p - 1.0) : (l == 1 ? (4.0 * p) * (1.0 - p) : p * (2.0 * p - 1.0));
-}
-constexpr double em2_d(int l, double p) { return l == 0 ? 4.0 * p - 3.0 : (l == 1 ? 4.0 - 8.0 * p : 4.0 * p - 1.0); }
-constexpr int em2_nodes(int dim) { return dim == 2 ? 9 : 27; }
-
-// The order-2 simplices (elmat_model._p2_simplex): the vertices, then the midpoints of the edges EM_P2_TRI_EDGES / EM_P2_TET_EDGES.  N and dN at the
-// reference point pt from the barycentric coordinates L and their constant gradients EM_TRI_D / EM_TET_D.
-constexpr int p2s_nodes(int dim) { return dim == 2 ? 6 : 10; }
-constexpr bool p2s_type(int dim, int nd) { return nd == p2s_nodes(dim); }
-constexpr int EM_P2_TRI_EDGES[3][2] = {{0, 1}, {1, 2}, {2, 0}};
-constexpr int EM_P2_TET_EDGES[6][2] = {{0, 1}, {0, 2}, {0, 3}, {1, 2}, {1, 3}, {2, 3}};
-template <int DIM>
-struct P2Simplex {
-    double N[p2s_nodes(DIM)];
-    double dN[p2s_nodes(DIM)][DIM];
-};
-template <int DIM>
-constexpr P2Simplex<DIM> p2_simplex(const double *pt) {
-    P2Simplex<DIM> r{};
-    double L[4] = {0.0, 0.0, 0.0, 0.0}, D[4][3] = {};
-    if (DIM == 2) L[0] = (1.0 - pt[0]) - pt[1];
-    else L[0] = ((1.0 - pt[0]) - pt[1]) - pt[DIM - 1];
-    for (int k = 0; k < DIM; ++k) L[1 + k] = pt[k];
-    for (int i = 0; i <= DIM; ++i)
-        for (int k = 0; k < DIM; ++k) D[i][k] = DIM == 2 ? EM_TRI_D[i % 3][k % 2] : EM_TET_D[i][k];
-    for (int i = 0; i <= DIM; ++i) {
-        r.N[i] = L[i] * (2.0 * L[i] - 1.0);
-        for (int k = 0; k < DIM; ++k) r.dN[i][k] = (4.0 * L[i] - 1.0) * D[i][k];
-    }
-    for (int e = 0; e < p2s_nodes(DIM) - DIM - 1; ++e) {
-        const int i = DIM == 2 ? EM_P2_TRI_EDGES[e % 3][0] : EM_P2_TET_EDGES[e][0];
-        const int j = DIM == 2 ? EM_P2_TRI_EDGES[e % 3][1] : EM_P2_TET_EDGES[e][1];
-        r.N[DIM + 1 + e] = (4.0 * L[i]) * L[j];
-        for (int k = 0; k < DIM; ++k) r.dN[DIM + 1 + e][k] = (4.0 * L[i]) * D[j][k] + (4.0 * L[j]) * D[i][k];
-    }
-    return r;
-}
-constexpr double EM_TET_A = 0.1381966011250105, EM_TET_B = 0.5854101966249685;
-// point q of the stiffness rules of the order-2 simplices: the order-1 mass rules (EM_WEDGE_TRI; EM_TET_A / EM_TET_B)
-struct EmPoint {
-    double x[3];
-};
-constexpr EmPoint p2s_point(int dim, int q) {
-    if (dim == 2) return EmPoint{{EM_WEDGE_TRI[q % 3][0], EM_WEDGE_TRI[q % 3][1], 0.0}};
-    return EmPoint{{q == 1 ? EM_TET_B : EM_TET_A, q == 2 ? EM_TET_B : EM_TET_A, q == 3 ? EM_TET_B : EM_TET_A}};
-}
-
-// the rule's table, folded at compile time: the reference gradient of node a at point q (node-major, so that lanes that differ
-// in the point read neighbouring doubles) and the weight of point q.  The tensor-product types have as many points as nodes;
-// the triangle has 3 and the tetrahedron 4.
-constexpr int em2_points(int dim, int nd) { return p2s_type(dim, nd) ? dim + 1 : nd; }
-template <int DIM, int ND>
-struct Em2Table {
-    static constexpr int NQ = em2_points(DIM, ND);
-    double dN[ND][em2_points(DIM, ND)][DIM];
-    double w[em2_points(DIM, ND)];
-};
-template <int DIM, int ND>
-constexpr Em2Table<DIM, ND> em2_table() {
-    Em2Table<DIM, ND> t{};
-    if constexpr (p2s_type(DIM, ND)) {
-        for (int q = 0; q <= DIM; ++q) {
-            const EmPoint pt = p2s_point(DIM, q);
-            const P2Simplex<DIM> f = p2_simplex<DIM>(pt.x);
-            t.w[q] = DIM == 2 ? 0.16666666666666666 : 0.041666666666666664;
-            for (int a = 0; a < ND; ++a)
-                for (int j = 0; j < DIM; ++j) t.dN[a][q][j] = f.dN[a][j];
-        }
-    } else {
-        for (int q = 0; q < em2_nodes(DIM); ++q) {
-            const int qx = q % 3, qy = (q / 3) % 3, qz = q / 9;
-            const double px = EM2_GAUSS[qx], py = EM2_GAUSS[qy], pz = EM2_GAUSS[qz];
-            t.w[q] = DIM == 2 ? EM2_W[qx] * EM2_W[qy] : (EM2_W[qx] * EM2_W[qy]) * EM2_W[qz];
-            for (int a = 0; a < em2_nodes(DIM); ++a) {
-                if (DIM == 2) {
-                    const int ix = EM2_QUAD_LOC[a][0], iy = EM2_QUAD_LOC[a][1];
-                    t.dN[a][q][0] = em2_d(ix, px) * em2_n(iy, py);
-                    t.dN[a][q][1] = em2_n(ix, px) * em2_d(iy, py);
-                } else {
-                    const int ix = a % 3, iy = (a / 3) % 3, iz = a / 9;
-                    t.dN[a][q][0] = em2_d(ix, px) * (em2_n(iy, py) * em2_n(iz, pz));
-                    t.dN[a][q][1] = em2_d(iy, py) * (em2_n(ix, px) * em2_n(iz, pz));
-                    t.dN[a][q][DIM - 1] = em2_d(iz, pz) * (em2_n(ix, px) * em2_n(iy, py));
-                }
-            }
-        }
-    }
-    return t;
-}
-template <int DIM, int ND>
-__device__ const Em2Table<DIM, ND> EM2_TABLE = em2_table<DIM, ND>();
-
+// (shape functions, rules and tables: elmat_ref.h; the tensor-product types have as many points as nodes, the triangle 3, the
+// tetrahedron 4)
 // BLOCK threads, EPB elements per workgroup, BS x BS node pairs per lane in the entry phase, QC points per pass.
 // The hex of elasticity: one element (its tile is 52 KB), 378 node pairs on 384 lanes.  The hex of diffusion: lanes own
 // 3 x 3 node pairs (the flux of 3 nodes and the gradient of 3 nodes from LDS feed 9 entries: one pair per lane would wait
@@ -459,7 +338,7 @@ __device__ __forceinline__ void em_tensor(const double *c, int ncoef, double *K)
 // true): the stage phase copies the NQ * ncoef doubles of every element of the workgroup, at coef + qoff[e] * ncoef, as they
 // are; the G phase forms K_q from the row of ITS point -- the global q = q0 + qq, not the index in the pass -- and the entry
 // phase of elasticity reads lambda_q, mu_q of the point of its term.
-template <int DIM, int ND, int KIND, class Cfg, class Table, bool KQ>
+template <int DIM, int ND, int KIND, class Cfg, bool KQ, class Table>
 __device__ __forceinline__ void em2_body(const Table &T, int count, const int *__restrict__ list, const int *__restrict__ eI,
                                          const int *__restrict__ eJ, const roff_t *__restrict__ moff,
                                          const roff_t *__restrict__ qoff, const double *__restrict__ coords,
@@ -546,24 +425,7 @@ __device__ __forceinline__ void em2_body(const Table &T, int count, const int *_
         for (int i = 0; i < DIM; ++i)
 #pragma unroll
             for (int j = 0; j < DIM; ++j) J[i][j] = sJ[idx * DD + i * DIM + j];
-        if constexpr (DIM == 2) {
-            det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-            C[0][0] = J[1][1];
-            C[0][1] = -J[1][0];
-            C[1][0] = -J[0][1];
-            C[1][1] = J[0][0];
-        } else {
-            C[0][0] = J[1][1] * J[2][2] - J[1][2] * J[2][1];
-            C[0][1] = J[1][2] * J[2][0] - J[1][0] * J[2][2];
-            C[0][2] = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-            C[1][0] = J[0][2] * J[2][1] - J[0][1] * J[2][2];
-            C[1][1] = J[0][0] * J[2][2] - J[0][2] * J[2][0];
-            C[1][2] = J[0][1] * J[2][0] - J[0][0] * J[2][1];
-            C[2][0] = J[0][1] * J[1][2] - J[0][2] * J[1][1];
-            C[2][1] = J[0][2] * J[1][0] - J[0][0] * J[1][2];
-            C[2][2] = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-            det = (J[0][0] * C[0][0] + J[0][1] * C[0][1]) + J[0][2] * C[0][2];
-        }
+        em_cofactors<DIM>(J, C, det);
         if (!(det > 0.0) && sE[el] >= 0) atomicMin(bad, sE[el]);
         double *P = sP + idx * PW;
 #pragma unroll
@@ -691,12 +553,7 @@ __device__ __forceinline__ void em2_body(const Table &T, int count, const int *_
         }
     }
     __syncthreads();
-    const long left = (long)count - (long)blockIdx.x * EPB;
-    const int total = (int)(left < EPB ? left : EPB) * SS;
-    for (int t = tid; t < total; t += BLOCK) {
-        const int l = t / SS;
-        out[obase[l] + (t - l * SS)] = tile[t];
-    }
+    em_write_tile<BLOCK, SS>(em_tile_doubles<EPB, SS>(count), obase, tile, out);
 }
 
 template <int DIM, int ND, int KIND>
@@ -706,113 +563,15 @@ __global__ __launch_bounds__((Em2Cfg<DIM, ND, KIND>::BLOCK)) void em2_kernel(int
                                                                            const double *__restrict__ coords,
                                                                            const double *__restrict__ coef, int ncoef,
                                                                            double *__restrict__ out, int *__restrict__ bad) {
-    em2_body<DIM, ND, KIND, Em2Cfg<DIM, ND, KIND>, Em2Table<DIM, ND>, false>(EM2_TABLE<DIM, ND>, count, list, eI, eJ, moff, nullptr,
-                                                                             coords, coef, ncoef, out, bad);
+    em2_body<DIM, ND, KIND, Em2Cfg<DIM, ND, KIND>, false>(em2_rule_table<DIM, ND>(), count, list, eI, eJ, moff, nullptr, coords, coef,
+                                                          ncoef, out, bad);
 }
 
 // ---- mass matrices and load vectors ------------------------------------------------------------------------------------------
 // elmat_model.py's element_mass / element_loads.  The rule of a type is its stiffness rule, except for the simplices: three
 // points (EM_WEDGE_TRI, weight 1/6) on the triangle and four (EM_TET_A / EM_TET_B, weight 1/24) on the tetrahedron.  The order-2
 // simplices: 6 points (degree 4) on the triangle, 14 (degree 5) on the tetrahedron -- elmat_model's P2_TRI_POINTS / P2_TET_POINTS.
-constexpr int mass_points(int dim, int nd) {
-    return nd == 9 || nd == 27 ? nd : (dim == 2 ? (nd == 3 ? 3 : (nd == 6 ? 6 : 4)) : (nd == 4 ? 4 : (nd == 10 ? 14 : nd)));
-}
-constexpr double EM_P2_TRI_A[2] = {0.44594849091596483, 0.09157621350977073};
-constexpr double EM_P2_TRI_W[2] = {0.11169079483900572, 0.054975871827660935};
-constexpr double EM_P2_TET_A[2] = {0.3108859192633006, 0.09273525031089122};
-constexpr double EM_P2_TET_W[3] = {0.018781320953002643, 0.012248840519393659, 0.007091003462846911};
-constexpr double EM_P2_TET_EDGE_A = 0.04550370412564965;
-// point q of the mass rule of an order-2 simplex and its weight
-constexpr EmPoint p2s_mass_point(int dim, int q) {
-    if (dim == 2) {
-        const double a = EM_P2_TRI_A[q / 3], b = 1.0 - 2.0 * a;
-        return EmPoint{{q % 3 == 1 ? b : a, q % 3 == 2 ? b : a, 0.0}};
-    }
-    if (q < 8) {
-        const double a = EM_P2_TET_A[q / 4], b = 1.0 - 3.0 * a;
-        return EmPoint{{q % 4 == 1 ? b : a, q % 4 == 2 ? b : a, q % 4 == 3 ? b : a}};
-    }
-    const double a = EM_P2_TET_EDGE_A, b = 0.5 - a;
-    const int i = EM_P2_TET_EDGES[q - 8][0], j = EM_P2_TET_EDGES[q - 8][1];      // barycentrics i and j are b, the point (L1, L2, L3)
-    return EmPoint{{i == 1 || j == 1 ? b : a, i == 2 || j == 2 ? b : a, i == 3 || j == 3 ? b : a}};
-}
-constexpr double p2s_mass_weight(int dim, int q) { return dim == 2 ? EM_P2_TRI_W[q / 3] : EM_P2_TET_W[q < 8 ? q / 4 : 2]; }
-
-// the rule's table, folded at compile time: reference gradients and shape values of node a at point q (dN node-major as in
-// Em2Table, N point-major: the entry phase reads N of neighbouring nodes at one point) and the weight of point q
-template <int DIM, int ND>
-struct MassTable {
-    static constexpr int NQ = mass_points(DIM, ND);
-    double dN[ND][NQ][DIM];
-    double N[NQ][ND];
-    double w[NQ];
-};
-template <int DIM, int ND>
-constexpr MassTable<DIM, ND> mass_table() {
-    MassTable<DIM, ND> t{};
-    constexpr int NQ = MassTable<DIM, ND>::NQ;
-    if constexpr (p2s_type(DIM, ND)) {
-        for (int q = 0; q < NQ; ++q) {
-            const EmPoint pt = p2s_mass_point(DIM, q);
-            const P2Simplex<DIM> f = p2_simplex<DIM>(pt.x);
-            t.w[q] = p2s_mass_weight(DIM, q);
-            for (int a = 0; a < ND; ++a) {
-                t.N[q][a] = f.N[a];
-                for (int j = 0; j < DIM; ++j) t.dN[a][q][j] = f.dN[a][j];
-            }
-        }
-    } else if constexpr (ND == em2_nodes(DIM)) {
-        const Em2Table<DIM, ND> g = em2_table<DIM, ND>();
-        for (int q = 0; q < NQ; ++q) {
-            const double px = EM2_GAUSS[q % 3], py = EM2_GAUSS[(q / 3) % 3], pz = EM2_GAUSS[q / 9];
-            t.w[q] = g.w[q];
-            for (int a = 0; a < ND; ++a) {
-                for (int j = 0; j < DIM; ++j) t.dN[a][q][j] = g.dN[a][q][j];
-                if (DIM == 2)
-                    t.N[q][a] = em2_n(EM2_QUAD_LOC[a % 9][0], px) * em2_n(EM2_QUAD_LOC[a % 9][1], py);
-                else
-                    t.N[q][a] = em2_n(a % 3, px) * (em2_n((a / 3) % 3, py) * em2_n(a / 9, pz));
-            }
-        }
-    } else {
-        for (int q = 0; q < NQ; ++q) {
-            const EmGrad<DIM, ND> g = em_ref_grad<DIM, ND>(q);     // (the simplices': the same at every point)
-            for (int a = 0; a < ND; ++a)
-                for (int j = 0; j < DIM; ++j) t.dN[a][q][j] = g.v[a][j];
-            t.w[q] = EmType<DIM, ND>::W;
-            if constexpr (DIM == 2 && ND == 3) {
-                const double x = EM_WEDGE_TRI[q][0], y = EM_WEDGE_TRI[q][1];
-                t.w[q] = 0.16666666666666666;
-                t.N[q][0] = (1.0 - x) - y;
-                t.N[q][1] = x;
-                t.N[q][2] = y;
-            } else if constexpr (DIM == 3 && ND == 4) {
-                const double x = q == 1 ? EM_TET_B : EM_TET_A, y = q == 2 ? EM_TET_B : EM_TET_A, z = q == 3 ? EM_TET_B : EM_TET_A;
-                t.w[q] = 0.041666666666666664;
-                t.N[q][0] = ((1.0 - x) - y) - z;
-                t.N[q][1] = x;
-                t.N[q][2] = y;
-                t.N[q][3] = z;
-            } else if constexpr (DIM == 2 && ND == 4) {
-                const double px = EM_GAUSS[q & 1], py = EM_GAUSS[(q >> 1) & 1];
-                for (int a = 0; a < 4; ++a) t.N[q][a] = em_f(EM_QUAD_LOC[a][0], px) * em_f(EM_QUAD_LOC[a][1], py);
-            } else if constexpr (DIM == 3 && ND == 8) {
-                const double px = EM_GAUSS[q & 1], py = EM_GAUSS[(q >> 1) & 1], pz = EM_GAUSS[(q >> 2) & 1];
-                for (int a = 0; a < 8; ++a)
-                    t.N[q][a] = em_f(EM_HEX_LOC[a][0], px) * (em_f(EM_HEX_LOC[a][1], py) * em_f(EM_HEX_LOC[a][2], pz));
-            } else {
-                const double xi = EM_WEDGE_TRI[q % 3][0], eta = EM_WEDGE_TRI[q % 3][1], zeta = EM_GAUSS[q / 3];
-                const double T[3] = {(1.0 - xi) - eta, xi, eta};
-                const double L[2] = {1.0 - zeta, zeta};
-                for (int a = 0; a < 2; ++a)
-                    for (int i = 0; i < 3; ++i) t.N[q][a * 3 + i] = T[i] * L[a];
-            }
-        }
-    }
-    return t;
-}
-template <int DIM, int ND>
-__device__ const MassTable<DIM, ND> MASS_TABLE = mass_table<DIM, ND>();
+// (ref_mass_rule and MASS_TABLE, above)
 
 // the node pairs a <= b of an element, row by row: a * 32 + b
 template <int ND>
@@ -1012,8 +771,7 @@ __device__ __forceinline__ void mass_body(int count, const int *__restrict__ lis
     if (!out) return;                             // (the same in every lane of the grid)
     if (tid < EPB) obase[tid] = sE[tid] < 0 ? 0 : (moff ? moff[sE[tid]] : (roff_t)sE[tid] * SS);
     __syncthreads();
-    const long left = (long)count - (long)blockIdx.x * EPB;
-    const int total = (int)(left < EPB ? left : EPB) * SS;
+    const int total = em_tile_doubles<EPB, SS>(count);
     const bool fill = VDIM > 1 || accumulate;
     if (fill) {
         // ---- fill
@@ -1045,10 +803,7 @@ __device__ __forceinline__ void mass_body(int count, const int *__restrict__ lis
     }
     __syncthreads();
     // ---- tile
-    for (int t = tid; t < total; t += BLOCK) {
-        const int l = t / SS;
-        out[obase[l] + (t - l * SS)] = tile[t];
-    }
+    em_write_tile<BLOCK, SS>(total, obase, tile, out);
 }
 
 template <int DIM, int ND, int VDIM>
@@ -1093,8 +848,8 @@ __global__ __launch_bounds__((EmKqCfg<DIM, ND, KIND>::BLOCK)) void emkq_kernel(i
                                                                              const double *__restrict__ coords,
                                                                              const double *__restrict__ coefq, int ncoef,
                                                                              double *__restrict__ out, int *__restrict__ bad) {
-    em2_body<DIM, ND, KIND, EmKqCfg<DIM, ND, KIND>, MassTable<DIM, ND>, true>(MASS_TABLE<DIM, ND>, count, list, eI, eJ, moff, qoff,
-                                                                              coords, coefq, ncoef, out, bad);
+    em2_body<DIM, ND, KIND, EmKqCfg<DIM, ND, KIND>, true>(MASS_TABLE<DIM, ND>, count, list, eI, eJ, moff, qoff, coords, coefq, ncoef,
+                                                          out, bad);
 }
 
 // the last phase of the load kernels: sQ holds s * fq per (element, point, component)
@@ -1379,44 +1134,7 @@ __global__ __launch_bounds__(MASS_BLOCK) void qp_error_kernel(int count, const i
 constexpr int bdr_face_type(int dim, int fn) { return dim == 2 ? fn - 2 : (fn == 3 || fn == 6 ? 2 : (fn == 4 ? 3 : 4)); }
 // (BdrFace, bdr_num_faces, BDR_FACE_NODES and bdr_face: elmat_types.h)
 
-// the rule of a face type, folded at compile time from the expressions of mass_table: the segments have their own lines
-// (em_f / em_df on the 2 Gauss points, em2_n / em2_d on the 3), a face of DIM 3 is the element type (2, FN)
-constexpr int bdr_points(int dim, int fn) { return dim == 2 ? fn : mass_points(2, fn); }
-template <int DIM, int FN>
-struct BdrTable {
-    static constexpr int NQ = bdr_points(DIM, FN);
-    double dN[FN][NQ][DIM - 1];
-    double N[NQ][FN];
-    double w[NQ];
-};
-template <int DIM, int FN>
-constexpr BdrTable<DIM, FN> bdr_table() {
-    BdrTable<DIM, FN> t{};
-    constexpr int NQ = BdrTable<DIM, FN>::NQ;
-    if constexpr (DIM == 3) {
-        const MassTable<2, FN> m = mass_table<2, FN>();
-        for (int q = 0; q < NQ; ++q) {
-            t.w[q] = m.w[q];
-            for (int a = 0; a < FN; ++a) {
-                t.N[q][a] = m.N[q][a];
-                t.dN[a][q][0] = m.dN[a][q][0];
-                t.dN[a][q][DIM - 2] = m.dN[a][q][1];
-            }
-        }
-    } else {
-        for (int q = 0; q < NQ; ++q) {
-            const double p = FN == 2 ? EM_GAUSS[q % 2] : EM2_GAUSS[q];
-            t.w[q] = FN == 2 ? 0.5 : EM2_W[q];
-            for (int a = 0; a < FN; ++a) {
-                t.N[q][a] = FN == 2 ? em_f(a, p) : em2_n(a, p);
-                t.dN[a][q][0] = FN == 2 ? em_df(a) : em2_d(a, p);
-            }
-        }
-    }
-    return t;
-}
-template <int DIM, int FN>
-__device__ const BdrTable<DIM, FN> BDR_TABLE = bdr_table<DIM, FN>();
+// (the rule of a face type: ref_face_rule; its table: bdr_rule_table, above)
 
 constexpr int BDR_BLOCK = 256;
 constexpr int bdr_fpb(int fn) { return fn == 9 ? 5 : (fn == 4 ? 16 : 32); }      // faces per workgroup
@@ -1462,7 +1180,7 @@ __device__ inline void bdr_stage_points(int count, const int *__restrict__ list,
                                         const double *__restrict__ coords, const double *__restrict__ coef,
                                         const double *__restrict__ g, double *sX, double *sG, double *sS, int *sE, int *bad) {
     constexpr int NQ = BdrTable<DIM, FN>::NQ;
-    const BdrTable<DIM, FN> &T = BDR_TABLE<DIM, FN>;
+    const BdrTable<DIM, FN> &T = bdr_rule_table<DIM, FN>();
     __shared__ double sC[FPB];
     __shared__ int sF[FPB];
     const int tid = threadIdx.x;
@@ -1540,7 +1258,7 @@ __global__ __launch_bounds__(BDR_BLOCK) void bdr_mass_kernel(int count, const in
                                                              const double *__restrict__ coords, const double *__restrict__ coef,
                                                              double *out, int *__restrict__ bad) {
     constexpr int FPB = bdr_fpb(FN), NQ = BdrTable<DIM, FN>::NQ, NPAIR = FN * (FN + 1) / 2;
-    const BdrTable<DIM, FN> &T = BDR_TABLE<DIM, FN>;
+    const BdrTable<DIM, FN> &T = bdr_rule_table<DIM, FN>();
     __shared__ double sX[FPB * FN * DIM];
     __shared__ double sS[FPB * NQ];
     __shared__ int sE[FPB];
@@ -1580,7 +1298,7 @@ __global__ __launch_bounds__(BDR_BLOCK) void bdr_load_kernel(int count, const in
                                                              const double *__restrict__ coef, const double *__restrict__ g,
                                                              double *out, int *__restrict__ bad) {
     constexpr int FPB = bdr_fpb(FN), NQ = BdrTable<DIM, FN>::NQ;
-    const BdrTable<DIM, FN> &T = BDR_TABLE<DIM, FN>;
+    const BdrTable<DIM, FN> &T = bdr_rule_table<DIM, FN>();
     __shared__ double sX[FPB * FN * DIM];
     __shared__ double sG[FPB * FN * VDIM];
     __shared__ double sS[FPB * NQ];
@@ -1639,6 +1357,8 @@ __global__ __launch_bounds__(256) void em_dofs_kernel(long nconn, int comp, cons
     for (int c = 0; c < comp; ++c) out[k * comp + c] = comp * eJ[k] + c;
 }
 
+// ---- the launches ---------------------------------------------------------------------------------------------------------------
+// what the kernels of every family are launched with; EmFrame fills it
 struct EmLaunch {
     hipStream_t s;
     const int *eI, *eJ;
@@ -1647,127 +1367,119 @@ struct EmLaunch {
     int ncoef;
     double *out;
     int *bad;
-    const roff_t *qoff = nullptr;      // the offsets of the points: coef then holds a row per POINT (emkq_kernel, mass_kq_kernel)
+    const roff_t *qoff;      // the offsets of the points: coef then holds a row per POINT (emkq_kernel, mass_kq_kernel)
 };
+// one launch on the stream, the launch error checked
+template <class... P, class... A>
+void em_run(void (*kernel)(P...), hipStream_t s, int blocks, int threads, A... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(threads), 0, s, args...);
+    SA_HIP_CHECK(hipGetLastError());
+}
 
-template <int DIM, int ND, int KIND>
-void em_launch(const EmLaunch &L, int count, const int *list) {
-    constexpr int BLOCK = em_block(DIM, ND, KIND), EPB = BLOCK / ND;
-    hipLaunchKernelGGL((em_kernel<DIM, ND, KIND>), dim3((unsigned)div_up(count, EPB)), dim3(BLOCK), 0, L.s, count, list, L.eI, L.eJ,
-                       L.moff, L.coords, L.coef, L.ncoef, L.out, L.bad);
-    SA_HIP_CHECK(hipGetLastError());
-}
-template <int DIM, int ND, int KIND>
-void em2_launch(const EmLaunch &L, int count, const int *list) {
-    typedef Em2Cfg<DIM, ND, KIND> Cfg;
-    hipLaunchKernelGGL((em2_kernel<DIM, ND, KIND>), dim3((unsigned)div_up(count, Cfg::EPB)), dim3(Cfg::BLOCK), 0, L.s, count, list, L.eI,
-                       L.eJ, L.moff, L.coords, L.coef, L.ncoef, L.out, L.bad);
-    SA_HIP_CHECK(hipGetLastError());
-}
-template <int DIM, int ND, int KIND>
-void emkq_launch(const EmLaunch &L, int count, const int *list) {
-    typedef EmKqCfg<DIM, ND, KIND> Cfg;
-    hipLaunchKernelGGL((emkq_kernel<DIM, ND, KIND>), dim3((unsigned)div_up(count, Cfg::EPB)), dim3(Cfg::BLOCK), 0, L.s, count, list, L.eI,
-                       L.eJ, L.moff, L.qoff, L.coords, L.coef, L.ncoef, L.out, L.bad);
-    SA_HIP_CHECK(hipGetLastError());
-}
-template <int KIND>
-void emkq_launch_type(const EmLaunch &L, int type, int count, const int *list) {
-    switch (type) {
-        case 0: emkq_launch<2, 3, KIND>(L, count, list); break;
-        case 1: emkq_launch<2, 4, KIND>(L, count, list); break;
-        case 2: emkq_launch<3, 4, KIND>(L, count, list); break;
-        case 3: emkq_launch<3, 6, KIND>(L, count, list); break;
-        case 4: emkq_launch<3, 8, KIND>(L, count, list); break;
-        case 5: emkq_launch<2, 9, KIND>(L, count, list); break;
-        case 6: emkq_launch<3, 27, KIND>(L, count, list); break;
-        case 7: emkq_launch<2, 6, KIND>(L, count, list); break;
-        default: emkq_launch<3, 10, KIND>(L, count, list); break;
-    }
-}
+// the stiffness forms of `count` elements of one type: order 1 em_kernel, order 2 em2_kernel, rows per point emkq_kernel
 template <int KIND>
 void em_launch_type(const EmLaunch &L, int type, int count, const int *list) {
-    if (L.qoff) return emkq_launch_type<KIND>(L, type, count, list);
-    switch (type) {
-        case 0: em_launch<2, 3, KIND>(L, count, list); break;
-        case 1: em_launch<2, 4, KIND>(L, count, list); break;
-        case 2: em_launch<3, 4, KIND>(L, count, list); break;
-        case 3: em_launch<3, 6, KIND>(L, count, list); break;
-        case 4: em_launch<3, 8, KIND>(L, count, list); break;
-        case 5: em2_launch<2, 9, KIND>(L, count, list); break;
-        case 6: em2_launch<3, 27, KIND>(L, count, list); break;
-        case 7: em2_launch<2, 6, KIND>(L, count, list); break;
-        default: em2_launch<3, 10, KIND>(L, count, list); break;
-    }
+    with_elem_type(type, [&](auto tag) {
+        constexpr int DIM = decltype(tag)::DIM, ND = decltype(tag)::ND;
+        if (L.qoff) {
+            typedef EmKqCfg<DIM, ND, KIND> Cfg;
+            em_run(emkq_kernel<DIM, ND, KIND>, L.s, div_up(count, Cfg::EPB), Cfg::BLOCK, count, list, L.eI, L.eJ, L.moff, L.qoff, L.coords,
+                   L.coef, L.ncoef, L.out, L.bad);
+        } else if constexpr (em_order1(DIM, ND)) {
+            constexpr int BLOCK = em_block(DIM, ND, KIND);
+            em_run(em_kernel<DIM, ND, KIND>, L.s, div_up(count, BLOCK / ND), BLOCK, count, list, L.eI, L.eJ, L.moff, L.coords, L.coef,
+                   L.ncoef, L.out, L.bad);
+        } else {
+            typedef Em2Cfg<DIM, ND, KIND> Cfg;
+            em_run(em2_kernel<DIM, ND, KIND>, L.s, div_up(count, Cfg::EPB), Cfg::BLOCK, count, list, L.eI, L.eJ, L.moff, L.coords, L.coef,
+                   L.ncoef, L.out, L.bad);
+        }
+    });
 }
-
-template <int DIM, int ND>
-void mass_launch(const EmLaunch &L, int vdim, int accumulate, int count, const int *list) {
-    if (L.qoff && vdim == 1)
-        hipLaunchKernelGGL((mass_kq_kernel<DIM, ND, 1>), dim3((unsigned)div_up(count, mass_epb(ND, 1))), dim3(MASS_BLOCK), 0, L.s, count,
-                           list, L.eI, L.eJ, L.moff, L.qoff, L.coords, L.coef, accumulate, L.out, L.bad);
-    else if (L.qoff)
-        hipLaunchKernelGGL((mass_kq_kernel<DIM, ND, DIM>), dim3((unsigned)div_up(count, mass_epb(ND, DIM))), dim3(MASS_BLOCK), 0, L.s,
-                           count, list, L.eI, L.eJ, L.moff, L.qoff, L.coords, L.coef, accumulate, L.out, L.bad);
-    else if (vdim == 1)
-        hipLaunchKernelGGL((mass_kernel<DIM, ND, 1>), dim3((unsigned)div_up(count, mass_epb(ND, 1))), dim3(MASS_BLOCK), 0, L.s, count,
-                           list, L.eI, L.eJ, L.moff, L.coords, L.coef, accumulate, L.out, L.bad);
-    else
-        hipLaunchKernelGGL((mass_kernel<DIM, ND, DIM>), dim3((unsigned)div_up(count, mass_epb(ND, DIM))), dim3(MASS_BLOCK), 0, L.s,
-                           count, list, L.eI, L.eJ, L.moff, L.coords, L.coef, accumulate, L.out, L.bad);
-    SA_HIP_CHECK(hipGetLastError());
-}
-template <int DIM, int ND>
-void load_launch(const EmLaunch &L, int vdim, const double *src, int count, const int *list) {
-    const dim3 grid((unsigned)div_up(count, load_epb(ND)));
-    if (vdim == 1)
-        hipLaunchKernelGGL((load_kernel<DIM, ND, 1>), grid, dim3(MASS_BLOCK), 0, L.s, count, list, L.eI, L.eJ, L.coords, L.coef, src,
-                           L.out, L.bad);
-    else
-        hipLaunchKernelGGL((load_kernel<DIM, ND, DIM>), grid, dim3(MASS_BLOCK), 0, L.s, count, list, L.eI, L.eJ, L.coords, L.coef,
-                           src, L.out, L.bad);
-    SA_HIP_CHECK(hipGetLastError());
-}
-// src nullptr: the mass matrices, else the load vectors
+// src nullptr: the mass matrices (L.qoff: with a coefficient per point), else the load vectors
 void mass_launch_type(const EmLaunch &L, int type, int vdim, int accumulate, const double *src, int count, const int *list) {
-#define SA_MASS_CASE(T, DIM, ND)                                       \
-    case T:                                                            \
-        if (src) load_launch<DIM, ND>(L, vdim, src, count, list);      \
-        else mass_launch<DIM, ND>(L, vdim, accumulate, count, list);   \
-        break;
-    switch (type) {
-        SA_MASS_CASE(0, 2, 3)
-        SA_MASS_CASE(1, 2, 4)
-        SA_MASS_CASE(2, 3, 4)
-        SA_MASS_CASE(3, 3, 6)
-        SA_MASS_CASE(4, 3, 8)
-        SA_MASS_CASE(5, 2, 9)
-        SA_MASS_CASE(6, 3, 27)
-        SA_MASS_CASE(7, 2, 6)
-        default: SA_MASS_CASE(8, 3, 10)
-    }
-#undef SA_MASS_CASE
+    with_elem_type(type, [&](auto tag) {
+        with_vdim(tag, vdim, [&](auto t, auto vd) {
+            constexpr int DIM = decltype(t)::DIM, ND = decltype(t)::ND, VDIM = decltype(vd)::value;
+            if (src)
+                em_run(load_kernel<DIM, ND, VDIM>, L.s, div_up(count, load_epb(ND)), MASS_BLOCK, count, list, L.eI, L.eJ, L.coords, L.coef,
+                       src, L.out, L.bad);
+            else if (L.qoff)
+                em_run(mass_kq_kernel<DIM, ND, VDIM>, L.s, div_up(count, mass_epb(ND, VDIM)), MASS_BLOCK, count, list, L.eI, L.eJ, L.moff,
+                       L.qoff, L.coords, L.coef, accumulate, L.out, L.bad);
+            else
+                em_run(mass_kernel<DIM, ND, VDIM>, L.s, div_up(count, mass_epb(ND, VDIM)), MASS_BLOCK, count, list, L.eI, L.eJ, L.moff,
+                       L.coords, L.coef, accumulate, L.out, L.bad);
+        });
+    });
 }
 
-const char *const EM_NAME = "saamge_amd_element_matrices: ";
+// the calls on data at the points: what they launch with beyond EmLaunch (its coef: of QP_LOADS; its out: the vectors of QP_LOADS)
+enum QpCall { QP_POINTS, QP_EVAL, QP_LOADS, QP_ERRORS };
+struct QpLaunch {
+    const roff_t *qoff;
+    const double *in;         // u (QP_EVAL, QP_ERRORS) or fq (QP_LOADS)
+    const double *exq, *exgradq;
+    double *a, *b;            // xq, wdet / uq, gradq / -, - / err, -
+};
+void qp_launch_type(QpCall call, const EmLaunch &L, const QpLaunch &Q, int type, int vdim, int count, const int *list) {
+    with_elem_type(type, [&](auto tag) {
+        with_vdim(tag, vdim, [&](auto t, auto vd) {
+            constexpr int DIM = decltype(t)::DIM, ND = decltype(t)::ND, VDIM = decltype(vd)::value;
+            const int blocks = div_up(count, call == QP_LOADS ? load_epb(ND) : qp_epb(ND));
+            if (call == QP_POINTS)
+                em_run(qp_points_kernel<DIM, ND>, L.s, blocks, MASS_BLOCK, count, list, L.eI, L.eJ, Q.qoff, L.coords, Q.a, Q.b, L.bad);
+            else if (call == QP_EVAL)
+                em_run(qp_eval_kernel<DIM, ND, VDIM>, L.s, blocks, MASS_BLOCK, count, list, L.eI, L.eJ, Q.qoff, L.coords, Q.in, Q.a, Q.b,
+                       L.bad);
+            else if (call == QP_LOADS)
+                em_run(qp_load_kernel<DIM, ND, VDIM>, L.s, blocks, MASS_BLOCK, count, list, L.eI, L.eJ, Q.qoff, L.coords, L.coef, Q.in,
+                       L.out, L.bad);
+            else
+                em_run(qp_error_kernel<DIM, ND, VDIM>, L.s, blocks, MASS_BLOCK, count, list, L.eI, L.eJ, Q.qoff, L.coords, Q.in, Q.exq,
+                       Q.exgradq, Q.a, L.bad);
+        });
+    });
+}
 
-// ---- what the three entry points share ------------------------------------------------------------------------------------
+// the boundary forms of the faces `list` of elements of type `type` (em_type_index) with the local face index lf: the face loads
+// of g, or (g nullptr) the face mass
+void bdr_launch_face(const EmLaunch &L, const int *face_elem, const double *g, int dim, int vdim, int type, int lf, int count,
+                     const int *list) {
+    const BdrFace F = bdr_face(type, lf);
+    const int nd = EM_TYPE_ND[type];
+    const bool found = with_face_type(dim, BDR_FACE_NODES[type][lf], [&](auto tag) {
+        with_vdim(tag, vdim, [&](auto t, auto vd) {
+            constexpr int DIM = decltype(t)::DIM, FN = decltype(t)::ND, VDIM = decltype(vd)::value;
+            const int blocks = div_up(count, bdr_fpb(FN));
+            if (g)
+                em_run(bdr_load_kernel<DIM, FN, VDIM>, L.s, blocks, BDR_BLOCK, count, list, F, nd, L.eI, L.eJ, face_elem, L.coords, L.coef,
+                       g, L.out, L.bad);
+            else
+                em_run(bdr_mass_kernel<DIM, FN, VDIM>, L.s, blocks, BDR_BLOCK, count, list, F, nd, L.eI, L.eJ, L.moff, face_elem, L.coords,
+                       L.coef, L.out, L.bad);
+        });
+    });
+    SA_REQUIRE(found, "boundary forms: no such face type");
+}
+
+// ---- what the entry points share ------------------------------------------------------------------------------------------
 // the checks that need no device: info as a call without elements leaves it, the dimension and the counts ...
-void em_begin(const std::string &name, int NV, int dim, int NE, long long info[8]) {
+void em_begin(const std::string &name, const MeshArgs &m, long long info[8]) {
     if (info) {
         for (int k = 0; k < 8; ++k) info[k] = 0;
         info[6] = -1;
     }
-    SA_REQUIRE(dim == 2 || dim == 3, name + "dim must be 2 or 3");
-    SA_REQUIRE(NV >= 0 && NE >= 0, name + "NV < 0 or NE < 0");
+    SA_REQUIRE(m.dim == 2 || m.dim == 3, name + "dim must be 2 or 3");
+    SA_REQUIRE(m.NV >= 0 && m.NE >= 0, name + "NV < 0 or NE < 0");
 }
 // ... and the sizes; comp: dofs per node
-void em_check_sizes(const std::string &name, int NV, int dim, int NE, int nde, const int *elem_ptr, int comp) {
-    SA_REQUIRE((int64_t)NV * comp <= INT_MAX, name + "dim * NV beyond 32 bits");
-    if (!elem_ptr) {
-        SA_REQUIRE(em_type_index(dim, nde) >= 0,
-                   name + "nde = " + std::to_string(nde) + " nodes are no supported element type in " + std::to_string(dim) + "D");
-        SA_REQUIRE((int64_t)NE * nde * comp <= INT_MAX, name + "NE * nde beyond 32 bits");
+void em_check_sizes(const std::string &name, const MeshArgs &m, int comp) {
+    SA_REQUIRE((int64_t)m.NV * comp <= INT_MAX, name + "dim * NV beyond 32 bits");
+    if (!m.elem_ptr) {
+        SA_REQUIRE(em_type_index(m.dim, m.nde) >= 0, name + "nde = " + std::to_string(m.nde) +
+                                                         " nodes are no supported element type in " + std::to_string(m.dim) + "D");
+        SA_REQUIRE((int64_t)m.NE * m.nde * comp <= INT_MAX, name + "NE * nde beyond 32 bits");
     }
 }
 
@@ -1778,17 +1490,16 @@ struct EmMesh : DeviceMesh {
     int count[EM_TYPES] = {};
     int64_t doubles = 0;          // of the packed result: sum of size^2 (square) or of size
 };
-void em_mesh(hipStream_t s, const std::string &name, int NV, int dim, int NE, int nde, const int *elem_ptr,
-             const int *elem_to_vertex, int comp, bool square, EmMesh &M, long long info[8]) {
-    import_mesh(s, name, NV, NE, nde, elem_ptr, elem_to_vertex, M);
+void em_mesh(hipStream_t s, const std::string &name, const MeshArgs &m, int comp, bool square, EmMesh &M, long long info[8]) {
+    const int dim = m.dim, NE = m.NE, nde = m.nde;
+    import_mesh(s, name, m.NV, NE, nde, m.elem_ptr, m.elem_to_vertex, M);
     SA_REQUIRE((int64_t)M.nconn * comp <= INT_MAX, name + "dim * elem_ptr[NE] beyond 32 bits");
     // ---- types, lists, offsets of the packed matrices
     M.word.alloc(1);
-    if (elem_ptr) {
+    if (m.elem_ptr) {
         DBuf<int> sq((size_t)NE), cls((size_t)NE), flag, pos;
         SA_HIP_CHECK(hipMemsetAsync(M.word.p, 0x7f, sizeof(int), s));
-        hipLaunchKernelGGL(em_classify_kernel, grid_flat(NE), dim3(256), 0, s, NE, dim, comp, M.eI, cls.p, sq.p, M.word.p);
-        SA_HIP_CHECK(hipGetLastError());
+        em_run(em_classify_kernel, s, div_up(NE, 256), 256, NE, dim, comp, M.eI, cls.p, sq.p, M.word.p);
         const int first = read_one(M.word.p, s);
         if (first < NE) {
             const int nd = read_one(M.eI + first + 1, s) - read_one(M.eI + first, s);
@@ -1817,15 +1528,6 @@ void em_mesh(hipStream_t s, const std::string &name, int NV, int dim, int NE, in
     }
 }
 
-// the integer minimum the kernels left in M.word: the first element with a non-positive determinant
-void em_refuse_bad(hipStream_t s, const std::string &name, const EmMesh &M, int NE, long long info[8]) {
-    const int bad = read_one(M.word.p, s);
-    if (bad < NE) {
-        if (info) info[6] = bad;
-        SA_REQUIRE(false, name + "element " + std::to_string(bad) + ": the Jacobian determinant is not positive");
-    }
-}
-
 // ---- the offsets of the points of the mass rule ------------------------------------------------------------------------------
 // the number of points of every element (its type has been checked)
 __global__ __launch_bounds__(256) void qp_count_kernel(int NE, int dim, const int *__restrict__ eI, int *__restrict__ cnt) {
@@ -1837,304 +1539,276 @@ __global__ __launch_bounds__(256) void qp_offsets_kernel(int NE, int nq, roff_t 
     if (e <= NE) qoff[e] = (roff_t)e * nq;
 }
 // qoff: the NE + 1 offsets on the device; returns NQ
-int64_t qp_offsets(hipStream_t s, int dim, int NE, int nde, const int *elem_ptr, const EmMesh &M, DBuf<roff_t> &qoff) {
+int64_t qp_offsets(hipStream_t s, const MeshArgs &m, const EmMesh &M, DBuf<roff_t> &qoff) {
+    const int NE = m.NE;
     qoff.alloc((size_t)NE + 1);
-    if (elem_ptr) {
+    if (m.elem_ptr) {
         DBuf<int> cnt((size_t)NE);
-        hipLaunchKernelGGL(qp_count_kernel, grid_flat(NE), dim3(256), 0, s, NE, dim, M.eI, cnt.p);
-        SA_HIP_CHECK(hipGetLastError());
+        em_run(qp_count_kernel, s, div_up(NE, 256), 256, NE, m.dim, M.eI, cnt.p);
         exclusive_scan_off(s, NE, cnt.p, qoff.p);
         return read_one(qoff.p + NE, s);
     }
-    const int nq = mass_points(dim, nde);
-    hipLaunchKernelGGL(qp_offsets_kernel, grid_flat((long)NE + 1), dim3(256), 0, s, NE, nq, qoff.p);
-    SA_HIP_CHECK(hipGetLastError());
+    const int nq = mass_points(m.dim, m.nde);
+    em_run(qp_offsets_kernel, s, div_up((int64_t)NE + 1, 256), 256, NE, nq, qoff.p);
     return (int64_t)NE * nq;
 }
 
-// the mass matrices (src nullptr) or the load vectors of the arguments of saamge_amd_element_mass / _loads, already checked;
-// at_points (saamge_amd_element_mass_points): coef holds one double per point of the mass rule
-void mass_or_loads(hipStream_t s, const std::string &name, int NV, int dim, const double *coords, int NE, int nde,
-                   const int *elem_ptr, const int *elem_to_vertex, int vdim, const double *coef, const double *src, int accumulate,
-                   double *out, long long info[8], bool at_points = false) {
-    if (NE == 0) return;
-    EmMesh M;
-    em_mesh(s, name, NV, dim, NE, nde, elem_ptr, elem_to_vertex, vdim, !src, M, info);
-    DBuf<double> hold_X, hold_c, hold_src, hold_out;
-    DBuf<roff_t> qoff;
-    const size_t ncoef = at_points ? (size_t)qp_offsets(s, dim, NE, nde, elem_ptr, M, qoff) : (size_t)NE;
-    EmLaunch L;
-    L.qoff = qoff.p;
-    L.s = s;
-    L.eI = elem_ptr ? M.eI : nullptr;
-    L.eJ = M.eJ;
-    L.moff = M.moff.p;
-    L.coords = device_view(hold_X, coords, (size_t)NV * dim, s);
-    L.coef = coef ? device_view(hold_c, coef, ncoef, s) : nullptr;
-    L.ncoef = 1;
-    L.out = out;
-    if (out && !is_device_ptr(out)) {
-        if (accumulate) upload(hold_out, (const double *)out, (size_t)M.doubles, s);
-        else hold_out.alloc((size_t)M.doubles);
-        L.out = hold_out.p;
-    }
-    L.bad = M.word.p;
-    const double *dsrc = src ? device_view(hold_src, src, (size_t)NV * vdim, s) : nullptr;
-    SA_HIP_CHECK(hipMemsetAsync(M.word.p, 0x7f, sizeof(int), s));
-    for (int t = 0; t < EM_TYPES; ++t)
-        if (M.count[t]) mass_launch_type(L, t, vdim, accumulate, dsrc, M.count[t], M.list[t].p);
-    em_refuse_bad(s, name, M, NE, info);
-    if (hold_out.p) SA_HIP_CHECK(hipMemcpyAsync(out, hold_out.p, (size_t)M.doubles * sizeof(double), hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
-}
-
-// ---- data at the points of the mass rule --------------------------------------------------------------------------------------
-
-enum QpCall { QP_POINTS, QP_EVAL, QP_LOADS, QP_ERRORS };
-struct QpLaunch {
-    EmLaunch L;               // (coef: of QP_LOADS; out: its vectors)
-    const roff_t *qoff;
-    const double *in;         // u (QP_EVAL, QP_ERRORS) or fq (QP_LOADS)
-    const double *exq, *exgradq;
-    double *a, *b;            // xq, wdet / uq, gradq / -, - / err, -
-};
-template <int DIM, int ND, int VDIM>
-void qp_launch(QpCall call, const QpLaunch &Q, int count, const int *list) {
-    const EmLaunch &L = Q.L;
-    const dim3 grid((unsigned)div_up(count, call == QP_LOADS ? load_epb(ND) : qp_epb(ND))), block(MASS_BLOCK);
-    if (call == QP_POINTS)
-        hipLaunchKernelGGL((qp_points_kernel<DIM, ND>), grid, block, 0, L.s, count, list, L.eI, L.eJ, Q.qoff, L.coords, Q.a, Q.b, L.bad);
-    else if (call == QP_EVAL)
-        hipLaunchKernelGGL((qp_eval_kernel<DIM, ND, VDIM>), grid, block, 0, L.s, count, list, L.eI, L.eJ, Q.qoff, L.coords, Q.in, Q.a,
-                           Q.b, L.bad);
-    else if (call == QP_LOADS)
-        hipLaunchKernelGGL((qp_load_kernel<DIM, ND, VDIM>), grid, block, 0, L.s, count, list, L.eI, L.eJ, Q.qoff, L.coords, L.coef, Q.in,
-                           L.out, L.bad);
-    else
-        hipLaunchKernelGGL((qp_error_kernel<DIM, ND, VDIM>), grid, block, 0, L.s, count, list, L.eI, L.eJ, Q.qoff, L.coords, Q.in, Q.exq,
-                           Q.exgradq, Q.a, L.bad);
-    SA_HIP_CHECK(hipGetLastError());
-}
-void qp_launch_type(QpCall call, const QpLaunch &Q, int type, int vdim, int count, const int *list) {
-#define SA_QP_CASE(T, DIM, ND)                                                  \
-    case T:                                                                     \
-        if (vdim == 1) qp_launch<DIM, ND, 1>(call, Q, count, list);             \
-        else qp_launch<DIM, ND, DIM>(call, Q, count, list);                     \
-        break;
-    switch (type) {
-        SA_QP_CASE(0, 2, 3)
-        SA_QP_CASE(1, 2, 4)
-        SA_QP_CASE(2, 3, 4)
-        SA_QP_CASE(3, 3, 6)
-        SA_QP_CASE(4, 3, 8)
-        SA_QP_CASE(5, 2, 9)
-        SA_QP_CASE(6, 3, 27)
-        SA_QP_CASE(7, 2, 6)
-        default: SA_QP_CASE(8, 3, 10)
-    }
-#undef SA_QP_CASE
-}
-
-// an output of `n` doubles that may be a host pointer: the kernels write to dev(), finish() copies it home
-struct QpOut {
+// ---- the frame of a call ----------------------------------------------------------------------------------------------------------
+// an output of `n` doubles that may be a host pointer: the kernels write to dev(), finish() copies it home.  load: the kernels
+// add to what it holds, so a host array is brought along.
+struct EmOut {
     double *user = nullptr;
     DBuf<double> hold;
     size_t n = 0;
-    double *dev(double *p, size_t count) {
+    double *dev(hipStream_t s, double *p, size_t count, bool load = false) {
         user = p;
         n = count;
         if (!p || is_device_ptr(p)) return p;
-        hold.alloc(count);
+        if (load) upload(hold, (const double *)p, count, s);
+        else hold.alloc(count);
         return hold.p;
     }
     void finish(hipStream_t s) {
         if (hold.p && n) SA_HIP_CHECK(hipMemcpyAsync(user, hold.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
     }
 };
+// What every driver does around its launches, in the order the stream sees it: open (the mesh, checked), points (the offsets of
+// the points, where the call has any), inputs (the launch arguments: device views of the coordinates and the coefficients),
+// target / out[] (outputs, host or device), run (the bad word reset, the types looped, the first bad element refused), then
+// copy_home and sync.  A refusal writes no output: the kernels of a call that refuses have written to the frame's buffers at most.
+struct EmFrame {
+    const hipStream_t s;
+    const std::string &name;
+    const MeshArgs &m;
+    long long *const info;
+    EmMesh M;
+    EmLaunch L{};
+    DBuf<roff_t> qoff;
+    DBuf<double> hold_X, hold_c;
+    EmOut out[2];      // [0]: what L.out writes, or the first output of a call on data at the points
+
+    EmFrame(hipStream_t s_, const std::string &name_, const MeshArgs &m_, long long *info_) : s(s_), name(name_), m(m_), info(info_) {}
+    // comp: dofs per node; square: the results are packed matrices; mesh_info: info[0 .. 5] and info[7] as em_mesh fills them
+    void open(int comp, bool square, bool mesh_info = true) { em_mesh(s, name, m, comp, square, M, mesh_info ? info : nullptr); }
+    // returns NQ; rows: the coefficients of this call come one row per point
+    int64_t points(bool rows) {
+        const int64_t NQ = qp_offsets(s, m, M, qoff);
+        coef_rows = rows;
+        return NQ;
+    }
+    // coef: n doubles in rows of ncoef, nullptr: none
+    void inputs(const double *coef = nullptr, size_t n = 0, int ncoef = 1) {
+        L = EmLaunch{s, m.elem_ptr ? M.eI : nullptr, M.eJ, M.moff.p, device_view(hold_X, m.coords, (size_t)m.NV * m.dim, s), nullptr,
+                     ncoef, nullptr, M.word.p, coef_rows ? qoff.p : nullptr};
+        coefficients(coef, n);
+    }
+    void coefficients(const double *coef, size_t n) { L.coef = coef ? device_view(hold_c, coef, n, s) : nullptr; }
+    void target(double *p, size_t n, bool load = false) { L.out = out[0].dev(s, p, n, load); }
+    void reset_bad() { SA_HIP_CHECK(hipMemsetAsync(M.word.p, 0x7f, sizeof(int), s)); }
+    // f(type, count, list) for the elements of every type the mesh has
+    template <class F>
+    void for_types(F &&f) {
+        for (int t = 0; t < EM_TYPES; ++t)
+            if (M.count[t]) f(t, M.count[t], (const int *)M.list[t].p);
+    }
+    // the integer minimum the kernels left in the bad word: the first element (face) of `limit` that is refused
+    void refuse_bad(int limit, const char *noun, const char *what) {
+        const int bad = read_one((const int *)M.word.p, s);
+        if (bad < limit) {
+            if (info) info[6] = bad;
+            SA_REQUIRE(false, name + noun + std::to_string(bad) + what);
+        }
+    }
+    template <class F>
+    void run(F &&f) {
+        reset_bad();
+        for_types(f);
+        refuse_bad(m.NE, "element ", ": the Jacobian determinant is not positive");
+    }
+    void copy_home() {
+        out[0].finish(s);
+        out[1].finish(s);
+    }
+    void sync() { SA_HIP_CHECK(hipStreamSynchronize(s)); }
+
+  private:
+    bool coef_rows = false;
+};
+
+// ---- the drivers ------------------------------------------------------------------------------------------------------------------
+// saamge_amd_element_matrices and, at_points, saamge_amd_element_matrices_points: coef then holds a row per point of the mass rule
+void stiffness(hipStream_t s, const std::string &name, bool at_points, const MeshArgs &m, int kind, int ncoef, const double *coef,
+               double *elmat_out, int *dof_ptr_out, int *elem_to_dof_out, long long info[8]) {
+    const int dim = m.dim, NE = m.NE;
+    // ---- what needs no device
+    em_begin(name, m, info);
+    SA_REQUIRE(kind == 0 || kind == 1, name + "kind must be 0 (diffusion) or 1 (elasticity)");
+    if (kind == 1)
+        SA_REQUIRE(ncoef == 2, name + "ncoef must be 2 (lambda, mu) for elasticity");
+    else
+        SA_REQUIRE(ncoef == 1 || ncoef == dim || ncoef == dim * (dim + 1) / 2,
+                   name + "ncoef must be 1, dim or dim (dim + 1) / 2 for diffusion");
+    SA_REQUIRE(NE == 0 || (m.coords && m.elem_to_vertex && coef),
+               name + "null argument: coords, elem_to_vertex or " + (at_points ? "coefq" : "coef"));
+    const int comp = kind ? dim : 1;
+    em_check_sizes(name, m, comp);
+    if (NE == 0) return;
+    // ---- the matrices (elmat_out NULL: the determinants are still checked)
+    EmFrame F(s, name, m, info);
+    F.open(comp, true);
+    const size_t rows = at_points ? (size_t)F.points(true) : (size_t)NE;
+    F.inputs(coef, rows * ncoef, ncoef);
+    F.target(elmat_out, (size_t)F.M.doubles);
+    F.run([&](int t, int count, const int *list) {
+        if (kind) em_launch_type<1>(F.L, t, count, list);
+        else em_launch_type<0>(F.L, t, count, list);
+    });
+    F.copy_home();
+    // ---- the dof lists the matrices are indexed by
+    const long nconn = F.M.nconn;
+    DBuf<int> dptr, dofs;
+    if (dof_ptr_out) {
+        dptr.alloc((size_t)NE + 1);
+        em_run(em_dof_ptr_kernel, s, div_up((int64_t)NE + 1, 256), 256, NE, comp, F.M.eI, dptr.p);
+        SA_HIP_CHECK(hipMemcpyAsync(dof_ptr_out, dptr.p, ((size_t)NE + 1) * sizeof(int), hipMemcpyDefault, s));
+    }
+    if (elem_to_dof_out) {
+        dofs.alloc((size_t)nconn * comp);
+        em_run(em_dofs_kernel, s, std::max(1, div_up(nconn, 256)), 256, nconn, comp, F.M.eJ, dofs.p);
+        SA_HIP_CHECK(hipMemcpyAsync(elem_to_dof_out, dofs.p, (size_t)nconn * comp * sizeof(int), hipMemcpyDefault, s));
+    }
+    F.sync();
+}
+
+// the mass matrices (src nullptr) or the load vectors of the arguments of saamge_amd_element_mass / _loads, already checked;
+// at_points (saamge_amd_element_mass_points): coef holds one double per point of the mass rule
+void mass_or_loads(hipStream_t s, const std::string &name, const MeshArgs &m, int vdim, const double *coef, const double *src,
+                   int accumulate, double *out, long long info[8], bool at_points = false) {
+    if (m.NE == 0) return;
+    EmFrame F(s, name, m, info);
+    F.open(vdim, !src);
+    F.inputs(coef, at_points ? (size_t)F.points(true) : (size_t)m.NE);
+    F.target(out, (size_t)F.M.doubles, accumulate);
+    DBuf<double> hold_src;
+    const double *dsrc = src ? device_view(hold_src, src, (size_t)m.NV * vdim, s) : nullptr;
+    F.run([&](int t, int count, const int *list) { mass_launch_type(F.L, t, vdim, accumulate, dsrc, count, list); });
+    F.copy_home();
+    F.sync();
+}
+// saamge_amd_element_mass and, at_points, saamge_amd_element_mass_points (coef_name: what the C ABI calls the coefficients)
+void mass_entry(hipStream_t s, const std::string &name, bool at_points, const char *coef_name, const MeshArgs &m, int vdim,
+                const double *coef, int accumulate, double *elmat_inout, long long info[8]) {
+    em_begin(name, m, info);
+    SA_REQUIRE(vdim == 1 || vdim == m.dim, name + "vdim must be 1 or dim");
+    SA_REQUIRE(m.NE == 0 || coef, name + "null argument: " + coef_name);
+    SA_REQUIRE(m.NE == 0 || (m.coords && m.elem_to_vertex), name + "null argument: coords or elem_to_vertex");
+    SA_REQUIRE(!accumulate || elmat_inout, name + "null argument: accumulate needs the matrices in elmat_inout");
+    em_check_sizes(name, m, vdim);
+    mass_or_loads(s, name, m, vdim, coef, nullptr, accumulate ? 1 : 0, elmat_inout, info, at_points);
+}
 
 // The four calls on data at the points, the arguments the C ABI names.  A refusal writes no output: the determinants of the
 // whole mesh are checked (mass_kernel without an output) before the first kernel that writes.
-void points_call(QpCall call, hipStream_t s, const std::string &name, int NV, int dim, const double *coords, int NE, int nde,
-                 const int *elem_ptr, const int *elem_to_vertex, int vdim, const double *coef, const double *in, const char *in_name,
-                 const double *exq, const double *exgradq, long long *qp_ptr_out, double *out_a, double *out_b, long long info[8]) {
-    em_begin(name, NV, dim, NE, info);
+void points_call(QpCall call, hipStream_t s, const std::string &name, const MeshArgs &m, int vdim, const double *coef,
+                 const double *in, const char *in_name, const double *exq, const double *exgradq, long long *qp_ptr_out, double *out_a,
+                 double *out_b, long long info[8]) {
+    const int dim = m.dim, NE = m.NE;
+    em_begin(name, m, info);
     SA_REQUIRE(vdim == 1 || vdim == dim, name + "vdim must be 1 or dim");
-    SA_REQUIRE(NE == 0 || (coords && elem_to_vertex), name + "null argument: coords or elem_to_vertex");
-    em_check_sizes(name, NV, dim, NE, nde, elem_ptr, vdim);
-    EmMesh M;
-    if (NE) em_mesh(s, name, NV, dim, NE, nde, elem_ptr, elem_to_vertex, vdim, false, M, info);
+    SA_REQUIRE(NE == 0 || (m.coords && m.elem_to_vertex), name + "null argument: coords or elem_to_vertex");
+    em_check_sizes(name, m, vdim);
+    EmFrame F(s, name, m, info);
+    if (NE) F.open(vdim, false);
     if (info) info[5] = 0;
     SA_REQUIRE(call == QP_POINTS || in, name + "null argument: " + in_name);
     if (NE == 0) {
         const long long zero = 0;
         if (qp_ptr_out) SA_HIP_CHECK(hipMemcpyAsync(qp_ptr_out, &zero, sizeof(zero), hipMemcpyDefault, s));
-        SA_HIP_CHECK(hipStreamSynchronize(s));
+        F.sync();
         return;
     }
-    // ---- the offsets of the points
-    DBuf<roff_t> qoff;
-    const int64_t NQ = qp_offsets(s, dim, NE, nde, elem_ptr, M, qoff);
-    if (info) info[5] = (long long)NQ;
+    const size_t nq = (size_t)F.points(false);
+    if (info) info[5] = (long long)nq;
     // ---- the determinants, before anything is written
-    DBuf<double> hold_X, hold_c, hold_in, hold_e, hold_g;
-    QpLaunch Q;
-    EmLaunch &L = Q.L;
-    L.s = s;
-    L.eI = elem_ptr ? M.eI : nullptr;
-    L.eJ = M.eJ;
-    L.moff = nullptr;
-    L.coords = device_view(hold_X, coords, (size_t)NV * dim, s);
-    L.coef = nullptr;
-    L.ncoef = 1;
-    L.out = nullptr;
-    L.bad = M.word.p;
-    SA_HIP_CHECK(hipMemsetAsync(M.word.p, 0x7f, sizeof(int), s));
-    for (int t = 0; t < EM_TYPES; ++t)
-        if (M.count[t]) mass_launch_type(L, t, 1, 0, nullptr, M.count[t], M.list[t].p);
-    em_refuse_bad(s, name, M, NE, info);
+    F.inputs();
+    F.run([&](int t, int count, const int *list) { mass_launch_type(F.L, t, 1, 0, nullptr, count, list); });
     // ---- the call
-    QpOut oa, ob;
-    const size_t nq = (size_t)NQ;
-    Q.qoff = qoff.p;
-    Q.in = in ? device_view(hold_in, in, call == QP_LOADS ? nq * vdim : (size_t)NV * vdim, s) : nullptr;
-    Q.exq = exq ? device_view(hold_e, exq, nq * vdim, s) : nullptr;
-    Q.exgradq = exgradq ? device_view(hold_g, exgradq, nq * vdim * dim, s) : nullptr;
-    Q.a = Q.b = nullptr;
+    DBuf<double> hold_in, hold_e, hold_g;
+    const double *din = in ? device_view(hold_in, in, call == QP_LOADS ? nq * vdim : (size_t)m.NV * vdim, s) : nullptr;
+    const double *dexq = exq ? device_view(hold_e, exq, nq * vdim, s) : nullptr;
+    const double *dexgradq = exgradq ? device_view(hold_g, exgradq, nq * vdim * dim, s) : nullptr;
+    double *a = nullptr, *b = nullptr;
     if (call == QP_POINTS) {
-        Q.a = oa.dev(out_a, nq * dim);
-        Q.b = ob.dev(out_b, nq);
+        a = F.out[0].dev(s, out_a, nq * dim);
+        b = F.out[1].dev(s, out_b, nq);
     } else if (call == QP_EVAL) {
-        Q.a = oa.dev(out_a, nq * vdim);
-        Q.b = ob.dev(out_b, nq * vdim * dim);
+        a = F.out[0].dev(s, out_a, nq * vdim);
+        b = F.out[1].dev(s, out_b, nq * vdim * dim);
     } else if (call == QP_LOADS) {
-        L.coef = coef ? device_view(hold_c, coef, (size_t)NE, s) : nullptr;
-        L.out = oa.dev(out_a, (size_t)M.doubles);
+        F.coefficients(coef, (size_t)NE);
+        F.target(out_a, (size_t)F.M.doubles);
     } else {
-        Q.a = oa.dev(out_a, (size_t)NE * 2);
+        a = F.out[0].dev(s, out_a, (size_t)NE * 2);
     }
-    if (Q.a || Q.b || L.out) {
-        for (int t = 0; t < EM_TYPES; ++t)
-            if (M.count[t]) qp_launch_type(call, Q, t, vdim, M.count[t], M.list[t].p);
-    }
-    oa.finish(s);
-    ob.finish(s);
-    if (qp_ptr_out) SA_HIP_CHECK(hipMemcpyAsync(qp_ptr_out, qoff.p, ((size_t)NE + 1) * sizeof(roff_t), hipMemcpyDefault, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
-}
-
-// ---- boundary forms ---------------------------------------------------------------------------------------------------------
-struct BdrLaunch {
-    hipStream_t s;
-    const int *eI, *eJ, *face_elem;
-    const roff_t *moff;
-    const double *coords, *coef, *g;
-    double *out;
-    int *bad;
-};
-template <int DIM, int FN, int VDIM>
-void bdr_launch(const BdrLaunch &L, const BdrFace &F, int nd, int count, const int *list) {
-    const dim3 grid((unsigned)div_up(count, bdr_fpb(FN)));
-    if (L.g)
-        hipLaunchKernelGGL((bdr_load_kernel<DIM, FN, VDIM>), grid, dim3(BDR_BLOCK), 0, L.s, count, list, F, nd, L.eI, L.eJ, L.face_elem,
-                           L.coords, L.coef, L.g, L.out, L.bad);
-    else
-        hipLaunchKernelGGL((bdr_mass_kernel<DIM, FN, VDIM>), grid, dim3(BDR_BLOCK), 0, L.s, count, list, F, nd, L.eI, L.eJ, L.moff,
-                           L.face_elem, L.coords, L.coef, L.out, L.bad);
-    SA_HIP_CHECK(hipGetLastError());
-}
-// the faces `list` of elements of type `type` (em_type_index) with the local face index lf
-void bdr_launch_face(const BdrLaunch &L, int dim, int vdim, int type, int lf, int count, const int *list) {
-    const BdrFace F = bdr_face(type, lf);
-    const int nd = EM_TYPE_ND[type], fn = BDR_FACE_NODES[type][lf];
-#define SA_BDR_CASE(DIM, FN)                                            \
-    if (dim == DIM && fn == FN) {                                       \
-        if (vdim == 1) bdr_launch<DIM, FN, 1>(L, F, nd, count, list);   \
-        else bdr_launch<DIM, FN, DIM>(L, F, nd, count, list);           \
-        return;                                                         \
-    }
-    SA_BDR_CASE(2, 2)
-    SA_BDR_CASE(2, 3)
-    SA_BDR_CASE(3, 3)
-    SA_BDR_CASE(3, 4)
-    SA_BDR_CASE(3, 9)
-    SA_BDR_CASE(3, 6)
-#undef SA_BDR_CASE
-    SA_REQUIRE(false, "boundary forms: no such face type");
+    const QpLaunch Q{F.qoff.p, din, dexq, dexgradq, a, b};
+    if (a || b || F.L.out) F.for_types([&](int t, int count, const int *list) { qp_launch_type(call, F.L, Q, t, vdim, count, list); });
+    F.copy_home();
+    if (qp_ptr_out) SA_HIP_CHECK(hipMemcpyAsync(qp_ptr_out, F.qoff.p, ((size_t)NE + 1) * sizeof(roff_t), hipMemcpyDefault, s));
+    F.sync();
 }
 
 // the face mass (g nullptr) or the face loads of the arguments of saamge_amd_boundary_mass / _loads, already checked
-void boundary_forms(hipStream_t s, const std::string &name, int NV, int dim, const double *coords, int NE, int nde,
-                    const int *elem_ptr, const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim,
-                    const double *coef, const double *g, double *out, long long info[8]) {
+void boundary_forms(hipStream_t s, const std::string &name, const MeshArgs &m, int NF, const int *face_elem, const int *face_local,
+                    int vdim, const double *coef, const double *g, double *out, long long info[8]) {
+    const int dim = m.dim, NE = m.NE;
     if (NF == 0) return;
     if (NE == 0 && info) info[6] = 0;
     SA_REQUIRE(NE > 0, name + "face 0: face_elem is outside [0, NE)");
-    EmMesh M;
-    em_mesh(s, name, NV, dim, NE, nde, elem_ptr, elem_to_vertex, vdim, !g, M, nullptr);
+    EmFrame F(s, name, m, info);
+    F.open(vdim, !g, false);
     // ---- the face list: ranges, repeated pairs, the key of every face
     FaceList FL;
-    check_face_list(s, name, dim, NE, M.eI, NF, face_elem, face_local, FL, info ? info + 6 : nullptr);
-    const int *fe = FL.fe;
-    const DBuf<int> &key = FL.key;
-    DBuf<int> words(1), flag((size_t)NF), pos((size_t)NF + 1);
+    check_face_list(s, name, dim, NE, F.M.eI, NF, face_elem, face_local, FL, info ? info + 6 : nullptr);
+    DBuf<int> flag((size_t)NF), pos((size_t)NF + 1);
     // ---- one list per (element type, local face)
     DBuf<int> list[EM_TYPES][BDR_MAX_FACES];
     int count[EM_TYPES][BDR_MAX_FACES] = {};
     int64_t doubles = 0;
-    for (int t = 0; t < EM_TYPES; ++t) {
-        if (!M.count[t]) continue;
+    F.for_types([&](int t, int, const int *) {
         for (int lf = 0; lf < bdr_num_faces(t); ++lf) {
-            const int c = count[t][lf] = make_list(s, NF, key.p, t * 8 + lf, flag, pos, list[t][lf]);
+            const int c = count[t][lf] = make_list(s, NF, FL.key.p, t * 8 + lf, flag, pos, list[t][lf]);
             const int fn = BDR_FACE_NODES[t][lf];
             if (info) info[bdr_face_type(dim, fn)] += c;
             doubles += (int64_t)c * (g ? fn * vdim : fn * fn * vdim);
         }
-    }
+    });
     if (info) {
         info[5] = (long long)doubles;
         info[7] = FL.touched;
     }
     // ---- the passes: ascending local face, so that the faces of one element are added in that order
-    DBuf<double> hold_X, hold_c, hold_g, hold_out;
-    BdrLaunch L;
-    L.s = s;
-    L.eI = elem_ptr ? M.eI : nullptr;
-    L.eJ = M.eJ;
-    L.face_elem = fe;
-    L.moff = M.moff.p;
-    L.coords = device_view(hold_X, coords, (size_t)NV * dim, s);
-    L.coef = coef ? device_view(hold_c, coef, (size_t)NF, s) : nullptr;
-    L.g = g ? device_view(hold_g, g, (size_t)NV * vdim, s) : nullptr;
-    L.out = out;
-    if (out && !is_device_ptr(out)) {
-        upload(hold_out, (const double *)out, (size_t)M.doubles, s);
-        L.out = hold_out.p;
-    }
-    L.bad = words.p;
-    SA_HIP_CHECK(hipMemsetAsync(words.p, 0x7f, sizeof(int), s));
+    F.inputs(coef, (size_t)NF);
+    DBuf<double> hold_g;
+    const double *dg = g ? device_view(hold_g, g, (size_t)m.NV * vdim, s) : nullptr;
+    F.target(out, (size_t)F.M.doubles, true);
+    F.reset_bad();
     for (int lf = 0; lf < BDR_MAX_FACES; ++lf)
         for (int t = 0; t < EM_TYPES; ++t)
-            if (count[t][lf]) bdr_launch_face(L, dim, vdim, t, lf, count[t][lf], list[t][lf].p);
-    const int bad = read_one((const int *)words.p, s);
-    if (bad < NF) {
-        if (info) info[6] = bad;
-        SA_REQUIRE(false, name + "face " + std::to_string(bad) + ": the measure is not positive");
-    }
-    if (hold_out.p) SA_HIP_CHECK(hipMemcpyAsync(out, hold_out.p, (size_t)M.doubles * sizeof(double), hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
+            if (count[t][lf]) bdr_launch_face(F.L, FL.fe, dg, dim, vdim, t, lf, count[t][lf], list[t][lf].p);
+    F.refuse_bad(NF, "face ", ": the measure is not positive");
+    F.copy_home();
+    F.sync();
 }
-
 // the checks of both entry points that need no device
-void bdr_begin(const std::string &name, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
-               const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim, long long info[8]) {
-    em_begin(name, NV, dim, NE, info);
+void bdr_begin(const std::string &name, const MeshArgs &m, int NF, const int *face_elem, const int *face_local, int vdim,
+               long long info[8]) {
+    em_begin(name, m, info);
     SA_REQUIRE(NF >= 0, name + "NF < 0");
-    SA_REQUIRE(vdim == 1 || vdim == dim, name + "vdim must be 1 or dim");
+    SA_REQUIRE(vdim == 1 || vdim == m.dim, name + "vdim must be 1 or dim");
     SA_REQUIRE(NF == 0 || (face_elem && face_local), name + "null argument: face_elem or face_local");
-    SA_REQUIRE(NF == 0 || NE == 0 || (coords && elem_to_vertex), name + "null argument: coords or elem_to_vertex");
-    em_check_sizes(name, NV, dim, NE, nde, elem_ptr, vdim);
+    SA_REQUIRE(NF == 0 || m.NE == 0 || (m.coords && m.elem_to_vertex), name + "null argument: coords or elem_to_vertex");
+    em_check_sizes(name, m, vdim);
 }
-
 }  // namespace
 
 // The mesh argument of every call of this file and of mesh_faces.hip (elmat.h)
@@ -2202,171 +1876,66 @@ void check_face_list(hipStream_t s, const std::string &name, int dim, int NE, co
     L.touched = w[2];
 }
 
-namespace {
-// saamge_amd_element_matrices and, at_points, saamge_amd_element_matrices_points: coef then holds a row per point of the mass rule
-void stiffness(hipStream_t s, const std::string &name, bool at_points, int NV, int dim, const double *coords, int NE, int nde,
-               const int *elem_ptr, const int *elem_to_vertex, int kind, int ncoef, const double *coef, double *elmat_out,
-               int *dof_ptr_out, int *elem_to_dof_out, long long info[8]) {
-    // ---- what needs no device
-    em_begin(name, NV, dim, NE, info);
-    SA_REQUIRE(kind == 0 || kind == 1, name + "kind must be 0 (diffusion) or 1 (elasticity)");
-    if (kind == 1)
-        SA_REQUIRE(ncoef == 2, name + "ncoef must be 2 (lambda, mu) for elasticity");
-    else
-        SA_REQUIRE(ncoef == 1 || ncoef == dim || ncoef == dim * (dim + 1) / 2,
-                   name + "ncoef must be 1, dim or dim (dim + 1) / 2 for diffusion");
-    SA_REQUIRE(NE == 0 || (coords && elem_to_vertex && coef),
-               name + "null argument: coords, elem_to_vertex or " + (at_points ? "coefq" : "coef"));
-    const int comp = kind ? dim : 1;
-    em_check_sizes(name, NV, dim, NE, nde, elem_ptr, comp);
-    if (NE == 0) return;
-    EmMesh M;
-    em_mesh(s, name, NV, dim, NE, nde, elem_ptr, elem_to_vertex, comp, true, M, info);
-    const int *eI = M.eI, *eJ = M.eJ;
-    const long nconn = M.nconn;
-    const int64_t doubles = M.doubles;      // (info[5])
-    // ---- the matrices (elmat_out NULL: the determinants are still checked)
-    DBuf<double> hold_X, hold_c, hold_out;
-    DBuf<roff_t> qoff;
-    const size_t rows = at_points ? (size_t)qp_offsets(s, dim, NE, nde, elem_ptr, M, qoff) : (size_t)NE;
-    EmLaunch L;
-    L.s = s;
-    L.eI = elem_ptr ? eI : nullptr;
-    L.eJ = eJ;
-    L.moff = M.moff.p;
-    L.qoff = qoff.p;
-    L.coords = device_view(hold_X, coords, (size_t)NV * dim, s);
-    L.coef = device_view(hold_c, coef, rows * ncoef, s);
-    L.ncoef = ncoef;
-    L.out = elmat_out;
-    if (elmat_out && !is_device_ptr(elmat_out)) {
-        hold_out.alloc((size_t)doubles);
-        L.out = hold_out.p;
-    }
-    L.bad = M.word.p;
-    SA_HIP_CHECK(hipMemsetAsync(M.word.p, 0x7f, sizeof(int), s));
-    for (int t = 0; t < EM_TYPES; ++t) {
-        if (!M.count[t]) continue;
-        if (kind) em_launch_type<1>(L, t, M.count[t], M.list[t].p);
-        else em_launch_type<0>(L, t, M.count[t], M.list[t].p);
-    }
-    em_refuse_bad(s, name, M, NE, info);
-    if (hold_out.p) SA_HIP_CHECK(hipMemcpyAsync(elmat_out, hold_out.p, (size_t)doubles * sizeof(double), hipMemcpyDeviceToHost, s));
-    // ---- the dof lists the matrices are indexed by
-    DBuf<int> dptr, dofs;
-    if (dof_ptr_out) {
-        dptr.alloc((size_t)NE + 1);
-        hipLaunchKernelGGL(em_dof_ptr_kernel, grid_flat((long)NE + 1), dim3(256), 0, s, NE, comp, eI, dptr.p);
-        SA_HIP_CHECK(hipGetLastError());
-        SA_HIP_CHECK(hipMemcpyAsync(dof_ptr_out, dptr.p, ((size_t)NE + 1) * sizeof(int), hipMemcpyDefault, s));
-    }
-    if (elem_to_dof_out) {
-        dofs.alloc((size_t)nconn * comp);
-        hipLaunchKernelGGL(em_dofs_kernel, grid_flat(nconn), dim3(256), 0, s, nconn, comp, eJ, dofs.p);
-        SA_HIP_CHECK(hipGetLastError());
-        SA_HIP_CHECK(hipMemcpyAsync(elem_to_dof_out, dofs.p, (size_t)nconn * comp * sizeof(int), hipMemcpyDefault, s));
-    }
-    SA_HIP_CHECK(hipStreamSynchronize(s));
-}
-}  // namespace
-
-void element_matrices(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
-                      const int *elem_to_vertex, int kind, int ncoef, const double *coef, double *elmat_out, int *dof_ptr_out,
+// ---- the entry points (elmat.h) -----------------------------------------------------------------------------------------------
+void element_matrices(hipStream_t s, const MeshArgs &m, int kind, int ncoef, const double *coef, double *elmat_out, int *dof_ptr_out,
                       int *elem_to_dof_out, long long info[8]) {
-    stiffness(s, EM_NAME, false, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, kind, ncoef, coef, elmat_out, dof_ptr_out,
-              elem_to_dof_out, info);
+    stiffness(s, "saamge_amd_element_matrices: ", false, m, kind, ncoef, coef, elmat_out, dof_ptr_out, elem_to_dof_out, info);
 }
-
-void element_matrices_points(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
-                             const int *elem_to_vertex, int kind, int ncoef, const double *coefq, double *elmat_out,
+void element_matrices_points(hipStream_t s, const MeshArgs &m, int kind, int ncoef, const double *coefq, double *elmat_out,
                              int *dof_ptr_out, int *elem_to_dof_out, long long info[8]) {
-    stiffness(s, "saamge_amd_element_matrices_points: ", true, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, kind, ncoef, coefq,
-              elmat_out, dof_ptr_out, elem_to_dof_out, info);
+    stiffness(s, "saamge_amd_element_matrices_points: ", true, m, kind, ncoef, coefq, elmat_out, dof_ptr_out, elem_to_dof_out, info);
 }
 
-void element_mass_points(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
-                         const int *elem_to_vertex, int vdim, const double *coefq, int accumulate, double *elmat_inout,
+void element_mass(hipStream_t s, const MeshArgs &m, int vdim, const double *coef, int accumulate, double *elmat_inout,
+                  long long info[8]) {
+    mass_entry(s, "saamge_amd_element_mass: ", false, "coef", m, vdim, coef, accumulate, elmat_inout, info);
+}
+void element_mass_points(hipStream_t s, const MeshArgs &m, int vdim, const double *coefq, int accumulate, double *elmat_inout,
                          long long info[8]) {
-    const std::string name("saamge_amd_element_mass_points: ");
-    em_begin(name, NV, dim, NE, info);
-    SA_REQUIRE(vdim == 1 || vdim == dim, name + "vdim must be 1 or dim");
-    SA_REQUIRE(NE == 0 || coefq, name + "null argument: coefq");
-    SA_REQUIRE(NE == 0 || (coords && elem_to_vertex), name + "null argument: coords or elem_to_vertex");
-    SA_REQUIRE(!accumulate || elmat_inout, name + "null argument: accumulate needs the matrices in elmat_inout");
-    em_check_sizes(name, NV, dim, NE, nde, elem_ptr, vdim);
-    mass_or_loads(s, name, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, coefq, nullptr, accumulate ? 1 : 0, elmat_inout,
-                  info, true);
+    mass_entry(s, "saamge_amd_element_mass_points: ", true, "coefq", m, vdim, coefq, accumulate, elmat_inout, info);
 }
 
-void element_mass(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
-                  const int *elem_to_vertex, int vdim, const double *coef, int accumulate, double *elmat_inout, long long info[8]) {
-    const std::string name("saamge_amd_element_mass: ");
-    em_begin(name, NV, dim, NE, info);
-    SA_REQUIRE(vdim == 1 || vdim == dim, name + "vdim must be 1 or dim");
-    SA_REQUIRE(NE == 0 || coef, name + "null argument: coef");
-    SA_REQUIRE(NE == 0 || (coords && elem_to_vertex), name + "null argument: coords or elem_to_vertex");
-    SA_REQUIRE(!accumulate || elmat_inout, name + "null argument: accumulate needs the matrices in elmat_inout");
-    em_check_sizes(name, NV, dim, NE, nde, elem_ptr, vdim);
-    mass_or_loads(s, name, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, coef, nullptr, accumulate ? 1 : 0, elmat_inout,
-                  info);
-}
-
-void element_loads(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
-                   const int *elem_to_vertex, int vdim, const double *coef, const double *src, double *elvec_out,
+void element_loads(hipStream_t s, const MeshArgs &m, int vdim, const double *coef, const double *src, double *elvec_out,
                    long long info[8]) {
     const std::string name("saamge_amd_element_loads: ");
-    em_begin(name, NV, dim, NE, info);
-    SA_REQUIRE(vdim == 1 || vdim == dim, name + "vdim must be 1 or dim");
+    em_begin(name, m, info);
+    SA_REQUIRE(vdim == 1 || vdim == m.dim, name + "vdim must be 1 or dim");
     SA_REQUIRE(src, name + "null argument: src");
-    SA_REQUIRE(NE == 0 || (coords && elem_to_vertex), name + "null argument: coords or elem_to_vertex");
-    em_check_sizes(name, NV, dim, NE, nde, elem_ptr, vdim);
-    mass_or_loads(s, name, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, coef, src, 0, elvec_out, info);
+    SA_REQUIRE(m.NE == 0 || (m.coords && m.elem_to_vertex), name + "null argument: coords or elem_to_vertex");
+    em_check_sizes(name, m, vdim);
+    mass_or_loads(s, name, m, vdim, coef, src, 0, elvec_out, info);
 }
 
-void boundary_mass(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
-                   const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim, const double *coef,
+void boundary_mass(hipStream_t s, const MeshArgs &m, int NF, const int *face_elem, const int *face_local, int vdim, const double *coef,
                    double *elmat_inout, long long info[8]) {
     const std::string name("saamge_amd_boundary_mass: ");
-    bdr_begin(name, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, vdim, info);
+    bdr_begin(name, m, NF, face_elem, face_local, vdim, info);
     SA_REQUIRE(NF == 0 || coef, name + "null argument: coef");
-    boundary_forms(s, name, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, vdim, coef, nullptr,
-                   elmat_inout, info);
+    boundary_forms(s, name, m, NF, face_elem, face_local, vdim, coef, nullptr, elmat_inout, info);
 }
-
-void boundary_loads(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
-                    const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim, const double *coef,
+void boundary_loads(hipStream_t s, const MeshArgs &m, int NF, const int *face_elem, const int *face_local, int vdim, const double *coef,
                     const double *g, double *elvec_inout, long long info[8]) {
     const std::string name("saamge_amd_boundary_loads: ");
-    bdr_begin(name, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, vdim, info);
+    bdr_begin(name, m, NF, face_elem, face_local, vdim, info);
     SA_REQUIRE(g, name + "null argument: g");
-    boundary_forms(s, name, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, vdim, coef, g,
-                   elvec_inout, info);
+    boundary_forms(s, name, m, NF, face_elem, face_local, vdim, coef, g, elvec_inout, info);
 }
 
-void element_points(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
-                    const int *elem_to_vertex, long long *qp_ptr_out, double *xq_out, double *wdet_out, long long info[8]) {
-    points_call(QP_POINTS, s, "saamge_amd_element_points: ", NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, 1, nullptr, nullptr,
-                "", nullptr, nullptr, qp_ptr_out, xq_out, wdet_out, info);
+void element_points(hipStream_t s, const MeshArgs &m, long long *qp_ptr_out, double *xq_out, double *wdet_out, long long info[8]) {
+    points_call(QP_POINTS, s, "saamge_amd_element_points: ", m, 1, nullptr, nullptr, "", nullptr, nullptr, qp_ptr_out, xq_out, wdet_out,
+                info);
 }
-
-void element_eval(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
-                  const int *elem_to_vertex, int vdim, const double *u, double *uq_out, double *gradq_out, long long info[8]) {
-    points_call(QP_EVAL, s, "saamge_amd_element_eval: ", NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, nullptr, u, "u",
-                nullptr, nullptr, nullptr, uq_out, gradq_out, info);
+void element_eval(hipStream_t s, const MeshArgs &m, int vdim, const double *u, double *uq_out, double *gradq_out, long long info[8]) {
+    points_call(QP_EVAL, s, "saamge_amd_element_eval: ", m, vdim, nullptr, u, "u", nullptr, nullptr, nullptr, uq_out, gradq_out, info);
 }
-
-void element_loads_points(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
-                          const int *elem_to_vertex, int vdim, const double *coef, const double *fq, double *elvec_out,
+void element_loads_points(hipStream_t s, const MeshArgs &m, int vdim, const double *coef, const double *fq, double *elvec_out,
                           long long info[8]) {
-    points_call(QP_LOADS, s, "saamge_amd_element_loads_points: ", NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, coef, fq,
-                "fq", nullptr, nullptr, nullptr, elvec_out, nullptr, info);
+    points_call(QP_LOADS, s, "saamge_amd_element_loads_points: ", m, vdim, coef, fq, "fq", nullptr, nullptr, nullptr, elvec_out, nullptr,
+                info);
 }
-
-void element_errors(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
-                    const int *elem_to_vertex, int vdim, const double *u, const double *exq, const double *exgradq, double *err_out,
-                    long long info[8]) {
-    points_call(QP_ERRORS, s, "saamge_amd_element_errors: ", NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, vdim, nullptr, u, "u",
-                exq, exgradq, nullptr, err_out, nullptr, info);
+void element_errors(hipStream_t s, const MeshArgs &m, int vdim, const double *u, const double *exq, const double *exgradq,
+                    double *err_out, long long info[8]) {
+    points_call(QP_ERRORS, s, "saamge_amd_element_errors: ", m, vdim, nullptr, u, "u", exq, exgradq, nullptr, err_out, nullptr, info);
 }
 
 }  // namespace saamge_amd
