@@ -175,6 +175,8 @@ static Params convert_params(const saamge_amd_params *params, void *stream) {
         p.nu_relax[i] = params->nu_relax[i];
         p.nu_pro[i] = params->nu_pro[i];
     }
+    // refused here, before any kernel runs, and not by sas_poly_roots in the middle of a coarse level's setup
+    for (int i = 0; i < p.num_coarsenings; ++i) SA_REQUIRE(p.nu_relax[i] > 0, "nu_relax must be positive");
     p.avoid_ess_bdr_dofs = params->avoid_ess_bdr_dofs;
     p.testmesh = params->testmesh;
     p.coarse_solver = params->coarse_solver;

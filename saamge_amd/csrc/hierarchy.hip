@@ -1269,7 +1269,7 @@ static int pcg_loop(Hierarchy &H, const DCsr &A, const std::function<void(const 
         prec(r, z);
         pdot(r, z, sc + 2);
         const double betanom = read_scalar(s, sc + 2);
-        if (hist) hist[i] = betanom;
+        if (hist && i <= max_iter) hist[i] = betanom;      // hist holds max_iter + 1 doubles: with max_iter <= 0 the one update still runs
         if (betanom < r0) {
             if (converged) *converged = 1;
             final_iter = i;
