@@ -559,6 +559,49 @@ int saamge_amd_boundary_mass(int NV, int dim, const double *coords, int NE, int 
 int saamge_amd_boundary_loads(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                               const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim,
                               const double *coef, const double *g, void *stream, double *elvec_inout, long long info[8]);
+/* ---- boundary data at the face points (csrc/elmat.hip) ----
+ * What saamge_amd_element_points / _eval / _loads_points / _mass_points give inside the elements, on a list of faces: where the
+ * face points are and the outward normal there, a nodal field and its whole gradient there, the Robin term with a coefficient
+ * per point and the Neumann term of data given at the points -- so that a flux g = k grad u . n, a nonlinear alpha(u) or a
+ * boundary flux is formed on the device.  saamge_amd/elmat_model.py (boundary_points, boundary_eval, boundary_mass_points,
+ * boundary_loads_points) defines every operation and the device gives the same bits.  Everything not said here is as for the
+ * boundary forms above: the face lists, the local faces, the rule of a face type, the pointers (host or device, each on its
+ * own), the stream, info[0..4], [6], [7].
+ * THE POINTS of face f of the list are those of its face type's rule, in the rule's order: point q of face f has the global
+ * index fp_ptr[f] + q, fp_ptr NF + 1 offsets of 64 bits, NFQ = fp_ptr[NF].  The index follows the order of the LIST: a permuted
+ * list permutes the point arrays by whole faces (and leaves the matrices and vectors as they are).
+ * saamge_amd_boundary_points: fp_ptr_out (NF + 1); xq_out (NFQ x dim), x_q[i] = sum_c N_c(q) X[c][i] over the face nodes
+ * ascending; wmeas_out (NFQ), w_q meas_q; normal_out (NFQ x dim), the unit normal that points out of the owning element: in 3D
+ * (t_0 x t_1) / meas with the tangents t_j = sum_c X[c] dN_c[j], in 2D (t_y, -t_x) / meas, the division last.  Any of the four
+ * may be NULL.  info[5] = NFQ.
+ * saamge_amd_boundary_eval: u NV x vdim at the nodes.  uq_out (NFQ x vdim) is the trace through the face's own shape functions,
+ * sum_c N_c u[c][i] over the face nodes.  gradq_out (NFQ x vdim x dim) is the WHOLE gradient of the owning element's field at the
+ * face point, not its tangential part: the element's dN_a of all its nodes at the reference position of the face point, J, the
+ * cofactors and (sum_k r[i][k] C[j][k]) / det as saamge_amd_element_eval.  Either output may be NULL; info[5] = NFQ.  The
+ * element's determinant is checked at every face point whether or not gradq_out is given.
+ * saamge_amd_boundary_mass_points: saamge_amd_boundary_mass with s = (w meas) coefq[fp_ptr[f] + q], coefq NFQ doubles; equal
+ * values at the points of each face give the bits of saamge_amd_boundary_mass.  info[5] = additions made.
+ * saamge_amd_boundary_loads_points: gq NFQ x vdim, the data AT THE POINTS; coef NF doubles or NULL: 1.  Face dof (a, i) gets the
+ * sum over the points, ascending from 0.0, of (s gq[q][i]) N_a, s = (w meas) coef[f], added as saamge_amd_boundary_loads adds.
+ * With gq = the uq_out of saamge_amd_boundary_eval of a nodal g the result has the bits of saamge_amd_boundary_loads(g).  Data
+ * that jumps across an edge of a box (a flux through n) takes ONE call.
+ * Refused, in this order: vdim not 1 or dim; NF < 0; NULL face lists, NULL coefq / gq / u -- before anything touches the device;
+ * the mesh; the first face out of range; the first repeated (element, local face); the first face whose measure is not positive;
+ * for saamge_amd_boundary_eval the first face (lowest index of the list) whose element has a non-positive determinant at a face
+ * point.  A refusal writes no output: every face is checked before the first kernel that writes. */
+int saamge_amd_boundary_points(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                               const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, void *stream,
+                               long long *fp_ptr_out, double *xq_out, double *wmeas_out, double *normal_out, long long info[8]);
+int saamge_amd_boundary_eval(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                             const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim,
+                             const double *u, void *stream, double *uq_out, double *gradq_out, long long info[8]);
+int saamge_amd_boundary_mass_points(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                    const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim,
+                                    const double *coefq /* NFQ */, void *stream, double *elmat_inout, long long info[8]);
+int saamge_amd_boundary_loads_points(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                     const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim,
+                                     const double *coef /* NF or NULL */, const double *gq /* NFQ x vdim */, void *stream,
+                                     double *elvec_inout, long long info[8]);
 /* ---- the faces of a mesh found on the device (csrc/mesh_faces.hip) ----
  * Which element lies across each local face, and from that the boundary face list the boundary forms take, the element graph
  * through faces that saamge_amd_partition_graph takes, and the essential-dof flags that saamge_amd_operator_assemble and

@@ -469,6 +469,56 @@ inline BoundaryFormsInfo boundary_loads_into(int NV, int dim, const double *coor
     return r;
 }
 
+// == boundary data at the face points (saamge_amd_boundary_points, _eval, _mass_points, _loads_points) ==
+// Point q of face f of the list has the global index fp_ptr[f] + q; NFQ = fp_ptr[NF] comes back in `additions` from points and
+// eval.  Into the caller's arrays, each a host or a device pointer; the outputs of points and eval may each be nullptr.  Layouts
+// and operations in saamge_amd.h.
+inline BoundaryFormsInfo boundary_points_into(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                              const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local,
+                                              long long *fp_ptr_out, double *xq_out, double *wmeas_out, double *normal_out,
+                                              void *stream = nullptr) {
+    long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (saamge_amd_boundary_points(NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, stream, fp_ptr_out,
+                                   xq_out, wmeas_out, normal_out, info))
+        throw std::runtime_error(saamge_amd_last_error());
+    const BoundaryFormsInfo r = {info[0], info[1], info[2], info[3], info[4], info[5], info[6], info[7]};
+    return r;
+}
+// u: NV x vdim at the nodes; uq_out NFQ x vdim the trace, gradq_out NFQ x vdim x dim the whole gradient
+inline BoundaryFormsInfo boundary_eval_into(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                            const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local,
+                                            int vdim, const double *u, double *uq_out, double *gradq_out, void *stream = nullptr) {
+    long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (saamge_amd_boundary_eval(NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, vdim, u, stream, uq_out,
+                                 gradq_out, info))
+        throw std::runtime_error(saamge_amd_last_error());
+    const BoundaryFormsInfo r = {info[0], info[1], info[2], info[3], info[4], info[5], info[6], info[7]};
+    return r;
+}
+// coefq: the coefficient at the face points (NFQ)
+inline BoundaryFormsInfo boundary_mass_points_into(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                                   const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local,
+                                                   int vdim, const double *coefq, double *elmat_inout, void *stream = nullptr) {
+    long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (saamge_amd_boundary_mass_points(NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, vdim, coefq,
+                                        stream, elmat_inout, info))
+        throw std::runtime_error(saamge_amd_last_error());
+    const BoundaryFormsInfo r = {info[0], info[1], info[2], info[3], info[4], info[5], info[6], info[7]};
+    return r;
+}
+// gq: the data at the face points (NFQ x vdim); coef == nullptr: 1.
+inline BoundaryFormsInfo boundary_loads_points_into(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                                    const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local,
+                                                    int vdim, const double *coef, const double *gq, double *elvec_inout,
+                                                    void *stream = nullptr) {
+    long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (saamge_amd_boundary_loads_points(NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, vdim, coef, gq,
+                                         stream, elvec_inout, info))
+        throw std::runtime_error(saamge_amd_last_error());
+    const BoundaryFormsInfo r = {info[0], info[1], info[2], info[3], info[4], info[5], info[6], info[7]};
+    return r;
+}
+
 // == the operator assembled on the device (saamge_amd_operator_assemble) ==
 // Owner of the handle.  rowptr() / col() / val() are device arrays that live as long as this object: hand them to
 // saamge_amd_ml_produce_data64 / _mixed64 as A.  elem_ptr == nullptr: every element has nde dofs.

@@ -42,6 +42,7 @@ SYMBOLS = [
     "saamge_amd_level_order_info", "saamge_amd_ae_order", "saamge_amd_element_matrices",
     "saamge_amd_element_mass", "saamge_amd_element_loads", "saamge_amd_operator_assemble_rhs",
     "saamge_amd_boundary_mass", "saamge_amd_boundary_loads",
+    "saamge_amd_boundary_points", "saamge_amd_boundary_eval", "saamge_amd_boundary_mass_points", "saamge_amd_boundary_loads_points",
     "saamge_amd_element_points", "saamge_amd_element_eval", "saamge_amd_element_loads_points", "saamge_amd_element_errors",
     "saamge_amd_element_matrices_points", "saamge_amd_element_mass_points",
     "saamge_amd_face_table_build", "saamge_amd_face_table_arrays", "saamge_amd_face_table_get", "saamge_amd_face_table_free",
@@ -1087,6 +1088,108 @@ def boundary_loads(coords, elem_to_vertex, face_elem, face_local, g, vdim=1, coe
     got = _mass_call(lambda: load().saamge_amd_boundary_loads(
         C.c_int(NV), C.c_int(dim), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_int(NF), _ptr(fe), _ptr(fl),
         C.c_int(vdim), _ptr(coef), _ptr(g), C.c_void_p(stream), _ptr(None if sizes_only else add_to), info), info)
+    return got if sizes_only else add_to
+
+
+# ---- boundary data at the face points (elmat_model.boundary_points / _eval / _mass_points / _loads_points) ----
+def _num_face_points(NV, dim, coords, NE, nde, ep, e2v, NF, fe, fl, stream, brought):
+    """NFQ from the checks-only call (saamge_amd_boundary_points without outputs: info[5]), which refuses what the writing call
+    would refuse; brought: (name, array, doubles per point) of the outputs the caller brings, which must hold NFQ rows -- the
+    library writes through the pointers it is given"""
+    info = (C.c_longlong * 8)()
+    NFQ = _mass_call(lambda: load().saamge_amd_boundary_points(
+        C.c_int(NV), C.c_int(dim), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_int(NF), _ptr(fe), _ptr(fl),
+        C.c_void_p(stream), None, None, None, None, info), info)[5]
+    for name, a, width in brought:
+        if a is not None and int(a.numel() if hasattr(a, "data_ptr") else a.size) != NFQ * width:
+            raise ValueError("out[%r]: %d doubles are needed" % (name, NFQ * width))
+    return NFQ
+
+
+def boundary_points(coords, elem_to_vertex, face_elem, face_local, elem_ptr=None, device=False,
+                    want=("fp_ptr", "xq", "wmeas", "normal"), out=None, stream=0, sizes_only=False):
+    """saamge_amd_boundary_points: (fp_ptr (NF + 1,) int64, xq (NFQ, dim), wmeas (NFQ,), normal (NFQ, dim)) -- the points of the
+    face rule of every listed face (point q of face f OF THE LIST: index fp_ptr[f] + q), their physical coordinates, weight *
+    measure there and the unit normal that points out of the owning element.  want: which of the four are asked for, the others
+    are passed as NULL and come back None; out: a dict of arrays / tensors to write into, by the same names.  device=True: torch
+    tensors on the GPU.  sizes_only: info (8 integers: faces by type [0..4], [5] = NFQ, -1, elements touched).  A refusal raises
+    RuntimeError with `.info` (info[6]: the first refused face) and writes nothing."""
+    coords, e2v, _, ep = _element_arrays(coords, elem_to_vertex, None, elem_ptr)
+    fe, fl, _, NF = _face_arrays(face_elem, face_local, None)
+    NV, dim, NE, nde, _ = _mass_sizes(coords, e2v, ep, 1, False)
+    out = dict(out or {})
+    want = () if sizes_only else tuple(want)
+    NFQ = _num_face_points(NV, dim, coords, NE, nde, ep, e2v, NF, fe, fl, stream,
+                           [(k, out.get(k), w) for k, w in (("xq", dim), ("wmeas", 1), ("normal", dim))]) if want else 0
+    fp = out.get("fp_ptr")
+    if fp is None and "fp_ptr" in want:
+        fp = _new_ints(NF + 1, np.int64, "int64", device)
+    xq = _new_or(out.get("xq"), NFQ * dim, device, "xq" in want)
+    wmeas = _new_or(out.get("wmeas"), NFQ, device, "wmeas" in want)
+    normal = _new_or(out.get("normal"), NFQ * dim, device, "normal" in want)
+    info = (C.c_longlong * 8)()
+    got = _mass_call(lambda: load().saamge_amd_boundary_points(
+        C.c_int(NV), C.c_int(dim), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_int(NF), _ptr(fe), _ptr(fl),
+        C.c_void_p(stream), _ptr(fp), _ptr(xq), _ptr(wmeas), _ptr(normal), info), info)
+    if sizes_only:
+        return got
+    return fp, None if xq is None else xq.reshape(NFQ, dim), wmeas, None if normal is None else normal.reshape(NFQ, dim)
+
+
+def boundary_eval(coords, elem_to_vertex, face_elem, face_local, u, vdim=1, elem_ptr=None, device=False, want=("uq", "gradq"),
+                  out=None, stream=0):
+    """saamge_amd_boundary_eval: (uq (NFQ, vdim), gradq (NFQ, vdim, dim)) of the nodal field u, (NV, vdim) or (NV,), at the points
+    of `boundary_points`: the trace through the face's shape functions and the WHOLE gradient of the owning element's field
+    (gradq[q, i, j]: component i along x_j).  want / out / device / stream as there; want=(): the checks only."""
+    coords, e2v, _, ep = _element_arrays(coords, elem_to_vertex, None, elem_ptr)
+    fe, fl, _, NF = _face_arrays(face_elem, face_local, None)
+    vdim = int(vdim)
+    NV, dim, NE, nde, _ = _mass_sizes(coords, e2v, ep, vdim, False)
+    out = dict(out or {})
+    NFQ = _num_face_points(NV, dim, coords, NE, nde, ep, e2v, NF, fe, fl, stream,
+                           [(k, out.get(k), w) for k, w in (("uq", vdim), ("gradq", vdim * dim))]) if want else 0
+    uq = _new_or(out.get("uq"), NFQ * vdim, device, "uq" in want)
+    gq = _new_or(out.get("gradq"), NFQ * vdim * dim, device, "gradq" in want)
+    info = (C.c_longlong * 8)()
+    _mass_call(lambda: load().saamge_amd_boundary_eval(
+        C.c_int(NV), C.c_int(dim), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_int(NF), _ptr(fe), _ptr(fl),
+        C.c_int(vdim), _ptr(_doubles(u)), C.c_void_p(stream), _ptr(uq), _ptr(gq), info), info)
+    return None if uq is None else uq.reshape(NFQ, vdim), None if gq is None else gq.reshape(NFQ, vdim, dim)
+
+
+def boundary_mass_points(coords, elem_to_vertex, face_elem, face_local, coefq, vdim=1, elem_ptr=None, add_to=None, device=False,
+                         stream=0, sizes_only=False):
+    """saamge_amd_boundary_mass_points: `boundary_mass` with the coefficient coefq (NFQ,) given at the points of
+    `boundary_points` -- alpha(u_q) formed from the output of `boundary_eval` goes in as it is.  Everything else as there; a
+    refusal writes nothing."""
+    coords, e2v, _, ep = _element_arrays(coords, elem_to_vertex, None, elem_ptr)
+    fe, fl, coefq, NF = _face_arrays(face_elem, face_local, coefq)
+    vdim = int(vdim)
+    NV, dim, NE, nde, doubles = _mass_sizes(coords, e2v, ep, vdim, True)
+    if not sizes_only:
+        add_to = _in_place_target(add_to, doubles, device)
+    info = (C.c_longlong * 8)()
+    got = _mass_call(lambda: load().saamge_amd_boundary_mass_points(
+        C.c_int(NV), C.c_int(dim), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_int(NF), _ptr(fe), _ptr(fl),
+        C.c_int(vdim), _ptr(coefq), C.c_void_p(stream), _ptr(None if sizes_only else add_to), info), info)
+    return got if sizes_only else add_to
+
+
+def boundary_loads_points(coords, elem_to_vertex, face_elem, face_local, gq, vdim=1, coef=None, elem_ptr=None, add_to=None,
+                          device=False, stream=0, sizes_only=False):
+    """saamge_amd_boundary_loads_points: `boundary_loads` of data given AT THE POINTS of `boundary_points`, gq (NFQ, vdim) or
+    (NFQ,); coef (NF,) or None: 1.  A flux g = k grad u . n formed from `normal` does not jump across the edges of a box, so all
+    sides go in one call.  Everything else as `boundary_loads`; a refusal writes nothing."""
+    coords, e2v, _, ep = _element_arrays(coords, elem_to_vertex, None, elem_ptr)
+    fe, fl, coef, NF = _face_arrays(face_elem, face_local, coef)
+    vdim = int(vdim)
+    NV, dim, NE, nde, doubles = _mass_sizes(coords, e2v, ep, vdim, False)
+    if not sizes_only:
+        add_to = _in_place_target(add_to, doubles, device)
+    info = (C.c_longlong * 8)()
+    got = _mass_call(lambda: load().saamge_amd_boundary_loads_points(
+        C.c_int(NV), C.c_int(dim), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_int(NF), _ptr(fe), _ptr(fl),
+        C.c_int(vdim), _ptr(coef), _ptr(_doubles(gq)), C.c_void_p(stream), _ptr(None if sizes_only else add_to), info), info)
     return got if sizes_only else add_to
 
 

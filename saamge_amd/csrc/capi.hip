@@ -867,6 +867,50 @@ int saamge_amd_boundary_loads(int NV, int dim, const double *coords, int NE, int
     SA_API_END
 }
 
+int saamge_amd_boundary_points(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                               const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, void *stream,
+                               long long *fp_ptr_out, double *xq_out, double *wmeas_out, double *normal_out, long long info[8]) {
+    SA_API_BEGIN
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
+    boundary_points(s, m, NF, face_elem, face_local, fp_ptr_out, xq_out, wmeas_out, normal_out, info);
+    SA_API_END
+}
+
+int saamge_amd_boundary_eval(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                             const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim,
+                             const double *u, void *stream, double *uq_out, double *gradq_out, long long info[8]) {
+    SA_API_BEGIN
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
+    boundary_eval(s, m, NF, face_elem, face_local, vdim, u, uq_out, gradq_out, info);
+    SA_API_END
+}
+
+int saamge_amd_boundary_mass_points(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                    const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim,
+                                    const double *coefq, void *stream, double *elmat_inout, long long info[8]) {
+    SA_API_BEGIN
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
+    boundary_mass_points(s, m, NF, face_elem, face_local, vdim, coefq, elmat_inout, info);
+    SA_API_END
+}
+
+int saamge_amd_boundary_loads_points(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
+                                     const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim,
+                                     const double *coef, const double *gq, void *stream, double *elvec_inout, long long info[8]) {
+    SA_API_BEGIN
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
+    boundary_loads_points(s, m, NF, face_elem, face_local, vdim, coef, gq, elvec_inout, info);
+    SA_API_END
+}
+
 int saamge_amd_element_points(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                               const int *elem_to_vertex, void *stream, long long *qp_ptr_out, double *xq_out, double *wdet_out,
                               long long info[8]) {

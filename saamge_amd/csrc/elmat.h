@@ -39,6 +39,25 @@ void boundary_mass(hipStream_t s, const MeshArgs &m, int NF, const int *face_ele
 void boundary_loads(hipStream_t s, const MeshArgs &m, int NF, const int *face_elem, const int *face_local, int vdim, const double *coef,
                     const double *g, double *elvec_inout, long long info[8]);
 
+// Boundary data at the face points (elmat_model.boundary_points / boundary_eval / boundary_mass_points / boundary_loads_points):
+// point q of face f of the list has the global index fp_ptr[f] + q, NFQ = fp_ptr[NF], in the order of the LIST.  Face lists, checks
+// and info[0..4], [6], [7] as boundary_mass; every pointer host or device; a refusal writes no output.
+// The arguments of saamge_amd_boundary_points: fp_ptr_out (NF + 1), xq_out (NFQ x dim), wmeas_out (NFQ), normal_out (NFQ x dim), the
+// unit normal out of the owning element; any of them may be NULL.  info[5] = NFQ.
+void boundary_points(hipStream_t s, const MeshArgs &m, int NF, const int *face_elem, const int *face_local, long long *fp_ptr_out,
+                     double *xq_out, double *wmeas_out, double *normal_out, long long info[8]);
+// The arguments of saamge_amd_boundary_eval: the nodal u (NV x vdim) at the face points, uq_out (NFQ x vdim) the trace and gradq_out
+// (NFQ x vdim x dim) the whole gradient of the owning element's field; either may be NULL.  The first face whose element has a
+// non-positive determinant at a face point is refused.  info[5] = NFQ.
+void boundary_eval(hipStream_t s, const MeshArgs &m, int NF, const int *face_elem, const int *face_local, int vdim, const double *u,
+                   double *uq_out, double *gradq_out, long long info[8]);
+// The arguments of saamge_amd_boundary_mass_points: boundary_mass with the coefficient coefq (NFQ) given at the face points.
+void boundary_mass_points(hipStream_t s, const MeshArgs &m, int NF, const int *face_elem, const int *face_local, int vdim,
+                          const double *coefq, double *elmat_inout, long long info[8]);
+// The arguments of saamge_amd_boundary_loads_points: boundary_loads of gq (NFQ x vdim) given at the face points; coef (NF) NULL: 1.0.
+void boundary_loads_points(hipStream_t s, const MeshArgs &m, int NF, const int *face_elem, const int *face_local, int vdim,
+                           const double *coef, const double *gq, double *elvec_inout, long long info[8]);
+
 // Data at the points of the mass rule (elmat_model.element_points / element_eval / element_loads_points / element_errors): point q
 // of element e has the global index qp_ptr[e] + q, NQ = qp_ptr[NE].  Every pointer host or device; a refusal writes no output.
 // The arguments of saamge_amd_element_points: qp_ptr_out (NE + 1), xq_out (NQ x dim), wdet_out (NQ); any of them may be NULL.

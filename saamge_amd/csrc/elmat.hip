@@ -36,6 +36,12 @@
 // that turns a type index into a launch (em_launch_type, mass_launch_type, qp_launch_type, bdr_launch_face), the frame of a
 // call (EmFrame: mesh, launch arguments, outputs on the host or the device, the bad word, the loop over the types, the
 // refusal, the copy home) and the four drivers on it (stiffness, mass_or_loads, points_call, boundary_forms).  DESIGN.md 4.9.7.
+//
+// Boundary data at the face points -- where the points of the listed faces are, the outward unit normals, the trace and the whole
+// gradient of a nodal field there, the face mass with a coefficient per point and the face loads of data given at the points -- runs
+// on the stage and point phases of the boundary forms (bdr_stage_points; bdr_points_kernel, bdr_mass_q_kernel, bdr_load_q_kernel)
+// and, for the gradient, on a kernel templated on the element type that stages all nodes of the owning element (bdr_eval_kernel).
+// DESIGN.md 4.9.8.
 #include "elmat.h"
 #include "elmat_ref.h"
 
@@ -1174,11 +1180,15 @@ __global__ __launch_bounds__(256) void bdr_touched_kernel(int nwords, const unsi
 //   point   one lane per (face, point): the tangents, m2, meas = sqrt(m2) and s = (w * meas) * c in registers; a measure that
 //           is not positive sends the face's index in the list to the integer minimum *bad
 // list: the faces of this launch (indices into face_elem / coef), all of one element type (nd nodes) and one local face F.
-template <int DIM, int FN, int VDIM, int FPB>
+// fp (the calls on data at the face points; nullptr: none): the offsets of the faces' points, fp[f] of every staged face to sO.
+// CQ: coef holds one coefficient per POINT, point q of face f at fp[f] + q, in the place of one per face.  GEOM: the unit normal
+// of every point to sNrm, DIM doubles per (face, point): (n0, n1, n2) / meas, in 2D (t_y, -t_x) / meas, the division last.
+template <int DIM, int FN, int VDIM, int FPB, bool CQ = false, bool GEOM = false>
 __device__ inline void bdr_stage_points(int count, const int *__restrict__ list, const BdrFace &F, int nd, const int *__restrict__ eI,
                                         const int *__restrict__ eJ, const int *__restrict__ face_elem,
                                         const double *__restrict__ coords, const double *__restrict__ coef,
-                                        const double *__restrict__ g, double *sX, double *sG, double *sS, int *sE, int *bad) {
+                                        const double *__restrict__ g, double *sX, double *sG, double *sS, int *sE, int *bad,
+                                        const roff_t *__restrict__ fp = nullptr, roff_t *sO = nullptr, double *sNrm = nullptr) {
     constexpr int NQ = BdrTable<DIM, FN>::NQ;
     const BdrTable<DIM, FN> &T = bdr_rule_table<DIM, FN>();
     __shared__ double sC[FPB];
@@ -1205,12 +1215,14 @@ __device__ inline void bdr_stage_points(int count, const int *__restrict__ list,
             if (a == 0) {
                 sE[fl] = e;
                 sF[fl] = f;
-                sC[fl] = coef ? coef[f] : 1.0;
+                sC[fl] = coef && !CQ ? coef[f] : 1.0;
+                if (fp) sO[fl] = fp[f];
             }
         } else if (a == 0) {
             sE[fl] = -1;
             sF[fl] = -1;
             sC[fl] = 0.0;
+            if (fp) sO[fl] = 0;
         }
 #pragma unroll
         for (int d = 0; d < DIM; ++d) sX[idx * DIM + d] = x[d];
@@ -1233,17 +1245,26 @@ __device__ inline void bdr_stage_points(int count, const int *__restrict__ list,
                 for (int c = 1; c < FN; ++c) v = v + X[c * DIM + i] * T.dN[c][q][j];
                 t[j][i] = v;
             }
+        double n[DIM];
         if constexpr (DIM == 2) {
             m2 = t[0][0] * t[0][0] + t[0][1] * t[0][1];
+            n[0] = t[0][1];
+            n[1] = -t[0][0];
         } else {
-            const double n0 = t[0][1] * t[DIM - 2][2] - t[0][2] * t[DIM - 2][1];
-            const double n1 = t[0][2] * t[DIM - 2][0] - t[0][0] * t[DIM - 2][2];
-            const double n2 = t[0][0] * t[DIM - 2][1] - t[0][1] * t[DIM - 2][0];
-            m2 = (n0 * n0 + n1 * n1) + n2 * n2;
+            n[0] = t[0][1] * t[DIM - 2][2] - t[0][2] * t[DIM - 2][1];
+            n[1] = t[0][2] * t[DIM - 2][0] - t[0][0] * t[DIM - 2][2];
+            n[2] = t[0][0] * t[DIM - 2][1] - t[0][1] * t[DIM - 2][0];
+            m2 = (n[0] * n[0] + n[1] * n[1]) + n[DIM - 1] * n[DIM - 1];
         }
         const double meas = sqrt(m2);
         if (!(meas > 0.0) && sF[fl] >= 0) atomicMin(bad, sF[fl]);
-        sS[idx] = (T.w[q] * meas) * sC[fl];
+        double c = sC[fl];
+        if constexpr (CQ) c = sF[fl] >= 0 ? coef[sO[fl] + q] : 0.0;
+        sS[idx] = (T.w[q] * meas) * c;
+        if constexpr (GEOM) {
+#pragma unroll
+            for (int i = 0; i < DIM; ++i) sNrm[idx * DIM + i] = n[i] / meas;
+        }
     }
     __syncthreads();
 }
@@ -1251,18 +1272,22 @@ __device__ inline void bdr_stage_points(int count, const int *__restrict__ list,
 // The face mass, added to the matrices in out (nullptr: the checks only).  After stage and point:
 //   entry   one lane per (face, node pair a <= b of the face): the whole sum over the points, in ascending order, lives in the
 //           lane and is added to the element's entries (a, b) and (b, a) of every component in global memory
-template <int DIM, int FN, int VDIM>
-__global__ __launch_bounds__(BDR_BLOCK) void bdr_mass_kernel(int count, const int *__restrict__ list, const BdrFace F, int nd,
-                                                             const int *__restrict__ eI, const int *__restrict__ eJ,
-                                                             const roff_t *__restrict__ moff, const int *__restrict__ face_elem,
-                                                             const double *__restrict__ coords, const double *__restrict__ coef,
-                                                             double *out, int *__restrict__ bad) {
+// The body serves bdr_mass_kernel (fp nullptr: coef one double per face) and, at the face points, saamge_amd_boundary_mass_points
+// (coef one double per POINT, point q of face f at fp[f] + q).
+template <int DIM, int FN, int VDIM, bool CQ>
+__device__ __forceinline__ void bdr_mass_body(int count, const int *__restrict__ list, const BdrFace &F, int nd,
+                                              const int *__restrict__ eI, const int *__restrict__ eJ, const roff_t *__restrict__ moff,
+                                              const int *__restrict__ face_elem, const double *__restrict__ coords,
+                                              const double *__restrict__ coef, const roff_t *__restrict__ fp, double *out,
+                                              int *__restrict__ bad) {
     constexpr int FPB = bdr_fpb(FN), NQ = BdrTable<DIM, FN>::NQ, NPAIR = FN * (FN + 1) / 2;
     const BdrTable<DIM, FN> &T = bdr_rule_table<DIM, FN>();
     __shared__ double sX[FPB * FN * DIM];
     __shared__ double sS[FPB * NQ];
+    __shared__ roff_t sO[CQ ? FPB : 1];
     __shared__ int sE[FPB];
-    bdr_stage_points<DIM, FN, VDIM, FPB>(count, list, F, nd, eI, eJ, face_elem, coords, coef, nullptr, sX, nullptr, sS, sE, bad);
+    bdr_stage_points<DIM, FN, VDIM, FPB, CQ>(count, list, F, nd, eI, eJ, face_elem, coords, coef, nullptr, sX, nullptr, sS, sE, bad, fp,
+                                             sO);
     if (!out) return;                             // (the same in every lane of the grid)
     const int S = nd * VDIM;
     for (int idx = threadIdx.x; idx < FPB * NPAIR; idx += BDR_BLOCK) {
@@ -1286,32 +1311,58 @@ __global__ __launch_bounds__(BDR_BLOCK) void bdr_mass_kernel(int count, const in
         }
     }
 }
+template <int DIM, int FN, int VDIM>
+__global__ __launch_bounds__(BDR_BLOCK) void bdr_mass_kernel(int count, const int *__restrict__ list, const BdrFace F, int nd,
+                                                             const int *__restrict__ eI, const int *__restrict__ eJ,
+                                                             const roff_t *__restrict__ moff, const int *__restrict__ face_elem,
+                                                             const double *__restrict__ coords, const double *__restrict__ coef,
+                                                             double *out, int *__restrict__ bad) {
+    bdr_mass_body<DIM, FN, VDIM, false>(count, list, F, nd, eI, eJ, moff, face_elem, coords, coef, nullptr, out, bad);
+}
+// coefq: one coefficient per point, point q of face f at fp[f] + q
+template <int DIM, int FN, int VDIM>
+__global__ __launch_bounds__(BDR_BLOCK) void bdr_mass_q_kernel(int count, const int *__restrict__ list, const BdrFace F, int nd,
+                                                               const int *__restrict__ eI, const int *__restrict__ eJ,
+                                                               const roff_t *__restrict__ moff, const int *__restrict__ face_elem,
+                                                               const double *__restrict__ coords, const double *__restrict__ coefq,
+                                                               const roff_t *__restrict__ fp, double *out, int *__restrict__ bad) {
+    bdr_mass_body<DIM, FN, VDIM, true>(count, list, F, nd, eI, eJ, moff, face_elem, coords, coefq, fp, out, bad);
+}
 
 // The face loads of the nodal g (NV x VDIM), added to the vectors in out (nullptr: the checks only).  After stage and point:
 //   source  one lane per (face, point, component): gq = sum over the face nodes, ascending, of N_c * g_c; s * gq is kept
 //   dof     one lane per (face, face node, component): the whole sum over the points of (s * gq) * N_a, added to the element's
 //           vector at the dof of the node in global memory
-template <int DIM, int FN, int VDIM>
-__global__ __launch_bounds__(BDR_BLOCK) void bdr_load_kernel(int count, const int *__restrict__ list, const BdrFace F, int nd,
-                                                             const int *__restrict__ eI, const int *__restrict__ eJ,
-                                                             const int *__restrict__ face_elem, const double *__restrict__ coords,
-                                                             const double *__restrict__ coef, const double *__restrict__ g,
-                                                             double *out, int *__restrict__ bad) {
+// The body serves bdr_load_kernel (GQ false) and, at the face points, saamge_amd_boundary_loads_points (GQ true: g holds the data
+// AT THE POINTS, row fp[f] + q for point q of face f, read where bdr_load_kernel interpolates the nodal data).
+template <int DIM, int FN, int VDIM, bool GQ>
+__device__ __forceinline__ void bdr_load_body(int count, const int *__restrict__ list, const BdrFace &F, int nd,
+                                              const int *__restrict__ eI, const int *__restrict__ eJ, const int *__restrict__ face_elem,
+                                              const double *__restrict__ coords, const double *__restrict__ coef,
+                                              const double *__restrict__ g, const roff_t *__restrict__ fp, double *out,
+                                              int *__restrict__ bad) {
     constexpr int FPB = bdr_fpb(FN), NQ = BdrTable<DIM, FN>::NQ;
     const BdrTable<DIM, FN> &T = bdr_rule_table<DIM, FN>();
     __shared__ double sX[FPB * FN * DIM];
-    __shared__ double sG[FPB * FN * VDIM];
+    __shared__ double sG[GQ ? 1 : FPB * FN * VDIM];
     __shared__ double sS[FPB * NQ];
     __shared__ double sQ[FPB * NQ * VDIM];
+    __shared__ roff_t sO[GQ ? FPB : 1];
     __shared__ int sE[FPB];
-    bdr_stage_points<DIM, FN, VDIM, FPB>(count, list, F, nd, eI, eJ, face_elem, coords, coef, g, sX, sG, sS, sE, bad);
+    bdr_stage_points<DIM, FN, VDIM, FPB>(count, list, F, nd, eI, eJ, face_elem, coords, coef, GQ ? nullptr : g, sX, sG, sS, sE, bad, fp,
+                                         sO);
     if (!out) return;                             // (the same in every lane of the grid)
     const int tid = threadIdx.x;
     for (int idx = tid; idx < FPB * NQ * VDIM; idx += BDR_BLOCK) {
         const int fl = idx / (NQ * VDIM), r = idx - fl * (NQ * VDIM), q = r / VDIM, i = r - q * VDIM;
-        const double *G = sG + fl * FN * VDIM + i;
-        double gq = T.N[q][0] * G[0];
-        for (int c = 1; c < FN; ++c) gq = gq + T.N[q][c] * G[c * VDIM];
+        double gq;
+        if constexpr (GQ) {
+            gq = sE[fl] < 0 ? 0.0 : g[sO[fl] * VDIM + r];
+        } else {
+            const double *G = sG + fl * FN * VDIM + i;
+            gq = T.N[q][0] * G[0];
+            for (int c = 1; c < FN; ++c) gq = gq + T.N[q][c] * G[c * VDIM];
+        }
         sQ[idx] = sS[fl * NQ + q] * gq;
     }
     __syncthreads();
@@ -1329,6 +1380,178 @@ __global__ __launch_bounds__(BDR_BLOCK) void bdr_load_kernel(int count, const in
         const long vb = eI ? (long)eI[e] : (long)e * nd;
         double *v = out + (vb + F.node[a]) * VDIM + i;
         *v = *v + acc;
+    }
+}
+template <int DIM, int FN, int VDIM>
+__global__ __launch_bounds__(BDR_BLOCK) void bdr_load_kernel(int count, const int *__restrict__ list, const BdrFace F, int nd,
+                                                             const int *__restrict__ eI, const int *__restrict__ eJ,
+                                                             const int *__restrict__ face_elem, const double *__restrict__ coords,
+                                                             const double *__restrict__ coef, const double *__restrict__ g,
+                                                             double *out, int *__restrict__ bad) {
+    bdr_load_body<DIM, FN, VDIM, false>(count, list, F, nd, eI, eJ, face_elem, coords, coef, g, nullptr, out, bad);
+}
+template <int DIM, int FN, int VDIM>
+__global__ __launch_bounds__(BDR_BLOCK) void bdr_load_q_kernel(int count, const int *__restrict__ list, const BdrFace F, int nd,
+                                                               const int *__restrict__ eI, const int *__restrict__ eJ,
+                                                               const int *__restrict__ face_elem, const double *__restrict__ coords,
+                                                               const double *__restrict__ coef, const double *__restrict__ gq,
+                                                               const roff_t *__restrict__ fp, double *out, int *__restrict__ bad) {
+    bdr_load_body<DIM, FN, VDIM, true>(count, list, F, nd, eI, eJ, face_elem, coords, coef, gq, fp, out, bad);
+}
+
+// ---- boundary data at the face points ---------------------------------------------------------------------------------------------
+// elmat_model.py's boundary_points / boundary_eval (boundary_mass_points and boundary_loads_points: the bodies above).  Point q of
+// face f OF THE LIST has the global index fp[f] + q (fp: NF + 1 offsets, 64 bits), whatever bucket the face is worked in: the
+// kernels place what they write through fp[f] of the face's index in the list.
+// The points of the faces: xq (NFQ x DIM), wmeas (NFQ), normal (NFQ x DIM); any may be nullptr.  After stage and point, one lane
+// per (face, point, coordinate): consecutive lanes store consecutive doubles of a face's rows.
+template <int DIM, int FN>
+__global__ __launch_bounds__(BDR_BLOCK) void bdr_points_kernel(int count, const int *__restrict__ list, const BdrFace F, int nd,
+                                                               const int *__restrict__ eI, const int *__restrict__ eJ,
+                                                               const int *__restrict__ face_elem, const double *__restrict__ coords,
+                                                               const roff_t *__restrict__ fp, double *__restrict__ xq,
+                                                               double *__restrict__ wmeas, double *__restrict__ normal,
+                                                               int *__restrict__ bad) {
+    constexpr int FPB = bdr_fpb(FN), NQ = BdrTable<DIM, FN>::NQ;
+    const BdrTable<DIM, FN> &T = bdr_rule_table<DIM, FN>();
+    __shared__ double sX[FPB * FN * DIM];
+    __shared__ double sS[FPB * NQ];
+    __shared__ double sNrm[FPB * NQ * DIM];
+    __shared__ roff_t sO[FPB];
+    __shared__ int sE[FPB];
+    bdr_stage_points<DIM, FN, 1, FPB, false, true>(count, list, F, nd, eI, eJ, face_elem, coords, nullptr, nullptr, sX, nullptr, sS, sE,
+                                                   bad, fp, sO, sNrm);      // (the coefficient is 1.0: s = weight * meas)
+    for (int idx = threadIdx.x; idx < FPB * NQ * DIM; idx += BDR_BLOCK) {
+        const int fl = idx / (NQ * DIM), r = idx - fl * (NQ * DIM), q = r / DIM, i = r - q * DIM;
+        if (sE[fl] < 0) continue;
+        const roff_t at = sO[fl] * DIM + r;
+        if (normal) normal[at] = sNrm[idx];
+        if (wmeas && i == 0) wmeas[sO[fl] + q] = sS[fl * NQ + q];
+        if (xq) {
+            const double *X = sX + fl * FN * DIM + i;
+            double x = T.N[q][0] * X[0];
+            for (int c = 1; c < FN; ++c) x = x + T.N[q][c] * X[c * DIM];
+            xq[at] = x;
+        }
+    }
+}
+
+// the element's gradients at the points of its local faces (FaceGradTable, elmat_ref.h): the largest, the 27-node hexahedron's,
+// has 6 x 27 x 9 x 3 doubles (35 KB).  The objects live in global memory like the tables of the rules; a launch works one local
+// face, whose block (at most 5.8 KB) the workgroup copies to LDS: the lanes of the J phase read it at addresses that differ from
+// lane to lane, as mass_point_phases reads sD.
+template <int DIM, int ND>
+__device__ const FaceGradTable<DIM, ND> FACE_GRAD_TABLE = face_grad_table<DIM, ND>();
+// faces per workgroup: bdr_fpb's, except where an element of 10 or more nodes per face would take the LDS past 32 KB
+constexpr int bdr_eval_fpb(int nd, int fn) { return nd >= 10 && fn != 9 ? 16 : bdr_fpb(fn); }
+
+// The nodal u (NV x VDIM) at the face points: uq (NFQ x VDIM), the trace through the face's own shape functions (gq of
+// bdr_load_kernel), and gradq (NFQ x VDIM x DIM), the whole gradient of the owning element's field; either may be nullptr.
+// Templated on the ELEMENT type <DIM, ND> and on the face type FN; lf: the local face of this launch.  Phases:
+//   element the coordinates and u of ALL ND nodes of the owning element and the block of the face's gradients into LDS
+//   stage, point   bdr_stage_points: the face's nodes (with u), the measures (not positive: the face to *bad)
+//   J       one lane per (face, point): J[i][j] = sum over the element's nodes, ascending, of x_a[i] * dN_a[j], the cofactors and
+//           det (not positive: the face's index in the list to *bad_det) to sP, as mass_point_phases keeps them
+//   value   one lane per (face, point, component): uq and, as qp_value forms it, r[k] = sum over the nodes of u_a * dN_a[k],
+//           g[j] = (r . C[j]) / det
+template <int DIM, int ND, int FN, int VDIM>
+__global__ __launch_bounds__(BDR_BLOCK) void bdr_eval_kernel(int count, const int *__restrict__ list, const BdrFace F, int lf,
+                                                             const int *__restrict__ eI, const int *__restrict__ eJ,
+                                                             const int *__restrict__ face_elem, const double *__restrict__ coords,
+                                                             const double *__restrict__ u, const roff_t *__restrict__ fp,
+                                                             double *__restrict__ uq, double *__restrict__ gradq,
+                                                             int *__restrict__ bad, int *__restrict__ bad_det) {
+    constexpr int FPB = bdr_eval_fpb(ND, FN), NQ = BdrTable<DIM, FN>::NQ, MQ = FaceGradTable<DIM, ND>::MAXQ, DD = DIM * DIM, PW = DD + 1;
+    const BdrTable<DIM, FN> &T = bdr_rule_table<DIM, FN>();
+    __shared__ double sX[FPB * FN * DIM];
+    __shared__ double sG[FPB * FN * VDIM];
+    __shared__ double sS[FPB * NQ];
+    __shared__ double sXe[FPB * ND * DIM];
+    __shared__ double sUe[FPB * ND * VDIM];
+    __shared__ double sD[ND * MQ * DIM];
+    __shared__ double sP[FPB * NQ * PW];
+    __shared__ roff_t sO[FPB];
+    __shared__ int sE[FPB];
+    const int tid = threadIdx.x;
+    // ---- element (the barriers of bdr_stage_points cover it)
+    for (int idx = tid; idx < FPB * ND; idx += BDR_BLOCK) {
+        const int fl = idx / ND, a = idx - fl * ND;
+        const long slot = (long)blockIdx.x * FPB + fl;
+        double x[DIM], uv[VDIM];
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) x[d] = 0.0;
+#pragma unroll
+        for (int i = 0; i < VDIM; ++i) uv[i] = 0.0;
+        if (slot < count) {
+            const int e = face_elem[list[slot]];
+            const long vb = eI ? (long)eI[e] : (long)e * ND;
+            const int v = eJ[vb + a];
+#pragma unroll
+            for (int d = 0; d < DIM; ++d) x[d] = coords[(long)v * DIM + d];
+#pragma unroll
+            for (int i = 0; i < VDIM; ++i) uv[i] = u[(long)v * VDIM + i];
+        }
+#pragma unroll
+        for (int d = 0; d < DIM; ++d) sXe[idx * DIM + d] = x[d];
+#pragma unroll
+        for (int i = 0; i < VDIM; ++i) sUe[idx * VDIM + i] = uv[i];
+    }
+    const double *D = &FACE_GRAD_TABLE<DIM, ND>.dN[lf][0][0][0];
+    for (int idx = tid; idx < ND * MQ * DIM; idx += BDR_BLOCK) sD[idx] = D[idx];
+    bdr_stage_points<DIM, FN, VDIM, FPB>(count, list, F, ND, eI, eJ, face_elem, coords, nullptr, u, sX, sG, sS, sE, bad, fp, sO);
+    // ---- J
+    for (int idx = tid; idx < FPB * NQ; idx += BDR_BLOCK) {
+        const int fl = idx / NQ, q = idx - fl * NQ;
+        const double *X = sXe + fl * ND * DIM, *Dq = sD + q * DIM;
+        double J[DIM][DIM], C[DIM][DIM], det;
+#pragma unroll
+        for (int i = 0; i < DIM; ++i)
+#pragma unroll
+            for (int j = 0; j < DIM; ++j) {
+                double t = X[i] * Dq[j];
+                for (int a = 1; a < ND; ++a) t = t + X[a * DIM + i] * Dq[a * MQ * DIM + j];
+                J[i][j] = t;
+            }
+        em_cofactors<DIM>(J, C, det);
+        if (!(det > 0.0) && sE[fl] >= 0) atomicMin(bad_det, list[(long)blockIdx.x * FPB + fl]);
+        double *P = sP + idx * PW;
+#pragma unroll
+        for (int i = 0; i < DIM; ++i)
+#pragma unroll
+            for (int j = 0; j < DIM; ++j) P[i * DIM + j] = C[i][j];
+        P[DD] = det;
+    }
+    if (!uq && !gradq) return;                    // (the same in every lane of the grid)
+    __syncthreads();
+    // ---- value
+    for (int idx = tid; idx < FPB * NQ * VDIM; idx += BDR_BLOCK) {
+        const int fl = idx / (NQ * VDIM), r = idx - fl * (NQ * VDIM), q = r / VDIM, i = r - q * VDIM;
+        if (sE[fl] < 0) continue;
+        const roff_t at = sO[fl] * VDIM + r;
+        if (uq) {
+            const double *G = sG + fl * FN * VDIM + i;
+            double v = T.N[q][0] * G[0];
+            for (int c = 1; c < FN; ++c) v = v + T.N[q][c] * G[c * VDIM];
+            uq[at] = v;
+        }
+        if (gradq) {
+            const double *U = sUe + fl * ND * VDIM + i, *Dq = sD + q * DIM, *P = sP + (fl * NQ + q) * PW;
+            double rr[DIM];
+#pragma unroll
+            for (int k = 0; k < DIM; ++k) rr[k] = U[0] * Dq[k];
+            for (int a = 1; a < ND; ++a) {
+                const double f = U[a * VDIM];
+#pragma unroll
+                for (int k = 0; k < DIM; ++k) rr[k] = rr[k] + f * Dq[a * MQ * DIM + k];
+            }
+            const double det = P[DD];
+#pragma unroll
+            for (int j = 0; j < DIM; ++j) {
+                double t = rr[0] * P[j * DIM + 0] + rr[1] * P[j * DIM + 1];
+                if constexpr (DIM == 3) t = t + rr[2] * P[j * DIM + 2];
+                gradq[at * DIM + j] = t / det;
+            }
+        }
     }
 }
 
@@ -1442,21 +1665,54 @@ void qp_launch_type(QpCall call, const EmLaunch &L, const QpLaunch &Q, int type,
     });
 }
 
-// the boundary forms of the faces `list` of elements of type `type` (em_type_index) with the local face index lf: the face loads
-// of g, or (g nullptr) the face mass
-void bdr_launch_face(const EmLaunch &L, const int *face_elem, const double *g, int dim, int vdim, int type, int lf, int count,
+// the calls on a face list: what they launch with beyond EmLaunch (its coef: per face, or per point for BDR_MASS with fp; its out:
+// the matrices / vectors of BDR_MASS / BDR_LOADS)
+enum BdrCall { BDR_MASS, BDR_LOADS, BDR_POINTS, BDR_EVAL };
+struct BdrLaunch {
+    const int *face_elem;
+    const double *in;         // g at the nodes, or with fp at the points (BDR_LOADS); u (BDR_EVAL)
+    const roff_t *fp;         // the offsets of the faces' points; nullptr: the forms with data per face / at the nodes
+    double *a, *b, *c;        // xq, wmeas, normal / uq, gradq, -
+    int *bad_det;             // BDR_EVAL: the first face whose element has a non-positive determinant at a face point
+};
+// the call on the faces `list` of elements of type `type` (em_type_index) with the local face index lf
+void bdr_launch_face(BdrCall call, const EmLaunch &L, const BdrLaunch &B, int dim, int vdim, int type, int lf, int count,
                      const int *list) {
     const BdrFace F = bdr_face(type, lf);
-    const int nd = EM_TYPE_ND[type];
-    const bool found = with_face_type(dim, BDR_FACE_NODES[type][lf], [&](auto tag) {
+    const int nd = EM_TYPE_ND[type], fn = BDR_FACE_NODES[type][lf];
+    bool found = false;
+    if (call == BDR_EVAL) {      // templated on the element type too
+        with_elem_type(type, [&](auto etag) {
+            with_face_nodes(etag, fn, [&](auto fc) {
+                with_vdim(etag, vdim, [&](auto t, auto vd) {
+                    constexpr int DIM = decltype(t)::DIM, ND = decltype(t)::ND, FN = decltype(fc)::value, VDIM = decltype(vd)::value;
+                    em_run(bdr_eval_kernel<DIM, ND, FN, VDIM>, L.s, div_up(count, bdr_eval_fpb(ND, FN)), BDR_BLOCK, count, list, F, lf, L.eI,
+                           L.eJ, B.face_elem, L.coords, B.in, B.fp, B.a, B.b, L.bad, B.bad_det);
+                    found = true;
+                });
+            });
+        });
+        SA_REQUIRE(found, "boundary forms: no such face type");
+        return;
+    }
+    found = with_face_type(dim, fn, [&](auto tag) {
         with_vdim(tag, vdim, [&](auto t, auto vd) {
             constexpr int DIM = decltype(t)::DIM, FN = decltype(t)::ND, VDIM = decltype(vd)::value;
             const int blocks = div_up(count, bdr_fpb(FN));
-            if (g)
-                em_run(bdr_load_kernel<DIM, FN, VDIM>, L.s, blocks, BDR_BLOCK, count, list, F, nd, L.eI, L.eJ, face_elem, L.coords, L.coef,
-                       g, L.out, L.bad);
+            if (call == BDR_POINTS)
+                em_run(bdr_points_kernel<DIM, FN>, L.s, blocks, BDR_BLOCK, count, list, F, nd, L.eI, L.eJ, B.face_elem, L.coords, B.fp, B.a,
+                       B.b, B.c, L.bad);
+            else if (call == BDR_LOADS && B.fp)
+                em_run(bdr_load_q_kernel<DIM, FN, VDIM>, L.s, blocks, BDR_BLOCK, count, list, F, nd, L.eI, L.eJ, B.face_elem, L.coords,
+                       L.coef, B.in, B.fp, L.out, L.bad);
+            else if (call == BDR_LOADS)
+                em_run(bdr_load_kernel<DIM, FN, VDIM>, L.s, blocks, BDR_BLOCK, count, list, F, nd, L.eI, L.eJ, B.face_elem, L.coords, L.coef,
+                       B.in, L.out, L.bad);
+            else if (B.fp)
+                em_run(bdr_mass_q_kernel<DIM, FN, VDIM>, L.s, blocks, BDR_BLOCK, count, list, F, nd, L.eI, L.eJ, L.moff, B.face_elem,
+                       L.coords, L.coef, B.fp, L.out, L.bad);
             else
-                em_run(bdr_mass_kernel<DIM, FN, VDIM>, L.s, blocks, BDR_BLOCK, count, list, F, nd, L.eI, L.eJ, L.moff, face_elem, L.coords,
+                em_run(bdr_mass_kernel<DIM, FN, VDIM>, L.s, blocks, BDR_BLOCK, count, list, F, nd, L.eI, L.eJ, L.moff, B.face_elem, L.coords,
                        L.coef, L.out, L.bad);
         });
     });
@@ -1612,8 +1868,8 @@ struct EmFrame {
             if (M.count[t]) f(t, M.count[t], (const int *)M.list[t].p);
     }
     // the integer minimum the kernels left in the bad word: the first element (face) of `limit` that is refused
-    void refuse_bad(int limit, const char *noun, const char *what) {
-        const int bad = read_one((const int *)M.word.p, s);
+    void refuse_bad(int limit, const char *noun, const char *what, const int *word = nullptr) {
+        const int bad = read_one(word ? word : (const int *)M.word.p, s);
         if (bad < limit) {
             if (info) info[6] = bad;
             SA_REQUIRE(false, name + noun + std::to_string(bad) + what);
@@ -1757,15 +2013,53 @@ void points_call(QpCall call, hipStream_t s, const std::string &name, const Mesh
     F.sync();
 }
 
-// the face mass (g nullptr) or the face loads of the arguments of saamge_amd_boundary_mass / _loads, already checked
-void boundary_forms(hipStream_t s, const std::string &name, const MeshArgs &m, int NF, const int *face_elem, const int *face_local,
-                    int vdim, const double *coef, const double *g, double *out, long long info[8]) {
+// ---- the offsets of the points of a face list ---------------------------------------------------------------------------------------
+// the points of the rule of local face lf of element type t, by the key t * 8 + lf that bdr_check_kernel gives every face
+struct BdrPointCounts {
+    unsigned char n[EM_TYPES * 8];
+};
+constexpr BdrPointCounts bdr_point_counts() {
+    BdrPointCounts c{};
+    for (int t = 0; t < EM_TYPES; ++t)
+        for (int lf = 0; lf < bdr_num_faces(t); ++lf)
+            c.n[t * 8 + lf] = (unsigned char)face_points(em_type_dim(t), BDR_FACE_NODES[t][lf]);
+    return c;
+}
+__device__ const BdrPointCounts BDR_POINT_COUNTS = bdr_point_counts();
+__global__ __launch_bounds__(256) void bdr_point_count_kernel(int NF, const int *__restrict__ key, int *__restrict__ cnt) {
+    const long f = (long)blockIdx.x * 256 + threadIdx.x;
+    if (f < NF) cnt[f] = BDR_POINT_COUNTS.n[key[f]];      // (the list has been checked: no key is negative)
+}
+// fp: the NF + 1 offsets on the device, in the order of the list; returns NFQ
+int64_t bdr_offsets(hipStream_t s, int NF, const int *key, DBuf<roff_t> &fp) {
+    DBuf<int> cnt((size_t)NF);
+    fp.alloc((size_t)NF + 1);
+    em_run(bdr_point_count_kernel, s, div_up(NF, 256), 256, NF, key, cnt.p);
+    exclusive_scan_off(s, NF, cnt.p, fp.p);
+    return read_one(fp.p + NF, s);
+}
+
+// The calls on a face list, their arguments already checked.  BDR_MASS / BDR_LOADS with at_points false: saamge_amd_boundary_mass
+// / _loads (coef per face, `in` the nodal g; out_a the matrices / vectors added to).  at_points: the four calls on data at the face
+// points -- BDR_MASS: coef per POINT; BDR_LOADS: `in` the data at the points; BDR_POINTS: fp_out, out_a / _b / _c = xq, wmeas,
+// normal; BDR_EVAL: `in` the nodal u, out_a / _b = uq, gradq.  These four refuse before they write: a pass of their kernels without
+// outputs checks every measure (and determinant) first.
+void boundary_forms(BdrCall call, bool at_points, hipStream_t s, const std::string &name, const MeshArgs &m, int NF,
+                    const int *face_elem, const int *face_local, int vdim, const double *coef, const double *in, long long *fp_out,
+                    double *out_a, double *out_b, double *out_c, long long info[8]) {
     const int dim = m.dim, NE = m.NE;
-    if (NF == 0) return;
+    if (NF == 0) {
+        if (fp_out) {      // (the one offset of an empty list; without it an empty list touches no device)
+            const long long zero = 0;
+            SA_HIP_CHECK(hipMemcpyAsync(fp_out, &zero, sizeof(zero), hipMemcpyDefault, s));
+            SA_HIP_CHECK(hipStreamSynchronize(s));
+        }
+        return;
+    }
     if (NE == 0 && info) info[6] = 0;
     SA_REQUIRE(NE > 0, name + "face 0: face_elem is outside [0, NE)");
     EmFrame F(s, name, m, info);
-    F.open(vdim, !g, false);
+    F.open(vdim, call == BDR_MASS, false);
     // ---- the face list: ranges, repeated pairs, the key of every face
     FaceList FL;
     check_face_list(s, name, dim, NE, F.M.eI, NF, face_elem, face_local, FL, info ? info + 6 : nullptr);
@@ -1779,24 +2073,55 @@ void boundary_forms(hipStream_t s, const std::string &name, const MeshArgs &m, i
             const int c = count[t][lf] = make_list(s, NF, FL.key.p, t * 8 + lf, flag, pos, list[t][lf]);
             const int fn = BDR_FACE_NODES[t][lf];
             if (info) info[bdr_face_type(dim, fn)] += c;
-            doubles += (int64_t)c * (g ? fn * vdim : fn * fn * vdim);
+            doubles += (int64_t)c * (call == BDR_MASS ? fn * fn * vdim : fn * vdim);
         }
     });
+    // ---- the offsets of the points, in the order of the LIST
+    DBuf<roff_t> fp;
+    const size_t nfq = at_points ? (size_t)bdr_offsets(s, NF, FL.key.p, fp) : 0;
     if (info) {
-        info[5] = (long long)doubles;
+        info[5] = call == BDR_POINTS || call == BDR_EVAL ? (long long)nfq : (long long)doubles;
         info[7] = FL.touched;
     }
     // ---- the passes: ascending local face, so that the faces of one element are added in that order
-    F.inputs(coef, (size_t)NF);
-    DBuf<double> hold_g;
-    const double *dg = g ? device_view(hold_g, g, (size_t)m.NV * vdim, s) : nullptr;
-    F.target(out, (size_t)F.M.doubles, true);
+    F.inputs(coef, call == BDR_MASS && at_points ? nfq : (size_t)NF);
+    DBuf<double> hold_in;
+    DBuf<int> bad_det;
+    if (call == BDR_EVAL) {
+        bad_det.alloc(1);
+        SA_HIP_CHECK(hipMemsetAsync(bad_det.p, 0x7f, sizeof(int), s));
+    }
+    BdrLaunch B{FL.fe, nullptr, fp.p, nullptr, nullptr, nullptr, bad_det.p};
+    if (in) B.in = device_view(hold_in, in, call == BDR_LOADS && at_points ? nfq * vdim : (size_t)m.NV * vdim, s);
+    auto passes = [&] {
+        for (int lf = 0; lf < BDR_MAX_FACES; ++lf)
+            for (int t = 0; t < EM_TYPES; ++t)
+                if (count[t][lf]) bdr_launch_face(call, F.L, B, dim, vdim, t, lf, count[t][lf], list[t][lf].p);
+    };
+    auto refuse = [&] {
+        F.refuse_bad(NF, "face ", ": the measure is not positive");
+        if (call == BDR_EVAL) F.refuse_bad(NF, "face ", ": the Jacobian determinant of the element is not positive", bad_det.p);
+    };
     F.reset_bad();
-    for (int lf = 0; lf < BDR_MAX_FACES; ++lf)
-        for (int t = 0; t < EM_TYPES; ++t)
-            if (count[t][lf]) bdr_launch_face(F.L, FL.fe, dg, dim, vdim, t, lf, count[t][lf], list[t][lf].p);
-    F.refuse_bad(NF, "face ", ": the measure is not positive");
+    EmOut third;
+    bool write = true;
+    if (at_points) {      // nothing is written before every face has passed
+        passes();
+        refuse();
+        write = out_a || out_b || out_c;
+    }
+    if (call == BDR_MASS || call == BDR_LOADS) {
+        F.target(out_a, (size_t)F.M.doubles, true);
+    } else {
+        B.a = F.out[0].dev(s, out_a, nfq * (call == BDR_POINTS ? dim : vdim));
+        B.b = F.out[1].dev(s, out_b, call == BDR_POINTS ? nfq : nfq * vdim * dim);
+        B.c = third.dev(s, out_c, nfq * dim);
+    }
+    if (write) passes();
+    if (!at_points) refuse();
     F.copy_home();
+    third.finish(s);
+    if (fp_out) SA_HIP_CHECK(hipMemcpyAsync(fp_out, fp.p, ((size_t)NF + 1) * sizeof(roff_t), hipMemcpyDefault, s));
     F.sync();
 }
 // the checks of both entry points that need no device
@@ -1911,14 +2236,45 @@ void boundary_mass(hipStream_t s, const MeshArgs &m, int NF, const int *face_ele
     const std::string name("saamge_amd_boundary_mass: ");
     bdr_begin(name, m, NF, face_elem, face_local, vdim, info);
     SA_REQUIRE(NF == 0 || coef, name + "null argument: coef");
-    boundary_forms(s, name, m, NF, face_elem, face_local, vdim, coef, nullptr, elmat_inout, info);
+    boundary_forms(BDR_MASS, false, s, name, m, NF, face_elem, face_local, vdim, coef, nullptr, nullptr, elmat_inout, nullptr, nullptr,
+                   info);
 }
 void boundary_loads(hipStream_t s, const MeshArgs &m, int NF, const int *face_elem, const int *face_local, int vdim, const double *coef,
                     const double *g, double *elvec_inout, long long info[8]) {
     const std::string name("saamge_amd_boundary_loads: ");
     bdr_begin(name, m, NF, face_elem, face_local, vdim, info);
     SA_REQUIRE(g, name + "null argument: g");
-    boundary_forms(s, name, m, NF, face_elem, face_local, vdim, coef, g, elvec_inout, info);
+    boundary_forms(BDR_LOADS, false, s, name, m, NF, face_elem, face_local, vdim, coef, g, nullptr, elvec_inout, nullptr, nullptr, info);
+}
+
+void boundary_points(hipStream_t s, const MeshArgs &m, int NF, const int *face_elem, const int *face_local, long long *fp_ptr_out,
+                     double *xq_out, double *wmeas_out, double *normal_out, long long info[8]) {
+    const std::string name("saamge_amd_boundary_points: ");
+    bdr_begin(name, m, NF, face_elem, face_local, 1, info);
+    boundary_forms(BDR_POINTS, true, s, name, m, NF, face_elem, face_local, 1, nullptr, nullptr, fp_ptr_out, xq_out, wmeas_out,
+                   normal_out, info);
+}
+void boundary_eval(hipStream_t s, const MeshArgs &m, int NF, const int *face_elem, const int *face_local, int vdim, const double *u,
+                   double *uq_out, double *gradq_out, long long info[8]) {
+    const std::string name("saamge_amd_boundary_eval: ");
+    bdr_begin(name, m, NF, face_elem, face_local, vdim, info);
+    SA_REQUIRE(u, name + "null argument: u");
+    boundary_forms(BDR_EVAL, true, s, name, m, NF, face_elem, face_local, vdim, nullptr, u, nullptr, uq_out, gradq_out, nullptr, info);
+}
+void boundary_mass_points(hipStream_t s, const MeshArgs &m, int NF, const int *face_elem, const int *face_local, int vdim,
+                          const double *coefq, double *elmat_inout, long long info[8]) {
+    const std::string name("saamge_amd_boundary_mass_points: ");
+    bdr_begin(name, m, NF, face_elem, face_local, vdim, info);
+    SA_REQUIRE(NF == 0 || coefq, name + "null argument: coefq");
+    boundary_forms(BDR_MASS, true, s, name, m, NF, face_elem, face_local, vdim, coefq, nullptr, nullptr, elmat_inout, nullptr, nullptr,
+                   info);
+}
+void boundary_loads_points(hipStream_t s, const MeshArgs &m, int NF, const int *face_elem, const int *face_local, int vdim,
+                           const double *coef, const double *gq, double *elvec_inout, long long info[8]) {
+    const std::string name("saamge_amd_boundary_loads_points: ");
+    bdr_begin(name, m, NF, face_elem, face_local, vdim, info);
+    SA_REQUIRE(NF == 0 || gq, name + "null argument: gq");
+    boundary_forms(BDR_LOADS, true, s, name, m, NF, face_elem, face_local, vdim, coef, gq, nullptr, elvec_inout, nullptr, nullptr, info);
 }
 
 void element_points(hipStream_t s, const MeshArgs &m, long long *qp_ptr_out, double *xq_out, double *wdet_out, long long info[8]) {

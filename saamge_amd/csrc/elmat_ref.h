@@ -388,5 +388,103 @@ constexpr int mass_points_of(TagList<T...>, int dim, int nd) {
 }
 constexpr int mass_points(int dim, int nd) { return mass_points_of(ElemTypes{}, dim, nd); }
 constexpr bool em_order1(int dim, int nd) { return em_type_index(dim, nd) >= 0 && em_type_index(dim, nd) < 5; }
+// face_points: of the rule of the face type (dim, fn), 0: no such face type
+template <class... T>
+constexpr int face_points_of(TagList<T...>, int dim, int fn) {
+    int n = 0;
+    ((n = T::DIM == dim && T::ND == fn ? FaceRule<T::DIM, T::ND>::NQ : n), ...);
+    return n;
+}
+constexpr int face_points(int dim, int fn) { return face_points_of(FaceTypes{}, dim, fn); }
+// the dimension of the element type with this index, 0: no such type
+template <class... T>
+constexpr int elem_dim_of(TagList<T...>, int type) {
+    int i = 0, d = 0;
+    ((d = i++ == type ? T::DIM : d), ...);
+    return d;
+}
+constexpr int em_type_dim(int type) { return elem_dim_of(ElemTypes{}, type); }
+// the fork on the node count of a local face of an element type, written once: f(the constant FN).  The faces of a type have
+// one node count, except the wedge's (triangles first, then quadrilaterals)
+template <int DIM, int ND, class F>
+void with_face_nodes(ElemTag<DIM, ND>, int fn, F &&f) {
+    constexpr int T = em_type_index(DIM, ND), A = BDR_FACE_NODES[T][0], B = BDR_FACE_NODES[T][bdr_num_faces(T) - 1];
+    if (fn == A) f(std::integral_constant<int, A>{});
+    else if constexpr (B != A) {
+        if (fn == B) f(std::integral_constant<int, B>{});
+    }
+}
+
+// ---- the element's gradients at the face points (elmat_model.REF_NODES, face_ref_point, face_gradients) -----------------------------
+// the reference position of node a of the type, coordinate k
+template <int DIM, int ND>
+constexpr double ref_node(int a, int k) {
+    if constexpr (ND == DIM + 1) {                            // the vertices of the simplex
+        return a == k + 1 ? 1.0 : 0.0;
+    } else if constexpr (DIM == 2 && ND == 4) {
+        return EM_QUAD_LOC[a][k];
+    } else if constexpr (DIM == 3 && ND == 8) {
+        return EM_HEX_LOC[a][k];
+    } else if constexpr (DIM == 3 && ND == 6) {               // node a = 3 * layer + triangle vertex
+        return k == 2 ? a / 3 : (a % 3 == k + 1 ? 1.0 : 0.0);
+    } else if constexpr (DIM == 2 && ND == 9) {
+        return 0.5 * EM2_QUAD_LOC[a][k];
+    } else if constexpr (DIM == 3 && ND == 27) {
+        return 0.5 * (k == 0 ? a % 3 : (k == 1 ? (a / 3) % 3 : a / 9));
+    } else {                                                  // the order-2 simplices: the vertices, then the midpoints of the edges
+        if (a <= DIM) return a == k + 1 ? 1.0 : 0.0;
+        const int i = DIM == 2 ? EM_P2_TRI_EDGES[(a - DIM - 1) % 3][0] : EM_P2_TET_EDGES[(a - DIM - 1) % 6][0];
+        const int j = DIM == 2 ? EM_P2_TRI_EDGES[(a - DIM - 1) % 3][1] : EM_P2_TET_EDGES[(a - DIM - 1) % 6][1];
+        return 0.5 * ((i == k + 1 ? 1.0 : 0.0) + (j == k + 1 ? 1.0 : 0.0));
+    }
+}
+// xi, the reference position in the element <DIM, ND> of point q of a face F with the table `face`: the sum over the face nodes
+// c, ascending, of N_c(q) * ref_node(node c), the first product as it is, N from the face's own table (ref_table, the one builder)
+template <int DIM, int ND, int FN>
+constexpr void face_ref_point(const BdrTable<DIM, FN> &face, const BdrFace &F, int q, double (&xi)[DIM]) {
+    for (int k = 0; k < DIM; ++k) {
+        double v = face.N[q][0] * ref_node<DIM, ND>(F.node[0], k);
+        for (int c = 1; c < FN; ++c) v = v + face.N[q][c] * ref_node<DIM, ND>(F.node[c], k);
+        xi[k] = v;
+    }
+}
+// Per local face lf of the element type <DIM, ND> and per point q of the face's rule: dN[a][q][k], the gradients of ALL nodes of
+// the element at face_ref_point (ref_shape).  A face's block is node-major like RefTable::dN, the points MAXQ apart (the wedge's
+// triangles have 3 points, its quadrilaterals 4).
+template <int DIM, int ND>
+struct FaceGradTable {
+    static constexpr int TYPE = em_type_index(DIM, ND), NF = bdr_num_faces(TYPE);
+    static constexpr int MAXQ = face_points(DIM, BDR_FACE_NODES[TYPE][0]) > face_points(DIM, BDR_FACE_NODES[TYPE][NF - 1])
+                                    ? face_points(DIM, BDR_FACE_NODES[TYPE][0])
+                                    : face_points(DIM, BDR_FACE_NODES[TYPE][NF - 1]);
+    double dN[NF][ND][MAXQ][DIM];
+};
+template <int DIM, int ND, int FN>
+constexpr void face_grad_fill(FaceGradTable<DIM, ND> &t, int lf) {
+    if constexpr (tag_index(FaceTypes{}, DIM, FN) >= 0) {
+        const BdrTable<DIM, FN> face = bdr_table<DIM, FN>();
+        const BdrFace F = bdr_face(em_type_index(DIM, ND), lf);
+        for (int q = 0; q < BdrTable<DIM, FN>::NQ; ++q) {
+            double xi[DIM] = {};
+            face_ref_point<DIM, ND, FN>(face, F, q, xi);
+            const RefShape<DIM, ND> f = ref_shape<DIM, ND>(xi);
+            for (int a = 0; a < ND; ++a)
+                for (int k = 0; k < DIM; ++k) t.dN[lf][a][q][k] = f.dN[a][k];
+        }
+    }
+}
+template <int DIM, int ND>
+constexpr FaceGradTable<DIM, ND> face_grad_table() {
+    FaceGradTable<DIM, ND> t{};
+    for (int lf = 0; lf < t.NF; ++lf) {
+        const int fn = BDR_FACE_NODES[t.TYPE][lf];
+        if (fn == 2) face_grad_fill<DIM, ND, 2>(t, lf);
+        else if (fn == 3) face_grad_fill<DIM, ND, 3>(t, lf);
+        else if (fn == 4) face_grad_fill<DIM, ND, 4>(t, lf);
+        else if (fn == 6) face_grad_fill<DIM, ND, 6>(t, lf);
+        else face_grad_fill<DIM, ND, 9>(t, lf);
+    }
+    return t;
+}
 
 }  // namespace saamge_amd

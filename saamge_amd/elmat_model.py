@@ -52,6 +52,9 @@ are those of the scalar formulas).
                the mass rule in the place of the coefficient per element: defined at the end of this file.
   boundary    FACE_NODES, boundary_mass and boundary_loads: the face mass and the face loads of a list of (element, local face)
                pairs, added into the owning elements' matrices and vectors: defined at the end of this file.
+  face points  boundary_points, boundary_eval, boundary_mass_points and boundary_loads_points: the points of the listed faces with
+               weight * measure and the outward unit normal, the trace and the whole gradient of a nodal field there, the face mass
+               with a coefficient per point and the face loads of data given there: defined at the end of this file.
 """
 import numpy as np
 
@@ -138,37 +141,61 @@ def point_weight(dim, nd, q):
     return WEIGHT[(dim, nd)]
 
 
-def reference_gradients(dim, nd, q):
-    """dN[a][j] at point q of the type's rule, as Python floats."""
+def rule_point(dim, nd, q):
+    """the reference point q of the type's stiffness rule; None for the order-1 simplices, whose gradients are the same everywhere"""
     if (dim, nd) == (2, 9):
-        px, py = GAUSS3[q % 3], GAUSS3[q // 3]
+        return (GAUSS3[q % 3], GAUSS3[q // 3])
+    if (dim, nd) == (3, 27):
+        return (GAUSS3[q % 3], GAUSS3[(q // 3) % 3], GAUSS3[q // 9])
+    if (dim, nd) == (2, 6):
+        return WEDGE_TRI[q]
+    if (dim, nd) == (3, 10):
+        return TET_POINTS[q]
+    if (dim, nd) in ((2, 3), (3, 4)):
+        return None
+    if (dim, nd) == (2, 4):
+        return (GAUSS[q & 1], GAUSS[(q >> 1) & 1])
+    if (dim, nd) == (3, 8):
+        return (GAUSS[q & 1], GAUSS[(q >> 1) & 1], GAUSS[(q >> 2) & 1])
+    if (dim, nd) == (3, 6):
+        return WEDGE_TRI[q % 3] + (GAUSS[q // 3],)
+    raise ValueError("%d nodes: no supported element type in %dD" % (nd, dim))
+
+
+def gradients_at(dim, nd, pt):
+    """dN[a][j] of the type at the reference point pt, as Python floats: the one statement of every type's gradients (the rules'
+    tables and the tables at the face points are this function at their points)."""
+    if (dim, nd) == (2, 9):
+        px, py = pt
         return [(_d2(ix, px) * _n2(iy, py), _n2(ix, px) * _d2(iy, py)) for (ix, iy) in Q2_QUAD_LOC]
     if (dim, nd) == (3, 27):
-        px, py, pz = GAUSS3[q % 3], GAUSS3[(q // 3) % 3], GAUSS3[q // 9]
+        px, py, pz = pt
         return [(_d2(ix, px) * (_n2(iy, py) * _n2(iz, pz)), _d2(iy, py) * (_n2(ix, px) * _n2(iz, pz)),
                  _d2(iz, pz) * (_n2(ix, px) * _n2(iy, py))) for (ix, iy, iz) in Q2_HEX_LOC]
-    if (dim, nd) == (2, 6):
-        return _p2_simplex(2, WEDGE_TRI[q])[1]
-    if (dim, nd) == (3, 10):
-        return _p2_simplex(3, TET_POINTS[q])[1]
+    if (dim, nd) in P2_SIMPLEX:
+        return _p2_simplex(dim, pt)[1]
     if (dim, nd) == (2, 3):
         return [tuple(d) for d in TRI_D]
     if (dim, nd) == (3, 4):
         return [tuple(d) for d in TET_D]
     if (dim, nd) == (2, 4):
-        px, py = GAUSS[q & 1], GAUSS[(q >> 1) & 1]
+        px, py = pt
         return [(_df(lx) * _f(ly, py), _f(lx, px) * _df(ly)) for (lx, ly) in QUAD_LOC]
     if (dim, nd) == (3, 8):
-        px, py, pz = GAUSS[q & 1], GAUSS[(q >> 1) & 1], GAUSS[(q >> 2) & 1]
+        px, py, pz = pt
         return [(_df(lx) * (_f(ly, py) * _f(lz, pz)), _df(ly) * (_f(lx, px) * _f(lz, pz)), _df(lz) * (_f(lx, px) * _f(ly, py)))
                 for (lx, ly, lz) in HEX_LOC]
     if (dim, nd) == (3, 6):
-        xi, eta = WEDGE_TRI[q % 3]
-        zeta = GAUSS[q // 3]
+        xi, eta, zeta = pt
         T = ((1.0 - xi) - eta, xi, eta)
         L = (1.0 - zeta, zeta)
         return [(TRI_D[i][0] * L[a], TRI_D[i][1] * L[a], T[i] * _df(a)) for a in (0, 1) for i in (0, 1, 2)]
     raise ValueError("%d nodes: no supported element type in %dD" % (nd, dim))
+
+
+def reference_gradients(dim, nd, q):
+    """dN[a][j] at point q of the type's rule, as Python floats."""
+    return gradients_at(dim, nd, rule_point(dim, nd, q))
 
 
 def _cofactors(J, dim):
@@ -406,9 +433,9 @@ def mass_point_weight(dim, nd, q):
 def mass_reference_gradients(dim, nd, q):
     """dN[a][j] at point q of the type's MASS rule: the stiffness rule's, except for the order-2 simplices"""
     if (dim, nd) == (2, 6):
-        return _p2_simplex(2, P2_TRI_POINTS[q])[1]
+        return gradients_at(2, 6, P2_TRI_POINTS[q])
     if (dim, nd) == (3, 10):
-        return _p2_simplex(3, P2_TET_POINTS[q])[1]
+        return gradients_at(3, 10, P2_TET_POINTS[q])
     return reference_gradients(dim, nd, q)
 
 
@@ -659,13 +686,14 @@ def face_rule(dim, fn):
             for q in range(MASS_NPOINTS[(2, fn)])]
 
 
-def _face_points(X, dim, fn, c):
+def _face_points(X, dim, fn, c, rows=None, geom=False):
     """Per point of the face rule: (N, s) with s = (weight * meas) * c over the n faces of X (n, fn, dim), and per face whether
-    a measure was not positive."""
+    a measure was not positive.  rows (boundary_mass_points): c holds one coefficient per point, point q of face k takes
+    c[rows[k] + q].  geom (boundary_points): (N, s, normal) with the unit normal, its dim components each divided by meas."""
     bad = np.zeros(X.shape[0], bool)
     out = []
     with np.errstate(all="ignore"):
-        for N, dN, w in face_rule(dim, fn):
+        for q, (N, dN, w) in enumerate(face_rule(dim, fn)):
             t = [[None] * dim for _ in range(dim - 1)]
             for j in range(dim - 1):
                 for i in range(dim):
@@ -675,13 +703,16 @@ def _face_points(X, dim, fn, c):
                     t[j][i] = v
             if dim == 2:
                 m2 = t[0][0] * t[0][0] + t[0][1] * t[0][1]
+                nrm = (t[0][1], -t[0][0])
             else:
                 (ax, ay, az), (bx, by, bz) = t
                 n0, n1, n2 = ay * bz - az * by, az * bx - ax * bz, ax * by - ay * bx
                 m2 = (n0 * n0 + n1 * n1) + n2 * n2
+                nrm = (n0, n1, n2)
             meas = np.sqrt(m2)
             bad |= ~(meas > 0.0)
-            out.append((N, (w * meas) * c))
+            s = (w * meas) * (c if rows is None else c[rows + q])
+            out.append((N, s, np.stack([v / meas for v in nrm], axis=1)) if geom else (N, s))
     return out, bad
 
 
@@ -742,6 +773,12 @@ def boundary_mass(coords, elem_to_vertex, face_elem, face_local, coef, vdim=1, e
         raise ValueError("coef: (NF,) is needed")
     fe, fl = _face_list(dim, nd, face_elem, face_local)
     coef = _face_coef(coef, len(fe), True)
+    return _add_face_mass(X, dim, ep, e2v, nd, vdim, fe, fl, coef, None, add_to, elem_ptr is None)
+
+
+def _add_face_mass(X, dim, ep, e2v, nd, vdim, fe, fl, coef, fp, add_to, square):
+    """boundary_mass after its checks.  fp None: coef (NF,) per face; else (boundary_mass_points) coef (NFQ,) per point, point q
+    of face f at fp[f] + q."""
     if add_to is None:
         raise ValueError("add_to: the matrices the faces are added to are needed")
     moff = np.concatenate([[0], np.cumsum((nd * vdim) ** 2)])
@@ -753,7 +790,8 @@ def boundary_mass(coords, elem_to_vertex, face_elem, face_local, coef, vdim=1, e
         for lf, c, ids in _face_buckets(dim, nd, fe, fl):
             nodes = np.array(FACE_NODES[(dim, c)][lf])
             fn, S = len(nodes), c * vdim
-            points, bad[ids] = _face_points(X[e2v[ep[fe[ids]][:, None] + nodes]], dim, fn, coef[ids])
+            points, bad[ids] = _face_points(X[e2v[ep[fe[ids]][:, None] + nodes]], dim, fn, coef[ids] if fp is None else coef,
+                                            None if fp is None else fp[ids])
             pa, pb = np.triu_indices(fn)
             acc = np.zeros((len(ids), len(pa)))
             for N, s in points:
@@ -767,7 +805,7 @@ def boundary_mass(coords, elem_to_vertex, face_elem, face_local, coef, vdim=1, e
                     for idx in ([base + r * S + cc] if a == b else [base + r * S + cc, base + cc * S + r]):
                         out[idx] = out[idx] + acc[:, k]          # (an element occurs once in a bucket: no index twice)
     _refuse_measure(bad)
-    if elem_ptr is None:
+    if square:
         return out.reshape(len(nd), nd[0] * vdim, nd[0] * vdim) if len(nd) else out.reshape(0, 0, 0)
     return out
 
@@ -786,6 +824,12 @@ def boundary_loads(coords, elem_to_vertex, face_elem, face_local, g, vdim=1, coe
     G = G.reshape(NV, vdim)
     fe, fl = _face_list(dim, nd, face_elem, face_local)
     coef = _face_coef(coef, len(fe), False)
+    return _add_face_loads(X, dim, ep, e2v, nd, vdim, fe, fl, coef, G, None, add_to, elem_ptr is None)
+
+
+def _add_face_loads(X, dim, ep, e2v, nd, vdim, fe, fl, coef, G, fp, add_to, rows):
+    """boundary_loads after its checks.  fp None: G (NV, vdim) at the nodes; else (boundary_loads_points) G (NFQ, vdim) at the
+    points, point q of face f at fp[f] + q, read where the nodal data is interpolated."""
     if add_to is None:
         raise ValueError("add_to: the vectors the faces are added to are needed")
     out = np.array(add_to, np.float64).ravel()
@@ -798,19 +842,22 @@ def boundary_loads(coords, elem_to_vertex, face_elem, face_local, g, vdim=1, coe
             fn = len(nodes)
             v = e2v[ep[fe[ids]][:, None] + nodes]
             points, bad[ids] = _face_points(X[v], dim, fn, coef[ids])
-            F = G[v]                                                 # (n, fn, vdim)
+            F = G[v] if fp is None else None                         # (n, fn, vdim)
             acc = np.zeros((len(ids), fn, vdim))
-            for N, s in points:
-                gq = N[0] * F[:, 0, :]
-                for a in range(1, fn):
-                    gq = gq + N[a] * F[:, a, :]
+            for q, (N, s) in enumerate(points):
+                if fp is None:
+                    gq = N[0] * F[:, 0, :]
+                    for a in range(1, fn):
+                        gq = gq + N[a] * F[:, a, :]
+                else:
+                    gq = G[fp[ids] + q]
                 sg = s[:, None] * gq
                 term = sg[:, None, :] * np.array(N)[None, :, None]
                 acc = acc + term
             idx = (ep[fe[ids]] * vdim)[:, None, None] + (vdim * nodes)[None, :, None] + np.arange(vdim)[None, None, :]
             out[idx] = out[idx] + acc
     _refuse_measure(bad)
-    if elem_ptr is None:
+    if rows:
         return out.reshape(len(nd), nd[0] * vdim) if len(nd) else out.reshape(0, 0)
     return out
 
@@ -1081,3 +1128,154 @@ def element_mass_points(coords, elem_to_vertex, coefq, vdim=1, elem_ptr=None, ad
     if elem_ptr is None:
         return out.reshape(NE, nd[0] * vdim, nd[0] * vdim) if NE else out.reshape(0, 0, 0)
     return out
+
+
+# ---- boundary data at the face points: the points and the normals, traces, the Robin and Neumann terms of point data ------------------
+#   points       the points of face f of the list are those of its face type's rule (face_rule), in the rule's order; point q of
+#                face f has the global index fp_ptr[f] + q, fp_ptr (NF + 1,) int64, NFQ = fp_ptr[NF]: the index follows the LIST, not
+#                the buckets the faces are worked in, so a permuted list permutes the point arrays by whole faces.
+#                xq[q][i] = sum over the face nodes c, ascending, of N_c * x_c[i], the first product as it is; wmeas[q] = w_q * meas_q:
+#                the bits of s of _face_points with the coefficient 1.0; normal[q] = (n0, n1, n2) / meas with n = t_0 x t_1 of
+#                _face_points in 3D, (t_y, -t_x) / meas in 2D, the division last: the unit normal that points out of the owning
+#                element (FACE_NODES orders every face of every type so; tests/test_bdr_points_model.py holds it to that).
+#   eval         u nodal (NV, vdim).  uq[q][i] = sum over the FACE nodes, ascending, of N_c * u_c[i]: gq of boundary_loads.  gradq is
+#                the whole gradient of the ELEMENT's field at the face point: the reference position of the point in the element is
+#                xi[k] = sum over the face nodes c, ascending, of N_c * REF_NODES[node c][k], the first product as it is
+#                (face_ref_point); dN_a = gradients_at(xi) of ALL nodes of the element (face_gradients); J[i][j] = sum over the nodes,
+#                ascending, of x_a[i] * dN_a[j]; _cofactors; then everything is _eval_point's: r[i][k], (sum_k r[i][k] C[j][k]) / det.
+#   mass         boundary_mass with s = (w * meas) * coefq[fp_ptr[f] + q]; coefq (NFQ,).
+#   loads        gq (NFQ, vdim) at the points: face dof (a, i) gets the sum over the points, ascending from 0.0, of
+#                (s * gq[q][i]) * N_a, s = (w * meas) * coef_f (coef None: 1.0); added as boundary_loads adds.
+#   refused      vdim; missing face lists, u, coefq, gq; what _mesh refuses; what _face_list refuses; data of the wrong size; the
+#                first face with a non-positive measure; for eval, then the first face (lowest index of the list) with a point
+#                where the element's determinant is not positive -- whether or not the gradient is asked for (FaceError, .face).
+def _ref_nodes():
+    tri, tet = [(0.0, 0.0), (1.0, 0.0), (0.0, 1.0)], [(0.0, 0.0, 0.0), (1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0)]
+    out = {(2, 3): tri, (3, 4): tet,
+           (2, 4): [(float(x), float(y)) for (x, y) in QUAD_LOC],
+           (3, 8): [(float(x), float(y), float(z)) for (x, y, z) in HEX_LOC],
+           (3, 6): [(x, y, float(a)) for a in (0, 1) for (x, y) in tri],
+           (2, 9): [(0.5 * x, 0.5 * y) for (x, y) in Q2_QUAD_LOC],
+           (3, 27): [(0.5 * x, 0.5 * y, 0.5 * z) for (x, y, z) in Q2_HEX_LOC]}
+    for (dim, nd), V in (((2, 6), tri), ((3, 10), tet)):
+        out[(dim, nd)] = V + [tuple(0.5 * (V[i][k] + V[j][k]) for k in range(dim)) for (i, j) in P2_EDGES[dim]]
+    return out
+
+
+REF_NODES = _ref_nodes()                     # the reference position of every node of every type (exact doubles)
+FACE_NPOINTS = {k: len(face_rule(*k)) for k in FACE_TYPE_INDEX}
+
+
+def face_ref_point(dim, nd, lf, q):
+    """the reference position, in the element (dim, nd), of point q of its local face lf"""
+    nodes = FACE_NODES[(dim, nd)][lf]
+    N, R = face_rule(dim, len(nodes))[q][0], REF_NODES[(dim, nd)]
+    xi = []
+    for k in range(dim):
+        t = N[0] * R[nodes[0]][k]
+        for c in range(1, len(nodes)):
+            t = t + N[c] * R[nodes[c]][k]
+        xi.append(t)
+    return tuple(xi)
+
+
+def face_gradients(dim, nd, lf, q):
+    """dN[a][k] of all nd nodes of the element type at point q of its local face lf, as Python floats"""
+    return gradients_at(dim, nd, face_ref_point(dim, nd, lf, q))
+
+
+def _face_mesh(coords, elem_to_vertex, elem_ptr, vdim, face_elem, face_local, needed=()):
+    """The checks the four calls share, in their order; needed: (array, what) pairs that must not be None.  Returns the mesh, the
+    checked face list and fp_ptr."""
+    shape = np.shape(coords)
+    if len(shape) == 2 and shape[1] in (2, 3):
+        _vdim(vdim, shape[1])                                        # (refused before the mesh is looked at)
+    if face_elem is None or face_local is None:
+        raise ValueError("face_elem and face_local: (NF,) are needed")
+    for a, what in needed:
+        if a is None:
+            raise ValueError("%s is needed" % what)
+    X, dim, ep, e2v, nd = _mesh(coords, elem_to_vertex, elem_ptr)
+    vdim = _vdim(vdim, dim)
+    fe, fl = _face_list(dim, nd, face_elem, face_local)
+    npts = np.array([FACE_NPOINTS[(dim, len(FACE_NODES[(dim, int(nd[e]))][l]))] for e, l in zip(fe, fl)], np.int64)
+    fp = np.concatenate([[0], np.cumsum(npts)]).astype(np.int64)
+    return X, dim, ep, e2v, nd, vdim, fe, fl, fp
+
+
+def _refuse_face_det(bad):
+    if bad.any():
+        raise FaceError(int(np.flatnonzero(bad)[0]), "the Jacobian determinant of the element is not positive")
+
+
+def boundary_points(coords, elem_to_vertex, face_elem, face_local, elem_ptr=None):
+    """(fp_ptr (NF + 1,) int64, xq (NFQ, dim), wmeas (NFQ,), normal (NFQ, dim)): the points of the face rule of every listed face,
+    weight * measure there and the unit normal that points out of the owning element."""
+    X, dim, ep, e2v, nd, _, fe, fl, fp = _face_mesh(coords, elem_to_vertex, elem_ptr, 1, face_elem, face_local)
+    NFQ = int(fp[-1])
+    xq, wmeas, normal = np.zeros((NFQ, dim)), np.zeros(NFQ), np.zeros((NFQ, dim))
+    bad = np.zeros(len(fe), bool)
+    with np.errstate(all="ignore"):
+        for lf, c, ids in _face_buckets(dim, nd, fe, fl):
+            nodes = np.array(FACE_NODES[(dim, c)][lf])
+            Xf = X[e2v[ep[fe[ids]][:, None] + nodes]]
+            points, bad[ids] = _face_points(Xf, dim, len(nodes), 1.0, geom=True)
+            for q, (N, s, n) in enumerate(points):
+                xq[fp[ids] + q] = _eval_point(N, None, None, None, Xf, dim, False)[0]
+                wmeas[fp[ids] + q] = s
+                normal[fp[ids] + q] = n
+    _refuse_measure(bad)
+    return fp, xq, wmeas, normal
+
+
+def boundary_eval(coords, elem_to_vertex, face_elem, face_local, u, vdim=1, elem_ptr=None, grad=True):
+    """(uq (NFQ, vdim), gradq (NFQ, vdim, dim)) of the nodal field u (NV, vdim) or (NV,) at the face points: the trace through the
+    face's shape functions and the whole gradient of the owning element's field; grad=False: gradq is None (the determinants are
+    checked all the same)."""
+    X, dim, ep, e2v, nd, vdim, fe, fl, fp = _face_mesh(coords, elem_to_vertex, elem_ptr, vdim, face_elem, face_local,
+                                                       [(u, "u: (NV, vdim)")])
+    U = _point_data(u, (X.shape[0], vdim), "u: (NV, vdim)")
+    NFQ = int(fp[-1])
+    uq, gq = np.zeros((NFQ, vdim)), np.zeros((NFQ, vdim, dim)) if grad else None
+    bad, bad_det = np.zeros(len(fe), bool), np.zeros(len(fe), bool)
+    with np.errstate(all="ignore"):
+        for lf, c, ids in _face_buckets(dim, nd, fe, fl):
+            nodes = np.array(FACE_NODES[(dim, c)][lf])
+            v = e2v[ep[fe[ids]][:, None] + nodes]
+            ve = e2v[ep[fe[ids]][:, None] + np.arange(c)]
+            points, bad[ids] = _face_points(X[v], dim, len(nodes), 1.0)
+            Xe, Ue, Uf = X[ve], U[ve], U[v]
+            for q, (N, _) in enumerate(points):
+                uq[fp[ids] + q] = _eval_point(N, None, None, None, Uf, dim, False)[0]
+                dN = face_gradients(dim, c, lf, q)
+                J = [[None] * dim for _ in range(dim)]
+                for i in range(dim):
+                    for j in range(dim):
+                        t = Xe[:, 0, i] * dN[0][j]
+                        for a in range(1, c):
+                            t = t + Xe[:, a, i] * dN[a][j]
+                        J[i][j] = t
+                C, det = _cofactors(J, dim)
+                bad_det[ids] |= ~(det > 0.0)
+                if grad:
+                    gq[fp[ids] + q] = _eval_point([0.0] * c, dN, C, det, Ue, dim, True)[1]
+    _refuse_measure(bad)
+    _refuse_face_det(bad_det)
+    return uq, gq
+
+
+def boundary_mass_points(coords, elem_to_vertex, face_elem, face_local, coefq, vdim=1, elem_ptr=None, add_to=None):
+    """boundary_mass with the coefficient coefq (NFQ,) given at the face points of boundary_points."""
+    X, dim, ep, e2v, nd, vdim, fe, fl, fp = _face_mesh(coords, elem_to_vertex, elem_ptr, vdim, face_elem, face_local,
+                                                       [(coefq, "coefq: (NFQ,)")])
+    coefq = _point_data(coefq, (int(fp[-1]),), "coefq: (NFQ,)")
+    return _add_face_mass(X, dim, ep, e2v, nd, vdim, fe, fl, coefq, fp, add_to, elem_ptr is None)
+
+
+def boundary_loads_points(coords, elem_to_vertex, face_elem, face_local, gq, vdim=1, coef=None, elem_ptr=None, add_to=None):
+    """boundary_loads of data given AT THE FACE POINTS of boundary_points, gq (NFQ, vdim) or (NFQ,); coef (NF,) or None (1.0)."""
+    X, dim, ep, e2v, nd, vdim, fe, fl, fp = _face_mesh(coords, elem_to_vertex, elem_ptr, vdim, face_elem, face_local,
+                                                       [(gq, "gq: (NFQ, vdim)")])
+    G = _point_data(gq, (int(fp[-1]), vdim), "gq: (NFQ, vdim)")
+    coef = _face_coef(coef, len(fe), False)
+    return _add_face_loads(X, dim, ep, e2v, nd, vdim, fe, fl, coef, G, fp, add_to, elem_ptr is None)

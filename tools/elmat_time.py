@@ -8,6 +8,7 @@ warm-up, `--reps` repetitions (all listed).  One JSON line per case.
     python tools/elmat_time.py [--hex 128,256] [--elasticity 64] [--q2-hex 64,128] [--q2-elasticity 32,64] [--quad9 2048]
                                [--reps 3] [--host-reps 3] [--hbm-gbs 8000] [--fp64-gops 39300] [--no-host] [--no-mass]
                                [--rhs 256] [--boundary] [--p2-simplex] [--p2-tet 64] [--p2-tri 2048] [--points] [--point-coef]
+                               [--boundary-points]
 
 Beside every stiffness case, on the same mesh and in the same run (--no-mass: not): the mass matrices of the same layout
 (saamge_amd_element_mass; vdim 1 beside diffusion, dim beside elasticity), written (`<case>:mass`) and added to the stiffness
@@ -40,6 +41,14 @@ must move (coordinates, vertex lists and coefficients read once, the matrices wr
 accumulate), `hbm_bound_ms` that at --hbm-gbs, `expected_extra_ms` the coefficient bytes the new call reads beyond its
 yardstick at that rate, `ratio` new / yardstick (best of the repetitions) and `point_ratio` the points of the mass rule over the
 points of the yardstick's rule.
+
+--boundary-points: only the boundary data at the face points (saamge_amd_boundary_points, _eval with and without the gradient,
+_mass_points, _loads_points; vdim 1) on ALL boundary faces of Q1 hexes 128^3, Q2 hexes 64^3 and the 10-node tetrahedra of the 64^3
+split, same protocol; `bound_bytes` is what the call must move (face lists and offsets, the coordinates and ids of the nodes it
+reads, point data read once, outputs written once, matrices and vectors read and written) and `hbm_bound_ms` that at --hbm-gbs;
+beside the two forms, in the same run, the per-face call of --boundary they parallel (`per_face_call_ms`, `ratio`).  The calls
+run a host clock round many small launches (one list and one or two passes per local face): the time is the call's, not a kernel's,
+and that of points and eval covers the two library calls their Python wrappers make (a checks-only call for NFQ, then the call).
 
 The vertices are jittered by 0.2 mesh widths, so no two elements are alike.  A case that does not fit is reported as skipped
 with the error.
@@ -82,6 +91,7 @@ def main():
     ap.add_argument("--p2-simplex", action="store_true")
     ap.add_argument("--points", action="store_true")
     ap.add_argument("--point-coef", action="store_true")
+    ap.add_argument("--boundary-points", action="store_true")
     ap.add_argument("--p2-tet", type=int, default=64)
     ap.add_argument("--p2-tri", type=int, default=2048)
     a = ap.parse_args()
@@ -350,6 +360,67 @@ def main():
             except (RuntimeError, MemoryError) as e:
                 print(json.dumps({"case": "point_coef:" + name, "skipped": str(e)[:200]}), flush=True)
             X = e2v = kq = lq = sq = ke = le = se = out = o1 = None
+            torch.cuda.empty_cache()
+            capi.release_cached_memory()
+        return
+
+    if a.boundary_points:
+        def reps(call):
+            timed(call)                            # warm-up
+            return [round(timed(call)[0], 3) for _ in range(a.reps)]
+        for name, n, nd in [("hex128", 128, 8), ("q2_hex64", 64, 27), ("tet10_64", 64, 10)]:
+            try:
+                if nd == 10:
+                    X, e2v, g, P = mesh_p2(n, 3)
+                    fe, fl = simplex_boundary(P, n, 3)
+                    P = None
+                else:
+                    X, e2v, g = mesh(n) if nd == 8 else mesh_q2(n, 3)
+                    fe, fl = grid_boundary(n, 3)
+                NE, NF = int(e2v.shape[0]), int(fe.numel())
+                info = capi.boundary_points(X, e2v, fe, fl, sizes_only=True)
+                NFQ, fn = info[5], {8: 4, 27: 9, 10: 6}[nd]
+                alpha = 0.5 + 1.5 * torch.rand(NF, generator=g, device=dev, dtype=torch.float64)
+                alphaq = 0.5 + 1.5 * torch.rand(NFQ, generator=g, device=dev, dtype=torch.float64)
+                u = torch.rand(X.shape[0], generator=g, device=dev, dtype=torch.float64)
+                gq = torch.rand(NFQ, generator=g, device=dev, dtype=torch.float64)
+                out = torch.zeros(NE * nd * nd, dtype=torch.float64, device=dev)
+                vec = torch.zeros(NE * nd, dtype=torch.float64, device=dev)
+                pts = {"fp_ptr": torch.zeros(NF + 1, dtype=torch.int64, device=dev), "xq": torch.zeros(NFQ * 3, dtype=torch.float64, device=dev),
+                       "wmeas": torch.zeros(NFQ, dtype=torch.float64, device=dev), "normal": torch.zeros(NFQ * 3, dtype=torch.float64, device=dev)}
+                ev = {"uq": torch.zeros(NFQ, dtype=torch.float64, device=dev), "gradq": torch.zeros(NFQ * 3, dtype=torch.float64, device=dev)}
+                st = stream
+                # what a call must move: the face lists and the offsets (4 + 4 + 8 bytes per face), the coordinates of the nodes
+                # it reads and their vertex ids (the face's nodes; eval with the gradient: all nodes of the owning element, with
+                # u), point inputs read once, outputs written once (the matrices and vectors: read and written)
+                lists, face_nodes, elem_nodes = 16 * NF, NF * fn * (24 + 4), NF * nd * (24 + 8 + 4)
+                calls = [
+                    ("points", lists + face_nodes + 8 * NFQ * 7 + 8 * NF, None,
+                     lambda: capi.boundary_points(X, e2v, fe, fl, out=pts, stream=st())),
+                    ("eval", lists + face_nodes + NF * fn * 8 + elem_nodes + 8 * NFQ * 4, None,
+                     lambda: capi.boundary_eval(X, e2v, fe, fl, u, out=ev, stream=st())),
+                    ("eval_trace_only", lists + face_nodes + NF * fn * 8 + 8 * NFQ, None,
+                     lambda: capi.boundary_eval(X, e2v, fe, fl, u, want=("uq",), out={"uq": ev["uq"]}, stream=st())),
+                    ("mass_points", lists + face_nodes + 8 * NFQ + 16 * NF * fn * fn,
+                     lambda: capi.boundary_mass(X, e2v, fe, fl, alpha, add_to=out, stream=st()),
+                     lambda: capi.boundary_mass_points(X, e2v, fe, fl, alphaq, add_to=out, stream=st())),
+                    ("loads_points", lists + face_nodes + 8 * NF + 8 * NFQ + 16 * NF * fn,
+                     lambda: capi.boundary_loads(X, e2v, fe, fl, u, coef=alpha, add_to=vec, stream=st()),
+                     lambda: capi.boundary_loads_points(X, e2v, fe, fl, gq, coef=alpha, add_to=vec, stream=st())),
+                ]
+                for tag, nbytes, old, new in calls:
+                    t = reps(new)
+                    b_ms = 1e3 * nbytes / (a.hbm_gbs * 1e9)
+                    rec = {"case": "boundary_points:%s:%s" % (name, tag), "elements": NE, "faces": NF, "face_points": NFQ,
+                           "device_ms": t, "bound_bytes": int(nbytes), "hbm_bound_ms": round(b_ms, 5),
+                           "fraction_of_bound": round(b_ms / min(t), 5)}
+                    if old:
+                        rec["per_face_call_ms"] = reps(old)
+                        rec["ratio"] = round(min(t) / min(rec["per_face_call_ms"]), 3)
+                    print(json.dumps(rec), flush=True)
+            except (RuntimeError, MemoryError) as e:
+                print(json.dumps({"case": "boundary_points:" + name, "skipped": str(e)[:200]}), flush=True)
+            X = e2v = fe = fl = alpha = alphaq = u = gq = out = vec = pts = ev = None
             torch.cuda.empty_cache()
             capi.release_cached_memory()
         return
