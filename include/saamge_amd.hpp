@@ -15,6 +15,7 @@
 #ifndef SAAMGE_AMD_HPP
 #define SAAMGE_AMD_HPP
 
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -195,6 +196,9 @@ struct MeshPartitions {
     }
 };
 namespace detail {
+// owner of a handle of the C interface: the library's free function runs when the owner dies, and the handle moves with it
+template <class H>
+using Handle = std::unique_ptr<H, void (*)(H *)>;
 // copies the levels of P to the host and frees P
 inline MeshPartitions take_partitions(saamge_amd_partitioning *P, int levels) {
     MeshPartitions out;
@@ -526,44 +530,42 @@ class AssembledOperator {
 public:
     AssembledOperator(int n, int NE, int nde, const int *elem_ptr, const int *elem_to_dof, const double *elmat,
                       const signed char *bdr_dofs, void *stream = nullptr)
-        : op_(nullptr), n_(n), nnz_(0), rowptr_(nullptr), col_(nullptr), val_(nullptr) {
-        if (saamge_amd_operator_assemble(n, NE, nde, elem_ptr, elem_to_dof, elmat, bdr_dofs, stream, &op_))
+        : op_(nullptr, saamge_amd_operator_free), n_(n), nnz_(0), rowptr_(nullptr), col_(nullptr), val_(nullptr) {
+        saamge_amd_operator *op = nullptr;
+        if (saamge_amd_operator_assemble(n, NE, nde, elem_ptr, elem_to_dof, elmat, bdr_dofs, stream, &op))
             throw std::runtime_error(saamge_amd_last_error());
-        if (saamge_amd_operator_arrays(op_, &rowptr_, &col_, &val_, &nnz_)) {
-            saamge_amd_operator_free(op_);
-            throw std::runtime_error(saamge_amd_last_error());
-        }
+        op_.reset(op);
+        if (saamge_amd_operator_arrays(op, &rowptr_, &col_, &val_, &nnz_)) throw std::runtime_error(saamge_amd_last_error());
     }
-    ~AssembledOperator() { saamge_amd_operator_free(op_); }
+    AssembledOperator(AssembledOperator &&) = default;
+    AssembledOperator &operator=(AssembledOperator &&) = default;
     int rows() const { return n_; }
     long long nnz() const { return nnz_; }
     const long long *rowptr() const { return rowptr_; }
     const int *col() const { return col_; }
     const double *val() const { return val_; }
-    saamge_amd_operator *handle() const { return op_; }
+    saamge_amd_operator *handle() const { return op_.get(); }
     // host copies
     void get(std::vector<long long> &rowptr, std::vector<int> &col, std::vector<double> &val) const {
         rowptr.assign((size_t)n_ + 1, 0);
         col.assign((size_t)nnz_, 0);
         val.assign((size_t)nnz_, 0.0);
-        if (saamge_amd_operator_get(op_, rowptr.data(), col.data(), val.data(), nullptr)) throw std::runtime_error(saamge_amd_last_error());
+        if (saamge_amd_operator_get(op_.get(), rowptr.data(), col.data(), val.data(), nullptr)) throw std::runtime_error(saamge_amd_last_error());
     }
     // new element matrices, same mesh: val() rewritten in place (then adapt_update_operators(h, nullptr))
     void update(const double *elmat) {
-        if (saamge_amd_operator_update(op_, elmat)) throw std::runtime_error(saamge_amd_last_error());
+        if (saamge_amd_operator_update(op_.get(), elmat)) throw std::runtime_error(saamge_amd_last_error());
     }
     void eliminate_rhs(const double *elmat, const double *x_ess, double *b) const {
-        if (saamge_amd_operator_eliminate_rhs(op_, elmat, x_ess, b)) throw std::runtime_error(saamge_amd_last_error());
+        if (saamge_amd_operator_eliminate_rhs(op_.get(), elmat, x_ess, b)) throw std::runtime_error(saamge_amd_last_error());
     }
     // b (n, overwritten) from the packed element vectors of element_loads_into on the operator's mesh
     void assemble_rhs(const double *elvec, double *b) const {
-        if (saamge_amd_operator_assemble_rhs(op_, elvec, b)) throw std::runtime_error(saamge_amd_last_error());
+        if (saamge_amd_operator_assemble_rhs(op_.get(), elvec, b)) throw std::runtime_error(saamge_amd_last_error());
     }
 
 private:
-    AssembledOperator(const AssembledOperator &);
-    AssembledOperator &operator=(const AssembledOperator &);
-    saamge_amd_operator *op_;
+    detail::Handle<saamge_amd_operator> op_;
     int n_;
     long long nnz_;
     const long long *rowptr_;
@@ -582,36 +584,20 @@ struct FaceTableInfo {
 class FaceTable {
 public:
     FaceTable(int NV, int dim, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex, void *stream = nullptr)
-        : t_(nullptr), NE_(NE), NB_(0), nnz_(0), info_(), slot_ptr_(nullptr), xadj_(nullptr), nbr_elem_(nullptr), nbr_local_(nullptr),
-          bdr_elem_(nullptr), bdr_local_(nullptr), adj_(nullptr) {
+        : t_(nullptr, saamge_amd_face_table_free), NE_(NE), NB_(0), nnz_(0), info_(), slot_ptr_(nullptr), xadj_(nullptr),
+          nbr_elem_(nullptr), nbr_local_(nullptr), bdr_elem_(nullptr), bdr_local_(nullptr), adj_(nullptr) {
         long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (saamge_amd_face_table_build(NV, dim, NE, nde, elem_ptr, elem_to_vertex, stream, &t_, info))
+        saamge_amd_face_table *t = nullptr;
+        if (saamge_amd_face_table_build(NV, dim, NE, nde, elem_ptr, elem_to_vertex, stream, &t, info))
             throw std::runtime_error(saamge_amd_last_error());
+        t_.reset(t);
         const FaceTableInfo r = {info[0], info[1], info[2], info[3], info[4], info[5], info[6], info[7]};
         info_ = r;
-        if (saamge_amd_face_table_arrays(t_, &slot_ptr_, &nbr_elem_, &nbr_local_, &NB_, &bdr_elem_, &bdr_local_, &xadj_, &adj_, &nnz_)) {
-            saamge_amd_face_table_free(t_);
+        if (saamge_amd_face_table_arrays(t, &slot_ptr_, &nbr_elem_, &nbr_local_, &NB_, &bdr_elem_, &bdr_local_, &xadj_, &adj_, &nnz_))
             throw std::runtime_error(saamge_amd_last_error());
-        }
     }
-    FaceTable(FaceTable &&o) noexcept
-        : t_(o.t_), NE_(o.NE_), NB_(o.NB_), nnz_(o.nnz_), info_(o.info_), slot_ptr_(o.slot_ptr_), xadj_(o.xadj_),
-          nbr_elem_(o.nbr_elem_), nbr_local_(o.nbr_local_), bdr_elem_(o.bdr_elem_), bdr_local_(o.bdr_local_), adj_(o.adj_) {
-        o.t_ = nullptr;
-    }
-    FaceTable &operator=(FaceTable &&o) noexcept {
-        if (this != &o) {
-            saamge_amd_face_table_free(t_);
-            t_ = o.t_; NE_ = o.NE_; NB_ = o.NB_; nnz_ = o.nnz_; info_ = o.info_;
-            slot_ptr_ = o.slot_ptr_; xadj_ = o.xadj_; nbr_elem_ = o.nbr_elem_; nbr_local_ = o.nbr_local_;
-            bdr_elem_ = o.bdr_elem_; bdr_local_ = o.bdr_local_; adj_ = o.adj_;
-            o.t_ = nullptr;
-        }
-        return *this;
-    }
-    FaceTable(const FaceTable &) = delete;
-    FaceTable &operator=(const FaceTable &) = delete;
-    ~FaceTable() { saamge_amd_face_table_free(t_); }
+    FaceTable(FaceTable &&) = default;
+    FaceTable &operator=(FaceTable &&) = default;
     int elements() const { return NE_; }
     long long slots() const { return info_.slots; }
     long long boundary_faces() const { return NB_; }
@@ -624,7 +610,7 @@ public:
     const int *bdr_local() const { return bdr_local_; }
     const long long *xadj() const { return xadj_; }
     const int *adj() const { return adj_; }
-    saamge_amd_face_table *handle() const { return t_; }
+    saamge_amd_face_table *handle() const { return t_.get(); }
     // host copies
     void get(std::vector<long long> &slot_ptr, std::vector<int> &nbr_elem, std::vector<int> &nbr_local, std::vector<int> &bdr_elem,
              std::vector<int> &bdr_local, std::vector<long long> &xadj, std::vector<int> &adj) const {
@@ -635,13 +621,13 @@ public:
         bdr_elem.assign((size_t)NB_, 0);
         bdr_local.assign((size_t)NB_, 0);
         adj.assign((size_t)nnz_, 0);
-        if (saamge_amd_face_table_get(t_, slot_ptr.data(), nbr_elem.data(), nbr_local.data(), nullptr, bdr_elem.data(),
+        if (saamge_amd_face_table_get(t_.get(), slot_ptr.data(), nbr_elem.data(), nbr_local.data(), nullptr, bdr_elem.data(),
                                       bdr_local.data(), xadj.data(), adj.data(), nullptr))
             throw std::runtime_error(saamge_amd_last_error());
     }
 
 private:
-    saamge_amd_face_table *t_;
+    detail::Handle<saamge_amd_face_table> t_;
     int NE_;
     long long NB_, nnz_;
     FaceTableInfo info_;
@@ -659,37 +645,21 @@ class MeshLift {
 public:
     MeshLift(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex,
              const FaceTable *faces = nullptr, void *stream = nullptr)
-        : m_(nullptr), NV_(NV), NE_(NE), dim_(dim), NV2_(0), info_(), coords2_(nullptr), elem_ptr2_(nullptr), elem_to_node_(nullptr),
-          edge_hi_(nullptr), edge_ptr_(nullptr), face_slot_(nullptr) {
+        : m_(nullptr, saamge_amd_mesh_lift_free), NV_(NV), NE_(NE), dim_(dim), NV2_(0), info_(), coords2_(nullptr),
+          elem_ptr2_(nullptr), elem_to_node_(nullptr), edge_hi_(nullptr), edge_ptr_(nullptr), face_slot_(nullptr) {
         long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        saamge_amd_mesh_lift *m = nullptr;
         if (saamge_amd_mesh_lift_order2(NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, faces ? faces->handle() : nullptr, stream,
-                                        &m_, info))
+                                        &m, info))
             throw std::runtime_error(saamge_amd_last_error());
+        m_.reset(m);
         const MeshLiftInfo r = {info[0], info[1], info[2], info[3], info[4], info[5], info[6], info[7]};
         info_ = r;
-        if (saamge_amd_mesh_lift_arrays(m_, &NV2_, &coords2_, &elem_ptr2_, &elem_to_node_, &edge_ptr_, &edge_hi_, &face_slot_)) {
-            saamge_amd_mesh_lift_free(m_);
+        if (saamge_amd_mesh_lift_arrays(m, &NV2_, &coords2_, &elem_ptr2_, &elem_to_node_, &edge_ptr_, &edge_hi_, &face_slot_))
             throw std::runtime_error(saamge_amd_last_error());
-        }
     }
-    MeshLift(MeshLift &&o) noexcept
-        : m_(o.m_), NV_(o.NV_), NE_(o.NE_), dim_(o.dim_), NV2_(o.NV2_), info_(o.info_), coords2_(o.coords2_), elem_ptr2_(o.elem_ptr2_),
-          elem_to_node_(o.elem_to_node_), edge_hi_(o.edge_hi_), edge_ptr_(o.edge_ptr_), face_slot_(o.face_slot_) {
-        o.m_ = nullptr;
-    }
-    MeshLift &operator=(MeshLift &&o) noexcept {
-        if (this != &o) {
-            saamge_amd_mesh_lift_free(m_);
-            m_ = o.m_; NV_ = o.NV_; NE_ = o.NE_; dim_ = o.dim_; NV2_ = o.NV2_; info_ = o.info_;
-            coords2_ = o.coords2_; elem_ptr2_ = o.elem_ptr2_; elem_to_node_ = o.elem_to_node_; edge_hi_ = o.edge_hi_;
-            edge_ptr_ = o.edge_ptr_; face_slot_ = o.face_slot_;
-            o.m_ = nullptr;
-        }
-        return *this;
-    }
-    MeshLift(const MeshLift &) = delete;
-    MeshLift &operator=(const MeshLift &) = delete;
-    ~MeshLift() { saamge_amd_mesh_lift_free(m_); }
+    MeshLift(MeshLift &&) = default;
+    MeshLift &operator=(MeshLift &&) = default;
     int elements() const { return NE_; }
     int nodes() const { return NV2_; }
     const MeshLiftInfo &info() const { return info_; }
@@ -699,7 +669,7 @@ public:
     const long long *edge_ptr() const { return edge_ptr_; }
     const int *edge_hi() const { return edge_hi_; }
     const long long *face_slot() const { return face_slot_; }
-    saamge_amd_mesh_lift *handle() const { return m_; }
+    saamge_amd_mesh_lift *handle() const { return m_.get(); }
     // host copies; coords2 stays empty where the lift was made without coordinates
     void get(std::vector<double> &coords2, std::vector<int> &elem_ptr2, std::vector<int> &elem_to_node, std::vector<long long> &edge_ptr,
              std::vector<int> &edge_hi, std::vector<long long> &face_slot) const {
@@ -709,13 +679,13 @@ public:
         edge_ptr.assign((size_t)NV_ + 1, 0);
         edge_hi.assign((size_t)info_.edges, 0);
         face_slot.assign((size_t)info_.face_nodes, 0);
-        if (saamge_amd_mesh_lift_get(m_, nullptr, coords2.data(), elem_ptr2.data(), elem_to_node.data(), edge_ptr.data(), edge_hi.data(),
+        if (saamge_amd_mesh_lift_get(m_.get(), nullptr, coords2.data(), elem_ptr2.data(), elem_to_node.data(), edge_ptr.data(), edge_hi.data(),
                                      face_slot.data()))
             throw std::runtime_error(saamge_amd_last_error());
     }
 
 private:
-    saamge_amd_mesh_lift *m_;
+    detail::Handle<saamge_amd_mesh_lift> m_;
     int NV_, NE_, dim_, NV2_;
     MeshLiftInfo info_;
     const double *coords2_;
@@ -742,34 +712,20 @@ class MeshRefine {
 public:
     MeshRefine(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex, int levels = 1,
                bool want_interp = false, void *stream = nullptr)
-        : m_(nullptr), dim_(dim), NV_(0), NE_(0), info_(), coords_(nullptr), elem_ptr_(nullptr), elem_to_vertex_(nullptr) {
+        : m_(nullptr, saamge_amd_mesh_refine_free), dim_(dim), NV_(0), NE_(0), info_(), coords_(nullptr), elem_ptr_(nullptr),
+          elem_to_vertex_(nullptr) {
         long long info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (saamge_amd_mesh_refine(NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, levels, want_interp ? 1 : 0, stream, &m_, info))
+        saamge_amd_refined_mesh *m = nullptr;
+        if (saamge_amd_mesh_refine(NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, levels, want_interp ? 1 : 0, stream, &m, info))
             throw std::runtime_error(saamge_amd_last_error());
+        m_.reset(m);
         const MeshRefineInfo r = {info[0], info[1], info[2], info[3], info[4], info[5], info[6], info[7]};
         info_ = r;
-        if (saamge_amd_mesh_refine_arrays(m_, &NV_, &NE_, &coords_, &elem_ptr_, &elem_to_vertex_)) {
-            saamge_amd_mesh_refine_free(m_);
+        if (saamge_amd_mesh_refine_arrays(m, &NV_, &NE_, &coords_, &elem_ptr_, &elem_to_vertex_))
             throw std::runtime_error(saamge_amd_last_error());
-        }
     }
-    MeshRefine(MeshRefine &&o) noexcept
-        : m_(o.m_), dim_(o.dim_), NV_(o.NV_), NE_(o.NE_), info_(o.info_), coords_(o.coords_), elem_ptr_(o.elem_ptr_),
-          elem_to_vertex_(o.elem_to_vertex_) {
-        o.m_ = nullptr;
-    }
-    MeshRefine &operator=(MeshRefine &&o) noexcept {
-        if (this != &o) {
-            saamge_amd_mesh_refine_free(m_);
-            m_ = o.m_; dim_ = o.dim_; NV_ = o.NV_; NE_ = o.NE_; info_ = o.info_;
-            coords_ = o.coords_; elem_ptr_ = o.elem_ptr_; elem_to_vertex_ = o.elem_to_vertex_;
-            o.m_ = nullptr;
-        }
-        return *this;
-    }
-    MeshRefine(const MeshRefine &) = delete;
-    MeshRefine &operator=(const MeshRefine &) = delete;
-    ~MeshRefine() { saamge_amd_mesh_refine_free(m_); }
+    MeshRefine(MeshRefine &&) = default;
+    MeshRefine &operator=(MeshRefine &&) = default;
     int vertices() const { return NV_; }
     int elements() const { return NE_; }
     int levels() const { return (int)info_.levels; }
@@ -777,10 +733,10 @@ public:
     const double *coords() const { return coords_; }
     const int *elem_ptr() const { return elem_ptr_; }
     const int *elem_to_vertex() const { return elem_to_vertex_; }
-    saamge_amd_refined_mesh *handle() const { return m_; }
+    saamge_amd_refined_mesh *handle() const { return m_.get(); }
     MeshRefineLevelInfo level_info(int level) const {
         long long v[8];
-        if (saamge_amd_mesh_refine_level_info(m_, level, v)) throw std::runtime_error(saamge_amd_last_error());
+        if (saamge_amd_mesh_refine_level_info(m_.get(), level, v)) throw std::runtime_error(saamge_amd_last_error());
         const MeshRefineLevelInfo r = {v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]};
         return r;
     }
@@ -789,25 +745,25 @@ public:
         coords.assign(coords_ ? (size_t)NV_ * (size_t)dim_ : 0, 0.0);
         elem_ptr.assign((size_t)NE_ + 1, 0);
         elem_to_vertex.assign((size_t)info_.entries, 0);
-        if (saamge_amd_mesh_refine_get(m_, nullptr, nullptr, coords.data(), elem_ptr.data(), elem_to_vertex.data()))
+        if (saamge_amd_mesh_refine_get(m_.get(), nullptr, nullptr, coords.data(), elem_ptr.data(), elem_to_vertex.data()))
             throw std::runtime_error(saamge_amd_last_error());
     }
     // P_level on the host (the mesh was refined with want_interp)
     MeshInterp interp(int level) const {
         MeshInterp P;
         long long nnz = 0;
-        if (saamge_amd_mesh_refine_interp_get(m_, level, &P.nrows, &P.ncols, &nnz, nullptr, nullptr, nullptr))
+        if (saamge_amd_mesh_refine_interp_get(m_.get(), level, &P.nrows, &P.ncols, &nnz, nullptr, nullptr, nullptr))
             throw std::runtime_error(saamge_amd_last_error());
         P.rowptr.assign((size_t)P.nrows + 1, 0);
         P.col.assign((size_t)nnz, 0);
         P.val.assign((size_t)nnz, 0.0);
-        if (saamge_amd_mesh_refine_interp_get(m_, level, nullptr, nullptr, nullptr, P.rowptr.data(), P.col.data(), P.val.data()))
+        if (saamge_amd_mesh_refine_interp_get(m_.get(), level, nullptr, nullptr, nullptr, P.rowptr.data(), P.col.data(), P.val.data()))
             throw std::runtime_error(saamge_amd_last_error());
         return P;
     }
 
 private:
-    saamge_amd_refined_mesh *m_;
+    detail::Handle<saamge_amd_refined_mesh> m_;
     int dim_, NV_, NE_;
     MeshRefineInfo info_;
     const double *coords_;

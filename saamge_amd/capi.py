@@ -170,6 +170,40 @@ def _ptr(a):
     return C.c_void_p(a.ctypes.data)
 
 
+class _Handle(object):
+    """Owner of a handle of the library, `h`, until free() / close() or the end of a `with` block; _FREE names the C function
+    that frees it."""
+    _FREE = None
+    h = None
+
+    @classmethod
+    def build(cls, *args, **kw):
+        return cls(*args, **kw)
+
+    def free(self):
+        if self.h is not None and self.h.value:
+            free = getattr(load(), self._FREE)
+            free.restype = None
+            free(self.h)
+        self.h = None
+
+    def close(self):
+        self.free()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+        return False
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 def default_params(num_coarsenings=1, theta=0.003, nu_relax=3, testmesh=False, keep_debug=False,
                    coarse_rtol=1e-14, workspace_bytes=None, dist_min_local_rows=None,
                    coarse_solver=None, nu_pro=0, correct_nullspace=False, extra_modes=None, algebraic=False,
@@ -207,9 +241,10 @@ def default_params(num_coarsenings=1, theta=0.003, nu_relax=3, testmesh=False, k
     return p
 
 
-class Hierarchy(object):
+class Hierarchy(_Handle):
     """Owner of a saamge_amd_hierarchy (== ml_data_t).  Mirrors the reference call
     sequence: ml_produce_data -> VCycleSolver::Mult / CGSolver::Mult -> ml_free_data."""
+    _FREE = "saamge_amd_ml_free_data"
 
     def _prepare_params(self, params, group, stream, dist_solve):
         """A private copy of the caller's params with the collectives of `group` installed."""
@@ -401,17 +436,6 @@ class Hierarchy(object):
             _check(load().saamge_amd_update_operators(self.h, _ptr(new_val)))
         else:
             _check(load().saamge_amd_update_operators2(self.h, _ptr(new_val), C.c_int(int(coarse_solver))))
-
-    def close(self):
-        if self.h:
-            load().saamge_amd_ml_free_data(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ---- solve ----
     def vcycle(self, b, x=None):
@@ -1207,83 +1231,83 @@ def _new_ints(n, np_dt, torch_dt, device):
     return np.zeros(max(int(n), 1), np_dt)[:int(n)]
 
 
-class FaceTable(object):
+class _MeshHandle(_Handle):
+    """A handle whose device arrays a table describes.  _FIELDS: the arguments of the C calls _ARRAYS (addresses) and _GET (copies)
+    after the handle, in their order -- (name, numpy dtype, shape(self)) an array, shape None: the handle has no such array;
+    (name, ctypes type) a count."""
+    _ARRAYS = _GET = None
+    _FIELDS = ()
+
+    def arrays(self):
+        """dict of the raw device addresses of the handle's arrays (0: the handle has no such array) and of its counts, by the
+        names of the class's docstring; valid until free().  `pointer(name)` wraps one for the other entry points."""
+        slots = [C.c_void_p() if len(f) == 3 else f[1](0) for f in self._FIELDS]
+        _check(getattr(load(), self._ARRAYS)(self.h, *[C.byref(v) for v in slots]))
+        return {f[0]: int(v.value or 0) for f, v in zip(self._FIELDS, slots)}
+
+    def pointer(self, name, shape=None):
+        """the handle's device array `name` as an object the wrappers take in place of a device tensor (valid until free()), in
+        the shape `get()` gives it unless `shape` says otherwise (a node list as (NE, nodes) on a mesh of one type)"""
+        _, dt, own = next(f for f in self._FIELDS if f[0] == name and len(f) == 3)
+        own = own(self)
+        d = _DevicePointer(self.arrays()[name], dt)
+        assert own is not None, "the handle has no " + name
+        d.shape = own
+        if shape is not None:
+            d.shape = tuple(shape)
+            assert int(np.prod(d.shape)) == int(np.prod(own))
+        return d
+
+    def get(self, device=False):
+        """the handle's arrays in the order of the class's docstring (None: the handle has no such array): numpy arrays, or torch
+        tensors on the GPU with device=True"""
+        out = []
+        for f in self._FIELDS:
+            shape = f[2](self) if len(f) == 3 else None
+            if shape is None:
+                out.append(None)
+            elif f[1] is np.float64:
+                out.append(_new_doubles(int(np.prod(shape)), device))
+            else:
+                out.append(_new_ints(int(np.prod(shape)), f[1], np.dtype(f[1]).name, device))
+        _check(getattr(load(), self._GET)(self.h, *[_ptr(a) for a in out]))
+        return tuple(a if a is None else a.reshape(f[2](self)) for f, a in zip(self._FIELDS, out) if len(f) == 3)
+
+
+def _lift_arguments(coords, elem_to_vertex, elem_ptr, NV, dim):
+    """(coords, e2v, ep, NV, dim, NE, nde): the head of MeshLift and MeshRefine -- the sizes from coords, or NV and dim given"""
+    coords, e2v, _, ep = _element_arrays(coords, elem_to_vertex, None, elem_ptr)
+    if coords is not None:
+        NV, dim = int(coords.shape[0]), int(coords.shape[1])
+    elif NV is None or dim is None:
+        raise ValueError("without coords, NV and dim are needed")
+    NV, NE, nde = _mesh_sizes(NV, e2v, ep)
+    return coords, e2v, ep, NV, int(dim), NE, nde
+
+
+class FaceTable(_MeshHandle):
     """saamge_amd_face_table_build: which element lies across each local face of a mesh, owned by the library until free()
     (or the end of a `with` block).  saamge_amd/mesh_model.py defines every integer.  elem_to_vertex ((NE, nodes), or flat with
     elem_ptr) and elem_ptr: numpy arrays or device tensors, each on its own.  `.info`: the 8 integers of the call; a refusal
-    raises RuntimeError with `.info` (info[6]: the lowest element with a non-manifold face)."""
+    raises RuntimeError with `.info` (info[6]: the lowest element with a non-manifold face).
+    Arrays: slot_ptr int64, nbr_elem, nbr_local, bdr_elem, bdr_local int32, xadj int64, adj int32; counts: NB, nnz."""
+    _FREE, _ARRAYS, _GET = "saamge_amd_face_table_free", "saamge_amd_face_table_arrays", "saamge_amd_face_table_get"
+    _FIELDS = (("slot_ptr", np.int64, lambda t: (t.NE + 1,)), ("nbr_elem", np.int32, lambda t: (t.slots,)),
+               ("nbr_local", np.int32, lambda t: (t.slots,)), ("NB", C.c_longlong), ("bdr_elem", np.int32, lambda t: (t.NB,)),
+               ("bdr_local", np.int32, lambda t: (t.NB,)), ("xadj", np.int64, lambda t: (t.NE + 1,)),
+               ("adj", np.int32, lambda t: (t.nnz,)), ("nnz", C.c_longlong))
 
     def __init__(self, NV, dim, elem_to_vertex, elem_ptr=None, stream=0):
         _, e2v, _, ep = _element_arrays(None, elem_to_vertex, None, elem_ptr)
         NV, NE, nde = _mesh_sizes(NV, e2v, ep)
         h = C.c_void_p()
         info = (C.c_longlong * 8)()
-        self.h = None
         self.info = _mass_call(lambda: load().saamge_amd_face_table_build(
             C.c_int(NV), C.c_int(int(dim)), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_void_p(stream), C.byref(h), info), info)
         self.h = h
         self.NE = NE
-        NB, nnz = C.c_longlong(0), C.c_longlong(0)
-        _check(load().saamge_amd_face_table_get(self.h, None, None, None, C.byref(NB), None, None, None, None, C.byref(nnz)))
-        self.NB, self.nnz, self.slots = int(NB.value), int(nnz.value), self.info[0]
-
-    @classmethod
-    def build(cls, NV, dim, elem_to_vertex, elem_ptr=None, stream=0):
-        return cls(NV, dim, elem_to_vertex, elem_ptr=elem_ptr, stream=stream)
-
-    def arrays(self):
-        """dict of raw device addresses (slot_ptr, nbr_elem, nbr_local, bdr_elem, bdr_local, xadj, adj) and the counts NB, nnz;
-        valid until free().  `pointer(name)` wraps one for the other entry points."""
-        p = [C.c_void_p() for _ in range(7)]
-        NB, nnz = C.c_longlong(0), C.c_longlong(0)
-        _check(load().saamge_amd_face_table_arrays(self.h, C.byref(p[0]), C.byref(p[1]), C.byref(p[2]), C.byref(NB), C.byref(p[3]),
-                                                   C.byref(p[4]), C.byref(p[5]), C.byref(p[6]), C.byref(nnz)))
-        names = ("slot_ptr", "nbr_elem", "nbr_local", "bdr_elem", "bdr_local", "xadj", "adj")
-        out = {k: int(v.value or 0) for k, v in zip(names, p)}
-        out.update(NB=int(NB.value), nnz=int(nnz.value))
-        return out
-
-    def pointer(self, name):
-        """the handle's device array `name` as an object the wrappers take in place of a device tensor (valid until free())"""
-        a = self.arrays()
-        n = {"slot_ptr": self.NE + 1, "xadj": self.NE + 1, "nbr_elem": self.slots, "nbr_local": self.slots, "bdr_elem": self.NB,
-             "bdr_local": self.NB, "adj": self.nnz}[name]
-        d = _DevicePointer(a[name], np.int64 if name in ("slot_ptr", "xadj") else np.int32)
-        d.shape = (n,)
-        return d
-
-    def get(self, device=False):
-        """(slot_ptr int64, nbr_elem, nbr_local, bdr_elem, bdr_local int32, xadj int64, adj int32): numpy arrays, or torch tensors
-        on the GPU with device=True."""
-        out = [_new_ints(self.NE + 1, np.int64, "int64", device), _new_ints(self.slots, np.int32, "int32", device),
-               _new_ints(self.slots, np.int32, "int32", device), _new_ints(self.NB, np.int32, "int32", device),
-               _new_ints(self.NB, np.int32, "int32", device), _new_ints(self.NE + 1, np.int64, "int64", device),
-               _new_ints(self.nnz, np.int32, "int32", device)]
-        _check(load().saamge_amd_face_table_get(self.h, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), None, _ptr(out[3]), _ptr(out[4]),
-                                                _ptr(out[5]), _ptr(out[6]), None))
-        return tuple(out)
-
-    def free(self):
-        if self.h is not None and self.h.value:
-            free = load().saamge_amd_face_table_free
-            free.restype = None
-            free(self.h)
-        self.h = None
-
-    close = free
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.free()
-        return False
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+        counts = self.arrays()
+        self.NB, self.nnz, self.slots = counts["NB"], counts["nnz"], self.info[0]
 
 
 def face_nodes(NV, dim, elem_to_vertex, face_elem, face_local, elem_ptr=None, device=False, stream=0):
@@ -1331,7 +1355,7 @@ def face_dofs(NV, dim, elem_to_vertex, face_elem, face_local, bdr_dofs, vdim=1, 
         C.c_uint(int(comp_mask) & 0xffffffff), C.c_int(int(flag)), C.c_void_p(stream), _ptr(bdr_dofs), info), info)
 
 
-class MeshLift(object):
+class MeshLift(_MeshHandle):
     """saamge_amd_mesh_lift_order2: an order-1 mesh lifted to order 2 on the same elements -- all node coordinates, the element
     -> node lists in the node orders `element_matrices` takes (6-node triangle, 9-node quadrilateral, 10-node tetrahedron,
     27-node hexahedron), and the edge table found on the way -- owned by the library until free() (or the end of a `with`
@@ -1339,91 +1363,30 @@ class MeshLift(object):
     coordinates, then NV and dim are needed), elem_to_vertex ((NE, nodes), or flat with elem_ptr) and elem_ptr: numpy arrays or
     device tensors, each on its own.  faces: a `FaceTable` of the same mesh (used where the mesh has a hexahedron), None: built
     inside.  `.info`: the 8 integers of the call (NV2, edges, face nodes, centre nodes, entries of elem_to_node, the most edges
-    of a vertex, -1, unlisted vertices); a refusal raises RuntimeError with `.info` (info[6]: the lowest refused element)."""
+    of a vertex, -1, unlisted vertices); a refusal raises RuntimeError with `.info` (info[6]: the lowest refused element).
+    Arrays: coords2 float64 (NV2, dim) -- none without coordinates --, elem_ptr2 int32, elem_to_node int32 (flat: element e is
+    elem_to_node[elem_ptr2[e]:elem_ptr2[e + 1]], on a mesh of one type too), edge_ptr int64, edge_hi int32, face_slot int64;
+    count: NV2."""
     NAMES = ("coords2", "elem_ptr2", "elem_to_node", "edge_ptr", "edge_hi", "face_slot")
+    _FREE, _ARRAYS, _GET = "saamge_amd_mesh_lift_free", "saamge_amd_mesh_lift_arrays", "saamge_amd_mesh_lift_get"
+    _FIELDS = (("NV2", C.c_int), ("coords2", np.float64, lambda m: (m.NV2, m.dim) if m.has_coords else None),
+               ("elem_ptr2", np.int32, lambda m: (m.NE + 1,)), ("elem_to_node", np.int32, lambda m: (m.entries,)),
+               ("edge_ptr", np.int64, lambda m: (m.NV + 1,)), ("edge_hi", np.int32, lambda m: (m.NEd,)),
+               ("face_slot", np.int64, lambda m: (m.NFq,)))
 
     def __init__(self, coords, elem_to_vertex, elem_ptr=None, faces=None, NV=None, dim=None, stream=0):
-        coords, e2v, _, ep = _element_arrays(coords, elem_to_vertex, None, elem_ptr)
-        if coords is not None:
-            NV, dim = int(coords.shape[0]), int(coords.shape[1])
-        elif NV is None or dim is None:
-            raise ValueError("without coords, NV and dim are needed")
-        NV, NE, nde = _mesh_sizes(NV, e2v, ep)
+        coords, e2v, ep, NV, dim, NE, nde = _lift_arguments(coords, elem_to_vertex, elem_ptr, NV, dim)
         h = C.c_void_p()
         info = (C.c_longlong * 8)()
-        self.h = None
         self.info = _mass_call(lambda: load().saamge_amd_mesh_lift_order2(
-            C.c_int(NV), C.c_int(int(dim)), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v),
+            C.c_int(NV), C.c_int(dim), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v),
             faces.h if faces is not None else None, C.c_void_p(stream), C.byref(h), info), info)
         self.h = h
-        self.NV, self.NE, self.dim, self.has_coords = NV, NE, int(dim), coords is not None
+        self.NV, self.NE, self.dim, self.has_coords = NV, NE, dim, coords is not None
         self.NV2, self.NEd, self.NFq, self.NC, self.entries = self.info[:5]
 
-    @classmethod
-    def build(cls, coords, elem_to_vertex, elem_ptr=None, faces=None, NV=None, dim=None, stream=0):
-        return cls(coords, elem_to_vertex, elem_ptr=elem_ptr, faces=faces, NV=NV, dim=dim, stream=stream)
 
-    def _sizes(self):
-        return {"coords2": self.NV2 * self.dim if self.has_coords else 0, "elem_ptr2": self.NE + 1, "elem_to_node": self.entries,
-                "edge_ptr": self.NV + 1, "edge_hi": self.NEd, "face_slot": self.NFq}
-
-    def arrays(self):
-        """dict of raw device addresses (coords2 -- 0 without coordinates --, elem_ptr2, elem_to_node, edge_ptr, edge_hi,
-        face_slot) and NV2; valid until free().  `pointer(name)` wraps one for the other entry points."""
-        p = [C.c_void_p() for _ in range(6)]
-        NV2 = C.c_int(0)
-        _check(load().saamge_amd_mesh_lift_arrays(self.h, C.byref(NV2), *[C.byref(v) for v in p]))
-        out = {k: int(v.value or 0) for k, v in zip(self.NAMES, p)}
-        out.update(NV2=int(NV2.value))
-        return out
-
-    def pointer(self, name, shape=None):
-        """the handle's device array `name` as an object the wrappers take in place of a device tensor (valid until free());
-        coords2 has the shape (NV2, dim), the others are flat unless `shape` says otherwise (elem_to_node as (NE, nodes) on a
-        mesh of one type)"""
-        dt = {"coords2": np.float64, "edge_ptr": np.int64, "face_slot": np.int64}.get(name, np.int32)
-        d = _DevicePointer(self.arrays()[name], dt)
-        d.shape = tuple(shape) if shape is not None else (self.NV2, self.dim) if name == "coords2" else (self._sizes()[name],)
-        assert int(np.prod(d.shape)) == self._sizes()[name]
-        return d
-
-    def get(self, device=False):
-        """(coords2 float64 (NV2, dim) or None, elem_ptr2 int32, elem_to_node int32 (flat: element e is
-        elem_to_node[elem_ptr2[e]:elem_ptr2[e + 1]], on a mesh of one type too), edge_ptr int64, edge_hi int32, face_slot int64):
-        numpy arrays, or torch tensors on the GPU with device=True."""
-        n = self._sizes()
-        out = [_new_doubles(n["coords2"], device) if self.has_coords else None, _new_ints(n["elem_ptr2"], np.int32, "int32", device),
-               _new_ints(n["elem_to_node"], np.int32, "int32", device), _new_ints(n["edge_ptr"], np.int64, "int64", device),
-               _new_ints(n["edge_hi"], np.int32, "int32", device), _new_ints(n["face_slot"], np.int64, "int64", device)]
-        _check(load().saamge_amd_mesh_lift_get(self.h, None, *[_ptr(a) for a in out]))
-        if self.has_coords:
-            out[0] = out[0].reshape(self.NV2, self.dim)
-        return tuple(out)
-
-    def free(self):
-        if self.h is not None and self.h.value:
-            free = load().saamge_amd_mesh_lift_free
-            free.restype = None
-            free(self.h)
-        self.h = None
-
-    close = free
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.free()
-        return False
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class MeshRefine(object):
+class MeshRefine(_MeshHandle):
     """saamge_amd_mesh_refine: an order-1 mesh refined uniformly `levels` times on the device -- every triangle and quadrilateral
     into 4, every tetrahedron and hexahedron into 8 elements of its own type --, owned by the library until free() (or the end of
     a `with` block).  saamge_amd/mesh_refine_model.py defines every integer and every coordinate bit.  Child k of element e is
@@ -1432,63 +1395,24 @@ class MeshRefine(object):
     arrays or device tensors, each on its own.  want_interp: the vertex -> vertex interpolations P_0 .. P_{levels-1} are kept
     (`interp(level)`).  `.info`: the 8 integers of the call (NV, NE and entries of elem_to_vertex of the result, levels, total nnz
     of the kept P, the most edges of a vertex, -1, unlisted vertices); a refusal raises RuntimeError with `.info` (info[6]: the
-    lowest refused element)."""
+    lowest refused element).
+    Arrays: coords float64 (NV, dim) -- none without coordinates --, elem_ptr int32, elem_to_vertex int32 (flat: element c is
+    elem_to_vertex[elem_ptr[c]:elem_ptr[c + 1]], on a mesh of one type too); counts: NV, NE."""
     NAMES = ("coords", "elem_ptr", "elem_to_vertex")
+    _FREE, _ARRAYS, _GET = "saamge_amd_mesh_refine_free", "saamge_amd_mesh_refine_arrays", "saamge_amd_mesh_refine_get"
+    _FIELDS = (("NV", C.c_int), ("NE", C.c_int), ("coords", np.float64, lambda m: (m.NV, m.dim) if m.has_coords else None),
+               ("elem_ptr", np.int32, lambda m: (m.NE + 1,)), ("elem_to_vertex", np.int32, lambda m: (m.entries,)))
 
     def __init__(self, coords, elem_to_vertex, elem_ptr=None, levels=1, want_interp=False, NV=None, dim=None, stream=0):
-        coords, e2v, _, ep = _element_arrays(coords, elem_to_vertex, None, elem_ptr)
-        if coords is not None:
-            NV, dim = int(coords.shape[0]), int(coords.shape[1])
-        elif NV is None or dim is None:
-            raise ValueError("without coords, NV and dim are needed")
-        NV, NE, nde = _mesh_sizes(NV, e2v, ep)
+        coords, e2v, ep, NV, dim, NE, nde = _lift_arguments(coords, elem_to_vertex, elem_ptr, NV, dim)
         h = C.c_void_p()
         info = (C.c_longlong * 8)()
-        self.h = None
         self.info = _mass_call(lambda: load().saamge_amd_mesh_refine(
-            C.c_int(NV), C.c_int(int(dim)), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_int(int(levels)),
+            C.c_int(NV), C.c_int(dim), _ptr(coords), C.c_int(NE), C.c_int(nde), _ptr(ep), _ptr(e2v), C.c_int(int(levels)),
             C.c_int(int(bool(want_interp))), C.c_void_p(stream), C.byref(h), info), info)
         self.h = h
-        self.dim, self.has_coords, self.want_interp = int(dim), coords is not None, bool(want_interp)
+        self.dim, self.has_coords, self.want_interp = dim, coords is not None, bool(want_interp)
         self.NV, self.NE, self.entries, self.levels = self.info[:4]
-
-    @classmethod
-    def build(cls, coords, elem_to_vertex, elem_ptr=None, levels=1, want_interp=False, NV=None, dim=None, stream=0):
-        return cls(coords, elem_to_vertex, elem_ptr=elem_ptr, levels=levels, want_interp=want_interp, NV=NV, dim=dim, stream=stream)
-
-    def _sizes(self):
-        return {"coords": self.NV * self.dim if self.has_coords else 0, "elem_ptr": self.NE + 1, "elem_to_vertex": self.entries}
-
-    def arrays(self):
-        """dict of raw device addresses (coords -- 0 without coordinates --, elem_ptr, elem_to_vertex) and NV, NE; valid until
-        free().  `pointer(name)` wraps one for the other entry points."""
-        p = [C.c_void_p() for _ in range(3)]
-        NV, NE = C.c_int(0), C.c_int(0)
-        _check(load().saamge_amd_mesh_refine_arrays(self.h, C.byref(NV), C.byref(NE), *[C.byref(v) for v in p]))
-        out = {k: int(v.value or 0) for k, v in zip(self.NAMES, p)}
-        out.update(NV=int(NV.value), NE=int(NE.value))
-        return out
-
-    def pointer(self, name, shape=None):
-        """the handle's device array `name` as an object the wrappers take in place of a device tensor (valid until free());
-        coords has the shape (NV, dim), the others are flat unless `shape` says otherwise (elem_to_vertex as (NE, nodes) on a
-        mesh of one type)"""
-        d = _DevicePointer(self.arrays()[name], np.float64 if name == "coords" else np.int32)
-        d.shape = tuple(shape) if shape is not None else (self.NV, self.dim) if name == "coords" else (self._sizes()[name],)
-        assert int(np.prod(d.shape)) == self._sizes()[name]
-        return d
-
-    def get(self, device=False):
-        """(coords float64 (NV, dim) or None, elem_ptr int32, elem_to_vertex int32 (flat: element c is
-        elem_to_vertex[elem_ptr[c]:elem_ptr[c + 1]], on a mesh of one type too)): numpy arrays, or torch tensors on the GPU with
-        device=True."""
-        n = self._sizes()
-        out = [_new_doubles(n["coords"], device) if self.has_coords else None, _new_ints(n["elem_ptr"], np.int32, "int32", device),
-               _new_ints(n["elem_to_vertex"], np.int32, "int32", device)]
-        _check(load().saamge_amd_mesh_refine_get(self.h, None, None, *[_ptr(a) for a in out]))
-        if self.has_coords:
-            out[0] = out[0].reshape(self.NV, self.dim)
-        return tuple(out)
 
     def level_info(self, level):
         """[NV, NE, entries of the vertex list, NEd, NFq, centres, the most edges of a vertex, nnz of P_level] of level `level`
@@ -1517,28 +1441,6 @@ class MeshRefine(object):
                _new_doubles(nnz.value, device)]
         _check(load().saamge_amd_mesh_refine_interp_get(self.h, C.c_int(int(level)), None, None, None, *[_ptr(a) for a in out]))
         return (int(nrows.value), int(ncols.value)) + tuple(out)
-
-    def free(self):
-        if self.h is not None and self.h.value:
-            free = load().saamge_amd_mesh_refine_free
-            free.restype = None
-            free(self.h)
-        self.h = None
-
-    close = free
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.free()
-        return False
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 def get_options():
@@ -1648,11 +1550,12 @@ def partition_refine_info():
     return dict(rounds=int(info[0]), moved=int(info[1]), gain=int(info[2]), converged=int(info[3]))
 
 
-class Partitioning(object):
+class Partitioning(_Handle):
     """saamge_amd_partition_mesh: the partitions of every coarsening, owned by the library until close().  Keywords beyond
     the named ones are the fields of PartitionOptions (seeding=1: spaced seeds) or, with `growth` among them (1: balanced
     growth), of PartitionOptionsV2 (saamge_amd_partition_mesh_v2).  refine_rounds: one count per coarsening, the boundary
     refinement of saamge_amd_partition_mesh_refined (None: the entry points without it)."""
+    _FREE = "saamge_amd_partitioning_free"
 
     def __init__(self, elem_to_dof, ND, elems_per_agg, elem_ptr=None, nde=0, NE=None, stream=0, refine_rounds=None, **opts):
         if refine_rounds is not None:
@@ -1710,19 +1613,6 @@ class Partitioning(object):
         _check(load().saamge_amd_partitioning_graph(self.h, C.c_int(level), _ptr(xadj), _ptr(adj), None, None))
         return xadj, adj
 
-    def close(self):
-        if self.h is not None and self.h.value:
-            free = load().saamge_amd_partitioning_free
-            free.restype = None
-            free(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def partition_mesh(elem_to_dof, ND, elems_per_agg, elem_ptr=None, **kw):
     return Partitioning(elem_to_dof, ND, elems_per_agg, elem_ptr=elem_ptr, **kw)
@@ -1738,9 +1628,10 @@ class _DevicePointer(object):
         return self._address
 
 
-class Operator(object):
+class Operator(_Handle):
     """saamge_amd_operator_assemble: the fine operator assembled on the device from the element matrices, owned by the
     library until close().  saamge_amd/assemble_model.py defines its pattern and values."""
+    _FREE = "saamge_amd_operator_free"
 
     def __init__(self, n, elem_to_dof, elmat, bdr=None, elem_ptr=None, nde=0, NE=None, stream=0):
         if NE is None:
@@ -1821,19 +1712,6 @@ class Operator(object):
         c = (C.c_longlong * 6)()
         _check(load().saamge_amd_operator_path_counts(self.h, c))
         return {"symbolic": tuple(int(v) for v in c[:3]), "numeric": tuple(int(v) for v in c[3:])}
-
-    def close(self):
-        if self.h is not None and self.h.value:
-            free = load().saamge_amd_operator_free
-            free.restype = None
-            free(self.h)
-        self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def operator_path_limits(short_candidates=-1, lds_candidates=-1):

@@ -68,6 +68,37 @@ static void require_device(const Hierarchy &H) {
     set_thread_stream(H.stream);     // device blocks freed by this call are ordered after the hierarchy's stream
 }
 
+// The prologue of every entry point of the element layer and the mesh layer: the call's stream is the thread's while it runs, the
+// mesh arguments travel as one, errors become the return code.
+template <class F>
+static int mesh_call(const MeshArgs &m, void *stream, F call) {
+    SA_API_BEGIN
+    hipStream_t s = (hipStream_t)stream;
+    ThreadStreamScope scope(s);
+    call(s, m);
+    SA_API_END
+}
+// mesh_call for an entry point that makes a handle: *out gets the handle once `build` has filled it.  On a refusal *out stays
+// unwritten, or (clear) is NULL from the entry on.
+template <class H, class F>
+static int mesh_handle_call(const char *name, H **out, bool clear, const MeshArgs &m, void *stream, F build) {
+    return mesh_call(m, stream, [&](hipStream_t s, const MeshArgs &mm) {
+        SA_REQUIRE(out, std::string(name) + ": null argument: out");
+        if (clear) *out = nullptr;
+        std::unique_ptr<H> P(new H);
+        build(s, mm, *P);
+        *out = P.release();
+    });
+}
+// what the getters of the mesh handles share
+static void require_device(int device, const char *what) {
+    SA_REQUIRE(current_device() == device, std::string("the calling thread's current HIP device is not the ") + what + "'s device");
+}
+template <class T>
+static void copy_out(void *dst, const DBuf<T> &src) {
+    if (dst && src.n) SA_HIP_CHECK(hipMemcpy(dst, src.p, src.n * sizeof(T), hipMemcpyDefault));
+}
+
 extern "C" int saamge_amd_comm_native_stream(const saamge_amd_params *p, void **stream);      // comm.hip
 
 extern "C" {
@@ -815,180 +846,128 @@ int saamge_amd_ae_order(int ND, int NE, int nde, const int *elem_ptr, const int 
 int saamge_amd_element_matrices(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                                 const int *elem_to_vertex, int kind, int ncoef, const double *coef, void *stream,
                                 double *elmat_out, int *dof_ptr_out, int *elem_to_dof_out, long long info[8]) {
-    SA_API_BEGIN
-    hipStream_t s = (hipStream_t)stream;
-    ThreadStreamScope scope(s);
-    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
-    element_matrices(s, m, kind, ncoef, coef, elmat_out, dof_ptr_out, elem_to_dof_out, info);
-    SA_API_END
+    return mesh_call({NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex}, stream, [&](hipStream_t s, const MeshArgs &m) {
+        element_matrices(s, m, kind, ncoef, coef, elmat_out, dof_ptr_out, elem_to_dof_out, info);
+    });
 }
 
 int saamge_amd_element_mass(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                             const int *elem_to_vertex, int vdim, const double *coef, void *stream, int accumulate,
                             double *elmat_inout, long long info[8]) {
-    SA_API_BEGIN
-    hipStream_t s = (hipStream_t)stream;
-    ThreadStreamScope scope(s);
-    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
-    element_mass(s, m, vdim, coef, accumulate, elmat_inout, info);
-    SA_API_END
+    return mesh_call({NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex}, stream, [&](hipStream_t s, const MeshArgs &m) {
+        element_mass(s, m, vdim, coef, accumulate, elmat_inout, info);
+    });
 }
 
 int saamge_amd_element_loads(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                              const int *elem_to_vertex, int vdim, const double *coef, const double *src, void *stream,
                              double *elvec_out, long long info[8]) {
-    SA_API_BEGIN
-    hipStream_t s = (hipStream_t)stream;
-    ThreadStreamScope scope(s);
-    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
-    element_loads(s, m, vdim, coef, src, elvec_out, info);
-    SA_API_END
+    return mesh_call({NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex}, stream, [&](hipStream_t s, const MeshArgs &m) {
+        element_loads(s, m, vdim, coef, src, elvec_out, info);
+    });
 }
 
 int saamge_amd_boundary_mass(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                              const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim,
                              const double *coef, void *stream, double *elmat_inout, long long info[8]) {
-    SA_API_BEGIN
-    hipStream_t s = (hipStream_t)stream;
-    ThreadStreamScope scope(s);
-    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
-    boundary_mass(s, m, NF, face_elem, face_local, vdim, coef, elmat_inout, info);
-    SA_API_END
+    return mesh_call({NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex}, stream, [&](hipStream_t s, const MeshArgs &m) {
+        boundary_mass(s, m, NF, face_elem, face_local, vdim, coef, elmat_inout, info);
+    });
 }
 
 int saamge_amd_boundary_loads(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                               const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim,
                               const double *coef, const double *g, void *stream, double *elvec_inout, long long info[8]) {
-    SA_API_BEGIN
-    hipStream_t s = (hipStream_t)stream;
-    ThreadStreamScope scope(s);
-    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
-    boundary_loads(s, m, NF, face_elem, face_local, vdim, coef, g, elvec_inout, info);
-    SA_API_END
+    return mesh_call({NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex}, stream, [&](hipStream_t s, const MeshArgs &m) {
+        boundary_loads(s, m, NF, face_elem, face_local, vdim, coef, g, elvec_inout, info);
+    });
 }
 
 int saamge_amd_boundary_points(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                                const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, void *stream,
                                long long *fp_ptr_out, double *xq_out, double *wmeas_out, double *normal_out, long long info[8]) {
-    SA_API_BEGIN
-    hipStream_t s = (hipStream_t)stream;
-    ThreadStreamScope scope(s);
-    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
-    boundary_points(s, m, NF, face_elem, face_local, fp_ptr_out, xq_out, wmeas_out, normal_out, info);
-    SA_API_END
+    return mesh_call({NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex}, stream, [&](hipStream_t s, const MeshArgs &m) {
+        boundary_points(s, m, NF, face_elem, face_local, fp_ptr_out, xq_out, wmeas_out, normal_out, info);
+    });
 }
 
 int saamge_amd_boundary_eval(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                              const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim,
                              const double *u, void *stream, double *uq_out, double *gradq_out, long long info[8]) {
-    SA_API_BEGIN
-    hipStream_t s = (hipStream_t)stream;
-    ThreadStreamScope scope(s);
-    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
-    boundary_eval(s, m, NF, face_elem, face_local, vdim, u, uq_out, gradq_out, info);
-    SA_API_END
+    return mesh_call({NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex}, stream, [&](hipStream_t s, const MeshArgs &m) {
+        boundary_eval(s, m, NF, face_elem, face_local, vdim, u, uq_out, gradq_out, info);
+    });
 }
 
 int saamge_amd_boundary_mass_points(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                                     const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim,
                                     const double *coefq, void *stream, double *elmat_inout, long long info[8]) {
-    SA_API_BEGIN
-    hipStream_t s = (hipStream_t)stream;
-    ThreadStreamScope scope(s);
-    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
-    boundary_mass_points(s, m, NF, face_elem, face_local, vdim, coefq, elmat_inout, info);
-    SA_API_END
+    return mesh_call({NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex}, stream, [&](hipStream_t s, const MeshArgs &m) {
+        boundary_mass_points(s, m, NF, face_elem, face_local, vdim, coefq, elmat_inout, info);
+    });
 }
 
 int saamge_amd_boundary_loads_points(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                                      const int *elem_to_vertex, int NF, const int *face_elem, const int *face_local, int vdim,
                                      const double *coef, const double *gq, void *stream, double *elvec_inout, long long info[8]) {
-    SA_API_BEGIN
-    hipStream_t s = (hipStream_t)stream;
-    ThreadStreamScope scope(s);
-    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
-    boundary_loads_points(s, m, NF, face_elem, face_local, vdim, coef, gq, elvec_inout, info);
-    SA_API_END
+    return mesh_call({NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex}, stream, [&](hipStream_t s, const MeshArgs &m) {
+        boundary_loads_points(s, m, NF, face_elem, face_local, vdim, coef, gq, elvec_inout, info);
+    });
 }
 
 int saamge_amd_element_points(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                               const int *elem_to_vertex, void *stream, long long *qp_ptr_out, double *xq_out, double *wdet_out,
                               long long info[8]) {
-    SA_API_BEGIN
-    hipStream_t s = (hipStream_t)stream;
-    ThreadStreamScope scope(s);
-    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
-    element_points(s, m, qp_ptr_out, xq_out, wdet_out, info);
-    SA_API_END
+    return mesh_call({NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex}, stream, [&](hipStream_t s, const MeshArgs &m) {
+        element_points(s, m, qp_ptr_out, xq_out, wdet_out, info);
+    });
 }
 
 int saamge_amd_element_eval(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                             const int *elem_to_vertex, int vdim, const double *u, void *stream, double *uq_out, double *gradq_out,
                             long long info[8]) {
-    SA_API_BEGIN
-    hipStream_t s = (hipStream_t)stream;
-    ThreadStreamScope scope(s);
-    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
-    element_eval(s, m, vdim, u, uq_out, gradq_out, info);
-    SA_API_END
+    return mesh_call({NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex}, stream, [&](hipStream_t s, const MeshArgs &m) {
+        element_eval(s, m, vdim, u, uq_out, gradq_out, info);
+    });
 }
 
 int saamge_amd_element_loads_points(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                                     const int *elem_to_vertex, int vdim, const double *coef, const double *fq, void *stream,
                                     double *elvec_out, long long info[8]) {
-    SA_API_BEGIN
-    hipStream_t s = (hipStream_t)stream;
-    ThreadStreamScope scope(s);
-    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
-    element_loads_points(s, m, vdim, coef, fq, elvec_out, info);
-    SA_API_END
+    return mesh_call({NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex}, stream, [&](hipStream_t s, const MeshArgs &m) {
+        element_loads_points(s, m, vdim, coef, fq, elvec_out, info);
+    });
 }
 
 int saamge_amd_element_errors(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                               const int *elem_to_vertex, int vdim, const double *u, const double *exq, const double *exgradq,
                               void *stream, double *err_out, long long info[8]) {
-    SA_API_BEGIN
-    hipStream_t s = (hipStream_t)stream;
-    ThreadStreamScope scope(s);
-    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
-    element_errors(s, m, vdim, u, exq, exgradq, err_out, info);
-    SA_API_END
+    return mesh_call({NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex}, stream, [&](hipStream_t s, const MeshArgs &m) {
+        element_errors(s, m, vdim, u, exq, exgradq, err_out, info);
+    });
 }
 
 int saamge_amd_element_matrices_points(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                                        const int *elem_to_vertex, int kind, int ncoef, const double *coefq, void *stream,
                                        double *elmat_out, int *dof_ptr_out, int *elem_to_dof_out, long long info[8]) {
-    SA_API_BEGIN
-    hipStream_t s = (hipStream_t)stream;
-    ThreadStreamScope scope(s);
-    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
-    element_matrices_points(s, m, kind, ncoef, coefq, elmat_out, dof_ptr_out, elem_to_dof_out, info);
-    SA_API_END
+    return mesh_call({NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex}, stream, [&](hipStream_t s, const MeshArgs &m) {
+        element_matrices_points(s, m, kind, ncoef, coefq, elmat_out, dof_ptr_out, elem_to_dof_out, info);
+    });
 }
 
 int saamge_amd_element_mass_points(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                                    const int *elem_to_vertex, int vdim, const double *coefq, void *stream, int accumulate,
                                    double *elmat_inout, long long info[8]) {
-    SA_API_BEGIN
-    hipStream_t s = (hipStream_t)stream;
-    ThreadStreamScope scope(s);
-    const MeshArgs m{NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex};
-    element_mass_points(s, m, vdim, coefq, accumulate, elmat_inout, info);
-    SA_API_END
+    return mesh_call({NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex}, stream, [&](hipStream_t s, const MeshArgs &m) {
+        element_mass_points(s, m, vdim, coefq, accumulate, elmat_inout, info);
+    });
 }
 
 // ---- the faces of a mesh (mesh_faces.hip) -----------------------------------------------------------------------------------
 int saamge_amd_face_table_build(int NV, int dim, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex, void *stream,
                                 saamge_amd_face_table **out, long long info[8]) {
-    SA_API_BEGIN
-    SA_REQUIRE(out, "saamge_amd_face_table_build: null argument: out");
-    *out = nullptr;
-    hipStream_t s = (hipStream_t)stream;
-    ThreadStreamScope scope(s);
-    std::unique_ptr<saamge_amd_face_table> P(new saamge_amd_face_table);
-    face_table_build(s, NV, dim, NE, nde, elem_ptr, elem_to_vertex, P->t, info);
-    *out = P.release();
-    SA_API_END
+    return mesh_handle_call("saamge_amd_face_table_build", out, true, {NV, dim, nullptr, NE, nde, elem_ptr, elem_to_vertex}, stream,
+                            [&](hipStream_t s, const MeshArgs &m, saamge_amd_face_table &h) { face_table_build(s, m, h.t, info); });
 }
 
 int saamge_amd_face_table_arrays(const saamge_amd_face_table *t, const long long **slot_ptr, const int **nbr_elem,
@@ -1015,18 +994,14 @@ int saamge_amd_face_table_get(const saamge_amd_face_table *t, long long *slot_pt
     const FaceTable &T = t->t;
     if (NB) *NB = T.NB;
     if (nnz) *nnz = T.nnz;
-    if (slot_ptr || nbr_elem || nbr_local || bdr_elem || bdr_local || xadj || adj)
-        SA_REQUIRE(current_device() == T.device, "the calling thread's current HIP device is not the face table's device");
-    const auto copy = [](void *dst, const void *src, size_t bytes) {
-        if (dst && bytes) SA_HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyDefault));
-    };
-    copy(slot_ptr, T.slot_ptr.p, T.slot_ptr.n * sizeof(roff_t));
-    copy(nbr_elem, T.nbr_elem.p, T.nbr_elem.n * sizeof(int));
-    copy(nbr_local, T.nbr_local.p, T.nbr_local.n * sizeof(int));
-    copy(bdr_elem, T.bdr_elem.p, T.bdr_elem.n * sizeof(int));
-    copy(bdr_local, T.bdr_local.p, T.bdr_local.n * sizeof(int));
-    copy(xadj, T.xadj.p, T.xadj.n * sizeof(roff_t));
-    copy(adj, T.adj.p, T.adj.n * sizeof(int));
+    if (slot_ptr || nbr_elem || nbr_local || bdr_elem || bdr_local || xadj || adj) require_device(T.device, "face table");
+    copy_out(slot_ptr, T.slot_ptr);
+    copy_out(nbr_elem, T.nbr_elem);
+    copy_out(nbr_local, T.nbr_local);
+    copy_out(bdr_elem, T.bdr_elem);
+    copy_out(bdr_local, T.bdr_local);
+    copy_out(xadj, T.xadj);
+    copy_out(adj, T.adj);
     SA_API_END
 }
 
@@ -1035,35 +1010,27 @@ void saamge_amd_face_table_free(saamge_amd_face_table *t) { delete t; }
 int saamge_amd_face_nodes(int NV, int dim, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex, int NF,
                           const int *face_elem, const int *face_local, void *stream, int *face_ptr_out, int *face_nodes_out,
                           long long *count_out) {
-    SA_API_BEGIN
-    hipStream_t s = (hipStream_t)stream;
-    ThreadStreamScope scope(s);
-    face_nodes(s, NV, dim, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, face_ptr_out, face_nodes_out, count_out);
-    SA_API_END
+    return mesh_call({NV, dim, nullptr, NE, nde, elem_ptr, elem_to_vertex}, stream, [&](hipStream_t s, const MeshArgs &m) {
+        face_nodes(s, m, NF, face_elem, face_local, face_ptr_out, face_nodes_out, count_out);
+    });
 }
 
 int saamge_amd_face_dofs(int NV, int dim, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex, int NF,
                          const int *face_elem, const int *face_local, int vdim, unsigned comp_mask, int flag, void *stream,
                          signed char *bdr_dofs_inout, long long info[4]) {
-    SA_API_BEGIN
-    hipStream_t s = (hipStream_t)stream;
-    ThreadStreamScope scope(s);
-    face_dofs(s, NV, dim, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local, vdim, comp_mask, flag, bdr_dofs_inout, info);
-    SA_API_END
+    return mesh_call({NV, dim, nullptr, NE, nde, elem_ptr, elem_to_vertex}, stream, [&](hipStream_t s, const MeshArgs &m) {
+        face_dofs(s, m, NF, face_elem, face_local, vdim, comp_mask, flag, bdr_dofs_inout, info);
+    });
 }
 
 // ---- an order-1 mesh lifted to order 2 (mesh_lift.hip) ------------------------------------------------------------------------
 int saamge_amd_mesh_lift_order2(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
                                 const int *elem_to_vertex, const saamge_amd_face_table *faces, void *stream,
                                 saamge_amd_mesh_lift **out, long long info[8]) {
-    SA_API_BEGIN
-    SA_REQUIRE(out, "saamge_amd_mesh_lift_order2: null argument: out");
-    hipStream_t s = (hipStream_t)stream;
-    ThreadStreamScope scope(s);
-    std::unique_ptr<saamge_amd_mesh_lift> P(new saamge_amd_mesh_lift);
-    mesh_lift_order2(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, faces ? &faces->t : nullptr, P->l, info);
-    *out = P.release();
-    SA_API_END
+    return mesh_handle_call("saamge_amd_mesh_lift_order2", out, false, {NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex}, stream,
+                            [&](hipStream_t s, const MeshArgs &m, saamge_amd_mesh_lift &h) {
+                                mesh_lift_order2(s, m, faces ? &faces->t : nullptr, h.l, info);
+                            });
 }
 
 int saamge_amd_mesh_lift_arrays(const saamge_amd_mesh_lift *m, int *NV2, const double **coords2, const int **elem_ptr2,
@@ -1087,17 +1054,13 @@ int saamge_amd_mesh_lift_get(const saamge_amd_mesh_lift *m, int *NV2, double *co
     SA_REQUIRE(m, "saamge_amd_mesh_lift_get: null argument");
     const MeshLift &L = m->l;
     if (NV2) *NV2 = L.NV2;
-    if (coords2 || elem_ptr2 || elem_to_node || edge_ptr || edge_hi || face_slot)
-        SA_REQUIRE(current_device() == L.device, "the calling thread's current HIP device is not the lifted mesh's device");
-    const auto copy = [](void *dst, const void *src, size_t bytes) {
-        if (dst && bytes) SA_HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyDefault));
-    };
-    copy(coords2, L.coords2.p, L.coords2.n * sizeof(double));
-    copy(elem_ptr2, L.elem_ptr2.p, L.elem_ptr2.n * sizeof(int));
-    copy(elem_to_node, L.elem_to_node.p, L.elem_to_node.n * sizeof(int));
-    copy(edge_ptr, L.edge_ptr.p, L.edge_ptr.n * sizeof(roff_t));
-    copy(edge_hi, L.edge_hi.p, L.edge_hi.n * sizeof(int));
-    copy(face_slot, L.face_slot.p, L.face_slot.n * sizeof(roff_t));
+    if (coords2 || elem_ptr2 || elem_to_node || edge_ptr || edge_hi || face_slot) require_device(L.device, "lifted mesh");
+    copy_out(coords2, L.coords2);
+    copy_out(elem_ptr2, L.elem_ptr2);
+    copy_out(elem_to_node, L.elem_to_node);
+    copy_out(edge_ptr, L.edge_ptr);
+    copy_out(edge_hi, L.edge_hi);
+    copy_out(face_slot, L.face_slot);
     SA_API_END
 }
 
@@ -1106,14 +1069,10 @@ void saamge_amd_mesh_lift_free(saamge_amd_mesh_lift *m) { delete m; }
 // ---- an order-1 mesh refined uniformly (mesh_refine.hip) ------------------------------------------------------------------------
 int saamge_amd_mesh_refine(int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex,
                            int levels, int want_interp, void *stream, saamge_amd_refined_mesh **out, long long info[8]) {
-    SA_API_BEGIN
-    SA_REQUIRE(out, "saamge_amd_mesh_refine: null argument: out");
-    hipStream_t s = (hipStream_t)stream;
-    ThreadStreamScope scope(s);
-    std::unique_ptr<saamge_amd_refined_mesh> P(new saamge_amd_refined_mesh);
-    mesh_refine(s, NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex, levels, want_interp, P->r, info);
-    *out = P.release();
-    SA_API_END
+    return mesh_handle_call("saamge_amd_mesh_refine", out, false, {NV, dim, coords, NE, nde, elem_ptr, elem_to_vertex}, stream,
+                            [&](hipStream_t s, const MeshArgs &m, saamge_amd_refined_mesh &h) {
+                                mesh_refine(s, m, levels, want_interp, h.r, info);
+                            });
 }
 
 int saamge_amd_mesh_refine_arrays(const saamge_amd_refined_mesh *m, int *NV, int *NE, const double **coords, const int **elem_ptr,
@@ -1135,14 +1094,10 @@ int saamge_amd_mesh_refine_get(const saamge_amd_refined_mesh *m, int *NV, int *N
     const MeshRefine &R = m->r;
     if (NV) *NV = R.NV;
     if (NE) *NE = R.NE;
-    if (coords || elem_ptr || elem_to_vertex)
-        SA_REQUIRE(current_device() == R.device, "the calling thread's current HIP device is not the refined mesh's device");
-    const auto copy = [](void *dst, const void *src, size_t bytes) {
-        if (dst && bytes) SA_HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyDefault));
-    };
-    copy(coords, R.coords.p, R.coords.n * sizeof(double));
-    copy(elem_ptr, R.elem_ptr.p, R.elem_ptr.n * sizeof(int));
-    copy(elem_to_vertex, R.elem_to_vertex.p, R.elem_to_vertex.n * sizeof(int));
+    if (coords || elem_ptr || elem_to_vertex) require_device(R.device, "refined mesh");
+    copy_out(coords, R.coords);
+    copy_out(elem_ptr, R.elem_ptr);
+    copy_out(elem_to_vertex, R.elem_to_vertex);
     SA_API_END
 }
 
@@ -1183,14 +1138,10 @@ int saamge_amd_mesh_refine_interp_get(const saamge_amd_refined_mesh *m, int leve
     if (nrows) *nrows = P.nrows;
     if (ncols) *ncols = P.ncols;
     if (nnz) *nnz = P.nnz;
-    if (rowptr || col || val)
-        SA_REQUIRE(current_device() == m->r.device, "the calling thread's current HIP device is not the refined mesh's device");
-    const auto copy = [](void *dst, const void *src, size_t bytes) {
-        if (dst && bytes) SA_HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyDefault));
-    };
-    copy(rowptr, P.rowptr.p, P.rowptr.n * sizeof(int));
-    copy(col, P.col.p, P.col.n * sizeof(int));
-    copy(val, P.val.p, P.val.n * sizeof(double));
+    if (rowptr || col || val) require_device(m->r.device, "refined mesh");
+    copy_out(rowptr, P.rowptr);
+    copy_out(col, P.col);
+    copy_out(val, P.val);
     SA_API_END
 }
 

@@ -272,6 +272,8 @@ inline int pick_lanes_per_row(int64_t nnz, int nrows) {
 }
 
 inline int div_up(int64_t a, int64_t b) { return int((a + b - 1) / b); }
+// the grid of a kernel with one lane per item and 256 lanes per workgroup (one workgroup for no items: the launch stays valid)
+inline dim3 grid_flat(long n) { return dim3((unsigned)(n > 256 ? (n + 255) / 256 : 1)); }
 // Home slot of `key` in an open-addressing table of `size` slots (a power of two >= 2): the HIGH bits of the multiplicative
 // hash.  (Until round 4 the tables took the low bits, which are a permutation of the key's own low bits: the dofs of a box
 // of a lexicographically numbered grid -- x + 257 y + 66049 z -- collide in lattices, 4.2 probes per look-up instead of 1.0

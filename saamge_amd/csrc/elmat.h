@@ -6,16 +6,9 @@
 
 #include <string>
 
-namespace saamge_amd {
+#include "mesh.h"      // MeshArgs: the mesh arguments every call below starts with
 
-// The mesh arguments every entry point of the C ABI starts with (include/saamge_amd.h): NV vertices with dim coordinates each,
-// NE elements of nde nodes each or, elem_ptr not NULL, with the offsets elem_ptr into elem_to_vertex.  Host or device pointers.
-struct MeshArgs {
-    int NV, dim;
-    const double *coords;
-    int NE, nde;
-    const int *elem_ptr, *elem_to_vertex;
-};
+namespace saamge_amd {
 
 // The arguments of saamge_amd_element_matrices after the mesh.  The checks that need no device run before the first HIP call;
 // info is filled before a refusal for a non-positive Jacobian is thrown.  Every call below runs on s and returns with s idle.
@@ -82,29 +75,5 @@ void element_matrices_points(hipStream_t s, const MeshArgs &m, int kind, int nco
                              int *dof_ptr_out, int *elem_to_dof_out, long long info[8]);
 void element_mass_points(hipStream_t s, const MeshArgs &m, int vdim, const double *coefq, int accumulate, double *elmat_inout,
                          long long info[8]);
-
-// A mesh argument brought to the device and checked: what every call of elmat.hip and of mesh_faces.hip starts with.  elem_ptr
-// NULL: NE elements of nde nodes each.  Host arrays are uploaded (the offsets first: they say how much of elem_to_vertex there
-// is), device arrays are used where they are.  Refused with `name` in front or by check_mesh_device: malformed offsets, a vertex
-// id outside [0, NV) -- before any kernel reads through the ids --, a vertex listed twice in an element.  NE > 0.
-struct DeviceMesh {
-    DBuf<int> hold_I, hold_J;
-    const int *eI = nullptr, *eJ = nullptr;      // NE + 1 offsets, the flat vertex lists
-    long nconn = 0;                              // eI[NE]
-};
-void import_mesh(hipStream_t s, const std::string &name, int NV, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex,
-                 DeviceMesh &M);
-
-// The checks of a face list, shared by the boundary forms and the face-list calls of mesh_faces.hip.  The mesh (NE > 0
-// elements, offsets eI on the device) has been checked.  Refused with `name` in front: the first face (lowest index) with
-// face_elem outside [0, NE) or face_local outside the range of the element's type, then the first face whose (element, local
-// face) the list holds more than once; *refused (may be NULL) gets that index.  face_elem / face_local: host or device pointers.
-struct FaceList {
-    DBuf<int> hold_fe, hold_fl, key;      // key[f] = type * 8 + local face (em_type_index)
-    const int *fe = nullptr, *fl = nullptr;      // the lists on the device
-    int touched = 0;                      // distinct elements of the list
-};
-void check_face_list(hipStream_t s, const std::string &name, int dim, int NE, const int *eI, int NF, const int *face_elem,
-                     const int *face_local, FaceList &L, long long *refused);
 
 }  // namespace saamge_amd

@@ -51,7 +51,6 @@
 #include <vector>
 
 #include "operator.h"
-#include "partition.h"
 
 // every rounding of the model is one IEEE operation: no product is fused with the sum that follows it, anywhere in this file
 #pragma clang fp contract(off)
@@ -90,8 +89,6 @@ constexpr int em_block(int dim, int nd, int kind) {
     const int size = nd * (kind ? dim : 1);
     return (256 / nd) * size * size * 8 <= 40960 ? 256 : 64;
 }
-
-inline dim3 grid_flat(long n) { return dim3((unsigned)std::max<long>(1, (n + 255) / 256)); }
 
 // ---- pieces the kernels share (a piece is shared only where the kernel's gfx950 body stays the parent's) ------
 // the cofactors C[i][j] of J[i][j] and the determinant (elmat_model._cofactors), in the statement order of em_kernel and em2_body:
@@ -1145,35 +1142,7 @@ constexpr int bdr_face_type(int dim, int fn) { return dim == 2 ? fn - 2 : (fn ==
 constexpr int BDR_BLOCK = 256;
 constexpr int bdr_fpb(int fn) { return fn == 9 ? 5 : (fn == 4 ? 16 : 32); }      // faces per workgroup
 
-// The checks of the face list.  Face f with face_elem outside [0, NE) or face_local outside the range of the element's type:
-// key[f] = -1 and f to the integer minimum words[0]; else key[f] = type * 8 + local face, and the face's bit is set in the byte
-// of its element (mask: one byte per element, four to a word) -- a bit that was already set raises words[1].
-__global__ __launch_bounds__(256) void bdr_check_kernel(int NF, int NE, int dim, const int *__restrict__ eI,
-                                                        const int *__restrict__ face_elem, const int *__restrict__ face_local,
-                                                        unsigned *__restrict__ mask, int *__restrict__ key, int *__restrict__ words) {
-    const long f = (long)blockIdx.x * 256 + threadIdx.x;
-    if (f >= NF) return;
-    const int e = face_elem[f], lf = face_local[f];
-    int k = -1;
-    if (e >= 0 && e < NE) {
-        const int t = em_type_index(dim, eI[e + 1] - eI[e]);      // (the mesh has been checked: t >= 0)
-        if (t >= 0 && lf >= 0 && lf < bdr_num_faces(t)) {
-            k = t * 8 + lf;
-            const unsigned bit = 1u << (8 * (e & 3) + lf);
-            if (atomicOr(mask + (e >> 2), bit) & bit) atomicOr(words + 1, 1);
-        }
-    }
-    key[f] = k;
-    if (k < 0) atomicMin(words, (int)f);
-}
-// the number of elements whose byte of the mask is not zero, added to *count
-__global__ __launch_bounds__(256) void bdr_touched_kernel(int nwords, const unsigned *__restrict__ mask, int *__restrict__ count) {
-    const long w = (long)blockIdx.x * 256 + threadIdx.x;
-    if (w >= nwords) return;
-    const unsigned m = mask[w];
-    const int n = ((m & 0xffu) != 0) + ((m & 0xff00u) != 0) + ((m & 0xff0000u) != 0) + ((m & 0xff000000u) != 0);
-    if (n) atomicAdd(count, n);
-}
+// (the checks of a face list: check_face_list, mesh.hip)
 
 // Phases of both kernels, a barrier after each:
 //   stage   one lane per (face, face node): the node's coordinates (and g) into LDS; the face's element, coefficient, offsets
@@ -1556,10 +1525,6 @@ __global__ __launch_bounds__(BDR_BLOCK) void bdr_eval_kernel(int count, const in
 }
 
 // ---- tables ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void em_offsets_kernel(int NE, int nd, int *__restrict__ eI) {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e <= NE) eI[e] = (int)(e * nd);
-}
 // type of every element (-1: none, and the smallest such element in *first) and the size of its matrix
 __global__ __launch_bounds__(256) void em_classify_kernel(int NE, int dim, int comp, const int *__restrict__ eI,
                                                           int *__restrict__ cls, int *__restrict__ sq, int *__restrict__ first) {
@@ -1720,24 +1685,7 @@ void bdr_launch_face(BdrCall call, const EmLaunch &L, const BdrLaunch &B, int di
 }
 
 // ---- what the entry points share ------------------------------------------------------------------------------------------
-// the checks that need no device: info as a call without elements leaves it, the dimension and the counts ...
-void em_begin(const std::string &name, const MeshArgs &m, long long info[8]) {
-    if (info) {
-        for (int k = 0; k < 8; ++k) info[k] = 0;
-        info[6] = -1;
-    }
-    SA_REQUIRE(m.dim == 2 || m.dim == 3, name + "dim must be 2 or 3");
-    SA_REQUIRE(m.NV >= 0 && m.NE >= 0, name + "NV < 0 or NE < 0");
-}
-// ... and the sizes; comp: dofs per node
-void em_check_sizes(const std::string &name, const MeshArgs &m, int comp) {
-    SA_REQUIRE((int64_t)m.NV * comp <= INT_MAX, name + "dim * NV beyond 32 bits");
-    if (!m.elem_ptr) {
-        SA_REQUIRE(em_type_index(m.dim, m.nde) >= 0, name + "nde = " + std::to_string(m.nde) +
-                                                         " nodes are no supported element type in " + std::to_string(m.dim) + "D");
-        SA_REQUIRE((int64_t)m.NE * m.nde * comp <= INT_MAX, name + "NE * nde beyond 32 bits");
-    }
-}
+// (the checks that need no device: mesh_begin, then the call's own, then mesh_check_sizes -- mesh.h)
 
 // the mesh on the device, checked; the elements of every type; square: the offsets of the packed matrices
 struct EmMesh : DeviceMesh {
@@ -1748,7 +1696,7 @@ struct EmMesh : DeviceMesh {
 };
 void em_mesh(hipStream_t s, const std::string &name, const MeshArgs &m, int comp, bool square, EmMesh &M, long long info[8]) {
     const int dim = m.dim, NE = m.NE, nde = m.nde;
-    import_mesh(s, name, m.NV, NE, nde, m.elem_ptr, m.elem_to_vertex, M);
+    import_mesh(s, name, m, M);
     SA_REQUIRE((int64_t)M.nconn * comp <= INT_MAX, name + "dim * elem_ptr[NE] beyond 32 bits");
     // ---- types, lists, offsets of the packed matrices
     M.word.alloc(1);
@@ -1757,11 +1705,7 @@ void em_mesh(hipStream_t s, const std::string &name, const MeshArgs &m, int comp
         SA_HIP_CHECK(hipMemsetAsync(M.word.p, 0x7f, sizeof(int), s));
         em_run(em_classify_kernel, s, div_up(NE, 256), 256, NE, dim, comp, M.eI, cls.p, sq.p, M.word.p);
         const int first = read_one(M.word.p, s);
-        if (first < NE) {
-            const int nd = read_one(M.eI + first + 1, s) - read_one(M.eI + first, s);
-            SA_REQUIRE(false, name + "element " + std::to_string(first) + ": " + std::to_string(nd) +
-                                  " nodes are no supported element type in " + std::to_string(dim) + "D");
-        }
+        if (first < NE) refuse_element_type(s, name, dim, M.eI, first);
         flag.alloc((size_t)NE);
         pos.alloc((size_t)NE + 1);
         for (int t = 0; t < EM_TYPES; ++t)
@@ -1897,7 +1841,7 @@ void stiffness(hipStream_t s, const std::string &name, bool at_points, const Mes
                double *elmat_out, int *dof_ptr_out, int *elem_to_dof_out, long long info[8]) {
     const int dim = m.dim, NE = m.NE;
     // ---- what needs no device
-    em_begin(name, m, info);
+    mesh_begin(name, m, info);
     SA_REQUIRE(kind == 0 || kind == 1, name + "kind must be 0 (diffusion) or 1 (elasticity)");
     if (kind == 1)
         SA_REQUIRE(ncoef == 2, name + "ncoef must be 2 (lambda, mu) for elasticity");
@@ -1907,7 +1851,7 @@ void stiffness(hipStream_t s, const std::string &name, bool at_points, const Mes
     SA_REQUIRE(NE == 0 || (m.coords && m.elem_to_vertex && coef),
                name + "null argument: coords, elem_to_vertex or " + (at_points ? "coefq" : "coef"));
     const int comp = kind ? dim : 1;
-    em_check_sizes(name, m, comp);
+    mesh_check_sizes(name, m, comp, false);
     if (NE == 0) return;
     // ---- the matrices (elmat_out NULL: the determinants are still checked)
     EmFrame F(s, name, m, info);
@@ -1954,12 +1898,12 @@ void mass_or_loads(hipStream_t s, const std::string &name, const MeshArgs &m, in
 // saamge_amd_element_mass and, at_points, saamge_amd_element_mass_points (coef_name: what the C ABI calls the coefficients)
 void mass_entry(hipStream_t s, const std::string &name, bool at_points, const char *coef_name, const MeshArgs &m, int vdim,
                 const double *coef, int accumulate, double *elmat_inout, long long info[8]) {
-    em_begin(name, m, info);
+    mesh_begin(name, m, info);
     SA_REQUIRE(vdim == 1 || vdim == m.dim, name + "vdim must be 1 or dim");
     SA_REQUIRE(m.NE == 0 || coef, name + "null argument: " + coef_name);
     SA_REQUIRE(m.NE == 0 || (m.coords && m.elem_to_vertex), name + "null argument: coords or elem_to_vertex");
     SA_REQUIRE(!accumulate || elmat_inout, name + "null argument: accumulate needs the matrices in elmat_inout");
-    em_check_sizes(name, m, vdim);
+    mesh_check_sizes(name, m, vdim, false);
     mass_or_loads(s, name, m, vdim, coef, nullptr, accumulate ? 1 : 0, elmat_inout, info, at_points);
 }
 
@@ -1969,10 +1913,10 @@ void points_call(QpCall call, hipStream_t s, const std::string &name, const Mesh
                  const double *in, const char *in_name, const double *exq, const double *exgradq, long long *qp_ptr_out, double *out_a,
                  double *out_b, long long info[8]) {
     const int dim = m.dim, NE = m.NE;
-    em_begin(name, m, info);
+    mesh_begin(name, m, info);
     SA_REQUIRE(vdim == 1 || vdim == dim, name + "vdim must be 1 or dim");
     SA_REQUIRE(NE == 0 || (m.coords && m.elem_to_vertex), name + "null argument: coords or elem_to_vertex");
-    em_check_sizes(name, m, vdim);
+    mesh_check_sizes(name, m, vdim, false);
     EmFrame F(s, name, m, info);
     if (NE) F.open(vdim, false);
     if (info) info[5] = 0;
@@ -2127,79 +2071,14 @@ void boundary_forms(BdrCall call, bool at_points, hipStream_t s, const std::stri
 // the checks of both entry points that need no device
 void bdr_begin(const std::string &name, const MeshArgs &m, int NF, const int *face_elem, const int *face_local, int vdim,
                long long info[8]) {
-    em_begin(name, m, info);
+    mesh_begin(name, m, info);
     SA_REQUIRE(NF >= 0, name + "NF < 0");
     SA_REQUIRE(vdim == 1 || vdim == m.dim, name + "vdim must be 1 or dim");
     SA_REQUIRE(NF == 0 || (face_elem && face_local), name + "null argument: face_elem or face_local");
     SA_REQUIRE(NF == 0 || m.NE == 0 || (m.coords && m.elem_to_vertex), name + "null argument: coords or elem_to_vertex");
-    em_check_sizes(name, m, vdim);
+    mesh_check_sizes(name, m, vdim, false);
 }
 }  // namespace
-
-// The mesh argument of every call of this file and of mesh_faces.hip (elmat.h)
-void import_mesh(hipStream_t s, const std::string &name, int NV, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex,
-                 DeviceMesh &M) {
-    // ---- the mesh: offsets first, they say how much of elem_to_vertex there is
-    if (elem_ptr) {
-        M.eI = device_view(M.hold_I, elem_ptr, (size_t)NE + 1, s);
-    } else {
-        M.hold_I.alloc((size_t)NE + 1);
-        hipLaunchKernelGGL(em_offsets_kernel, grid_flat((long)NE + 1), dim3(256), 0, s, NE, nde, M.hold_I.p);
-        SA_HIP_CHECK(hipGetLastError());
-        M.eI = M.hold_I.p;
-    }
-    M.eJ = elem_to_vertex;
-    if (!is_device_ptr(elem_to_vertex)) {
-        long total = (long)NE * nde;
-        if (elem_ptr) {
-            const hvec<int> hI = fetch_host(M.eI, (size_t)NE + 1, s);
-            for (int e = 0; e < NE; ++e)
-                SA_REQUIRE(hI[0] == 0 && hI[(size_t)e + 1] > hI[(size_t)e], name + "elem_ptr: must start at 0 and every element needs a vertex");
-            total = hI[(size_t)NE];
-        }
-        upload(M.hold_J, elem_to_vertex, (size_t)total, s);
-        M.eJ = M.hold_J.p;
-    }
-    M.nconn = check_mesh_device(s, NE, M.eI, M.eJ, NV);      // offsets, vertex ids in [0, NV), no vertex twice in an element
-}
-
-// The checks of a face list (elmat.h): shared by the boundary forms and the face-list calls of mesh_faces.hip.
-void check_face_list(hipStream_t s, const std::string &name, int dim, int NE, const int *eI, int NF, const int *face_elem,
-                     const int *face_local, FaceList &L, long long *refused) {
-    L.key.alloc((size_t)NF);
-    DBuf<int> words(3);
-    const int *fe = L.fe = device_view(L.hold_fe, face_elem, (size_t)NF, s);
-    const int *fl = L.fl = device_view(L.hold_fl, face_local, (size_t)NF, s);
-    const int nwords = (int)(((int64_t)NE + 3) / 4);
-    DBuf<unsigned> mask((size_t)nwords);
-    mask.zero(s);
-    const int init[3] = {INT_MAX, 0, 0};
-    SA_HIP_CHECK(hipMemcpyAsync(words.p, init, sizeof(init), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(bdr_check_kernel, grid_flat(NF), dim3(256), 0, s, NF, NE, dim, eI, fe, fl, mask.p, L.key.p, words.p);
-    SA_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(bdr_touched_kernel, grid_flat(nwords), dim3(256), 0, s, nwords, (const unsigned *)mask.p, words.p + 2);
-    SA_HIP_CHECK(hipGetLastError());
-    int w[3];
-    read_back(w, (const int *)words.p, 3, s);
-    if (w[0] < NF) {
-        if (refused) *refused = w[0];
-        const int e = read_one(fe + w[0], s);
-        SA_REQUIRE(false, name + "face " + std::to_string(w[0]) + ": " +
-                              (e < 0 || e >= NE ? "face_elem is outside [0, NE)" : "face_local is outside the element type's range"));
-    }
-    if (w[1]) {      // a pair is listed twice: the first face of the list that is one of a repeated pair, found on the host
-        const hvec<int> he = fetch_host(fe, (size_t)NF, s), hl = fetch_host(fl, (size_t)NF, s);
-        std::vector<std::pair<int64_t, int>> pairs((size_t)NF);
-        for (int f = 0; f < NF; ++f) pairs[(size_t)f] = {(int64_t)he[(size_t)f] * 8 + hl[(size_t)f], f};
-        std::sort(pairs.begin(), pairs.end());
-        int first = NF;
-        for (size_t k = 0; k + 1 < pairs.size(); ++k)
-            if (pairs[k].first == pairs[k + 1].first && (k == 0 || pairs[k - 1].first != pairs[k].first)) first = std::min(first, pairs[k].second);
-        if (refused) *refused = first;
-        SA_REQUIRE(false, name + "face " + std::to_string(first) + ": the same (element, local face) is listed twice");
-    }
-    L.touched = w[2];
-}
 
 // ---- the entry points (elmat.h) -----------------------------------------------------------------------------------------------
 void element_matrices(hipStream_t s, const MeshArgs &m, int kind, int ncoef, const double *coef, double *elmat_out, int *dof_ptr_out,
@@ -2223,11 +2102,11 @@ void element_mass_points(hipStream_t s, const MeshArgs &m, int vdim, const doubl
 void element_loads(hipStream_t s, const MeshArgs &m, int vdim, const double *coef, const double *src, double *elvec_out,
                    long long info[8]) {
     const std::string name("saamge_amd_element_loads: ");
-    em_begin(name, m, info);
+    mesh_begin(name, m, info);
     SA_REQUIRE(vdim == 1 || vdim == m.dim, name + "vdim must be 1 or dim");
     SA_REQUIRE(src, name + "null argument: src");
     SA_REQUIRE(m.NE == 0 || (m.coords && m.elem_to_vertex), name + "null argument: coords or elem_to_vertex");
-    em_check_sizes(name, m, vdim);
+    mesh_check_sizes(name, m, vdim, false);
     mass_or_loads(s, name, m, vdim, coef, src, 0, elvec_out, info);
 }
 

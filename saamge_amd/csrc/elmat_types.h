@@ -1,11 +1,14 @@
 // The element types and their local faces (elmat_model.py: ALL_TYPE_INDEX, FACE_NODES), folded at compile time: shared by the
-// element layer (elmat.hip) and the face table (mesh_faces.hip).
+// element layer (elmat.hip) and the mesh layer (mesh_faces.hip, mesh_lift.hip, mesh_refine.hip).
 #pragma once
 
 namespace saamge_amd {
 
 constexpr int EM_HEX_LOC[8][3] = {{0, 0, 0}, {1, 0, 0}, {1, 1, 0}, {0, 1, 0}, {0, 0, 1}, {1, 0, 1}, {1, 1, 1}, {0, 1, 1}};
 constexpr int EM2_QUAD_LOC[9][2] = {{0, 0}, {2, 0}, {2, 2}, {0, 2}, {1, 0}, {2, 1}, {1, 2}, {0, 1}, {1, 1}};
+// the 27-node hexahedron is lexicographic: the node at reference position (x, y, z) in {0, 1, 2}^3; corner j is HEX_LOC[j] doubled
+constexpr int em_hex27_node(int x, int y, int z) { return (z * 3 + y) * 3 + x; }
+constexpr int em_hex27_corner(int j) { return em_hex27_node(2 * EM_HEX_LOC[j][0], 2 * EM_HEX_LOC[j][1], 2 * EM_HEX_LOC[j][2]); }
 
 // types 0 .. 4: order 1 (info[0 .. 4]); 5, 6: the order-2 quadrilateral and hexahedron; 7, 8: the order-2 triangle (6 nodes)
 // and tetrahedron (10 nodes); info[7] counts all four
@@ -51,7 +54,7 @@ constexpr BdrFace bdr_face(int type, int lf) {
             for (int d = 0; d < 3; ++d)
                 p[d] = 2 * EM_HEX_LOC[c[0]][d] + EM2_QUAD_LOC[k][0] * (EM_HEX_LOC[c[1]][d] - EM_HEX_LOC[c[0]][d]) +
                        EM2_QUAD_LOC[k][1] * (EM_HEX_LOC[c[3]][d] - EM_HEX_LOC[c[0]][d]);
-            f.node[k] = (p[2] * 3 + p[1]) * 3 + p[0];
+            f.node[k] = em_hex27_node(p[0], p[1], p[2]);
         }
     }
     return f;

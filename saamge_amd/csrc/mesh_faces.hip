@@ -13,14 +13,13 @@
 //   mf_rows_kernel    one lane per element, twice (count, then fill after two scans over the elements, which is slot order):
 //                     the boundary faces of the element in ascending local face, and its distinct neighbours sorted by a fixed
 //                     network over its at most 6 slots.  No appended lists; the only atomics are integer counters and minima.
-// The face-list calls (face_nodes, face_dofs) share the checks of the boundary forms (check_face_list, elmat.hip).
+// The face-list calls (face_nodes, face_dofs) share the checks of the boundary forms (check_face_list, mesh.hip).
 #include "mesh_faces.h"
 
 #include <algorithm>
 #include <climits>
 
-#include "elmat.h"
-#include "elmat_types.h"
+#include "mesh.h"
 #include "operator.h"      // upload
 
 namespace saamge_amd {
@@ -33,8 +32,6 @@ __global__ void d2e_fill_kernel(int NE, const int *__restrict__ e2d_I, const int
 namespace {
 
 typedef unsigned long long u64;
-
-inline dim3 grid_flat(long n) { return dim3((unsigned)std::max<long>(1, (n + 255) / 256)); }
 
 // ---- the tables of mesh_model.py, folded from FACE_NODES (elmat_types.h) ----------------------------------------------------
 struct MfTables {
@@ -54,8 +51,7 @@ constexpr MfTables mf_tables() {
     for (int ty = 0; ty < EM_TYPES; ++ty) {
         t.nfaces[ty] = bdr_num_faces(ty);
         t.ncn[ty] = NCN[ty];
-        for (int j = 0; j < NCN[ty]; ++j)      // the 27-node hexahedron is lexicographic: corner HEX_LOC[j] doubled
-            t.corner_node[ty][j] = ty == 6 ? (2 * EM_HEX_LOC[j][2] * 3 + 2 * EM_HEX_LOC[j][1]) * 3 + 2 * EM_HEX_LOC[j][0] : j;
+        for (int j = 0; j < NCN[ty]; ++j) t.corner_node[ty][j] = ty == 6 ? em_hex27_corner(j) : j;
         for (int lf = 0; lf < t.nfaces[ty]; ++lf) {
             const BdrFace f = bdr_face(ty, lf);
             const int fn = BDR_FACE_NODES[ty][lf];
@@ -93,21 +89,14 @@ constexpr MfTables MF_HOST = mf_tables();
 // without a neighbour, [3] the largest number of elements at one vertex
 constexpr int MF_WORDS = 4;
 
-// the number of local faces of every element; an element of no type goes to the minimum *first
-__global__ __launch_bounds__(256) void mf_classify_kernel(int NE, int dim, const int *__restrict__ eI, int *__restrict__ nfaces,
-                                                          int *__restrict__ first) {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= NE) return;
-    const int t = em_type_index(dim, eI[e + 1] - eI[e]);
-    nfaces[e] = t < 0 ? 0 : MF.nfaces[t];
-    if (t < 0) atomicMin(first, (int)e);
-}
-// the maximum of cnt[0 .. n) into *out (which only grows: a stale read costs an atomic, never the result)
+// what mesh_classify_kernel keeps per element: the number of its local faces
+struct MfFaceCount {
+    __device__ int operator()(int t, int) const { return t < 0 ? 0 : MF.nfaces[t]; }
+};
+// the maximum of cnt[0 .. n) into *out
 __global__ __launch_bounds__(256) void mf_max_kernel(int n, const int *__restrict__ cnt, int *__restrict__ out) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int c = cnt[i];
-    if (c > *(volatile int *)out) atomicMax(out, c);
+    if (i < n) raise_max(out, cnt[i]);
 }
 
 // One lane per slot: lane t is local face t % stride of element t / stride (stride: the most faces an element of this mesh can
@@ -251,58 +240,28 @@ __global__ __launch_bounds__(256) void mf_face_dofs_kernel(int NF, const int *__
     if (changed) atomicAdd(counts + 1, (u64)changed);
 }
 
-// ---- the mesh: on the device, checked, with the number of faces of every element -------------------------------------------------
-struct MfMesh : DeviceMesh {
-    DBuf<int> nfaces;
-    int stride = 0;      // the most faces an element of the mesh can have
-};
-// the checks of the mesh arguments that need no device
-void mf_begin(const std::string &name, int NV, int dim, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex, bool used) {
-    SA_REQUIRE(dim == 2 || dim == 3, name + "dim must be 2 or 3");
-    SA_REQUIRE(NV >= 0 && NE >= 0, name + "NV < 0 or NE < 0");
-    SA_REQUIRE(!used || NE == 0 || elem_to_vertex, name + "null argument: elem_to_vertex");
-    if (!elem_ptr) {
-        SA_REQUIRE(em_type_index(dim, nde) >= 0,
-                   name + "nde = " + std::to_string(nde) + " nodes are no supported element type in " + std::to_string(dim) + "D");
-        SA_REQUIRE((int64_t)NE * nde <= INT_MAX, name + "NE * nde beyond 32 bits");
-    }
-}
-void mf_mesh(hipStream_t s, const std::string &name, int NV, int dim, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex,
-             MfMesh &M) {
-    import_mesh(s, name, NV, NE, nde, elem_ptr, elem_to_vertex, M);
-    M.nfaces.alloc((size_t)NE);
-    DBuf<int> word(1);
-    SA_HIP_CHECK(hipMemsetAsync(word.p, 0x7f, sizeof(int), s));
-    hipLaunchKernelGGL(mf_classify_kernel, grid_flat(NE), dim3(256), 0, s, NE, dim, M.eI, M.nfaces.p, word.p);
-    SA_HIP_CHECK(hipGetLastError());
-    const int first = read_one((const int *)word.p, s);
-    if (first < NE) {
-        const int nd = read_one(M.eI + first + 1, s) - read_one(M.eI + first, s);
-        SA_REQUIRE(false, name + "element " + std::to_string(first) + ": " + std::to_string(nd) +
-                              " nodes are no supported element type in " + std::to_string(dim) + "D");
-    }
-    M.stride = elem_ptr ? (dim == 2 ? 4 : BDR_MAX_FACES) : MF_HOST.nfaces[em_type_index(dim, nde)];
+// ---- the mesh: on the device, checked, with the number of faces of every element (ClassifiedMesh::count) ----------------------
+void mf_mesh(hipStream_t s, const std::string &name, const MeshArgs &m, ClassifiedMesh &M) {
+    classified_mesh(s, name, m, M, MfFaceCount());
+    M.stride = m.elem_ptr ? (m.dim == 2 ? 4 : BDR_MAX_FACES) : MF_HOST.nfaces[em_type_index(m.dim, m.nde)];      // the most faces
 }
 
-// what face_nodes and face_dofs share: the checks without a device, the mesh, the face list
-void mf_face_begin(const std::string &name, int NV, int dim, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex, int NF,
-                   const int *face_elem, const int *face_local) {
-    SA_REQUIRE(dim == 2 || dim == 3, name + "dim must be 2 or 3");
+// what face_nodes and face_dofs share: the checks without a device of the mesh and of the face list
+void mf_face_begin(const std::string &name, const MeshArgs &m, int NF, const int *face_elem, const int *face_local) {
+    SA_REQUIRE(m.dim == 2 || m.dim == 3, name + "dim must be 2 or 3");
     SA_REQUIRE(NF >= 0, name + "NF < 0");
     SA_REQUIRE(NF == 0 || (face_elem && face_local), name + "null argument: face_elem or face_local");
-    mf_begin(name, NV, dim, NE, nde, elem_ptr, elem_to_vertex, NF > 0);
+    mesh_begin(name, m, nullptr);
+    mesh_check_sizes(name, m, 0, NF > 0);      // (elem_to_vertex may be NULL when there is nothing to read)
 }
 
 }  // namespace
 
-void face_table_build(hipStream_t s, int NV, int dim, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex, FaceTable &T,
-                      long long info[8]) {
+void face_table_build(hipStream_t s, const MeshArgs &m, FaceTable &T, long long info[8]) {
     const std::string name("saamge_amd_face_table_build: ");
-    if (info) {
-        for (int k = 0; k < 8; ++k) info[k] = 0;
-        info[6] = -1;
-    }
-    mf_begin(name, NV, dim, NE, nde, elem_ptr, elem_to_vertex, true);
+    const int NV = m.NV, dim = m.dim, NE = m.NE;
+    mesh_begin(name, m, info);
+    mesh_check_sizes(name, m, 0, true);
     T.device = current_device();
     T.NE = NE;
     T.slot_ptr.alloc((size_t)NE + 1);
@@ -313,9 +272,9 @@ void face_table_build(hipStream_t s, int NV, int dim, int NE, int nde, const int
         SA_HIP_CHECK(hipStreamSynchronize(s));
         return;
     }
-    MfMesh M;
-    mf_mesh(s, name, NV, dim, NE, nde, elem_ptr, elem_to_vertex, M);
-    exclusive_scan_off(s, NE, M.nfaces.p, T.slot_ptr.p);
+    ClassifiedMesh M;
+    mf_mesh(s, name, m, M);
+    exclusive_scan_off(s, NE, M.count.p, T.slot_ptr.p);
     const roff_t slots = read_one((const roff_t *)T.slot_ptr.p + NE, s);
     // ---- the elements at every vertex
     DBuf<int> v2e_I((size_t)NV + 1), v2e_J((size_t)M.nconn), cnt((size_t)NV), words(MF_WORDS);
@@ -375,15 +334,16 @@ void face_table_build(hipStream_t s, int NV, int dim, int NE, int nde, const int
     }
 }
 
-void face_nodes(hipStream_t s, int NV, int dim, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex, int NF,
-                const int *face_elem, const int *face_local, int *face_ptr_out, int *face_nodes_out, long long *count_out) {
+void face_nodes(hipStream_t s, const MeshArgs &m, int NF, const int *face_elem, const int *face_local, int *face_ptr_out,
+                int *face_nodes_out, long long *count_out) {
     const std::string name("saamge_amd_face_nodes: ");
+    const int dim = m.dim, NE = m.NE;
     if (count_out) *count_out = 0;
-    mf_face_begin(name, NV, dim, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local);
+    mf_face_begin(name, m, NF, face_elem, face_local);
     if (NF == 0) return;
     SA_REQUIRE(NE > 0, name + "face 0: face_elem is outside [0, NE)");
-    MfMesh M;
-    mf_mesh(s, name, NV, dim, NE, nde, elem_ptr, elem_to_vertex, M);
+    ClassifiedMesh M;
+    mf_mesh(s, name, m, M);
     FaceList L;
     check_face_list(s, name, dim, NE, M.eI, NF, face_elem, face_local, L, nullptr);
     DBuf<int> fn((size_t)NF), fptr((size_t)NF + 1);
@@ -409,15 +369,15 @@ void face_nodes(hipStream_t s, int NV, int dim, int NE, int nde, const int *elem
     SA_HIP_CHECK(hipStreamSynchronize(s));
 }
 
-void face_dofs(hipStream_t s, int NV, int dim, int NE, int nde, const int *elem_ptr, const int *elem_to_vertex, int NF,
-               const int *face_elem, const int *face_local, int vdim, unsigned comp_mask, int flag, signed char *bdr_dofs_inout,
-               long long info[4]) {
+void face_dofs(hipStream_t s, const MeshArgs &m, int NF, const int *face_elem, const int *face_local, int vdim, unsigned comp_mask,
+               int flag, signed char *bdr_dofs_inout, long long info[4]) {
     const std::string name("saamge_amd_face_dofs: ");
+    const int NV = m.NV, dim = m.dim, NE = m.NE;
     if (info) {
         info[0] = info[1] = info[2] = 0;
         info[3] = -1;
     }
-    mf_face_begin(name, NV, dim, NE, nde, elem_ptr, elem_to_vertex, NF, face_elem, face_local);
+    mf_face_begin(name, m, NF, face_elem, face_local);
     SA_REQUIRE(vdim == 1 || vdim == dim, name + "vdim must be 1 or dim");
     SA_REQUIRE(comp_mask >= 1u && comp_mask < (1u << vdim), name + "comp_mask must lie in 1 .. 2^vdim - 1");
     SA_REQUIRE(flag >= 1 && flag <= 127, name + "flag must lie in 1 .. 127");
@@ -426,8 +386,8 @@ void face_dofs(hipStream_t s, int NV, int dim, int NE, int nde, const int *elem_
     if (NF == 0) return;
     if (NE == 0 && info) info[3] = 0;
     SA_REQUIRE(NE > 0, name + "face 0: face_elem is outside [0, NE)");
-    MfMesh M;
-    mf_mesh(s, name, NV, dim, NE, nde, elem_ptr, elem_to_vertex, M);
+    ClassifiedMesh M;
+    mf_mesh(s, name, m, M);
     FaceList L;
     check_face_list(s, name, dim, NE, M.eI, NF, face_elem, face_local, L, info ? info + 3 : nullptr);
     const size_t bytes = (size_t)NV * vdim;

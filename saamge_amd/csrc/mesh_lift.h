@@ -22,7 +22,6 @@ struct MeshLift {
 // The arguments of saamge_amd_mesh_lift_order2; faces NULL: the face table is built inside where the mesh has a hexahedron.
 // The checks that need no device run before the first HIP call; the vertex ids are checked before any kernel reads through
 // them.  Runs on s and returns with s idle.
-void mesh_lift_order2(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
-                      const int *elem_to_vertex, const FaceTable *faces, MeshLift &L, long long info[8]);
+void mesh_lift_order2(hipStream_t s, const MeshArgs &m, const FaceTable *faces, MeshLift &L, long long info[8]);
 
 }  // namespace saamge_amd

@@ -23,15 +23,12 @@
 #include <algorithm>
 #include <climits>
 
-#include "elmat.h"
-#include "elmat_types.h"
+#include "mesh.h"
 #include "operator.h"      // device_view
 
 namespace saamge_amd {
 
 namespace {
-
-inline dim3 grid_flat(long n) { return dim3((unsigned)std::max<long>(1, (n + 255) / 256)); }
 
 // ---- the tables of mesh_lift_model.py: LOCAL_EDGES and, per local node of the lifted element, what it is ---------------------------
 constexpr int ML_MAX_EDGES = 12, ML_MAX_ND2 = 27;
@@ -116,18 +113,17 @@ constexpr MlTables ML_HOST = ml_tables();
 // face table are not those of its type (minima), [3] the most edges one vertex owns
 constexpr int ML_WORDS = 4;
 
-// the nodes of every lifted element and whether it has a centre node; an element of no type / without a lift goes to a minimum
-__global__ __launch_bounds__(256) void ml_classify_kernel(int NE, int dim, const int *__restrict__ eI, int *__restrict__ nd2,
-                                                          int *__restrict__ centre, int *__restrict__ words) {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= NE) return;
-    const int t = em_type_index(dim, eI[e + 1] - eI[e]);
-    const int n2 = t < 0 ? 0 : ML.nd2[t];
-    nd2[e] = n2;
-    centre[e] = (int)(t == 1 || t == 4);
-    if (t < 0) atomicMin(words, (int)e);
-    else if (n2 == 0) atomicMin(words + 1, (int)e);
-}
+// what mesh_classify_kernel keeps per element: the nodes of the lifted element and whether it has a centre node; an element
+// without a lift goes to the minimum *no_lift
+struct MlLiftedNodes {
+    int *centre, *no_lift;
+    __device__ int operator()(int t, int e) const {
+        const int n2 = t < 0 ? 0 : ML.nd2[t];
+        centre[e] = (int)(t == 1 || t == 4);
+        if (t >= 0 && n2 == 0) atomicMin(no_lift, e);
+        return n2;
+    }
+};
 // a face table handed in: every element has the slots of its type
 __global__ __launch_bounds__(256) void ml_fits_kernel(int NE, int dim, const int *__restrict__ eI, const roff_t *__restrict__ slot_ptr,
                                                       int *__restrict__ words) {
@@ -206,7 +202,7 @@ __global__ __launch_bounds__(256) void ml_sort_kernel(int NV, const roff_t *__re
         prev = x;
     }
     owned[v] = (int)w;
-    if ((int)w > *(volatile int *)(words + 3)) atomicMax(words + 3, (int)w);
+    raise_max(words + 3, (int)w);
 }
 __global__ __launch_bounds__(256) void ml_edge_hi_kernel(int NV, const roff_t *__restrict__ raw_ptr, const int *__restrict__ raw,
                                                          const roff_t *__restrict__ edge_ptr, int *__restrict__ edge_hi) {
@@ -227,9 +223,7 @@ __global__ __launch_bounds__(256) void ml_face_flag_kernel(long total, int dim, 
     const roff_t s0 = slot_ptr[e];
     if (lf >= (int)(slot_ptr[e + 1] - s0)) return;
     const roff_t s = s0 + lf;
-    const int ne = nbr_elem[s];
-    const roff_t other = ne < 0 ? s : slot_ptr[ne] + nbr_local[s];
-    flag[s] = (int)(em_type_index(dim, eI[e + 1] - eI[e]) == 4 && other >= s);
+    flag[s] = (int)(em_type_index(dim, eI[e + 1] - eI[e]) == 4 && opposite_slot(slot_ptr, nbr_elem, nbr_local, s) >= s);
 }
 __global__ __launch_bounds__(256) void ml_face_slot_kernel(long slots, const int *__restrict__ flag, const roff_t *__restrict__ rank,
                                                            roff_t *__restrict__ face_slot) {
@@ -237,11 +231,6 @@ __global__ __launch_bounds__(256) void ml_face_slot_kernel(long slots, const int
     if (s < slots && flag[s]) face_slot[rank[s]] = s;
 }
 
-__device__ inline void ml_order(int &x, int &y) {
-    const int lo = min(x, y), hi = max(x, y);
-    x = lo;
-    y = hi;
-}
 // One lane per (element, local node of the lifted element): lane t is node t % stride of element t / stride.  X2: all
 // coordinates, rows [0, NV) hold the vertices already; the lane writes the row of its own node (no row below NV).
 template <bool COORDS>
@@ -264,31 +253,19 @@ __global__ __launch_bounds__(256) void ml_nodes_kernel(long total, int stride, i
     } else if (kind == ML_EDGE) {
         const int v0 = eJ[b + ML.edge[type][arg][0]], v1 = eJ[b + ML.edge[type][arg][1]];
         const int a = min(v0, v1), hi = max(v0, v1);
-        roff_t lo = edge_ptr[a], up = edge_ptr[a + 1];                  // bisection for the last entry <= hi: the pair itself
-        while (up - lo > 1) {
-            const roff_t mid = lo + (up - lo) / 2;
-            if (edge_hi[mid] <= hi) lo = mid;
-            else up = mid;
-        }
-        node = (int)(NV + lo);
+        node = (int)(NV + last_le(edge_hi, edge_ptr[a], edge_ptr[a + 1], hi));      // the last entry <= hi: the pair itself
         if (COORDS)
             for (int d = 0; d < dim; ++d) X2[(long)node * dim + d] = 0.5 * (X2[(long)a * dim + d] + X2[(long)hi * dim + d]);
     } else if (kind == ML_FACE) {
         const roff_t s = slot_ptr[e] + arg;
-        const int ne = nbr_elem[s];
-        const roff_t other = ne < 0 ? s : slot_ptr[ne] + nbr_local[s];
-        node = (int)(NV + NEd + face_rank[min(s, other)]);
+        node = (int)(NV + NEd + face_rank[min(s, opposite_slot(slot_ptr, nbr_elem, nbr_local, s))]);
         if (COORDS) {
-            int v0 = eJ[b + BDR_HEX_FACES[arg][0]], v1 = eJ[b + BDR_HEX_FACES[arg][1]], v2 = eJ[b + BDR_HEX_FACES[arg][2]],
-                v3 = eJ[b + BDR_HEX_FACES[arg][3]];
-            ml_order(v0, v1);      // a fixed network of five exchanges
-            ml_order(v2, v3);
-            ml_order(v0, v2);
-            ml_order(v1, v3);
-            ml_order(v1, v2);
+            int v[4] = {eJ[b + BDR_HEX_FACES[arg][0]], eJ[b + BDR_HEX_FACES[arg][1]], eJ[b + BDR_HEX_FACES[arg][2]],
+                        eJ[b + BDR_HEX_FACES[arg][3]]};
+            sort4(v);
             for (int d = 0; d < dim; ++d)
-                X2[(long)node * dim + d] = 0.25 * ((X2[(long)v0 * dim + d] + X2[(long)v1 * dim + d]) +
-                                                   (X2[(long)v2 * dim + d] + X2[(long)v3 * dim + d]));
+                X2[(long)node * dim + d] = 0.25 * ((X2[(long)v[0] * dim + d] + X2[(long)v[1] * dim + d]) +
+                                                   (X2[(long)v[2] * dim + d] + X2[(long)v[3] * dim + d]));
         }
     } else {
         node = (int)(NV + NEd + NFq + centre_rank[e]);
@@ -310,22 +287,15 @@ __global__ __launch_bounds__(256) void ml_nodes_kernel(long total, int stride, i
 
 }  // namespace
 
-void mesh_lift_order2(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
-                      const int *elem_to_vertex, const FaceTable *faces, MeshLift &L, long long info[8]) {
+void mesh_lift_order2(hipStream_t s, const MeshArgs &m, const FaceTable *faces, MeshLift &L, long long info[8]) {
     const std::string name("saamge_amd_mesh_lift_order2: ");
-    if (info) {
-        for (int k = 0; k < 8; ++k) info[k] = 0;
-        info[6] = -1;
-    }
-    // ---- the checks that need no device
-    SA_REQUIRE(dim == 2 || dim == 3, name + "dim must be 2 or 3");
-    SA_REQUIRE(NV >= 0 && NE >= 0, name + "NV < 0 or NE < 0");
-    SA_REQUIRE(NE == 0 || elem_to_vertex, name + "null argument: elem_to_vertex");
-    if (!elem_ptr) {
-        const int t = em_type_index(dim, nde);
-        SA_REQUIRE(t >= 0, name + "nde = " + std::to_string(nde) + " nodes are no supported element type in " + std::to_string(dim) + "D");
-        SA_REQUIRE((int64_t)NE * std::max(nde, ML_HOST.nd2[t]) <= INT_MAX, name + "the element -> node lists are beyond 32 bits");
-    }
+    const int NV = m.NV, dim = m.dim, NE = m.NE, nde = m.nde;
+    const int *const elem_ptr = m.elem_ptr;
+    const double *const coords = m.coords;
+    // ---- the checks that need no device; the limit is the lift's own: the lifted lists are the longer ones
+    mesh_begin(name, m, info);
+    const int t1 = em_type_index(dim, nde);
+    mesh_check_sizes(name, m, 0, true, t1 < 0 ? 0 : ML_HOST.nd2[t1], "the element -> node lists are beyond 32 bits");
     SA_REQUIRE(!faces || faces->NE == NE, name + "faces: the face table does not fit the mesh (its number of elements)");
     L.device = current_device();
     SA_REQUIRE(!faces || faces->device == L.device, name + "faces: the face table lives on another device");
@@ -349,21 +319,19 @@ void mesh_lift_order2(hipStream_t s, int NV, int dim, const double *coords, int 
         return;
     }
     DeviceMesh M;
-    import_mesh(s, name, NV, NE, nde, elem_ptr, elem_to_vertex, M);
+    import_mesh(s, name, m, M);
     // ---- the type of every element
     DBuf<int> nd2((size_t)NE), centre((size_t)NE), words(ML_WORDS);
     const int init[ML_WORDS] = {INT_MAX, INT_MAX, INT_MAX, 0};
     SA_HIP_CHECK(hipMemcpyAsync(words.p, init, sizeof(init), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(ml_classify_kernel, grid_flat(NE), dim3(256), 0, s, NE, dim, M.eI, nd2.p, centre.p, words.p);
-    SA_HIP_CHECK(hipGetLastError());
+    mesh_classify(s, NE, dim, M.eI, nd2.p, words.p, MlLiftedNodes{centre.p, words.p + 1});
     int w[ML_WORDS];
     read_back(w, (const int *)words.p, ML_WORDS, s);
-    if (w[0] < NE || w[1] < NE) {
-        const int first = w[0] < NE ? w[0] : w[1];
-        const int nd = read_one(M.eI + first + 1, s) - read_one(M.eI + first, s);
-        const std::string which = name + "element " + std::to_string(first) + ": ";
-        SA_REQUIRE(w[0] >= NE, which + std::to_string(nd) + " nodes are no supported element type in " + std::to_string(dim) + "D");
-        if (info) info[6] = first;
+    if (w[0] < NE) refuse_element_type(s, name, dim, M.eI, w[0]);
+    if (w[1] < NE) {
+        const int nd = read_one(M.eI + w[1] + 1, s) - read_one(M.eI + w[1], s);
+        const std::string which = name + "element " + std::to_string(w[1]) + ": ";
+        if (info) info[6] = w[1];
         SA_REQUIRE(nd != 6 || dim != 3, which + "a wedge has no order-2 type");
         SA_REQUIRE(false, which + std::to_string(nd) + " nodes: the element is of order 2 already");
     }
@@ -428,7 +396,7 @@ void mesh_lift_order2(hipStream_t s, int NV, int dim, const double *coords, int 
         if (!T) {
             long long finfo[8];
             try {
-                face_table_build(s, NV, dim, NE, nde, elem_ptr ? M.eI : nullptr, M.eJ, own, finfo);
+                face_table_build(s, MeshArgs{NV, dim, nullptr, NE, nde, elem_ptr ? M.eI : nullptr, M.eJ}, own, finfo);
             } catch (const Error &) {
                 if (info) info[6] = finfo[6];
                 throw;

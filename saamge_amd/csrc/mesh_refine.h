@@ -10,6 +10,7 @@
 // faces of hexahedra and the centres of level j, in the order of the lift (mesh_lift.h).
 #pragma once
 #include "common.h"
+#include "mesh.h"
 
 namespace saamge_amd {
 
@@ -37,7 +38,6 @@ struct MeshRefine {
 
 // The arguments of saamge_amd_mesh_refine.  Every level is lifted by mesh_lift_order2, with its checks; the lifted node list
 // of a level is released before the next level is lifted.  Runs on s and returns with s idle.
-void mesh_refine(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
-                 const int *elem_to_vertex, int levels, int want_interp, MeshRefine &R, long long info[8]);
+void mesh_refine(hipStream_t s, const MeshArgs &m, int levels, int want_interp, MeshRefine &R, long long info[8]);
 
 }  // namespace saamge_amd

@@ -9,7 +9,7 @@
 //                       vertex, 2 per edge, 4 per face, 4 | 8 per centre --, the owner of an edge is found by bisection in
 //                       edge_ptr, the vertices of a face from its slot of face_slot, and the columns of a face or centre row are
 //                       put in ascending order by a fixed network of exchanges.
-// A list that mixes types needs, for the rows of faces and centres, the element of a slot and of a centre: mr_classify_kernel and
+// A list that mixes types needs, for the rows of faces and centres, the element of a slot and of a centre: mesh_classify_kernel and
 // two scans give the offsets both are found in by bisection.  A list of one type needs neither (slot s is face s % 6 of
 // hexahedron s / 6, centre c is element c).
 #include "mesh_refine.h"
@@ -17,15 +17,13 @@
 #include <algorithm>
 #include <climits>
 
-#include "elmat_types.h"
+#include "mesh.h"
 #include "mesh_lift.h"
 #include "operator.h"      // device_view
 
 namespace saamge_amd {
 
 namespace {
-
-inline dim3 grid_flat(long n) { return dim3((unsigned)std::max<long>(1, (n + 255) / 256)); }
 
 // ---- mesh_refine_model.CHILDREN: local corner j of child k as an index into the parent's lifted local node list ---------------
 constexpr int MR_MAX_CHILDREN = 8, MR_MAX_ND = 8;
@@ -51,8 +49,8 @@ constexpr MrTables mr_tables() {
         }
     for (int k = 0; k < 8; ++k)
         for (int j = 0; j < 8; ++j)
-            t.child[4][k][j] = ((EM_HEX_LOC[k][2] + EM_HEX_LOC[j][2]) * 3 + (EM_HEX_LOC[k][1] + EM_HEX_LOC[j][1])) * 3 +
-                               (EM_HEX_LOC[k][0] + EM_HEX_LOC[j][0]);
+            t.child[4][k][j] = em_hex27_node(EM_HEX_LOC[k][0] + EM_HEX_LOC[j][0], EM_HEX_LOC[k][1] + EM_HEX_LOC[j][1],
+                                             EM_HEX_LOC[k][2] + EM_HEX_LOC[j][2]);
     return t;
 }
 // a lifted node with m ones in its reference position is listed by 2^m children (a corner by 1, an edge node by 2, a face node
@@ -70,7 +68,7 @@ constexpr bool mr_tables_ok() {
     for (int p = 0; p < 9; ++p)
         if (used2[p] != (1 << ((EM2_QUAD_LOC[p][0] == 1) + (EM2_QUAD_LOC[p][1] == 1)))) return false;
     for (int k = 0; k < 8; ++k) {
-        if (t.child[4][k][k] != (2 * EM_HEX_LOC[k][2] * 3 + 2 * EM_HEX_LOC[k][1]) * 3 + 2 * EM_HEX_LOC[k][0]) return false;
+        if (t.child[4][k][k] != em_hex27_corner(k)) return false;
         for (int j = 0; j < 8; ++j) {
             if (t.child[4][k][j] < 0 || t.child[4][k][j] >= 27) return false;
             ++used3[t.child[4][k][j]];
@@ -91,39 +89,6 @@ constexpr bool mr_tables_ok() {
 }
 static_assert(mr_tables_ok(), "mesh_refine: the child tables");
 __device__ const MrTables MR = mr_tables();
-
-__device__ __host__ constexpr void mr_order(int &x, int &y) {
-    const int lo = x < y ? x : y, hi = x < y ? y : x;
-    x = lo;
-    y = hi;
-}
-// ascending order of 4 values by the five exchanges of the lift, of 8 by Batcher's odd-even merge (19 exchanges)
-__device__ __host__ constexpr void mr_sort4(int *v) {
-    mr_order(v[0], v[1]);
-    mr_order(v[2], v[3]);
-    mr_order(v[0], v[2]);
-    mr_order(v[1], v[3]);
-    mr_order(v[1], v[2]);
-}
-__device__ __host__ constexpr void mr_sort8(int *v) {
-    mr_order(v[0], v[1]); mr_order(v[2], v[3]); mr_order(v[4], v[5]); mr_order(v[6], v[7]);
-    mr_order(v[0], v[2]); mr_order(v[1], v[3]); mr_order(v[4], v[6]); mr_order(v[5], v[7]);
-    mr_order(v[1], v[2]); mr_order(v[5], v[6]);
-    mr_order(v[0], v[4]); mr_order(v[1], v[5]); mr_order(v[2], v[6]); mr_order(v[3], v[7]);
-    mr_order(v[2], v[4]); mr_order(v[3], v[5]);
-    mr_order(v[1], v[2]); mr_order(v[3], v[4]); mr_order(v[5], v[6]);
-}
-constexpr bool mr_sort8_ok() {      // a network that sorts every sequence of zeros and ones sorts every sequence
-    for (int m = 0; m < 256; ++m) {
-        int v[8] = {};
-        for (int i = 0; i < 8; ++i) v[i] = (m >> i) & 1;
-        mr_sort8(v);
-        for (int i = 0; i < 7; ++i)
-            if (v[i] > v[i + 1]) return false;
-    }
-    return true;
-}
-static_assert(mr_sort8_ok(), "mesh_refine: the network of eight");
 
 // One lane per (child, local corner): lane t is corner t % stride of child t / stride (stride: the most corners an element of
 // this mesh can have).  eI NULL: NE elements of nde corners each.  Child c of a parent whose list starts at b and has nd
@@ -148,26 +113,15 @@ __global__ __launch_bounds__(256) void mr_children_kernel(long total, int stride
     }
 }
 
-// nf[e]: the faces of element e, centre[e]: it has a centre node (a mixed list with the interpolation asked for)
-__global__ __launch_bounds__(256) void mr_classify_kernel(int NE, int dim, const int *__restrict__ eI, int *__restrict__ nf,
-                                                          int *__restrict__ centre) {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= NE) return;
-    const int t = em_type_index(dim, eI[e + 1] - eI[e]);
-    nf[e] = bdr_num_faces(t);
-    centre[e] = (int)(t == 1 || t == 4);
-}
-
-// the last i of [0, n) with ptr[i] <= x (ptr ascending, ptr[0] <= x)
-__device__ inline long mr_last_le(const roff_t *__restrict__ ptr, long n, roff_t x) {
-    long lo = 0, up = n;
-    while (up - lo > 1) {
-        const long mid = lo + (up - lo) / 2;
-        if (ptr[mid] <= x) lo = mid;
-        else up = mid;
+// what mesh_classify_kernel keeps per element of a mixed list with the interpolation asked for: the number of its faces and
+// whether it has a centre node (the lift has classified the mesh: every element has a type)
+struct MrFacesAndCentre {
+    int *centre;
+    __device__ int operator()(int t, int e) const {
+        centre[e] = (int)(t == 1 || t == 4);
+        return bdr_num_faces(t);
     }
-    return lo;
-}
+};
 
 // One lane per row r of P, r in [0, NV2], NV2 = NV + NEd + NFq + NC; lane NV2 writes rowptr[NV2] = nnz.  slot_ptr NULL: slot s
 // is face s % 6 of element s / 6; centre_rank NULL: centre c is element c.
@@ -189,18 +143,18 @@ __global__ __launch_bounds__(256) void mr_interp_kernel(int NV, long NEd, long N
     } else if (r < NV + NEd) {
         const long k = r - NV, o = edges0 + 2 * k;
         rowptr[r] = (int)o;
-        col[o] = (int)mr_last_le(edge_ptr, NV, (roff_t)k);      // the owner a: edge_ptr[a] <= k < edge_ptr[a + 1]
+        col[o] = (int)last_le(edge_ptr, 0, NV, (roff_t)k);      // the owner a: edge_ptr[a] <= k < edge_ptr[a + 1]
         col[o + 1] = edge_hi[k];                                // b > a
         val[o] = val[o + 1] = 0.5;
     } else if (r < NV + NEd + NFq) {
         const long f = r - NV - NEd, o = faces0 + 4 * f;
         const roff_t s = face_slot[f];
-        const long e = slot_ptr ? mr_last_le(slot_ptr, NE, s) : (long)(s / BDR_MAX_FACES);
+        const long e = slot_ptr ? last_le(slot_ptr, 0, NE, s) : (long)(s / BDR_MAX_FACES);
         const int lf = (int)(s - (slot_ptr ? slot_ptr[e] : (roff_t)e * BDR_MAX_FACES));
         const long b = eI ? (long)eI[e] : e * nde;
         int v[4];
         for (int i = 0; i < 4; ++i) v[i] = eJ[b + BDR_HEX_FACES[lf][i]];
-        mr_sort4(v);
+        sort4(v);
         rowptr[r] = (int)o;
         for (int i = 0; i < 4; ++i) {
             col[o + i] = v[i];
@@ -208,13 +162,13 @@ __global__ __launch_bounds__(256) void mr_interp_kernel(int NV, long NEd, long N
         }
     } else if (r < NV2) {
         const long c = r - NV - NEd - NFq, o = centres0 + (long)cc * c;
-        const long e = centre_rank ? mr_last_le(centre_rank, NE, (roff_t)c) : c;
+        const long e = centre_rank ? last_le(centre_rank, 0, NE, (roff_t)c) : c;
         const long b = eI ? (long)eI[e] : e * nde;
         rowptr[r] = (int)o;
         if (cc == 4) {
             int v[4];
             for (int i = 0; i < 4; ++i) v[i] = eJ[b + i];
-            mr_sort4(v);
+            sort4(v);
             for (int i = 0; i < 4; ++i) {
                 col[o + i] = v[i];
                 val[o + i] = 0.25;
@@ -222,7 +176,7 @@ __global__ __launch_bounds__(256) void mr_interp_kernel(int NV, long NEd, long N
         } else {
             int v[8];
             for (int i = 0; i < 8; ++i) v[i] = eJ[b + i];
-            mr_sort8(v);
+            sort8(v);
             for (int i = 0; i < 8; ++i) {
                 col[o + i] = v[i];
                 val[o + i] = 0.125;
@@ -235,13 +189,12 @@ __global__ __launch_bounds__(256) void mr_interp_kernel(int NV, long NEd, long N
 
 }  // namespace
 
-void mesh_refine(hipStream_t s, int NV, int dim, const double *coords, int NE, int nde, const int *elem_ptr,
-                 const int *elem_to_vertex, int levels, int want_interp, MeshRefine &R, long long info[8]) {
+void mesh_refine(hipStream_t s, const MeshArgs &m, int levels, int want_interp, MeshRefine &R, long long info[8]) {
     const std::string name("saamge_amd_mesh_refine: ");
-    if (info) {
-        for (int k = 0; k < 8; ++k) info[k] = 0;
-        info[6] = -1;
-    }
+    const int NV = m.NV, dim = m.dim, NE = m.NE, nde = m.nde;
+    const double *const coords = m.coords;
+    const int *const elem_ptr = m.elem_ptr, *const elem_to_vertex = m.elem_to_vertex;
+    mesh_info_begin(info);      // (the levels come first here; the lift of level 0 checks the mesh)
     SA_REQUIRE(levels >= 1, name + "levels must be at least 1");
     SA_REQUIRE(levels <= MESH_REFINE_MAX_LEVELS, name + "levels above " + std::to_string(MESH_REFINE_MAX_LEVELS));
     const bool uniform = !elem_ptr;
@@ -259,7 +212,7 @@ void mesh_refine(hipStream_t s, int NV, int dim, const double *coords, int NE, i
         MeshLift L;
         long long li[8] = {0, 0, 0, 0, 0, 0, -1, 0};
         try {
-            mesh_lift_order2(s, nv, dim, X, ne, nde, uniform ? nullptr : I, J, nullptr, L, li);
+            mesh_lift_order2(s, MeshArgs{nv, dim, X, ne, nde, uniform ? nullptr : I, J}, nullptr, L, li);
         } catch (const Error &e) {
             if (info) info[6] = li[6];
             throw Error(e.code, name + "level " + std::to_string(j) + ": " + e.what());
@@ -310,8 +263,7 @@ void mesh_refine(hipStream_t s, int NV, int dim, const double *coords, int NE, i
                 DBuf<int> nf((size_t)ne), centre((size_t)ne);
                 slot_ptr.alloc((size_t)ne + 1);
                 centre_rank.alloc((size_t)ne + 1);
-                hipLaunchKernelGGL(mr_classify_kernel, grid_flat(ne), dim3(256), 0, s, ne, dim, I, nf.p, centre.p);
-                SA_HIP_CHECK(hipGetLastError());
+                mesh_classify(s, ne, dim, I, nf.p, (int *)nullptr, MrFacesAndCentre{centre.p});      // (no element without a type)
                 exclusive_scan_off(s, ne, nf.p, slot_ptr.p);
                 exclusive_scan_off(s, ne, centre.p, centre_rank.p);
             }

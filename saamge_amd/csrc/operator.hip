@@ -42,8 +42,6 @@ constexpr int OP_ELEMS_LDS = 64;           // elements of a row of the LDS numer
 constexpr int OP_ESS = 0x02;               // SAAMGE_AMD_ON_ESS_DOMAIN_BORDER
 constexpr int OP_MAX_ND = 46340;           // nd * nd stays below 2^31
 
-inline dim3 grid_flat(long n) { return dim3((unsigned)std::max<long>(1, (n + 255) / 256)); }
-
 // ---- tables ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void op_first_free_kernel(int n, const int *__restrict__ cnt, int *__restrict__ first) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;

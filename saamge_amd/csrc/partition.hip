@@ -41,7 +41,6 @@ inline int pt_bits(int n) {
     return b;
 }
 inline dim3 grid_rows(long n) { return dim3((unsigned)((n * PT_LPR + 255) / 256)); }
-inline dim3 grid_flat(long n) { return dim3((unsigned)std::max<long>(1, (n + 255) / 256)); }
 
 __device__ inline unsigned pt_prio(unsigned i, unsigned seed) {
     unsigned x = i + seed * 0x9E3779B9u;
