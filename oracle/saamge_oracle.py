@@ -576,10 +576,18 @@ class Level(object):
     pass
 
 
+# Test hook (tests/conditional_cases.py): callable (rel, AEs_stiffm) called once per level, before that level's eigenproblems.
+# EVECTS_HOOK and MIS_BASIS_HOOK get no level argument; a test that replaces bases on every level learns from this call
+# which level the calls that follow belong to, and on which relations and agglomerate matrices they work.
+LEVEL_HOOK = None
+
+
 def build_level(A, rel, AEs_stiffm, theta, nu_relax, nu_pro=0, testmesh=False, extra=None,
                 drop_tol=0.0):
     """tg_init_data + tg_build_hierarchy + tg_update_coarse_operator
     (src/tg.cpp:402-430, :502-540, :979-1014)."""
+    if LEVEL_HOOK is not None:
+        LEVEL_HOOK(rel, AEs_stiffm)
     lv = Level()
     lv.A = A.tocsr()
     lv.rel = rel

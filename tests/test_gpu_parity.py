@@ -414,21 +414,26 @@ def test_poisson3d_matches_oracle(n, blk, cblk, K):
     x_gpu = h.vcycle(b)
     x_ref = o.vcycle(H, b)
     # degenerate eigenspaces (symmetric AEs) make the coarse *basis* non-unique; with two
-    # levels the V-cycle is invariant to it, with three the level-1 smoother is not.
+    # levels the V-cycle is invariant to it, with three the level-1 smoother is not -- where there IS such a freedom.
+    # The three-level row here, (8, 8, 8) / (4, 4, 4) / [(2, 2, 1)], has none: one vector per agglomerate on both levels, the
+    # oracle with rotated eigenvectors and flipped MIS signs agrees with itself to 1e-16 (tests/test_conditional_cases.py), and
+    # the library's V-cycle deviates by 5.4e-16 with 3 / 3 iterations (measured 2026-10-20).  So it carries VCYCLE_TOL and equal
+    # iteration counts, not the 5e-2 / +-1 it had; the cases where the freedom is real are held level by level in
+    # tests/test_gpu_conditional_parity.py.
     # The 64-vector case keeps singular directions down to 1e-10 sigma_0 on rank-deficient MIS
     # blocks; those directions are round-off (LAPACK's differs from ours), so the coarse spaces
     # agree only to ~1e-8 there.
     many = K[2] == 1000.0001
-    tol = (1e-6 if many else VCYCLE_TOL) if ncoars == 1 else 5e-2
-    assert np.linalg.norm(x_gpu - x_ref) <= tol * np.linalg.norm(x_ref)
+    tol = 1e-6 if many else VCYCLE_TOL
+    dev = np.linalg.norm(x_gpu - x_ref) / np.linalg.norm(x_ref)
     x, it, conv, hist = h.pcg(prob.b, rel_tol=1e-8)
     xr, itr, convr, histr = o.solve(H, prob.b, rel_tol=1e-8)
+    print("poisson %s / %s / %s: V-cycle deviation %.2e, iterations %d / %d" % (n, blk, cblk, dev, it, itr))
+    assert dev <= tol
     assert conv and convr
+    assert it == itr
     if ncoars == 1:
-        assert it == itr
         assert np.allclose(hist, histr, rtol=1e-4 if many else 1e-7, atol=1e-10 * histr[0])
-    else:
-        assert abs(it - itr) <= 1
     assert np.linalg.norm(prob.A @ x - prob.b) <= 1e-6 * np.linalg.norm(prob.b)
     h.close()
 
@@ -544,7 +549,10 @@ def test_elasticity3d_matches_oracle(levels):
     """Vector dofs (3 per vertex, byVDIM, 24 x 24 element matrices): the six rigid-body modes
     are an exactly degenerate zero eigenvalue on every AE away from the clamped face, so the
     eigenvector *basis* (and with it the column normalisation before the SVD) is not unique;
-    counts, spans and the preconditioned iteration are."""
+    counts, spans and the preconditioned iteration are.  With three levels this test pins only what does not depend on
+    that basis (ncoarse on level 1, the V-cycle to 5e-2, iterations +-1); level 1 itself -- D, eigenvalues, singular values,
+    Ac, the cycle, at the level-0 tolerances -- is held in tests/test_gpu_conditional_parity.py (case q1_elasticity), where
+    the oracle is given the library's own basis."""
     o = _oracle()
     cblk = [(2, 2, 1)] if levels == 3 else None
     prob = pr.elasticity3d_problem((8, 6, 4), blk=(4, 3, 2), coarse_blk=cblk)
@@ -600,7 +608,10 @@ def test_q2_elasticity3d_three_level_matches_oracle():
     weighted-l1 diagonal D_ii = sum_j |a_ij| sqrt(a_ii / a_jj) of a coarse agglomerate matrix (src/mbox.cpp:913-949)
     is not invariant under a rotation of that basis, the six rigid-body modes give every MIS repeated singular
     values, so the level-1 eigenvalues of two correct implementations differ in the second digit (measured: 5.22e-4
-    vs 5.27e-4) and with them the coarsest space; the iteration counts then agree to within a few."""
+    vs 5.27e-4) and with them the coarsest space; the iteration counts then agree to within a few.
+    Where level 1 IS held: tests/test_gpu_conditional_parity.py (case q2_elasticity, the size of
+    tests/test_oracle_mis_rotation.py) gives the oracle the library's own basis on every level and asks the level-0
+    tolerances of the level-1 Ds, eigenvalues, singular values, Ac entries, V-cycle and PCG history."""
     o = _oracle()
     prob = pr.elasticity3d_q2_problem((8, 8, 4), blk=(4, 4, 4))
     nae = int(prob.partitions[0].max()) + 1
