@@ -1185,6 +1185,13 @@ __global__ void apply_dscale_kernel(int count, const int *ns, const int64_t *mof
     }
 }
 
+// W = D^-1/2 A D^-1/2 of every matrix of the batch, from the caller's A (host or device) and the diagonals dD (device)
+static void upload_scaled(hipStream_t s, EigBatch &b, const double *A, const double *dD) {
+    SA_HIP_CHECK(hipMemcpyAsync(b.W.p, A, 8 * (size_t)b.h_moff[b.count], hipMemcpyDefault, s));
+    hipLaunchKernelGGL(apply_dscale_kernel, dim3(b.count), dim3(256), 0, s, b.count, b.n.p, b.moff.p, b.voff.p, b.W.p, dD,
+                       b.dis.p);
+}
+
 int saamge_amd_lower_eigens_batched(int count, const int *n, const double *A, const double *D,
                                     double vl, double vu, int *m, double *evals, double *evecs) {
     SA_API_BEGIN
@@ -1198,19 +1205,15 @@ int saamge_amd_lower_eigens_batched(int count, const int *n, const double *A, co
     eig_batch_alloc(b, sizes, opt, s);
     b.set_window(vu);
     b.dense_only = opt.eig_dense_only != 0;
-    SA_HIP_CHECK(hipMemcpyAsync(b.W.p, A, 8 * (size_t)b.h_moff[count], hipMemcpyDefault, s));
     DBuf<double> dD;
     dD.assign(D, (size_t)b.h_voff[count], s);
-    hipLaunchKernelGGL(apply_dscale_kernel, dim3(count), dim3(256), 0, s, count, b.n.p, b.moff.p,
-                       b.voff.p, b.W.p, dD.p, b.dis.p);
+    upload_scaled(s, b, A, dD.p);
     eig_tridiagonalize(s, b);
     eig_count(s, b, vl, vu);
     if (b.ss_failed || b.nbad) {     // few-eigenpairs path gave up (on the batch or on some matrices): the dense path on a fresh copy
         b.dense_only = true;
         b.subspace = b.ss_failed = false;
-        SA_HIP_CHECK(hipMemcpyAsync(b.W.p, A, 8 * (size_t)b.h_moff[count], hipMemcpyDefault, s));
-        hipLaunchKernelGGL(apply_dscale_kernel, dim3(count), dim3(256), 0, s, count, b.n.p, b.moff.p,
-                           b.voff.p, b.W.p, dD.p, b.dis.p);
+        upload_scaled(s, b, A, dD.p);
         eig_tridiagonalize(s, b);
         eig_count(s, b, vl, vu);
     }
@@ -1245,11 +1248,9 @@ int saamge_amd_inertia_batched(int count, const int *n, const double *A, const d
     EigBatch b;
     eig_batch_alloc(b, sizes, opt, s);
     b.set_window(vu);
-    SA_HIP_CHECK(hipMemcpyAsync(b.W.p, A, 8 * (size_t)b.h_moff[count], hipMemcpyDefault, s));
     DBuf<double> dD;
     dD.assign(D, (size_t)b.h_voff[count], s);
-    hipLaunchKernelGGL(apply_dscale_kernel, dim3(count), dim3(256), 0, s, count, b.n.p, b.moff.p,
-                       b.voff.p, b.W.p, dD.p, b.dis.p);
+    upload_scaled(s, b, A, dD.p);
     (void)eig_subspace_factor(s, b);      // (the inertia pass runs ahead of the Cholesky factorisation)
     SA_REQUIRE((int)b.h_inertia.size() == count, "the inertia pass is switched off");
     std::copy(b.h_inertia.begin(), b.h_inertia.end(), neg);

@@ -38,11 +38,6 @@ struct EigBatch {
     DBuf<int64_t> roff;     // [count+1] reflector offsets
     DBuf<double> Gbuf;      // per (matrix, 64-row block) partial V^T X (SB x SB each)
     DBuf<int64_t> goff;
-    // symmetric fused update: per matrix the 64 x SB partial products of
-    // the tiles below the diagonal, tile (I, J) at xpoff[b] + I (I - 1) / 2 + J
-    DBuf<double> Xpart;
-    DBuf<int64_t> xpoff;
-    std::vector<int64_t> h_xpoff;
     std::vector<int64_t> h_roff, h_goff;
     // few-eigenpairs path: Ritz values of the accepted block; `dense_only`
     // forces the dense path for this batch (fallback after a failed subspace attempt)
@@ -118,7 +113,6 @@ void eig_batch_alloc(EigBatch &b, const std::vector<int> &sizes, const Options &
 void eig_tridiagonalize(hipStream_t s, EigBatch &b, int phases = 3);
 void eig_tridiagonalize_two_stage(hipStream_t s, EigBatch &b, int phases);
 void eig_backtransform_two_stage(hipStream_t s, EigBatch &b, const int64_t *xoff, double *evecs);
-int64_t chase_reflector_count(int n);
 void eig_batch_two_stage_buffers(EigBatch &b, size_t nrefl, bool need_bandg, hipStream_t s);
 // few-eigenpairs path (eig2.hip), see there
 bool eig_batch_takes_subspace(const EigBatch &b);   // what eig_tridiagonalize will decide for this batch
@@ -127,8 +121,10 @@ bool eig_subspace_iterate(hipStream_t s, EigBatch &b, double vu);
 void eig_subspace_vectors(hipStream_t s, EigBatch &b, const int64_t *eoff, const int64_t *xoff, double *evals,
                           double *evecs);
 void eig_arena_release();   // frees the persistent workspace
-double *eig_arena_bandsave(const EigBatch &b, size_t doubles);   // persistent scratch of the inertia pass
-double *eig_arena_subpanels(const EigBatch &b, size_t doubles); // packed sub-panels of the outer blocks of the wide-band factorisations
+// persistent scratch of the few-eigenpairs path (grow-only, per workspace slot): the bands saved by the inertia pass; the
+// packed sub-panels of the outer blocks of the wide-band factorisations
+enum class EigScratch { BandSave, SubPanels };
+double *eig_arena_scratch(const EigBatch &b, EigScratch which, size_t doubles);
 // the batch of some matrices of `full` (class representatives, dedupe.h) in the same workspace
 void eig_batch_compact(hipStream_t s, EigBatch &cb, EigBatch &full, const std::vector<int> &reps);
 // bytes of device workspace one matrix of size n needs (for chunk sizing)

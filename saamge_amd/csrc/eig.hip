@@ -13,8 +13,8 @@
 // Reference behaviour: amg/src/xpacks.cpp:222-314 (dsygvx, range 'V' on (-1, theta],
 // fallback to the single smallest pair), amg/src/spectral.cpp:124-237.
 #include "eig.h"
-
-
+#include "eig_dense_plan.h"
+#include "eig_device.h"
 
 #include <cfloat>
 #include <cstdlib>
@@ -25,24 +25,13 @@ namespace saamge_amd {
 constexpr int TRI_NT = 1024;  // threads per workgroup in phase 1 (16 wavefronts)
 constexpr int VEC_NT = 256;   // threads per workgroup in phase 3
 constexpr int VEC_MAXB = 254; // decoupled blocks of one tridiagonal handled separately (more: one last block)
+static_assert(DENSE_PLAN_NB == EIG_NB && DENSE_PLAN_TRI_NT == TRI_NT && DENSE_PLAN_VEC_MAXB == VEC_MAXB,
+              "eig_dense_plan.h restates the sizes of the kernels");
 
 __device__ inline double wave_sum(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
     return __shfl(v, 0, 64);
-}
-
-template <int NT>
-__device__ inline double block_sum(double v, double *red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = 0.0;
-#pragma unroll
-    for (int i = 0; i < NT / 64; ++i) r += red[i];
-    return r;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -312,14 +301,8 @@ __global__ __launch_bounds__(64) void count_kernel(const int *__restrict__ ns,
 // ---------------------------------------------------------------------------------------
 // phase 3
 // ---------------------------------------------------------------------------------------
-__device__ inline double unit_rand(unsigned a, unsigned b) {  // deterministic uniform(-1,1)
-    unsigned h = a * 2654435761u ^ (b + 0x9e3779b9u + (a << 6) + (a >> 2));
-    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-    return ((double)h + 0.5) * (2.0 / 4294967296.0) - 1.0;
-}
-
 // GWS: the per-matrix work arrays (tridiagonal, LU factors, iterate: ~58 n bytes) live in a global
-// workspace instead of LDS -- agglomerates beyond ~2 900 rows, where they no longer fit 160 KiB
+// workspace instead of LDS -- agglomerates beyond 2 748 rows, where they no longer fit 160 KiB (dense_vec_plan)
 // (same code through generic pointers; the workgroup barriers order the accesses).
 template <bool GWS>
 __global__ __launch_bounds__(VEC_NT) void eigvec_kernel(
@@ -752,9 +735,9 @@ static bool use_one_stage(const EigBatch &b) { return b.opt.eig_dense_one_stage 
 // multi-GB buffers costs 0.1-0.4 s each on this platform; the arena is allocated once per
 // process and reused by every chunk / level / hierarchy).  Single stream, sequential use.
 struct EigArena {
-    DBuf<double> W, panel, d, e, tau, dis, Tfac, Xbuf, Zbuf, Vpk, Vpk2, trash, rv, rtau, bandg, Gbuf, Xpart, bandsave, subpanels;
+    DBuf<double> W, panel, d, e, tau, dis, Tfac, Xbuf, Zbuf, Vpk, Vpk2, trash, rv, rtau, bandg, Gbuf, bandsave, subpanels;
     DBuf<int> n, m, j0;
-    DBuf<int64_t> moff, voff, roff, goff, xpoff;
+    DBuf<int64_t> moff, voff, roff, goff;
 };
 static int g_slot = 0;   // workspace of the batch being set up (single host thread)
 static EigArena &arena() {
@@ -775,18 +758,12 @@ void eig_arena_release() {
     }
     g_slot = 0;
 }
-double *eig_arena_bandsave(const EigBatch &b, size_t doubles) {
+double *eig_arena_scratch(const EigBatch &b, EigScratch which, size_t doubles) {
     g_slot = b.slot;
     EigArena &a = arena();
-    if (a.bandsave.n < doubles) a.bandsave.alloc(doubles + doubles / 8 + 64);
-    return a.bandsave.p;
-}
-
-double *eig_arena_subpanels(const EigBatch &b, size_t doubles) {
-    g_slot = b.slot;
-    EigArena &a = arena();
-    if (a.subpanels.n < doubles) a.subpanels.alloc(doubles + doubles / 8 + 64);
-    return a.subpanels.p;
+    DBuf<double> &buf = which == EigScratch::BandSave ? a.bandsave : a.subpanels;
+    if (buf.n < doubles) buf.alloc(doubles + doubles / 8 + 64);
+    return buf.p;
 }
 
 void eig_batch_alloc(EigBatch &b, const std::vector<int> &sizes, const Options &opt, hipStream_t s, int slot) {
@@ -844,20 +821,7 @@ void eig_batch_two_stage_buffers(EigBatch &b, size_t nrefl, bool need_bandg, hip
     arena_view(b.rv, a.rv, nrefl * EIG_SB + EIG_SB);
     arena_view(b.rtau, a.rtau, nrefl + 1);
     if (need_bandg) arena_view(b.bandg, a.bandg, rows * 2 * EIG_SB);
-    if (!b.h_xpoff.empty()) {
-        arena_view(b.xpoff, a.xpoff, (size_t)b.count + 1);
-        arena_view(b.Xpart, a.Xpart, (size_t)b.h_xpoff[b.count] * 64 * EIG_SB + 64);
-        SA_HIP_CHECK(hipMemcpyAsync(b.xpoff.p, b.h_xpoff.data(), 8 * ((size_t)b.count + 1), hipMemcpyHostToDevice, s));
-        SA_HIP_CHECK(hipStreamSynchronize(s));
-    }
 }
-
-static size_t tri_lds_bytes(int n) { return sizeof(double) * (2 * (size_t)n + TRI_NT + 2 * EIG_NB + TRI_NT / 64); }
-static size_t vec_lds_bytes(int n) {
-    return sizeof(double) * (7 * (size_t)n + 8) + sizeof(int) * 8 + sizeof(unsigned short) * ((size_t)n + 3 * (VEC_MAXB + 2)) +
-           (size_t)n + 64;
-}
-constexpr size_t LDS_MAX = 160 * 1024;
 
 __global__ void gather_int_kernel(int n, const int *__restrict__ idx, const int *__restrict__ src, int *__restrict__ dst) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -915,12 +879,7 @@ void eig_batch_compact(hipStream_t s, EigBatch &cb, EigBatch &full, const std::v
     cb.dense_only = full.dense_only;
 }
 
-size_t eig_workspace_bytes(int n) {
-    const size_t nn = (size_t)n;
-    // (the packed sub-panels of the blocked wide-band factorisation: only matrices that can have a band beyond the LDS window)
-    const size_t sub = nn > 512 ? 16 * EIG_SB : 0;
-    return 8 * (nn * nn + nn * (EIG_NB + 8) + nn * nn / 2 + nn * (3 * EIG_SB + 2 * EIG_SB + sub) + 64);
-}
+size_t eig_workspace_bytes(int n) { return dense_workspace_bytes(n); }
 
 // The few-eigenpairs path (eig2.hip) is the default for batches whose largest agglomerate has at
 // least Options::eig_min_n (64) rows -- measured faster than the dense reduction on the 405-row and
@@ -930,6 +889,16 @@ size_t eig_workspace_bytes(int n) {
 bool eig_batch_takes_subspace(const EigBatch &b) {
     // (saamge_amd_options.eig_min_n: smallest agglomerate size of a batch that takes the few-eigenpairs path)
     return !b.dense_only && b.max_n >= b.opt.eig_min_n;
+}
+
+// Once per process, ahead of the first launch of the dense path: the three kernels of this file that take their work arrays
+// in dynamic LDS may have all of it.
+static void dense_allow_large_lds() {
+    static bool done = false;
+    if (done) return;
+    for (const void *kernel : {(const void *)tridiag_kernel, (const void *)eigvec_kernel<false>, (const void *)count_kernel})
+        SA_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DENSE_LDS_MAX));
+    done = true;
 }
 
 void eig_tridiagonalize(hipStream_t s, EigBatch &b, int phases) {
@@ -943,14 +912,7 @@ void eig_tridiagonalize(hipStream_t s, EigBatch &b, int phases) {
         return;
     }
     b.subspace = false;
-    static bool attr0 = false;
-    if (!attr0) {
-        SA_HIP_CHECK(hipFuncSetAttribute((const void *)eigvec_kernel<false>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX));
-        SA_HIP_CHECK(hipFuncSetAttribute((const void *)count_kernel,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX));
-        attr0 = true;
-    }
+    dense_allow_large_lds();
     if (!use_one_stage(b)) {
         b.two_stage = true;
         eig_tridiagonalize_two_stage(s, b, phases);
@@ -958,18 +920,8 @@ void eig_tridiagonalize(hipStream_t s, EigBatch &b, int phases) {
     }
     b.two_stage = false;
     if (!(phases & 1)) return;   // one-stage: everything happens in "phase 1"
-    const size_t lds = tri_lds_bytes(b.max_n);
-    SA_REQUIRE(lds <= LDS_MAX, "agglomerate too large for the LDS-resident reflector vectors");
-    static bool attr_set = false;
-    if (!attr_set) {
-        SA_HIP_CHECK(hipFuncSetAttribute((const void *)tridiag_kernel,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX));
-        SA_HIP_CHECK(hipFuncSetAttribute((const void *)eigvec_kernel<false>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX));
-        SA_HIP_CHECK(hipFuncSetAttribute((const void *)count_kernel,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX));
-        attr_set = true;
-    }
+    const size_t lds = dense_tri_lds_bytes(b.max_n);
+    SA_REQUIRE(lds <= DENSE_LDS_MAX, "agglomerate too large for the LDS-resident reflector vectors");
     double flops = 0.0, bytes = 0.0;
     for (int n : b.h_n) {
         flops += 4.0 / 3.0 * (double)n * n * n;
@@ -990,8 +942,8 @@ void eig_count(hipStream_t s, EigBatch &b, double vl, double vu) {
         if (b.ss_failed) b.h_m.assign((size_t)b.count, 1);     // the caller redoes the batch densely
         return;
     }
-    const size_t lds = sizeof(double) * 2 * (size_t)b.max_n;
-    SA_REQUIRE(lds <= LDS_MAX, "agglomerate too large for the Sturm kernel");
+    const size_t lds = dense_sturm_lds_bytes(b.max_n);
+    SA_REQUIRE(lds <= DENSE_LDS_MAX, "agglomerate too large for the Sturm kernel");
     profiler().begin(s);
     hipLaunchKernelGGL(count_kernel, dim3(b.count), dim3(64), lds, s, b.n.p, b.voff.p, b.d.p,
                        b.e.p, vl, vu, b.m.p, b.j0.p);
@@ -1010,21 +962,21 @@ void eig_vectors(hipStream_t s, EigBatch &b, const int64_t *eoff, const int64_t 
         eig_subspace_vectors(s, b, eoff, xoff, evals, evecs);
         return;
     }
-    const size_t lds = vec_lds_bytes(b.max_n);
+    const DenseVecPlan plan = dense_vec_plan(b.max_n);
     double flops = 0.0;
     for (int i = 0; i < b.count; ++i) flops += 2.0 * (double)b.h_n[i] * b.h_n[i] * b.h_m[i];
     DBuf<double> gws;
-    if (lds > LDS_MAX) {      // work arrays in global memory
-        SA_REQUIRE(b.max_n < 65536, "agglomerate too large for the inverse iteration's 16-bit block tables");
-        gws.alloc((size_t)b.count * (lds / 8 + 2));
+    if (plan.global_ws) {      // work arrays in global memory
+        SA_REQUIRE(b.max_n < DENSE_VEC_GLOBAL_MAX_N, "agglomerate too large for the inverse iteration's 16-bit block tables");
+        gws.alloc((size_t)b.count * plan.ws_doubles);
     }
     profiler().begin(s);
-    if (lds > LDS_MAX)
-        hipLaunchKernelGGL(eigvec_kernel<true>, dim3(b.count), dim3(VEC_NT), 64, s, b.n.p, b.moff.p,
+    if (plan.global_ws)
+        hipLaunchKernelGGL(eigvec_kernel<true>, dim3(b.count), dim3(VEC_NT), plan.lds_bytes, s, b.n.p, b.moff.p,
                            b.voff.p, b.W.p, b.d.p, b.e.p, b.tau.p, b.dis.p, b.m.p, b.j0.p, eoff, xoff,
-                           evals, evecs, b.two_stage ? 0 : 1, b.vl, b.vu, gws.p, (int64_t)(lds / 8 + 2));
+                           evals, evecs, b.two_stage ? 0 : 1, b.vl, b.vu, gws.p, (int64_t)plan.ws_doubles);
     else
-        hipLaunchKernelGGL(eigvec_kernel<false>, dim3(b.count), dim3(VEC_NT), lds, s, b.n.p, b.moff.p,
+        hipLaunchKernelGGL(eigvec_kernel<false>, dim3(b.count), dim3(VEC_NT), plan.lds_bytes, s, b.n.p, b.moff.p,
                            b.voff.p, b.W.p, b.d.p, b.e.p, b.tau.p, b.dis.p, b.m.p, b.j0.p, eoff, xoff,
                            evals, evecs, b.two_stage ? 0 : 1, b.vl, b.vu, (double *)nullptr, (int64_t)0);
     SA_HIP_CHECK(hipGetLastError());

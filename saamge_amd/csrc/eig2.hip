@@ -20,6 +20,8 @@
 #include <cfloat>
 
 #include "eig.h"
+#include "eig_dense_plan.h"
+#include "eig_device.h"
 #include "eig_ss_plan.h"
 
 #include <cstdlib>
@@ -28,12 +30,6 @@ namespace saamge_amd {
 
 constexpr int SB = EIG_SB;      // band width
 constexpr int LDB = 2 * SB;     // band storage: distances 0 .. 2*SB-1 (band + bulge)
-
-__device__ inline double unit_rand_ss(unsigned a, unsigned b) {  // deterministic uniform(-1,1)
-    unsigned h = a * 2654435761u ^ (b + 0x9e3779b9u + (a << 6) + (a >> 2));
-    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-    return ((double)h + 0.5) * (2.0 / 4294967296.0) - 1.0;
-}
 
 __device__ inline double gsum16(double v) {   // sum inside each 16-lane group
     v += __shfl_xor(v, 1, 64);
@@ -108,18 +104,6 @@ __device__ inline double xsum32(double v) {
     auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
     return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
 }
-template <int NT>
-__device__ inline double bsum(double v, double *red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = 0.0;
-#pragma unroll
-    for (int i = 0; i < NT / 64; ++i) r += red[i];
-    return r;
-}
 
 // XCD-aware work decode: workgroups are dealt round-robin over the 8 XCDs, so linear id
 // 8 (g T + t) + x  ->  matrix 8 g + x, tile t : all tiles of one matrix run back to back on ONE
@@ -179,7 +163,7 @@ __global__ __launch_bounds__(NT) void sbr_qr_kernel(int k0, const int *__restric
         const double alpha = pc[c];
         double ss = 0.0;
         for (int i = c + 1 + tid; i < np; i += NT) ss = fma(pc[i], pc[i], ss);
-        ss = bsum<NT>(ss, red);
+        ss = block_sum<NT>(ss, red);
         double tau = 0.0, beta = alpha, scale = 0.0;
         if (ss != 0.0) {
             beta = -copysign(fast_sqrt(fma(alpha, alpha, ss)), alpha);
@@ -750,8 +734,7 @@ __global__ __launch_bounds__(S2_NT) void sbr_fused_kernel(int k0, const int *__r
 // stage 2: bulge chasing
 // ---------------------------------------------------------------------------------------
 
-// number of chase steps of sweep s
-__device__ __host__ inline int chase_steps(int n, int s) { return (n - 1 - s + SB - 1) / SB; }
+// (chase_steps(n, s), the number of chase steps of sweep s: eig_dense_plan.h)
 
 struct BandRef {
     double *p;
@@ -764,24 +747,22 @@ __device__ inline void wave_lds_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CS
 
 constexpr int HAND = 4 * SB + 2;  // per-wave LDS scratch: vprev[SB], tau, pad, sv[SB], sw[SB], sx[SB]
 
-// One chase step of sweep s (q-th block), executed by 16 NCQ lanes (a "slot": NCQ = 4: a whole
-// wavefront; NCQ = 2: half of one, the two halves work on different sweeps).  Lane l of the slot:
+// One chase step of sweep s (q-th block), executed by the 16 NCQ = 64 lanes of a "slot": a whole wavefront (half-wavefront
+// slots, NCQ = 2, measured slower: 70.2 against 42.9 ms at 128^3).  Lane l of the slot:
 // r = l & 15 is the row inside the SB x SB block, cq = l >> 4 selects SB / NCQ of its 16 columns.
 // Vectors that every lane needs (v, w, first column) go through a slot-private LDS scratch
 // instead of cross-lane permutes; the 16-lane sums use DPP row rotations.  s, q (and everything
 // derived from them) are per-slot values; a slot is active or idle as a whole, so the DPP rows and
 // the permlane swaps below never mix active and idle lanes.
-template <int NCQ>
+constexpr int CHASE_NCQ = 4;        // column groups of 16 lanes per chase step
+constexpr int CHASE_NT = 1024;      // threads of band_chase_kernel: CHASE_NT / (16 CHASE_NCQ) slots, one sweep each
 __device__ inline void chase_step(const BandRef &B, int n, int s, int q, double *hand,
                                   double *refl_v, double *refl_tau, int lane) {
+    constexpr int NCQ = CHASE_NCQ;
     constexpr int CPL = SB / NCQ;               // columns per lane
     const int sl = lane & (16 * NCQ - 1);       // lane inside the slot
     const int r = sl & 15, cq = sl >> 4;
-    auto rowsum = [](double v) {                // sum over the NCQ column groups of a row
-        if (NCQ == 4) return xsum32(xsum16(v));
-        if (NCQ == 2) return xsum16(v);
-        return v;
-    };
+    auto rowsum = [](double v) { return xsum32(xsum16(v)); };   // sum over the NCQ column groups of a row
     double *vprev = hand, *sv = hand + SB + 2, *sw = sv + SB, *sx = sw + SB;
     const int i0 = s + 1 + q * SB;              // first row of I_q
     const int L = min(SB, n - i0);              // |I_q| >= 1
@@ -892,14 +873,14 @@ __device__ inline void chase_step(const BandRef &B, int n, int s, int q, double 
 
 // IN_LDS: the band lives in LDS.  A compile-time switch, so that every band access is a 32-bit
 // ds_read / ds_write; with a run-time choice of the base pointer the accesses become FLAT
-// instructions with 64-bit address arithmetic.  NT threads = NT / (16 NCQ) slots, one sweep each.
-template <bool IN_LDS, int NCQ, int NT>
-__global__ __launch_bounds__(NT) void band_chase_kernel(
+// instructions with 64-bit address arithmetic.
+template <bool IN_LDS>
+__global__ __launch_bounds__(CHASE_NT) void band_chase_kernel(
     const int *__restrict__ ns, const int64_t *__restrict__ moff, const int64_t *__restrict__ voff,
     const int64_t *__restrict__ roff, const double *__restrict__ Wm, double *__restrict__ bandg,
-    int band_in_lds, double *__restrict__ dd, double *__restrict__ ee, double *__restrict__ rv,
-    double *__restrict__ rtau) {
+    double *__restrict__ dd, double *__restrict__ ee, double *__restrict__ rv, double *__restrict__ rtau) {
     extern __shared__ __align__(16) double lds[];
+    constexpr int NCQ = CHASE_NCQ, NT = CHASE_NT;
     constexpr int NSLOT = NT / (16 * NCQ);
     const int b = blockIdx.x;
     const int n = ns[b];
@@ -955,7 +936,7 @@ __global__ __launch_bounds__(NT) void band_chase_kernel(
             if (s < nsweeps && t >= s_begin) {
                 const int q = t - s_begin;
                 const int rid = cum[s] + q;
-                chase_step<NCQ>(B, n, s, q, myhand, RV + (size_t)rid * SB, RT + rid, lane);
+                chase_step(B, n, s, q, myhand, RV + (size_t)rid * SB, RT + rid, lane);
             }
             __syncthreads();
         }
@@ -1075,190 +1056,166 @@ __global__ __launch_bounds__(NT) void backtransform2_kernel(
 // ---------------------------------------------------------------------------------------
 // host driver
 // ---------------------------------------------------------------------------------------
-int64_t chase_reflector_count(int n) {
-    int64_t r = 0;
-    for (int s = 0; s + 3 <= n; ++s) r += chase_steps(n, s);
-    return r;
+static_assert(DENSE_PLAN_SB == SB && DENSE_FUSED_ROWS == SF_ROWS && DENSE_CHASE_HAND == HAND && DENSE_CHASE_THREADS == CHASE_NT &&
+                  DENSE_CHASE_SLOTS == CHASE_NT / (16 * CHASE_NCQ) && SM_NT == 256,
+              "eig_dense_plan.h restates the sizes of the kernels");
+
+// Once per process, ahead of the first launch of the two-stage reduction: the kernels that take dynamic LDS beyond the
+// default bound may have what the plan can ask of them.
+static void two_stage_allow_large_lds() {
+    static bool done = false;
+    if (done) return;
+    for (const void *kernel : {(const void *)band_chase_kernel<true>, (const void *)band_chase_kernel<false>,
+                               (const void *)backtransform2_kernel<256>, (const void *)backtransform2_kernel<1024>})
+        SA_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)DENSE_LDS_MAX));
+    SA_HIP_CHECK(hipFuncSetAttribute((const void *)sbr_qr_kernel<256, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)DENSE_QR_LDS_MAX));
+    done = true;
 }
 
-// Lanes per chase step and threads per matrix (ncq = 4 | 2
-// column groups of 16 lanes per step, nt / (16 ncq) sweeps in flight).  Measured at 128^3
-// (n = 405, 8 192 matrices): 64 lanes per step 42.9 ms, 32 lanes 70.2 ms, 16 lanes 96 ms, and
-// 32 slots instead of 16 do not help the 2 600-row level-1 matrices either (80 vs 60 ms): a step
-// is a chain of ~180 dependent operations (LDS round trips, 64-bit DPP sums, the reflector's
-// rsq / rcp), and spreading a step over more lanes shortens that chain -- fewer lanes per step
-// save instructions but the kernel is bound by the chain, not by issue slots.
-struct ChaseConfig {
-    int ncq, nt;
-    int slots() const { return nt / (16 * ncq); }
+// The two-stage reduction of one batch: what its steps share.  Every kernel, thread count, grid and LDS size below is what
+// eig_dense_plan.h says for the batch's largest matrix (nmax rows); a matrix without the panel or the rows returns at once.
+struct DenseReduce {
+    hipStream_t s;
+    EigBatch &b;
+    const int nmax, cnt8;
+    const bool prof;            // under the profiler every kernel of stage 1 is a row of its own
+    size_t nrefl = 0;           // chase reflectors of the batch
+    double flops = 0.0, bytes = 0.0;
+    double *Vcur = nullptr, *Vnext = nullptr;   // packed V of the current / the next panel
+    DenseReduce(hipStream_t s_, EigBatch &b_)
+        : s(s_), b(b_), nmax(b_.max_n), cnt8(dense_cnt8(b_.count)), prof(profiler().enabled) {}
 };
-// a whole wavefront per chase step (NCQ = 4), 16 slots per workgroup: a sweep of n rows keeps ~n / 32 sweeps in
-// flight at the minimum spacing of two steps (half-wavefront slots, NCQ = 2, measured slower in round 1)
-static ChaseConfig chase_config(int) { return ChaseConfig{4, 1024}; }
+
+// a launch of stage 1 as a profiler row (nothing launched: the row counts the call all the same)
+template <class Launch>
+static void dense_timed(const DenseReduce &f, const char *label, double bytes, Launch &&launch) {
+    if (f.prof) profiler().begin(f.s);
+    launch();
+    if (f.prof) profiler().end(f.s, label, bytes, 0.0);
+}
+
+static void launch_qr(const DenseReduce &f, int k0, double *Vp) {
+    const EigBatch &b = f.b;
+    const DenseQrPlan q = dense_qr_plan(dense_panel(f.nmax, k0).npmax);
+    auto kernel = q.kind == DenseQr::Reg256 ? sbr_qr_reg_kernel
+                : q.kind == DenseQr::Lds256 ? sbr_qr_kernel<256, true> : sbr_qr_kernel<1024, false>;
+    hipLaunchKernelGGL(kernel, dim3(b.count), dim3(q.threads), q.lds_bytes, f.s, k0, b.n.p, b.moff.p, b.voff.p, b.W.p,
+                       b.Tfac.p, Vp);
+}
+static void launch_symm(const DenseReduce &f, int k0, double *Vp) {
+    const EigBatch &b = f.b;
+    const int tiles = dense_symm_tiles(dense_panel(f.nmax, k0).npmax);
+    hipLaunchKernelGGL(sbr_symm_kernel, dim3(f.cnt8 * tiles), dim3(SY_NT), 0, f.s, k0, b.n.p, b.moff.p, b.voff.p, b.W.p, Vp,
+                       b.Xbuf.p, b.goff.p, b.Gbuf.p, b.count, tiles);
+}
+static void launch_z(const DenseReduce &f, int k0, double *Vp) {
+    const EigBatch &b = f.b;
+    const int tiles = dense_z_tiles(dense_panel(f.nmax, k0).npmax);
+    hipLaunchKernelGGL(sbr_z_kernel, dim3(f.cnt8 * tiles), dim3(SM_NT), 0, f.s, k0, b.n.p, b.voff.p, Vp, b.Tfac.p, b.Xbuf.p,
+                       b.goff.p, b.Gbuf.p, b.Zbuf.p, b.count, tiles);
+}
+
+// 1. where every matrix keeps its chase reflectors and its partial products; flops and bytes of stage 1
+static void dense_offsets(DenseReduce &f) {
+    EigBatch &b = f.b;
+    b.h_roff.assign((size_t)b.count + 1, 0);
+    b.h_goff.assign((size_t)b.count + 1, 0);
+    for (int i = 0; i < b.count; ++i) {
+        b.h_roff[i + 1] = b.h_roff[i] + chase_reflector_count(b.h_n[i]);
+        b.h_goff[i + 1] = b.h_goff[i] + dense_g_block(b.h_n[i]);
+    }
+    f.nrefl = (size_t)b.h_roff[b.count];
+    for (int n : b.h_n) {
+        f.flops += 4.0 / 3.0 * (double)n * n * n;
+        f.bytes += 8.0 * (double)n * n;
+    }
+}
+
+// 2. the first panel: QR, X = A22 V as a product of its own, Z
+static void dense_first_panel(DenseReduce &f) {
+    f.Vcur = f.b.Vpk.p;
+    f.Vnext = f.b.Vpk2.p;
+    dense_timed(f, "eig_sbr_qr", 0.0, [&] { launch_qr(f, 0, f.Vcur); });
+    dense_timed(f, "eig_sbr_symm", 0.0, [&] { launch_symm(f, 0, f.Vcur); });
+    dense_timed(f, "eig_sbr_z", 0.0, [&] { launch_z(f, 0, f.Vcur); });
+}
+// 3. panel k0 of the look-ahead pipeline: the update of the next panel's columns, that panel's QR, then the update of the
+// rest with the next panel's product X' = A22' V' riding on the same pass, and Z'.  One fused kernel, vector FMAs with
+// scalar-cache operands.  Measured alternatives (profiles/r01_*): separate product / update kernels, the same update on
+// the matrix cores (fp64 MFMA sustains 46 TFLOP/s against 69 for v_fma_f64: tools/fma64_bench.hip) and a
+// lower-triangle-only variant were all slower or equal -- none is bound by FMA issue or HBM bytes, they are bound by
+// operand delivery (scalar-load latency).
+static void dense_panel_step(DenseReduce &f, int k0) {
+    const EigBatch &b = f.b;
+    const DensePanel p = dense_panel(f.nmax, k0);
+    dense_timed(f, "eig_sbr_panel", 0.0, [&] {
+        const int tiles = dense_panel_update_tiles(p.npmax);
+        hipLaunchKernelGGL(sbr_panel_update_kernel, dim3(f.cnt8 * tiles), dim3(256), 0, f.s, k0, b.n.p, b.moff.p, b.voff.p,
+                           b.W.p, f.Vcur, b.Zbuf.p, b.count, tiles);
+    });
+    dense_timed(f, "eig_sbr_qr", 0.0, [&] { if (p.has_next) launch_qr(f, k0 + SB, f.Vnext); });
+    const bool two_rows = dense_fused_rows_per_lane(p.npn) == 2;
+    double lb = 0.0;      // (one label per kernel symbol, bytes of THIS launch: 16 np'^2 per matrix)
+    if (f.prof)
+        for (int n : b.h_n) {
+            const double q = (double)n - k0 - 2 * SB;
+            if (n - k0 - SB >= 2 && q >= 1.0) lb += 16.0 * q * q;
+        }
+    dense_timed(f, two_rows ? "eig_sbr_fused" : "eig_sbr_fused1", lb, [&] {
+        if (!p.fused) return;
+        const int tiles = dense_fused_tiles(p.npn);
+        hipLaunchKernelGGL((two_rows ? sbr_fused_kernel<true, 2> : sbr_fused_kernel<true, 1>), dim3(f.cnt8 * tiles), dim3(S2_NT),
+                           0, f.s, k0, b.n.p, b.moff.p, b.voff.p, b.W.p, f.Vcur, b.Zbuf.p, f.Vnext, b.Xbuf.p, b.goff.p, b.Gbuf.p,
+                           b.trash.p, b.count, tiles, SB, (const int *)nullptr, (const double *)nullptr,
+                           (const double *)nullptr, (const int *)nullptr);
+    });
+    dense_timed(f, "eig_sbr_z", 0.0, [&] { if (p.has_next) launch_z(f, k0 + SB, f.Vnext); });
+    std::swap(f.Vcur, f.Vnext);
+}
+
+// 4. stage 2: band -> tridiagonal
+static void dense_band_chase(DenseReduce &f) {
+    const EigBatch &b = f.b;
+    const DenseChasePlan c = dense_chase_plan(f.nmax);
+    double cflops = 0.0;
+    for (int n : b.h_n) cflops += 6.0 * (double)n * n * SB;
+    profiler().begin(f.s);
+    hipLaunchKernelGGL(c.band_in_lds ? band_chase_kernel<true> : band_chase_kernel<false>, dim3(b.count), dim3(CHASE_NT),
+                       c.lds_bytes, f.s, b.n.p, b.moff.p, b.voff.p, b.roff.p, b.W.p, b.bandg.p, b.d.p, b.e.p, b.rv.p, b.rtau.p);
+    SA_HIP_CHECK(hipGetLastError());
+    profiler().end(f.s, "eig_band_chase", 0.0, cflops);
+}
 
 void eig_tridiagonalize_two_stage(hipStream_t s, EigBatch &b, int phases) {
     if (!b.count) return;
-    static bool attr = false;
-    if (!attr) {
-#define SA_CHASE_ATTR(L, Q, T)                                                              \
-    SA_HIP_CHECK(hipFuncSetAttribute((const void *)band_chase_kernel<L, Q, T>,                 \
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
-        SA_CHASE_ATTR(true, 4, 1024); SA_CHASE_ATTR(false, 4, 1024);
-#undef SA_CHASE_ATTR
-        SA_HIP_CHECK(hipFuncSetAttribute((const void *)backtransform2_kernel<256>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        SA_HIP_CHECK(hipFuncSetAttribute((const void *)backtransform2_kernel<1024>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        SA_HIP_CHECK(hipFuncSetAttribute((const void *)sbr_qr_kernel<256, true>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        attr = true;
-    }
-    const size_t rows = (size_t)b.h_voff[b.count];
-    (void)rows;
-    b.h_roff.assign((size_t)b.count + 1, 0);
-    for (int i = 0; i < b.count; ++i) b.h_roff[i + 1] = b.h_roff[i] + chase_reflector_count(b.h_n[i]);
-    const size_t nrefl = (size_t)b.h_roff[b.count];
-    const int nmax0 = b.max_n;
-    const size_t fixed0 = sizeof(double) * (chase_config(nmax0).slots() * HAND) + sizeof(int) * (2 * (size_t)nmax0 + 4);
-    const bool in_lds0 = fixed0 + sizeof(double) * (size_t)nmax0 * LDB + 64 <= 160 * 1024;
-    b.h_xpoff.clear();
-    b.h_goff.assign((size_t)b.count + 1, 0);
-    for (int i = 0; i < b.count; ++i)
-        b.h_goff[i + 1] = b.h_goff[i] + (int64_t)((b.h_n[i] + 63) / 64) * SB * SB;
-    if (phases & 1) eig_batch_two_stage_buffers(b, nrefl, !in_lds0, s);
-    double flops = 0.0, bytes = 0.0;
-    for (int n : b.h_n) {
-        flops += 4.0 / 3.0 * (double)n * n * n;
-        bytes += 8.0 * (double)n * n;
-    }
-    // ---- stage 1 ----
-    const int nmax = b.max_n;
-    const bool prof = profiler().enabled;
-    // The product of panel p + 1 rides on the update of panel p (one fused kernel, vector FMAs with scalar-cache
-    // operands).  Measured alternatives (round 1, profiles/r01_*): separate product / update kernels, the same
-    // update on the matrix cores (fp64 MFMA sustains 46 TFLOP/s against 69 for v_fma_f64: tools/fma64_bench.hip)
-    // and a lower-triangle-only variant were all slower or equal -- none is bound by FMA issue or HBM bytes, they
-    // are bound by operand delivery (scalar-load latency).
-    constexpr int rpl = 2;      // rows per lane of the fused kernel (one row per lane: measured slower on the dense reduction, round 1)
+    two_stage_allow_large_lds();
+    DenseReduce f(s, b);
+    dense_offsets(f);
     if (phases & 1) {
-    if (!prof) profiler().begin(s);
-    const int cnt8 = 8 * div_up(b.count, 8);
-    auto launch_qr = [&](int k0, double *Vp) {
-        const int npmax = nmax - k0 - SB;
-        if (npmax <= 512)
-            hipLaunchKernelGGL(sbr_qr_reg_kernel, dim3(b.count), dim3(256), 0, s, k0, b.n.p, b.moff.p,
-                               b.voff.p, b.W.p, b.Tfac.p, Vp);
-        else if ((size_t)npmax * SB * sizeof(double) <= 96 * 1024)
-            hipLaunchKernelGGL((sbr_qr_kernel<256, true>), dim3(b.count), dim3(256),
-                               (size_t)npmax * SB * sizeof(double), s, k0, b.n.p, b.moff.p, b.voff.p,
-                               b.W.p, b.Tfac.p, Vp);
-        else
-            hipLaunchKernelGGL((sbr_qr_kernel<1024, false>), dim3(b.count), dim3(1024), 0, s, k0,
-                               b.n.p, b.moff.p, b.voff.p, b.W.p, b.Tfac.p, Vp);
-    };
-    auto launch_symm = [&](int k0, double *Vp) {
-        const int npmax = nmax - k0 - SB;
-        hipLaunchKernelGGL(sbr_symm_kernel, dim3(cnt8 * div_up(npmax, 64)), dim3(SY_NT), 0, s, k0,
-                           b.n.p, b.moff.p, b.voff.p, b.W.p, Vp, b.Xbuf.p, b.goff.p, b.Gbuf.p, b.count,
-                           div_up(npmax, 64));
-    };
-    auto launch_z = [&](int k0, double *Vp) {
-        const int npmax = nmax - k0 - SB;
-        hipLaunchKernelGGL(sbr_z_kernel, dim3(cnt8 * div_up(npmax, SM_NT)), dim3(SM_NT), 0, s, k0,
-                           b.n.p, b.voff.p, Vp, b.Tfac.p, b.Xbuf.p, b.goff.p, b.Gbuf.p,
-                           b.Zbuf.p, b.count, div_up(npmax, SM_NT));
-    };
-    if (nmax - SB >= 2) {
-        // look-ahead pipeline: the product of panel p+1 rides on the update of panel p
-        double *Vcur = b.Vpk.p, *Vnext = b.Vpk2.p;
-        if (prof) profiler().begin(s);
-        launch_qr(0, Vcur);
-        if (prof) { profiler().end(s, "eig_sbr_qr", 0.0, 0.0); profiler().begin(s); }
-        launch_symm(0, Vcur);
-        if (prof) { profiler().end(s, "eig_sbr_symm", 0.0, 0.0); profiler().begin(s); }
-        launch_z(0, Vcur);
-        if (prof) profiler().end(s, "eig_sbr_z", 0.0, 0.0);
-        for (int k0 = 0; nmax - k0 - SB >= 2; k0 += SB) {
-            const int npmax = nmax - k0 - SB;          // order of A22(k0)
-            const int npn = npmax - SB;                // order of A22' = A22(k0 + SB)
-            const bool has_next = npn >= 2;
-            if (prof) profiler().begin(s);
-            hipLaunchKernelGGL(sbr_panel_update_kernel, dim3(cnt8 * div_up(npmax, 256)), dim3(256), 0, s,
-                               k0, b.n.p, b.moff.p, b.voff.p, b.W.p, Vcur, b.Zbuf.p, b.count,
-                               div_up(npmax, 256));
-            if (prof) { profiler().end(s, "eig_sbr_panel", 0.0, 0.0); profiler().begin(s); }
-            if (has_next) launch_qr(k0 + SB, Vnext);
-            if (prof) { profiler().end(s, "eig_sbr_qr", 0.0, 0.0); profiler().begin(s); }
-            // two rows per lane are ~10 % faster per row slot but pad the strip count to 128 rows
-            const bool two_rows = rpl == 2 &&
-                (double)div_up(npn, 2 * SF_ROWS) * (2 * SF_ROWS) < 1.10 * (double)div_up(npn, SF_ROWS) * SF_ROWS;
-            if (npn >= 1 && two_rows)
-                hipLaunchKernelGGL((sbr_fused_kernel<true, 2>), dim3(cnt8 * div_up(npn, 2 * SF_ROWS)), dim3(S2_NT), 0, s,
-                                   k0, b.n.p, b.moff.p, b.voff.p, b.W.p, Vcur, b.Zbuf.p, Vnext, b.Xbuf.p,
-                                   b.goff.p, b.Gbuf.p, b.trash.p, b.count, div_up(npn, 2 * SF_ROWS), SB);
-            else if (npn >= 1)
-                hipLaunchKernelGGL((sbr_fused_kernel<true, 1>), dim3(cnt8 * div_up(npn, SF_ROWS)), dim3(S2_NT), 0, s,
-                                   k0, b.n.p, b.moff.p, b.voff.p, b.W.p, Vcur, b.Zbuf.p, Vnext, b.Xbuf.p,
-                                   b.goff.p, b.Gbuf.p, b.trash.p, b.count, div_up(npn, SF_ROWS), SB);
-            if (prof) {
-                // (one label per kernel symbol, bytes of THIS launch: 16 np'^2 per matrix)
-                double lb = 0.0;
-                for (int n : b.h_n) {
-                    const double q = (double)n - k0 - 2 * SB;
-                    if (n - k0 - SB >= 2 && q >= 1.0) lb += 16.0 * q * q;
-                }
-                profiler().end(s, two_rows ? "eig_sbr_fused" : "eig_sbr_fused1", lb, 0.0);
-                profiler().begin(s);
-            }
-            if (has_next) launch_z(k0 + SB, Vnext);
-            if (prof) profiler().end(s, "eig_sbr_z", 0.0, 0.0);
-            std::swap(Vcur, Vnext);
+        // (the buffers of both stages; the band and its bulge in global memory only where the chase will not hold them in LDS)
+        eig_batch_two_stage_buffers(b, f.nrefl, !dense_chase_plan(f.nmax).band_in_lds, s);
+        if (!f.prof) profiler().begin(s);
+        if (dense_panel(f.nmax, 0).exists) {
+            dense_first_panel(f);
+            for (int k0 = 0; dense_panel(f.nmax, k0).exists; k0 += SB) dense_panel_step(f, k0);
         }
+        SA_HIP_CHECK(hipGetLastError());
+        if (!f.prof) profiler().end(s, "eig_band_reduce", f.bytes, f.flops);
     }
-    SA_HIP_CHECK(hipGetLastError());
-    if (!prof) profiler().end(s, "eig_band_reduce", bytes, flops);
-    }
-    if (!(phases & 2)) return;
-    // ---- stage 2 ----
-    const ChaseConfig cc = chase_config(nmax);
-    const size_t fixed = sizeof(double) * (cc.slots() * HAND) + sizeof(int) * (2 * (size_t)nmax + 4);
-    const size_t band_bytes = sizeof(double) * (size_t)nmax * LDB;
-    const int in_lds = (fixed + band_bytes + 64 <= 160 * 1024) ? 1 : 0;
-    double cflops = 0.0;
-    for (int n : b.h_n) cflops += 6.0 * (double)n * n * SB;
-    profiler().begin(s);
-#define SA_CHASE(Q, T)                                                                                          \
-    if (cc.ncq == Q && cc.nt == T) {                                                                            \
-        if (in_lds)                                                                                             \
-            hipLaunchKernelGGL((band_chase_kernel<true, Q, T>), dim3(b.count), dim3(T), fixed + band_bytes + 64, s, \
-                               b.n.p, b.moff.p, b.voff.p, b.roff.p, b.W.p, b.bandg.p, in_lds, b.d.p, b.e.p,     \
-                               b.rv.p, b.rtau.p);                                                               \
-        else                                                                                                    \
-            hipLaunchKernelGGL((band_chase_kernel<false, Q, T>), dim3(b.count), dim3(T), fixed + 64, s, b.n.p,  \
-                               b.moff.p, b.voff.p, b.roff.p, b.W.p, b.bandg.p, in_lds, b.d.p, b.e.p, b.rv.p,    \
-                               b.rtau.p);                                                                       \
-    }
-    SA_CHASE(4, 1024)
-#undef SA_CHASE
-    SA_HIP_CHECK(hipGetLastError());
-    profiler().end(s, "eig_band_chase", 0.0, cflops);
+    if (phases & 2) dense_band_chase(f);
 }
 
 void eig_backtransform_two_stage(hipStream_t s, EigBatch &b, const int64_t *xoff, double *evecs) {
     if (!b.count) return;
-    const size_t lds = sizeof(double) * ((size_t)b.max_n + 2 * SB) + sizeof(int) * ((size_t)b.max_n + 4) + 64;
-    SA_REQUIRE(lds <= 160 * 1024, "agglomerate too large for the LDS-resident back-transformation");
+    const DenseBackPlan plan = dense_back_plan(b.max_n);
+    SA_REQUIRE(plan.lds_bytes <= DENSE_LDS_MAX, "agglomerate too large for the LDS-resident back-transformation");
     double flops = 0.0;
     for (int i = 0; i < b.count; ++i) flops += 4.0 * (double)b.h_n[i] * b.h_n[i] * b.h_m[i];
     profiler().begin(s);
-    if (b.max_n > 1024)
-        hipLaunchKernelGGL((backtransform2_kernel<1024>), dim3(b.count), dim3(1024), lds, s, b.n.p,
-                           b.moff.p, b.voff.p, b.roff.p, b.W.p, b.Tfac.p, b.rv.p, b.rtau.p, b.dis.p,
-                           b.m.p, xoff, evecs);
-    else
-        hipLaunchKernelGGL((backtransform2_kernel<256>), dim3(b.count), dim3(256), lds, s, b.n.p,
-                           b.moff.p, b.voff.p, b.roff.p, b.W.p, b.Tfac.p, b.rv.p, b.rtau.p, b.dis.p,
-                           b.m.p, xoff, evecs);
+    hipLaunchKernelGGL(plan.threads == 1024 ? backtransform2_kernel<1024> : backtransform2_kernel<256>, dim3(b.count),
+                       dim3(plan.threads), plan.lds_bytes, s, b.n.p, b.moff.p, b.voff.p, b.roff.p, b.W.p, b.Tfac.p, b.rv.p,
+                       b.rtau.p, b.dis.p, b.m.p, xoff, evecs);
     SA_HIP_CHECK(hipGetLastError());
     profiler().end(s, "eig_backtransform", 0.0, flops);
 }
@@ -1586,7 +1543,7 @@ __global__ __launch_bounds__(256) void ss_init_kernel(const int *__restrict__ ns
     const short *pm = perm ? perm + voff[b] : nullptr;
     for (int idx = threadIdx.x; idx < n * NB; idx += 256) {
         const int r = idx / NB, pr = pm ? pm[r] : r;       // (dis is in agglomerate order, the matrix in perm order)
-        Xb[pr * NB + (idx % NB)] = ((idx % NB) == 0) ? (x0c ? x0c[voff[b] + r] : 1.0) / db[r] : unit_rand_ss((unsigned)(pr * NB + (idx % NB)), (unsigned)n);
+        Xb[pr * NB + (idx % NB)] = ((idx % NB) == 0) ? (x0c ? x0c[voff[b] + r] : 1.0) / db[r] : unit_rand((unsigned)(pr * NB + (idx % NB)), (unsigned)n);
     }
 }
 
@@ -2382,7 +2339,7 @@ __global__ __launch_bounds__(256) void ss_lock_kernel(const int *__restrict__ li
         for (int q = 0; q < SS_LOCK_PITCH; ++q) Vb[(size_t)r * SS_LOCK_PITCH + q] = q < SS_LOCK ? x[q] : 0.0;
 #pragma unroll
         for (int q = 0; q < SS_B; ++q)
-            Xb[(size_t)r * SS_B + q] = q < SS_B - SS_LOCK ? x[SS_LOCK + q] : unit_rand_ss((unsigned)(r * SS_B + q) + 0x9E3779B9u, (unsigned)n + 17u);
+            Xb[(size_t)r * SS_B + q] = q < SS_B - SS_LOCK ? x[SS_LOCK + q] : unit_rand((unsigned)(r * SS_B + q) + 0x9E3779B9u, (unsigned)n + 17u);
     }
     __shared__ double m_old[SS_B];
     if (threadIdx.x < SS_B) m_old[threadIdx.x] = mu[(size_t)b * SS_B + threadIdx.x];
@@ -2996,7 +2953,7 @@ static void ss_factor_blocked(hipStream_t s, const SsWalk &w) {
     const size_t rows = (size_t)b.h_voff[b.count];
     const size_t pstride = (rows * SB + 15) / 16 * 16;
     if (b.ss_sub_n < pstride * G * 2) {      // (both operand sets, whichever factorisation comes first)
-        b.ss_sub = eig_arena_subpanels(b, pstride * G * 2);
+        b.ss_sub = eig_arena_scratch(b, EigScratch::SubPanels,pstride * G * 2);
         b.ss_sub_n = pstride * G * 2;
     }
     double *Pc = b.ss_sub;
@@ -3182,7 +3139,7 @@ static void ss_certify_counts(SsFactor &f) {
     }
     DBuf<int64_t> d_soff;
     d_soff.from_host(soff, s);
-    b.ss_save = eig_arena_bandsave(b, (size_t)soff[b.count] + 1);
+    b.ss_save = eig_arena_scratch(b, EigScratch::BandSave,(size_t)soff[b.count] + 1);
     b.ss_soff = std::move(d_soff);
     launch_band_copy<false>(s, b);
     hipLaunchKernelGGL(ss_shift_kernel, dim3(b.count), dim3(256), 0, s, b.n.p, b.moff.p, b.W.p, b.window_vu);
@@ -3367,7 +3324,6 @@ static bool ss_collect_pivots(SsFactor &f) {
 // counts.  Returns false when the batch has to take the dense path.
 bool eig_subspace_factor(hipStream_t s, EigBatch &b) {
     b.ss_nb = 8;      // block of the iteration; 16 where more pairs are wanted than eight vectors reach (decided after the inertia pass)
-    b.h_xpoff.clear();
     b.h_goff.assign((size_t)b.count + 1, 0);
     b.h_roff.assign((size_t)b.count + 1, 0);
     eig_batch_two_stage_buffers(b, 1, false, s);

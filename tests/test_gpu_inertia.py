@@ -79,7 +79,7 @@ import sys, numpy as np
 sys.path.insert(0, %r)
 from saamge_amd import capi
 
-def unit_rand(a, b):            # csrc/eig2.hip unit_rand_ss
+def unit_rand(a, b):            # csrc/eig_device.h unit_rand
     M = 0xFFFFFFFF
     h = ((a * 2654435761) & M) ^ ((b + 0x9e3779b9 + ((a << 6) & M) + (a >> 2)) & M)
     h ^= h >> 16; h = (h * 0x85ebca6b) & M; h ^= h >> 13; h = (h * 0xc2b2ae35) & M; h ^= h >> 16

@@ -83,8 +83,9 @@ def test_batched_lower_eigens_vs_lapack(seed):
 
 def test_batched_lower_eigens_large_agglomerates():
     """Agglomerate sizes of the headline configs (405 = 8x8x4 Q1, 729 = 8^3 Q1) and beyond the
-    LDS-resident band (n > ~1150: band and bulge in global memory; 2187 = the 4^3 Q2 elasticity
-    agglomerate of BASELINE config 5)."""
+    LDS-resident band of the dense path (n > 588: band and bulge in global memory, csrc/eig_dense_plan.h;
+    2187 = the 4^3 Q2 elasticity agglomerate of BASELINE config 5).  Under the default eig_min_n these matrices
+    take the few-eigenpairs path: test_dense_path_reaches_every_kernel_plan below holds the dense path to them."""
     capi, o = _capi(), _oracle()
     rng = np.random.default_rng(5)
     mats, diags = [], []
@@ -98,6 +99,52 @@ def test_batched_lower_eigens_large_agglomerates():
     res = capi.lower_eigens_batched(mats, diags, -1.0, theta)
     for L, D, (w, X) in zip(mats, diags, res):
         wr, Xr = o.lower_eigens_dense(L, D, theta)
+        assert len(w) == len(wr) and len(w) >= 1
+        assert np.allclose(w, wr, rtol=0, atol=EIG_TOL)
+        assert np.allclose(X.T @ (D[:, None] * X), np.eye(len(w)), atol=1e-10)
+        R = L @ X - (D[:, None] * X) * w[None, :]
+        assert np.abs(R).max() <= 1e-10 * max(1.0, np.abs(L).max())
+        assert np.allclose(_proj(X, D), _proj(Xr, D), atol=PROJ_TOL)
+
+
+_LARGE_AGGLOMERATES = {}
+
+
+def _large_agglomerates():
+    """The four matrices of the test above (same generator, seed 5), their diagonals and the oracle's pairs at theta = 0.01:
+    built once, shared and left unchanged by the cases below."""
+    if not _LARGE_AGGLOMERATES:
+        o = _oracle()
+        rng = np.random.default_rng(5)
+        for n in [405, 729, 1300, 2187]:
+            G = sp.random(n, n, density=8.0 / n, random_state=rng).toarray()
+            W = np.abs(G + G.T)
+            L = np.diag(W.sum(axis=1)) - W + 1e-4 * np.diag(rng.random(n))
+            D = o.snd_D_from_dense(L)
+            _LARGE_AGGLOMERATES[n] = (L, D, o.lower_eigens_dense(L, D, 0.01))
+    return _LARGE_AGGLOMERATES
+
+
+# Batches that reach the plan values of the dense path (csrc/eig_dense_plan.h, DESIGN.md section 4.17) under eig_dense_only:
+#   [405]         register QR only (npmax <= 389), band in LDS (405 <= 588), 256-thread back-transformation
+#   [729]         register and LDS QR (npmax = 713 at k0 = 0), band in HBM
+#   [1300, 2187]  all three QR kernels as k0 grows (npmax = 2171: the 1 024-thread one), band in HBM, 1 024-thread
+#                 back-transformation, both variants of the fused update
+#   [405] with eig_dense_one_stage: the one-stage kernel
+# (The global-workspace eigenvector kernel, from 2 749 rows on, is reached by no GPU test: tests/cxx/eig_dense_plan_test.cpp
+# holds its threshold.)
+@pytest.mark.parametrize("sizes,one_stage", [((405,), 0), ((729,), 0), ((1300, 2187), 0), ((405,), 1)])
+def test_dense_path_reaches_every_kernel_plan(sizes, one_stage):
+    """The assertions of test_batched_lower_eigens_large_agglomerates, on its matrices, with the dense path forced."""
+    capi = _capi()
+    cases = [_large_agglomerates()[n] for n in sizes]
+    theta = 0.01
+    old = capi.set_options(eig_dense_only=1, eig_dense_one_stage=one_stage)
+    try:
+        res = capi.lower_eigens_batched([L for L, _, _ in cases], [D for _, D, _ in cases], -1.0, theta)
+    finally:
+        capi.set_options(eig_dense_only=old.eig_dense_only, eig_dense_one_stage=old.eig_dense_one_stage)
+    for (L, D, (wr, Xr)), (w, X) in zip(cases, res):
         assert len(w) == len(wr) and len(w) >= 1
         assert np.allclose(w, wr, rtol=0, atol=EIG_TOL)
         assert np.allclose(X.T @ (D[:, None] * X), np.eye(len(w)), atol=1e-10)
