@@ -897,6 +897,43 @@ int  saamge_amd_operator_path_counts(const saamge_amd_operator *op, long long co
  * that follow, process-wide.  Defaults and upper limits 64 and 4096; a negative value: the default. */
 int  saamge_amd_operator_set_path_limits(int short_candidates, int lds_candidates);
 
+/* ---- lowest eigenpairs of A x = lambda M x: LOBPCG with soft locking, preconditioned by the V-cycle ----
+ * The definition is saamge_amd/lobpcg_model.py; DESIGN.md section 4.18.  The library keeps essential dofs as decoupled
+ * diagonal rows, each of them an eigenvector of the pencil with eigenvalue a_ii / m_ii that may lie among the lowest:
+ * with constrain_essential the iteration runs in the subspace that is zero there (invariant under A, under an M whose
+ * essential rows and columns are eliminated like A's, and under the V-cycle followed by the mask). */
+typedef struct saamge_amd_lobpcg_options {
+    int nev;                  /* wanted pairs, 1 .. 16 */
+    int block;                /* nb, nev <= nb <= 16; 0: nev */
+    double tol;               /* pair j accepted when ||A x - lambda M x||_2 <= tol * lambda * ||M x||_2; > 0 */
+    int max_iter;             /* >= 0 */
+    int constrain_essential;  /* 1: rows the hierarchy was set up with as essential (SAAMGE_AMD_ON_ESS_DOMAIN_BORDER in its
+                                 level-0 agg_flags, what saamge_amd_get_mis returns) are held at zero in every vector */
+    unsigned seed;            /* start block when x0 == NULL */
+} saamge_amd_lobpcg_options;
+void saamge_amd_lobpcg_options_default(saamge_amd_lobpcg_options *o);   /* 1, 0, 1e-8, 100, 1, 0 */
+/* A = the hierarchy's level-0 operator, B = its V-cycle (plugs included).  M: n x n CSR, symmetric positive definite,
+ * 64-bit row offsets (what saamge_amd_operator_arrays returns), NULL = identity.  x0: n x nb column-major or NULL.
+ * evals (host, nev), evecs (n x nev column-major, M-orthonormal), res (host, nev: the rho_j), hist (host,
+ * (max_iter + 1) x nev row-major, may be NULL; rows 0 .. *iters are written).  M, x0, evecs: host or device pointers, each
+ * on its own.  res, iters, converged may be NULL.  *converged = 0 with a zero return: max_iter reached, or a breakdown (a
+ * Gram matrix of the basis that is not safely positive definite, twice in a row); evals, evecs hold the best pairs so far.
+ * Refused with a nonzero return, the argument named in saamge_amd_last_error, before any work memory is taken, any kernel
+ * is launched or any output written (the hierarchy's flags and a device-resident M are read to be checked): a NULL h, o, evals or
+ * evecs; nev, block, tol, max_iter out of range; 3 nb above the number of unconstrained rows; M offsets that do not start
+ * at 0 or decrease, a column outside [0, n); a level 0 that is row-partitioned over several ranks.
+ * Work memory: 9 nb n doubles (6 nb n without M) from the library's pool, returned before the call returns. */
+int saamge_amd_lobpcg(saamge_amd_hierarchy *h, const long long *Mrowptr, const int *Mcol, const double *Mval,
+                      const saamge_amd_lobpcg_options *o, const double *x0, double *evals, double *evecs,
+                      double *res, int *iters, int *converged, double *hist);
+/* The two block kernels on their own (tests), like saamge_amd_spgemm; host or device pointers, blocks column-major.
+ * gram: G_host (p x q, column-major) = S^T T, 1 <= p, q <= 48, lds, ldt >= n; T == S (and ldt == lds, q == p) does half
+ * the work; deterministic.  combine: Y (n x q) = S C (accumulate != 0: Y += S C), C_host p x q column-major; Y may be S
+ * itself (the same pointer and leading dimension), any other overlap of the two is refused. */
+int saamge_amd_blockvec_gram(int n, int p, const double *S, long long lds, int q, const double *T, long long ldt, double *G_host);
+int saamge_amd_blockvec_combine(int n, int p, const double *S, long long lds, int q, const double *C_host, double *Y,
+                                long long ldy, int accumulate);
+
 #ifdef __cplusplus
 }
 #endif

@@ -163,6 +163,38 @@ inline int kalchev_pcg(ml_data_t *h, const double *b, double *x, int print_iter 
     return conv ? iters : -iters;
 }
 
+// == lowest eigenpairs of A x = lambda M x (saamge_amd_lobpcg): LOBPCG with soft locking, B = the hierarchy's V-cycle ==
+// Options with the library's defaults; a mass matrix as three arrays (host or device, 64-bit offsets; all null: identity).
+struct LobpcgOptions : saamge_amd_lobpcg_options {
+    LobpcgOptions() { saamge_amd_lobpcg_options_default(this); }
+};
+struct MassMatrix {
+    const long long *rowptr = nullptr;
+    const int *col = nullptr;
+    const double *val = nullptr;
+};
+struct LobpcgResult {
+    std::vector<double> evals, res;     // nev each; res: ||A x - lambda M x|| / (lambda ||M x||)
+    std::vector<double> hist;           // (iters + 1) x nev, row-major
+    int iters = 0;
+    bool converged = false;             // false: max_iter reached or a breakdown; evals / evecs are the best pairs so far
+};
+// evecs: n x nev column-major, host or device; x0: n x nb column-major (host or device) or nullptr for the hashed start
+inline LobpcgResult lobpcg(ml_data_t *h, const LobpcgOptions &o, double *evecs, const MassMatrix &M = MassMatrix(),
+                           const double *x0 = nullptr) {
+    LobpcgResult r;
+    const size_t nev = o.nev > 0 ? (size_t)o.nev : 0, rows = o.max_iter >= 0 ? (size_t)o.max_iter + 1 : 0;
+    r.evals.assign(nev, 0.0);
+    r.res.assign(nev, 0.0);
+    r.hist.assign(rows * nev, 0.0);
+    int conv = 0;
+    if (saamge_amd_lobpcg(h, M.rowptr, M.col, M.val, &o, x0, r.evals.data(), evecs, r.res.data(), &r.iters, &conv, r.hist.data()))
+        throw std::runtime_error(saamge_amd_last_error());
+    r.converged = conv != 0;
+    r.hist.resize((size_t)(r.iters + 1) * nev);
+    return r;
+}
+
 // == agglomerate partitions built on the device (saamge_amd_partition_graph / saamge_amd_partition_mesh) ==
 // One level on a symmetric CSR graph (host or device arrays): part is resized to n; returns the number of parts produced
 // (elems_per_agg is a target).  o == nullptr: the library's defaults.  The options struct is handed on whole (o->seeding = 1:

@@ -50,6 +50,7 @@ SYMBOLS = [
     "saamge_amd_mesh_lift_order2", "saamge_amd_mesh_lift_arrays", "saamge_amd_mesh_lift_get", "saamge_amd_mesh_lift_free",
     "saamge_amd_mesh_refine", "saamge_amd_mesh_refine_arrays", "saamge_amd_mesh_refine_get", "saamge_amd_mesh_refine_level_info",
     "saamge_amd_mesh_refine_interp_arrays", "saamge_amd_mesh_refine_interp_get", "saamge_amd_mesh_refine_free",
+    "saamge_amd_lobpcg_options_default", "saamge_amd_lobpcg", "saamge_amd_blockvec_gram", "saamge_amd_blockvec_combine",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong))
@@ -507,6 +508,37 @@ class Hierarchy(_Handle):
                                      C.c_double(abs_tol), C.c_int(max_iter), C.c_int(int(squared_tol)),
                                      C.c_int(int(zero_guess)), C.byref(it), C.byref(conv), _ptr(hist)))
         return x, it.value, bool(conv.value), hist[:it.value + 1].copy()
+
+    def lobpcg(self, nev, block=0, M=None, x0=None, tol=1e-8, max_iter=100, constrain_essential=True, seed=0, evecs=None):
+        """The lowest nev pairs of A x = lambda M x (saamge_amd_lobpcg; the definition: saamge_amd.lobpcg_model).  M: None,
+        a scipy matrix, or (rowptr, col, val) with 64-bit offsets (numpy arrays or device pointers / tensors); x0: n x nb
+        (numpy, any layout; or a device pointer / tensor holding it column-major); evecs: a device pointer / tensor for
+        n x nev column-major, or None.  -> lam, X (n x nev; `evecs` itself when given), res, iters, converged, hist."""
+        n = int(self.level_info(0)["n"])
+        nb = block or nev
+        o = LobpcgOptions()
+        load().saamge_amd_lobpcg_options_default(C.byref(o))
+        o.nev, o.block, o.tol, o.max_iter = int(nev), int(block), float(tol), int(max_iter)
+        o.constrain_essential, o.seed = int(bool(constrain_essential)), int(seed)
+        if M is None:
+            m = (None, None, None)
+        elif isinstance(M, tuple):
+            m = M
+        else:
+            import scipy.sparse as sp
+            M = sp.csr_matrix(M)
+            m = (np.ascontiguousarray(M.indptr, dtype=np.int64), np.ascontiguousarray(M.indices, dtype=np.int32),
+                 np.ascontiguousarray(M.data, dtype=np.float64))
+        if isinstance(x0, np.ndarray):
+            assert x0.shape == (n, nb)
+            x0 = np.ascontiguousarray(x0.T, dtype=np.float64)       # column-major n x nb
+        lam, res = np.zeros(max(nev, 0)), np.zeros(max(nev, 0))
+        X = np.zeros((max(nev, 0), n)) if evecs is None else evecs
+        hist = np.zeros((max(max_iter, 0) + 1, max(nev, 0)))
+        it, conv = C.c_int(0), C.c_int(0)
+        _check(load().saamge_amd_lobpcg(self.h, _ptr(m[0]), _ptr(m[1]), _ptr(m[2]), C.byref(o), _ptr(x0), _ptr(lam), _ptr(X),
+                                        _ptr(res), C.byref(it), C.byref(conv), _ptr(hist)))
+        return lam, (X.T if evecs is None else evecs), res, it.value, int(conv.value), hist[:it.value + 1].copy()
 
     # ---- inspection ----
     @property
@@ -1717,6 +1749,47 @@ class Operator(_Handle):
 def operator_path_limits(short_candidates=-1, lds_candidates=-1):
     """Tests: candidate limits of the short and the LDS path of the assemblies that follow (-1: the default)."""
     _check(load().saamge_amd_operator_set_path_limits(C.c_int(int(short_candidates)), C.c_int(int(lds_candidates))))
+
+
+class LobpcgOptions(C.Structure):      # saamge_amd_lobpcg_options
+    _fields_ = [("nev", C.c_int), ("block", C.c_int), ("tol", C.c_double), ("max_iter", C.c_int),
+                ("constrain_essential", C.c_int), ("seed", C.c_uint)]
+
+
+def _block(a):
+    """a block of vectors for the C ABI: numpy n x p -> (column-major copy, ld = n); (pointer or tensor, n, p, ld) as given"""
+    if isinstance(a, tuple):
+        return a
+    a = np.asarray(a, dtype=np.float64)
+    return np.ascontiguousarray(a.T), a.shape[0], a.shape[1], a.shape[0]
+
+
+def blockvec_gram(S, T=None):
+    """G = S^T T (saamge_amd_blockvec_gram); T = None: T is S itself (half the work).  A block: numpy n x p, or
+    (pointer / tensor / column-major numpy buffer, n, p, ld)."""
+    s, n, p, lds = _block(S)
+    t, n2, q, ldt = (s, n, p, lds) if T is None else _block(T)
+    assert n2 == n
+    G = np.zeros((max(q, 0), max(p, 0)))
+    _check(load().saamge_amd_blockvec_gram(C.c_int(n), C.c_int(p), _ptr(s), C.c_longlong(lds), C.c_int(q), _ptr(t),
+                                           C.c_longlong(ldt), _ptr(G)))
+    return G.T
+
+
+def blockvec_combine(S, Cm, Y=None, accumulate=False):
+    """Y = S C or Y += S C (saamge_amd_blockvec_combine).  S, Y: blocks as blockvec_gram takes them (Y None: a new numpy
+    block, returned n x q; Y given as a tuple is written in place and returned as given)."""
+    s, n, p, lds = _block(S)
+    Cm = np.asarray(Cm, dtype=np.float64)
+    q = Cm.shape[1]
+    assert Cm.shape[0] == p
+    fresh = Y is None or not isinstance(Y, tuple)
+    y, n2, q2, ldy = _block(np.zeros((n, q)) if Y is None else Y)
+    assert (n2, q2) == (n, q)
+    c = np.ascontiguousarray(Cm.T)      # column-major p x q; named, so that it outlives the pointer taken from it
+    _check(load().saamge_amd_blockvec_combine(C.c_int(n), C.c_int(p), _ptr(s), C.c_longlong(lds), C.c_int(q),
+                                              _ptr(c), _ptr(y), C.c_longlong(ldy), C.c_int(int(accumulate))))
+    return y.T if fresh else Y
 
 
 def pool_counts(reset=False):

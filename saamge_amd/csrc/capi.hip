@@ -2,10 +2,14 @@
 #include <cstdlib>
 #include "../../include/saamge_amd.h"
 
+#include <cmath>
+#include <memory>
 #include <string>
 
+#include "blockvec.h"
 #include "elmat.h"
 #include "hierarchy.h"
+#include "lobpcg.h"
 #include "mesh_faces.h"
 #include "mesh_lift.h"
 #include "mesh_refine.h"
@@ -1657,6 +1661,127 @@ void saamge_amd_operator_free(saamge_amd_operator *op) {
         delete op;
         dev_pool_close_stream(s);
     }
+}
+
+// ---- lowest eigenpairs (lobpcg.hip) and its block kernels on their own (blockvec.hip) ------------------------------------
+void saamge_amd_lobpcg_options_default(saamge_amd_lobpcg_options *o) {
+    if (!o) return;
+    o->nev = 1;
+    o->block = 0;
+    o->tol = 1e-8;
+    o->max_iter = 100;
+    o->constrain_essential = 1;
+    o->seed = 0;
+}
+
+int saamge_amd_lobpcg(saamge_amd_hierarchy *h, const long long *Mrowptr, const int *Mcol, const double *Mval,
+                      const saamge_amd_lobpcg_options *o, const double *x0, double *evals, double *evecs,
+                      double *res, int *iters, int *converged, double *hist) {
+    SA_API_BEGIN
+    SA_REQUIRE(h, "lobpcg: null argument: h");
+    SA_REQUIRE(o, "lobpcg: null argument: o");
+    SA_REQUIRE(evals, "lobpcg: null argument: evals");
+    SA_REQUIRE(evecs, "lobpcg: null argument: evecs");
+    LobpcgOptions lo;
+    SA_REQUIRE(o->nev >= 1 && o->nev <= BV_MAX_NORMS, "lobpcg: nev must lie in 1 .. 16");
+    SA_REQUIRE(o->block == 0 || (o->block >= o->nev && o->block <= BV_MAX_NORMS), "lobpcg: block must be 0 or lie in nev .. 16");
+    SA_REQUIRE(std::isfinite(o->tol) && o->tol > 0.0, "lobpcg: tol must be positive");
+    SA_REQUIRE(o->max_iter >= 0, "lobpcg: max_iter must not be negative");
+    lo.nev = o->nev;
+    lo.nb = o->block ? o->block : o->nev;
+    lo.tol = o->tol;
+    lo.max_iter = o->max_iter;
+    lo.constrain_essential = o->constrain_essential != 0;
+    lo.seed = o->seed;
+    Hierarchy &H = *h->H;
+    require_device(H);
+    Level &L0 = *H.levels[0];
+    SA_REQUIRE(!L0.dist.on, "lobpcg: h: level 0 is row-partitioned over several ranks (multi-rank is not supported)");
+    hipStream_t s = H.stream;
+    const int n = L0.A.nrows;
+    long nfree = n;
+    if (lo.constrain_essential) {
+        fetch_relations_ae_host(L0.rel, L0.drel, s);
+        SA_REQUIRE((int)L0.rel.agg_flags.size() == n && (int)L0.drel.flags.n == n, "lobpcg: h: the hierarchy holds no flags of its rows");
+        for (signed char f : L0.rel.agg_flags) nfree -= (f & FLAG_ON_ESS_BORDER) ? 1 : 0;
+    }
+    SA_REQUIRE(3L * lo.nb <= nfree, "lobpcg: block: 3 nb exceeds the number of unconstrained rows");
+    DCsr M;
+    if (Mrowptr) {
+        SA_REQUIRE(Mcol && Mval, "lobpcg: Mcol, Mval: null with row offsets given");
+        const hvec<long long> rp = fetch_host(Mrowptr, (size_t)n + 1, s);
+        SA_REQUIRE(rp[0] == 0, "lobpcg: Mrowptr: the row offsets must start at 0");
+        for (int i = 0; i < n; ++i) SA_REQUIRE(rp[i + 1] >= rp[i], "lobpcg: Mrowptr: the row offsets must not decrease");
+        const hvec<int> cols = fetch_host(Mcol, (size_t)rp[n], s);
+        for (int c : cols) SA_REQUIRE(c >= 0 && c < n, "lobpcg: Mcol: a column index outside [0, n)");
+        M.nrows = M.ncols = n;
+        M.nnz = rp[n];
+        import_rowptr(M.rowptr, Mrowptr, 64, (size_t)n + 1, s);
+        import_array(M.col, Mcol, (size_t)M.nnz, s);
+        import_array(M.val, Mval, (size_t)M.nnz, s);
+        M.lanes_per_row = pick_lanes_per_row(M.nnz, n);
+    }
+    DBuf<double> start;
+    if (x0) import_array(start, x0, (size_t)n * lo.nb, s);
+    std::vector<double> ev(lo.nev), rs(lo.nev);
+    int it = 0, conv = 0;
+    {
+        VecOut vx(evecs, (size_t)n * lo.nev, s, false);
+        lobpcg_solve(H, Mrowptr ? &M : nullptr, lo, x0 ? start.p : nullptr, ev.data(), vx.p, rs.data(), &it, &conv, hist);
+        vx.finish();
+    }
+    std::copy(ev.begin(), ev.end(), evals);
+    if (res) std::copy(rs.begin(), rs.end(), res);
+    if (iters) *iters = it;
+    if (converged) *converged = conv;
+    SA_API_END
+}
+
+// a column-major block (rows x cols, leading dimension ld) of a host or device pointer, on the device
+static size_t block_extent(int rows, int cols, long long ld) { return (size_t)(cols - 1) * (size_t)ld + (size_t)rows; }
+
+int saamge_amd_blockvec_gram(int n, int p, const double *S, long long lds, int q, const double *T, long long ldt, double *G_host) {
+    SA_API_BEGIN
+    SA_REQUIRE(S && T && G_host, "blockvec_gram: null argument");
+    SA_REQUIRE(n >= 1, "blockvec_gram: n must be positive");
+    SA_REQUIRE(p >= 1 && p <= BV_MAX_COLS, "blockvec_gram: p must lie in 1 .. 48");
+    SA_REQUIRE(q >= 1 && q <= BV_MAX_COLS, "blockvec_gram: q must lie in 1 .. 48");
+    SA_REQUIRE(lds >= n, "blockvec_gram: lds is below n");
+    SA_REQUIRE(ldt >= n, "blockvec_gram: ldt is below n");
+    hipStream_t s = 0;
+    set_thread_stream(s);
+    VecIn vs(S, block_extent(n, p, lds), s);
+    const bool same = T == S && ldt == lds && q == p;
+    std::unique_ptr<VecIn> vt(same ? nullptr : new VecIn(T, block_extent(n, q, ldt), s));
+    DBuf<double> scratch(bv_gram_scratch(n, p, q)), G((size_t)p * q);
+    bv_gram(s, n, p, vs.p, (long)lds, q, same ? vs.p : vt->p, (long)ldt, scratch.p, G.p);
+    read_back(G_host, G.p, (size_t)p * q, s);
+    SA_API_END
+}
+
+int saamge_amd_blockvec_combine(int n, int p, const double *S, long long lds, int q, const double *C_host, double *Y,
+                                long long ldy, int accumulate) {
+    SA_API_BEGIN
+    SA_REQUIRE(S && C_host && Y, "blockvec_combine: null argument");
+    SA_REQUIRE(n >= 1, "blockvec_combine: n must be positive");
+    SA_REQUIRE(p >= 1 && p <= BV_MAX_COLS, "blockvec_combine: p must lie in 1 .. 48");
+    SA_REQUIRE(q >= 1 && q <= BV_MAX_COLS, "blockvec_combine: q must lie in 1 .. 48");
+    SA_REQUIRE(lds >= n, "blockvec_combine: lds is below n");
+    SA_REQUIRE(ldy >= n, "blockvec_combine: ldy is below n");
+    SA_REQUIRE(bv_combine_aliasing_ok(n, p, S, (long)lds, q, Y, (long)ldy),
+               "blockvec_combine: Y overlaps S without being S itself (the same pointer and leading dimension)");
+    hipStream_t s = 0;
+    set_thread_stream(s);
+    const bool in_place = Y == S;
+    // in place the block is max(p, q) columns wide: one buffer that is read as S and written as Y
+    VecOut vy(Y, block_extent(n, in_place ? std::max(p, q) : q, ldy), s, accumulate != 0 || in_place || ldy > n);
+    std::unique_ptr<VecIn> vs(in_place ? nullptr : new VecIn(S, block_extent(n, p, lds), s));
+    DBuf<double> C;
+    C.assign(C_host, (size_t)p * q, s);
+    BvBlocks B{{in_place ? vy.p : vs->p, nullptr, nullptr}, {vy.p, nullptr, nullptr}, 1};
+    bv_combine(s, n, p, q, C.p, accumulate != 0, B, (long)lds, (long)ldy);
+    vy.finish();
+    SA_API_END
 }
 
 }  // extern "C"

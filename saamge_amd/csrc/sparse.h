@@ -32,6 +32,20 @@ void build_dinv_neg(hipStream_t s, const DCsr &A, double *sqrt_diag_tmp, double 
 // byte codes of the smoother's diagonal factor (operators with <= 256 distinct values of it and the staged coded format)
 void build_dinv_codes(hipStream_t s, DCsr &A, const double *dinv_neg, const Options &opt);
 
+// the sum of v over a workgroup of 256 lanes in a fixed order (valid on thread 0); sh: 4 doubles of LDS.  Shared by the
+// deterministic reductions: dot below and the column norms of blockvec.hip.
+__device__ inline double block_sum_256(double v, double *sh) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+    if (l == 0) sh[w] = v;
+    __syncthreads();
+    double r = 0.0;
+    if (threadIdx.x == 0) r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    __syncthreads();
+    return r;
+}
+
 // deterministic dot product: out[0] = sum a_i b_i ; `partials` holds >= 1024 doubles
 void dot(hipStream_t s, int n, const double *a, const double *b, double *partials, double *out);
 // PCG fused vector updates, scalars on the device:

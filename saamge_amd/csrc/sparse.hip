@@ -1904,19 +1904,7 @@ void build_dinv_codes(hipStream_t s, DCsr &A, const double *dinv, const Options 
     D.src = dinv;
 }
 
-// ---- deterministic dot product -----------------------------------------------------------
-__device__ inline double block_sum_256(double v, double *sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-    if (l == 0) sh[w] = v;
-    __syncthreads();
-    double r = 0.0;
-    if (threadIdx.x == 0) r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    __syncthreads();
-    return r;  // valid on thread 0
-}
-
+// ---- deterministic dot product (block_sum_256: sparse.h) -----------------------------------
 __global__ __launch_bounds__(256) void dot_partial_kernel(int n, const double *__restrict__ a,
                                                           const double *__restrict__ b,
                                                           double *__restrict__ partials) {
