@@ -4,6 +4,7 @@
 // the sums are bit-reproducible and match the reference's accumulation order.
 #include "assemble.h"
 #include "eig_ss_plan.h"
+#include "devtab.h"
 
 #include <cstdlib>
 
@@ -1562,10 +1563,6 @@ __global__ __launch_bounds__(AI_NT) void asm_hash_kernel(AeInputs v, int hsize, 
     if (tid == 0 && blockIdx.y == 0) { h.h1 += dd_mix((unsigned long long)n + 0x4444444444444444ull); h.h2 += dd_mix((unsigned long long)n ^ 0x7777777777777777ull); }
     h.block_finish<true>(out, b);
 }
-__global__ void scatter_int_kernel(int n, const int *__restrict__ idx, const int *__restrict__ src, int *__restrict__ dst) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[idx[i]] = src[i];
-}
 __global__ __launch_bounds__(AI_NT) void asm_verify_kernel(AeInputs v, int hsize, const int *__restrict__ rep, int *__restrict__ differ) {
     extern __shared__ __align__(16) unsigned char ai_lds[];
     __shared__ AiHeads hd[AI_NT / 64];
@@ -1675,8 +1672,7 @@ void ae_build(hipStream_t s, const DevRelations &rel, const DCsr *A, const DevEl
                 // for the comparison with the classes of other chunks -- is their assembled form (DdSource kind 1)
                 if (batch.bw.n < (size_t)batch.count) batch.bw.alloc((size_t)batch.count);
                 SA_HIP_CHECK(hipMemsetAsync(batch.bw.p, 0, sizeof(int) * (size_t)batch.count, s));
-                hipLaunchKernelGGL(scatter_int_kernel, dim3(div_up(cb.count, 256)), dim3(256), 0, s, cb.count, d_reps.p, cb.bw.p, batch.bw.p);
-                SA_HIP_CHECK(hipGetLastError());
+                dev_scatter(s, cb.count, (const int *)d_reps.p, (const int *)cb.bw.p, batch.bw.p);
                 batch.has_bw = cb.has_bw;
                 batch.has_perm = cb.has_perm;
                 classes->src = eig_dedupe_source(batch);

@@ -717,9 +717,7 @@ static int spmv_entry(int nrows, int ncols, const void *rowptr, int rowptr_bits,
     A.nrows = nrows;
     A.ncols = ncols;
     import_rowptr(A.rowptr, rowptr, rowptr_bits, (size_t)nrows + 1, s);
-    roff_t nnz = 0;
-    SA_HIP_CHECK(hipMemcpyAsync(&nnz, A.rowptr.p + nrows, sizeof(roff_t), hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
+    roff_t nnz = read_one(A.rowptr.p + nrows, s);
     A.nnz = nnz;
     import_array(A.col, col, (size_t)A.nnz, s);
     import_array(A.val, val, (size_t)A.nnz, s);

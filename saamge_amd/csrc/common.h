@@ -218,6 +218,13 @@ inline hvec<T> fetch_host(const T *src, size_t n, hipStream_t s) {
     }
     return v;
 }
+// The first n values of a device buffer into a host vector (resized).  Only enqueues the copy: callers batch several under
+// one synchronise of their own.
+template <class T>
+inline void download(hvec<T> &dst, const DBuf<T> &src, size_t n, hipStream_t s) {
+    dst.resize(n);
+    if (n) SA_HIP_CHECK(hipMemcpyAsync(dst.data(), src.p, n * sizeof(T), hipMemcpyDeviceToHost, s));
+}
 // n values from the device in one transfer (synchronises the stream)
 template <class T>
 inline void read_back(T *dst, const T *src, size_t n, hipStream_t s) {
@@ -251,12 +258,6 @@ struct DCsr {
     mutable int max_row = -1;  // longest row (computed on first use by the fused AE assembly)
     Sell sell;  // optional SELL-64 copy for the SpMV family (sell.h)
 };
-
-// exclusive scans (mis.hip); out has n + 1 entries
-void exclusive_scan_int(hipStream_t s, int n, const int *in, int *out);
-// the same without the host synchronisation: `tile_sums` is the caller's scratch of div_up(n, 1024) + 1 ints
-void exclusive_scan_int_async(hipStream_t s, int n, const int *in, int *out, int *tile_sums);
-void exclusive_scan_off(hipStream_t s, int n, const int *in, roff_t *out);
 
 // Row offsets crossing the C ABI (sparse.hip).  In: int32 (the reference's HYPRE_Int; widened on the device)
 // or int64 (device pointers viewed in place); host or device pointer either way.  Out: narrowed to int32 for

@@ -10,6 +10,7 @@
 // their owners before each SpMV: pack kernel -> alltoallv (RCCL send/recv groups through
 // torch.distributed) -> unpack kernel.  No column renumbering, no second matrix copy.
 #include "dist.h"
+#include "devtab.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -44,12 +45,6 @@ __global__ __launch_bounds__(256) void halo_slice_kernel(int row0, int nloc, con
         out |= (c < row0 || c >= row0 + nloc);
     }
     if (out) sflag[r >> 6] = 1;
-}
-
-__global__ __launch_bounds__(256) void halo_compact_kernel(int n, const int *__restrict__ flag,
-                                                           const int *__restrict__ pos, int *__restrict__ idx) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n && flag[i]) idx[pos[i]] = (int)i;
 }
 
 __global__ __launch_bounds__(256) void halo_pack_kernel(int n, const int *__restrict__ idx,
@@ -203,14 +198,10 @@ bool dist_setup_level(Hierarchy &H, int lev) {
                            D.nloc, L.A.rowptr.p, L.A.col.p, flag.p);
     SA_HIP_CHECK(hipGetLastError());
     exclusive_scan_int(s, n, flag.p, pos.p);
-    int nrecv = 0;
-    SA_HIP_CHECK(hipMemcpyAsync(&nrecv, pos.p + n, sizeof(int), hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
+    int nrecv = read_one(pos.p + n, s);
     D.nrecv = nrecv;
     D.recv_idx.alloc((size_t)nrecv + 1);
-    hipLaunchKernelGGL(halo_compact_kernel, dim3(div_up(n, 256)), dim3(256), 0, s, n, flag.p, pos.p,
-                       D.recv_idx.p);
-    SA_HIP_CHECK(hipGetLastError());
+    dev_compact_scatter(s, n, flag.p, pos.p, D.recv_idx.p);
     std::vector<long long> rcnt((size_t)world, 0);
     {
         DBuf<int> view;

@@ -11,6 +11,7 @@
 // assembles, factors and coarsens exactly the agglomerates made of its own elements (the reference's invariant: no
 // agglomerate straddles ranks), so the agglomerate ownership ranges of every level follow the inputs.
 #include "hierarchy.h"
+#include "devtab.h"
 
 namespace saamge_amd {
 
@@ -124,9 +125,7 @@ Hierarchy *hierarchy_create_dist(const ParCsrIn &A, int NE_loc, int nde, const i
         DBuf<long long> cmap;
         const long long dn = cnt[(size_t)rank * K + 1];
         import_array(di, A.diag_i, (size_t)A.nrows + 1, s);
-        int dnnz = 0;
-        SA_HIP_CHECK(hipMemcpyAsync(&dnnz, di.p + A.nrows, sizeof(int), hipMemcpyDeviceToHost, s));
-        SA_HIP_CHECK(hipStreamSynchronize(s));
+        int dnnz = read_one(di.p + A.nrows, s);
         import_array(dj, A.diag_j, (size_t)dnnz, s);
         import_array(da, A.diag_a, (size_t)dnnz, s);
         const long long onnz = dn - dnnz;

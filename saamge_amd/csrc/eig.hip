@@ -15,6 +15,7 @@
 #include "eig.h"
 #include "eig_dense_plan.h"
 #include "eig_device.h"
+#include "devtab.h"
 
 #include <cfloat>
 #include <cstdlib>
@@ -823,10 +824,6 @@ void eig_batch_two_stage_buffers(EigBatch &b, size_t nrefl, bool need_bandg, hip
     if (need_bandg) arena_view(b.bandg, a.bandg, rows * 2 * EIG_SB);
 }
 
-__global__ void gather_int_kernel(int n, const int *__restrict__ idx, const int *__restrict__ src, int *__restrict__ dst) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = src[idx[i]];
-}
 
 // the batch of the class representatives: the same workspace, per-matrix tables of its own
 void eig_batch_compact(hipStream_t s, EigBatch &cb, EigBatch &full, const std::vector<int> &reps) {
@@ -865,8 +862,7 @@ void eig_batch_compact(hipStream_t s, EigBatch &cb, EigBatch &full, const std::v
         DBuf<int> idx;
         idx.from_host(reps, s);
         cb.bw.alloc((size_t)cb.count);
-        hipLaunchKernelGGL(gather_int_kernel, dim3(div_up(cb.count, 256)), dim3(256), 0, s, cb.count, idx.p, full.bw.p, cb.bw.p);
-        SA_HIP_CHECK(hipGetLastError());
+        dev_gather(s, cb.count, (const int *)idx.p, (const int *)full.bw.p, cb.bw.p);
         SA_HIP_CHECK(hipStreamSynchronize(s));      // (idx is freed on return)
     }
     cb.has_x0c = full.has_x0c;

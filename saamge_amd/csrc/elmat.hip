@@ -44,6 +44,7 @@
 // DESIGN.md 4.9.8.
 #include "elmat.h"
 #include "elmat_ref.h"
+#include "devtab.h"
 
 #include <algorithm>
 #include <climits>

@@ -4,6 +4,7 @@
 #include "dist.h"
 #include "dense.h"
 #include "spgemm.h"
+#include "devtab.h"
 
 #include <algorithm>
 #include <cmath>
@@ -61,16 +62,6 @@ static double *scratch_get(int slot, size_t need) {
 
 static void finish_csr(DCsr &A) { A.lanes_per_row = pick_lanes_per_row(A.nnz, A.nrows > 0 ? A.nrows : 1); }
 
-__global__ void iota_int_kernel(long n, int *p) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) p[i] = (int)i;
-}
-
-__global__ void iota64_kernel(long n, int64_t scale, int64_t *p) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) p[i] = i * scale;
-}
-
 // Mixed elements: checks of a device-resident elem_ptr (NE + 1 entries) and elem_to_dof (elem_ptr[NE] entries, read only
 // after the offsets passed), the sizes of the elements and their squares.  info = {error bits, MAX_ELEM_DOFS - smallest element,
 // largest element}, zero-initialised.
@@ -116,9 +107,7 @@ static int check_elem_ptr(int NE, const int *elem_ptr, const int *elem_to_dof, i
         const auto h = info.to_host(s);
         bits = h[0]; mn = MAX_ELEM_DOFS - h[1]; mx = h[2];
         if (!bits) {
-            int last = 0;
-            SA_HIP_CHECK(hipMemcpyAsync(&last, elem_ptr + NE, sizeof(int), hipMemcpyDeviceToHost, s));
-            SA_HIP_CHECK(hipStreamSynchronize(s));
+            int last = read_one(elem_ptr + NE, s);
             nconn = last;
         }
     }
@@ -139,14 +128,6 @@ static int check_elem_ptr(int NE, const int *elem_ptr, const int *elem_to_dof, i
     return mn == mx ? mx : 0;
 }
 
-__global__ void gather_kernel(long n, const int *__restrict__ idx, const double *__restrict__ src, double *__restrict__ dst) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = src[idx[i]];
-}
-__global__ void fill_kernel(long n, double *p, double v) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) p[i] = v;
-}
 
 // In-place all-gather of an array of which rank r holds the elements [at(begin[r]), at(begin[r + 1])), `bytes` bytes each.
 template <class Begin, class At>
@@ -699,8 +680,7 @@ static void level_eigenproblems(LevelBuild &B) {
         if (lev > 0 && H.levels[lev - 1]->cvec_next.n == (size_t)L.A.nrows) {
             const size_t rows = (size_t)batch.h_voff[cnt];
             batch.x0c.alloc(rows);
-            hipLaunchKernelGGL(gather_kernel, dim3(div_up((long)rows, 256)), dim3(256), 0, s, (long)rows,
-                               L.drel.ae2d_J.p + L.rel.AE_to_dof.I[ae0], H.levels[lev - 1]->cvec_next.p, batch.x0c.p);
+            dev_gather(s, (long)rows, L.drel.ae2d_J.p + L.rel.AE_to_dof.I[ae0], H.levels[lev - 1]->cvec_next.p, batch.x0c.p);
             batch.has_x0c = true;
         }
         const RowsSpan span = rows_span(L.rel, ae0, B.ae_lo, B.ae_hi);
@@ -762,7 +742,7 @@ static void level_concatenate(LevelBuild &B) {
         if (extra && c.ae0 == 0) {
             const int64_t first = (int64_t)L.ae_m[0] * sizes[0];
             SA_HIP_CHECK(hipMemcpyAsync(L.evecs.p, c.evecs.p, 8 * first, hipMemcpyDeviceToDevice, s));
-            hipLaunchKernelGGL(fill_kernel, dim3(div_up(sizes[0], 256)), dim3(256), 0, s, (long)sizes[0], L.evecs.p + first, 1.0);
+            dev_fill(s, (long)sizes[0], 1.0, L.evecs.p + first);
             if (c.evecs.n > (size_t)first)
                 SA_HIP_CHECK(hipMemcpyAsync(L.evecs.p + L.ae_xoff[1], c.evecs.p + first, 8 * (c.evecs.n - first), hipMemcpyDeviceToDevice, s));
         } else if (c.evecs.n) {
@@ -869,7 +849,7 @@ static void level_transfer(LevelBuild &B) {
         if (lev > 0 && H.levels[lev - 1]->cvec_next.n == (size_t)L.A.nrows) cv = H.levels[lev - 1]->cvec_next.p;
         else {
             ones.alloc((size_t)L.A.nrows);
-            hipLaunchKernelGGL(fill_kernel, dim3(div_up((long)L.A.nrows, 256)), dim3(256), 0, s, (long)L.A.nrows, ones.p, 1.0);
+            dev_fill(s, (long)L.A.nrows, 1.0, ones.p);
             cv = ones.p;
         }
         spmv(s, L.R, cv, L.cvec_next.p);
@@ -1220,13 +1200,6 @@ static void smooth_inplace(Hierarchy &H, const DCsr &A, const double *dinv,
     if (cur != x) vec_copy(s, nl, cur + off, x + off);
 }
 
-static double read_scalar(hipStream_t s, const double *dptr) {
-    double v;
-    SA_HIP_CHECK(hipMemcpyAsync(&v, dptr, sizeof(double), hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
-    return v;
-}
-
 // The PCG loop shared by the outer solve and the coarsest solver (MFEM CGSolver::Mult order
 // of operations == kalchev_pcg, amg/src/mfem_addons.cpp:106-248).  Row-partitioned (D != null):
 // vector updates and inner products run on the own rows, the products are summed over ranks,
@@ -1250,7 +1223,7 @@ static int pcg_loop(Hierarchy &H, const DCsr &A, const std::function<void(const 
     prec(r, z);
     vec_copy(s, n, z + off, d + off);
     pdot(d, r, sc + 0);
-    const double nom0 = read_scalar(s, sc + 0);
+    const double nom0 = read_one(sc + 0, s);
     if (hist) hist[0] = nom0;
     const double r0 = squared ? std::max(nom0 * rel_tol * rel_tol, abs_tol * abs_tol)
                               : std::max(nom0 * rel_tol, abs_tol);
@@ -1261,14 +1234,14 @@ static int pcg_loop(Hierarchy &H, const DCsr &A, const std::function<void(const 
     }
     halo_then(H, D, d, [&](hipStream_t st, RowRange rq) { spmv(st, A, d, q, rq); });
     pdot(q, d, sc + 1);
-    if (read_scalar(s, sc + 1) == 0.0) return 0;
+    if (read_one(sc + 1, s) == 0.0) return 0;
     int i = 1;
     int final_iter = max_iter;
     for (;;) {
         pcg_update_xr(s, n, sc, x + off, r + off, d + off, q + off);
         prec(r, z);
         pdot(r, z, sc + 2);
-        const double betanom = read_scalar(s, sc + 2);
+        const double betanom = read_one(sc + 2, s);
         if (hist && i <= max_iter) hist[i] = betanom;      // hist holds max_iter + 1 doubles: with max_iter <= 0 the one update still runs
         if (betanom < r0) {
             if (converged) *converged = 1;
@@ -1501,8 +1474,7 @@ Hierarchy *hierarchy_create(int n, const void *Arow, int rowptr_bits, const int 
         NE = n;
         nde = 1;
         iota_e2d.alloc((size_t)n);
-        hipLaunchKernelGGL(iota_int_kernel, dim3(div_up(n, 256)), dim3(256), 0, stream, (long)n, iota_e2d.p);
-        SA_HIP_CHECK(hipGetLastError());
+        dev_iota(stream, (long)n, 1, iota_e2d.p);
         elem_to_dof = iota_e2d.p;
         elmat = nullptr;
         bdr = nullptr;
@@ -1531,9 +1503,7 @@ Hierarchy *hierarchy_create(int n, const void *Arow, int rowptr_bits, const int 
     Level &L0 = *H.levels[0];
     {
         import_rowptr(L0.A.rowptr, Arow, rowptr_bits, (size_t)n + 1, s);
-        roff_t nnz = 0;
-        SA_HIP_CHECK(hipMemcpyAsync(&nnz, L0.A.rowptr.p + n, sizeof(roff_t), hipMemcpyDeviceToHost, s));
-        SA_HIP_CHECK(hipStreamSynchronize(s));
+        roff_t nnz = read_one(L0.A.rowptr.p + n, s);
         L0.A.nrows = L0.A.ncols = n;
         L0.A.nnz = nnz;
         import_array(L0.A.col, Acol, (size_t)nnz, s);
@@ -1546,9 +1516,7 @@ Hierarchy *hierarchy_create(int n, const void *Arow, int rowptr_bits, const int 
             // per-rank inputs: only the matrices of the rank's own elements exist (they are never exchanged); the offsets of
             // the other elements stay 0 -- no kernel of this rank touches an agglomerate made of them
             L0.elmat.off.zero(s);
-            hipLaunchKernelGGL(iota64_kernel, dim3(div_up((long)H.dist_in->NE_loc + 1, 256)), dim3(256), 0, s, (long)H.dist_in->NE_loc + 1,
-                               (int64_t)nde * nde, L0.elmat.off.p + H.dist_in->elem0);
-            SA_HIP_CHECK(hipGetLastError());
+            dev_iota(s, (long)H.dist_in->NE_loc + 1, (int64_t)nde * nde, L0.elmat.off.p + H.dist_in->elem0);
             import_array(L0.elmat.val, elmat, (size_t)H.dist_in->NE_loc * nde * nde, s);
             L0.elmat.first = H.dist_in->elem0;
         } else if (elem_ptr) {
@@ -1558,15 +1526,11 @@ Hierarchy *hierarchy_create(int n, const void *Arow, int rowptr_bits, const int 
             hipLaunchKernelGGL(elem_sq_kernel, dim3(div_up((long)NE, 256)), dim3(256), 0, s, (long)NE, H.e2d_ptr.p, sq.p);
             SA_HIP_CHECK(hipGetLastError());
             exclusive_scan_off(s, NE, sq.p, L0.elmat.off.p);
-            int64_t total = 0;
-            SA_HIP_CHECK(hipMemcpyAsync(&total, L0.elmat.off.p + NE, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-            SA_HIP_CHECK(hipStreamSynchronize(s));
+            int64_t total = read_one(L0.elmat.off.p + NE, s);
             import_array(L0.elmat.val, elmat, (size_t)total, s);
             L0.elmat.max_nd = max_nd;
         } else {
-        hipLaunchKernelGGL(iota64_kernel, dim3(div_up((long)NE + 1, 256)), dim3(256), 0, s, (long)NE + 1,
-                           (int64_t)nde * nde, L0.elmat.off.p);
-        SA_HIP_CHECK(hipGetLastError());
+        dev_iota(s, (long)NE + 1, (int64_t)nde * nde, L0.elmat.off.p);
         if (!p.algebraic) import_array(L0.elmat.val, elmat, (size_t)NE * nde * nde, s);
         }
         L0.elmat.nde = nde;

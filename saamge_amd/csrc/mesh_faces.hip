@@ -15,6 +15,7 @@
 //                     network over its at most 6 slots.  No appended lists; the only atomics are integer counters and minima.
 // The face-list calls (face_nodes, face_dofs) share the checks of the boundary forms (check_face_list, mesh.hip).
 #include "mesh_faces.h"
+#include "devtab.h"
 
 #include <algorithm>
 #include <climits>
@@ -23,11 +24,6 @@
 #include "operator.h"      // upload
 
 namespace saamge_amd {
-
-// dof -> element transpose (topology.hip)
-__global__ void d2e_count_kernel(long nconn, const int *__restrict__ e2d_J, int *__restrict__ cnt);
-__global__ void d2e_fill_kernel(int NE, const int *__restrict__ e2d_I, const int *__restrict__ e2d_J, const int *__restrict__ d2e_I,
-                                int *__restrict__ cursor, int *__restrict__ d2e_J);
 
 namespace {
 
@@ -281,13 +277,10 @@ void face_table_build(hipStream_t s, const MeshArgs &m, FaceTable &T, long long 
     const int init[MF_WORDS] = {INT_MAX, 0, 0, 0};
     SA_HIP_CHECK(hipMemcpyAsync(words.p, init, sizeof(init), hipMemcpyHostToDevice, s));
     cnt.zero(s);
-    hipLaunchKernelGGL(d2e_count_kernel, grid_flat(M.nconn), dim3(256), 0, s, M.nconn, M.eJ, cnt.p);
+    dev_histogram(s, M.nconn, M.eJ, cnt.p);
     hipLaunchKernelGGL(mf_max_kernel, grid_flat(NV), dim3(256), 0, s, NV, (const int *)cnt.p, words.p + 3);
     SA_HIP_CHECK(hipGetLastError());
-    exclusive_scan_int(s, NV, cnt.p, v2e_I.p);
-    cnt.zero(s);
-    hipLaunchKernelGGL(d2e_fill_kernel, grid_flat(NE), dim3(256), 0, s, NE, M.eI, M.eJ, (const int *)v2e_I.p, cnt.p, v2e_J.p);
-    SA_HIP_CHECK(hipGetLastError());
+    dev_table_finish(s, NE, M.eI, M.eJ, NV, cnt.p, v2e_I.p, v2e_J.p, false);
     // ---- the matching
     T.nbr_elem.alloc((size_t)slots);
     T.nbr_local.alloc((size_t)slots);

@@ -19,6 +19,7 @@
 //                     representative, a centre the rank of its element.  With coordinates the same lane writes the node's
 //                     coordinates; the lanes of several elements write the same bits to a shared edge or face node.
 #include "mesh_lift.h"
+#include "devtab.h"
 
 #include <algorithm>
 #include <climits>
@@ -131,10 +132,6 @@ __global__ __launch_bounds__(256) void ml_fits_kernel(int NE, int dim, const int
     if (e >= NE) return;
     const int t = em_type_index(dim, eI[e + 1] - eI[e]);
     if (slot_ptr[e + 1] - slot_ptr[e] != (roff_t)bdr_num_faces(t)) atomicMin(words + 2, (int)e);
-}
-__global__ __launch_bounds__(256) void ml_narrow_kernel(int n, const roff_t *__restrict__ in, int *__restrict__ out) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = (int)in[i];
 }
 // mark[v] = 1 for every vertex an element lists (every lane stores the same value)
 __global__ __launch_bounds__(256) void ml_mark_kernel(long nconn, const int *__restrict__ eJ, int *__restrict__ mark) {
@@ -348,8 +345,7 @@ void mesh_lift_order2(hipStream_t s, const MeshArgs &m, const FaceTable *faces, 
     L.entries = (long long)read_one((const roff_t *)ep2_wide.p + NE, s);
     L.NC = read_one((const int *)centre_rank.p + NE, s);
     SA_REQUIRE(L.entries <= INT_MAX, name + "the element -> node lists are beyond 32 bits");
-    hipLaunchKernelGGL(ml_narrow_kernel, grid_flat((long)NE + 1), dim3(256), 0, s, NE + 1, (const roff_t *)ep2_wide.p, L.elem_ptr2.p);
-    SA_HIP_CHECK(hipGetLastError());
+    dev_convert(s, (long)NE + 1, (const roff_t *)ep2_wide.p, L.elem_ptr2.p);
     ep2_wide.release();
     nd2.release();
     centre.release();

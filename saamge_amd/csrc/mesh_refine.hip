@@ -13,6 +13,7 @@
 // two scans give the offsets both are found in by bisection.  A list of one type needs neither (slot s is face s % 6 of
 // hexahedron s / 6, centre c is element c).
 #include "mesh_refine.h"
+#include "devtab.h"
 
 #include <algorithm>
 #include <climits>

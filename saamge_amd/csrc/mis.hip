@@ -4,6 +4,7 @@
 // reductions are wavefront shuffles, no LDS traffic besides the tiny sort scratch.
 #include "mis.h"
 #include "assemble.h"
+#include "devtab.h"
 
 #include <cfloat>
 
@@ -297,10 +298,6 @@ __global__ __launch_bounds__(256) void mis_verify_kernel(MisIn v, int nm, const 
         isrep[m] = (r0 == m || !same) ? 1 : 0;
     }
 }
-__global__ __launch_bounds__(256) void mis_list_kernel(int nm, const int *__restrict__ isrep, const int *__restrict__ pos, int *__restrict__ list) {
-    const int m = blockIdx.x * 256 + threadIdx.x;
-    if (m < nm && isrep[m]) list[pos[m]] = m;
-}
 // results of the first members to the other members of their classes (a wavefront per MIS)
 __global__ __launch_bounds__(256) void mis_copy_kernel(MisIn v, int nm, const int *__restrict__ rep) {
     const int m = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -335,8 +332,7 @@ void mis_svd(hipStream_t s, const DevRelations &rel, int num_mises, int max_ctot
         hipLaunchKernelGGL(mis_verify_kernel, dim3(div_up(nm, 4)), dim3(256), 0, s, v, nm, h.p, rep.p, isrep.p);
         SA_HIP_CHECK(hipGetLastError());
         exclusive_scan_int(s, nm, isrep.p, pos.p);
-        hipLaunchKernelGGL(mis_list_kernel, dim3(div_up(nm, 256)), dim3(256), 0, s, nm, isrep.p, pos.p, list.p);
-        SA_HIP_CHECK(hipGetLastError());
+        dev_compact_scatter(s, nm, isrep.p, pos.p, list.p);
         int last[2] = {0, 0};
         SA_HIP_CHECK(hipMemcpyAsync(&last[0], pos.p + (nm - 1), sizeof(int), hipMemcpyDeviceToHost, s));
         SA_HIP_CHECK(hipMemcpyAsync(&last[1], isrep.p + (nm - 1), sizeof(int), hipMemcpyDeviceToHost, s));
@@ -378,90 +374,6 @@ __global__ __launch_bounds__(256) void r_len_kernel(int nm, const int *__restric
     const int r = mis2d_I[m + 1] - mis2d_I[m], c0 = coloff[m];
     for (int v = 0; v < k[m]; ++v) len[c0 + v] = r;
 }
-
-// exclusive scan of ints, three small kernels (tile = 1024); OUT = int, or roff_t for the row offsets of an
-// operator (counts are int, their running sum may pass 2^31)
-template <class OUT>
-__global__ __launch_bounds__(256) void scan_tile_kernel(int n, const int *__restrict__ in,
-                                                        OUT *__restrict__ out, OUT *__restrict__ tsum) {
-    __shared__ OUT sh[256];
-    const long base = (long)blockIdx.x * 1024;
-    int v[4];
-    OUT run = 0;
-    for (int q = 0; q < 4; ++q) {
-        const long i = base + threadIdx.x * 4 + q;
-        v[q] = (i < n) ? in[i] : 0;
-        run += v[q];
-    }
-    sh[threadIdx.x] = run;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-        const OUT t = (threadIdx.x >= o) ? sh[threadIdx.x - o] : 0;
-        __syncthreads();
-        sh[threadIdx.x] += t;
-        __syncthreads();
-    }
-    OUT excl = sh[threadIdx.x] - run;
-    for (int q = 0; q < 4; ++q) {
-        const long i = base + threadIdx.x * 4 + q;
-        if (i < n) out[i] = excl;
-        excl += v[q];
-    }
-    if (threadIdx.x == 255) tsum[blockIdx.x] = sh[255];
-}
-template <class OUT>
-__global__ __launch_bounds__(256) void scan_sums_kernel(int nt, OUT *__restrict__ tsum, OUT *__restrict__ total) {
-    __shared__ OUT sh[256];
-    __shared__ OUT carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < nt; base += 256) {
-        const int i = base + threadIdx.x;
-        const OUT x = (i < nt) ? tsum[i] : 0;
-        sh[threadIdx.x] = x;
-        __syncthreads();
-        for (int o = 1; o < 256; o <<= 1) {
-            const OUT t = (threadIdx.x >= o) ? sh[threadIdx.x - o] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (i < nt) tsum[i] = carry + sh[threadIdx.x] - x;
-        __syncthreads();
-        if (threadIdx.x == 255) carry += sh[255];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-template <class OUT>
-__global__ __launch_bounds__(256) void scan_add_kernel(int n, OUT *__restrict__ out,
-                                                       const OUT *__restrict__ tsum,
-                                                       const OUT *__restrict__ total) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] += tsum[i >> 10];
-    if (i == 0) out[n] = *total;
-}
-
-// out has n+1 entries
-template <class OUT>
-static void exclusive_scan_t(hipStream_t s, int n, const int *in, OUT *out) {
-    const int nt = div_up(n, 1024);
-    DBuf<OUT> tsum((size_t)nt + 1);
-    hipLaunchKernelGGL(scan_tile_kernel<OUT>, dim3(nt), dim3(256), 0, s, n, in, out, tsum.p);
-    hipLaunchKernelGGL(scan_sums_kernel<OUT>, dim3(1), dim3(256), 0, s, nt, tsum.p, tsum.p + nt);
-    hipLaunchKernelGGL(scan_add_kernel<OUT>, dim3(div_up(n, 256)), dim3(256), 0, s, n, out, (const OUT *)tsum.p, (const OUT *)(tsum.p + nt));
-    SA_HIP_CHECK(hipGetLastError());
-    SA_HIP_CHECK(hipStreamSynchronize(s));  // tsum is freed on return
-}
-void exclusive_scan_int(hipStream_t s, int n, const int *in, int *out) { exclusive_scan_t<int>(s, n, in, out); }
-void exclusive_scan_int_async(hipStream_t s, int n, const int *in, int *out, int *tsum) {
-    const int nt = div_up(n, 1024);
-    hipLaunchKernelGGL(scan_tile_kernel<int>, dim3(nt), dim3(256), 0, s, n, in, out, tsum);
-    hipLaunchKernelGGL(scan_sums_kernel<int>, dim3(1), dim3(256), 0, s, nt, tsum, tsum + nt);
-    hipLaunchKernelGGL(scan_add_kernel<int>, dim3(div_up(n, 256)), dim3(256), 0, s, n, out, (const int *)tsum, (const int *)(tsum + nt));
-    SA_HIP_CHECK(hipGetLastError());
-}
-void exclusive_scan_off(hipStream_t s, int n, const int *in, roff_t *out) { exclusive_scan_t<roff_t>(s, n, in, out); }
 
 __global__ __launch_bounds__(256) void p_fill_kernel(int ND, const int *__restrict__ mises,
                                                      const int *__restrict__ row_in_mis,
@@ -1052,23 +964,6 @@ __global__ __launch_bounds__(256) void rap_num_class_kernel(int nm, int m_lo, in
     if ((threadIdx.x & 63) == 0 && lds) atomicMax(&sc[RAP_SC_SMALL_LDS], (unsigned long long)lds);
 }
 
-__global__ __launch_bounds__(256) void rap_scatter_kernel(int nm, const int *__restrict__ flag, const int *__restrict__ pos,
-                                                          int *__restrict__ list) {
-    const int m = blockIdx.x * 256 + threadIdx.x;
-    if (m < nm && flag[m]) list[pos[m]] = m;
-}
-
-// list = the m < nm with flag[m] != 0, ascending; pos: scratch of nm + 1 ints.  Returns their number.
-static int rap_compact(hipStream_t s, int nm, const int *flag, int *pos, DBuf<int> &list) {
-    exclusive_scan_int(s, nm, flag, pos);
-    int n = 0;
-    SA_HIP_CHECK(hipMemcpyAsync(&n, pos + nm, sizeof(int), hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
-    list.alloc((size_t)n);
-    if (n) hipLaunchKernelGGL(rap_scatter_kernel, dim3(div_up(nm, 256)), dim3(256), 0, s, nm, flag, (const int *)pos, list.p);
-    return n;
-}
-
 void rap_mis(hipStream_t s, const DevRelations &rel, const Relations &hrel, const DCsr &A,
              const std::vector<int> &h_k, const std::vector<int> &h_coloff, const int *d_k,
              const int *d_coloff, const int64_t *d_u_off, const double *U, DCsr &Ac, int rank, int world,
@@ -1098,7 +993,7 @@ void rap_mis(hipStream_t s, const DevRelations &rel, const Relations &hrel, cons
     {   // (two lists by the number of dofs, as for the numeric kernel below)
         hipLaunchKernelGGL(rap_sym_class_kernel, gm, dim3(256), 0, s, nm, rel.mis2d_I.p, fa.p, fb.p);
         DBuf<int> d_sym_small, d_sym_big;
-        const int n_small = rap_compact(s, nm, fa.p, pos.p, d_sym_small), n_big = rap_compact(s, nm, fb.p, pos.p, d_sym_big);
+        const int n_small = dev_compact(s, nm, fa.p, pos.p, d_sym_small), n_big = dev_compact(s, nm, fb.p, pos.p, d_sym_big);
         if (n_big)
             hipLaunchKernelGGL((rap_symbolic_kernel<RAP_NT, RAP_HASH>), dim3((unsigned)n_big), dim3(RAP_NT), 0, s, d_sym_big.p, 0,
                                rel.mis2d_I.p, rel.mis2d_J.p, A.rowptr.p, A.col.p, pack.p, d_k, cnt.p, nullptr, nullptr, err.p, stage.p,
@@ -1116,7 +1011,7 @@ void rap_mis(hipStream_t s, const DevRelations &rel, const Relations &hrel, cons
     auto h_sc = sc.to_host(s);
     if (h_sc[RAP_SC_AGAIN]) {   // small MISes whose neighbours did not fit the small tables: once more, full size
         DBuf<int> d_again;
-        const int n_again = rap_compact(s, nm, fa.p, pos.p, d_again);
+        const int n_again = dev_compact(s, nm, fa.p, pos.p, d_again);
         hipLaunchKernelGGL((rap_symbolic_kernel<RAP_NT, RAP_HASH>), dim3((unsigned)n_again), dim3(RAP_NT), 0, s, d_again.p, 0,
                            rel.mis2d_I.p, rel.mis2d_J.p, A.rowptr.p, A.col.p, pack.p, d_k, cnt.p, nullptr, nullptr, err.p, stage.p,
                            STAGE_CAP, maxrow);
@@ -1129,9 +1024,7 @@ void rap_mis(hipStream_t s, const DevRelations &rel, const Relations &hrel, cons
     const int cnt_max = (int)h_sc[RAP_SC_CNT_MAX];
     DBuf<int> nbr_ptr((size_t)nm + 1);
     exclusive_scan_int(s, nm, cnt.p, nbr_ptr.p);
-    int nbr_total = 0;
-    SA_HIP_CHECK(hipMemcpyAsync(&nbr_total, nbr_ptr.p + nm, sizeof(int), hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
+    int nbr_total = read_one(nbr_ptr.p + nm, s);
     DBuf<int> nbr((size_t)nbr_total + 1);
     if (cnt_max <= STAGE_CAP)      // every list was staged by the counting pass
         hipLaunchKernelGGL(rap_unstage_kernel, dim3(div_up((long)nm * STAGE_CAP, 256)), dim3(256), 0, s, nm, STAGE_CAP, stage.p,
@@ -1184,7 +1077,7 @@ void rap_mis(hipStream_t s, const DevRelations &rel, const Relations &hrel, cons
     // the MISes of this rank's range in two lists: few dofs (one wavefront per MIS, the LDS those need), the others
     hipLaunchKernelGGL(rap_num_class_kernel, gm, dim3(256), 0, s, nm, m_lo, m_hi, d_k, rel.mis2d_I.p, small_need.p, fa.p, fb.p, sc.p);
     DBuf<int> d_small, d_big;
-    const int n_small = rap_compact(s, nm, fa.p, pos.p, d_small), n_big = rap_compact(s, nm, fb.p, pos.p, d_big);
+    const int n_small = dev_compact(s, nm, fa.p, pos.p, d_small), n_big = dev_compact(s, nm, fb.p, pos.p, d_big);
     const size_t small_lds = (size_t)sc.to_host(s)[RAP_SC_SMALL_LDS];
     if (n_big)
         hipLaunchKernelGGL(rap_numeric_kernel<RAP_NT>, dim3((unsigned)n_big), dim3(RAP_NT), lds_doubles * 8, s,

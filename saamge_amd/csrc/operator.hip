@@ -16,6 +16,7 @@
 // row]; the owner of an entry then walks its line of the table.  Rows whose table does not fit walk the dof lists in
 // global memory per entry.  No floating-point atomics, no reduction whose order could vary.
 #include "operator.h"
+#include "devtab.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -25,12 +26,6 @@
 #include "partition.h"
 
 namespace saamge_amd {
-
-// topology.hip: dof -> element lists
-__global__ void d2e_count_kernel(long nconn, const int *__restrict__ e2d_J, int *__restrict__ cnt);
-__global__ void d2e_fill_kernel(int NE, const int *__restrict__ e2d_I, const int *__restrict__ e2d_J,
-                                const int *__restrict__ d2e_I, int *__restrict__ cursor, int *__restrict__ d2e_J);
-__global__ void d2e_sort_kernel(int ND, const int *__restrict__ d2e_I, int *__restrict__ d2e_J);
 
 namespace {
 
@@ -85,12 +80,6 @@ __global__ __launch_bounds__(256) void op_flag_kernel(int n, const int *__restri
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i < n) flag[i] = cls[i] == which;
 }
-__global__ __launch_bounds__(256) void op_list_kernel(int n, const int *__restrict__ flag, const int *__restrict__ pos,
-                                                      int *__restrict__ list) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n && flag[i]) list[pos[i]] = (int)i;
-}
-
 // ---- symbolic pass --------------------------------------------------------------------------------------------------
 template <bool FILL>
 __global__ __launch_bounds__(256) void op_sym_short_kernel(int nrows, const int *__restrict__ list, const int *__restrict__ d2e_I,
@@ -451,14 +440,7 @@ void numeric_pass(hipStream_t s, AssembledOperator &op, const double *elmat) {
 int make_list(hipStream_t s, int n, const int *cls, int which, DBuf<int> &flag, DBuf<int> &pos, DBuf<int> &list) {
     hipLaunchKernelGGL(op_flag_kernel, grid_flat(n), dim3(256), 0, s, n, cls, which, flag.p);
     SA_HIP_CHECK(hipGetLastError());
-    exclusive_scan_int(s, n, flag.p, pos.p);
-    const int m = read_one(pos.p + n, s);
-    list.alloc((size_t)m);
-    if (m) {
-        hipLaunchKernelGGL(op_list_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)flag.p, (const int *)pos.p, list.p);
-        SA_HIP_CHECK(hipGetLastError());
-    }
-    return m;
+    return dev_compact(s, n, flag.p, pos.p, list);
 }
 
 void operator_assemble(hipStream_t s, int n, int NE, int nde, const int *elem_ptr, const int *elem_to_dof,
@@ -502,7 +484,7 @@ void operator_assemble(hipStream_t s, int n, int NE, int nde, const int *elem_pt
     // dof -> elements, ascending
     DBuf<int> cnt((size_t)n + 1), info(1);
     cnt.zero(s);
-    if (op.nconn) hipLaunchKernelGGL(d2e_count_kernel, grid_flat(op.nconn), dim3(256), 0, s, op.nconn, (const int *)op.eJ.p, cnt.p);
+    if (op.nconn) dev_histogram(s, op.nconn, op.eJ.p, cnt.p);
     SA_HIP_CHECK(hipMemsetAsync(info.p, 0x7f, sizeof(int), s));
     hipLaunchKernelGGL(op_first_free_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)cnt.p, info.p);
     SA_HIP_CHECK(hipGetLastError());
@@ -512,12 +494,7 @@ void operator_assemble(hipStream_t s, int n, int NE, int nde, const int *elem_pt
     }
     op.d2e_I.alloc((size_t)n + 1);
     op.d2e_J.alloc((size_t)op.nconn);
-    exclusive_scan_int(s, n, cnt.p, op.d2e_I.p);
-    cnt.zero(s);
-    hipLaunchKernelGGL(d2e_fill_kernel, grid_flat(NE), dim3(256), 0, s, NE, (const int *)op.eI.p, (const int *)op.eJ.p,
-                       (const int *)op.d2e_I.p, cnt.p, op.d2e_J.p);
-    hipLaunchKernelGGL(d2e_sort_kernel, grid_flat(n), dim3(256), 0, s, n, (const int *)op.d2e_I.p, op.d2e_J.p);
-    SA_HIP_CHECK(hipGetLastError());
+    dev_table_finish(s, NE, op.eI.p, op.eJ.p, n, cnt.p, op.d2e_I.p, op.d2e_J.p, true);
     // offsets of the packed element matrices
     if (elem_ptr) {
         DBuf<int> sq((size_t)NE);

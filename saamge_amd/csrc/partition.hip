@@ -10,23 +10,17 @@
 //
 // What the phases share is written once, ahead of them.  On the device: row_lane / row_entries (which lane of which row a
 // thread is, and the walk over its entries), group_reduce (the shuffles, over a row's lanes or a wavefront) and pt_run_start
-// (the rank within a sorted run, for the quotas).  On the host: GraphView with sweep / flat (the two launch shapes), ball_min /
-// ball_flag (the ball sweeps by run-time first / last) and PairSorter (the radix sorts of a phase and their temporary
-// storage).  The counts of a call go back to the caller (PartitionStats, RefineStats); nothing here remembers a call.
+// (the rank within a sorted run, for the quotas).  On the host: GraphView with sweep (the row launch; the flat one is devtab.h's launch_flat), ball_min /
+// ball_flag (the ball sweeps by run-time first / last); the radix sorts of a phase and their temporary storage are devsort.h's
+// PairSorter.  The counts of a call go back to the caller (PartitionStats, RefineStats); nothing here remembers a call.
 #include "partition.h"
-
-#include <hipcub/hipcub.hpp>
+#include "devsort.h"
 
 #include <algorithm>
 #include <climits>
 #include <type_traits>
 
 namespace saamge_amd {
-
-// topology.hip: dof -> element lists
-__global__ void d2e_count_kernel(long nconn, const int *__restrict__ e2d_J, int *__restrict__ cnt);
-__global__ void d2e_fill_kernel(int NE, const int *__restrict__ e2d_I, const int *__restrict__ e2d_J,
-                                const int *__restrict__ d2e_I, int *__restrict__ cursor, int *__restrict__ d2e_J);
 
 namespace {
 
@@ -35,11 +29,6 @@ constexpr int PT_LPR = 8;          // lanes per row of the CSR sweeps
 constexpr int PT_WAVE = 64;
 constexpr u64 PT_NONE = ~0ull;
 
-inline int pt_bits(int n) {
-    int b = 1;
-    while ((1ll << b) < n) ++b;
-    return b;
-}
 inline dim3 grid_rows(long n) { return dim3((unsigned)((n * PT_LPR + 255) / 256)); }
 
 __device__ inline unsigned pt_prio(unsigned i, unsigned seed) {
@@ -97,15 +86,6 @@ __device__ inline int pt_run_start(const int *lab, int j) {
         else hi = mid;
     }
     return lo;
-}
-
-__global__ __launch_bounds__(256) void pt_fill_int_kernel(long n, int v, int *__restrict__ a) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) a[i] = v;
-}
-__global__ __launch_bounds__(256) void pt_fill_u64_kernel(long n, u64 v, u64 *__restrict__ a) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) a[i] = v;
 }
 
 // ---- growth ---------------------------------------------------------------------------------------------------------
@@ -775,17 +755,12 @@ void sweep(const GraphView &g, K kernel, A... args) {
     hipLaunchKernelGGL(kernel, grid_rows(g.n), dim3(256), 0, g.s, g.n, g.xadj, g.adj, args...);
     SA_HIP_CHECK(hipGetLastError());
 }
-// one thread per item: kernel(count, args...)
-template <class K, class... A>
-void flat(hipStream_t s, long count, K kernel, A... args) {
-    hipLaunchKernelGGL(kernel, grid_flat(count), dim3(256), 0, s, count, args...);
-    SA_HIP_CHECK(hipGetLastError());
-}
+// fills of lists that may be empty
 void fill_int(hipStream_t s, long n, int v, int *a) {
-    if (n) flat(s, n, pt_fill_int_kernel, v, a);
+    if (n) dev_fill(s, n, v, a);
 }
 void fill_u64(hipStream_t s, long n, u64 v, u64 *a) {
-    if (n) flat(s, n, pt_fill_u64_kernel, v, a);
+    if (n) dev_fill(s, n, v, a);
 }
 // one hop of a ball sweep; first / last pick the instantiation (state and newseed are read by those forms alone)
 void ball_min(const GraphView &g, bool first, bool last, const int *state, const u64 *src, u64 *dst, int *newseed) {
@@ -797,40 +772,6 @@ void ball_flag(const GraphView &g, bool last, const int *src, int *dst, const in
                int *counters) {
     sweep(g, last ? pt_ball_flag_kernel<true> : pt_ball_flag_kernel<false>, src, dst, newseed, seedval, state, counters);
 }
-
-// The stable radix sorts of (key, value) pairs of one phase, u64 / int and int / int, at most n pairs each.  It owns the
-// sort's temporary storage, sized once by the library's queries for n pairs.
-class PairSorter {
-    hipStream_t s;
-    size_t tmp_bytes;
-    DBuf<char> tmp;
-    template <class K, class V>
-    size_t query(const K *kin, K *kout, const V *vin, V *vout, int m, int end_bit) const {   // (a host call, nothing is launched)
-        size_t b = 0;
-        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, b, kin, kout, vin, vout, m, 0, end_bit, s));
-        return b;
-    }
-
-  public:
-    // key_bits, label_bits: the widest bit range the phase sorts u64 keys and int keys over (0: it sorts none of these)
-    PairSorter(hipStream_t s_, int n, int key_bits, int label_bits = 0) : s(s_) {
-        const int *ci = nullptr;
-        int *i = nullptr;
-        tmp_bytes = query((const u64 *)nullptr, (u64 *)nullptr, ci, i, n, key_bits);
-        if (label_bits) tmp_bytes = std::max(tmp_bytes, query(ci, i, ci, i, n, label_bits));
-        tmp.alloc(tmp_bytes + 16);
-    }
-    // (kout, vout) = the first m <= n pairs of (kin, vin), stably ordered by the bits [0, end_bit) of the keys
-    template <class K, class V>
-    void sort(const K *kin, K *kout, const V *vin, V *vout, int m, int end_bit) {
-        // tmp was sized by the queries for n pairs and serves the m <= n of this call.  That rests on the assumption that the
-        // sort never asks for more temporary storage for fewer pairs or fewer bits; the library chooses its path by the count,
-        // so the assumption is checked by a query for this call and not relied on.
-        size_t b = query(kin, kout, vin, vout, m, end_bit);
-        SA_REQUIRE(b <= tmp_bytes, "partition: the sort asks for more temporary storage than the phase sized it for");
-        SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs((void *)tmp.p, b, kin, kout, vin, vout, m, 0, end_bit, s));
-    }
-};
 
 struct Grower {
     const GraphView g;
@@ -855,7 +796,7 @@ struct Grower {
             if (c[1] == 0) return;
             if (c[0] == 0) {  // a component without a seed
                 fill_u64(s, 1, PT_NONE, key.p);
-                flat(s, n, pt_min_unlabelled_kernel, label, g.seed, key.p);
+                launch_flat(s, n, pt_min_unlabelled_kernel, label, g.seed, key.p);
                 hipLaunchKernelGGL(pt_stall_seed_kernel, dim3(1), dim3(1), 0, s, key.p, nlabels, label, isseed.p);
                 SA_HIP_CHECK(hipGetLastError());
                 ++nlabels;
@@ -868,13 +809,13 @@ struct Grower {
         GrowthStats st;
         DBuf<int> sizes((size_t)nlabels), claim((size_t)n), ids((size_t)n), ids2((size_t)n), lab((size_t)n), lab2((size_t)n);
         DBuf<u64> keys((size_t)n), keys2((size_t)n);
-        const int lab_bits = pt_bits(nlabels);
-        PairSorter sorter(s, n, 48, lab_bits);
+        const int lab_bits = bits_for(nlabels);
+        PairSorter<u64> sorter(s, n, 48, lab_bits);
         int first_unlabelled = -1;
         for (;;) {
             sizes.zero(s);
             counters.zero(s);
-            flat(s, n, pt_count_kernel, label, sizes.p);
+            launch_flat(s, n, pt_count_kernel, label, sizes.p);
             sweep(g, pt_claim_kernel, label, sizes.p, cap, g.seed, claim.p, keys.p, ids.p, counters.p);
             const auto c = counters.to_host(s);
             const int m = c[0], unlabelled = c[1];
@@ -884,16 +825,16 @@ struct Grower {
             if (m == 0) {   // release
                 DBuf<int> nopen(1);
                 nopen.zero(s);
-                flat(s, nlabels, pt_count_open_kernel, sizes.p, cap, nopen.p);
+                launch_flat(s, nlabels, pt_count_open_kernel, sizes.p, cap, nopen.p);
                 st.open_parts = nopen.to_host(s)[0];
                 st.released_nodes = unlabelled;
                 break;
             }
             ++st.rounds;
             sorter.sort(keys.p, keys2.p, ids.p, ids2.p, m, 48);
-            flat(s, m, pt_claim_gather_kernel, ids2.p, claim.p, lab.p);
+            launch_flat(s, m, pt_claim_gather_kernel, ids2.p, claim.p, lab.p);
             sorter.sort(lab.p, lab2.p, ids2.p, ids.p, m, lab_bits);
-            flat(s, m, pt_claim_apply_kernel, lab2.p, ids.p, sizes.p, cap, label);
+            launch_flat(s, m, pt_claim_apply_kernel, lab2.p, ids.p, sizes.p, cap, label);
         }
         SA_HIP_CHECK(hipStreamSynchronize(s));   // the temporaries go out of scope
         if (st.released_nodes) grow(nullptr);
@@ -903,7 +844,7 @@ struct Grower {
     void sizes_of(DBuf<int> &sizes) {
         sizes.alloc((size_t)nlabels + 1);
         sizes.zero(s);
-        flat(s, n, pt_count_kernel, label, sizes.p);
+        launch_flat(s, n, pt_count_kernel, label, sizes.p);
     }
     // the parts with k[p] > 0 are cleared down to their k[p] nodes of lowest priority; km1 = max(k - 1, 0)
     void reseed(const DBuf<int> &sizes, const DBuf<int> &k, const DBuf<int> &km1) {
@@ -912,11 +853,11 @@ struct Grower {
         exclusive_scan_int(s, nlabels, km1.p, off.p);
         DBuf<u64> keys((size_t)n), keys2((size_t)n);
         DBuf<int> ids((size_t)n), ids2((size_t)n);
-        flat(s, n, pt_sort_keys_kernel, label, g.seed, keys.p, ids.p);
-        const int end_bit = 32 + pt_bits(nlabels);
-        PairSorter sorter(s, n, end_bit);
+        launch_flat(s, n, pt_sort_keys_kernel, label, g.seed, keys.p, ids.p);
+        const int end_bit = 32 + bits_for(nlabels);
+        PairSorter<u64> sorter(s, n, end_bit);
         sorter.sort(keys.p, keys2.p, ids.p, ids2.p, n, end_bit);
-        flat(s, n, pt_reseed_kernel, keys2.p, ids2.p, start.p, k.p, off.p, nlabels, label, isseed.p);
+        launch_flat(s, n, pt_reseed_kernel, keys2.p, ids2.p, start.p, k.p, off.p, nlabels, label, isseed.p);
         nlabels += read_one(off.p + nlabels, s);  // (synchronises: the temporaries go out of scope)
     }
     // Spaced first seeding.  One independent set: rounds of r min sweeps, the decision and r flag sweeps, one read of the
@@ -961,7 +902,7 @@ struct Grower {
         }
         int ne = 0;
         if (ns < target) {   // top-up from the greedy (r - 1)-independent extension
-            flat(s, n, pt_ext_init_kernel, r == 1 ? PT_EXT : PT_UNDECIDED, w.state.p, w.newseed.p);
+            launch_flat(s, n, pt_ext_init_kernel, r == 1 ? PT_EXT : PT_UNDECIDED, w.state.p, w.newseed.p);
             if (r == 1) ne = n - ns;
             else {
                 counters.zero(s);
@@ -972,11 +913,11 @@ struct Grower {
         const int nsel = ns < target ? std::min(target, ns + ne) : ns;
         DBuf<u64> keys((size_t)n), keys2((size_t)n);
         DBuf<int> ids((size_t)n), ids2((size_t)n);
-        flat(s, n, pt_spaced_keys_kernel, w.state.p, g.seed, keys.p, ids.p);
-        PairSorter sorter(s, n, 34);
+        launch_flat(s, n, pt_spaced_keys_kernel, w.state.p, g.seed, keys.p, ids.p);
+        PairSorter<u64> sorter(s, n, 34);
         sorter.sort(keys.p, keys2.p, ids.p, ids2.p, n, 34);
         label = a.p;
-        flat(s, n, pt_spaced_label_kernel, keys2.p, ids2.p, ns, nsel, label, isseed.p);
+        launch_flat(s, n, pt_spaced_label_kernel, keys2.p, ids2.p, ns, nsel, label, isseed.p);
         SA_HIP_CHECK(hipStreamSynchronize(s));   // the temporaries go out of scope
         nlabels = nsel;
         st.radius = r;
@@ -994,8 +935,8 @@ struct Grower {
         }
         DBuf<u64> best((size_t)nlabels);
         best.zero(s);
-        flat(s, n, pt_centre_max_kernel, label, depth.p, isseed.p, g.seed, best.p);
-        flat(s, n, pt_centre_pick_kernel, label, depth.p, isseed.p, g.seed, best.p);
+        launch_flat(s, n, pt_centre_max_kernel, label, depth.p, isseed.p, g.seed, best.p);
+        launch_flat(s, n, pt_centre_pick_kernel, label, depth.p, isseed.p, g.seed, best.p);
         SA_HIP_CHECK(hipStreamSynchronize(s));
     }
     bool merge_round(int min_size, int max_size) {
@@ -1006,9 +947,9 @@ struct Grower {
         fill_u64(s, nlabels, PT_NONE, win.p);
         info.zero(s);
         sweep(g, pt_propose_kernel, label, sizes.p, min_size, max_size, prop.p);
-        flat(s, nlabels, pt_win_kernel, prop.p, sizes.p, win.p);
-        flat(s, nlabels, pt_decide_kernel, prop.p, win.p, target.p, info.p);
-        flat(s, n, pt_relabel_kernel, target.p, label);
+        launch_flat(s, nlabels, pt_win_kernel, prop.p, sizes.p, win.p);
+        launch_flat(s, nlabels, pt_decide_kernel, prop.p, win.p, target.p, info.p);
+        launch_flat(s, n, pt_relabel_kernel, target.p, label);
         return info.to_host(s)[0] != 0;
     }
 };
@@ -1022,11 +963,11 @@ int64_t check_graph_device(hipStream_t s, int n, const roff_t *xadj, const int *
     if (n == 0) return 0;
     DBuf<int> err(1);
     err.zero(s);
-    flat(s, n, pt_check_xadj_kernel, xadj, err.p);
+    launch_flat(s, n, pt_check_xadj_kernel, xadj, err.p);
     SA_REQUIRE(!err.to_host(s)[0], "xadj: must start at 0 and ascend");
     const roff_t nnz = read_one(xadj + n, s);
     SA_REQUIRE(nnz == 0 || adj, "null argument: adj");
-    flat(s, n, pt_check_adj_kernel, xadj, adj, err.p);
+    launch_flat(s, n, pt_check_adj_kernel, xadj, adj, err.p);
     const int bits = err.to_host(s)[0];
     SA_REQUIRE(!(bits & 2), "adj: entry outside [0, n)");
     SA_REQUIRE(!(bits & 4), "graph is not symmetric: an entry without its transpose");
@@ -1037,11 +978,11 @@ long check_mesh_device(hipStream_t s, int NE, const int *e2d_I, const int *e2d_J
     if (NE == 0) return 0;
     DBuf<int> err(1);
     err.zero(s);
-    flat(s, NE, pt_check_eptr_kernel, e2d_I, err.p);
+    launch_flat(s, NE, pt_check_eptr_kernel, e2d_I, err.p);
     SA_REQUIRE(!err.to_host(s)[0], "elem_ptr: must start at 0 and every element needs a dof");
     const long nconn = read_one(e2d_I + NE, s);
-    flat(s, nconn, pt_check_dofs_kernel, ND, e2d_J, err.p);
-    flat(s, NE, pt_check_repeat_kernel, e2d_I, e2d_J, err.p);
+    launch_flat(s, nconn, pt_check_dofs_kernel, ND, e2d_J, err.p);
+    launch_flat(s, NE, pt_check_repeat_kernel, e2d_I, e2d_J, err.p);
     const int bits = err.to_host(s)[0];
     SA_REQUIRE(!(bits & 2), "elem_to_dof entry out of range");
     SA_REQUIRE(!(bits & 4), "elem_to_dof: an element lists a dof twice");
@@ -1095,7 +1036,7 @@ void partition_graph_device(hipStream_t s, int n, const roff_t *xadj, const int 
             DBuf<int> sizes, k((size_t)g.nlabels), km1((size_t)g.nlabels + 1), info(1);
             g.sizes_of(sizes);
             info.zero(s);
-            flat(s, g.nlabels, pt_over_kernel, sizes.p, max_size, epa, k.p, km1.p, info.p);
+            launch_flat(s, g.nlabels, pt_over_kernel, sizes.p, max_size, epa, k.p, km1.p, info.p);
             if (info.to_host(s)[0] == 0) break;
             DBuf<int> old((size_t)n);
             SA_HIP_CHECK(hipMemcpyAsync(old.p, g.label, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, s));
@@ -1113,11 +1054,11 @@ void partition_graph_device(hipStream_t s, int n, const roff_t *xadj, const int 
 void renumber_device(hipStream_t s, int n, const int *label, int nlabels, int *part, int *nparts_out) {
     DBuf<int> minid((size_t)nlabels), first((size_t)n), rank((size_t)n + 1), newnum((size_t)nlabels);
     fill_int(s, nlabels, n, minid.p);
-    flat(s, n, pt_minid_kernel, label, minid.p);
-    flat(s, n, pt_first_kernel, label, minid.p, first.p);
+    launch_flat(s, n, pt_minid_kernel, label, minid.p);
+    launch_flat(s, n, pt_first_kernel, label, minid.p, first.p);
     exclusive_scan_int(s, n, first.p, rank.p);
-    flat(s, n, pt_newnum_kernel, label, first.p, rank.p, newnum.p);
-    flat(s, n, pt_apply_kernel, label, newnum.p, part);
+    launch_flat(s, n, pt_newnum_kernel, label, first.p, rank.p, newnum.p);
+    launch_flat(s, n, pt_apply_kernel, label, newnum.p, part);
     *nparts_out = read_one(rank.p + n, s);
 }
 
@@ -1127,8 +1068,8 @@ void check_partition_device(hipStream_t s, int n, const int *label, int nparts) 
     DBuf<int> sizes((size_t)nparts), err(1);
     sizes.zero(s);
     err.zero(s);
-    flat(s, n, pt_check_labels_kernel, label, nparts, sizes.p, err.p);
-    flat(s, nparts, pt_check_empty_kernel, sizes.p, err.p);
+    launch_flat(s, n, pt_check_labels_kernel, label, nparts, sizes.p, err.p);
+    launch_flat(s, nparts, pt_check_empty_kernel, sizes.p, err.p);
     const int bits = err.to_host(s)[0];
     SA_REQUIRE(!(bits & 1), "part: label outside [0, nparts)");
     SA_REQUIRE(!(bits & 2), "part: an empty part");
@@ -1147,33 +1088,33 @@ RefineStats refine_partition_device(hipStream_t s, int n, const roff_t *xadj, co
     DBuf<int> sizes((size_t)nparts), target((size_t)n), gain((size_t)n), cand((size_t)n), counters(3);
     DBuf<int> ids((size_t)n), ids2((size_t)n), lab((size_t)n), lab2((size_t)n), pos((size_t)n), pos2((size_t)n);
     DBuf<u64> key((size_t)n), ka((size_t)n), kb((size_t)n), wkeys((size_t)n), wkeys2((size_t)n), totals(2);
-    const int lab_bits = pt_bits(nparts + 1);
-    PairSorter sorter(s, n, 48, lab_bits);
+    const int lab_bits = bits_for(nparts + 1);
+    PairSorter<u64> sorter(s, n, 48, lab_bits);
     totals.zero(s);
     const dim3 free_grid((unsigned)std::min<long>(((long)n + 3) / 4, 2048));
     while (st.rounds < rounds) {
         sizes.zero(s);
         counters.zero(s);
         fill_u64(s, n, PT_NONE, key.p);
-        flat(s, n, pt_count_kernel, label, sizes.p);
+        launch_flat(s, n, pt_count_kernel, label, sizes.p);
         sweep(g, pt_refine_count_kernel, label, sizes.p, max_size, floor_size, target.p, gain.p, cand.p, counters.p);
         hipLaunchKernelGGL(pt_refine_free_kernel, free_grid, dim3(256), 0, s, xadj, adj, label, cand.p, gain.p, seed, key.p,
                            counters.p);
         SA_HIP_CHECK(hipGetLastError());
         ball_min(g, false, false, nullptr, key.p, ka.p, nullptr);
         ball_min(g, false, false, nullptr, ka.p, kb.p, nullptr);
-        flat(s, n, pt_refine_winner_kernel, key.p, kb.p, wkeys.p, ids.p, counters.p);
+        launch_flat(s, n, pt_refine_winner_kernel, key.p, kb.p, wkeys.p, ids.p, counters.p);
         const auto c = counters.to_host(s);
         if (c[1] == 0) { st.converged = 1; break; }
         const int m = c[2];
         SA_REQUIRE(m >= 1 && m <= n, "refinement: candidates without a winner");
         ++st.rounds;
         sorter.sort(wkeys.p, wkeys2.p, ids.p, ids2.p, m, 48);
-        flat(s, m, pt_refine_target_kernel, ids2.p, target.p, lab.p, pos.p);
+        launch_flat(s, m, pt_refine_target_kernel, ids2.p, target.p, lab.p, pos.p);
         sorter.sort(lab.p, lab2.p, pos.p, pos2.p, m, lab_bits);
-        flat(s, m, pt_refine_admit_kernel, lab2.p, pos2.p, ids2.p, label, sizes.p, max_size, nparts, lab.p);
+        launch_flat(s, m, pt_refine_admit_kernel, lab2.p, pos2.p, ids2.p, label, sizes.p, max_size, nparts, lab.p);
         sorter.sort(lab.p, lab2.p, ids2.p, ids.p, m, lab_bits);
-        flat(s, m, pt_refine_apply_kernel, lab2.p, ids.p, sizes.p, floor_size, nparts, target.p, gain.p, label, totals.p);
+        launch_flat(s, m, pt_refine_apply_kernel, lab2.p, ids.p, sizes.p, floor_size, nparts, target.p, gain.p, label, totals.p);
     }
     const auto tot = totals.to_host(s);   // (synchronises: the temporaries go out of scope)
     st.moved = (long long)tot[0];
@@ -1188,13 +1129,8 @@ void element_graph_device(hipStream_t s, int NE, const int *e2d_I, const int *e2
     if (NE == 0) { xadj.zero(s); adj.alloc(0); return; }
     const long nconn = read_one(e2d_I + NE, s);
     DBuf<int> d2e_I((size_t)ND + 1), d2e_J((size_t)nconn), cnt((size_t)std::max(ND, NE) + 1);
-    cnt.zero(s);
-    hipLaunchKernelGGL(d2e_count_kernel, grid_flat(nconn), dim3(256), 0, s, nconn, e2d_J, cnt.p);
-    SA_HIP_CHECK(hipGetLastError());
-    exclusive_scan_int(s, ND, cnt.p, d2e_I.p);
-    cnt.zero(s);
-    hipLaunchKernelGGL(d2e_fill_kernel, grid_flat(NE), dim3(256), 0, s, NE, e2d_I, e2d_J, (const int *)d2e_I.p, cnt.p, d2e_J.p);
     // (the lists need no order: every row of the graph is sorted at the end)
+    dev_table_transpose(s, NE, e2d_I, e2d_J, nconn, ND, d2e_I.p, d2e_J.p, false, cnt.p);
     hipLaunchKernelGGL(pt_elem_graph_kernel<false>, grid_flat(NE), dim3(256), 0, s, NE, e2d_I, e2d_J, (const int *)d2e_I.p,
                        (const int *)d2e_J.p, min_shared, cnt.p, (const roff_t *)nullptr, (int *)nullptr);
     SA_HIP_CHECK(hipGetLastError());
@@ -1228,7 +1164,7 @@ void quotient_graph_device(hipStream_t s, int n, const roff_t *xadj, const int *
         hipLaunchKernelGGL(pt_cut_fill_kernel, grid_flat(n), dim3(256), 0, s, n, xadj, adj, part, (const roff_t *)pos.p, keys.p);
         SA_HIP_CHECK(hipGetLastError());
         size_t tb = 0, tb2 = 0;
-        const int end_bit = 32 + pt_bits(nparts);
+        const int end_bit = 32 + bits_for(nparts);
         SA_HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, keys.p, sorted.p, (int)ncut, 0, end_bit, s));
         SA_HIP_CHECK(hipcub::DeviceSelect::Unique(nullptr, tb2, sorted.p, uniq.p, nsel.p, (int)ncut, s));
         DBuf<char> tmp(std::max(tb, tb2) + 16);

@@ -3,6 +3,7 @@
 // the XCD L2 keeps the gathered x entries, fused epilogues for the residual, the
 // prolongation-add and the polynomial-smoother step.  HBM-bound: 12 B per nonzero.
 #include "sparse.h"
+#include "devtab.h"
 #include <array>
 #include <climits>
 
@@ -1448,15 +1449,6 @@ __global__ __launch_bounds__(256) void sell_code_kernel(int nslices, const roff_
     if (lane == 0) ntab[slice] = 512 + m_nt;
 }
 
-__global__ __launch_bounds__(256) void widen_offsets_kernel(long n, const int *__restrict__ in, roff_t *__restrict__ out) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = in[i];
-}
-__global__ __launch_bounds__(256) void narrow_offsets_kernel(long n, const roff_t *__restrict__ in, int *__restrict__ out) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = (int)in[i];
-}
-
 void import_rowptr(DBuf<roff_t> &dst, const void *src, int bits, size_t n, hipStream_t s) {
     SA_REQUIRE(bits == 32 || bits == 64, "row offsets must be 32 or 64 bits wide");
     if (bits == 64) {
@@ -1466,8 +1458,7 @@ void import_rowptr(DBuf<roff_t> &dst, const void *src, int bits, size_t n, hipSt
     DBuf<int> narrow;
     import_array(narrow, (const int *)src, n, s);
     dst.alloc(n);
-    if (n) hipLaunchKernelGGL(widen_offsets_kernel, dim3(div_up((long)n, 256)), dim3(256), 0, s, (long)n, narrow.p, dst.p);
-    SA_HIP_CHECK(hipGetLastError());
+    if (n) dev_convert(s, (long)n, (const int *)narrow.p, dst.p);
     SA_HIP_CHECK(hipStreamSynchronize(s));      // `narrow` may be an upload that is freed on return
 }
 
@@ -1476,8 +1467,7 @@ void export_rowptr32(int *dst_host, const DBuf<roff_t> &src, size_t n, hipStream
     const roff_t last = read_one(src.p + (n - 1), s);
     SA_REQUIRE(last < ((roff_t)1 << 31), "operator has more than 2^31 entries: use the 64-bit getter");
     DBuf<int> narrow(n);
-    hipLaunchKernelGGL(narrow_offsets_kernel, dim3(div_up((long)n, 256)), dim3(256), 0, s, (long)n, src.p, narrow.p);
-    SA_HIP_CHECK(hipGetLastError());
+    dev_convert(s, (long)n, (const roff_t *)src.p, narrow.p);
     read_back(dst_host, narrow.p, n, s);
 }
 

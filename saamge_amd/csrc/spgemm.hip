@@ -9,6 +9,7 @@
 // writes: no floating-point atomics, results are run-to-run and rank-to-rank reproducible.
 // The row is then sorted by column (wave-level bitonic in LDS) and written out.
 #include "spgemm.h"
+#include "devtab.h"
 
 namespace saamge_amd {
 
@@ -218,9 +219,7 @@ static bool spgemm_dense_b(hipStream_t s, const DCsr &A, const DCsr &B, DCsr &C)
     hipLaunchKernelGGL(spgemm_dense_b_kernel, dim3(n), dim3(256), 0, s, 0, B.ncols, A.rowptr.p, A.col.p, A.val.p,
                        Bd.p, Bm.p, rowcnt.p, nullptr, nullptr, nullptr);
     exclusive_scan_off(s, n, rowcnt.p, C.rowptr.p);
-    roff_t nnz = 0;
-    SA_HIP_CHECK(hipMemcpyAsync(&nnz, C.rowptr.p + n, sizeof(roff_t), hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
+    roff_t nnz = read_one(C.rowptr.p + n, s);
     C.nnz = nnz;
     C.col.alloc((size_t)nnz + 1);
     C.val.alloc((size_t)nnz + 1);
@@ -278,9 +277,7 @@ void spgemm(hipStream_t s, const DCsr &A, const DCsr &B, const DCsr *E, const do
     SA_REQUIRE(tier < 3, "spgemm: a product row has more than ~8000 entries");
     g_last_route = tier;
     exclusive_scan_off(s, n, rowcnt.p, C.rowptr.p);
-    roff_t nnz = 0;
-    SA_HIP_CHECK(hipMemcpyAsync(&nnz, C.rowptr.p + n, sizeof(roff_t), hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
+    roff_t nnz = read_one(C.rowptr.p + n, s);
     C.nnz = nnz;
     C.col.alloc((size_t)nnz + 1);
     C.val.alloc((size_t)nnz + 1);
@@ -293,10 +290,6 @@ void spgemm(hipStream_t s, const DCsr &A, const DCsr &B, const DCsr *E, const do
 }
 
 // ---- transpose --------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void tr_count_kernel(long nnz, const int *__restrict__ col, int *__restrict__ cnt) {
-    const long k = (long)blockIdx.x * 256 + threadIdx.x;
-    if (k < nnz) atomicAdd(&cnt[col[k]], 1);
-}
 __global__ __launch_bounds__(256) void tr_fill_kernel(int nrows, const roff_t *__restrict__ rowptr,
                                                       const int *__restrict__ col, const double *__restrict__ val,
                                                       const roff_t *__restrict__ Trow, int *__restrict__ cursor,
@@ -365,7 +358,7 @@ void csr_transpose(hipStream_t s, const DCsr &P, DCsr &R) {
     DBuf<int> cnt((size_t)R.nrows), tcol((size_t)P.nnz + 1);
     DBuf<double> tval((size_t)P.nnz + 1);
     cnt.zero(s);
-    hipLaunchKernelGGL(tr_count_kernel, dim3(div_up(P.nnz, 256)), dim3(256), 0, s, (long)P.nnz, P.col.p, cnt.p);
+    dev_histogram(s, (long)P.nnz, P.col.p, cnt.p);
     exclusive_scan_off(s, R.nrows, cnt.p, R.rowptr.p);
     cnt.zero(s);
     hipLaunchKernelGGL(tr_fill_kernel, dim3(div_up((long)P.nrows * 4, 256)), dim3(256), 0, s, P.nrows, P.rowptr.p,
@@ -425,9 +418,7 @@ void csr_threshold(hipStream_t s, const DCsr &A, double tol, DCsr &C) {
         hipLaunchKernelGGL((threshold_kernel<false>), grid, dim3(256), 0, s, A.nrows, tol, A.rowptr.p, A.col.p,
                            A.val.p, cnt.p, nullptr, nullptr, nullptr);
     exclusive_scan_off(s, A.nrows, cnt.p, C.rowptr.p);
-    roff_t nnz = 0;
-    SA_HIP_CHECK(hipMemcpyAsync(&nnz, C.rowptr.p + A.nrows, sizeof(roff_t), hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
+    roff_t nnz = read_one(C.rowptr.p + A.nrows, s);
     C.nnz = nnz;
     C.col.alloc((size_t)nnz + 1);
     C.val.alloc((size_t)nnz + 1);

@@ -5,6 +5,7 @@
 // small thread pool; dof_to_elem and elem_ldof (only consumed by the assembly kernel) are
 // built on the device.
 #include "topology.h"
+#include "devtab.h"
 
 #include <algorithm>
 #include <atomic>
@@ -496,34 +497,6 @@ void build_relations_mis(Relations &r, const HostCsr *aggregates_A) {
 // device-side pieces: dof_to_elem (transpose with ascending rows) and elem_ldof
 // ---------------------------------------------------------------------------------------
 
-__global__ __launch_bounds__(256) void d2e_count_kernel(long nconn, const int *__restrict__ e2d_J,
-                                                        int *__restrict__ cnt) {
-    const long k = (long)blockIdx.x * 256 + threadIdx.x;
-    if (k < nconn) atomicAdd(&cnt[e2d_J[k]], 1);
-}
-__global__ __launch_bounds__(256) void d2e_fill_kernel(int NE, const int *__restrict__ e2d_I,
-                                                       const int *__restrict__ e2d_J,
-                                                       const int *__restrict__ d2e_I,
-                                                       int *__restrict__ cursor, int *__restrict__ d2e_J) {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= NE) return;
-    for (int k = e2d_I[e]; k < e2d_I[e + 1]; ++k) {
-        const int d = e2d_J[k];
-        d2e_J[d2e_I[d] + atomicAdd(&cursor[d], 1)] = (int)e;
-    }
-}
-__global__ __launch_bounds__(256) void d2e_sort_kernel(int ND, const int *__restrict__ d2e_I,
-                                                       int *__restrict__ d2e_J) {
-    const long d = (long)blockIdx.x * 256 + threadIdx.x;
-    if (d >= ND) return;
-    const int b = d2e_I[d], e = d2e_I[d + 1];
-    for (int i = b + 1; i < e; ++i) {  // insertion sort, rows are short
-        const int v = d2e_J[i];
-        int j = i - 1;
-        while (j >= b && d2e_J[j] > v) { d2e_J[j + 1] = d2e_J[j]; --j; }
-        d2e_J[j + 1] = v;
-    }
-}
 __global__ __launch_bounds__(256) void elem_ldof_kernel(int NE, const int *__restrict__ e2d_I,
                                                         const int *__restrict__ e2d_J,
                                                         const int *__restrict__ part,
@@ -559,13 +532,7 @@ void upload_relations_ae(DevRelations &d, const Relations &r, hipStream_t s) {
     d.elem_ldof.alloc((size_t)nconn);
     {
         DBuf<int> cnt((size_t)r.ND);
-        cnt.zero(s);
-        hipLaunchKernelGGL(d2e_count_kernel, dim3(div_up(nconn, 256)), dim3(256), 0, s, nconn, d.e2d_J.p, cnt.p);
-        exclusive_scan_int(s, r.ND, cnt.p, d.d2e_I.p);
-        cnt.zero(s);
-        hipLaunchKernelGGL(d2e_fill_kernel, dim3(div_up(r.NE, 256)), dim3(256), 0, s, r.NE, d.e2d_I.p,
-                           d.e2d_J.p, d.d2e_I.p, cnt.p, d.d2e_J.p);
-        hipLaunchKernelGGL(d2e_sort_kernel, dim3(div_up(r.ND, 256)), dim3(256), 0, s, r.ND, d.d2e_I.p, d.d2e_J.p);
+        dev_table_transpose(s, r.NE, d.e2d_I.p, d.e2d_J.p, nconn, r.ND, d.d2e_I.p, d.d2e_J.p, true, cnt.p);
         hipLaunchKernelGGL(elem_ldof_kernel, dim3(div_up(r.NE, 256)), dim3(256), 0, s, r.NE, d.e2d_I.p,
                            d.e2d_J.p, d.part.p, d.d2ae_I.p, d.d2ae_J.p, d.dof_id_inAE.p, d.elem_ldof.p);
         SA_HIP_CHECK(hipGetLastError());
@@ -591,14 +558,6 @@ __global__ __launch_bounds__(256) void topo_check_kernel(long NE, long nconn, in
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i < NE && (part[i] < 0 || part[i] >= nparts)) atomicOr(err, 1);
     if (i < nconn && (e2d_J[i] < 0 || e2d_J[i] >= ND)) atomicOr(err, 2);
-}
-__global__ __launch_bounds__(256) void iota_scaled_kernel(long n, int scale, int *__restrict__ out) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = (int)(i * scale);
-}
-__global__ __launch_bounds__(256) void key_count_kernel(long n, const int *__restrict__ key, int *__restrict__ cnt) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) atomicAdd(&cnt[key[i]], 1);
 }
 // Count and fill for keys that come in runs (the partition of lexicographically numbered elements: eight neighbours share an
 // agglomerate): one atomic per run of equal keys in a wavefront instead of one per element -- the 64 atomics of a wavefront fell
@@ -844,22 +803,13 @@ __global__ __launch_bounds__(256) void d2ae_sort_flags_kernel(int ND, const int 
     flags[d] = f;
 }
 
-template <class T>
-static void download(hvec<T> &dst, const DBuf<T> &src, size_t n, hipStream_t s) {
-    dst.resize(n);
-    if (n) SA_HIP_CHECK(hipMemcpyAsync(dst.data(), src.p, n * sizeof(T), hipMemcpyDeviceToHost, s));
-}
-
 bool build_relations_ae_device(Relations &r, DevRelations &d, const int *e2d_dev, int NE, int nde,
                                const int *e2d_I_dev, const int *part_dev, int nparts, int ND,
                                const signed char *bdr_dev, hipStream_t s) {
     const bool csr = e2d_I_dev != nullptr;      // elements of different sizes
     long nconn = (long)NE * nde;
     if (csr) {
-        int last = 0;
-        SA_HIP_CHECK(hipMemcpyAsync(&last, e2d_I_dev + NE, sizeof(int), hipMemcpyDeviceToHost, s));
-        SA_HIP_CHECK(hipStreamSynchronize(s));
-        nconn = last;
+        nconn = read_one(e2d_I_dev + NE, s);
     }
     r.ND = ND;
     r.NE = NE;
@@ -870,7 +820,7 @@ bool build_relations_ae_device(Relations &r, DevRelations &d, const int *e2d_dev
         d.e2d_I.view(const_cast<int *>(e2d_I_dev), (size_t)NE + 1);
     } else {
         d.e2d_I.alloc((size_t)NE + 1);
-        hipLaunchKernelGGL(iota_scaled_kernel, dim3(div_up((long)NE + 1, 256)), dim3(256), 0, s, (long)NE + 1, nde, d.e2d_I.p);
+        dev_iota(s, (long)NE + 1, nde, d.e2d_I.p);
     }
     DBuf<int> err(1), cnt((size_t)std::max(nparts, ND) + 1);
     err.zero(s);
@@ -893,14 +843,7 @@ bool build_relations_ae_device(Relations &r, DevRelations &d, const int *e2d_dev
     {
         SA_HIP_CHECK(hipEventRecord(ev_fork, s));
         SA_HIP_CHECK(hipStreamWaitEvent(s2, ev_fork, 0));
-        SA_HIP_CHECK(hipMemsetAsync(cnt2.p, 0, sizeof(int) * (size_t)ND, s2));
-        hipLaunchKernelGGL(d2e_count_kernel, dim3(div_up(nconn, 256)), dim3(256), 0, s2, nconn, d.e2d_J.p, cnt2.p);
-        exclusive_scan_int_async(s2, ND, cnt2.p, d.d2e_I.p, sums2.p);
-        SA_HIP_CHECK(hipMemsetAsync(cnt2.p, 0, sizeof(int) * (size_t)ND, s2));
-        hipLaunchKernelGGL(d2e_fill_kernel, dim3(div_up(NE, 256)), dim3(256), 0, s2, NE, d.e2d_I.p, d.e2d_J.p, d.d2e_I.p,
-                           cnt2.p, d.d2e_J.p);
-        hipLaunchKernelGGL(d2e_sort_kernel, dim3(div_up(ND, 256)), dim3(256), 0, s2, ND, d.d2e_I.p, d.d2e_J.p);
-        SA_HIP_CHECK(hipGetLastError());
+        dev_table_transpose_async(s2, NE, d.e2d_I.p, d.e2d_J.p, nconn, ND, d.d2e_I.p, d.d2e_J.p, true, cnt2.p, sums2.p);
         SA_HIP_CHECK(hipEventRecord(ev_join, s2));
     }
     struct JoinSide {      // (every way out of this function waits for the side stream: its buffers are released here)
@@ -979,7 +922,7 @@ bool build_relations_ae_device(Relations &r, DevRelations &d, const int *e2d_dev
     d.dof_id_inAE.alloc((size_t)nae2d);
     d.flags.alloc((size_t)ND);
     SA_HIP_CHECK(hipMemsetAsync(cnt.p, 0, sizeof(int) * (size_t)ND, s));
-    hipLaunchKernelGGL(key_count_kernel, dim3(div_up(nae2d, 256)), dim3(256), 0, s, nae2d, d.ae2d_J.p, cnt.p);
+    dev_histogram(s, nae2d, d.ae2d_J.p, cnt.p);
     hipLaunchKernelGGL(any_zero_kernel, dim3(div_up(ND, 256)), dim3(256), 0, s, (long)ND, cnt.p, 8, err.p);
     exclusive_scan_int(s, ND, cnt.p, d.d2ae_I.p);
     SA_HIP_CHECK(hipMemsetAsync(cnt.p, 0, sizeof(int) * (size_t)ND, s));

@@ -15,8 +15,7 @@
 //   3. mis_to_dof = stable radix sort of the dofs by MIS id (hipcub): ascending dofs inside a MIS.
 //   4. mis_to_AE = the representative's AE list; AE_to_mis = stable sort of the (MIS, AE) pairs by AE.
 //   5. pair_loc: AE-local index of every MIS dof for every AE of the MIS.
-#include <hipcub/hipcub.hpp>
-
+#include "devsort.h"
 #include "topology.h"
 
 namespace saamge_amd {
@@ -34,19 +33,6 @@ __device__ inline unsigned long long hash_ae_row(const int *row, int rs) {
     }
     h ^= h >> 29;
     return h == EMPTY_KEY ? 0ull : h;
-}
-
-__global__ __launch_bounds__(256) void mis_fill_kernel(long n, int v, int *p) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) p[i] = v;
-}
-__global__ __launch_bounds__(256) void mis_fill64_kernel(long n, unsigned long long v, unsigned long long *p) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) p[i] = v;
-}
-__global__ __launch_bounds__(256) void mis_iota_kernel(long n, int *p) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) p[i] = (int)i;
 }
 
 __global__ __launch_bounds__(256) void mis_multi_flag_kernel(int ND, const int *__restrict__ I, int *__restrict__ flag) {
@@ -105,11 +91,6 @@ __global__ __launch_bounds__(256) void mis_ids_kernel(int ND, const int *__restr
     if (is_rep[i]) reps[rank[i]] = (int)i;
 }
 
-__global__ __launch_bounds__(256) void mis_hist_kernel(long n, const int *__restrict__ key, int *__restrict__ cnt) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) atomicAdd(&cnt[key[i]], 1);
-}
-
 __global__ __launch_bounds__(256) void mis_rowpos_kernel(int ND, const int *__restrict__ mis2d_I, const int *__restrict__ mis2d_J,
                                                          const int *__restrict__ mises, int *__restrict__ row_in_mis) {
     const long k = (long)blockIdx.x * 256 + threadIdx.x;
@@ -144,10 +125,6 @@ __global__ __launch_bounds__(256) void mis_pair_size_kernel(long npairs, const i
     const long q = (long)blockIdx.x * 256 + threadIdx.x;
     if (q < npairs) { const int m = mis_of_pair[q]; sz[q] = mis2d_I[m + 1] - mis2d_I[m]; }
 }
-__global__ __launch_bounds__(256) void mis_widen_kernel(long n, const int *__restrict__ in, int64_t *__restrict__ out) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = in[i];
-}
 __global__ __launch_bounds__(256) void mis_pair_loc_kernel(int ND, const int *__restrict__ I, const int *__restrict__ dof_id_inAE,
                                                            const int *__restrict__ mises, const int *__restrict__ row_in_mis,
                                                            const int *__restrict__ mis2ae_I, const int64_t *__restrict__ pair_loc_off,
@@ -157,30 +134,6 @@ __global__ __launch_bounds__(256) void mis_pair_loc_kernel(int ND, const int *__
     const int m = mises[i], k = row_in_mis[i], q0 = mis2ae_I[m];
     // every dof of the MIS has the same AE list: the t-th AE of the dof's row is the t-th AE of the MIS
     for (int t = 0; t < I[i + 1] - I[i]; ++t) pair_loc[pair_loc_off[q0 + t] + k] = dof_id_inAE[I[i] + t];
-}
-
-int bits_for(int n) {
-    int b = 1;
-    while ((1ll << b) < n) ++b;
-    return b;
-}
-
-// stable sort of the pairs (key[i], i) by key; out_vals = the permutation
-void stable_sort_by_key(hipStream_t s, int n, const int *key, int nkeys, int *out_vals) {
-    if (n == 0) return;
-    DBuf<int> iota((size_t)n), keys_out((size_t)n);
-    hipLaunchKernelGGL(mis_iota_kernel, dim3(div_up(n, 256)), dim3(256), 0, s, (long)n, iota.p);
-    size_t tmp_bytes = 0;
-    SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, key, keys_out.p, iota.p, out_vals, n, 0, bits_for(nkeys), s));
-    DBuf<char> tmp(tmp_bytes + 16);
-    SA_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs((void *)tmp.p, tmp_bytes, key, keys_out.p, iota.p, out_vals, n, 0, bits_for(nkeys), s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));      // the temporaries go out of scope
-}
-
-template <class T>
-void fetch(hvec<T> &dst, const DBuf<T> &src, size_t n, hipStream_t s) {
-    dst.resize(n);
-    if (n) SA_HIP_CHECK(hipMemcpyAsync(dst.data(), src.p, sizeof(T) * n, hipMemcpyDeviceToHost, s));
 }
 
 }  // namespace
@@ -197,16 +150,14 @@ bool build_relations_mis_device(Relations &r, DevRelations &d, hipStream_t s) {
     DBuf<int> flag((size_t)ND + 1), pos((size_t)ND + 2);
     hipLaunchKernelGGL(mis_multi_flag_kernel, dim3(g), dim3(256), 0, s, ND, I, flag.p);
     exclusive_scan_int(s, ND, flag.p, pos.p);
-    int n_multi = 0;
-    SA_HIP_CHECK(hipMemcpyAsync(&n_multi, pos.p + ND, sizeof(int), hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
+    const int n_multi = read_one((const int *)pos.p + ND, s);
     unsigned cap = 1024;
     while (cap < 2u * (unsigned)std::max(n_multi, 1)) cap <<= 1;
     DBuf<unsigned long long> keys((size_t)cap);
     DBuf<int> minv((size_t)cap), single_min((size_t)nparts), hslot((size_t)ND), rep_of((size_t)ND), err(1);
-    hipLaunchKernelGGL(mis_fill64_kernel, dim3(div_up(cap, 256)), dim3(256), 0, s, (long)cap, EMPTY_KEY, keys.p);
-    hipLaunchKernelGGL(mis_fill_kernel, dim3(div_up(cap, 256)), dim3(256), 0, s, (long)cap, 0x7fffffff, minv.p);
-    hipLaunchKernelGGL(mis_fill_kernel, dim3(div_up(nparts, 256)), dim3(256), 0, s, (long)nparts, 0x7fffffff, single_min.p);
+    dev_fill(s, (long)cap, EMPTY_KEY, keys.p);
+    dev_fill(s, (long)cap, 0x7fffffff, minv.p);
+    dev_fill(s, (long)nparts, 0x7fffffff, single_min.p);
     err.zero(s);
     hipLaunchKernelGGL(mis_insert_kernel, dim3(g), dim3(256), 0, s, ND, I, J, single_min.p, keys.p, minv.p, cap - 1, hslot.p);
     hipLaunchKernelGGL(mis_rep_kernel, dim3(g), dim3(256), 0, s, ND, I, J, single_min.p, minv.p, hslot.p, rep_of.p, flag.p, err.p);
@@ -227,7 +178,7 @@ bool build_relations_mis_device(Relations &r, DevRelations &d, hipStream_t s) {
     {
         DBuf<int> cnt((size_t)nm + 1);
         cnt.zero(s);
-        hipLaunchKernelGGL(mis_hist_kernel, dim3(g), dim3(256), 0, s, (long)ND, d.mises.p, cnt.p);
+        dev_histogram(s, (long)ND, d.mises.p, cnt.p);
         exclusive_scan_int(s, nm, cnt.p, d.mis2d_I.p);
     }
     stable_sort_by_key(s, ND, d.mises.p, nm, d.mis2d_J.p);
@@ -240,9 +191,7 @@ bool build_relations_mis_device(Relations &r, DevRelations &d, hipStream_t s) {
         hipLaunchKernelGGL(mis_ae_count_kernel, dim3(div_up(nm, 256)), dim3(256), 0, s, nm, reps.p, I, cnt.p);
         exclusive_scan_int(s, nm, cnt.p, d.mis2ae_I.p);
     }
-    int npairs = 0;
-    SA_HIP_CHECK(hipMemcpyAsync(&npairs, d.mis2ae_I.p + nm, sizeof(int), hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
+    const int npairs = read_one((const int *)d.mis2ae_I.p + nm, s);
     d.mis2ae_J.alloc((size_t)npairs);
     DBuf<int> mis_of_pair((size_t)npairs);
     hipLaunchKernelGGL(mis_ae_fill_kernel, dim3(div_up(nm, 256)), dim3(256), 0, s, nm, reps.p, I, J, d.mis2ae_I.p, d.mis2ae_J.p,
@@ -253,7 +202,7 @@ bool build_relations_mis_device(Relations &r, DevRelations &d, hipStream_t s) {
     {
         DBuf<int> cnt((size_t)nparts + 1);
         cnt.zero(s);
-        hipLaunchKernelGGL(mis_hist_kernel, dim3(div_up(npairs, 256)), dim3(256), 0, s, (long)npairs, d.mis2ae_J.p, cnt.p);
+        dev_histogram(s, (long)npairs, d.mis2ae_J.p, cnt.p);
         exclusive_scan_int(s, nparts, cnt.p, d.ae2mis_I.p);
     }
     stable_sort_by_key(s, npairs, d.mis2ae_J.p, nparts, d.ae_pair.p);
@@ -266,7 +215,7 @@ bool build_relations_mis_device(Relations &r, DevRelations &d, hipStream_t s) {
         hipLaunchKernelGGL(mis_pair_size_kernel, dim3(div_up(npairs, 256)), dim3(256), 0, s, (long)npairs, mis_of_pair.p, d.mis2d_I.p, sz.p);
         exclusive_scan_int(s, npairs, sz.p, off.p);      // (the total is the number of (dof, AE) incidences: fits 32 bits with d2ae_J)
         SA_HIP_CHECK(hipMemcpyAsync(&total, off.p + npairs, sizeof(int), hipMemcpyDeviceToHost, s));
-        hipLaunchKernelGGL(mis_widen_kernel, dim3(div_up(npairs + 1, 256)), dim3(256), 0, s, (long)npairs + 1, off.p, d.pair_loc_off.p);
+        dev_convert(s, (long)npairs + 1, (const int *)off.p, d.pair_loc_off.p);
         SA_HIP_CHECK(hipStreamSynchronize(s));
     }
     d.pair_loc.alloc((size_t)total);
@@ -275,16 +224,16 @@ bool build_relations_mis_device(Relations &r, DevRelations &d, hipStream_t s) {
     SA_HIP_CHECK(hipGetLastError());
     // ---- host copies of what host code reads ----
     r.num_mises = nm;
-    fetch(r.mises, d.mises, (size_t)ND, s);
+    download(r.mises, d.mises, (size_t)ND, s);
     r.mis_to_dof.ncols = ND;
-    fetch(r.mis_to_dof.I, d.mis2d_I, (size_t)nm + 1, s);
-    fetch(r.mis_to_dof.J, d.mis2d_J, (size_t)ND, s);
+    download(r.mis_to_dof.I, d.mis2d_I, (size_t)nm + 1, s);
+    download(r.mis_to_dof.J, d.mis2d_J, (size_t)ND, s);
     r.mis_to_AE.ncols = nparts;
-    fetch(r.mis_to_AE.I, d.mis2ae_I, (size_t)nm + 1, s);
-    fetch(r.mis_to_AE.J, d.mis2ae_J, (size_t)npairs, s);
+    download(r.mis_to_AE.I, d.mis2ae_I, (size_t)nm + 1, s);
+    download(r.mis_to_AE.J, d.mis2ae_J, (size_t)npairs, s);
     r.AE_to_mis.ncols = nm;
-    fetch(r.AE_to_mis.I, d.ae2mis_I, (size_t)nparts + 1, s);
-    fetch(r.AE_to_mis.J, d.ae2mis_J, (size_t)npairs, s);
+    download(r.AE_to_mis.I, d.ae2mis_I, (size_t)nparts + 1, s);
+    download(r.AE_to_mis.J, d.ae2mis_J, (size_t)npairs, s);
     SA_HIP_CHECK(hipStreamSynchronize(s));
     return true;
 }

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <vector>
 #include "sparse.h"
+#include "devtab.h"
 using namespace saamge_amd;
 
 __global__ void count_kernel(int n, int *cnt) {
