@@ -265,7 +265,7 @@ static void blocktri_sweeps(hipStream_t s, const BlockTri &B, const double *b, d
     }
     {
         const int r0 = B.off[K - 1], nk = B.off[K] - r0;
-        SA_HIP_CHECK(hipMemcpyAsync(B.xp.p + r0, B.z.p + r0, 8 * (size_t)nk, hipMemcpyDeviceToDevice, s));
+        copy_device(B.xp.p + r0, (const double *)B.z.p + r0, (size_t)nk, s);
     }
     for (int k = K - 2; k >= 0; --k) {
         const int r0 = B.off[k], nk = B.off[k + 1] - r0;

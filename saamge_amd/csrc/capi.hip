@@ -27,7 +27,7 @@ struct saamge_amd_hierarchy {
 struct saamge_amd_partitioning {
     int device = 0;
     std::vector<DBuf<int>> part;             // device
-    std::vector<std::vector<int>> part_host;
+    std::vector<hvec<int>> part_host;
     std::vector<const int *> part_ptr, part_host_ptr;
     std::vector<int> n_elem, nparts;
     std::vector<DBuf<roff_t>> xadj;
@@ -98,10 +98,9 @@ static int mesh_handle_call(const char *name, H **out, bool clear, const MeshArg
 static void require_device(int device, const char *what) {
     SA_REQUIRE(current_device() == device, std::string("the calling thread's current HIP device is not the ") + what + "'s device");
 }
+// an output of a getter of a handle without a stream (the call that built it has synchronised its own): on the null stream
 template <class T>
-static void copy_out(void *dst, const DBuf<T> &src) {
-    if (dst && src.n) SA_HIP_CHECK(hipMemcpy(dst, src.p, src.n * sizeof(T), hipMemcpyDefault));
-}
+static void copy_out(void *dst, const DBuf<T> &src) { copy_to_caller((T *)dst, src, (hipStream_t) nullptr); }
 
 extern "C" int saamge_amd_comm_native_stream(const saamge_amd_params *p, void **stream);      // comm.hip
 
@@ -357,33 +356,9 @@ void saamge_amd_ml_free_data(saamge_amd_hierarchy *h) {
     }
 }
 
-// stage a host vector on the device when needed
-struct VecIn {
-    DBuf<double> buf;
-    const double *p;
-    VecIn(const double *src, size_t n, hipStream_t s) {
-        if (is_device_ptr(src)) p = src;
-        else { buf.assign(src, n, s); p = buf.p; }
-    }
-};
-struct VecOut {
-    DBuf<double> buf;
-    double *p, *host = nullptr;
-    size_t n;
-    hipStream_t s;
-    VecOut(double *dst, size_t n_, hipStream_t s_, bool load) : n(n_), s(s_) {
-        if (is_device_ptr(dst)) p = dst;
-        else {
-            host = dst;
-            if (load) buf.assign(dst, n, s); else buf.alloc(n);
-            p = buf.p;
-        }
-    }
-    void finish() {
-        if (host && n) SA_HIP_CHECK(hipMemcpyAsync(host, p, 8 * n, hipMemcpyDeviceToHost, s));
-        SA_HIP_CHECK(hipStreamSynchronize(s));
-    }
-};
+// the vectors of a call: host arrays are staged on the device (xfer.h)
+typedef DevIn<double> VecIn;
+typedef DevOut<double> VecOut;
 
 int saamge_amd_vcycle_mult(saamge_amd_hierarchy *h, const double *b, double *x) {
     SA_API_BEGIN
@@ -539,8 +514,7 @@ int saamge_amd_level_order_info(const saamge_amd_hierarchy *h, int level, long l
     if (H.params.opt.ae_order == 1) {      // what the setup's ordering pass added up
         if (L.order_info.n == 4) {
             int v[4];
-            SA_HIP_CHECK(hipMemcpyAsync(v, L.order_info.p, sizeof v, hipMemcpyDeviceToHost, s));
-            SA_HIP_CHECK(hipStreamSynchronize(s));
+            read_back(v, (const int *)L.order_info.p, 4, s);
             for (int i = 0; i < 4; ++i) info[i] = v[i];
         }
     } else {      // ae_order = 0: the setup measures nothing; the band of the rank / box order of those chunks, now
@@ -594,12 +568,11 @@ static int get_csr(const saamge_amd_hierarchy *h, int level, int which, void *ro
     const DCsr &M = level_op(H, level, which);
     hipStream_t s = H.stream;
     if (rowptr && rowptr_bits == 64)
-        SA_HIP_CHECK(hipMemcpyAsync(rowptr, M.rowptr.p, sizeof(roff_t) * ((size_t)M.nrows + 1), hipMemcpyDeviceToHost, s));
+        copy_to_caller((roff_t *)rowptr, (const roff_t *)M.rowptr.p, (size_t)M.nrows + 1, s);
     else if (rowptr)
         export_rowptr32((int *)rowptr, M.rowptr, (size_t)M.nrows + 1, s);
-    if (col && M.nnz) SA_HIP_CHECK(hipMemcpyAsync(col, M.col.p, 4 * (size_t)M.nnz, hipMemcpyDeviceToHost, s));
-    if (val && M.nnz) SA_HIP_CHECK(hipMemcpyAsync(val, M.val.p, 8 * (size_t)M.nnz, hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
+    copy_to_caller(col, (const int *)M.col.p, (size_t)M.nnz, s);
+    copy_to_caller(val, (const double *)M.val.p, (size_t)M.nnz, s);
     SA_API_END
 }
 int saamge_amd_get_csr(const saamge_amd_hierarchy *h, int level, int which, int *rowptr, int *col, double *val) {
@@ -672,10 +645,9 @@ int saamge_amd_get_ae_eigens(const saamge_amd_hierarchy *h, int level, int *ae_m
     hipStream_t s = H.stream;
     if (ae_m) std::copy(L.ae_m.begin(), L.ae_m.end(), ae_m);
     if (evals || evecs || ae_D) SA_REQUIRE(H.params.keep_debug, "hierarchy was built without keep_debug");
-    if (evals && L.evals.n) SA_HIP_CHECK(hipMemcpyAsync(evals, L.evals.p, 8 * L.evals.n, hipMemcpyDeviceToHost, s));
-    if (evecs && L.evecs.n) SA_HIP_CHECK(hipMemcpyAsync(evecs, L.evecs.p, 8 * L.evecs.n, hipMemcpyDeviceToHost, s));
-    if (ae_D && L.ae_D.n) SA_HIP_CHECK(hipMemcpyAsync(ae_D, L.ae_D.p, 8 * L.ae_D.n, hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
+    copy_to_caller(evals, L.evals, s);
+    copy_to_caller(evecs, L.evecs, s);
+    copy_to_caller(ae_D, L.ae_D, s);
     SA_API_END
 }
 
@@ -690,7 +662,7 @@ int saamge_amd_get_mis_svd(const saamge_amd_hierarchy *h, int level, long long *
     if (sig_off) for (int m = 0; m <= nm; ++m) sig_off[m] = L.mis_s_off[m];
     if (sig) {
         SA_REQUIRE(H.params.keep_debug, "hierarchy was built without keep_debug");
-        if (L.mis_s_off[nm]) SA_HIP_CHECK(hipMemcpyAsync(sig, L.mis_sig.p, 8 * (size_t)L.mis_s_off[nm], hipMemcpyDeviceToHost, s));
+        copy_to_caller(sig, (const double *)L.mis_sig.p, (size_t)L.mis_s_off[nm], s);
     }
     if (U) {
         auto all = L.mis_U.to_host(s);
@@ -701,7 +673,6 @@ int saamge_amd_get_mis_svd(const saamge_amd_hierarchy *h, int level, long long *
             o += cnt;
         }
     }
-    SA_HIP_CHECK(hipStreamSynchronize(s));
     SA_API_END
 }
 
@@ -719,8 +690,8 @@ static int spmv_entry(int nrows, int ncols, const void *rowptr, int rowptr_bits,
     import_rowptr(A.rowptr, rowptr, rowptr_bits, (size_t)nrows + 1, s);
     roff_t nnz = read_one(A.rowptr.p + nrows, s);
     A.nnz = nnz;
-    import_array(A.col, col, (size_t)A.nnz, s);
-    import_array(A.val, val, (size_t)A.nnz, s);
+    A.col = DevIn<int>(col, (size_t)A.nnz, s).take();
+    A.val = DevIn<double>(val, (size_t)A.nnz, s).take();
     A.lanes_per_row = pick_lanes_per_row(A.nnz, nrows > 0 ? nrows : 1);
     // spmv_sell (tests): through the SELL-64 copy and its coded slices, the format of the level operators
     if (nrows == ncols && opt.spmv_sell) build_sell(s, A, opt);
@@ -756,18 +727,16 @@ static void import_host_csr(DCsr &M, const char *name, int nrows, int ncols, con
     import_rowptr(M.rowptr, rowptr, 32, (size_t)nrows + 1, s);
     M.col.assign(col, nnz, s);
     M.val.assign(val, nnz, s);
-    SA_HIP_CHECK(hipStreamSynchronize(s));
     M.lanes_per_row = pick_lanes_per_row(M.nnz, nrows > 0 ? nrows : 1);
 }
 // row offsets and *nnz always; the entries when both arrays are given (the first call of a caller asks for the sizes)
 static void export_host_csr(const DCsr &M, int *rowptr, long long *nnz, int *col, double *val, hipStream_t s) {
     if (rowptr) export_rowptr32(rowptr, M.rowptr, (size_t)M.nrows + 1, s);
     if (nnz) *nnz = (long long)M.nnz;
-    if (col && val && M.nnz) {
-        SA_HIP_CHECK(hipMemcpyAsync(col, M.col.p, 4 * (size_t)M.nnz, hipMemcpyDeviceToHost, s));
-        SA_HIP_CHECK(hipMemcpyAsync(val, M.val.p, 8 * (size_t)M.nnz, hipMemcpyDeviceToHost, s));
+    if (col && val) {
+        copy_to_caller(col, (const int *)M.col.p, (size_t)M.nnz, s);
+        copy_to_caller(val, (const double *)M.val.p, (size_t)M.nnz, s);
     }
-    SA_HIP_CHECK(hipStreamSynchronize(s));
 }
 
 int saamge_amd_spgemm(int nrows, int ninner, int ncols, const int *Arow, const int *Acol, const double *Aval,
@@ -827,7 +796,7 @@ int saamge_amd_ae_order(int ND, int NE, int nde, const int *elem_ptr, const int 
         // (no eigensolver workspace: the sizes and row offsets of the batch only)
         EigBatch b;
         b.count = nparts;
-        b.h_n = sizes;
+        b.h_n.assign(sizes.begin(), sizes.end());
         b.h_voff.assign((size_t)nparts + 1, 0);
         for (int p = 0; p < nparts; ++p) {
             b.h_voff[(size_t)p + 1] = b.h_voff[(size_t)p] + sizes[(size_t)p];
@@ -1189,7 +1158,7 @@ __global__ void apply_dscale_kernel(int count, const int *ns, const int64_t *mof
 
 // W = D^-1/2 A D^-1/2 of every matrix of the batch, from the caller's A (host or device) and the diagonals dD (device)
 static void upload_scaled(hipStream_t s, EigBatch &b, const double *A, const double *dD) {
-    SA_HIP_CHECK(hipMemcpyAsync(b.W.p, A, 8 * (size_t)b.h_moff[b.count], hipMemcpyDefault, s));
+    upload(b.W.p, A, (size_t)b.h_moff[b.count], s);
     hipLaunchKernelGGL(apply_dscale_kernel, dim3(b.count), dim3(256), 0, s, b.count, b.n.p, b.moff.p, b.voff.p, b.W.p, dD,
                        b.dis.p);
 }
@@ -1263,6 +1232,7 @@ void saamge_amd_release_cached_memory(void) {
     (void)hipDeviceSynchronize();
     eig_arena_release();
     dev_pool_release();
+    pinned_pool_release();      // the idle page-locked blocks as well (not counted by saamge_amd_cached_memory_bytes)
 }
 long long saamge_amd_cached_memory_bytes(void) { return (long long)dev_pool_idle_bytes(); }
 void saamge_amd_memory_stats(long long *live_bytes, long long *peak_bytes, int reset_peak) {
@@ -1349,9 +1319,10 @@ void saamge_amd_partition_growth_info(long long info[4]) {
 
 // a caller's graph on the device, checked: host columns need host offsets, which are checked before they say how much to copy
 static void import_graph(hipStream_t s, int n, const long long *xadj, const int *adj, DBuf<roff_t> &dx, DBuf<int> &da) {
-    import_array(dx, (const roff_t *)xadj, (size_t)n + 1, s);
+    DevIn<roff_t> in_x((const roff_t *)xadj, (size_t)n + 1, s);
+    dx = in_x.take();
     if (!is_device_ptr(adj)) {
-        const bool xh = !is_device_ptr(xadj);
+        const bool xh = !in_x.on_device;
         if (xh) for (int i = 0; i < n; ++i) SA_REQUIRE(xadj[0] == 0 && xadj[i + 1] >= xadj[i], "xadj: must start at 0 and ascend");
         const roff_t nnz = n == 0 ? 0 : (xh ? (roff_t)xadj[n] : 0);
         SA_REQUIRE(xh || n == 0, "xadj on the device with adj on the host");
@@ -1385,13 +1356,11 @@ int saamge_amd_partition_graph_v2(int n, const long long *xadj, const int *adj, 
     ThreadStreamScope scope(s);
     {
         DBuf<roff_t> dx;
-        DBuf<int> da, dp;
+        DBuf<int> da;
         import_graph(s, n, xadj, adj, dx, da);
-        if (is_device_ptr(part)) dp.view(part, (size_t)n);
-        else dp.alloc((size_t)n);
+        DevOut<int> dp(part, (size_t)n, s, false);
         partition_graph_device(s, n, dx.p, da.p, elems_per_agg, po, dp.p, nparts_out, &t_partition_stats);
-        if (n && !is_device_ptr(part)) SA_HIP_CHECK(hipMemcpyAsync(part, dp.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-        SA_HIP_CHECK(hipStreamSynchronize(s));
+        dp.finish();
     }
     SA_API_END
 }
@@ -1412,7 +1381,7 @@ int saamge_amd_partition_refine(int n, const long long *xadj, const int *adj, in
         DBuf<roff_t> dx;
         DBuf<int> da, lab((size_t)n), out;
         import_graph(s, n, xadj, adj, dx, da);
-        if (n) SA_HIP_CHECK(hipMemcpyAsync(lab.p, part, (size_t)n * sizeof(int), hipMemcpyDefault, s));
+        upload(lab.p, (const int *)part, (size_t)n, s);
         check_partition_device(s, n, lab.p, nparts);
         t_refine_stats = RefineStats();
         const RefineStats st = t_refine_stats = refine_partition_device(s, n, dx.p, da.p, nparts, lab.p, rounds, max_size, min_size, seed);
@@ -1423,7 +1392,7 @@ int saamge_amd_partition_refine(int n, const long long *xadj, const int *adj, in
             renumber_device(s, n, lab.p, nparts, out.p, &np);
             result = out.p;
         }
-        if (n) SA_HIP_CHECK(hipMemcpyAsync(part, result, (size_t)n * sizeof(int), hipMemcpyDefault, s));
+        copy_to_caller(part, result, (size_t)n, s);
         SA_HIP_CHECK(hipStreamSynchronize(s));
         if (info) { info[0] = st.rounds; info[1] = st.moved; info[2] = st.gain; info[3] = st.converged; }
     }
@@ -1461,7 +1430,7 @@ int saamge_amd_partition_mesh_refined(int NE, int nde, const int *elem_ptr, cons
     {
         DBuf<int> eI, eJ;
         if (elem_ptr) {
-            import_array(eI, elem_ptr, (size_t)NE + 1, s);
+            eI = DevIn<int>(elem_ptr, (size_t)NE + 1, s).take();
         } else {
             SA_REQUIRE((int64_t)NE * nde < INT_MAX, "NE * nde beyond 32 bits");
             std::vector<int> h((size_t)NE + 1);
@@ -1492,17 +1461,14 @@ int saamge_amd_partition_mesh_refined(int NE, int nde, const int *elem_ptr, cons
             int max_size = 0, min_size = 0;
             resolve_partition_sizes(elems_per_agg[k], po, &max_size, &min_size);
             DBuf<int> lab((size_t)n);
-            SA_HIP_CHECK(hipMemcpyAsync(lab.p, P->part.back().p, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, s));
+            copy_device(lab.p, (const int *)P->part.back().p, (size_t)n, s);
             t_refine_stats = refine_partition_device(s, n, P->xadj[(size_t)k].p, P->adj[(size_t)k].p, np, lab.p, refine_rounds[k],
                                                      max_size, min_size, po.seed);
             renumber_device(s, n, lab.p, np, P->part.back().p, &np);
         }
         P->n_elem.push_back(n);
         P->nparts.push_back(np);
-        std::vector<int> h((size_t)n);
-        if (n) SA_HIP_CHECK(hipMemcpyAsync(h.data(), P->part.back().p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-        SA_HIP_CHECK(hipStreamSynchronize(s));
-        P->part_host.push_back(std::move(h));
+        P->part_host.push_back(P->part.back().to_host(s));
         P->xadj.emplace_back();
         P->adj.emplace_back();
         quotient_graph_device(s, n, P->xadj[(size_t)k].p, P->adj[(size_t)k].p, P->part.back().p, np, P->xadj.back(), P->adj.back());
@@ -1530,7 +1496,7 @@ int saamge_amd_partitioning_get(const saamge_amd_partitioning *p, int level, int
     SA_API_BEGIN
     SA_REQUIRE(p, "null argument");
     SA_REQUIRE(level >= 0 && level < (int)p->part.size(), "level out of range");
-    const std::vector<int> &h = p->part_host[(size_t)level];
+    const hvec<int> &h = p->part_host[(size_t)level];
     if (part_host && !h.empty()) std::memcpy(part_host, h.data(), h.size() * sizeof(int));
     if (n_elem) *n_elem = p->n_elem[(size_t)level];
     if (nparts) *nparts = p->nparts[(size_t)level];
@@ -1547,8 +1513,8 @@ int saamge_amd_partitioning_graph(const saamge_amd_partitioning *p, int level, l
     const size_t nn = p->xadj[l].n - 1;
     if (n) *n = (int)nn;
     if (nnz) *nnz = p->nnz[l];
-    if (xadj) SA_HIP_CHECK(hipMemcpy(xadj, p->xadj[l].p, (nn + 1) * sizeof(roff_t), hipMemcpyDefault));
-    if (adj && p->nnz[l]) SA_HIP_CHECK(hipMemcpy(adj, p->adj[l].p, (size_t)p->nnz[l] * sizeof(int), hipMemcpyDefault));
+    copy_to_caller((roff_t *)xadj, (const roff_t *)p->xadj[l].p, nn + 1, nullptr);
+    copy_to_caller(adj, (const int *)p->adj[l].p, (size_t)p->nnz[l], nullptr);
     SA_API_END
 }
 
@@ -1589,9 +1555,10 @@ int saamge_amd_operator_get(const saamge_amd_operator *op, long long *rowptr, in
     const AssembledOperator &o = op->op;
     require_operator_device(o);
     if (nnz) *nnz = (long long)o.nnz;
-    if (rowptr) SA_HIP_CHECK(hipMemcpy(rowptr, o.rowptr.p, ((size_t)o.n + 1) * sizeof(roff_t), hipMemcpyDefault));
-    if (col && o.nnz) SA_HIP_CHECK(hipMemcpy(col, o.col.p, (size_t)o.nnz * sizeof(int), hipMemcpyDefault));
-    if (val && o.nnz) SA_HIP_CHECK(hipMemcpy(val, o.val.p, (size_t)o.nnz * sizeof(double), hipMemcpyDefault));
+    // (on the null stream, as the other getters of handles)
+    copy_to_caller((roff_t *)rowptr, (const roff_t *)o.rowptr.p, (size_t)o.n + 1, nullptr);
+    copy_to_caller(col, (const int *)o.col.p, (size_t)o.nnz, nullptr);
+    copy_to_caller(val, (const double *)o.val.p, (size_t)o.nnz, nullptr);
     SA_API_END
 }
 
@@ -1715,17 +1682,17 @@ int saamge_amd_lobpcg(saamge_amd_hierarchy *h, const long long *Mrowptr, const i
         M.nrows = M.ncols = n;
         M.nnz = rp[n];
         import_rowptr(M.rowptr, Mrowptr, 64, (size_t)n + 1, s);
-        import_array(M.col, Mcol, (size_t)M.nnz, s);
-        import_array(M.val, Mval, (size_t)M.nnz, s);
+        M.col = DevIn<int>(Mcol, (size_t)M.nnz, s).take();
+        M.val = DevIn<double>(Mval, (size_t)M.nnz, s).take();
         M.lanes_per_row = pick_lanes_per_row(M.nnz, n);
     }
-    DBuf<double> start;
-    if (x0) import_array(start, x0, (size_t)n * lo.nb, s);
+    DevIn<double> start;
+    start.bind(x0, (size_t)n * lo.nb, s);
     std::vector<double> ev(lo.nev), rs(lo.nev);
     int it = 0, conv = 0;
     {
         VecOut vx(evecs, (size_t)n * lo.nev, s, false);
-        lobpcg_solve(H, Mrowptr ? &M : nullptr, lo, x0 ? start.p : nullptr, ev.data(), vx.p, rs.data(), &it, &conv, hist);
+        lobpcg_solve(H, Mrowptr ? &M : nullptr, lo, start.p, ev.data(), vx.p, rs.data(), &it, &conv, hist);
         vx.finish();
     }
     std::copy(ev.begin(), ev.end(), evals);

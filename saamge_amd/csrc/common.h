@@ -49,30 +49,6 @@ inline void adopt_device(int dev) { SA_HIP_CHECK(hipSetDevice(dev)); }
 // non-blocking helper stream number `slot` of the calling thread's current device
 hipStream_t side_stream(int slot);
 
-// ---- pinned host memory: pooled allocator for the big host-side tables -----------------
-// Pageable <-> device copies run at a few GB/s; page-locked ones at PCIe speed.  hipHostMalloc
-// itself is slow (it pins pages), so freed blocks are kept in a size-class pool and reused
-// by the next level / hierarchy.
-void *pinned_alloc(size_t bytes);
-void pinned_free(void *p, size_t bytes);
-void pinned_pool_release();
-
-template <class T>
-struct PinnedAlloc {
-    typedef T value_type;
-    PinnedAlloc() {}
-    template <class U>
-    PinnedAlloc(const PinnedAlloc<U> &) {}
-    T *allocate(size_t n) { return (T *)pinned_alloc(n * sizeof(T)); }
-    void deallocate(T *p, size_t n) { pinned_free((void *)p, n * sizeof(T)); }
-    template <class U>
-    bool operator==(const PinnedAlloc<U> &) const { return true; }
-    template <class U>
-    bool operator!=(const PinnedAlloc<U> &) const { return false; }
-};
-template <class T>
-using hvec = std::vector<T, PinnedAlloc<T>>;
-
 inline bool is_device_ptr(const void *p) {
     if (!p) return false;
     hipPointerAttribute_t a;
@@ -83,6 +59,10 @@ inline bool is_device_ptr(const void *p) {
     }
     return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
 }
+
+}  // namespace saamge_amd
+#include "xfer.h"      // the pinned host pool, hvec, and the transfer layer: every host <-> device and device <-> device copy
+namespace saamge_amd {
 
 // ---- process-wide diagnostics and the host heap policy (runtime.hip) ----------------------
 // Applied once, with the host_heap_pad_mb of the first hierarchy of the process (capi.hip): see Options::host_heap_pad_mb
@@ -123,7 +103,7 @@ struct ThreadStreamScope {       // the calling thread's stream for a scope (res
 // event on a dead handle.
 void dev_pool_close_stream(hipStream_t s);
 
-// RAII device buffer.
+// RAII device buffer.  What fills and reads it is in xfer.h.
 template <class T>
 struct DBuf {
     T *p = nullptr;
@@ -155,89 +135,17 @@ struct DBuf {
     void zero(hipStream_t s = 0) {
         if (n) SA_HIP_CHECK(hipMemsetAsync(p, 0, n * sizeof(T), s));
     }
-    // copy from a host OR device pointer
-    void assign(const T *src, size_t n_, hipStream_t s = 0) {
-        alloc(n_);
-        if (!n) return;
-        SA_HIP_CHECK(hipMemcpyAsync(p, src, n * sizeof(T), hipMemcpyDefault, s));
-    }
+    // a copy of n values at a host OR device pointer, of a host vector; back as a host vector.  All complete on return (xfer.h).
+    void assign(const T *src, size_t n_, hipStream_t s = 0) { upload(*this, src, n_, s); }
     template <class V>
-    void from_host(const V &v, hipStream_t s = 0) {
-        alloc(v.size());
-        if (!n) return;
-        const size_t bytes = n * sizeof(T);
-        // A large pageable vector goes through a page-locked block of the library's own (never returned to the system): handed
-        // over as it is, the runtime registers the caller's pages with the GPU for the transfer and keeps the registration
-        // cached -- pages that go back to the kernel when the vector dies (host_heap_policy, runtime.hip).
-        const bool pinned = std::is_same<typename V::allocator_type, PinnedAlloc<typename V::value_type>>::value;
-        if (!pinned && bytes >= (256u << 10)) {
-            void *stage = pinned_alloc(bytes);
-            std::memcpy(stage, v.data(), bytes);
-            const hipError_t e = hipMemcpyAsync(p, stage, bytes, hipMemcpyHostToDevice, s);
-            const hipError_t e2 = hipStreamSynchronize(s);
-            pinned_free(stage, bytes);
-            SA_HIP_CHECK(e);
-            SA_HIP_CHECK(e2);
-            return;
-        }
-        SA_HIP_CHECK(hipMemcpyAsync(p, v.data(), bytes, hipMemcpyHostToDevice, s));
-        SA_HIP_CHECK(hipStreamSynchronize(s));  // v may be a temporary
-    }
-    hvec<T> to_host(hipStream_t s = 0) const {
-        hvec<T> v(n);
-        if (n) {
-            SA_HIP_CHECK(hipMemcpyAsync(v.data(), p, n * sizeof(T), hipMemcpyDeviceToHost, s));
-            SA_HIP_CHECK(hipStreamSynchronize(s));
-        }
-        return v;
-    }
+    void from_host(const V &v, hipStream_t s = 0) { upload(*this, v, s); }
+    hvec<T> to_host(hipStream_t s = 0) const { return fetch_host((const T *)p, n, s); }
     // non-owning view of an existing device pointer
     void view(T *ptr, size_t n_) {
         release();
         p = ptr; n = n_; owned = false;
     }
 };
-
-// Bring an input array (host or device pointer) to the device: device pointers are
-// viewed in place (zero copy), host pointers are uploaded once.
-template <class T>
-inline void import_array(DBuf<T> &dst, const T *src, size_t n, hipStream_t s) {
-    if (is_device_ptr(src))
-        dst.view(const_cast<T *>(src), n);
-    else
-        dst.assign(src, n, s);
-}
-
-// Fetch an input array to the host (for host-side topology).
-template <class T>
-inline hvec<T> fetch_host(const T *src, size_t n, hipStream_t s) {
-    hvec<T> v(n);
-    if (n) {
-        SA_HIP_CHECK(hipMemcpyAsync(v.data(), src, n * sizeof(T), hipMemcpyDefault, s));
-        SA_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    return v;
-}
-// The first n values of a device buffer into a host vector (resized).  Only enqueues the copy: callers batch several under
-// one synchronise of their own.
-template <class T>
-inline void download(hvec<T> &dst, const DBuf<T> &src, size_t n, hipStream_t s) {
-    dst.resize(n);
-    if (n) SA_HIP_CHECK(hipMemcpyAsync(dst.data(), src.p, n * sizeof(T), hipMemcpyDeviceToHost, s));
-}
-// n values from the device in one transfer (synchronises the stream)
-template <class T>
-inline void read_back(T *dst, const T *src, size_t n, hipStream_t s) {
-    SA_HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
-}
-// one value from the device (synchronises the stream)
-template <class T>
-inline T read_one(const T *p, hipStream_t s) {
-    T v;
-    read_back(&v, p, 1, s);
-    return v;
-}
 
 // Row offsets of every CSR / SELL operator are 64-bit: column indices and dimensions are int32 like the
 // reference's hypre/MFEM types, but the stored entries of one operator may exceed 2^31 (Q2 elasticity at

@@ -52,7 +52,7 @@ DdSource eig_dedupe_source(const EigBatch &b);
 bool eig_dedupe_find(hipStream_t s, const DdSource &src, int count, int max_n, DdClasses &out, int debug);      // false: fewer than a quarter duplicates
 int eig_dedupe_group(const unsigned long long *hh, int count, std::vector<int> &rep);      // rep[i] = first matrix with i's hash; returns the classes
 std::vector<unsigned long long> eig_dedupe_hash_list(hipStream_t s, const DdSource &src, int max_n, const std::vector<int> &list);
-std::vector<long> eig_dedupe_words(hipStream_t s, const DdSource &src, const std::vector<int> &h_n, const std::vector<int> &list);
+std::vector<long> eig_dedupe_words(hipStream_t s, const DdSource &src, const hvec<int> &h_n, const std::vector<int> &list);
 void eig_dedupe_pack(hipStream_t s, const DdSource &src, int max_n, const std::vector<int> &list, const std::vector<long> &words,
                      std::vector<DBuf<unsigned long long>> &blobs);
 void eig_dedupe_compare(hipStream_t s, const DdSource &src, int max_n, const std::vector<int> &list,
@@ -75,7 +75,7 @@ struct LevelClasses {
     };
     // The classes of one chunk (cl, found on src) against those of earlier chunks; new ones are registered with their words.
     // Returns the batch-local indices to solve (first members of the new classes), their ids, and per matrix its class id.
-    std::vector<int> admit(hipStream_t s, const DdSource &src, const std::vector<int> &h_n, int max_n, const DdClasses &cl,
+    std::vector<int> admit(hipStream_t s, const DdSource &src, const hvec<int> &h_n, int max_n, const DdClasses &cl,
                            std::vector<int> &solve_ids, std::vector<int> &class_of);
     void set_result(int id, int m, bool bad, const double *evals, const double *evecs) { Entry &e = entries[id]; e.m = m; e.bad = bad; e.evals = evals; e.evecs = evecs; }
     void mark_bad(int id) { entries[id].bad = true; }

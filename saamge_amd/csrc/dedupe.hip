@@ -270,7 +270,7 @@ void eig_dedupe_compare(hipStream_t s, const DdSource &src, int max_n, const std
     for (size_t q = 0; q < list.size(); ++q) same[q] = hd[q] ? 0 : 1;
 }
 // word counts of some matrices (host): the half bandwidths come from the device
-std::vector<long> eig_dedupe_words(hipStream_t s, const DdSource &src, const std::vector<int> &h_n, const std::vector<int> &list) {
+std::vector<long> eig_dedupe_words(hipStream_t s, const DdSource &src, const hvec<int> &h_n, const std::vector<int> &list) {
     std::vector<long> w(list.size());
     hvec<int> hb;
     if (src.kind == 1) { DBuf<int> tmp; tmp.view(const_cast<int *>(src.bws), h_n.size()); hb = tmp.to_host(s); }
@@ -286,7 +286,7 @@ DdSource eig_dedupe_source(const EigBatch &b) {
     return v;
 }
 
-std::vector<int> LevelClasses::admit(hipStream_t s, const DdSource &src, const std::vector<int> &h_n, int max_n, const DdClasses &cl,
+std::vector<int> LevelClasses::admit(hipStream_t s, const DdSource &src, const hvec<int> &h_n, int max_n, const DdClasses &cl,
                                      std::vector<int> &solve_ids, std::vector<int> &class_of) {
     const int nl = (int)cl.reps.size();
     std::vector<int> l2g((size_t)nl, -1);

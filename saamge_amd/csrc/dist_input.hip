@@ -79,15 +79,9 @@ Hierarchy *hierarchy_create_dist(const ParCsrIn &A, int NE_loc, int nde, const i
     const int K = 3 + MAX_LEVELS;
     std::vector<long long> cnt((size_t)world * K, 0), coff((size_t)world + 1);
     {
-        DBuf<int> di_v, oi_v;
-        import_array(di_v, A.diag_i, (size_t)A.nrows + 1, s);
-        int dn = 0, on = 0;
-        SA_HIP_CHECK(hipMemcpyAsync(&dn, di_v.p + A.nrows, sizeof(int), hipMemcpyDeviceToHost, s));
-        if (A.offd_i) {
-            import_array(oi_v, A.offd_i, (size_t)A.nrows + 1, s);
-            SA_HIP_CHECK(hipMemcpyAsync(&on, oi_v.p + A.nrows, sizeof(int), hipMemcpyDeviceToHost, s));
-        }
-        SA_HIP_CHECK(hipStreamSynchronize(s));
+        // the last row offsets, of host or device arrays
+        const int dn = fetch_host(A.diag_i + A.nrows, 1, s)[0];
+        const int on = A.offd_i ? fetch_host(A.offd_i + A.nrows, 1, s)[0] : 0;
         long long *mine = cnt.data() + (size_t)rank * K;
         mine[0] = A.nrows;
         mine[1] = (long long)dn + on;
@@ -120,20 +114,20 @@ Hierarchy *hierarchy_create_dist(const ParCsrIn &A, int NE_loc, int nde, const i
     std::vector<long long> boff((size_t)world + 1);
     // ---- the operator: row lengths -> global row offsets -> merged, sorted rows of the own block -> all-gather ----
     {
-        DBuf<int> di, dj, oi, oj;
-        DBuf<double> da, oa;
-        DBuf<long long> cmap;
         const long long dn = cnt[(size_t)rank * K + 1];
-        import_array(di, A.diag_i, (size_t)A.nrows + 1, s);
-        int dnnz = read_one(di.p + A.nrows, s);
-        import_array(dj, A.diag_j, (size_t)dnnz, s);
-        import_array(da, A.diag_a, (size_t)dnnz, s);
+        const DevIn<int> di(A.diag_i, (size_t)A.nrows + 1, s);
+        const int dnnz = read_one(di.p + A.nrows, s);
+        const DevIn<int> dj(A.diag_j, (size_t)dnnz, s);
+        const DevIn<double> da(A.diag_a, (size_t)dnnz, s);
         const long long onnz = dn - dnnz;
+        DevIn<int> oi, oj;
+        DevIn<double> oa;
+        DevIn<long long> cmap;
         if (A.offd_i) {
-            import_array(oi, A.offd_i, (size_t)A.nrows + 1, s);
-            import_array(oj, A.offd_j, (size_t)onnz, s);
-            import_array(oa, A.offd_a, (size_t)onnz, s);
-            import_array(cmap, A.col_map_offd, (size_t)A.num_cols_offd, s);
+            oi.bind(A.offd_i, (size_t)A.nrows + 1, s);
+            oj.bind(A.offd_j, (size_t)onnz, s);
+            oa.bind(A.offd_a, (size_t)onnz, s);
+            cmap.bind(A.col_map_offd, (size_t)A.num_cols_offd, s);
         }
         DBuf<int> len((size_t)n + 1);
         len.zero(s);
@@ -166,17 +160,14 @@ Hierarchy *hierarchy_create_dist(const ParCsrIn &A, int NE_loc, int nde, const i
     // ---- integer topology: elem_to_dof (global dof ids), boundary flags of the own rows, partitions ----
     {
         din->e2d.alloc((size_t)NE * nde);
-        if (NE_loc)
-            SA_HIP_CHECK(hipMemcpyAsync(din->e2d.p + (size_t)el_off[rank] * nde, elem_to_dof, sizeof(int) * (size_t)NE_loc * nde,
-                                        hipMemcpyDefault, s));
+        upload(din->e2d.p + (size_t)el_off[rank] * nde, elem_to_dof, (size_t)NE_loc * nde, s);
         if (world > 1) {
             for (int r = 0; r <= world; ++r) boff[r] = 4ll * nde * el_off[r];
             gather(p, s, din->e2d.p, boff);
         }
         din->bdr.alloc((size_t)n);
         din->bdr.zero(s);
-        if (bdr_own && A.nrows)
-            SA_HIP_CHECK(hipMemcpyAsync(din->bdr.p + row0, bdr_own, (size_t)A.nrows, hipMemcpyDefault, s));
+        if (bdr_own) upload(din->bdr.p + row0, bdr_own, (size_t)A.nrows, s);
         if (world > 1) {
             for (int r = 0; r <= world; ++r) boff[r] = row_off[r];
             gather(p, s, din->bdr.p, boff);
@@ -190,8 +181,7 @@ Hierarchy *hierarchy_create_dist(const ParCsrIn &A, int NE_loc, int nde, const i
             SA_REQUIRE(ae_off[l][world] > 0 && ae_off[l][world] < (1ll << 31), "per-rank inputs: no agglomerates on a level");
             din->parts[l].alloc((size_t)all);
             if (mine) {
-                DBuf<int> loc;
-                import_array(loc, partitions[l], (size_t)mine, s);
+                const DevIn<int> loc(partitions[l], (size_t)mine, s);
                 hipLaunchKernelGGL(add_offset_kernel, dim3(div_up(mine, 256)), dim3(256), 0, s, (long)mine, (int)ae_off[l][rank],
                                    loc.p, din->parts[l].p + src_off[rank]);
                 SA_HIP_CHECK(hipGetLastError());

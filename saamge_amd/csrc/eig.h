@@ -38,7 +38,7 @@ struct EigBatch {
     DBuf<int64_t> roff;     // [count+1] reflector offsets
     DBuf<double> Gbuf;      // per (matrix, 64-row block) partial V^T X (SB x SB each)
     DBuf<int64_t> goff;
-    std::vector<int64_t> h_roff, h_goff;
+    hvec<int64_t> h_roff, h_goff;
     // few-eigenpairs path: Ritz values of the accepted block; `dense_only`
     // forces the dense path for this batch (fallback after a failed subspace attempt)
     DBuf<double> ss_mu;
@@ -56,7 +56,7 @@ struct EigBatch {
     bool order_ran = false;       // ae_build gave the batch a permutation (ae_perm_kernel ran)
     bool has_bw = false;    // bw was filled by the assembly (from the sparse rows): no scan of the dense matrices
     DBuf<int> bw;           // [count] half bandwidths (banded Cholesky), host copy; empty = full matrices
-    std::vector<int> h_bw;
+    hvec<int> h_bw;
     int ss_bwmax = 0;
     // certified count: the upper end of the window must be known when the matrices are factored
     // (set_window before eig_tridiagonalize); h_inertia[i] = #{eigenvalues of C_i < vu} from the
@@ -98,8 +98,9 @@ struct EigBatch {
     size_t ss_sub_n = 0;
     DBuf<int64_t> ss_soff;
     std::vector<double> h_sigma;
-    std::vector<int> h_n, h_m;
-    std::vector<int64_t> h_moff, h_voff;
+    hvec<int> h_n;
+    std::vector<int> h_m;
+    hvec<int64_t> h_moff, h_voff;
 };
 
 // sizes known on the host; allocates everything but leaves W/dis to be filled by the caller

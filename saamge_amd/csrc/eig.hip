@@ -771,7 +771,7 @@ void eig_batch_alloc(EigBatch &b, const std::vector<int> &sizes, const Options &
     b.opt = opt;
     b.slot = g_slot = slot & 1;
     b.count = (int)sizes.size();
-    b.h_n = sizes;
+    b.h_n.assign(sizes.begin(), sizes.end());
     b.has_perm = false;
     b.has_bw = false;
     b.h_moff.assign(b.count + 1, 0);
@@ -789,9 +789,9 @@ void eig_batch_alloc(EigBatch &b, const std::vector<int> &sizes, const Options &
     arena_view(b.n, a.n, (size_t)b.count);
     arena_view(b.moff, a.moff, (size_t)b.count + 1);
     arena_view(b.voff, a.voff, (size_t)b.count + 1);
-    SA_HIP_CHECK(hipMemcpyAsync(b.n.p, b.h_n.data(), 4 * (size_t)b.count, hipMemcpyHostToDevice, s));
-    SA_HIP_CHECK(hipMemcpyAsync(b.moff.p, b.h_moff.data(), 8 * ((size_t)b.count + 1), hipMemcpyHostToDevice, s));
-    SA_HIP_CHECK(hipMemcpyAsync(b.voff.p, b.h_voff.data(), 8 * ((size_t)b.count + 1), hipMemcpyHostToDevice, s));
+    upload_async(b.n.p, b.h_n, (size_t)b.count, s);
+    upload_async(b.moff.p, b.h_moff, (size_t)b.count + 1, s);
+    upload_async(b.voff.p, b.h_voff, (size_t)b.count + 1, s);
     SA_HIP_CHECK(hipStreamSynchronize(s));
     arena_view(b.W, a.W, (size_t)b.h_moff[b.count]);
     arena_view(b.d, a.d, rows);
@@ -816,8 +816,8 @@ void eig_batch_two_stage_buffers(EigBatch &b, size_t nrefl, bool need_bandg, hip
     arena_view(b.roff, a.roff, (size_t)b.count + 1);
     arena_view(b.goff, a.goff, (size_t)b.count + 1);
     arena_view(b.Gbuf, a.Gbuf, (size_t)b.h_goff[b.count] + 1);
-    SA_HIP_CHECK(hipMemcpyAsync(b.goff.p, b.h_goff.data(), 8 * ((size_t)b.count + 1), hipMemcpyHostToDevice, s));
-    SA_HIP_CHECK(hipMemcpyAsync(b.roff.p, b.h_roff.data(), 8 * ((size_t)b.count + 1), hipMemcpyHostToDevice, s));
+    upload_async(b.goff.p, b.h_goff, (size_t)b.count + 1, s);
+    upload_async(b.roff.p, b.h_roff, (size_t)b.count + 1, s);
     SA_HIP_CHECK(hipStreamSynchronize(s));
     arena_view(b.rv, a.rv, nrefl * EIG_SB + EIG_SB);
     arena_view(b.rtau, a.rtau, nrefl + 1);

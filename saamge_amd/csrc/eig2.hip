@@ -3099,8 +3099,7 @@ static void ss_measure_bands(SsFactor &f) {
         hipLaunchKernelGGL(ss_band_kernel, dim3(b.count, ny), dim3(256), 0, s, b.n.p, b.moff.p, b.W.p, b.bw.p);
         profiler().end(s, "eig_ss_band", 0.0, 0.0);
     }
-    b.h_bw.resize((size_t)b.count);
-    SA_HIP_CHECK(hipMemcpyAsync(b.h_bw.data(), b.bw.p, sizeof(int) * (size_t)b.count, hipMemcpyDeviceToHost, s));
+    download(b.h_bw, b.bw, (size_t)b.count, s);
     SA_HIP_CHECK(hipStreamSynchronize(s));
     for (int v : b.h_bw) f.bwmax = std::max(f.bwmax, v);
     b.ss_bwmax = f.bwmax;
@@ -3361,7 +3360,7 @@ struct SsIter {
     // would exit at once, but the survivors (agglomerates on the domain boundary: every 64th id, runs of 64)
     // would then sit on a few CUs -- block ids map to XCDs and CUs round-robin -- and a launch with 6 % of
     // the matrices active took as long as a full one.
-    std::vector<int> h_active;
+    hvec<int> h_active;
     DBuf<int> active;
     int nact = 0;
     // matrices with seven to twelve wanted pairs: the first six are locked when they have converged (ss_lock_kernel)
@@ -3380,7 +3379,7 @@ struct SsIter {
     void read_state() { auto t = state.to_host(s); hstate.assign(t.begin(), t.end()); }
     void send_active() {
         nact = (int)h_active.size();
-        if (nact) SA_HIP_CHECK(hipMemcpyAsync(active.p, h_active.data(), sizeof(int) * (size_t)nact, hipMemcpyHostToDevice, s));
+        upload_async(active.p, h_active, (size_t)nact, s);      // (the list next changes after read_state has synchronised)
     }
 };
 
@@ -3589,7 +3588,7 @@ static void ss_iter_reshift(SsIter &it, int iter) {
         if (hi2[i] && !(it.hstate[i] & 1) && !b.h_bad[i]) {     // the new shift was not below the spectrum after all
             mark_bad(b, i);
             it.hstate[i] |= 2;
-            SA_HIP_CHECK(hipMemcpyAsync(it.state.p + i, &gave_up, sizeof(int), hipMemcpyHostToDevice, s));
+            upload_async(it.state.p + i, &gave_up, 1, s);
         }
     DBuf<int> d_req;
     DBuf<double> d_delta;

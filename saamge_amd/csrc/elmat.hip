@@ -1755,24 +1755,6 @@ int64_t qp_offsets(hipStream_t s, const MeshArgs &m, const EmMesh &M, DBuf<roff_
 }
 
 // ---- the frame of a call ----------------------------------------------------------------------------------------------------------
-// an output of `n` doubles that may be a host pointer: the kernels write to dev(), finish() copies it home.  load: the kernels
-// add to what it holds, so a host array is brought along.
-struct EmOut {
-    double *user = nullptr;
-    DBuf<double> hold;
-    size_t n = 0;
-    double *dev(hipStream_t s, double *p, size_t count, bool load = false) {
-        user = p;
-        n = count;
-        if (!p || is_device_ptr(p)) return p;
-        if (load) upload(hold, (const double *)p, count, s);
-        else hold.alloc(count);
-        return hold.p;
-    }
-    void finish(hipStream_t s) {
-        if (hold.p && n) SA_HIP_CHECK(hipMemcpyAsync(user, hold.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
-    }
-};
 // What every driver does around its launches, in the order the stream sees it: open (the mesh, checked), points (the offsets of
 // the points, where the call has any), inputs (the launch arguments: device views of the coordinates and the coefficients),
 // target / out[] (outputs, host or device), run (the bad word reset, the types looped, the first bad element refused), then
@@ -1785,8 +1767,8 @@ struct EmFrame {
     EmMesh M;
     EmLaunch L{};
     DBuf<roff_t> qoff;
-    DBuf<double> hold_X, hold_c;
-    EmOut out[2];      // [0]: what L.out writes, or the first output of a call on data at the points
+    DevIn<double> in_X, in_c;
+    DevOut<double> out[2];      // [0]: what L.out writes, or the first output of a call on data at the points
 
     EmFrame(hipStream_t s_, const std::string &name_, const MeshArgs &m_, long long *info_) : s(s_), name(name_), m(m_), info(info_) {}
     // comp: dofs per node; square: the results are packed matrices; mesh_info: info[0 .. 5] and info[7] as em_mesh fills them
@@ -1799,12 +1781,12 @@ struct EmFrame {
     }
     // coef: n doubles in rows of ncoef, nullptr: none
     void inputs(const double *coef = nullptr, size_t n = 0, int ncoef = 1) {
-        L = EmLaunch{s, m.elem_ptr ? M.eI : nullptr, M.eJ, M.moff.p, device_view(hold_X, m.coords, (size_t)m.NV * m.dim, s), nullptr,
+        L = EmLaunch{s, m.elem_ptr ? M.eI : nullptr, M.eJ, M.moff.p, in_X.bind(m.coords, (size_t)m.NV * m.dim, s), nullptr,
                      ncoef, nullptr, M.word.p, coef_rows ? qoff.p : nullptr};
         coefficients(coef, n);
     }
-    void coefficients(const double *coef, size_t n) { L.coef = coef ? device_view(hold_c, coef, n, s) : nullptr; }
-    void target(double *p, size_t n, bool load = false) { L.out = out[0].dev(s, p, n, load); }
+    void coefficients(const double *coef, size_t n) { L.coef = in_c.bind(coef, n, s); }
+    void target(double *p, size_t n, bool load = false) { L.out = out[0].bind(p, n, s, load); }
     void reset_bad() { SA_HIP_CHECK(hipMemsetAsync(M.word.p, 0x7f, sizeof(int), s)); }
     // f(type, count, list) for the elements of every type the mesh has
     template <class F>
@@ -1827,8 +1809,8 @@ struct EmFrame {
         refuse_bad(m.NE, "element ", ": the Jacobian determinant is not positive");
     }
     void copy_home() {
-        out[0].finish(s);
-        out[1].finish(s);
+        out[0].finish();
+        out[1].finish();
     }
     void sync() { SA_HIP_CHECK(hipStreamSynchronize(s)); }
 
@@ -1871,12 +1853,12 @@ void stiffness(hipStream_t s, const std::string &name, bool at_points, const Mes
     if (dof_ptr_out) {
         dptr.alloc((size_t)NE + 1);
         em_run(em_dof_ptr_kernel, s, div_up((int64_t)NE + 1, 256), 256, NE, comp, F.M.eI, dptr.p);
-        SA_HIP_CHECK(hipMemcpyAsync(dof_ptr_out, dptr.p, ((size_t)NE + 1) * sizeof(int), hipMemcpyDefault, s));
+        copy_to_caller(dof_ptr_out, dptr, s);
     }
     if (elem_to_dof_out) {
         dofs.alloc((size_t)nconn * comp);
         em_run(em_dofs_kernel, s, std::max(1, div_up(nconn, 256)), 256, nconn, comp, F.M.eJ, dofs.p);
-        SA_HIP_CHECK(hipMemcpyAsync(elem_to_dof_out, dofs.p, (size_t)nconn * comp * sizeof(int), hipMemcpyDefault, s));
+        copy_to_caller(elem_to_dof_out, dofs, s);
     }
     F.sync();
 }
@@ -1890,8 +1872,8 @@ void mass_or_loads(hipStream_t s, const std::string &name, const MeshArgs &m, in
     F.open(vdim, !src);
     F.inputs(coef, at_points ? (size_t)F.points(true) : (size_t)m.NE);
     F.target(out, (size_t)F.M.doubles, accumulate);
-    DBuf<double> hold_src;
-    const double *dsrc = src ? device_view(hold_src, src, (size_t)m.NV * vdim, s) : nullptr;
+    const DevIn<double> in_src(src, (size_t)m.NV * vdim, s);
+    const double *dsrc = in_src.p;
     F.run([&](int t, int count, const int *list) { mass_launch_type(F.L, t, vdim, accumulate, dsrc, count, list); });
     F.copy_home();
     F.sync();
@@ -1924,7 +1906,7 @@ void points_call(QpCall call, hipStream_t s, const std::string &name, const Mesh
     SA_REQUIRE(call == QP_POINTS || in, name + "null argument: " + in_name);
     if (NE == 0) {
         const long long zero = 0;
-        if (qp_ptr_out) SA_HIP_CHECK(hipMemcpyAsync(qp_ptr_out, &zero, sizeof(zero), hipMemcpyDefault, s));
+        copy_to_caller(qp_ptr_out, &zero, 1, s);
         F.sync();
         return;
     }
@@ -1934,27 +1916,25 @@ void points_call(QpCall call, hipStream_t s, const std::string &name, const Mesh
     F.inputs();
     F.run([&](int t, int count, const int *list) { mass_launch_type(F.L, t, 1, 0, nullptr, count, list); });
     // ---- the call
-    DBuf<double> hold_in, hold_e, hold_g;
-    const double *din = in ? device_view(hold_in, in, call == QP_LOADS ? nq * vdim : (size_t)m.NV * vdim, s) : nullptr;
-    const double *dexq = exq ? device_view(hold_e, exq, nq * vdim, s) : nullptr;
-    const double *dexgradq = exgradq ? device_view(hold_g, exgradq, nq * vdim * dim, s) : nullptr;
+    const DevIn<double> in_in(in, call == QP_LOADS ? nq * vdim : (size_t)m.NV * vdim, s), in_e(exq, nq * vdim, s),
+        in_g(exgradq, nq * vdim * dim, s);
     double *a = nullptr, *b = nullptr;
     if (call == QP_POINTS) {
-        a = F.out[0].dev(s, out_a, nq * dim);
-        b = F.out[1].dev(s, out_b, nq);
+        a = F.out[0].bind(out_a, nq * dim, s, false);
+        b = F.out[1].bind(out_b, nq, s, false);
     } else if (call == QP_EVAL) {
-        a = F.out[0].dev(s, out_a, nq * vdim);
-        b = F.out[1].dev(s, out_b, nq * vdim * dim);
+        a = F.out[0].bind(out_a, nq * vdim, s, false);
+        b = F.out[1].bind(out_b, nq * vdim * dim, s, false);
     } else if (call == QP_LOADS) {
         F.coefficients(coef, (size_t)NE);
         F.target(out_a, (size_t)F.M.doubles);
     } else {
-        a = F.out[0].dev(s, out_a, (size_t)NE * 2);
+        a = F.out[0].bind(out_a, (size_t)NE * 2, s, false);
     }
-    const QpLaunch Q{F.qoff.p, din, dexq, dexgradq, a, b};
+    const QpLaunch Q{F.qoff.p, in_in.p, in_e.p, in_g.p, a, b};
     if (a || b || F.L.out) F.for_types([&](int t, int count, const int *list) { qp_launch_type(call, F.L, Q, t, vdim, count, list); });
     F.copy_home();
-    if (qp_ptr_out) SA_HIP_CHECK(hipMemcpyAsync(qp_ptr_out, F.qoff.p, ((size_t)NE + 1) * sizeof(roff_t), hipMemcpyDefault, s));
+    copy_to_caller((roff_t *)qp_ptr_out, (const roff_t *)F.qoff.p, (size_t)NE + 1, s);
     F.sync();
 }
 
@@ -1996,8 +1976,7 @@ void boundary_forms(BdrCall call, bool at_points, hipStream_t s, const std::stri
     if (NF == 0) {
         if (fp_out) {      // (the one offset of an empty list; without it an empty list touches no device)
             const long long zero = 0;
-            SA_HIP_CHECK(hipMemcpyAsync(fp_out, &zero, sizeof(zero), hipMemcpyDefault, s));
-            SA_HIP_CHECK(hipStreamSynchronize(s));
+            copy_to_caller(fp_out, &zero, 1, s);
         }
         return;
     }
@@ -2030,14 +2009,13 @@ void boundary_forms(BdrCall call, bool at_points, hipStream_t s, const std::stri
     }
     // ---- the passes: ascending local face, so that the faces of one element are added in that order
     F.inputs(coef, call == BDR_MASS && at_points ? nfq : (size_t)NF);
-    DBuf<double> hold_in;
+    const DevIn<double> in_in(in, call == BDR_LOADS && at_points ? nfq * vdim : (size_t)m.NV * vdim, s);
     DBuf<int> bad_det;
     if (call == BDR_EVAL) {
         bad_det.alloc(1);
         SA_HIP_CHECK(hipMemsetAsync(bad_det.p, 0x7f, sizeof(int), s));
     }
-    BdrLaunch B{FL.fe, nullptr, fp.p, nullptr, nullptr, nullptr, bad_det.p};
-    if (in) B.in = device_view(hold_in, in, call == BDR_LOADS && at_points ? nfq * vdim : (size_t)m.NV * vdim, s);
+    BdrLaunch B{FL.fe, in_in.p, fp.p, nullptr, nullptr, nullptr, bad_det.p};
     auto passes = [&] {
         for (int lf = 0; lf < BDR_MAX_FACES; ++lf)
             for (int t = 0; t < EM_TYPES; ++t)
@@ -2048,7 +2026,7 @@ void boundary_forms(BdrCall call, bool at_points, hipStream_t s, const std::stri
         if (call == BDR_EVAL) F.refuse_bad(NF, "face ", ": the Jacobian determinant of the element is not positive", bad_det.p);
     };
     F.reset_bad();
-    EmOut third;
+    DevOut<double> third;
     bool write = true;
     if (at_points) {      // nothing is written before every face has passed
         passes();
@@ -2058,15 +2036,15 @@ void boundary_forms(BdrCall call, bool at_points, hipStream_t s, const std::stri
     if (call == BDR_MASS || call == BDR_LOADS) {
         F.target(out_a, (size_t)F.M.doubles, true);
     } else {
-        B.a = F.out[0].dev(s, out_a, nfq * (call == BDR_POINTS ? dim : vdim));
-        B.b = F.out[1].dev(s, out_b, call == BDR_POINTS ? nfq : nfq * vdim * dim);
-        B.c = third.dev(s, out_c, nfq * dim);
+        B.a = F.out[0].bind(out_a, nfq * (call == BDR_POINTS ? dim : vdim), s, false);
+        B.b = F.out[1].bind(out_b, call == BDR_POINTS ? nfq : nfq * vdim * dim, s, false);
+        B.c = third.bind(out_c, nfq * dim, s, false);
     }
     if (write) passes();
     if (!at_points) refuse();
     F.copy_home();
-    third.finish(s);
-    if (fp_out) SA_HIP_CHECK(hipMemcpyAsync(fp_out, fp.p, ((size_t)NF + 1) * sizeof(roff_t), hipMemcpyDefault, s));
+    third.finish();
+    copy_to_caller((roff_t *)fp_out, (const roff_t *)fp.p, (size_t)NF + 1, s);
     F.sync();
 }
 // the checks of both entry points that need no device

@@ -366,12 +366,9 @@ static void level_topology(LevelBuild &B, Table &&e2d, const hvec<int> &part, co
     if (B.aggregates) {
         join_galerkin(H);     // the arbitration reads this level's operator
         aggA.nrows = L.A.nrows;
-        aggA.rowptr.resize((size_t)L.A.nrows + 1);
-        aggA.col.resize((size_t)L.A.nnz);
-        aggA.val.resize((size_t)L.A.nnz);
-        SA_HIP_CHECK(hipMemcpyAsync(aggA.rowptr.data(), L.A.rowptr.p, sizeof(roff_t) * ((size_t)L.A.nrows + 1), hipMemcpyDeviceToHost, s));
-        SA_HIP_CHECK(hipMemcpyAsync(aggA.col.data(), L.A.col.p, sizeof(int) * (size_t)L.A.nnz, hipMemcpyDeviceToHost, s));
-        SA_HIP_CHECK(hipMemcpyAsync(aggA.val.data(), L.A.val.p, sizeof(double) * (size_t)L.A.nnz, hipMemcpyDeviceToHost, s));
+        download(aggA.rowptr, L.A.rowptr, (size_t)L.A.nrows + 1, s);
+        download(aggA.col, L.A.col, (size_t)L.A.nnz, s);
+        download(aggA.val, L.A.val, (size_t)L.A.nnz, s);
         SA_HIP_CHECK(hipStreamSynchronize(s));
     }
     // (the tables go to the device from the same thread, on a side stream, while the eigensolver runs)
@@ -530,7 +527,7 @@ static void eig_redo_bad(LevelBuild &B, int slot, Chunk &c, std::vector<int> m_a
     packed_offsets(cnt, m_all.data(), sizes, eoff, xoff);
     DBuf<double> evals((size_t)eoff[cnt]), evecs((size_t)xoff[cnt]);
     auto copy = [&](double *dst, const double *src, int64_t n_) {
-        if (n_ > 0) SA_HIP_CHECK(hipMemcpyAsync(dst, src, 8 * (size_t)n_, hipMemcpyDeviceToDevice, s));
+        if (n_ > 0) copy_device(dst, src, (size_t)n_, s);
     };
     size_t ri = 0;
     for (int i = 0; i < cnt;) {
@@ -738,15 +735,15 @@ static void level_concatenate(LevelBuild &B) {
     L.evals.alloc((size_t)L.ae_eoff[nparts]);
     L.evecs.alloc((size_t)L.ae_xoff[nparts]);
     for (Chunk &c : B.chunks) {
-        if (c.evals.n) SA_HIP_CHECK(hipMemcpyAsync(L.evals.p + L.ae_eoff[c.ae0], c.evals.p, 8 * c.evals.n, hipMemcpyDeviceToDevice, s));
+        copy_device(L.evals.p + L.ae_eoff[c.ae0], (const double *)c.evals.p, c.evals.n, s);
         if (extra && c.ae0 == 0) {
             const int64_t first = (int64_t)L.ae_m[0] * sizes[0];
-            SA_HIP_CHECK(hipMemcpyAsync(L.evecs.p, c.evecs.p, 8 * first, hipMemcpyDeviceToDevice, s));
+            copy_device(L.evecs.p, (const double *)c.evecs.p, (size_t)first, s);
             dev_fill(s, (long)sizes[0], 1.0, L.evecs.p + first);
             if (c.evecs.n > (size_t)first)
-                SA_HIP_CHECK(hipMemcpyAsync(L.evecs.p + L.ae_xoff[1], c.evecs.p + first, 8 * (c.evecs.n - first), hipMemcpyDeviceToDevice, s));
-        } else if (c.evecs.n) {
-            SA_HIP_CHECK(hipMemcpyAsync(L.evecs.p + L.ae_xoff[c.ae0], c.evecs.p, 8 * c.evecs.n, hipMemcpyDeviceToDevice, s));
+                copy_device(L.evecs.p + L.ae_xoff[1], (const double *)c.evecs.p + first, c.evecs.n - (size_t)first, s);
+        } else {
+            copy_device(L.evecs.p + L.ae_xoff[c.ae0], (const double *)c.evecs.p, c.evecs.n, s);
         }
     }
     SA_HIP_CHECK(hipStreamSynchronize(s));
@@ -775,7 +772,7 @@ static void level_mis_svd(LevelBuild &B) {
     L.mis_s_off.assign((size_t)nm + 1, 0);
     int max_ctot = 0;
     const int nextra = (lev == 0 && P.extra_modes) ? P.num_extra_modes : 0;
-    if (nextra) import_array(L.extra, P.extra_modes, (size_t)nextra * L.A.nrows, s);
+    if (nextra) L.extra = DevIn<double>(P.extra_modes, (size_t)nextra * L.A.nrows, s).take();
     for (int m = 0; m < nm; ++m) {
         int ctot = nextra;
         for (int q = rel.mis_to_AE.I[m]; q < rel.mis_to_AE.I[m + 1]; ++q) ctot += L.ae_m[rel.mis_to_AE.J[q]];
@@ -945,10 +942,10 @@ static void prepare_next_host(const Level &L, const roff_t *p_rowptr_dev, const 
     Table &e2d = out.e2d;
     e2d.ncols = L.mis_coloff.back();
     e2d.I.assign((size_t)nparts + 1, 0);
-    hvec<roff_t> p_rowptr((size_t)p_nrows + 1);
-    hvec<double> p_val((size_t)p_nnz + 1);
-    SA_HIP_CHECK(hipMemcpyAsync(p_rowptr.data(), p_rowptr_dev, sizeof(roff_t) * ((size_t)p_nrows + 1), hipMemcpyDeviceToHost, s));
-    if (p_nnz) SA_HIP_CHECK(hipMemcpyAsync(p_val.data(), p_val_dev, sizeof(double) * (size_t)p_nnz, hipMemcpyDeviceToHost, s));
+    hvec<roff_t> p_rowptr;
+    hvec<double> p_val;
+    download(p_rowptr, p_rowptr_dev, (size_t)p_nrows + 1, s);
+    download(p_val, p_val_dev, (size_t)p_nnz, s);
     SA_HIP_CHECK(hipStreamSynchronize(s));
     // colpos: for every (AE, MIS) incidence (aligned with AE_to_mis.J) the position of each of
     // the MIS's coarse dofs in the coarse element's dof list
@@ -1252,7 +1249,7 @@ static int pcg_loop(Hierarchy &H, const DCsr &A, const std::function<void(const 
         pcg_update_d(s, n, sc, d + off, z + off);
         halo_then(H, D, d, [&](hipStream_t st, RowRange rq) { spmv(st, A, d, q, rq); });
         pdot(d, q, sc + 1);
-        SA_HIP_CHECK(hipMemcpyAsync(sc + 0, sc + 2, sizeof(double), hipMemcpyDeviceToDevice, s));
+        copy_device(sc + 0, (const double *)sc + 2, 1, s);
     }
     return final_iter;
 }
@@ -1262,12 +1259,9 @@ static void coarse_solve(Hierarchy &H, const double *rc, double *xc) {
     if (Ac.nrows == 0) return;
     if (H.user_coarse_solve) {      // tg_data_t::coarse_solver assigned by the caller (host solver)
         const size_t n = (size_t)Ac.nrows;
-        hvec<double> hr(n), hx(n, 0.0);
-        SA_HIP_CHECK(hipMemcpyAsync(hr.data(), rc, 8 * n, hipMemcpyDeviceToHost, H.stream));
-        SA_HIP_CHECK(hipStreamSynchronize(H.stream));
+        hvec<double> hr = fetch_host(rc, n, H.stream), hx(n, 0.0);
         SA_REQUIRE(H.user_coarse_solve(H.user_coarse_ctx, (int)n, hr.data(), hx.data()) == 0, "user coarse solver failed");
-        SA_HIP_CHECK(hipMemcpyAsync(xc, hx.data(), 8 * n, hipMemcpyHostToDevice, H.stream));
-        SA_HIP_CHECK(hipStreamSynchronize(H.stream));
+        upload(xc, (const double *)hx.data(), n, H.stream);
         H.last_coarse_iters = 0;
         return;
     }
@@ -1305,13 +1299,9 @@ static void user_smooth(Hierarchy &H, int level, int (*fn)(void *, int, int, con
     Level &L = *H.levels[level];
     SA_REQUIRE(!L.dist.on, "a caller's smoother cannot run on a level that is row-partitioned over several ranks");
     const size_t n = (size_t)L.A.nrows;
-    hvec<double> hb(n), hx(n, 0.0);
-    SA_HIP_CHECK(hipMemcpyAsync(hb.data(), b, 8 * n, hipMemcpyDeviceToHost, H.stream));
-    if (!zero_start) SA_HIP_CHECK(hipMemcpyAsync(hx.data(), x, 8 * n, hipMemcpyDeviceToHost, H.stream));
-    SA_HIP_CHECK(hipStreamSynchronize(H.stream));
+    hvec<double> hb = fetch_host(b, n, H.stream), hx = zero_start ? hvec<double>(n, 0.0) : fetch_host((const double *)x, n, H.stream);
     SA_REQUIRE(fn(ctx, level, (int)n, hb.data(), hx.data()) == 0, "the caller's smoother failed");
-    SA_HIP_CHECK(hipMemcpyAsync(x, hx.data(), 8 * n, hipMemcpyHostToDevice, H.stream));
-    SA_HIP_CHECK(hipStreamSynchronize(H.stream));
+    upload(x, (const double *)hx.data(), n, H.stream);
 }
 
 // One V(1,1)-cycle from x = 0 (tg_cycle_atb, amg/src/tg.cpp:91-132).  On a row-partitioned
@@ -1447,7 +1437,7 @@ static void add_nullspace_level(Hierarchy &H) {
                        N.P.col.p, N.P.val.p);
     SA_HIP_CHECK(hipGetLastError());
     const roff_t nc_off = nc;
-    SA_HIP_CHECK(hipMemcpyAsync(N.P.rowptr.p + nc, &nc_off, sizeof(roff_t), hipMemcpyHostToDevice, s));
+    upload_async(N.P.rowptr.p + nc, &nc_off, 1, s);
     SA_HIP_CHECK(hipStreamSynchronize(s));
     N.P.lanes_per_row = 1;
     csr_transpose(s, N.P, N.R);
@@ -1506,8 +1496,8 @@ Hierarchy *hierarchy_create(int n, const void *Arow, int rowptr_bits, const int 
         roff_t nnz = read_one(L0.A.rowptr.p + n, s);
         L0.A.nrows = L0.A.ncols = n;
         L0.A.nnz = nnz;
-        import_array(L0.A.col, Acol, (size_t)nnz, s);
-        import_array(L0.A.val, Aval, (size_t)nnz, s);
+        L0.A.col = DevIn<int>(Acol, (size_t)nnz, s).take();
+        L0.A.val = DevIn<double>(Aval, (size_t)nnz, s).take();
         finish_csr(L0.A);
     }
     {
@@ -1517,21 +1507,21 @@ Hierarchy *hierarchy_create(int n, const void *Arow, int rowptr_bits, const int 
             // the other elements stay 0 -- no kernel of this rank touches an agglomerate made of them
             L0.elmat.off.zero(s);
             dev_iota(s, (long)H.dist_in->NE_loc + 1, (int64_t)nde * nde, L0.elmat.off.p + H.dist_in->elem0);
-            import_array(L0.elmat.val, elmat, (size_t)H.dist_in->NE_loc * nde * nde, s);
+            L0.elmat.val = DevIn<double>(elmat, (size_t)H.dist_in->NE_loc * nde * nde, s).take();
             L0.elmat.first = H.dist_in->elem0;
         } else if (elem_ptr) {
             // mixed elements: element e's matrix at sum_{f<e} nd_f^2
-            import_array(H.e2d_ptr, elem_ptr, (size_t)NE + 1, s);
+            H.e2d_ptr = DevIn<int>(elem_ptr, (size_t)NE + 1, s).take();
             DBuf<int> sq((size_t)NE);
             hipLaunchKernelGGL(elem_sq_kernel, dim3(div_up((long)NE, 256)), dim3(256), 0, s, (long)NE, H.e2d_ptr.p, sq.p);
             SA_HIP_CHECK(hipGetLastError());
             exclusive_scan_off(s, NE, sq.p, L0.elmat.off.p);
             int64_t total = read_one(L0.elmat.off.p + NE, s);
-            import_array(L0.elmat.val, elmat, (size_t)total, s);
+            L0.elmat.val = DevIn<double>(elmat, (size_t)total, s).take();
             L0.elmat.max_nd = max_nd;
         } else {
         dev_iota(s, (long)NE + 1, (int64_t)nde * nde, L0.elmat.off.p);
-        if (!p.algebraic) import_array(L0.elmat.val, elmat, (size_t)NE * nde * nde, s);
+        if (!p.algebraic) L0.elmat.val = DevIn<double>(elmat, (size_t)NE * nde * nde, s).take();
         }
         L0.elmat.nde = nde;
         L0.elmat.algebraic = p.algebraic;
@@ -1640,9 +1630,7 @@ void hierarchy_update_operators(Hierarchy &H, const double *new_val) {
             L0.A.val.view(const_cast<double *>(new_val), (size_t)L0.A.nnz);   // device arrays are used in place
         } else {
             if (!L0.A.val.owned) L0.A.val.alloc((size_t)L0.A.nnz);           // never write into the caller's array
-            SA_HIP_CHECK(hipMemcpyAsync(L0.A.val.p, new_val, sizeof(double) * (size_t)L0.A.nnz,
-                                        hipMemcpyHostToDevice, s));
-            SA_HIP_CHECK(hipStreamSynchronize(s));
+            upload(L0.A.val.p, new_val, (size_t)L0.A.nnz, s);
         }
     }
     for (int lev = 0; lev < nspec; ++lev) {

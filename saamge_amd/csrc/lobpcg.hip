@@ -39,7 +39,7 @@ void lobpcg_solve(Hierarchy &H, const DCsr *M, const LobpcgOptions &o, const dou
         if (M) spmv(s, *M, column(S, c), column(MS, c));
     };
 
-    if (x0) SA_HIP_CHECK(hipMemcpyAsync(S, x0, 8 * (size_t)nb * n, hipMemcpyDeviceToDevice, s));
+    if (x0) copy_device(S, x0, (size_t)nb * n, s);
     else bv_hash_start(s, n, nb, o.seed, S, ld);
     if (flags) bv_mask(s, n, nb, flags, FLAG_ON_ESS_BORDER, S, ld);
     for (int j = 0; j < nb; ++j) products(j);
@@ -49,7 +49,7 @@ void lobpcg_solve(Hierarchy &H, const DCsr *M, const LobpcgOptions &o, const dou
     std::vector<double> lam(nb, 0.0), rho(nb, std::numeric_limits<double>::infinity()), norms(2 * BV_MAX_NORMS);
     // R = A X - M X diag(lam) into the W columns of the A S buffer, and the rho_j
     auto residuals = [&]() {
-        SA_HIP_CHECK(hipMemcpyAsync(lam_dev.p, lam.data(), 8 * (size_t)nb, hipMemcpyHostToDevice, s));
+        upload_async(lam_dev.p, (const double *)lam.data(), (size_t)nb, s);      // (read_back below synchronises)
         bv_residual(s, n, nb, AS, MS, ld, lam_dev.p, column(AS, 2 * nb), ld, scratch.p, norms_dev.p);
         read_back(norms.data(), norms_dev.p, norms.size(), s);
         for (int j = 0; j < nb; ++j) {
@@ -91,7 +91,7 @@ void lobpcg_solve(Hierarchy &H, const DCsr *M, const LobpcgOptions &o, const dou
             break;
         }
         lh::assemble_coefficients(width, nb, m, idx, C.data(), have_w, Cfull.data());
-        SA_HIP_CHECK(hipMemcpyAsync(Cdev.p, Cfull.data(), 8 * Cfull.size(), hipMemcpyHostToDevice, s));
+        upload_async(Cdev.p, (const double *)Cfull.data(), Cfull.size(), s);      // (residuals() synchronises before Cfull changes)
         // The whole buffer is combined: columns outside the basis meet zero rows of Cfull.  They must be FINITE (0 * inf
         // would poison X): the buffers start as zeros, and every column written since is a finite vector of an earlier basis.
         BvBlocks B{{S, AS, MS}, {S, AS, MS}, M ? 3 : 2};
@@ -119,7 +119,7 @@ void lobpcg_solve(Hierarchy &H, const DCsr *M, const LobpcgOptions &o, const dou
     if (res) std::copy(rho.begin(), rho.begin() + nev, res);
     if (iters) *iters = it;
     if (converged) *converged = conv;
-    SA_HIP_CHECK(hipMemcpyAsync(evecs, S, 8 * (size_t)nev * n, hipMemcpyDeviceToDevice, s));
+    copy_device(evecs, (const double *)S, (size_t)nev * n, s);
     SA_HIP_CHECK(hipStreamSynchronize(s));
 }
 

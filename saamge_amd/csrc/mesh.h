@@ -93,7 +93,8 @@ __device__ inline void raise_max(int *out, int c) {
 // face_elem outside [0, NE) or face_local outside the range of the element's type, then the first face whose (element, local
 // face) the list holds more than once; *refused (may be NULL) gets that index.  face_elem / face_local: host or device pointers.
 struct FaceList {
-    DBuf<int> hold_fe, hold_fl, key;      // key[f] = type * 8 + local face (em_type_index)
+    DevIn<int> in_fe, in_fl;
+    DBuf<int> key;                        // key[f] = type * 8 + local face (em_type_index)
     const int *fe = nullptr, *fl = nullptr;      // the lists on the device
     int touched = 0;                      // distinct elements of the list
 };

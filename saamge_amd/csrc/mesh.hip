@@ -7,7 +7,6 @@
 #include <utility>
 #include <vector>
 
-#include "operator.h"       // upload, device_view
 #include "partition.h"      // check_mesh_device
 
 namespace saamge_amd {
@@ -71,13 +70,13 @@ void import_mesh(hipStream_t s, const std::string &name, const MeshArgs &m, Devi
     const int NE = m.NE;
     // ---- the mesh: offsets first, they say how much of elem_to_vertex there is
     if (m.elem_ptr) {
-        M.eI = device_view(M.hold_I, m.elem_ptr, (size_t)NE + 1, s);
+        M.hold_I = DevIn<int>(m.elem_ptr, (size_t)NE + 1, s).take();
     } else {
         M.hold_I.alloc((size_t)NE + 1);
         hipLaunchKernelGGL(mesh_offsets_kernel, grid_flat((long)NE + 1), dim3(256), 0, s, NE, m.nde, M.hold_I.p);
         SA_HIP_CHECK(hipGetLastError());
-        M.eI = M.hold_I.p;
     }
+    M.eI = M.hold_I.p;
     M.eJ = m.elem_to_vertex;
     if (!is_device_ptr(m.elem_to_vertex)) {
         long total = (long)NE * m.nde;
@@ -103,13 +102,13 @@ void check_face_list(hipStream_t s, const std::string &name, int dim, int NE, co
                      const int *face_local, FaceList &L, long long *refused) {
     L.key.alloc((size_t)NF);
     DBuf<int> words(3);
-    const int *fe = L.fe = device_view(L.hold_fe, face_elem, (size_t)NF, s);
-    const int *fl = L.fl = device_view(L.hold_fl, face_local, (size_t)NF, s);
+    const int *fe = L.fe = L.in_fe.bind(face_elem, (size_t)NF, s);
+    const int *fl = L.fl = L.in_fl.bind(face_local, (size_t)NF, s);
     const int nwords = (int)(((int64_t)NE + 3) / 4);
     DBuf<unsigned> mask((size_t)nwords);
     mask.zero(s);
     const int init[3] = {INT_MAX, 0, 0};
-    SA_HIP_CHECK(hipMemcpyAsync(words.p, init, sizeof(init), hipMemcpyHostToDevice, s));
+    upload_async(words.p, init, 3, s);
     hipLaunchKernelGGL(bdr_check_kernel, grid_flat(NF), dim3(256), 0, s, NF, NE, dim, eI, fe, fl, mask.p, L.key.p, words.p);
     SA_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(bdr_touched_kernel, grid_flat(nwords), dim3(256), 0, s, nwords, (const unsigned *)mask.p, words.p + 2);

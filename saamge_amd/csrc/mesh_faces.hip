@@ -21,7 +21,6 @@
 #include <climits>
 
 #include "mesh.h"
-#include "operator.h"      // upload
 
 namespace saamge_amd {
 
@@ -275,7 +274,7 @@ void face_table_build(hipStream_t s, const MeshArgs &m, FaceTable &T, long long 
     // ---- the elements at every vertex
     DBuf<int> v2e_I((size_t)NV + 1), v2e_J((size_t)M.nconn), cnt((size_t)NV), words(MF_WORDS);
     const int init[MF_WORDS] = {INT_MAX, 0, 0, 0};
-    SA_HIP_CHECK(hipMemcpyAsync(words.p, init, sizeof(init), hipMemcpyHostToDevice, s));
+    upload_async(words.p, init, MF_WORDS, s);
     cnt.zero(s);
     dev_histogram(s, M.nconn, M.eJ, cnt.p);
     hipLaunchKernelGGL(mf_max_kernel, grid_flat(NV), dim3(256), 0, s, NV, (const int *)cnt.p, words.p + 3);
@@ -345,21 +344,14 @@ void face_nodes(hipStream_t s, const MeshArgs &m, int NF, const int *face_elem, 
     exclusive_scan_int(s, NF, fn.p, fptr.p);      // (at most 9 NF: NF is a count of int-indexed entries)
     const int count = read_one((const int *)fptr.p + NF, s);
     if (count_out) *count_out = count;
-    if (face_ptr_out) SA_HIP_CHECK(hipMemcpyAsync(face_ptr_out, fptr.p, ((size_t)NF + 1) * sizeof(int), hipMemcpyDefault, s));
+    copy_to_caller(face_ptr_out, fptr, s);
     if (face_nodes_out) {
-        DBuf<int> hold;
-        int *out = face_nodes_out;
-        if (!is_device_ptr(face_nodes_out)) {
-            hold.alloc((size_t)count);
-            out = hold.p;
-        }
+        DevOut<int> out(face_nodes_out, (size_t)count, s, false);
         hipLaunchKernelGGL(mf_face_nodes_kernel, grid_flat(NF), dim3(256), 0, s, NF, (const int *)L.key.p, L.fe, M.eI, M.eJ,
-                           (const int *)fptr.p, out);
+                           (const int *)fptr.p, out.p);
         SA_HIP_CHECK(hipGetLastError());
-        if (hold.p) SA_HIP_CHECK(hipMemcpyAsync(face_nodes_out, hold.p, (size_t)count * sizeof(int), hipMemcpyDeviceToHost, s));
-        SA_HIP_CHECK(hipStreamSynchronize(s));
+        out.finish();
     }
-    SA_HIP_CHECK(hipStreamSynchronize(s));
 }
 
 void face_dofs(hipStream_t s, const MeshArgs &m, int NF, const int *face_elem, const int *face_local, int vdim, unsigned comp_mask,
@@ -383,24 +375,17 @@ void face_dofs(hipStream_t s, const MeshArgs &m, int NF, const int *face_elem, c
     mf_mesh(s, name, m, M);
     FaceList L;
     check_face_list(s, name, dim, NE, M.eI, NF, face_elem, face_local, L, info ? info + 3 : nullptr);
-    const size_t bytes = (size_t)NV * vdim;
-    DBuf<signed char> hold;
-    signed char *bdr = bdr_dofs_inout;
-    if (!is_device_ptr(bdr_dofs_inout)) {
-        upload(hold, (const signed char *)bdr_dofs_inout, bytes, s);
-        bdr = hold.p;
-    }
+    DevOut<signed char> bdr(bdr_dofs_inout, (size_t)NV * vdim, s, true);
     DBuf<unsigned> nodes(((size_t)NV + 31) / 32);
     DBuf<u64> counts(2);
     nodes.zero(s);
     counts.zero(s);
     hipLaunchKernelGGL(mf_face_dofs_kernel, grid_flat(NF), dim3(256), 0, s, NF, (const int *)L.key.p, L.fe, M.eI, M.eJ, vdim, comp_mask,
-                       (unsigned)flag, bdr, nodes.p, counts.p);
+                       (unsigned)flag, bdr.p, nodes.p, counts.p);
     SA_HIP_CHECK(hipGetLastError());
     u64 c[2];
     read_back(c, (const u64 *)counts.p, 2, s);
-    if (hold.p) SA_HIP_CHECK(hipMemcpyAsync(bdr_dofs_inout, hold.p, bytes, hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
+    bdr.finish();
     if (info) {
         info[0] = NF;
         info[1] = (long long)c[0];

@@ -25,7 +25,6 @@
 #include <climits>
 
 #include "mesh.h"
-#include "operator.h"      // device_view
 
 namespace saamge_amd {
 
@@ -301,15 +300,15 @@ void mesh_lift_order2(hipStream_t s, const MeshArgs &m, const FaceTable *faces, 
     L.dim = dim;
     L.edge_ptr.alloc((size_t)NV + 1);
     L.elem_ptr2.alloc((size_t)NE + 1);
-    DBuf<double> hold_X;
-    const double *X = coords ? device_view(hold_X, coords, (size_t)NV * dim, s) : nullptr;
+    const DevIn<double> in_X(coords, (size_t)NV * dim, s);
+    const double *X = in_X.p;
     if (NE == 0) {
         L.edge_ptr.zero(s);
         L.elem_ptr2.zero(s);
         L.NV2 = NV;
         if (coords) {
             L.coords2.alloc((size_t)NV * dim);
-            if (NV) SA_HIP_CHECK(hipMemcpyAsync(L.coords2.p, X, (size_t)NV * dim * sizeof(double), hipMemcpyDeviceToDevice, s));
+            copy_device(L.coords2.p, X, (size_t)NV * dim, s);
         }
         SA_HIP_CHECK(hipStreamSynchronize(s));
         if (info) info[0] = info[7] = NV;
@@ -320,7 +319,7 @@ void mesh_lift_order2(hipStream_t s, const MeshArgs &m, const FaceTable *faces, 
     // ---- the type of every element
     DBuf<int> nd2((size_t)NE), centre((size_t)NE), words(ML_WORDS);
     const int init[ML_WORDS] = {INT_MAX, INT_MAX, INT_MAX, 0};
-    SA_HIP_CHECK(hipMemcpyAsync(words.p, init, sizeof(init), hipMemcpyHostToDevice, s));
+    upload_async(words.p, init, ML_WORDS, s);
     mesh_classify(s, NE, dim, M.eI, nd2.p, words.p, MlLiftedNodes{centre.p, words.p + 1});
     int w[ML_WORDS];
     read_back(w, (const int *)words.p, ML_WORDS, s);
@@ -428,7 +427,7 @@ void mesh_lift_order2(hipStream_t s, const MeshArgs &m, const FaceTable *faces, 
     L.elem_to_node.alloc((size_t)L.entries);
     if (coords) {
         L.coords2.alloc((size_t)NV2 * dim);
-        if (NV) SA_HIP_CHECK(hipMemcpyAsync(L.coords2.p, X, (size_t)NV * dim * sizeof(double), hipMemcpyDeviceToDevice, s));
+        copy_device(L.coords2.p, X, (size_t)NV * dim, s);
     }
     const int stride = elem_ptr ? (dim == 2 ? 9 : ML_MAX_ND2) : ML_HOST.nd2[em_type_index(dim, nde)];
     const long total = (long)NE * stride;

@@ -20,7 +20,6 @@
 
 #include "mesh.h"
 #include "mesh_lift.h"
-#include "operator.h"      // device_view
 
 namespace saamge_amd {
 
@@ -224,9 +223,9 @@ void mesh_refine(hipStream_t s, const MeshArgs &m, int levels, int want_interp, 
             R.dim = dim;
             unlisted = li[7];
             if (ne > 0) {
-                if (!uniform) I = device_view(bufI, elem_ptr, (size_t)ne + 1, s);
+                if (!uniform) I = (bufI = DevIn<int>(elem_ptr, (size_t)ne + 1, s).take()).p;
                 conn = uniform ? (long long)ne * nde : (long long)read_one(I + ne, s);
-                J = device_view(bufJ, elem_to_vertex, (size_t)conn, s);
+                J = (bufJ = DevIn<int>(elem_to_vertex, (size_t)conn, s).take()).p;
             }
         }
         const long long nnz = (long long)nv + 2 * L.NEd + 4 * L.NFq + (long long)cc * L.NC;

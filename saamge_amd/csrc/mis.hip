@@ -333,11 +333,7 @@ void mis_svd(hipStream_t s, const DevRelations &rel, int num_mises, int max_ctot
         SA_HIP_CHECK(hipGetLastError());
         exclusive_scan_int(s, nm, isrep.p, pos.p);
         dev_compact_scatter(s, nm, isrep.p, pos.p, list.p);
-        int last[2] = {0, 0};
-        SA_HIP_CHECK(hipMemcpyAsync(&last[0], pos.p + (nm - 1), sizeof(int), hipMemcpyDeviceToHost, s));
-        SA_HIP_CHECK(hipMemcpyAsync(&last[1], isrep.p + (nm - 1), sizeof(int), hipMemcpyDeviceToHost, s));
-        SA_HIP_CHECK(hipStreamSynchronize(s));
-        const int nrep = last[0] + last[1];
+        const int nrep = read_one((const int *)pos.p + (nm - 1), s) + read_one((const int *)isrep.p + (nm - 1), s);
         profiler().end(s, "eig_dedupe", 0.0, 0.0);
         if (io.debug & 1) std::fprintf(stderr, "MISes: %d distinct of %d\n", nrep, nm);
         profiler().begin(s);
@@ -566,11 +562,8 @@ bool coarse_e2d_device(hipStream_t s, const DevRelations &rel, const Relations &
     e2d.ncols = ncoarse;
     e2d.I.resize((size_t)nparts + 1);
     for (int e = 0; e <= nparts; ++e) e2d.I[e] = h_ptr[(size_t)hrel.AE_to_mis.I[e]];
-    e2d.J.resize((size_t)total);
-    if (total) {
-        SA_HIP_CHECK(hipMemcpyAsync(e2d.J.data(), d_J.p, sizeof(int) * (size_t)total, hipMemcpyDeviceToHost, s));
-        SA_HIP_CHECK(hipStreamSynchronize(s));
-    }
+    download(e2d.J, d_J, (size_t)total, s);
+    SA_HIP_CHECK(hipStreamSynchronize(s));
     return true;
 }
 
@@ -1041,8 +1034,7 @@ void rap_mis(hipStream_t s, const DevRelations &rel, const Relations &hrel, cons
     SA_HIP_CHECK(hipGetLastError());
     Ac.rowptr.alloc((size_t)nc + 1);
     exclusive_scan_off(s, nc, rowlen.p, Ac.rowptr.p);
-    roff_t nnz = 0;
-    SA_HIP_CHECK(hipMemcpyAsync(&nnz, Ac.rowptr.p + nc, sizeof(roff_t), hipMemcpyDeviceToHost, s));
+    const roff_t nnz = read_one((const roff_t *)Ac.rowptr.p + nc, s);
     h_sc = sc.to_host(s);
     const size_t need_max = (size_t)h_sc[RAP_SC_NEED_MAX], small_max = (size_t)h_sc[RAP_SC_SMALL_MAX];
     // Blocks that fit 64 KiB in one pass get by with the k output rows + >= 8 rows of T per chunk of

@@ -3,36 +3,8 @@
 #pragma once
 #include "common.h"
 
-#include <cstring>
-
 namespace saamge_amd {
 
-// a copy the handle owns; a large pageable source goes through a page-locked block (DBuf::from_host says why)
-template <class T>
-inline void upload(DBuf<T> &dst, const T *src, size_t n, hipStream_t s) {
-    dst.alloc(n);
-    if (!n) return;
-    const size_t bytes = n * sizeof(T);
-    if (!is_device_ptr(src) && bytes >= (256u << 10)) {
-        void *stage = pinned_alloc(bytes);
-        std::memcpy(stage, src, bytes);
-        const hipError_t e = hipMemcpyAsync(dst.p, stage, bytes, hipMemcpyHostToDevice, s);
-        const hipError_t e2 = hipStreamSynchronize(s);
-        pinned_free(stage, bytes);
-        SA_HIP_CHECK(e);
-        SA_HIP_CHECK(e2);
-        return;
-    }
-    SA_HIP_CHECK(hipMemcpyAsync(dst.p, src, bytes, hipMemcpyDefault, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
-}
-// a device pointer is used where it is
-template <class T>
-inline const T *device_view(DBuf<T> &hold, const T *src, size_t n, hipStream_t s) {
-    if (is_device_ptr(src)) return src;
-    upload(hold, src, n, s);
-    return hold.p;
-}
 // the ids i in [0, n) with cls[i] == which, ascending (flag: n ints, pos: n + 1 ints of scratch); returns their number
 int make_list(hipStream_t s, int n, const int *cls, int which, DBuf<int> &flag, DBuf<int> &pos, DBuf<int> &list);
 

@@ -536,8 +536,8 @@ void operator_numeric(AssembledOperator &op, const double *elmat) {
     SA_REQUIRE(elmat || !op.elmat_len, "null argument: elmat");
     if (!op.nnz) return;
     hipStream_t s = op.stream;
-    DBuf<double> hold;
-    const double *d = device_view(hold, elmat, (size_t)op.elmat_len, s);
+    const DevIn<double> in(elmat, (size_t)op.elmat_len, s);
+    const double *d = in.p;
     numeric_pass(s, op, d);
     SA_HIP_CHECK(hipStreamSynchronize(s));
 }
@@ -546,8 +546,8 @@ void operator_eliminate_rhs(const AssembledOperator &op, const double *elmat, co
     SA_REQUIRE(elmat || !op.elmat_len, "null argument: elmat");
     if (!op.n || !op.bdr.p) return;      // no essential dof
     hipStream_t s = op.stream;
-    DBuf<double> hold;
-    const double *d = device_view(hold, elmat, (size_t)op.elmat_len, s);
+    const DevIn<double> in(elmat, (size_t)op.elmat_len, s);
+    const double *d = in.p;
     hipLaunchKernelGGL(op_rhs_kernel, grid_flat(op.n), dim3(256), 0, s, op.n, (const int *)op.d2e_I.p, (const int *)op.d2e_J.p,
                        (const int *)op.eI.p, (const int *)op.eJ.p, (const roff_t *)op.moff.p, op.nde, d,
                        (const signed char *)op.bdr.p, (const roff_t *)op.rowptr.p, (const int *)op.col.p, x_ess, b);
@@ -559,8 +559,8 @@ void operator_assemble_rhs(const AssembledOperator &op, const double *elvec, dou
     SA_REQUIRE(elvec || !op.nconn, "null argument: elvec");
     if (!op.n) return;
     hipStream_t s = op.stream;
-    DBuf<double> hold;
-    const double *d = device_view(hold, elvec, (size_t)op.nconn, s);
+    const DevIn<double> in(elvec, (size_t)op.nconn, s);
+    const double *d = in.p;
     hipLaunchKernelGGL(op_rhs_assemble_kernel, grid_flat(op.n), dim3(256), 0, s, op.n, (const int *)op.d2e_I.p,
                        (const int *)op.d2e_J.p, (const int *)op.eI.p, (const int *)op.eJ.p, d, b);
     SA_HIP_CHECK(hipGetLastError());

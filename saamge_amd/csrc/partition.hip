@@ -1016,10 +1016,10 @@ void partition_graph_device(hipStream_t s, int n, const roff_t *xadj, const int 
         g.nlabels = 1;
         DBuf<int> sizes(2), k(1), km1(2);
         const int hs[2] = {n, 0}, hk[2] = {target - 1, 0};
-        SA_HIP_CHECK(hipMemcpyAsync(sizes.p, hs, sizeof hs, hipMemcpyHostToDevice, s));
-        SA_HIP_CHECK(hipMemcpyAsync(k.p, &target, sizeof(int), hipMemcpyHostToDevice, s));
-        SA_HIP_CHECK(hipMemcpyAsync(km1.p, hk, sizeof hk, hipMemcpyHostToDevice, s));
-        SA_HIP_CHECK(hipStreamSynchronize(s));
+        upload_async(sizes.p, hs, 2, s);
+        upload_async(k.p, &target, 1, s);
+        upload_async(km1.p, hk, 2, s);
+        SA_HIP_CHECK(hipStreamSynchronize(s));      // (the sources are locals)
         g.reseed(sizes, k, km1);
     }
     const auto grow = [&] {
@@ -1039,7 +1039,7 @@ void partition_graph_device(hipStream_t s, int n, const roff_t *xadj, const int 
             launch_flat(s, g.nlabels, pt_over_kernel, sizes.p, max_size, epa, k.p, km1.p, info.p);
             if (info.to_host(s)[0] == 0) break;
             DBuf<int> old((size_t)n);
-            SA_HIP_CHECK(hipMemcpyAsync(old.p, g.label, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, s));
+            copy_device(old.p, (const int *)g.label, (size_t)n, s);
             g.reseed(sizes, k, km1);
             g.grow(old.p);
             SA_HIP_CHECK(hipStreamSynchronize(s));

@@ -17,7 +17,7 @@ namespace saamge_amd {
 namespace {
 std::mutex g_pin_mu;
 std::multimap<size_t, void *> g_pin_free;
-constexpr size_t PIN_MIN = 256 * 1024;
+constexpr size_t PIN_MIN = STAGE_MIN_BYTES;      // what is not staged is not pinned either (xfer.h)
 size_t pin_class(size_t bytes) {
     size_t c = PIN_MIN;
     while (c < bytes) c <<= 1;
@@ -159,8 +159,8 @@ bool env_timing() { return timing_mode() == 1; }
 // SAAMGE_AMD_TIMING=host: the phases' host times WITHOUT synchronising the stream at their ends
 bool env_timing_host() { return timing_mode() == 2; }
 // The setup builds some tens of MB of host tables per hierarchy in std::vectors, copies some of them to and from the device
-// (pageable memory: the runtime registers the pages with the GPU for the transfer and keeps such registrations cached) and
-// releases them with the hierarchy.  What glibc then does with the memory decides how the NEXT setup starts:
+// (where they are handed over as pageable memory the runtime registers the pages with the GPU for the transfer and keeps such
+// registrations cached) and releases them with the hierarchy.  What glibc then does with the memory decides how the NEXT setup starts:
 //  * from the heap, with the default trimming: the top of the heap goes back to the kernel at every release and is grown
 //    again by the next hierarchy.  Unmapping pages the GPU driver still knows invalidates its registration, and the
 //    process's queues are stopped and restored: the first kernel of the next setup starts ~20 ms late (GPU trace: the queue
@@ -171,6 +171,10 @@ bool env_timing_host() { return timing_mode() == 2; }
 //  * from a heap that is never trimmed: neither.  That is what this asks for, once per process: blocks up to glibc's
 //    maximum of 32 MB from the heap, no trimming, the heap grown in steps of host_heap_pad_mb.
 // MPI libraries with registration caches set the same three parameters for the same reason.  DESIGN.md section 7.0.
+// The transfers themselves follow one rule (xfer.h): a host source of STAGE_MIN_BYTES or more that is not page-locked is
+// staged through the pinned pool by every upload that completes on return; smaller sources, hvecs, device-to-host copies and
+// copies into a caller's memory go directly; enqueue-only uploads take an hvec or less than STAGE_MIN_BYTES and nothing else.
+// The cause of the faults measured above is not known.
 void host_heap_policy(int mb) {
     static std::once_flag once;
     std::call_once(once, [mb] {

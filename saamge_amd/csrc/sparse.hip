@@ -1452,11 +1452,10 @@ __global__ __launch_bounds__(256) void sell_code_kernel(int nslices, const roff_
 void import_rowptr(DBuf<roff_t> &dst, const void *src, int bits, size_t n, hipStream_t s) {
     SA_REQUIRE(bits == 32 || bits == 64, "row offsets must be 32 or 64 bits wide");
     if (bits == 64) {
-        import_array(dst, (const roff_t *)src, n, s);
+        dst = DevIn<roff_t>((const roff_t *)src, n, s).take();
         return;
     }
-    DBuf<int> narrow;
-    import_array(narrow, (const int *)src, n, s);
+    const DevIn<int> narrow((const int *)src, n, s);
     dst.alloc(n);
     if (n) dev_convert(s, (long)n, (const int *)narrow.p, dst.p);
     SA_HIP_CHECK(hipStreamSynchronize(s));      // `narrow` may be an upload that is freed on return
@@ -1881,7 +1880,7 @@ void build_dinv_codes(hipStream_t s, DCsr &A, const double *dinv, const Options 
     if (!A.nrows || !A.sell.built || !A.sell.stage.regular() || !(opt.sell & 32)) return;
     D.tab.alloc(256);
     std::vector<unsigned long long> empty(256, DINV_EMPTY);
-    SA_HIP_CHECK(hipMemcpyAsync(D.tab.p, empty.data(), 256 * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+    upload_async(D.tab.p, (const unsigned long long *)empty.data(), 256, s);
     DBuf<int> overflow(1);
     overflow.zero(s);
     SA_HIP_CHECK(hipStreamSynchronize(s));      // (empty is a local)
@@ -1963,7 +1962,7 @@ void pcg_update_d(hipStream_t s, int n, const double *sc, double *d, const doubl
 }
 
 void vec_copy(hipStream_t s, int n, const double *src, double *dst) {
-    if (n) SA_HIP_CHECK(hipMemcpyAsync(dst, src, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+    if (n > 0) copy_device(dst, src, (size_t)n, s);
 }
 void vec_zero(hipStream_t s, int n, double *dst) {
     if (n) SA_HIP_CHECK(hipMemsetAsync(dst, 0, sizeof(double) * n, s));

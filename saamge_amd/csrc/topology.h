@@ -52,9 +52,9 @@ void build_relations_ae(Relations &r, Table &&elem_to_dof, const hvec<int> &part
 // amg/src/aggregates.cpp:324-487; Arbitrator::suggest, amg/src/arbitrator.cpp:93-204).
 struct HostCsr {
     int nrows = 0;
-    std::vector<roff_t> rowptr;
-    std::vector<int> col;
-    std::vector<double> val;
+    hvec<roff_t> rowptr;
+    hvec<int> col;
+    hvec<double> val;
 };
 void build_relations_mis(Relations &r, const HostCsr *aggregates_A = nullptr);
 

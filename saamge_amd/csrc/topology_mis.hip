@@ -164,11 +164,8 @@ bool build_relations_mis_device(Relations &r, DevRelations &d, hipStream_t s) {
     SA_HIP_CHECK(hipGetLastError());
     // ---- 2. MIS ids ----
     exclusive_scan_int(s, ND, flag.p, pos.p);
-    int nm = 0, herr = 0;
-    SA_HIP_CHECK(hipMemcpyAsync(&nm, pos.p + ND, sizeof(int), hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipMemcpyAsync(&herr, err.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    SA_HIP_CHECK(hipStreamSynchronize(s));
-    if (herr) return false;      // hash collision (1) or a dof outside every agglomerate (2): host path decides
+    const int nm = read_one((const int *)pos.p + ND, s);
+    if (read_one((const int *)err.p, s)) return false;      // hash collision (1) or a dof outside every agglomerate (2): host path decides
     d.mises.alloc((size_t)ND);
     DBuf<int> reps((size_t)nm);
     hipLaunchKernelGGL(mis_ids_kernel, dim3(g), dim3(256), 0, s, ND, rep_of.p, pos.p, flag.p, d.mises.p, reps.p);
@@ -214,9 +211,8 @@ bool build_relations_mis_device(Relations &r, DevRelations &d, hipStream_t s) {
         DBuf<int> sz((size_t)npairs + 1), off((size_t)npairs + 2);
         hipLaunchKernelGGL(mis_pair_size_kernel, dim3(div_up(npairs, 256)), dim3(256), 0, s, (long)npairs, mis_of_pair.p, d.mis2d_I.p, sz.p);
         exclusive_scan_int(s, npairs, sz.p, off.p);      // (the total is the number of (dof, AE) incidences: fits 32 bits with d2ae_J)
-        SA_HIP_CHECK(hipMemcpyAsync(&total, off.p + npairs, sizeof(int), hipMemcpyDeviceToHost, s));
         dev_convert(s, (long)npairs + 1, (const int *)off.p, d.pair_loc_off.p);
-        SA_HIP_CHECK(hipStreamSynchronize(s));
+        total = read_one((const int *)off.p + npairs, s);
     }
     d.pair_loc.alloc((size_t)total);
     hipLaunchKernelGGL(mis_pair_loc_kernel, dim3(g), dim3(256), 0, s, ND, I, d.dof_id_inAE.p, d.mises.p, d.dof_row_in_mis.p,

@@ -54,6 +54,26 @@ def test_product_has_no_oracle_dependency():
                 assert "oracle" not in txt.replace("no CPU fallback", ""), os.path.join(dirpath, f)
 
 
+def test_copies_go_through_the_transfer_layer():
+    """Every host <-> device and device <-> device copy of the library is a call of csrc/xfer.h: the runtime's copy functions
+    are named there and in the one line of the exported saamge_amd_memcpy (capi.hip), and the pinned pool hands out memory to
+    that header (hvec, the staging block) and inside runtime.hip only."""
+    csrc = os.path.join(ROOT, "saamge_amd", "csrc")
+    copies, pinned = [], []
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h", ".cpp")):
+            continue
+        lines = open(os.path.join(csrc, f)).read().splitlines()
+        for i, line in enumerate(lines):
+            if "hipMemcpy" in line and f != "xfer.h":
+                copies.append((f, " ".join(lines[max(0, i - 2):i + 1])))
+            if re.search(r"\bpinned_alloc\s*\(", line) and f not in ("xfer.h", "runtime.hip"):
+                pinned.append((f, line.strip()))
+    assert len(copies) == 1 and copies[0][0] == "capi.hip" and "int saamge_amd_memcpy(" in copies[0][1], copies
+    assert not pinned, pinned
+    assert "hipMemcpy" in open(os.path.join(csrc, "xfer.h")).read()
+
+
 def test_generators_consistent():
     import torch
     from saamge_amd import problems as pr

@@ -148,9 +148,7 @@ int main(int argc, char **argv) {
     hipLaunchKernelGGL(count_kernel, dim3(grid), dim3(256), 0, s, n, cnt.p);
     A.rowptr.alloc((size_t)N + 1);
     exclusive_scan_off(s, (int)N, cnt.p, A.rowptr.p);
-    roff_t nnz = 0;
-    hipMemcpyAsync(&nnz, A.rowptr.p + N, sizeof(roff_t), hipMemcpyDeviceToHost, s);
-    hipStreamSynchronize(s);
+    const roff_t nnz = read_one((const roff_t *)A.rowptr.p + N, s);
     A.nnz = nnz;
     A.col.alloc((size_t)nnz);
     A.val.alloc((size_t)nnz);
