@@ -71,7 +71,7 @@ def _oracle():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# cases: nu_pro = 0, theta = 0.003, two coarsenings
+# cases: nu_pro = 0, two coarsenings, theta = 0.003 unless the case names its own
 # ---------------------------------------------------------------------------------------------------------------------
 def _q2_elasticity():
     prob = pr.elasticity3d_q2_problem((4, 4, 2), blk=(2, 2, 2))
@@ -80,18 +80,39 @@ def _q2_elasticity():
     return prob
 
 
-# name -> (problem, testmesh).  Level sizes in the comments: dofs per level, then the coarsest operator.
+@functools.lru_cache(maxsize=None)
+def _pskew():
+    """2 601 dofs, 8 agglomerates of 405 on level 0 (read-only: shared by the cases at its several theta)"""
+    return pr.poisson3d_problem((16, 16, 8), blk=(8, 8, 4), coef="skew", coarse_blk=[(2, 2, 1)])
+
+
+@functools.lru_cache(maxsize=None)
+def _el():
+    """945 dofs, 8 agglomerates of 180 on level 0 (read-only: shared by the cases at its several theta)"""
+    return pr.elasticity3d_problem((8, 6, 4), blk=(4, 3, 2), coarse_blk=[(2, 2, 1)])
+
+
+# name -> (problem, testmesh[, theta]).  Level sizes in the comments: dofs per level, then the coarsest operator.
 CASES = {
     "q2_elasticity": (_q2_elasticity, False),                                                               # 1 215 / 43 / 4
-    "q1_elasticity": (lambda: pr.elasticity3d_problem((8, 6, 4), blk=(4, 3, 2), coarse_blk=[(2, 2, 1)]), False),   # 945 / 125 / 4
+    "q1_elasticity": (_el, False),                                                                          # 945 / 125 / 4
     # 32 agglomerates, 8 on level 1 with six vectors on the free ones: interior MISes, level-1 MISes shared by four and by eight
     # agglomerates.  2 x 3 x 2 elements per agglomerate, not the 2 x 2 x 2 of an (8, 8, 8) mesh: there the two bending modes of
     # a clamped agglomerate are a degenerate pair of which "at least one" picks an arbitrary member (a precondition below).
     "q1_elasticity_interior": (lambda: pr.elasticity3d_problem((8, 6, 8), blk=(2, 3, 2), coarse_blk=[(2, 1, 2)]), False),   # 1 701 / 673 / 124
     "mltest": (lambda: pr.mltest_problem(order=1, levels=3), True),       # no basis freedom: the injection path and the ones column
     "poisson": (lambda: pr.poisson3d_problem((8, 8, 8), blk=(4, 4, 4), coarse_blk=[(2, 2, 1)]), False),   # one vector per agglomerate
+    # Larger theta, the quality knob turned up (LARGE_THETA; the regime of each is asserted on the oracle alone in
+    # tests/test_conditional_cases.py): many vectors per agglomerate, wide MIS gathers cut by sigma, 12-225 coarse dofs per MIS.
+    "pskew_t012": (_pskew, False, 0.12),       # 2 601 / 187: 4-6 vectors per agglomerate, then 6
+    "el_t005": (_el, False, 0.05),             # 945 / 279: 8, then 12 (the lock path)
+    "el_t0057": (_el, False, 0.057),           # 945 / 364: 10 and 13 in one batch (13 is what the block of sixteen vectors is for)
+    "el_t006": (_el, False, 0.06),             # 945 / 400: 10 and 17 in one batch (the lock path beside matrices no block holds)
+    "pskew_t025": (_pskew, False, 0.25),       # 2 601 / 739: 40-44, then 175-180 of 483 rows; level-1 product blocks over the LDS budget
+    "el_t012": (_el, False, 0.12),             # 945 / 592: 25-39, then 127-129 of 380 rows; level-1 product blocks over the LDS budget
 }
 ELASTICITY = ("q2_elasticity", "q1_elasticity", "q1_elasticity_interior")
+LARGE_THETA = ("pskew_t012", "el_t005", "el_t0057", "el_t006", "pskew_t025", "el_t012")
 NCOARS = 2
 
 
@@ -102,6 +123,10 @@ def problem(name):
 
 def uses_testmesh(name):
     return CASES[name][1]
+
+
+def theta_of(name):
+    return CASES[name][2] if len(CASES[name]) > 2 else THETA
 
 
 def vcycle_rhs(prob):
@@ -416,12 +441,12 @@ def standin_hierarchy(prob, ncoars=NCOARS, theta=THETA, testmesh=False, seed=1, 
 def plain_oracle(name):
     """the unconditioned oracle of a case, built once (read-only)"""
     o, prob = _oracle(), problem(name)
-    return o.ml_produce_data(prob.A, prob.elem_to_dof, prob.elmat, prob.bdr, prob.partitions[:NCOARS], theta=THETA, nu_relax=3,
-                             testmesh=uses_testmesh(name))
+    return o.ml_produce_data(prob.A, prob.elem_to_dof, prob.elmat, prob.bdr, prob.partitions[:NCOARS], theta=theta_of(name),
+                             nu_relax=3, testmesh=uses_testmesh(name))
 
 
 @functools.lru_cache(maxsize=None)
 def standin(name):
     """(hierarchy, view) of the stand-in implementation of a case, built once (tests take .mutated() copies)"""
-    H = standin_hierarchy(problem(name), testmesh=uses_testmesh(name))
+    H = standin_hierarchy(problem(name), theta=theta_of(name), testmesh=uses_testmesh(name))
     return H, oracle_view(H)

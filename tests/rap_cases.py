@@ -15,6 +15,7 @@ operators and bases whose entries are within a few hundred binades of 1."""
 from fractions import Fraction
 
 import numpy as np
+import scipy.sparse as sp
 
 
 def fma_exact(a, b, c):
@@ -63,6 +64,32 @@ def neighbours(A, mises, k, dofs):
     cols = np.concatenate([A.indices[A.indptr[g]:A.indptr[g + 1]] for g in dofs] + [np.zeros(0, dtype=A.indices.dtype)])
     ms = np.unique(mises[cols])
     return ms[k[ms] > 0]
+
+
+def mis_adjacency(A, mises, k):
+    """nm x nm 0/1 matrix: MIS m2 with k > 0 holds the column of a stored entry (zeros included) of a row of MIS m1."""
+    k = np.asarray(k)
+    n, nm = A.shape[0], len(k)
+    M = sp.csr_matrix((np.ones(n), (mises, np.arange(n))), shape=(nm, n))
+    pat = sp.csr_matrix((np.ones(len(A.indices)), A.indices, A.indptr), shape=A.shape)
+    adj = sp.csr_matrix(M @ pat @ M.T)
+    adj.data[:] = 1.0
+    return sp.csr_matrix(adj @ sp.diags((k > 0).astype(np.float64)))
+
+
+LDS_BUDGET = 160 * 1024 // 8      # doubles of LDS a workgroup of the product may take (rap_mis, csrc/mis.hip)
+
+
+def lds_need(adj, k):
+    """Per MIS (one_pass, floor), as rap_size_kernel counts them (0 where k = 0): the doubles of LDS with which the block is
+    done in one pass -- the tables of its nn neighbours, its k accumulator rows and one row of T, each of ncol doubles -- and
+    the least the kernel can work with, tables and two rows.  one_pass > LDS_BUDGET: the block takes the multi-pass path
+    (KC < k1); floor > LDS_BUDGET: the library refuses.  `adj`: mis_adjacency(A, mises, k) with its zeros eliminated."""
+    k = np.asarray(k, dtype=np.int64)
+    nn = np.diff(adj.indptr).astype(np.int64)
+    ncol = np.asarray(adj @ k.astype(np.float64)).astype(np.int64)
+    on = k > 0
+    return np.where(on, 3 * nn + 2 + (k + 1) * ncol, 0), np.where(on, 3 * nn + 2 + 2 * ncol, 0)
 
 
 def emulate_mis_rows(A, P, mises, k, m2d_I, m2d_J, m1, scalar=False):

@@ -1,8 +1,9 @@
 """CPU checks of tests/conditional_cases.py, the cases and the comparison that tests/test_gpu_conditional_parity.py holds the
 library to: the comparison run oracle against oracle (a stand-in implementation that rotates the eigenvectors inside equal
 eigenvalues and flips the signs of the MIS basis columns), the preconditions under which the cases leave no freedom once the
-basis is shared, mutations of the stand-in's derived data that the comparison must name, and the same mutations passing the
-loose criteria that were all the suite had below level 0."""
+basis is shared (the eigenvalue selection and the SVD cut), the regime that the cases at larger theta are there for,
+mutations of the stand-in's derived data that the comparison must name, and the same mutations passing the loose criteria
+that were all the suite had below level 0."""
 import numpy as np
 import pytest
 import scipy.linalg as sla
@@ -32,7 +33,7 @@ def test_round_trip_oracle_against_oracle(name):
     member of the family: against the UNCONDITIONED oracle its level-1 eigenvalues differ (elasticity cases)."""
     prob = cc.problem(name)
     H_A, view = cc.standin(name)
-    H_B, recorded = cc.conditional_oracle(prob, cc.NCOARS, view, testmesh=cc.uses_testmesh(name))
+    H_B, recorded = cc.conditional_oracle(prob, cc.NCOARS, view, theta=cc.theta_of(name), testmesh=cc.uses_testmesh(name))
     levels, solves = cc.compare_conditional(prob, view, H_B, recorded)
     print(cc.format_measured(name, levels, solves))
     for lev, n, v in _numbers(levels, solves):
@@ -55,8 +56,8 @@ def test_round_off_on_the_injected_bases_stays_orders_below_the_tolerances(name)
     (P is the noisy one here, so it is not compared.)"""
     prob = cc.problem(name)
     H_A, view = cc.standin(name)
-    H_B, recorded = cc.conditional_oracle(prob, cc.NCOARS, view, testmesh=cc.uses_testmesh(name), evect_noise=NOISE,
-                                          basis_noise=NOISE, seed=2)
+    H_B, recorded = cc.conditional_oracle(prob, cc.NCOARS, view, theta=cc.theta_of(name), testmesh=cc.uses_testmesh(name),
+                                          evect_noise=NOISE, basis_noise=NOISE, seed=2)
     levels, solves = cc.measure_conditional(prob, view, H_B, recorded)
     print(cc.format_measured(name + " (noise %g)" % NOISE, levels, solves))
     for lev, n, v in _numbers(levels, solves):
@@ -94,7 +95,7 @@ def test_preconditions_of_the_cases_on_the_oracle_alone(name):
     least one" -- otherwise the COUNT or the span, not only the basis, would be an implementation's choice.  On the plain
     oracle and on the stand-in (whose level-1 matrices differ).  A case that fails is replaced, not excused."""
     for H in (cc.plain_oracle(name), cc.standin(name)[0]):
-        for lev, (gap, cut) in enumerate(_selection_gaps(H)):
+        for lev, (gap, cut) in enumerate(_selection_gaps(H, cc.theta_of(name))):
             assert not cut, (name, lev, cut)
             assert gap >= 1e-6, (name, lev, gap)
 
@@ -109,6 +110,109 @@ def test_the_preconditions_reject_cubic_agglomerates_on_the_clamped_face():
     H = o.ml_produce_data(prob.A, prob.elem_to_dof, prob.elmat, prob.bdr, prob.partitions[:1], theta=cc.THETA, nu_relax=3)
     gap, cut = _selection_gaps(H)[0]
     assert cut and gap < 1e-9
+
+
+def _gathers(lv):
+    """per MIS of a level that has an SVD (more than one dof, not all essential, a non-zero gather):
+    (mis, rows, candidate columns, kept, singular values)"""
+    rel, m = lv.rel, [z.shape[1] for z in lv.evects]
+    rows = np.diff(rel.mis_to_dof.I)
+    return [(i, int(rows[i]), sum(m[int(a)] for a in rel.mis_to_AE.row(i)), int(lv.mis_numcoarsedof[i]), lv.mis_svals[i])
+            for i in range(rel.num_mises) if rows[i] > 1 and lv.mis_svals[i] is not None]
+
+
+def _cut_margins(H):
+    """over the MISes of all levels: the smallest kept sigma / sigma_0 and the largest dropped one (0 if no cut drops any)"""
+    kept, dropped = np.inf, 0.0
+    for lv in H.levels[:cc.NCOARS]:
+        for mis, rows, cols, k, s in _gathers(lv):
+            kept = min(kept, s[k - 1] / s[0])
+            if k < len(s):
+                dropped = max(dropped, s[k] / s[0])
+    return kept, dropped
+
+
+@pytest.mark.parametrize("name", list(cc.CASES))
+def test_the_svd_cut_leaves_no_choice(name):
+    """The second place where a COUNT could be an implementation's choice: a MIS keeps the directions with
+    sigma > 1e-10 sigma_0.  On every MIS of every level the last kept singular value is >= 1e-6 sigma_0 and the first dropped
+    one <= 1e-12 sigma_0 (measured: >= 1.1e-5 and <= 1.5e-15, on pskew_t012 and el_t005), so round-off of either
+    implementation, amplified or not, cannot move k.  On the plain oracle and on the stand-in."""
+    for H in (cc.plain_oracle(name), cc.standin(name)[0]):
+        kept, dropped = _cut_margins(H)
+        print("%s: smallest kept sigma / sigma_0 %.1e, largest dropped %.1e" % (name, kept, dropped))
+        assert kept >= 1e-6 and dropped <= 1e-12, (name, kept, dropped)
+
+
+# What the cases at larger theta are FOR, per case: the eigenvectors per agglomerate (smallest, largest) on level 0 and on the
+# plain oracle's level 1; the class every member's level 1 stays in (the stand-in's level 1 is another member of the family,
+# whose counts differ by one or two on elasticity): its bounds are the eigensolver's own, csrc/eig_ss_plan.h -- up to six pairs
+# for the block of eight, up to twelve with its lock, from fifteen on past every block -- and for the two largest cases from a
+# quarter of the rows on; and whether level 1 holds a block of the Galerkin product over its LDS budget and a wide MIS of more
+# than 64 rows.
+REGIME = {
+    "pskew_t012": ((4, 6), (6, 6), (1, 6), False),
+    "el_t005": ((8, 8), (12, 12), (7, 12), False),              # every agglomerate within the lock path's twelve
+    "el_t0057": ((10, 13), (22, 22), (15, 265), False),         # level 0: a batch whose largest want is 13, the block of sixteen
+    "el_t006": ((10, 17), (29, 30), (15, 265), False),          # level 0: the lock path beside matrices no block holds
+    "pskew_t025": ((40, 44), (175, 180), (120, 482), True),     # level 1: 175-180 pairs of 481-483 rows
+    "el_t012": ((25, 39), (127, 129), (95, 379), True),         # level 1: 127-129 pairs of 380 rows
+}
+assert set(REGIME) == set(cc.LARGE_THETA)
+
+
+@pytest.mark.parametrize("name", list(cc.LARGE_THETA))
+def test_the_cases_at_larger_theta_are_in_the_regime_they_are_named_for(name):
+    """Conditions on the inputs, so that a change of a problem generator cannot empty these cases silently: the range of
+    eigenvectors per agglomerate on level 0 and (the plain oracle's) on level 1, the class of level 1 on any member, on level 0
+    a wide MIS gather (more candidate columns than dofs: the row-wise Jacobi of mis_svd_kernel) and a MIS whose cut drops a
+    direction, no block of the Galerkin product that rap_mis would refuse (rap_cases.lds_need), and for pskew_t025 and el_t012 a
+    level-1 block that needs more LDS in one pass than rap_mis may take (the multi-pass path) and a wide level-1 MIS of more
+    than 64 rows (more than one lane pass over V).  On the plain oracle and on the stand-in."""
+    import rap_cases as rc
+    range0, range1, class1, heavy = REGIME[name]
+    for H in (cc.plain_oracle(name), cc.standin(name)[0]):
+        m0, m1 = ([z.shape[1] for z in H.levels[lev].evects] for lev in range(2))
+        assert (min(m0), max(m0)) == range0, (name, m0)
+        assert class1[0] <= min(m1) and max(m1) <= class1[1], (name, m1)
+        if H is cc.plain_oracle(name):
+            assert (min(m1), max(m1)) == range1, (name, m1)
+        g0, g1 = _gathers(H.levels[0]), _gathers(H.levels[1])
+        assert any(cols > rows for mis, rows, cols, k, s in g0), name
+        assert any(k < len(s) for mis, rows, cols, k, s in g0), name
+        over = 0
+        for lv in H.levels[:cc.NCOARS]:
+            k = np.asarray(lv.mis_numcoarsedof)
+            adj = rc.mis_adjacency(lv.A, lv.rel.mises, k)
+            adj.eliminate_zeros()
+            need, floor = rc.lds_need(adj, k)
+            assert floor.max() <= rc.LDS_BUDGET, (name, floor.max())      # the library must not refuse
+            over += int((need > rc.LDS_BUDGET).sum()) if lv is H.levels[1] else 0
+        if heavy:
+            assert over >= 1, name
+            assert any(cols > rows > 64 for mis, rows, cols, k, s in g1), (name, [(rows, cols) for mis, rows, cols, k, s in g1])
+
+
+@pytest.mark.parametrize("theta,vectors", [(0.15, (7, 8)), (0.19, (14, 14))])
+def test_the_sensitivity_bound_rejects_the_skew_problem_between_its_two_cases(theta, vectors):
+    """The obvious cases between pskew_t012 and pskew_t025: theta = 0.15 (7-8 vectors per fine agglomerate, the lock path) and
+    0.19 (fourteen on every one: the block of sixteen).  Both pass every precondition -- selection gaps, the SVD cut -- but a
+    level-0 MIS keeps a direction at 3e-6 sigma_0, and 2e-15 of noise on the injected eigenvectors moves that MIS's column
+    space by 4.8e-11 / 3.0e-11: above MIS_SENSITIVITY.  Those regimes come from the elasticity problem instead (el_t005,
+    el_t0057); the margin is not widened."""
+    prob = cc._pskew()
+    H_A = cc.standin_hierarchy(prob, theta=theta)
+    m0 = [z.shape[1] for z in H_A.levels[0].evects]
+    assert (min(m0), max(m0)) == vectors, m0
+    for lev, (gap, cut) in enumerate(_selection_gaps(H_A, theta)):
+        assert not cut and gap >= 1e-6, (lev, gap, cut)
+    kept, dropped = _cut_margins(H_A)
+    assert 1e-6 <= kept <= 1e-5 and dropped <= 1e-12, (kept, dropped)
+    view = cc.oracle_view(H_A)
+    H_B, recorded = cc.conditional_oracle(prob, cc.NCOARS, view, theta=theta, evect_noise=NOISE, basis_noise=NOISE, seed=2)
+    moved = recorded[0]["colspace"][0]
+    print("pskew theta %g: smallest kept sigma / sigma_0 %.1e, level-0 column space under the noise %.1e" % (theta, kept, moved))
+    assert moved > MIS_SENSITIVITY
 
 
 # ---------------------------------------------------------------------------------------------------------------------

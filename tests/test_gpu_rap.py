@@ -4,11 +4,12 @@ entrywise a-priori bound against scipy's P^T A P for larger cases with the rows 
 and the row pointers that the device scan makes.  Everything goes through the C ABI (get_csr, get_mis, get_table).
 Run with `pytest -m gpu` on an MI355X.
 
-The KC < k1 path of rap_numeric_kernel (a block too wide for its k rows of LDS at once) is not reached here: there is no
-entry point that takes a smaller LDS budget, and no option field was added for one."""
+The KC < k1 path of rap_numeric_kernel (a block too wide for its k rows of LDS at once) is reached by the theta = 0.5 case of
+test_every_mis_in_the_specified_order: 12 of its 27 MISes (k = 49 and 147) need more than the 20 480 doubles a workgroup
+may take (rap_cases.lds_need restates rap_size_kernel's count), and every one of them is held to the emulation bit for bit;
+the test asserts that some MIS takes that path there and that none does at theta = 0.003."""
 import numpy as np
 import pytest
-import scipy.sparse as sp
 
 from saamge_amd import problems as pr
 
@@ -30,19 +31,9 @@ def _level(h, lev):
     return A, P, Ac, mises, k, I, J
 
 
-def _mis_adjacency(A, mises, k):
-    """nm x nm 0/1 matrix: MIS m2 with k > 0 holds the column of a stored entry (zeros included) of a row of MIS m1."""
-    n, nm = A.shape[0], len(k)
-    M = sp.csr_matrix((np.ones(n), (mises, np.arange(n))), shape=(nm, n))
-    pat = sp.csr_matrix((np.ones(len(A.indices)), A.indices, A.indptr), shape=A.shape)
-    adj = sp.csr_matrix(M @ pat @ M.T)
-    adj.data[:] = 1.0
-    return sp.csr_matrix(adj @ sp.diags((k > 0).astype(np.float64)))
-
-
 def _check_structure(h, lev, A, Ac, mises, k):
     """Ac.indptr from the device scan == the row lengths that the neighbour lists imply; nnzAc == indptr[-1]."""
-    adj = _mis_adjacency(A, mises, k)
+    adj = rc.mis_adjacency(A, mises, k)
     adj.eliminate_zeros()
     ncol = np.asarray(adj @ k.astype(np.float64)).astype(np.int64)
     lens = np.repeat(ncol, k)
@@ -70,7 +61,14 @@ def test_every_mis_in_the_specified_order(coef, theta):
     sizes = np.diff(I)
     on = sizes[k > 0]
     assert on.min() == 1 and on.max() > 64 and len(set(on.tolist())) >= 5
-    _check_structure(h, 0, A, Ac, mises, k)
+    adj = _check_structure(h, 0, A, Ac, mises, k)
+    # which path of rap_numeric_kernel the blocks take: all k rows of a block in LDS at once, or several passes (KC < k1)
+    need, floor = rc.lds_need(adj, k)
+    multipass = np.nonzero(need > rc.LDS_BUDGET)[0]
+    print("theta %g: largest block needs %d doubles of LDS in one pass (budget %d); multi-pass MISes %s with k = %s" % (
+        theta, need.max(), rc.LDS_BUDGET, multipass.tolist(), sorted(set(k[multipass].tolist()))))
+    assert floor.max() <= rc.LDS_BUDGET
+    assert len(multipass) >= 1 if theta == 0.5 else len(multipass) == 0
     fmas = sum(rc.check_mis_exact(Ac, A, P, mises, k, I, J, m1) for m1 in range(len(k)))
     assert fmas > 0
     h.close()
