@@ -7,6 +7,7 @@
 #include <string>
 
 #include "blockvec.h"
+#include "cycle.h"
 #include "elmat.h"
 #include "hierarchy.h"
 #include "lobpcg.h"
@@ -384,10 +385,7 @@ int saamge_amd_vcycle(saamge_amd_hierarchy *h, const double *b, double *x, int i
     const size_t n = (size_t)L0.A.nrows;
     VecIn vb(b, n, H.stream);
     VecOut vx(x, n, H.stream, true);
-    // x <- x + B (b - A x)
-    spmv_residual(H.stream, L0.A, vx.p, vb.p, H.pcg_r.p);
-    vcycle_apply(H, 0, H.pcg_r.p, H.pcg_z.p);
-    vec_axpy(H.stream, (int)n, 1.0, H.pcg_z.p, vx.p);
+    vcycle_iterate(H, vb.p, vx.p);      // x <- x + B (b - A x)
     vx.finish();
     SA_API_END
 }
@@ -395,8 +393,8 @@ int saamge_amd_vcycle(saamge_amd_hierarchy *h, const double *b, double *x, int i
 int saamge_amd_set_coarse_solver(saamge_amd_hierarchy *h, saamge_amd_coarse_solve_fn fn, void *ctx) {
     SA_API_BEGIN
     SA_REQUIRE(h, "null argument");
-    h->H->user_coarse_solve = fn;
-    h->H->user_coarse_ctx = ctx;
+    h->H->coarse.user_solve = fn;
+    h->H->coarse.user_ctx = ctx;
     SA_API_END
 }
 
@@ -475,7 +473,7 @@ int saamge_amd_level_info(const saamge_amd_hierarchy *h, int level, long long in
     long long tot = 0;
     for (int m : L.ae_m) tot += m;
     info[7] = tot;
-    info[8] = H.last_coarse_iters;
+    info[8] = H.coarse.last_iters;
     info[9] = L.ae_xoff.empty() ? 0 : L.ae_xoff.back();
     info[10] = L.mis_s_off.empty() ? 0 : L.mis_s_off.back();
     long long usz = 0;
@@ -548,14 +546,15 @@ int saamge_amd_coarse_solver_info(const saamge_amd_hierarchy *h, long long info[
     const Hierarchy &H = *h->H;
     for (int i = 0; i < 8; ++i) info[i] = 0;
     SA_REQUIRE(!H.levels.empty(), "no levels");
-    info[0] = H.user_coarse_solve ? 0 : H.coarse_kind;
+    const CoarseSolver &C = H.coarse;
+    info[0] = C.user_solve ? 0 : C.kind;
     info[1] = H.levels.back()->Ac.nrows;
-    if (H.coarse_kind == 3) {
-        info[2] = H.c_bt.nblk;
-        info[3] = H.c_bt.max_block;
-        info[4] = (long long)H.c_bt.Sinv.n;
-    } else if (H.coarse_kind == 1) {
-        info[4] = (long long)H.c_L.n;
+    if (C.kind == 3) {
+        info[2] = C.bt.nblk;
+        info[3] = C.bt.max_block;
+        info[4] = (long long)C.bt.Sinv.n;
+    } else if (C.kind == 1) {
+        info[4] = (long long)C.inv.n;
     }
     SA_API_END
 }

@@ -2,17 +2,18 @@
 // tg_data_t / interp_data_t (reference: amg/inc/ml.hpp:118-120, amg/inc/levels.hpp:47-64,
 // amg/inc/tg_data.hpp:47-83, amg/inc/interp.hpp:54-100).
 #pragma once
-#include <exception>
+#include <chrono>
+#include <cstdio>
 #include <memory>
-#include <thread>
 #include <utility>
 
 #include "assemble.h"
-#include "blocktri.h"
 #include "common.h"
+#include "cycle.h"
 #include "eig.h"
 #include "mis.h"
 #include "options.h"
+#include "side_task.h"
 #include "sparse.h"
 #include "topology.h"
 
@@ -72,8 +73,7 @@ struct Level {                  // tg_data_t + interp_data_t + agg_partitioning_
     DCsr A;                     // level operator (level 0: the user's matrix, viewed or copied)
     DCsr P, R, Ac;              // interp, restr, coarse operator
     DCsr Ptent;                 // tentative prolongator, kept apart only when nu_pro > 0 (P is then the smoothed one)
-    DBuf<double> dinv_neg;      // smpr_poly_data_t::Dinv_neg
-    std::vector<double> roots;  // smpr_poly_data_t::roots (SAS)
+    Smoother sm;                // smpr_poly_data_t of A
     double theta = 0.0;
     int nu_relax = 3;
     Relations rel;              // host topology
@@ -99,8 +99,8 @@ struct Level {                  // tg_data_t + interp_data_t + agg_partitioning_
     DBuf<double> mis_U, mis_sig;        // mis_tent_interps (packed r x k, column-major), singular values
     DBuf<int> d_mis_k, d_mis_coloff;
     DBuf<int64_t> d_mis_u_off;
-    // solve-phase work vectors
-    DBuf<double> x, b, r, t0, t1;
+    // solve-phase work vectors (the smoother's: sm.tmp)
+    DBuf<double> x, b, r;
     DBuf<double> extra;                 // level 0: device copy / view of Params::extra_modes
     // R (R ... 1): the NEXT level's representation of the constant vector -- first start vector of that level's
     // few-eigenpairs iteration and the candidate of its known-null-vector shortcut (eig.h: EigBatch::x0c)
@@ -155,18 +155,9 @@ struct Hierarchy {              // ml_data_t
     hipStream_t stream = 0;
     int device = 0;             // the GPU this hierarchy lives on (current device of the creating thread)
     std::vector<std::unique_ptr<Level>> levels;
-    // coarsest solver
-    int coarse_kind = 2;        // 1 explicit dense inverse, 2 inner PCG, 3 block-tridiagonal direct solve (blocktri.hip)
-    BlockTri c_bt;
-    DBuf<double> c_dinv, c_r, c_z, c_d, c_q, c_t0, c_t1, c_b, c_x;
-    DBuf<double> c_L, c_work;   // explicit inverse of the coarsest operator (coarse_kind 1)
-    std::vector<double> c_roots;
-    // PCG scratch
-    DBuf<double> pcg_r, pcg_z, pcg_d, pcg_q, scal, partials;
-    int last_coarse_iters = 0;
-    // tg_data_t::coarse_solver plug: host callback replacing the built-in coarsest solve
-    int (*user_coarse_solve)(void *ctx, int n, const double *rc_host, double *xc_host) = nullptr;
-    void *user_coarse_ctx = nullptr;
+    CoarseSolver coarse;        // solver of the coarsest operator, levels.back()->Ac
+    PcgWork pcg;                // the outer solve
+    DBuf<double> scal, partials;        // scalars and dot-product partials of both PCGs (cycle.h: PcgWork)
     // smoother plug per level (saamge_amd_set_smoother): host callbacks, x += M^-1 (b - A x)
     struct UserSmoother {
         int (*pre)(void *ctx, int level, int n, const double *b_host, double *x_host) = nullptr;
@@ -183,13 +174,12 @@ struct Hierarchy {              // ml_data_t
     std::unique_ptr<DistIn> dist_in;      // per-rank inputs: the gathered operator / topology the level-0 arrays view
     // setup only: the Galerkin product of level `galerkin_lev` runs on its own thread and stream beside the
     // next level's element matrices and eigenproblems (which need the level's size, not its operator)
-    std::thread galerkin_thread;
-    std::exception_ptr galerkin_err;
+    // (declared after everything the product works on: the task is joined before any of that goes away)
+    SideTask galerkin_task;
     int galerkin_lev = -1;
     // row-partitioned solve: fork / join events of the interior-rows stream (halo_then)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     ~Hierarchy() {
-        if (galerkin_thread.joinable()) galerkin_thread.join();
         if (ev_fork) (void)hipEventDestroy(ev_fork);
         if (ev_join) (void)hipEventDestroy(ev_join);
     }
@@ -215,13 +205,22 @@ Hierarchy *hierarchy_create_dist(const ParCsrIn &A, int NE_loc, int nde, const i
 // device pointer, nullptr = the level-0 values were changed in place), all interpolations kept.
 void hierarchy_update_operators(Hierarchy &h, const double *new_val);
 
-// VCycleSolver::Mult with iterative_mode = false (amg/src/solve.cpp:309-323): x = B b.
-void vcycle_apply(Hierarchy &h, int level, const double *b, double *x);
-// smpr_sym_poly (amg/src/smpr.cpp:213-234): x += M^-1 (b - A x)
-void smoother_apply(Hierarchy &h, int level, const double *b, double *x);
-// MFEM CGSolver / kalchev_pcg (amg/src/mfem_addons.cpp:106-248).  b, x device pointers.
-// Returns iterations; hist (host, may be null) receives (B r_k, r_k), k = 0..iters.
-int pcg_solve(Hierarchy &h, const double *b, double *x, double rel_tol, double abs_tol,
-              int max_iter, int squared_tol, int zero_guess, int *converged, double *hist);
+// SAAMGE_AMD_TIMING=1 prints host-side phase times (the reference's "TIMING:" lines)
+struct PhaseTimer {
+    bool on, host;
+    hipStream_t s;
+    std::chrono::steady_clock::time_point t0;
+    explicit PhaseTimer(hipStream_t st) : on(env_timing() || env_timing_host()), host(env_timing_host()), s(st) {
+        t0 = std::chrono::steady_clock::now();
+    }
+    void lap(const char *what, int lev) {
+        if (!on) return;
+        if (!host) (void)hipStreamSynchronize(s);
+        auto t1 = std::chrono::steady_clock::now();
+        std::fprintf(stderr, "TIMING: level %d %-28s %9.3f ms\n", lev, what,
+                     std::chrono::duration<double, std::milli>(t1 - t0).count());
+        t0 = std::chrono::steady_clock::now();
+    }
+};
 
 }  // namespace saamge_amd

@@ -1,53 +1,15 @@
-// Setup (ml_produce_data) and solve (V-cycle, PCG) orchestration.  Host C++ driving the HIP
-// kernels; all numerics run on the device, the integer topology on the host.
+// Setup (ml_produce_data, adapt_update_operators) orchestration; the solve phase is cycle.hip.  Host C++ driving the
+// HIP kernels; all numerics run on the device, the integer topology on the host.
 #include "hierarchy.h"
 #include "dist.h"
-#include "dense.h"
 #include "spgemm.h"
 #include "devtab.h"
 
 #include <algorithm>
 #include <cmath>
-#include <chrono>
 #include <cstdlib>
-#include <functional>
-#include <thread>
 
 namespace saamge_amd {
-
-// smpr_sas_poly_roots (amg/src/smpr.cpp:282-306)
-static std::vector<double> sas_poly_roots(int nu) {
-    SA_REQUIRE(nu > 0, "nu_relax must be positive");
-    std::vector<double> r;
-    const double denom = (double)(2 * nu + 1);
-    for (int i = 0; i <= 2 * nu; ++i) {
-        const double v = std::cos(((double)i * M_PI) / denom);
-        r.push_back(v * v);
-    }
-    for (int i = 1; i <= nu; ++i) {
-        const double v = std::sin(((double)i * M_PI) / denom);
-        r.push_back(v * v);
-    }
-    return r;
-}
-
-// SAAMGE_AMD_TIMING=1 prints host-side phase times (the reference's "TIMING:" lines)
-struct PhaseTimer {
-    bool on, host;
-    hipStream_t s;
-    std::chrono::steady_clock::time_point t0;
-    explicit PhaseTimer(hipStream_t st) : on(env_timing() || env_timing_host()), host(env_timing_host()), s(st) {
-        t0 = std::chrono::steady_clock::now();
-    }
-    void lap(const char *what, int lev) {
-        if (!on) return;
-        if (!host) (void)hipStreamSynchronize(s);
-        auto t1 = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "TIMING: level %d %-28s %9.3f ms\n", lev, what,
-                     std::chrono::duration<double, std::milli>(t1 - t0).count());
-        t0 = std::chrono::steady_clock::now();
-    }
-};
 
 // grow-only scratch buffers that survive across chunks / levels / hierarchies
 static DBuf<double> &scratch_pool(int slot) {
@@ -150,6 +112,14 @@ static int fit_count(int i0, int i1, size_t budget, Bytes bytes_of) {
     return cnt;
 }
 
+// Ac = R (A P) as general sparse products (mfem::RAP, amg/inc/tg.hpp:696-709)
+static void galerkin_general(hipStream_t s, const DCsr &A, const DCsr &P, const DCsr &R, DCsr &Ac) {
+    DCsr AP;
+    spgemm(s, A, P, nullptr, nullptr, 1.0, 0.0, AP);
+    Ac = DCsr();      // (an operator update: the old product goes before the new one is made)
+    spgemm(s, R, AP, nullptr, nullptr, 1.0, 0.0, Ac);
+}
+
 // ---------------------------------------------------------------------------------------
 // one coarsening: tg_init_data + tg_build_hierarchy + tg_update_coarse_operator
 // ---------------------------------------------------------------------------------------
@@ -172,7 +142,7 @@ static void level_galerkin(Hierarchy &H, int lev, bool first, hipStream_t s) {
     } else {
         // interp_smooth (amg/src/interp.cpp:172-229): P = prod_k (I + (1/tau_k) Dinv_neg A) P_tent with
         // tau_k = sin^2(k pi / (2 nu + 1)) (smpr_sa_poly_roots, amg/src/smpr.cpp:266-280); then
-        // R = P^T and Ac = R A P (mfem::RAP, amg/inc/tg.hpp:696-709) as general sparse products.
+        // R = P^T and Ac = R A P (galerkin_general).
         const int nu = P.nu_pro[lev];
         if (first) L.Ptent = std::move(L.P);
         DCsr tmp[2];
@@ -181,7 +151,7 @@ static void level_galerkin(Hierarchy &H, int lev, bool first, hipStream_t s) {
             const double sn = std::sin((double)k * M_PI / (double)(2 * nu + 1));
             DCsr &dst = tmp[k & 1];
             dst = DCsr();
-            spgemm(s, L.A, *cur, cur, L.dinv_neg.p, 1.0 / (sn * sn), 1.0, dst);
+            spgemm(s, L.A, *cur, cur, L.sm.dinv_neg.p, 1.0 / (sn * sn), 1.0, dst);
             cur = &dst;
         }
         if (P.smooth_drop_tol != 0.0)   // AltThreshold (amg/src/interp.cpp:219-227)
@@ -189,26 +159,22 @@ static void level_galerkin(Hierarchy &H, int lev, bool first, hipStream_t s) {
         else
             L.P = std::move(tmp[nu & 1]);
         csr_transpose(s, L.P, L.R);
-        DCsr AP;
-        spgemm(s, L.A, L.P, nullptr, nullptr, 1.0, 0.0, AP);
-        spgemm(s, L.R, AP, nullptr, nullptr, 1.0, 0.0, L.Ac);
+        galerkin_general(s, L.A, L.P, L.R, L.Ac);
     }
 }
 
-static void level_galerkin(Hierarchy &H, int lev, bool first) { level_galerkin(H, lev, first, H.stream); }
+// fn as the body of a side task (side_task.h) that works on GPU `dev` and allocates, copies and frees on `stream`
+template <class F>
+static auto on_gpu(int dev, hipStream_t stream, F fn) {
+    return [dev, stream, fn = std::move(fn)]() mutable { adopt_device(dev); set_thread_stream(stream); fn(); };
+}
 
-// The deferred Galerkin product (see Hierarchy::galerkin_thread): wait for it and hand its result to the
-// next level.
+// The deferred Galerkin product (see Hierarchy::galerkin_task): wait for it and hand its result to the next level.
 static void join_galerkin(Hierarchy &H) {
     if (H.galerkin_lev < 0) return;
-    if (H.galerkin_thread.joinable()) H.galerkin_thread.join();
     const int lev = H.galerkin_lev;
     H.galerkin_lev = -1;
-    if (H.galerkin_err) {
-        std::exception_ptr e = H.galerkin_err;
-        H.galerkin_err = nullptr;
-        std::rethrow_exception(e);
-    }
+    H.galerkin_task.join();
     H.levels[lev + 1]->A = std::move(H.levels[lev]->Ac);     // A_{l+1} = Ac_l  (amg/src/ml.cpp:134)
 }
 
@@ -223,8 +189,6 @@ static void prepare_next_host(const Level &L, const roff_t *p_rowptr_dev, const 
                               int64_t p_nnz, hipStream_t s, NextPrep &out);
 
 // ---- build_level: one coarsening as a sequence of stages over the state below ----
-// a worker that is joined before what it works on goes away
-struct JoinedThread { std::thread t; ~JoinedThread() { if (t.joinable()) t.join(); } };
 // packed eigenpairs of the agglomerates of one chunk of the eigenproblem stage
 struct Chunk { int ae0, count; DBuf<double> evals, evecs; std::vector<int64_t> eoff, xoff; DBuf<int64_t> d_eoff, d_xoff; };
 struct LevelBuild {
@@ -238,7 +202,6 @@ struct LevelBuild {
     // topology: the MIS tables are built on a host thread while the GPU solves the local eigenproblems
     HostCsr aggA;
     bool aggregates = false;
-    std::exception_ptr mis_err;
     bool operator_pending = false;      // the level's operator is still in the making (deferred Galerkin product of the finer level)
     // local eigenproblems: sizes and ownership of the agglomerates, the chunks' results
     bool keep_rows = false;
@@ -258,8 +221,7 @@ struct LevelBuild {
     bool counted[2] = {false, false};
     bool overlap_iter = false;
     hipStream_t iter_stream = nullptr;
-    std::exception_ptr iter_err;
-    JoinedThread mis_thread, iter_thread;      // (last: joined first)
+    SideTask mis_task, iter_task;      // (last: joined before anything they work on goes away)
 
     LevelBuild(Hierarchy &H_, int lev_, int nparts_) : H(H_), lev(lev_), L(*H_.levels[lev_]), P(H_.params), s(H_.stream), nparts(nparts_),
                                                        world(H_.params.world > 1 ? H_.params.world : 1), dev(current_device()), tm(H_.stream) {}
@@ -297,17 +259,6 @@ static std::vector<int> balanced_ranges(int n, int world, Cost cost) {
     return begin;
 }
 
-// SELL-64 copy of the level operator for the SpMV family + smoother data (smpr_init_poly_data,
-// amg/src/smpr.cpp:359-423)
-static void level_operator_data(Level &L, const Params &P, hipStream_t s) {
-    build_sell(s, L.A, P.opt);
-    L.dinv_neg.alloc((size_t)L.A.nrows);
-    DBuf<double> tmp((size_t)L.A.nrows);
-    build_dinv_neg(s, L.A, tmp.p, L.dinv_neg.p);
-    build_dinv_codes(s, L.A, L.dinv_neg.p, P.opt);
-    SA_HIP_CHECK(hipStreamSynchronize(s));
-}
-
 // Stage 1: the agglomerate tables, the start of the MIS-table thread, the operator's SELL copy and smoother data.
 static void level_topology(LevelBuild &B, Table &&e2d, const hvec<int> &part, const signed char *bdr_host, const DeviceInputs *din) {
     Hierarchy &H = B.H; Level &L = B.L; const Params &P = B.P; hipStream_t s = B.s;
@@ -315,20 +266,12 @@ static void level_topology(LevelBuild &B, Table &&e2d, const hvec<int> &part, co
     // Fine level, device-resident inputs: the SELL copy of the operator and the smoother diagonal (bandwidth work on A alone) are
     // built on a thread and stream of their own BESIDE the device build of the AE tables (integer work on elem_to_dof: sorts,
     // hash sets, atomics), and joined where they used to run, before the eigenproblems.
-    std::exception_ptr op_err;
-    JoinedThread op_thread;
+    SideTask op_task;
     const bool op_early = lev == 0 && din && !env_serial() && !profiler().enabled && H.galerkin_lev < 0 && (P.opt.overlap & 8);
     if (op_early) {
         hipStream_t os = side_stream(6);
-        const int dev0 = B.dev;
         SA_HIP_CHECK(hipStreamSynchronize(s));          // (the operator's arrays are complete)
-        op_thread.t = std::thread([&L, &P, &op_err, os, dev0]() {
-            try {
-                adopt_device(dev0);
-                set_thread_stream(os);
-                level_operator_data(L, P, os);
-            } catch (...) { op_err = std::current_exception(); }
-        });
+        op_task.start(on_gpu(B.dev, os, [&L, &P, os]() { operator_data(os, L.A, P.opt, true, L.sm); }));
     }
     bool on_device = false;
     if (din) {
@@ -358,9 +301,8 @@ static void level_topology(LevelBuild &B, Table &&e2d, const hvec<int> &part, co
         upload_relations_ae(L.drel, L.rel, s);
         B.tm.lap("upload topology", lev);
     }
-    // the MIS tables are built on a host thread while the GPU solves the local eigenproblems
-    // (do_aggregates, amg/src/ml.cpp:149: aggregates with arbitration on the LAST coarsening; the
-    // greedy arbitration reads the level matrix on the host)
+    // the MIS tables are built on a host thread while the GPU solves the local eigenproblems (do_aggregates, amg/src/ml.cpp:149:
+    // aggregates with arbitration on the LAST coarsening; the greedy arbitration reads the level matrix on the host)
     HostCsr &aggA = B.aggA;
     B.aggregates = P.do_aggregates && lev == P.num_coarsenings - 1;
     if (B.aggregates) {
@@ -376,46 +318,30 @@ static void level_topology(LevelBuild &B, Table &&e2d, const hvec<int> &part, co
     // SAAMGE_AMD_SERIAL=1: no worker threads anywhere in the setup (counter passes attribute launches per thread; the
     // work runs in line, same streams).  The "stream_stack.cpp: Check failed" aborts once seen under rocprofv3 --pmc came
     // from static destructors calling HIP at exit (fixed in round 4: those objects are never destroyed), not from threads
-    auto mis_work = [&B, mis_stream]() {
+    B.mis_task.start(on_gpu(B.dev, mis_stream, [&B, mis_stream]() {      // (the worker allocates and copies: same GPU as the caller)
         Level &L = B.L;
-        try {
-            adopt_device(B.dev);   // the worker allocates and copies: same GPU as the caller
-            set_thread_stream(mis_stream);
-            // MIS tables on the device; aggregates with arbitration are
-            // sequential by definition and stay on the host
-            constexpr bool host_mis = false;      // (the host build stays the fallback after a hash collision and for aggregates with arbitration)
-            PhaseTimer tmis(mis_stream);
-            bool on_dev = false;
-            if (!B.aggregates && !host_mis) on_dev = build_relations_mis_device(L.rel, L.drel, mis_stream);
-            if (on_dev) tmis.lap("    device MIS tables", B.lev);
-            if (!on_dev) {
-                fetch_relations_ae_host(L.rel, L.drel, mis_stream);
-                build_relations_mis(L.rel, B.aggregates ? &B.aggA : nullptr);
-                upload_relations_mis(L.drel, L.rel, mis_stream);
-            }
-            SA_HIP_CHECK(hipStreamSynchronize(mis_stream));
-        } catch (...) { B.mis_err = std::current_exception(); }
-    };
-    if (env_serial()) {
-        mis_work();
-        set_thread_stream(s);
-    } else {
-        B.mis_thread.t = std::thread(mis_work);
-    }
+        // MIS tables on the device; aggregates with arbitration are sequential by definition and stay on the host, which
+        // is also the fallback after a hash collision
+        PhaseTimer tmis(mis_stream);
+        if (!B.aggregates && build_relations_mis_device(L.rel, L.drel, mis_stream)) {
+            tmis.lap("    device MIS tables", B.lev);
+        } else {
+            fetch_relations_ae_host(L.rel, L.drel, mis_stream);
+            build_relations_mis(L.rel, B.aggregates ? &B.aggA : nullptr);
+            upload_relations_mis(L.drel, L.rel, mis_stream);
+        }
+        SA_HIP_CHECK(hipStreamSynchronize(mis_stream));
+    }), env_serial());
+    if (env_serial()) set_thread_stream(s);
     // the operator's SELL copy and smoother data; on a coarse level the operator may still be in the making (deferred
     // Galerkin product of the finer level): then after the eigenproblems, which do not read it
     B.operator_pending = H.galerkin_lev >= 0;
     // (Measured in round 4 and dropped: the fine level's SELL copy and D^-1 -- 13 ms of bandwidth work the setup itself does not
     // need -- on a thread and stream of their own beside the next level: setup 247 -> 243 ms, but the smoother then ran at 221
     // instead of 216 us per step and the step took 399 instead of 390 ms.)
-    if (op_early) {
-        op_thread.t.join();
-        if (op_err) std::rethrow_exception(op_err);
-    } else if (!B.operator_pending) {
-        join_galerkin(H);
-        level_operator_data(L, P, s);
-    }
-    L.roots = sas_poly_roots(L.nu_relax);
+    if (op_early) op_task.join();
+    else if (!B.operator_pending) { join_galerkin(H); operator_data(s, L.A, P.opt, true, L.sm); }
+    L.sm.roots = sas_poly_roots(L.nu_relax);
 }
 
 // ---- stage 2: local spectral problems, chunked over AEs (interp_compute_vectors) ----
@@ -466,18 +392,10 @@ static void eig_start_iterate(LevelBuild &B, int slot) {
     B.counted[slot] = false;
     if (!B.overlap_iter || !batch.subspace || batch.ss_failed || !batch.count) return;
     B.counted[slot] = true;
-    B.iter_thread.t = std::thread([&B, slot]() {
-        try {
-            adopt_device(B.dev);
-            set_thread_stream(B.iter_stream);
-            eig_count(B.iter_stream, B.batches[slot], -1.0, B.L.theta);
-            SA_HIP_CHECK(hipStreamSynchronize(B.iter_stream));
-        } catch (...) { B.iter_err = std::current_exception(); }
-    });
-}
-static void eig_join_iterate(LevelBuild &B) {
-    if (B.iter_thread.t.joinable()) B.iter_thread.t.join();
-    if (B.iter_err) { std::exception_ptr e = B.iter_err; B.iter_err = nullptr; std::rethrow_exception(e); }
+    B.iter_task.start(on_gpu(B.dev, B.iter_stream, [&B, slot]() {
+        eig_count(B.iter_stream, B.batches[slot], -1.0, B.L.theta);
+        SA_HIP_CHECK(hipStreamSynchronize(B.iter_stream));
+    }));
 }
 // the dense path on (re-)assembled matrices: batch b = the agglomerates from ae0 on, whose first row is row0 of the rank's
 static void eig_dense_pass(LevelBuild &B, EigBatch &b, int ae0, int64_t row0) {
@@ -695,17 +613,17 @@ static void level_eigenproblems(LevelBuild &B) {
         B.pend_ae0[slot] = ae0;
         B.pend_cnt[slot] = cnt;
         B.pend_row0[slot] = row0;
-        if (prev >= 0) { eig_join_iterate(B); eig_chunk_finish(B, prev); }
+        if (prev >= 0) { B.iter_task.join(); eig_chunk_finish(B, prev); }
         eig_start_iterate(B, slot);
         prev = slot;
         row0 += rows_chunk;
         ae0 += cnt;
     }
-    if (prev >= 0) { eig_join_iterate(B); eig_chunk_finish(B, prev); }
+    if (prev >= 0) { B.iter_task.join(); eig_chunk_finish(B, prev); }
     B.tm.lap("local eigenproblems", lev);
     if (B.operator_pending) {
         join_galerkin(H);
-        level_operator_data(L, P, s);
+        operator_data(s, L.A, P.opt, true, L.sm);
         B.tm.lap("operator (deferred Galerkin product) + SELL + D", lev);
     }
 }
@@ -763,8 +681,7 @@ static void level_concatenate(LevelBuild &B) {
 static void level_mis_svd(LevelBuild &B) {
     Level &L = B.L; const Params &P = B.P; const Relations &rel = L.rel; hipStream_t s = B.s;
     const int lev = B.lev, world = B.world;
-    if (B.mis_thread.t.joinable()) B.mis_thread.t.join();
-    if (B.mis_err) std::rethrow_exception(B.mis_err);
+    B.mis_task.join();
     B.tm.lap("MIS tables (join)", lev);
     const int nm = rel.num_mises;
     std::vector<int64_t> g_off((size_t)nm + 1, 0);
@@ -838,7 +755,7 @@ static void level_transfer(LevelBuild &B) {
     L.mis_coloff.assign((size_t)nm + 1, 0);
     for (int m = 0; m < nm; ++m) L.mis_coloff[m + 1] = L.mis_coloff[m] + L.mis_k[m];
     L.d_mis_coloff.from_host(L.mis_coloff, s);
-    build_P_R(s, L.drel, rel, L.mis_k, L.mis_u_off, L.d_mis_k.p, L.d_mis_coloff.p, L.d_mis_u_off.p, L.mis_U.p, L.P, L.R);
+    build_P_R(s, L.drel, rel, L.mis_k, L.d_mis_k.p, L.d_mis_coloff.p, L.d_mis_u_off.p, L.mis_U.p, L.P, L.R);
     if (lev + 1 < P.num_coarsenings) {     // the next level's representation of the constant vector (P^T P = I)
         L.cvec_next.alloc((size_t)L.R.nrows);
         const double *cv = nullptr;
@@ -852,52 +769,39 @@ static void level_transfer(LevelBuild &B) {
         spmv(s, L.R, cv, L.cvec_next.p);
         SA_HIP_CHECK(hipStreamSynchronize(s));
     }
-    // the host half of the next level's inputs runs beside the Galerkin product (own thread, own
-    // stream); with a smoothed prolongator level_galerkin moves P, so it is done afterwards
-    std::exception_ptr prep_err;
-    JoinedThread prep_thread;
-    // (device build first: ~1 ms on the main stream; the host build is the fallback for AEs with more
-    // coarse dofs than the kernel's LDS holds)
-    constexpr bool host_e2d = false;
-    if (lev + 1 < P.num_coarsenings && P.nu_pro[lev] == 0 && !host_e2d) {
+    // The next level's element lists from the tentative P.  Device build first (~1 ms on the main stream); its fallback for AEs with
+    // more coarse dofs than the kernel's LDS holds is the host half, on a thread and stream of its own beside the Galerkin product.
+    // With a smoothed prolongator level_galerkin moves P, so both are left to prepare_next_level.
+    SideTask prep_task;
+    const bool tent_next = lev + 1 < P.num_coarsenings && P.nu_pro[lev] == 0;
+    if (tent_next) {
         NextPrep &np = L.next_prep;
-        np.on_device = coarse_e2d_device(s, L.drel, rel, L.d_mis_k.p, L.d_mis_coloff.p, L.mis_coloff.back(),
-                                         L.P.rowptr.p, L.P.val.p, np.d_colpos_ptr, np.d_colpos, np.e2d);
-        np.ready = np.on_device;
+        np.ready = np.on_device = coarse_e2d_device(s, L.drel, rel, L.d_mis_k.p, L.d_mis_coloff.p, L.mis_coloff.back(),
+                                                    L.P.rowptr.p, L.P.val.p, np.d_colpos_ptr, np.d_colpos, np.e2d);
     }
-    if (lev + 1 < P.num_coarsenings && P.nu_pro[lev] == 0 && !L.next_prep.ready) {
+    if (tent_next && !L.next_prep.ready) {
         hipStream_t side = side_stream(1);
         SA_HIP_CHECK(hipStreamSynchronize(s));       // P is complete
-        prep_thread.t = std::thread([&L, &prep_err, prp = L.P.rowptr.p, pvl = L.P.val.p, pnr = L.P.nrows, pnz = L.P.nnz, sd = side, dev]() {
-            try {
-                adopt_device(dev);
-                set_thread_stream(sd);
-                prepare_next_host(L, prp, pvl, pnr, pnz, sd, L.next_prep);
-                SA_HIP_CHECK(hipStreamSynchronize(sd));      // nothing of this thread is in flight after the join
-            } catch (...) { prep_err = std::current_exception(); }
-        });
+        prep_task.start(on_gpu(dev, side, [&L, prp = L.P.rowptr.p, pvl = L.P.val.p, pnr = L.P.nrows, pnz = L.P.nnz, sd = side]() {
+            prepare_next_host(L, prp, pvl, pnr, pnz, sd, L.next_prep);
+            SA_HIP_CHECK(hipStreamSynchronize(sd));      // nothing of this thread is in flight after the join
+        }));
     }
     // With another spectral level to come the product runs beside that level's element matrices and
     // eigenproblems (they need its size only); Options::overlap bit 2 cleared and the profiled step keep it in line.
-    const bool no_overlap = !(P.opt.overlap & 4) || env_serial();
-    const bool defer = lev + 1 < P.num_coarsenings && P.nu_pro[lev] == 0 && B.world == 1 && !no_overlap && !profiler().enabled;
+    const bool defer = tent_next && B.world == 1 && (P.opt.overlap & 4) && !env_serial() && !profiler().enabled;
     if (defer) {
         SA_HIP_CHECK(hipStreamSynchronize(s));       // the operands are complete
         hipStream_t gs = side_stream(2);
         H.galerkin_lev = lev;
-        H.galerkin_thread = std::thread([&H, lev, gs, dev]() {
-            try {
-                adopt_device(dev);
-                set_thread_stream(gs);
-                level_galerkin(H, lev, true, gs);
-                SA_HIP_CHECK(hipStreamSynchronize(gs));
-            } catch (...) { H.galerkin_err = std::current_exception(); }
-        });
+        H.galerkin_task.start(on_gpu(dev, gs, [&H, lev, gs]() {
+            level_galerkin(H, lev, true, gs);
+            SA_HIP_CHECK(hipStreamSynchronize(gs));
+        }));
     } else {
-        level_galerkin(H, lev, true);
+        level_galerkin(H, lev, true, s);
     }
-    if (prep_thread.t.joinable()) prep_thread.t.join();
-    if (prep_err) std::rethrow_exception(prep_err);
+    prep_task.join();
     B.tm.lap(defer ? "P, R (RAP deferred)" : "P, R, RAP", lev);
 }
 
@@ -920,7 +824,7 @@ static void build_level(Hierarchy &H, int lev, Table &&e2d, const hvec<int> &par
     }
     // work vectors
     const size_t n = (size_t)L.A.nrows;
-    L.x.alloc(n); L.b.alloc(n); L.r.alloc(n); L.t0.alloc(n);
+    L.x.alloc(n); L.b.alloc(n); L.r.alloc(n); L.sm.tmp.alloc(n);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -958,7 +862,7 @@ static void prepare_next_host(const Level &L, const roff_t *p_rowptr_dev, const 
     colpos.assign((size_t)colpos_ptr.back(), -1);
     // two passes over the AEs (count, then fill), both split over host threads
     {
-        int T = (int)std::thread::hardware_concurrency();
+        int T = (int)SideTask::hardware_threads();
         if (T < 1) T = 1;
         if (T > 16) T = 16;
         if (nparts < 64) T = 1;
@@ -988,9 +892,9 @@ static void prepare_next_host(const Level &L, const roff_t *p_rowptr_dev, const 
         };
         const int dev = current_device();
         for (int pass = 0; pass < 2; ++pass) {
-            std::vector<std::thread> th;
+            std::vector<SideTask> th((size_t)T);
             for (int t = 0; t < T; ++t)
-                th.emplace_back([&, t, pass]() {
+                th[(size_t)t].start([&, t, pass]() {
                     (void)hipSetDevice(dev);
                     std::vector<int> stamp((size_t)e2d.ncols, -1);
                     const int eb = (int)((int64_t)nparts * t / T), ee = (int)((int64_t)nparts * (t + 1) / T);
@@ -1018,10 +922,8 @@ static Table prepare_next_level(Hierarchy &H, int lev) {
         // (always the TENTATIVE prolongator: the coarse elements are built from mis_tent_interps)
         const DCsr &PT = L.Ptent.nrows ? L.Ptent : L.P;
         NextPrep &np = L.next_prep;
-        constexpr bool host_e2d = false;
-        if (!host_e2d)
-            np.on_device = coarse_e2d_device(s, L.drel, rel, L.d_mis_k.p, L.d_mis_coloff.p, L.mis_coloff.back(),
-                                             PT.rowptr.p, PT.val.p, np.d_colpos_ptr, np.d_colpos, np.e2d);
+        np.on_device = coarse_e2d_device(s, L.drel, rel, L.d_mis_k.p, L.d_mis_coloff.p, L.mis_coloff.back(),
+                                         PT.rowptr.p, PT.val.p, np.d_colpos_ptr, np.d_colpos, np.e2d);
         if (!np.on_device) prepare_next_host(L, PT.rowptr.p, PT.val.p, PT.nrows, PT.nnz, s, L.next_prep);
     }
     Table e2d = std::move(L.next_prep.e2d);
@@ -1047,22 +949,16 @@ static Table prepare_next_level(Hierarchy &H, int lev) {
     // The next level's AE tables are a HOST build (7.8 ms on the headline's level 1).  Its inputs are complete here -- the coarse
     // element lists just made, the caller's partition -- and nothing below needs its result: it runs on a thread of its own
     // beside the coarse element matrices (20 ms of device work during which this thread only waits).
-    std::exception_ptr topo_err;
-    JoinedThread topo_joined;
-    std::thread &topo_thread = topo_joined.t;
+    SideTask topo_task;
     if (lev + 1 < H.params.num_coarsenings && lev + 1 < (int)H.coarse_parts.size() && !H.coarse_parts[(size_t)lev + 1].empty() &&
         !env_serial()) {
         const int dev = current_device();
         const int nd_next = L.mis_coloff.back(), np_next = H.nparts_in[(size_t)lev + 1];
-        Table *e2d_copy = new Table(e2d);
         const hvec<int> *part_next = &H.coarse_parts[(size_t)lev + 1];
-        topo_thread = std::thread([&N, &topo_err, e2d_copy, part_next, nd_next, np_next, dev]() {
-            std::unique_ptr<Table> own(e2d_copy);
-            try {
-                adopt_device(dev);
-                build_relations_ae(N.rel, std::move(*own), *part_next, np_next, nd_next, nullptr);
-                N.rel_prebuilt = true;
-            } catch (...) { topo_err = std::current_exception(); }
+        topo_task.start([&N, own = Table(e2d), part_next, nd_next, np_next, dev]() mutable {      // (host work only: no stream)
+            adopt_device(dev);
+            build_relations_ae(N.rel, std::move(own), *part_next, np_next, nd_next, nullptr);
+            N.rel_prebuilt = true;
         });
     }
     std::vector<int> sizes((size_t)nparts);
@@ -1112,255 +1008,8 @@ static Table prepare_next_level(Hierarchy &H, int lev) {
         ae0 += cnt;
     }
     if (world > 1) allgather_ranges(H.params, N.elmat.val.p, 8, L.ae_begin, [&](int p) { return out_off[p]; }, "coarse element matrices");
-    if (topo_thread.joinable()) topo_thread.join();
-    if (topo_err) std::rethrow_exception(topo_err);
+    topo_task.join();
     return e2d;
-}
-
-// ---------------------------------------------------------------------------------------
-// coarsest solver: PCG on the coarsest operator, preconditioned by its own polynomial smoother
-// (the reference's parallel "coarse direct" is likewise an inner PCG to 1e-16,
-// amg/src/tg.cpp:998-1003)
-// ---------------------------------------------------------------------------------------
-static const DCsr &coarsest_op(const Hierarchy &H) { return H.levels.back()->Ac; }
-
-static void setup_coarse_solver(Hierarchy &H) {
-    DCsr &Ac = H.levels.back()->Ac;
-    hipStream_t s = H.stream;
-    const size_t n = (size_t)Ac.nrows;
-    build_sell(s, Ac, H.params.opt);
-    H.coarse_kind = 2;
-    H.c_dinv.alloc(n);
-    H.c_r.alloc(n); H.c_z.alloc(n); H.c_d.alloc(n); H.c_q.alloc(n); H.c_t0.alloc(n); H.c_t1.alloc(n);
-    if (n) {
-        DBuf<double> tmp(n);
-        build_dinv_neg(s, Ac, tmp.p, H.c_dinv.p);
-        SA_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    H.c_roots = sas_poly_roots(H.levels.back()->nu_relax);
-    // Dense direct solve (the reference's serial `--coarse-direct`, amg/src/tg.cpp:979-1014) as an explicit
-    // inverse when the coarsest operator is small enough (coarse_solver 0 = auto: n <= 8192, i.e. up to 512 MiB;
-    // 1 = always): at n = 3317 the inverse costs a few ms once and 20 us per V-cycle, the inner PCG ~2.4 ms per
-    // V-cycle.  A non-positive pivot (semi-definite operator) falls back to the inner PCG.
-    const int want = H.params.coarse_solver;
-    constexpr long dense_max = 8192;
-    H.c_bt = BlockTri();
-    if (n && (want == 1 || (want == 0 && (long)n <= dense_max)) && n <= 16384) {
-        if (dense_inverse_spd(s, Ac, H.c_L)) H.coarse_kind = 1;
-        else H.c_L.release();
-    } else if (n && (want == 1 || want == 3)) {
-        // a DIRECT solve was asked for (the reference's coarse_direct, src/tg.cpp:990-996) on an operator beyond one dense
-        // inverse: block-tridiagonal elimination over a level structure of its graph (blocktri.hip)
-        if (blocktri_factor(s, Ac, H.c_bt)) H.coarse_kind = 3;
-    }
-}
-
-static inline RowRange rows_of(const Level::Dist *D) {
-    RowRange rr;
-    if (D) { rr.row0 = D->row0; rr.nrows = D->nloc; }
-    return rr;
-}
-
-// x = poly(b) starting from x = 0; result lands in x, `tmp` is the ping-pong partner.
-// Row-partitioned (D != null): own rows only; the halo of the result is NOT refreshed (the next
-// operator application does that, halo_then).
-static void smooth_from_zero(Hierarchy &H, const DCsr &A, const double *dinv,
-                             const std::vector<double> &roots, const double *b, double *x, double *tmp,
-                             Level::Dist *D = nullptr) {
-    hipStream_t s = H.stream;
-    const int deg = (int)roots.size();
-    const int off = D ? D->row0 : 0, nl = D ? D->nloc : A.nrows;
-    double *cur = ((deg - 1) % 2 == 0) ? x : tmp;
-    double *oth = (cur == x) ? tmp : x;
-    smooth_first(s, nl, dinv + off, b + off, cur + off, 1.0 / roots[0]);
-    for (int i = 1; i < deg; ++i) {
-        const double scale = 1.0 / roots[i];
-        halo_then(H, D, cur, [&](hipStream_t q, RowRange rr) { smooth_step(q, A, dinv, b, cur, oth, scale, rr); });
-        std::swap(cur, oth);
-    }
-}
-
-// x += M^-1 (b - A x).  Row-partitioned: x is valid on the own rows on entry and on return (every step
-// refreshes the halo it reads).
-static void smooth_inplace(Hierarchy &H, const DCsr &A, const double *dinv,
-                           const std::vector<double> &roots, const double *b, double *x, double *tmp,
-                           Level::Dist *D = nullptr) {
-    hipStream_t s = H.stream;
-    const int deg = (int)roots.size();
-    const int off = D ? D->row0 : 0, nl = D ? D->nloc : A.nrows;
-    double *cur = x, *oth = tmp;
-    for (int i = 0; i < deg; ++i) {
-        const double scale = 1.0 / roots[i];
-        halo_then(H, D, cur, [&](hipStream_t q, RowRange rr) { smooth_step(q, A, dinv, b, cur, oth, scale, rr); });
-        std::swap(cur, oth);
-    }
-    if (cur != x) vec_copy(s, nl, cur + off, x + off);
-}
-
-// The PCG loop shared by the outer solve and the coarsest solver (MFEM CGSolver::Mult order
-// of operations == kalchev_pcg, amg/src/mfem_addons.cpp:106-248).  Row-partitioned (D != null):
-// vector updates and inner products run on the own rows, the products are summed over ranks,
-// the search direction's halo is refreshed before each A d.
-static int pcg_loop(Hierarchy &H, const DCsr &A, const std::function<void(const double *, double *)> &prec,
-                    const double *b, double *x, double *r, double *z, double *d, double *q,
-                    double rel_tol, double abs_tol, int max_iter, bool squared, bool zero_guess,
-                    int *converged, double *hist, double *sc, Level::Dist *D = nullptr) {
-    hipStream_t s = H.stream;
-    const int off = D ? D->row0 : 0, n = D ? D->nloc : A.nrows;
-    auto pdot = [&](const double *u, const double *v, double *out) {
-        dot(s, n, u + off, v + off, H.partials.p, out);
-        if (D) dist_allreduce(H, out, 1);
-    };
-    if (zero_guess) {
-        vec_zero(s, n, x + off);
-        vec_copy(s, n, b + off, r + off);
-    } else {
-        halo_then(H, D, x, [&](hipStream_t q, RowRange rq) { spmv_residual(q, A, x, b, r, rq); });
-    }
-    prec(r, z);
-    vec_copy(s, n, z + off, d + off);
-    pdot(d, r, sc + 0);
-    const double nom0 = read_one(sc + 0, s);
-    if (hist) hist[0] = nom0;
-    const double r0 = squared ? std::max(nom0 * rel_tol * rel_tol, abs_tol * abs_tol)
-                              : std::max(nom0 * rel_tol, abs_tol);
-    if (converged) *converged = 0;
-    if (nom0 <= r0) {
-        if (converged) *converged = 1;
-        return 0;
-    }
-    halo_then(H, D, d, [&](hipStream_t st, RowRange rq) { spmv(st, A, d, q, rq); });
-    pdot(q, d, sc + 1);
-    if (read_one(sc + 1, s) == 0.0) return 0;
-    int i = 1;
-    int final_iter = max_iter;
-    for (;;) {
-        pcg_update_xr(s, n, sc, x + off, r + off, d + off, q + off);
-        prec(r, z);
-        pdot(r, z, sc + 2);
-        const double betanom = read_one(sc + 2, s);
-        if (hist && i <= max_iter) hist[i] = betanom;      // hist holds max_iter + 1 doubles: with max_iter <= 0 the one update still runs
-        if (betanom < r0) {
-            if (converged) *converged = 1;
-            final_iter = i;
-            break;
-        }
-        if (++i > max_iter) break;
-        pcg_update_d(s, n, sc, d + off, z + off);
-        halo_then(H, D, d, [&](hipStream_t st, RowRange rq) { spmv(st, A, d, q, rq); });
-        pdot(d, q, sc + 1);
-        copy_device(sc + 0, (const double *)sc + 2, 1, s);
-    }
-    return final_iter;
-}
-
-static void coarse_solve(Hierarchy &H, const double *rc, double *xc) {
-    const DCsr &Ac = coarsest_op(H);
-    if (Ac.nrows == 0) return;
-    if (H.user_coarse_solve) {      // tg_data_t::coarse_solver assigned by the caller (host solver)
-        const size_t n = (size_t)Ac.nrows;
-        hvec<double> hr = fetch_host(rc, n, H.stream), hx(n, 0.0);
-        SA_REQUIRE(H.user_coarse_solve(H.user_coarse_ctx, (int)n, hr.data(), hx.data()) == 0, "user coarse solver failed");
-        upload(xc, (const double *)hx.data(), n, H.stream);
-        H.last_coarse_iters = 0;
-        return;
-    }
-    if (H.coarse_kind == 1) {
-        // x = X b and one step of iterative refinement, x += X (b - Ac x): the elimination's round-off
-        // (~cond(Ac) eps) is pushed to the level of the residual evaluation
-        const int n = Ac.nrows;
-        dense_symv(H.stream, n, H.c_L.p, rc, xc, false);
-        spmv_residual(H.stream, Ac, xc, rc, H.c_r.p);
-        dense_symv(H.stream, n, H.c_L.p, H.c_r.p, xc, true);
-        H.last_coarse_iters = 0;
-        return;
-    }
-    if (H.coarse_kind == 3) {
-        blocktri_solve(H.stream, Ac, H.c_bt, rc, xc);
-        H.last_coarse_iters = 0;
-        return;
-    }
-    auto prec = [&](const double *r, double *z) {
-        smooth_from_zero(H, Ac, H.c_dinv.p, H.c_roots, r, z, H.c_t0.p);
-    };
-    // scalar slots 4.. so the outer PCG's scalars (slots 0..2) survive
-    int conv = 0;
-    H.last_coarse_iters = pcg_loop(H, Ac, prec, rc, xc, H.c_r.p, H.c_z.p, H.c_d.p, H.c_q.p,
-                                   H.params.coarse_rtol, 0.0, H.params.coarse_max_iter, false, true,
-                                   &conv, nullptr, H.scal.p + 4);
-}
-
-static Level::Dist *dist_of(Level &L) { return L.dist.on ? &L.dist : nullptr; }
-
-// a caller's smoother (saamge_amd_set_smoother; the reference's smpr_ft plug, src/tg.cpp:113,131): x += M^-1 (b - A x)
-// on host copies.  zero_start: the cycle's x is not initialised yet, the callback receives x = 0.
-static void user_smooth(Hierarchy &H, int level, int (*fn)(void *, int, int, const double *, double *), void *ctx,
-                        const double *b, double *x, bool zero_start) {
-    Level &L = *H.levels[level];
-    SA_REQUIRE(!L.dist.on, "a caller's smoother cannot run on a level that is row-partitioned over several ranks");
-    const size_t n = (size_t)L.A.nrows;
-    hvec<double> hb = fetch_host(b, n, H.stream), hx = zero_start ? hvec<double>(n, 0.0) : fetch_host((const double *)x, n, H.stream);
-    SA_REQUIRE(fn(ctx, level, (int)n, hb.data(), hx.data()) == 0, "the caller's smoother failed");
-    upload(x, (const double *)hx.data(), n, H.stream);
-}
-
-// One V(1,1)-cycle from x = 0 (tg_cycle_atb, amg/src/tg.cpp:91-132).  On a row-partitioned
-// level b is read and x is written on the own rows only.
-static void vcycle_rec(Hierarchy &H, int level, const double *b, double *x) {
-    Level &L = *H.levels[level];
-    hipStream_t s = H.stream;
-    Level::Dist *D = dist_of(L);
-    const bool last = (level + 1 == (int)H.levels.size());
-    const Hierarchy::UserSmoother us = level < (int)H.user_smoothers.size() ? H.user_smoothers[level] : Hierarchy::UserSmoother();
-    if (us.pre) user_smooth(H, level, us.pre, us.ctx, b, x, true);
-    else smooth_from_zero(H, L.A, L.dinv_neg.p, L.roots, b, x, L.t0.p, D);   // pre_smoother, x0 = 0
-    halo_then(H, D, x, [&](hipStream_t q, RowRange rr) { spmv_residual(q, L.A, x, b, L.r.p, rr); });   // res = b - A x
-    double *rc = last ? H.c_b.p : H.levels[level + 1]->b.p;
-    double *xc = last ? H.c_x.p : H.levels[level + 1]->x.p;
-    spmv(s, L.R, L.r.p, rc);                                            // resc = R res
-    if (D) {      // res is zero outside the own rows: partial sums
-        constexpr bool no_rs = false;
-        // a row-partitioned coarser level reads the restricted residual on its own rows only: reduce-scatter
-        if (!last && !no_rs && H.levels[level + 1]->dist.on) dist_reduce_scatter_rows(H, H.levels[level + 1]->dist, rc);
-        else dist_allreduce(H, rc, L.R.nrows);
-    }
-    if (last) {
-        coarse_solve(H, rc, xc);
-    } else {
-        vcycle_rec(H, level + 1, rc, xc);
-        Level &N = *H.levels[level + 1];
-        if (N.dist.on) dist_allgather_rows(H, N.dist, xc);
-    }
-    spmv_add(s, L.P, xc, x, rows_of(D));                                // x += P xc
-    if (us.post) user_smooth(H, level, us.post, us.ctx, b, x, false);
-    else smooth_inplace(H, L.A, L.dinv_neg.p, L.roots, b, x, L.t0.p, D);     // post_smoother
-}
-
-void smoother_apply(Hierarchy &H, int level, const double *b, double *x) {
-    Level &L = *H.levels[level];
-    Level::Dist *D = dist_of(L);
-    smooth_inplace(H, L.A, L.dinv_neg.p, L.roots, b, x, L.t0.p, D);
-    if (D) dist_allgather_rows(H, *D, x);
-}
-
-void vcycle_apply(Hierarchy &H, int level, const double *b, double *x) {
-    vcycle_rec(H, level, b, x);
-    Level &L = *H.levels[level];
-    if (L.dist.on) dist_allgather_rows(H, L.dist, x);
-}
-
-int pcg_solve(Hierarchy &H, const double *b, double *x, double rel_tol, double abs_tol,
-              int max_iter, int squared_tol, int zero_guess, int *converged, double *hist) {
-    Level &L0 = *H.levels[0];
-    Level::Dist *D = dist_of(L0);
-    auto prec = [&](const double *r, double *z) { vcycle_rec(H, 0, r, z); };
-    PhaseTimer tm(H.stream);
-    struct Lap { PhaseTimer &t; ~Lap() { t.lap("TOTAL pcg_solve", 0); } } lap{tm};
-    const int it = pcg_loop(H, L0.A, prec, b, x, H.pcg_r.p, H.pcg_z.p, H.pcg_d.p, H.pcg_q.p, rel_tol,
-                            abs_tol, max_iter, squared_tol != 0, zero_guess != 0, converged, hist,
-                            H.scal.p, D);
-    if (D) dist_allgather_rows(H, *D, x);  // every rank returns the full solution
-    return it;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1416,14 +1065,8 @@ static void add_nullspace_level(Hierarchy &H) {
     N.A = std::move(L.Ac);
     N.theta = 0.0;
     N.nu_relax = 3;
-    N.roots = sas_poly_roots(3);
-    build_sell(s, N.A, H.params.opt);
-    N.dinv_neg.alloc((size_t)nc);
-    {
-        DBuf<double> tmp((size_t)nc);
-        build_dinv_neg(s, N.A, tmp.p, N.dinv_neg.p);
-        SA_HIP_CHECK(hipStreamSynchronize(s));
-    }
+    N.sm.roots = sas_poly_roots(3);
+    operator_data(s, N.A, H.params.opt, false, N.sm);
     N.P.nrows = nc;
     N.P.ncols = nact;
     N.P.nnz = nc;
@@ -1441,12 +1084,10 @@ static void add_nullspace_level(Hierarchy &H) {
     SA_HIP_CHECK(hipStreamSynchronize(s));
     N.P.lanes_per_row = 1;
     csr_transpose(s, N.P, N.R);
-    DCsr AP;
-    spgemm(s, N.A, N.P, nullptr, nullptr, 1.0, 0.0, AP);
-    spgemm(s, N.R, AP, nullptr, nullptr, 1.0, 0.0, N.Ac);
+    galerkin_general(s, N.A, N.P, N.R, N.Ac);
     N.rel.ND = nc;
     N.rel.nparts = nact;
-    N.x.alloc((size_t)nc); N.b.alloc((size_t)nc); N.r.alloc((size_t)nc); N.t0.alloc((size_t)nc);
+    N.x.alloc((size_t)nc); N.b.alloc((size_t)nc); N.r.alloc((size_t)nc); N.sm.tmp.alloc((size_t)nc);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1526,10 +1167,9 @@ Hierarchy *hierarchy_create(int n, const void *Arow, int rowptr_bits, const int 
         L0.elmat.nde = nde;
         L0.elmat.algebraic = p.algebraic;
     }
-    // Level-0 topology inputs that are device-resident stay there (device build of the AE tables)
-    constexpr bool host_topo = false;      // (host inputs take the host build; device inputs the device build)
+    // Level-0 topology inputs that are device-resident stay there (device build of the AE tables); host inputs take the host build
     DeviceInputs din;
-    const bool dev_inputs = !host_topo && is_device_ptr(elem_to_dof) && is_device_ptr(partitions[0]) &&
+    const bool dev_inputs = is_device_ptr(elem_to_dof) && is_device_ptr(partitions[0]) &&
                             (!bdr || is_device_ptr(bdr));
     Table e2d;
     hvec<signed char> bdr_h;
@@ -1595,10 +1235,8 @@ Hierarchy *hierarchy_create(int n, const void *Arow, int rowptr_bits, const int 
         tm0.lap("corrected null-space level", 0);
     }
     setup_coarse_solver(H);
-    const size_t nc = (size_t)coarsest_op(H).nrows;
-    H.c_b.alloc(nc);
-    H.c_x.alloc(nc);
-    H.pcg_r.alloc((size_t)n); H.pcg_z.alloc((size_t)n); H.pcg_d.alloc((size_t)n); H.pcg_q.alloc((size_t)n);
+    H.pcg.alloc((size_t)n);
+    H.pcg.sc = H.scal.p;
     SA_HIP_CHECK(hipStreamSynchronize(s));
     tm0.lap("coarse solver + vectors", 0);
     if (p.world > 1 && p.alltoallv) {
@@ -1617,13 +1255,11 @@ Hierarchy *hierarchy_create(int n, const void *Arow, int rowptr_bits, const int 
     return Hp.release();
 }
 
-// adapt_update_operators (amg/src/adapt.cpp:171-219): the matrix changed (same sparsity, same
-// topology): keep every interpolation (the eigenproblems are NOT solved again), refresh the
-// smoother diagonals, re-smooth P where nu_pro > 0, rebuild all Galerkin operators and the coarsest
-// solver.
+// adapt_update_operators (amg/src/adapt.cpp:171-219): the matrix changed (same sparsity, same topology): keep every
+// interpolation (the eigenproblems are NOT solved again), refresh every operator's solve data (operator_data), re-smooth P
+// where nu_pro > 0, rebuild all Galerkin operators and the coarsest solver.
 void hierarchy_update_operators(Hierarchy &H, const double *new_val) {
     hipStream_t s = H.stream;
-    const int nspec = H.params.num_coarsenings;
     Level &L0 = *H.levels[0];
     if (new_val && new_val != L0.A.val.p) {
         if (is_device_ptr(new_val)) {
@@ -1633,31 +1269,18 @@ void hierarchy_update_operators(Hierarchy &H, const double *new_val) {
             upload(L0.A.val.p, new_val, (size_t)L0.A.nnz, s);
         }
     }
-    for (int lev = 0; lev < nspec; ++lev) {
+    for (int lev = 0; lev < H.params.num_coarsenings; ++lev) {
         Level &L = *H.levels[lev];
-        build_sell(s, L.A, H.params.opt);
-        {
-            DBuf<double> tmp((size_t)L.A.nrows);
-            build_dinv_neg(s, L.A, tmp.p, L.dinv_neg.p);
-            build_dinv_codes(s, L.A, L.dinv_neg.p, H.params.opt);
-            SA_HIP_CHECK(hipStreamSynchronize(s));
-        }
+        operator_data(s, L.A, H.params.opt, true, L.sm);
         L.Ac = DCsr();
-        level_galerkin(H, lev, false);
+        level_galerkin(H, lev, false, s);
         if (lev + 1 < (int)H.levels.size()) H.levels[lev + 1]->A = std::move(L.Ac);
     }
     if (H.params.correct_nullspace) {   // the scaling_P level: same interpolation, new operators
         Level &N = *H.levels.back();
-        build_sell(s, N.A, H.params.opt);
-        DBuf<double> tmp((size_t)N.A.nrows);
-        build_dinv_neg(s, N.A, tmp.p, N.dinv_neg.p);
-        SA_HIP_CHECK(hipStreamSynchronize(s));
-        DCsr AP;
-        spgemm(s, N.A, N.P, nullptr, nullptr, 1.0, 0.0, AP);
-        N.Ac = DCsr();
-        spgemm(s, N.R, AP, nullptr, nullptr, 1.0, 0.0, N.Ac);
+        operator_data(s, N.A, H.params.opt, false, N.sm);
+        galerkin_general(s, N.A, N.P, N.R, N.Ac);
     }
-    H.c_L.release();
     setup_coarse_solver(H);
     SA_HIP_CHECK(hipStreamSynchronize(s));
 }

@@ -10,6 +10,7 @@
 #include <limits>
 
 #include "blockvec.h"
+#include "cycle.h"
 #include "lobpcg_host.h"
 #include "sparse.h"
 

@@ -40,7 +40,7 @@ void mis_svd(hipStream_t s, const DevRelations &rel, int num_mises, int max_ctot
 // P (ND x nc) and R = P^T from the MIS blocks (contrib_tent_insert_simple,
 // amg/src/contrib.cpp:170-194; explicit zeros are kept in the block pattern).
 void build_P_R(hipStream_t s, const DevRelations &rel, const Relations &hrel,
-               const std::vector<int> &h_k, const std::vector<int64_t> &h_u_off, const int *d_k,
+               const std::vector<int> &h_k, const int *d_k,
                const int *d_coloff, const int64_t *d_u_off, const double *U, DCsr &P, DCsr &R);
 
 // Coarse elements of the next level on the device: coarse elem_to_dof = AE_to_dof x pattern(P_tent) in

@@ -416,9 +416,8 @@ __global__ __launch_bounds__(256) void r_fill_kernel(int num_mises, const int *_
 }
 
 void build_P_R(hipStream_t s, const DevRelations &rel, const Relations &hrel,
-               const std::vector<int> &h_k, const std::vector<int64_t> &h_u_off, const int *d_k,
+               const std::vector<int> &h_k, const int *d_k,
                const int *d_coloff, const int64_t *d_u_off, const double *U, DCsr &P, DCsr &R) {
-    (void)h_u_off;
     const int ND = hrel.ND;
     int nc = 0;
     int64_t nnz = 0;

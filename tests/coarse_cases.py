@@ -22,7 +22,7 @@ from scipy.sparse.csgraph import connected_components
 BT_MAX_BLOCK = 12288      # blocktri.hip
 BT_MIN_BLOCK = 256
 DNB = 64                  # dense.hip: columns per step of the block Gauss-Jordan elimination
-DENSE_MAX = 16384         # hierarchy.hip: the largest operator that gets one explicit dense inverse
+DENSE_MAX = 16384         # cycle.hip: the largest operator that gets one explicit dense inverse
 
 
 # ---------------------------------------------------------------------------------------------------------------------

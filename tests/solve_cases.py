@@ -4,7 +4,7 @@ checks them on the host.
 
 The tests vary what the C ABI exposes and every other test leaves at its default: `nu_relax` per level (the SAS polynomial of
 level l has 3 nu_l + 1 roots, so nu = 1, 2, 3, 4 gives the degrees 4, 7, 10, 13 -- both parities, and with them both
-arms of the two ping-pong loops in csrc/hierarchy.hip), and `squared_tol`, `abs_tol`, `max_iter`, `zero_guess` of the
+arms of the two ping-pong loops in csrc/cycle.hip), and `squared_tol`, `abs_tol`, `max_iter`, `zero_guess` of the
 outer PCG.
 
     tiles   2 730 rows   constant coefficient: ten staged 256-row tiles and the folded partial one, pair-coded slices,

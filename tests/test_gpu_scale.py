@@ -84,7 +84,7 @@ def test_scale_golden(name, eigensolver):
 def test_scale_golden_with_single_matrices_on_the_dense_path():
     """A few matrices of a chunk leave the few-eigenpairs path (no certificate, a non-positive pivot, no
     convergence ...): they alone are redone by the dense path and the chunk's results are put together again
-    (csrc/hierarchy.hip, post()).  saamge_amd_options.eig_force_fallback = 50 marks every 50th agglomerate: 10 of the 512 level-0
+    (csrc/hierarchy.hip, eig_redo_bad).  saamge_amd_options.eig_force_fallback = 50 marks every 50th agglomerate: 10 of the 512 level-0
     agglomerates go alone (in runs of one; with 1 GiB chunks also across chunk boundaries), the one marked
     agglomerate of the 8 on level 1 exceeds the 10 % limit and takes the whole level with it."""
     from saamge_amd import capi

@@ -11,6 +11,8 @@ by the squared relative rule.  Here:
      coarsest PCG under an odd-degree polynomial, update_operators, and the refusal of nu_relax = 0.
   C  the stopping rules of pcg_loop, each threshold derived from the oracle's history and a factor >= 10 from every entry.
   D  `hist` holds max_iter + 1 doubles and not one more.
+  E  pcg, the stationary iteration, the smoother and update_operators on ONE hierarchy: the second pcg repeats the first
+     bit for bit.
 
 Hierarchies are built once per (problem, degrees) and closed when the module is done."""
 import ctypes as C
@@ -371,3 +373,30 @@ def test_hist_gets_max_iter_plus_one_doubles_and_no_more(max_iter):
     assert it.value == itr == max_iter and bool(conv.value) == convr and not convr
     assert np.allclose(hist[:max_iter + 1], histr[:max_iter + 1], rtol=HIST_RTOL, atol=0.0)
     assert sc.rel_dev(x, xr) <= 1e-9      # (the one step at max_iter = 0 is taken, as in the oracle)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# E. the calls of one hierarchy share its workspaces
+# ---------------------------------------------------------------------------------------------------------------------
+def test_calls_share_a_hierarchys_workspaces_without_disturbing_each_other():
+    """skew2 with coarse_solver = 2, so that the inner PCG runs inside every V-cycle (its vectors, and its scalars beside the
+    outer solve's): pcg -> x1; the stationary iteration (the outer PCG's r and z), the smoother on level 0 (its scratch
+    vector), update_operators with the values unchanged (operator data and coarsest solver rebuilt); pcg again -> x2.
+    x1 and x2, the two histories and the iteration counts are equal bit for bit."""
+    prob = sc.problem("skew2")
+    h = _build("skew2", (3,), coarse_solver=2)
+    try:
+        assert h.coarse_solver_info()["kind"] == 2
+        x1, it1, conv1, hist1 = h.pcg(prob.b, rel_tol=sc.PCG_REL_TOL)
+        assert conv1 and it1 > 0 and h.level_info(0)["coarse_iters"] > 0
+        b, x0 = sc.smoother_data(prob.ND)
+        assert np.all(np.isfinite(h.vcycle_iterative(prob.b, x0.copy())))
+        assert np.all(np.isfinite(h.smoother(0, b, x0.copy())))
+        h.update_operators(prob.A.tocsr().data.copy())
+        x2, it2, conv2, hist2 = h.pcg(prob.b, rel_tol=sc.PCG_REL_TOL)
+        print("pcg before / after: %d / %d iterations, %d history entries" % (it1, it2, len(hist1)))
+        assert it2 == it1 and conv2 == conv1
+        assert x2.tobytes() == x1.tobytes()
+        assert hist2.tobytes() == hist1.tobytes()
+    finally:
+        h.close()

@@ -4,7 +4,7 @@
 # Every rocprofv3 pass runs under a timeout as a GUARD only.  Until round 3 counter passes aborted at process exit
 # ("stream_stack.cpp: Check failed", then a hang in the signal handler): the library's static buffers were destroyed
 # after main() and called hipEventRecord into a runtime that was already torn down.  Round 4: no static object of the
-# library owns device memory through a destructor any more (csrc/eig.hip arena(), assemble.hip, hierarchy.hip).
+# library owns device memory through a destructor any more (csrc/eig.hip arena(), assemble.hip, hierarchy.hip scratch_pool(); the solve phase, csrc/cycle.hip, has no statics).
 set -o pipefail
 export TMPDIR=/tmp
 R=$PWD
