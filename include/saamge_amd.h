@@ -934,6 +934,27 @@ int saamge_amd_blockvec_gram(int n, int p, const double *S, long long lds, int q
 int saamge_amd_blockvec_combine(int n, int p, const double *S, long long lds, int q, const double *C_host, double *Y,
                                 long long ldy, int accumulate);
 
+/* ---- block solves: k columns per call ----
+ * saamge_amd_spmv, _smoother, _vcycle and _pcg on k columns at once: the matrix data of every level is read once for the
+ * columns of a launch (up to 8; more run in chunks) instead of once per column.  Blocks are column-major with a leading
+ * dimension, host or device pointers exactly as the single-vector calls take them; rows past the row count are padding
+ * and keep what they hold.  THE CONTRACT: column j of every output, iters[j], converged[j] and column j's history are bit
+ * for bit what the single-vector call returns when it is given column j alone on the same hierarchy and options (the block
+ * kernels keep every row's order of additions).  hist: k x (max_iter + 1), column j's history at hist + j (max_iter + 1),
+ * entries 0 .. its own last step written and the rest left as they are; may be NULL, like converged.  A caller's smoother
+ * or coarsest solver is called once per column; the dense and the block-tridiagonal coarsest solves run column by column.
+ * Refused, each by name, before any HIP call and before anything is written: k < 1 or k > 64; a NULL block; a leading
+ * dimension below the row count; X overlapping B (Y overlapping X for spmv_block); a row-partitioned hierarchy.
+ * Work memory: the cycle's vectors for min(k, 8) columns, taken from the pool at the hierarchy's first block call, grown
+ * only by a wider call, returned with the hierarchy (saamge_amd_memory_stats shows it). */
+int saamge_amd_spmv_block(int nrows, int ncols, const int *rowptr, const int *col, const double *val, int k, const double *X,
+                          long long ldx, double *Y, long long ldy);      /* honours spmv_sell like saamge_amd_spmv */
+int saamge_amd_smoother_block(saamge_amd_hierarchy *h, int level, int k, const double *B, long long ldb, double *X, long long ldx);
+int saamge_amd_vcycle_block(saamge_amd_hierarchy *h, int k, const double *B, long long ldb, double *X, long long ldx,
+                            int iterative_mode);
+int saamge_amd_pcg_block(saamge_amd_hierarchy *h, int k, const double *B, long long ldb, double *X, long long ldx, double rel_tol,
+                         double abs_tol, int max_iter, int squared_tol, int zero_guess, int *iters, int *converged, double *hist);
+
 #ifdef __cplusplus
 }
 #endif

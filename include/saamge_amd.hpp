@@ -15,6 +15,7 @@
 #ifndef SAAMGE_AMD_HPP
 #define SAAMGE_AMD_HPP
 
+#include <limits>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -192,6 +193,36 @@ inline LobpcgResult lobpcg(ml_data_t *h, const LobpcgOptions &o, double *evecs, 
         throw std::runtime_error(saamge_amd_last_error());
     r.converged = conv != 0;
     r.hist.resize((size_t)(r.iters + 1) * nev);
+    return r;
+}
+
+// == block solves: k columns per call (saamge_amd_*_block) ==
+// Blocks are column-major with a leading dimension, host or device.  Column j of every result, its iteration count, flag
+// and history are bit for bit what the single-vector call returns for column j alone.
+inline void spmv_block(int nrows, int ncols, const int *rowptr, const int *col, const double *val, int k, const double *X,
+                       long long ldx, double *Y, long long ldy) {
+    if (saamge_amd_spmv_block(nrows, ncols, rowptr, col, val, k, X, ldx, Y, ldy)) throw std::runtime_error(saamge_amd_last_error());
+}
+inline void smoother_block(ml_data_t *h, int level, int k, const double *B, long long ldb, double *X, long long ldx) {
+    if (saamge_amd_smoother_block(h, level, k, B, ldb, X, ldx)) throw std::runtime_error(saamge_amd_last_error());
+}
+inline void vcycle_block(ml_data_t *h, int k, const double *B, long long ldb, double *X, long long ldx, bool iterative_mode = false) {
+    if (saamge_amd_vcycle_block(h, k, B, ldb, X, ldx, iterative_mode ? 1 : 0)) throw std::runtime_error(saamge_amd_last_error());
+}
+struct PcgBlockResult {
+    std::vector<int> iters, converged;      // k each
+    std::vector<double> hist;               // k x (max_iter + 1), column j first; NaN past column j's own last step
+};
+inline PcgBlockResult pcg_block(ml_data_t *h, int k, const double *B, long long ldb, double *X, long long ldx, double rel_tol,
+                                double abs_tol, int max_iter, bool squared_tol = true, bool zero_guess = true) {
+    PcgBlockResult r;
+    const size_t kk = k > 0 ? (size_t)k : 0;
+    r.iters.assign(kk, 0);
+    r.converged.assign(kk, 0);
+    r.hist.assign(kk * ((size_t)(max_iter > 0 ? max_iter : 0) + 1), std::numeric_limits<double>::quiet_NaN());
+    if (saamge_amd_pcg_block(h, k, B, ldb, X, ldx, rel_tol, abs_tol, max_iter, squared_tol ? 1 : 0, zero_guess ? 1 : 0, r.iters.data(),
+                             r.converged.data(), r.hist.data()))
+        throw std::runtime_error(saamge_amd_last_error());
     return r;
 }
 

@@ -51,6 +51,7 @@ SYMBOLS = [
     "saamge_amd_mesh_refine", "saamge_amd_mesh_refine_arrays", "saamge_amd_mesh_refine_get", "saamge_amd_mesh_refine_level_info",
     "saamge_amd_mesh_refine_interp_arrays", "saamge_amd_mesh_refine_interp_get", "saamge_amd_mesh_refine_free",
     "saamge_amd_lobpcg_options_default", "saamge_amd_lobpcg", "saamge_amd_blockvec_gram", "saamge_amd_blockvec_combine",
+    "saamge_amd_spmv_block", "saamge_amd_smoother_block", "saamge_amd_vcycle_block", "saamge_amd_pcg_block",
 ]
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_longlong))
@@ -509,6 +510,40 @@ class Hierarchy(_Handle):
                                      C.c_int(int(zero_guess)), C.byref(it), C.byref(conv), _ptr(hist)))
         return x, it.value, bool(conv.value), hist[:it.value + 1].copy()
 
+    # ---- block solves: k columns per call.  A block is column-major with a leading dimension: a C-contiguous numpy array of
+    # shape (k, ld) whose row j is column j (ld >= n; the entries past n are padding and stay untouched), or a device
+    # pointer / tensor with `ld` given.  Column j of every result is bit for bit the single-vector call on column j.
+    @staticmethod
+    def _ld(a, ld):
+        return int(ld) if ld is not None else int(a.shape[1])
+
+    def smoother_block(self, level, B, X, k=None, ldb=None, ldx=None):
+        k = int(k if k is not None else B.shape[0])
+        _check(load().saamge_amd_smoother_block(self.h, C.c_int(level), C.c_int(k), _ptr(B), C.c_longlong(self._ld(B, ldb)),
+                                                _ptr(X), C.c_longlong(self._ld(X, ldx))))
+        return X
+
+    def vcycle_block(self, B, X, iterative_mode=False, k=None, ldb=None, ldx=None):
+        k = int(k if k is not None else B.shape[0])
+        _check(load().saamge_amd_vcycle_block(self.h, C.c_int(k), _ptr(B), C.c_longlong(self._ld(B, ldb)), _ptr(X),
+                                              C.c_longlong(self._ld(X, ldx)), C.c_int(int(iterative_mode))))
+        return X
+
+    def pcg_block(self, B, X, rel_tol=1e-6, abs_tol=0.0, max_iter=1000, squared_tol=True, zero_guess=True, k=None, ldb=None,
+                  ldx=None, hist=None, iters=None, converged=None):
+        """-> X, iters (k,), converged (k,), hist (k, max_iter + 1): row j is column j's history, written up to its own last
+        step (the rest keeps what `hist` held: NaN in a new array)."""
+        k = int(k if k is not None else B.shape[0])
+        iters = np.zeros(max(k, 1), dtype=np.int32) if iters is None else iters
+        converged = np.zeros(max(k, 1), dtype=np.int32) if converged is None else converged
+        if hist is None:
+            hist = np.full((max(k, 1), max(max_iter, 0) + 1), np.nan)
+        _check(load().saamge_amd_pcg_block(self.h, C.c_int(k), _ptr(B), C.c_longlong(self._ld(B, ldb)), _ptr(X),
+                                           C.c_longlong(self._ld(X, ldx)), C.c_double(rel_tol), C.c_double(abs_tol),
+                                           C.c_int(max_iter), C.c_int(int(squared_tol)), C.c_int(int(zero_guess)), _ptr(iters),
+                                           _ptr(converged), _ptr(hist)))
+        return X, iters, converged, hist
+
     def lobpcg(self, nev, block=0, M=None, x0=None, tol=1e-8, max_iter=100, constrain_essential=True, seed=0, evecs=None):
         """The lowest nev pairs of A x = lambda M x (saamge_amd_lobpcg; the definition: saamge_amd.lobpcg_model).  M: None,
         a scipy matrix, or (rowptr, col, val) with 64-bit offsets (numpy arrays or device pointers / tensors); x0: n x nb
@@ -670,6 +705,20 @@ def spmv(A, x):
                                   _ptr(np.ascontiguousarray(A.data, dtype=np.float64)),
                                   _ptr(np.ascontiguousarray(x, dtype=np.float64)), _ptr(y)))
     return y
+
+
+def spmv_block(A, X, Y, k=None, ldx=None, ldy=None):
+    """Y[j] = A X[j] for the k columns of a block (saamge_amd_spmv_block; honours spmv_sell like spmv).  X: (k, ldx), Y: (k, ldy)
+    C-contiguous numpy arrays (row j = column j of the column-major block), or device pointers with the leading dimensions."""
+    A = A.tocsr()
+    k = int(k if k is not None else X.shape[0])
+    _check(load().saamge_amd_spmv_block(C.c_int(A.shape[0]), C.c_int(A.shape[1]),
+                                        _ptr(np.ascontiguousarray(A.indptr, dtype=np.int32)),
+                                        _ptr(np.ascontiguousarray(A.indices, dtype=np.int32)),
+                                        _ptr(np.ascontiguousarray(A.data, dtype=np.float64)), C.c_int(k), _ptr(X),
+                                        C.c_longlong(int(ldx) if ldx is not None else int(X.shape[1])), _ptr(Y),
+                                        C.c_longlong(int(ldy) if ldy is not None else int(Y.shape[1]))))
+    return Y
 
 
 def lower_eigens_batched(mats, diags, vl, vu):

@@ -1748,4 +1748,99 @@ int saamge_amd_blockvec_combine(int n, int p, const double *S, long long lds, in
     SA_API_END
 }
 
+// ---- block solves: k columns per call (cycle.hip) ---------------------------------------------------------
+// What every block call refuses, before any HIP call and before anything is written.
+static void require_blocks(const char *who, int k, long long nb, const double *B, long long ldb, long long nx, const double *X,
+                           long long ldx) {
+    const std::string w(who);
+    SA_REQUIRE(k >= 1 && k <= 64, w + ": k must lie in 1 .. 64");
+    SA_REQUIRE(B && X, w + ": null block");
+    SA_REQUIRE(ldb >= nb && ldx >= nx, w + ": a leading dimension is below the row count");
+    const double *Be = B + block_extent((int)nb, k, ldb), *Xe = X + block_extent((int)nx, k, ldx);
+    SA_REQUIRE(Xe <= B || Be <= X, w + ": X overlaps B");
+}
+static Hierarchy &block_hierarchy(const char *who, saamge_amd_hierarchy *h) {
+    SA_REQUIRE(h && h->H, std::string(who) + ": null hierarchy");
+    for (auto &L : h->H->levels)
+        SA_REQUIRE(!L->dist.on, std::string(who) + ": the hierarchy is row-partitioned over several ranks (block solves are not available)");
+    return *h->H;
+}
+// the blocks of a call on the device: a host block is staged whole (rows past the row count come home as they went)
+struct BlockArgs {
+    VecIn vb;
+    VecOut vx;
+    std::vector<double *> b, x;
+    BlockArgs(int n, int k, const double *B, long long ldb, double *X, long long ldx, bool load, hipStream_t s)
+        : vb(B, block_extent(n, k, ldb), s), vx(X, block_extent(n, k, ldx), s, load || ldx > n),
+          b(block_columns(vb.p, (long)ldb, k)), x(block_columns(vx.p, (long)ldx, k)) {}
+};
+
+int saamge_amd_spmv_block(int nrows, int ncols, const int *rowptr, const int *col, const double *val, int k, const double *X,
+                          long long ldx, double *Y, long long ldy) {
+    SA_API_BEGIN
+    SA_REQUIRE(rowptr && col && val && nrows >= 0 && ncols >= 0, "spmv_block: bad argument");
+    require_blocks("spmv_block", k, ncols, X, ldx, nrows, Y, ldy);
+    const Options opt = g_default_options;
+    validate_options(opt);
+    hipStream_t s = 0;
+    set_thread_stream(s);
+    DCsr A;
+    A.nrows = nrows;
+    A.ncols = ncols;
+    import_rowptr(A.rowptr, rowptr, 32, (size_t)nrows + 1, s);
+    A.nnz = read_one(A.rowptr.p + nrows, s);
+    A.col = DevIn<int>(col, (size_t)A.nnz, s).take();
+    A.val = DevIn<double>(val, (size_t)A.nnz, s).take();
+    A.lanes_per_row = pick_lanes_per_row(A.nnz, nrows > 0 ? nrows : 1);
+    if (nrows == ncols && opt.spmv_sell) build_sell(s, A, opt);      // (as saamge_amd_spmv)
+    VecIn vx(X, block_extent(ncols, k, ldx), s);
+    VecOut vy(Y, block_extent(nrows, k, ldy), s, ldy > nrows);
+    for (int c = 0; c < block_num_chunks(k); ++c) {
+        const BlockChunk ch = block_chunk(k, c);
+        spmv_block(s, A, Cols(vx.p + (size_t)ch.first * ldx, (long)ldx, ch.count), Cols(vy.p + (size_t)ch.first * ldy, (long)ldy, ch.count));
+    }
+    vy.finish();
+    SA_API_END
+}
+
+int saamge_amd_smoother_block(saamge_amd_hierarchy *h, int level, int k, const double *B, long long ldb, double *X, long long ldx) {
+    SA_API_BEGIN
+    Hierarchy &H = block_hierarchy("smoother_block", h);
+    SA_REQUIRE(level >= 0 && level < (int)H.levels.size(), "smoother_block: bad level");
+    const int n = H.levels[level]->A.nrows;
+    require_blocks("smoother_block", k, n, B, ldb, n, X, ldx);
+    require_device(H);
+    BlockArgs a(n, k, B, ldb, X, ldx, true, H.stream);
+    smoother_apply_block(H, level, k, a.b.data(), a.x.data());
+    a.vx.finish();
+    SA_API_END
+}
+
+int saamge_amd_vcycle_block(saamge_amd_hierarchy *h, int k, const double *B, long long ldb, double *X, long long ldx, int iterative_mode) {
+    SA_API_BEGIN
+    Hierarchy &H = block_hierarchy("vcycle_block", h);
+    const int n = H.levels[0]->A.nrows;
+    require_blocks("vcycle_block", k, n, B, ldb, n, X, ldx);
+    require_device(H);
+    BlockArgs a(n, k, B, ldb, X, ldx, iterative_mode != 0, H.stream);
+    if (iterative_mode) vcycle_iterate_block(H, k, a.b.data(), a.x.data());
+    else vcycle_apply_block(H, k, a.b.data(), a.x.data());
+    a.vx.finish();
+    SA_API_END
+}
+
+int saamge_amd_pcg_block(saamge_amd_hierarchy *h, int k, const double *B, long long ldb, double *X, long long ldx, double rel_tol,
+                         double abs_tol, int max_iter, int squared_tol, int zero_guess, int *iters, int *converged, double *hist) {
+    SA_API_BEGIN
+    Hierarchy &H = block_hierarchy("pcg_block", h);
+    const int n = H.levels[0]->A.nrows;
+    require_blocks("pcg_block", k, n, B, ldb, n, X, ldx);
+    SA_REQUIRE(iters, "pcg_block: null argument: iters");
+    require_device(H);
+    BlockArgs a(n, k, B, ldb, X, ldx, !zero_guess, H.stream);
+    pcg_solve_block(H, k, a.b.data(), a.x.data(), rel_tol, abs_tol, max_iter, squared_tol, zero_guess, iters, converged, hist);
+    a.vx.finish();
+    SA_API_END
+}
+
 }  // extern "C"

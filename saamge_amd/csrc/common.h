@@ -221,7 +221,9 @@ struct Profiler {
         }
         SA_HIP_CHECK(hipEventRecord(e0, s));
     }
-    void end(hipStream_t s, const char *name, double bytes, double flops, double fmt_bytes = 0.0) {
+    // count: the applications this one timing covers (a block launch on k columns is listed as k applications under the
+    // single-vector label, with the bytes and flops of all of them)
+    void end(hipStream_t s, const char *name, double bytes, double flops, double fmt_bytes = 0.0, int count = 1) {
         if (!enabled) return;
         SA_HIP_CHECK(hipEventRecord(e1, s));
         SA_HIP_CHECK(hipEventSynchronize(e1));
@@ -229,7 +231,7 @@ struct Profiler {
         SA_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
         KernelStat &k = level_tag > 0 ? get(std::string(name) + "@L" + std::to_string(level_tag)) : get(name);
         k.ms += ms;
-        k.launches += 1;
+        k.launches += count;
         k.bytes += bytes;
         k.flops += flops;
         k.fmt_bytes += fmt_bytes > 0.0 ? fmt_bytes : bytes;

@@ -38,6 +38,19 @@ struct CoarseSolver {
     void *user_ctx = nullptr;
 };
 
+// Workspace of the block solve phase (Hierarchy::block): `width` columns of every vector the single-vector cycle keeps once.
+// Empty until the first block call, grown only when a wider call arrives (at most BLOCK_MAX columns: wider calls run in
+// chunks), released with the hierarchy.
+struct BlockWork {
+    int width = 0;
+    struct Vecs { DBuf<double> b, x, r, tmp; };      // b, x: the levels below the finest and the coarsest operator
+    std::vector<Vecs> lv;
+    Vecs coarse;                                     // coarse.tmp: ping-pong partner of the inner PCG's smoother
+    struct Pcg { DBuf<double> r, z, d, q; double *sc = nullptr; };
+    Pcg pcg, cpcg;                                   // the outer solve and the coarsest solver's inner PCG
+    DBuf<double> scal, partials;                     // 4 scalars per column and PCG; 1024 partials per column
+};
+
 // smpr_sas_poly_roots (amg/src/smpr.cpp:282-306)
 std::vector<double> sas_poly_roots(int nu);
 // What an operator needs before it can be smoothed (smpr_init_poly_data, amg/src/smpr.cpp:359-423): its SELL-64 copy for the SpMV
@@ -60,5 +73,17 @@ void smoother_apply(Hierarchy &h, int level, const double *b, double *x);
 // Returns iterations; hist (host, may be null) receives (B r_k, r_k), k = 0..iters.
 int pcg_solve(Hierarchy &h, const double *b, double *x, double rel_tol, double abs_tol,
               int max_iter, int squared_tol, int zero_guess, int *converged, double *hist);
+
+// ---- the same on k >= 1 columns (device pointers, one per column; any k: more than BLOCK_MAX columns run in chunks) ----------
+// Column j of every result, its iteration count, flag and history are bit for bit what the call above returns for column j
+// alone.  Row-partitioned hierarchies are refused.
+void smoother_apply_block(Hierarchy &h, int level, int k, const double *const *b, double *const *x);
+void vcycle_apply_block(Hierarchy &h, int k, const double *const *b, double *const *x);
+void vcycle_iterate_block(Hierarchy &h, int k, const double *const *b, double *const *x);
+// iters, converged (may be null): k ints; hist (host, may be null): column j's history at hist + j (max_iter + 1)
+void pcg_solve_block(Hierarchy &h, int k, const double *const *b, double *const *x, double rel_tol, double abs_tol, int max_iter,
+                     int squared_tol, int zero_guess, int *iters, int *converged, double *hist);
+// the columns c[0 .. k) (null: 0 .. k - 1) of a column-major block as a pointer list
+std::vector<double *> block_columns(const double *base, long ld, int k, const int *c = nullptr);
 
 }  // namespace saamge_amd

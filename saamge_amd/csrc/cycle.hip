@@ -268,4 +268,235 @@ int pcg_solve(Hierarchy &H, const double *b, double *x, double rel_tol, double a
     return it;
 }
 
+// ---- the block solve phase ----------------------------------------------------------------------------
+// The functions above once more on a list of at most BLOCK_MAX columns: the same steps in the same order, each step one
+// block member of the SpMV family (sparse.h) in place of the single one, so that every column keeps its bits.  They stand
+// beside the single-vector functions and do not replace them: those carry the row-partitioned solve (halo_then, the
+// reductions over ranks, own-row offsets) through every step, which has no block form, and their launches are left as they
+// are.  A list of one column runs the single-vector kernels (every block member does that for k = 1).
+static void require_block(Hierarchy &H, int k) {
+    SA_REQUIRE(k >= 1, "block solve: k must be positive");
+    for (auto &L : H.levels)
+        SA_REQUIRE(!L->dist.on, "block solves are not available on a row-partitioned hierarchy");
+    BlockWork &W = H.block;
+    const size_t w = (size_t)std::min(k, BLOCK_MAX);
+    if ((int)w <= W.width) return;
+    const size_t nl = H.levels.size();
+    W.lv.resize(nl);
+    for (size_t l = 0; l < nl; ++l) {
+        const size_t n = (size_t)H.levels[l]->A.nrows;
+        if (l > 0) { W.lv[l].b.alloc(n * w); W.lv[l].x.alloc(n * w); }
+        W.lv[l].r.alloc(n * w);
+        W.lv[l].tmp.alloc(n * w);
+    }
+    const size_t nc = (size_t)H.levels.back()->Ac.nrows, n0 = (size_t)H.levels[0]->A.nrows;
+    W.coarse.b.alloc(nc * w);
+    W.coarse.x.alloc(nc * w);
+    W.coarse.tmp.alloc(nc * w);
+    for (DBuf<double> *v : {&W.pcg.r, &W.pcg.z, &W.pcg.d, &W.pcg.q}) v->alloc(n0 * w);
+    for (DBuf<double> *v : {&W.cpcg.r, &W.cpcg.z, &W.cpcg.d, &W.cpcg.q}) v->alloc(nc * w);
+    W.scal.alloc(2 * 4 * BLOCK_MAX);
+    W.partials.alloc(1024 * BLOCK_MAX);
+    W.pcg.sc = W.scal.p;
+    W.cpcg.sc = W.scal.p + 4 * BLOCK_MAX;
+    W.width = (int)w;
+}
+static Cols work_cols(const DBuf<double> &v, int n, int k) { return Cols(v.p, n, k); }
+
+static void smooth_from_zero_block(Hierarchy &H, const DCsr &A, const Smoother &sm, const Cols &tmp, const Cols &b, const Cols &x) {
+    const double *dinv = sm.dinv_neg.p;
+    const int deg = (int)sm.roots.size();
+    const Cols *cur = ((deg - 1) % 2 == 0) ? &x : &tmp;
+    const Cols *oth = (cur == &x) ? &tmp : &x;
+    smooth_first_block(H.stream, A.nrows, dinv, b, *cur, 1.0 / sm.roots[0]);
+    for (int i = 1; i < deg; ++i) {
+        smooth_step_block(H.stream, A, dinv, b, *cur, *oth, 1.0 / sm.roots[i]);
+        std::swap(cur, oth);
+    }
+}
+static void smooth_inplace_block(Hierarchy &H, const DCsr &A, const Smoother &sm, const Cols &tmp, const Cols &b, const Cols &x) {
+    const double *dinv = sm.dinv_neg.p;
+    const int deg = (int)sm.roots.size();
+    const Cols *cur = &x, *oth = &tmp;
+    for (int i = 0; i < deg; ++i) {
+        smooth_step_block(H.stream, A, dinv, b, *cur, *oth, 1.0 / sm.roots[i]);
+        std::swap(cur, oth);
+    }
+    if (cur != &x) vec_copy_block(H.stream, A.nrows, *cur, x);
+}
+
+// pcg_loop on the columns of b / x.  All columns still in the loop are at the same step i; a column that meets one of
+// pcg_loop's exits leaves the list at exactly that step, with pcg_loop's return value and flag.  The scalars of column j are
+// W.sc[4 j ..]; the host reads all of them back in one copy per step.  hist: column j's history at hist[j] (or null).
+static void pcg_loop_block(Hierarchy &H, const DCsr &A, const std::function<void(const Cols &, const Cols &)> &prec, const Cols &b,
+                           const Cols &x, BlockWork::Pcg &W, double rel_tol, double abs_tol, int max_iter, bool squared,
+                           bool zero_guess, int *iters, int *converged, double *const *hist) {
+    hipStream_t s = H.stream;
+    const int n = A.nrows, k = b.k;
+    const Cols R = work_cols(W.r, n, k), Z = work_cols(W.z, n, k), Dd = work_cols(W.d, n, k), Q = work_cols(W.q, n, k);
+    const Cols SC(W.sc, 4, k);
+    double *partials = H.block.partials.p;
+    std::vector<int> act(k);
+    for (int j = 0; j < k; ++j) act[j] = j;
+    auto pick = [&](const Cols &c) {
+        Cols r;
+        r.k = (int)act.size();
+        for (int j = 0; j < r.k; ++j) r.p[j] = c.p[act[j]];
+        return r;
+    };
+    double sc[4 * BLOCK_MAX], r0[BLOCK_MAX];
+    // leave(keep): the columns for which keep(j) is false leave the list
+    auto leave = [&](const std::function<bool(int)> &keep) {
+        std::vector<int> rest;
+        for (int j : act) if (keep(j)) rest.push_back(j);
+        act.swap(rest);
+    };
+    if (zero_guess) {
+        vec_zero_block(s, n, x);
+        vec_copy_block(s, n, b, R);
+    } else {
+        spmv_residual_block(s, A, x, b, R);
+    }
+    prec(R, Z);
+    vec_copy_block(s, n, Z, Dd);
+    dot_block(s, n, Dd, R, partials, SC, 0);
+    read_back(sc, (const double *)W.sc, (size_t)4 * k, s);
+    leave([&](int j) {
+        const double nom0 = sc[4 * j];
+        if (hist) hist[j][0] = nom0;
+        r0[j] = squared ? std::max(nom0 * rel_tol * rel_tol, abs_tol * abs_tol) : std::max(nom0 * rel_tol, abs_tol);
+        iters[j] = 0;
+        if (converged) converged[j] = nom0 <= r0[j] ? 1 : 0;
+        return !(nom0 <= r0[j]);
+    });
+    if (act.empty()) return;
+    spmv_block(s, A, pick(Dd), pick(Q));
+    dot_block(s, n, pick(Q), pick(Dd), partials, pick(SC), 1);
+    read_back(sc, (const double *)W.sc, (size_t)4 * k, s);
+    leave([&](int j) { return !(sc[4 * j + 1] == 0.0); });
+    int i = 1;
+    while (!act.empty()) {
+        pcg_update_xr_block(s, n, pick(SC), pick(x), pick(R), pick(Dd), pick(Q));
+        prec(pick(R), pick(Z));
+        dot_block(s, n, pick(R), pick(Z), partials, pick(SC), 2);
+        read_back(sc, (const double *)W.sc, (size_t)4 * k, s);
+        leave([&](int j) {
+            const double betanom = sc[4 * j + 2];
+            if (hist && i <= max_iter) hist[j][i] = betanom;
+            if (betanom < r0[j]) {
+                if (converged) converged[j] = 1;
+                iters[j] = i;
+                return false;
+            }
+            return true;
+        });
+        if (++i > max_iter) {
+            for (int j : act) iters[j] = max_iter;
+            break;
+        }
+        if (act.empty()) break;
+        pcg_update_d_block(s, n, pick(SC), pick(Dd), pick(Z));
+        spmv_block(s, A, pick(Dd), pick(Q));
+        dot_block(s, n, pick(Dd), pick(Q), partials, pick(SC), 1);
+        pcg_shift_nom_block(s, pick(SC));
+    }
+}
+
+// The coarsest solve of a block.  The inner PCG (kind 2) is the block loop; the dense inverse with its refinement step
+// (kind 1), the block-tridiagonal solve (kind 3) and a caller's solver run column by column through coarse_solve.
+static void coarse_solve_block(Hierarchy &H, const Cols &rc, const Cols &xc) {
+    const DCsr &Ac = H.levels.back()->Ac;
+    CoarseSolver &C = H.coarse;
+    if (Ac.nrows == 0) return;
+    if (C.user_solve || C.kind != 2) {
+        for (int j = 0; j < rc.k; ++j) coarse_solve(H, rc.p[j], xc.p[j]);
+        return;
+    }
+    const Cols tmp = work_cols(H.block.coarse.tmp, Ac.nrows, rc.k);
+    auto prec = [&](const Cols &r, const Cols &z) {
+        Cols t = tmp;
+        t.k = r.k;
+        smooth_from_zero_block(H, Ac, C.sm, t, r, z);
+    };
+    int its[BLOCK_MAX], conv[BLOCK_MAX];
+    pcg_loop_block(H, Ac, prec, rc, xc, H.block.cpcg, H.params.coarse_rtol, 0.0, H.params.coarse_max_iter, false, true, its, conv,
+                   nullptr);
+    C.last_iters = its[rc.k - 1];
+}
+
+static void vcycle_rec_block(Hierarchy &H, int level, const Cols &b, const Cols &x) {
+    Level &L = *H.levels[level];
+    hipStream_t s = H.stream;
+    BlockWork &W = H.block;
+    const int k = b.k, n = L.A.nrows;
+    const bool last = (level + 1 == (int)H.levels.size());
+    const Hierarchy::UserSmoother us = level < (int)H.user_smoothers.size() ? H.user_smoothers[level] : Hierarchy::UserSmoother();
+    const Cols tmp = work_cols(W.lv[level].tmp, n, k), res = work_cols(W.lv[level].r, n, k);
+    if (us.pre) for (int j = 0; j < k; ++j) user_smooth(H, level, us.pre, us.ctx, b.p[j], x.p[j], true);      // (a plug: per column)
+    else smooth_from_zero_block(H, L.A, L.sm, tmp, b, x);
+    spmv_residual_block(s, L.A, x, b, res);
+    const int nc = L.R.nrows;
+    const Cols rc = work_cols(last ? W.coarse.b : W.lv[level + 1].b, nc, k), xc = work_cols(last ? W.coarse.x : W.lv[level + 1].x, nc, k);
+    spmv_block(s, L.R, res, rc);
+    if (last) coarse_solve_block(H, rc, xc);
+    else vcycle_rec_block(H, level + 1, rc, xc);
+    spmv_add_block(s, L.P, xc, x);
+    if (us.post) for (int j = 0; j < k; ++j) user_smooth(H, level, us.post, us.ctx, b.p[j], x.p[j], false);
+    else smooth_inplace_block(H, L.A, L.sm, tmp, b, x);
+}
+
+std::vector<double *> block_columns(const double *base, long ld, int k, const int *c) {
+    std::vector<double *> p((size_t)k);
+    for (int j = 0; j < k; ++j) p[j] = const_cast<double *>(base) + (size_t)(c ? c[j] : j) * (size_t)ld;
+    return p;
+}
+// chunk c of the two pointer lists (block_chunks.h)
+static Cols chunk_cols(const BlockChunk &ch, const double *const *p) {
+    Cols r;
+    r.k = ch.count;
+    for (int j = 0; j < ch.count; ++j) r.p[j] = const_cast<double *>(p[ch.first + j]);
+    return r;
+}
+template <class F>
+static void for_chunks(int k, const double *const *b, double *const *x, F &&f) {
+    for (int c = 0; c < block_num_chunks(k); ++c) {
+        const BlockChunk ch = block_chunk(k, c);
+        f(ch, chunk_cols(ch, b), chunk_cols(ch, x));
+    }
+}
+
+void smoother_apply_block(Hierarchy &H, int level, int k, const double *const *b, double *const *x) {
+    require_block(H, k);
+    Level &L = *H.levels[level];
+    for_chunks(k, b, x, [&](const BlockChunk &ch, const Cols &bc, const Cols &xc) {
+        smooth_inplace_block(H, L.A, L.sm, work_cols(H.block.lv[level].tmp, L.A.nrows, ch.count), bc, xc);
+    });
+}
+void vcycle_apply_block(Hierarchy &H, int k, const double *const *b, double *const *x) {
+    require_block(H, k);
+    for_chunks(k, b, x, [&](const BlockChunk &, const Cols &bc, const Cols &xc) { vcycle_rec_block(H, 0, bc, xc); });
+}
+void vcycle_iterate_block(Hierarchy &H, int k, const double *const *b, double *const *x) {
+    require_block(H, k);
+    const DCsr &A = H.levels[0]->A;
+    for_chunks(k, b, x, [&](const BlockChunk &ch, const Cols &bc, const Cols &xc) {
+        const Cols r = work_cols(H.block.pcg.r, A.nrows, ch.count), z = work_cols(H.block.pcg.z, A.nrows, ch.count);
+        spmv_residual_block(H.stream, A, xc, bc, r);
+        vcycle_rec_block(H, 0, r, z);
+        vec_axpy_block(H.stream, A.nrows, 1.0, z, xc);
+    });
+}
+void pcg_solve_block(Hierarchy &H, int k, const double *const *b, double *const *x, double rel_tol, double abs_tol, int max_iter,
+                     int squared_tol, int zero_guess, int *iters, int *converged, double *hist) {
+    require_block(H, k);
+    const size_t stride = (size_t)std::max(max_iter, 0) + 1;
+    auto prec = [&](const Cols &r, const Cols &z) { vcycle_rec_block(H, 0, r, z); };
+    for_chunks(k, b, x, [&](const BlockChunk &ch, const Cols &bc, const Cols &xc) {
+        double *hp[BLOCK_MAX];
+        for (int j = 0; j < ch.count; ++j) hp[j] = hist ? hist + (size_t)(ch.first + j) * stride : nullptr;
+        pcg_loop_block(H, H.levels[0]->A, prec, bc, xc, H.block.pcg, rel_tol, abs_tol, max_iter, squared_tol != 0, zero_guess != 0,
+                       iters + ch.first, converged ? converged + ch.first : nullptr, hist ? hp : nullptr);
+    });
+}
+
 }  // namespace saamge_amd

@@ -158,6 +158,7 @@ struct Hierarchy {              // ml_data_t
     CoarseSolver coarse;        // solver of the coarsest operator, levels.back()->Ac
     PcgWork pcg;                // the outer solve
     DBuf<double> scal, partials;        // scalars and dot-product partials of both PCGs (cycle.h: PcgWork)
+    BlockWork block;            // vectors of the block solve phase: nothing until the first block call (cycle.h)
     // smoother plug per level (saamge_amd_set_smoother): host callbacks, x += M^-1 (b - A x)
     struct UserSmoother {
         int (*pre)(void *ctx, int level, int n, const double *b_host, double *x_host) = nullptr;

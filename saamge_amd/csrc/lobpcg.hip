@@ -3,7 +3,8 @@
 // 2 nb + j, so that one in-place combination of the whole buffer writes the new X and P side by side.  Per iteration: two
 // Gram products of the whole buffer, one transfer of both to the host (lobpcg_host.h picks the basis columns in the
 // model's order X, W, P and returns the coefficients), one combination applied to the three buffers in one launch, the
-// residuals (stored where A W goes next), and per unlocked column one V-cycle, one A product and one M product.
+// residuals (stored where A W goes next), and for the unlocked columns together one block V-cycle, one block A product and one
+// block M product (cycle.h, sparse.h: each column with the bits of the single-vector call).
 #include "lobpcg.h"
 
 #include <cmath>
@@ -35,15 +36,22 @@ void lobpcg_solve(Hierarchy &H, const DCsr *M, const LobpcgOptions &o, const dou
     DBuf<double> Gdev(2 * (size_t)width * width), Cdev((size_t)width * 2 * nb), lam_dev((size_t)nb), norms_dev(2 * BV_MAX_NORMS);
     const signed char *flags = o.constrain_essential ? L0.drel.flags.p : nullptr;
     auto column = [&](double *buf, int c) { return buf + (size_t)c * ld; };
-    auto products = [&](int c) {        // the operator products of one new basis column
-        spmv(s, A, column(S, c), column(AS, c));
-        if (M) spmv(s, *M, column(S, c), column(MS, c));
+    // the operator products of new basis columns: block members of the SpMV family, each column with the bits of spmv
+    auto products = [&](const std::vector<int> &cols) {
+        for (int c = 0; c < block_num_chunks((int)cols.size()); ++c) {
+            const BlockChunk ch = block_chunk((int)cols.size(), c);
+            const Cols xs(S, ld, ch.count, cols.data() + ch.first);
+            spmv_block(s, A, xs, Cols(AS, ld, ch.count, cols.data() + ch.first));
+            if (M) spmv_block(s, *M, xs, Cols(MS, ld, ch.count, cols.data() + ch.first));
+        }
     };
 
     if (x0) copy_device(S, x0, (size_t)nb * n, s);
     else bv_hash_start(s, n, nb, o.seed, S, ld);
     if (flags) bv_mask(s, n, nb, flags, FLAG_ON_ESS_BORDER, S, ld);
-    for (int j = 0; j < nb; ++j) products(j);
+    std::vector<int> cols(nb);
+    for (int j = 0; j < nb; ++j) cols[j] = j;
+    products(cols);
 
     bool have_w[lh::MAX_BLOCK] = {}, have_p[lh::MAX_BLOCK] = {}, active[lh::MAX_BLOCK] = {};
     std::vector<double> G(2 * (size_t)width * width), GA, GM, theta(width), C, Cfull((size_t)width * 2 * nb);
@@ -105,15 +113,18 @@ void lobpcg_solve(Hierarchy &H, const DCsr *M, const LobpcgOptions &o, const dou
         for (int j = 0; j < nev; ++j) done = done && rho[j] <= o.tol;
         if (done) { conv = 1; break; }
         if (it == o.max_iter) break;
+        // the unlocked columns as one block: V-cycles, then the mask, then the products of the new W columns
+        cols.clear();
         for (int j = 0; j < nb; ++j) {
             active[j] = !(rho[j] <= o.tol);
             have_w[j] = active[j];
-            if (!active[j]) continue;
-            const int c = 2 * nb + j;
-            vcycle_apply(H, 0, column(AS, c), column(S, c));
-            if (flags) bv_mask(s, n, 1, flags, FLAG_ON_ESS_BORDER, column(S, c), ld);
-            products(c);
+            if (active[j]) cols.push_back(2 * nb + j);
         }
+        const std::vector<double *> rs = block_columns(AS, ld, (int)cols.size(), cols.data());
+        const std::vector<double *> ws = block_columns(S, ld, (int)cols.size(), cols.data());
+        if (!cols.empty()) vcycle_apply_block(H, (int)cols.size(), rs.data(), ws.data());
+        if (flags) for (int c : cols) bv_mask(s, n, 1, flags, FLAG_ON_ESS_BORDER, column(S, c), ld);
+        products(cols);
         it += 1;
     }
     std::copy(lam.begin(), lam.begin() + nev, evals);

@@ -1,5 +1,6 @@
 // CSR SpMV family, fused polynomial-smoother step, vector kernels (launch wrappers).
 #pragma once
+#include "block_chunks.h"
 #include "common.h"
 #include "options.h"
 
@@ -56,5 +57,34 @@ void pcg_update_d(hipStream_t s, int n, const double *sc, double *d, const doubl
 void vec_copy(hipStream_t s, int n, const double *src, double *dst);
 void vec_zero(hipStream_t s, int n, double *dst);
 void vec_axpy(hipStream_t s, int n, double a, const double *x, double *y);  // y += a x
+
+// ---- block members: the same operations on k <= BLOCK_MAX columns per launch ----------------------------
+// Column j of every result holds the bits the single-vector routine above gives for column j alone: a block kernel reads
+// the matrix entry once and keeps one set of accumulators per column, in the single kernel's order.  The columns of a block
+// are a list of pointers (they need be neither contiguous nor equally strided); k == 1 goes through the single routine.
+struct Cols {
+    int k = 0;
+    double *p[BLOCK_MAX] = {};
+    Cols() {}
+    // columns c[0 .. k) of a column-major block (c == null: columns 0 .. k - 1)
+    Cols(const double *base, long ld, int k_, const int *c = nullptr) : k(k_) {
+        for (int j = 0; j < k; ++j) p[j] = const_cast<double *>(base) + (size_t)(c ? c[j] : j) * (size_t)ld;
+    }
+};
+void spmv_block(hipStream_t s, const DCsr &A, const Cols &x, const Cols &y);
+void spmv_residual_block(hipStream_t s, const DCsr &A, const Cols &x, const Cols &b, const Cols &r);
+void spmv_add_block(hipStream_t s, const DCsr &P, const Cols &xc, const Cols &x);
+void smooth_step_block(hipStream_t s, const DCsr &A, const double *dinv_neg, const Cols &b, const Cols &xin, const Cols &xout,
+                       double scale);
+void smooth_first_block(hipStream_t s, int n, const double *dinv_neg, const Cols &b, const Cols &xout, double scale);
+// out.p[j][slot] = a_j . b_j ; `partials` holds >= 1024 k doubles
+void dot_block(hipStream_t s, int n, const Cols &a, const Cols &b, double *partials, const Cols &out, int slot);
+// sc.p[j]: the three scalars of column j
+void pcg_update_xr_block(hipStream_t s, int n, const Cols &sc, const Cols &x, const Cols &r, const Cols &d, const Cols &z);
+void pcg_update_d_block(hipStream_t s, int n, const Cols &sc, const Cols &d, const Cols &z);
+void pcg_shift_nom_block(hipStream_t s, const Cols &sc);      // sc_j[0] = sc_j[2]
+void vec_copy_block(hipStream_t s, int n, const Cols &src, const Cols &dst);
+void vec_zero_block(hipStream_t s, int n, const Cols &dst);
+void vec_axpy_block(hipStream_t s, int n, double a, const Cols &x, const Cols &y);
 
 }  // namespace saamge_amd

@@ -1978,4 +1978,462 @@ void vec_axpy(hipStream_t s, int n, double a, const double *x, double *y) {
     SA_HIP_CHECK(hipGetLastError());
 }
 
+// ---- block members: K columns per launch, every column with the bits of the single kernels ----------------
+// The columns of a launch, by value: R roles of BLOCK_MAX pointers each and the mask of the slots that are stored.  A kernel
+// of width K reads slots 0 .. K - 1 with compile-time indices (they stay in scalar registers); a slot whose bit is clear
+// repeats slot 0, so its loads are valid and its sums are dropped.
+template <int R>
+struct BlockPtrs {
+    double *p[R][BLOCK_MAX];
+    unsigned mask;
+};
+enum { ROLE_X = 0, ROLE_Y = 1, ROLE_B = 2, ROLE_XROW = 3 };
+template <int R>
+static void set_role(BlockPtrs<R> &v, int role, const Cols &c) {
+    for (int j = 0; j < BLOCK_MAX; ++j) v.p[role][j] = c.p[j < c.k ? j : 0];
+}
+static unsigned cols_mask(const Cols &c) { return (1u << c.k) - 1u; }
+
+// The row's K sums over a slice, as sell_row_general takes its one: the same decoding of the three slice formats, the entry's
+// column, value and code loaded ONCE, then K gathers and K fmas into accumulator pair j -- s0 and s1 alternately over whole
+// groups of four entries, the tail into s0.  No LDS staging, no preloaded code words: neither changes a sum.
+template <int K>
+__device__ __forceinline__ void sell_row_general_block(int lane, int grow, int gslice, roff_t beg, roff_t end, int nt,
+                                                       const int *__restrict__ col, const double *__restrict__ val,
+                                                       const int *__restrict__ tab, const unsigned *__restrict__ codes,
+                                                       const double *__restrict__ vtab, double *const (&x)[BLOCK_MAX],
+                                                       double (&sum)[K]) {
+    const int *cp = col + beg + lane;
+    const double *vp = val + beg + lane;
+    const int w = (int)((end - beg) >> 6);
+    double s0[K], s1[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) s0[j] = s1[j] = 0.0;
+    auto quad = [&](int c0, int c1, int c2, int c3, double v0, double v1, double v2, double v3) {
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            const double *xj = x[j];
+            s0[j] = fma(v0, xj[c0], s0[j]);
+            s1[j] = fma(v1, xj[c1], s1[j]);
+            s0[j] = fma(v2, xj[c2], s0[j]);
+            s1[j] = fma(v3, xj[c3], s1[j]);
+        }
+    };
+    auto one = [&](int c, double v) {
+#pragma unroll
+        for (int j = 0; j < K; ++j) s0[j] = fma(v, x[j][c], s0[j]);
+    };
+    int k = 0;
+    if (nt >= 256) {
+        const int np = pair_count(nt);
+        const int mytab = (lane < np) ? tab[pair_table_at(gslice, nt) + lane] : 0;
+        const double myval = (lane < np) ? vtab[pair_table_at(gslice, nt) + lane] : 0.0;
+        const unsigned *wp = code_words(codes, beg, gslice, lane);
+        for (; k + 4 <= w; k += 4) {
+            const unsigned cw = __builtin_nontemporal_load(wp + 16 * k);
+            const int i0 = (int)(cw & 255u), i1 = (int)((cw >> 8) & 255u), i2 = (int)((cw >> 16) & 255u), i3 = (int)(cw >> 24);
+            quad(grow + __shfl(mytab, i0), grow + __shfl(mytab, i1), grow + __shfl(mytab, i2), grow + __shfl(mytab, i3),
+                 __shfl(myval, i0), __shfl(myval, i1), __shfl(myval, i2), __shfl(myval, i3));
+        }
+        if (k < w) {
+            unsigned cw = __builtin_nontemporal_load(wp + 16 * k);
+            for (; k < w; ++k, cw >>= 8) {
+                const int i0 = (int)(cw & 255u);
+                one(grow + __shfl(mytab, i0), __shfl(myval, i0));
+            }
+        }
+    } else if (nt >= 0) {
+        const int mytab = tab[(size_t)gslice * 64 + lane];
+        const unsigned *wp = code_words(codes, beg, gslice, lane);
+        for (; k + 4 <= w; k += 4) {
+            const unsigned cw = __builtin_nontemporal_load(wp + 16 * k);
+            const double v0 = __builtin_nontemporal_load(vp + 64 * k), v1 = __builtin_nontemporal_load(vp + 64 * (k + 1));
+            const double v2 = __builtin_nontemporal_load(vp + 64 * (k + 2)), v3 = __builtin_nontemporal_load(vp + 64 * (k + 3));
+            quad(grow + __shfl(mytab, (int)(cw & 255u)), grow + __shfl(mytab, (int)((cw >> 8) & 255u)),
+                 grow + __shfl(mytab, (int)((cw >> 16) & 255u)), grow + __shfl(mytab, (int)(cw >> 24)), v0, v1, v2, v3);
+        }
+        if (k < w) {
+            unsigned cw = __builtin_nontemporal_load(wp + 16 * k);
+            for (; k < w; ++k, cw >>= 8) one(grow + __shfl(mytab, (int)(cw & 255u)), __builtin_nontemporal_load(vp + 64 * k));
+        }
+    }
+    for (; k + 4 <= w; k += 4) {
+        const int c0 = __builtin_nontemporal_load(cp + 64 * k), c1 = __builtin_nontemporal_load(cp + 64 * (k + 1));
+        const int c2 = __builtin_nontemporal_load(cp + 64 * (k + 2)), c3 = __builtin_nontemporal_load(cp + 64 * (k + 3));
+        const double v0 = __builtin_nontemporal_load(vp + 64 * k), v1 = __builtin_nontemporal_load(vp + 64 * (k + 1));
+        const double v2 = __builtin_nontemporal_load(vp + 64 * (k + 2)), v3 = __builtin_nontemporal_load(vp + 64 * (k + 3));
+        quad(c0, c1, c2, c3, v0, v1, v2, v3);
+    }
+    for (; k < w; ++k) one(__builtin_nontemporal_load(cp + 64 * k), __builtin_nontemporal_load(vp + 64 * k));
+#pragma unroll
+    for (int j = 0; j < K; ++j) sum[j] = s0[j] + s1[j];
+}
+
+// Whole operators (row0 = 0), one lane per row, 256-row tiles dealt to the XCDs like the single kernels' (tile_deal).
+template <int MODE, int K>
+__global__ __launch_bounds__(256) void sell_block_kernel(int nrows, int nblocks, int per_xcd, const roff_t *__restrict__ sptr,
+                                                         const int *__restrict__ col, const double *__restrict__ val,
+                                                         const int *__restrict__ ntab, const int *__restrict__ tab,
+                                                         const unsigned *__restrict__ codes, const double *__restrict__ vtab,
+                                                         const double *__restrict__ dinv, double scale, BlockPtrs<4> v) {
+    const int blk = xcd_block(per_xcd);
+    if (blk >= nblocks) return;
+    const long row = (long)blk * 256 + threadIdx.x;
+    const int slice = __builtin_amdgcn_readfirstlane((int)(row >> 6));
+    const int lane = threadIdx.x & 63;
+    if ((long)slice * 64 >= nrows) return;
+    const roff_t beg = sptr[slice], end = sptr[slice + 1];
+    const int nt = ntab[slice];
+    double sum[K];
+    sell_row_general_block<K>(lane, (int)row, slice, beg, end, nt, col, val, tab, codes, vtab, v.p[ROLE_X], sum);
+    if (row >= nrows) return;
+    const double d = (MODE == MODE_SMOOTH) ? dinv[row] : 0.0;      // (once per row, whatever K)
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        if (!((v.mask >> j) & 1u)) continue;
+        RowTerms t{0.0, d, 0.0};
+        if (MODE == MODE_RESIDUAL || MODE == MODE_SMOOTH) t.b = v.p[ROLE_B][j][row];
+        if (MODE == MODE_ADD) t.x = v.p[ROLE_Y][j][row];
+        if (MODE == MODE_SMOOTH) t.x = v.p[ROLE_XROW][j][row];
+        spmv_epilogue<MODE>(sum[j], t, scale, v.p[ROLE_Y][j], row);
+    }
+}
+
+// The CSR order of spmv_kernel per column: lane l of L takes entries beg + l, beg + l + L, ..., then the __shfl_down tree.
+// Plain and add: the modes the cycle (P, R) and the eigensolver (M) use on CSR operators.
+template <int L, int MODE, int K>
+__global__ __launch_bounds__(256) void spmv_block_kernel(int nrows, const roff_t *__restrict__ rowptr, const int *__restrict__ col,
+                                                         const double *__restrict__ val, BlockPtrs<4> v) {
+    static_assert(MODE == MODE_PLAIN || MODE == MODE_ADD, "the CSR block kernel has no b and no diagonal");
+    const long gtid = (long)blockIdx.x * 256 + threadIdx.x;
+    const int lane = threadIdx.x & (L - 1);
+    const long row = gtid / L;
+    if (row >= nrows) return;
+    const roff_t beg = rowptr[row], end = rowptr[row + 1];
+    double sum[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) sum[j] = 0.0;
+    for (roff_t k = beg + lane; k < end; k += L) {
+        const double a = __builtin_nontemporal_load(val + k);
+        const int c = __builtin_nontemporal_load(col + k);
+#pragma unroll
+        for (int j = 0; j < K; ++j) sum[j] = fma(a, v.p[ROLE_X][j][c], sum[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+#pragma unroll
+        for (int o = L / 2; o > 0; o >>= 1) sum[j] += __shfl_down(sum[j], o, L);
+    }
+    if (lane != 0) return;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        if (!((v.mask >> j) & 1u)) continue;
+        RowTerms t{0.0, 0.0, 0.0};
+        if (MODE == MODE_ADD) t.x = v.p[ROLE_Y][j][row];
+        spmv_epilogue<MODE>(sum[j], t, 0.0, v.p[ROLE_Y][j], row);
+    }
+}
+
+template <int MODE, int K>
+static void launch_sell_block(hipStream_t s, const DCsr &A, const double *dinv, double scale, const BlockPtrs<4> &v) {
+    const Sell &S = A.sell;
+    const TileDeal d = tile_deal(A.nrows);
+    hipLaunchKernelGGL((sell_block_kernel<MODE, K>), dim3(d.grid), dim3(256), 0, s, A.nrows, d.nblocks, d.per_xcd, S.ptr.p, S.col.p,
+                       S.val.p, S.ntab.p, S.tab.p, S.code.p, S.vtab.p, dinv, scale, v);
+}
+template <int MODE, int K>
+static void launch_csr_block(hipStream_t s, const DCsr &A, const BlockPtrs<4> &v) {
+    const int L = A.lanes_per_row;
+    const int grid = div_up((long)A.nrows * L, 256);
+#define SA_CASE(LL)                                                                                                          \
+    case LL:                                                                                                                 \
+        hipLaunchKernelGGL((spmv_block_kernel<LL, MODE, K>), dim3(grid), dim3(256), 0, s, A.nrows, A.rowptr.p, A.col.p, A.val.p, v); \
+        break;
+    switch (L) {
+        SA_CASE(1) SA_CASE(2) SA_CASE(4) SA_CASE(8) SA_CASE(16) SA_CASE(32) SA_CASE(64)
+        default: SA_REQUIRE(false, "bad lanes_per_row");
+    }
+#undef SA_CASE
+}
+// The block application of a whole operator.  Which operators run a block kernel is decided by their FORMAT, an observable:
+//   SELL copy with the operator-level dictionary   column by column through the single routine (its kernels walk 16-bit codes in a
+//                                                  persistent grid: no block form in this change)
+//   SELL copy otherwise                            sell_block_kernel (any mix of pair-coded, offset-coded and plain slices)
+//   no SELL copy (P, R, a caller's M), plain / add spmv_block_kernel; the other two modes column by column
+template <int MODE>
+static bool block_kernel_applies(const DCsr &A, int k) {
+    const bool csr_ok = MODE == MODE_PLAIN || MODE == MODE_ADD;
+    return k > 1 && !(A.sell.built && A.sell.dict.on) && (A.sell.built || csr_ok);
+}
+template <int MODE>
+static void launch_spmv_block(hipStream_t s, const DCsr &A, const Cols &x, const Cols &y, const Cols *b, const double *dinv, double scale) {
+    const int k = x.k;
+    const Sell &S = A.sell;
+    BlockPtrs<4> v;
+    set_role(v, ROLE_X, x);
+    set_role(v, ROLE_Y, y);
+    set_role(v, ROLE_B, b ? *b : x);
+    set_role(v, ROLE_XROW, x);
+    v.mask = cols_mask(x);
+#define SA_WIDTHS(CALL)                          \
+    switch (block_width(k)) {                    \
+        case 2: CALL(2); break;                  \
+        case 4: CALL(4); break;                  \
+        default: CALL(8); break;                 \
+    }
+    if (S.built) {
+#define SA_SELL(KK) launch_sell_block<MODE, KK>(s, A, dinv, scale, v)
+        SA_WIDTHS(SA_SELL)
+#undef SA_SELL
+    } else {
+        constexpr int CM = (MODE == MODE_PLAIN || MODE == MODE_ADD) ? MODE : MODE_PLAIN;      // (block_kernel_applies: never the other two)
+#define SA_CSR(KK) launch_csr_block<CM, KK>(s, A, v)
+        SA_WIDTHS(SA_CSR)
+#undef SA_CSR
+    }
+#undef SA_WIDTHS
+    SA_HIP_CHECK(hipGetLastError());
+}
+static void require_spmv_cols(const Cols &x, const Cols &y, const Cols *b) {
+    SA_REQUIRE(x.k >= 1 && x.k <= BLOCK_MAX && y.k == x.k && (!b || b->k == x.k), "block SpMV: bad column lists");
+}
+// bytes in the format the block kernel runs: the matrix data once, the vectors (`per_row` doubles per row) k times
+static inline double block_fmt_bytes(const DCsr &A, int k, double per_row) {
+    return A.sell.built ? A.sell.stream_bytes + per_row * 8.0 * k * A.nrows : 0.0;
+}
+// The profile lists a block launch on k columns as k applications under the single-vector label (tests and tools count
+// applications per label), with the algorithmic bytes and flops of all k.
+void spmv_block(hipStream_t s, const DCsr &A, const Cols &x, const Cols &y) {
+    require_spmv_cols(x, y, nullptr);
+    if (A.nrows == 0) return;
+    if (!block_kernel_applies<MODE_PLAIN>(A, x.k)) {
+        for (int j = 0; j < x.k; ++j) spmv(s, A, x.p[j], y.p[j]);
+        return;
+    }
+    profiler().begin(s);
+    launch_spmv_block<MODE_PLAIN>(s, A, x, y, nullptr, nullptr, 0.0);
+    profiler().end(s, spmv_label("spmv", A).c_str(), x.k * spmv_bytes(A, RowRange()), x.k * spmv_flops(A, RowRange()),
+                   block_fmt_bytes(A, x.k, 2.0), x.k);
+}
+void spmv_residual_block(hipStream_t s, const DCsr &A, const Cols &x, const Cols &b, const Cols &r) {
+    require_spmv_cols(x, r, &b);
+    if (A.nrows == 0) return;
+    if (!block_kernel_applies<MODE_RESIDUAL>(A, x.k)) {
+        for (int j = 0; j < x.k; ++j) spmv_residual(s, A, x.p[j], b.p[j], r.p[j]);
+        return;
+    }
+    profiler().begin(s);
+    launch_spmv_block<MODE_RESIDUAL>(s, A, x, r, &b, nullptr, 0.0);
+    profiler().end(s, spmv_label("spmv_residual", A).c_str(), x.k * (spmv_bytes(A, RowRange()) + 8.0 * A.nrows),
+                   x.k * spmv_flops(A, RowRange()), block_fmt_bytes(A, x.k, 3.0), x.k);
+}
+void spmv_add_block(hipStream_t s, const DCsr &P, const Cols &xc, const Cols &x) {
+    require_spmv_cols(xc, x, nullptr);
+    if (P.nrows == 0) return;
+    if (!block_kernel_applies<MODE_ADD>(P, xc.k)) {
+        for (int j = 0; j < xc.k; ++j) spmv_add(s, P, xc.p[j], x.p[j]);
+        return;
+    }
+    profiler().begin(s);
+    launch_spmv_block<MODE_ADD>(s, P, xc, x, nullptr, nullptr, 0.0);
+    profiler().end(s, spmv_label("spmv_add", P).c_str(), xc.k * (spmv_bytes(P, RowRange()) + 8.0 * P.nrows),
+                   xc.k * spmv_flops(P, RowRange()), block_fmt_bytes(P, xc.k, 3.0), xc.k);
+}
+void smooth_step_block(hipStream_t s, const DCsr &A, const double *dinv_neg, const Cols &b, const Cols &xin, const Cols &xout,
+                       double scale) {
+    require_spmv_cols(xin, xout, &b);
+    if (A.nrows == 0) return;
+    if (!block_kernel_applies<MODE_SMOOTH>(A, xin.k)) {
+        for (int j = 0; j < xin.k; ++j) smooth_step(s, A, dinv_neg, b.p[j], xin.p[j], xout.p[j], scale);
+        return;
+    }
+    profiler().begin(s);
+    launch_spmv_block<MODE_SMOOTH>(s, A, xin, xout, &b, dinv_neg, scale);
+    profiler().end(s, spmv_label("smooth_step", A).c_str(), xin.k * (spmv_bytes(A, RowRange()) + 24.0 * A.nrows),
+                   xin.k * spmv_flops(A, RowRange()), block_fmt_bytes(A, xin.k, 3.0) + (A.sell.built ? 8.0 * A.nrows : 0.0), xin.k);
+}
+
+// ---- block forms of the vector kernels: blockIdx.y is the column, the grid in x and every index are the single kernel's ----
+// (the column's pointer by a chain of uniform selects: a run-time index into the by-value struct would go through scratch)
+template <int R>
+__device__ __forceinline__ double *block_col(const BlockPtrs<R> &v, int role, int j) {
+    double *p = v.p[role][0];
+#pragma unroll
+    for (int q = 1; q < BLOCK_MAX; ++q) p = (j == q) ? v.p[role][q] : p;
+    return p;
+}
+__global__ __launch_bounds__(256) void smooth_first_block_kernel(int n, const double *__restrict__ dinv, double scale, BlockPtrs<2> v) {
+    const double *b = block_col(v, 0, blockIdx.y);
+    double *xout = block_col(v, 1, blockIdx.y);
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) xout[i] = scale * (dinv[i] * (0.0 - b[i]));
+}
+__global__ __launch_bounds__(256) void copy_block_kernel(int n, BlockPtrs<2> v) {
+    const double *src = block_col(v, 0, blockIdx.y);
+    double *dst = block_col(v, 1, blockIdx.y);
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] = src[i];
+}
+__global__ __launch_bounds__(256) void zero_block_kernel(int n, BlockPtrs<1> v) {
+    double *dst = block_col(v, 0, blockIdx.y);
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] = 0.0;
+}
+__global__ __launch_bounds__(256) void axpy_block_kernel(int n, double a, BlockPtrs<2> v) {
+    const double *x = block_col(v, 0, blockIdx.y);
+    double *y = block_col(v, 1, blockIdx.y);
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) y[i] = fma(a, x[i], y[i]);
+}
+// dot's partial and final order per column: column j's partials at partials[1024 j ..]
+__global__ __launch_bounds__(256) void dot_partial_block_kernel(int n, BlockPtrs<2> v, double *__restrict__ partials) {
+    __shared__ double sh[4];
+    const double *a = block_col(v, 0, blockIdx.y), *b = block_col(v, 1, blockIdx.y);
+    double acc = 0.0;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) acc = fma(a[i], b[i], acc);
+    const double r = block_sum_256(acc, sh);
+    if (threadIdx.x == 0) partials[(size_t)blockIdx.y * 1024 + blockIdx.x] = r;
+}
+__global__ __launch_bounds__(256) void dot_final_block_kernel(int np, const double *__restrict__ partials, BlockPtrs<1> v, int slot) {
+    __shared__ double sh[4];
+    double *out = block_col(v, 0, blockIdx.x);
+    const double *mine = partials + (size_t)blockIdx.x * 1024;
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < np; i += 256) acc += mine[i];
+    const double r = block_sum_256(acc, sh);
+    if (threadIdx.x == 0) out[slot] = r;
+}
+enum { PCG_SC = 0, PCG_X = 1, PCG_R = 2, PCG_D = 3, PCG_Z = 4 };
+__global__ __launch_bounds__(256) void pcg_update_xr_block_kernel(int n, BlockPtrs<5> v) {
+    const double *sc = block_col(v, PCG_SC, blockIdx.y);
+    double *x = block_col(v, PCG_X, blockIdx.y), *r = block_col(v, PCG_R, blockIdx.y);
+    const double *d = block_col(v, PCG_D, blockIdx.y), *z = block_col(v, PCG_Z, blockIdx.y);
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double alpha = sc[0] / sc[1];
+    x[i] = fma(alpha, d[i], x[i]);
+    r[i] = fma(-alpha, z[i], r[i]);
+}
+__global__ __launch_bounds__(256) void pcg_update_d_block_kernel(int n, BlockPtrs<3> v) {
+    const double *sc = block_col(v, 0, blockIdx.y);
+    double *d = block_col(v, 1, blockIdx.y);
+    const double *z = block_col(v, 2, blockIdx.y);
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double beta = sc[2] / sc[0];
+    d[i] = fma(beta, d[i], z[i]);
+}
+__global__ __launch_bounds__(64) void pcg_shift_nom_block_kernel(BlockPtrs<1> v) {
+    double *sc = block_col(v, 0, blockIdx.x);
+    if (threadIdx.x == 0) sc[0] = sc[2];
+}
+
+static void require_cols(int k, std::initializer_list<const Cols *> cs) {
+    SA_REQUIRE(k >= 1 && k <= BLOCK_MAX, "block vector kernel: bad column count");
+    for (const Cols *c : cs) SA_REQUIRE(c->k == k, "block vector kernel: column lists of different lengths");
+}
+void smooth_first_block(hipStream_t s, int n, const double *dinv_neg, const Cols &b, const Cols &xout, double scale) {
+    require_cols(b.k, {&xout});
+    if (!n) return;
+    if (b.k == 1) return smooth_first(s, n, dinv_neg, b.p[0], xout.p[0], scale);
+    BlockPtrs<2> v;
+    set_role(v, 0, b);
+    set_role(v, 1, xout);
+    v.mask = cols_mask(b);
+    profiler().begin(s);
+    hipLaunchKernelGGL(smooth_first_block_kernel, dim3(div_up(n, 256), b.k), dim3(256), 0, s, n, dinv_neg, scale, v);
+    SA_HIP_CHECK(hipGetLastError());
+    profiler().end(s, "smooth_first", 24.0 * n * b.k, 2.0 * n * b.k, 0.0, b.k);
+}
+void vec_copy_block(hipStream_t s, int n, const Cols &src, const Cols &dst) {
+    require_cols(src.k, {&dst});
+    if (n <= 0) return;
+    if (src.k == 1) return vec_copy(s, n, src.p[0], dst.p[0]);
+    BlockPtrs<2> v;
+    set_role(v, 0, src);
+    set_role(v, 1, dst);
+    v.mask = cols_mask(src);
+    hipLaunchKernelGGL(copy_block_kernel, dim3(div_up(n, 256), src.k), dim3(256), 0, s, n, v);
+    SA_HIP_CHECK(hipGetLastError());
+}
+void vec_zero_block(hipStream_t s, int n, const Cols &dst) {
+    require_cols(dst.k, {});
+    if (n <= 0) return;
+    if (dst.k == 1) return vec_zero(s, n, dst.p[0]);
+    BlockPtrs<1> v;
+    set_role(v, 0, dst);
+    v.mask = cols_mask(dst);
+    hipLaunchKernelGGL(zero_block_kernel, dim3(div_up(n, 256), dst.k), dim3(256), 0, s, n, v);
+    SA_HIP_CHECK(hipGetLastError());
+}
+void vec_axpy_block(hipStream_t s, int n, double a, const Cols &x, const Cols &y) {
+    require_cols(x.k, {&y});
+    if (!n) return;
+    if (x.k == 1) return vec_axpy(s, n, a, x.p[0], y.p[0]);
+    BlockPtrs<2> v;
+    set_role(v, 0, x);
+    set_role(v, 1, y);
+    v.mask = cols_mask(x);
+    hipLaunchKernelGGL(axpy_block_kernel, dim3(div_up(n, 256), x.k), dim3(256), 0, s, n, a, v);
+    SA_HIP_CHECK(hipGetLastError());
+}
+void dot_block(hipStream_t s, int n, const Cols &a, const Cols &b, double *partials, const Cols &out, int slot) {
+    require_cols(a.k, {&b, &out});
+    if (a.k == 1) return dot(s, n, a.p[0], b.p[0], partials, out.p[0] + slot);
+    int grid = div_up(n, 256 * 8);      // (dot's grid: the partial sums of a column depend on it)
+    if (grid > 1024) grid = 1024;
+    if (grid < 1) grid = 1;
+    BlockPtrs<2> v;
+    set_role(v, 0, a);
+    set_role(v, 1, b);
+    v.mask = cols_mask(a);
+    BlockPtrs<1> o;
+    set_role(o, 0, out);
+    o.mask = v.mask;
+    profiler().begin(s);
+    hipLaunchKernelGGL(dot_partial_block_kernel, dim3(grid, a.k), dim3(256), 0, s, n, v, partials);
+    hipLaunchKernelGGL(dot_final_block_kernel, dim3(a.k), dim3(256), 0, s, grid, partials, o, slot);
+    SA_HIP_CHECK(hipGetLastError());
+    profiler().end(s, "dot", 16.0 * n * a.k, 2.0 * n * a.k, 0.0, a.k);
+}
+void pcg_update_xr_block(hipStream_t s, int n, const Cols &sc, const Cols &x, const Cols &r, const Cols &d, const Cols &z) {
+    require_cols(sc.k, {&x, &r, &d, &z});
+    if (!n) return;
+    if (sc.k == 1) return pcg_update_xr(s, n, sc.p[0], x.p[0], r.p[0], d.p[0], z.p[0]);
+    BlockPtrs<5> v;
+    set_role(v, PCG_SC, sc);
+    set_role(v, PCG_X, x);
+    set_role(v, PCG_R, r);
+    set_role(v, PCG_D, d);
+    set_role(v, PCG_Z, z);
+    v.mask = cols_mask(sc);
+    profiler().begin(s);
+    hipLaunchKernelGGL(pcg_update_xr_block_kernel, dim3(div_up(n, 256), sc.k), dim3(256), 0, s, n, v);
+    SA_HIP_CHECK(hipGetLastError());
+    profiler().end(s, "pcg_update_xr", 48.0 * n * sc.k, 4.0 * n * sc.k, 0.0, sc.k);
+}
+void pcg_update_d_block(hipStream_t s, int n, const Cols &sc, const Cols &d, const Cols &z) {
+    require_cols(sc.k, {&d, &z});
+    if (!n) return;
+    if (sc.k == 1) return pcg_update_d(s, n, sc.p[0], d.p[0], z.p[0]);
+    BlockPtrs<3> v;
+    set_role(v, 0, sc);
+    set_role(v, 1, d);
+    set_role(v, 2, z);
+    v.mask = cols_mask(sc);
+    profiler().begin(s);
+    hipLaunchKernelGGL(pcg_update_d_block_kernel, dim3(div_up(n, 256), sc.k), dim3(256), 0, s, n, v);
+    SA_HIP_CHECK(hipGetLastError());
+    profiler().end(s, "pcg_update_d", 24.0 * n * sc.k, 2.0 * n * sc.k, 0.0, sc.k);
+}
+void pcg_shift_nom_block(hipStream_t s, const Cols &sc) {
+    require_cols(sc.k, {});
+    if (sc.k == 1) return copy_device(sc.p[0], (const double *)sc.p[0] + 2, 1, s);
+    BlockPtrs<1> v;
+    set_role(v, 0, sc);
+    v.mask = cols_mask(sc);
+    hipLaunchKernelGGL(pcg_shift_nom_block_kernel, dim3(sc.k), dim3(64), 0, s, v);
+    SA_HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace saamge_amd
