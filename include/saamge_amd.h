@@ -278,7 +278,8 @@ int saamge_amd_ml_produce_data_parcsr(const saamge_amd_parcsr *A, int NE_local, 
 int saamge_amd_update_operators(saamge_amd_hierarchy *h, const double *new_val);
 /* tg_update_coarse_operator(A, tg_data, perform_solve_init, coarse_direct), inc/tg.hpp:610-612: the same update with
  * the coarsest solver chosen again -- coarse_solver with the meaning of the params field of that name: 1 = the
- * reference's coarse_direct = true, 2 = its CG on the coarsest operator; -1 keeps the one the hierarchy was built with. */
+ * reference's coarse_direct = true, 2 = its CG on the coarsest operator; -1 keeps the kind in
+ * place: the one the hierarchy was built with, or the one the last call with 1 or 2 chose. */
 int saamge_amd_update_operators2(saamge_amd_hierarchy *h, const double *new_val, int coarse_solver);
 /* ml_free_data, inc/ml.hpp:196 */
 void saamge_amd_ml_free_data(saamge_amd_hierarchy *h);

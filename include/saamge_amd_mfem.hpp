@@ -1,7 +1,20 @@
 // saamge_amd_mfem.hpp -- the reference's own C++ entry points for the setup + solve hot path, in
-// namespace saamge, as thin adaptors over the C ABI (saamge_amd.h).  Compiled only where MFEM + hypre
-// headers exist (SAAMGE_AMD_WITH_MFEM; not in the build container -- tests/test_cxx_boundary.py compiles it
-// against tests/mfem_stub/, a declaration-only stand-in for the handful of MFEM types used here).
+// namespace saamge, as thin adaptors over the C ABI (saamge_amd.h).  Compiled where MFEM + hypre headers exist
+// (SAAMGE_AMD_WITH_MFEM).  They do not exist in the build container: there tests/test_cxx_boundary.py compiles this file
+// against tests/mfem_stub/ (declarations only), and tests/cxx/mfem_adaptor_run.cpp RUNS the entry points below (the list:
+// INTEGRATION.md section 2) against tests/mfem_mini/, a defining single-rank stand-in for the handful of MFEM types used
+// here; tests/test_gpu_mfem_adaptor.py holds what it gets to the C ABI's own results bit for bit.  Not run:
+// ml_device_partitioner, and the branch for a matrix distributed over several ranks (detail::MpiCollectives,
+// detail::DistLayout, the _parcsr call) beyond detail::local_to_true.
+//
+// Plug state.  The C ABI keeps the smoother and coarse-solver plugs per HIERARCHY, so what is installed there is recorded
+// where every VCycleSolver of the hierarchy sees it: in tg_data_t (installed_pre / installed_post / plugged), with the
+// trampolines' context object owned by the tg_data as well.  A solver object holds no such state: one that dies leaves
+// nothing dangling, and the next one compares the caller's choice with what the library really holds -- before every Mult
+// and every kalchev_pcg alike.  The finest level's operator is a solver's own (SetOperator): it is in the context only
+// for the length of a call.  (The other way --
+// uninstall in the destructor, install again at every Mult -- costs two calls per level and cycle and still breaks when two
+// solvers of one tg_data are alive at once, which is the reference drivers' own pattern.)
 //
 // A driver written against <saamge.hpp> (amg/test/mltest/mltest.cpp:667-793 is the model) keeps its
 // call sequence:
@@ -144,8 +157,8 @@ inline void smpr_sym_poly(mfem::HypreParMatrix &A, const mfem::Vector &b, mfem::
     if (saamge_amd_smoother(d->h, d->level, b.GetData(), x.GetData())) mfem::mfem_error(saamge_amd_last_error());
 }
 
-namespace detail { struct DistLayout; }
-struct interp_data_t;       // (opaque here: the per-AE eigenpairs live on the GPU; saamge_amd_get_ae_eigens exports them)
+namespace detail { struct DistLayout; struct SmootherPlug; }
+struct interp_data_t;      // (opaque here: the per-AE eigenpairs live on the GPU; saamge_amd_get_ae_eigens exports them)
 
 // == tg_data_t (inc/tg_data.hpp:47-83).  Ac / interp / restr are host copies for inspection; the GPU owns the
 // operators the cycle uses.  coarse_solver may be assigned by the caller (test/algebraic/algebraic.cpp:282-283):
@@ -175,7 +188,13 @@ struct tg_data_t {
     double init_smooth_drop_tol = 0.0;
     bool init_use_arpack = false;
     mfem::SparseMatrix *Ac_diag = nullptr, *interp_diag = nullptr, *restr_diag = nullptr;
-    HYPRE_Int row_starts[2][2];
+    HYPRE_Int row_starts[2][2];            // [0]: fine rows, [1]: coarse rows; Ac / interp / restr point INTO this struct
+    // what the C ABI holds for this level right now (smoothers) and for the hierarchy (coarse solver; read on the finest
+    // level's tg_data only), shared by every VCycleSolver made from this tg_data; smoother_plug is the trampolines' context
+    // (owned, made by the first Mult)
+    smpr_ft installed_pre = smpr_sym_poly, installed_post = smpr_sym_poly;
+    mfem::Solver *plugged = nullptr;
+    detail::SmootherPlug *smoother_plug = nullptr;
     // a hierarchy built from a DISTRIBUTED HypreParMatrix: the ranks' row blocks (vectors at this boundary are the rank's
     // true-dof block) and the MPI collectives the library calls back into; owned by the finest level's tg_data
     detail::DistLayout *dist = nullptr;
@@ -412,27 +431,42 @@ inline mfem::Table *table_from(const saamge_amd_hierarchy *h, int level, int whi
     std::copy(J.begin(), J.end(), t->GetJ());
     return t;
 }
+// Ac / interp / restr of tg over its *_diag blocks, with row and column starts that live in tg itself.  A HypreParMatrix
+// may keep the pointers it is given (hypre did not copy them in the versions the reference targets), so the three are made
+// again whenever the struct that holds row_starts changes (tg_build_hierarchy).
+inline void wrap_operators(tg_data_t &tg, MPI_Comm comm) {
+    mfem::SparseMatrix *diag[3] = {tg.interp_diag, tg.restr_diag, tg.Ac_diag};
+    mfem::HypreParMatrix **par[3] = {&tg.interp, &tg.restr, &tg.Ac};
+    const int fine_rows[3] = {1, 0, 0}, fine_cols[3] = {0, 1, 0};
+    for (int q = 0; q < 3; ++q) {
+        delete *par[q];
+        *par[q] = new mfem::HypreParMatrix(comm, diag[q]->Height(), diag[q]->Width(), tg.row_starts[fine_rows[q] ? 0 : 1],
+                                           tg.row_starts[fine_cols[q] ? 0 : 1], diag[q]);
+    }
+}
 // host copies of the level's operators as HypreParMatrix (one rank)
 inline void fetch_operators(tg_data_t &tg, MPI_Comm comm) {
     long long info[16];
     if (saamge_amd_level_info(tg.h, tg.level, info)) mfem::mfem_error(saamge_amd_last_error());
     const int n = (int)info[0], nc = (int)info[4];
-    struct Sel { int which, rows, cols; long long nnz; mfem::SparseMatrix **diag; mfem::HypreParMatrix **par; };
-    Sel sel[3] = {{1, n, nc, info[5], &tg.interp_diag, &tg.interp},
-                  {2, nc, n, info[5], &tg.restr_diag, &tg.restr},
-                  {3, nc, nc, info[6], &tg.Ac_diag, &tg.Ac}};
+    struct Sel { int which, rows, cols; long long nnz; mfem::SparseMatrix **diag; };
+    Sel sel[3] = {{1, n, nc, info[5], &tg.interp_diag},
+                  {2, nc, n, info[5], &tg.restr_diag},
+                  {3, nc, nc, info[6], &tg.Ac_diag}};
     tg.row_starts[0][0] = 0; tg.row_starts[0][1] = n;
     tg.row_starts[1][0] = 0; tg.row_starts[1][1] = nc;
     for (int q = 0; q < 3; ++q) {
         int *I = new int[sel[q].rows + 1];
         int *J = new int[sel[q].nnz];
         double *V = new double[sel[q].nnz];
-        if (saamge_amd_get_csr(tg.h, tg.level, sel[q].which, I, J, V)) mfem::mfem_error(saamge_amd_last_error());
+        if (saamge_amd_get_csr(tg.h, tg.level, sel[q].which, I, J, V)) {
+            delete[] I; delete[] J; delete[] V;
+            mfem::mfem_error(saamge_amd_last_error());
+        }
         *sel[q].diag = new mfem::SparseMatrix(I, J, V, sel[q].rows, sel[q].cols);      // takes ownership of the arrays
-        HYPRE_Int *rs = sel[q].rows == n ? tg.row_starts[0] : tg.row_starts[1];
-        HYPRE_Int *cs = sel[q].cols == n ? tg.row_starts[0] : tg.row_starts[1];
-        *sel[q].par = new mfem::HypreParMatrix(comm, sel[q].rows, sel[q].cols, rs, cs, *sel[q].diag);
     }
+    // (by position, not by comparing sizes: n == nc would otherwise hand every operator the fine starts)
+    wrap_operators(tg, comm);
 }
 inline int coarse_solver_trampoline(void *ctx, int n, const double *rc, double *xc) {
     mfem::Solver *s = *(mfem::Solver **)ctx;
@@ -465,6 +499,25 @@ inline int post_smoother_trampoline(void *ctx, int level, int n, const double *b
     return smoother_trampoline(p, p->tg->post_smoother, n, b, x);
 }
 
+// the element matrices as the C ABI takes them: element e's nd_e x nd_e matrix ROW-major at sum_{f<e} nd_f^2, entry (a, b)
+// = Matrix::Elem(a, b) of what the provider hands out (GetMatrix once per element; deleted when the provider says free_matr)
+inline std::vector<double> pack_element_matrices(const agg_partitioning_relations_t &r, const ElementMatrixProvider &provider) {
+    long long elsize = 0;
+    for (int e = 0; e < r.NE; ++e) elsize += (long long)r.elem_to_dof->RowSize(e) * r.elem_to_dof->RowSize(e);
+    std::vector<double> elmat((size_t)elsize);
+    size_t off = 0;
+    for (int e = 0; e < r.NE; ++e) {
+        const int nd = r.elem_to_dof->RowSize(e);
+        bool free_matr = false;
+        mfem::Matrix *m = provider.GetMatrix(e, free_matr);
+        for (int a = 0; a < nd; ++a)
+            for (int b = 0; b < nd; ++b) elmat[off + (size_t)a * nd + b] = m->Elem(a, b);
+        off += (size_t)nd * nd;
+        if (free_matr) delete m;
+    }
+    return elmat;
+}
+
 }  // namespace detail
 
 // ml_produce_data (inc/ml.hpp:192-194, src/ml.cpp:379-472).  Takes ownership of the provider (freed by
@@ -483,26 +536,11 @@ inline ml_data_t *ml_produce_data(mfem::HypreParMatrix &Ag, agg_partitioning_rel
     // element matrices, raw: element e's nd_e x nd_e matrix row-major at sum_{f<e} nd_f^2 (elements of one size: NE x nde x nde)
     const int nde = r.elem_to_dof->RowSize(0);
     bool mixed = false;
-    long long elsize = 0;
-    for (int e = 0; e < NE; ++e) {
-        const long long nd = r.elem_to_dof->RowSize(e);
-        mixed = mixed || nd != nde;
-        elsize += nd * nd;
-    }
+    for (int e = 0; e < NE; ++e) mixed = mixed || r.elem_to_dof->RowSize(e) != nde;
     if (mixed && distributed)
         mfem::mfem_error("ml_produce_data: elements with different numbers of dofs are not supported on the per-rank path "
                          "(saamge_amd_ml_produce_data_parcsr)");
-    std::vector<double> elmat((size_t)elsize);
-    size_t off = 0;
-    for (int e = 0; e < NE; ++e) {
-        const int nd = r.elem_to_dof->RowSize(e);
-        bool free_matr = false;
-        mfem::Matrix *m = elem_data_finest->GetMatrix(e, free_matr);
-        for (int a = 0; a < nd; ++a)
-            for (int b = 0; b < nd; ++b) elmat[(size_t)off + (size_t)a * nd + b] = m->Elem(a, b);
-        off += (size_t)nd * nd;
-        if (free_matr) delete m;
-    }
+    const std::vector<double> elmat = detail::pack_element_matrices(r, *elem_data_finest);
     // partitions of every coarsening: level 0 from agg_part_rels, coarser ones from the partitioner hook on the
     // AE adjacency graph elem_to_elem_{k+1} = AE_to_elem x elem_to_elem x elem_to_AE (src/aggregates.cpp:1768-1771)
     std::vector<std::vector<int> > parts((size_t)nco);
@@ -640,7 +678,10 @@ inline void tg_free_data(tg_data_t *tg) {           // inc/tg.hpp:576, src/tg.cp
     delete tg->Ac_diag; delete tg->interp_diag; delete tg->restr_diag;
     delete tg->poly_data;
     delete tg->elem_data;
+    // a coarser level's tg_data goes before the hierarchy does: the library must not keep its plug context
+    if (!tg->owns_h && tg->h && tg->smoother_plug) saamge_amd_set_smoother(tg->h, tg->level, nullptr, nullptr, nullptr);
     if (tg->owns_h) saamge_amd_ml_free_data(tg->h);
+    delete tg->smoother_plug;
     delete tg->dist;          // (after the hierarchy: its collectives are the hierarchy's callbacks)
     delete tg;
 }
@@ -709,6 +750,8 @@ inline void tg_build_hierarchy(mfem::HypreParMatrix &Ag, tg_data_t &tg_data, con
     tg_data.pre_smoother = pre; tg_data.post_smoother = post; tg_data.coarse_solver = cs; tg_data.tag = tag;
     tg_data.init_nu_pro = inp; tg_data.init_nu_relax = inr; tg_data.init_smooth_drop_tol = idt; tg_data.init_use_arpack = iua;
     delete built;                      // (shallow: every owned pointer moved to tg_data)
+    // ... except that Ac / interp / restr were made over built->row_starts: made again over the caller's struct
+    if (tg_data.Ac_diag) detail::wrap_operators(tg_data, Ag.GetComm());
     delete ml->levels_list.finest;
     delete ml;
 }
@@ -813,13 +856,8 @@ class VCycleSolver : public mfem::Solver {
 public:
     VCycleSolver(tg_data_t *tg_data_in, bool iterative_mode_)
         : mfem::Solver(tg_data_in->dist ? tg_data_in->dist->nloc : tg_data_in->restr->Width(), iterative_mode_), tg_data(tg_data_in),
-          A(NULL), plugged(NULL) {
+          A(NULL) {
         if (tg_data->level != 0) mfem::mfem_error("VCycleSolver: only the finest level's tg_data can be cycled from outside");
-        for (tg_data_t *t = tg_data; t; t = t->coarser_tg) {
-            detail::SmootherPlug pl = {t, NULL};
-            plugs.push_back(pl);
-            installed.push_back(std::make_pair((smpr_ft)smpr_sym_poly, (smpr_ft)smpr_sym_poly));
-        }
     }
     virtual ~VCycleSolver() {}
     virtual void SetOperator(const mfem::Operator &op) {
@@ -827,27 +865,7 @@ public:
         if (A == NULL) mfem::mfem_error("VCycleSolver::SetOperator : not HypreParMatrix!");     // src/solve.cpp:301-307
     }
     virtual void Mult(const mfem::Vector &b, mfem::Vector &x) const {
-        // a coarse_solver assigned by the caller takes over the coarsest solve (tg_data_t::coarse_solver plug)
-        if (tg_data->coarse_solver != plugged) {
-            plugged = tg_data->coarse_solver;
-            if (saamge_amd_set_coarse_solver(tg_data->h, plugged ? detail::coarse_solver_trampoline : nullptr,
-                                             (void *)&tg_data->coarse_solver))
-                mfem::mfem_error(saamge_amd_last_error());
-        }
-        // pre_smoother / post_smoother assigned by the caller (the reference copies the TG options into every tg_data_t,
-        // src/tg.cpp:411-414, and tg_cycle_atb calls them, :113,131): anything but smpr_sym_poly is routed through the
-        // C ABI's smoother plug, with the level's operator (the finer level's Ac below the finest)
-        size_t k = 0;
-        for (tg_data_t *t = tg_data; t; t = t->coarser_tg, ++k) {
-            plugs[k].A = (k == 0) ? A : plugs[k - 1].tg->Ac;
-            if (t->pre_smoother == installed[k].first && t->post_smoother == installed[k].second) continue;
-            installed[k] = std::make_pair(t->pre_smoother, t->post_smoother);
-            if (saamge_amd_set_smoother(tg_data->h, t->level,
-                                        t->pre_smoother != smpr_sym_poly ? detail::pre_smoother_trampoline : nullptr,
-                                        t->post_smoother != smpr_sym_poly ? detail::post_smoother_trampoline : nullptr,
-                                        (void *)&plugs[k]))
-                mfem::mfem_error(saamge_amd_last_error());
-        }
+        PlugScope plugs(*this);
         if (tg_data->dist) {
             // distributed: b and x are the rank's true-dof blocks (HypreParVector data); the library's vectors are global
             const detail::DistLayout &d = *tg_data->dist;
@@ -863,6 +881,7 @@ public:
     // the PCG loop of kalchev_pcg on the GPU with this cycle as the preconditioner
     int pcg(const double *b, double *x, int print_iter, int max_num_iter, double RTOLERANCE, double ATOLERANCE,
             bool zero_rhs) const {
+        PlugScope plugs(*this);      // (kalchev_pcg without a Mult before it must see the caller's plugs as well)
         try {
             if (tg_data->dist) {
                 const detail::DistLayout &d = *tg_data->dist;
@@ -881,11 +900,42 @@ public:
         return 0;
     }
 private:
+    // Brings the C ABI's plugs in line with tg_data before anything that cycles (Mult and pcg alike), and takes this solver's
+    // operator out of the finest level's context afterwards: the matrix is the caller's and may not outlive the call.
+    struct PlugScope {
+        const VCycleSolver &s;
+        explicit PlugScope(const VCycleSolver &s_) : s(s_) { s.establish_plugs(); }
+        ~PlugScope() { if (s.tg_data->smoother_plug) s.tg_data->smoother_plug->A = NULL; }
+    };
+    void establish_plugs() const {
+        // a coarse_solver assigned by the caller takes over the coarsest solve (tg_data_t::coarse_solver plug)
+        // (tg_data->plugged is what the library holds, whichever solver object installed it: see "Plug state" at the top)
+        if (tg_data->coarse_solver != tg_data->plugged) {
+            if (saamge_amd_set_coarse_solver(tg_data->h, tg_data->coarse_solver ? detail::coarse_solver_trampoline : nullptr,
+                                             (void *)&tg_data->coarse_solver))
+                mfem::mfem_error(saamge_amd_last_error());
+            tg_data->plugged = tg_data->coarse_solver;
+        }
+        // pre_smoother / post_smoother assigned by the caller (the reference copies the TG options into every tg_data_t,
+        // src/tg.cpp:411-414, and tg_cycle_atb calls them, :113,131): anything but smpr_sym_poly is routed through the
+        // C ABI's smoother plug, with the level's operator (the finer level's Ac below the finest).  The context lives in the
+        // level's tg_data; the finest level's operator is this solver's (SetOperator), set for the length of the call.
+        for (tg_data_t *t = tg_data, *finer = NULL; t; finer = t, t = t->coarser_tg) {
+            if (!t->smoother_plug) t->smoother_plug = new detail::SmootherPlug;
+            t->smoother_plug->tg = t;
+            t->smoother_plug->A = finer ? finer->Ac : A;
+            if (t->pre_smoother == t->installed_pre && t->post_smoother == t->installed_post) continue;
+            if (saamge_amd_set_smoother(tg_data->h, t->level,
+                                        t->pre_smoother != smpr_sym_poly ? detail::pre_smoother_trampoline : nullptr,
+                                        t->post_smoother != smpr_sym_poly ? detail::post_smoother_trampoline : nullptr,
+                                        (void *)t->smoother_plug))
+                mfem::mfem_error(saamge_amd_last_error());
+            t->installed_pre = t->pre_smoother;
+            t->installed_post = t->post_smoother;
+        }
+    }
     tg_data_t *tg_data;
     mfem::HypreParMatrix *A;
-    mutable mfem::Solver *plugged;
-    mutable std::vector<detail::SmootherPlug> plugs;                   // one per level (their addresses are the plug's ctx)
-    mutable std::vector<std::pair<smpr_ft, smpr_ft> > installed;       // what the C ABI currently holds per level
 };
 
 // == SpectralAMGSolver (inc/solve.hpp:149-177, src/solve.cpp:167-230).  The reference derives the partition
