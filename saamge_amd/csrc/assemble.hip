@@ -474,20 +474,25 @@ __global__ __launch_bounds__(256) void ae_rows8_kernel(
 // slot in each (round 4).  An assembled entry (row g, column c) used to walk g's element list in global memory -- per
 // element its partition and its dofs -- for every one of the row's ~27 entries; now the lists are made once per dof, and
 // an entry matches the row's list against the column's in LDS: one global load (the element-matrix entry) per common
-// element, the same products in the same order.  An agglomerate with a dof in more than MW elements takes walk_entry.
+// element, the same products in the same order.
+// Only the dofs SHARED between agglomerates (bit 0 of the flag) get a list: entry_assembled wants that bit on the row and on
+// the column, so the list of any other dof was never read (147 of the 405 rows of an interior 9 x 9 x 5 agglomerate).  The first
+// loop collects the shared rows in lsh, the second makes MW items per shared row.  An agglomerate with a SHARED dof in more than
+// MW elements takes walk_entry; an unshared dof in more than MW elements no longer sends its agglomerate there, which changes no
+// bit: it has no assembled entry, and walk_entry adds the same terms in the same order anyway.
 // HEX8: 8-dof elements, lists of 8, the 8 x 8 match unrolled.  Otherwise elements of at most 8 dofs and of different sizes
 // (level 0 of a mesh of hexes and prisms, tetrahedra or pyramids): lists of AR_MW (a vertex of a hex / prism mesh lies in up
 // to 12 elements), the slots in use and each element's size kept beside them (lne, dnd).
 constexpr int AR_MW = 16;
 constexpr size_t AR_LDS_MAX = 64 * 1024;      // what the kernel may ask for without an attribute
 // The LDS of ae_rows_lds_kernel: the one place that knows its layout.  The host asks size() what to launch with for the
-// largest agglomerate of the batch (the table size hsize: a power of two >= 2 n; 24 bytes cover the alignment of del);
+// largest agglomerate of the batch (the table size hsize: a power of two >= 2 n; 24 bytes cover nsh and the alignment before it);
 // the kernel carves its dynamic LDS for its own agglomerate's n rows with the hsize it was launched with.
 template <bool HEX8>
 struct RowsLds {
     static constexpr int MW = HEX8 ? 8 : AR_MW;
-    // per row: la0, lg, llen (, lne), lflag; del, dkk (, dnd)
-    static constexpr size_t ROW_BYTES = sizeof(roff_t) + (HEX8 ? 2 : 3) * sizeof(int) + 1 + (size_t)MW * (sizeof(int) + (HEX8 ? 1 : 2));
+    // per row: la0, lg, llen (, lne), lsh, lflag; del, dkk (, dnd)
+    static constexpr size_t ROW_BYTES = sizeof(roff_t) + (HEX8 ? 2 : 3) * sizeof(int) + sizeof(short) + 1 + (size_t)MW * (sizeof(int) + (HEX8 ? 1 : 2));
     static size_t size(int max_n, int &hsize) {
         for (hsize = 64; hsize < 2 * max_n; hsize <<= 1) {}
         return (size_t)max_n * ROW_BYTES + (size_t)hsize * (sizeof(int) + sizeof(short)) + 24;
@@ -497,7 +502,10 @@ struct RowsLds {
     int *llen;              // [n] entries of the row
     int *lne;               // [n] slots of the dof's element list in use (<= MW; not HEX8)
     AiTable loc;            // [hsize] dof -> local index
+    short *lsh;             // [*nsh <= n] the rows of the dofs shared between agglomerates (bit 0 of the flag), in any order
     signed char *lflag;     // [n]
+    int *nsh;               // their number
+    // the lists of the shared rows, each at its row's place (the host knows no bound on *nsh below n without reading it back)
     int *del;               // [n][MW] element or -1
     unsigned char *dkk;     // [n][MW] slot of the dof in it
     unsigned char *dnd;     // [n][MW] its number of dofs (not HEX8)
@@ -511,8 +519,10 @@ struct RowsLds {
         loc.key = (int *)take(sizeof(int) * (size_t)hsize);
         loc.val = (short *)take(sizeof(short) * (size_t)hsize);
         loc.mask = (unsigned)(hsize - 1);
+        lsh = (short *)take(sizeof(short) * (size_t)n);
         lflag = (signed char *)take((size_t)n);
         o = (o + 3) & ~(size_t)3;
+        nsh = (int *)take(sizeof(int));
         del = (int *)take(sizeof(int) * (size_t)MW * n);
         dkk = take((size_t)MW * n);
         dnd = take(HEX8 ? 0 : (size_t)MW * n);
@@ -532,45 +542,99 @@ __global__ __launch_bounds__(256) void ae_rows_lds_kernel(
     const RowsLds<HEX8> L(ar_lds, n, hsize);
     const int tid = threadIdx.x;
     L.loc.clear(tid, 256);
+    if (tid == 0) *L.nsh = 0;
     __syncthreads();
     const int *dofs = ae2d_J + ae2d_I[p];
-    bool many = false;      // (a dof with more than MW elements: the agglomerate takes the walk through global memory)
+    bool many = false;      // (a shared dof with more than MW elements: the agglomerate takes the walk through global memory)
     for (int i = tid; i < n; i += 256) {
         const int g = dofs[i];
         const roff_t a0 = Arow[g];
+        const int fl = flags[g];
         L.lg[i] = g;
         L.la0[i] = a0;
         L.llen[i] = (int)(Arow[g + 1] - a0);
-        L.lflag[i] = flags[g];
+        L.lflag[i] = (signed char)fl;
         L.loc.insert(g, i);
-        if (!HEX8) {      // (here and not in the loop below: a store by one slot in MW cost the kernel 5 %)
-            const int cnt = d2e_I[g + 1] - d2e_I[g];
-            many = many || cnt > MW;
-            L.lne[i] = min(cnt, MW);
-        }
-    }
-    for (int it = tid; it < n * MW; it += 256) {
-        const int i = it / MW, q = it % MW;
-        const int g = dofs[i];
-        const int qb = d2e_I[g], cnt = d2e_I[g + 1] - qb;
-        if (HEX8) many = many || cnt > MW;
-        int e = -1, kk = 0, nd = 0;
-        if (q < cnt) {
-            e = d2e_J[qb + q];
-            if (part[e] != p) {
-                e = -1;
-            } else if (HEX8) {
-                const int4 lo = *(const int4 *)(e2d_J + (size_t)e * 8), hi = *(const int4 *)(e2d_J + (size_t)e * 8 + 4);
-                kk = slot8(lo, hi, g);
-            } else {
-                const int eb = e2d_I[e];
-                nd = e2d_I[e + 1] - eb;
-                kk = elem_slot(e2d_J + eb, nd, g);
+        if (fl & 1) {
+            L.lsh[atomicAdd(L.nsh, 1)] = (short)i;
+            if (!HEX8) {      // (here and not in the loop below: a store by one slot in MW cost the kernel 5 %)
+                const int cnt = d2e_I[g + 1] - d2e_I[g];
+                many = many || cnt > MW;
+                L.lne[i] = min(cnt, MW);
             }
         }
-        L.del[it] = e;
-        L.dkk[it] = (unsigned char)kk;
-        if (!HEX8) L.dnd[it] = (unsigned char)nd;
+    }
+    __syncthreads();
+    // MW items per shared row, UL of them per thread and trip.  An item is a chain of dependent loads (the row's dof from LDS, its
+    // element range, the element, its agglomerate, its dofs): each level is requested for all UL items before the next is looked
+    // at, from addresses that are valid for every item (an item past the end, past its dof's list or outside the agglomerate
+    // reads what item 0 / position 0 reads) and masked at use -- loads under their conditions each waited on their own.
+    const int nit = *L.nsh * MW;
+    constexpr int UL = 4;
+    for (int it0 = tid; it0 < nit; it0 += 256 * UL) {
+        int at[UL], gs[UL], qs[UL], es[UL], kks[UL], nds[UL];
+        bool in[UL];
+#pragma unroll
+        for (int u = 0; u < UL; ++u) {
+            const int it = it0 + 256 * u;
+            in[u] = it < nit;
+            const int i = L.lsh[in[u] ? it / MW : 0];
+            qs[u] = it % MW;
+            at[u] = i * MW + qs[u];
+            gs[u] = L.lg[i];
+        }
+#pragma unroll
+        for (int u = 0; u < UL; ++u) {
+            const int qb = d2e_I[gs[u]], cnt = d2e_I[gs[u] + 1] - qb;
+            if (HEX8) many = many || (in[u] && cnt > MW);
+            in[u] = in[u] & (qs[u] < cnt);      // (not &&: behind it the second offset is loaded under a branch, with a wait of its own)
+            qs[u] += qb;
+        }
+#pragma unroll
+        for (int u = 0; u < UL; ++u) es[u] = d2e_J[in[u] ? qs[u] : 0];
+#pragma unroll
+        for (int u = 0; u < UL; ++u) in[u] = (part[es[u]] == p) & in[u];
+        if constexpr (HEX8) {
+            int4 lo[UL], hi[UL];
+#pragma unroll
+            for (int u = 0; u < UL; ++u) {
+                lo[u] = *(const int4 *)(e2d_J + (size_t)es[u] * 8);
+                hi[u] = *(const int4 *)(e2d_J + (size_t)es[u] * 8 + 4);
+            }
+#pragma unroll
+            for (int u = 0; u < UL; ++u) {      // slot8 without its early exits: behind those the compiler loads the dofs one by one
+                const int g = gs[u];
+                const unsigned m = (unsigned)(lo[u].x == g) | (unsigned)(lo[u].y == g) << 1 | (unsigned)(lo[u].z == g) << 2 |
+                                   (unsigned)(lo[u].w == g) << 3 | (unsigned)(hi[u].x == g) << 4 | (unsigned)(hi[u].y == g) << 5 |
+                                   (unsigned)(hi[u].z == g) << 6 | (unsigned)(hi[u].w == g) << 7;
+                kks[u] = __ffs(m) - 1;
+                nds[u] = 0;
+            }
+        } else {
+            int ebs[UL];
+#pragma unroll
+            for (int u = 0; u < UL; ++u) {
+                ebs[u] = e2d_I[es[u]];
+                nds[u] = e2d_I[es[u] + 1] - ebs[u];
+            }
+#pragma unroll
+            for (int u = 0; u < UL; ++u) {      // (at most 8 dofs per element: rows_eligible)
+                int dd[8];
+#pragma unroll
+                for (int t = 0; t < 8; ++t) dd[t] = (in[u] && t < nds[u]) ? e2d_J[ebs[u] + t] : -1;
+                kks[u] = -1;
+#pragma unroll
+                for (int t = 7; t >= 0; --t)
+                    if (dd[t] == gs[u]) kks[u] = t;      // (the first match: elem_slot)
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < UL; ++u) {
+            if (it0 + 256 * u >= nit) continue;
+            L.del[at[u]] = in[u] ? es[u] : -1;
+            L.dkk[at[u]] = (unsigned char)(in[u] ? kks[u] : 0);
+            if (!HEX8) L.dnd[at[u]] = (unsigned char)(in[u] ? nds[u] : 0);
+        }
     }
     const bool walk = __syncthreads_or(many ? 1 : 0) != 0;
     const size_t obase = (size_t)voff[b] * RW;
@@ -608,16 +672,32 @@ __global__ __launch_bounds__(256) void ae_rows_lds_kernel(
                 } else if (!walk) {     // the elements of g inside the agglomerate that also hold c, ascending in g's list (walk_entry's order)
                     const int *er = L.del + lr * MW, *ec = L.del + lc * MW;
                     if constexpr (HEX8) {       // the 8 x 8 match, unrolled
+                        // the matches first (LDS only), then the element-matrix entries of all of them requested together, then
+                        // the sum in the order of the list: with load and add inside one loop each entry waited for the one before
+                        double m[MW];
+                        unsigned has = 0;
+                        int ecs[MW], jc[MW];
+#pragma unroll
+                        for (int q2 = 0; q2 < MW; ++q2) {
+                            ecs[q2] = ec[q2];
+                            jc[q2] = L.dkk[lc * MW + q2];
+                        }
 #pragma unroll
                         for (int q = 0; q < MW; ++q) {
                             const int e = er[q];
-                            if (e < 0) continue;
                             int jj = -1;
 #pragma unroll
                             for (int q2 = 0; q2 < MW; ++q2)
-                                if (ec[q2] == e) jj = L.dkk[lc * MW + q2];
-                            if (jj >= 0) v += elval[((size_t)e * 8 + L.dkk[lr * MW + q]) * 8 + jj];
+                                if (ecs[q2] == e) jj = jc[q2];
+                            m[q] = 0.0;
+                            if (e >= 0 && jj >= 0) {
+                                has |= 1u << q;
+                                m[q] = elval[((size_t)e * 8 + L.dkk[lr * MW + q]) * 8 + jj];
+                            }
                         }
+#pragma unroll
+                        for (int q = 0; q < MW; ++q)
+                            if (has >> q & 1) v += m[q];
                     } else {                    // counted loops over the slots in use
                         const int nr = L.lne[lr], nc = L.lne[lc];
                         for (int q = 0; q < nr; ++q) {
